@@ -12,14 +12,20 @@ barrier and the MAX / SUM of the timing.  Two partitions of the work are measure
           sharding.balanced_assignment (longest compressed stream first).  With several GPUs THIS is the line's `value`
           ("scaling": "strong"; the weak leg is reported beside it as "weak_scaling").  `--scaling weak|strong|both` override.
 
-Beside the line's value: `end_to_end` (host .drc bytes -> host arrays: pinned staging, one upload and one download per batch,
-two batches in flight), `pool` (the in-library work queue over all GPUs of the job, from rank 0), `encode` (configs[4]),
-`cpu_baseline` (the oracle on the host cores), `oracle_check` (decoded meshes against the oracle, after the timed region).
+A plain run times only the line's value: it generates the batch, warms up, times --steps decodes and prints the line.  With
+--full it also measures, beside the value: `end_to_end` (host .drc bytes -> host arrays: pinned staging, one upload and one
+download per batch, two batches in flight), `pool` (the in-library work queue over all GPUs of the job, from rank 0), `encode`
+(configs[4]), `sustained`, `dialects`, `shader_clock_ghz`, `cpu_baseline` (the oracle on the host cores), `oracle_check`
+(decoded meshes against the oracle, after the timed region).
+
+--dump-outputs DIR writes what the last timed step decoded for a fixed sample of the line's batch (faces, attribute values,
+portable values and point maps, as float32 / float64 .npy), so that two builds can be compared output for output.
 
 The timed region of each leg is bracketed by a barrier + synchronize, the MAX over ranks is reported.  Rank 0 prints
 one JSON line.
 
     python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus N --steps K --warmup W
 """
@@ -326,6 +332,39 @@ def oracle_check(batch, blob, offsets, indices):
     return bad
 
 
+DUMP_MESHES = 8
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(batch, out_dir):
+    """What the last decode of `batch` gave a caller (Batch.result: faces, and per attribute its values, portable values and
+    point map) for a fixed sample of meshes (seeded, so every run with the same arguments picks the same ones), as
+    DIR/mesh<i>_*.npy: floats as they are, integers as float64 (exact).  Meshes are added in sample order while the files
+    stay within DUMP_BUDGET_BYTES."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    idx = np.sort(np.random.default_rng(0).choice(batch.n, size=min(DUMP_MESHES, batch.n), replace=False))
+    written, total = [], 0
+    for i in idx:
+        m = batch.result(int(i)).ConnectedData
+        arrays = {"faces": m.Faces}
+        for a, att in enumerate(m.Attributes):
+            arrays["att%d_values" % a] = att.Values
+            arrays["att%d_point_map" % a] = att.PointMap
+            if att.PortableValues is not None:
+                arrays["att%d_portable" % a] = att.PortableValues
+        arrays = {k: v if v.dtype in (np.float32, np.float64) else v.astype(np.float64) for k, v in arrays.items()}
+        size = sum(v.nbytes for v in arrays.values())
+        if total + size > DUMP_BUDGET_BYTES:
+            break
+        for k, v in arrays.items():
+            np.save(os.path.join(out_dir, "mesh%05d_%s.npy" % (i, k)), v)
+        written.append(int(i))
+        total += size
+    np.save(os.path.join(out_dir, "sample_meshes.npy"), np.array(written, np.float64))
+    return {"dir": out_dir, "meshes": written, "bytes": total}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -346,7 +385,13 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-encode", action="store_true")
     ap.add_argument("--check", type=int, default=64, help="meshes of the rank-0 batch compared with the oracle after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the line's value (oracle check, sustained, encode, end_to_end, dialects, pool, "
+                         "cpu_baseline, shader clock); the --no-* / --check / --e2e-batches / --encode-meshes options apply to these")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's results for a fixed sample of meshes as DIR/*.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     libs = [os.path.join(ROOT, *f) for f in (("draco-sharp_amd", "csrc", "libdraco_mi355x.so"), ("draco-sharp_amd", "synth", "libdsa_synth.so"),
                                              ("oracle", "liboracle.so"))]
@@ -421,6 +466,9 @@ def main():
 
     do_weak = args.scaling in ("weak", "both", "auto")
     do_strong = args.scaling == "strong" or (args.scaling in ("both", "auto") and world > 1)
+    # the leg whose batch is the line's value (see the end of main): its results are the ones --dump-outputs writes
+    line_leg = "strong" if (not do_weak or (world > 1 and args.scaling == "auto")) else "weak"
+    dumped = None
     out, strong = None, None
     t_gen = t_upload = 0.0
     weak_blob = weak_offsets = None
@@ -435,6 +483,8 @@ def main():
         batch = dsa.Batch(ctx, blob=blob, offsets=offsets)
         t_upload = time.perf_counter() - t0
         elapsed, stages = timed_leg(batch)
+        if args.dump_outputs and rank == 0 and line_leg == "weak":
+            dumped = dump_outputs(batch, args.dump_outputs)
         alg_bytes = batch.algorithmic_bytes
         alg_bytes_all = comm.sum(alg_bytes)
         weak_blob, weak_offsets = blob, offsets
@@ -484,12 +534,12 @@ def main():
             }
             # shader clock under this load, in-kernel: s_memtime ticks / s_memrealtime ticks (100 MHz) of the traversal and the
             # connectivity wave of 32 meshes of the batch, median (MI355X_MICROARCH.md, "DVFS give-back", item 6)
-            dbg = [batch.debug_array(i, 4, np.uint32, 20) for i in range(0, args.meshes, max(1, args.meshes // 32))]
+            dbg = [batch.debug_array(i, 4, np.uint32, 20) for i in range(0, args.meshes, max(1, args.meshes // 32))] if args.full else []
             for name, a, b in (("traverse", 6, 17), ("connectivity", 13, 15)):
                 q = sorted(float(d[a]) / float(d[b]) * 0.1 for d in dbg if len(d) > b and d[b])
                 if q:
                     out.setdefault("shader_clock_ghz", {})[name] = round(q[len(q) // 2], 3)
-            if args.check > 0:
+            if args.full and args.check > 0:
                 idx = sorted(set(int(i) for i in np.linspace(0, args.meshes - 1, min(args.check, args.meshes))))
                 bad = oracle_check(batch, blob, offsets, idx)
                 if bad:
@@ -510,6 +560,8 @@ def main():
         streams = [bytes(blob[int(offsets[i]):int(offsets[i + 1])]) for i in mine]
         batch = dsa.Batch(ctx, streams)
         elapsed, stages = timed_leg(batch)
+        if args.dump_outputs and rank == 0 and line_leg == "strong":
+            dumped = dump_outputs(batch, args.dump_outputs)
         alg_bytes_all = comm.sum(batch.algorithmic_bytes)
         shard_sizes = [int(comm.sum(len(mine) if r == rank else 0)) for r in range(world)]
         if rank == 0:
@@ -518,24 +570,25 @@ def main():
                       "meshes_per_gpu": shard_sizes, "assignment": "sharding.balanced_assignment (longest compressed stream first)",
                       "gb_per_s": alg_bytes_all / step_s / 1e9, "stage_ms_rank0": stages, "generate_s": t_gen_s}
         batch.close()
+    # ---- --full: the legs beside the line's value
     sustained = None
-    if not args.no_sustained and weak_blob is not None:
+    if args.full and not args.no_sustained and weak_blob is not None:
         sustained = sustained_leg(dsa, ctx, weak_blob, weak_offsets, max(4, args.steps), args.warmup, comm if world > 1 else None, barrier, world)
     encode = None
-    if not args.no_encode:                                           # every rank: the leg's clock is the slowest rank's
+    if args.full and not args.no_encode:                             # every rank: the leg's clock is the slowest rank's
         encode = encode_leg(dsa, synth, ctx, nx, ny, args.encode_meshes, comm if world > 1 else None, barrier if world > 1 else None, world)
     e2e = None
-    if not args.no_end_to_end and weak_blob is not None:             # every rank its own batches: the clock is the slowest rank's
+    if args.full and not args.no_end_to_end and weak_blob is not None:   # every rank its own batches: the clock is the slowest rank's
         e2e = end_to_end_leg(dsa, ctx, weak_blob, weak_offsets, args.e2e_batches, 2, comm if world > 1 else None, barrier if world > 1 else None, world, compact=True)
         e2e["full_layout"] = end_to_end_leg(dsa, ctx, weak_blob, weak_offsets, args.e2e_batches, 2, comm if world > 1 else None, barrier if world > 1 else None, world, compact=False)
     # (behind the end-to-end leg: the seamed batches of this leg have arenas of 120 GB at this batch size, and for seconds after such
     # an arena is freed the downloads of the end-to-end pipeline run at half the link rate -- 17 - 23 k meshes/s instead of 31 k;
     # profiles/README.md)
     dialects = None
-    if not args.no_dialects and world == 1 and weak_blob is not None:
+    if args.full and not args.no_dialects and world == 1 and weak_blob is not None:
         dialects = dialects_leg(dsa, synth, ctx, nx, ny, args.meshes, 3)
     pool = None
-    if not args.no_pool:
+    if args.full and not args.no_pool:
         # the in-library work queue over all GPUs of the job, from rank 0 alone (the other ranks have released their contexts'
         # caches and wait at the barrier): BASELINE.json configs[3] as a single-process host (the C# one) runs it
         ctx.close()
@@ -587,7 +640,9 @@ def main():
             out["pool"] = pool
         out["notes"] = ("value / gb_per_s: compressed bytes resident in HBM -> results in HBM (no PCIe in the timed region); end_to_end: host bytes -> host "
                         "arrays; cpu_baseline: the oracle incl. its numpy export on the host")
-        if not args.no_cpu_baseline and weak_blob is not None:       # rank 0, on the node's host cores, after every GPU leg
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
+        if args.full and not args.no_cpu_baseline and weak_blob is not None:   # rank 0, on the node's host cores, after every GPU leg
             out["cpu_baseline"] = cpu_baseline(weak_blob, weak_offsets, 1, 10.0, 1024)
             out["cpu_baseline_all_cores"] = cpu_baseline(weak_blob, weak_offsets, min(host_cores, 32), 10.0, 4096)
         print(json.dumps(out))

@@ -7,7 +7,7 @@ for spec in "$@"; do
   IFS=: read -r tag lib e1 e2 e3 <<< "$spec"
   if [ "$lib" = default ]; then unset DSA_LIB; else export DSA_LIB=$R/$lib; fi
   for kv in $e1 $e2 $e3; do export $kv; done
-  python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-encode --no-end-to-end --no-pool --check 8 > $O/oab_$tag.json 2> $O/oab_$tag.err || { tail -5 $O/oab_$tag.err; exit 1; }
+  python $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-encode --no-end-to-end --no-pool --check 8 > $O/oab_$tag.json 2> $O/oab_$tag.err || { tail -5 $O/oab_$tag.err; exit 1; }
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/oab_${tag}_trace -- python $R/bench.py $ARGS > $O/oab_${tag}_trace.log 2>&1
   python $R/tools/trace_summary.py $O/oab_${tag}_trace > $O/oab_${tag}_timeline.txt
   rm -rf $O/oab_${tag}_trace

@@ -1,6 +1,6 @@
 #!/bin/bash
 R=$PWD; O=$R/gpurun_out; mkdir -p $O
-A="--steps 6 --warmup 2 --no-cpu-baseline --no-encode --no-end-to-end --no-pool --check 4 --scaling weak"
+A="--full --steps 6 --warmup 2 --no-cpu-baseline --no-encode --no-end-to-end --no-pool --check 4 --scaling weak"
 for n in 4096 2048; do
   for lib in default build_abl/lib_oct3.so build_abl/lib_oct0.so off; do
     if [ "$lib" = default ]; then unset DSA_LIB; unset DSA_OCT_STREAMS; elif [ "$lib" = off ]; then unset DSA_LIB; export DSA_OCT_STREAMS=0; else export DSA_LIB=$R/$lib; unset DSA_OCT_STREAMS; fi

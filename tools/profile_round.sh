@@ -9,7 +9,7 @@ O=$R/gpurun_out
 mkdir -p $O
 ARGS="--steps 3 --warmup 1 --no-cpu-baseline --no-encode --no-end-to-end --no-pool --no-sustained --no-dialects --check 0 --scaling weak"
 cd /tmp && export TMPDIR=/tmp
-python $R/bench.py > $O/${tag}_bench.json 2> $O/${tag}_bench.err
+python $R/bench.py --full > $O/${tag}_bench.json 2> $O/${tag}_bench.err
 echo "bench done"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${tag}_trace -- python $R/bench.py $ARGS > $O/${tag}_trace.log 2>&1
 echo "trace done"
