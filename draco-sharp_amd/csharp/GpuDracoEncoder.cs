@@ -1,5 +1,8 @@
-// GPU-backed twin of Draco.IO.DracoEncoder (src/Draco/IO/DracoEncoder.cs:8-41) for triangle meshes with per-vertex
-// positions / normals / texture coordinates.  Not compiled in the build image (no .NET SDK); the executable twin
+// GPU-backed twin of Draco.IO.DracoEncoder (src/Draco/IO/DracoEncoder.cs:8-41) for triangle meshes with positions, normals and
+// texture coordinates.  Like the reference (CornerTable.cs:571-596 CreateFromAttribute), a mesh whose points do not map one to one
+// onto position values, or whose normal / texture coordinate mapping differs from the position mapping, is coded in corner form:
+// vertices are position values, normals / texture coordinates keep their own values with an id per corner, and the edges where
+// those ids change become attribute seams (dsa_encode_batch_corners).  Not compiled in the build image (no .NET SDK); the executable twin
 // is draco-sharp_amd/encoder.py.  Config options honoured: quantisation bits per attribute type and Speed
 // (src/Draco/IO/Config.cs); everything else keeps the reference's defaults (standard Edgebreaker, DFS traversal).
 using System;
@@ -40,6 +43,16 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
         IntPtr encoded = IntPtr.Zero;
         try
         {
+            bool anyCorners = false;
+            foreach (var m in meshes) anyCorners = anyCorners || NeedsCornerForm(m);
+            if (anyCorners)
+            {
+                var cin = new DsaMeshCornerInput[meshes.Count];
+                for (int i = 0; i < meshes.Count; ++i) CornerForm(meshes[i], ref cin[i], pins);
+                fixed (DsaMeshCornerInput* p = cin)
+                    NativeMethods.Check(NativeMethods.dsa_encode_batch_corners(_ctx, (uint)meshes.Count, p, in opt, out encoded), _ctx, "dsa_encode_batch_corners");
+                return Streams(encoded, meshes.Count);
+            }
             for (int i = 0; i < meshes.Count; ++i)
             {
                 var m = meshes[i];
@@ -57,19 +70,108 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
             }
             fixed (DsaMeshInput* p = inputs)
                 NativeMethods.Check(NativeMethods.dsa_encode_batch(_ctx, (uint)meshes.Count, p, in opt, out encoded), _ctx, "dsa_encode_batch");
-            var result = new byte[meshes.Count][];
-            for (uint i = 0; i < meshes.Count; ++i)
-            {
-                NativeMethods.Check(NativeMethods.dsa_encoded_stream(encoded, i, out var bytes, out var length), _ctx, $"mesh {i}");
-                result[i] = new ReadOnlySpan<byte>(bytes, (int)length).ToArray();
-            }
-            return result;
+            return Streams(encoded, meshes.Count);
         }
         finally
         {
             if (encoded != IntPtr.Zero) NativeMethods.dsa_encoded_free(encoded);
             foreach (var h in pins) if (h.IsAllocated) h.Free();
         }
+    }
+
+    private byte[][] Streams(IntPtr encoded, int count)
+    {
+        var result = new byte[count][];
+        for (uint i = 0; i < count; ++i)
+        {
+            NativeMethods.Check(NativeMethods.dsa_encoded_stream(encoded, i, out var bytes, out var length), _ctx, $"mesh {i}");
+            result[i] = new ReadOnlySpan<byte>(bytes, (int)length).ToArray();
+        }
+        return result;
+    }
+
+    // corner form when the points do not map one to one onto position values, or a normal / texture coordinate mapping differs
+    // from the position mapping
+    private static bool NeedsCornerForm(Mesh.Mesh m)
+    {
+        var pa = m.GetNamedAttribute(GeometryAttributeType.Position);
+        if (pa == null) return false;
+        var seen = new bool[Math.Max(pa.UniqueEntriesCount, (uint)m.PointsCount)];
+        for (uint p = 0; p < m.PointsCount; ++p)
+        {
+            uint v = pa.MappedIndex(p);
+            if (v >= seen.Length || seen[v]) return true;
+            seen[v] = true;
+        }
+        return SeparateIds(m, pa, GeometryAttributeType.Normal) || SeparateIds(m, pa, GeometryAttributeType.TexCoord);
+    }
+
+    private static bool SeparateIds(Mesh.Mesh m, PointAttribute pa, GeometryAttributeType type)
+    {
+        var a = m.GetNamedAttribute(type);
+        if (a == null) return false;
+        for (uint p = 0; p < m.PointsCount; ++p) if (a.MappedIndex(p) != pa.MappedIndex(p)) return true;
+        return false;
+    }
+
+    // Vertices = position values, faces = the position value of every corner; a normal / texture coordinate attribute whose mapping
+    // differs from the positions' keeps its own values with an id per corner, otherwise it is per vertex.  The generic attribute is
+    // per vertex (the value of the last point of each position value).
+    private static void CornerForm(Mesh.Mesh m, ref DsaMeshCornerInput c, List<GCHandle> pins)
+    {
+        var pa = m.GetNamedAttribute(GeometryAttributeType.Position)!;
+        uint nv = 0;
+        for (uint p = 0; p < m.PointsCount; ++p) nv = Math.Max(nv, pa.MappedIndex(p) + 1);
+        var faces = new uint[m.FacesCount * 3];
+        var pointOf = new uint[m.FacesCount * 3];
+        for (int f = 0; f < m.FacesCount; ++f)
+        {
+            var face = m.GetFace((uint)f);
+            for (int k = 0; k < 3; ++k) { pointOf[3 * f + k] = (uint)face[k]; faces[3 * f + k] = pa.MappedIndex((uint)face[k]); }
+        }
+        c.Mesh.NumVertices = nv;
+        c.Mesh.NumFaces = (uint)m.FacesCount;
+        c.Mesh.Faces = (uint*)Pin(faces, pins);
+        c.Mesh.Positions = (float*)Pin(Values(pa, nv, 3), pins);
+        c.Mesh.Normals = (float*)Pin(PerCornerOrVertex(m, pa, GeometryAttributeType.Normal, 3, nv, pointOf, out var nid, out c.NumNormals), pins);
+        c.NormalCorners = (uint*)Pin(nid, pins);
+        c.Mesh.Texcoords = (float*)Pin(PerCornerOrVertex(m, pa, GeometryAttributeType.TexCoord, 2, nv, pointOf, out var tid, out c.NumTexcoords), pins);
+        c.TexcoordCorners = (uint*)Pin(tid, pins);
+        var generic = Bytes(m, GeometryAttributeType.Generic, out uint gc);
+        if (generic != null)
+        {
+            var g = new byte[nv * gc];
+            for (uint p = 0; p < m.PointsCount; ++p) Array.Copy(generic, p * gc, g, pa.MappedIndex(p) * gc, gc);
+            c.Mesh.Generic = (byte*)Pin(g, pins);
+            c.Mesh.GenericComponents = gc;
+        }
+    }
+
+    private static float[]? PerCornerOrVertex(Mesh.Mesh m, PointAttribute pa, GeometryAttributeType type, int nc, uint nv, uint[] pointOf, out uint[]? ids, out uint rows)
+    {
+        ids = null;
+        rows = 0;
+        var a = m.GetNamedAttribute(type);
+        if (a == null) return null;
+        if (!SeparateIds(m, pa, type))
+        {
+            var v = new float[nv * nc];
+            for (uint p = 0; p < m.PointsCount; ++p)
+                for (int c = 0; c < nc; ++c) v[pa.MappedIndex(p) * nc + c] = a.Buffer!.Read<float>((int)(a.ByteOffset + a.MappedIndex(p) * a.ByteStride + 4 * c));
+            return v;
+        }
+        ids = new uint[pointOf.Length];
+        for (int k = 0; k < pointOf.Length; ++k) { ids[k] = a.MappedIndex(pointOf[k]); rows = Math.Max(rows, ids[k] + 1); }
+        return Values(a, rows, nc);
+    }
+
+    // the first `count` values of a float attribute, by value index
+    private static float[] Values(PointAttribute a, uint count, int nc)
+    {
+        var v = new float[count * nc];
+        for (uint i = 0; i < count; ++i)
+            for (int c = 0; c < nc; ++c) v[i * nc + c] = a.Buffer!.Read<float>((int)(a.ByteOffset + i * a.ByteStride + 4 * c));
+        return v;
     }
 
     // values of a per-vertex float attribute in point order (null when the mesh has no such attribute)
@@ -79,7 +181,7 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
         if (a == null) return null;
         var v = new float[m.PointsCount * nc];
         for (uint p = 0; p < m.PointsCount; ++p)
-            for (int c = 0; c < nc; ++c) v[p * nc + c] = a.Buffer!.Read<float>((int)(a.MappedIndex(p) * a.ByteStride + 4 * c));
+            for (int c = 0; c < nc; ++c) v[p * nc + c] = a.Buffer!.Read<float>((int)(a.ByteOffset + a.MappedIndex(p) * a.ByteStride + 4 * c));
         return v;
     }
 
@@ -92,7 +194,7 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
         nc = (uint)a.NumComponents;
         var v = new byte[m.PointsCount * nc];
         for (uint p = 0; p < m.PointsCount; ++p)
-            for (int c = 0; c < nc; ++c) v[p * nc + c] = a.Buffer!.Read<byte>((int)(a.MappedIndex(p) * a.ByteStride + c));
+            for (int c = 0; c < nc; ++c) v[p * nc + c] = a.Buffer!.Read<byte>((int)(a.ByteOffset + a.MappedIndex(p) * a.ByteStride + c));
         return v;
     }
 

@@ -82,6 +82,16 @@ internal unsafe struct DsaMeshInput
     public uint Reserved;
 }
 
+// dsa_mesh_corner_input (dsa_encode_batch_corners): normals / texture coordinates given per corner
+[StructLayout(LayoutKind.Sequential)]
+internal unsafe struct DsaMeshCornerInput
+{
+    public DsaMeshInput Mesh;       // Normals / Texcoords hold NumNormals / NumTexcoords rows where the ids below are set
+    public uint* NormalCorners;     // 3 * NumFaces row ids into Mesh.Normals, or null: per vertex
+    public uint* TexcoordCorners;   // 3 * NumFaces row ids into Mesh.Texcoords, or null: per vertex
+    public uint NumNormals, NumTexcoords;
+}
+
 internal static unsafe partial class NativeMethods
 {
     private const string Lib = "draco_mi355x";
@@ -130,6 +140,7 @@ internal static unsafe partial class NativeMethods
     // encode direction (DracoEncoder.Encode, src/Draco/IO/DracoEncoder.cs:22-41)
     [DllImport(Lib)] internal static extern void dsa_encode_default_options(out DsaEncodeOptions options);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_batch(IntPtr ctx, uint n, DsaMeshInput* meshes, in DsaEncodeOptions options, out IntPtr encoded);
+    [DllImport(Lib)] internal static extern DsaStatus dsa_encode_batch_corners(IntPtr ctx, uint n, DsaMeshCornerInput* meshes, in DsaEncodeOptions options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern uint dsa_encoded_size(IntPtr encoded);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encoded_stream(IntPtr encoded, uint mesh, out byte* bytes, out nuint length);
     [DllImport(Lib)] internal static extern void dsa_encoded_free(IntPtr encoded);

@@ -50,6 +50,7 @@ struct EncLane {
   // attribute values upload and quantise behind them on `st`
   hipStream_t walk_st = nullptr;
   hipEvent_t tables_done = nullptr, walk_done = nullptr;
+  hipEvent_t seams_done = nullptr;                   // attributes given per corner: the seam tables are built, the attribute walks may start
   // device memory of the lane, grown on demand and kept: hipMalloc / hipFree wait for every stream of the device, which would
   // put the chunks of a batch back in single file
   struct Buf {
@@ -65,12 +66,13 @@ struct EncLane {
       return hipSuccess;
     }
     ~Buf() { if (p) (void)hipFree(p); }
-  } arena, streams, conns, packed, items;
+  } arena, streams, conns, seams, packed, items;
   ~EncLane() {
     if (walk_st) { (void)hipStreamSynchronize(walk_st); (void)hipStreamDestroy(walk_st); }
     if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
     if (tables_done) (void)hipEventDestroy(tables_done);
     if (walk_done) (void)hipEventDestroy(walk_done);
+    if (seams_done) (void)hipEventDestroy(seams_done);
   }
 };
 

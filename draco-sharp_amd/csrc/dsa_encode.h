@@ -28,6 +28,7 @@
 
 #include "dsa_encode_host.h"
 #include "dsa_encode_conn.h"
+#include "dsa_encode_seams.h"
 
 namespace dsa {
 
@@ -38,7 +39,8 @@ struct EncStream {                 // one per (mesh, attribute); lives in device
   uint64_t hist_raw;               // u32[hist_cap]
   uint64_t out_rans, out_bits;     // coded bytes
   uint64_t prob, cum;              // u32[num_symbols] (filled by the host between the two device phases)
-  uint32_t nv, nc_out, nc, kind;   // kind 0: quantised + wrap, 1: normals (octahedral, canonicalised delta), 2: uint8 integers + wrap (src: bytes)
+  uint32_t nv, nc_out, nc, kind;   // nv: entries; kind 0: quantised + wrap, 1: normals (octahedral, canonicalised delta), 2: uint8 integers + wrap (src: bytes)
+  uint32_t rows, rows_pad;         // value rows of `src` / `vals` (= nv, but for an attribute given per corner: its row count; k_enc_seam_operands sets nv)
   uint32_t bits, prediction, hist_cap, out_cap;
   float qmin[4], qrange;
   int32_t wrap_mn, wrap_mx;
@@ -65,7 +67,7 @@ __global__ __launch_bounds__(256) void k_enc_bounds(uint8_t *arena, EncStream *s
   const uint32_t nc = S.nc_out, tid = threadIdx.x;
   float mn[4], mx[4];
   for (uint32_t c = 0; c < 4; ++c) { mn[c] = src[c < nc ? c : 0]; mx[c] = mn[c]; }
-  for (uint32_t v = tid; v < S.nv; v += 256)
+  for (uint32_t v = tid; v < S.rows; v += 256)
     for (uint32_t c = 0; c < nc; ++c) { const float x = src[(size_t)v * nc + c]; if (x < mn[c]) mn[c] = x; if (x > mx[c]) mx[c] = x; }
   for (uint32_t c = 0; c < 4; ++c) { s_mn[c][tid] = mn[c]; s_mx[c][tid] = mx[c]; }
   __syncthreads();
@@ -119,17 +121,17 @@ __global__ __launch_bounds__(256) void k_enc_quantize(uint8_t *arena, EncStream 
   const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
   if (S.kind == 0) {                // Quantizer: floor((v - min) * (max_q / range) + 0.5), every step rounded to f32
     const float inv_delta = __fdiv_rn((float)(int32_t)((1u << S.bits) - 1u), S.qrange);
-    const uint32_t nc = S.nc_out, total = S.nv * nc;
+    const uint32_t nc = S.nc_out, total = S.rows * nc;
     for (uint32_t i = tid; i < total; i += stride) {
       const float v = __fsub_rn(src[i], S.qmin[i % nc]);
       vals[i] = (int32_t)floorf(__fadd_rn(__fmul_rn(v, inv_delta), 0.5f));
     }
   } else if (S.kind == 2) {         // an integer attribute: its values as they are (SequentialIntegerAttributeEncoder.cs: no transform)
     const uint8_t *srcb = arena + S.src;
-    const uint32_t total = S.nv * S.nc;
+    const uint32_t total = S.rows * S.nc;
     for (uint32_t i = tid; i < total; i += stride) vals[i] = (int32_t)srcb[i];
   } else {
-    for (uint32_t v = tid; v < S.nv; v += stride) {
+    for (uint32_t v = tid; v < S.rows; v += stride) {
       int32_t s, t;
       enc_oct_from_float(src + (size_t)v * 3, (int32_t)S.bits, s, t);
       vals[2 * v] = s; vals[2 * v + 1] = t;
@@ -374,6 +376,28 @@ __global__ __launch_bounds__(256) void k_enc_unpack(uint8_t *arena, const uint8_
 }  // namespace dsa
 
 // ------------------------------------------------------------------------------------------------ host side
+namespace dsa {
+// Value rows and entries of an attribute in traversal order (entry p: the value of the corner the walk reached it by; ids null:
+// the corner's vertex) and its parallelogram operand entries on table `ct` (MeshPredictionSchemeParallelogramEncoder.cs:35-56).
+template <class CT>
+static void entry_maps(const CT &ct, const synth::Sequence &seq, const uint32_t *ids, std::vector<uint32_t> &e2v, std::vector<int32_t> *ops) {
+  const uint32_t entries = (uint32_t)seq.data_to_corner.size();
+  e2v.resize(entries);
+  if (ops) ops->assign((size_t)3 * entries, -1);
+  for (uint32_t p = 0; p < entries; ++p) {
+    const uint32_t ci = seq.data_to_corner[p];
+    e2v[p] = ids ? ids[ci] : ct.vertex(ci);
+    if (p == 0 || !ops) continue;
+    const uint32_t oci = ct.opposite(ci);
+    if (oci == synth::kInvalid) continue;
+    const int32_t vo = seq.vertex_to_data[ct.vertex(oci)];
+    const int32_t vn = seq.vertex_to_data[ct.vertex(synth::CornerTable::next(oci))];
+    const int32_t vp = seq.vertex_to_data[ct.vertex(synth::CornerTable::prev(oci))];
+    if (vo < (int32_t)p && vn < (int32_t)p && vp < (int32_t)p) { (*ops)[3 * p] = vn; (*ops)[3 * p + 1] = vp; (*ops)[3 * p + 2] = vo; }
+  }
+}
+}  // namespace dsa
+
 struct dsa_encoded {
   dsa_context *ctx = nullptr;
   std::vector<std::vector<uint8_t>> streams;
@@ -391,11 +415,16 @@ void dsa_encode_default_options(dsa_encode_options *o) {
   o->position_prediction = d.pos_prediction; o->texcoord_prediction = d.uv_prediction;
 }
 
-static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint32_t batch_n, const dsa_mesh_input *meshes, const dsa_encode_options *options, dsa_encoded **out);
-static dsa_status encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_encode_options *options, dsa_encoded **out);
+// Both entry points share one chunk path: `meshes` (dsa_encode_batch) or `corners` (dsa_encode_batch_corners), the other null.
+static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint32_t batch_n, const dsa_mesh_input *meshes, const dsa_mesh_corner_input *corners, const dsa_encode_options *options, dsa_encoded **out);
+static dsa_status encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_mesh_corner_input *corners, const dsa_encode_options *options, dsa_encoded **out);
 dsa_status dsa_encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_encode_options *options, dsa_encoded **out) {
   if (!ctx || !out || (n && !meshes)) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "null argument");
-  DSA_GUARD(ctx, encode_batch(ctx, n, meshes, options, out));     // host vectors and threads inside: nothing may unwind into the caller
+  DSA_GUARD(ctx, encode_batch(ctx, n, meshes, nullptr, options, out));     // host vectors and threads inside: nothing may unwind into the caller
+}
+dsa_status dsa_encode_batch_corners(dsa_context *ctx, uint32_t n, const dsa_mesh_corner_input *meshes, const dsa_encode_options *options, dsa_encoded **out) {
+  if (!ctx || !out || (n && !meshes)) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "null argument");
+  DSA_GUARD(ctx, encode_batch(ctx, n, nullptr, meshes, options, out));
 }
 // A batch is coded in chunks, several of them in flight (each on a lane of its own: stream + pinned staging + device memory).  The
 // device stages of a chunk are bound by latency -- the walks of k_enc_connectivity take a memory round trip per step, 0.1 - 0.2 s
@@ -405,7 +434,7 @@ dsa_status dsa_encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *
 // those go first (phase A of every chunk in front of any phase B, hostutil::UploadTurns), the attribute values follow while the
 // walks run, on a stream of their own.  Streams of one priority share four hardware queues, on which the kernels of different
 // streams wait for each other: four lanes, their walk streams at another priority.  Small batches are one chunk.
-static dsa_status encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_encode_options *options, dsa_encoded **out) {
+static dsa_status encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_mesh_corner_input *corners, const dsa_encode_options *options, dsa_encoded **out) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const uint32_t max_lanes = [&]() { const char *e = getenv("DSA_ENC_LANES"); const int v = e ? atoi(e) : 0; return (uint32_t)(v >= 1 && v <= 16 ? v : 4); }();
   const uint32_t chunk_max = [&]() { const char *e = getenv("DSA_ENC_CHUNK"); const int v = e ? atoi(e) : 0; return (uint32_t)(v >= 1 ? v : 0); }();
@@ -427,6 +456,7 @@ static dsa_status encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_inpu
     HIP_TRY(ctx, hipStreamCreateWithPriority(&l->walk_st, hipStreamNonBlocking, (ctx->enc_lanes.size() & 1) ? greatest : least));
     HIP_TRY(ctx, hipEventCreateWithFlags(&l->tables_done, hipEventDisableTiming));
     HIP_TRY(ctx, hipEventCreateWithFlags(&l->walk_done, hipEventDisableTiming));
+    HIP_TRY(ctx, hipEventCreateWithFlags(&l->seams_done, hipEventDisableTiming));
     ctx->enc_lanes.push_back(std::move(l));
   }
   hostutil::UploadTurns upload_turn(chunks);
@@ -452,7 +482,7 @@ static dsa_status encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_inpu
         ctx->enc_lanes[l]->upload_chunk = c;
         dsa_encoded *part = nullptr;
         const auto t_chunk = std::chrono::steady_clock::now();
-        const dsa_status st = encode_chunk(&sink, *ctx->enc_lanes[l], cnt, n, meshes + base, options, &part);
+        const dsa_status st = encode_chunk(&sink, *ctx->enc_lanes[l], cnt, n, meshes ? meshes + base : nullptr, corners ? corners + base : nullptr, options, &part);
         if (getenv("DSA_ENC_TIMING")) fprintf(stderr, "[dsa_encode_batch] chunk %u (%u meshes) returned after %8.2f ms\n", c, cnt, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_chunk).count());
         if (st != DSA_OK) { errs[l] = sink.err; int ok = DSA_OK; failed.compare_exchange_strong(ok, st); break; }
         std::unique_ptr<dsa_encoded> owner(part);
@@ -474,7 +504,12 @@ static dsa_status encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_inpu
   *out = E.release();
   return DSA_OK;
 }
-static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint32_t batch_n, const dsa_mesh_input *meshes, const dsa_encode_options *options, dsa_encoded **out) {
+static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint32_t batch_n, const dsa_mesh_input *meshes_v, const dsa_mesh_corner_input *corners, const dsa_encode_options *options, dsa_encoded **out) {
+  // mesh i of the chunk, whichever entry point it came through (ids: its corner ids, null without)
+  struct MeshRef {
+    const dsa_mesh_input *v; const dsa_mesh_corner_input *c;
+    const dsa_mesh_input &operator[](size_t i) const { return c ? c[i].mesh : v[i]; }
+  } meshes{meshes_v, corners};
   hostutil::TurnGuard turn(lane.upload_turn, lane.upload_chunk);      // (whatever happens below, the other chunks' uploads do not wait for this one's)
   HIP_TRY(ctx, hipSetDevice(lane.device));
   dsa_encode_options od;
@@ -496,6 +531,9 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
   std::vector<synth::MeshIn> ins(n);
   std::vector<std::vector<uint32_t>> e2v(n);
   std::vector<std::vector<int32_t>> ops(n);
+  // attributes given per corner, host connectivity: per attribute its own entry -> value row, and its own operands when it is seamed
+  std::vector<std::vector<std::vector<uint32_t>>> att_e2v(n);
+  std::vector<std::vector<std::vector<int32_t>>> att_ops(n);
   // DSA_ENC_TIMING=1 (diagnostics): wall time of every phase on stderr
   static const bool timing = getenv("DSA_ENC_TIMING") != nullptr;
   auto t_last = std::chrono::steady_clock::now();
@@ -519,28 +557,36 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
     synth::MeshIn &in = ins[i];
     in.pos = m.positions; in.nv = m.num_vertices; in.faces = m.faces; in.nf = m.num_faces; in.normals = m.normals; in.uvs = m.texcoords;
     in.generic = (m.generic && m.generic_components >= 1 && m.generic_components <= 4) ? m.generic : nullptr;
+    if (corners) {
+      const dsa_mesh_corner_input &cm = corners[i];
+      if (m.generic && (m.generic_components < 1 || m.generic_components > 4)) { E->status[i] = DSA_ERR_INVALID_ARGUMENT; E->messages[i] = "generic attribute needs 1 - 4 components"; return; }
+      if ((cm.normal_corners && !m.normals) || (cm.texcoord_corners && !m.texcoords)) { E->status[i] = DSA_ERR_INVALID_ARGUMENT; E->messages[i] = "corner ids without their values"; return; }
+      in.normal_corners = cm.normal_corners; in.nn = cm.num_normals;
+      in.uv_corners = cm.texcoord_corners; in.nu = cm.num_texcoords;
+    }
     try {
       synth::check(m.positions && m.faces && m.num_vertices >= 3 && m.num_faces >= 1, "mesh needs positions and faces");
       for (size_t k = 0; k < (size_t)m.num_faces * 3; ++k) synth::check(m.faces[k] < m.num_vertices, "face index out of range");
+      if (in.normal_corners) for (size_t k = 0; k < (size_t)m.num_faces * 3; ++k) synth::check(in.normal_corners[k] < in.nn, "normal id out of range");
+      if (in.uv_corners) for (size_t k = 0; k < (size_t)m.num_faces * 3; ++k) synth::check(in.uv_corners[k] < in.nu, "texture coordinate id out of range");
       synth::check(host_conn || (uint64_t)m.num_faces * 3 <= (uint64_t)dsa::EC_CORNER_MASK, "mesh too large for the device connectivity coder");
       synth::Options mo = opt;                                   // (the components of the generic attribute are the mesh's own)
       mo.generic_components = in.generic ? (int32_t)m.generic_components : 1;
-      if (!host_conn) { synth::plan_attributes(in, mo, plans[i]); return; }       // the rest of the plan comes from the device
+      if (!host_conn) {                                          // the rest of the plan comes from the device
+        synth::check(!((in.normal_corners || in.uv_corners) && opt.single_connectivity), "attributes given per corner need a connectivity of their own (single_connectivity = 0)");
+        synth::check(!(in.normal_corners || in.uv_corners) || 24ull * m.num_faces + 16u < (1ull << 32), "mesh too large for the device connectivity coder");
+        synth::plan_attributes(in, mo, plans[i]);
+        return;
+      }
       synth::plan_mesh(in, mo, plans[i]);
       const synth::MeshPlan &pl = plans[i];
-      const uint32_t V = m.num_vertices;
-      e2v[i].resize(V);
-      ops[i].assign((size_t)3 * V, -1);
-      for (uint32_t p = 0; p < V; ++p) {
-        const uint32_t ci = pl.seq.data_to_corner[p];
-        e2v[i][p] = pl.ct.vertex(ci);
-        if (p == 0) continue;
-        const uint32_t oci = pl.ct.opposite(ci);
-        if (oci == synth::kInvalid) continue;
-        const int32_t vo = pl.seq.vertex_to_data[pl.ct.vertex(oci)];
-        const int32_t vn = pl.seq.vertex_to_data[pl.ct.vertex(synth::CornerTable::next(oci))];
-        const int32_t vp = pl.seq.vertex_to_data[pl.ct.vertex(synth::CornerTable::prev(oci))];
-        if (vo < (int32_t)p && vn < (int32_t)p && vp < (int32_t)p) { ops[i][3 * p] = vn; ops[i][3 * p + 1] = vp; ops[i][3 * p + 2] = vo; }
+      dsa::entry_maps(pl.ct, pl.seq, nullptr, e2v[i], &ops[i]);
+      att_e2v[i].assign(pl.atts.size(), {}); att_ops[i].assign(pl.atts.size(), {});
+      for (size_t k = 1; k < pl.atts.size(); ++k) {
+        const uint32_t *ids = pl.atts[k].corner_value;
+        if (!ids) continue;
+        if (pl.seamed(k)) dsa::entry_maps(pl.conns[k], pl.seq_att[k], ids, att_e2v[i][k], &att_ops[i][k]);
+        else dsa::entry_maps(pl.ct, pl.seq, ids, att_e2v[i][k], nullptr);      // (the positions' operands)
       }
     } catch (const std::exception &e) { E->status[i] = DSA_ERR_INVALID_DATA; E->messages[i] = e.what(); }
   };
@@ -549,7 +595,14 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
   // ---- device layout
   std::vector<dsa::EncStream> hs;
   std::vector<dsa::EncConn> hc(host_conn ? 0 : n);
+  std::vector<dsa::EncSeam> hz;                   // device connectivity: one per (mesh, attribute given per corner)
   std::vector<uint32_t> first_stream(n + 1, 0);
+  // value rows of attribute k of mesh i: its ids' row count when it is given per corner
+  auto rows_of = [&](uint32_t i, const synth::PortableAttr &a) -> uint32_t {
+    if (!a.corner_value) return meshes[i].num_vertices;
+    return a.att_type == 1 ? corners[i].num_normals : corners[i].num_texcoords;
+  };
+  auto ids_narrow = [&](uint32_t i, const synth::PortableAttr &a) { return rows_of(i, a) <= 65536; };
   // What the host provides (faces, raw attribute values; with host connectivity the traversal order and operands) lies at the
   // front of the arena in one run, so that it travels in a few large transfers out of pinned staging; everything else behind it.
   auto al = [](uint64_t b) { return (b + 255) & ~255ull; };
@@ -558,14 +611,22 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
     if (E->status[i] != DSA_OK) continue;
     const uint64_t V = meshes[i].num_vertices, F = meshes[i].num_faces;
     in_total += host_conn ? al(4 * V) + al(12 * V) : al((V <= 65536 ? 6 : 12) * F);      // (faces of a mesh of up to 65 536 vertices travel as 16-bit indices)
-    for (auto &a : plans[i].atts) in_total += al(4 * V * (uint64_t)a.nc_out);
+    for (size_t k = 0; k < plans[i].atts.size(); ++k) {
+      const synth::PortableAttr &a = plans[i].atts[k];
+      in_total += al(4 * (uint64_t)rows_of(i, a) * (uint64_t)a.nc_out);
+      if (!a.corner_value) continue;
+      if (host_conn) { const uint64_t ent = att_e2v[i][k].size(); in_total += al(4 * ent) + (att_ops[i][k].empty() ? 0 : al(12 * ent)); }
+      else in_total += al((ids_narrow(i, a) ? 6 : 12) * F);          // the ids travel with the faces, narrowed like them
+    }
   }
   uint64_t cur = in_total, cur_in = 0;
   auto take = [&](uint64_t bytes) { uint64_t at = cur; cur = (cur + bytes + 255) & ~255ull; return at; };
   auto take_in = [&](uint64_t bytes) { uint64_t at = cur_in; cur_in = (cur_in + bytes + 255) & ~255ull; return at; };
   struct Upload { uint64_t off; const void *src; size_t bytes; bool narrow; };       // narrow: src is u32[bytes / 2], the staging copy keeps the low halves
-  std::vector<Upload> uploads_a, uploads;          // phase A: what the walks need (the faces); the rest
+  std::vector<Upload> uploads_a, uploads;          // phase A: what the walks need (the faces, the corner ids); the rest
+  uint32_t max_rows = 0;
   std::vector<uint64_t> faces_at(n, 0);
+  std::vector<std::vector<uint64_t>> ids_at(n);
   if (!host_conn)
     for (uint32_t i = 0; i < n; ++i) {
       if (E->status[i] != DSA_OK) continue;
@@ -574,6 +635,15 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
       const bool narrow = meshes[i].num_vertices <= 65536;
       faces_at[i] = take_in((narrow ? 6ull : 12ull) * meshes[i].num_faces);
       uploads_a.push_back({faces_at[i], meshes[i].faces, (narrow ? 6ull : 12ull) * meshes[i].num_faces, narrow});
+      // corner ids right behind (the seam kernels read them as they were uploaded: 16-bit where the row count allows)
+      ids_at[i].assign(plans[i].atts.size(), 0);
+      for (size_t k = 0; k < plans[i].atts.size(); ++k) {
+        const synth::PortableAttr &a = plans[i].atts[k];
+        if (!a.corner_value) continue;
+        const uint64_t bytes = (ids_narrow(i, a) ? 6ull : 12ull) * meshes[i].num_faces;
+        ids_at[i][k] = take_in(bytes);
+        uploads_a.push_back({ids_at[i][k], a.corner_value, bytes, ids_narrow(i, a)});
+      }
     }
   for (uint32_t i = 0; i < n; ++i) {
     first_stream[i] = (uint32_t)hs.size();
@@ -596,21 +666,45 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
       C.d2c = take(4ull * V); C.v2d = take(4ull * V);
       C.e2v = o_e2v; C.ops = o_ops;
     }
-    for (auto &a : plans[i].atts) {
+    for (size_t k = 0; k < plans[i].atts.size(); ++k) {
+      const synth::PortableAttr &a = plans[i].atts[k];
       dsa::EncStream S;
       memset(&S, 0, sizeof(S));
       const bool integer = a.att_type == 4;                  // the generic uint8 attribute
       const void *src = a.att_type == 0 ? (const void *)meshes[i].positions : (a.att_type == 1 ? (const void *)meshes[i].normals : (integer ? (const void *)meshes[i].generic : (const void *)meshes[i].texcoords));
-      S.nv = V; S.nc_out = (uint32_t)a.nc_out; S.nc = (uint32_t)a.nc; S.kind = a.seq_type == 3 ? 1u : (integer ? 2u : 0u);
+      // entries: V, or for an attribute given per corner as many as its walk has (host connectivity) / may have (device: 3F at
+      // most, k_enc_seam_operands sets the count)
+      const uint32_t rows = rows_of(i, a);
+      uint32_t entries = V, cap = V;
+      S.e2v = o_e2v; S.ops = o_ops;
+      if (a.corner_value && host_conn) {
+        entries = cap = (uint32_t)att_e2v[i][k].size();
+        S.e2v = take_in(4ull * entries);
+        uploads.push_back({S.e2v, att_e2v[i][k].data(), 4ull * entries, false});
+        if (!att_ops[i][k].empty()) { S.ops = take_in(12ull * entries); uploads.push_back({S.ops, att_ops[i][k].data(), 12ull * entries, false}); }
+      } else if (a.corner_value) {
+        const uint32_t F = meshes[i].num_faces;
+        cap = 3u * F;
+        dsa::EncSeam Z;
+        memset(&Z, 0, sizeof(Z));
+        Z.mesh = i; Z.stream = (uint32_t)hs.size(); Z.ids = ids_at[i][k]; Z.ids_narrow = ids_narrow(i, a) ? 1u : 0u; Z.rows = rows;
+        Z.edge_seam = take(3ull * F); Z.vert_seam = take(V); Z.afirst = take(4ull * V); Z.aoff = take(4ull * (V + 1));
+        Z.c2av = take(12ull * F); Z.opp2 = take(12ull * F); Z.v2lm = take(12ull * F); Z.avis = take(3ull * F); Z.frec = take(32ull * F);
+        Z.stack = take(4ull * F); Z.d2c = take(12ull * F); Z.v2d = take(12ull * F); Z.e2v = take(12ull * F); Z.ops = take(36ull * F);
+        Z.rank = take(4ull * F); Z.rcorner = take(4ull * F); Z.eoff = take(4ull * (F + 1)); Z.bits = take(4ull * ((3ull * F + 31) / 32));
+        S.e2v = Z.e2v; S.ops = Z.ops;
+        hz.push_back(Z);
+      }
+      S.nv = entries; S.rows = rows; S.nc_out = (uint32_t)a.nc_out; S.nc = (uint32_t)a.nc; S.kind = a.seq_type == 3 ? 1u : (integer ? 2u : 0u);
       S.bits = integer ? 9u : (uint32_t)a.bits; S.prediction = (uint32_t)a.prediction;      // (9: the zig-zagged corrections of bytes are below 512)
-      const uint64_t src_bytes = (integer ? 1ull : 4ull) * V * S.nc_out;
+      const uint64_t src_bytes = (integer ? 1ull : 4ull) * rows * S.nc_out;
       S.src = take_in(src_bytes);
       uploads.push_back({S.src, src, src_bytes, false});
-      S.e2v = o_e2v; S.ops = o_ops;
-      S.vals = take(4ull * V * S.nc); S.d = take(4ull * V * S.nc); S.syms = take(4ull * V * S.nc); S.bl = take(V);
+      S.vals = take(4ull * rows * S.nc); S.d = take(4ull * cap * S.nc); S.syms = take(4ull * cap * S.nc); S.bl = take(cap);
+      max_rows = std::max(max_rows, std::max(rows, cap));
       S.hist_cap = (1u << S.bits) + 2u;                      // zig-zag of a wrapped correction / a positive octahedral correction fits
       S.hist_raw = take(4ull * S.hist_cap);
-      S.out_cap = 4u * V * S.nc + 16u;
+      S.out_cap = 4u * cap * S.nc + 16u;
       S.out_rans = take(S.out_cap); S.out_bits = take(S.out_cap);
       const uint64_t table_cap = std::max<uint64_t>(S.hist_cap, 64);   // the tagged scheme's alphabet is 33 bit lengths
       S.prob = take(4ull * table_cap); S.cum = take(4ull * table_cap);
@@ -623,6 +717,8 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
   uint8_t *arena = nullptr;
   dsa::EncStream *d_streams = nullptr;
   dsa::EncConn *d_conns = nullptr;
+  dsa::EncSeam *d_seams = nullptr;
+  const uint32_t nz = (uint32_t)hz.size();
   auto cleanup = [&]() {};      // the lane owns its device memory (EncLane::Buf): nothing to release per chunk
 #define ENC_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { return set_err(ctx, e_ == hipErrorOutOfMemory ? DSA_ERR_OUT_OF_MEMORY : DSA_ERR_DEVICE, "%s failed: %s", #call, hipGetErrorString(e_)); } } while (0)
   // pieces of the arena -> one host buffer (items[k].packed_off filled in); host buffer -> pieces of the arena
@@ -700,9 +796,7 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
     ENC_TRY(upload(host_conn ? uploads : uploads_a));
     if (host_conn) turn.release();
     ENC_TRY(hipMemcpyAsync(d_streams, hs.data(), sizeof(dsa::EncStream) * ns, hipMemcpyHostToDevice, st));
-    uint32_t maxv = 0;
-    for (auto &S : hs) maxv = std::max(maxv, S.nv);
-    const uint32_t gx = std::max(1u, std::min(64u, (maxv + 2047) / 2048));
+    const uint32_t gx = std::max(1u, std::min(64u, (max_rows + 2047) / 2048));
     lap("layout + uploads queued");
     // ---- device phase 0: corner table, Edgebreaker symbols, attribute order, operand entries (one wave per mesh); meshes that
     // failed the host's checks have F = 0 and no arrays
@@ -724,6 +818,21 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
       ENC_TRY(hipEventRecord(lane.tables_done, st));
       ENC_TRY(hipStreamWaitEvent(lane.walk_st, lane.tables_done, 0));
       hipLaunchKernelGGL(dsa::k_enc_connectivity, dim3((n + walk_lanes - 1) / walk_lanes), dim3(WAVE), 0, lane.walk_st, arena, d_conns, n, walk_lanes);
+      if (nz) {
+        // attributes given per corner: seams and attribute vertices beside the connectivity walk, the attribute walks behind it
+        ENC_TRY(lane.seams.ensure(sizeof(dsa::EncSeam) * nz));
+        d_seams = (dsa::EncSeam *)lane.seams.p;
+        ENC_TRY(hipMemcpyAsync(d_seams, hz.data(), sizeof(dsa::EncSeam) * nz, hipMemcpyHostToDevice, st));
+        const dim3 gz(gt.x, nz);
+        hipLaunchKernelGGL(dsa::k_enc_seam_edges, gz, dim3(256), 0, st, arena, d_conns, d_seams, nz);
+        hipLaunchKernelGGL(dsa::k_enc_seam_fans, gz, dim3(256), 0, st, arena, d_conns, d_seams, nz);
+        hipLaunchKernelGGL(dsa::k_enc_seam_offsets, dim3(nz), dim3(WAVE), 0, st, arena, d_conns, d_seams, nz);
+        hipLaunchKernelGGL(dsa::k_enc_seam_assign, gz, dim3(256), 0, st, arena, d_conns, d_seams, nz);
+        hipLaunchKernelGGL(dsa::k_enc_seam_records, gz, dim3(256), 0, st, arena, d_conns, d_seams, nz);
+        ENC_TRY(hipEventRecord(lane.seams_done, st));
+        ENC_TRY(hipStreamWaitEvent(lane.walk_st, lane.seams_done, 0));
+        hipLaunchKernelGGL(dsa::k_enc_seam_walk, dim3((nz + walk_lanes - 1) / walk_lanes), dim3(WAVE), 0, lane.walk_st, arena, d_conns, d_seams, nz, walk_lanes);
+      }
       ENC_TRY(hipEventRecord(lane.walk_done, lane.walk_st));
       turn.release();
       turn.acquire_b();
@@ -733,6 +842,14 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
       hipLaunchKernelGGL(dsa::k_enc_quantize, dim3(gx, ns), dim3(256), 0, st, arena, d_streams, ns);
       ENC_TRY(hipStreamWaitEvent(st, lane.walk_done, 0));
       hipLaunchKernelGGL(dsa::k_enc_operands, gt, dim3(256), 0, st, arena, d_conns, n);
+      if (nz) {
+        const dim3 gz(gt.x, nz);
+        hipLaunchKernelGGL(dsa::k_enc_seam_operands<dsa::EncStream>, gz, dim3(256), 0, st, arena, d_conns, d_seams, nz, d_streams);
+        hipLaunchKernelGGL(dsa::k_enc_seam_rank, gz, dim3(256), 0, st, arena, d_conns, d_seams, nz);
+        hipLaunchKernelGGL(dsa::k_enc_seam_count, gz, dim3(256), 0, st, arena, d_conns, d_seams, nz);
+        hipLaunchKernelGGL(dsa::k_enc_seam_scan, dim3(nz), dim3(WAVE), 0, st, arena, d_conns, d_seams, nz);
+        hipLaunchKernelGGL(dsa::k_enc_seam_bits, gz, dim3(256), 0, st, arena, d_conns, d_seams, nz);
+      }
     } else {
       hipLaunchKernelGGL(dsa::k_enc_bounds, dim3(ns), dim3(256), 0, st, arena, d_streams, ns);
       hipLaunchKernelGGL(dsa::k_enc_quantize, dim3(gx, ns), dim3(256), 0, st, arena, d_streams, ns);
@@ -746,6 +863,7 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
     }
     ENC_TRY(hipMemcpyAsync(hs.data(), d_streams, sizeof(dsa::EncStream) * ns, hipMemcpyDeviceToHost, st));
     if (!host_conn) ENC_TRY(hipMemcpyAsync(hc.data(), d_conns, sizeof(dsa::EncConn) * n, hipMemcpyDeviceToHost, st));
+    if (nz) ENC_TRY(hipMemcpyAsync(hz.data(), d_seams, sizeof(dsa::EncSeam) * nz, hipMemcpyDeviceToHost, st));
     ENC_TRY(hipStreamSynchronize(st));
     lap("device phases 0 + 1");
     if (!host_conn) {
@@ -779,6 +897,34 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
         const uint32_t *sp = C.num_splits ? (const uint32_t *)(conn_host + conn_items[k + 2].packed_off) : nullptr;
         for (size_t q = 0; q < eb.splits.size(); ++q) eb.splits[q] = {sp[3 * q], sp[3 * q + 1], sp[3 * q + 2]};
       }, 8);
+      // attributes given per corner: a failed seam step fails its mesh; the seam bits of seamed attributes come down packed
+      std::vector<dsa::PackItem> seam_items;
+      for (uint32_t z = 0; z < nz; ++z) {
+        const dsa::EncSeam &Z = hz[z];
+        const uint32_t i = Z.mesh;
+        if (E->status[i] != DSA_OK) continue;
+        if (Z.status != dsa::ENC_SEAM_OK) {
+          E->status[i] = DSA_ERR_INVALID_DATA; E->messages[i] = dsa::enc_seam_message(Z.status);
+          for (uint32_t sk = first_stream[i]; sk < first_stream[i + 1]; ++sk) hs[sk].overflow = 1;
+          continue;
+        }
+        synth::MeshPlan &pl = plans[i];
+        if (pl.seamed_given.empty()) pl.seamed_given.assign(pl.atts.size(), 0);
+        pl.seamed_given[Z.stream - first_stream[i]] = Z.interior_seams ? 1 : 0;
+        if (Z.interior_seams) seam_items.push_back({Z.bits, 0, 4u * ((hc[i].interior_edges + 31u) / 32u), z});
+      }
+      std::vector<uint8_t> seam_host;
+      ENC_ST(gather(seam_items, seam_host, nullptr));
+      for (auto &it : seam_items) {
+        const dsa::EncSeam &Z = hz[it.pad];
+        synth::MeshPlan &pl = plans[Z.mesh];
+        if (E->status[Z.mesh] != DSA_OK) continue;
+        const uint32_t ne = hc[Z.mesh].interior_edges;
+        if (pl.seam_bits_given.empty()) pl.seam_bits_given.assign(pl.atts.size(), std::vector<uint8_t>(ne, 0));
+        std::vector<uint8_t> &b = pl.seam_bits_given[Z.stream - first_stream[Z.mesh]];
+        const uint32_t *words = (const uint32_t *)(seam_host.data() + it.packed_off);
+        for (uint32_t e = 0; e < ne; ++e) b[e] = (uint8_t)((words[e >> 5] >> (e & 31u)) & 1u);
+      }
     }
   }
   lap("connectivity results");

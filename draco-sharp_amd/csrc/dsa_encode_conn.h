@@ -236,6 +236,76 @@ __device__ __forceinline__ EcHop ec_hop(const EcFace &r, uint32_t k) {
 }
 enum { EC_MARK = 6, EC_MARK2 = 7, EC_CORNER_MASK = 0x1FFFFFFF, EC_SYMBOL_SHIFT = 29 };    // words of a face record; fields of a `processed` entry
 
+// Depth-first attribute order over the decoder's face order (DepthFirstTraverser.cs:9-99), one lane: the second walk of
+// k_enc_connectivity over the position table, and the walk of a seamed attribute over that attribute's face records
+// (dsa_encode_seams.h).  Vertex marks: 2 on a boundary, 4 visited; face mark: word EC_MARK2 of the record.  Entries go to
+// d2c / v2d (nv of them at most); returns how many vertices were visited, `stuck` when the step bound or a full stack stopped it.
+__device__ __forceinline__ uint32_t ec_dfs_walk(const uint4 *frec, uint32_t *fw, uint8_t *vvis, uint32_t *stack, uint32_t *d2c, int32_t *v2d,
+                                                const uint32_t *processed, const uint32_t *init_corners, uint32_t nproc, uint32_t ninit,
+                                                uint32_t F, uint32_t V, uint32_t step_limit, bool &stuck) {
+  const uint32_t nstarts = nproc + ninit;
+  uint32_t count = 0, dfs_steps = 0, nfaces = 0;
+  auto visit = [&](uint32_t v, uint32_t vm, uint32_t c) { vvis[v] = (uint8_t)(vm | 4u); v2d[v] = (int32_t)count; if (count < V) d2c[count] = c; ++count; };
+  for (uint32_t i = 0; i < nstarts && !stuck && nfaces < F;) {
+    // the next start whose face is still to do: eight candidates a round trip
+    uint32_t cand[8], m2[8];
+#pragma unroll
+    for (uint32_t j = 0; j < 8; ++j) {
+      const uint32_t k = i + j;
+      cand[j] = k < nstarts ? (k < nproc ? processed[nproc - 1 - k] & (uint32_t)EC_CORNER_MASK : init_corners[k - nproc]) : DSA_INVALID;
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < 8; ++j) m2[j] = cand[j] != DSA_INVALID ? fw[8 * (cand[j] / 3u) + EC_MARK2] : 1u;
+    uint32_t start = DSA_INVALID, hit = 8;
+#pragma unroll
+    for (uint32_t j = 0; j < 8; ++j) if (hit == 8 && m2[j] == 0) { hit = j; start = cand[j]; }
+    if (hit == 8) { i += 8; continue; }
+    i += hit + 1;
+    uint32_t sp = 0;
+    stack[sp++] = start;
+    {
+      const EcFace sf = ec_face(frec, start / 3u);
+      const uint32_t k = start - 3u * (start / 3u);
+      const uint32_t nvx = k == 0 ? sf.v1 : (k == 1 ? sf.v2 : sf.v0), pvx = k == 0 ? sf.v2 : (k == 1 ? sf.v0 : sf.v1);
+      { const uint32_t m = vvis[nvx]; if (!(m & 4u)) visit(nvx, m, ec_next(start)); }
+      { const uint32_t m = vvis[pvx]; if (!(m & 4u)) visit(pvx, m, ec_prev(start)); }
+    }
+    while (sp && !stuck) {
+      uint32_t corner = stack[sp - 1];
+      if (corner == DSA_INVALID) { --sp; continue; }
+      uint32_t f = corner / 3u;
+      EcFace cur = ec_face(frec, f);
+      if (cur.mark2 != 0) { --sp; continue; }
+      for (;;) {
+        if (++dfs_steps > step_limit || count > V) { stuck = true; break; }
+        const EcHop h = ec_hop(cur, corner - 3u * f);
+        const uint32_t fr = h.rc == DSA_INVALID ? 0u : h.rc / 3u, fl = h.lc == DSA_INVALID ? 0u : h.lc / 3u;
+        const uint32_t vm = vvis[h.v];
+        const EcFace R = ec_face(frec, fr), L = ec_face(frec, fl);
+        const bool r_done = h.rc == DSA_INVALID || fr == f || R.mark2 != 0, l_done = h.lc == DSA_INVALID || fl == f || L.mark2 != 0;
+        fw[8 * f + EC_MARK2] = 1u;
+        ++nfaces;
+        if (!(vm & 4u)) {
+          visit(h.v, vm, corner);
+          if (!(vm & 2u)) { corner = h.rc; f = fr; cur = R; continue; }
+        }
+        if (r_done) {
+          if (l_done) { --sp; break; }
+          corner = h.lc; f = fl; cur = L;
+        } else {
+          if (l_done) { corner = h.rc; f = fr; cur = R; }
+          else {
+            if (sp >= F) { stuck = true; break; }
+            stack[sp - 1] = h.lc; stack[sp++] = h.rc;
+            break;
+          }
+        }
+      }
+    }
+  }
+  return count;
+}
+
 // Lane l of block b walks mesh b * lanes_per_wave + l.  A step of either walk is one memory round trip -- the marks of the vertex
 // at the corner and the records of the two faces across, which all hang off what the previous step loaded, are issued together --
 // and two stores (the mark of the face; the corner and its symbol).  Lanes whose meshes differ in shape diverge and rejoin by
@@ -394,67 +464,8 @@ __global__ __launch_bounds__(WAVE) void k_enc_connectivity(uint8_t *arena, EncCo
   // ---- depth-first attribute order over the decoder's face order (processed corners last to first, then the init
   // corners), DepthFirstTraverser.cs:9-99.  A vertex is on a boundary -- SwingLeft of its left-most corner is invalid -- exactly
   // when it is the end of an edge without an opposite.  The marks of this walk are its own (mark2, bit 4 of a vertex).
-  const uint32_t nstarts = nproc + ninit;
-  uint32_t count = 0, dfs_steps = 0, nfaces = 0;
   bool stuck = false;
-  auto visit = [&](uint32_t v, uint32_t vm, uint32_t c) { vvis[v] = (uint8_t)(vm | 4u); v2d[v] = (int32_t)count; if (count < V) d2c[count] = c; ++count; };
-  for (uint32_t i = 0; i < nstarts && !stuck && nfaces < F;) {
-    // the next start whose face is still to do: eight candidates a round trip
-    uint32_t cand[8], m2[8];
-#pragma unroll
-    for (uint32_t j = 0; j < 8; ++j) {
-      const uint32_t k = i + j;
-      cand[j] = k < nstarts ? (k < nproc ? processed[nproc - 1 - k] & (uint32_t)EC_CORNER_MASK : init_corners[k - nproc]) : DSA_INVALID;
-    }
-#pragma unroll
-    for (uint32_t j = 0; j < 8; ++j) m2[j] = cand[j] != DSA_INVALID ? fw[8 * (cand[j] / 3u) + EC_MARK2] : 1u;
-    uint32_t start = DSA_INVALID, hit = 8;
-#pragma unroll
-    for (uint32_t j = 0; j < 8; ++j) if (hit == 8 && m2[j] == 0) { hit = j; start = cand[j]; }
-    if (hit == 8) { i += 8; continue; }
-    i += hit + 1;
-    uint32_t sp = 0;
-    stack[sp++] = start;
-    {
-      const EcFace sf = ec_face(frec, start / 3u);
-      const uint32_t k = start - 3u * (start / 3u);
-      const uint32_t nvx = k == 0 ? sf.v1 : (k == 1 ? sf.v2 : sf.v0), pvx = k == 0 ? sf.v2 : (k == 1 ? sf.v0 : sf.v1);
-      { const uint32_t m = vvis[nvx]; if (!(m & 4u)) visit(nvx, m, ec_next(start)); }
-      { const uint32_t m = vvis[pvx]; if (!(m & 4u)) visit(pvx, m, ec_prev(start)); }
-    }
-    while (sp && !stuck) {
-      uint32_t corner = stack[sp - 1];
-      if (corner == DSA_INVALID) { --sp; continue; }
-      uint32_t f = corner / 3u;
-      EcFace cur = ec_face(frec, f);
-      if (cur.mark2 != 0) { --sp; continue; }
-      for (;;) {
-        if (++dfs_steps > step_limit || count > V) { stuck = true; break; }
-        const EcHop h = ec_hop(cur, corner - 3u * f);
-        const uint32_t fr = h.rc == DSA_INVALID ? 0u : h.rc / 3u, fl = h.lc == DSA_INVALID ? 0u : h.lc / 3u;
-        const uint32_t vm = vvis[h.v];
-        const EcFace R = ec_face(frec, fr), L = ec_face(frec, fl);
-        const bool r_done = h.rc == DSA_INVALID || fr == f || R.mark2 != 0, l_done = h.lc == DSA_INVALID || fl == f || L.mark2 != 0;
-        fw[8 * f + EC_MARK2] = 1u;
-        ++nfaces;
-        if (!(vm & 4u)) {
-          visit(h.v, vm, corner);
-          if (!(vm & 2u)) { corner = h.rc; f = fr; cur = R; continue; }
-        }
-        if (r_done) {
-          if (l_done) { --sp; break; }
-          corner = h.lc; f = fl; cur = L;
-        } else {
-          if (l_done) { corner = h.rc; f = fr; cur = R; }
-          else {
-            if (sp >= F) { stuck = true; break; }
-            stack[sp - 1] = h.lc; stack[sp++] = h.rc;
-            break;
-          }
-        }
-      }
-    }
-  }
+  const uint32_t count = ec_dfs_walk(frec, fw, vvis, stack, d2c, v2d, processed, init_corners, nproc, ninit, F, V, step_limit, stuck);
   E->num_entries = count;
   if (stuck) ec_fail(E, ENC_RING, count);
   else if (count != V) ec_fail(E, ENC_UNREACHED, count);

@@ -1167,7 +1167,14 @@ struct MeshPlan {
   // whose attributes are all per vertex.
   std::vector<AttrConn> conns;
   std::vector<Sequence> seq_att;
-  bool seamed(size_t att) const { return att < conns.size() && conns[att].ct && !conns[att].no_interior_seams; }
+  // The same found on the device (dsa_encode_seams.h), where there is no corner table here: per attribute 1 = seamed, and per
+  // attribute the seam bits of every interior edge in decoder face order (all zero for an attribute without seams).
+  std::vector<uint8_t> seamed_given;
+  std::vector<std::vector<uint8_t>> seam_bits_given;
+  bool seamed(size_t att) const {
+    if (!seamed_given.empty()) return att < seamed_given.size() && seamed_given[att];
+    return att < conns.size() && conns[att].ct && !conns[att].no_interior_seams;
+  }
   bool uses_pd(size_t att) const { return !seamed(att) && (traversal_method == 2 || (traversal_method == 1 && (single || att == 0))); }
   const Sequence &seq_of(size_t att) const { return seamed(att) ? seq_att[att] : (uses_pd(att) ? seq_pd : seq); }
   std::vector<PortableAttr> atts;    // descriptors; vals / quantisation parameters are filled by whoever codes the values
@@ -1258,7 +1265,9 @@ static void write_stream(ByteWriter &w, const MeshIn &in, const MeshPlan &pl, Va
     write_rabs(w, eb.start_face_bits);
     bool any_seams = false;
     for (size_t i = 1; i < pl.atts.size(); ++i) any_seams = any_seams || pl.seamed(i);
-    if (pl.num_att_data && any_seams) {
+    if (pl.num_att_data && any_seams && !pl.seam_bits_given.empty()) {
+      for (uint32_t i = 0; i < pl.num_att_data; ++i) write_rabs(w, pl.seam_bits_given[i + 1]);
+    } else if (pl.num_att_data && any_seams) {
       // MeshEdgeBreakerEncoder.cs:418-440: in decoder face order, for every interior edge whose other face comes later,
       // one bit per attribute -- is the edge a seam of that attribute; a block per attribute (MeshEdgeBreakerTraversalEncoder.cs:62-70)
       std::vector<uint8_t> vis(ct.nf(), 0);

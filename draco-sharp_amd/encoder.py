@@ -40,13 +40,19 @@ class Config:
 
 class MeshData:
     """Triangle mesh with per-vertex attributes: positions (V,3) f32, faces (F,3) u32, optional normals (V,3), uvs (V,2) and one
-    generic uint8 attribute of 1 - 4 components (V,) or (V,C): vertex colours, ids (ABI 4)."""
+    generic uint8 attribute of 1 - 4 components (V,) or (V,C): vertex colours, ids (ABI 4).
 
-    def __init__(self, positions, faces, normals=None, texcoords=None, generic=None):
+    normal_corners / texcoord_corners (F,3) u32: the normals / texture coordinates given per corner -- row ids into `normals` /
+    `texcoords`, which then hold as many rows as the ids need (UV charts, hard edges).  Edges whose end points carry different ids
+    on their two faces become attribute seams (dsa_encode_batch_corners)."""
+
+    def __init__(self, positions, faces, normals=None, texcoords=None, generic=None, normal_corners=None, texcoord_corners=None):
         self.positions = np.ascontiguousarray(positions, np.float32)
         self.faces = np.ascontiguousarray(faces, np.uint32)
         self.normals = None if normals is None else np.ascontiguousarray(normals, np.float32)
         self.texcoords = None if texcoords is None else np.ascontiguousarray(texcoords, np.float32)
+        self.normal_corners = self._ids(normal_corners, self.normals, 3, "normal")
+        self.texcoord_corners = self._ids(texcoord_corners, self.texcoords, 2, "texcoord")
         self.generic = None
         if generic is not None:
             g = np.ascontiguousarray(generic, np.uint8)
@@ -54,6 +60,27 @@ class MeshData:
             if len(g) != len(self.positions) or not 1 <= g.shape[1] <= 4:
                 raise ValueError("generic attribute: one row of 1 - 4 uint8 components per vertex")
             self.generic = g
+
+    def _ids(self, ids, rows, nc, name):
+        if ids is None:
+            return None
+        if rows is None:
+            raise ValueError("%s_corners needs %ss" % (name, name))
+        if rows.ndim != 2 or rows.shape[1] != nc:
+            raise ValueError("%ss given per corner: one row of %d components per value" % (name, nc))
+        a = np.asarray(ids)
+        if a.shape != (len(self.faces), 3) and a.size != 3 * len(self.faces):
+            raise ValueError("%s_corners: one id per face corner, shape (F, 3)" % name)
+        if a.size and (np.issubdtype(a.dtype, np.signedinteger) and a.min() < 0):
+            raise ValueError("%s_corners: ids are row numbers, not negative" % name)
+        a = np.ascontiguousarray(a.reshape(len(self.faces), 3), np.uint32)
+        if a.size and int(a.max()) >= len(rows):
+            raise ValueError("%s_corners: id %d out of range (%d rows)" % (name, int(a.max()), len(rows)))
+        return a
+
+    @property
+    def per_corner(self):
+        return getattr(self, "normal_corners", None) is not None or getattr(self, "texcoord_corners", None) is not None
 
 
 class EncodedStreams:
@@ -121,19 +148,28 @@ class DracoEncoder:
         ctx = self._ctx or default_context()
         L = native.lib()
         n = len(meshes)
-        arr = (native.MeshInput * max(1, n))()
+        # the corner entry point only when some mesh carries ids; otherwise exactly the per-vertex call
+        corners = any(getattr(m, "per_corner", False) for m in meshes)
+        arr = ((native.MeshCornerInput if corners else native.MeshInput) * max(1, n))()
         for i, m in enumerate(meshes):
-            arr[i].num_vertices, arr[i].num_faces = len(m.positions), len(m.faces)
-            arr[i].positions, arr[i].faces = m.positions.ctypes.data, m.faces.ctypes.data
-            arr[i].normals = m.normals.ctypes.data if m.normals is not None else None
-            arr[i].texcoords = m.texcoords.ctypes.data if m.texcoords is not None else None
+            mi = arr[i].mesh if corners else arr[i]
+            mi.num_vertices, mi.num_faces = len(m.positions), len(m.faces)
+            mi.positions, mi.faces = m.positions.ctypes.data, m.faces.ctypes.data
+            mi.normals = m.normals.ctypes.data if m.normals is not None else None
+            mi.texcoords = m.texcoords.ctypes.data if m.texcoords is not None else None
             g = getattr(m, "generic", None)
-            arr[i].generic = g.ctypes.data if g is not None else None
-            arr[i].generic_components = g.shape[1] if g is not None else 0
+            mi.generic = g.ctypes.data if g is not None else None
+            mi.generic_components = g.shape[1] if g is not None else 0
+            if corners:
+                nci, uci = getattr(m, "normal_corners", None), getattr(m, "texcoord_corners", None)
+                arr[i].normal_corners = nci.ctypes.data if nci is not None else None
+                arr[i].texcoord_corners = uci.ctypes.data if uci is not None else None
+                arr[i].num_normals = len(m.normals) if m.normals is not None else 0
+                arr[i].num_texcoords = len(m.texcoords) if m.texcoords is not None else 0
         opt = (config or Config())._native()
         h = C.c_void_p()
         t0 = time.perf_counter()
-        st = L.dsa_encode_batch(ctx._h, n, arr, C.byref(opt), C.byref(h))
+        st = (L.dsa_encode_batch_corners if corners else L.dsa_encode_batch)(ctx._h, n, arr, C.byref(opt), C.byref(h))
         t1 = time.perf_counter()
         if st != 0:
             _raise(st, ctx.error())

@@ -22,7 +22,7 @@ EXPORTS = [
     "dsa_batch_device_point_map", "dsa_batch_output_bytes", "dsa_batch_download", "dsa_batch_compact_bytes", "dsa_batch_download_compact", "dsa_batch_host_output", "dsa_batch_output_layout",
     "dsa_host_alloc", "dsa_host_free", "dsa_host_register", "dsa_host_unregister", "dsa_batch_copy_metadata", "dsa_batch_copy_debug", "dsa_context_set_profiling", "dsa_batch_stage_times",
     "dsa_batch_kernel_times", "dsa_context_trim", "dsa_context_schedule_note",
-    "dsa_encode_default_options", "dsa_encode_batch", "dsa_encoded_size", "dsa_encoded_stream", "dsa_encoded_free",
+    "dsa_encode_default_options", "dsa_encode_batch", "dsa_encode_batch_corners", "dsa_encoded_size", "dsa_encoded_stream", "dsa_encoded_free",
     "dsa_pool_create", "dsa_pool_destroy", "dsa_pool_size", "dsa_pool_last_error", "dsa_pool_decode", "dsa_pool_job_locate",
     "dsa_pool_job_chunks", "dsa_pool_job_free", "dsa_pool_plan",
 ]
@@ -38,6 +38,12 @@ class MeshInput(C.Structure):
     _fields_ = [("num_vertices", C.c_uint32), ("num_faces", C.c_uint32), ("positions", C.c_void_p), ("faces", C.c_void_p),
                 ("normals", C.c_void_p), ("texcoords", C.c_void_p), ("generic", C.c_void_p), ("generic_components", C.c_uint32),
                 ("reserved", C.c_uint32)]
+
+
+class MeshCornerInput(C.Structure):
+    """dsa_mesh_corner_input: a mesh whose normals / texture coordinates may be given per corner (row ids per face corner)."""
+    _fields_ = [("mesh", MeshInput), ("normal_corners", C.c_void_p), ("texcoord_corners", C.c_void_p),
+                ("num_normals", C.c_uint32), ("num_texcoords", C.c_uint32)]
 
 
 class MeshInfo(C.Structure):
@@ -131,6 +137,7 @@ def lib():
         L.dsa_encode_default_options.argtypes = [C.POINTER(EncodeOptions)]
         L.dsa_encode_default_options.restype = None
         L.dsa_encode_batch.argtypes = [vp, u32, C.POINTER(MeshInput), C.POINTER(EncodeOptions), C.POINTER(vp)]
+        L.dsa_encode_batch_corners.argtypes = [vp, u32, C.POINTER(MeshCornerInput), C.POINTER(EncodeOptions), C.POINTER(vp)]
         L.dsa_encoded_size.restype = u32
         L.dsa_encoded_size.argtypes = [vp]
         L.dsa_encoded_stream.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(C.c_size_t)]

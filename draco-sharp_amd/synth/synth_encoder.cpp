@@ -162,9 +162,10 @@ int synth_encode_mesh(const float *pos, uint32_t nv, const uint32_t *faces, uint
 // (MeshEdgeBreakerEncoder.cs:403-440, MeshAttributeCornerTable.cs:32-155).
 int synth_encode_mesh_corners(const float *pos, uint32_t nv, const uint32_t *faces, uint32_t nf, const float *normals, uint32_t nn,
                               const uint32_t *normal_corners, const float *uvs, uint32_t nu, const uint32_t *uv_corners,
-                              const synth_options *opt, uint8_t **out, size_t *out_len) {
+                              const uint8_t *generic, const synth_options *opt, uint8_t **out, size_t *out_len) {
   try {
-    synth::MeshIn in{pos, nv, faces, nf, normals, uvs, nullptr, normals ? normal_corners : nullptr, nn, uvs ? uv_corners : nullptr, nu};
+    // (the generic attribute stays per vertex: nv rows of opt->generic_components bytes, or NULL)
+    synth::MeshIn in{pos, nv, faces, nf, normals, uvs, generic, normals ? normal_corners : nullptr, nn, uvs ? uv_corners : nullptr, nu};
     for (size_t k = 0; k < (size_t)nf * 3; ++k) {
       synth::check(faces[k] < nv, "face index out of range");
       synth::check(!in.normal_corners || in.normal_corners[k] < nn, "normal id out of range");

@@ -256,6 +256,24 @@ void dsa_encode_default_options(dsa_encode_options *options);
  * encoded (non-manifold, isolated vertex, index out of range) fails alone: see dsa_encoded_stream. */
 dsa_status dsa_encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_encode_options *options,
                             dsa_encoded **out);
+/* Meshes whose normals and / or texture coordinates are given per corner (UV charts, hard edges): what the reference encoder
+ * takes from a point cloud whose attributes map points to values (CornerTable.cs:571-596 CreateFromAttribute).  An edge whose end
+ * points carry different ids on its two faces becomes an attribute seam (MeshAttributeCornerTable.cs:32-155): seam bits, the
+ * attribute's own corner table and order, a corner attribute in the stream (MeshEdgeBreakerEncoder.cs:403-440).  Standard
+ * Edgebreaker, difference / parallelogram prediction, single_connectivity = 0.  Positions and the generic attribute stay per
+ * vertex.  Added after ABI 4 without changing it: callers detect the feature by the symbol dsa_encode_batch_corners. */
+typedef struct dsa_mesh_corner_input {
+  dsa_mesh_input mesh;                 /* as for dsa_encode_batch; when an id array below is set, the matching value array
+                                          (mesh.normals / mesh.texcoords) holds num_* rows instead of num_vertices */
+  const uint32_t *normal_corners;      /* 3 * num_faces row ids into mesh.normals, or NULL: per vertex */
+  const uint32_t *texcoord_corners;    /* 3 * num_faces row ids into mesh.texcoords, or NULL: per vertex */
+  uint32_t num_normals, num_texcoords;
+} dsa_mesh_corner_input;
+/* dsa_encode_batch for dsa_mesh_corner_input; the result is read with the dsa_encoded_* accessors.  A mesh fails alone
+ * (dsa_encoded_stream): a row id >= its row count (DSA_ERR_INVALID_DATA), ids with single_connectivity = 1 (DSA_ERR_INVALID_DATA),
+ * generic != NULL with generic_components outside 1..4 or ids without their values (DSA_ERR_INVALID_ARGUMENT). */
+dsa_status dsa_encode_batch_corners(dsa_context *ctx, uint32_t n, const dsa_mesh_corner_input *meshes,
+                                    const dsa_encode_options *options, dsa_encoded **out);
 uint32_t dsa_encoded_size(const dsa_encoded *encoded);
 /* Bytes of stream `mesh` (owned by `encoded`, valid until dsa_encoded_free) or that mesh's failure status. */
 dsa_status dsa_encoded_stream(const dsa_encoded *encoded, uint32_t mesh, const uint8_t **bytes, size_t *length);
