@@ -133,6 +133,7 @@ template <> struct Rec<false> {
   struct Raw { uint4 v, o; };
   static __device__ __forceinline__ Raw load(const uint32_t *frec, uint32_t f) { Raw r; r.v = ((const uint4 *)frec)[(size_t)f * 2]; r.o = ((const uint4 *)frec)[(size_t)f * 2 + 1]; return r; }
   static __device__ __forceinline__ Raw none() { Raw r; r.v = make_uint4(0, 0, 0, 0); r.o = make_uint4(DSA_INVALID, DSA_INVALID, DSA_INVALID, 0); return r; }
+  static __device__ __forceinline__ Raw or_none(bool ok, const Raw &x) { return ok ? x : none(); }
   // (operands by value: a conditional expression over members of a referenced struct selects an ADDRESS, which keeps the struct in scratch)
   static __device__ __forceinline__ uint32_t sel3(uint32_t k, uint32_t x, uint32_t y, uint32_t z) { return k == 0 ? x : (k == 1 ? y : z); }
   static __device__ __forceinline__ uint32_t vertex(const Raw &r, uint32_t k) { return sel3(k, r.v.x, r.v.y, r.v.z); }
@@ -160,6 +161,7 @@ template <> struct Rec<true> {
   static __device__ __forceinline__ uint32_t field(uint64_t w, uint32_t k) { return (uint32_t)((int32_t)((uint32_t)(w >> (21u * k)) << 11) >> 11); }   // sign-extended
   static __device__ __forceinline__ Raw load(const uint32_t *frec, uint32_t f) { const uint4 q = ((const uint4 *)frec)[f]; Raw r; r.v = (uint64_t)q.x | ((uint64_t)q.y << 32); r.o = (uint64_t)q.z | ((uint64_t)q.w << 32); return r; }
   static __device__ __forceinline__ Raw none() { Raw r; r.v = 0; r.o = ~0ull; return r; }
+  static __device__ __forceinline__ Raw or_none(bool ok, const Raw &x) { Raw r; r.v = ok ? x.v : 0ull; r.o = ok ? x.o : ~0ull; return r; }
   static __device__ __forceinline__ uint32_t vertex(const Raw &r, uint32_t k) { return field(r.v, k); }
   static __device__ __forceinline__ uint32_t opp(const Raw &r, uint32_t k) { return field(r.o, k); }
   static __device__ __forceinline__ uint32_t get_v(const uint32_t *frec, uint32_t c) { return field(((const uint64_t *)frec)[(size_t)(c >> 2) * 2], c & 3u); }
@@ -1215,8 +1217,6 @@ __device__ __forceinline__ void para_operands_flat(uint32_t p, const uint32_t *f
 //     extrapolated id against what the records it loaded say, and only lanes whose ids all agree take part.  The progressions
 //     continue the previous run, or, at the start of a side, combine the exact ids of the first pair with the steps the same
 //     direction had the last time (step history keyed by the step of a: a spiral has four directions).
-//   * when all six progressions are linear, "which earlier pair of this run holds face / tip X" is arithmetic
-//     ((X - first) / step is an integer below the run length) instead of a search in the LDS tables.
 //   * dependent attempt (no history for the direction): exact hops seed the path, then records of a, records of b and the marks
 //     in three round trips, as the data dependences dictate; membership through the tables.
 //   * the pair a run ends on was loaded and judged like every other: its two elements go to the scalar step with their record
@@ -1296,12 +1296,15 @@ __device__ __forceinline__ void traverse_wave(uint8_t *arena, const MeshLayout &
   // shader clocks by phase: [0] fast loads (issue -> ids checked), [1] element inputs + seed, [2] dependent hops + loads, [3] membership + verdict,
   // [4] retirement + progressions, [5] scalar step
   uint64_t tp_acc[6] = {0, 0, 0, 0, 0, 0}, tp_last = clk();
-  uint32_t np_fast_hit = 0, np_dep = 0, np_head = 0, np_hist = 0, np_lin = 0, np_hand = 0;
+  // (DSA_TRAV_NO_FAST / _NO_HIST / _NO_DEP switch one attempt kind off, for the accounting in profiles/README.md)
+  uint32_t np_fast_hit = 0, np_dep = 0, np_head = 0, np_hist = 0, np_lin = 0, np_hand = 0, np_pairs1 = 0, np_pairs2 = 0;
 #define TPROF(slot_) { const uint64_t t_ = clk(); tp_acc[slot_] += t_ - tp_last; tp_last = t_; }
 #define TCOUNT(x_) ++x_
+#define TADD(x_, n_) x_ += (n_)
 #else
 #define TPROF(slot_)
 #define TCOUNT(x_)
+#define TADD(x_, n_)
 #endif
 #define TR_FAIL(site) { if (lane == 0) fail(D, ST_INVALID, (site)); failed = true; break; }
 #define VISIT_SCALAR(v_, c_, fl_) { if (lane == 0) { vflag[v_] = (uint8_t)((fl_) | 1u); d2c[count] = (c_); v2d[v_] = (int32_t)count; } ++count; }
@@ -1361,6 +1364,9 @@ __device__ __forceinline__ void traverse_wave(uint8_t *arena, const MeshLayout &
       bool pair_ok = false;
       uint32_t len = 0;
 
+#ifdef DSA_TRAV_NO_FAST
+      have_prog = false;
+#endif
       if (have_prog && backoff == 0) { kind = 1; lin = prog_lin; }
       else {
         // ---------------------------------------------------------------- this element: record, marks; the record behind its right edge
@@ -1376,12 +1382,14 @@ __device__ __forceinline__ void traverse_wave(uint8_t *arena, const MeshLayout &
         if (have_state) bits = c_bits;
         else {
           // tip flag and the state of both sides, and the record a run from here would need next, issued together
-          const uint32_t tip_flag = vflag[v];
-          const uint32_t side_r = rc != DSA_INVALID ? (uint32_t)fvis[rc >> 2] : 1u, side_l = lc != DSA_INVALID ? (uint32_t)fvis[lc >> 2] : 1u;
           // (the records behind both edges ride along: whichever way the step goes, the next element's record is here)
-          Raw rl0 = R::none();
-          if (rc != DSA_INVALID) { rb0 = R::load(frec, rc >> 2); have_seed = true; }
-          if (lc != DSA_INVALID) rl0 = R::load(frec, lc >> 2);
+          const bool r_ok = rc != DSA_INVALID, l_ok = lc != DSA_INVALID;
+          const uint32_t fr = r_ok ? rc >> 2 : 0u, fl = l_ok ? lc >> 2 : 0u;
+          const uint32_t tip_flag = vflag[v], side_r0 = fvis[fr], side_l0 = fvis[fl];
+          rb0 = R::or_none(r_ok, R::load(frec, fr));
+          const Raw rl0 = R::or_none(l_ok, R::load(frec, fl));
+          have_seed = r_ok;
+          const uint32_t side_r = r_ok ? side_r0 : 1u, side_l = l_ok ? side_l0 : 1u;
           have_kids = true;
           { const uint32_t kr = rc & 3u, kl = lc & 3u;
             kr_v = uni(R::vertex(rb0, kr)); kr_rc = uni(R::opp(rb0, k_next(kr))); kr_lc = uni(R::opp(rb0, k_prev(kr)));
@@ -1403,6 +1411,9 @@ __device__ __forceinline__ void traverse_wave(uint8_t *arena, const MeshLayout &
           const uint32_t d1 = a1 - corner;
           // steps this direction had the last time (keyed by the step of a)
           const uint32_t e = dir & 3u;
+#ifdef DSA_TRAV_NO_HIST
+          no_hist = true;
+#endif
           const bool hm = !no_hist && d1 != 0u && corner_ok(a1) && uni(sh_hist[8 * e]) == d1;
           if (hm) {
             const uint32_t s_b = uni(sh_hist[8 * e + 1]), s_ta = uni(sh_hist[8 * e + 2]), s_tb = uni(sh_hist[8 * e + 3]), s_la = uni(sh_hist[8 * e + 4]), s_rb = uni(sh_hist[8 * e + 5]);
@@ -1410,7 +1421,11 @@ __device__ __forceinline__ void traverse_wave(uint8_t *arena, const MeshLayout &
             p_la = lc == DSA_INVALID ? DSA_INVALID : lc + lane * s_la; p_rb = rB0 == DSA_INVALID ? DSA_INVALID : rB0 + lane * s_rb;
             kind = 2; lin = true;
             TCOUNT(np_hist);
-          } else {
+          }
+#ifdef DSA_TRAV_NO_DEP
+          else { }
+#else
+          else {
             // ------------------------------------------------------------ dependent attempt: exact hops seed the candidate path
             // a_0, a_1, a_2 = succ(a_1) with succ(a) = Opposite(Previous(Opposite(Next(a)))); lanes 3.. extrapolate with constant
             // second difference; every link is verified from the records the lanes load anyway
@@ -1442,13 +1457,15 @@ __device__ __forceinline__ void traverse_wave(uint8_t *arena, const MeshLayout &
             }
             len = leading_lanes(a_ok);                 // verified chain a_0 .. a_(len-1)
             pair_ok = lane < len && b_ok && tipB < NV && corner_ok(lcB) && (rcB == DSA_INVALID || corner_ok(rcB));
-            if (pair_ok) {                             // state before the step
-              const uint32_t m0 = lane == 0 ? 0u : fvis[a >> 2], m4 = lcA != DSA_INVALID ? fvis[lcA >> 2] : 1u, m1 = fvis[b >> 2];
-              const uint32_t m2 = rcB != DSA_INVALID ? fvis[rcB >> 2] : 1u, m3 = fvis[lcB >> 2], ta = vflag[tipA], tb = vflag[tipB];
-              marks = TR_MARKS(m0, m1, m2, m3, m4, ta, tb);
+            if (pair_ok) {                             // state before the step (all loads issued together: see the fast attempt)
+              const bool la_ok = lcA != DSA_INVALID, rb_ok = rcB != DSA_INVALID;
+              const uint32_t m0 = fvis[a >> 2], m4 = fvis[la_ok ? lcA >> 2 : 0u], m1 = fvis[b >> 2];
+              const uint32_t m2 = fvis[rb_ok ? rcB >> 2 : 0u], m3 = fvis[lcB >> 2], ta = vflag[tipA], tb = vflag[tipB];
+              marks = TR_MARKS(lane == 0 ? 0u : m0, m1, rb_ok ? m2 : 1u, m3, la_ok ? m4 : 1u, ta, tb);
             }
             TCOUNT(np_dep);
           }
+#endif
         } else if (backoff) --backoff;
         must_scalar = false;
         TPROF(1);
@@ -1460,15 +1477,17 @@ __device__ __forceinline__ void traverse_wave(uint8_t *arena, const MeshLayout &
         a = p_a;
         const bool a_ok = lane < window && corner_ok(a);
         const bool bp_ok = a_ok && corner_ok(p_b);
-        Raw ra = R::none(), rb = R::none();
-        if (a_ok) ra = R::load(frec, a >> 2);
-        if (bp_ok) rb = R::load(frec, p_b >> 2);
-        if (bp_ok) {
-          const uint32_t m0 = lane == 0 ? 0u : fvis[a >> 2], m1 = fvis[p_b >> 2], m4 = corner_ok(p_la) ? fvis[p_la >> 2] : 1u;
-          const uint32_t m2 = corner_ok(p_rb) ? fvis[p_rb >> 2] : 1u, m3 = corner_ok(p_an) ? fvis[p_an >> 2] : 1u;
-          const uint32_t ta = p_ta < NV ? vflag[p_ta] : 1u, tb = p_tb < NV ? vflag[p_tb] : 1u;
-          marks = TR_MARKS(m0, m1, m2, m3, m4, ta, tb);
-        }
+        // Every load of the attempt at once, unconditionally, at id 0 where its guard is false, and the guards applied to the values
+        // afterwards: a load under a guard of its own is completed inside that branch (the value is converted there), so the nine
+        // loads would be as many round trips.
+        const bool la_ok = corner_ok(p_la), rb_ok = corner_ok(p_rb), an_ok = corner_ok(p_an), ta_ok = p_ta < NV, tb_ok = p_tb < NV;
+        const uint32_t fa_l = a_ok ? a >> 2 : 0u, fb_l = bp_ok ? p_b >> 2 : 0u;
+        const Raw ra0 = R::load(frec, fa_l), rb1 = R::load(frec, fb_l);
+        const uint32_t m0 = fvis[fa_l], m1 = fvis[fb_l], m4 = fvis[la_ok ? p_la >> 2 : 0u];
+        const uint32_t m2 = fvis[rb_ok ? p_rb >> 2 : 0u], m3 = fvis[an_ok ? p_an >> 2 : 0u];
+        const uint32_t ta = vflag[ta_ok ? p_ta : 0u], tb = vflag[tb_ok ? p_tb : 0u];
+        const Raw ra = R::or_none(a_ok, ra0), rb = R::or_none(bp_ok, rb1);
+        if (bp_ok) marks = TR_MARKS(lane == 0 ? 0u : m0, m1, rb_ok ? m2 : 1u, an_ok ? m3 : 1u, la_ok ? m4 : 1u, ta_ok ? ta : 1u, tb_ok ? tb : 1u);
         const uint32_t ka = a & 3u, kb = p_b & 3u;
         tipA = R::vertex(ra, ka); b = R::opp(ra, k_next(ka)); lcA = R::opp(ra, k_prev(ka));
         tipB = R::vertex(rb, kb); rcB = R::opp(rb, k_next(kb)); lcB = R::opp(rb, k_prev(kb));
@@ -1491,60 +1510,9 @@ __device__ __forceinline__ void traverse_wave(uint8_t *arena, const MeshLayout &
         // of them.  A tip that was visited before the run can never count as new, so only unvisited tips are looked up; the
         // neighbour faces only where their state before the run leaves the question open.
         uint32_t sfa = TR_NONE, sfb = TR_NONE, sta = TR_NONE, stb = TR_NONE, srf = TR_NONE, slf = TR_NONE, sla = TR_NONE;
-        // Are the four id sequences (faces of a, faces of b, tips of a, tips of b) closed forms over the verified lanes?  A fast
-        // attempt checked every lane against its progression; a dependent one built a by formula, the others are checked here against
-        // the fit through lanes 0 .. 2.  Strictly monotonic sequences with a constant second difference: "which pair holds X" is a
-        // division (linear) or a six-step bisection on the closed form -- no LDS tables.
-        int32_t fa0, fas, fad, fb0, fbs, fbd, ta0, tas, tad, tb0, tbs, tbd;
-        bool arith;
+        // Membership through the tables, also where the ids are progressions: the closed-form answer (a division or a bisection per
+        // lookup) was measured to cost more issue and more clocks than the LDS round trips it saves (profiles/README.md, round 5).
         {
-          const uint32_t tri = lane * (lane - 1u) / 2u;
-          const bool two = len >= 2, three = len >= 3;
-          auto fit = [&](uint32_t x, int32_t &q0, int32_t &qs, int32_t &qd) {
-            const uint32_t x0 = rdlane(x, 0), x1 = rdlane(x, 1), x2 = rdlane(x, 2);
-            q0 = (int32_t)x0; qs = two ? (int32_t)(x1 - x0) : 1; qd = three ? (int32_t)((x2 - x1) - (x1 - x0)) : 0;
-          };
-          auto mono = [&](int32_t s_, int32_t d_) -> bool {
-            const int32_t last = s_ + d_ * (int32_t)(two ? len - 2u : 0u);
-            return s_ != 0 && last != 0 && ((s_ ^ last) >= 0) && d_ > -(1 << 24) && d_ < (1 << 24);
-          };
-          int32_t a0, as_, ad, b0, bs_, bd;
-          fit(a, a0, as_, ad); fit(b, b0, bs_, bd); fit(tipA, ta0, tas, tad); fit(tipB, tb0, tbs, tbd);
-          arith = ((as_ | ad | bs_ | bd) & 3) == 0 && mono(as_, ad) && mono(bs_, bd) && mono(tas, tad) && mono(tbs, tbd);
-          if (arith && kind == 3)
-            arith = __ballot(lane < len && (a != (uint32_t)a0 + lane * (uint32_t)as_ + (uint32_t)ad * tri || b != (uint32_t)b0 + lane * (uint32_t)bs_ + (uint32_t)bd * tri ||
-                                            tipA != (uint32_t)ta0 + lane * (uint32_t)tas + (uint32_t)tad * tri || tipB != (uint32_t)tb0 + lane * (uint32_t)tbs + (uint32_t)tbd * tri)) == 0;
-          fa0 = a0 >> 2; fas = as_ >> 2; fad = ad >> 2; fb0 = b0 >> 2; fbs = bs_ >> 2; fbd = bd >> 2;
-        }
-        if (arith) {
-          TCOUNT(np_lin);
-          const float iA = 1.0f / (float)fas, iB = 1.0f / (float)fbs, iTA = 1.0f / (float)tas, iTB = 1.0f / (float)tbs;
-          auto pos_in = [&](uint32_t X, int32_t first, int32_t step, int32_t dd, float inv, uint32_t odd) -> uint32_t {
-            if (dd == 0) {                                    // X = first + j step
-              const int32_t d = (int32_t)X - first;
-              const int32_t j = (int32_t)__builtin_rintf((float)d * inv);
-              return (j >= 0 && (uint32_t)j < len && j * step == d) ? 2u * (uint32_t)j + odd : TR_NONE;
-            }
-            int32_t j = 0;                                    // the last j whose element is not beyond X
-#pragma unroll
-            for (int32_t bit = 32; bit >= 1; bit >>= 1) {
-              const int32_t t = j + bit;
-              const int32_t qt = first + t * step + dd * (t * (t - 1) / 2);
-              if ((uint32_t)t < len && (step > 0 ? qt <= (int32_t)X : qt >= (int32_t)X)) j = t;
-            }
-            return first + j * step + dd * (j * (j - 1) / 2) == (int32_t)X ? 2u * (uint32_t)j + odd : TR_NONE;
-          };
-          auto face_pos = [&](uint32_t X) -> uint32_t { const uint32_t x = pos_in(X, fa0, fas, fad, iA, 0u), y = pos_in(X, fb0, fbs, fbd, iB, 1u); return x < y ? x : y; };
-          auto tip_pos = [&](uint32_t X) -> uint32_t { const uint32_t x = pos_in(X, ta0, tas, tad, iTA, 0u), y = pos_in(X, tb0, tbs, tbd, iTB, 1u); return x < y ? x : y; };
-          if (pair_ok) {
-            sfa = face_pos(fa); sfb = face_pos(fb);
-            if (!(flA & 1u)) sta = tip_pos(tipA);
-            if (!(flB & 1u)) stb = tip_pos(tipB);
-            if (rcB != DSA_INVALID && fR_before == 0) srf = face_pos(rcB >> 2);
-            if (fL_before == 0) slf = face_pos(lcB >> 2);
-            if (lcA != DSA_INVALID && fLA_before == 0 && flA != 0) sla = face_pos(lcA >> 2);
-          }
-        } else {
           // two small open-addressing tables in LDS, slot = run tag (24) | id (32) | position (8); a slot of an older run counts
           // as empty, so nothing is cleared between runs.  Exact: the smallest position per id wins (ds_min_u64).
           if (++run_id >= 0x00FFFFF0u) {        // 24-bit run tags: start over with empty tables (meshes with > 16 M runs)
@@ -1679,6 +1647,8 @@ __device__ __forceinline__ void traverse_wave(uint8_t *arena, const MeshLayout &
           if ((fuse_operands & 2u) && K < window && len > K) { side2 = side1; side1 = K; const uint32_t m = (side1 > side2 ? side1 : side2) + 4; window = m < WAVE ? m : WAVE; }
           else window = WAVE;
           if (kind != 3) TCOUNT(np_fast_hit);
+          if (kind == 1) TADD(np_pairs1, K);
+          if (kind == 2) TADD(np_pairs2, K);
           TPROF(4);
           if (K >= win_used) continue;
           if (K < len) ++dir;                    // stopped by a verdict, not by a wrong guess: a turn
@@ -1766,6 +1736,7 @@ __device__ __forceinline__ void traverse_wave(uint8_t *arena, const MeshLayout &
 #ifdef DSA_TRAV_PROFILE
     for (int i = 0; i < 5; ++i) D->dbg[10 + (i < 3 ? i : i + 5)] = (uint32_t)(tp_acc[i] >> 4);   // [10] [11] [12] [18] [19], in units of 16 clocks
     D->dbg[0] = (uint32_t)(tp_acc[5] >> 4); D->dbg[1] = np_fast_hit; D->dbg[2] = np_dep; D->dbg[4] = np_head; D->dbg[13] = np_hist; D->dbg[14] = np_lin; D->dbg[15] = np_hand;
+    D->dbg[16] = np_pairs1; D->dbg[17] = np_pairs2;
 #endif
     // a valid stream carries exactly one entry per encoded vertex (k_locate sized the symbol streams on that)
     if (count != expect) fail(D, ST_INVALID, 305);
@@ -1818,6 +1789,7 @@ __device__ __forceinline__ void traverse_wave(uint8_t *arena, const MeshLayout &
 #undef VISIT_SCALAR
 #undef TPROF
 #undef TCOUNT
+#undef TADD
 #undef fA_before
 #undef fB_before
 #undef fR_before
