@@ -38,6 +38,16 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
         opt.NormalBits = config.GetAttributeOption((int)GeometryAttributeType.Normal, ConfigOptionName.Attribute.QuantizationBits, opt.NormalBits);
         opt.SymbolScheme = config.GetOption(ConfigOptionName.SymbolEncodingMethod, opt.SymbolScheme);
         opt.CompressionLevel = 10 - config.Speed;
+        // explicitly set schemes (ConfigOptionName.EdgeBreakerMethod, ConfigOptionName.Attribute.PredictionScheme) go through
+        // dsa_encode_batch_ex; unset, the call and its bytes are what they were
+        const int unset = int.MinValue;
+        int ebMethod = config.GetOption(ConfigOptionName.EdgeBreakerMethod, unset);
+        int uvScheme = config.GetAttributeOption((int)GeometryAttributeType.TexCoord, ConfigOptionName.Attribute.PredictionScheme, unset);
+        int posScheme = config.GetAttributeOption((int)GeometryAttributeType.Position, ConfigOptionName.Attribute.PredictionScheme, unset);
+        int normalScheme = config.GetAttributeOption((int)GeometryAttributeType.Normal, ConfigOptionName.Attribute.PredictionScheme, unset);
+        if (uvScheme != unset) opt.TexcoordPrediction = uvScheme;
+        if (posScheme != unset) opt.PositionPrediction = posScheme;
+        bool extended = ebMethod != unset || normalScheme != unset;
         var inputs = new DsaMeshInput[meshes.Count];
         var pins = new List<GCHandle>();
         IntPtr encoded = IntPtr.Zero;
@@ -45,12 +55,23 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
         {
             bool anyCorners = false;
             foreach (var m in meshes) anyCorners = anyCorners || NeedsCornerForm(m);
-            if (anyCorners)
+            if (anyCorners || extended)
             {
                 var cin = new DsaMeshCornerInput[meshes.Count];
                 for (int i = 0; i < meshes.Count; ++i) CornerForm(meshes[i], ref cin[i], pins);
                 fixed (DsaMeshCornerInput* p = cin)
-                    NativeMethods.Check(NativeMethods.dsa_encode_batch_corners(_ctx, (uint)meshes.Count, p, in opt, out encoded), _ctx, "dsa_encode_batch_corners");
+                {
+                    if (extended)
+                    {
+                        NativeMethods.dsa_encode_default_options_ex(out var ex);
+                        ex.Base = opt;
+                        ex.EdgebreakerMethod = ebMethod != unset ? ebMethod : 0;
+                        ex.NormalPrediction = normalScheme != unset ? normalScheme : 0;
+                        NativeMethods.Check(NativeMethods.dsa_encode_batch_ex(_ctx, (uint)meshes.Count, p, in ex, out encoded), _ctx, "dsa_encode_batch_ex");
+                    }
+                    else
+                        NativeMethods.Check(NativeMethods.dsa_encode_batch_corners(_ctx, (uint)meshes.Count, p, in opt, out encoded), _ctx, "dsa_encode_batch_corners");
+                }
                 return Streams(encoded, meshes.Count);
             }
             for (int i = 0; i < meshes.Count; ++i)

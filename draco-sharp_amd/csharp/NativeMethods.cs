@@ -69,6 +69,16 @@ internal struct DsaEncodeOptions
     public int PositionPrediction, TexcoordPrediction;
 }
 
+// dsa_encode_options_ex (dsa_encode_batch_ex): valence Edgebreaker, TexCoordsPortable, GeometricNormal
+[StructLayout(LayoutKind.Sequential)]
+internal unsafe struct DsaEncodeOptionsEx
+{
+    public DsaEncodeOptions Base;
+    public int EdgebreakerMethod;   // 0 standard, 2 valence, -1 by speed and face count (DracoEncoder.cs:86-97)
+    public int NormalPrediction;    // 0 difference, 6 GeometricNormal
+    public fixed int Reserved[6];   // zero
+}
+
 [StructLayout(LayoutKind.Sequential)]
 internal unsafe struct DsaMeshInput
 {
@@ -141,6 +151,8 @@ internal static unsafe partial class NativeMethods
     [DllImport(Lib)] internal static extern void dsa_encode_default_options(out DsaEncodeOptions options);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_batch(IntPtr ctx, uint n, DsaMeshInput* meshes, in DsaEncodeOptions options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_batch_corners(IntPtr ctx, uint n, DsaMeshCornerInput* meshes, in DsaEncodeOptions options, out IntPtr encoded);
+    [DllImport(Lib)] internal static extern void dsa_encode_default_options_ex(out DsaEncodeOptionsEx options);
+    [DllImport(Lib)] internal static extern DsaStatus dsa_encode_batch_ex(IntPtr ctx, uint n, DsaMeshCornerInput* meshes, in DsaEncodeOptionsEx options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern uint dsa_encoded_size(IntPtr encoded);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encoded_stream(IntPtr encoded, uint mesh, out byte* bytes, out nuint length);
     [DllImport(Lib)] internal static extern void dsa_encoded_free(IntPtr encoded);

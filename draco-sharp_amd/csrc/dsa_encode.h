@@ -29,6 +29,7 @@
 #include "dsa_encode_host.h"
 #include "dsa_encode_conn.h"
 #include "dsa_encode_seams.h"
+#include "dsa_encode_schemes.h"
 
 namespace dsa {
 
@@ -39,7 +40,8 @@ struct EncStream {                 // one per (mesh, attribute); lives in device
   uint64_t hist_raw;               // u32[hist_cap]
   uint64_t out_rans, out_bits;     // coded bytes
   uint64_t prob, cum;              // u32[num_symbols] (filled by the host between the two device phases)
-  uint32_t nv, nc_out, nc, kind;   // nv: entries; kind 0: quantised + wrap, 1: normals (octahedral, canonicalised delta), 2: uint8 integers + wrap (src: bytes)
+  uint32_t nv, nc_out, nc, kind;   // nv: entries; kind 0: quantised + wrap, 1: normals (octahedral, canonicalised delta), 2: uint8 integers + wrap (src: bytes),
+                                   //   3: a valence context list of the connectivity (syms given, nc 1; no values, no prediction)
   uint32_t rows, rows_pad;         // value rows of `src` / `vals` (= nv, but for an attribute given per corner: its row count; k_enc_seam_operands sets nv)
   uint32_t bits, prediction, hist_cap, out_cap;
   float qmin[4], qrange;
@@ -51,6 +53,13 @@ struct EncStream {                 // one per (mesh, attribute); lives in device
   uint32_t rans_len, bits_len;
   uint64_t plan_order, plan_tmp;   // u32[table_cap] each: scratch of k_enc_plan
   uint32_t usbl, plan_status;      // raw scheme: unique-symbols bit length; dsa::plan::PLAN_* of k_enc_plan
+  // prediction 5 (TexCoordsPortable, kind 0) and 6 (GeometricNormal, kind 1): the topology view of dsa_encode_schemes.h (EncTopo)
+  // -- set by the host, for a seamed attribute on the device path by k_enc_seam_topo -> k_enc_corr
+  uint64_t pos_vals, t_c2p, t_c2a, t_opp, t_d2c, t_v2d;
+  uint64_t ori;                    // u8[cap] per entry 0 / 2 / 3 (TexCoordsPortable's branch and orientation) -- k_enc_corr -> k_enc_orient
+  uint64_t flags;                  // u32[(cap + 31) / 32] side bits, bit k of the list: orientations (delta-coded against true, last
+                                   //   entry first; k_enc_orient) or flips (entry order; k_enc_corr) -- -> download (write_rabs)
+  uint32_t t_nc3, num_flags;       // 3F; OUTPUT: bits in `flags`
 };
 
 __device__ __forceinline__ uint32_t enc_msb(uint32_t v) { return 31u - (uint32_t)__builtin_clz(v); }
@@ -130,7 +139,7 @@ __global__ __launch_bounds__(256) void k_enc_quantize(uint8_t *arena, EncStream 
     const uint8_t *srcb = arena + S.src;
     const uint32_t total = S.rows * S.nc;
     for (uint32_t i = tid; i < total; i += stride) vals[i] = (int32_t)srcb[i];
-  } else {
+  } else if (S.kind == 1) {
     for (uint32_t v = tid; v < S.rows; v += stride) {
       int32_t s, t;
       enc_oct_from_float(src + (size_t)v * 3, (int32_t)S.bits, s, t);
@@ -144,6 +153,7 @@ __global__ __launch_bounds__(256) void k_enc_gather(uint8_t *arena, EncStream *s
   const uint32_t si = blockIdx.x;
   if (si >= ns) return;
   EncStream &S = streams[si];
+  if (S.kind == 3) return;
   __shared__ int32_t s_mn[256], s_mx[256];
   const int32_t *vals = (const int32_t *)(arena + S.vals);
   int32_t *d = (int32_t *)(arena + S.d);
@@ -168,6 +178,7 @@ __global__ __launch_bounds__(256) void k_enc_corr(uint8_t *arena, EncStream *str
   const uint32_t si = blockIdx.y;
   if (si >= ns) return;
   EncStream &S = streams[si];
+  if (S.kind == 3) return;                      // (a valence context list: k_enc_list_stats)
   __shared__ uint32_t s_tag[33];
   __shared__ uint32_t s_max;
   __shared__ unsigned long long s_bl;
@@ -193,14 +204,35 @@ __global__ __launch_bounds__(256) void k_enc_corr(uint8_t *arena, EncStream *str
   if ((max_dif & 1) == 0) max_corr -= 1;
   // octahedron
   const int32_t o_max_q = (1 << S.bits) - 1, o_center = (o_max_q - 1) / 2;
+  // TexCoordsPortable / GeometricNormal: positions and topology (dsa_encode_schemes.h)
+  const bool portable = S.kind == 0 && S.prediction == 5, geometric = S.kind == 1 && S.prediction == 6;
+  EncTopo T;
+  T.d = d; T.pos = (const int32_t *)(arena + S.pos_vals);
+  T.c2p = (const uint32_t *)(arena + S.t_c2p); T.c2a = (const uint32_t *)(arena + S.t_c2a); T.opp = (const uint32_t *)(arena + S.t_opp);
+  T.d2c = (const uint32_t *)(arena + S.t_d2c); T.v2d = (const int32_t *)(arena + S.t_v2d); T.nc3 = S.t_nc3;
+  uint8_t *ori = arena + S.ori;
+  uint32_t *flags = (uint32_t *)(arena + S.flags);
   for (uint32_t p = tid; p < S.nv; p += stride) {
     uint32_t mc = 0;
-    if (S.kind != 1) {
+    if (geometric) {
+      uint32_t sy[2];
+      bool flip = false;
+      if (!enc_geo_normal(T, p, (int32_t)S.bits, sy, flip)) { S.overflow = 1; sy[0] = sy[1] = 0; }
+      if (flip) atomicOr(&flags[p >> 5], 1u << (p & 31u));
+      for (uint32_t c = 0; c < 2; ++c) {
+        syms[2 * p + c] = sy[c];
+        if (sy[c] < S.hist_cap) atomicAdd(lds_hist ? &s_hist[sy[c]] : &hist[sy[c]], 1u); else S.overflow = 1;
+        mc = sy[c] > mc ? sy[c] : mc;
+      }
+    } else if (S.kind != 1) {
       int32_t vn = -1, vp = -1, vo = -1;
       if (S.prediction == 1 && p > 0) { vn = ops[3 * p]; vp = ops[3 * p + 1]; vo = ops[3 * p + 2]; }
+      int32_t tp[2] = {0, 0};
+      if (portable) { uint32_t o = 0; enc_tex_portable(T, p, tp, o); ori[p] = (uint8_t)o; }
       for (uint32_t c = 0; c < nc; ++c) {
         int32_t pred;
-        if (vn >= 0) pred = d[(size_t)vn * nc + c] + d[(size_t)vp * nc + c] - d[(size_t)vo * nc + c];
+        if (portable) pred = tp[c & 1u];
+        else if (vn >= 0) pred = d[(size_t)vn * nc + c] + d[(size_t)vp * nc + c] - d[(size_t)vo * nc + c];
         else pred = p > 0 ? d[(size_t)(p - 1) * nc + c] : 0;
         const int32_t pc = pred > mx ? mx : (pred < mn ? mn : pred);
         int32_t cr = d[(size_t)p * nc + c] - pc;
@@ -252,7 +284,7 @@ __global__ __launch_bounds__(WAVE) void k_enc_plan(uint8_t *arena, EncStream *st
   const uint32_t si = blockIdx.x * WAVE + threadIdx.x;
   if (si >= ns) return;
   EncStream &S = streams[si];
-  if (S.overflow) return;
+  if (S.overflow || (S.kind == 3 && S.nv == 0)) return;      // (an empty context list is not coded: its size 0 is all of it)
   if (S.max_value >= S.hist_cap) { S.overflow = 1; return; }
   const uint32_t *raw = (const uint32_t *)(arena + S.hist_raw);
   uint32_t *prob = (uint32_t *)(arena + S.prob), *cum = (uint32_t *)(arena + S.cum);
@@ -279,7 +311,7 @@ __global__ __launch_bounds__(WAVE) void k_enc_rans(uint8_t *arena, EncStream *st
   const uint32_t si = blockIdx.x, lane = threadIdx.x;
   if (si >= ns) return;
   EncStream &S = streams[si];
-  if (S.overflow) return;
+  if (S.overflow || (S.kind == 3 && S.nv == 0)) return;
   const uint32_t *prob = (const uint32_t *)(arena + S.prob), *cum = (const uint32_t *)(arena + S.cum);
   const uint32_t *syms = (const uint32_t *)(arena + S.syms);
   const uint8_t *bl = arena + S.bl;
@@ -355,6 +387,79 @@ __global__ __launch_bounds__(WAVE) void k_enc_rans(uint8_t *arena, EncStream *st
   S.bits_len = blen;
 }
 
+// Statistics of a valence context list (kind 3; its symbols are given): bit lengths, histograms, maximum -- what k_enc_corr
+// gathers for an attribute (symbol_stats of the host coder, nc = 1).  One block per stream.
+__global__ __launch_bounds__(256) void k_enc_list_stats(uint8_t *arena, EncStream *streams, uint32_t ns) {
+  const uint32_t si = blockIdx.x;
+  if (si >= ns) return;
+  EncStream &S = streams[si];
+  if (S.kind != 3 || S.overflow) return;
+  __shared__ uint32_t s_hist[8];
+  if (threadIdx.x < 8) s_hist[threadIdx.x] = 0;
+  __syncthreads();
+  const uint32_t *syms = (const uint32_t *)(arena + S.syms);
+  uint8_t *bl = arena + S.bl;
+  for (uint32_t p = threadIdx.x; p < S.nv; p += 256) {
+    const uint32_t v = syms[p] < 8u ? syms[p] : 7u;
+    bl[p] = (uint8_t)((v > 0 ? enc_msb(v) : 0u) + 1u);
+    atomicAdd(&s_hist[v], 1u);
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  uint32_t *hist = (uint32_t *)(arena + S.hist_raw);
+  unsigned long long total = 0;
+  for (uint32_t v = 0; v < 8; ++v) {
+    const uint32_t c = s_hist[v];
+    if (!c) continue;
+    if (v >= S.hist_cap) { S.overflow = 1; continue; }
+    hist[v] = c;
+    const uint32_t b = (v > 0 ? enc_msb(v) : 0u) + 1u;
+    S.hist_tag[b] += c;
+    total += (unsigned long long)c * b;
+    S.max_value = v;
+  }
+  S.total_bl = total;
+}
+
+// TexCoordsPortable's orientation bits (write_attribute_values, prediction 5): only the entries that took the full branch, last
+// entry first, each coded as "equal to the one before" (the first against true).  One wave per stream, 64 entries a round: the
+// kept lanes find their predecessor among the lower lanes of the round (or the round before) and set their bit at their place.
+__global__ __launch_bounds__(WAVE) void k_enc_orient(uint8_t *arena, EncStream *streams, uint32_t ns) {
+  const uint32_t si = blockIdx.x, lane = threadIdx.x;
+  if (si >= ns) return;
+  EncStream &S = streams[si];
+  if (S.kind != 0 || S.prediction != 5 || S.overflow) return;
+  const uint8_t *ori = arena + S.ori;
+  uint32_t *flags = (uint32_t *)(arena + S.flags);
+  const uint32_t nv = S.nv;
+  uint32_t base = 0;
+  bool carry = true;
+#if defined(__HIPCC__)
+  const uint64_t below = (1ull << lane) - 1ull;
+  for (uint32_t r0 = 0; r0 < nv; r0 += WAVE) {
+    const uint32_t r = r0 + lane;                     // the r-th entry from the end
+    const uint32_t o = r < nv ? ori[nv - 1u - r] : 0u;
+    const bool kept = o != 0u, val = o == 3u;
+    const uint64_t km = __ballot(kept), om = __ballot(kept && val);
+    const uint64_t lower = km & below;
+    const bool before = lower ? ((om >> (63 - __clzll(lower))) & 1ull) != 0 : carry;
+    if (kept && val == before) { const uint32_t at = base + (uint32_t)__popcll(lower); atomicOr(&flags[at >> 5], 1u << (at & 31u)); }
+    if (km) carry = ((om >> (63 - __clzll(km))) & 1ull) != 0;
+    base += (uint32_t)__popcll(km);
+  }
+#else
+  if (lane == 0)
+    for (uint32_t r = 0; r < nv; ++r) {
+      const uint32_t o = ori[nv - 1u - r];
+      if (!o) continue;
+      const bool val = o == 3u;
+      if (val == carry) flags[base >> 5] |= 1u << (base & 31u);
+      carry = val; ++base;
+    }
+#endif
+  if (lane == 0) S.num_flags = base;
+}
+
 }  // namespace dsa
 
 namespace dsa {
@@ -415,16 +520,48 @@ void dsa_encode_default_options(dsa_encode_options *o) {
   o->position_prediction = d.pos_prediction; o->texcoord_prediction = d.uv_prediction;
 }
 
-// Both entry points share one chunk path: `meshes` (dsa_encode_batch) or `corners` (dsa_encode_batch_corners), the other null.
-static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint32_t batch_n, const dsa_mesh_input *meshes, const dsa_mesh_corner_input *corners, const dsa_encode_options *options, dsa_encoded **out);
-static dsa_status encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_mesh_corner_input *corners, const dsa_encode_options *options, dsa_encoded **out);
+void dsa_encode_default_options_ex(dsa_encode_options_ex *o) {
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  dsa_encode_default_options(&o->base);
+}
+
+// All entry points share one chunk path: `meshes` (dsa_encode_batch) or `corners` (dsa_encode_batch_corners / _ex), the other
+// null; `ex` (dsa_encode_batch_ex) the schemes beyond standard Edgebreaker + difference / parallelogram, else null.
+static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint32_t batch_n, const dsa_mesh_input *meshes, const dsa_mesh_corner_input *corners, const dsa_encode_options *options, const dsa_encode_options_ex *ex, dsa_encoded **out);
+static dsa_status encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_mesh_corner_input *corners, const dsa_encode_options *options, const dsa_encode_options_ex *ex, dsa_encoded **out);
+// The prediction methods the device coder writes; any other value would put a method byte in front of data it does not describe.
+static dsa_status check_schemes(dsa_context *ctx, const dsa_encode_options *o, const dsa_encode_options_ex *ex) {
+  if (o && o->position_prediction != 0 && o->position_prediction != 1)
+    return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "position_prediction %d: the encoder writes 0 (difference) or 1 (parallelogram)", (int)o->position_prediction);
+  if (o && o->texcoord_prediction != 0 && o->texcoord_prediction != 1 && o->texcoord_prediction != 5)
+    return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "texcoord_prediction %d: the encoder writes 0 (difference), 1 (parallelogram) or 5 (TexCoordsPortable)", (int)o->texcoord_prediction);
+  if (!ex) return DSA_OK;
+  if (ex->edgebreaker_method != 0 && ex->edgebreaker_method != 2 && ex->edgebreaker_method != -1)
+    return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "edgebreaker_method %d: 0 (standard), 2 (valence) or -1 (by speed and face count)", (int)ex->edgebreaker_method);
+  if (ex->normal_prediction != 0 && ex->normal_prediction != 6)
+    return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "normal_prediction %d: 0 (difference) or 6 (GeometricNormal)", (int)ex->normal_prediction);
+  for (int k = 0; k < 6; ++k)
+    if (ex->reserved[k] != 0) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "dsa_encode_options_ex.reserved[%d] is not zero", k);
+  return DSA_OK;
+}
 dsa_status dsa_encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_encode_options *options, dsa_encoded **out) {
   if (!ctx || !out || (n && !meshes)) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "null argument");
-  DSA_GUARD(ctx, encode_batch(ctx, n, meshes, nullptr, options, out));     // host vectors and threads inside: nothing may unwind into the caller
+  if (check_schemes(ctx, options, nullptr) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+  DSA_GUARD(ctx, encode_batch(ctx, n, meshes, nullptr, options, nullptr, out));     // host vectors and threads inside: nothing may unwind into the caller
 }
 dsa_status dsa_encode_batch_corners(dsa_context *ctx, uint32_t n, const dsa_mesh_corner_input *meshes, const dsa_encode_options *options, dsa_encoded **out) {
   if (!ctx || !out || (n && !meshes)) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "null argument");
-  DSA_GUARD(ctx, encode_batch(ctx, n, nullptr, meshes, options, out));
+  if (check_schemes(ctx, options, nullptr) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+  DSA_GUARD(ctx, encode_batch(ctx, n, nullptr, meshes, options, nullptr, out));
+}
+dsa_status dsa_encode_batch_ex(dsa_context *ctx, uint32_t n, const dsa_mesh_corner_input *meshes, const dsa_encode_options_ex *options, dsa_encoded **out) {
+  if (!ctx || !out || (n && !meshes)) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "null argument");
+  dsa_encode_options_ex d;
+  dsa_encode_default_options_ex(&d);
+  if (options) d = *options;
+  if (check_schemes(ctx, &d.base, &d) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+  DSA_GUARD(ctx, encode_batch(ctx, n, nullptr, meshes, &d.base, &d, out));
 }
 // A batch is coded in chunks, several of them in flight (each on a lane of its own: stream + pinned staging + device memory).  The
 // device stages of a chunk are bound by latency -- the walks of k_enc_connectivity take a memory round trip per step, 0.1 - 0.2 s
@@ -434,7 +571,7 @@ dsa_status dsa_encode_batch_corners(dsa_context *ctx, uint32_t n, const dsa_mesh
 // those go first (phase A of every chunk in front of any phase B, hostutil::UploadTurns), the attribute values follow while the
 // walks run, on a stream of their own.  Streams of one priority share four hardware queues, on which the kernels of different
 // streams wait for each other: four lanes, their walk streams at another priority.  Small batches are one chunk.
-static dsa_status encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_mesh_corner_input *corners, const dsa_encode_options *options, dsa_encoded **out) {
+static dsa_status encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_mesh_corner_input *corners, const dsa_encode_options *options, const dsa_encode_options_ex *ex, dsa_encoded **out) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const uint32_t max_lanes = [&]() { const char *e = getenv("DSA_ENC_LANES"); const int v = e ? atoi(e) : 0; return (uint32_t)(v >= 1 && v <= 16 ? v : 4); }();
   const uint32_t chunk_max = [&]() { const char *e = getenv("DSA_ENC_CHUNK"); const int v = e ? atoi(e) : 0; return (uint32_t)(v >= 1 ? v : 0); }();
@@ -482,7 +619,7 @@ static dsa_status encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_inpu
         ctx->enc_lanes[l]->upload_chunk = c;
         dsa_encoded *part = nullptr;
         const auto t_chunk = std::chrono::steady_clock::now();
-        const dsa_status st = encode_chunk(&sink, *ctx->enc_lanes[l], cnt, n, meshes ? meshes + base : nullptr, corners ? corners + base : nullptr, options, &part);
+        const dsa_status st = encode_chunk(&sink, *ctx->enc_lanes[l], cnt, n, meshes ? meshes + base : nullptr, corners ? corners + base : nullptr, options, ex, &part);
         if (getenv("DSA_ENC_TIMING")) fprintf(stderr, "[dsa_encode_batch] chunk %u (%u meshes) returned after %8.2f ms\n", c, cnt, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_chunk).count());
         if (st != DSA_OK) { errs[l] = sink.err; int ok = DSA_OK; failed.compare_exchange_strong(ok, st); break; }
         std::unique_ptr<dsa_encoded> owner(part);
@@ -504,7 +641,7 @@ static dsa_status encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_inpu
   *out = E.release();
   return DSA_OK;
 }
-static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint32_t batch_n, const dsa_mesh_input *meshes_v, const dsa_mesh_corner_input *corners, const dsa_encode_options *options, dsa_encoded **out) {
+static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint32_t batch_n, const dsa_mesh_input *meshes_v, const dsa_mesh_corner_input *corners, const dsa_encode_options *options, const dsa_encode_options_ex *ex, dsa_encoded **out) {
   // mesh i of the chunk, whichever entry point it came through (ids: its corner ids, null without)
   struct MeshRef {
     const dsa_mesh_input *v; const dsa_mesh_corner_input *c;
@@ -521,6 +658,13 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
   opt.pos_bits = od.position_bits; opt.uv_bits = od.texcoord_bits; opt.normal_bits = od.normal_bits;
   opt.single_connectivity = od.single_connectivity; opt.force_scheme = od.symbol_scheme; opt.compression_level = od.compression_level;
   opt.pos_prediction = od.position_prediction; opt.uv_prediction = od.texcoord_prediction;
+  opt.normal_prediction = ex ? ex->normal_prediction : 0;
+  // valence symbols per mesh: asked for, or by the reference's rule (speed < 5 and not a tiny mesh)
+  const int32_t eb_method = ex ? ex->edgebreaker_method : 0;
+  auto valence_of = [&](uint32_t i) { return eb_method == 2 || (eb_method == -1 && opt.compression_level > 5 && meshes[i].num_faces >= 1000); };
+  // meshes of the chunk coded with valence symbols (the walks then record the start faces' times)
+  bool any_valence = false;
+  for (uint32_t i = 0; i < n; ++i) any_valence = any_valence || valence_of(i);
   dsa_encoded *E = new (std::nothrow) dsa_encoded();
   if (!E) return set_err(ctx, DSA_ERR_OUT_OF_MEMORY, "host allocation failed");
   std::unique_ptr<dsa_encoded> E_owner(E);      // released into *out at the very end; every other exit frees it
@@ -534,6 +678,9 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
   // attributes given per corner, host connectivity: per attribute its own entry -> value row, and its own operands when it is seamed
   std::vector<std::vector<std::vector<uint32_t>>> att_e2v(n);
   std::vector<std::vector<std::vector<int32_t>>> att_ops(n);
+  std::vector<std::vector<std::vector<uint32_t>>> att_opp(n);       // the same, prediction 5 / 6 of a seamed attribute: its table's opposites
+  // attribute k of plan `pl` reads the mesh's topology (TexCoordsPortable, GeometricNormal)
+  auto topo_scheme = [](const synth::PortableAttr &a) { return (a.seq_type == 2 && a.prediction == 5) || (a.seq_type == 3 && a.prediction == 6); };
   // DSA_ENC_TIMING=1 (diagnostics): wall time of every phase on stderr
   static const bool timing = getenv("DSA_ENC_TIMING") != nullptr;
   auto t_last = std::chrono::steady_clock::now();
@@ -572,6 +719,7 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
       synth::check(host_conn || (uint64_t)m.num_faces * 3 <= (uint64_t)dsa::EC_CORNER_MASK, "mesh too large for the device connectivity coder");
       synth::Options mo = opt;                                   // (the components of the generic attribute are the mesh's own)
       mo.generic_components = in.generic ? (int32_t)m.generic_components : 1;
+      mo.predictive_connectivity = valence_of(i) ? 2 : 0;
       if (!host_conn) {                                          // the rest of the plan comes from the device
         synth::check(!((in.normal_corners || in.uv_corners) && opt.single_connectivity), "attributes given per corner need a connectivity of their own (single_connectivity = 0)");
         synth::check(!(in.normal_corners || in.uv_corners) || 24ull * m.num_faces + 16u < (1ull << 32), "mesh too large for the device connectivity coder");
@@ -587,6 +735,13 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
         if (!ids) continue;
         if (pl.seamed(k)) dsa::entry_maps(pl.conns[k], pl.seq_att[k], ids, att_e2v[i][k], &att_ops[i][k]);
         else dsa::entry_maps(pl.ct, pl.seq, ids, att_e2v[i][k], nullptr);      // (the positions' operands)
+      }
+      att_opp[i].assign(pl.atts.size(), {});
+      for (size_t k = 1; k < pl.atts.size(); ++k) {
+        if (!pl.seamed(k) || !topo_scheme(pl.atts[k])) continue;
+        std::vector<uint32_t> &o = att_opp[i][k];
+        o.resize(pl.ct.nc());
+        for (uint32_t c = 0; c < pl.ct.nc(); ++c) o[c] = pl.conns[k].opposite(c);
       }
     } catch (const std::exception &e) { E->status[i] = DSA_ERR_INVALID_DATA; E->messages[i] = e.what(); }
   };
@@ -618,6 +773,17 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
       if (host_conn) { const uint64_t ent = att_e2v[i][k].size(); in_total += al(4 * ent) + (att_ops[i][k].empty() ? 0 : al(12 * ent)); }
       else in_total += al((ids_narrow(i, a) ? 6 : 12) * F);          // the ids travel with the faces, narrowed like them
     }
+    if (!host_conn) continue;
+    // host connectivity: the topology of TexCoordsPortable / GeometricNormal and the valence context lists travel too
+    const synth::MeshPlan &pl = plans[i];
+    bool needs_topo = false;
+    for (size_t k = 0; k < pl.atts.size(); ++k) {
+      needs_topo = needs_topo || topo_scheme(pl.atts[k]);
+      if (topo_scheme(pl.atts[k]) && pl.atts[k].corner_value && pl.seamed(k))
+        in_total += 2 * al(4 * pl.conns[k].c2v.size()) + 2 * al(4 * pl.seq_att[k].data_to_corner.size());
+    }
+    if (needs_topo) in_total += 2 * al(4 * pl.ct.c2v.size()) + 2 * al(4 * pl.seq.data_to_corner.size());
+    if (pl.valence) for (int k = 0; k < 6; ++k) in_total += al(4 * pl.ctx_symbols[k].size());
   }
   uint64_t cur = in_total, cur_in = 0;
   auto take = [&](uint64_t bytes) { uint64_t at = cur; cur = (cur + bytes + 255) & ~255ull; return at; };
@@ -665,7 +831,23 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
       C.symbols = take(F); C.start_bits = take(F); C.splits = take(12ull * C.split_cap);
       C.d2c = take(4ull * V); C.v2d = take(4ull * V);
       C.e2v = o_e2v; C.ops = o_ops;
+      C.vstream = DSA_INVALID;
+      if (valence_of(i)) {
+        C.init_time = take(4ull * F); C.vtime = take(4ull * F); C.vval = take(4ull * ((uint64_t)V + F)); C.vc2v = take(12ull * F);
+        C.vctx = take(F); C.vsyms = take(4ull * F); C.vbl = take(F); C.vrans = take(4ull * F + 96); C.vbits = take(4ull * F + 96);
+      }
     }
+    // TexCoordsPortable / GeometricNormal: the position table and order (device: the connectivity's; host: uploaded once per mesh)
+    uint64_t t_c2v = 0, t_opp = 0, t_d2c = 0, t_v2d = 0;
+    bool needs_topo = false;
+    for (const synth::PortableAttr &a : plans[i].atts) needs_topo = needs_topo || topo_scheme(a);
+    if (needs_topo && host_conn) {
+      const synth::MeshPlan &pl = plans[i];
+      t_c2v = take_in(4ull * pl.ct.c2v.size()); uploads.push_back({t_c2v, pl.ct.c2v.data(), 4ull * pl.ct.c2v.size(), false});
+      t_opp = take_in(4ull * pl.ct.opp.size()); uploads.push_back({t_opp, pl.ct.opp.data(), 4ull * pl.ct.opp.size(), false});
+      t_d2c = take_in(4ull * pl.seq.data_to_corner.size()); uploads.push_back({t_d2c, pl.seq.data_to_corner.data(), 4ull * pl.seq.data_to_corner.size(), false});
+      t_v2d = take_in(4ull * pl.seq.vertex_to_data.size()); uploads.push_back({t_v2d, pl.seq.vertex_to_data.data(), 4ull * pl.seq.vertex_to_data.size(), false});
+    } else if (needs_topo) { t_c2v = hc[i].faces; t_opp = hc[i].opp; t_d2c = hc[i].d2c; t_v2d = hc[i].v2d; }
     for (size_t k = 0; k < plans[i].atts.size(); ++k) {
       const synth::PortableAttr &a = plans[i].atts[k];
       dsa::EncStream S;
@@ -709,7 +891,43 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
       const uint64_t table_cap = std::max<uint64_t>(S.hist_cap, 64);   // the tagged scheme's alphabet is 33 bit lengths
       S.prob = take(4ull * table_cap); S.cum = take(4ull * table_cap);
       S.plan_order = take(4ull * table_cap); S.plan_tmp = take(4ull * table_cap);
+      if (topo_scheme(a)) {
+        S.pos_vals = hs[first_stream[i]].vals;                  // (the positions are attribute 0: their stream is the mesh's first)
+        S.t_c2p = S.t_c2a = t_c2v; S.t_opp = t_opp; S.t_d2c = t_d2c; S.t_v2d = t_v2d;
+        S.t_nc3 = 3u * meshes[i].num_faces;
+        if (host_conn && a.corner_value && plans[i].seamed(k)) {             // a seamed attribute's own table and order
+          const synth::MeshPlan &pl = plans[i];
+          const std::vector<uint32_t> &c2a = pl.conns[k].c2v, &o2 = att_opp[i][k], &d2c = pl.seq_att[k].data_to_corner;
+          const std::vector<int32_t> &v2d = pl.seq_att[k].vertex_to_data;
+          S.t_c2a = take_in(4ull * c2a.size()); uploads.push_back({S.t_c2a, c2a.data(), 4ull * c2a.size(), false});
+          S.t_opp = take_in(4ull * o2.size()); uploads.push_back({S.t_opp, o2.data(), 4ull * o2.size(), false});
+          S.t_d2c = take_in(4ull * d2c.size()); uploads.push_back({S.t_d2c, d2c.data(), 4ull * d2c.size(), false});
+          S.t_v2d = take_in(4ull * v2d.size()); uploads.push_back({S.t_v2d, v2d.data(), 4ull * v2d.size(), false});
+        }
+        if (a.seq_type == 2) S.ori = take(cap);
+        S.flags = take(4ull * ((cap + 31) / 32));
+      }
       hs.push_back(S);
+    }
+    // valence symbols: six more streams, the context lists (kind 3, one component, alphabet C S L R E).  Device connectivity: the
+    // lists' sizes and places are set by k_enc_val_split in the mesh's regions; host connectivity: the host coder's lists, uploaded.
+    if (valence_of(i)) {
+      if (!host_conn) hc[i].vstream = (uint32_t)hs.size();
+      for (int k = 0; k < 6; ++k) {
+        dsa::EncStream S;
+        memset(&S, 0, sizeof(S));
+        S.kind = 3; S.nc = S.nc_out = 1; S.bits = 3; S.hist_cap = 8;
+        S.hist_raw = take(4ull * S.hist_cap);
+        S.prob = take(4ull * 64); S.cum = take(4ull * 64); S.plan_order = take(4ull * 64); S.plan_tmp = take(4ull * 64);
+        if (host_conn) {
+          const std::vector<uint32_t> &list = plans[i].ctx_symbols[k];
+          const uint32_t cnt = (uint32_t)list.size();
+          S.nv = cnt;
+          if (cnt) { S.syms = take_in(4ull * cnt); uploads.push_back({S.syms, list.data(), 4ull * cnt, false}); }
+          S.bl = take(cnt); S.out_cap = 4u * cnt + 16u; S.out_rans = take(S.out_cap); S.out_bits = take(S.out_cap);
+        }
+        hs.push_back(S);
+      }
     }
   }
   first_stream[n] = (uint32_t)hs.size();
@@ -817,7 +1035,7 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
       // the walks on their stream; the attribute values travel and are quantised meanwhile
       ENC_TRY(hipEventRecord(lane.tables_done, st));
       ENC_TRY(hipStreamWaitEvent(lane.walk_st, lane.tables_done, 0));
-      hipLaunchKernelGGL(dsa::k_enc_connectivity, dim3((n + walk_lanes - 1) / walk_lanes), dim3(WAVE), 0, lane.walk_st, arena, d_conns, n, walk_lanes);
+      hipLaunchKernelGGL(any_valence ? dsa::k_enc_connectivity_timed : dsa::k_enc_connectivity, dim3((n + walk_lanes - 1) / walk_lanes), dim3(WAVE), 0, lane.walk_st, arena, d_conns, n, walk_lanes);
       if (nz) {
         // attributes given per corner: seams and attribute vertices beside the connectivity walk, the attribute walks behind it
         ENC_TRY(lane.seams.ensure(sizeof(dsa::EncSeam) * nz));
@@ -833,6 +1051,12 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
         ENC_TRY(hipStreamWaitEvent(lane.walk_st, lane.seams_done, 0));
         hipLaunchKernelGGL(dsa::k_enc_seam_walk, dim3((nz + walk_lanes - 1) / walk_lanes), dim3(WAVE), 0, lane.walk_st, arena, d_conns, d_seams, nz, walk_lanes);
       }
+      if (any_valence) {
+        // valence context lists behind the walks, on their stream: one more serial pass per mesh, then the lists into six streams
+        hipLaunchKernelGGL(dsa::k_enc_val_init, gt, dim3(256), 0, lane.walk_st, arena, d_conns, n);
+        hipLaunchKernelGGL(dsa::k_enc_valence, dim3((n + walk_lanes - 1) / walk_lanes), dim3(WAVE), 0, lane.walk_st, arena, d_conns, n, walk_lanes);
+        hipLaunchKernelGGL(dsa::k_enc_val_split<dsa::EncStream>, dim3(n), dim3(WAVE), 0, lane.walk_st, arena, d_conns, n, d_streams);
+      }
       ENC_TRY(hipEventRecord(lane.walk_done, lane.walk_st));
       turn.release();
       turn.acquire_b();
@@ -845,6 +1069,7 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
       if (nz) {
         const dim3 gz(gt.x, nz);
         hipLaunchKernelGGL(dsa::k_enc_seam_operands<dsa::EncStream>, gz, dim3(256), 0, st, arena, d_conns, d_seams, nz, d_streams);
+        hipLaunchKernelGGL(dsa::k_enc_seam_topo<dsa::EncStream>, dim3((nz + 255) / 256), dim3(256), 0, st, d_conns, d_seams, nz, d_streams);
         hipLaunchKernelGGL(dsa::k_enc_seam_rank, gz, dim3(256), 0, st, arena, d_conns, d_seams, nz);
         hipLaunchKernelGGL(dsa::k_enc_seam_count, gz, dim3(256), 0, st, arena, d_conns, d_seams, nz);
         hipLaunchKernelGGL(dsa::k_enc_seam_scan, dim3(nz), dim3(WAVE), 0, st, arena, d_conns, d_seams, nz);
@@ -857,6 +1082,8 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
     // ---- device phase 1: quantise, order, correct, count
     hipLaunchKernelGGL(dsa::k_enc_gather, dim3(ns), dim3(256), 0, st, arena, d_streams, ns);
     hipLaunchKernelGGL(dsa::k_enc_corr, dim3(gx, ns), dim3(256), 0, st, arena, d_streams, ns);
+    hipLaunchKernelGGL(dsa::k_enc_orient, dim3(ns), dim3(WAVE), 0, st, arena, d_streams, ns);
+    hipLaunchKernelGGL(dsa::k_enc_list_stats, dim3(ns), dim3(256), 0, st, arena, d_streams, ns);
     if (!host_plan) {       // device phase 2 follows at once: tables by k_enc_plan, no host round trip
       hipLaunchKernelGGL(dsa::k_enc_plan, dim3((ns + WAVE - 1) / WAVE), dim3(WAVE), 0, st, arena, d_streams, ns, (int)opt.force_scheme, (int)opt.compression_level);
       hipLaunchKernelGGL(dsa::k_enc_rans, dim3(ns), dim3(WAVE), 0, st, arena, d_streams, ns);
@@ -937,6 +1164,7 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
   {
     std::vector<dsa::PackItem> items;
     for (uint32_t s = 0; s < ns; ++s) {
+      if (hs[s].kind == 3 && hs[s].nv == 0) continue;
       if (hs[s].overflow || hs[s].max_value >= hs[s].hist_cap) { hs[s].overflow = 1; continue; }
       items.push_back({hs[s].hist_raw, 0, 4u * (hs[s].max_value + 1u), s});
     }
@@ -950,7 +1178,7 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
   std::vector<std::string> plan_error(ns);
   auto plan_stream = [&](uint32_t s) {
     const uint32_t i = (uint32_t)stream_mesh[s];
-    if (E->status[i] != DSA_OK) return;
+    if (E->status[i] != DSA_OK || (hs[s].kind == 3 && hs[s].nv == 0)) return;
     try {
       synth::check(!hs[s].overflow, "symbol outside the histogram range");
       synth::SymbolStats stt;
@@ -992,7 +1220,7 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
   }
   lap("histograms + symbol plans");
   // ---- device phase 2: entropy coding
-  std::vector<std::vector<uint8_t>> rans(ns), bits(ns);
+  std::vector<std::vector<uint8_t>> rans(ns), bits(ns), flag_bits(ns);
   if (ns) {
     hipStream_t st = lane.st;
     if (host_plan) {
@@ -1002,21 +1230,30 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
       ENC_TRY(hipStreamSynchronize(st));
     }
     // coded bytes of every stream (and, when k_enc_plan made them, the probability tables: the stream carries them)
+    // and the side bits of TexCoordsPortable / GeometricNormal, packed
     std::vector<dsa::PackItem> items;
     for (uint32_t s = 0; s < ns; ++s) {
       if (hs[s].overflow || E->status[stream_mesh[s]] != DSA_OK) continue;
+      if (hs[s].kind == 1 && hs[s].prediction == 6) hs[s].num_flags = hs[s].nv;
       items.push_back({hs[s].out_rans, 0, hs[s].rans_len, s});
       items.push_back({hs[s].out_bits, 0, hs[s].bits_len, s});
       items.push_back({hs[s].prob, 0, host_plan ? 0u : 4u * hs[s].num_symbols, s});
+      items.push_back({hs[s].flags, 0, hs[s].flags ? 4u * ((hs[s].num_flags + 31u) / 32u) : 0u, s});
     }
     std::vector<uint8_t> unused;
     const uint8_t *host = nullptr;
     ENC_ST(gather(items, unused, &host));
-    hostutil::parallel_for((uint32_t)(items.size() / 3), [&](uint32_t m) {
-      const size_t k = 3 * (size_t)m;
+    hostutil::parallel_for((uint32_t)(items.size() / 4), [&](uint32_t m) {
+      const size_t k = 4 * (size_t)m;
       const uint32_t s = items[k].pad;
       if (items[k].len) rans[s].assign(host + items[k].packed_off, host + items[k].packed_off + items[k].len);
       if (items[k + 1].len) bits[s].assign(host + items[k + 1].packed_off, host + items[k + 1].packed_off + items[k + 1].len);
+      if (hs[s].flags) {
+        const uint32_t *words = (const uint32_t *)(host + items[k + 3].packed_off);
+        flag_bits[s].resize(hs[s].num_flags);
+        for (uint32_t e = 0; e < hs[s].num_flags; ++e) flag_bits[s][e] = (uint8_t)((words[e >> 5] >> (e & 31u)) & 1u);
+      }
+      if (hs[s].kind == 3 && hs[s].nv == 0) return;
       if (!host_plan) {                      // the bytes in front of the payload: scheme, (raw: unique-symbols bit length), table
         synth::SymbolPlan &pl = splans[s];
         pl.method = (int)hs[s].method;
@@ -1037,23 +1274,41 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
   auto layout_one = [&](uint32_t i) {
     if (E->status[i] != DSA_OK) return;
     bool bad = false;
-    for (uint32_t s = first_stream[i]; s < first_stream[i + 1]; ++s) bad = bad || hs[s].overflow;
+    for (uint32_t s = first_stream[i]; s < first_stream[i + 1]; ++s) bad = bad || hs[s].overflow;     // (the context lists included)
     if (bad) { E->status[i] = DSA_ERR_INVALID_DATA; E->messages[i] = "entropy coding failed"; return; }
     synth::ByteWriter w;
     const uint32_t s0 = first_stream[i];
+    // a symbol stream as encode_symbols writes it: scheme and table, coded bytes, (tagged) the raw bit fields
+    auto coded = [&](synth::ByteWriter &bw, uint32_t s) {
+      bw.bytes(splans[s].head.d);
+      bw.varint(rans[s].size());
+      bw.bytes(rans[s]);
+      if (hs[s].method == 0) bw.bytes(bits[s]);
+    };
     try {
-    synth::write_stream(w, ins[i], plans[i],
+    synth::MeshPlan &pl = plans[i];
+    if (pl.valence) {                                        // the six context lists: their streams follow the attributes'
+      const uint32_t v0 = s0 + (uint32_t)pl.atts.size();
+      pl.ctx_given = true;
+      for (uint32_t k = 0; k < 6; ++k) {
+        pl.ctx_count[k] = hs[v0 + k].nv;
+        synth::ByteWriter bw;
+        if (hs[v0 + k].nv) coded(bw, v0 + k);
+        pl.ctx_coded[k].swap(bw.d);
+      }
+    }
+    synth::write_stream(w, ins[i], pl,
       [&](synth::ByteWriter &bw, size_t k) {               // SequentialIntegerAttributeEncoder.cs:55-128
         const dsa::EncStream &S = hs[s0 + k];
-        const synth::PortableAttr &a = plans[i].atts[k];
-        if (S.kind == 1) { bw.i8(0); bw.i8(3); } else { bw.i8((int8_t)a.prediction); bw.i8(1); }
+        const synth::PortableAttr &a = pl.atts[k];
+        const bool geometric = S.kind == 1 && S.prediction == 6, portable = S.kind == 0 && S.prediction == 5;
+        if (S.kind == 1) { bw.i8(geometric ? 6 : 0); bw.i8(3); } else { bw.i8((int8_t)a.prediction); bw.i8(1); }
         bw.u8(1);
-        bw.bytes(splans[s0 + k].head.d);
-        bw.varint(rans[s0 + k].size());
-        bw.bytes(rans[s0 + k]);
-        if (S.method == 0) bw.bytes(bits[s0 + k]);
+        coded(bw, s0 + (uint32_t)k);
+        if (portable) { bw.i32((int32_t)flag_bits[s0 + k].size()); synth::write_rabs(bw, flag_bits[s0 + k]); }
         if (S.kind == 1) { const int32_t max_q = (1 << S.bits) - 1; bw.i32(max_q); bw.i32((max_q - 1) / 2); }
         else { bw.i32(S.wrap_mn); bw.i32(S.wrap_mx); }
+        if (geometric) synth::write_rabs(bw, flag_bits[s0 + k]);
       },
       [&](synth::ByteWriter &bw, size_t k) {               // AttributeQuantizationTransform.cs:123-134 / AttributeOctahedronTransform.cs:44-47
         const dsa::EncStream &S = hs[s0 + k];

@@ -35,6 +35,11 @@ struct EncConn {                   // one per mesh; device memory, mirrored on t
   uint32_t fail_key;               // k_enc_table_corners: the least status code that any vertex earned (the host coder's order of checks), or ~0
   uint32_t num_symbols, num_start_bits, num_splits, num_split_symbols, num_processed, num_init, num_entries, interior_edges;   // OUTPUT
   uint32_t status, detail;         // 0 ok; else the host coder's complaint (see enc_conn_message)
+  // valence context lists (dsa_encode_schemes.h, which lists the regions with their writers and readers); vstream: the first of
+  // the mesh's six list streams, DSA_INVALID for a mesh coded with standard symbols (all regions then 0)
+  uint64_t init_time, vtime, vval, vc2v, vctx, vsyms, vbl, vrans, vbits;
+  uint32_t vstream;
+  uint32_t vcount[6];              // OUTPUT of k_enc_valence: symbols per context
 };
 // A face as the walks see it: the vertices at its corners, the corners across its edges (o[k] = opposite of corner 3f + k), and two
 // marks -- mark: 0 not visited by the Edgebreaker walk; 1 visited; s + 2 visited, and the S with symbol id s was coded at it (what
@@ -312,7 +317,10 @@ __device__ __forceinline__ uint32_t ec_dfs_walk(const uint4 *frec, uint32_t *fw,
 // the compiler's rules; meshes of one shape (a batch of scans of one kind) step in lockstep.
 // Every walk below ends by itself on a mesh that passed the checks above (the host coder, which has no such counter, was fuzzed
 // with 20 000 damaged meshes); the counter only makes sure that a kernel can never spin: a GPU does not take Ctrl-C.
-__global__ __launch_bounds__(WAVE) void k_enc_connectivity(uint8_t *arena, EncConn *conns, uint32_t n, uint32_t lanes_per_wave) {
+// record_time (k_enc_connectivity_timed): the walk also records, per interior start face, how many symbols were coded before it
+// (init_time; what the valence pass needs of the host coder's face_time beside the order of `processed`).
+template <bool record_time>
+__device__ __forceinline__ void ec_connectivity(uint8_t *arena, EncConn *conns, uint32_t n, uint32_t lanes_per_wave) {
   if (threadIdx.x >= lanes_per_wave) return;
   const uint32_t mesh = blockIdx.x * lanes_per_wave + threadIdx.x;
   if (mesh >= n) return;
@@ -447,6 +455,7 @@ __global__ __launch_bounds__(WAVE) void k_enc_connectivity(uint8_t *arena, EncCo
       if (interior_face) {
         vvis[c2v[start]] |= 1; vvis[c2v[ec_next(start)]] |= 1; vvis[c2v[ec_prev(start)]] |= 1;
         fw[8 * face + EC_MARK] = 1u;
+        if (record_time && E->init_time) ((uint32_t *)(arena + E->init_time))[ninit] = nproc;
         init_corners[ninit++] = ec_next(start);
         const uint32_t o = opp[ec_next(start)];
         if (o != DSA_INVALID && fw[8 * (o / 3u) + EC_MARK] == 0) encode_from_corner(o);
@@ -469,6 +478,13 @@ __global__ __launch_bounds__(WAVE) void k_enc_connectivity(uint8_t *arena, EncCo
   E->num_entries = count;
   if (stuck) ec_fail(E, ENC_RING, count);
   else if (count != V) ec_fail(E, ENC_UNREACHED, count);
+}
+__global__ __launch_bounds__(WAVE) void k_enc_connectivity(uint8_t *arena, EncConn *conns, uint32_t n, uint32_t lanes_per_wave) {
+  ec_connectivity<false>(arena, conns, n, lanes_per_wave);
+}
+// the same for a chunk with meshes coded with valence symbols (dsa_encode_schemes.h)
+__global__ __launch_bounds__(WAVE) void k_enc_connectivity_timed(uint8_t *arena, EncConn *conns, uint32_t n, uint32_t lanes_per_wave) {
+  ec_connectivity<true>(arena, conns, n, lanes_per_wave);
 }
 
 // ---- the symbols as bytes; entry -> vertex and the parallelogram operand entries of every entry (MeshPredictionSchemeParallelogramEncoder.cs:35-56)

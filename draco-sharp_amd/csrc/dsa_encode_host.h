@@ -1160,6 +1160,10 @@ struct MeshPlan {
   int force_scheme = -1, compression_level = 5;
   bool valence = false;              // valence Edgebreaker traversal: six context symbol lists
   std::vector<uint32_t> ctx_symbols[6];
+  // The same coded elsewhere (the device encoder): per list its symbol count and its bytes as encode_symbols writes them
+  bool ctx_given = false;
+  uint32_t ctx_count[6] = {0, 0, 0, 0, 0, 0};
+  std::vector<uint8_t> ctx_coded[6];
   bool predictive = false;           // predictive Edgebreaker traversal: explicit symbols + prediction bits below
   std::vector<uint8_t> explicit_symbols, predictions;   // encoder order
   // Attributes given per corner: conns[att] is the attribute's own connectivity, seq_att[att] its depth-first order
@@ -1301,6 +1305,7 @@ static void write_stream(ByteWriter &w, const MeshIn &in, const MeshPlan &pl, Va
     }
     if (pl.valence)        // MeshEdgeBreakerTraversalValenceDecoder.cs:43-68: the six context lists, each through the symbol coder
       for (int i = 0; i < 6; ++i) {
+        if (pl.ctx_given) { w.varint(pl.ctx_count[i]); w.bytes(pl.ctx_coded[i]); continue; }
         w.varint(pl.ctx_symbols[i].size());
         if (!pl.ctx_symbols[i].empty()) encode_symbols(w, pl.ctx_symbols[i], 1, pl.force_scheme, pl.compression_level);
       }

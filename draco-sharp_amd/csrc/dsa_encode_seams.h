@@ -22,13 +22,14 @@ struct EncSeam {                   // one per (mesh, attribute given per corner)
   uint64_t edge_seam, vert_seam;   // u8[3F] edge across corner cut (seam or boundary), u8[V] vertex on a cut -- k_enc_seam_edges -> k_enc_seam_bits / k_enc_seam_fans
   uint64_t afirst, aoff;           // u32[V] first corner of a vertex's fans, u32[V+1] attribute vertex ids per position vertex (scan)
                                    //   -- k_enc_seam_fans, k_enc_seam_offsets -> k_enc_seam_assign
-  uint64_t c2av, opp2, v2lm;       // u32[3F] attribute vertex per corner -- k_enc_seam_assign -> k_enc_seam_operands; u32[3F] opposite cut at
-                                   //   seams -- k_enc_seam_records -> k_enc_seam_operands; u32[3F] left-most corner per attribute vertex
+  uint64_t c2av, opp2, v2lm;       // u32[3F] attribute vertex per corner -- k_enc_seam_assign -> k_enc_seam_operands, k_enc_corr (prediction 5
+                                   //   / 6); u32[3F] opposite cut at seams -- k_enc_seam_records -> k_enc_seam_operands, k_enc_corr (the
+                                   //   ring of GeometricNormal, the neighbours of TexCoordsPortable); u32[3F] left-most corner per attribute vertex
                                    //   -- k_enc_seam_assign -> (the host check; AttrConn::v2lm)
   uint64_t avis, frec;             // u8[3F] attribute vertex marks (2 boundary, 4 visited), EcFace[F] the attribute's face records
                                    //   -- k_enc_seam_records -> k_enc_seam_walk
   uint64_t stack, d2c, v2d;        // u32[F] walk stack -- k_enc_seam_walk only; u32[3F], i32[3F] entries -- k_enc_seam_walk (v2d: -1 by
-                                   //   k_enc_seam_assign) -> k_enc_seam_operands
+                                   //   k_enc_seam_assign) -> k_enc_seam_operands, k_enc_corr (prediction 5 / 6)
   uint64_t e2v, ops;               // u32[3F] value row per entry, i32[9F] operand entries (the stream's own) -- k_enc_seam_operands -> k_enc_gather / k_enc_corr
   uint64_t rank, rcorner, eoff;    // u32[F] decoder rank of a face, u32[F] corner at a rank -- k_enc_seam_rank -> k_enc_seam_bits;
                                    //   u32[F+1] seam-bit offset per rank -- k_enc_seam_count, k_enc_seam_scan -> k_enc_seam_bits

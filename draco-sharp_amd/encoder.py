@@ -17,15 +17,43 @@ from .decoder import DeviceException, _raise, default_context
 
 
 class Config:
-    """Subset of src/Draco/IO/Config.cs that the device path honours."""
+    """Subset of src/Draco/IO/Config.cs that the device path honours.
+
+    The method ids are the format's own: edgebreaker_method 0 standard, 2 valence, -1 the reference's rule per mesh (valence at
+    speed < 5 for meshes of 1000 faces or more); position_prediction 0 difference, 1 parallelogram; texcoord_prediction also 5
+    TexCoordsPortable; normal_prediction 0 difference, 6 GeometricNormal.  Defaults write what the speed-5 default writes."""
+
+    EDGEBREAKER_METHODS = (0, 2, -1)
+    POSITION_PREDICTIONS = (0, 1)
+    TEXCOORD_PREDICTIONS = (0, 1, 5)
+    NORMAL_PREDICTIONS = (0, 6)
 
     def __init__(self, position_bits=11, texcoord_bits=10, normal_bits=8, speed=5, single_connectivity=False,
-                 symbol_scheme=-1, position_prediction=1, texcoord_prediction=1):
+                 symbol_scheme=-1, position_prediction=1, texcoord_prediction=1, edgebreaker_method=0, normal_prediction=0):
+        for name, value, legal in (("edgebreaker_method", edgebreaker_method, self.EDGEBREAKER_METHODS),
+                                   ("position_prediction", position_prediction, self.POSITION_PREDICTIONS),
+                                   ("texcoord_prediction", texcoord_prediction, self.TEXCOORD_PREDICTIONS),
+                                   ("normal_prediction", normal_prediction, self.NORMAL_PREDICTIONS)):
+            if value not in legal:
+                raise ValueError("%s %r: the encoder writes one of %s" % (name, value, legal))
         self.position_bits, self.texcoord_bits, self.normal_bits = position_bits, texcoord_bits, normal_bits
         self.speed = speed                      # compression level = 10 - speed (DracoEncoder.cs:50-56)
         self.single_connectivity = single_connectivity
         self.symbol_scheme = symbol_scheme
         self.position_prediction, self.texcoord_prediction = position_prediction, texcoord_prediction
+        self.edgebreaker_method, self.normal_prediction = edgebreaker_method, normal_prediction
+
+    @property
+    def extended(self):
+        """True when an option only dsa_encode_batch_ex takes is set."""
+        return self.edgebreaker_method != 0 or self.normal_prediction != 0
+
+    def _native_ex(self):
+        o = native.EncodeOptionsEx()
+        native.lib().dsa_encode_default_options_ex(C.byref(o))
+        o.base = self._native()
+        o.edgebreaker_method, o.normal_prediction = self.edgebreaker_method, self.normal_prediction
+        return o
 
     def _native(self):
         o = native.EncodeOptions()
@@ -148,8 +176,11 @@ class DracoEncoder:
         ctx = self._ctx or default_context()
         L = native.lib()
         n = len(meshes)
-        # the corner entry point only when some mesh carries ids; otherwise exactly the per-vertex call
-        corners = any(getattr(m, "per_corner", False) for m in meshes)
+        config = config or Config()
+        ex = config.extended
+        # the corner entry point only when some mesh carries ids (or an option needs dsa_encode_batch_ex, which takes the corner
+        # form); otherwise exactly the per-vertex call
+        corners = ex or any(getattr(m, "per_corner", False) for m in meshes)
         arr = ((native.MeshCornerInput if corners else native.MeshInput) * max(1, n))()
         for i, m in enumerate(meshes):
             mi = arr[i].mesh if corners else arr[i]
@@ -166,10 +197,11 @@ class DracoEncoder:
                 arr[i].texcoord_corners = uci.ctypes.data if uci is not None else None
                 arr[i].num_normals = len(m.normals) if m.normals is not None else 0
                 arr[i].num_texcoords = len(m.texcoords) if m.texcoords is not None else 0
-        opt = (config or Config())._native()
+        opt = config._native_ex() if ex else config._native()
         h = C.c_void_p()
         t0 = time.perf_counter()
-        st = (L.dsa_encode_batch_corners if corners else L.dsa_encode_batch)(ctx._h, n, arr, C.byref(opt), C.byref(h))
+        entry = L.dsa_encode_batch_ex if ex else (L.dsa_encode_batch_corners if corners else L.dsa_encode_batch)
+        st = entry(ctx._h, n, arr, C.byref(opt), C.byref(h))
         t1 = time.perf_counter()
         if st != 0:
             _raise(st, ctx.error())

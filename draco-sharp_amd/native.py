@@ -22,7 +22,8 @@ EXPORTS = [
     "dsa_batch_device_point_map", "dsa_batch_output_bytes", "dsa_batch_download", "dsa_batch_compact_bytes", "dsa_batch_download_compact", "dsa_batch_host_output", "dsa_batch_output_layout",
     "dsa_host_alloc", "dsa_host_free", "dsa_host_register", "dsa_host_unregister", "dsa_batch_copy_metadata", "dsa_batch_copy_debug", "dsa_context_set_profiling", "dsa_batch_stage_times",
     "dsa_batch_kernel_times", "dsa_context_trim", "dsa_context_schedule_note",
-    "dsa_encode_default_options", "dsa_encode_batch", "dsa_encode_batch_corners", "dsa_encoded_size", "dsa_encoded_stream", "dsa_encoded_free",
+    "dsa_encode_default_options", "dsa_encode_batch", "dsa_encode_batch_corners",
+    "dsa_encode_default_options_ex", "dsa_encode_batch_ex", "dsa_encoded_size", "dsa_encoded_stream", "dsa_encoded_free",
     "dsa_pool_create", "dsa_pool_destroy", "dsa_pool_size", "dsa_pool_last_error", "dsa_pool_decode", "dsa_pool_job_locate",
     "dsa_pool_job_chunks", "dsa_pool_job_free", "dsa_pool_plan",
 ]
@@ -32,6 +33,13 @@ class EncodeOptions(C.Structure):
     _fields_ = [("position_bits", C.c_int32), ("texcoord_bits", C.c_int32), ("normal_bits", C.c_int32),
                 ("single_connectivity", C.c_int32), ("symbol_scheme", C.c_int32), ("compression_level", C.c_int32),
                 ("position_prediction", C.c_int32), ("texcoord_prediction", C.c_int32)]
+
+
+class EncodeOptionsEx(C.Structure):
+    """dsa_encode_options_ex: valence Edgebreaker (edgebreaker_method 2, or -1 by speed and face count) and GeometricNormal
+    (normal_prediction 6) beside the options of dsa_encode_batch."""
+    _fields_ = [("base", EncodeOptions), ("edgebreaker_method", C.c_int32), ("normal_prediction", C.c_int32),
+                ("reserved", C.c_int32 * 6)]
 
 
 class MeshInput(C.Structure):
@@ -138,6 +146,9 @@ def lib():
         L.dsa_encode_default_options.restype = None
         L.dsa_encode_batch.argtypes = [vp, u32, C.POINTER(MeshInput), C.POINTER(EncodeOptions), C.POINTER(vp)]
         L.dsa_encode_batch_corners.argtypes = [vp, u32, C.POINTER(MeshCornerInput), C.POINTER(EncodeOptions), C.POINTER(vp)]
+        L.dsa_encode_default_options_ex.argtypes = [C.POINTER(EncodeOptionsEx)]
+        L.dsa_encode_default_options_ex.restype = None
+        L.dsa_encode_batch_ex.argtypes = [vp, u32, C.POINTER(MeshCornerInput), C.POINTER(EncodeOptionsEx), C.POINTER(vp)]
         L.dsa_encoded_size.restype = u32
         L.dsa_encoded_size.argtypes = [vp]
         L.dsa_encoded_stream.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(C.c_size_t)]

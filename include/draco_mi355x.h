@@ -231,8 +231,8 @@ typedef struct dsa_encode_options {
   int32_t single_connectivity; /* 0: one attributes decoder per attribute (Draco default at speed 5), 1: one for all */
   int32_t symbol_scheme;       /* -1 choose per stream (SymbolEncoding.cs:8-40), 0 tagged, 1 raw */
   int32_t compression_level;   /* 0..10, default 5 */
-  int32_t position_prediction; /* PredictionSchemeMethod: 1 parallelogram (default), 0 difference */
-  int32_t texcoord_prediction;
+  int32_t position_prediction; /* PredictionSchemeMethod: 1 parallelogram (default), 0 difference; other values fail the call */
+  int32_t texcoord_prediction; /* 1 parallelogram (default), 0 difference, 5 TexCoordsPortable; other values fail the call */
 } dsa_encode_options;
 
 typedef struct dsa_mesh_input {
@@ -274,6 +274,23 @@ typedef struct dsa_mesh_corner_input {
  * generic != NULL with generic_components outside 1..4 or ids without their values (DSA_ERR_INVALID_ARGUMENT). */
 dsa_status dsa_encode_batch_corners(dsa_context *ctx, uint32_t n, const dsa_mesh_corner_input *meshes,
                                     const dsa_encode_options *options, dsa_encoded **out);
+/* The schemes stock encoders write at their default level: valence Edgebreaker symbols, TexCoordsPortable texture coordinates,
+ * GeometricNormal normals (Constants.EdgeBreakerTraversalDecoderType, PredictionSchemeMethod).  Added after ABI 4 without
+ * changing it: callers detect the feature by the symbol dsa_encode_batch_ex.  A value outside the ones listed fails the call with
+ * DSA_ERR_INVALID_ARGUMENT (dsa_last_error says which). */
+typedef struct dsa_encode_options_ex {
+  dsa_encode_options base;      /* as for dsa_encode_batch; base.texcoord_prediction may also be 5 (TexCoordsPortable),
+                                   base.position_prediction is 0 or 1 */
+  int32_t edgebreaker_method;   /* 0 standard (default), 2 valence, -1 the reference's rule (DracoEncoder.cs:86-97), decided per
+                                   mesh: valence when compression_level > 5 (speed < 5) and the mesh has >= 1000 faces */
+  int32_t normal_prediction;    /* 0 difference (default), 6 GeometricNormal */
+  int32_t reserved[6];          /* must be zero */
+} dsa_encode_options_ex;
+void dsa_encode_default_options_ex(dsa_encode_options_ex *options);
+/* dsa_encode_batch_corners with the options above: meshes with per-vertex attributes, attributes given per corner, or both.  A
+ * mesh fails alone as there; the streams of legal dsa_encode_batch / _corners options are the same bytes through either call. */
+dsa_status dsa_encode_batch_ex(dsa_context *ctx, uint32_t n, const dsa_mesh_corner_input *meshes, const dsa_encode_options_ex *options,
+                               dsa_encoded **out);
 uint32_t dsa_encoded_size(const dsa_encoded *encoded);
 /* Bytes of stream `mesh` (owned by `encoded`, valid until dsa_encoded_free) or that mesh's failure status. */
 dsa_status dsa_encoded_stream(const dsa_encoded *encoded, uint32_t mesh, const uint8_t **bytes, size_t *length);
