@@ -231,10 +231,5 @@ def seamed_mesh(synth, kind, nx, ny, seed, normal_charts=None, uv_charts="stripe
     """A synthetic mesh with its normals and / or texture coordinates given per corner (chart_of_faces patterns; None:
     that attribute stays per vertex).  Returns the arguments of synth.encode_mesh_corners:
     (pos, faces, normal rows, normal ids or None, uv rows, uv ids or None)."""
-    pos, nrm, uv, faces = synth.make_mesh(kind, nx, ny, seed)
-    nid = uid = None
-    if normal_charts:
-        nid, nrm = split_by_chart(faces, nrm, chart_of_faces(pos, faces, normal_charts, seed + 1), [0.3, -0.2, 0.1])
-    if uv_charts:
-        uid, uv = split_by_chart(faces, uv, chart_of_faces(pos, faces, uv_charts, seed + 2), [1.25, 0.5])
-    return pos, faces, nrm, nid, uv, uid
+    import irregular
+    return irregular.with_seams(*synth.make_mesh(kind, nx, ny, seed), normal_charts, uv_charts, seed)

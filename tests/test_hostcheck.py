@@ -11,6 +11,7 @@ import pytest
 
 import oracle
 import draco_sharp_amd.synth as synth
+import irregular
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "hostcheck", "general_host.cpp")
@@ -84,9 +85,12 @@ def test_house04_through_the_general_path_source(exe, house04_bytes, tmp_path):
     # decoder branches no stock setting reaches: non-canonicalised octahedral transform, uncompressed integers, prediction method -2
     (synth.HOLES, 14, 12, {"normal_transform": 2}), (synth.TORUS, 10, 8, {"raw_integers": 4, "predictive_connectivity": 2}),
     (synth.GRID, 14, 11, {"raw_integers": 1, "pos_bits": 6, "uv_bits": 6, "normal_bits": 5}), (synth.TWO_PARTS, 9, 6, {"raw_integers": 2, "pos_bits": 10, "normal_transform": 2, "force_scheme": 0}),
-    (synth.HOLES, 14, 12, {"no_prediction": 7}), (synth.TORUS, 10, 8, {"no_prediction": 5, "uv_prediction": 5, "single_connectivity": 1})])
+    (synth.HOLES, 14, 12, {"no_prediction": 7}), (synth.TORUS, 10, 8, {"no_prediction": 5, "uv_prediction": 5, "single_connectivity": 1})] +
+    # irregular connectivity (tests/irregular.py: flipped, subdivided, thickened, shuffled, fans, strip, components), the dialects in turn
+    [(c.name, 0, 0, list(irregular.DIALECTS.values())[k % len(irregular.DIALECTS)]) for k, c in enumerate(irregular.SMALL)] +
+    [(c.name, 0, 0, list(irregular.DIALECTS.values())[(k + 2) % len(irregular.DIALECTS)]) for k, c in enumerate(irregular.SMALL)])
 def test_synthetic_meshes_through_the_general_path_source(exe, tmp_path, kind, nx, ny, opts):
-    pos, nrm, uv, faces = synth.make_mesh(kind, nx, ny, 7)
+    pos, nrm, uv, faces = irregular.mesh(kind) if isinstance(kind, str) else synth.make_mesh(kind, nx, ny, 7)
     data = synth.encode_mesh(pos, faces, nrm, uv, opt=synth.options(**opts))
     ref = oracle.decode(data)
     for half_lut in (False, True):                    # the two rANS look-up table resolutions of the device launches

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import draco_sharp_amd.synth as synth
+import irregular
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "hostcheck", "encconn_host.cpp")
@@ -49,6 +50,10 @@ def test_sound_meshes_of_every_shape(exe, tmp_path):
     meshes.append((4, np.array([[0, 1, 2], [0, 3, 1], [0, 2, 3], [1, 3, 2]])))     # a tetrahedron: closed, interior start face
     fan = np.array([[0, i, i + 1] for i in range(1, 200)] + [[0, 200, 1]])      # a vertex of valence 200
     meshes.append((201, fan))
+    for c in irregular.SMALL:                    # flipped, subdivided, thickened, shuffled: valences 3 .. 21, ids and faces in no order
+        pos, _, _, faces = irregular.mesh(c)
+        meshes.append((len(pos), faces))
+    assert len(meshes) >= 29 + len(irregular.SMALL) >= 43
     out = run(exe, tmp_path, meshes)
     assert "%d meshes, %d coded alike, 0 refused alike" % (len(meshes), len(meshes)) in out
 

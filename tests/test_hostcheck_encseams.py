@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import draco_sharp_amd.synth as synth
+import irregular
 import meshutil
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -52,6 +53,23 @@ def seamed(kind, nx, ny, seed, normal_charts, uv_charts):
     return (len(pos), faces, None if nid is None else (len(nrm), nid), None if uid is None else (len(uv), uid))
 
 
+def irregular_seamed():
+    """The small cases of tests/irregular.py (fans of 1 .. 300 corners, ids and faces in no order, handles), two chart patterns each."""
+    meshes = []
+    for k, c in enumerate(irregular.SMALL):
+        pos, nrm, uv, faces = irregular.mesh(c)
+        for j in (k, k + 3):
+            _, _, rows_n, nid, rows_u, uid = irregular.with_seams(pos, nrm, uv, faces, PATTERNS[(j + 1) % len(PATTERNS)], PATTERNS[j % len(PATTERNS)], seed=j)
+            meshes.append((len(pos), faces, (len(rows_n), nid), (len(rows_u), uid)))
+    return meshes
+
+
+def test_irregular_meshes_are_all_coded(exe, tmp_path):
+    meshes = irregular_seamed()
+    out = run(exe, tmp_path, meshes)
+    assert "%d meshes, %d coded alike, 0 refused alike, " % (len(meshes), len(meshes)) in out, out
+
+
 def test_topologies_by_chart_patterns(exe, tmp_path):
     meshes = []
     for k, kind in enumerate(KINDS):
@@ -60,6 +78,8 @@ def test_topologies_by_chart_patterns(exe, tmp_path):
             meshes.append(seamed(kind, nx, ny, 10 * k + j, None, pat))          # UV only
             meshes.append(seamed(kind, nx, ny, 10 * k + j, pat, None))          # normals only
             meshes.append(seamed(kind, nx, ny, 10 * k + j, pat, PATTERNS[(j + 2) % len(PATTERNS)]))      # both
+    meshes += irregular_seamed()
+    assert len(meshes) == 90 + 2 * len(irregular.SMALL)
     out = run(exe, tmp_path, meshes)
     n = len(meshes)
     assert "%d meshes, " % n in out, out

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import draco_sharp_amd.synth as synth
+import irregular
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "hostcheck", "encvalence_host.cpp")
@@ -50,12 +51,20 @@ def test_context_lists_of_every_shape(exe, tmp_path):
     fan = np.array([[0, i, i + 1] for i in range(1, 200)] + [[0, 200, 1]])      # a vertex of valence 200
     meshes.append((201, fan))
     meshes.append((152, fan[:150]))                                             # an open fan
+    splitting = 0
+    for c in irregular.SMALL:                    # flipped, subdivided, thickened, shuffled: every context list, both clamps
+        pos, _, _, faces = irregular.mesh(c)
+        splitting += c.splits and len(meshes) % 4 != 3          # (the driver codes every fourth mesh with standard symbols)
+        meshes.append((len(pos), faces))
+    assert splitting >= 4
     out = run(exe, tmp_path, meshes)
     m = re.search(r"(\d+) meshes, (\d+) valence lists alike \((\d+) with topology splits\), (\d+) standard, (\d+) refused alike", out)
     assert m, out
     total, alike, splits, standard, refused = map(int, m.groups())
     assert total == len(meshes) and refused == 0 and alike + standard == total and alike >= 3 * total // 4 - 1
-    assert splits >= 5                       # tori, holes and two-part meshes split the traversal: the S-symbol fan walks ran
+    # tori, holes and two-part meshes split the traversal (the S-symbol fan walks ran): at least the five the grids gave before,
+    # and every irregular case with a handle, a hole or a second component
+    assert splits >= 5 + splitting
 
 
 def test_damaged_meshes_fail_alike(exe, tmp_path):

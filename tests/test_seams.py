@@ -11,6 +11,7 @@ import os
 import numpy as np
 import pytest
 
+import irregular
 import oracle
 import draco_sharp_amd.synth as synth
 from meshutil import seamed_mesh, source_corner_faces_seamed
@@ -72,12 +73,13 @@ def test_seams_at_64k_triangles():
 
 
 # ------------------------------------------------------------------ the general path's source on the host (ASan / UBSan)
-@pytest.mark.parametrize("kind,nx,ny", TOPOLOGIES)
+@pytest.mark.parametrize("kind,nx,ny", TOPOLOGIES + [(c.name, 0, 0) for c in irregular.SMALL])
 def test_seamed_streams_through_the_general_path_source(kind, nx, ny, tmp_path):
     import test_hostcheck as th
     exe = _hostcheck_exe(th)
     for charts in PATTERNS:
-        args = seamed_mesh(synth, kind, nx, ny, 7, *charts)
+        # (a name: one of the irregular meshes of tests/irregular.py, cut by the same charts)
+        args = irregular.with_seams(*irregular.mesh(kind), *charts, seed=7) if isinstance(kind, str) else seamed_mesh(synth, kind, nx, ny, 7, *charts)
         for opt in (dict(), dict(predictive_connectivity=2, uv_prediction=5, normal_prediction=6), dict(uv_prediction=4, pos_prediction=2, force_scheme=0)):
             data = synth.encode_mesh_corners(*args, opt=synth.options(**opt))
             status, detail, got = th.host_decode(exe, data, tmp_path, force=True)

@@ -7,6 +7,7 @@ import itertools, sys, os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import numpy as np, oracle, draco_sharp_amd as dsa, draco_sharp_amd.synth as synth
+import irregular
 from meshutil import seamed_mesh
 from test_gpu_parity import assert_same
 
@@ -16,9 +17,12 @@ def run(seed=1, ctx=None, big=False):
         ctx = dsa.Context(0)
     topologies = [(synth.GRID, 14, 11), (synth.TORUS, 12, 9), (synth.HOLES, 16, 13), (synth.TWO_PARTS, 9, 6)]
     streams, labels = [], []
+    irr = np.random.default_rng([seed, 0x1226])          # the irregular draw: one mesh in three flipped, split, shuffled, sometimes thickened
     for ti, (kind, nx, ny) in enumerate(topologies):
         for n_chart, u_chart in itertools.product((None, "stripes", "random"), (None, "stripes", "checker")):
             args = seamed_mesh(synth, kind, nx, ny, seed + ti, n_chart, u_chart)
+            if irr.integers(0, 3) == 0:
+                args = irregular.with_seams(*irregular.roughen(*synth.make_mesh(kind, nx, ny, seed + ti), irr), n_chart, u_chart, seed + ti)
             for scheme in (dict(force_scheme=1), dict(force_scheme=0), dict(raw_integers=2, pos_bits=10, uv_bits=10)):
                 for pp, up, npred, conn in itertools.product((0, 1, 4), (0, 1, 5, 4), (0, 6), (0, 2)):
                     if (ti + pp + up + npred + conn) % 2:            # half of the product per topology (each combination on two of the four)
@@ -38,6 +42,8 @@ def run(seed=1, ctx=None, big=False):
     # a generic attribute of 0 / 1 / 4 components, the symbol scheme left to the writer
     for ti, (kind, nx, ny) in enumerate(topologies[:3]):
         pos, nrm, uv, faces = synth.make_mesh(kind, nx + 6, ny + 5, seed + 10 + ti)
+        if ti == 1:
+            pos, nrm, uv, faces = irregular.roughen(pos, nrm, uv, faces, irr)
         for bits, single, gc, scheme in itertools.product((dict(), dict(pos_bits=14, uv_bits=12, normal_bits=10)), (0, 1), (0, 1, 4), (-1, 0, 1)):
             gen = None if gc == 0 else ((np.arange(len(pos) * gc, dtype=np.int64) * 7919 + ti) % 256).astype(np.uint8).reshape(-1, gc)
             for pp, up, npred, conn in itertools.product((0, 1, 4), (0, 1, 5), (0, 6), (0, 2)):

@@ -8,7 +8,9 @@ import oracle
 import draco_sharp_amd as dsa, draco_sharp_amd.synth as synth
 
 
-def random_case(rng):
+def random_case(rng, irr=None):
+    """irr: the generator of the irregular draw (tests/irregular.py: roughen), apart from `rng` so that the options of a seed stay
+    what they were; None: grids only."""
     kind = int(rng.choice([synth.GRID, synth.TORUS, synth.SPHERE, synth.HOLES, synth.TWO_PARTS]))
     nx, ny = int(rng.integers(4, 48)), int(rng.integers(4, 40))
     if kind == synth.HOLES:
@@ -31,10 +33,16 @@ def random_case(rng):
         opt["raw_integers"] = raw
     mesh_seed = int(rng.integers(0, 1 << 30))
     pos, nrm, uv, faces = synth.make_mesh(kind, nx, ny, mesh_seed)
+    grid_vertices = len(pos)
+    # one case in three on irregular connectivity: flips, 1->3 splits, a shuffle of ids and faces, sometimes a thickened surface
+    rough = irr is not None and irr.integers(0, 3) == 0
+    if rough:
+        import irregular
+        pos, nrm, uv, faces = irregular.roughen(pos, nrm, uv, faces, irr)
     with_n, with_uv = bool(rng.integers(0, 4)), bool(rng.integers(0, 4))
     # one case in three gives its attributes per corner (attribute seams, corner attributes); they need a connectivity of their own
     if rng.integers(0, 3) == 0 and (with_n or with_uv):
-        from meshutil import seamed_mesh
+        import irregular
         patterns = ["stripes", "island", "checker", "random", "single", "none", None]
         charts = (str(rng.choice(patterns[:6])) if with_n and rng.integers(0, 2) else None, str(rng.choice(patterns[:6])) if with_uv and rng.integers(0, 2) else None)
         opt["single_connectivity"] = 0
@@ -45,21 +53,24 @@ def random_case(rng):
             opt.update(traversal_method=0, predictive_connectivity=int(rng.choice([0, 2])), pos_prediction=int(rng.choice([0, 1, 4])), uv_prediction=int(rng.choice([0, 1, 5])))
             if rng.integers(0, 3) == 0 and not opt.get("raw_integers"):
                 opt["force_scheme"] = 0
-        pos, faces, nrm, nid, uv, uid = seamed_mesh(synth, kind, nx, ny, mesh_seed, *charts)
+        pos, faces, nrm, nid, uv, uid = irregular.with_seams(pos, nrm, uv, faces, *charts, seed=mesh_seed)       # (meshutil.seamed_mesh on a grid)
         return synth.encode_mesh_corners(pos, faces, nrm if with_n else None, nid if with_n else None, uv if with_uv else None, uid if with_uv else None,
-                                         opt=synth.options(**opt)), (kind, nx, ny, opt, with_n, with_uv, charts)
+                                         opt=synth.options(**opt)), (kind, nx, ny, opt, with_n, with_uv, charts, rough)
     # one per-vertex case in four carries a generic attribute of 1 - 4 uint8 components (vertex colours)
     gen = None
     if rng.integers(0, 4) == 0:
         gc = int(rng.integers(1, 5))
         opt["generic_components"] = gc
-        gen = rng.integers(0, 256, (len(pos), gc)).astype(np.uint8)
-    return synth.encode_mesh(pos, faces, nrm if with_n else None, uv if with_uv else None, generic=gen, opt=synth.options(**opt)), (kind, nx, ny, opt, with_n, with_uv)
+        gen = rng.integers(0, 256, (grid_vertices, gc)).astype(np.uint8)
+        if len(pos) != grid_vertices:
+            gen = np.concatenate([gen, irr.integers(0, 256, (len(pos) - grid_vertices, gc)).astype(np.uint8)])
+    return synth.encode_mesh(pos, faces, nrm if with_n else None, uv if with_uv else None, generic=gen, opt=synth.options(**opt)), (kind, nx, ny, opt, with_n, with_uv, rough)
 
 
 def run(count, seed, ctx=None):
     rng = np.random.default_rng(seed)
-    cases = [random_case(rng) for _ in range(count)]
+    irr = np.random.default_rng([seed, 0x1226])          # the irregular draw: seeded from the run's seed, apart from the options
+    cases = [random_case(rng, irr) for _ in range(count)]
     own = ctx is None
     ctx = ctx or dsa.Context(0)
     b = dsa.Batch(ctx, [c[0] for c in cases])

@@ -5,8 +5,11 @@ import os, sys
 os.environ["DSA_ENC_HOST_CONN"] = "0"; os.environ["DSA_ENC_HOST_PLAN"] = "0"
 import os; ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import numpy as np, draco_sharp_amd as dsa, draco_sharp_amd.synth as synth
+import irregular
 count = int(sys.argv[1]) if len(sys.argv) > 1 else 300
-rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 3)
+seed = int(sys.argv[2]) if len(sys.argv) > 2 else 3
+rng = np.random.default_rng(seed)
+irr = np.random.default_rng([seed, 0x1226])     # the irregular draw, apart from the options: a seed keeps the options it had
 ctx = dsa.Context(0)
 enc = dsa.DracoEncoder(ctx)
 bad = done = 0
@@ -23,6 +26,10 @@ while done < count:
         gen = None
         if rng.integers(0, 3) == 0:                  # a generic uint8 attribute of 1 - 4 components (ABI 4)
             gen = rng.integers(0, 256, (len(pos), int(rng.integers(1, 5)))).astype(np.uint8)
+        if irr.integers(0, 3) == 0:                  # one mesh in three on irregular connectivity (flips, splits, shuffle, thicken)
+            pos, nrm, uv, faces = irregular.roughen(pos, nrm, uv, faces, irr)
+            if gen is not None and len(gen) != len(pos):
+                gen = np.concatenate([gen, irr.integers(0, 256, (len(pos) - len(gen), gen.shape[1])).astype(np.uint8)])
         group.append((pos, faces, nrm if rng.integers(0, 4) else None, uv if rng.integers(0, 4) else None, gen))
     got = enc.EncodeBatch([dsa.MeshData(*m) for m in group], cfg)
     opt = synth.options(pos_bits=cfg.position_bits, uv_bits=cfg.texcoord_bits, normal_bits=cfg.normal_bits, single_connectivity=1 if cfg.single_connectivity else 0,
