@@ -5,6 +5,8 @@
 // those ids change become attribute seams (dsa_encode_batch_corners).  Not compiled in the build image (no .NET SDK); the executable twin
 // is draco-sharp_amd/encoder.py.  Config options honoured: quantisation bits per attribute type and Speed
 // (src/Draco/IO/Config.cs); everything else keeps the reference's defaults (standard Edgebreaker, DFS traversal).
+// An explicitly set ConfigOptionName.EncodingMethod of SequentialEncoding (with ConfigOptionName.CompressConnectivity) and a
+// PointCloud that is not a Mesh go through dsa_encode_sequential_batch: points and faces in the caller's order, one value per point.
 using System;
 using System.Collections.Generic;
 using System.IO;
@@ -29,8 +31,74 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
         writer.Write(EncodeBatch(new[] { mesh }, config)[0]);
     }
 
+    /// <summary>Point clouds (not meshes): sequential point-cloud streams, point i of the stream is point i of the cloud.</summary>
+    public void Encode(BinaryWriter writer, Config config, PointCloud.PointCloud cloud)
+    {
+        if (cloud is Mesh.Mesh mesh) { Encode(writer, config, mesh); return; }
+        writer.Write(EncodeSequential(new[] { cloud }, config, 0)[0]);
+    }
+
+    public byte[][] EncodeBatch(IReadOnlyList<PointCloud.PointCloud> clouds, Config config)
+    {
+        foreach (var c in clouds) if (c is Mesh.Mesh) throw new ArgumentException("a batch holds meshes or point clouds, not both");
+        return EncodeSequential(clouds, config, 0);
+    }
+
+    // dsa_encode_sequential_batch: geometry 1 meshes, 0 point clouds; one value per point, in point order
+    private byte[][] EncodeSequential(IReadOnlyList<PointCloud.PointCloud> items, Config config, int geometry)
+    {
+        NativeMethods.dsa_encode_sequential_default_options(out var so);
+        so.Base.PositionBits = config.GetAttributeOption((int)GeometryAttributeType.Position, ConfigOptionName.Attribute.QuantizationBits, so.Base.PositionBits);
+        so.Base.TexcoordBits = config.GetAttributeOption((int)GeometryAttributeType.TexCoord, ConfigOptionName.Attribute.QuantizationBits, so.Base.TexcoordBits);
+        so.Base.NormalBits = config.GetAttributeOption((int)GeometryAttributeType.Normal, ConfigOptionName.Attribute.QuantizationBits, so.Base.NormalBits);
+        so.Base.SymbolScheme = config.GetOption(ConfigOptionName.SymbolEncodingMethod, so.Base.SymbolScheme);
+        so.Base.CompressionLevel = 10 - config.Speed;
+        so.Geometry = geometry;
+        so.CompressConnectivity = geometry == 1 && config.GetOption(ConfigOptionName.CompressConnectivity, false) ? 1 : 0;
+        var inputs = new DsaMeshInput[items.Count];
+        var pins = new List<GCHandle>();
+        IntPtr encoded = IntPtr.Zero;
+        try
+        {
+            for (int i = 0; i < items.Count; ++i)
+            {
+                var m = items[i];
+                inputs[i].NumVertices = (uint)m.PointsCount;
+                inputs[i].Positions = (float*)Pin(Floats(m, GeometryAttributeType.Position, 3), pins);
+                inputs[i].Normals = (float*)Pin(Floats(m, GeometryAttributeType.Normal, 3), pins);
+                inputs[i].Texcoords = (float*)Pin(Floats(m, GeometryAttributeType.TexCoord, 2), pins);
+                var generic = Bytes(m, GeometryAttributeType.Generic, out uint genericComponents);
+                inputs[i].Generic = (byte*)Pin(generic, pins);
+                inputs[i].GenericComponents = generic == null ? 0 : genericComponents;
+                if (geometry == 1 && m is Mesh.Mesh mesh)
+                {
+                    inputs[i].NumFaces = (uint)mesh.FacesCount;
+                    var faces = new uint[mesh.FacesCount * 3];
+                    for (int f = 0; f < mesh.FacesCount; ++f) { var face = mesh.GetFace((uint)f); faces[3 * f] = (uint)face[0]; faces[3 * f + 1] = (uint)face[1]; faces[3 * f + 2] = (uint)face[2]; }
+                    inputs[i].Faces = (uint*)Pin(faces, pins);
+                }
+            }
+            fixed (DsaMeshInput* p = inputs)
+                NativeMethods.Check(NativeMethods.dsa_encode_sequential_batch(_ctx, (uint)items.Count, p, in so, out encoded), _ctx, "dsa_encode_sequential_batch");
+            return Streams(encoded, items.Count);
+        }
+        finally
+        {
+            if (encoded != IntPtr.Zero) NativeMethods.dsa_encoded_free(encoded);
+            foreach (var h in pins) if (h.IsAllocated) h.Free();
+        }
+    }
+
     public byte[][] EncodeBatch(IReadOnlyList<Mesh.Mesh> meshes, Config config)
     {
+        // an explicitly set EncodingMethod of SequentialEncoding: the sequential call (unset, or Edgebreaker: the call and its bytes
+        // are what they were; the reference's speed-10 rule applies only where the option is unset, and stays Edgebreaker here)
+        if (config.IsOptionSet(ConfigOptionName.EncodingMethod) && config.GetOption(ConfigOptionName.EncodingMethod, -1) == Constants.EncodingMethod.SequentialEncoding)
+        {
+            var items = new PointCloud.PointCloud[meshes.Count];
+            for (int i = 0; i < meshes.Count; ++i) items[i] = meshes[i];
+            return EncodeSequential(items, config, 1);
+        }
         NativeMethods.dsa_encode_default_options(out var opt);
         // per-attribute-type options are keyed by (int)GeometryAttributeType (Config.cs:55-62)
         opt.PositionBits = config.GetAttributeOption((int)GeometryAttributeType.Position, ConfigOptionName.Attribute.QuantizationBits, opt.PositionBits);
@@ -196,7 +264,7 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
     }
 
     // values of a per-vertex float attribute in point order (null when the mesh has no such attribute)
-    private static float[]? Floats(Mesh.Mesh m, GeometryAttributeType type, int nc)
+    private static float[]? Floats(PointCloud.PointCloud m, GeometryAttributeType type, int nc)
     {
         var a = m.GetNamedAttribute(type);
         if (a == null) return null;
@@ -207,7 +275,7 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
     }
 
     // a uint8 attribute of 1 - 4 components per point (the first of its type), or null
-    private static byte[]? Bytes(Mesh.Mesh m, GeometryAttributeType type, out uint nc)
+    private static byte[]? Bytes(PointCloud.PointCloud m, GeometryAttributeType type, out uint nc)
     {
         nc = 0;
         var a = m.GetNamedAttribute(type);

@@ -79,6 +79,16 @@ internal unsafe struct DsaEncodeOptionsEx
     public fixed int Reserved[6];   // zero
 }
 
+// dsa_encode_sequential_options (dsa_encode_sequential_batch): sequential meshes and point clouds
+[StructLayout(LayoutKind.Sequential)]
+internal unsafe struct DsaEncodeSequentialOptions
+{
+    public DsaEncodeOptions Base;       // quantisation bits, SymbolScheme, CompressionLevel are used
+    public int Geometry;                // 1 triangular mesh, 0 point cloud (Constants.EncodingType)
+    public int CompressConnectivity;    // 0 raw indices, 1 compressed (ConfigOptionName.CompressConnectivity)
+    public fixed int Reserved[6];       // zero
+}
+
 [StructLayout(LayoutKind.Sequential)]
 internal unsafe struct DsaMeshInput
 {
@@ -153,6 +163,8 @@ internal static unsafe partial class NativeMethods
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_batch_corners(IntPtr ctx, uint n, DsaMeshCornerInput* meshes, in DsaEncodeOptions options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern void dsa_encode_default_options_ex(out DsaEncodeOptionsEx options);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_batch_ex(IntPtr ctx, uint n, DsaMeshCornerInput* meshes, in DsaEncodeOptionsEx options, out IntPtr encoded);
+    [DllImport(Lib)] internal static extern void dsa_encode_sequential_default_options(out DsaEncodeSequentialOptions options);
+    [DllImport(Lib)] internal static extern DsaStatus dsa_encode_sequential_batch(IntPtr ctx, uint n, DsaMeshInput* meshes, in DsaEncodeSequentialOptions options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern uint dsa_encoded_size(IntPtr encoded);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encoded_stream(IntPtr encoded, uint mesh, out byte* bytes, out nuint length);
     [DllImport(Lib)] internal static extern void dsa_encoded_free(IntPtr encoded);

@@ -60,6 +60,7 @@ struct EncStream {                 // one per (mesh, attribute); lives in device
   uint64_t flags;                  // u32[(cap + 31) / 32] side bits, bit k of the list: orientations (delta-coded against true, last
                                    //   entry first; k_enc_orient) or flips (entry order; k_enc_corr) -- -> download (write_rabs)
   uint32_t t_nc3, num_flags;       // 3F; OUTPUT: bits in `flags`
+  uint32_t linear, pad;            // linear: entry i is value row i (sequential streams, dsa_encode_sequential.h): `d` is `vals`, no e2v, no gather
 };
 
 __device__ __forceinline__ uint32_t enc_msb(uint32_t v) { return 31u - (uint32_t)__builtin_clz(v); }
@@ -160,6 +161,9 @@ __global__ __launch_bounds__(256) void k_enc_gather(uint8_t *arena, EncStream *s
   const uint32_t *e2v = (const uint32_t *)(arena + S.e2v);
   const uint32_t nc = S.nc, tid = threadIdx.x;
   int32_t mn = 0x7FFFFFFF, mx = (int32_t)0x80000000;
+  if (S.linear) {                  // the values are in entry order where they lie: the bounds alone
+    for (uint32_t i = tid, total = S.nv * nc; i < total; i += 256) { const int32_t x = vals[i]; if (x < mn) mn = x; if (x > mx) mx = x; }
+  } else
   for (uint32_t e = tid; e < S.nv; e += 256) {
     const uint32_t v = e2v[e];
     for (uint32_t c = 0; c < nc; ++c) { const int32_t x = vals[(size_t)v * nc + c]; d[(size_t)e * nc + c] = x; if (x < mn) mn = x; if (x > mx) mx = x; }
@@ -510,6 +514,204 @@ struct dsa_encoded {
   std::vector<std::string> messages;
 };
 
+// ---- transfers of a chunk, shared by the chunk functions (encode_chunk below, encode_sequential_chunk of dsa_encode_sequential.h)
+struct EncUpload { uint64_t off; const void *src; size_t bytes; bool narrow; };       // narrow: src is u32[bytes / 2], the staging copy keeps the low halves
+// uploads in pieces through the lane's two pinned staging buffers: host threads fill one while the DMA engine drains the
+// other (a pageable source would be staged by the runtime, one thread, a few GB/s)
+static hipError_t enc_upload(EncLane &lane, uint8_t *arena, hipStream_t st, const std::vector<EncUpload> &ups) {
+  const uint64_t piece_cap = 192ull << 20;
+  size_t i0 = 0;
+  while (i0 < ups.size()) {
+    const uint64_t lo = ups[i0].off;
+    size_t i1 = i0 + 1;
+    while (i1 < ups.size() && ups[i1].off + ups[i1].bytes - lo <= piece_cap) ++i1;
+    const uint64_t hi = ups[i1 - 1].off + ups[i1 - 1].bytes;
+    hostutil::Staging &stg = lane.stage[lane.next];
+    lane.next ^= 1;
+    hipError_t e = stg.acquire((size_t)(hi - lo));
+    if (e != hipSuccess) return e;
+    uint8_t *h = stg.buf.p;
+    hostutil::parallel_for((uint32_t)(i1 - i0), [&](uint32_t k) {
+      const EncUpload &u = ups[i0 + k];
+      if (!u.narrow) { memcpy(h + (u.off - lo), u.src, u.bytes); return; }
+      const uint32_t *src = (const uint32_t *)u.src;
+      uint16_t *dst = (uint16_t *)(h + (u.off - lo));               // (offsets are multiples of 256)
+      for (size_t e = 0, ne = u.bytes / 2; e < ne; ++e) dst[e] = (uint16_t)src[e];
+    }, 2);
+    e = hipMemcpyAsync(arena + lo, h, (size_t)(hi - lo), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = stg.submitted(st);
+    if (e != hipSuccess) return e;
+    i0 = i1;
+  }
+  return hipSuccess;
+}
+// pieces of the arena -> one host buffer (items[k].packed_off filled in); host buffer -> pieces of the arena
+// (with `view`: no copy into `host`; *view points at the pieces in the lane's pinned staging buffer, valid until the gather after next)
+static dsa_status enc_gather(EncLane &lane, const uint8_t *arena, std::vector<dsa::PackItem> &items, std::vector<uint8_t> &host, const uint8_t **view) {
+  uint64_t total = 0;
+  for (auto &it : items) { it.packed_off = total; total += ((uint64_t)it.len + 15) & ~15ull; }
+  if (view) *view = nullptr; else host.resize(total);
+  if (items.empty() || total == 0) return DSA_OK;
+  uint8_t *d_packed = nullptr; dsa::PackItem *d_items = nullptr;
+  hipError_t e = lane.packed.ensure(total);
+  if (e == hipSuccess) e = lane.items.ensure(sizeof(dsa::PackItem) * items.size());
+  d_packed = (uint8_t *)lane.packed.p; d_items = (dsa::PackItem *)lane.items.p;
+  if (e == hipSuccess) e = hipMemcpyAsync(d_items, items.data(), sizeof(dsa::PackItem) * items.size(), hipMemcpyHostToDevice, lane.st);
+  if (e == hipSuccess) { hipLaunchKernelGGL(dsa::k_enc_pack, dim3((uint32_t)items.size()), dim3(256), 0, lane.st, arena, d_packed, d_items, (uint32_t)items.size()); e = hipGetLastError(); }
+  // through pinned staging (a pageable destination is staged by the runtime at a fraction of the link's rate)
+  hostutil::Staging &stg = lane.stage[lane.next];
+  lane.next ^= 1;
+  if (e == hipSuccess) e = stg.acquire((size_t)total);
+  if (e == hipSuccess) e = hipMemcpyAsync(stg.buf.p, d_packed, total, hipMemcpyDeviceToHost, lane.st);
+  if (e == hipSuccess) e = hipStreamSynchronize(lane.st);
+  if (e == hipSuccess) { if (view) *view = stg.buf.p; else hostutil::parallel_memcpy(host.data(), stg.buf.p, (size_t)total); }
+  return e == hipSuccess ? DSA_OK : (e == hipErrorOutOfMemory ? DSA_ERR_OUT_OF_MEMORY : DSA_ERR_DEVICE);
+}
+static dsa_status enc_scatter(EncLane &lane, uint8_t *arena, std::vector<dsa::PackItem> &items, const std::vector<uint8_t> &host) {
+  if (items.empty() || host.empty()) return DSA_OK;
+  uint8_t *d_packed = nullptr; dsa::PackItem *d_items = nullptr;
+  hipError_t e = lane.packed.ensure(host.size());
+  if (e == hipSuccess) e = lane.items.ensure(sizeof(dsa::PackItem) * items.size());
+  d_packed = (uint8_t *)lane.packed.p; d_items = (dsa::PackItem *)lane.items.p;
+  if (e == hipSuccess) e = hipMemcpyAsync(d_items, items.data(), sizeof(dsa::PackItem) * items.size(), hipMemcpyHostToDevice, lane.st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_packed, host.data(), host.size(), hipMemcpyHostToDevice, lane.st);
+  if (e == hipSuccess) { hipLaunchKernelGGL(dsa::k_enc_unpack, dim3((uint32_t)items.size()), dim3(256), 0, lane.st, arena, d_packed, d_items, (uint32_t)items.size()); e = hipGetLastError(); }
+  if (e == hipSuccess) e = hipStreamSynchronize(lane.st);
+  return e == hipSuccess ? DSA_OK : (e == hipErrorOutOfMemory ? DSA_ERR_OUT_OF_MEMORY : DSA_ERR_DEVICE);
+}
+
+#define ENC_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { return set_err(ctx, e_ == hipErrorOutOfMemory ? DSA_ERR_OUT_OF_MEMORY : DSA_ERR_DEVICE, "%s failed: %s", #call, hipGetErrorString(e_)); } } while (0)
+#define ENC_ST(call) do { dsa_status s_ = (call); if (s_ != DSA_OK) { return set_err(ctx, s_, "%s failed", #call); } } while (0)
+// ---- scheme choice and rANS tables by the host from the device statistics (DSA_ENC_HOST_PLAN), between the two device phases:
+// histograms down, plans by threads over streams, tables up.  A stream whose plan fails fails its mesh.
+static dsa_status enc_host_plans(dsa_context *ctx, EncLane &lane, uint8_t *arena, std::vector<dsa::EncStream> &hs, const std::vector<int> &stream_mesh, dsa_encoded *E,
+                                 const synth::Options &opt, std::vector<synth::SymbolPlan> &splans) {
+  const uint32_t ns = (uint32_t)hs.size();
+  std::vector<std::vector<uint32_t>> hists(ns);
+  auto gather = [&](std::vector<dsa::PackItem> &items, std::vector<uint8_t> &host, const uint8_t **view) { return enc_gather(lane, arena, items, host, view); };
+  auto scatter = [&](std::vector<dsa::PackItem> &items, const std::vector<uint8_t> &host) { return enc_scatter(lane, arena, items, host); };
+  {
+    std::vector<dsa::PackItem> items;
+    for (uint32_t s = 0; s < ns; ++s) {
+      if (hs[s].kind == 3 && hs[s].nv == 0) continue;
+      if (hs[s].overflow || hs[s].max_value >= hs[s].hist_cap) { hs[s].overflow = 1; continue; }
+      items.push_back({hs[s].hist_raw, 0, 4u * (hs[s].max_value + 1u), s});
+    }
+    std::vector<uint8_t> host;
+    ENC_ST(gather(items, host, nullptr));
+    for (auto &it : items) {
+      hists[it.pad].resize(it.len / 4);
+      memcpy(hists[it.pad].data(), host.data() + it.packed_off, it.len);
+    }
+  }
+  std::vector<std::string> plan_error(ns);
+  auto plan_stream = [&](uint32_t s) {
+    const uint32_t i = (uint32_t)stream_mesh[s];
+    if (E->status[i] != DSA_OK || (hs[s].kind == 3 && hs[s].nv == 0)) return;
+    try {
+      synth::check(!hs[s].overflow, "symbol outside the histogram range");
+      synth::SymbolStats stt;
+      stt.n = (size_t)hs[s].nv * hs[s].nc; stt.nc = (int)hs[s].nc; stt.max_value = hs[s].max_value; stt.total_bl = hs[s].total_bl;
+      stt.tag_freq.assign(hs[s].hist_tag, hs[s].hist_tag + 33);
+      stt.raw_freq.assign(hists[s].begin(), hists[s].end());
+      synth::plan_symbols(stt, opt.force_scheme, opt.compression_level, splans[s]);
+      hs[s].method = (uint32_t)splans[s].method;
+      hs[s].precision_bits = (uint32_t)splans[s].coder.precision_bits;
+      hs[s].num_symbols = splans[s].coder.num_symbols;
+      synth::check(splans[s].coder.num_symbols <= std::max<uint32_t>(hs[s].hist_cap, 64), "alphabet larger than the table region");
+    } catch (const std::exception &e) { plan_error[s] = e.what(); if (plan_error[s].empty()) plan_error[s] = "symbol plan failed"; hs[s].overflow = 1; }
+  };
+  hostutil::parallel_for(ns, plan_stream);
+  {
+    std::vector<dsa::PackItem> items;
+    std::vector<uint8_t> host;
+    for (uint32_t s = 0; s < ns; ++s) {
+      const uint32_t i = (uint32_t)stream_mesh[s];
+      if (E->status[i] != DSA_OK) continue;
+      if (!plan_error[s].empty()) { E->status[i] = DSA_ERR_INVALID_DATA; E->messages[i] = plan_error[s]; continue; }
+      const uint32_t bytes = 4u * splans[s].coder.num_symbols;
+      for (int t = 0; t < 2; ++t) {
+        const std::vector<uint32_t> &src = t == 0 ? splans[s].coder.prob : splans[s].coder.cum;
+        items.push_back({t == 0 ? hs[s].prob : hs[s].cum, (uint64_t)host.size(), bytes, s});
+        host.insert(host.end(), (const uint8_t *)src.data(), (const uint8_t *)src.data() + bytes);
+        host.resize((host.size() + 15) & ~(size_t)15);
+      }
+    }
+    ENC_ST(scatter(items, host));
+  }
+  return DSA_OK;
+}
+// the plans of k_enc_plan: what it refused, said per mesh
+static void enc_device_plan_errors(const std::vector<dsa::EncStream> &hs, const std::vector<int> &stream_mesh, dsa_encoded *E) {
+  const uint32_t ns = (uint32_t)hs.size();
+  for (uint32_t s = 0; s < ns; ++s) {
+    const uint32_t i = (uint32_t)stream_mesh[s];
+    if (E->status[i] != DSA_OK || !hs[s].overflow) continue;
+    E->status[i] = DSA_ERR_INVALID_DATA;
+    E->messages[i] = hs[s].plan_status ? dsa::plan::plan_message((int)hs[s].plan_status) : "symbol outside the histogram range";
+  }
+}
+// ---- device phase 2: entropy coding (behind the host's plans: k_enc_rans here; k_enc_plan's: it has run), then the coded bytes of
+// every stream, the probability tables k_enc_plan made and the side bits down in one transfer; splans[s].head receives the bytes in
+// front of the payload.
+static dsa_status enc_code_streams(dsa_context *ctx, EncLane &lane, uint8_t *arena, dsa::EncStream *d_streams, std::vector<dsa::EncStream> &hs, const std::vector<int> &stream_mesh,
+                                   const dsa_encoded *E, bool host_plan, std::vector<synth::SymbolPlan> &splans, std::vector<std::vector<uint8_t>> &rans,
+                                   std::vector<std::vector<uint8_t>> &bits, std::vector<std::vector<uint8_t>> &flag_bits) {
+  const uint32_t ns = (uint32_t)hs.size();
+  auto gather = [&](std::vector<dsa::PackItem> &items, std::vector<uint8_t> &host, const uint8_t **view) { return enc_gather(lane, arena, items, host, view); };
+  hipStream_t st = lane.st;
+  if (host_plan) {
+    ENC_TRY(hipMemcpyAsync(d_streams, hs.data(), sizeof(dsa::EncStream) * ns, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(dsa::k_enc_rans, dim3(ns), dim3(WAVE), 0, st, arena, d_streams, ns);
+    ENC_TRY(hipMemcpyAsync(hs.data(), d_streams, sizeof(dsa::EncStream) * ns, hipMemcpyDeviceToHost, st));
+    ENC_TRY(hipStreamSynchronize(st));
+  }
+  // coded bytes of every stream (and, when k_enc_plan made them, the probability tables: the stream carries them)
+  // and the side bits of TexCoordsPortable / GeometricNormal, packed
+  std::vector<dsa::PackItem> items;
+  for (uint32_t s = 0; s < ns; ++s) {
+    if (hs[s].overflow || E->status[stream_mesh[s]] != DSA_OK) continue;
+    if (hs[s].kind == 1 && hs[s].prediction == 6) hs[s].num_flags = hs[s].nv;
+    items.push_back({hs[s].out_rans, 0, hs[s].rans_len, s});
+    items.push_back({hs[s].out_bits, 0, hs[s].bits_len, s});
+    items.push_back({hs[s].prob, 0, host_plan ? 0u : 4u * hs[s].num_symbols, s});
+    items.push_back({hs[s].flags, 0, hs[s].flags ? 4u * ((hs[s].num_flags + 31u) / 32u) : 0u, s});
+  }
+  std::vector<uint8_t> unused;
+  const uint8_t *host = nullptr;
+  ENC_ST(gather(items, unused, &host));
+  hostutil::parallel_for((uint32_t)(items.size() / 4), [&](uint32_t m) {
+    const size_t k = 4 * (size_t)m;
+    const uint32_t s = items[k].pad;
+    if (items[k].len) rans[s].assign(host + items[k].packed_off, host + items[k].packed_off + items[k].len);
+    if (items[k + 1].len) bits[s].assign(host + items[k + 1].packed_off, host + items[k + 1].packed_off + items[k + 1].len);
+    if (hs[s].flags) {
+      const uint32_t *words = (const uint32_t *)(host + items[k + 3].packed_off);
+      flag_bits[s].resize(hs[s].num_flags);
+      for (uint32_t e = 0; e < hs[s].num_flags; ++e) flag_bits[s][e] = (uint8_t)((words[e >> 5] >> (e & 31u)) & 1u);
+    }
+    if (hs[s].kind == 3 && hs[s].nv == 0) return;
+    if (!host_plan) {                      // the bytes in front of the payload: scheme, (raw: unique-symbols bit length), table
+      synth::SymbolPlan &pl = splans[s];
+      pl.method = (int)hs[s].method;
+      pl.coder.num_symbols = hs[s].num_symbols;
+      const uint32_t *pr = (const uint32_t *)(host + items[k + 2].packed_off);
+      pl.coder.prob.assign(pr, pr + hs[s].num_symbols);
+      pl.head.u8((uint8_t)pl.method);
+      if (pl.method != 0) pl.head.u8((uint8_t)hs[s].usbl);
+      pl.coder.write_table(pl.head);
+    }
+  }, 8);
+  return DSA_OK;
+}
+// a symbol stream as encode_symbols writes it: scheme and table, coded bytes, (tagged) the raw bit fields
+static void enc_put_coded(synth::ByteWriter &bw, const synth::SymbolPlan &pl, const std::vector<uint8_t> &rans, const std::vector<uint8_t> &bits, uint32_t method) {
+  bw.bytes(pl.head.d);
+  bw.varint(rans.size());
+  bw.bytes(rans);
+  if (method == 0) bw.bytes(bits);
+}
+
 extern "C" {
 
 void dsa_encode_default_options(dsa_encode_options *o) {
@@ -571,7 +773,10 @@ dsa_status dsa_encode_batch_ex(dsa_context *ctx, uint32_t n, const dsa_mesh_corn
 // those go first (phase A of every chunk in front of any phase B, hostutil::UploadTurns), the attribute values follow while the
 // walks run, on a stream of their own.  Streams of one priority share four hardware queues, on which the kernels of different
 // streams wait for each other: four lanes, their walk streams at another priority.  Small batches are one chunk.
-static dsa_status encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_mesh_corner_input *corners, const dsa_encode_options *options, const dsa_encode_options_ex *ex, dsa_encoded **out) {
+// `code_chunk(sink, lane, base, count, &part)`: codes meshes base .. base + count of the batch on the lane.
+extern "C++" {
+template <class ChunkFn>
+static dsa_status encode_batch_chunks(dsa_context *ctx, uint32_t n, ChunkFn &&code_chunk, dsa_encoded **out) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const uint32_t max_lanes = [&]() { const char *e = getenv("DSA_ENC_LANES"); const int v = e ? atoi(e) : 0; return (uint32_t)(v >= 1 && v <= 16 ? v : 4); }();
   const uint32_t chunk_max = [&]() { const char *e = getenv("DSA_ENC_CHUNK"); const int v = e ? atoi(e) : 0; return (uint32_t)(v >= 1 ? v : 0); }();
@@ -619,7 +824,7 @@ static dsa_status encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_inpu
         ctx->enc_lanes[l]->upload_chunk = c;
         dsa_encoded *part = nullptr;
         const auto t_chunk = std::chrono::steady_clock::now();
-        const dsa_status st = encode_chunk(&sink, *ctx->enc_lanes[l], cnt, n, meshes ? meshes + base : nullptr, corners ? corners + base : nullptr, options, ex, &part);
+        const dsa_status st = code_chunk(&sink, *ctx->enc_lanes[l], base, cnt, &part);
         if (getenv("DSA_ENC_TIMING")) fprintf(stderr, "[dsa_encode_batch] chunk %u (%u meshes) returned after %8.2f ms\n", c, cnt, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_chunk).count());
         if (st != DSA_OK) { errs[l] = sink.err; int ok = DSA_OK; failed.compare_exchange_strong(ok, st); break; }
         std::unique_ptr<dsa_encoded> owner(part);
@@ -640,6 +845,12 @@ static dsa_status encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_inpu
   if (getenv("DSA_ENC_TIMING")) fprintf(stderr, "[dsa_encode_batch] batch of %u done\n", n);
   *out = E.release();
   return DSA_OK;
+}
+}  // extern "C++"
+static dsa_status encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_mesh_corner_input *corners, const dsa_encode_options *options, const dsa_encode_options_ex *ex, dsa_encoded **out) {
+  return encode_batch_chunks(ctx, n, [&](dsa_context *sink, EncLane &lane, uint32_t base, uint32_t cnt, dsa_encoded **part) {
+    return encode_chunk(sink, lane, cnt, n, meshes ? meshes + base : nullptr, corners ? corners + base : nullptr, options, ex, part);
+  }, out);
 }
 static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint32_t batch_n, const dsa_mesh_input *meshes_v, const dsa_mesh_corner_input *corners, const dsa_encode_options *options, const dsa_encode_options_ex *ex, dsa_encoded **out) {
   // mesh i of the chunk, whichever entry point it came through (ids: its corner ids, null without)
@@ -788,7 +999,7 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
   uint64_t cur = in_total, cur_in = 0;
   auto take = [&](uint64_t bytes) { uint64_t at = cur; cur = (cur + bytes + 255) & ~255ull; return at; };
   auto take_in = [&](uint64_t bytes) { uint64_t at = cur_in; cur_in = (cur_in + bytes + 255) & ~255ull; return at; };
-  struct Upload { uint64_t off; const void *src; size_t bytes; bool narrow; };       // narrow: src is u32[bytes / 2], the staging copy keeps the low halves
+  using Upload = EncUpload;
   std::vector<Upload> uploads_a, uploads;          // phase A: what the walks need (the faces, the corner ids); the rest
   uint32_t max_rows = 0;
   std::vector<uint64_t> faces_at(n, 0);
@@ -938,42 +1149,7 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
   dsa::EncSeam *d_seams = nullptr;
   const uint32_t nz = (uint32_t)hz.size();
   auto cleanup = [&]() {};      // the lane owns its device memory (EncLane::Buf): nothing to release per chunk
-#define ENC_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { return set_err(ctx, e_ == hipErrorOutOfMemory ? DSA_ERR_OUT_OF_MEMORY : DSA_ERR_DEVICE, "%s failed: %s", #call, hipGetErrorString(e_)); } } while (0)
-  // pieces of the arena -> one host buffer (items[k].packed_off filled in); host buffer -> pieces of the arena
-  // (with `view`: no copy into `host`; *view points at the pieces in the lane's pinned staging buffer, valid until the gather after next)
-  auto gather = [&](std::vector<dsa::PackItem> &items, std::vector<uint8_t> &host, const uint8_t **view) -> dsa_status {
-    uint64_t total = 0;
-    for (auto &it : items) { it.packed_off = total; total += ((uint64_t)it.len + 15) & ~15ull; }
-    if (view) *view = nullptr; else host.resize(total);
-    if (items.empty() || total == 0) return DSA_OK;
-    uint8_t *d_packed = nullptr; dsa::PackItem *d_items = nullptr;
-    hipError_t e = lane.packed.ensure(total);
-    if (e == hipSuccess) e = lane.items.ensure(sizeof(dsa::PackItem) * items.size());
-    d_packed = (uint8_t *)lane.packed.p; d_items = (dsa::PackItem *)lane.items.p;
-    if (e == hipSuccess) e = hipMemcpyAsync(d_items, items.data(), sizeof(dsa::PackItem) * items.size(), hipMemcpyHostToDevice, lane.st);
-    if (e == hipSuccess) { hipLaunchKernelGGL(dsa::k_enc_pack, dim3((uint32_t)items.size()), dim3(256), 0, lane.st, arena, d_packed, d_items, (uint32_t)items.size()); e = hipGetLastError(); }
-    // through pinned staging (a pageable destination is staged by the runtime at a fraction of the link's rate)
-    hostutil::Staging &stg = lane.stage[lane.next];
-    lane.next ^= 1;
-    if (e == hipSuccess) e = stg.acquire((size_t)total);
-    if (e == hipSuccess) e = hipMemcpyAsync(stg.buf.p, d_packed, total, hipMemcpyDeviceToHost, lane.st);
-    if (e == hipSuccess) e = hipStreamSynchronize(lane.st);
-    if (e == hipSuccess) { if (view) *view = stg.buf.p; else hostutil::parallel_memcpy(host.data(), stg.buf.p, (size_t)total); }
-    return e == hipSuccess ? DSA_OK : (e == hipErrorOutOfMemory ? DSA_ERR_OUT_OF_MEMORY : DSA_ERR_DEVICE);
-  };
-  auto scatter = [&](std::vector<dsa::PackItem> &items, const std::vector<uint8_t> &host) -> dsa_status {
-    if (items.empty() || host.empty()) return DSA_OK;
-    uint8_t *d_packed = nullptr; dsa::PackItem *d_items = nullptr;
-    hipError_t e = lane.packed.ensure(host.size());
-    if (e == hipSuccess) e = lane.items.ensure(sizeof(dsa::PackItem) * items.size());
-    d_packed = (uint8_t *)lane.packed.p; d_items = (dsa::PackItem *)lane.items.p;
-    if (e == hipSuccess) e = hipMemcpyAsync(d_items, items.data(), sizeof(dsa::PackItem) * items.size(), hipMemcpyHostToDevice, lane.st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_packed, host.data(), host.size(), hipMemcpyHostToDevice, lane.st);
-    if (e == hipSuccess) { hipLaunchKernelGGL(dsa::k_enc_unpack, dim3((uint32_t)items.size()), dim3(256), 0, lane.st, arena, d_packed, d_items, (uint32_t)items.size()); e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipStreamSynchronize(lane.st);
-    return e == hipSuccess ? DSA_OK : (e == hipErrorOutOfMemory ? DSA_ERR_OUT_OF_MEMORY : DSA_ERR_DEVICE);
-  };
-#define ENC_ST(call) do { dsa_status s_ = (call); if (s_ != DSA_OK) { return set_err(ctx, s_, "%s failed", #call); } } while (0)
+  auto gather = [&](std::vector<dsa::PackItem> &items, std::vector<uint8_t> &host, const uint8_t **view) { return enc_gather(lane, arena, items, host, view); };
   if (ns) {
     hipStream_t st = lane.st;
     ENC_TRY(lane.arena.ensure(cur ? cur : 256));
@@ -981,35 +1157,7 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
     arena = (uint8_t *)lane.arena.p; d_streams = (dsa::EncStream *)lane.streams.p;
     if (lane.walk_st) ENC_TRY(hipStreamSynchronize(lane.walk_st));     // (idle unless a previous chunk on this lane ended in an error)
     ENC_TRY(hipMemsetAsync(arena, 0, cur, st));              // histograms start at zero
-    // uploads in pieces through the lane's two pinned staging buffers: host threads fill one while the DMA engine drains the
-    // other (a pageable source would be staged by the runtime, one thread, a few GB/s)
-    auto upload = [&](const std::vector<Upload> &ups) -> hipError_t {
-      const uint64_t piece_cap = 192ull << 20;
-      size_t i0 = 0;
-      while (i0 < ups.size()) {
-        const uint64_t lo = ups[i0].off;
-        size_t i1 = i0 + 1;
-        while (i1 < ups.size() && ups[i1].off + ups[i1].bytes - lo <= piece_cap) ++i1;
-        const uint64_t hi = ups[i1 - 1].off + ups[i1 - 1].bytes;
-        hostutil::Staging &stg = lane.stage[lane.next];
-        lane.next ^= 1;
-        hipError_t e = stg.acquire((size_t)(hi - lo));
-        if (e != hipSuccess) return e;
-        uint8_t *h = stg.buf.p;
-        hostutil::parallel_for((uint32_t)(i1 - i0), [&](uint32_t k) {
-          const Upload &u = ups[i0 + k];
-          if (!u.narrow) { memcpy(h + (u.off - lo), u.src, u.bytes); return; }
-          const uint32_t *src = (const uint32_t *)u.src;
-          uint16_t *dst = (uint16_t *)(h + (u.off - lo));               // (offsets are multiples of 256)
-          for (size_t e = 0, ne = u.bytes / 2; e < ne; ++e) dst[e] = (uint16_t)src[e];
-        }, 2);
-        e = hipMemcpyAsync(arena + lo, h, (size_t)(hi - lo), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = stg.submitted(st);
-        if (e != hipSuccess) return e;
-        i0 = i1;
-      }
-      return hipSuccess;
-    };
+    auto upload = [&](const std::vector<Upload> &ups) { return enc_upload(lane, arena, st, ups); };
     turn.acquire_a();
     ENC_TRY(upload(host_conn ? uploads : uploads_a));
     if (host_conn) turn.release();
@@ -1157,117 +1305,14 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
   lap("connectivity results");
   // ---- host phase 2: scheme choice and rANS tables from the device statistics
   std::vector<synth::SymbolPlan> splans(ns);
-  std::vector<std::vector<uint32_t>> hists(ns);
   std::vector<int> stream_mesh(ns, 0);
   for (uint32_t i = 0; i < n; ++i) for (uint32_t s = first_stream[i]; s < first_stream[i + 1]; ++s) stream_mesh[s] = (int)i;
-  if (host_plan) {
-  {
-    std::vector<dsa::PackItem> items;
-    for (uint32_t s = 0; s < ns; ++s) {
-      if (hs[s].kind == 3 && hs[s].nv == 0) continue;
-      if (hs[s].overflow || hs[s].max_value >= hs[s].hist_cap) { hs[s].overflow = 1; continue; }
-      items.push_back({hs[s].hist_raw, 0, 4u * (hs[s].max_value + 1u), s});
-    }
-    std::vector<uint8_t> host;
-    ENC_ST(gather(items, host, nullptr));
-    for (auto &it : items) {
-      hists[it.pad].resize(it.len / 4);
-      memcpy(hists[it.pad].data(), host.data() + it.packed_off, it.len);
-    }
-  }
-  std::vector<std::string> plan_error(ns);
-  auto plan_stream = [&](uint32_t s) {
-    const uint32_t i = (uint32_t)stream_mesh[s];
-    if (E->status[i] != DSA_OK || (hs[s].kind == 3 && hs[s].nv == 0)) return;
-    try {
-      synth::check(!hs[s].overflow, "symbol outside the histogram range");
-      synth::SymbolStats stt;
-      stt.n = (size_t)hs[s].nv * hs[s].nc; stt.nc = (int)hs[s].nc; stt.max_value = hs[s].max_value; stt.total_bl = hs[s].total_bl;
-      stt.tag_freq.assign(hs[s].hist_tag, hs[s].hist_tag + 33);
-      stt.raw_freq.assign(hists[s].begin(), hists[s].end());
-      synth::plan_symbols(stt, opt.force_scheme, opt.compression_level, splans[s]);
-      hs[s].method = (uint32_t)splans[s].method;
-      hs[s].precision_bits = (uint32_t)splans[s].coder.precision_bits;
-      hs[s].num_symbols = splans[s].coder.num_symbols;
-      synth::check(splans[s].coder.num_symbols <= std::max<uint32_t>(hs[s].hist_cap, 64), "alphabet larger than the table region");
-    } catch (const std::exception &e) { plan_error[s] = e.what(); if (plan_error[s].empty()) plan_error[s] = "symbol plan failed"; hs[s].overflow = 1; }
-  };
-  hostutil::parallel_for(ns, plan_stream);
-  {
-    std::vector<dsa::PackItem> items;
-    std::vector<uint8_t> host;
-    for (uint32_t s = 0; s < ns; ++s) {
-      const uint32_t i = (uint32_t)stream_mesh[s];
-      if (E->status[i] != DSA_OK) continue;
-      if (!plan_error[s].empty()) { E->status[i] = DSA_ERR_INVALID_DATA; E->messages[i] = plan_error[s]; continue; }
-      const uint32_t bytes = 4u * splans[s].coder.num_symbols;
-      for (int t = 0; t < 2; ++t) {
-        const std::vector<uint32_t> &src = t == 0 ? splans[s].coder.prob : splans[s].coder.cum;
-        items.push_back({t == 0 ? hs[s].prob : hs[s].cum, (uint64_t)host.size(), bytes, s});
-        host.insert(host.end(), (const uint8_t *)src.data(), (const uint8_t *)src.data() + bytes);
-        host.resize((host.size() + 15) & ~(size_t)15);
-      }
-    }
-    ENC_ST(scatter(items, host));
-  }
-  } else {
-    for (uint32_t s = 0; s < ns; ++s) {
-      const uint32_t i = (uint32_t)stream_mesh[s];
-      if (E->status[i] != DSA_OK || !hs[s].overflow) continue;
-      E->status[i] = DSA_ERR_INVALID_DATA;
-      E->messages[i] = hs[s].plan_status ? dsa::plan::plan_message((int)hs[s].plan_status) : "symbol outside the histogram range";
-    }
-  }
+  if (host_plan) { const dsa_status ps = enc_host_plans(ctx, lane, arena, hs, stream_mesh, E, opt, splans); if (ps != DSA_OK) return ps; }
+  else enc_device_plan_errors(hs, stream_mesh, E);
   lap("histograms + symbol plans");
   // ---- device phase 2: entropy coding
   std::vector<std::vector<uint8_t>> rans(ns), bits(ns), flag_bits(ns);
-  if (ns) {
-    hipStream_t st = lane.st;
-    if (host_plan) {
-      ENC_TRY(hipMemcpyAsync(d_streams, hs.data(), sizeof(dsa::EncStream) * ns, hipMemcpyHostToDevice, st));
-      hipLaunchKernelGGL(dsa::k_enc_rans, dim3(ns), dim3(WAVE), 0, st, arena, d_streams, ns);
-      ENC_TRY(hipMemcpyAsync(hs.data(), d_streams, sizeof(dsa::EncStream) * ns, hipMemcpyDeviceToHost, st));
-      ENC_TRY(hipStreamSynchronize(st));
-    }
-    // coded bytes of every stream (and, when k_enc_plan made them, the probability tables: the stream carries them)
-    // and the side bits of TexCoordsPortable / GeometricNormal, packed
-    std::vector<dsa::PackItem> items;
-    for (uint32_t s = 0; s < ns; ++s) {
-      if (hs[s].overflow || E->status[stream_mesh[s]] != DSA_OK) continue;
-      if (hs[s].kind == 1 && hs[s].prediction == 6) hs[s].num_flags = hs[s].nv;
-      items.push_back({hs[s].out_rans, 0, hs[s].rans_len, s});
-      items.push_back({hs[s].out_bits, 0, hs[s].bits_len, s});
-      items.push_back({hs[s].prob, 0, host_plan ? 0u : 4u * hs[s].num_symbols, s});
-      items.push_back({hs[s].flags, 0, hs[s].flags ? 4u * ((hs[s].num_flags + 31u) / 32u) : 0u, s});
-    }
-    std::vector<uint8_t> unused;
-    const uint8_t *host = nullptr;
-    ENC_ST(gather(items, unused, &host));
-    hostutil::parallel_for((uint32_t)(items.size() / 4), [&](uint32_t m) {
-      const size_t k = 4 * (size_t)m;
-      const uint32_t s = items[k].pad;
-      if (items[k].len) rans[s].assign(host + items[k].packed_off, host + items[k].packed_off + items[k].len);
-      if (items[k + 1].len) bits[s].assign(host + items[k + 1].packed_off, host + items[k + 1].packed_off + items[k + 1].len);
-      if (hs[s].flags) {
-        const uint32_t *words = (const uint32_t *)(host + items[k + 3].packed_off);
-        flag_bits[s].resize(hs[s].num_flags);
-        for (uint32_t e = 0; e < hs[s].num_flags; ++e) flag_bits[s][e] = (uint8_t)((words[e >> 5] >> (e & 31u)) & 1u);
-      }
-      if (hs[s].kind == 3 && hs[s].nv == 0) return;
-      if (!host_plan) {                      // the bytes in front of the payload: scheme, (raw: unique-symbols bit length), table
-        synth::SymbolPlan &pl = splans[s];
-        pl.method = (int)hs[s].method;
-        pl.coder.num_symbols = hs[s].num_symbols;
-        const uint32_t *pr = (const uint32_t *)(host + items[k + 2].packed_off);
-        pl.coder.prob.assign(pr, pr + hs[s].num_symbols);
-        pl.head.u8((uint8_t)pl.method);
-        if (pl.method != 0) pl.head.u8((uint8_t)hs[s].usbl);
-        pl.coder.write_table(pl.head);
-      }
-    }, 8);
-  }
-#undef ENC_TRY
-#undef ENC_ST
+  if (ns) { const dsa_status cs = enc_code_streams(ctx, lane, arena, d_streams, hs, stream_mesh, E, host_plan, splans, rans, bits, flag_bits); if (cs != DSA_OK) return cs; }
   lap("device phase 2 + downloads");
   cleanup();
   // ---- host phase 3: stream layout (threads over meshes; write_stream may throw like any part of the host coder)
@@ -1278,13 +1323,7 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
     if (bad) { E->status[i] = DSA_ERR_INVALID_DATA; E->messages[i] = "entropy coding failed"; return; }
     synth::ByteWriter w;
     const uint32_t s0 = first_stream[i];
-    // a symbol stream as encode_symbols writes it: scheme and table, coded bytes, (tagged) the raw bit fields
-    auto coded = [&](synth::ByteWriter &bw, uint32_t s) {
-      bw.bytes(splans[s].head.d);
-      bw.varint(rans[s].size());
-      bw.bytes(rans[s]);
-      if (hs[s].method == 0) bw.bytes(bits[s]);
-    };
+    auto coded = [&](synth::ByteWriter &bw, uint32_t s) { enc_put_coded(bw, splans[s], rans[s], bits[s], hs[s].method); };
     try {
     synth::MeshPlan &pl = plans[i];
     if (pl.valence) {                                        // the six context lists: their streams follow the attributes'
@@ -1337,3 +1376,8 @@ dsa_status dsa_encoded_stream(const dsa_encoded *e, uint32_t mesh, const uint8_t
 void dsa_encoded_free(dsa_encoded *e) { delete e; }
 
 }  // extern "C"
+
+#include "dsa_encode_sequential.h"
+
+#undef ENC_TRY
+#undef ENC_ST

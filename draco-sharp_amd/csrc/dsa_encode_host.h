@@ -1358,45 +1358,73 @@ static void encode_mesh(const MeshIn &in, const Options &opt, std::vector<uint8_
   out.swap(w.d);
 }
 
-// Sequential mesh (Mesh/MeshSequentialEncoder.cs:9-121 with the bitstream's index widths): faces as point indices,
-// compressed (differences, sign in the LSB, through the symbol coder) or raw; one attributes encoder with a linear
-// sequencer, so values are in point order and predicted by Difference + Wrap / canonicalised octahedral delta.
-static void encode_mesh_sequential(const MeshIn &in, const Options &opt, bool compressed, std::vector<uint8_t> &out) {
-  ByteWriter w;
+// ------------------------------------------------------------------ sequential streams
+// Sequential mesh (Mesh/MeshSequentialEncoder.cs:9-121 with the bitstream's index widths) and sequential point cloud
+// (PointCloud/PointCloudSequentialEncoder.cs): faces as point indices, compressed (differences, sign in the LSB, through the
+// symbol coder) or raw; one attributes encoder with a linear sequencer (Attributes/LinearSequencer.cs), so values are in point
+// order and predicted by Difference + Wrap / canonicalised octahedral delta.
+
+// Attribute descriptors of a sequential stream: positions, normals, texture coordinates, the generic uint8 attribute; all Difference.
+static void plan_sequential_attributes(const MeshIn &in, const Options &opt, std::vector<PortableAttr> &atts) {
+  atts.clear();
+  { PortableAttr a; a.att_type = 0; a.nc = a.nc_out = 3; a.seq_type = 2; a.data_type = 9; a.prediction = 0; a.bits = opt.pos_bits; atts.push_back(a); }
+  if (in.normals) { PortableAttr a; a.att_type = 1; a.nc_out = 3; a.nc = 2; a.seq_type = 3; a.data_type = 9; a.bits = opt.normal_bits; a.prediction = 0; atts.push_back(a); }
+  if (in.uvs) { PortableAttr a; a.att_type = 3; a.nc = a.nc_out = 2; a.seq_type = 2; a.data_type = 9; a.prediction = 0; a.bits = opt.uv_bits; atts.push_back(a); }
+  if (in.generic) { PortableAttr a; a.att_type = 4; a.nc = a.nc_out = opt.generic_components >= 1 && opt.generic_components <= 4 ? opt.generic_components : 1; a.seq_type = 1; a.data_type = 2; a.prediction = 0; atts.push_back(a); }
+}
+// Compressed indices: symbol k = |f[k] - f[k-1]| << 1 | sign, f[-1] = 0 (MeshSequentialEncoder.cs:84-121)
+static void sequential_index_symbols(const uint32_t *faces, size_t count, std::vector<uint32_t> &sym) {
+  sym.resize(count);
+  int64_t last = 0;
+  for (size_t k = 0; k < count; ++k) {
+    const int64_t diff = (int64_t)faces[k] - last;
+    sym[k] = ((uint32_t)(diff < 0 ? -diff : diff) << 1) | (diff < 0 ? 1u : 0u);
+    last = faces[k];
+  }
+}
+// Raw indices at the bitstream's widths: u8 below 256 points, u16 below 65 536, varint below 2^21, u32 from there
+// (MeshSequentialDecoder.cs:30-75); straight from the caller's array to the end of the stream.
+static void write_raw_indices(ByteWriter &w, const uint32_t *faces, size_t count, uint32_t nv) {
+  const size_t at = w.d.size();
+  if (nv < 256) { w.d.resize(at + count); uint8_t *o = w.d.data() + at; for (size_t k = 0; k < count; ++k) o[k] = (uint8_t)faces[k]; }
+  else if (nv < (1u << 16)) { w.d.resize(at + 2 * count); uint8_t *o = w.d.data() + at; for (size_t k = 0; k < count; ++k) { o[2 * k] = (uint8_t)faces[k]; o[2 * k + 1] = (uint8_t)(faces[k] >> 8); } }
+  else if (nv < (1u << 21)) { w.d.reserve(at + 3 * count); for (size_t k = 0; k < count; ++k) w.varint(faces[k]); }
+  else { w.d.resize(at + 4 * count); uint8_t *o = w.d.data() + at; for (size_t k = 0; k < count; ++k) for (int b = 0; b < 4; ++b) o[4 * k + b] = (uint8_t)(faces[k] >> (8 * b)); }
+}
+// The byte layout of both stream kinds from pieces coded on either side (the CPU coder below, the device encoder of
+// dsa_encode_sequential.h): header, (mesh: counts, connectivity method, indices through `indices`), one attributes encoder,
+// then every attribute's values and every attribute's transform parameters through the callbacks.
+template <class IndexWriter, class ValuesWriter, class TransformWriter>
+static void write_sequential_stream(ByteWriter &w, bool mesh, uint32_t nv, uint32_t nf, bool compressed, const std::vector<PortableAttr> &atts,
+                                    IndexWriter &&indices, ValuesWriter &&values, TransformWriter &&transform) {
   w.d.insert(w.d.end(), {'D', 'R', 'A', 'C', 'O'});
-  w.u8(2); w.u8(2); w.u8(1); w.u8(0); w.u16(0);
-  w.varint(in.nf);
-  w.varint(in.nv);
-  if (compressed) {
-    w.u8(0);
-    std::vector<uint32_t> sym((size_t)in.nf * 3);
-    int64_t last = 0;
-    for (size_t k = 0; k < sym.size(); ++k) {
-      const int64_t diff = (int64_t)in.faces[k] - last;
-      sym[k] = ((uint32_t)(diff < 0 ? -diff : diff) << 1) | (diff < 0 ? 1u : 0u);
-      last = in.faces[k];
-    }
-    encode_symbols(w, sym, 1, opt.force_scheme, opt.compression_level);
-  } else {
-    w.u8(1);
-    for (size_t k = 0; k < (size_t)in.nf * 3; ++k) {
-      const uint32_t v = in.faces[k];
-      if (in.nv < 256) w.u8((uint8_t)v);
-      else if (in.nv < (1u << 16)) w.u16((uint16_t)v);
-      else if (in.nv < (1u << 21)) w.varint(v);
-      else w.u32(v);
-    }
-  }
+  w.u8(2); w.u8(2); w.u8(mesh ? 1 : 0); w.u8(0); w.u16(0);
+  if (mesh) {
+    w.varint(nf);
+    w.varint(nv);
+    w.u8(compressed ? 0 : 1);
+    indices(w);
+  } else w.i32((int32_t)nv);
+  w.u8(1);
+  w.varint(atts.size());
+  for (size_t i = 0; i < atts.size(); ++i) { w.u8((uint8_t)atts[i].att_type); w.u8((uint8_t)atts[i].data_type); w.u8((uint8_t)atts[i].nc_out); w.u8(0); w.varint(i); }
+  for (auto &a : atts) w.u8((uint8_t)a.seq_type);
+  for (size_t i = 0; i < atts.size(); ++i) values(w, i);
+  for (size_t i = 0; i < atts.size(); ++i) transform(w, i);
+}
+// The CPU coder of both kinds: `mesh` false writes a point cloud of in.nv points (in.faces is not read).
+static void encode_sequential(const MeshIn &in, const Options &opt, bool mesh, bool compressed, std::vector<uint8_t> &out) {
   std::vector<PortableAttr> atts;
-  { PortableAttr a; a.att_type = 0; a.nc = a.nc_out = 3; a.seq_type = 2; a.data_type = 9; a.prediction = 0; quantize(in.pos, in.nv, 3, opt.pos_bits, a); atts.push_back(a); }
-  if (in.normals) {
-    PortableAttr a; a.att_type = 1; a.nc_out = 3; a.nc = 2; a.seq_type = 3; a.data_type = 9; a.bits = opt.normal_bits; a.prediction = 0;
-    Octa o(opt.normal_bits);
-    a.vals.resize((size_t)in.nv * 2);
-    for (uint32_t v = 0; v < in.nv; ++v) { int s, t; o.from_float_vector(in.normals + (size_t)v * 3, s, t); a.vals[(size_t)v * 2] = s; a.vals[(size_t)v * 2 + 1] = t; }
-    atts.push_back(a);
+  plan_sequential_attributes(in, opt, atts);
+  for (auto &a : atts) {
+    if (a.att_type == 0) quantize(in.pos, in.nv, 3, opt.pos_bits, a);
+    else if (a.att_type == 1) {
+      Octa o(opt.normal_bits);
+      a.vals.resize((size_t)in.nv * 2);
+      for (uint32_t v = 0; v < in.nv; ++v) { int s, t; o.from_float_vector(in.normals + (size_t)v * 3, s, t); a.vals[(size_t)v * 2] = s; a.vals[(size_t)v * 2 + 1] = t; }
+    } else if (a.att_type == 3) quantize(in.uvs, in.nv, 2, opt.uv_bits, a);
+    else { a.vals.resize((size_t)in.nv * a.nc); for (size_t k = 0; k < (size_t)in.nv * a.nc; ++k) a.vals[k] = in.generic[k]; }
   }
-  if (in.uvs) { PortableAttr a; a.att_type = 3; a.nc = a.nc_out = 2; a.seq_type = 2; a.data_type = 9; a.prediction = 0; quantize(in.uvs, in.nv, 2, opt.uv_bits, a); atts.push_back(a); }
   // linear order: entry i = point i.  write_attribute_values wants a corner table and a sequence: an identity stand-in
   CornerTable ct;
   ct.c2v.resize(in.nv);
@@ -1404,38 +1432,31 @@ static void encode_mesh_sequential(const MeshIn &in, const Options &opt, bool co
   Sequence seq;
   seq.data_to_corner.resize(in.nv);
   for (uint32_t v = 0; v < in.nv; ++v) seq.data_to_corner[v] = v;
-  w.u8(1);
-  w.varint(atts.size());
-  for (size_t i = 0; i < atts.size(); ++i) { w.u8((uint8_t)atts[i].att_type); w.u8((uint8_t)atts[i].data_type); w.u8((uint8_t)atts[i].nc_out); w.u8(0); w.varint(i); }
-  for (auto &a : atts) w.u8((uint8_t)a.seq_type);
-  for (auto &a : atts) write_attribute_values(w, a, ct, ct, seq, opt);
-  for (auto &a : atts) write_attribute_transform(w, a);
+  ByteWriter w;
+  write_sequential_stream(w, mesh, in.nv, in.nf, compressed, atts,
+                          [&](ByteWriter &bw) {
+                            if (!compressed) { write_raw_indices(bw, in.faces, (size_t)in.nf * 3, in.nv); return; }
+                            std::vector<uint32_t> sym;
+                            sequential_index_symbols(in.faces, (size_t)in.nf * 3, sym);
+                            encode_symbols(bw, sym, 1, opt.force_scheme, opt.compression_level);
+                          },
+                          [&](ByteWriter &bw, size_t i) { write_attribute_values(bw, atts[i], ct, ct, seq, opt); },
+                          [&](ByteWriter &bw, size_t i) { write_attribute_transform(bw, atts[i]); });
   out.swap(w.d);
 }
-
-// Point cloud, sequential (BASELINE config 1): int32 num_points, one attributes
-// decoder, positions quantised, Difference + Wrap in linear order.
+// (the entry points of before the generic attribute joined: positions, normals, texture coordinates)
+static void encode_mesh_sequential(const MeshIn &in, const Options &opt, bool compressed, std::vector<uint8_t> &out) {
+  MeshIn m = in;
+  m.generic = nullptr;
+  encode_sequential(m, opt, true, compressed, out);
+}
+// Point cloud, sequential (BASELINE config 1), positions only: int32 num_points, one attributes decoder, positions quantised,
+// Difference + Wrap in linear order, always through the symbol coder.
 static void encode_point_cloud(const float *pos, uint32_t n, const Options &opt, std::vector<uint8_t> &out) {
-  PortableAttr a; a.att_type = 0; a.nc = a.nc_out = 3; a.seq_type = 2; a.data_type = 9; a.prediction = 0;
-  quantize(pos, n, 3, opt.pos_bits, a);
-  ByteWriter w;
-  w.d.insert(w.d.end(), {'D', 'R', 'A', 'C', 'O'});
-  w.u8(2); w.u8(2); w.u8(0); w.u8(0); w.u16(0);
-  w.i32((int32_t)n);
-  w.u8(1);
-  w.varint(1);
-  w.u8(0); w.u8(9); w.u8(3); w.u8(0); w.varint(0);
-  w.u8(2);
-  WrapEnc wr; wr.init(a.vals);
-  w.i8(0); w.i8(1);
-  std::vector<uint32_t> symbols((size_t)n * 3);
-  for (size_t p = n; p-- > 0;)
-    for (int c = 0; c < 3; ++c) symbols[p * 3 + c] = zigzag(wr.corr(a.vals[p * 3 + c], p ? a.vals[(p - 1) * 3 + c] : 0));
-  w.u8(1);
-  encode_symbols(w, symbols, 3, opt.force_scheme, opt.compression_level);
-  w.i32(wr.mn); w.i32(wr.mx);
-  write_attribute_transform(w, a);
-  out.swap(w.d);
+  MeshIn in{pos, n, nullptr, 0, nullptr, nullptr, nullptr};
+  Options o = opt;
+  o.raw_integers = 0; o.no_prediction = 0;
+  encode_sequential(in, o, false, false, out);
 }
 
 }  // namespace synth

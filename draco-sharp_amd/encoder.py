@@ -21,16 +21,24 @@ class Config:
 
     The method ids are the format's own: edgebreaker_method 0 standard, 2 valence, -1 the reference's rule per mesh (valence at
     speed < 5 for meshes of 1000 faces or more); position_prediction 0 difference, 1 parallelogram; texcoord_prediction also 5
-    TexCoordsPortable; normal_prediction 0 difference, 6 GeometricNormal.  Defaults write what the speed-5 default writes."""
+    TexCoordsPortable; normal_prediction 0 difference, 6 GeometricNormal.  Defaults write what the speed-5 default writes.
+
+    encoding_method (Constants.cs EncodingMethod): 1 Edgebreaker (default), 0 sequential -- faces as point indices, points and
+    faces in the caller's order, any list of triangles legal -- or -1 the reference's rule (DracoEncoder.cs:43-57: sequential
+    exactly when speed == 10).  compress_connectivity (ConfigOptionName.CompressConnectivity) chooses compressed over raw indices
+    of a sequential mesh.  A sequential stream predicts by Difference: the prediction and connectivity options above do not shape it."""
 
     EDGEBREAKER_METHODS = (0, 2, -1)
     POSITION_PREDICTIONS = (0, 1)
     TEXCOORD_PREDICTIONS = (0, 1, 5)
     NORMAL_PREDICTIONS = (0, 6)
+    ENCODING_METHODS = (1, 0, -1)
 
     def __init__(self, position_bits=11, texcoord_bits=10, normal_bits=8, speed=5, single_connectivity=False,
-                 symbol_scheme=-1, position_prediction=1, texcoord_prediction=1, edgebreaker_method=0, normal_prediction=0):
-        for name, value, legal in (("edgebreaker_method", edgebreaker_method, self.EDGEBREAKER_METHODS),
+                 symbol_scheme=-1, position_prediction=1, texcoord_prediction=1, edgebreaker_method=0, normal_prediction=0,
+                 encoding_method=1, compress_connectivity=False):
+        for name, value, legal in (("encoding_method", encoding_method, self.ENCODING_METHODS),
+                                   ("edgebreaker_method", edgebreaker_method, self.EDGEBREAKER_METHODS),
                                    ("position_prediction", position_prediction, self.POSITION_PREDICTIONS),
                                    ("texcoord_prediction", texcoord_prediction, self.TEXCOORD_PREDICTIONS),
                                    ("normal_prediction", normal_prediction, self.NORMAL_PREDICTIONS)):
@@ -42,6 +50,20 @@ class Config:
         self.symbol_scheme = symbol_scheme
         self.position_prediction, self.texcoord_prediction = position_prediction, texcoord_prediction
         self.edgebreaker_method, self.normal_prediction = edgebreaker_method, normal_prediction
+        self.encoding_method, self.compress_connectivity = encoding_method, bool(compress_connectivity)
+
+    @property
+    def sequential(self):
+        """True when meshes are written as sequential streams: asked for, or by the reference's rule at speed 10."""
+        return self.encoding_method == 0 or (self.encoding_method == -1 and self.speed == 10)
+
+    def _native_sequential(self, geometry):
+        o = native.EncodeSequentialOptions()
+        native.lib().dsa_encode_sequential_default_options(C.byref(o))
+        o.base = self._native()
+        o.geometry = geometry
+        o.compress_connectivity = 1 if (self.compress_connectivity and geometry == 1) else 0
+        return o
 
     @property
     def extended(self):
@@ -111,6 +133,28 @@ class MeshData:
         return getattr(self, "normal_corners", None) is not None or getattr(self, "texcoord_corners", None) is not None
 
 
+class PointCloudData:
+    """Point cloud with per-point attributes: positions (N,3) f32, optional normals (N,3), texcoords (N,2) and one generic uint8
+    attribute of 1 - 4 components (N,) or (N,C).  Written as a sequential point-cloud stream (dsa_encode_sequential_batch,
+    geometry 0): point i of the stream is row i."""
+
+    def __init__(self, positions, normals=None, texcoords=None, generic=None):
+        self.positions = np.ascontiguousarray(positions, np.float32)
+        self.faces = np.zeros((0, 3), np.uint32)
+        self.normals = None if normals is None else np.ascontiguousarray(normals, np.float32)
+        self.texcoords = None if texcoords is None else np.ascontiguousarray(texcoords, np.float32)
+        for a, nc, name in ((self.positions, 3, "positions"), (self.normals, 3, "normals"), (self.texcoords, 2, "texcoords")):
+            if a is not None and (a.ndim != 2 or a.shape[1] != nc or len(a) != len(self.positions)):
+                raise ValueError("%s: one row of %d components per point" % (name, nc))
+        self.generic = None
+        if generic is not None:
+            g = np.ascontiguousarray(generic, np.uint8)
+            g = g.reshape(len(g), -1)
+            if len(g) != len(self.positions) or not 1 <= g.shape[1] <= 4:
+                raise ValueError("generic attribute: one row of 1 - 4 uint8 components per point")
+            self.generic = g
+
+
 class EncodedStreams:
     """The .drc streams of a batch, a sequence of `bytes`.  The bytes stay in the library's buffers until a stream is asked
     for (indexing, iteration), so that a caller who hands the batch on -- to a file, a socket, dsa.Batch -- pays for one copy of
@@ -172,11 +216,21 @@ class DracoEncoder:
         self._ctx = context
 
     def EncodeBatch(self, meshes, config=None):
-        """meshes: list of MeshData -> sequence of bytes (.drc streams, EncodedStreams).  A mesh that cannot be encoded raises."""
-        ctx = self._ctx or default_context()
-        L = native.lib()
+        """meshes: list of MeshData (or of PointCloudData) -> sequence of bytes (.drc streams, EncodedStreams).  A sequential
+        config (Config.sequential) and point clouds go through dsa_encode_sequential_batch.  A mesh that cannot be encoded raises."""
         n = len(meshes)
         config = config or Config()
+        # what the batch is, before anything touches the device: meshes or point clouds, not both; a sequential stream has one
+        # value per point
+        clouds = sum(1 for m in meshes if isinstance(m, PointCloudData))
+        if clouds and clouds != n:
+            raise ValueError("a batch holds meshes or point clouds, not both")
+        if (clouds or config.sequential) and any(getattr(m, "per_corner", False) for m in meshes):
+            raise ValueError("attributes given per corner need Edgebreaker connectivity (encoding_method 1): a sequential stream has one value per point")
+        ctx = self._ctx or default_context()
+        L = native.lib()
+        if clouds or config.sequential:
+            return self._encode_sequential(ctx, meshes, config, 0 if clouds else 1)
         ex = config.extended
         # the corner entry point only when some mesh carries ids (or an option needs dsa_encode_batch_ex, which takes the corner
         # form); otherwise exactly the per-vertex call
@@ -209,6 +263,27 @@ class DracoEncoder:
         if os.environ.get("DSA_ENC_TIMING"):            # diagnostics, like the library's own phase clocks
             print("[EncodeBatch] native call %.1f ms, result handles %.1f ms" % ((t1 - t0) * 1e3, (time.perf_counter() - t1) * 1e3), flush=True)
         return r
+
+    def _encode_sequential(self, ctx, meshes, config, geometry):
+        L = native.lib()
+        n = len(meshes)
+        arr = (native.MeshInput * max(1, n))()
+        for i, m in enumerate(meshes):
+            mi = arr[i]
+            mi.num_vertices, mi.num_faces = len(m.positions), len(m.faces)
+            mi.positions = m.positions.ctypes.data
+            mi.faces = m.faces.ctypes.data if len(m.faces) else None
+            mi.normals = m.normals.ctypes.data if m.normals is not None else None
+            mi.texcoords = m.texcoords.ctypes.data if m.texcoords is not None else None
+            g = getattr(m, "generic", None)
+            mi.generic = g.ctypes.data if g is not None else None
+            mi.generic_components = g.shape[1] if g is not None else 0
+        opt = config._native_sequential(geometry)
+        h = C.c_void_p()
+        st = L.dsa_encode_sequential_batch(ctx._h, n, arr, C.byref(opt), C.byref(h))
+        if st != 0:
+            _raise(st, ctx.error())
+        return EncodedStreams(ctx, h, n)
 
     def Encode(self, mesh, config=None):
         return self.EncodeBatch([mesh], config)[0]

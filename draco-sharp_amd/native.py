@@ -23,7 +23,8 @@ EXPORTS = [
     "dsa_host_alloc", "dsa_host_free", "dsa_host_register", "dsa_host_unregister", "dsa_batch_copy_metadata", "dsa_batch_copy_debug", "dsa_context_set_profiling", "dsa_batch_stage_times",
     "dsa_batch_kernel_times", "dsa_context_trim", "dsa_context_schedule_note",
     "dsa_encode_default_options", "dsa_encode_batch", "dsa_encode_batch_corners",
-    "dsa_encode_default_options_ex", "dsa_encode_batch_ex", "dsa_encoded_size", "dsa_encoded_stream", "dsa_encoded_free",
+    "dsa_encode_default_options_ex", "dsa_encode_batch_ex", "dsa_encode_sequential_default_options", "dsa_encode_sequential_batch",
+    "dsa_encoded_size", "dsa_encoded_stream", "dsa_encoded_free",
     "dsa_pool_create", "dsa_pool_destroy", "dsa_pool_size", "dsa_pool_last_error", "dsa_pool_decode", "dsa_pool_job_locate",
     "dsa_pool_job_chunks", "dsa_pool_job_free", "dsa_pool_plan",
 ]
@@ -39,6 +40,13 @@ class EncodeOptionsEx(C.Structure):
     """dsa_encode_options_ex: valence Edgebreaker (edgebreaker_method 2, or -1 by speed and face count) and GeometricNormal
     (normal_prediction 6) beside the options of dsa_encode_batch."""
     _fields_ = [("base", EncodeOptions), ("edgebreaker_method", C.c_int32), ("normal_prediction", C.c_int32),
+                ("reserved", C.c_int32 * 6)]
+
+
+class EncodeSequentialOptions(C.Structure):
+    """dsa_encode_sequential_options: sequential meshes (geometry 1; compress_connectivity 0 raw indices, 1 compressed) and point
+    clouds (geometry 0) beside the quantisation bits, symbol_scheme and compression_level of dsa_encode_batch."""
+    _fields_ = [("base", EncodeOptions), ("geometry", C.c_int32), ("compress_connectivity", C.c_int32),
                 ("reserved", C.c_int32 * 6)]
 
 
@@ -149,6 +157,9 @@ def lib():
         L.dsa_encode_default_options_ex.argtypes = [C.POINTER(EncodeOptionsEx)]
         L.dsa_encode_default_options_ex.restype = None
         L.dsa_encode_batch_ex.argtypes = [vp, u32, C.POINTER(MeshCornerInput), C.POINTER(EncodeOptionsEx), C.POINTER(vp)]
+        L.dsa_encode_sequential_default_options.argtypes = [C.POINTER(EncodeSequentialOptions)]
+        L.dsa_encode_sequential_default_options.restype = None
+        L.dsa_encode_sequential_batch.argtypes = [vp, u32, C.POINTER(MeshInput), C.POINTER(EncodeSequentialOptions), C.POINTER(vp)]
         L.dsa_encoded_size.restype = u32
         L.dsa_encoded_size.argtypes = [vp]
         L.dsa_encoded_stream.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(C.c_size_t)]

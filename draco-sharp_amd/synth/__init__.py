@@ -49,6 +49,8 @@ def lib():
                                                C.POINTER(C.c_size_t)]
         L.synth_encode_mesh_sequential.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int,
                                                    C.POINTER(Options), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+        L.synth_encode_sequential.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                              C.c_int, C.POINTER(Options), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
         L.synth_free.argtypes = [C.c_void_p]
         L.synth_make_mesh.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_uint32),
                                       C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -171,6 +173,52 @@ def encode_point_cloud(pos, opt=None):
     data = C.string_at(out, n.value)
     L.synth_free(out)
     return data
+
+
+def _sequential(pos, faces, normals, uvs, generic, geometry, compressed, opt):
+    L = lib()
+    pos = np.ascontiguousarray(pos, np.float32)
+    faces = None if faces is None else np.ascontiguousarray(faces, np.uint32)
+    nrm = None if normals is None else np.ascontiguousarray(normals, np.float32)
+    uv = None if uvs is None else np.ascontiguousarray(uvs, np.float32)
+    opt = opt or options()
+    gen = None
+    if generic is not None:
+        gen = np.ascontiguousarray(generic, np.uint8)
+        gen = gen.reshape(len(gen), -1)
+        if len(gen) != len(pos) or not 1 <= gen.shape[1] <= 4:
+            raise ValueError("generic attribute: one row of 1 - 4 uint8 components per point")
+        if opt.generic_components != gen.shape[1]:          # the components are the array's own (a copy: the caller's options stay)
+            o2 = Options()
+            C.memmove(C.byref(o2), C.byref(opt), C.sizeof(Options))
+            o2.generic_components = gen.shape[1]
+            opt = o2
+    for a, name in ((nrm, "normals"), (uv, "uvs")):
+        if a is not None and len(a) != len(pos):
+            raise ValueError("%s: one row per point" % name)
+    out, n = C.c_void_p(), C.c_size_t()
+    rc = L.synth_encode_sequential(pos.ctypes.data, len(pos), None if faces is None else faces.ctypes.data,
+                                   0 if faces is None else len(faces), None if nrm is None else nrm.ctypes.data,
+                                   None if uv is None else uv.ctypes.data, None if gen is None else gen.ctypes.data,
+                                   geometry, 1 if compressed else 0, C.byref(opt), C.byref(out), C.byref(n))
+    if rc:
+        raise RuntimeError(_err())
+    data = C.string_at(out, n.value)
+    L.synth_free(out)
+    return data
+
+
+def encode_sequential(pos, faces, normals=None, uvs=None, generic=None, compressed=False, opt=None):
+    """Sequential mesh stream with every per-vertex attribute (generic: uint8 (V,) or (V, 1..4)): faces and points keep the
+    caller's order; any list of triangles over the points is legal.  compressed: indices through the symbol coder, else raw
+    at the bitstream's widths.  What dsa_encode_sequential_batch must write for geometry 1."""
+    return _sequential(pos, faces, normals, uvs, generic, 1, compressed, opt)
+
+
+def encode_point_cloud_attributes(pos, normals=None, uvs=None, generic=None, opt=None):
+    """Sequential point cloud with per-point normals / texture coordinates / generic uint8 attribute; positions only:
+    the bytes of encode_point_cloud.  What dsa_encode_sequential_batch must write for geometry 0."""
+    return _sequential(pos, None, normals, uvs, generic, 0, False, opt)
 
 
 def make_batch(kind, nx, ny, seed0, count, normals=True, uvs=True, opt=None, threads=None):

@@ -201,6 +201,26 @@ int synth_encode_point_cloud(const float *pos, uint32_t n, const synth_options *
     return 0;
   } catch (const std::exception &e) { snprintf(g_err, sizeof(g_err), "%s", e.what()); return 1; }
 }
+// Sequential stream of either kind with every per-vertex attribute (dsa_encode_host.h encode_sequential): geometry 1 a triangle mesh
+// (compressed: indices through the symbol coder, else raw), 0 a point cloud of nv points (faces must be absent).  normals / uvs /
+// generic may be NULL; generic: nv rows of opt->generic_components bytes.
+int synth_encode_sequential(const float *pos, uint32_t nv, const uint32_t *faces, uint32_t nf, const float *normals, const float *uvs,
+                            const uint8_t *generic, int geometry, int compressed, const synth_options *opt, uint8_t **out, size_t *out_len) {
+  try {
+    synth::check(geometry == 0 || geometry == 1, "geometry: 1 (triangular mesh) or 0 (point cloud)");
+    synth::check(geometry == 1 || nf == 0, "a point cloud has no faces");
+    synth::check(pos != nullptr && nv > 0, "positions are missing");
+    synth::check(geometry == 0 || (faces != nullptr && nf > 0), "a mesh needs faces");
+    for (size_t k = 0; k < (size_t)nf * 3; ++k) synth::check(faces[k] < nv, "face index out of range");
+    synth::MeshIn in{pos, nv, faces, nf, normals, uvs, generic};
+    std::vector<uint8_t> buf;
+    synth::encode_sequential(in, to_opt(opt), geometry == 1, compressed != 0, buf);
+    *out = (uint8_t *)malloc(buf.size() ? buf.size() : 1);
+    memcpy(*out, buf.data(), buf.size());
+    *out_len = buf.size();
+    return 0;
+  } catch (const std::exception &e) { snprintf(g_err, sizeof(g_err), "%s", e.what()); return 1; }
+}
 void synth_free(uint8_t *p) { free(p); }
 
 // Procedural mesh: returns counts; call once with NULL outputs to size, then again to fill.

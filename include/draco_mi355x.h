@@ -218,7 +218,8 @@ const char *dsa_context_schedule_note(const dsa_context *ctx);
 
 /* ------------------------------------------------------------------ encode direction
  * Drop-in for DracoEncoder.Encode(BinaryWriter, Config, PointCloud, attributes)   src/Draco/IO/DracoEncoder.cs:22-41
- * on a batch of triangle meshes with per-vertex attributes: Edgebreaker (standard traversal) connectivity, quantisation,
+ * on a batch of triangle meshes with per-vertex attributes (sequential meshes and point clouds: dsa_encode_sequential_batch
+ * below): Edgebreaker (standard traversal) connectivity, quantisation,
  * prediction, symbol statistics, scheme selection and rANS coding as HIP kernels (BASELINE.json configs[4]); the host
  * checks index ranges before and lays the bytes of each stream out after (batches below 256 meshes let the host
  * threads do connectivity and symbol plans as well: the device's fixed latency exceeds their work).
@@ -238,7 +239,7 @@ typedef struct dsa_encode_options {
 typedef struct dsa_mesh_input {
   uint32_t num_vertices, num_faces;
   const float *positions;      /* num_vertices * 3 */
-  const uint32_t *faces;       /* num_faces * 3 vertex indices; manifold, no isolated vertices */
+  const uint32_t *faces;       /* num_faces * 3 vertex indices; manifold, no isolated vertices (dsa_encode_sequential_batch: any) */
   const float *normals;        /* num_vertices * 3 or NULL */
   const float *texcoords;      /* num_vertices * 2 or NULL */
   /* ABI 4: one generic attribute of 1 - 4 uint8 components per vertex (vertex colours, material ids ...), coded as an integer
@@ -291,6 +292,33 @@ void dsa_encode_default_options_ex(dsa_encode_options_ex *options);
  * mesh fails alone as there; the streams of legal dsa_encode_batch / _corners options are the same bytes through either call. */
 dsa_status dsa_encode_batch_ex(dsa_context *ctx, uint32_t n, const dsa_mesh_corner_input *meshes, const dsa_encode_options_ex *options,
                                dsa_encoded **out);
+/* Sequential streams: what the reference's encoder writes at speed 10 (DracoEncoder.cs:43-57, :79-82 EncodingMethod ->
+ * Mesh/MeshSequentialEncoder.cs) and for a point cloud (PointCloud/PointCloudSequentialEncoder.cs).  No corner table and no
+ * traversal: any list of triangles over any set of points is legal -- non-manifold edges and vertices, isolated vertices,
+ * degenerate and duplicated faces -- and the stream returns the caller's points and faces in the caller's order (point i is
+ * vertex i, face k is faces[3k .. 3k + 2]).  One attributes encoder with a linear sequencer; positions, texture coordinates and
+ * the generic attribute by Difference + wrap, normals by the canonicalised octahedral delta.  Attribute quantisation, prediction,
+ * the index symbols of compressed connectivity, scheme selection and rANS coding are HIP kernels; raw indices are laid out by
+ * the host from the caller's array at the bitstream's widths (u8 below 256 points, u16 below 65 536, varint below 2^21, u32 from
+ * there).  Added after ABI 4 without changing it: callers detect the feature by the symbol dsa_encode_sequential_batch. */
+typedef struct dsa_encode_sequential_options {
+  dsa_encode_options base;       /* position_bits, texcoord_bits, normal_bits, symbol_scheme, compression_level are used;
+                                    single_connectivity, position_prediction and texcoord_prediction do not influence the bytes
+                                    (values dsa_encode_batch refuses still fail the call) */
+  int32_t geometry;              /* 1 triangular mesh (default), 0 point cloud (Constants.EncodingType) */
+  int32_t compress_connectivity; /* 0 raw indices (default, = ConfigOptionName.CompressConnectivity false), 1 compressed:
+                                    differences of consecutive indices, sign in the low bit, through the symbol coder */
+  int32_t reserved[6];           /* must be zero */
+} dsa_encode_sequential_options;   /* 64 bytes */
+void dsa_encode_sequential_default_options(dsa_encode_sequential_options *options);
+/* Encodes n meshes (geometry 1) or n point clouds (geometry 0: positions and the per-point attributes of dsa_mesh_input,
+ * num_faces = 0) into n sequential .drc streams, read with the dsa_encoded_* accessors.  An option outside its values or a
+ * non-zero reserved entry fails the call with DSA_ERR_INVALID_ARGUMENT (dsa_last_error names the field).  A mesh fails alone
+ * (dsa_encoded_stream) and the rest of the batch encodes: positions missing or num_vertices = 0, geometry 1 without faces, a
+ * face index >= num_vertices (DSA_ERR_INVALID_DATA); geometry 0 with num_faces != 0 -- faces are not dropped silently -- or
+ * generic != NULL with generic_components outside 1..4 (DSA_ERR_INVALID_ARGUMENT).  Nothing else about a mesh is checked. */
+dsa_status dsa_encode_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes,
+                                       const dsa_encode_sequential_options *options, dsa_encoded **out);
 uint32_t dsa_encoded_size(const dsa_encoded *encoded);
 /* Bytes of stream `mesh` (owned by `encoded`, valid until dsa_encoded_free) or that mesh's failure status. */
 dsa_status dsa_encoded_stream(const dsa_encoded *encoded, uint32_t mesh, const uint8_t **bytes, size_t *length);

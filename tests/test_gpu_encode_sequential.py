@@ -1,0 +1,367 @@
+"""Encode direction, sequential meshes and point clouds (dsa_encode_sequential_batch).  The device coder must write, byte for byte,
+the stream of the CPU coder (synth.encode_sequential / synth.encode_point_cloud_attributes) with the symbol plans made on either
+side, and the streams must round-trip through the GPU decoder to the input arrays themselves: faces element for element, point i
+input vertex i, values the numpy quantisation of the input (tests/seqcases.py).  Everything is byte or array equality."""
+import ctypes as C
+import itertools
+
+import numpy as np
+import pytest
+
+import draco_sharp_amd as dsa
+import draco_sharp_amd.synth as synth
+import irregular
+import seqcases
+from draco_sharp_amd import native
+
+pytestmark = pytest.mark.gpu
+
+KINDS = (synth.GRID, synth.TORUS, synth.SPHERE, synth.HOLES, synth.TWO_PARTS)
+BOTH_PLANS = pytest.mark.parametrize("host_plan", ["0", "1"])
+SUBSETS = list(itertools.product((False, True), repeat=3))          # normals, texture coordinates, generic
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = dsa.Context(0)
+    yield c
+    c.close()
+
+
+def opt_of(cfg):
+    return synth.options(pos_bits=cfg.position_bits, uv_bits=cfg.texcoord_bits, normal_bits=cfg.normal_bits,
+                         force_scheme=cfg.symbol_scheme, compression_level=10 - cfg.speed)
+
+
+def cpu(m, cfg):
+    """The CPU coder's stream of MeshData / PointCloudData m under cfg."""
+    if isinstance(m, dsa.PointCloudData):
+        return synth.encode_point_cloud_attributes(m.positions, m.normals, m.texcoords, m.generic, opt=opt_of(cfg))
+    return synth.encode_sequential(m.positions, m.faces, m.normals, m.texcoords, m.generic, compressed=cfg.compress_connectivity, opt=opt_of(cfg))
+
+
+def raw_seq(ctx, meshes, opt):
+    """dsa_encode_sequential_batch with an EncodeSequentialOptions: (call status, [(status, bytes or None)])."""
+    L = native.lib()
+    n = len(meshes)
+    arr = (native.MeshInput * max(1, n))()
+    for i, m in enumerate(meshes):
+        mi = arr[i]
+        mi.num_vertices, mi.num_faces = len(m.positions), len(m.faces)
+        mi.positions = m.positions.ctypes.data
+        mi.faces = m.faces.ctypes.data if len(m.faces) else None
+        mi.normals = m.normals.ctypes.data if m.normals is not None else None
+        mi.texcoords = m.texcoords.ctypes.data if m.texcoords is not None else None
+        mi.generic = m.generic.ctypes.data if m.generic is not None else None
+        mi.generic_components = m.generic.shape[1] if m.generic is not None else 0
+    h = C.c_void_p()
+    st = L.dsa_encode_sequential_batch(ctx._h, n, arr, C.byref(opt) if opt is not None else None, C.byref(h))
+    if st != 0:
+        return st, None
+    out = []
+    p, ln = C.c_void_p(), C.c_size_t()
+    for i in range(n):
+        s = L.dsa_encoded_stream(h, i, C.byref(p), C.byref(ln))
+        out.append((s, C.string_at(p, ln.value) if s == 0 else None))
+    L.dsa_encoded_free(h)
+    return st, out
+
+
+def encode(ctx, meshes, cfg, geometry=1):
+    st, out = raw_seq(ctx, meshes, cfg._native_sequential(geometry))
+    assert st == 0, ctx.error()
+    return out
+
+
+def seq(**kw):
+    return dsa.Config(encoding_method=0, **kw)
+
+
+def kind_meshes(k0=0, generic=True):
+    out = []
+    for k, kind in enumerate(KINDS):
+        nx, ny = (16, 14) if kind == synth.HOLES else (9 + k + k0, 7 + 2 * k)
+        pos, nrm, uv, faces = synth.make_mesh(kind, nx, ny, 30 + k + k0)
+        gen = seqcases.generic_of(len(pos), 1 + k % 4, k) if generic and k % 2 == 0 else None
+        out.append(dsa.MeshData(pos, faces, nrm if k != 3 else None, uv if k != 1 else None, generic=gen))
+    return out
+
+
+def irregular_meshes(cases):
+    return [dsa.MeshData(pos, faces, nrm, uv) for pos, nrm, uv, faces in (irregular.mesh(c) for c in cases)]
+
+
+def cloud(points, subset=(True, True, True), seed=0):
+    rng = np.random.default_rng(50 + seed)
+    pos = np.cumsum(rng.normal(size=(points, 3)), axis=0).astype(np.float32)
+    nrm = rng.normal(size=(points, 3)).astype(np.float32)
+    nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
+    uv = rng.random((points, 2)).astype(np.float32)
+    n, u, g = subset
+    return dsa.PointCloudData(pos, nrm if n else None, uv if u else None, seqcases.generic_of(points, 1 + seed % 4, seed) if g else None)
+
+
+def same_as_cpu(meshes, got, cfg):
+    for i, (m, (st, g)) in enumerate(zip(meshes, got)):
+        assert st == 0, i
+        assert g == cpu(m, cfg), i
+
+
+@BOTH_PLANS
+@pytest.mark.parametrize("compressed", [False, True])
+def test_every_kind_and_irregular_case_matches_cpu_coder(ctx, monkeypatch, host_plan, compressed):
+    monkeypatch.setenv("DSA_ENC_HOST_PLAN", host_plan)
+    cfg = seq(compress_connectivity=compressed)
+    meshes = kind_meshes() + irregular_meshes(irregular.CASES)
+    same_as_cpu(meshes, encode(ctx, meshes, cfg), cfg)
+
+
+@BOTH_PLANS
+def test_quantisation_bits_4_to_18(ctx, monkeypatch, host_plan):
+    monkeypatch.setenv("DSA_ENC_HOST_PLAN", host_plan)
+    meshes = kind_meshes(1)
+    for bits in range(4, 19):
+        for compressed in (False, True):
+            cfg = seq(position_bits=bits, texcoord_bits=bits, normal_bits=bits, compress_connectivity=compressed)
+            same_as_cpu(meshes, encode(ctx, meshes, cfg), cfg)
+
+
+@BOTH_PLANS
+def test_symbol_schemes_and_compression_levels(ctx, monkeypatch, host_plan):
+    monkeypatch.setenv("DSA_ENC_HOST_PLAN", host_plan)
+    meshes = kind_meshes(2) + irregular_meshes(irregular.SMALL[:3])
+    for scheme, level, compressed in itertools.product((-1, 0, 1), (0, 5, 10), (False, True)):
+        cfg = seq(symbol_scheme=scheme, speed=10 - level, compress_connectivity=compressed)
+        same_as_cpu(meshes, encode(ctx, meshes, cfg), cfg)
+
+
+@BOTH_PLANS
+def test_index_widths(ctx, monkeypatch, host_plan):
+    """Below 256, below 65 536 and above 65 536 points, at the boundaries themselves; 16- and 32-bit face uploads."""
+    monkeypatch.setenv("DSA_ENC_HOST_PLAN", host_plan)
+    meshes = []
+    for points in sorted(seqcases.WIDTH_GRIDS):
+        pos, nrm, uv, faces = seqcases.grid(points)
+        faces = faces.copy()
+        faces[-1, 2] = points - 1
+        meshes.append(dsa.MeshData(pos, faces, nrm, uv, generic=seqcases.generic_of(points, 2)))
+    pos, nrm, uv, faces = synth.make_mesh(synth.GRID, 300, 250, 3)
+    assert len(pos) == 75551
+    meshes.append(dsa.MeshData(pos, faces, nrm, uv))
+    for compressed in (False, True):
+        cfg = seq(compress_connectivity=compressed)
+        got = encode(ctx, meshes, cfg)
+        same_as_cpu(meshes, got, cfg)
+        assert len(got[-1][1]) == (357578 if compressed else 1464503)
+
+
+def test_two_million_points_with_raw_indices(ctx):
+    pos, nrm, uv, faces = synth.make_mesh(synth.GRID, 1448, 1448, 8)
+    assert len(pos) >= 1 << 21                                      # u32 indices
+    m = dsa.MeshData(pos, faces, nrm, uv)
+    cfg = seq()
+    got = encode(ctx, [m], cfg)
+    same_as_cpu([m], got, cfg)
+    head = 11 + 4 + 4 + 1                                           # header, two 4-byte varints, connectivity method
+    assert np.array_equal(np.frombuffer(got[0][1], "<u4", 3 * len(faces), head), faces.ravel())
+
+
+def test_batch_of_five(ctx, monkeypatch):
+    monkeypatch.delenv("DSA_ENC_HOST_PLAN", raising=False)
+    meshes = kind_meshes(4)
+    for compressed in (False, True):
+        cfg = seq(compress_connectivity=compressed)
+        same_as_cpu(meshes, encode(ctx, meshes, cfg), cfg)
+
+
+def test_crowded_batch_device_plans_by_default(ctx, monkeypatch):
+    monkeypatch.delenv("DSA_ENC_HOST_PLAN", raising=False)
+    monkeypatch.delenv("DSA_ENC_CHUNK", raising=False)
+    base = kind_meshes(5) + irregular_meshes(irregular.SMALL)
+    meshes = [base[i % len(base)] for i in range(640)]             # two chunks of 512 and 128
+    for compressed in (True, False):
+        cfg = seq(compress_connectivity=compressed)
+        got = encode(ctx, meshes, cfg)
+        want = [cpu(m, cfg) for m in base]
+        for i, (st, g) in enumerate(got):
+            assert st == 0 and g == want[i % len(base)], i
+
+
+def test_bench_size_batch(ctx, monkeypatch):
+    monkeypatch.delenv("DSA_ENC_HOST_PLAN", raising=False)
+    pair = []
+    for seed in (1000, 1001):
+        pos, nrm, uv, faces = synth.make_mesh(synth.GRID, 128, 256, seed)
+        pair.append(dsa.MeshData(pos, faces, nrm, uv))
+    assert len(pair[0].faces) == 65536
+    meshes = [pair[i % 2] for i in range(64)]
+    for compressed in (True, False):
+        cfg = seq(compress_connectivity=compressed)
+        got = encode(ctx, meshes, cfg)
+        want = [cpu(m, cfg) for m in pair]
+        for i, (st, g) in enumerate(got):
+            assert st == 0 and g == want[i % 2], i
+
+
+@BOTH_PLANS
+def test_point_clouds_with_each_attribute_subset(ctx, monkeypatch, host_plan):
+    monkeypatch.setenv("DSA_ENC_HOST_PLAN", host_plan)
+    clouds = [cloud(n, s, k) for k, s in enumerate(SUBSETS) for n in (1, 3000 + 17 * k)]
+    cfg = seq()
+    got = encode(ctx, clouds, cfg, geometry=0)
+    same_as_cpu(clouds, got, cfg)
+    only_positions = clouds[1]
+    assert only_positions.normals is None and only_positions.generic is None
+    assert got[1][1] == synth.encode_point_cloud(only_positions.positions)
+
+
+def test_point_cloud_of_a_million_points(ctx):
+    pc = cloud(1000003, (True, False, True), 3)
+    cfg = seq(position_bits=16)
+    got = encode(ctx, [pc], cfg, geometry=0)
+    same_as_cpu([pc], got, cfg)
+
+
+def decode_all(ctx, streams):
+    b = dsa.Batch(ctx, streams)
+    b.decode()
+    for i in range(len(streams)):
+        assert b.status(i) == 0, (i, b.status(i), b.mesh_info(i).detail)
+    return b
+
+
+@BOTH_PLANS
+def test_round_trip_through_the_gpu_decoder(ctx, monkeypatch, host_plan):
+    monkeypatch.setenv("DSA_ENC_HOST_PLAN", host_plan)
+    meshes = kind_meshes(6) + irregular_meshes(irregular.SMALL[:6]) + [dsa.MeshData(p, f, n, u) for _, p, n, u, f in seqcases.refused_by_edgebreaker()]
+    pos, nrm, uv, faces = seqcases.grid(65536)
+    meshes.append(dsa.MeshData(pos, faces, nrm, uv, generic=seqcases.generic_of(len(pos), 4)))
+    bits = (12, 9, 11)
+    for compressed in (False, True):
+        cfg = seq(position_bits=bits[0], normal_bits=bits[1], texcoord_bits=bits[2], compress_connectivity=compressed)
+        streams = [g for _, g in encode(ctx, meshes, cfg)]
+        b = decode_all(ctx, streams)
+        for i, m in enumerate(meshes):
+            d = b.result(i).ConnectedData
+            assert type(d) is dsa.Mesh
+            seqcases.check_decoded_gpu(d, m.positions, m.faces, m.normals, m.texcoords, m.generic, bits)
+        b.close()
+    clouds = [cloud(n, s, k) for k, s in enumerate(SUBSETS) for n in (1, 2000 + k)]
+    cfg = seq(position_bits=bits[0], normal_bits=bits[1], texcoord_bits=bits[2])
+    b = decode_all(ctx, [g for _, g in encode(ctx, clouds, cfg, geometry=0)])
+    for i, pc in enumerate(clouds):
+        d = b.result(i).ConnectedData
+        assert type(d) is dsa.PointCloud
+        seqcases.check_decoded_gpu(d, pc.positions, None, pc.normals, pc.texcoords, pc.generic, bits)
+    b.close()
+
+
+@BOTH_PLANS
+def test_bad_inputs_fail_alone(ctx, monkeypatch, host_plan):
+    monkeypatch.setenv("DSA_ENC_HOST_PLAN", host_plan)
+    good = kind_meshes(7)
+    bad_faces = good[1].faces.copy()
+    bad_faces[4, 2] = len(good[1].positions)                        # an index out of range
+    bad = dsa.MeshData(good[1].positions, bad_faces, good[1].normals, good[1].texcoords)
+    empty = dsa.MeshData(good[0].positions, good[0].faces[:0])      # a mesh without faces
+    for compressed in (False, True):
+        cfg = seq(compress_connectivity=compressed)
+        got = encode(ctx, good[:2] + [bad, empty] + good[2:], cfg)
+        assert got[2] == (native.DSA_ERR_INVALID_DATA, None) and got[3] == (native.DSA_ERR_INVALID_DATA, None)
+        same_as_cpu(good, got[:2] + got[4:], cfg)
+    # a point cloud that carries faces: refused, not stripped of them
+    clouds = [cloud(500 + k, SUBSETS[k], k) for k in range(4)]
+    with_faces = dsa.MeshData(good[0].positions, good[0].faces)
+    cfg = seq()
+    got = encode(ctx, clouds[:1] + [with_faces] + clouds[1:], cfg, geometry=0)
+    assert got[1] == (native.DSA_ERR_INVALID_ARGUMENT, None)
+    same_as_cpu(clouds, got[:1] + got[2:], cfg)
+    # the generic attribute's component count
+    g5 = dsa.MeshData(good[0].positions, good[0].faces)
+    g5.generic = np.zeros((len(g5.positions), 5), np.uint8)
+    got = encode(ctx, [good[0], g5], cfg)
+    assert got[1] == (native.DSA_ERR_INVALID_ARGUMENT, None) and got[0] == (0, cpu(good[0], cfg))
+
+
+@BOTH_PLANS
+def test_duplicated_face_mesh_is_refused_by_edgebreaker_and_coded_here(ctx, monkeypatch, host_plan):
+    """The mesh of test_gpu_encode_stock.py::test_non_manifold_mesh_fails_alone."""
+    monkeypatch.setenv("DSA_ENC_HOST_CONN", host_plan)
+    monkeypatch.setenv("DSA_ENC_HOST_PLAN", host_plan)
+    pos, nrm, uv, faces = synth.make_mesh(synth.GRID, 10, 8, 3)
+    bad = dsa.MeshData(pos, np.concatenate([faces, faces[:1]]), nrm, uv)
+    L = native.lib()
+    arr = (native.MeshInput * 1)()
+    arr[0].num_vertices, arr[0].num_faces = len(bad.positions), len(bad.faces)
+    arr[0].positions, arr[0].faces = bad.positions.ctypes.data, bad.faces.ctypes.data
+    arr[0].normals, arr[0].texcoords = bad.normals.ctypes.data, bad.texcoords.ctypes.data
+    h = C.c_void_p()
+    o = dsa.Config()._native()
+    assert L.dsa_encode_batch(ctx._h, 1, arr, C.byref(o), C.byref(h)) == 0
+    p, ln = C.c_void_p(), C.c_size_t()
+    assert L.dsa_encoded_stream(h, 0, C.byref(p), C.byref(ln)) == native.DSA_ERR_INVALID_DATA
+    L.dsa_encoded_free(h)
+    for compressed in (False, True):
+        cfg = seq(compress_connectivity=compressed)
+        got = encode(ctx, [bad], cfg)
+        same_as_cpu([bad], got, cfg)
+        b = decode_all(ctx, [got[0][1]])
+        seqcases.check_decoded_gpu(b.result(0).ConnectedData, bad.positions, bad.faces, bad.normals, bad.texcoords)
+        b.close()
+
+
+def test_option_errors_fail_the_call_and_name_the_field(ctx):
+    L = native.lib()
+    m = kind_meshes()[:1]
+
+    def fresh():
+        o = native.EncodeSequentialOptions()
+        L.dsa_encode_sequential_default_options(C.byref(o))
+        return o
+    o = fresh()
+    o.reserved[0] = 1
+    assert raw_seq(ctx, m, o)[0] == native.DSA_ERR_INVALID_ARGUMENT and "reserved" in ctx.error()
+    o = fresh()
+    o.geometry = 2
+    assert raw_seq(ctx, m, o)[0] == native.DSA_ERR_INVALID_ARGUMENT and "geometry" in ctx.error()
+    o = fresh()
+    o.compress_connectivity = 2
+    assert raw_seq(ctx, m, o)[0] == native.DSA_ERR_INVALID_ARGUMENT and "compress_connectivity" in ctx.error()
+    o = fresh()
+    o.base.position_prediction = 4
+    assert raw_seq(ctx, m, o)[0] == native.DSA_ERR_INVALID_ARGUMENT and "position_prediction" in ctx.error()
+    o = fresh()
+    o.base.normal_bits = 1
+    assert raw_seq(ctx, m, o)[0] == native.DSA_ERR_INVALID_ARGUMENT and "bits" in ctx.error()
+    # the fields of `base` that shape only Edgebreaker streams do not influence the bytes
+    o = fresh()
+    o.base.single_connectivity, o.base.position_prediction, o.base.texcoord_prediction = 1, 0, 5
+    st, got = raw_seq(ctx, m, o)
+    assert st == 0 and got[0] == (0, cpu(m[0], seq()))
+    # NULL options: the defaults (a mesh, raw indices)
+    assert raw_seq(ctx, m, None)[1][0] == (0, cpu(m[0], seq()))
+
+
+def test_python_surface(ctx):
+    enc = dsa.DracoEncoder(ctx)
+    meshes = kind_meshes(8)
+    for cfg in (seq(), seq(compress_connectivity=True), dsa.Config(encoding_method=-1, speed=10, compress_connectivity=True)):
+        assert cfg.sequential
+        got = enc.EncodeBatch(meshes, cfg)
+        assert len(got) == len(meshes)
+        for m, g in zip(meshes, got):
+            assert g == cpu(m, cfg)
+    # the reference's rule below speed 10, and the default: Edgebreaker, the bytes of before
+    plain = [dsa.MeshData(m.positions, m.faces, m.normals, m.texcoords) for m in meshes]
+    for cfg in (dsa.Config(encoding_method=-1, speed=9), dsa.Config()):
+        for m, g in zip(plain, enc.EncodeBatch(plain, cfg)):
+            assert g == synth.encode_mesh(m.positions, m.faces, m.normals, m.texcoords, opt=synth.options(compression_level=10 - cfg.speed))
+    clouds = [cloud(100 + k, SUBSETS[k], k) for k in range(8)]
+    for cfg in (None, seq(position_bits=14), dsa.Config(speed=10)):
+        for pc, g in zip(clouds, enc.EncodeBatch(clouds, cfg)):
+            assert g == cpu(pc, cfg or dsa.Config())
+    assert enc.Encode(clouds[0]) == synth.encode_point_cloud(clouds[0].positions)
+    with pytest.raises(dsa.InvalidDataException):
+        bad = dsa.MeshData(meshes[0].positions, meshes[0].faces.copy())
+        bad.faces[0, 0] = len(bad.positions)
+        enc.EncodeBatch([bad], seq())
