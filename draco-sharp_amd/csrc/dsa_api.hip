@@ -30,9 +30,9 @@ static const char *kStageNames[DSA_NUM_STAGES] = {"locate", "connectivity", "tra
 // Kernels timed one by one (dsa_batch_kernel_times): an event pair around each on the stream it is launched on, so that a duration
 // here is a row of `rocprofv3 --kernel-trace --stats` (first launch of that kernel in the decode where a kernel is launched twice).
 enum { KT_CHAIN = 0, KT_CONNECTIVITY, KT_TRAVERSE, KT_SYMBOLS_EARLY, KT_SYMBOLS_LATE, KT_OCT_STREAMS, KT_PREDICT_WRAP_EARLY, KT_PREDICT_WRAP_LATE, KT_FACES,
-       KT_SEAM_TABLES, KT_TRAVERSE_ATT, KT_TEXCOORDS, KT_COUNT };
+       KT_SEAM_TABLES, KT_TRAVERSE_ATT, KT_TEXCOORDS, KT_TAGS, KT_COUNT };
 static const char *kKernelNames[KT_COUNT] = {"k_chain", "k_connectivity", "k_traverse", "k_symbols_reg[early]", "k_symbols_reg[late]", "k_predict_oct_streams",
-                                             "k_predict_wrap[early]", "k_predict_wrap[late]", "k_faces", "k_seam_tables", "k_traverse_att", "k_texcoords"};
+                                             "k_predict_wrap[early]", "k_predict_wrap[late]", "k_faces", "k_seam_tables", "k_traverse_att", "k_texcoords", "k_tags"};
 
 
 }  // namespace
@@ -604,7 +604,9 @@ dsa_status dsa_batch_decode(dsa_batch *b) {
   // tagged symbol streams: a round of {tag stream on a wave of its own, the walk taken up behind it} per attribute a mesh can
   // have (what follows a tagged attribute is only found by decoding its tags); nothing to do without them
   for (uint32_t r = 0; r < std::max<uint32_t>(1, b->max_atts); ++r) {
+    k_begin(KT_TAGS, st);                      // (the first round's: a mesh's first tagged attribute)
     hipLaunchKernelGGL(dsa::k_tags, dim3(n), dim3(WAVE), 0, st, b->arena, b->d_layouts, b->d_descs, n);
+    k_end(KT_TAGS, st);
     hipLaunchKernelGGL(dsa::k_locate_resume, dim3(n), dim3(WAVE), 0, st, b->arena, b->d_layouts, b->d_descs, n, b->d_globals);
   }
   // valence-coded connectivity: the six context lists of every mesh on waves of their own (the register-table decoder), in front
@@ -1374,11 +1376,11 @@ dsa_status dsa_batch_copy_debug(const dsa_batch *b, uint32_t mesh, int what, voi
     }
     case 3: off = L.v2d; bytes = 4ull * D.num_vertices; break;
     case 6: off = L.vstamp; bytes = std::min<uint64_t>(dst_bytes, 4ull * L.cap_vertices); break;     // traversal trace of a -DDSA_TRAV_TRACE build
-    case 5: {   // per attribute: {symbol source, alphabet size, rANS precision bits, rANS payload bytes}
+    case 5: {   // per attribute: {symbol source, alphabet size, rANS precision bits (tagged: 1 where k_tags decoded the tag stream, 0 where the walk did), rANS payload bytes}
       size_t need = sizeof(uint32_t) * 4 * DSA_MAX_ATT;
       if (dst_bytes < need) return set_err(b->ctx, DSA_ERR_INVALID_ARGUMENT, "destination too small");
       uint32_t *o = (uint32_t *)dst;
-      for (uint32_t a = 0; a < DSA_MAX_ATT; ++a) { o[4 * a] = D.att[a].source; o[4 * a + 1] = D.att[a].num_symbols; o[4 * a + 2] = D.att[a].precision_bits; o[4 * a + 3] = D.att[a].size_rans; }
+      for (uint32_t a = 0; a < DSA_MAX_ATT; ++a) { o[4 * a] = D.att[a].source; o[4 * a + 1] = D.att[a].num_symbols; o[4 * a + 2] = D.att[a].source == SRC_TAGGED ? D.att[a].tags_done : D.att[a].precision_bits; o[4 * a + 3] = D.att[a].size_rans; }
       if (written) *written = need;
       return DSA_OK;
     }

@@ -173,9 +173,11 @@ struct SymbolStats {
   uint32_t max_value = 0;
   uint64_t total_bl = 0;              // sum of the per-entry bit lengths
   std::vector<uint64_t> tag_freq;     // [33] histogram of per-entry bit lengths
-  std::vector<uint64_t> raw_freq;     // [max_value + 1] histogram of symbol values
+  std::vector<uint64_t> raw_freq;     // [max_value + 1] histogram of symbol values; empty where the raw scheme is out of the question
 };
-static void symbol_stats(const std::vector<uint32_t> &v, int nc, SymbolStats &st, std::vector<uint32_t> *bit_lengths_out = nullptr) {
+// force_scheme != 1 and symbols above 18 bits (32-bit integer attributes): the scheme is the tagged one whatever the histogram of
+// values says (choose_scheme), so it is not built -- it would have up to 2^32 entries.
+static void symbol_stats(const std::vector<uint32_t> &v, int nc, SymbolStats &st, std::vector<uint32_t> *bit_lengths_out = nullptr, int force_scheme = 1) {
   st.n = v.size(); st.nc = nc; st.max_value = 0; st.total_bl = 0;
   st.tag_freq.assign(33, 0);
   std::vector<uint32_t> bl;
@@ -189,8 +191,11 @@ static void symbol_stats(const std::vector<uint32_t> &v, int nc, SymbolStats &st
     st.total_bl += b;
     ++st.tag_freq[b];
   }
-  st.raw_freq.assign((size_t)st.max_value + 1, 0);
-  for (uint32_t x : v) ++st.raw_freq[x];
+  st.raw_freq.clear();
+  if (force_scheme == 1 || st.max_value < (1u << 18)) {
+    st.raw_freq.assign((size_t)st.max_value + 1, 0);
+    for (uint32_t x : v) ++st.raw_freq[x];
+  }
   if (bit_lengths_out) bit_lengths_out->swap(bl);
 }
 // SymbolEncoding.cs:8-40 (E-2 corrected): scheme choice, then the coder's tables.  `head` receives the bytes that
@@ -202,6 +207,12 @@ struct SymbolPlan {
 };
 static void plan_symbols(const SymbolStats &st, int force_scheme, int compression_level, SymbolPlan &pl) {
   int usbl = 0;
+  if (st.raw_freq.empty()) {          // symbols above 18 bits, raw scheme not forced: tagged (what choose_scheme answers for them)
+    pl.method = 0;
+    pl.head.u8(0);
+    pl.coder.create(pl.head, 5, st.tag_freq);
+    return;
+  }
   const int rc = dsa::plan::choose_scheme(st.tag_freq.data(), st.raw_freq.data(), st.max_value, (uint64_t)st.n, (uint32_t)st.nc, st.total_bl,
                                           force_scheme, compression_level, &pl.method, &usbl);
   check(rc == dsa::plan::PLAN_OK, dsa::plan::plan_message(rc));
@@ -219,7 +230,7 @@ static void encode_symbols(ByteWriter &w, const std::vector<uint32_t> &v, int nc
   if (v.empty()) return;
   SymbolStats st;
   std::vector<uint32_t> bit_lengths;
-  symbol_stats(v, nc, st, &bit_lengths);
+  symbol_stats(v, nc, st, &bit_lengths, force_scheme);
   SymbolPlan pl;
   plan_symbols(st, force_scheme, compression_level, pl);
   w.bytes(pl.head.d);
@@ -701,10 +712,13 @@ struct Options {
                                      // (what stock encoders do at their highest level); 2 prediction degree for every decoder (CPU coder only)
   // Decoder branches no stock encoder setting reaches (CPU coder only; tests and tools/soak.py):
   int32_t normal_transform = 3;      // 3 NormalOctahedronCanonicalized, 2 NormalOctahedron (difference prediction)
-  int32_t raw_integers = 0;          // 1 / 2 / 4: values of the difference / parallelogram attributes stored uncompressed at that many
+  int32_t raw_integers = 0;          // 1 / 2 / 3 / 4: values of the difference / parallelogram attributes stored uncompressed at that many
                                      // bytes (SequentialIntegerAttributeDecoder.cs:68-84)
-  int32_t no_prediction = 0;         // bit 0 positions, bit 1 texture coordinates, bit 2 normals: prediction method -2 (none)
-  int32_t generic_components = 1;    // components of the generic attribute (uint8 each: 4 = the RGBA colours of a scan); CPU coder only
+  int32_t no_prediction = 0;         // bit 0 positions, bit 1 texture coordinates, bit 2 normals, bit 3 the generic attribute: prediction
+                                     // method -2 (none)
+  int32_t generic_components = 1;    // components of the generic attribute (4 = the RGBA colours of a scan); CPU coder only
+  int32_t generic_data_type = 2;     // element type of the generic attribute, Draco's ids: 1 int8, 2 uint8, 3 int16, 4 uint16, 5 int32,
+                                     // 6 uint32 (joint indices, 16-bit colours, feature ids); CPU coder only
 };
 
 // Octahedral quantisation (OctahedronToolBox.cs:28-119)
@@ -828,9 +842,23 @@ static void oct_canon_corr(const Octa &o, const int32_t orig_in[2], const int32_
   out[1] = o.make_positive(ot - pt);
 }
 
+// Element k of a generic attribute of Draco data type dt as its int32 value (uint32 by reinterpretation).
+static int32_t generic_value(const void *g, size_t k, int dt) {
+  switch (dt) {
+    case 1: return ((const int8_t *)g)[k];
+    case 2: return ((const uint8_t *)g)[k];
+    case 3: return ((const int16_t *)g)[k];
+    case 4: return ((const uint16_t *)g)[k];
+    case 5: return ((const int32_t *)g)[k];
+    case 6: return (int32_t)((const uint32_t *)g)[k];
+    default: check(false, "generic_data_type must be 1 (int8) to 6 (uint32)"); return 0;
+  }
+}
+
 struct MeshIn {
   const float *pos; uint32_t nv; const uint32_t *faces; uint32_t nf;
-  const float *normals; const float *uvs; const uint8_t *generic;
+  const float *normals; const float *uvs;
+  const void *generic;               // nv * generic_components elements of Options::generic_data_type (uint8 unless the CPU coder is told otherwise)
   // Attributes given per corner (the CPU coder only): value ids per corner of `faces` (3 * nf) into `normals` (nn rows) /
   // `uvs` (nu rows); an interior edge whose end points carry different ids on its two faces is an attribute seam
   // (MeshAttributeCornerTable.cs:32-78).  Null: one value per vertex.
@@ -901,7 +929,7 @@ static void write_attribute_values(ByteWriter &w, const PortableAttr &a, const C
   auto put_symbols = [&](const std::vector<uint32_t> &sy) {
     if (opt.raw_integers == 0) { w.u8(1); encode_symbols(w, sy, nc, opt.force_scheme, opt.compression_level); return; }
     const int nb = opt.raw_integers;
-    check(nb == 1 || nb == 2 || nb == 4, "raw_integers must be 1, 2 or 4");
+    check(nb >= 1 && nb <= 4, "raw_integers must be 1, 2, 3 or 4");
     w.u8(0);
     w.u8((uint8_t)nb);
     for (uint32_t v : sy) {
@@ -918,7 +946,7 @@ static void write_attribute_values(ByteWriter &w, const PortableAttr &a, const C
   }
   std::vector<uint32_t> symbols(entries * nc);
   {
-    const int none_bit = a.seq_type == 3 ? 4 : (a.att_type == 0 ? 1 : (a.att_type == 3 ? 2 : 0));
+    const int none_bit = a.seq_type == 3 ? 4 : (a.att_type == 0 ? 1 : (a.att_type == 3 ? 2 : (a.att_type == 4 ? 8 : 0)));
     if (opt.no_prediction & none_bit) {        // PredictionSchemeMethod.None (-2): no transform byte, the values themselves, signed
       w.i8(-2);
       for (size_t i = 0; i < symbols.size(); ++i) symbols[i] = zigzag(d[i]);
@@ -1193,7 +1221,7 @@ static void plan_attributes(const MeshIn &in, const Options &opt, MeshPlan &pl) 
   if (in.normals) { PortableAttr a; a.att_type = 1; a.nc_out = 3; a.nc = 2; a.seq_type = 3; a.data_type = 9; a.bits = opt.normal_bits; a.prediction = opt.normal_prediction == 6 ? 6 : 0; a.corner_value = in.normal_corners; pl.atts.push_back(a); }
   if (in.uvs) { PortableAttr a; a.att_type = 3; a.nc = a.nc_out = 2; a.seq_type = 2; a.data_type = 9; a.prediction = opt.uv_prediction; a.bits = opt.uv_bits; a.corner_value = in.uv_corners; pl.atts.push_back(a); }
   // (the generic attribute takes the constrained multi-parallelogram scheme where the positions do: what an encoder at its highest levels writes)
-  if (in.generic) { PortableAttr a; a.att_type = 4; a.nc = a.nc_out = opt.generic_components >= 1 && opt.generic_components <= 4 ? opt.generic_components : 1; a.seq_type = 1; a.data_type = 2; a.prediction = opt.pos_prediction == 4 ? 4 : 1; pl.atts.push_back(a); }
+  if (in.generic) { PortableAttr a; a.att_type = 4; a.nc = a.nc_out = opt.generic_components >= 1 && opt.generic_components <= 4 ? opt.generic_components : 1; a.seq_type = 1; a.data_type = opt.generic_data_type; a.prediction = opt.pos_prediction == 4 ? 4 : 1; pl.atts.push_back(a); }
   pl.single = opt.single_connectivity != 0;
   pl.num_att_data = pl.single ? 0 : (uint32_t)pl.atts.size() - 1;
   pl.force_scheme = opt.force_scheme; pl.compression_level = opt.compression_level;
@@ -1346,7 +1374,7 @@ static void encode_mesh(const MeshIn &in, const Options &opt, std::vector<uint8_
       a.vals.resize((size_t)n * 2);
       for (uint32_t v = 0; v < n; ++v) { int s, t; o.from_float_vector(in.normals + (size_t)v * 3, s, t); a.vals[(size_t)v * 2] = s; a.vals[(size_t)v * 2 + 1] = t; }
     } else if (a.att_type == 3) quantize(in.uvs, in.uv_corners ? in.nu : in.nv, 2, opt.uv_bits, a);
-    else { a.vals.resize((size_t)in.nv * a.nc); for (size_t k = 0; k < (size_t)in.nv * a.nc; ++k) a.vals[k] = in.generic[k]; }
+    else { a.vals.resize((size_t)in.nv * a.nc); for (size_t k = 0; k < (size_t)in.nv * a.nc; ++k) a.vals[k] = generic_value(in.generic, k, a.data_type); }
   }
   ByteWriter w;
   write_stream(w, in, pl,
@@ -1364,13 +1392,13 @@ static void encode_mesh(const MeshIn &in, const Options &opt, std::vector<uint8_
 // symbol coder) or raw; one attributes encoder with a linear sequencer (Attributes/LinearSequencer.cs), so values are in point
 // order and predicted by Difference + Wrap / canonicalised octahedral delta.
 
-// Attribute descriptors of a sequential stream: positions, normals, texture coordinates, the generic uint8 attribute; all Difference.
+// Attribute descriptors of a sequential stream: positions, normals, texture coordinates, the generic integer attribute; all Difference.
 static void plan_sequential_attributes(const MeshIn &in, const Options &opt, std::vector<PortableAttr> &atts) {
   atts.clear();
   { PortableAttr a; a.att_type = 0; a.nc = a.nc_out = 3; a.seq_type = 2; a.data_type = 9; a.prediction = 0; a.bits = opt.pos_bits; atts.push_back(a); }
   if (in.normals) { PortableAttr a; a.att_type = 1; a.nc_out = 3; a.nc = 2; a.seq_type = 3; a.data_type = 9; a.bits = opt.normal_bits; a.prediction = 0; atts.push_back(a); }
   if (in.uvs) { PortableAttr a; a.att_type = 3; a.nc = a.nc_out = 2; a.seq_type = 2; a.data_type = 9; a.prediction = 0; a.bits = opt.uv_bits; atts.push_back(a); }
-  if (in.generic) { PortableAttr a; a.att_type = 4; a.nc = a.nc_out = opt.generic_components >= 1 && opt.generic_components <= 4 ? opt.generic_components : 1; a.seq_type = 1; a.data_type = 2; a.prediction = 0; atts.push_back(a); }
+  if (in.generic) { PortableAttr a; a.att_type = 4; a.nc = a.nc_out = opt.generic_components >= 1 && opt.generic_components <= 4 ? opt.generic_components : 1; a.seq_type = 1; a.data_type = opt.generic_data_type; a.prediction = 0; atts.push_back(a); }
 }
 // Compressed indices: symbol k = |f[k] - f[k-1]| << 1 | sign, f[-1] = 0 (MeshSequentialEncoder.cs:84-121)
 static void sequential_index_symbols(const uint32_t *faces, size_t count, std::vector<uint32_t> &sym) {
@@ -1423,7 +1451,7 @@ static void encode_sequential(const MeshIn &in, const Options &opt, bool mesh, b
       a.vals.resize((size_t)in.nv * 2);
       for (uint32_t v = 0; v < in.nv; ++v) { int s, t; o.from_float_vector(in.normals + (size_t)v * 3, s, t); a.vals[(size_t)v * 2] = s; a.vals[(size_t)v * 2 + 1] = t; }
     } else if (a.att_type == 3) quantize(in.uvs, in.nv, 2, opt.uv_bits, a);
-    else { a.vals.resize((size_t)in.nv * a.nc); for (size_t k = 0; k < (size_t)in.nv * a.nc; ++k) a.vals[k] = in.generic[k]; }
+    else { a.vals.resize((size_t)in.nv * a.nc); for (size_t k = 0; k < (size_t)in.nv * a.nc; ++k) a.vals[k] = generic_value(in.generic, k, a.data_type); }
   }
   // linear order: entry i = point i.  write_attribute_values wants a corner table and a sequence: an identity stand-in
   CornerTable ct;

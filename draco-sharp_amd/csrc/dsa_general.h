@@ -787,7 +787,7 @@ __device__ __forceinline__ bool decode_descriptors(const MeshLayout &L, MeshDesc
     GREQ(r.ok && a.seq_type <= 3, 131);
     if (a.seq_type == 2) GREQ(a.data_type == 9 && a.nc <= 4, 132);
     if (a.seq_type == 3) GREQ(a.data_type == 9 && a.nc == 3, 133);
-    if (a.seq_type == 1) { const uint32_t w = data_type_length(a.data_type); GREQ(w == 1 || w == 2 || w == 4, 134); }
+    if (a.seq_type == 1) GREQ(a.data_type >= 1 && a.data_type <= 6, 134);   // int8 ... uint32 (SequentialIntegerAttributeDecoder.cs:103-140)
   }
   natt += (uint32_t)k;
   return true;

@@ -574,7 +574,7 @@ __device__ inline void locate_attribute_headers(uint8_t *arena, const MeshLayout
       REQUIRE(r.ok && a.seq_type <= 3, 131);
       if (a.seq_type == 2) REQUIRE(a.data_type == 9 && a.nc <= 4, 132);
       if (a.seq_type == 3) REQUIRE(a.data_type == 9 && a.nc == 3, 133);
-      if (a.seq_type == 1) { uint32_t w = data_type_length(a.data_type); REQUIRE(w == 1 || w == 2 || w == 4, 134); }
+      if (a.seq_type == 1) REQUIRE(a.data_type >= 1 && a.data_type <= 6, 134);   // int8 ... uint32: what StoreValues narrows to (SequentialIntegerAttributeDecoder.cs:103-140)
     }
     natt += (uint32_t)k;
   }

@@ -19,7 +19,12 @@ class Options(C.Structure):
                 ("compression_level", C.c_int32), ("pos_prediction", C.c_int32), ("uv_prediction", C.c_int32),
                 ("normal_prediction", C.c_int32), ("traversal_method", C.c_int32), ("predictive_connectivity", C.c_int32),
                 ("normal_transform", C.c_int32), ("raw_integers", C.c_int32), ("no_prediction", C.c_int32),
-                ("generic_components", C.c_int32)]
+                ("generic_components", C.c_int32), ("generic_data_type", C.c_int32)]
+
+
+# element types of the generic attribute (CPU coder only): numpy dtype -> Draco's data type id
+GENERIC_DATA_TYPES = {np.dtype(np.int8): 1, np.dtype(np.uint8): 2, np.dtype(np.int16): 3, np.dtype(np.uint16): 4,
+                      np.dtype(np.int32): 5, np.dtype(np.uint32): 6}
 
 
 def build(force=False):
@@ -77,6 +82,22 @@ def _err():
     return lib().synth_last_error().decode()
 
 
+def _generic(generic, opt):
+    """The generic attribute as a contiguous array of its own integer dtype (anything else: uint8, as before) and options
+    whose generic_data_type says so (a copy: the caller's options stay)."""
+    gen = np.asarray(generic)
+    if gen.dtype not in GENERIC_DATA_TYPES:
+        gen = gen.astype(np.uint8)
+    gen = np.ascontiguousarray(gen)
+    dt = GENERIC_DATA_TYPES[gen.dtype]
+    if opt.generic_data_type != dt:
+        o2 = Options()
+        C.memmove(C.byref(o2), C.byref(opt), C.sizeof(Options))
+        o2.generic_data_type = dt
+        opt = o2
+    return gen, opt
+
+
 def make_mesh(kind, nx, ny, seed):
     """Returns (pos[V,3] f32, normals[V,3] f32, uv[V,2] f32, faces[F,3] u32)."""
     L = lib()
@@ -98,9 +119,11 @@ def encode_mesh(pos, faces, normals=None, uvs=None, generic=None, opt=None):
     faces = np.ascontiguousarray(faces, np.uint32)
     nrm = None if normals is None else np.ascontiguousarray(normals, np.float32)
     uv = None if uvs is None else np.ascontiguousarray(uvs, np.float32)
-    gen = None if generic is None else np.ascontiguousarray(generic, np.uint8)
     out, n = C.c_void_p(), C.c_size_t()
     opt = opt or options()
+    gen = None
+    if generic is not None:
+        gen, opt = _generic(generic, opt)
     rc = L.synth_encode_mesh(pos.ctypes.data, len(pos), faces.ctypes.data, len(faces),
                              None if nrm is None else nrm.ctypes.data, None if uv is None else uv.ctypes.data,
                              None if gen is None else gen.ctypes.data, C.byref(opt), C.byref(out), C.byref(n))
@@ -115,7 +138,7 @@ def encode_mesh_corners(pos, faces, normals=None, normal_corners=None, uvs=None,
     """Mesh whose normals / texture coordinates are given per corner: `faces` [F,3] index `pos`, `normal_corners` /
     `uv_corners` [F,3] index the rows of `normals` / `uvs` (None: that attribute has one row per vertex).  Edges across
     which the ids differ become attribute seams in the stream (seam bits, attribute corner table, corner attribute).
-    `generic`: the per-vertex uint8 attribute of encode_mesh (its components per opt.generic_components)."""
+    `generic`: the per-vertex integer attribute of encode_mesh (its components per opt.generic_components)."""
     L = lib()
     pos = np.ascontiguousarray(pos, np.float32)
     faces = np.ascontiguousarray(faces, np.uint32)
@@ -123,7 +146,6 @@ def encode_mesh_corners(pos, faces, normals=None, normal_corners=None, uvs=None,
     uv = None if uvs is None else np.ascontiguousarray(uvs, np.float32)
     nci = None if normal_corners is None else np.ascontiguousarray(normal_corners, np.uint32)
     uci = None if uv_corners is None else np.ascontiguousarray(uv_corners, np.uint32)
-    gen = None if generic is None else np.ascontiguousarray(generic, np.uint8)
     for ids, vals, name in ((nci, nrm, "normal"), (uci, uv, "uv")):
         if ids is not None and (vals is None or ids.shape != faces.shape):
             raise ValueError("%s_corners needs %ss and one id per corner of `faces`" % (name, name))
@@ -131,6 +153,9 @@ def encode_mesh_corners(pos, faces, normals=None, normal_corners=None, uvs=None,
             raise ValueError("per-vertex %ss need one row per vertex" % name)
     out, n = C.c_void_p(), C.c_size_t()
     opt = opt or options()
+    gen = None
+    if generic is not None:
+        gen, opt = _generic(generic, opt)
     rc = L.synth_encode_mesh_corners(pos.ctypes.data, len(pos), faces.ctypes.data, len(faces),
                                      None if nrm is None else nrm.ctypes.data, 0 if nrm is None else len(nrm),
                                      None if nci is None else nci.ctypes.data,
@@ -184,10 +209,10 @@ def _sequential(pos, faces, normals, uvs, generic, geometry, compressed, opt):
     opt = opt or options()
     gen = None
     if generic is not None:
-        gen = np.ascontiguousarray(generic, np.uint8)
+        gen, opt = _generic(generic, opt)
         gen = gen.reshape(len(gen), -1)
         if len(gen) != len(pos) or not 1 <= gen.shape[1] <= 4:
-            raise ValueError("generic attribute: one row of 1 - 4 uint8 components per point")
+            raise ValueError("generic attribute: one row of 1 - 4 integer components per point")
         if opt.generic_components != gen.shape[1]:          # the components are the array's own (a copy: the caller's options stay)
             o2 = Options()
             C.memmove(C.byref(o2), C.byref(opt), C.sizeof(Options))
@@ -209,14 +234,14 @@ def _sequential(pos, faces, normals, uvs, generic, geometry, compressed, opt):
 
 
 def encode_sequential(pos, faces, normals=None, uvs=None, generic=None, compressed=False, opt=None):
-    """Sequential mesh stream with every per-vertex attribute (generic: uint8 (V,) or (V, 1..4)): faces and points keep the
+    """Sequential mesh stream with every per-vertex attribute (generic: (V,) or (V, 1..4) of int8 / uint8 / int16 / uint16 / int32 / uint32): faces and points keep the
     caller's order; any list of triangles over the points is legal.  compressed: indices through the symbol coder, else raw
     at the bitstream's widths.  What dsa_encode_sequential_batch must write for geometry 1."""
     return _sequential(pos, faces, normals, uvs, generic, 1, compressed, opt)
 
 
 def encode_point_cloud_attributes(pos, normals=None, uvs=None, generic=None, opt=None):
-    """Sequential point cloud with per-point normals / texture coordinates / generic uint8 attribute; positions only:
+    """Sequential point cloud with per-point normals / texture coordinates / generic integer attribute; positions only:
     the bytes of encode_point_cloud.  What dsa_encode_sequential_batch must write for geometry 0."""
     return _sequential(pos, None, normals, uvs, generic, 0, False, opt)
 

@@ -116,7 +116,7 @@ extern "C" {
 
 struct synth_options {
   int32_t pos_bits, uv_bits, normal_bits, single_connectivity, force_scheme, compression_level, pos_prediction, uv_prediction, normal_prediction, traversal_method, predictive_connectivity,
-      normal_transform, raw_integers, no_prediction, generic_components;
+      normal_transform, raw_integers, no_prediction, generic_components, generic_data_type;
 };
 
 static thread_local char g_err[256];
@@ -130,7 +130,7 @@ static synth::Options to_opt(const synth_options *o) {
     r.compression_level = o->compression_level; r.pos_prediction = o->pos_prediction; r.uv_prediction = o->uv_prediction;
     r.normal_prediction = o->normal_prediction; r.traversal_method = o->traversal_method;
     r.predictive_connectivity = o->predictive_connectivity;
-    r.normal_transform = o->normal_transform; r.raw_integers = o->raw_integers; r.no_prediction = o->no_prediction; r.generic_components = o->generic_components;
+    r.normal_transform = o->normal_transform; r.raw_integers = o->raw_integers; r.no_prediction = o->no_prediction; r.generic_components = o->generic_components; r.generic_data_type = o->generic_data_type;
   }
   return r;
 }
@@ -140,12 +140,12 @@ void synth_default_options(synth_options *o) {
   o->force_scheme = d.force_scheme; o->compression_level = d.compression_level; o->pos_prediction = d.pos_prediction; o->uv_prediction = d.uv_prediction;
   o->normal_prediction = d.normal_prediction; o->traversal_method = d.traversal_method;
   o->predictive_connectivity = d.predictive_connectivity;
-  o->normal_transform = d.normal_transform; o->raw_integers = d.raw_integers; o->no_prediction = d.no_prediction; o->generic_components = d.generic_components;
+  o->normal_transform = d.normal_transform; o->raw_integers = d.raw_integers; o->no_prediction = d.no_prediction; o->generic_components = d.generic_components; o->generic_data_type = d.generic_data_type;
 }
 
 // Encodes one mesh.  normals/uvs/generic may be NULL.  *out is malloc'ed; free with synth_free.
 int synth_encode_mesh(const float *pos, uint32_t nv, const uint32_t *faces, uint32_t nf, const float *normals,
-                      const float *uvs, const uint8_t *generic, const synth_options *opt, uint8_t **out, size_t *out_len) {
+                      const float *uvs, const void *generic, const synth_options *opt, uint8_t **out, size_t *out_len) {
   try {
     synth::MeshIn in{pos, nv, faces, nf, normals, uvs, generic};
     std::vector<uint8_t> buf;
@@ -162,9 +162,9 @@ int synth_encode_mesh(const float *pos, uint32_t nv, const uint32_t *faces, uint
 // (MeshEdgeBreakerEncoder.cs:403-440, MeshAttributeCornerTable.cs:32-155).
 int synth_encode_mesh_corners(const float *pos, uint32_t nv, const uint32_t *faces, uint32_t nf, const float *normals, uint32_t nn,
                               const uint32_t *normal_corners, const float *uvs, uint32_t nu, const uint32_t *uv_corners,
-                              const uint8_t *generic, const synth_options *opt, uint8_t **out, size_t *out_len) {
+                              const void *generic, const synth_options *opt, uint8_t **out, size_t *out_len) {
   try {
-    // (the generic attribute stays per vertex: nv rows of opt->generic_components bytes, or NULL)
+    // (the generic attribute stays per vertex: nv rows of opt->generic_components elements of opt->generic_data_type, or NULL)
     synth::MeshIn in{pos, nv, faces, nf, normals, uvs, generic, normals ? normal_corners : nullptr, nn, uvs ? uv_corners : nullptr, nu};
     for (size_t k = 0; k < (size_t)nf * 3; ++k) {
       synth::check(faces[k] < nv, "face index out of range");
@@ -203,9 +203,9 @@ int synth_encode_point_cloud(const float *pos, uint32_t n, const synth_options *
 }
 // Sequential stream of either kind with every per-vertex attribute (dsa_encode_host.h encode_sequential): geometry 1 a triangle mesh
 // (compressed: indices through the symbol coder, else raw), 0 a point cloud of nv points (faces must be absent).  normals / uvs /
-// generic may be NULL; generic: nv rows of opt->generic_components bytes.
+// generic may be NULL; generic: nv rows of opt->generic_components elements of opt->generic_data_type.
 int synth_encode_sequential(const float *pos, uint32_t nv, const uint32_t *faces, uint32_t nf, const float *normals, const float *uvs,
-                            const uint8_t *generic, int geometry, int compressed, const synth_options *opt, uint8_t **out, size_t *out_len) {
+                            const void *generic, int geometry, int compressed, const synth_options *opt, uint8_t **out, size_t *out_len) {
   try {
     synth::check(geometry == 0 || geometry == 1, "geometry: 1 (triangular mesh) or 0 (point cloud)");
     synth::check(geometry == 1 || nf == 0, "a point cloud has no faces");

@@ -195,7 +195,8 @@ dsa_status dsa_batch_copy_metadata(const dsa_batch *batch, uint32_t mesh, uint8_
  * what: 0 opposite[3F], 1 corner_to_vertex[3F], 2 data_to_corner[entries], 3 vertex_to_data[vertices],
  *       4 uint32[20] clocks recorded by the per-mesh kernels (s_memtime deltas between phases; [13..17] ticks, start and
  *         duration of the connectivity and the traversal wave in s_memrealtime ticks: readable for failed meshes too),
- *       5 uint32[DSA_MAX_ATTRIBUTES][4] per attribute {symbol source, alphabet size, rANS precision bits, rANS payload bytes},
+ *       5 uint32[DSA_MAX_ATTRIBUTES][4] per attribute {symbol source, alphabet size, rANS precision bits (tagged symbols: 1 where
+ *         k_tags decoded the tag stream, 0 where the stream walk did), rANS payload bytes},
  *       6 the traversal trace of a -DDSA_TRAV_TRACE build. */
 dsa_status dsa_batch_copy_debug(const dsa_batch *batch, uint32_t mesh, int what, void *dst, size_t dst_bytes, size_t *written);
 

@@ -1699,7 +1699,7 @@ struct AttributeSectionDecoder {
     if (a.seq_type == 0) return;
     if (a.seq_type == 1) {
       int w = data_type_length(a.data_type);
-      require(w == 1 || w == 2 || w == 4, "unsupported integer attribute type");
+      require(a.data_type >= 1 && a.data_type <= 6, "unsupported integer attribute type");   // :105-139: int8 ... uint32, else NotImplementedException
       a.values.assign((size_t)num_entries * a.nc * w, 0);
       for (size_t i = 0; i < (size_t)num_entries * a.nc; ++i) {
         int32_t v = a.portable[i];

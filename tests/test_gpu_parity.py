@@ -864,7 +864,7 @@ def test_constrained_multi_parallelogram_positions_on_the_fast_kernels(ctx):
         # the scheme on the texture coordinates as well, and on a generic attribute (vertex colours of a scan): every attribute of the
         # position connectivity gets its records where the first one shows the scheme
         streams.append(synth.encode_mesh(pos, faces, nrm, uv, opt=synth.options(pos_prediction=4, uv_prediction=4)))
-        streams.append(synth.encode_mesh(pos, faces, nrm, uv, generic=(np.arange(len(pos), dtype=np.int32) * 7919) % 251, opt=synth.options(pos_prediction=4, uv_prediction=4, force_scheme=k_scheme(len(streams)))))
+        streams.append(synth.encode_mesh(pos, faces, nrm, uv, generic=((np.arange(len(pos), dtype=np.int32) * 7919) % 251).astype(np.uint8), opt=synth.options(pos_prediction=4, uv_prediction=4, force_scheme=k_scheme(len(streams)))))
         # four components (the RGBA colours of a scan) and two
         for gc in (4, 2):
             g = ((np.arange(len(pos) * gc, dtype=np.int64) * 7919) % 251).astype(np.uint8).reshape(-1, gc)

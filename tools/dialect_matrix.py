@@ -5,9 +5,10 @@ multi-parallelogram), texture coordinates (difference, parallelogram, TexCoordsP
 reaches rarely (a late-located attribute beside a scheme that reuses a region, say).  usage: python tools/dialect_matrix.py [seed [big]]"""
 import itertools, sys, os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests')); sys.path.insert(0, os.path.join(ROOT, 'tools'))
 import numpy as np, oracle, draco_sharp_amd as dsa, draco_sharp_amd.synth as synth
 import irregular
+import soak
 from meshutil import seamed_mesh
 from test_gpu_parity import assert_same
 
@@ -18,6 +19,7 @@ def run(seed=1, ctx=None, big=False):
     topologies = [(synth.GRID, 14, 11), (synth.TORUS, 12, 9), (synth.HOLES, 16, 13), (synth.TWO_PARTS, 9, 6)]
     streams, labels = [], []
     irr = np.random.default_rng([seed, 0x1226])          # the irregular draw: one mesh in three flipped, split, shuffled, sometimes thickened
+    typ = np.random.default_rng([seed, 0x7E9D])          # the typed draw: element type (int8 ... uint32) and value pattern of the generic attribute
     for ti, (kind, nx, ny) in enumerate(topologies):
         for n_chart, u_chart in itertools.product((None, "stripes", "random"), (None, "stripes", "checker")):
             args = seamed_mesh(synth, kind, nx, ny, seed + ti, n_chart, u_chart)
@@ -39,13 +41,13 @@ def run(seed=1, ctx=None, big=False):
                         continue                                        # (a combination the writer refuses)
                     streams.append(s); labels.append((kind, n_chart, u_chart, opt))
     # second family, attributes per vertex: quantisation bits (the rANS precision tiers), one decoder for all attributes or one each,
-    # a generic attribute of 0 / 1 / 4 components, the symbol scheme left to the writer
+    # a generic attribute of 0 / 1 / 4 components of a drawn element type and pattern, the symbol scheme left to the writer
     for ti, (kind, nx, ny) in enumerate(topologies[:3]):
         pos, nrm, uv, faces = synth.make_mesh(kind, nx + 6, ny + 5, seed + 10 + ti)
         if ti == 1:
             pos, nrm, uv, faces = irregular.roughen(pos, nrm, uv, faces, irr)
         for bits, single, gc, scheme in itertools.product((dict(), dict(pos_bits=14, uv_bits=12, normal_bits=10)), (0, 1), (0, 1, 4), (-1, 0, 1)):
-            gen = None if gc == 0 else ((np.arange(len(pos) * gc, dtype=np.int64) * 7919 + ti) % 256).astype(np.uint8).reshape(-1, gc)
+            gen = None if gc == 0 else soak.typed_generic(typ, dict(force_scheme=scheme), len(pos), gc)
             for pp, up, npred, conn in itertools.product((0, 1, 4), (0, 1, 5), (0, 6), (0, 2)):
                 if (ti + pp + up + npred + conn + single + gc) % 3:      # a third of the product per topology
                     continue

@@ -1,16 +1,33 @@
 """Randomised differential run: N synthetic meshes with random encoder options (topology, size, bit depths, symbol
-scheme, prediction schemes, attribute order, Edgebreaker symbol coding, single / per-attribute connectivity) decoded
-in one batch and compared with the oracle.  usage: python tools/soak.py [count] [seed]"""
+scheme, prediction schemes, attribute order, Edgebreaker symbol coding, single / per-attribute connectivity, element type and value
+pattern of the generic attribute) decoded in one batch and compared with the oracle; integer attributes also with their input
+(tools/typedvalues.py: the pin).  usage: python tools/soak.py [count] [seed]"""
 import sys
-import os; ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
+import os; ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests')); sys.path.insert(0, os.path.join(ROOT, 'tools'))
 import numpy as np
 import oracle
 import draco_sharp_amd as dsa, draco_sharp_amd.synth as synth
 
 
-def random_case(rng, irr=None):
+def typed_generic(typ, opt, points, gc):
+    """The generic attribute of a case from the generator of the typed draw: element type (int8 ... uint32) and value pattern of
+    tools/typedvalues.py, within what the case's other options can carry -- uncompressed integers of 1 / 2 bytes take types no wider
+    than that, the raw symbol scheme takes 32-bit values only where their corrections stay below 2^18."""
+    import typedvalues
+    raw = opt.get("raw_integers", 0)
+    dtypes = [d for d in typedvalues.DTYPES if raw not in (1, 2) or d.itemsize <= raw]
+    dtype = dtypes[int(typ.integers(0, len(dtypes)))]
+    patterns = [p for p in typedvalues.PATTERNS if not (dtype.itemsize == 4 and opt["force_scheme"] == 1 and p in ("random", "extremes"))]
+    if raw in (1, 2) and dtype.itemsize == raw:
+        patterns = ["ramp", "sentinel"] if raw == 2 else ["random"]          # (an 8-bit wrap keeps every correction within a byte)
+    pattern = patterns[int(typ.integers(0, len(patterns)))]
+    return typedvalues.values(dtype, pattern, points, gc, seed=int(typ.integers(0, 1 << 30)))
+
+
+def random_case(rng, irr=None, typ=None):
     """irr: the generator of the irregular draw (tests/irregular.py: roughen), apart from `rng` so that the options of a seed stay
-    what they were; None: grids only."""
+    what they were; None: grids only.  typ: the generator of the typed draw (element type and pattern of the generic attribute),
+    apart from both for the same reason; None: uint8 noise.  Returns (stream, description, pin input or None)."""
     kind = int(rng.choice([synth.GRID, synth.TORUS, synth.SPHERE, synth.HOLES, synth.TWO_PARTS]))
     nx, ny = int(rng.integers(4, 48)), int(rng.integers(4, 40))
     if kind == synth.HOLES:
@@ -55,8 +72,8 @@ def random_case(rng, irr=None):
                 opt["force_scheme"] = 0
         pos, faces, nrm, nid, uv, uid = irregular.with_seams(pos, nrm, uv, faces, *charts, seed=mesh_seed)       # (meshutil.seamed_mesh on a grid)
         return synth.encode_mesh_corners(pos, faces, nrm if with_n else None, nid if with_n else None, uv if with_uv else None, uid if with_uv else None,
-                                         opt=synth.options(**opt)), (kind, nx, ny, opt, with_n, with_uv, charts, rough)
-    # one per-vertex case in four carries a generic attribute of 1 - 4 uint8 components (vertex colours)
+                                         opt=synth.options(**opt)), (kind, nx, ny, opt, with_n, with_uv, charts, rough), None
+    # one per-vertex case in four carries a generic attribute of 1 - 4 components (vertex colours, joint indices, feature ids)
     gen = None
     if rng.integers(0, 4) == 0:
         gc = int(rng.integers(1, 5))
@@ -64,19 +81,25 @@ def random_case(rng, irr=None):
         gen = rng.integers(0, 256, (grid_vertices, gc)).astype(np.uint8)
         if len(pos) != grid_vertices:
             gen = np.concatenate([gen, irr.integers(0, 256, (len(pos) - grid_vertices, gc)).astype(np.uint8)])
-    return synth.encode_mesh(pos, faces, nrm if with_n else None, uv if with_uv else None, generic=gen, opt=synth.options(**opt)), (kind, nx, ny, opt, with_n, with_uv, rough)
+        if typ is not None:
+            gen = typed_generic(typ, opt, len(pos), gc)
+    what = (kind, nx, ny, opt, with_n, with_uv, rough) + ((gen.dtype.name,) if gen is not None else ())
+    return (synth.encode_mesh(pos, faces, nrm if with_n else None, uv if with_uv else None, generic=gen, opt=synth.options(**opt)), what,
+            None if gen is None else (pos, faces, gen, opt["pos_bits"]))
 
 
 def run(count, seed, ctx=None):
     rng = np.random.default_rng(seed)
     irr = np.random.default_rng([seed, 0x1226])          # the irregular draw: seeded from the run's seed, apart from the options
-    cases = [random_case(rng, irr) for _ in range(count)]
+    typ = np.random.default_rng([seed, 0x7E9D])           # the typed draw, likewise
+    cases = [random_case(rng, irr, typ) for _ in range(count)]
+    import typedvalues
     own = ctx is None
     ctx = ctx or dsa.Context(0)
     b = dsa.Batch(ctx, [c[0] for c in cases])
     b.decode()
     bad = []
-    for i, (data, what) in enumerate(cases):
+    for i, (data, what, pin_input) in enumerate(cases):
         try:
             ref = oracle.decode(data)
         except oracle.OracleError as e:          # a stream the reference refuses (its own limits): the device must refuse it too
@@ -92,6 +115,10 @@ def run(count, seed, ctx=None):
             ok = ok and np.array_equal(a.PortableValues, r.portable) and np.array_equal(a.PointMap, r.point_map) and a.Values.tobytes() == r.values.tobytes()
         if not ok:
             bad.append((i, what, "differs from the oracle"))
+        elif pin_input is not None:              # integer attributes are lossless: the decoded mesh against the input itself
+            pos, faces, gen, pos_bits = pin_input
+            if m.Attributes[-1].Values.dtype != gen.dtype or not typedvalues.same_multiset(typedvalues.device_multiset(m), typedvalues.pin(pos, faces, gen, pos_bits)):
+                bad.append((i, what, "differs from the input"))
     b.close()
     if own:
         ctx.close()
