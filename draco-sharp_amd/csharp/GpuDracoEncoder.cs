@@ -7,6 +7,9 @@
 // (src/Draco/IO/Config.cs); everything else keeps the reference's defaults (standard Edgebreaker, DFS traversal).
 // An explicitly set ConfigOptionName.EncodingMethod of SequentialEncoding (with ConfigOptionName.CompressConnectivity) and a
 // PointCloud that is not a Mesh go through dsa_encode_sequential_batch: points and faces in the caller's order, one value per point.
+// Every PointAttribute beyond positions, normals, the first texture coordinates and a uint8 generic attribute -- colours, joints and
+// weights, further UV sets, feature ids -- is passed as an extra with its AttributeType, DataType, NumComponents, Normalized and
+// UniqueId (dsa_encode_attributes_batch / dsa_encode_attributes_sequential_batch); without such attributes the calls are what they were.
 using System;
 using System.Collections.Generic;
 using System.IO;
@@ -60,6 +63,8 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
         IntPtr encoded = IntPtr.Zero;
         try
         {
+            bool anyExtras = false;
+            foreach (var m in items) anyExtras = anyExtras || ExtraAttributes(m).Count > 0;
             for (int i = 0; i < items.Count; ++i)
             {
                 var m = items[i];
@@ -77,6 +82,14 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
                     for (int f = 0; f < mesh.FacesCount; ++f) { var face = mesh.GetFace((uint)f); faces[3 * f] = (uint)face[0]; faces[3 * f + 1] = (uint)face[1]; faces[3 * f + 2] = (uint)face[2]; }
                     inputs[i].Faces = (uint*)Pin(faces, pins);
                 }
+            }
+            if (anyExtras)
+            {
+                var ain = new DsaMeshAttrInput[items.Count];
+                for (int i = 0; i < items.Count; ++i) { ain[i].Mesh.Mesh = inputs[i]; Extras(items[i], null, (uint)items[i].PointsCount, ref ain[i], pins); }
+                fixed (DsaMeshAttrInput* p = ain)
+                    NativeMethods.Check(NativeMethods.dsa_encode_attributes_sequential_batch(_ctx, (uint)items.Count, p, in so, out encoded), _ctx, "dsa_encode_attributes_sequential_batch");
+                return Streams(encoded, items.Count);
             }
             fixed (DsaMeshInput* p = inputs)
                 NativeMethods.Check(NativeMethods.dsa_encode_sequential_batch(_ctx, (uint)items.Count, p, in so, out encoded), _ctx, "dsa_encode_sequential_batch");
@@ -121,8 +134,25 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
         IntPtr encoded = IntPtr.Zero;
         try
         {
-            bool anyCorners = false;
-            foreach (var m in meshes) anyCorners = anyCorners || NeedsCornerForm(m);
+            bool anyCorners = false, anyExtras = false;
+            foreach (var m in meshes) { anyCorners = anyCorners || NeedsCornerForm(m); anyExtras = anyExtras || ExtraAttributes(m).Count > 0; }
+            if (anyExtras)
+            {
+                // the attribute list rides on the corner form (extras per vertex: the value of the last point of each position value)
+                var ain = new DsaMeshAttrInput[meshes.Count];
+                for (int i = 0; i < meshes.Count; ++i)
+                {
+                    CornerForm(meshes[i], ref ain[i].Mesh, pins);
+                    Extras(meshes[i], meshes[i].GetNamedAttribute(GeometryAttributeType.Position), ain[i].Mesh.Mesh.NumVertices, ref ain[i], pins);
+                }
+                NativeMethods.dsa_encode_default_options_ex(out var ax);
+                ax.Base = opt;
+                ax.EdgebreakerMethod = ebMethod != unset ? ebMethod : 0;
+                ax.NormalPrediction = normalScheme != unset ? normalScheme : 0;
+                fixed (DsaMeshAttrInput* p = ain)
+                    NativeMethods.Check(NativeMethods.dsa_encode_attributes_batch(_ctx, (uint)meshes.Count, p, in ax, out encoded), _ctx, "dsa_encode_attributes_batch");
+                return Streams(encoded, meshes.Count);
+            }
             if (anyCorners || extended)
             {
                 var cin = new DsaMeshCornerInput[meshes.Count];
@@ -285,6 +315,64 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
         for (uint p = 0; p < m.PointsCount; ++p)
             for (int c = 0; c < nc; ++c) v[p * nc + c] = a.Buffer!.Read<byte>((int)(a.ByteOffset + a.MappedIndex(p) * a.ByteStride + c));
         return v;
+    }
+
+    // The attributes the built-in slots do not take, in the cloud's order: everything but the first position, normal and texture
+    // coordinate attribute and the generic attribute Bytes() passes as DsaMeshInput.Generic.
+    private static List<PointAttribute> ExtraAttributes(PointCloud.PointCloud m)
+    {
+        var builtin = new HashSet<PointAttribute>();
+        foreach (var t in new[] { GeometryAttributeType.Position, GeometryAttributeType.Normal, GeometryAttributeType.TexCoord })
+        {
+            var a = m.GetNamedAttribute(t);
+            if (a != null) builtin.Add(a);
+        }
+        var g = m.GetNamedAttribute(GeometryAttributeType.Generic);
+        if (g != null && g.DataType == DataType.UInt8 && g.NumComponents >= 1 && g.NumComponents <= 4) builtin.Add(g);
+        var extras = new List<PointAttribute>();
+        foreach (var a in m.Attributes) if (!builtin.Contains(a)) extras.Add(a);
+        return extras;
+    }
+
+    private static int ElementSize(DataType t) => t switch
+    {
+        DataType.Int8 or DataType.UInt8 => 1,
+        DataType.Int16 or DataType.UInt16 => 2,
+        DataType.Int32 or DataType.UInt32 or DataType.Float32 => 4,
+        _ => throw new NotSupportedException($"attribute data type {t}: the encoder takes Int8 .. UInt32 and Float32"),
+    };
+
+    // dsa_mesh_attr_input.attributes of a cloud: one packed row per vertex (pa null: per point; else per position value, the value of
+    // the last point of each), read at ByteOffset + ByteStride * id like GeometryAttribute does
+    private static void Extras(PointCloud.PointCloud m, PointAttribute? pa, uint nv, ref DsaMeshAttrInput dst, List<GCHandle> pins)
+    {
+        var extras = ExtraAttributes(m);
+        if (extras.Count == 0) return;
+        var list = new DsaAttributeInput[extras.Count];
+        for (int k = 0; k < extras.Count; ++k)
+        {
+            var a = extras[k];
+            if (a.AttributeType != GeometryAttributeType.Color && a.AttributeType != GeometryAttributeType.TexCoord && a.AttributeType != GeometryAttributeType.Generic)
+                throw new NotSupportedException($"a second attribute of type {a.AttributeType}: extras are colours, texture coordinates and generic attributes");
+            if (a.NumComponents < 1 || a.NumComponents > 4) throw new NotSupportedException("attributes of more than four components");
+            int row = ElementSize(a.DataType) * a.NumComponents;
+            var bytes = new byte[nv * row];
+            for (uint p = 0; p < m.PointsCount; ++p)
+            {
+                long src = a.ByteOffset + (long)a.MappedIndex(p) * a.ByteStride;
+                long at = (long)(pa == null ? p : pa.MappedIndex(p)) * row;
+                for (int b = 0; b < row; ++b) bytes[at + b] = a.Buffer!.Read<byte>((int)(src + b));
+            }
+            list[k].AttributeType = (int)a.AttributeType;
+            list[k].DataType = (int)a.DataType;
+            list[k].NumComponents = (uint)a.NumComponents;
+            list[k].Normalized = a.Normalized && a.DataType != DataType.Float32 ? 1 : 0;
+            list[k].UniqueId = a.UniqueId;
+            list[k].QuantizationBits = 0;
+            list[k].Values = (void*)Pin(bytes, pins);
+        }
+        dst.Attributes = (DsaAttributeInput*)Pin(list, pins);
+        dst.NumAttributes = (uint)extras.Count;
     }
 
     private static IntPtr Pin(Array? a, List<GCHandle> pins)

@@ -112,6 +112,29 @@ internal unsafe struct DsaMeshCornerInput
     public uint NumNormals, NumTexcoords;
 }
 
+// dsa_attribute_input: one more per-vertex attribute behind the built-in ones (40 bytes)
+[StructLayout(LayoutKind.Sequential)]
+internal unsafe struct DsaAttributeInput
+{
+    public int AttributeType;       // GeometryAttributeType: 2 colour, 3 texture coordinate, 4 generic
+    public int DataType;            // Draco.IO.Enums.DataType: 1 Int8 .. 6 UInt32, 9 Float32
+    public uint NumComponents;      // 1..4
+    public int Normalized;          // 0 / 1 (integer types)
+    public uint UniqueId;           // 0xFFFFFFFF: the attribute's index in the stream
+    public int QuantizationBits;    // Float32 only: 1..20; 0: the texture coordinates' bits for type 3, else 8
+    public void* Values;            // NumVertices rows, packed
+    public fixed uint Reserved[2];  // zero
+}
+
+// dsa_mesh_attr_input (dsa_encode_attributes_batch / dsa_encode_attributes_sequential_batch): a mesh with an attribute list (96 bytes)
+[StructLayout(LayoutKind.Sequential)]
+internal unsafe struct DsaMeshAttrInput
+{
+    public DsaMeshCornerInput Mesh;
+    public DsaAttributeInput* Attributes;   // written behind the built-in attributes in list order
+    public uint NumAttributes, Reserved;
+}
+
 internal static unsafe partial class NativeMethods
 {
     private const string Lib = "draco_mi355x";
@@ -165,6 +188,8 @@ internal static unsafe partial class NativeMethods
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_batch_ex(IntPtr ctx, uint n, DsaMeshCornerInput* meshes, in DsaEncodeOptionsEx options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern void dsa_encode_sequential_default_options(out DsaEncodeSequentialOptions options);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_sequential_batch(IntPtr ctx, uint n, DsaMeshInput* meshes, in DsaEncodeSequentialOptions options, out IntPtr encoded);
+    [DllImport(Lib)] internal static extern DsaStatus dsa_encode_attributes_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, in DsaEncodeOptionsEx options, out IntPtr encoded);
+    [DllImport(Lib)] internal static extern DsaStatus dsa_encode_attributes_sequential_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, in DsaEncodeSequentialOptions options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern uint dsa_encoded_size(IntPtr encoded);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encoded_stream(IntPtr encoded, uint mesh, out byte* bytes, out nuint length);
     [DllImport(Lib)] internal static extern void dsa_encoded_free(IntPtr encoded);

@@ -2,14 +2,15 @@
 //
 // Encode direction of the C-ABI (include/draco_mi355x.h, dsa_encode_*): the drop-in for
 //     DracoEncoder.Encode(BinaryWriter, Config, PointCloud, ...)        src/Draco/IO/DracoEncoder.cs:22-41
-// for a batch of triangle meshes with per-vertex positions / normals / texture coordinates
+// for a batch of triangle meshes with per-vertex positions / normals / texture coordinates, a generic uint8 attribute and an
+// attribute list of further typed integer / float attributes (dsa_encode_attributes_batch)
 // (BASELINE.json configs[4]: "batch quantize + parallelogram predict + rANS encode as HIP kernels").
 //
 // Split of the work:
 //   GPU   (dsa_encode_conn.h)  k_enc_connectivity corner table, Edgebreaker symbols, depth-first attribute order, parallelogram
 //                                                 operand entries, one wave per mesh (DSA_ENC_HOST_CONN=1: by the host coder)
 //   GPU   (this file)          k_enc_bounds      quantisation range per attribute   AttributeQuantizationTransform.cs:66-108
-//                              k_enc_quantize    floats -> portable ints, normals -> octahedral (s,t)   :136-177, OctahedronToolBox.cs:28-119
+//                              k_enc_quantize    floats -> portable ints, normals -> octahedral (s,t), typed integers -> int32   :136-177, OctahedronToolBox.cs:28-119
 //                              k_enc_gather      vertex order -> traversal order, wrap bounds           PredictionSchemeWrapTransform.cs:88-100
 //                              k_enc_corr        prediction, correction, zig-zag, symbol statistics     MeshPredictionSchemeParallelogramEncoder.cs:35-56,
 //                                                                                                       PredictionSchemeWrapEncodingTransform.cs:45-90,
@@ -40,8 +41,8 @@ struct EncStream {                 // one per (mesh, attribute); lives in device
   uint64_t hist_raw;               // u32[hist_cap]
   uint64_t out_rans, out_bits;     // coded bytes
   uint64_t prob, cum;              // u32[num_symbols] (filled by the host between the two device phases)
-  uint32_t nv, nc_out, nc, kind;   // nv: entries; kind 0: quantised + wrap, 1: normals (octahedral, canonicalised delta), 2: uint8 integers + wrap (src: bytes),
-                                   //   3: a valence context list of the connectivity (syms given, nc 1; no values, no prediction)
+  uint32_t nv, nc_out, nc, kind;   // nv: entries; kind 0: quantised + wrap, 1: normals (octahedral, canonicalised delta), 2: integers + wrap (src: elements of
+                                   //   type `elem`), 3: a valence context list of the connectivity (syms given, nc 1; no values, no prediction)
   uint32_t rows, rows_pad;         // value rows of `src` / `vals` (= nv, but for an attribute given per corner: its row count; k_enc_seam_operands sets nv)
   uint32_t bits, prediction, hist_cap, out_cap;
   float qmin[4], qrange;
@@ -60,8 +61,21 @@ struct EncStream {                 // one per (mesh, attribute); lives in device
   uint64_t flags;                  // u32[(cap + 31) / 32] side bits, bit k of the list: orientations (delta-coded against true, last
                                    //   entry first; k_enc_orient) or flips (entry order; k_enc_corr) -- -> download (write_rabs)
   uint32_t t_nc3, num_flags;       // 3F; OUTPUT: bits in `flags`
-  uint32_t linear, pad;            // linear: entry i is value row i (sequential streams, dsa_encode_sequential.h): `d` is `vals`, no e2v, no gather
+  uint32_t linear, elem;           // linear: entry i is value row i (sequential streams, dsa_encode_sequential.h): `d` is `vals`, no e2v, no gather
+                                   // elem (kind 2): Draco's data type of `src`, 1 int8, 2 uint8, 3 int16, 4 uint16, 5 int32, 6 uint32
 };
+
+// The raw symbol scheme takes symbols below 2^18 (dsa_symbol_plan.h choose_scheme; symbol_stats of the host coder builds no
+// histogram of values beyond): no stream's histogram is larger than this, and a stream whose histogram has this size may hold
+// symbols beyond it (32-bit integer attributes with spread values) -- those are not counted, and k_enc_plan goes the tagged way.
+static const uint32_t ENC_RAW_SYMBOL_LIMIT = 1u << 18, ENC_HIST_CAP_LIMIT = ENC_RAW_SYMBOL_LIMIT + 2u;
+static const int ENC_PLAN_RAW_BEYOND_LIMIT = 1000;      // plan_status beside dsa::plan::PLAN_*: see enc_plan_message
+static const char *const ENC_RAW_BEYOND_MESSAGE = "symbol_scheme 1 (raw) forced on an integer attribute with symbols of 2^18 and above: the device coder writes those tagged only";
+// hist_cap of an integer attribute whose values (as int32) span lo .. hi: zig-zagged wrapped corrections lie in 0 .. hi - lo + 1
+static inline uint32_t enc_integer_hist_cap(int32_t lo, int32_t hi) {
+  const uint64_t span = (uint64_t)((int64_t)hi - (int64_t)lo) + 3ull;
+  return (uint32_t)(span < ENC_HIST_CAP_LIMIT ? span : ENC_HIST_CAP_LIMIT);
+}
 
 __device__ __forceinline__ uint32_t enc_msb(uint32_t v) { return 31u - (uint32_t)__builtin_clz(v); }
 __device__ __forceinline__ uint32_t enc_zigzag(int32_t v) { return v >= 0 ? (uint32_t)v << 1 : (((uint32_t)(-(v + 1))) << 1) | 1u; }
@@ -137,9 +151,18 @@ __global__ __launch_bounds__(256) void k_enc_quantize(uint8_t *arena, EncStream 
       vals[i] = (int32_t)floorf(__fadd_rn(__fmul_rn(v, inv_delta), 0.5f));
     }
   } else if (S.kind == 2) {         // an integer attribute: its values as they are (SequentialIntegerAttributeEncoder.cs: no transform)
+    // rows are packed at itemsize * nc (a 2-byte type of 3 components is not 4-byte aligned per row): one element per lane and
+    // load, each aligned to its own size (src is 256-byte aligned), consecutive lanes consecutive elements; widened to int32,
+    // uint32 by reinterpretation (generic_value of the host coder).  The type is the stream's: the switch is uniform per block.
     const uint8_t *srcb = arena + S.src;
     const uint32_t total = S.rows * S.nc;
-    for (uint32_t i = tid; i < total; i += stride) vals[i] = (int32_t)srcb[i];
+    switch (S.elem) {
+      case 1: for (uint32_t i = tid; i < total; i += stride) vals[i] = (int32_t)((const int8_t *)srcb)[i]; break;
+      case 3: for (uint32_t i = tid; i < total; i += stride) vals[i] = (int32_t)((const int16_t *)srcb)[i]; break;
+      case 4: for (uint32_t i = tid; i < total; i += stride) vals[i] = (int32_t)((const uint16_t *)srcb)[i]; break;
+      case 5: case 6: for (uint32_t i = tid; i < total; i += stride) vals[i] = ((const int32_t *)srcb)[i]; break;
+      default: for (uint32_t i = tid; i < total; i += stride) vals[i] = (int32_t)srcb[i]; break;      // 2: uint8
+    }
   } else if (S.kind == 1) {
     for (uint32_t v = tid; v < S.rows; v += stride) {
       int32_t s, t;
@@ -190,6 +213,8 @@ __global__ __launch_bounds__(256) void k_enc_corr(uint8_t *arena, EncStream *str
   // global atomic per symbol was a third of the attribute kernels' time)
   __shared__ uint32_t s_hist[4098];
   const bool lds_hist = S.hist_cap <= 4098u;
+  // a symbol outside a histogram of the largest size is no overflow: the raw scheme is out of the question then (max_value tells k_enc_plan)
+  const bool beyond_ok = S.kind == 2 && S.hist_cap == ENC_HIST_CAP_LIMIT;
   if (lds_hist) for (uint32_t i = threadIdx.x; i < S.hist_cap; i += blockDim.x) s_hist[i] = 0;
   if (threadIdx.x < 33) s_tag[threadIdx.x] = 0;
   if (threadIdx.x == 0) { s_max = 0; s_bl = 0; }
@@ -243,7 +268,7 @@ __global__ __launch_bounds__(256) void k_enc_corr(uint8_t *arena, EncStream *str
         if (cr < min_corr) cr += max_dif; else if (cr > max_corr) cr -= max_dif;
         const uint32_t sy = enc_zigzag(cr);
         syms[(size_t)p * nc + c] = sy;
-        if (sy < S.hist_cap) atomicAdd(lds_hist ? &s_hist[sy] : &hist[sy], 1u); else S.overflow = 1;
+        if (sy < S.hist_cap) atomicAdd(lds_hist ? &s_hist[sy] : &hist[sy], 1u); else if (!beyond_ok) S.overflow = 1;
         mc = sy > mc ? sy : mc;
       }
     } else {                        // PredictionSchemeNormalOctahedronCanonicalizedEncodingTransform.cs:47-83
@@ -289,12 +314,17 @@ __global__ __launch_bounds__(WAVE) void k_enc_plan(uint8_t *arena, EncStream *st
   if (si >= ns) return;
   EncStream &S = streams[si];
   if (S.overflow || (S.kind == 3 && S.nv == 0)) return;      // (an empty context list is not coded: its size 0 is all of it)
-  if (S.max_value >= S.hist_cap) { S.overflow = 1; return; }
+  // symbols of 2^18 and above (an integer attribute): the tagged scheme whatever the histogram of values would say, which is not
+  // read -- plan_symbols of the host coder with no raw histogram.  The raw scheme forced on such a stream: refused here.
+  const bool tagged_only = S.kind == 2 && S.max_value >= ENC_RAW_SYMBOL_LIMIT;
+  if (tagged_only && force_scheme == 1) { S.plan_status = (uint32_t)ENC_PLAN_RAW_BEYOND_LIMIT; S.overflow = 1; return; }
+  if (!tagged_only && S.max_value >= S.hist_cap) { S.overflow = 1; return; }
   const uint32_t *raw = (const uint32_t *)(arena + S.hist_raw);
   uint32_t *prob = (uint32_t *)(arena + S.prob), *cum = (uint32_t *)(arena + S.cum);
   uint32_t *order = (uint32_t *)(arena + S.plan_order), *tmp = (uint32_t *)(arena + S.plan_tmp);
-  int method = 1, usbl = 0;
-  int rc = plan::choose_scheme((const uint32_t *)S.hist_tag, raw, S.max_value, (uint64_t)S.nv * S.nc, S.nc, (uint64_t)S.total_bl, force_scheme, compression_level, &method, &usbl);
+  int method = tagged_only ? 0 : 1, usbl = 0;
+  int rc = tagged_only ? (int)plan::PLAN_OK
+                       : plan::choose_scheme((const uint32_t *)S.hist_tag, raw, S.max_value, (uint64_t)S.nv * S.nc, S.nc, (uint64_t)S.total_bl, force_scheme, compression_level, &method, &usbl);
   int pb = 12;
   uint32_t nsym = 0;
   if (rc == plan::PLAN_OK)
@@ -594,6 +624,7 @@ static dsa_status enc_host_plans(dsa_context *ctx, EncLane &lane, uint8_t *arena
     std::vector<dsa::PackItem> items;
     for (uint32_t s = 0; s < ns; ++s) {
       if (hs[s].kind == 3 && hs[s].nv == 0) continue;
+      if (hs[s].kind == 2 && hs[s].max_value >= dsa::ENC_RAW_SYMBOL_LIMIT && !hs[s].overflow) continue;      // tagged only: no histogram of values (plan_stream)
       if (hs[s].overflow || hs[s].max_value >= hs[s].hist_cap) { hs[s].overflow = 1; continue; }
       items.push_back({hs[s].hist_raw, 0, 4u * (hs[s].max_value + 1u), s});
     }
@@ -610,6 +641,8 @@ static dsa_status enc_host_plans(dsa_context *ctx, EncLane &lane, uint8_t *arena
     if (E->status[i] != DSA_OK || (hs[s].kind == 3 && hs[s].nv == 0)) return;
     try {
       synth::check(!hs[s].overflow, "symbol outside the histogram range");
+      const bool tagged_only = hs[s].kind == 2 && hs[s].max_value >= dsa::ENC_RAW_SYMBOL_LIMIT;
+      synth::check(!(tagged_only && opt.force_scheme == 1), dsa::ENC_RAW_BEYOND_MESSAGE);
       synth::SymbolStats stt;
       stt.n = (size_t)hs[s].nv * hs[s].nc; stt.nc = (int)hs[s].nc; stt.max_value = hs[s].max_value; stt.total_bl = hs[s].total_bl;
       stt.tag_freq.assign(hs[s].hist_tag, hs[s].hist_tag + 33);
@@ -648,7 +681,8 @@ static void enc_device_plan_errors(const std::vector<dsa::EncStream> &hs, const 
     const uint32_t i = (uint32_t)stream_mesh[s];
     if (E->status[i] != DSA_OK || !hs[s].overflow) continue;
     E->status[i] = DSA_ERR_INVALID_DATA;
-    E->messages[i] = hs[s].plan_status ? dsa::plan::plan_message((int)hs[s].plan_status) : "symbol outside the histogram range";
+    E->messages[i] = hs[s].plan_status == (uint32_t)dsa::ENC_PLAN_RAW_BEYOND_LIMIT ? dsa::ENC_RAW_BEYOND_MESSAGE
+                     : (hs[s].plan_status ? dsa::plan::plan_message((int)hs[s].plan_status) : "symbol outside the histogram range");
   }
 }
 // ---- device phase 2: entropy coding (behind the host's plans: k_enc_rans here; k_enc_plan's: it has run), then the coded bytes of
@@ -730,8 +764,9 @@ void dsa_encode_default_options_ex(dsa_encode_options_ex *o) {
 
 // All entry points share one chunk path: `meshes` (dsa_encode_batch) or `corners` (dsa_encode_batch_corners / _ex), the other
 // null; `ex` (dsa_encode_batch_ex) the schemes beyond standard Edgebreaker + difference / parallelogram, else null.
-static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint32_t batch_n, const dsa_mesh_input *meshes, const dsa_mesh_corner_input *corners, const dsa_encode_options *options, const dsa_encode_options_ex *ex, dsa_encoded **out);
-static dsa_status encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_mesh_corner_input *corners, const dsa_encode_options *options, const dsa_encode_options_ex *ex, dsa_encoded **out);
+// `attrs` (dsa_encode_attributes_batch): meshes with an attribute list, both others null.
+static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint32_t batch_n, const dsa_mesh_input *meshes, const dsa_mesh_corner_input *corners, const dsa_mesh_attr_input *attrs, const dsa_encode_options *options, const dsa_encode_options_ex *ex, dsa_encoded **out);
+static dsa_status encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_mesh_corner_input *corners, const dsa_mesh_attr_input *attrs, const dsa_encode_options *options, const dsa_encode_options_ex *ex, dsa_encoded **out);
 // The prediction methods the device coder writes; any other value would put a method byte in front of data it does not describe.
 static dsa_status check_schemes(dsa_context *ctx, const dsa_encode_options *o, const dsa_encode_options_ex *ex) {
   if (o && o->position_prediction != 0 && o->position_prediction != 1)
@@ -750,12 +785,12 @@ static dsa_status check_schemes(dsa_context *ctx, const dsa_encode_options *o, c
 dsa_status dsa_encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_encode_options *options, dsa_encoded **out) {
   if (!ctx || !out || (n && !meshes)) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "null argument");
   if (check_schemes(ctx, options, nullptr) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
-  DSA_GUARD(ctx, encode_batch(ctx, n, meshes, nullptr, options, nullptr, out));     // host vectors and threads inside: nothing may unwind into the caller
+  DSA_GUARD(ctx, encode_batch(ctx, n, meshes, nullptr, nullptr, options, nullptr, out));     // host vectors and threads inside: nothing may unwind into the caller
 }
 dsa_status dsa_encode_batch_corners(dsa_context *ctx, uint32_t n, const dsa_mesh_corner_input *meshes, const dsa_encode_options *options, dsa_encoded **out) {
   if (!ctx || !out || (n && !meshes)) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "null argument");
   if (check_schemes(ctx, options, nullptr) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
-  DSA_GUARD(ctx, encode_batch(ctx, n, nullptr, meshes, options, nullptr, out));
+  DSA_GUARD(ctx, encode_batch(ctx, n, nullptr, meshes, nullptr, options, nullptr, out));
 }
 dsa_status dsa_encode_batch_ex(dsa_context *ctx, uint32_t n, const dsa_mesh_corner_input *meshes, const dsa_encode_options_ex *options, dsa_encoded **out) {
   if (!ctx || !out || (n && !meshes)) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "null argument");
@@ -763,7 +798,15 @@ dsa_status dsa_encode_batch_ex(dsa_context *ctx, uint32_t n, const dsa_mesh_corn
   dsa_encode_default_options_ex(&d);
   if (options) d = *options;
   if (check_schemes(ctx, &d.base, &d) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
-  DSA_GUARD(ctx, encode_batch(ctx, n, nullptr, meshes, &d.base, &d, out));
+  DSA_GUARD(ctx, encode_batch(ctx, n, nullptr, meshes, nullptr, &d.base, &d, out));
+}
+dsa_status dsa_encode_attributes_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_encode_options_ex *options, dsa_encoded **out) {
+  if (!ctx || !out || (n && !meshes)) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "null argument");
+  dsa_encode_options_ex d;
+  dsa_encode_default_options_ex(&d);
+  if (options) d = *options;
+  if (check_schemes(ctx, &d.base, &d) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+  DSA_GUARD(ctx, encode_batch(ctx, n, nullptr, nullptr, meshes, &d.base, &d, out));
 }
 // A batch is coded in chunks, several of them in flight (each on a lane of its own: stream + pinned staging + device memory).  The
 // device stages of a chunk are bound by latency -- the walks of k_enc_connectivity take a memory round trip per step, 0.1 - 0.2 s
@@ -847,17 +890,49 @@ static dsa_status encode_batch_chunks(dsa_context *ctx, uint32_t n, ChunkFn &&co
   return DSA_OK;
 }
 }  // extern "C++"
-static dsa_status encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_mesh_corner_input *corners, const dsa_encode_options *options, const dsa_encode_options_ex *ex, dsa_encoded **out) {
+static dsa_status encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_mesh_corner_input *corners, const dsa_mesh_attr_input *attrs, const dsa_encode_options *options, const dsa_encode_options_ex *ex, dsa_encoded **out) {
   return encode_batch_chunks(ctx, n, [&](dsa_context *sink, EncLane &lane, uint32_t base, uint32_t cnt, dsa_encoded **part) {
-    return encode_chunk(sink, lane, cnt, n, meshes ? meshes + base : nullptr, corners ? corners + base : nullptr, options, ex, part);
+    return encode_chunk(sink, lane, cnt, n, meshes ? meshes + base : nullptr, corners ? corners + base : nullptr, attrs ? attrs + base : nullptr, options, ex, part);
   }, out);
 }
-static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint32_t batch_n, const dsa_mesh_input *meshes_v, const dsa_mesh_corner_input *corners, const dsa_encode_options *options, const dsa_encode_options_ex *ex, dsa_encoded **out) {
-  // mesh i of the chunk, whichever entry point it came through (ids: its corner ids, null without)
+// The extras of a mesh with an attribute list as the host coder takes them (`ex` keeps them alive beside `in`); what the C structs
+// alone can say against them -- a reserved word -- is answered here, the rest by synth::extras_error.  "" when they can be written.
+static std::string enc_take_extras(const dsa_mesh_attr_input &am, std::vector<synth::ExtraAttr> &ex, synth::MeshIn &in) {
+  char buf[96];
+  if (am.reserved != 0) return "dsa_mesh_attr_input.reserved is not zero";
+  if (am.num_attributes && !am.attributes) return "attributes: the list is missing";
+  ex.resize(am.num_attributes);
+  for (uint32_t k = 0; k < am.num_attributes; ++k) {
+    const dsa_attribute_input &x = am.attributes[k];
+    for (int r = 0; r < 2; ++r)
+      if (x.reserved[r] != 0) { snprintf(buf, sizeof(buf), "attribute %u: reserved[%d] is not zero", k, r); return buf; }
+    ex[k].att_type = x.attribute_type; ex[k].data_type = x.data_type; ex[k].nc = x.num_components; ex[k].normalized = x.normalized;
+    ex[k].unique_id = x.unique_id; ex[k].bits = x.quantization_bits; ex[k].values = x.values;
+  }
+  in.extras = ex.data(); in.num_extras = am.num_attributes;
+  return synth::extras_error(in);
+}
+// hist_cap of an integer extra: one-byte types by their range, wider ones by the values present (a pass over the values by the
+// host thread that checks the mesh's indices anyway): zig-zagged wrapped corrections lie in 0 .. max - min + 1
+static uint32_t enc_extra_hist_cap(const synth::PortableAttr &a, uint32_t rows) {
+  if (synth::data_type_size(a.data_type) == 1) return (1u << 8) + 2u;
+  const size_t total = (size_t)rows * (size_t)a.nc;
+  int32_t lo = 0, hi = 0;
+  if (a.data_type == 3) { const int16_t *p = (const int16_t *)a.extra_values; int16_t l = p[0], h = p[0]; for (size_t k = 1; k < total; ++k) { l = p[k] < l ? p[k] : l; h = p[k] > h ? p[k] : h; } lo = l; hi = h; }
+  else if (a.data_type == 4) { const uint16_t *p = (const uint16_t *)a.extra_values; uint16_t l = p[0], h = p[0]; for (size_t k = 1; k < total; ++k) { l = p[k] < l ? p[k] : l; h = p[k] > h ? p[k] : h; } lo = l; hi = h; }
+  else { const int32_t *p = (const int32_t *)a.extra_values; lo = hi = p[0]; for (size_t k = 1; k < total; ++k) { lo = p[k] < lo ? p[k] : lo; hi = p[k] > hi ? p[k] : hi; } }     // (uint32 by reinterpretation)
+  return dsa::enc_integer_hist_cap(lo, hi);
+}
+static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint32_t batch_n, const dsa_mesh_input *meshes_v, const dsa_mesh_corner_input *corners_v, const dsa_mesh_attr_input *attrs, const dsa_encode_options *options, const dsa_encode_options_ex *ex, dsa_encoded **out) {
+  // mesh i of the chunk, whichever entry point it came through (corner(i): its corner form, null for dsa_encode_batch)
   struct MeshRef {
-    const dsa_mesh_input *v; const dsa_mesh_corner_input *c;
-    const dsa_mesh_input &operator[](size_t i) const { return c ? c[i].mesh : v[i]; }
-  } meshes{meshes_v, corners};
+    const dsa_mesh_input *v; const dsa_mesh_corner_input *c; const dsa_mesh_attr_input *a;
+    const dsa_mesh_corner_input *corner(size_t i) const { return a ? &a[i].mesh : (c ? &c[i] : nullptr); }
+    const dsa_mesh_input &operator[](size_t i) const { return (a || c) ? corner(i)->mesh : v[i]; }
+  } meshes{meshes_v, corners_v, attrs};
+  const bool corners = corners_v != nullptr || attrs != nullptr;
+  std::vector<std::vector<synth::ExtraAttr>> extras(attrs ? n : 0);
+  std::vector<std::vector<uint32_t>> extra_cap(attrs ? n : 0);      // per attribute of the plan: hist_cap of an integer extra, else 0
   hostutil::TurnGuard turn(lane.upload_turn, lane.upload_chunk);      // (whatever happens below, the other chunks' uploads do not wait for this one's)
   HIP_TRY(ctx, hipSetDevice(lane.device));
   dsa_encode_options od;
@@ -916,12 +991,23 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
     in.pos = m.positions; in.nv = m.num_vertices; in.faces = m.faces; in.nf = m.num_faces; in.normals = m.normals; in.uvs = m.texcoords;
     in.generic = (m.generic && m.generic_components >= 1 && m.generic_components <= 4) ? m.generic : nullptr;
     if (corners) {
-      const dsa_mesh_corner_input &cm = corners[i];
+      const dsa_mesh_corner_input &cm = *meshes.corner(i);
       if (m.generic && (m.generic_components < 1 || m.generic_components > 4)) { E->status[i] = DSA_ERR_INVALID_ARGUMENT; E->messages[i] = "generic attribute needs 1 - 4 components"; return; }
       if ((cm.normal_corners && !m.normals) || (cm.texcoord_corners && !m.texcoords)) { E->status[i] = DSA_ERR_INVALID_ARGUMENT; E->messages[i] = "corner ids without their values"; return; }
       in.normal_corners = cm.normal_corners; in.nn = cm.num_normals;
       in.uv_corners = cm.texcoord_corners; in.nu = cm.num_texcoords;
     }
+    if (attrs) {
+      const std::string why = enc_take_extras(attrs[i], extras[i], in);
+      if (!why.empty()) { E->status[i] = DSA_ERR_INVALID_ARGUMENT; E->messages[i] = why; return; }
+    }
+    // (the bounds of the integer extras' values, once the plan below has said which attributes there are)
+    auto extra_caps = [&]() {
+      if (!attrs) return;
+      extra_cap[i].assign(plans[i].atts.size(), 0);
+      for (size_t k = 0; k < plans[i].atts.size(); ++k)
+        if (plans[i].atts[k].extra_values && plans[i].atts[k].seq_type == 1) extra_cap[i][k] = enc_extra_hist_cap(plans[i].atts[k], m.num_vertices);
+    };
     try {
       synth::check(m.positions && m.faces && m.num_vertices >= 3 && m.num_faces >= 1, "mesh needs positions and faces");
       for (size_t k = 0; k < (size_t)m.num_faces * 3; ++k) synth::check(m.faces[k] < m.num_vertices, "face index out of range");
@@ -935,9 +1021,11 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
         synth::check(!((in.normal_corners || in.uv_corners) && opt.single_connectivity), "attributes given per corner need a connectivity of their own (single_connectivity = 0)");
         synth::check(!(in.normal_corners || in.uv_corners) || 24ull * m.num_faces + 16u < (1ull << 32), "mesh too large for the device connectivity coder");
         synth::plan_attributes(in, mo, plans[i]);
+        extra_caps();
         return;
       }
       synth::plan_mesh(in, mo, plans[i]);
+      extra_caps();
       const synth::MeshPlan &pl = plans[i];
       dsa::entry_maps(pl.ct, pl.seq, nullptr, e2v[i], &ops[i]);
       att_e2v[i].assign(pl.atts.size(), {}); att_ops[i].assign(pl.atts.size(), {});
@@ -966,7 +1054,7 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
   // value rows of attribute k of mesh i: its ids' row count when it is given per corner
   auto rows_of = [&](uint32_t i, const synth::PortableAttr &a) -> uint32_t {
     if (!a.corner_value) return meshes[i].num_vertices;
-    return a.att_type == 1 ? corners[i].num_normals : corners[i].num_texcoords;
+    return a.att_type == 1 ? meshes.corner(i)->num_normals : meshes.corner(i)->num_texcoords;
   };
   auto ids_narrow = [&](uint32_t i, const synth::PortableAttr &a) { return rows_of(i, a) <= 65536; };
   // What the host provides (faces, raw attribute values; with host connectivity the traversal order and operands) lies at the
@@ -1063,8 +1151,9 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
       const synth::PortableAttr &a = plans[i].atts[k];
       dsa::EncStream S;
       memset(&S, 0, sizeof(S));
-      const bool integer = a.att_type == 4;                  // the generic uint8 attribute
-      const void *src = a.att_type == 0 ? (const void *)meshes[i].positions : (a.att_type == 1 ? (const void *)meshes[i].normals : (integer ? (const void *)meshes[i].generic : (const void *)meshes[i].texcoords));
+      const bool integer = a.seq_type == 1;                  // the generic uint8 attribute, an integer extra
+      const void *src = a.extra_values ? a.extra_values
+                        : (a.att_type == 0 ? (const void *)meshes[i].positions : (a.att_type == 1 ? (const void *)meshes[i].normals : (integer ? (const void *)meshes[i].generic : (const void *)meshes[i].texcoords)));
       // entries: V, or for an attribute given per corner as many as its walk has (host connectivity) / may have (device: 3F at
       // most, k_enc_seam_operands sets the count)
       const uint32_t rows = rows_of(i, a);
@@ -1090,14 +1179,16 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
       }
       S.nv = entries; S.rows = rows; S.nc_out = (uint32_t)a.nc_out; S.nc = (uint32_t)a.nc; S.kind = a.seq_type == 3 ? 1u : (integer ? 2u : 0u);
       S.bits = integer ? 9u : (uint32_t)a.bits; S.prediction = (uint32_t)a.prediction;      // (9: the zig-zagged corrections of bytes are below 512)
-      const uint64_t src_bytes = (integer ? 1ull : 4ull) * rows * S.nc_out;
+      S.elem = integer ? (uint32_t)a.data_type : 0u;
+      const uint64_t src_bytes = (integer ? (uint64_t)synth::data_type_size(a.data_type) : 4ull) * rows * S.nc_out;
       S.src = take_in(src_bytes);
       uploads.push_back({S.src, src, src_bytes, false});
       S.vals = take(4ull * rows * S.nc); S.d = take(4ull * cap * S.nc); S.syms = take(4ull * cap * S.nc); S.bl = take(cap);
       max_rows = std::max(max_rows, std::max(rows, cap));
       S.hist_cap = (1u << S.bits) + 2u;                      // zig-zag of a wrapped correction / a positive octahedral correction fits
+      if (attrs && extra_cap[i][k]) S.hist_cap = extra_cap[i][k];       // an integer extra: by the values present
       S.hist_raw = take(4ull * S.hist_cap);
-      S.out_cap = 4u * cap * S.nc + 16u;
+      S.out_cap = 4u * cap * S.nc + 16u;                     // (tagged bit fields are at most 32 bits a symbol, a coded symbol at most 20 bits and the flush)
       S.out_rans = take(S.out_cap); S.out_bits = take(S.out_cap);
       const uint64_t table_cap = std::max<uint64_t>(S.hist_cap, 64);   // the tagged scheme's alphabet is 33 bit lengths
       S.prob = take(4ull * table_cap); S.cum = take(4ull * table_cap);

@@ -716,9 +716,10 @@ struct Options {
                                      // bytes (SequentialIntegerAttributeDecoder.cs:68-84)
   int32_t no_prediction = 0;         // bit 0 positions, bit 1 texture coordinates, bit 2 normals, bit 3 the generic attribute: prediction
                                      // method -2 (none)
-  int32_t generic_components = 1;    // components of the generic attribute (4 = the RGBA colours of a scan); CPU coder only
+  int32_t generic_components = 1;    // components of the generic attribute (4 = the RGBA colours of a scan)
   int32_t generic_data_type = 2;     // element type of the generic attribute, Draco's ids: 1 int8, 2 uint8, 3 int16, 4 uint16, 5 int32,
-                                     // 6 uint32 (joint indices, 16-bit colours, feature ids); CPU coder only
+                                     // 6 uint32 (joint indices, 16-bit colours, feature ids); the device encoder's generic attribute is
+                                     // uint8, it writes the other types from MeshIn::extras (dsa_mesh_attr_input)
 };
 
 // Octahedral quantisation (OctahedronToolBox.cs:28-119)
@@ -777,6 +778,9 @@ struct PortableAttr {
   const uint32_t *corner_value = nullptr;   // value id per corner of the source mesh (attributes given per corner: seams)
   std::vector<float> qmin; float qrange = 1; int bits = 0;
   int prediction = 1;
+  int normalized = 0;                  // the descriptor's flag
+  uint32_t unique_id = kInvalid;       // kInvalid: the attribute's index in the stream
+  const void *extra_values = nullptr;  // an attribute of MeshIn::extras: its rows, nc elements of data_type each (else the built-in source)
 };
 
 // AttributeQuantizationTransform.cs:66-108,136-177 + Core/Quantizer.cs (E-1 corrected)
@@ -855,6 +859,20 @@ static int32_t generic_value(const void *g, size_t k, int dt) {
   }
 }
 
+// One more per-vertex attribute behind the built-in ones (positions, normals, texture coordinates, the generic attribute):
+// colours, joints and weights, a second UV set, feature ids.  Integer element types are coded as they are, float32 quantised.
+struct ExtraAttr {
+  int32_t att_type = 4;              // 2 colour, 3 texture coordinate, 4 generic
+  int32_t data_type = 2;             // Draco's ids: 1 int8 ... 6 uint32, 9 float32
+  uint32_t nc = 1;                   // 1..4
+  int32_t normalized = 0;            // 0 / 1, into the descriptor (integer types)
+  uint32_t unique_id = kInvalid;     // kInvalid: the attribute's index in the stream
+  int32_t bits = 0;                  // float32: 1..20; 0: uv_bits for a texture coordinate, else 8
+  const void *values = nullptr;      // nv rows, packed
+};
+static const size_t kMaxAttributes = 16;   // DSA_MAX_ATTRIBUTES: what the decode direction takes
+static inline size_t data_type_size(int dt) { return (dt == 1 || dt == 2) ? 1 : ((dt == 3 || dt == 4) ? 2 : 4); }
+
 struct MeshIn {
   const float *pos; uint32_t nv; const uint32_t *faces; uint32_t nf;
   const float *normals; const float *uvs;
@@ -864,7 +882,42 @@ struct MeshIn {
   // (MeshAttributeCornerTable.cs:32-78).  Null: one value per vertex.
   const uint32_t *normal_corners = nullptr; uint32_t nn = 0;
   const uint32_t *uv_corners = nullptr; uint32_t nu = 0;
+  const ExtraAttr *extras = nullptr; uint32_t num_extras = 0;      // written behind the attributes above, in list order
 };
+
+// Why the extras of a mesh cannot be written ("" when they can): the attribute's index in the list and the field.
+static std::string extras_error(const MeshIn &in) {
+  const size_t builtins = 1 + (in.normals ? 1 : 0) + (in.uvs ? 1 : 0) + (in.generic ? 1 : 0);
+  char buf[160];
+  if (in.num_extras && !in.extras) return "attributes: the list is missing";
+  if (builtins + in.num_extras > kMaxAttributes) {
+    snprintf(buf, sizeof(buf), "attributes: %zu built-in and %u listed attributes exceed the %zu a stream may hold", builtins, in.num_extras, kMaxAttributes);
+    return buf;
+  }
+  auto bad = [&](uint32_t k, const char *field, long long v, const char *legal) {
+    snprintf(buf, sizeof(buf), "attribute %u: %s %lld: %s", k, field, v, legal);
+    return std::string(buf);
+  };
+  for (uint32_t k = 0; k < in.num_extras; ++k) {
+    const ExtraAttr &x = in.extras[k];
+    if (x.att_type != 2 && x.att_type != 3 && x.att_type != 4) return bad(k, "attribute_type", x.att_type, "2 (colour), 3 (texture coordinate) or 4 (generic)");
+    if (!((x.data_type >= 1 && x.data_type <= 6) || x.data_type == 9)) return bad(k, "data_type", x.data_type, "1 (int8) to 6 (uint32) or 9 (float32)");
+    if (x.nc < 1 || x.nc > 4) return bad(k, "num_components", x.nc, "1 to 4");
+    if (x.normalized != 0 && x.normalized != 1) return bad(k, "normalized", x.normalized, "0 or 1");
+    if (x.data_type == 9 && (x.bits < 0 || x.bits > 20)) return bad(k, "quantization_bits", x.bits, "1 to 20, or 0 for the default");
+    if (!x.values) { snprintf(buf, sizeof(buf), "attribute %u: values is NULL", k); return buf; }
+    const uint32_t uid = x.unique_id == kInvalid ? (uint32_t)(builtins + k) : x.unique_id;
+    for (uint32_t j = 0; j < builtins + k; ++j) {
+      const uint32_t other = j < builtins ? j : (in.extras[j - builtins].unique_id == kInvalid ? j : in.extras[j - builtins].unique_id);
+      if (other == uid) { snprintf(buf, sizeof(buf), "attribute %u: unique_id %u is the id of attribute %u of the stream", k, uid, j); return buf; }
+    }
+  }
+  return "";
+}
+// The descriptors of the extras, behind the built-in ones.  `prediction`: what the generic attribute gets on this path.
+static void plan_extra_attributes(const MeshIn &in, const Options &opt, int prediction, std::vector<PortableAttr> &atts);
+// Portable values of an extra: integers as they are, floats quantised (AttributeQuantizationTransform).
+static void fill_extra_values(const PortableAttr &a, uint32_t nv, PortableAttr &out);
 
 // One attribute's value section: method, transform, compressed flag, symbols, prediction data
 // (SequentialIntegerAttributeEncoder.cs:55-128)
@@ -1178,6 +1231,25 @@ static void write_attribute_transform(ByteWriter &w, const PortableAttr &a) {
   else if (a.seq_type == 3) w.u8((uint8_t)a.bits);
 }
 
+static void plan_extra_attributes(const MeshIn &in, const Options &opt, int prediction, std::vector<PortableAttr> &atts) {
+  const std::string err = extras_error(in);
+  check(err.empty(), err.c_str());
+  for (uint32_t k = 0; k < in.num_extras; ++k) {
+    const ExtraAttr &x = in.extras[k];
+    PortableAttr a;
+    a.att_type = x.att_type; a.nc = a.nc_out = (int)x.nc; a.data_type = x.data_type; a.prediction = prediction;
+    a.unique_id = x.unique_id; a.extra_values = x.values;
+    if (x.data_type == 9) { a.seq_type = 2; a.bits = x.bits ? x.bits : (x.att_type == 3 ? opt.uv_bits : 8); }
+    else { a.seq_type = 1; a.normalized = x.normalized; }
+    atts.push_back(a);
+  }
+}
+static void fill_extra_values(const PortableAttr &a, uint32_t nv, PortableAttr &out) {
+  if (a.seq_type == 2) { quantize((const float *)a.extra_values, nv, a.nc, a.bits, out); return; }
+  out.vals.resize((size_t)nv * a.nc);
+  for (size_t k = 0; k < (size_t)nv * a.nc; ++k) out.vals[k] = generic_value(a.extra_values, k, a.data_type);
+}
+
 // Everything about a mesh that does not depend on attribute values: connectivity, traversal order, attribute list.
 struct MeshPlan {
   CornerTable ct;
@@ -1222,6 +1294,7 @@ static void plan_attributes(const MeshIn &in, const Options &opt, MeshPlan &pl) 
   if (in.uvs) { PortableAttr a; a.att_type = 3; a.nc = a.nc_out = 2; a.seq_type = 2; a.data_type = 9; a.prediction = opt.uv_prediction; a.bits = opt.uv_bits; a.corner_value = in.uv_corners; pl.atts.push_back(a); }
   // (the generic attribute takes the constrained multi-parallelogram scheme where the positions do: what an encoder at its highest levels writes)
   if (in.generic) { PortableAttr a; a.att_type = 4; a.nc = a.nc_out = opt.generic_components >= 1 && opt.generic_components <= 4 ? opt.generic_components : 1; a.seq_type = 1; a.data_type = opt.generic_data_type; a.prediction = opt.pos_prediction == 4 ? 4 : 1; pl.atts.push_back(a); }
+  plan_extra_attributes(in, opt, opt.pos_prediction == 4 ? 4 : 1, pl.atts);
   pl.single = opt.single_connectivity != 0;
   pl.num_att_data = pl.single ? 0 : (uint32_t)pl.atts.size() - 1;
   pl.force_scheme = opt.force_scheme; pl.compression_level = opt.compression_level;
@@ -1349,7 +1422,7 @@ static void write_stream(ByteWriter &w, const MeshIn &in, const MeshPlan &pl, Va
   w.u8((uint8_t)num_encoders);
   // attribute data id, element type (1: corner attribute -- the attribute's own connectivity is used, :442-466), MeshTraversalMethod
   for (uint32_t i = 0; i < num_encoders; ++i) { w.i8(i == 0 ? -1 : (int8_t)(i - 1)); w.u8(pl.seamed(i) ? 1 : 0); w.u8(pl.uses_pd(i) ? 1 : 0); }
-  auto write_desc = [&](const PortableAttr &a, uint32_t uid) { w.u8((uint8_t)a.att_type); w.u8((uint8_t)a.data_type); w.u8((uint8_t)a.nc_out); w.u8(0); w.varint(uid); };
+  auto write_desc = [&](const PortableAttr &a, uint32_t index) { w.u8((uint8_t)a.att_type); w.u8((uint8_t)a.data_type); w.u8((uint8_t)a.nc_out); w.u8((uint8_t)a.normalized); w.varint(a.unique_id == kInvalid ? index : a.unique_id); };
   if (pl.single) {
     w.varint(atts.size());
     for (size_t i = 0; i < atts.size(); ++i) write_desc(atts[i], (uint32_t)i);
@@ -1367,7 +1440,8 @@ static void encode_mesh(const MeshIn &in, const Options &opt, std::vector<uint8_
   MeshPlan pl;
   plan_mesh(in, opt, pl);
   for (auto &a : pl.atts) {
-    if (a.att_type == 0) quantize(in.pos, in.nv, 3, opt.pos_bits, a);
+    if (a.extra_values) fill_extra_values(a, in.nv, a);
+    else if (a.att_type == 0) quantize(in.pos, in.nv, 3, opt.pos_bits, a);
     else if (a.att_type == 1) {
       const uint32_t n = in.normal_corners ? in.nn : in.nv;
       Octa o(opt.normal_bits);
@@ -1399,6 +1473,7 @@ static void plan_sequential_attributes(const MeshIn &in, const Options &opt, std
   if (in.normals) { PortableAttr a; a.att_type = 1; a.nc_out = 3; a.nc = 2; a.seq_type = 3; a.data_type = 9; a.bits = opt.normal_bits; a.prediction = 0; atts.push_back(a); }
   if (in.uvs) { PortableAttr a; a.att_type = 3; a.nc = a.nc_out = 2; a.seq_type = 2; a.data_type = 9; a.prediction = 0; a.bits = opt.uv_bits; atts.push_back(a); }
   if (in.generic) { PortableAttr a; a.att_type = 4; a.nc = a.nc_out = opt.generic_components >= 1 && opt.generic_components <= 4 ? opt.generic_components : 1; a.seq_type = 1; a.data_type = opt.generic_data_type; a.prediction = 0; atts.push_back(a); }
+  plan_extra_attributes(in, opt, 0, atts);
 }
 // Compressed indices: symbol k = |f[k] - f[k-1]| << 1 | sign, f[-1] = 0 (MeshSequentialEncoder.cs:84-121)
 static void sequential_index_symbols(const uint32_t *faces, size_t count, std::vector<uint32_t> &sym) {
@@ -1435,7 +1510,7 @@ static void write_sequential_stream(ByteWriter &w, bool mesh, uint32_t nv, uint3
   } else w.i32((int32_t)nv);
   w.u8(1);
   w.varint(atts.size());
-  for (size_t i = 0; i < atts.size(); ++i) { w.u8((uint8_t)atts[i].att_type); w.u8((uint8_t)atts[i].data_type); w.u8((uint8_t)atts[i].nc_out); w.u8(0); w.varint(i); }
+  for (size_t i = 0; i < atts.size(); ++i) { w.u8((uint8_t)atts[i].att_type); w.u8((uint8_t)atts[i].data_type); w.u8((uint8_t)atts[i].nc_out); w.u8((uint8_t)atts[i].normalized); w.varint(atts[i].unique_id == kInvalid ? (uint32_t)i : atts[i].unique_id); }
   for (auto &a : atts) w.u8((uint8_t)a.seq_type);
   for (size_t i = 0; i < atts.size(); ++i) values(w, i);
   for (size_t i = 0; i < atts.size(); ++i) transform(w, i);
@@ -1445,7 +1520,8 @@ static void encode_sequential(const MeshIn &in, const Options &opt, bool mesh, b
   std::vector<PortableAttr> atts;
   plan_sequential_attributes(in, opt, atts);
   for (auto &a : atts) {
-    if (a.att_type == 0) quantize(in.pos, in.nv, 3, opt.pos_bits, a);
+    if (a.extra_values) fill_extra_values(a, in.nv, a);
+    else if (a.att_type == 0) quantize(in.pos, in.nv, 3, opt.pos_bits, a);
     else if (a.att_type == 1) {
       Octa o(opt.normal_bits);
       a.vals.resize((size_t)in.nv * 2);

@@ -16,7 +16,14 @@
 
 #include "dsa_encode_seqidx.h"
 
-static dsa_status encode_sequential_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint32_t batch_n, const dsa_mesh_input *meshes, const dsa_encode_sequential_options &so, dsa_encoded **out) {
+// `attrs` (dsa_encode_attributes_sequential_batch): meshes with an attribute list, `meshes_v` null.
+static dsa_status encode_sequential_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint32_t batch_n, const dsa_mesh_input *meshes_v, const dsa_mesh_attr_input *attrs, const dsa_encode_sequential_options &so, dsa_encoded **out) {
+  struct MeshRef {
+    const dsa_mesh_input *v; const dsa_mesh_attr_input *a;
+    const dsa_mesh_input &operator[](size_t i) const { return a ? a[i].mesh.mesh : v[i]; }
+  } meshes{meshes_v, attrs};
+  std::vector<std::vector<synth::ExtraAttr>> extras(attrs ? n : 0);
+  std::vector<std::vector<uint32_t>> extra_cap(attrs ? n : 0);      // per attribute: hist_cap of an integer extra, else 0
   hostutil::TurnGuard turn(lane.upload_turn, lane.upload_chunk);
   HIP_TRY(ctx, hipSetDevice(lane.device));
   const dsa_encode_options &od = so.base;
@@ -41,6 +48,8 @@ static dsa_status encode_sequential_chunk(dsa_context *ctx, EncLane &lane, uint3
     if (!is_mesh && m.num_faces != 0) return refuse(DSA_ERR_INVALID_ARGUMENT, "a point cloud has no faces (geometry = 0, num_faces != 0)");
     if (is_mesh && (m.num_faces == 0 || !m.faces)) return refuse(DSA_ERR_INVALID_DATA, "a mesh needs faces");
     if (m.generic && (m.generic_components < 1 || m.generic_components > 4)) return refuse(DSA_ERR_INVALID_ARGUMENT, "generic attribute needs 1 - 4 components");
+    if (attrs && (attrs[i].mesh.normal_corners || attrs[i].mesh.texcoord_corners))
+      return refuse(DSA_ERR_INVALID_ARGUMENT, "corner ids with a sequential stream: it has one value per point (normal_corners / texcoord_corners must be NULL)");
     // (what the 32-bit sizes of a stream's regions hold: 4 bytes per component and symbol, and a margin)
     if (m.num_vertices > (1u << 28) || (compressed && m.num_faces > (1u << 28))) return refuse(DSA_ERR_INVALID_DATA, "mesh too large for the device coder");
     if (is_mesh) {
@@ -53,7 +62,16 @@ static dsa_status encode_sequential_chunk(dsa_context *ctx, EncLane &lane, uint3
     in.normals = m.normals; in.uvs = m.texcoords; in.generic = m.generic;
     synth::Options mo = opt;
     mo.generic_components = m.generic ? (int32_t)m.generic_components : 1;
+    if (attrs) {
+      const std::string why = enc_take_extras(attrs[i], extras[i], in);
+      if (!why.empty()) { E->status[i] = DSA_ERR_INVALID_ARGUMENT; E->messages[i] = why; return; }
+    }
     synth::plan_sequential_attributes(in, mo, atts[i]);
+    if (attrs) {
+      extra_cap[i].assign(atts[i].size(), 0);
+      for (size_t k = 0; k < atts[i].size(); ++k)
+        if (atts[i][k].extra_values && atts[i][k].seq_type == 1) extra_cap[i][k] = enc_extra_hist_cap(atts[i][k], m.num_vertices);
+    }
   });
   // ---- device layout: what the host provides (attribute values; the faces of compressed indices, 16-bit where every index fits) in
   // one run at the front of the arena, everything else behind it
@@ -66,7 +84,7 @@ static dsa_status encode_sequential_chunk(dsa_context *ctx, EncLane &lane, uint3
     if (E->status[i] != DSA_OK) continue;
     const uint64_t V = meshes[i].num_vertices, F = meshes[i].num_faces;
     if (compressed) in_total += al((V <= 65536 ? 6 : 12) * F);
-    for (const synth::PortableAttr &a : atts[i]) in_total += al((a.att_type == 4 ? 1ull : 4ull) * V * (uint64_t)a.nc_out);
+    for (const synth::PortableAttr &a : atts[i]) in_total += al((a.seq_type == 1 ? (uint64_t)synth::data_type_size(a.data_type) : 4ull) * V * (uint64_t)a.nc_out);
   }
   uint64_t cur = in_total, cur_in = 0;
   auto take = [&](uint64_t bytes) { uint64_t at = cur; cur = (cur + bytes + 255) & ~255ull; return at; };
@@ -77,20 +95,24 @@ static dsa_status encode_sequential_chunk(dsa_context *ctx, EncLane &lane, uint3
     first_stream[i] = (uint32_t)hs.size();
     if (E->status[i] != DSA_OK) continue;
     const uint32_t V = meshes[i].num_vertices;
-    for (const synth::PortableAttr &a : atts[i]) {
+    for (size_t k = 0; k < atts[i].size(); ++k) {
+      const synth::PortableAttr &a = atts[i][k];
       dsa::EncStream S;
       memset(&S, 0, sizeof(S));
-      const bool integer = a.att_type == 4;
-      const void *src = a.att_type == 0 ? (const void *)meshes[i].positions : (a.att_type == 1 ? (const void *)meshes[i].normals : (integer ? (const void *)meshes[i].generic : (const void *)meshes[i].texcoords));
+      const bool integer = a.seq_type == 1;
+      const void *src = a.extra_values ? a.extra_values
+                        : (a.att_type == 0 ? (const void *)meshes[i].positions : (a.att_type == 1 ? (const void *)meshes[i].normals : (integer ? (const void *)meshes[i].generic : (const void *)meshes[i].texcoords)));
       S.nv = S.rows = V; S.nc_out = (uint32_t)a.nc_out; S.nc = (uint32_t)a.nc; S.kind = a.seq_type == 3 ? 1u : (integer ? 2u : 0u);
       S.bits = integer ? 9u : (uint32_t)a.bits; S.prediction = 0; S.linear = 1;
-      const uint64_t src_bytes = (integer ? 1ull : 4ull) * V * S.nc_out;
+      S.elem = integer ? (uint32_t)a.data_type : 0u;
+      const uint64_t src_bytes = (integer ? (uint64_t)synth::data_type_size(a.data_type) : 4ull) * V * S.nc_out;
       S.src = take_in(src_bytes);
       uploads.push_back({S.src, src, (size_t)src_bytes, false});
       S.vals = S.d = take(4ull * V * S.nc);                   // linear order: the values are the entries
       S.syms = take(4ull * V * S.nc); S.bl = take(V);
       max_rows = std::max(max_rows, V);
       S.hist_cap = (1u << S.bits) + 2u;
+      if (attrs && extra_cap[i][k]) S.hist_cap = extra_cap[i][k];       // an integer extra: by the values present
       S.hist_raw = take(4ull * S.hist_cap);
       S.out_cap = 4u * V * S.nc + 16u;
       S.out_rans = take(S.out_cap); S.out_bits = take(S.out_cap);
@@ -210,8 +232,8 @@ void dsa_encode_sequential_default_options(dsa_encode_sequential_options *o) {
   o->compress_connectivity = 0;
 }
 
-dsa_status dsa_encode_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_encode_sequential_options *options, dsa_encoded **out) {
-  if (!ctx || !out || (n && !meshes)) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "null argument");
+static dsa_status encode_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_mesh_attr_input *attrs, const dsa_encode_sequential_options *options, dsa_encoded **out) {
+  if (!ctx || !out || (n && !meshes && !attrs)) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "null argument");
   dsa_encode_sequential_options d;
   dsa_encode_sequential_default_options(&d);
   if (options) d = *options;
@@ -226,8 +248,15 @@ dsa_status dsa_encode_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_m
   for (int k = 0; k < 6; ++k)
     if (d.reserved[k] != 0) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "dsa_encode_sequential_options.reserved[%d] is not zero", k);
   DSA_GUARD(ctx, encode_batch_chunks(ctx, n, [&](dsa_context *sink, EncLane &lane, uint32_t base, uint32_t cnt, dsa_encoded **part) {
-    return encode_sequential_chunk(sink, lane, cnt, n, meshes + base, d, part);
+    return encode_sequential_chunk(sink, lane, cnt, n, meshes ? meshes + base : nullptr, attrs ? attrs + base : nullptr, d, part);
   }, out));
+}
+
+dsa_status dsa_encode_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_encode_sequential_options *options, dsa_encoded **out) {
+  return encode_sequential_batch(ctx, n, meshes, nullptr, options, out);
+}
+dsa_status dsa_encode_attributes_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_encode_sequential_options *options, dsa_encoded **out) {
+  return encode_sequential_batch(ctx, n, nullptr, meshes, options, out);
 }
 
 }  // extern "C"

@@ -88,16 +88,74 @@ class Config:
         return o
 
 
+ATTRIBUTE_DATA_TYPES = {np.dtype(np.int8): 1, np.dtype(np.uint8): 2, np.dtype(np.int16): 3, np.dtype(np.uint16): 4,
+                        np.dtype(np.int32): 5, np.dtype(np.uint32): 6, np.dtype(np.float32): 9}      # Draco's DataType ids
+
+
+class Attribute:
+    """One more per-vertex (per-point) attribute behind positions / normals / the first UV set / `generic`: COLOR_0, JOINTS_0,
+    WEIGHTS_0, a second UV set, feature ids.  values (V,) or (V, 1..4); the element type is the array's: int8, uint8, int16,
+    uint16, int32, uint32 (coded as they are; 32-bit values within +-2^27 as int32) or float32 (quantised to quantization_bits,
+    1..20; 0: the texture coordinates' bits for attribute_type 3, else 8).  attribute_type 2 colour, 3 texture coordinate,
+    4 generic; normalized goes into the descriptor of an integer attribute; unique_id None: the attribute's index in the stream."""
+
+    def __init__(self, values, attribute_type=4, normalized=False, unique_id=None, quantization_bits=0):
+        v = np.asarray(values)
+        if v.dtype not in ATTRIBUTE_DATA_TYPES:
+            raise ValueError("attribute values of dtype %s: one of int8, uint8, int16, uint16, int32, uint32, float32" % v.dtype)
+        if v.ndim not in (1, 2) or len(v) == 0:
+            raise ValueError("attribute values: (V,) or (V, 1..4)")
+        v = np.ascontiguousarray(v).reshape(len(v), -1)
+        if not 1 <= v.shape[1] <= 4:
+            raise ValueError("attribute values: 1 - 4 components per vertex")
+        self.values = v
+        self.attribute_type, self.normalized, self.unique_id, self.quantization_bits = attribute_type, bool(normalized), unique_id, quantization_bits
+
+    @property
+    def data_type(self):
+        return ATTRIBUTE_DATA_TYPES[self.values.dtype]
+
+
+def _attributes(attributes, rows):
+    out = []
+    for k, a in enumerate(attributes or []):
+        if not isinstance(a, Attribute):
+            a = Attribute(a)
+        if len(a.values) != rows:
+            raise ValueError("attribute %d: one row per vertex (%d rows for %d vertices)" % (k, len(a.values), rows))
+        out.append(a)
+    return out
+
+
+def _fill_attr_input(dst, m, keep):
+    """dsa_mesh_attr_input.attributes / num_attributes of mesh `m`; `keep` holds the ctypes array alive."""
+    atts = getattr(m, "attributes", None) or []
+    dst.num_attributes = len(atts)
+    if not atts:
+        return
+    arr = (native.AttributeInput * len(atts))()
+    for k, a in enumerate(atts):
+        arr[k].attribute_type, arr[k].data_type, arr[k].num_components = a.attribute_type, a.data_type, a.values.shape[1]
+        arr[k].normalized = 1 if a.normalized else 0
+        arr[k].unique_id = native.UNIQUE_ID_DEFAULT if a.unique_id is None else a.unique_id
+        arr[k].quantization_bits = a.quantization_bits
+        arr[k].values = a.values.ctypes.data
+    keep.append(arr)
+    dst.attributes = arr
+
+
 class MeshData:
     """Triangle mesh with per-vertex attributes: positions (V,3) f32, faces (F,3) u32, optional normals (V,3), uvs (V,2) and one
-    generic uint8 attribute of 1 - 4 components (V,) or (V,C): vertex colours, ids (ABI 4).
+    generic uint8 attribute of 1 - 4 components (V,) or (V,C): vertex colours, ids (ABI 4).  attributes: a list of Attribute
+    (or arrays) written behind those, of any integer element type or float32 (dsa_encode_attributes_batch).
 
     normal_corners / texcoord_corners (F,3) u32: the normals / texture coordinates given per corner -- row ids into `normals` /
     `texcoords`, which then hold as many rows as the ids need (UV charts, hard edges).  Edges whose end points carry different ids
     on their two faces become attribute seams (dsa_encode_batch_corners)."""
 
-    def __init__(self, positions, faces, normals=None, texcoords=None, generic=None, normal_corners=None, texcoord_corners=None):
+    def __init__(self, positions, faces, normals=None, texcoords=None, generic=None, normal_corners=None, texcoord_corners=None, attributes=None):
         self.positions = np.ascontiguousarray(positions, np.float32)
+        self.attributes = _attributes(attributes, len(self.positions))
         self.faces = np.ascontiguousarray(faces, np.uint32)
         self.normals = None if normals is None else np.ascontiguousarray(normals, np.float32)
         self.texcoords = None if texcoords is None else np.ascontiguousarray(texcoords, np.float32)
@@ -136,10 +194,11 @@ class MeshData:
 class PointCloudData:
     """Point cloud with per-point attributes: positions (N,3) f32, optional normals (N,3), texcoords (N,2) and one generic uint8
     attribute of 1 - 4 components (N,) or (N,C).  Written as a sequential point-cloud stream (dsa_encode_sequential_batch,
-    geometry 0): point i of the stream is row i."""
+    geometry 0): point i of the stream is row i.  attributes: as for MeshData, one row per point."""
 
-    def __init__(self, positions, normals=None, texcoords=None, generic=None):
+    def __init__(self, positions, normals=None, texcoords=None, generic=None, attributes=None):
         self.positions = np.ascontiguousarray(positions, np.float32)
+        self.attributes = _attributes(attributes, len(self.positions))
         self.faces = np.zeros((0, 3), np.uint32)
         self.normals = None if normals is None else np.ascontiguousarray(normals, np.float32)
         self.texcoords = None if texcoords is None else np.ascontiguousarray(texcoords, np.float32)
@@ -232,12 +291,17 @@ class DracoEncoder:
         if clouds or config.sequential:
             return self._encode_sequential(ctx, meshes, config, 0 if clouds else 1)
         ex = config.extended
-        # the corner entry point only when some mesh carries ids (or an option needs dsa_encode_batch_ex, which takes the corner
-        # form); otherwise exactly the per-vertex call
-        corners = ex or any(getattr(m, "per_corner", False) for m in meshes)
-        arr = ((native.MeshCornerInput if corners else native.MeshInput) * max(1, n))()
+        # the attribute-list entry point only when some mesh has a list; the corner entry point only when some mesh carries ids (or
+        # an option needs dsa_encode_batch_ex, which takes the corner form); otherwise exactly the per-vertex call
+        listed = any(getattr(m, "attributes", None) for m in meshes)
+        corners = listed or ex or any(getattr(m, "per_corner", False) for m in meshes)
+        arr = ((native.MeshAttrInput if listed else (native.MeshCornerInput if corners else native.MeshInput)) * max(1, n))()
+        keep = []
         for i, m in enumerate(meshes):
-            mi = arr[i].mesh if corners else arr[i]
+            if listed:
+                _fill_attr_input(arr[i], m, keep)
+            ci = arr[i].mesh if listed else arr[i]
+            mi = ci.mesh if corners else arr[i]
             mi.num_vertices, mi.num_faces = len(m.positions), len(m.faces)
             mi.positions, mi.faces = m.positions.ctypes.data, m.faces.ctypes.data
             mi.normals = m.normals.ctypes.data if m.normals is not None else None
@@ -247,14 +311,14 @@ class DracoEncoder:
             mi.generic_components = g.shape[1] if g is not None else 0
             if corners:
                 nci, uci = getattr(m, "normal_corners", None), getattr(m, "texcoord_corners", None)
-                arr[i].normal_corners = nci.ctypes.data if nci is not None else None
-                arr[i].texcoord_corners = uci.ctypes.data if uci is not None else None
-                arr[i].num_normals = len(m.normals) if m.normals is not None else 0
-                arr[i].num_texcoords = len(m.texcoords) if m.texcoords is not None else 0
-        opt = config._native_ex() if ex else config._native()
+                ci.normal_corners = nci.ctypes.data if nci is not None else None
+                ci.texcoord_corners = uci.ctypes.data if uci is not None else None
+                ci.num_normals = len(m.normals) if m.normals is not None else 0
+                ci.num_texcoords = len(m.texcoords) if m.texcoords is not None else 0
+        opt = config._native_ex() if (ex or listed) else config._native()
         h = C.c_void_p()
         t0 = time.perf_counter()
-        entry = L.dsa_encode_batch_ex if ex else (L.dsa_encode_batch_corners if corners else L.dsa_encode_batch)
+        entry = L.dsa_encode_attributes_batch if listed else (L.dsa_encode_batch_ex if ex else (L.dsa_encode_batch_corners if corners else L.dsa_encode_batch))
         st = entry(ctx._h, n, arr, C.byref(opt), C.byref(h))
         t1 = time.perf_counter()
         if st != 0:
@@ -267,9 +331,13 @@ class DracoEncoder:
     def _encode_sequential(self, ctx, meshes, config, geometry):
         L = native.lib()
         n = len(meshes)
-        arr = (native.MeshInput * max(1, n))()
+        listed = any(getattr(m, "attributes", None) for m in meshes)
+        arr = ((native.MeshAttrInput if listed else native.MeshInput) * max(1, n))()
+        keep = []
         for i, m in enumerate(meshes):
-            mi = arr[i]
+            if listed:
+                _fill_attr_input(arr[i], m, keep)
+            mi = arr[i].mesh.mesh if listed else arr[i]
             mi.num_vertices, mi.num_faces = len(m.positions), len(m.faces)
             mi.positions = m.positions.ctypes.data
             mi.faces = m.faces.ctypes.data if len(m.faces) else None
@@ -280,7 +348,8 @@ class DracoEncoder:
             mi.generic_components = g.shape[1] if g is not None else 0
         opt = config._native_sequential(geometry)
         h = C.c_void_p()
-        st = L.dsa_encode_sequential_batch(ctx._h, n, arr, C.byref(opt), C.byref(h))
+        entry = L.dsa_encode_attributes_sequential_batch if listed else L.dsa_encode_sequential_batch
+        st = entry(ctx._h, n, arr, C.byref(opt), C.byref(h))
         if st != 0:
             _raise(st, ctx.error())
         return EncodedStreams(ctx, h, n)

@@ -24,6 +24,7 @@ EXPORTS = [
     "dsa_batch_kernel_times", "dsa_context_trim", "dsa_context_schedule_note",
     "dsa_encode_default_options", "dsa_encode_batch", "dsa_encode_batch_corners",
     "dsa_encode_default_options_ex", "dsa_encode_batch_ex", "dsa_encode_sequential_default_options", "dsa_encode_sequential_batch",
+    "dsa_encode_attributes_batch", "dsa_encode_attributes_sequential_batch",
     "dsa_encoded_size", "dsa_encoded_stream", "dsa_encoded_free",
     "dsa_pool_create", "dsa_pool_destroy", "dsa_pool_size", "dsa_pool_last_error", "dsa_pool_decode", "dsa_pool_job_locate",
     "dsa_pool_job_chunks", "dsa_pool_job_free", "dsa_pool_plan",
@@ -60,6 +61,22 @@ class MeshCornerInput(C.Structure):
     """dsa_mesh_corner_input: a mesh whose normals / texture coordinates may be given per corner (row ids per face corner)."""
     _fields_ = [("mesh", MeshInput), ("normal_corners", C.c_void_p), ("texcoord_corners", C.c_void_p),
                 ("num_normals", C.c_uint32), ("num_texcoords", C.c_uint32)]
+
+
+UNIQUE_ID_DEFAULT = 0xFFFFFFFF   # dsa_attribute_input.unique_id: the attribute's index in the stream
+
+
+class AttributeInput(C.Structure):
+    """dsa_attribute_input: one more per-vertex attribute behind the built-in ones (attribute_type 2 colour, 3 texture coordinate,
+    4 generic; data_type 1 int8 ... 6 uint32, 9 float32)."""
+    _fields_ = [("attribute_type", C.c_int32), ("data_type", C.c_int32), ("num_components", C.c_uint32), ("normalized", C.c_int32),
+                ("unique_id", C.c_uint32), ("quantization_bits", C.c_int32), ("values", C.c_void_p), ("reserved", C.c_uint32 * 2)]
+
+
+class MeshAttrInput(C.Structure):
+    """dsa_mesh_attr_input: a mesh (or point cloud) with an attribute list."""
+    _fields_ = [("mesh", MeshCornerInput), ("attributes", C.POINTER(AttributeInput)), ("num_attributes", C.c_uint32),
+                ("reserved", C.c_uint32)]
 
 
 class MeshInfo(C.Structure):
@@ -160,6 +177,8 @@ def lib():
         L.dsa_encode_sequential_default_options.argtypes = [C.POINTER(EncodeSequentialOptions)]
         L.dsa_encode_sequential_default_options.restype = None
         L.dsa_encode_sequential_batch.argtypes = [vp, u32, C.POINTER(MeshInput), C.POINTER(EncodeSequentialOptions), C.POINTER(vp)]
+        L.dsa_encode_attributes_batch.argtypes = [vp, u32, C.POINTER(MeshAttrInput), C.POINTER(EncodeOptionsEx), C.POINTER(vp)]
+        L.dsa_encode_attributes_sequential_batch.argtypes = [vp, u32, C.POINTER(MeshAttrInput), C.POINTER(EncodeSequentialOptions), C.POINTER(vp)]
         L.dsa_encoded_size.restype = u32
         L.dsa_encoded_size.argtypes = [vp]
         L.dsa_encoded_stream.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(C.c_size_t)]

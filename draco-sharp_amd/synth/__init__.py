@@ -27,6 +27,82 @@ GENERIC_DATA_TYPES = {np.dtype(np.int8): 1, np.dtype(np.uint8): 2, np.dtype(np.i
                       np.dtype(np.int32): 5, np.dtype(np.uint32): 6}
 
 
+FLOAT32_DATA_TYPE = 9
+UNIQUE_ID_DEFAULT = 0xFFFFFFFF
+
+
+class ExtraInput(C.Structure):
+    """synth_extra: one more per-vertex attribute behind the built-in ones."""
+    _fields_ = [("attribute_type", C.c_int32), ("data_type", C.c_int32), ("num_components", C.c_uint32), ("normalized", C.c_int32),
+                ("unique_id", C.c_uint32), ("quantization_bits", C.c_int32), ("values", C.c_void_p)]
+
+
+class Extra:
+    """One more per-vertex attribute for the `extra=[...]` of the encode calls: values (V,) or (V, 1..4) of int8 / uint8 / int16 /
+    uint16 / int32 / uint32 (coded as they are) or float32 (quantised to quantization_bits; 0: uv_bits for attribute_type 3, else
+    8).  attribute_type 2 colour, 3 texture coordinate, 4 generic; unique_id None: the attribute's index in the stream.
+    data_type / num_components override what the array says (the refusal tests)."""
+
+    def __init__(self, values, attribute_type=4, normalized=False, unique_id=None, quantization_bits=0, data_type=None, num_components=None):
+        v = np.asarray(values)
+        if v.dtype not in GENERIC_DATA_TYPES and v.dtype != np.dtype(np.float32):
+            raise ValueError("extra attribute: dtype %s is none of int8 ... uint32, float32" % v.dtype)
+        v = np.ascontiguousarray(v)
+        self.values = v.reshape(len(v), -1)
+        self.attribute_type = attribute_type
+        self.data_type = (GENERIC_DATA_TYPES.get(v.dtype, FLOAT32_DATA_TYPE)) if data_type is None else data_type
+        self.num_components = self.values.shape[1] if num_components is None else num_components
+        self.normalized = int(normalized)
+        self.unique_id = UNIQUE_ID_DEFAULT if unique_id is None else unique_id
+        self.quantization_bits = quantization_bits
+
+
+def _extras(extra, nv):
+    """The synth_extra array of a list of Extra; the Extras own the value arrays, keep them beside it."""
+    arr = (ExtraInput * max(1, len(extra)))()
+    for k, e in enumerate(extra):
+        if len(e.values) != nv:
+            raise ValueError("extra attribute %d: one row per vertex" % k)
+        arr[k].attribute_type, arr[k].data_type, arr[k].num_components = e.attribute_type, e.data_type, e.num_components
+        arr[k].normalized, arr[k].unique_id, arr[k].quantization_bits = e.normalized, e.unique_id, e.quantization_bits
+        arr[k].values = e.values.ctypes.data
+    return arr
+
+
+def _encode_attributes(edgebreaker, pos, faces, nrm, nci, uv, uci, generic, geometry, compressed, extra, opt):
+    """Any stream with `extra` behind the built-in attributes (synth_encode_attributes)."""
+    L = lib()
+    pos = np.ascontiguousarray(pos, np.float32)
+    faces = None if faces is None else np.ascontiguousarray(faces, np.uint32)
+    nrm = None if nrm is None else np.ascontiguousarray(nrm, np.float32)
+    uv = None if uv is None else np.ascontiguousarray(uv, np.float32)
+    nci = None if nci is None else np.ascontiguousarray(nci, np.uint32)
+    uci = None if uci is None else np.ascontiguousarray(uci, np.uint32)
+    opt = opt or options()
+    gen = None
+    if generic is not None:
+        gen, opt = _generic(generic, opt)
+        if not edgebreaker:
+            gen = gen.reshape(len(gen), -1)
+            if opt.generic_components != gen.shape[1]:
+                o2 = Options()
+                C.memmove(C.byref(o2), C.byref(opt), C.sizeof(Options))
+                o2.generic_components = gen.shape[1]
+                opt = o2
+    extra = [e if isinstance(e, Extra) else Extra(e) for e in extra]
+    arr = _extras(extra, len(pos))
+    ptr = lambda a: None if a is None else a.ctypes.data          # noqa: E731
+    out, n = C.c_void_p(), C.c_size_t()
+    rc = L.synth_encode_attributes(1 if edgebreaker else 0, ptr(pos), len(pos), ptr(faces), 0 if faces is None else len(faces),
+                                   ptr(nrm), 0 if nrm is None else len(nrm), ptr(nci), ptr(uv), 0 if uv is None else len(uv), ptr(uci),
+                                   ptr(gen), geometry, 1 if compressed else 0, arr, len(extra), C.byref(opt), C.byref(out), C.byref(n))
+    if rc:
+        raise RuntimeError(_err())
+    data = C.string_at(out, n.value)
+    L.synth_free(out)
+    return data
+
+
 def build(force=False):
     src = os.path.join(_DIR, "synth_encoder.cpp")
     deps = [src, os.path.join(_DIR, "..", "csrc", "dsa_encode_host.h")]
@@ -56,6 +132,9 @@ def lib():
                                                    C.POINTER(Options), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
         L.synth_encode_sequential.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                               C.c_int, C.POINTER(Options), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+        L.synth_encode_attributes.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                              C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(ExtraInput), C.c_uint32,
+                                              C.POINTER(Options), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
         L.synth_free.argtypes = [C.c_void_p]
         L.synth_make_mesh.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_uint32),
                                       C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -113,7 +192,10 @@ def make_mesh(kind, nx, ny, seed):
     return pos, nrm, uv, faces
 
 
-def encode_mesh(pos, faces, normals=None, uvs=None, generic=None, opt=None):
+def encode_mesh(pos, faces, normals=None, uvs=None, generic=None, opt=None, extra=None):
+    """extra: list of Extra (or arrays): more per-vertex attributes behind the built-in ones."""
+    if extra:
+        return _encode_attributes(True, pos, faces, normals, None, uvs, None, generic, 1, False, extra, opt)
     L = lib()
     pos = np.ascontiguousarray(pos, np.float32)
     faces = np.ascontiguousarray(faces, np.uint32)
@@ -134,7 +216,7 @@ def encode_mesh(pos, faces, normals=None, uvs=None, generic=None, opt=None):
     return data
 
 
-def encode_mesh_corners(pos, faces, normals=None, normal_corners=None, uvs=None, uv_corners=None, opt=None, generic=None):
+def encode_mesh_corners(pos, faces, normals=None, normal_corners=None, uvs=None, uv_corners=None, opt=None, generic=None, extra=None):
     """Mesh whose normals / texture coordinates are given per corner: `faces` [F,3] index `pos`, `normal_corners` /
     `uv_corners` [F,3] index the rows of `normals` / `uvs` (None: that attribute has one row per vertex).  Edges across
     which the ids differ become attribute seams in the stream (seam bits, attribute corner table, corner attribute).
@@ -151,6 +233,8 @@ def encode_mesh_corners(pos, faces, normals=None, normal_corners=None, uvs=None,
             raise ValueError("%s_corners needs %ss and one id per corner of `faces`" % (name, name))
         if ids is None and vals is not None and len(vals) != len(pos):
             raise ValueError("per-vertex %ss need one row per vertex" % name)
+    if extra:
+        return _encode_attributes(True, pos, faces, nrm, nci, uv, uci, generic, 1, False, extra, opt)
     out, n = C.c_void_p(), C.c_size_t()
     opt = opt or options()
     gen = None
@@ -200,7 +284,7 @@ def encode_point_cloud(pos, opt=None):
     return data
 
 
-def _sequential(pos, faces, normals, uvs, generic, geometry, compressed, opt):
+def _sequential(pos, faces, normals, uvs, generic, geometry, compressed, opt, extra=None):
     L = lib()
     pos = np.ascontiguousarray(pos, np.float32)
     faces = None if faces is None else np.ascontiguousarray(faces, np.uint32)
@@ -221,6 +305,8 @@ def _sequential(pos, faces, normals, uvs, generic, geometry, compressed, opt):
     for a, name in ((nrm, "normals"), (uv, "uvs")):
         if a is not None and len(a) != len(pos):
             raise ValueError("%s: one row per point" % name)
+    if extra:
+        return _encode_attributes(False, pos, faces, nrm, None, uv, None, gen, geometry, compressed, extra, opt)
     out, n = C.c_void_p(), C.c_size_t()
     rc = L.synth_encode_sequential(pos.ctypes.data, len(pos), None if faces is None else faces.ctypes.data,
                                    0 if faces is None else len(faces), None if nrm is None else nrm.ctypes.data,
@@ -233,17 +319,17 @@ def _sequential(pos, faces, normals, uvs, generic, geometry, compressed, opt):
     return data
 
 
-def encode_sequential(pos, faces, normals=None, uvs=None, generic=None, compressed=False, opt=None):
+def encode_sequential(pos, faces, normals=None, uvs=None, generic=None, compressed=False, opt=None, extra=None):
     """Sequential mesh stream with every per-vertex attribute (generic: (V,) or (V, 1..4) of int8 / uint8 / int16 / uint16 / int32 / uint32): faces and points keep the
     caller's order; any list of triangles over the points is legal.  compressed: indices through the symbol coder, else raw
     at the bitstream's widths.  What dsa_encode_sequential_batch must write for geometry 1."""
-    return _sequential(pos, faces, normals, uvs, generic, 1, compressed, opt)
+    return _sequential(pos, faces, normals, uvs, generic, 1, compressed, opt, extra)
 
 
-def encode_point_cloud_attributes(pos, normals=None, uvs=None, generic=None, opt=None):
+def encode_point_cloud_attributes(pos, normals=None, uvs=None, generic=None, opt=None, extra=None):
     """Sequential point cloud with per-point normals / texture coordinates / generic integer attribute; positions only:
     the bytes of encode_point_cloud.  What dsa_encode_sequential_batch must write for geometry 0."""
-    return _sequential(pos, None, normals, uvs, generic, 0, False, opt)
+    return _sequential(pos, None, normals, uvs, generic, 0, False, opt, extra)
 
 
 def make_batch(kind, nx, ny, seed0, count, normals=True, uvs=True, opt=None, threads=None):

@@ -221,6 +221,55 @@ int synth_encode_sequential(const float *pos, uint32_t nv, const uint32_t *faces
     return 0;
   } catch (const std::exception &e) { snprintf(g_err, sizeof(g_err), "%s", e.what()); return 1; }
 }
+// Any of the streams above with more per-vertex attributes behind the built-in ones (dsa_encode_host.h ExtraAttr; the layout of
+// dsa_attribute_input without its reserved words).  edgebreaker != 0: synth_encode_mesh_corners' arguments (corner id lists may
+// be NULL; geometry / compressed are not read); else synth_encode_sequential's (corner ids must be NULL).
+struct synth_extra {
+  int32_t attribute_type, data_type;
+  uint32_t num_components;
+  int32_t normalized;
+  uint32_t unique_id;
+  int32_t quantization_bits;
+  const void *values;
+};
+int synth_encode_attributes(int edgebreaker, const float *pos, uint32_t nv, const uint32_t *faces, uint32_t nf, const float *normals, uint32_t nn,
+                            const uint32_t *normal_corners, const float *uvs, uint32_t nu, const uint32_t *uv_corners, const void *generic,
+                            int geometry, int compressed, const synth_extra *extras, uint32_t num_extras, const synth_options *opt,
+                            uint8_t **out, size_t *out_len) {
+  try {
+    std::vector<synth::ExtraAttr> ex(num_extras);
+    for (uint32_t k = 0; k < num_extras; ++k) {
+      ex[k].att_type = extras[k].attribute_type; ex[k].data_type = extras[k].data_type; ex[k].nc = extras[k].num_components;
+      ex[k].normalized = extras[k].normalized; ex[k].unique_id = extras[k].unique_id; ex[k].bits = extras[k].quantization_bits;
+      ex[k].values = extras[k].values;
+    }
+    synth::MeshIn in{pos, nv, faces, nf, normals, uvs, generic};
+    in.extras = ex.data(); in.num_extras = num_extras;
+    std::vector<uint8_t> buf;
+    if (edgebreaker) {
+      in.normal_corners = normals ? normal_corners : nullptr; in.nn = nn;
+      in.uv_corners = uvs ? uv_corners : nullptr; in.nu = nu;
+      for (size_t k = 0; k < (size_t)nf * 3; ++k) {
+        synth::check(faces[k] < nv, "face index out of range");
+        synth::check(!in.normal_corners || in.normal_corners[k] < nn, "normal id out of range");
+        synth::check(!in.uv_corners || in.uv_corners[k] < nu, "texture coordinate id out of range");
+      }
+      synth::encode_mesh(in, to_opt(opt), buf);
+    } else {
+      synth::check(!normal_corners && !uv_corners, "a sequential stream has one value per point");
+      synth::check(geometry == 0 || geometry == 1, "geometry: 1 (triangular mesh) or 0 (point cloud)");
+      synth::check(geometry == 1 || nf == 0, "a point cloud has no faces");
+      synth::check(pos != nullptr && nv > 0, "positions are missing");
+      synth::check(geometry == 0 || (faces != nullptr && nf > 0), "a mesh needs faces");
+      for (size_t k = 0; k < (size_t)nf * 3; ++k) synth::check(faces[k] < nv, "face index out of range");
+      synth::encode_sequential(in, to_opt(opt), geometry == 1, compressed != 0, buf);
+    }
+    *out = (uint8_t *)malloc(buf.size() ? buf.size() : 1);
+    memcpy(*out, buf.data(), buf.size());
+    *out_len = buf.size();
+    return 0;
+  } catch (const std::exception &e) { snprintf(g_err, sizeof(g_err), "%s", e.what()); return 1; }
+}
 void synth_free(uint8_t *p) { free(p); }
 
 // Procedural mesh: returns counts; call once with NULL outputs to size, then again to fill.

@@ -320,6 +320,44 @@ void dsa_encode_sequential_default_options(dsa_encode_sequential_options *option
  * generic != NULL with generic_components outside 1..4 (DSA_ERR_INVALID_ARGUMENT).  Nothing else about a mesh is checked. */
 dsa_status dsa_encode_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes,
                                        const dsa_encode_sequential_options *options, dsa_encoded **out);
+/* The attribute list: any number of further per-vertex attributes behind the built-in ones (positions, normals, the first UV
+ * set, mesh.generic), what DracoEncoder.Encode(writer, config, pointCloud, attributes) takes -- COLOR_0, JOINTS_0 / WEIGHTS_0, a
+ * second UV set, feature ids.  Integer element types (int8 ... uint32) are coded as they are (SequentialAttributeEncoderType.
+ * Integer), float32 is quantised (Quantization); the prediction is the one mesh.generic gets: the positions' family for
+ * Edgebreaker streams, Difference for sequential ones -- never TexCoordsPortable, which stays the first UV set's.  Each extra
+ * goes into an attributes decoder by the rule that places mesh.generic (single_connectivity).  Values are read on the device in
+ * their own element type (k_enc_quantize); 32-bit values are promised within +-2^27 as int32 (the wrap transform's arithmetic is
+ * int32).  Added after ABI 4 without changing it: callers detect the feature by the symbol dsa_encode_attributes_batch. */
+#define DSA_UNIQUE_ID_DEFAULT 0xFFFFFFFFu
+typedef struct dsa_attribute_input {
+  int32_t attribute_type;     /* GeometryAttributeType: 2 colour, 3 texture coordinate, 4 generic */
+  int32_t data_type;          /* Draco DataType: 1 int8, 2 uint8, 3 int16, 4 uint16, 5 int32, 6 uint32, 9 float32 */
+  uint32_t num_components;    /* 1..4 */
+  int32_t normalized;         /* 0 / 1, written into the descriptor (integer types; a float32 attribute writes 0) */
+  uint32_t unique_id;         /* DSA_UNIQUE_ID_DEFAULT: the attribute's index in the stream */
+  int32_t quantization_bits;  /* float32 only: 1..20; 0 = texcoord_bits for attribute_type 3, else 8 */
+  const void *values;         /* num_vertices rows, packed (num_components elements of data_type each), one row per vertex / point */
+  uint32_t reserved[2];       /* must be zero */
+} dsa_attribute_input;          /* 40 bytes */
+typedef struct dsa_mesh_attr_input {
+  dsa_mesh_corner_input mesh;                 /* as for dsa_encode_batch_ex, its own `generic` included */
+  const dsa_attribute_input *attributes;      /* extras, written behind the built-in attributes in list order */
+  uint32_t num_attributes, reserved;          /* reserved: must be zero */
+} dsa_mesh_attr_input;          /* 96 bytes */
+/* dsa_encode_batch_ex (Edgebreaker) and dsa_encode_sequential_batch (sequential meshes, point clouds) for meshes with an
+ * attribute list.  With no extras the streams are the bytes of those calls; one extra {4, uint8, nc, 0, default} and no
+ * mesh.generic gives the bytes of the same data passed as mesh.generic.  Beside the failures of those calls a mesh fails alone
+ * with DSA_ERR_INVALID_ARGUMENT (the message names the attribute's index in the list and the field): built-in attributes plus
+ * extras exceed DSA_MAX_ATTRIBUTES; attribute_type, data_type, num_components, normalized or quantization_bits outside the
+ * values above; values NULL; a reserved word not zero; two attributes of the mesh with one unique id (built-in attributes have
+ * their index); the sequential call with corner ids (it has one value per point and does not drop them silently).  Integer
+ * symbols of 2^18 and above (32-bit types with spread values) are written by the tagged scheme, as the CPU coder does; with
+ * symbol_scheme = 1 forced such a mesh fails alone with DSA_ERR_INVALID_DATA -- the one place the device refuses what the CPU
+ * coder may attempt. */
+dsa_status dsa_encode_attributes_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes,
+                                       const dsa_encode_options_ex *options, dsa_encoded **out);
+dsa_status dsa_encode_attributes_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes,
+                                                  const dsa_encode_sequential_options *options, dsa_encoded **out);
 uint32_t dsa_encoded_size(const dsa_encoded *encoded);
 /* Bytes of stream `mesh` (owned by `encoded`, valid until dsa_encoded_free) or that mesh's failure status. */
 dsa_status dsa_encoded_stream(const dsa_encoded *encoded, uint32_t mesh, const uint8_t **bytes, size_t *length);
