@@ -10,6 +10,10 @@
 // Every PointAttribute beyond positions, normals, the first texture coordinates and a uint8 generic attribute -- colours, joints and
 // weights, further UV sets, feature ids -- is passed as an extra with its AttributeType, DataType, NumComponents, Normalized and
 // UniqueId (dsa_encode_attributes_batch / dsa_encode_attributes_sequential_batch); without such attributes the calls are what they were.
+// The levels above the default (dsa_encode_level_batch): an explicitly set position PredictionScheme of MultiParallelogram (2) or
+// ConstrainedMultiParallelogram (4) replaces Parallelogram by it; with SpeedLadder set, Config.Speed chooses as the reference does --
+// ConstrainedMultiParallelogram at Speed < 2 for meshes of 40 points or more, prediction-degree order at Speed 0.  Neither set: the
+// calls and their bytes are what they were.
 using System;
 using System.Collections.Generic;
 using System.IO;
@@ -22,6 +26,10 @@ namespace Draco.IO.Gpu;
 public sealed unsafe class GpuDracoEncoder : IDisposable
 {
     private IntPtr _ctx;
+
+    /// <summary>Follow the reference's speed ladder above its default level (PredictionSchemeEncoderFactory.cs:63-71,
+    /// MeshEdgeBreakerEncoder.cs:528-546) instead of writing the default level's schemes at every Speed.</summary>
+    public bool SpeedLadder { get; set; }
 
     public GpuDracoEncoder(int device = 0)
     {
@@ -129,6 +137,11 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
         if (uvScheme != unset) opt.TexcoordPrediction = uvScheme;
         if (posScheme != unset) opt.PositionPrediction = posScheme;
         bool extended = ebMethod != unset || normalScheme != unset;
+        int multi = 0, traversal = 0;
+        if (posScheme == 2 || posScheme == 4) { multi = posScheme; opt.PositionPrediction = 1; }      // (the options underneath keep the ids they take)
+        else if (SpeedLadder && posScheme == unset) multi = -1;
+        if (multi != 0 && uvScheme == multi) opt.TexcoordPrediction = 1;
+        if (SpeedLadder && config.Speed == 0) traversal = 1;
         var inputs = new DsaMeshInput[meshes.Count];
         var pins = new List<GCHandle>();
         IntPtr encoded = IntPtr.Zero;
@@ -136,7 +149,7 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
         {
             bool anyCorners = false, anyExtras = false;
             foreach (var m in meshes) { anyCorners = anyCorners || NeedsCornerForm(m); anyExtras = anyExtras || ExtraAttributes(m).Count > 0; }
-            if (anyExtras)
+            if (anyExtras || multi != 0 || traversal != 0)
             {
                 // the attribute list rides on the corner form (extras per vertex: the value of the last point of each position value)
                 var ain = new DsaMeshAttrInput[meshes.Count];
@@ -149,6 +162,16 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
                 ax.Base = opt;
                 ax.EdgebreakerMethod = ebMethod != unset ? ebMethod : 0;
                 ax.NormalPrediction = normalScheme != unset ? normalScheme : 0;
+                if (multi != 0 || traversal != 0)
+                {
+                    NativeMethods.dsa_encode_default_level_options(out var lv);
+                    lv.Ex = ax;
+                    lv.MultiParallelogram = multi;
+                    lv.TraversalMethod = traversal;
+                    fixed (DsaMeshAttrInput* p = ain)
+                        NativeMethods.Check(NativeMethods.dsa_encode_level_batch(_ctx, (uint)meshes.Count, p, in lv, out encoded), _ctx, "dsa_encode_level_batch");
+                    return Streams(encoded, meshes.Count);
+                }
                 fixed (DsaMeshAttrInput* p = ain)
                     NativeMethods.Check(NativeMethods.dsa_encode_attributes_batch(_ctx, (uint)meshes.Count, p, in ax, out encoded), _ctx, "dsa_encode_attributes_batch");
                 return Streams(encoded, meshes.Count);

@@ -79,6 +79,16 @@ internal unsafe struct DsaEncodeOptionsEx
     public fixed int Reserved[6];   // zero
 }
 
+// dsa_encode_level_options (dsa_encode_level_batch): MultiParallelogram / ConstrainedMultiParallelogram, prediction-degree order (96 bytes)
+[StructLayout(LayoutKind.Sequential)]
+internal unsafe struct DsaEncodeLevelOptions
+{
+    public DsaEncodeOptionsEx Ex;
+    public int MultiParallelogram;  // 0 off, 4 constrained, 2 plain, -1 by speed and point count (PredictionSchemeEncoderFactory.cs:63-71)
+    public int TraversalMethod;     // 0 depth first, 1 prediction degree for the positions' decoder, 2 for every decoder without seams
+    public fixed int Reserved[6];   // zero
+}
+
 // dsa_encode_sequential_options (dsa_encode_sequential_batch): sequential meshes and point clouds
 [StructLayout(LayoutKind.Sequential)]
 internal unsafe struct DsaEncodeSequentialOptions
@@ -188,6 +198,8 @@ internal static unsafe partial class NativeMethods
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_batch_ex(IntPtr ctx, uint n, DsaMeshCornerInput* meshes, in DsaEncodeOptionsEx options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern void dsa_encode_sequential_default_options(out DsaEncodeSequentialOptions options);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_sequential_batch(IntPtr ctx, uint n, DsaMeshInput* meshes, in DsaEncodeSequentialOptions options, out IntPtr encoded);
+    [DllImport(Lib)] internal static extern void dsa_encode_default_level_options(out DsaEncodeLevelOptions options);
+    [DllImport(Lib)] internal static extern DsaStatus dsa_encode_level_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, in DsaEncodeLevelOptions options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_attributes_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, in DsaEncodeOptionsEx options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_attributes_sequential_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, in DsaEncodeSequentialOptions options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern uint dsa_encoded_size(IntPtr encoded);

@@ -31,6 +31,7 @@
 #include "dsa_encode_conn.h"
 #include "dsa_encode_seams.h"
 #include "dsa_encode_schemes.h"
+#include "dsa_encode_multi.h"
 
 namespace dsa {
 
@@ -61,6 +62,11 @@ struct EncStream {                 // one per (mesh, attribute); lives in device
   uint64_t flags;                  // u32[(cap + 31) / 32] side bits, bit k of the list: orientations (delta-coded against true, last
                                    //   entry first; k_enc_orient) or flips (entry order; k_enc_corr) -- -> download (write_rabs)
   uint32_t t_nc3, num_flags;       // 3F; OUTPUT: bits in `flags`
+  // prediction 2 / 4 (MultiParallelogram, ConstrainedMultiParallelogram; kind 0 and 2; dsa_encode_multi.h): the topology view above;
+  // prediction 4: `ori` holds per entry the parallelograms found and their crease flags (k_enc_multi -> k_enc_crease), `flags` the
+  // four crease lists, list j packed from word cr_at[j] on, cr_n[j] bits (OUTPUT) -- k_enc_crease -> download (write_rabs)
+  uint32_t cr_at[4], cr_n[4];
+  uint32_t pd_want, pad_level;     // pd_want: an attribute given per corner whose decoder takes the prediction-degree order unless it is seamed
   uint32_t linear, elem;           // linear: entry i is value row i (sequential streams, dsa_encode_sequential.h): `d` is `vals`, no e2v, no gather
                                    // elem (kind 2): Draco's data type of `src`, 1 int8, 2 uint8, 3 int16, 4 uint16, 5 int32, 6 uint32
 };
@@ -69,6 +75,7 @@ struct EncStream {                 // one per (mesh, attribute); lives in device
 // histogram of values beyond): no stream's histogram is larger than this, and a stream whose histogram has this size may hold
 // symbols beyond it (32-bit integer attributes with spread values) -- those are not counted, and k_enc_plan goes the tagged way.
 static const uint32_t ENC_RAW_SYMBOL_LIMIT = 1u << 18, ENC_HIST_CAP_LIMIT = ENC_RAW_SYMBOL_LIMIT + 2u;
+static_assert(ENC_HIST_CAP_LIMIT == EM_HIST_CAP_LIMIT, "k_enc_multi counts symbols like k_enc_corr");
 static const int ENC_PLAN_RAW_BEYOND_LIMIT = 1000;      // plan_status beside dsa::plan::PLAN_*: see enc_plan_message
 static const char *const ENC_RAW_BEYOND_MESSAGE = "symbol_scheme 1 (raw) forced on an integer attribute with symbols of 2^18 and above: the device coder writes those tagged only";
 // hist_cap of an integer attribute whose values (as int32) span lo .. hi: zig-zagged wrapped corrections lie in 0 .. hi - lo + 1
@@ -206,6 +213,7 @@ __global__ __launch_bounds__(256) void k_enc_corr(uint8_t *arena, EncStream *str
   if (si >= ns) return;
   EncStream &S = streams[si];
   if (S.kind == 3) return;                      // (a valence context list: k_enc_list_stats)
+  if (S.kind != 1 && (S.prediction == 2 || S.prediction == 4)) return;      // (MultiParallelogram: k_enc_multi)
   __shared__ uint32_t s_tag[33];
   __shared__ uint32_t s_max;
   __shared__ unsigned long long s_bl;
@@ -690,7 +698,8 @@ static void enc_device_plan_errors(const std::vector<dsa::EncStream> &hs, const 
 // front of the payload.
 static dsa_status enc_code_streams(dsa_context *ctx, EncLane &lane, uint8_t *arena, dsa::EncStream *d_streams, std::vector<dsa::EncStream> &hs, const std::vector<int> &stream_mesh,
                                    const dsa_encoded *E, bool host_plan, std::vector<synth::SymbolPlan> &splans, std::vector<std::vector<uint8_t>> &rans,
-                                   std::vector<std::vector<uint8_t>> &bits, std::vector<std::vector<uint8_t>> &flag_bits) {
+                                   std::vector<std::vector<uint8_t>> &bits, std::vector<std::vector<uint8_t>> &flag_bits,
+                                   std::vector<std::vector<uint8_t>> *crease = nullptr) {
   const uint32_t ns = (uint32_t)hs.size();
   auto gather = [&](std::vector<dsa::PackItem> &items, std::vector<uint8_t> &host, const uint8_t **view) { return enc_gather(lane, arena, items, host, view); };
   hipStream_t st = lane.st;
@@ -709,7 +718,8 @@ static dsa_status enc_code_streams(dsa_context *ctx, EncLane &lane, uint8_t *are
     items.push_back({hs[s].out_rans, 0, hs[s].rans_len, s});
     items.push_back({hs[s].out_bits, 0, hs[s].bits_len, s});
     items.push_back({hs[s].prob, 0, host_plan ? 0u : 4u * hs[s].num_symbols, s});
-    items.push_back({hs[s].flags, 0, hs[s].flags ? 4u * ((hs[s].num_flags + 31u) / 32u) : 0u, s});
+    const bool creased = hs[s].kind != 1 && hs[s].prediction == 4;      // (its `flags` hold the four crease lists: below)
+    items.push_back({hs[s].flags, 0, hs[s].flags && !creased ? 4u * ((hs[s].num_flags + 31u) / 32u) : 0u, s});
   }
   std::vector<uint8_t> unused;
   const uint8_t *host = nullptr;
@@ -719,7 +729,7 @@ static dsa_status enc_code_streams(dsa_context *ctx, EncLane &lane, uint8_t *are
     const uint32_t s = items[k].pad;
     if (items[k].len) rans[s].assign(host + items[k].packed_off, host + items[k].packed_off + items[k].len);
     if (items[k + 1].len) bits[s].assign(host + items[k + 1].packed_off, host + items[k + 1].packed_off + items[k + 1].len);
-    if (hs[s].flags) {
+    if (hs[s].flags && !(hs[s].kind != 1 && hs[s].prediction == 4)) {
       const uint32_t *words = (const uint32_t *)(host + items[k + 3].packed_off);
       flag_bits[s].resize(hs[s].num_flags);
       for (uint32_t e = 0; e < hs[s].num_flags; ++e) flag_bits[s][e] = (uint8_t)((words[e >> 5] >> (e & 31u)) & 1u);
@@ -736,6 +746,26 @@ static dsa_status enc_code_streams(dsa_context *ctx, EncLane &lane, uint8_t *are
       pl.coder.write_table(pl.head);
     }
   }, 8);
+  // the crease lists of ConstrainedMultiParallelogram streams ((*crease)[4 s + j]: list j of stream s, a byte per flag): a
+  // transfer of their own, made only when the chunk has such streams
+  if (crease) {
+    std::vector<dsa::PackItem> citems;
+    for (uint32_t s = 0; s < ns; ++s) {
+      if (hs[s].overflow || E->status[stream_mesh[s]] != DSA_OK || hs[s].kind == 1 || hs[s].prediction != 4 || !hs[s].flags) continue;
+      for (uint32_t j = 0; j < 4; ++j) citems.push_back({hs[s].flags + 4ull * hs[s].cr_at[j], 0, 4u * ((hs[s].cr_n[j] + 31u) / 32u), 4u * s + j});
+    }
+    std::vector<uint8_t> unused2;
+    const uint8_t *chost = nullptr;
+    ENC_ST(gather(citems, unused2, &chost));
+    hostutil::parallel_for((uint32_t)citems.size(), [&](uint32_t m) {
+      const dsa::PackItem &it = citems[m];
+      const uint32_t cnt = hs[it.pad / 4u].cr_n[it.pad & 3u];
+      std::vector<uint8_t> &b = (*crease)[it.pad];
+      b.resize(cnt);
+      const uint32_t *words = (const uint32_t *)(chost + it.packed_off);
+      for (uint32_t e = 0; e < cnt; ++e) b[e] = (uint8_t)((words[e >> 5] >> (e & 31u)) & 1u);
+    }, 8);
+  }
   return DSA_OK;
 }
 // a symbol stream as encode_symbols writes it: scheme and table, coded bytes, (tagged) the raw bit fields
@@ -764,9 +794,10 @@ void dsa_encode_default_options_ex(dsa_encode_options_ex *o) {
 
 // All entry points share one chunk path: `meshes` (dsa_encode_batch) or `corners` (dsa_encode_batch_corners / _ex), the other
 // null; `ex` (dsa_encode_batch_ex) the schemes beyond standard Edgebreaker + difference / parallelogram, else null.
-// `attrs` (dsa_encode_attributes_batch): meshes with an attribute list, both others null.
-static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint32_t batch_n, const dsa_mesh_input *meshes, const dsa_mesh_corner_input *corners, const dsa_mesh_attr_input *attrs, const dsa_encode_options *options, const dsa_encode_options_ex *ex, dsa_encoded **out);
-static dsa_status encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_mesh_corner_input *corners, const dsa_mesh_attr_input *attrs, const dsa_encode_options *options, const dsa_encode_options_ex *ex, dsa_encoded **out);
+// `attrs` (dsa_encode_attributes_batch, dsa_encode_level_batch): meshes with an attribute list, both others null.
+// multi_parallelogram / traversal_method: the two options of dsa_encode_level_options, 0 from every other entry point.
+static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint32_t batch_n, const dsa_mesh_input *meshes, const dsa_mesh_corner_input *corners, const dsa_mesh_attr_input *attrs, const dsa_encode_options *options, const dsa_encode_options_ex *ex, dsa_encoded **out, int32_t multi_parallelogram = 0, int32_t traversal_method = 0);
+static dsa_status encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_mesh_corner_input *corners, const dsa_mesh_attr_input *attrs, const dsa_encode_options *options, const dsa_encode_options_ex *ex, dsa_encoded **out, int32_t multi_parallelogram = 0, int32_t traversal_method = 0);
 // The prediction methods the device coder writes; any other value would put a method byte in front of data it does not describe.
 static dsa_status check_schemes(dsa_context *ctx, const dsa_encode_options *o, const dsa_encode_options_ex *ex) {
   if (o && o->position_prediction != 0 && o->position_prediction != 1)
@@ -807,6 +838,27 @@ dsa_status dsa_encode_attributes_batch(dsa_context *ctx, uint32_t n, const dsa_m
   if (options) d = *options;
   if (check_schemes(ctx, &d.base, &d) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
   DSA_GUARD(ctx, encode_batch(ctx, n, nullptr, nullptr, meshes, &d.base, &d, out));
+}
+void dsa_encode_default_level_options(dsa_encode_level_options *o) {
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  dsa_encode_default_options_ex(&o->ex);
+}
+// The levels above the default: MultiParallelogram / ConstrainedMultiParallelogram in place of Parallelogram, prediction-degree
+// attribute order (dsa_encode_multi.h).  With both at 0 this is dsa_encode_attributes_batch.
+dsa_status dsa_encode_level_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_encode_level_options *options, dsa_encoded **out) {
+  if (!ctx || !out || (n && !meshes)) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "null argument");
+  dsa_encode_level_options d;
+  dsa_encode_default_level_options(&d);
+  if (options) d = *options;
+  if (check_schemes(ctx, &d.ex.base, &d.ex) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+  if (d.multi_parallelogram != 0 && d.multi_parallelogram != 2 && d.multi_parallelogram != 4 && d.multi_parallelogram != -1)
+    return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "multi_parallelogram %d: 0 (off), 2 (MultiParallelogram), 4 (ConstrainedMultiParallelogram) or -1 (by speed and vertex count)", (int)d.multi_parallelogram);
+  if (d.traversal_method != 0 && d.traversal_method != 1 && d.traversal_method != 2)
+    return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "traversal_method %d: 0 (depth first), 1 (prediction degree for the positions' decoder) or 2 (for every decoder without interior seams)", (int)d.traversal_method);
+  for (int k = 0; k < 6; ++k)
+    if (d.reserved[k] != 0) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "dsa_encode_level_options.reserved[%d] is not zero", k);
+  DSA_GUARD(ctx, encode_batch(ctx, n, nullptr, nullptr, meshes, &d.ex.base, &d.ex, out, d.multi_parallelogram, d.traversal_method));
 }
 // A batch is coded in chunks, several of them in flight (each on a lane of its own: stream + pinned staging + device memory).  The
 // device stages of a chunk are bound by latency -- the walks of k_enc_connectivity take a memory round trip per step, 0.1 - 0.2 s
@@ -890,9 +942,9 @@ static dsa_status encode_batch_chunks(dsa_context *ctx, uint32_t n, ChunkFn &&co
   return DSA_OK;
 }
 }  // extern "C++"
-static dsa_status encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_mesh_corner_input *corners, const dsa_mesh_attr_input *attrs, const dsa_encode_options *options, const dsa_encode_options_ex *ex, dsa_encoded **out) {
+static dsa_status encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_mesh_corner_input *corners, const dsa_mesh_attr_input *attrs, const dsa_encode_options *options, const dsa_encode_options_ex *ex, dsa_encoded **out, int32_t multi_parallelogram, int32_t traversal_method) {
   return encode_batch_chunks(ctx, n, [&](dsa_context *sink, EncLane &lane, uint32_t base, uint32_t cnt, dsa_encoded **part) {
-    return encode_chunk(sink, lane, cnt, n, meshes ? meshes + base : nullptr, corners ? corners + base : nullptr, attrs ? attrs + base : nullptr, options, ex, part);
+    return encode_chunk(sink, lane, cnt, n, meshes ? meshes + base : nullptr, corners ? corners + base : nullptr, attrs ? attrs + base : nullptr, options, ex, part, multi_parallelogram, traversal_method);
   }, out);
 }
 // The extras of a mesh with an attribute list as the host coder takes them (`ex` keeps them alive beside `in`); what the C structs
@@ -923,7 +975,7 @@ static uint32_t enc_extra_hist_cap(const synth::PortableAttr &a, uint32_t rows) 
   else { const int32_t *p = (const int32_t *)a.extra_values; lo = hi = p[0]; for (size_t k = 1; k < total; ++k) { lo = p[k] < lo ? p[k] : lo; hi = p[k] > hi ? p[k] : hi; } }     // (uint32 by reinterpretation)
   return dsa::enc_integer_hist_cap(lo, hi);
 }
-static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint32_t batch_n, const dsa_mesh_input *meshes_v, const dsa_mesh_corner_input *corners_v, const dsa_mesh_attr_input *attrs, const dsa_encode_options *options, const dsa_encode_options_ex *ex, dsa_encoded **out) {
+static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint32_t batch_n, const dsa_mesh_input *meshes_v, const dsa_mesh_corner_input *corners_v, const dsa_mesh_attr_input *attrs, const dsa_encode_options *options, const dsa_encode_options_ex *ex, dsa_encoded **out, int32_t multi_parallelogram, int32_t traversal_method) {
   // mesh i of the chunk, whichever entry point it came through (corner(i): its corner form, null for dsa_encode_batch)
   struct MeshRef {
     const dsa_mesh_input *v; const dsa_mesh_corner_input *c; const dsa_mesh_attr_input *a;
@@ -945,6 +997,13 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
   opt.single_connectivity = od.single_connectivity; opt.force_scheme = od.symbol_scheme; opt.compression_level = od.compression_level;
   opt.pos_prediction = od.position_prediction; opt.uv_prediction = od.texcoord_prediction;
   opt.normal_prediction = ex ? ex->normal_prediction : 0;
+  opt.traversal_method = traversal_method;
+  // MultiParallelogram per mesh: the method asked for, or by the reference's rule (speed < 2 and at least 40 points)
+  auto multi_of = [&](uint32_t i) -> int32_t {
+    return multi_parallelogram == -1 ? ((opt.compression_level >= 9 && meshes[i].num_vertices >= 40) ? 4 : 0) : multi_parallelogram;
+  };
+  // the prediction-degree order beside the depth-first one: every mesh of the chunk (the positions' decoder takes it at least)
+  const bool want_pd = traversal_method != 0;
   // valence symbols per mesh: asked for, or by the reference's rule (speed < 5 and not a tiny mesh)
   const int32_t eb_method = ex ? ex->edgebreaker_method : 0;
   auto valence_of = [&](uint32_t i) { return eb_method == 2 || (eb_method == -1 && opt.compression_level > 5 && meshes[i].num_faces >= 1000); };
@@ -961,12 +1020,15 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
   std::vector<synth::MeshIn> ins(n);
   std::vector<std::vector<uint32_t>> e2v(n);
   std::vector<std::vector<int32_t>> ops(n);
+  std::vector<std::vector<uint32_t>> e2v_pd(want_pd ? n : 0);         // the same in prediction-degree order (host connectivity)
+  std::vector<std::vector<int32_t>> ops_pd(want_pd ? n : 0);
   // attributes given per corner, host connectivity: per attribute its own entry -> value row, and its own operands when it is seamed
   std::vector<std::vector<std::vector<uint32_t>>> att_e2v(n);
   std::vector<std::vector<std::vector<int32_t>>> att_ops(n);
   std::vector<std::vector<std::vector<uint32_t>>> att_opp(n);       // the same, prediction 5 / 6 of a seamed attribute: its table's opposites
   // attribute k of plan `pl` reads the mesh's topology (TexCoordsPortable, GeometricNormal)
-  auto topo_scheme = [](const synth::PortableAttr &a) { return (a.seq_type == 2 && a.prediction == 5) || (a.seq_type == 3 && a.prediction == 6); };
+  auto multi_scheme = [](const synth::PortableAttr &a) { return a.seq_type != 3 && (a.prediction == 2 || a.prediction == 4); };
+  auto topo_scheme = [&](const synth::PortableAttr &a) { return (a.seq_type == 2 && a.prediction == 5) || (a.seq_type == 3 && a.prediction == 6) || multi_scheme(a); };
   // DSA_ENC_TIMING=1 (diagnostics): wall time of every phase on stderr
   static const bool timing = getenv("DSA_ENC_TIMING") != nullptr;
   auto t_last = std::chrono::steady_clock::now();
@@ -1017,6 +1079,10 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
       synth::Options mo = opt;                                   // (the components of the generic attribute are the mesh's own)
       mo.generic_components = in.generic ? (int32_t)m.generic_components : 1;
       mo.predictive_connectivity = valence_of(i) ? 2 : 0;
+      if (const int32_t mp = multi_of(i)) {                      // in place of Parallelogram (plan_attributes: the generic attribute and the extras follow the positions to method 4)
+        if (opt.pos_prediction == 1) mo.pos_prediction = mp;
+        if (opt.uv_prediction == 1) mo.uv_prediction = mp;
+      }
       if (!host_conn) {                                          // the rest of the plan comes from the device
         synth::check(!((in.normal_corners || in.uv_corners) && opt.single_connectivity), "attributes given per corner need a connectivity of their own (single_connectivity = 0)");
         synth::check(!(in.normal_corners || in.uv_corners) || 24ull * m.num_faces + 16u < (1ull << 32), "mesh too large for the device connectivity coder");
@@ -1028,12 +1094,13 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
       extra_caps();
       const synth::MeshPlan &pl = plans[i];
       dsa::entry_maps(pl.ct, pl.seq, nullptr, e2v[i], &ops[i]);
+      if (want_pd) dsa::entry_maps(pl.ct, pl.seq_pd, nullptr, e2v_pd[i], &ops_pd[i]);
       att_e2v[i].assign(pl.atts.size(), {}); att_ops[i].assign(pl.atts.size(), {});
       for (size_t k = 1; k < pl.atts.size(); ++k) {
         const uint32_t *ids = pl.atts[k].corner_value;
         if (!ids) continue;
         if (pl.seamed(k)) dsa::entry_maps(pl.conns[k], pl.seq_att[k], ids, att_e2v[i][k], &att_ops[i][k]);
-        else dsa::entry_maps(pl.ct, pl.seq, ids, att_e2v[i][k], nullptr);      // (the positions' operands)
+        else dsa::entry_maps(pl.ct, pl.uses_pd(k) ? pl.seq_pd : pl.seq, ids, att_e2v[i][k], nullptr);      // (the positions' operands)
       }
       att_opp[i].assign(pl.atts.size(), {});
       for (size_t k = 1; k < pl.atts.size(); ++k) {
@@ -1051,6 +1118,7 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
   std::vector<dsa::EncConn> hc(host_conn ? 0 : n);
   std::vector<dsa::EncSeam> hz;                   // device connectivity: one per (mesh, attribute given per corner)
   std::vector<uint32_t> first_stream(n + 1, 0);
+  bool any_multi = false, any_crease = false;      // streams of the chunk predicted by method 2 / 4; by method 4
   // value rows of attribute k of mesh i: its ids' row count when it is given per corner
   auto rows_of = [&](uint32_t i, const synth::PortableAttr &a) -> uint32_t {
     if (!a.corner_value) return meshes[i].num_vertices;
@@ -1082,6 +1150,7 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
         in_total += 2 * al(4 * pl.conns[k].c2v.size()) + 2 * al(4 * pl.seq_att[k].data_to_corner.size());
     }
     if (needs_topo) in_total += 2 * al(4 * pl.ct.c2v.size()) + 2 * al(4 * pl.seq.data_to_corner.size());
+    if (want_pd) in_total += al(4 * V) + al(12 * V) + 2 * al(4 * V);          // the second order: entry maps, and its topology view
     if (pl.valence) for (int k = 0; k < 6; ++k) in_total += al(4 * pl.ctx_symbols[k].size());
   }
   uint64_t cur = in_total, cur_in = 0;
@@ -1115,9 +1184,12 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
     if (E->status[i] != DSA_OK) continue;
     const uint32_t V = meshes[i].num_vertices;
     const uint64_t o_e2v = host_conn ? take_in(4ull * V) : take(4ull * V), o_ops = host_conn ? take_in(12ull * V) : take(12ull * V);
+    uint64_t o_e2v_pd = 0, o_ops_pd = 0;
+    if (want_pd) { o_e2v_pd = host_conn ? take_in(4ull * V) : take(4ull * V); o_ops_pd = host_conn ? take_in(12ull * V) : take(12ull * V); }
     if (host_conn) {
       uploads.push_back({o_e2v, e2v[i].data(), 4ull * V, false});
       uploads.push_back({o_ops, ops[i].data(), 12ull * V, false});
+      if (want_pd) { uploads.push_back({o_e2v_pd, e2v_pd[i].data(), 4ull * V, false}); uploads.push_back({o_ops_pd, ops_pd[i].data(), 12ull * V, false}); }
     } else {
       const uint32_t F = meshes[i].num_faces;
       dsa::EncConn &C = hc[i];
@@ -1130,6 +1202,10 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
       C.symbols = take(F); C.start_bits = take(F); C.splits = take(12ull * C.split_cap);
       C.d2c = take(4ull * V); C.v2d = take(4ull * V);
       C.e2v = o_e2v; C.ops = o_ops;
+      if (want_pd) {
+        C.pd_d2c = take(4ull * V); C.pd_v2d = take(4ull * V); C.pd_e2v = o_e2v_pd; C.pd_ops = o_ops_pd;
+        C.pd_next = take(12ull * F); C.pd_degree = take(4ull * V); C.pd_fvis = take(F);
+      }
       C.vstream = DSA_INVALID;
       if (valence_of(i)) {
         C.init_time = take(4ull * F); C.vtime = take(4ull * F); C.vval = take(4ull * ((uint64_t)V + F)); C.vc2v = take(12ull * F);
@@ -1137,7 +1213,7 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
       }
     }
     // TexCoordsPortable / GeometricNormal: the position table and order (device: the connectivity's; host: uploaded once per mesh)
-    uint64_t t_c2v = 0, t_opp = 0, t_d2c = 0, t_v2d = 0;
+    uint64_t t_c2v = 0, t_opp = 0, t_d2c = 0, t_v2d = 0, t_d2c_pd = 0, t_v2d_pd = 0;
     bool needs_topo = false;
     for (const synth::PortableAttr &a : plans[i].atts) needs_topo = needs_topo || topo_scheme(a);
     if (needs_topo && host_conn) {
@@ -1146,7 +1222,11 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
       t_opp = take_in(4ull * pl.ct.opp.size()); uploads.push_back({t_opp, pl.ct.opp.data(), 4ull * pl.ct.opp.size(), false});
       t_d2c = take_in(4ull * pl.seq.data_to_corner.size()); uploads.push_back({t_d2c, pl.seq.data_to_corner.data(), 4ull * pl.seq.data_to_corner.size(), false});
       t_v2d = take_in(4ull * pl.seq.vertex_to_data.size()); uploads.push_back({t_v2d, pl.seq.vertex_to_data.data(), 4ull * pl.seq.vertex_to_data.size(), false});
-    } else if (needs_topo) { t_c2v = hc[i].faces; t_opp = hc[i].opp; t_d2c = hc[i].d2c; t_v2d = hc[i].v2d; }
+      if (want_pd) {
+        t_d2c_pd = take_in(4ull * pl.seq_pd.data_to_corner.size()); uploads.push_back({t_d2c_pd, pl.seq_pd.data_to_corner.data(), 4ull * pl.seq_pd.data_to_corner.size(), false});
+        t_v2d_pd = take_in(4ull * pl.seq_pd.vertex_to_data.size()); uploads.push_back({t_v2d_pd, pl.seq_pd.vertex_to_data.data(), 4ull * pl.seq_pd.vertex_to_data.size(), false});
+      }
+    } else if (needs_topo) { t_c2v = hc[i].faces; t_opp = hc[i].opp; t_d2c = hc[i].d2c; t_v2d = hc[i].v2d; t_d2c_pd = hc[i].pd_d2c; t_v2d_pd = hc[i].pd_v2d; }
     for (size_t k = 0; k < plans[i].atts.size(); ++k) {
       const synth::PortableAttr &a = plans[i].atts[k];
       dsa::EncStream S;
@@ -1158,7 +1238,10 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
       // most, k_enc_seam_operands sets the count)
       const uint32_t rows = rows_of(i, a);
       uint32_t entries = V, cap = V;
-      S.e2v = o_e2v; S.ops = o_ops;
+      // the decoder of attribute k takes the prediction-degree order (MeshPlan::uses_pd; for an attribute given per corner on the
+      // device path: unless it turns out seamed -- k_enc_pd_corner_streams, k_enc_seam_topo)
+      const bool pd = want_pd && (host_conn ? plans[i].uses_pd(k) : (traversal_method == 2 || opt.single_connectivity != 0 || k == 0));
+      S.e2v = pd ? o_e2v_pd : o_e2v; S.ops = pd ? o_ops_pd : o_ops;
       if (a.corner_value && host_conn) {
         entries = cap = (uint32_t)att_e2v[i][k].size();
         S.e2v = take_in(4ull * entries);
@@ -1175,6 +1258,7 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
         Z.stack = take(4ull * F); Z.d2c = take(12ull * F); Z.v2d = take(12ull * F); Z.e2v = take(12ull * F); Z.ops = take(36ull * F);
         Z.rank = take(4ull * F); Z.rcorner = take(4ull * F); Z.eoff = take(4ull * (F + 1)); Z.bits = take(4ull * ((3ull * F + 31) / 32));
         S.e2v = Z.e2v; S.ops = Z.ops;
+        S.pd_want = pd ? 1u : 0u;
         hz.push_back(Z);
       }
       S.nv = entries; S.rows = rows; S.nc_out = (uint32_t)a.nc_out; S.nc = (uint32_t)a.nc; S.kind = a.seq_type == 3 ? 1u : (integer ? 2u : 0u);
@@ -1194,8 +1278,9 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
       S.prob = take(4ull * table_cap); S.cum = take(4ull * table_cap);
       S.plan_order = take(4ull * table_cap); S.plan_tmp = take(4ull * table_cap);
       if (topo_scheme(a)) {
-        S.pos_vals = hs[first_stream[i]].vals;                  // (the positions are attribute 0: their stream is the mesh's first)
-        S.t_c2p = S.t_c2a = t_c2v; S.t_opp = t_opp; S.t_d2c = t_d2c; S.t_v2d = t_v2d;
+        const bool multi = multi_scheme(a);
+        if (!multi) S.pos_vals = hs[first_stream[i]].vals;      // (the positions are attribute 0: their stream is the mesh's first)
+        S.t_c2p = S.t_c2a = t_c2v; S.t_opp = t_opp; S.t_d2c = pd ? t_d2c_pd : t_d2c; S.t_v2d = pd ? t_v2d_pd : t_v2d;
         S.t_nc3 = 3u * meshes[i].num_faces;
         if (host_conn && a.corner_value && plans[i].seamed(k)) {             // a seamed attribute's own table and order
           const synth::MeshPlan &pl = plans[i];
@@ -1206,8 +1291,17 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
           S.t_d2c = take_in(4ull * d2c.size()); uploads.push_back({S.t_d2c, d2c.data(), 4ull * d2c.size(), false});
           S.t_v2d = take_in(4ull * v2d.size()); uploads.push_back({S.t_v2d, v2d.data(), 4ull * v2d.size(), false});
         }
-        if (a.seq_type == 2) S.ori = take(cap);
-        S.flags = take(4ull * ((cap + 31) / 32));
+        if (multi) {
+          any_multi = true;
+          if (a.prediction == 4) {                               // found + crease flags per entry; the four crease lists
+            any_crease = true;
+            S.ori = take(cap);
+            S.flags = take(4ull * dsa::em_crease_words(cap, S.cr_at));
+          }
+        } else {
+          if (a.seq_type == 2) S.ori = take(cap);
+          S.flags = take(4ull * ((cap + 31) / 32));
+        }
       }
       hs.push_back(S);
     }
@@ -1275,6 +1369,7 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
       ENC_TRY(hipEventRecord(lane.tables_done, st));
       ENC_TRY(hipStreamWaitEvent(lane.walk_st, lane.tables_done, 0));
       hipLaunchKernelGGL(any_valence ? dsa::k_enc_connectivity_timed : dsa::k_enc_connectivity, dim3((n + walk_lanes - 1) / walk_lanes), dim3(WAVE), 0, lane.walk_st, arena, d_conns, n, walk_lanes);
+      if (want_pd) hipLaunchKernelGGL(dsa::k_enc_pd_walk, dim3((n + walk_lanes - 1) / walk_lanes), dim3(WAVE), 0, lane.walk_st, arena, d_conns, n, walk_lanes);
       if (nz) {
         // attributes given per corner: seams and attribute vertices beside the connectivity walk, the attribute walks behind it
         ENC_TRY(lane.seams.ensure(sizeof(dsa::EncSeam) * nz));
@@ -1305,9 +1400,11 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
       hipLaunchKernelGGL(dsa::k_enc_quantize, dim3(gx, ns), dim3(256), 0, st, arena, d_streams, ns);
       ENC_TRY(hipStreamWaitEvent(st, lane.walk_done, 0));
       hipLaunchKernelGGL(dsa::k_enc_operands, gt, dim3(256), 0, st, arena, d_conns, n);
+      if (want_pd) hipLaunchKernelGGL(dsa::k_enc_pd_operands, gt, dim3(256), 0, st, arena, d_conns, n);
       if (nz) {
         const dim3 gz(gt.x, nz);
         hipLaunchKernelGGL(dsa::k_enc_seam_operands<dsa::EncStream>, gz, dim3(256), 0, st, arena, d_conns, d_seams, nz, d_streams);
+        if (want_pd) hipLaunchKernelGGL(dsa::k_enc_pd_corner_streams<dsa::EncStream>, gz, dim3(256), 0, st, arena, d_conns, d_seams, nz, d_streams);
         hipLaunchKernelGGL(dsa::k_enc_seam_topo<dsa::EncStream>, dim3((nz + 255) / 256), dim3(256), 0, st, d_conns, d_seams, nz, d_streams);
         hipLaunchKernelGGL(dsa::k_enc_seam_rank, gz, dim3(256), 0, st, arena, d_conns, d_seams, nz);
         hipLaunchKernelGGL(dsa::k_enc_seam_count, gz, dim3(256), 0, st, arena, d_conns, d_seams, nz);
@@ -1321,6 +1418,8 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
     // ---- device phase 1: quantise, order, correct, count
     hipLaunchKernelGGL(dsa::k_enc_gather, dim3(ns), dim3(256), 0, st, arena, d_streams, ns);
     hipLaunchKernelGGL(dsa::k_enc_corr, dim3(gx, ns), dim3(256), 0, st, arena, d_streams, ns);
+    if (any_multi) hipLaunchKernelGGL(dsa::k_enc_multi<dsa::EncStream>, dim3(gx, ns), dim3(256), 0, st, arena, d_streams, ns);
+    if (any_crease) hipLaunchKernelGGL(dsa::k_enc_crease<dsa::EncStream>, dim3(ns), dim3(WAVE), 0, st, arena, d_streams, ns);
     hipLaunchKernelGGL(dsa::k_enc_orient, dim3(ns), dim3(WAVE), 0, st, arena, d_streams, ns);
     hipLaunchKernelGGL(dsa::k_enc_list_stats, dim3(ns), dim3(256), 0, st, arena, d_streams, ns);
     if (!host_plan) {       // device phase 2 follows at once: tables by k_enc_plan, no host round trip
@@ -1402,8 +1501,8 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
   else enc_device_plan_errors(hs, stream_mesh, E);
   lap("histograms + symbol plans");
   // ---- device phase 2: entropy coding
-  std::vector<std::vector<uint8_t>> rans(ns), bits(ns), flag_bits(ns);
-  if (ns) { const dsa_status cs = enc_code_streams(ctx, lane, arena, d_streams, hs, stream_mesh, E, host_plan, splans, rans, bits, flag_bits); if (cs != DSA_OK) return cs; }
+  std::vector<std::vector<uint8_t>> rans(ns), bits(ns), flag_bits(ns), crease(any_crease ? 4 * (size_t)ns : 0);
+  if (ns) { const dsa_status cs = enc_code_streams(ctx, lane, arena, d_streams, hs, stream_mesh, E, host_plan, splans, rans, bits, flag_bits, any_crease ? &crease : nullptr); if (cs != DSA_OK) return cs; }
   lap("device phase 2 + downloads");
   cleanup();
   // ---- host phase 3: stream layout (threads over meshes; write_stream may throw like any part of the host coder)
@@ -1436,6 +1535,8 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint
         bw.u8(1);
         coded(bw, s0 + (uint32_t)k);
         if (portable) { bw.i32((int32_t)flag_bits[s0 + k].size()); synth::write_rabs(bw, flag_bits[s0 + k]); }
+        if (S.kind != 1 && S.prediction == 4)                  // ...ConstrainedMultiParallelogramEncoder.cs: the four crease lists
+          for (size_t j = 0; j < 4; ++j) { const std::vector<uint8_t> &cl = crease[4 * (s0 + k) + j]; bw.varint(cl.size()); if (!cl.empty()) synth::write_rabs(bw, cl); }
         if (S.kind == 1) { const int32_t max_q = (1 << S.bits) - 1; bw.i32(max_q); bw.i32((max_q - 1) / 2); }
         else { bw.i32(S.wrap_mn); bw.i32(S.wrap_mx); }
         if (geometric) synth::write_rabs(bw, flag_bits[s0 + k]);

@@ -40,6 +40,11 @@ struct EncConn {                   // one per mesh; device memory, mirrored on t
   uint64_t init_time, vtime, vval, vc2v, vctx, vsyms, vbl, vrans, vbits;
   uint32_t vstream;
   uint32_t vcount[6];              // OUTPUT of k_enc_valence: symbols per context
+  // prediction-degree order (dsa_encode_multi.h), all 0 for a mesh whose decoders take the depth-first order alone:
+  //   pd_d2c, pd_v2d  u32[V], i32[V]  the second order                       k_enc_pd_walk -> k_enc_pd_operands, k_enc_multi / k_enc_corr (topology view)
+  //   pd_e2v, pd_ops  u32[V], i32[3V] entry -> vertex, operand entries       k_enc_pd_operands -> k_enc_gather / k_enc_corr
+  //   pd_next, pd_degree, pd_fvis  u32[3F], u32[V], u8[F]  stack links, degree counters, face marks   k_enc_pd_walk only
+  uint64_t pd_d2c, pd_v2d, pd_e2v, pd_ops, pd_next, pd_degree, pd_fvis;
 };
 // A face as the walks see it: the vertices at its corners, the corners across its edges (o[k] = opposite of corner 3f + k), and two
 // marks -- mark: 0 not visited by the Edgebreaker walk; 1 visited; s + 2 visited, and the S with symbol id s was coded at it (what

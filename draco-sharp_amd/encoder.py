@@ -26,22 +26,32 @@ class Config:
     encoding_method (Constants.cs EncodingMethod): 1 Edgebreaker (default), 0 sequential -- faces as point indices, points and
     faces in the caller's order, any list of triangles legal -- or -1 the reference's rule (DracoEncoder.cs:43-57: sequential
     exactly when speed == 10).  compress_connectivity (ConfigOptionName.CompressConnectivity) chooses compressed over raw indices
-    of a sequential mesh.  A sequential stream predicts by Difference: the prediction and connectivity options above do not shape it."""
+    of a sequential mesh.  A sequential stream predicts by Difference: the prediction and connectivity options above do not shape it.
+
+    The levels above the default (dsa_encode_level_batch): multi_parallelogram 4 writes ConstrainedMultiParallelogram, 2
+    MultiParallelogram, in place of Parallelogram (positions and the first UV set; with 4 and parallelogram positions also the
+    generic attribute and the attribute list), -1 the reference's rule per mesh (4 at speed < 2 for meshes of 40 points or more);
+    traversal_method 1 sequences the positions' decoder (every decoder under single_connectivity) in prediction-degree order, 2
+    every decoder without interior seams.  Sequential configs and point clouds refuse both: they predict by Difference in point order."""
 
     EDGEBREAKER_METHODS = (0, 2, -1)
     POSITION_PREDICTIONS = (0, 1)
     TEXCOORD_PREDICTIONS = (0, 1, 5)
     NORMAL_PREDICTIONS = (0, 6)
     ENCODING_METHODS = (1, 0, -1)
+    MULTI_PARALLELOGRAMS = (0, 2, 4, -1)
+    TRAVERSAL_METHODS = (0, 1, 2)
 
     def __init__(self, position_bits=11, texcoord_bits=10, normal_bits=8, speed=5, single_connectivity=False,
                  symbol_scheme=-1, position_prediction=1, texcoord_prediction=1, edgebreaker_method=0, normal_prediction=0,
-                 encoding_method=1, compress_connectivity=False):
+                 encoding_method=1, compress_connectivity=False, multi_parallelogram=0, traversal_method=0):
         for name, value, legal in (("encoding_method", encoding_method, self.ENCODING_METHODS),
                                    ("edgebreaker_method", edgebreaker_method, self.EDGEBREAKER_METHODS),
                                    ("position_prediction", position_prediction, self.POSITION_PREDICTIONS),
                                    ("texcoord_prediction", texcoord_prediction, self.TEXCOORD_PREDICTIONS),
-                                   ("normal_prediction", normal_prediction, self.NORMAL_PREDICTIONS)):
+                                   ("normal_prediction", normal_prediction, self.NORMAL_PREDICTIONS),
+                                   ("multi_parallelogram", multi_parallelogram, self.MULTI_PARALLELOGRAMS),
+                                   ("traversal_method", traversal_method, self.TRAVERSAL_METHODS)):
             if value not in legal:
                 raise ValueError("%s %r: the encoder writes one of %s" % (name, value, legal))
         self.position_bits, self.texcoord_bits, self.normal_bits = position_bits, texcoord_bits, normal_bits
@@ -51,6 +61,9 @@ class Config:
         self.position_prediction, self.texcoord_prediction = position_prediction, texcoord_prediction
         self.edgebreaker_method, self.normal_prediction = edgebreaker_method, normal_prediction
         self.encoding_method, self.compress_connectivity = encoding_method, bool(compress_connectivity)
+        self.multi_parallelogram, self.traversal_method = multi_parallelogram, traversal_method
+        if self.leveled and self.sequential:
+            raise ValueError("multi_parallelogram / traversal_method shape Edgebreaker streams: a sequential stream predicts by Difference in point order")
 
     @property
     def sequential(self):
@@ -69,6 +82,18 @@ class Config:
     def extended(self):
         """True when an option only dsa_encode_batch_ex takes is set."""
         return self.edgebreaker_method != 0 or self.normal_prediction != 0
+
+    @property
+    def leveled(self):
+        """True when an option only dsa_encode_level_batch takes is set."""
+        return self.multi_parallelogram != 0 or self.traversal_method != 0
+
+    def _native_level(self):
+        o = native.EncodeLevelOptions()
+        native.lib().dsa_encode_default_level_options(C.byref(o))
+        o.ex = self._native_ex()
+        o.multi_parallelogram, o.traversal_method = self.multi_parallelogram, self.traversal_method
+        return o
 
     def _native_ex(self):
         o = native.EncodeOptionsEx()
@@ -284,6 +309,8 @@ class DracoEncoder:
         clouds = sum(1 for m in meshes if isinstance(m, PointCloudData))
         if clouds and clouds != n:
             raise ValueError("a batch holds meshes or point clouds, not both")
+        if config.leveled and (clouds or config.sequential):
+            raise ValueError("multi_parallelogram / traversal_method shape Edgebreaker streams: point clouds and sequential streams predict by Difference in point order")
         if (clouds or config.sequential) and any(getattr(m, "per_corner", False) for m in meshes):
             raise ValueError("attributes given per corner need Edgebreaker connectivity (encoding_method 1): a sequential stream has one value per point")
         ctx = self._ctx or default_context()
@@ -293,7 +320,8 @@ class DracoEncoder:
         ex = config.extended
         # the attribute-list entry point only when some mesh has a list; the corner entry point only when some mesh carries ids (or
         # an option needs dsa_encode_batch_ex, which takes the corner form); otherwise exactly the per-vertex call
-        listed = any(getattr(m, "attributes", None) for m in meshes)
+        level = config.leveled      # dsa_encode_level_batch takes the widest input: always dsa_mesh_attr_input, an empty list is legal
+        listed = level or any(getattr(m, "attributes", None) for m in meshes)
         corners = listed or ex or any(getattr(m, "per_corner", False) for m in meshes)
         arr = ((native.MeshAttrInput if listed else (native.MeshCornerInput if corners else native.MeshInput)) * max(1, n))()
         keep = []
@@ -315,10 +343,10 @@ class DracoEncoder:
                 ci.texcoord_corners = uci.ctypes.data if uci is not None else None
                 ci.num_normals = len(m.normals) if m.normals is not None else 0
                 ci.num_texcoords = len(m.texcoords) if m.texcoords is not None else 0
-        opt = config._native_ex() if (ex or listed) else config._native()
+        opt = config._native_level() if level else (config._native_ex() if (ex or listed) else config._native())
         h = C.c_void_p()
         t0 = time.perf_counter()
-        entry = L.dsa_encode_attributes_batch if listed else (L.dsa_encode_batch_ex if ex else (L.dsa_encode_batch_corners if corners else L.dsa_encode_batch))
+        entry = L.dsa_encode_level_batch if level else L.dsa_encode_attributes_batch if listed else (L.dsa_encode_batch_ex if ex else (L.dsa_encode_batch_corners if corners else L.dsa_encode_batch))
         st = entry(ctx._h, n, arr, C.byref(opt), C.byref(h))
         t1 = time.perf_counter()
         if st != 0:

@@ -25,6 +25,7 @@ EXPORTS = [
     "dsa_encode_default_options", "dsa_encode_batch", "dsa_encode_batch_corners",
     "dsa_encode_default_options_ex", "dsa_encode_batch_ex", "dsa_encode_sequential_default_options", "dsa_encode_sequential_batch",
     "dsa_encode_attributes_batch", "dsa_encode_attributes_sequential_batch",
+    "dsa_encode_default_level_options", "dsa_encode_level_batch",
     "dsa_encoded_size", "dsa_encoded_stream", "dsa_encoded_free",
     "dsa_pool_create", "dsa_pool_destroy", "dsa_pool_size", "dsa_pool_last_error", "dsa_pool_decode", "dsa_pool_job_locate",
     "dsa_pool_job_chunks", "dsa_pool_job_free", "dsa_pool_plan",
@@ -41,6 +42,14 @@ class EncodeOptionsEx(C.Structure):
     """dsa_encode_options_ex: valence Edgebreaker (edgebreaker_method 2, or -1 by speed and face count) and GeometricNormal
     (normal_prediction 6) beside the options of dsa_encode_batch."""
     _fields_ = [("base", EncodeOptions), ("edgebreaker_method", C.c_int32), ("normal_prediction", C.c_int32),
+                ("reserved", C.c_int32 * 6)]
+
+
+class EncodeLevelOptions(C.Structure):
+    """dsa_encode_level_options: multi_parallelogram (0 off, 4 ConstrainedMultiParallelogram, 2 MultiParallelogram, -1 the
+    reference's rule per mesh) and traversal_method (0 depth first, 1 / 2 prediction degree) beside the options of
+    dsa_encode_attributes_batch."""
+    _fields_ = [("ex", EncodeOptionsEx), ("multi_parallelogram", C.c_int32), ("traversal_method", C.c_int32),
                 ("reserved", C.c_int32 * 6)]
 
 
@@ -179,6 +188,9 @@ def lib():
         L.dsa_encode_sequential_batch.argtypes = [vp, u32, C.POINTER(MeshInput), C.POINTER(EncodeSequentialOptions), C.POINTER(vp)]
         L.dsa_encode_attributes_batch.argtypes = [vp, u32, C.POINTER(MeshAttrInput), C.POINTER(EncodeOptionsEx), C.POINTER(vp)]
         L.dsa_encode_attributes_sequential_batch.argtypes = [vp, u32, C.POINTER(MeshAttrInput), C.POINTER(EncodeSequentialOptions), C.POINTER(vp)]
+        L.dsa_encode_default_level_options.argtypes = [C.POINTER(EncodeLevelOptions)]
+        L.dsa_encode_default_level_options.restype = None
+        L.dsa_encode_level_batch.argtypes = [vp, u32, C.POINTER(MeshAttrInput), C.POINTER(EncodeLevelOptions), C.POINTER(vp)]
         L.dsa_encoded_size.restype = u32
         L.dsa_encoded_size.argtypes = [vp]
         L.dsa_encoded_stream.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(C.c_size_t)]

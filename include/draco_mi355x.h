@@ -358,6 +358,30 @@ dsa_status dsa_encode_attributes_batch(dsa_context *ctx, uint32_t n, const dsa_m
                                        const dsa_encode_options_ex *options, dsa_encoded **out);
 dsa_status dsa_encode_attributes_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes,
                                                   const dsa_encode_sequential_options *options, dsa_encoded **out);
+/* The levels above the default of the reference's speed ladder, for the widest mesh input.
+ *   multi_parallelogram   replaces Parallelogram (method 1) where the stream would carry it.  4 ConstrainedMultiParallelogram
+ *       (PredictionSchemeEncoderFactory.cs:63-71): the positions (position_prediction == 1), the first UV set
+ *       (texcoord_prediction == 1), and -- where the positions take it -- mesh.generic and every extra.  2 MultiParallelogram:
+ *       positions and the first UV set only.  -1: the reference's rule per mesh, 4 when compression_level >= 9 (speed < 2) and
+ *       num_vertices >= 40, else off.  Difference, TexCoordsPortable, normals and GeometricNormal are untouched.  The crease flags
+ *       of method 4 are chosen per entry: the subset of its (up to four) parallelograms with the smallest wrapped correction --
+ *       the CPU coder's choice, not the reference's running-entropy heuristic; any choice decodes.
+ *   traversal_method      MeshTraversalMethod per attributes decoder: 0 depth first; 1 prediction degree
+ *       (MaxPredictionDegreeTraverser) for the positions' decoder (every decoder's under single_connectivity); 2 for every
+ *       decoder without interior seams.  A seamed attribute is always sequenced depth first.
+ * With both at 0 the streams are those of dsa_encode_attributes_batch; per-mesh failures are that call's.  A value outside the
+ * lists or a non-zero reserved word fails the call with DSA_ERR_INVALID_ARGUMENT and dsa_last_error names the field.  The streams
+ * are byte-identical to the CPU coder's.  Added after ABI 4 without changing it: callers detect the feature by the symbol
+ * dsa_encode_level_batch. */
+typedef struct dsa_encode_level_options {
+  dsa_encode_options_ex ex;      /* as for dsa_encode_attributes_batch, same legal values */
+  int32_t multi_parallelogram;   /* 0 off (default), 4, 2 or -1 */
+  int32_t traversal_method;      /* 0 depth first (default), 1 or 2 */
+  int32_t reserved[6];           /* must be zero */
+} dsa_encode_level_options;
+void dsa_encode_default_level_options(dsa_encode_level_options *options);
+dsa_status dsa_encode_level_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes,
+                                  const dsa_encode_level_options *options, dsa_encoded **out);
 uint32_t dsa_encoded_size(const dsa_encoded *encoded);
 /* Bytes of stream `mesh` (owned by `encoded`, valid until dsa_encoded_free) or that mesh's failure status. */
 dsa_status dsa_encoded_stream(const dsa_encoded *encoded, uint32_t mesh, const uint8_t **bytes, size_t *length);
