@@ -149,6 +149,7 @@ struct dsa_context {
   // and the gate is left out -- with a note here -- when the numbers no longer add up.
   bool gate_ok = false;
   std::string gate_note;
+  std::string sched_note;     // gate_note + what the context's most recent decode left out of the schedule (dsa_context_schedule_note)
 };
 
 struct dsa_batch {
@@ -177,6 +178,15 @@ struct dsa_batch {
   uint32_t max_faces = 0, max_vertices = 0, max_atts = 0, max_att_data = 0;
   uint64_t sum_vertices = 0;
   bool any_general = false, any_valence = false, any_seamed = false, any_multipara = false;
+  // the kernel groups (NEED_*, dsa_needs.h) the host parse found work for: per mesh and for the batch, [0] without / [1] with the
+  // octahedral delta on k_predict_oct_streams (which of the two a decode uses is its own choice); `launched`: what the most recent
+  // decode queued, `prune_note`: the groups it left out, in words
+  std::vector<uint32_t> mesh_needs[2];
+  uint32_t needs[2] = {NEED_ALL, NEED_ALL};
+  uint32_t launched = NEED_ALL;
+  int needs_k = 0;            // which of the two masks the most recent decode went by
+  bool note_made = false;
+  std::string prune_note;
   bool decoded = false, collected = false;
   hipEvent_t ev[DSA_NUM_STAGES + 1] = {};
   hipEvent_t ev_sym[2] = {};
@@ -266,6 +276,10 @@ hipError_t arena_alloc(dsa_context *ctx, uint64_t need, uint8_t **out, uint64_t 
   *cap = need;
   return e;
 }
+
+// The launch flags the product schedule runs with (dsa_batch_decode), as the predicates of dsa_needs.h read them; OS_FLAG is added
+// per decode.  A -DDSA_EXPERIMENTS build varies them from the environment, and does not prune its schedule.
+constexpr uint32_t kPruneFlags = PW_FLAG | SYM_WIDE;
 
 dsa_status build_batch(dsa_context *ctx, uint32_t n, const uint8_t *const *streams, const size_t *lengths, dsa_batch **out, bool all_general = false) {
   if (!ctx || !out || (n && (!streams || !lengths))) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "null argument");
@@ -363,6 +377,14 @@ dsa_status build_batch(dsa_context *ctx, uint32_t n, const uint8_t *const *strea
     b->host[worst].status = DSA_ERR_OUT_OF_MEMORY;
   }
   if (e != hipSuccess) return set_err(ctx, DSA_ERR_OUT_OF_MEMORY, "hipMalloc of %llu-byte arena failed: %s", (unsigned long long)b->arena_bytes, hipGetErrorString(e));
+  {   // what the needs walk of every mesh asks of the schedule, now that the capacities the predicates read are placed
+    for (int k = 0; k < 2; ++k) b->mesh_needs[k].assign(n, NEED_ALL);
+    for (uint32_t i = 0; i < n; ++i) {         // (a few predicates per attribute: not worth threads)
+      for (int k = 0; k < 2; ++k) b->mesh_needs[k][i] = all_general ? NEED_ALL : host_mesh_needs(b->host[i], b->layouts[i], kPruneFlags | (k ? OS_FLAG : 0u));
+      std::vector<AttrDesc>().swap(b->host[i].walk);
+    }
+    for (int k = 0; k < 2; ++k) { uint32_t m = 0; for (uint32_t i = 0; i < n; ++i) m |= b->mesh_needs[k][i]; b->needs[k] = m; }
+  }
   b->d_layouts = (MeshLayout *)(b->arena + off_layouts);
   b->d_globals = (BatchGlobals *)(b->arena + off_globals);
   b->d_compact = (CompactMesh *)(b->arena + off_compact);
@@ -431,6 +453,35 @@ dsa_status build_batch(dsa_context *ctx, uint32_t n, const uint8_t *const *strea
   guard.b = nullptr;
   *out = b;
   return DSA_OK;
+}
+
+// What a decode that launches the kernel groups `want` leaves out, in words (dsa_context_schedule_note, dsa_batch_copy_debug 8).
+std::string prune_note_of(uint32_t want, bool seamed) {
+  if (want == NEED_ALL) return "last decode: every kernel group launched";
+  std::string s = "last decode left out:";
+  const size_t empty = s.size();
+  if (!(want & NEED_TAGS)) s += " tags (k_tags, k_locate_resume);";
+  const struct { const char *name; uint32_t shift; bool there; } groups[3] = {{"early", NEED_SHIFT_EARLY, true}, {"late", NEED_SHIFT_LATE, true}, {"corner", NEED_SHIFT_CORNER, seamed}};
+  for (const auto &g : groups) {
+    if (!g.there) continue;
+    const uint32_t m = want >> g.shift;
+    if ((m & 0xFu) == 0xFu) continue;
+    s += std::string(" ") + g.name + " symbols:";
+    if (!(m & NEED_TIER0)) s += " tier 0";
+    if (!(m & NEED_TIER1)) s += " tier 1";
+    if (!(m & NEED_TIER2)) s += " tier 2";
+    if (!(m & NEED_WIDE)) s += " wide";
+    s += ";";
+  }
+  if (!(want & NEED_GEOMETRIC)) s += " GeometricNormal (k_flip_bits, k_vertex_positions, k_predict_geometric);";
+  if (!(want & NEED_TEXCOORDS)) s += " TexCoordsPortable (k_orient_bits, k_texcoords_prepare, k_texcoords);";
+  if (!(want & NEED_PREDICT_EARLY)) s += " early k_predict;";
+  if (!(want & NEED_PREDICT_LATE)) s += " late k_predict;";
+  if (!(want & NEED_WRAP_EARLY)) s += " early k_predict_wrap;";
+  if (!(want & NEED_FINALIZE_LATE)) s += " late k_finalize;";
+  if (s.size() == empty) s += " nothing";
+  else s.pop_back();
+  return s;
 }
 
 // The register arithmetic k_register_gate rests on (dsa_kernels.h): a SIMD's 512 vector registers hold four
@@ -596,25 +647,7 @@ dsa_status dsa_batch_decode(dsa_batch *b) {
   HIP_TRY(ctx, hipMemsetAsync(b->d_descs, 0, sizeof(MeshDesc) * n, st));
   HIP_TRY(ctx, hipMemsetAsync(&b->d_globals->pool_cursor, 0, sizeof(unsigned long long) * 2, st));   // the table pool starts empty
   HIP_TRY(ctx, mark());
-  {
-    uint32_t gx = std::max<uint32_t>(1, std::min<uint32_t>((b->max_faces + 16383) / 16384, 4));
-    hipLaunchKernelGGL(dsa::k_init, dim3(gx, n), dim3(256), 0, st, b->arena, b->d_layouts, n);
-  }
-  hipLaunchKernelGGL(dsa::k_locate, dim3(n), dim3(WAVE), 0, st, b->arena, b->d_layouts, b->d_descs, n, b->d_globals);
-  // tagged symbol streams: a round of {tag stream on a wave of its own, the walk taken up behind it} per attribute a mesh can
-  // have (what follows a tagged attribute is only found by decoding its tags); nothing to do without them
-  for (uint32_t r = 0; r < std::max<uint32_t>(1, b->max_atts); ++r) {
-    k_begin(KT_TAGS, st);                      // (the first round's: a mesh's first tagged attribute)
-    hipLaunchKernelGGL(dsa::k_tags, dim3(n), dim3(WAVE), 0, st, b->arena, b->d_layouts, b->d_descs, n);
-    k_end(KT_TAGS, st);
-    hipLaunchKernelGGL(dsa::k_locate_resume, dim3(n), dim3(WAVE), 0, st, b->arena, b->d_layouts, b->d_descs, n, b->d_globals);
-  }
-  // valence-coded connectivity: the six context lists of every mesh on waves of their own (the register-table decoder), in front
-  // of the connectivity waves, which would otherwise decode them one after the other at a third of the speed each
-  if (b->any_valence) hipLaunchKernelGGL(dsa::k_valence_lists, dim3(n, 6), dim3(WAVE), 0, st, b->arena, b->d_layouts, b->d_descs, n);
-  HIP_TRY(ctx, mark());
   const uint32_t na = std::max<uint32_t>(1, b->max_atts);
-  // fork: entropy decode of every attribute stream on the second stream (it only needs k_locate's offsets)
   // DSA_SERIAL=1 (diagnostics): everything on the main stream, so that stage times are stand-alone kernel times
   static const bool serial = getenv("DSA_SERIAL") != nullptr;
   // Everything else the schedule could vary by is fixed in the product library; a -DDSA_EXPERIMENTS build (csrc/Makefile, EXTRA=)
@@ -643,7 +676,52 @@ dsa_status dsa_batch_decode(dsa_batch *b) {
   const int oct_choice = []() { const char *e = getenv("DSA_OCT_STREAMS"); return e ? atoi(e) : -1; }();
   const bool oct_rule = n >= 3584 && (uint64_t)b->max_vertices * n <= 4 * b->sum_vertices;
   const uint32_t oct_flag = (oct_choice >= 0 ? oct_choice != 0 : oct_rule) && !(lane_flags & (LN_FLAG_OCT | LN_FLAG_PREDICT)) ? OS_FLAG : 0u;
+  // The kernel groups this decode launches (NEED_*, dsa_needs.h): those the host parse found work for in some mesh of the batch.
+  // Most batches come from one encoder setting -- raw 12-bit symbol streams, no tagged stream, no GeometricNormal or
+  // TexCoordsPortable -- and the launches that would find nothing to do stand in front of the entropy decoders and behind the
+  // last prediction, where the step pays for them one for one.  k_seal gets the set and refuses a mesh that needed more.
+  // DSA_PRUNE=0 (diagnostics, read per decode like DSA_OCT_STREAMS): every kernel, whatever the batch holds.
+  const bool prune_on = []() { const char *e = getenv("DSA_PRUNE"); return !e || atoi(e) != 0; }();
+#ifdef DSA_EXPERIMENTS
+  const uint32_t want = NEED_ALL;          // (the switches change which kernel takes what)
+  (void)prune_on;
+#else
+  // Where k_register_gate is in use, the four kernels in front of it stay: idle as they are for most batches, they are what keeps
+  // the gate off the machine while it is still empty -- k_symbols<2>, a wave of which wants 17 KB of LDS, is not through before the
+  // early launch has filled the SIMDs (9 ms into the bench decode), and a gate dispatched before that finds 136 free registers
+  // everywhere and holds nothing back.  They run on the low-priority stream, beside the critical path, not on it.
+  const uint32_t gate_front = (oct_flag && ctx->gate_ok) ? 0xFu << NEED_SHIFT_LATE : 0u;
+  const uint32_t want = prune_on ? (b->needs[oct_flag ? 1 : 0] | gate_front) : NEED_ALL;
+#endif
+  b->needs_k = oct_flag ? 1 : 0;
+  if (!b->note_made || want != b->launched) {
+    b->launched = want; b->note_made = true;
+    b->prune_note = prune_note_of(want, b->any_seamed);
+  }
+  {
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (ctx->sched_note.size() != ctx->gate_note.size() + 2 + b->prune_note.size() || ctx->sched_note.compare(ctx->gate_note.size() + 2, std::string::npos, b->prune_note) != 0)
+      ctx->sched_note = ctx->gate_note + "; " + b->prune_note;
+  }
+  {
+    uint32_t gx = std::max<uint32_t>(1, std::min<uint32_t>((b->max_faces + 16383) / 16384, 4));
+    hipLaunchKernelGGL(dsa::k_init, dim3(gx, n), dim3(256), 0, st, b->arena, b->d_layouts, n);
+  }
+  hipLaunchKernelGGL(dsa::k_locate, dim3(n), dim3(WAVE), 0, st, b->arena, b->d_layouts, b->d_descs, n, b->d_globals);
+  // tagged symbol streams: a round of {tag stream on a wave of its own, the walk taken up behind it} per attribute a mesh can
+  // have (what follows a tagged attribute is only found by decoding its tags); nothing to do without them
+  for (uint32_t r = 0; r < std::max<uint32_t>(1, b->max_atts) && (want & NEED_TAGS); ++r) {
+    k_begin(KT_TAGS, st);                      // (the first round's: a mesh's first tagged attribute)
+    hipLaunchKernelGGL(dsa::k_tags, dim3(n), dim3(WAVE), 0, st, b->arena, b->d_layouts, b->d_descs, n);
+    k_end(KT_TAGS, st);
+    hipLaunchKernelGGL(dsa::k_locate_resume, dim3(n), dim3(WAVE), 0, st, b->arena, b->d_layouts, b->d_descs, n, b->d_globals);
+  }
+  // valence-coded connectivity: the six context lists of every mesh on waves of their own (the register-table decoder), in front
+  // of the connectivity waves, which would otherwise decode them one after the other at a third of the speed each
+  if (b->any_valence) hipLaunchKernelGGL(dsa::k_valence_lists, dim3(n, 6), dim3(WAVE), 0, st, b->arena, b->d_layouts, b->d_descs, n);
+  HIP_TRY(ctx, mark());
   hipStream_t st2 = serial ? st : S.stream2, st3 = serial ? st : S.stream3;
+  // fork: entropy decode of every attribute stream on the second stream (it only needs k_locate's offsets)
   HIP_TRY(ctx, hipEventRecord(S.ev_fork, st));
   HIP_TRY(ctx, hipStreamWaitEvent(st2, S.ev_fork, 0));
   if (b->any_general) {                 // whole-mesh serial decode of the general-path meshes, beside the fast kernels
@@ -674,9 +752,9 @@ dsa_status dsa_batch_decode(dsa_batch *b) {
     const uint32_t per_wave = WAVE / lpm;
     hipStream_t st5 = serial ? st : S.stream5;
     HIP_TRY(ctx, hipStreamWaitEvent(st5, S.ev_fork, 0));
-    hipLaunchKernelGGL(dsa::k_flip_bits, dim3((n + per_wave - 1) / per_wave), dim3(WAVE), 0, st5, b->arena, b->d_layouts, b->d_descs, n, lpm, 0u);
+    if (want & NEED_GEOMETRIC) hipLaunchKernelGGL(dsa::k_flip_bits, dim3((n + per_wave - 1) / per_wave), dim3(WAVE), 0, st5, b->arena, b->d_layouts, b->d_descs, n, lpm, 0u);
     // and the orientation bits of TexCoordsPortable attributes, the same way
-    hipLaunchKernelGGL(dsa::k_orient_bits, dim3((n + per_wave - 1) / per_wave), dim3(WAVE), 0, st5, b->arena, b->d_layouts, b->d_descs, n, lpm, 0u);
+    if (want & NEED_TEXCOORDS) hipLaunchKernelGGL(dsa::k_orient_bits, dim3((n + per_wave - 1) / per_wave), dim3(WAVE), 0, st5, b->arena, b->d_layouts, b->d_descs, n, lpm, 0u);
     // and the crease flags of ConstrainedMultiParallelogram attributes: four streams each (only where the host parse saw the scheme)
     if (b->any_multipara) hipLaunchKernelGGL(dsa::k_crease_bits, dim3((n + WAVE / (4 * lpm) - 1) / (WAVE / (4 * lpm))), dim3(WAVE), 0, st5, b->arena, b->d_layouts, b->d_descs, n, lpm);
     HIP_TRY(ctx, hipEventRecord(S.ev_flips, st5));
@@ -737,7 +815,7 @@ dsa_status dsa_batch_decode(dsa_batch *b) {
       k_end(KT_SEAM_TABLES, st3);
       // a corner attribute whose extent is its entry count (tagged symbols, uncompressed integers) stopped the walk of its mesh: it
       // is taken up here, as many rounds of {tag stream, walk} as a mesh has attributes (nothing to do for most batches)
-      for (uint32_t r = 0; r < std::max<uint32_t>(1, b->max_atts); ++r) {
+      for (uint32_t r = 0; r < std::max<uint32_t>(1, b->max_atts) && (want & NEED_TAGS); ++r) {
         hipLaunchKernelGGL(dsa::k_tags, dim3(n), dim3(WAVE), 0, st3, b->arena, b->d_layouts, b->d_descs, n);
         hipLaunchKernelGGL(dsa::k_locate_resume, dim3(n), dim3(WAVE), 0, st3, b->arena, b->d_layouts, b->d_descs, n, b->d_globals);
       }
@@ -753,8 +831,8 @@ dsa_status dsa_batch_decode(dsa_batch *b) {
         const uint32_t per_wave = WAVE / lpm;
         hipStream_t st5 = serial ? st : S.stream5;
         HIP_TRY(ctx, hipStreamWaitEvent(st5, S.ev_tables, 0));
-        hipLaunchKernelGGL(dsa::k_flip_bits, dim3((n + per_wave - 1) / per_wave), dim3(WAVE), 0, st5, b->arena, b->d_layouts, b->d_descs, n, lpm, 1u);
-        hipLaunchKernelGGL(dsa::k_orient_bits, dim3((n + per_wave - 1) / per_wave), dim3(WAVE), 0, st5, b->arena, b->d_layouts, b->d_descs, n, lpm, 1u);
+        if (want & NEED_GEOMETRIC) hipLaunchKernelGGL(dsa::k_flip_bits, dim3((n + per_wave - 1) / per_wave), dim3(WAVE), 0, st5, b->arena, b->d_layouts, b->d_descs, n, lpm, 1u);
+        if (want & NEED_TEXCOORDS) hipLaunchKernelGGL(dsa::k_orient_bits, dim3((n + per_wave - 1) / per_wave), dim3(WAVE), 0, st5, b->arena, b->d_layouts, b->d_descs, n, lpm, 1u);
         HIP_TRY(ctx, hipEventRecord(S.ev_flips, st5));
       }
     }
@@ -799,13 +877,17 @@ dsa_status dsa_batch_decode(dsa_batch *b) {
   auto launch_symbols = [&](hipStream_t s, uint32_t fl, bool gate = false) {
     fl |= wide_flag;
     const uint32_t tier_blocks = (uint32_t)std::min<uint64_t>((uint64_t)n * na, SYM_TIER_BLOCKS);
-    // The kernels for everything but 12-bit-precision streams go first: for most batches they find nothing to do, which takes
-    // them microseconds while the machine is still filling and a millisecond and a half once every slot is held by a decoder
-    // (they used to follow k_symbols_reg: 1.7 ms of empty launches in front of the early attributes' prediction).
-    if (wide_flag) hipLaunchKernelGGL(dsa::k_symbols_wide, dim3(n, na), dim3(WAVE), 0, s, b->arena, b->d_layouts, b->d_descs, n, fl);
-    hipLaunchKernelGGL(dsa::k_symbols<1>, dim3(tier_blocks), dim3(WAVE), dsa::sym_tier_lds_bytes(1), s, b->arena, b->d_layouts, b->d_descs, n, na, fl);
-    hipLaunchKernelGGL(dsa::k_symbols<0>, dim3(tier_blocks), dim3(WAVE), dsa::sym_tier_lds_bytes(0), s, b->arena, b->d_layouts, b->d_descs, n, na, fl);
-    hipLaunchKernelGGL(dsa::k_symbols<2>, dim3(tier_blocks), dim3(WAVE), dsa::sym_tier_lds_bytes(2), s, b->arena, b->d_layouts, b->d_descs, n, na, fl);
+    // what the launch's group of attributes (early, late, corner; without the split: early and late) asks for beside k_symbols_reg
+    const uint32_t grp = (fl & SYM_CORNER) ? (want >> NEED_SHIFT_CORNER) : (((fl & SYM_LATE_ONLY) ? 0u : (want >> NEED_SHIFT_EARLY)) | ((fl & SYM_EARLY_ONLY) ? 0u : (want >> NEED_SHIFT_LATE)));
+    // The kernels for everything but 12-bit-precision streams go first, and only where the batch has such a stream: with nothing
+    // to do they take microseconds while the machine is still filling, but the chain is filling it by then -- measured, the four
+    // hold the early launch's stream for a millisecond in front of k_symbols_reg, whose decoders bound the step -- and a
+    // millisecond and a half once every slot is held by a decoder (they used to follow k_symbols_reg: 1.7 ms of empty launches
+    // in front of the early attributes' prediction).
+    if (wide_flag && (grp & NEED_WIDE)) hipLaunchKernelGGL(dsa::k_symbols_wide, dim3(n, na), dim3(WAVE), 0, s, b->arena, b->d_layouts, b->d_descs, n, fl);
+    if (grp & NEED_TIER1) hipLaunchKernelGGL(dsa::k_symbols<1>, dim3(tier_blocks), dim3(WAVE), dsa::sym_tier_lds_bytes(1), s, b->arena, b->d_layouts, b->d_descs, n, na, fl);
+    if (grp & NEED_TIER0) hipLaunchKernelGGL(dsa::k_symbols<0>, dim3(tier_blocks), dim3(WAVE), dsa::sym_tier_lds_bytes(0), s, b->arena, b->d_layouts, b->d_descs, n, na, fl);
+    if (grp & NEED_TIER2) hipLaunchKernelGGL(dsa::k_symbols<2>, dim3(tier_blocks), dim3(WAVE), dsa::sym_tier_lds_bytes(2), s, b->arena, b->d_layouts, b->d_descs, n, na, fl);
     if (gate) hipLaunchKernelGGL(dsa::k_register_gate, dim3(SYM_TIER_BLOCKS), dim3(WAVE), 0, s);
     const int kt = (fl & SYM_EARLY_ONLY) ? KT_SYMBOLS_EARLY : KT_SYMBOLS_LATE;
     k_begin(kt, s);
@@ -869,8 +951,8 @@ dsa_status dsa_batch_decode(dsa_batch *b) {
       hipLaunchKernelGGL(dsa::k_predict_oct_streams, dim3((n + WAVE - 1) / WAVE, na), dim3(WAVE), OS_RING * 1024u, st4, b->arena, b->d_layouts, b->d_descs, n);
       k_end(KT_OCT_STREAMS, st4);
     }
-    hipLaunchKernelGGL(dsa::k_predict, dim3(n, na), dim3(WAVE), 0, st4, b->arena, b->d_layouts, b->d_descs, n, 0u, lane_flags | oct_flag);
-    if (lane_flags & PW_FLAG) {
+    if (want & NEED_PREDICT_EARLY) hipLaunchKernelGGL(dsa::k_predict, dim3(n, na), dim3(WAVE), 0, st4, b->arena, b->d_layouts, b->d_descs, n, 0u, lane_flags | oct_flag);
+    if ((lane_flags & PW_FLAG) && (want & NEED_WRAP_EARLY)) {
       k_begin(KT_PREDICT_WRAP_EARLY, st4);
       hipLaunchKernelGGL(dsa::k_predict_wrap, dim3(n, na), dim3(WAVE), 0, st4, b->arena, b->d_layouts, b->d_descs, n, 0u, lane_flags);
       k_end(KT_PREDICT_WRAP_EARLY, st4);
@@ -902,7 +984,7 @@ dsa_status dsa_batch_decode(dsa_batch *b) {
     // finds the positions final (the TexCoordsPortable and GeometricNormal predictors read them)
     HIP_TRY(ctx, hipStreamWaitEvent(st, S.ev_pred, 0));
     if (lane_flags & PW_FLAG) hipLaunchKernelGGL(dsa::k_predict_wrap, dim3(n, na), dim3(WAVE), 0, st, b->arena, b->d_layouts, b->d_descs, n, 1u, lane_flags | PRED_FRONT);
-    hipLaunchKernelGGL(dsa::k_predict, dim3(n, na), dim3(WAVE), 0, st, b->arena, b->d_layouts, b->d_descs, n, 1u, lane_flags | PRED_FRONT);
+    if (want & NEED_PREDICT_LATE) hipLaunchKernelGGL(dsa::k_predict, dim3(n, na), dim3(WAVE), 0, st, b->arena, b->d_layouts, b->d_descs, n, 1u, lane_flags | PRED_FRONT);
     // (k_vertex_positions stays behind the second prediction launch: it leaves the positions by vertex in the operand region of the
     // position connectivity, which an attribute of that connectivity located only behind the seam tables still reads there)
     split_prediction = true;
@@ -922,7 +1004,7 @@ dsa_status dsa_batch_decode(dsa_batch *b) {
       hipLaunchKernelGGL(dsa::k_predict_wrap, dim3(n, na), dim3(WAVE), 0, st, b->arena, b->d_layouts, b->d_descs, n, 1u, lane_flags | behind);
       k_end(KT_PREDICT_WRAP_LATE, st);
     }
-    hipLaunchKernelGGL(dsa::k_predict, dim3(n, na), dim3(WAVE), 0, st, b->arena, b->d_layouts, b->d_descs, n, 1u, lane_flags | behind);
+    if (want & NEED_PREDICT_LATE) hipLaunchKernelGGL(dsa::k_predict, dim3(n, na), dim3(WAVE), 0, st, b->arena, b->d_layouts, b->d_descs, n, 1u, lane_flags | behind);
   }
   HIP_TRY(ctx, mark());
   {
@@ -937,24 +1019,26 @@ dsa_status dsa_batch_decode(dsa_batch *b) {
       hipLaunchKernelGGL(dsa::k_multipara_prepare, dim3(gx, n, na), dim3(256), 0, st, b->arena, b->d_layouts, b->d_descs, n);
       hipLaunchKernelGGL(dsa::k_multipara, dim3((n + 3) / 4, na), dim3(WAVE), 0, st, b->arena, b->d_layouts, b->d_descs, n, b->d_globals);
     }
-    hipLaunchKernelGGL(dsa::k_vertex_positions, dim3(gv, n), dim3(256), 0, st, b->arena, b->d_layouts, b->d_descs, n);
-    hipLaunchKernelGGL(dsa::k_predict_geometric, dim3(gx, n, na), dim3(256), 0, st, b->arena, b->d_layouts, b->d_descs, n);
+    if (want & NEED_GEOMETRIC) hipLaunchKernelGGL(dsa::k_vertex_positions, dim3(gv, n), dim3(256), 0, st, b->arena, b->d_layouts, b->d_descs, n);
+    if (want & NEED_GEOMETRIC) hipLaunchKernelGGL(dsa::k_predict_geometric, dim3(gx, n, na), dim3(256), 0, st, b->arena, b->d_layouts, b->d_descs, n);
     // TexCoordsPortable attributes: what depends on the mesh and the positions for every entry at once, then the chain over the
     // decoded texture coordinates, two lanes per attribute.  (The GeometricNormal kernels beside the chain, on another stream: the
     // chain's 128 waves, placed while the machine is full, share SIMDs among themselves -- 16 -> 27 ms even when those kernels
     // find nothing to do; kept one to a CU by an LDS allocation they still take 24 - 25 ms beside real GeometricNormal work,
     // whose memory traffic outlasts the chain's request distance: 75 against 73 ms.  One after the other.)
-    hipLaunchKernelGGL(dsa::k_texcoords_prepare, dim3(gx, n, na), dim3(256), 0, st, b->arena, b->d_layouts, b->d_descs, n);
-    k_begin(KT_TEXCOORDS, st);
-    hipLaunchKernelGGL(dsa::k_texcoords, dim3((2 * n + WAVE - 1) / WAVE, na), dim3(WAVE), 0, st, b->arena, b->d_layouts, b->d_descs, n);      // two lanes per attribute
-    k_end(KT_TEXCOORDS, st);
+    if (want & NEED_TEXCOORDS) {
+      hipLaunchKernelGGL(dsa::k_texcoords_prepare, dim3(gx, n, na), dim3(256), 0, st, b->arena, b->d_layouts, b->d_descs, n);
+      k_begin(KT_TEXCOORDS, st);
+      hipLaunchKernelGGL(dsa::k_texcoords, dim3((2 * n + WAVE - 1) / WAVE, na), dim3(WAVE), 0, st, b->arena, b->d_layouts, b->d_descs, n);      // two lanes per attribute
+      k_end(KT_TEXCOORDS, st);
+    }
   }
-  {
+  if (want & NEED_FINALIZE_LATE) {
     uint32_t gx = std::max<uint32_t>(1, std::min<uint32_t>((3 * b->max_faces + 65535) / 65536, 4));
     hipLaunchKernelGGL(dsa::k_finalize, dim3(gx, n, na), dim3(256), 0, st, b->arena, b->d_layouts, b->d_descs, n, 1u, lane_flags);
   }
   HIP_TRY(ctx, hipStreamWaitEvent(st, S.ev_maps, 0));
-  hipLaunchKernelGGL(dsa::k_seal, dim3((n + 255) / 256), dim3(256), 0, st, b->d_descs, n);
+  hipLaunchKernelGGL(dsa::k_seal, dim3((n + 255) / 256), dim3(256), 0, st, b->d_descs, b->d_layouts, n, lane_flags | oct_flag | wide_flag, want);
   HIP_TRY(ctx, mark());
   HIP_TRY(ctx, hipGetLastError());
   // every other stream has joined `st` by now: this event is the whole decode.  The descriptors follow on the download stream.
@@ -1329,6 +1413,21 @@ dsa_status dsa_batch_copy_metadata(const dsa_batch *b, uint32_t mesh, uint8_t *d
 }
 
 dsa_status dsa_batch_copy_debug(const dsa_batch *b, uint32_t mesh, int what, void *dst, size_t dst_bytes, size_t *written) {
+  if (what == 7 || what == 8) {   // the pruned schedule of this batch's most recent decode (a mesh handed to the general path included)
+    if (!b || mesh >= b->n || !dst) return DSA_ERR_INVALID_ARGUMENT;
+    if (what == 7) {   // {this mesh's need bits by the host parse, by the device (k_seal), the groups the decode launched, the batch's host mask}
+      if (dst_bytes < 16) return set_err(b->ctx, DSA_ERR_INVALID_ARGUMENT, "destination too small");
+      const int k = b->needs_k;
+      const uint32_t o[4] = {b->mesh_needs[k][mesh], b->descs[mesh].needs, b->launched, b->needs[k]};
+      memcpy(dst, o, 16);
+      if (written) *written = 16;
+    } else {           // the same in words: what it left out
+      const size_t len = std::min(b->prune_note.size(), dst_bytes);
+      memcpy(dst, b->prune_note.data(), len);
+      if (written) *written = len;
+    }
+    return DSA_OK;
+  }
   FOLLOW_RETRY(b, mesh, dsa_batch_copy_debug(rb_, rm_, what, dst, dst_bytes, written));
   CHECK_MESH(b, mesh);
   const MeshDesc &D = b->descs[mesh];
@@ -1408,7 +1507,7 @@ dsa_status dsa_batch_kernel_times(const dsa_batch *b, float *ms, const char **na
   return DSA_OK;
 }
 
-const char *dsa_context_schedule_note(const dsa_context *ctx) { return ctx ? ctx->gate_note.c_str() : ""; }
+const char *dsa_context_schedule_note(const dsa_context *ctx) { return ctx ? (ctx->sched_note.empty() ? ctx->gate_note.c_str() : ctx->sched_note.c_str()) : ""; }
 
 dsa_status dsa_context_trim(dsa_context *ctx) {
   if (!ctx) return DSA_ERR_INVALID_ARGUMENT;

@@ -183,7 +183,7 @@ __device__ bool skip_prob_table(Rd &r, uint32_t n, uint32_t *distinct) {
   *distinct = nz;
   return r.ok;
 }
-__device__ __forceinline__ uint32_t rans_precision_bits(uint32_t max_bit_length) {   // Entropy/RAnsSymbolCoding.cs:10-27
+__host__ __device__ __forceinline__ uint32_t rans_precision_bits(uint32_t max_bit_length) {   // Entropy/RAnsSymbolCoding.cs:10-27
   uint32_t p = (3 * max_bit_length) / 2;
   return p < 12 ? 12 : (p > 20 ? 20 : p);
 }

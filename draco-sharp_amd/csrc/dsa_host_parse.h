@@ -1,6 +1,7 @@
 // draco-sharp_amd/csrc/dsa_host_parse.h
 // Host side of batch construction that needs no HIP: the sizing parse of one stream (fixed header, section
-// lengths, attribute descriptors) and the placement of one mesh's regions in the batch arena.  Included by
+// lengths, attribute descriptors), the "needs" walk through its attribute value sections (which kernel groups of the decode
+// schedule have work for the mesh, dsa_needs.h) and the placement of one mesh's regions in the batch arena.  Included by
 // dsa_api.hip; tests/hostcheck includes it too, to lay out a one-mesh arena for the sanitizer build of the
 // general path.
 #pragma once
@@ -13,6 +14,7 @@
 #include <vector>
 
 #include "dsa_types.h"
+#include "dsa_needs.h"
 
 namespace {
 
@@ -25,14 +27,20 @@ struct HostMesh {
   bool valence = false;   // valence-coded connectivity on the fast kernels (k_valence_lists in front of the connectivity waves)
   bool seamed = false;    // corner-attribute decoders (attribute seams) on the fast kernels (k_seam_tables, k_traverse_att)
   uint32_t meta_off = 0, meta_len = 0;   // metadata block of the stream (flag 0x8000), for dsa_batch_copy_metadata
+  uint32_t off_attributes = 0;           // stream offset of the attribute section (its decoder-count byte)
   int first_method = -128;               // prediction method byte of the first attribute (the values of the first decoder start with it), -128: none
   std::vector<HostAttr> atts;
+  // the needs walk: what the value section of every attribute says about its kind, in the device's own descriptor format (the fields
+  // the predicates of dsa_needs.h read); walk_ok: the walk saw all of it -- else the mesh gets every kernel of the schedule
+  std::vector<AttrDesc> walk;
+  bool walk_ok = false;
 };
 
 struct HRd {
   const uint8_t *p; size_t n, pos = 0; bool ok = true;
   HRd(const uint8_t *d, size_t len) : p(d), n(len) {}
   uint32_t u8() { if (pos < n) return p[pos++]; ok = false; return 0; }
+  uint32_t u32() { uint32_t a = u8(); a |= u8() << 8; a |= u8() << 16; return a | (u8() << 24); }
   uint64_t varint() {
     uint64_t r = 0;
     for (int shift = 0; shift < 64; shift += 7) { uint32_t b = u8(); r |= (uint64_t)(b & 0x7F) << shift; if (!(b & 0x80)) return r; }
@@ -110,7 +118,9 @@ static uint32_t dt_len(uint32_t dt) {
   switch (dt) { case 1: case 2: case 11: return 1; case 3: case 4: return 2; case 5: case 6: case 9: return 4; case 7: case 8: case 10: return 8; default: return 0; }
 }
 
-// Mirrors the head of k_locate (same checks, same order) up to the attribute descriptors.
+static void host_walk_values(HRd &r, HostMesh &m, const std::vector<uint32_t> &dec_first);
+
+// Mirrors the head of k_locate (same checks, same order) up to the attribute descriptors; the needs walk goes on from there.
 static void host_parse(const uint8_t *s, size_t len, HostMesh &m, bool want_general = false) {
   HRd r(s, len);
   auto bad = [&](int code) { m.status = code; };
@@ -187,6 +197,7 @@ static void host_parse(const uint8_t *s, size_t len, HostMesh &m, bool want_gene
       }
     }
   }
+  m.off_attributes = (uint32_t)r.pos;
   uint32_t ndec = r.u8();
   if (!r.ok) return bad(ST_INVALID);
   if (ndec > DSA_MAX_ATT) return bad(ST_NOTIMPL);               // a valid stream, more attribute decoders than the device path carries
@@ -204,11 +215,13 @@ static void host_parse(const uint8_t *s, size_t len, HostMesh &m, bool want_gene
   const bool force_general = getenv("DSA_FORCE_GENERAL") != nullptr;   // tests: every Edgebreaker mesh through k_general
   if ((force_general || want_general) && !point_cloud) m.general = true;
   m.seamed = any_corner && !m.general;
+  std::vector<uint32_t> dec_first;
   for (uint32_t i = 0; i < ndec; ++i) {
     uint64_t k = r.varint();
     if (!r.ok) return bad(ST_INVALID);
     if (m.atts.size() + k > DSA_MAX_ATT) return bad(ST_NOTIMPL);
     size_t first = m.atts.size();
+    dec_first.push_back((uint32_t)first);
     for (uint64_t j = 0; j < k; ++j) {
       HostAttr a;
       a.att_type = (uint8_t)r.u8(); a.data_type = (uint8_t)r.u8(); a.nc = (uint8_t)r.u8(); (void)r.u8();
@@ -224,6 +237,122 @@ static void host_parse(const uint8_t *s, size_t len, HostMesh &m, bool want_gene
   for (auto &a : m.atts) if (a.nc == 0 || dt_len(a.data_type) == 0 || a.seq_type > 3) return bad(ST_INVALID);
   // SequentialIntegerAttributeDecoder.cs:70-76: the values of an integer / quantised attribute start with its prediction method
   if (!linear && !m.atts.empty() && m.atts[0].seq_type != 0 && r.pos < r.n) m.first_method = (int8_t)r.p[r.pos];
+  dec_first.push_back((uint32_t)m.atts.size());
+  if (!linear && !m.general && !any_corner) host_walk_values(r, m, dec_first);
+}
+
+// The needs walk: the value sections of the attributes of an Edgebreaker mesh on the fast kernels, every attribute one entry per
+// encoded vertex (no corner-attribute decoder), as locate_attribute_section / locate_attribute_values (dsa_locate.h) walk them --
+// but only as far as the host can see without decoding: a tagged symbol stream ends the walk (what follows it is only found by
+// decoding its tags), and so does anything the device parse would refuse or hand to the general path.  A walk that ends early
+// leaves walk_ok unset, and the mesh then asks for every kernel of the schedule.  Reads the headers and the probability tables only.
+static void host_walk_values(HRd &r, HostMesh &m, const std::vector<uint32_t> &dec_first) {
+  const uint64_t nv = m.enc_vertices;
+  m.walk.assign(m.atts.size(), AttrDesc());
+  auto rabs_skip = [&]() { (void)r.u8(); const uint64_t sz = r.varint(); r.skip(sz); return r.ok && sz >= 1; };
+  for (size_t d = 0; d + 1 < dec_first.size(); ++d) {
+    for (uint32_t ai = dec_first[d]; ai < dec_first[d + 1]; ++ai) {
+      const HostAttr &A = m.atts[ai];
+      AttrDesc &a = m.walk[ai];
+      a.att_type = A.att_type; a.data_type = A.data_type; a.nc = A.nc; a.seq_type = A.seq_type;
+      a.num_entries = (uint32_t)nv;
+      if (A.seq_type == 0) {       // generic: raw bytes
+        a.source = SRC_BYTES; a.nc_portable = A.nc;
+        r.skip((uint64_t)dt_len(A.data_type) * A.nc * nv);
+        if (!r.ok) return;
+        continue;
+      }
+      const uint32_t nc = A.seq_type == 3 ? 2u : A.nc;
+      a.nc_portable = (uint8_t)nc;
+      const uint64_t num_values = nv * nc;
+      const int method = (int8_t)r.u8();
+      if (!r.ok || method < -2 || method >= 7) return;
+      a.pred_method = (int8_t)method; a.have_scheme = 0; a.pred_transform = -1;
+      if (method != -2) {
+        const int tt = (int8_t)r.u8();
+        if (!r.ok || tt < -1 || tt >= 4) return;
+        a.pred_transform = (int8_t)tt;
+        a.have_scheme = A.seq_type == 3 ? (tt == 2 || tt == 3) : (tt == 1);
+      }
+      const uint32_t compressed = r.u8();
+      if (!r.ok) return;
+      if (compressed > 0) {
+        a.source = SRC_RAW;
+        if (num_values > 0) {
+          const uint32_t scheme = r.u8();
+          if (!r.ok || scheme != 1) return;                       // tagged: the host sees no further
+          const uint32_t mbl = r.u8();
+          if (!r.ok || mbl < 1 || mbl > 18) return;
+          a.precision_bits = (uint8_t)dsa::rans_precision_bits(mbl);
+          const uint64_t ns = r.varint();
+          if (!r.ok || ns < 1 || ns > (1u << 20)) return;
+          a.num_symbols = (uint32_t)ns;
+          a.off_table = (uint32_t)r.pos;
+          uint32_t nz = 0;                                        // (skip_prob_table, dsa_common.h)
+          for (uint64_t i = 0; i < ns && r.ok; ++i) {
+            const uint32_t pd = r.u8(), token = pd & 3;
+            if (token == 3) { const uint64_t off = pd >> 2; if (i + off >= ns) return; i += off; }
+            else { uint32_t pr = pd >> 2; for (uint32_t k = 0; k < token; ++k) pr |= r.u8() << (8 * (k + 1) - 2); nz += pr != 0; }
+          }
+          a.num_distinct = nz;
+          const uint64_t size = r.varint();
+          a.off_rans = (uint32_t)r.pos;
+          r.skip(size);
+          if (!r.ok || size < 1) return;
+          a.size_rans = (uint32_t)size;
+        }
+      } else {
+        a.source = SRC_FIXED;
+        const uint32_t nb = r.u8();
+        if (!r.ok || nb < 1 || nb > 4) return;
+        a.fixed_bytes = (uint8_t)nb;
+        r.skip((uint64_t)nb * num_values);
+        if (!r.ok) return;
+      }
+      if (a.have_scheme) {
+        if (a.pred_transform == 1) {
+          if (!(method == 0 || method == 1 || method == 4 || method == 5 || method == 6)) return;     // MultiParallelogram: the general path; others: refused
+          a.pred_kind = method == 1 ? 1 : (method == 5 ? 3 : (method == 4 ? 4 : 0));
+          if (a.pred_kind == 4)
+            for (int k = 0; k < 4; ++k) { const uint64_t nf = r.varint(); if (!r.ok || (nf > 0 && !rabs_skip())) return; }
+          if (a.pred_kind == 3) { (void)r.u32(); if (!rabs_skip()) return; }
+          a.wrap_min = (int32_t)r.u32(); a.wrap_max = (int32_t)r.u32();
+          if (!r.ok || a.wrap_min > a.wrap_max || (int64_t)a.wrap_max - (int64_t)a.wrap_min >= 0x7FFFFFFF) return;
+        } else {
+          a.pred_kind = method == 6 ? 2 : 0;
+          a.oct_max_q = (int32_t)r.u32();
+          if (a.pred_transform == 3) (void)r.u32();
+          if (!r.ok) return;
+          if (a.pred_kind == 2 && !rabs_skip()) return;
+        }
+      }
+    }
+    for (uint32_t ai = dec_first[d]; ai < dec_first[d + 1]; ++ai) {
+      AttrDesc &a = m.walk[ai];
+      if (a.seq_type == 2) { r.skip(4ull * a.nc + 4); a.q_bits = (uint8_t)r.u8(); }
+      else if (a.seq_type == 3) a.q_bits = (uint8_t)r.u8();
+      if (!r.ok) return;
+    }
+  }
+  m.walk_ok = true;
+}
+
+// The need bits of a mesh (dsa_needs.h) from the needs walk and the mesh's placement, for the launch flags of a decode.  Every bit,
+// which is the whole schedule, where the host cannot see: a failed or unfinished walk, a general-path mesh, a point cloud, a
+// sequential mesh, corner attributes (their entry counts are k_seam_tables'), a table that may come from the batch pool.
+static uint32_t host_mesh_needs(const HostMesh &h, const MeshLayout &L, uint32_t flags) {
+  if (h.status != 0 || !h.walk_ok || h.general || h.seamed || h.walk.size() != h.atts.size()) return NEED_ALL;
+  uint32_t nd = 0;
+  for (uint32_t ai = 0; ai < (uint32_t)h.walk.size(); ++ai) {
+    AttrDesc a = h.walk[ai];
+    if (a.source == SRC_RAW && a.num_symbols > SYM_MAX_LDS) {       // the cumulative table k_locate reserves (dsa_locate.h)
+      const uint64_t bytes = (((uint64_t)a.num_symbols + 2) * 4 + 15) & ~15ull;
+      if (bytes > L.out_cap[ai]) return NEED_ALL;
+      a.table = 1;
+    }
+    nd |= dsa::attr_needs(a, L, ai, flags);
+  }
+  return nd;
 }
 
 static inline uint64_t align_up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }

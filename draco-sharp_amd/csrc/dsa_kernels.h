@@ -28,6 +28,7 @@
 
 #include "dsa_common.h"
 #include "dsa_locate.h"
+#include "dsa_needs.h"
 #ifdef DSA_EXPERIMENTS
 #include "dsa_lanes.h"       // lane-per-chain kernels: bit-exact, measured slower on every workload tried (profiles/README.md); not in the product library
 #else
@@ -57,31 +58,9 @@ __device__ __forceinline__ T *uni_ptr(T *p) {
   return (T *)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v));
 }
 __device__ __forceinline__ uint32_t rdlane(uint32_t v, uint32_t l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l); }
-// The symbol kernels are launched twice when the batch is decoded on four streams: once for the attributes whose prediction
-// waits for the traversal (parallelogram: "late") and once, on a stream of higher priority that goes on to predict and
-// dequantise them, for those whose prediction does not ("early": difference, octahedral delta, none).
-#define SYM_WIDE 0x800u        // k_symbols_wide is part of the launch set (DSA_SYM_WIDE=0: its streams stay with the LDS tiers)
-#define SYM_EARLY_ONLY 0x100u
-#define SYM_LATE_ONLY 0x200u
-#define SYM_CORNER 0x1000u     // the launch for corner attributes (behind k_seam_tables, which counts their entries); every other launch skips them
-// late prediction of a batch with corner attributes, in two launches: what only waits for the position traversal / what waits for
-// the seam tables and the attribute traversals as well
-#define PRED_FRONT 0x10000u
-#define PRED_BEHIND 0x20000u
-__device__ __forceinline__ bool att_behind_tables(const AttrDesc &a) { return a.corner_data != 0 || a.late_located != 0; }
-__device__ __forceinline__ bool att_is_late(const AttrDesc &a) { return (a.have_scheme && a.pred_kind != 0) || att_behind_tables(a); }
-#define PW_FLAG 4u             // DSA_LANES bit 2: wrap schemes by k_predict_wrap (default on)
+// (the launch flags SYM_* / PRED_* / PW_FLAG / OS_FLAG and the predicates the kernels select their work by: dsa_needs.h)
 #define LATE_HANDOFF 0x40000u  // late attributes are predicted by the second of their two producers to finish (late_handoff below)
 __device__ __forceinline__ void late_handoff(uint8_t *arena, const MeshLayout &L, MeshDesc *D, uint32_t ai, uint32_t flags, uint32_t bit);
-__device__ __forceinline__ bool pred_filtered(const AttrDesc &a, uint32_t flags) {
-  return ((flags & PRED_FRONT) && att_behind_tables(a)) || ((flags & PRED_BEHIND) && !att_behind_tables(a));
-}
-__device__ __forceinline__ bool sym_filtered(const AttrDesc &a, uint32_t flags) {
-  if (att_behind_tables(a)) return !(flags & SYM_CORNER);
-  if (flags & SYM_CORNER) return true;
-  const bool late = a.have_scheme && a.pred_kind != 0;      // parallelogram, geometric normal, texture coordinates: after the traversal
-  return ((flags & SYM_EARLY_ONLY) && late) || ((flags & SYM_LATE_ONLY) && !late);
-}
 __device__ __forceinline__ uint64_t clk() { return __builtin_amdgcn_s_memtime(); }
 __device__ __forceinline__ uint64_t realclk() { return __builtin_amdgcn_s_memrealtime(); }   // constant 100 MHz
 // number of leading lanes (from lane 0) whose predicate is set
@@ -1996,8 +1975,6 @@ __device__ __forceinline__ void rans_decode_serial(MeshDesc *D, const uint8_t *s
 // every position; which symbol a slot belongs to is looked up afterwards by all 64 lanes in parallel
 // (slot -> symbol table in the attribute's scratch), fused with the zig-zag step.
 typedef uint32_t v32u __attribute__((ext_vector_type(32)));   // largest vector the backend indexes through M0
-#define REG_MAX_SYMS 4096     // a 12-bit-precision table has 4096 slots: no more symbols than that can have a frequency
-#define WIDE_MAX_SYMS 2048    // k_symbols_wide: 32 registers of 64 {cumulative, frequency} words
 
 // SYM_EARLY_FUSE (option, off by default): the wave that decoded the symbols of an "early" attribute (its prediction needs no
 // traversal data) goes on to predict and dequantise it -- what k_predict / k_predict_wrap / k_finalize of phase 0 do behind the
@@ -2031,7 +2008,6 @@ __device__ __forceinline__ void early_tail(uint8_t *arena, const MeshLayout &L, 
 // before the traversals end; the traversals end three before the last texture-coordinate streams), in the shadow of the other
 // meshes' work, and the k_predict_wrap launch behind everything finds little left.  `bit`: 1 = corrections, 2 = order and operands.
 // Release / acquire at agent scope around the flag: the two waves may sit on different XCDs (an L2 each).
-__device__ __forceinline__ bool wrap_fast_ok(const AttrDesc &a, uint32_t flags);
 __device__ __forceinline__ void late_handoff(uint8_t *arena, const MeshLayout &L, MeshDesc *D, uint32_t ai, uint32_t flags, uint32_t bit) {
   if (!(flags & LATE_HANDOFF) || D->general) return;
   AttrDesc &a = D->att[ai];
@@ -2089,9 +2065,7 @@ __device__ __forceinline__ void reg_decode_stream(uint8_t *arena, const MeshLayo
   } else {
     if (lanes::ln_sym_eligible(a, L, ai, flags)) return;             // k_symbols_lanes
     if (sym_filtered(a, flags)) return;                              // the other launch of the early / late pair
-    // one non-zero symbol = a frequency of 4096, which the packed {freq, rem - cum} word cannot hold: k_symbols<T> takes it
-    if (a.source != SRC_RAW || a.precision_bits != 12 || a.num_symbols > REG_MAX_SYMS || a.num_distinct <= 1) return;
-    if (L.out_cap[ai] < 4096 * 6 + REG_MAX_SYMS * 4) return;      // scratch for the tables (k_symbols<T> takes the stream instead)
+    if (!sym_reg_eligible(a, L, ai)) return;                         // k_symbols_wide / k_symbols<T> take the stream instead
     scratch = arena + L.out[ai];
   }
   const uint8_t *stream = arena + L.stream;
@@ -2351,20 +2325,7 @@ __global__ __launch_bounds__(WAVE, 6) void k_valence_lists(uint8_t *arena, const
 // Launched once per tier so that the LDS footprint of the cumulative table does not cap occupancy:
 //   TIER 0: alphabets <= 64 (table in one register per lane) + tagged / fixed-width sources
 //   TIER 1: alphabets <= 960      TIER 2: alphabets <= SYM_MAX_LDS and the large-alphabet fallback
-// Which raw streams k_symbols_reg takes (12-bit precision, at most 4096 symbols more than one of which occurs, table scratch in the attribute's output region).
-__device__ __forceinline__ bool sym_reg_eligible(const AttrDesc &a, const MeshLayout &L, uint32_t ai) {
-  return a.source == SRC_RAW && a.precision_bits == 12 && a.num_symbols <= REG_MAX_SYMS && a.num_distinct > 1 &&
-         L.out_cap[ai] >= 4096 * 6 + REG_MAX_SYMS * 4;
-}
-// Which raw streams k_symbols_wide takes: any precision, at most 2048 symbols to search -- those of the alphabet, or, for a sparse
-// large alphabet (14-bit positions: 16 384 ids, about 2 000 used), its non-zero ones -- and room for the tables in global memory.
-__device__ __forceinline__ bool sym_wide_eligible(const AttrDesc &a, const MeshLayout &L, uint32_t ai) {
-  if (a.source != SRC_RAW || a.num_distinct <= 1 || sym_reg_eligible(a, L, ai)) return false;
-  const bool compact = a.num_symbols > SYM_MAX_LDS;
-  const uint32_t nse = compact ? a.num_distinct : a.num_symbols;
-  if (nse <= 64 || nse > WIDE_MAX_SYMS || a.precision_bits > 16) return false;     // {cum, freq} packed in 16 + 16 bits
-  return compact ? (a.table != 0 && 2ull * nse + 1 <= (unsigned long long)a.num_symbols + 2) : (L.out_cap[ai] >= 4ull * (nse + 1));
-}
+// (which raw streams k_symbols_reg and k_symbols_wide take: sym_reg_eligible, sym_wide_eligible in dsa_needs.h)
 
 // =========================================================================
 // k_symbols_wide: rANS decode of raw streams of any precision whose search table (<= 2048 cumulative frequencies) fits the
@@ -2659,17 +2620,8 @@ __device__ __forceinline__ void symbols_tier_item(uint8_t *arena, const MeshLayo
   if (a.source == SRC_BYTES) return;
   if (lanes::ln_sym_eligible(a, L, ai, flags)) return;             // k_symbols_lanes
   if (sym_filtered(a, flags)) return;                              // the other launch of the early / late pair
-  // a sparse large alphabet (14-bit positions: 16 384 ids, a few thousand of them used) is searched through its non-zero
-  // symbols; the table k_locate reserved for the serial fallback holds the compact -> symbol map instead
-  const bool compact = a.source == SRC_RAW && a.num_symbols > SYM_MAX_LDS && a.num_distinct <= SYM_MAX_LDS && a.num_distinct >= 1 && a.table != 0;
-  {
-    const uint32_t ns = a.source == SRC_RAW ? a.num_symbols : 0u;
-    if (sym_reg_eligible(a, L, ai)) return;    // k_symbols_reg
-    if ((flags & SYM_WIDE) && sym_wide_eligible(a, L, ai)) return;   // k_symbols_wide
-    const uint32_t nse = compact ? a.num_distinct : ns;
-    const int tier = nse <= 64 ? 0 : (nse <= 960 ? 1 : 2);
-    if (tier != TIER) return;
-  }
+  const bool compact = sym_tier_compact(a);
+  if (sym_tier_of(a, L, ai, flags) != TIER) return;                // another tier, k_symbols_reg or k_symbols_wide
   const uint8_t *s = arena + L.stream;
   uint32_t *work = (uint32_t *)(arena + L.work[ai]);
   const uint32_t lane = lane_id();
@@ -2757,22 +2709,11 @@ __global__ __launch_bounds__(WAVE) void k_register_gate() { asm volatile("v_mov_
 __device__ __forceinline__ uint32_t addmod(uint32_t a, uint32_t b, uint32_t m) { uint32_t r = a + b; return r >= m ? r - m : r; }
 // phase 0: schemes that need no traversal data (difference / octahedral delta) -- launched behind the symbol
 // kernels on their stream; phase 1: parallelogram schemes, after the traversal.
-__device__ __forceinline__ bool wrap_fast_ok(const AttrDesc &a, uint32_t flags);
-__device__ __forceinline__ bool pw_dequant_fused(const AttrDesc &a, uint32_t flags);
-#define OS_FLAG 16u   // the canonicalised octahedral delta is k_predict_oct_streams' (crowded batches)
-__device__ __forceinline__ bool oct_stream_eligible(const AttrDesc &a) {
-  return a.have_scheme && a.source != SRC_BYTES && a.pred_transform == 3 && a.pred_kind == 0 && a.corner_data == 0 && a.num_entries != 0 && !a.early_done &&
-         a.oct_max_q >= 3 && a.oct_max_q < (1 << OCT_PK_MAX_BITS);      // the packed step's range; finer octahedra stay with k_predict
-}
 // The body of k_predict for one attribute on one wave (also the tail of an entropy-decode wave, see early_tail).
 __device__ __forceinline__ void predict_wave(uint8_t *arena, const MeshLayout &L, MeshDesc *D, uint32_t ai, uint32_t phase, uint32_t flags) {
   const AttrDesc &a = D->att[ai];
-  if (!a.have_scheme || a.source == SRC_BYTES) return;
-  if (wrap_fast_ok(a, flags)) return;                    // k_predict_wrap
   if (lanes::ln_oct_eligible(a, flags)) return;          // k_predict_oct_lanes
-  if ((flags & OS_FLAG) && oct_stream_eligible(a)) return;   // k_predict_oct_streams
-  if (a.pred_kind == 2 || a.pred_kind == 3 || a.pred_kind == 4) return;            // k_predict_geometric, k_texcoords, k_multipara
-  if (att_is_late(a) != (phase == 1) || pred_filtered(a, flags)) return;
+  if (predict_phase_of(a, flags) != (phase == 1 ? 1 : 0) || pred_filtered(a, flags)) return;      // another kernel's, or the other launch's
   int32_t *w = (int32_t *)(arena + L.work[ai]);
   const uint32_t nc = a.nc_portable, entries = a.num_entries;
   const uint32_t lane = lane_id();
@@ -3102,13 +3043,7 @@ __global__ __launch_bounds__(WAVE, 8) void k_predict_oct_streams(uint8_t *arena,
 // finished entries, lanes 1.. join while their prediction is "previous entry + (finished - finished)", every lane
 // re-evaluates the sequential step from its neighbour's value and the run is cut at the first disagreement.
 // =========================================================================
-__device__ __forceinline__ bool pw_dequant_fused(const AttrDesc &a, uint32_t flags) {
-  return wrap_fast_ok(a, flags) && a.seq_type == 2 && a.nc == a.nc_portable && a.q_bits >= 1 && a.q_bits <= 30;
-}
-__device__ __forceinline__ bool wrap_fast_ok(const AttrDesc &a, uint32_t flags) {
-  return (flags & PW_FLAG) && a.have_scheme && a.source != SRC_BYTES && a.pred_transform == 1 && a.pred_kind != 3 && a.pred_kind != 4 && a.nc_portable >= 1 && a.nc_portable <= 4 &&
-         (uint32_t)(1 + a.wrap_max - a.wrap_min) < (1u << 25) && a.num_entries != 0;
-}
+// (wrap_fast_ok, pw_dequant_fused: dsa_needs.h)
 // inclusive wave64 prefix sum, one v_add with a DPP operand per step where the backend fuses them
 __device__ __forceinline__ uint32_t wave_incl_sum(uint32_t x) {
   x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xF, 0xF, true);    // row_shr:1 (lanes without a source add 0)
@@ -3584,12 +3519,19 @@ __global__ __launch_bounds__(256) void k_point_maps(uint8_t *arena, const MeshLa
 }
 
 // k_seal: last kernel of a decode, one thread per mesh: the census of linked corners against the links made, and the seam
-// bits found by k_conn_checks against the number of interior edges.
-__global__ __launch_bounds__(256) void k_seal(MeshDesc *descs, uint32_t n) {
+// bits found by k_conn_checks against the number of interior edges.  It also has the last word on the pruned schedule: `launched`
+// are the kernel groups dsa_batch_decode queued (chosen from the host parse), `flags` the launch flags they ran with; the groups
+// the mesh needed follow from its finished descriptor through the predicates the kernels themselves used (mesh_needs), and a mesh
+// with a need outside `launched` does not end with status 0 -- it goes to the general path (dsa_batch_wait decodes it again in a
+// batch that launches everything), or fails with DSA_SITE_NEEDS where that path does not apply.
+__global__ __launch_bounds__(256) void k_seal(MeshDesc *descs, const MeshLayout *layouts, uint32_t n, uint32_t flags, uint32_t launched) {
   const uint32_t mesh = blockIdx.x * blockDim.x + threadIdx.x;
   if (mesh >= n) return;
   MeshDesc *D = &descs[mesh];
   if (status_of(D) != ST_OK) return;
+  const uint32_t needs = mesh_needs(*D, layouts[mesh], flags);
+  D->needs = needs;
+  if (!needs_covered(needs, launched)) { fail(D, ST_NOTIMPL, D->encoder_type != 0 ? DSA_SITE_RETRY_GENERAL : DSA_SITE_NEEDS); return; }
   if (D->general) return;                              // the general path's phase 2 has compared its own census
   if (D->values_pending) { fail(D, ST_INVALID, 159); return; }          // (the walk of the attribute sections did not get to its end)
   if (__hip_atomic_load(&D->linked_corners, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != D->interior_corners) { fail(D, ST_INVALID, 263); return; }

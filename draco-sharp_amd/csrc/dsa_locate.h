@@ -4,6 +4,7 @@
 // per-lane bodies under ASan (test infrastructure; the product library runs it only as the kernel k_locate).
 #pragma once
 #include "dsa_common.h"
+#include "dsa_needs.h"
 
 namespace dsa {
 
@@ -17,7 +18,7 @@ static inline unsigned long long atomicAdd(unsigned long long *p, unsigned long 
 // (their bit section has no length prefix), tags stored as bytes in the
 // attribute's output buffer for k_symbols.
 #define LOC_MAX_TAGS 64
-#define SYM_MAX_LDS 4032   // 63 blocks of 64 cumulative entries searched in LDS by k_symbols
+// (SYM_MAX_LDS, the largest alphabet k_symbols searches in LDS: dsa_needs.h)
 #define LOC_LUT_SLOTS 4096   // slot table of a tag stream (12-bit precision)
 #define LOC_LDS_WORDS (LOC_LUT_SLOTS / 4 + 4 * LN_RING_CHUNKS + LN_BLOCK / 4)   // one byte per slot + byte ring + the tags of one block
 

@@ -109,6 +109,7 @@ struct MeshDesc {
   uint8_t seam_tables_done;    // k_seam_tables has counted the vertices of the attribute tables (seam_nv)
   uint8_t pad_seam;
   uint32_t seam_nv[DSA_MAX_ATT_DATA];      // vertices of attribute data d's corner table (= entries of its decoder), by k_seam_tables
+  uint32_t needs;          // k_seal: the kernel groups of the decode schedule that had work for this mesh (NEED_*, dsa_needs.h)
   uint32_t dbg[20];        // diagnostics of the per-mesh kernels (tools/dbg_phases.py, bench.py): s_memtime deltas between phases;
                            // k_connectivity: [13] its s_memtime ticks, [14] its start and [15] its duration in s_memrealtime ticks
                            // (100 MHz); k_traverse: [6] ticks, [16] start, [17] duration: ticks / duration = the shader clock

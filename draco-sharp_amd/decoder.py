@@ -395,6 +395,18 @@ class Batch:
             _raise(st, self.ctx.error())
         return out[: written.value // out.itemsize]
 
+    def schedule_needs(self, i):
+        """The pruned schedule of the batch's most recent decode as mesh i saw it (dsa_batch_copy_debug 7; bits: NEED_* of
+        csrc/dsa_needs.h): {"host": the kernel groups the host parse asked for on the mesh's behalf, "device": those its
+        finished descriptor needed (k_seal; 0 for a mesh that failed), "launched": the groups the decode queued,
+        "batch": the host's mask for the whole batch}."""
+        v = self.debug_array(i, 7, np.uint32, 4)
+        return {"host": int(v[0]), "device": int(v[1]), "launched": int(v[2]), "batch": int(v[3])}
+
+    def schedule_note(self):
+        """Which kernel groups the batch's most recent decode left out, in words (dsa_batch_copy_debug 8)."""
+        return self.debug_array(0, 8, np.uint8, 1024).tobytes().decode() if self.n else ""
+
     def result(self, i):
         """Draco object of mesh i; raises what the reference would for a bad stream."""
         L = self._L

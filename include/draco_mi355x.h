@@ -197,7 +197,13 @@ dsa_status dsa_batch_copy_metadata(const dsa_batch *batch, uint32_t mesh, uint8_
  *         duration of the connectivity and the traversal wave in s_memrealtime ticks: readable for failed meshes too),
  *       5 uint32[DSA_MAX_ATTRIBUTES][4] per attribute {symbol source, alphabet size, rANS precision bits (tagged symbols: 1 where
  *         k_tags decoded the tag stream, 0 where the stream walk did), rANS payload bytes},
- *       6 the traversal trace of a -DDSA_TRAV_TRACE build. */
+ *       6 the traversal trace of a -DDSA_TRAV_TRACE build,
+ *       7 uint32[4] the pruned schedule of the batch's most recent decode as this mesh saw it, in the NEED_* bits of
+ *         csrc/dsa_needs.h: {kernel groups the host parse asked for on the mesh's behalf, groups the mesh's finished descriptor
+ *         needed (k_seal; 0 for a failed mesh), groups the decode launched, the host's mask for the whole batch} -- the second is
+ *         a subset of the first, and a mesh with a need outside the third does not end with status 0,
+ *       8 char[] the same in words: the kernel groups that decode left out (not terminated; `mesh` is ignored).
+ *       (7 and 8 describe this batch's decode also for a mesh that was handed to the general path.) */
 dsa_status dsa_batch_copy_debug(const dsa_batch *batch, uint32_t mesh, int what, void *dst, size_t dst_bytes, size_t *written);
 
 /* Per-stage device time of the last dsa_batch_decode, in ms (HIP events on the
@@ -214,7 +220,9 @@ dsa_status dsa_batch_kernel_times(const dsa_batch *batch, float *ms, const char 
 dsa_status dsa_context_trim(dsa_context *ctx);
 /* What the context found when it checked the assumptions its kernel schedule rests on (static string owned by the context): the
  * register counts of the kernels whose occupancy the late symbol launch of a crowded batch is timed by, and whether that
- * mechanism (k_register_gate) is in use or was left out because the counts of this build no longer add up. */
+ * mechanism (k_register_gate) is in use or was left out because the counts of this build no longer add up.  Behind it, after a
+ * "; ", the kernel groups the context's most recent decode left out because the host parse found no mesh of the batch that needs
+ * them (DSA_PRUNE=0 in the environment: nothing is left out); that part changes with every dsa_batch_decode on the context. */
 const char *dsa_context_schedule_note(const dsa_context *ctx);
 
 /* ------------------------------------------------------------------ encode direction
