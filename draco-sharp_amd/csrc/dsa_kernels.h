@@ -2039,11 +2039,27 @@ __device__ __forceinline__ void late_handoff(uint8_t *arena, const MeshLayout &L
 #define REG_TAGS 1
 #define REG_VLIST 2
 #define REG_SCRATCH_BYTES (4096u * 6u + REG_MAX_SYMS * 4u)
+// -DDSA_SYM_STAMPS (diagnostic builds, tools/sym_phases.py): where a k_symbols_reg wave spends its life, in units of 1024 shader
+// clocks, as 16-bit halves of the dbg slots k_chain leaves alone ([10] [11] [12] [18] [19]): phase p (0 set-up: tables and initial
+// state, 1 block loop, 2 what follows it up to early_tail) of attribute ai < 3 is half-word 3 p + ai of those five slots.
+#ifdef DSA_SYM_STAMPS
+#define REG_STAMP_BEGIN() uint64_t st_t = clk()
+#define REG_STAMP(p) { const uint64_t t_ = clk(); if (ATTR && ai < 3 && lane_id() == 0) { const uint32_t k_ = 3u * (p) + ai; \
+    ((uint16_t *)D->dbg)[k_ < 6 ? 20 + k_ : 30 + k_] = (uint16_t)((t_ - st_t) >> 10 > 65535 ? 65535 : (t_ - st_t) >> 10); } st_t = t_; }
+#else
+#define REG_STAMP_BEGIN()
+#define REG_STAMP(p)
+#endif
+// symbol -> correction: zig-zag, unless the transform's corrections are positive (D-4)
+__device__ __forceinline__ uint32_t reg_final_symbol(uint32_t v, bool positive) {
+  return positive ? v : ((v & 1u) ? (uint32_t)(-(int32_t)(v >> 1) - 1) : (v >> 1));
+}
 template <int MODE>
 __device__ __forceinline__ void reg_decode_stream(uint8_t *arena, const MeshLayout &L, MeshDesc *D, uint32_t ai, uint32_t flags) {
-  constexpr bool TAGS = MODE == REG_TAGS, VLIST = MODE == REG_VLIST;
+  constexpr bool TAGS = MODE == REG_TAGS, VLIST = MODE == REG_VLIST, ATTR = MODE == REG_ATTR;
   AttrDesc &a = D->att[VLIST ? 0u : ai];
   uint8_t *scratch;
+  REG_STAMP_BEGIN();
   uint32_t st_off_table = a.off_table, st_off_rans = a.off_rans, st_size_rans = a.size_rans, st_nsym = a.num_symbols;
   uint32_t st_values = a.num_entries * (TAGS ? 1u : (uint32_t)a.nc_portable);
   uint32_t *out = (uint32_t *)(arena + L.work[VLIST ? 0u : ai]);
@@ -2137,10 +2153,23 @@ __device__ __forceinline__ void reg_decode_stream(uint8_t *arena, const MeshLayo
   const uint32_t mis = (uint32_t)((L.stream + st_off_rans) & 3u);
   const uint32_t *abuf = (const uint32_t *)(arena + (L.stream + st_off_rans - mis));
   uint32_t chunk = 0x7FFFFFFFu, W = 0;
+  uint32_t next_chunk = 0x7FFFFFFFu, Wn = 0;   // the window below W (the stream is consumed from its tail), requested ahead of its use
   uint32_t mine = 0;
+  // REG_ATTR: the symbols of the block before the current one, gathered from slot_sym when that block ended and still on their
+  // way while this one decodes; transformed and stored when this one ends
+  uint32_t pend = 0;
+  const bool positive = ATTR && a.have_scheme && (a.pred_transform == 2 || a.pred_transform == 3);
   WAIT_VM0();
-  // 64 positions per outer iteration; the slot (low 12 bits of the state) of position j is parked in lane j
-  // and stored with one coalesced store.  The per-symbol loop is hand-scheduled (RAnsDecoder.cs:56-65):
+  REG_STAMP(0);
+  // 64 positions per outer iteration; the slot (low 12 bits of the state) of position j is parked in lane j.  REG_TAGS and
+  // REG_VLIST store the slots with one coalesced store and map them to symbols in a pass of their own behind the loop.  REG_ATTR
+  // never stores a slot: at the end of a block it gathers slot_sym[slot] from the register and leaves the load in flight across
+  // the next block (which names v[16:79] and its own operands only); at the end of that block it applies the transform (zig-zag,
+  // unless the corrections are positive, D-4) and stores the final values of the block before -- a full one, only the last block of
+  // a stream is short -- so no wave waits for the gather or reads its output twice.  The compiler places the waits: what counts is
+  // that `pend` and `Wn` are never copied or touched between their load and their use (a copy is a wait), which the order of the
+  // three statements at the end of the block below takes care of; check `make asm` after changing it.
+  // The per-symbol loop is hand-scheduled (RAnsDecoder.cs:56-65):
   //   * the state x and a 4-byte reservoir live in one SGPR pair {res, x}; a renormalisation byte is a
   //     single s_lshl_b64 of the pair (the stream is consumed from its tail, so an aligned little-endian
   //     dword holds the next 4 bytes most-significant first);
@@ -2235,7 +2264,13 @@ __device__ __forceinline__ void reg_decode_stream(uint8_t *arena, const MeshLayo
           else {
             const uint32_t end = off + mis;    // one past the next byte, in abuf coordinates
             const uint32_t d = (end - 1) >> 2, r = end - 4 * d, ch = d >> 6;
-            if (ch != chunk) { chunk = ch; W = abuf[(size_t)ch * 64 + lane]; WAIT_VM0(); }
+            if (ch != chunk) {
+              // a new window is the one requested blocks ago: a register move.  Only the first window of a stream (and one a
+              // single block runs through) is waited for on the spot
+              if (next_chunk == ch) W = Wn;
+              else { W = abuf[(size_t)ch * 64 + lane]; WAIT_VM0(); }
+              chunk = ch;
+            }
             const uint32_t res = rdlane(W, d & 63u) << (8 * (4 - r));
             rc = uni(r < off ? r : off);
             off -= rc;
@@ -2253,7 +2288,18 @@ __device__ __forceinline__ void reg_decode_stream(uint8_t *arena, const MeshLayo
         ++j;
       }
     }
-    if (lane < cnt) out[i0 + lane] = mine;
+    if (ATTR) { if (i0) out[i0 - WAVE + lane] = reg_final_symbol(pend, positive); }
+    else if (lane < cnt) out[i0 + lane] = mine;
+    // the window below the one in use, requested at the end of the block that entered it (behind the use of `pend`, whose wait
+    // would otherwise be this request's as well).  The requests stop at window 0: what lies below it is not the stream's (for
+    // the first stream of a batch, not the arena's)
+    if (chunk != 0x7FFFFFFFu && chunk != 0 && next_chunk != chunk - 1) { next_chunk = chunk - 1; Wn = abuf[next_chunk * 64u + lane]; }
+    if (ATTR) pend = slot_sym[mine & 4095u];   // (lanes past the end of the last block hold slots of positions that are not stored)
+  }
+  REG_STAMP(1);
+  if (ATTR) {                                  // the last block, full or not
+    const uint32_t last = (num_values - 1) & ~(WAVE - 1u);
+    if (lane < num_values - last) out[last + lane] = reg_final_symbol(pend, positive);
   }
   WAIT_VM0();
   __syncthreads();
@@ -2287,12 +2333,7 @@ __device__ __forceinline__ void reg_decode_stream(uint8_t *arena, const MeshLayo
     if (lane == 0) { a.table = (bits & 0x00FFFFFFFFFFFFFFull) | ((uint64_t)(worst > 255u ? 255u : worst) << 56); a.tags_done = 1; }
     return;
   }
-  // 5. slot -> symbol (lane parallel), then zig-zag unless the transform's corrections are positive (D-4)
-  const bool positive = a.have_scheme && (a.pred_transform == 2 || a.pred_transform == 3);
-  for (uint32_t i = lane; i < num_values; i += WAVE) {
-    uint32_t v = slot_sym[out[i] & 4095u];
-    out[i] = positive ? v : ((v & 1u) ? (uint32_t)(-(int32_t)(v >> 1) - 1) : (v >> 1));
-  }
+  REG_STAMP(2);
   early_tail(arena, L, D, ai, flags);
   late_handoff(arena, L, D, ai, flags, 1u);
 }
