@@ -20,6 +20,9 @@
 //                                                stream (dsa_symbol_plan.h, the code the host coder runs)   SymbolEncoding.cs:8-40, RAnsSymbolEncoder.cs:15-123
 //   host  (dsa_encode_host.h)  input checks; at the end the stream layout: bit-packing of the Edgebreaker symbols, table bytes, section order
 //                              (threads over meshes).  DSA_ENC_HOST_PLAN=1: the symbol plans by the host between the two device phases.
+//         (dsa_encode_layout.h) the request of an entry point, the state of a chunk, the per-mesh checks and plans, the arena layout
+// Every entry point fills an EncRequest and calls encode_request; a chunk of it goes through the stages of encode_chunk (or of
+// encode_sequential_chunk, dsa_encode_sequential.h) on a lane.
 // The result is byte-identical to the CPU coder of dsa_encode_host.h (tests/test_gpu_encode.py), hence decodes
 // bit-exactly to the quantised input.
 #pragma once
@@ -27,62 +30,12 @@
 #include <memory>
 #include <thread>
 
-#include "dsa_encode_host.h"
-#include "dsa_encode_conn.h"
-#include "dsa_encode_seams.h"
-#include "dsa_encode_schemes.h"
-#include "dsa_encode_multi.h"
+#include "dsa_encode_layout.h"
 
 namespace dsa {
 
-struct EncStream {                 // one per (mesh, attribute); lives in device memory, mirrored on the host
-  uint64_t src;                    // f32 source values, vertex order, nc_out per vertex
-  uint64_t e2v, ops;               // per mesh: entry -> vertex; i32[3*entries] parallelogram operand entries (next, prev, opposite) or -1
-  uint64_t vals, d, syms, bl;      // i32[nv*nc] vertex order, i32[nv*nc] traversal order, u32[nv*nc] symbols, u8[nv] bit length per entry
-  uint64_t hist_raw;               // u32[hist_cap]
-  uint64_t out_rans, out_bits;     // coded bytes
-  uint64_t prob, cum;              // u32[num_symbols] (filled by the host between the two device phases)
-  uint32_t nv, nc_out, nc, kind;   // nv: entries; kind 0: quantised + wrap, 1: normals (octahedral, canonicalised delta), 2: integers + wrap (src: elements of
-                                   //   type `elem`), 3: a valence context list of the connectivity (syms given, nc 1; no values, no prediction)
-  uint32_t rows, rows_pad;         // value rows of `src` / `vals` (= nv, but for an attribute given per corner: its row count; k_enc_seam_operands sets nv)
-  uint32_t bits, prediction, hist_cap, out_cap;
-  float qmin[4], qrange;
-  int32_t wrap_mn, wrap_mx;
-  uint32_t max_value, overflow;
-  unsigned long long total_bl;
-  uint32_t hist_tag[33];
-  uint32_t method, precision_bits, num_symbols;
-  uint32_t rans_len, bits_len;
-  uint64_t plan_order, plan_tmp;   // u32[table_cap] each: scratch of k_enc_plan
-  uint32_t usbl, plan_status;      // raw scheme: unique-symbols bit length; dsa::plan::PLAN_* of k_enc_plan
-  // prediction 5 (TexCoordsPortable, kind 0) and 6 (GeometricNormal, kind 1): the topology view of dsa_encode_schemes.h (EncTopo)
-  // -- set by the host, for a seamed attribute on the device path by k_enc_seam_topo -> k_enc_corr
-  uint64_t pos_vals, t_c2p, t_c2a, t_opp, t_d2c, t_v2d;
-  uint64_t ori;                    // u8[cap] per entry 0 / 2 / 3 (TexCoordsPortable's branch and orientation) -- k_enc_corr -> k_enc_orient
-  uint64_t flags;                  // u32[(cap + 31) / 32] side bits, bit k of the list: orientations (delta-coded against true, last
-                                   //   entry first; k_enc_orient) or flips (entry order; k_enc_corr) -- -> download (write_rabs)
-  uint32_t t_nc3, num_flags;       // 3F; OUTPUT: bits in `flags`
-  // prediction 2 / 4 (MultiParallelogram, ConstrainedMultiParallelogram; kind 0 and 2; dsa_encode_multi.h): the topology view above;
-  // prediction 4: `ori` holds per entry the parallelograms found and their crease flags (k_enc_multi -> k_enc_crease), `flags` the
-  // four crease lists, list j packed from word cr_at[j] on, cr_n[j] bits (OUTPUT) -- k_enc_crease -> download (write_rabs)
-  uint32_t cr_at[4], cr_n[4];
-  uint32_t pd_want, pad_level;     // pd_want: an attribute given per corner whose decoder takes the prediction-degree order unless it is seamed
-  uint32_t linear, elem;           // linear: entry i is value row i (sequential streams, dsa_encode_sequential.h): `d` is `vals`, no e2v, no gather
-                                   // elem (kind 2): Draco's data type of `src`, 1 int8, 2 uint8, 3 int16, 4 uint16, 5 int32, 6 uint32
-};
-
-// The raw symbol scheme takes symbols below 2^18 (dsa_symbol_plan.h choose_scheme; symbol_stats of the host coder builds no
-// histogram of values beyond): no stream's histogram is larger than this, and a stream whose histogram has this size may hold
-// symbols beyond it (32-bit integer attributes with spread values) -- those are not counted, and k_enc_plan goes the tagged way.
-static const uint32_t ENC_RAW_SYMBOL_LIMIT = 1u << 18, ENC_HIST_CAP_LIMIT = ENC_RAW_SYMBOL_LIMIT + 2u;
-static_assert(ENC_HIST_CAP_LIMIT == EM_HIST_CAP_LIMIT, "k_enc_multi counts symbols like k_enc_corr");
 static const int ENC_PLAN_RAW_BEYOND_LIMIT = 1000;      // plan_status beside dsa::plan::PLAN_*: see enc_plan_message
 static const char *const ENC_RAW_BEYOND_MESSAGE = "symbol_scheme 1 (raw) forced on an integer attribute with symbols of 2^18 and above: the device coder writes those tagged only";
-// hist_cap of an integer attribute whose values (as int32) span lo .. hi: zig-zagged wrapped corrections lie in 0 .. hi - lo + 1
-static inline uint32_t enc_integer_hist_cap(int32_t lo, int32_t hi) {
-  const uint64_t span = (uint64_t)((int64_t)hi - (int64_t)lo) + 3ull;
-  return (uint32_t)(span < ENC_HIST_CAP_LIMIT ? span : ENC_HIST_CAP_LIMIT);
-}
 
 __device__ __forceinline__ uint32_t enc_msb(uint32_t v) { return 31u - (uint32_t)__builtin_clz(v); }
 __device__ __forceinline__ uint32_t enc_zigzag(int32_t v) { return v >= 0 ? (uint32_t)v << 1 : (((uint32_t)(-(v + 1))) << 1) | 1u; }
@@ -523,37 +476,7 @@ __global__ __launch_bounds__(256) void k_enc_unpack(uint8_t *arena, const uint8_
 }  // namespace dsa
 
 // ------------------------------------------------------------------------------------------------ host side
-namespace dsa {
-// Value rows and entries of an attribute in traversal order (entry p: the value of the corner the walk reached it by; ids null:
-// the corner's vertex) and its parallelogram operand entries on table `ct` (MeshPredictionSchemeParallelogramEncoder.cs:35-56).
-template <class CT>
-static void entry_maps(const CT &ct, const synth::Sequence &seq, const uint32_t *ids, std::vector<uint32_t> &e2v, std::vector<int32_t> *ops) {
-  const uint32_t entries = (uint32_t)seq.data_to_corner.size();
-  e2v.resize(entries);
-  if (ops) ops->assign((size_t)3 * entries, -1);
-  for (uint32_t p = 0; p < entries; ++p) {
-    const uint32_t ci = seq.data_to_corner[p];
-    e2v[p] = ids ? ids[ci] : ct.vertex(ci);
-    if (p == 0 || !ops) continue;
-    const uint32_t oci = ct.opposite(ci);
-    if (oci == synth::kInvalid) continue;
-    const int32_t vo = seq.vertex_to_data[ct.vertex(oci)];
-    const int32_t vn = seq.vertex_to_data[ct.vertex(synth::CornerTable::next(oci))];
-    const int32_t vp = seq.vertex_to_data[ct.vertex(synth::CornerTable::prev(oci))];
-    if (vo < (int32_t)p && vn < (int32_t)p && vp < (int32_t)p) { (*ops)[3 * p] = vn; (*ops)[3 * p + 1] = vp; (*ops)[3 * p + 2] = vo; }
-  }
-}
-}  // namespace dsa
-
-struct dsa_encoded {
-  dsa_context *ctx = nullptr;
-  std::vector<std::vector<uint8_t>> streams;
-  std::vector<int32_t> status;
-  std::vector<std::string> messages;
-};
-
 // ---- transfers of a chunk, shared by the chunk functions (encode_chunk below, encode_sequential_chunk of dsa_encode_sequential.h)
-struct EncUpload { uint64_t off; const void *src; size_t bytes; bool narrow; };       // narrow: src is u32[bytes / 2], the staging copy keeps the low halves
 // uploads in pieces through the lane's two pinned staging buffers: host threads fill one while the DMA engine drains the
 // other (a pageable source would be staged by the runtime, one thread, a few GB/s)
 static hipError_t enc_upload(EncLane &lane, uint8_t *arena, hipStream_t st, const std::vector<EncUpload> &ups) {
@@ -584,11 +507,12 @@ static hipError_t enc_upload(EncLane &lane, uint8_t *arena, hipStream_t st, cons
   return hipSuccess;
 }
 // pieces of the arena -> one host buffer (items[k].packed_off filled in); host buffer -> pieces of the arena
-// (with `view`: no copy into `host`; *view points at the pieces in the lane's pinned staging buffer, valid until the gather after next)
-static dsa_status enc_gather(EncLane &lane, const uint8_t *arena, std::vector<dsa::PackItem> &items, std::vector<uint8_t> &host, const uint8_t **view) {
+// (into *host, or with `view` and no `host` without that copy: *view points at the pieces in the lane's pinned staging buffer, valid
+// until the gather after next)
+static dsa_status enc_gather(EncLane &lane, const uint8_t *arena, std::vector<dsa::PackItem> &items, std::vector<uint8_t> *host, const uint8_t **view) {
   uint64_t total = 0;
   for (auto &it : items) { it.packed_off = total; total += ((uint64_t)it.len + 15) & ~15ull; }
-  if (view) *view = nullptr; else host.resize(total);
+  if (view) *view = nullptr; else host->resize(total);
   if (items.empty() || total == 0) return DSA_OK;
   uint8_t *d_packed = nullptr; dsa::PackItem *d_items = nullptr;
   hipError_t e = lane.packed.ensure(total);
@@ -602,7 +526,7 @@ static dsa_status enc_gather(EncLane &lane, const uint8_t *arena, std::vector<ds
   if (e == hipSuccess) e = stg.acquire((size_t)total);
   if (e == hipSuccess) e = hipMemcpyAsync(stg.buf.p, d_packed, total, hipMemcpyDeviceToHost, lane.st);
   if (e == hipSuccess) e = hipStreamSynchronize(lane.st);
-  if (e == hipSuccess) { if (view) *view = stg.buf.p; else hostutil::parallel_memcpy(host.data(), stg.buf.p, (size_t)total); }
+  if (e == hipSuccess) { if (view) *view = stg.buf.p; else hostutil::parallel_memcpy(host->data(), stg.buf.p, (size_t)total); }
   return e == hipSuccess ? DSA_OK : (e == hipErrorOutOfMemory ? DSA_ERR_OUT_OF_MEMORY : DSA_ERR_DEVICE);
 }
 static dsa_status enc_scatter(EncLane &lane, uint8_t *arena, std::vector<dsa::PackItem> &items, const std::vector<uint8_t> &host) {
@@ -620,14 +544,17 @@ static dsa_status enc_scatter(EncLane &lane, uint8_t *arena, std::vector<dsa::Pa
 
 #define ENC_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { return set_err(ctx, e_ == hipErrorOutOfMemory ? DSA_ERR_OUT_OF_MEMORY : DSA_ERR_DEVICE, "%s failed: %s", #call, hipGetErrorString(e_)); } } while (0)
 #define ENC_ST(call) do { dsa_status s_ = (call); if (s_ != DSA_OK) { return set_err(ctx, s_, "%s failed", #call); } } while (0)
+#define ENC_STAGE(call) do { const dsa_status s_ = (call); if (s_ != DSA_OK) return s_; } while (0)      // (the stage has said why)
 // ---- scheme choice and rANS tables by the host from the device statistics (DSA_ENC_HOST_PLAN), between the two device phases:
 // histograms down, plans by threads over streams, tables up.  A stream whose plan fails fails its mesh.
-static dsa_status enc_host_plans(dsa_context *ctx, EncLane &lane, uint8_t *arena, std::vector<dsa::EncStream> &hs, const std::vector<int> &stream_mesh, dsa_encoded *E,
-                                 const synth::Options &opt, std::vector<synth::SymbolPlan> &splans) {
+static dsa_status enc_host_plans(dsa_context *ctx, EncLane &lane, EncChunk &ck) {
+  std::vector<dsa::EncStream> &hs = ck.L.streams;
+  std::vector<synth::SymbolPlan> &splans = ck.splans;
+  const std::vector<int> &stream_mesh = ck.stream_mesh;
+  const synth::Options &opt = ck.opt;
+  dsa_encoded *E = ck.E.get();
   const uint32_t ns = (uint32_t)hs.size();
   std::vector<std::vector<uint32_t>> hists(ns);
-  auto gather = [&](std::vector<dsa::PackItem> &items, std::vector<uint8_t> &host, const uint8_t **view) { return enc_gather(lane, arena, items, host, view); };
-  auto scatter = [&](std::vector<dsa::PackItem> &items, const std::vector<uint8_t> &host) { return enc_scatter(lane, arena, items, host); };
   {
     std::vector<dsa::PackItem> items;
     for (uint32_t s = 0; s < ns; ++s) {
@@ -637,7 +564,7 @@ static dsa_status enc_host_plans(dsa_context *ctx, EncLane &lane, uint8_t *arena
       items.push_back({hs[s].hist_raw, 0, 4u * (hs[s].max_value + 1u), s});
     }
     std::vector<uint8_t> host;
-    ENC_ST(gather(items, host, nullptr));
+    ENC_ST(enc_gather(lane, ck.arena, items, &host, nullptr));
     for (auto &it : items) {
       hists[it.pad].resize(it.len / 4);
       memcpy(hists[it.pad].data(), host.data() + it.packed_off, it.len);
@@ -678,12 +605,15 @@ static dsa_status enc_host_plans(dsa_context *ctx, EncLane &lane, uint8_t *arena
         host.resize((host.size() + 15) & ~(size_t)15);
       }
     }
-    ENC_ST(scatter(items, host));
+    ENC_ST(enc_scatter(lane, ck.arena, items, host));
   }
   return DSA_OK;
 }
 // the plans of k_enc_plan: what it refused, said per mesh
-static void enc_device_plan_errors(const std::vector<dsa::EncStream> &hs, const std::vector<int> &stream_mesh, dsa_encoded *E) {
+static void enc_device_plan_errors(EncChunk &ck) {
+  const std::vector<dsa::EncStream> &hs = ck.L.streams;
+  const std::vector<int> &stream_mesh = ck.stream_mesh;
+  dsa_encoded *E = ck.E.get();
   const uint32_t ns = (uint32_t)hs.size();
   for (uint32_t s = 0; s < ns; ++s) {
     const uint32_t i = (uint32_t)stream_mesh[s];
@@ -696,12 +626,16 @@ static void enc_device_plan_errors(const std::vector<dsa::EncStream> &hs, const 
 // ---- device phase 2: entropy coding (behind the host's plans: k_enc_rans here; k_enc_plan's: it has run), then the coded bytes of
 // every stream, the probability tables k_enc_plan made and the side bits down in one transfer; splans[s].head receives the bytes in
 // front of the payload.
-static dsa_status enc_code_streams(dsa_context *ctx, EncLane &lane, uint8_t *arena, dsa::EncStream *d_streams, std::vector<dsa::EncStream> &hs, const std::vector<int> &stream_mesh,
-                                   const dsa_encoded *E, bool host_plan, std::vector<synth::SymbolPlan> &splans, std::vector<std::vector<uint8_t>> &rans,
-                                   std::vector<std::vector<uint8_t>> &bits, std::vector<std::vector<uint8_t>> &flag_bits,
-                                   std::vector<std::vector<uint8_t>> *crease = nullptr) {
+static dsa_status enc_code_streams(dsa_context *ctx, EncLane &lane, EncChunk &ck) {
+  uint8_t *arena = ck.arena;
+  dsa::EncStream *d_streams = ck.d_streams;
+  std::vector<dsa::EncStream> &hs = ck.L.streams;
+  std::vector<synth::SymbolPlan> &splans = ck.splans;
+  std::vector<std::vector<uint8_t>> &rans = ck.rans, &bits = ck.bits, &flag_bits = ck.flag_bits;
+  const std::vector<int> &stream_mesh = ck.stream_mesh;
+  const dsa_encoded *E = ck.E.get();
+  const bool host_plan = ck.host_plan;
   const uint32_t ns = (uint32_t)hs.size();
-  auto gather = [&](std::vector<dsa::PackItem> &items, std::vector<uint8_t> &host, const uint8_t **view) { return enc_gather(lane, arena, items, host, view); };
   hipStream_t st = lane.st;
   if (host_plan) {
     ENC_TRY(hipMemcpyAsync(d_streams, hs.data(), sizeof(dsa::EncStream) * ns, hipMemcpyHostToDevice, st));
@@ -721,9 +655,8 @@ static dsa_status enc_code_streams(dsa_context *ctx, EncLane &lane, uint8_t *are
     const bool creased = hs[s].kind != 1 && hs[s].prediction == 4;      // (its `flags` hold the four crease lists: below)
     items.push_back({hs[s].flags, 0, hs[s].flags && !creased ? 4u * ((hs[s].num_flags + 31u) / 32u) : 0u, s});
   }
-  std::vector<uint8_t> unused;
   const uint8_t *host = nullptr;
-  ENC_ST(gather(items, unused, &host));
+  ENC_ST(enc_gather(lane, arena, items, nullptr, &host));
   hostutil::parallel_for((uint32_t)(items.size() / 4), [&](uint32_t m) {
     const size_t k = 4 * (size_t)m;
     const uint32_t s = items[k].pad;
@@ -746,21 +679,20 @@ static dsa_status enc_code_streams(dsa_context *ctx, EncLane &lane, uint8_t *are
       pl.coder.write_table(pl.head);
     }
   }, 8);
-  // the crease lists of ConstrainedMultiParallelogram streams ((*crease)[4 s + j]: list j of stream s, a byte per flag): a
+  // the crease lists of ConstrainedMultiParallelogram streams (ck.crease[4 s + j]: list j of stream s, a byte per flag): a
   // transfer of their own, made only when the chunk has such streams
-  if (crease) {
+  if (ck.L.any_crease) {
     std::vector<dsa::PackItem> citems;
     for (uint32_t s = 0; s < ns; ++s) {
       if (hs[s].overflow || E->status[stream_mesh[s]] != DSA_OK || hs[s].kind == 1 || hs[s].prediction != 4 || !hs[s].flags) continue;
       for (uint32_t j = 0; j < 4; ++j) citems.push_back({hs[s].flags + 4ull * hs[s].cr_at[j], 0, 4u * ((hs[s].cr_n[j] + 31u) / 32u), 4u * s + j});
     }
-    std::vector<uint8_t> unused2;
     const uint8_t *chost = nullptr;
-    ENC_ST(gather(citems, unused2, &chost));
+    ENC_ST(enc_gather(lane, arena, citems, nullptr, &chost));
     hostutil::parallel_for((uint32_t)citems.size(), [&](uint32_t m) {
       const dsa::PackItem &it = citems[m];
       const uint32_t cnt = hs[it.pad / 4u].cr_n[it.pad & 3u];
-      std::vector<uint8_t> &b = (*crease)[it.pad];
+      std::vector<uint8_t> &b = ck.crease[it.pad];
       b.resize(cnt);
       const uint32_t *words = (const uint32_t *)(chost + it.packed_off);
       for (uint32_t e = 0; e < cnt; ++e) b[e] = (uint8_t)((words[e >> 5] >> (e & 31u)) & 1u);
@@ -776,28 +708,318 @@ static void enc_put_coded(synth::ByteWriter &bw, const synth::SymbolPlan &pl, co
   if (method == 0) bw.bytes(bits);
 }
 
-extern "C" {
-
-void dsa_encode_default_options(dsa_encode_options *o) {
-  if (!o) return;
-  synth::Options d;
-  o->position_bits = d.pos_bits; o->texcoord_bits = d.uv_bits; o->normal_bits = d.normal_bits;
-  o->single_connectivity = d.single_connectivity; o->symbol_scheme = d.force_scheme; o->compression_level = d.compression_level;
-  o->position_prediction = d.pos_prediction; o->texcoord_prediction = d.uv_prediction;
+// an attribute's coded values as both stream writers carry them (SequentialIntegerAttributeEncoder.cs:55-128): prediction method
+// `method` and its transform, the symbols of stream s, the side bits of the method, the transform's data
+static void enc_write_attribute_values(synth::ByteWriter &bw, const EncChunk &ck, uint32_t s, int8_t method) {
+  const dsa::EncStream &S = ck.L.streams[s];
+  bw.i8(method); bw.i8(S.kind == 1 ? 3 : 1);
+  bw.u8(1);
+  enc_put_coded(bw, ck.splans[s], ck.rans[s], ck.bits[s], S.method);
+  if (S.kind == 0 && S.prediction == 5) { bw.i32((int32_t)ck.flag_bits[s].size()); synth::write_rabs(bw, ck.flag_bits[s]); }      // TexCoordsPortable's orientations
+  if (S.kind != 1 && S.prediction == 4)                    // ...ConstrainedMultiParallelogramEncoder.cs: the four crease lists
+    for (size_t j = 0; j < 4; ++j) { const std::vector<uint8_t> &cl = ck.crease[4 * (size_t)s + j]; bw.varint(cl.size()); if (!cl.empty()) synth::write_rabs(bw, cl); }
+  if (S.kind == 1) { const int32_t max_q = (1 << S.bits) - 1; bw.i32(max_q); bw.i32((max_q - 1) / 2); }
+  else { bw.i32(S.wrap_mn); bw.i32(S.wrap_mx); }
+  if (S.kind == 1 && S.prediction == 6) synth::write_rabs(bw, ck.flag_bits[s]);      // GeometricNormal's flips
+}
+// AttributeQuantizationTransform.cs:123-134 / AttributeOctahedronTransform.cs:44-47 (an integer attribute has no transform to describe)
+static void enc_write_transform(synth::ByteWriter &bw, const dsa::EncStream &S) {
+  if (S.kind == 0) { for (uint32_t c = 0; c < S.nc_out; ++c) bw.f32(S.qmin[c]); bw.f32(S.qrange); bw.u8((uint8_t)S.bits); }
+  else if (S.kind == 1) bw.u8((uint8_t)S.bits);
 }
 
-void dsa_encode_default_options_ex(dsa_encode_options_ex *o) {
-  if (!o) return;
-  memset(o, 0, sizeof(*o));
-  dsa_encode_default_options(&o->base);
+// DSA_ENC_TIMING=1 (diagnostics): wall time of every stage of a chunk on stderr
+struct EncLap {
+  const void *lane;
+  std::chrono::steady_clock::time_point last = std::chrono::steady_clock::now();
+  void operator()(const char *what) {
+    static const bool timing = getenv("DSA_ENC_TIMING") != nullptr;
+    if (!timing) return;
+    const auto now = std::chrono::steady_clock::now();
+    static const auto t_zero = now;
+    fprintf(stderr, "[dsa_encode_batch] lane %p at %9.2f ms: %-28s %8.2f ms\n", lane, std::chrono::duration<double, std::milli>(now - t_zero).count(), what, std::chrono::duration<double, std::milli>(now - last).count());
+    last = now;
+  }
+};
+static dsa_status enc_check_bits(dsa_context *ctx, const dsa_encode_options &o) {
+  if (o.position_bits < 1 || o.position_bits > 20 || o.texcoord_bits < 1 || o.texcoord_bits > 20 || o.normal_bits < 2 || o.normal_bits > 20)
+    return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "quantisation bits out of range (positions/texcoords 1..20, normals 2..20)");
+  return DSA_OK;
+}
+// Both symbol-plan stages and the connectivity are the serial algorithms on one lane per mesh / per stream: a batch takes 150 - 250 ms
+// (connectivity) and about 40 ms (plans) whatever its size, which the host threads beat on a small batch (measured: 64 meshes 84 ms
+// on the host, 128 meshes 252 ms on the device).  Below 256 meshes the host does both (DSA_ENC_HOST_CONN / DSA_ENC_HOST_PLAN = 1
+// or 0 force one or the other; read per call: the tests compare the paths).
+static bool enc_host_choice(const char *name, uint32_t batch_n) { const char *e = getenv(name); return e ? atoi(e) != 0 : batch_n < 256; }
+
+// ---- the stages of encode_chunk, in their order
+// host phase 1: checks, connectivity, traversal order, operand entries (threads over meshes)
+static dsa_status enc_stage_plans(dsa_context *ctx, EncChunk &ck) {
+  // (the quantisation bits of an Edgebreaker call are checked here, per chunk: a call with n = 0 has no chunk and returns DSA_OK
+  // whatever they are, while a sequential call checks them up front -- enc_check_request)
+  if (enc_check_bits(ctx, ck.rq.base()) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+  enc_begin_plans(ck, enc_host_choice("DSA_ENC_HOST_CONN", ck.batch_n), enc_host_choice("DSA_ENC_HOST_PLAN", ck.batch_n));
+  hostutil::parallel_for(ck.n, [&](uint32_t i) { enc_plan_mesh(ck, i); });          // capped thread count, every thread joined on every path (dsa_host_util.h)
+  return DSA_OK;
+}
+// the lane's device memory for the layout, cleared (histograms start at zero); the first uploads (host connectivity: all of them;
+// else phase A, what the walks need) on the chunk's turn on the link; the stream records.  Shared with encode_sequential_chunk.
+static dsa_status enc_stage_uploads(dsa_context *ctx, EncLane &lane, hostutil::TurnGuard &turn, EncChunk &ck) {
+  const EncLayout &L = ck.L;
+  const bool all = ck.host_conn || ck.rq.sequential;
+  ENC_TRY(lane.arena.ensure(L.total_bytes ? L.total_bytes : 256));
+  ENC_TRY(lane.streams.ensure(sizeof(dsa::EncStream) * L.streams.size()));
+  ck.arena = (uint8_t *)lane.arena.p; ck.d_streams = (dsa::EncStream *)lane.streams.p;
+  if (lane.walk_st) ENC_TRY(hipStreamSynchronize(lane.walk_st));     // (idle unless a previous chunk on this lane ended in an error)
+  ENC_TRY(hipMemsetAsync(ck.arena, 0, L.total_bytes, lane.st));
+  turn.acquire_a();
+  ENC_TRY(enc_upload(lane, ck.arena, lane.st, all ? L.uploads : L.uploads_a));
+  if (all) turn.release();
+  ENC_TRY(hipMemcpyAsync(ck.d_streams, L.streams.data(), sizeof(dsa::EncStream) * L.streams.size(), hipMemcpyHostToDevice, lane.st));
+  return DSA_OK;
+}
+// device phase 0 (device connectivity): corner table, Edgebreaker symbols, attribute order (one wave per mesh); meshes that failed
+// the host's checks have F = 0 and no arrays.  The walks on their stream; behind them the rest of the uploads.
+static dsa_status enc_stage_connectivity(dsa_context *ctx, EncLane &lane, hostutil::TurnGuard &turn, EncChunk &ck) {
+  if (ck.host_conn) return DSA_OK;
+  EncLayout &L = ck.L;
+  const uint32_t n = ck.n, nz = (uint32_t)L.seams.size();
+  // meshes to a wave of the walks (k_enc_connectivity: one lane per mesh); DSA_ENC_WALK_LANES = 1 .. 64 for measurements
+  const uint32_t walk_lanes = [&]() { const char *e = getenv("DSA_ENC_WALK_LANES"); const int v = e ? atoi(e) : 0; return (uint32_t)(v >= 1 && v <= 64 ? v : 16); }();
+  hipStream_t st = lane.st;
+  uint8_t *arena = ck.arena;
+  ENC_TRY(lane.conns.ensure(sizeof(dsa::EncConn) * n));
+  dsa::EncConn *d_conns = ck.d_conns = (dsa::EncConn *)lane.conns.p;
+  ENC_TRY(hipMemcpyAsync(d_conns, L.conns.data(), sizeof(dsa::EncConn) * n, hipMemcpyHostToDevice, st));
+  const dim3 gt(std::max(1u, std::min(128u, (3u * L.maxf + 1023u) / 1024u)), n);        // table kernels: blocks per mesh x meshes
+  hipLaunchKernelGGL(dsa::k_enc_table_clear, gt, dim3(256), 0, st, arena, d_conns, n);
+  hipLaunchKernelGGL(dsa::k_enc_table_count, gt, dim3(256), 0, st, arena, d_conns, n);
+  hipLaunchKernelGGL(dsa::k_enc_table_offsets, dim3(n), dim3(WAVE), 0, st, arena, d_conns, n);
+  hipLaunchKernelGGL(dsa::k_enc_table_lists, gt, dim3(256), 0, st, arena, d_conns, n);
+  hipLaunchKernelGGL(dsa::k_enc_table_opposites, gt, dim3(256), 0, st, arena, d_conns, n);
+  hipLaunchKernelGGL(dsa::k_enc_table_corners, gt, dim3(256), 0, st, arena, d_conns, n);
+  // the walks on their stream; the attribute values travel and are quantised meanwhile
+  ENC_TRY(hipEventRecord(lane.tables_done, st));
+  ENC_TRY(hipStreamWaitEvent(lane.walk_st, lane.tables_done, 0));
+  hipLaunchKernelGGL(L.any_valence ? dsa::k_enc_connectivity_timed : dsa::k_enc_connectivity, dim3((n + walk_lanes - 1) / walk_lanes), dim3(WAVE), 0, lane.walk_st, arena, d_conns, n, walk_lanes);
+  if (ck.want_pd) hipLaunchKernelGGL(dsa::k_enc_pd_walk, dim3((n + walk_lanes - 1) / walk_lanes), dim3(WAVE), 0, lane.walk_st, arena, d_conns, n, walk_lanes);
+  if (nz) {
+    // attributes given per corner: seams and attribute vertices beside the connectivity walk, the attribute walks behind it
+    ENC_TRY(lane.seams.ensure(sizeof(dsa::EncSeam) * nz));
+    dsa::EncSeam *d_seams = ck.d_seams = (dsa::EncSeam *)lane.seams.p;
+    ENC_TRY(hipMemcpyAsync(d_seams, L.seams.data(), sizeof(dsa::EncSeam) * nz, hipMemcpyHostToDevice, st));
+    const dim3 gz(gt.x, nz);
+    hipLaunchKernelGGL(dsa::k_enc_seam_edges, gz, dim3(256), 0, st, arena, d_conns, d_seams, nz);
+    hipLaunchKernelGGL(dsa::k_enc_seam_fans, gz, dim3(256), 0, st, arena, d_conns, d_seams, nz);
+    hipLaunchKernelGGL(dsa::k_enc_seam_offsets, dim3(nz), dim3(WAVE), 0, st, arena, d_conns, d_seams, nz);
+    hipLaunchKernelGGL(dsa::k_enc_seam_assign, gz, dim3(256), 0, st, arena, d_conns, d_seams, nz);
+    hipLaunchKernelGGL(dsa::k_enc_seam_records, gz, dim3(256), 0, st, arena, d_conns, d_seams, nz);
+    ENC_TRY(hipEventRecord(lane.seams_done, st));
+    ENC_TRY(hipStreamWaitEvent(lane.walk_st, lane.seams_done, 0));
+    hipLaunchKernelGGL(dsa::k_enc_seam_walk, dim3((nz + walk_lanes - 1) / walk_lanes), dim3(WAVE), 0, lane.walk_st, arena, d_conns, d_seams, nz, walk_lanes);
+  }
+  if (L.any_valence) {
+    // valence context lists behind the walks, on their stream: one more serial pass per mesh, then the lists into six streams
+    hipLaunchKernelGGL(dsa::k_enc_val_init, gt, dim3(256), 0, lane.walk_st, arena, d_conns, n);
+    hipLaunchKernelGGL(dsa::k_enc_valence, dim3((n + walk_lanes - 1) / walk_lanes), dim3(WAVE), 0, lane.walk_st, arena, d_conns, n, walk_lanes);
+    hipLaunchKernelGGL(dsa::k_enc_val_split<dsa::EncStream>, dim3(n), dim3(WAVE), 0, lane.walk_st, arena, d_conns, n, ck.d_streams);
+  }
+  ENC_TRY(hipEventRecord(lane.walk_done, lane.walk_st));
+  turn.release();
+  turn.acquire_b();
+  ENC_TRY(enc_upload(lane, arena, st, L.uploads));
+  turn.release();
+  return DSA_OK;
+}
+// device phase 1: quantise, (device connectivity, behind the walks: operand entries, seam results) order, correct, count; a
+// sequential chunk: the same kernels in point order, and the index symbols; without a host round trip for the plans device phase
+// 2 follows at once; then the records come back.  Shared with encode_sequential_chunk.
+static dsa_status enc_stage_attributes(dsa_context *ctx, EncLane &lane, EncChunk &ck) {
+  EncLayout &L = ck.L;
+  const uint32_t n = ck.n, ns = (uint32_t)L.streams.size(), nz = (uint32_t)L.seams.size(), nx = (uint32_t)L.idx.size();
+  const bool sequential = ck.rq.sequential, device_conn = !ck.host_conn && !sequential;
+  hipStream_t st = lane.st;
+  uint8_t *arena = ck.arena;
+  dsa::EncStream *d_streams = ck.d_streams;
+  dsa::EncConn *d_conns = ck.d_conns;
+  dsa::EncSeam *d_seams = ck.d_seams;
+  const uint32_t gx = std::max(1u, std::min(64u, (L.max_rows + 2047) / 2048));
+  hipLaunchKernelGGL(dsa::k_enc_bounds, dim3(ns), dim3(256), 0, st, arena, d_streams, ns);
+  hipLaunchKernelGGL(dsa::k_enc_quantize, dim3(gx, ns), dim3(256), 0, st, arena, d_streams, ns);
+  if (device_conn) {
+    const dim3 gt(std::max(1u, std::min(128u, (3u * L.maxf + 1023u) / 1024u)), n), gz(gt.x, nz);
+    ENC_TRY(hipStreamWaitEvent(st, lane.walk_done, 0));
+    hipLaunchKernelGGL(dsa::k_enc_operands, gt, dim3(256), 0, st, arena, d_conns, n);
+    if (ck.want_pd) hipLaunchKernelGGL(dsa::k_enc_pd_operands, gt, dim3(256), 0, st, arena, d_conns, n);
+    if (nz) {
+      hipLaunchKernelGGL(dsa::k_enc_seam_operands<dsa::EncStream>, gz, dim3(256), 0, st, arena, d_conns, d_seams, nz, d_streams);
+      if (ck.want_pd) hipLaunchKernelGGL(dsa::k_enc_pd_corner_streams<dsa::EncStream>, gz, dim3(256), 0, st, arena, d_conns, d_seams, nz, d_streams);
+      hipLaunchKernelGGL(dsa::k_enc_seam_topo<dsa::EncStream>, dim3((nz + 255) / 256), dim3(256), 0, st, d_conns, d_seams, nz, d_streams);
+      hipLaunchKernelGGL(dsa::k_enc_seam_rank, gz, dim3(256), 0, st, arena, d_conns, d_seams, nz);
+      hipLaunchKernelGGL(dsa::k_enc_seam_count, gz, dim3(256), 0, st, arena, d_conns, d_seams, nz);
+      hipLaunchKernelGGL(dsa::k_enc_seam_scan, dim3(nz), dim3(WAVE), 0, st, arena, d_conns, d_seams, nz);
+      hipLaunchKernelGGL(dsa::k_enc_seam_bits, gz, dim3(256), 0, st, arena, d_conns, d_seams, nz);
+    }
+  }
+  hipLaunchKernelGGL(dsa::k_enc_gather, dim3(ns), dim3(256), 0, st, arena, d_streams, ns);
+  hipLaunchKernelGGL(dsa::k_enc_corr, dim3(gx, ns), dim3(256), 0, st, arena, d_streams, ns);
+  if (L.any_multi) hipLaunchKernelGGL(dsa::k_enc_multi<dsa::EncStream>, dim3(gx, ns), dim3(256), 0, st, arena, d_streams, ns);
+  if (L.any_crease) hipLaunchKernelGGL(dsa::k_enc_crease<dsa::EncStream>, dim3(ns), dim3(WAVE), 0, st, arena, d_streams, ns);
+  if (!sequential) {
+    hipLaunchKernelGGL(dsa::k_enc_orient, dim3(ns), dim3(WAVE), 0, st, arena, d_streams, ns);
+    hipLaunchKernelGGL(dsa::k_enc_list_stats, dim3(ns), dim3(256), 0, st, arena, d_streams, ns);
+  }
+  if (nx) {                  // compressed indices of sequential meshes: their symbols and statistics
+    ENC_TRY(lane.conns.ensure(sizeof(dsa::EncSeqIdx) * nx));
+    dsa::EncSeqIdx *d_idx = (dsa::EncSeqIdx *)lane.conns.p;
+    ENC_TRY(hipMemcpyAsync(d_idx, L.idx.data(), sizeof(dsa::EncSeqIdx) * nx, hipMemcpyHostToDevice, st));
+    const uint32_t gi = std::max(1u, std::min(64u, (L.max_count + SEQ_SYMBOLS_PER_BLOCK - 1) / SEQ_SYMBOLS_PER_BLOCK));
+    hipLaunchKernelGGL(dsa::k_enc_seq_indices<dsa::EncStream>, dim3(gi, nx), dim3(SEQ_BLOCK), 0, st, arena, d_idx, nx, d_streams);
+  }
+  if (!ck.host_plan) {       // tables by k_enc_plan
+    hipLaunchKernelGGL(dsa::k_enc_plan, dim3((ns + WAVE - 1) / WAVE), dim3(WAVE), 0, st, arena, d_streams, ns, (int)ck.opt.force_scheme, (int)ck.opt.compression_level);
+    hipLaunchKernelGGL(dsa::k_enc_rans, dim3(ns), dim3(WAVE), 0, st, arena, d_streams, ns);
+  }
+  if (sequential) ENC_TRY(hipGetLastError());
+  ENC_TRY(hipMemcpyAsync(L.streams.data(), d_streams, sizeof(dsa::EncStream) * ns, hipMemcpyDeviceToHost, st));
+  if (device_conn) ENC_TRY(hipMemcpyAsync(L.conns.data(), d_conns, sizeof(dsa::EncConn) * n, hipMemcpyDeviceToHost, st));
+  if (nz) ENC_TRY(hipMemcpyAsync(L.seams.data(), d_seams, sizeof(dsa::EncSeam) * nz, hipMemcpyDeviceToHost, st));
+  ENC_TRY(hipStreamSynchronize(st));
+  return DSA_OK;
+}
+// a mesh the device refused: its status, and its attribute streams are not coded
+static void enc_refuse_mesh(EncChunk &ck, uint32_t i, const char *why) {
+  ck.refuse(i, DSA_ERR_INVALID_DATA, why);
+  for (uint32_t s = ck.L.first_stream[i]; s < ck.L.first_stream[i + 1]; ++s) ck.L.streams[s].overflow = 1;
+}
+// device connectivity: what the stream layout needs of it (symbols, start-face bits, split events, two counts) and of the
+// attributes given per corner (which are seamed, and their seam bits) comes down packed; a failed step fails its mesh
+static dsa_status enc_stage_conn_results(dsa_context *ctx, EncLane &lane, EncChunk &ck) {
+  if (ck.host_conn) return DSA_OK;
+  const EncLayout &L = ck.L;
+  std::vector<dsa::PackItem> conn_items;
+  for (uint32_t i = 0; i < ck.n; ++i) {
+    if (!ck.good(i)) continue;
+    const dsa::EncConn &C = L.conns[i];
+    if (C.status != dsa::ENC_OK) { enc_refuse_mesh(ck, i, dsa::enc_conn_message(C.status)); continue; }
+    conn_items.push_back({C.symbols, 0, C.num_symbols, i});
+    conn_items.push_back({C.start_bits, 0, C.num_start_bits, i});
+    conn_items.push_back({C.splits, 0, 12u * C.num_splits, i});
+    ck.plans[i].interior_edges = (int64_t)C.interior_edges;
+  }
+  const uint8_t *conn_host = nullptr;
+  ENC_ST(enc_gather(lane, ck.arena, conn_items, nullptr, &conn_host));
+  hostutil::parallel_for((uint32_t)(conn_items.size() / 3), [&](uint32_t m) {
+    const size_t k = 3 * (size_t)m;
+    const uint32_t i = conn_items[k].pad;
+    const dsa::EncConn &C = L.conns[i];
+    synth::EbResult &eb = ck.plans[i].eb;
+    eb.num_split_symbols = C.num_split_symbols;
+    if (conn_items[k].len) eb.symbols.assign(conn_host + conn_items[k].packed_off, conn_host + conn_items[k].packed_off + conn_items[k].len);
+    if (conn_items[k + 1].len) eb.start_face_bits.assign(conn_host + conn_items[k + 1].packed_off, conn_host + conn_items[k + 1].packed_off + conn_items[k + 1].len);
+    eb.splits.resize(C.num_splits);
+    const uint32_t *sp = C.num_splits ? (const uint32_t *)(conn_host + conn_items[k + 2].packed_off) : nullptr;
+    for (size_t q = 0; q < eb.splits.size(); ++q) eb.splits[q] = {sp[3 * q], sp[3 * q + 1], sp[3 * q + 2]};
+  }, 8);
+  std::vector<dsa::PackItem> seam_items;
+  for (uint32_t z = 0; z < L.seams.size(); ++z) {
+    const dsa::EncSeam &Z = L.seams[z];
+    const uint32_t i = Z.mesh;
+    if (!ck.good(i)) continue;
+    if (Z.status != dsa::ENC_SEAM_OK) { enc_refuse_mesh(ck, i, dsa::enc_seam_message(Z.status)); continue; }
+    synth::MeshPlan &pl = ck.plans[i];
+    if (pl.seamed_given.empty()) pl.seamed_given.assign(pl.atts.size(), 0);
+    pl.seamed_given[Z.stream - L.first_stream[i]] = Z.interior_seams ? 1 : 0;
+    if (Z.interior_seams) seam_items.push_back({Z.bits, 0, 4u * ((L.conns[i].interior_edges + 31u) / 32u), z});
+  }
+  std::vector<uint8_t> seam_host;
+  ENC_ST(enc_gather(lane, ck.arena, seam_items, &seam_host, nullptr));
+  for (auto &it : seam_items) {
+    const dsa::EncSeam &Z = L.seams[it.pad];
+    synth::MeshPlan &pl = ck.plans[Z.mesh];
+    if (!ck.good(Z.mesh)) continue;
+    const uint32_t ne = L.conns[Z.mesh].interior_edges;
+    if (pl.seam_bits_given.empty()) pl.seam_bits_given.assign(pl.atts.size(), std::vector<uint8_t>(ne, 0));
+    std::vector<uint8_t> &b = pl.seam_bits_given[Z.stream - L.first_stream[Z.mesh]];
+    const uint32_t *words = (const uint32_t *)(seam_host.data() + it.packed_off);
+    for (uint32_t e = 0; e < ne; ++e) b[e] = (uint8_t)((words[e >> 5] >> (e & 31u)) & 1u);
+  }
+  return DSA_OK;
+}
+// host phase 2 and device phase 2, shared with encode_sequential_chunk: scheme choice and rANS tables from the device statistics
+// (by the host, or what k_enc_plan said), then the entropy coding and its downloads; `lap`, when given, between the two
+static dsa_status enc_stage_code(dsa_context *ctx, EncLane &lane, EncChunk &ck, EncLap *lap) {
+  const uint32_t ns = (uint32_t)ck.L.streams.size();
+  ck.splans.resize(ns); ck.stream_mesh.assign(ns, 0);
+  for (uint32_t i = 0; i < ck.n; ++i) for (uint32_t s = ck.L.first_stream[i]; s < ck.L.first_stream[i + 1]; ++s) ck.stream_mesh[s] = (int)i;
+  if (ck.host_plan) ENC_STAGE(enc_host_plans(ctx, lane, ck));
+  else enc_device_plan_errors(ck);
+  if (lap) (*lap)("histograms + symbol plans");
+  ck.rans.resize(ns); ck.bits.resize(ns); ck.flag_bits.resize(ns); ck.crease.resize(ck.L.any_crease ? 4 * (size_t)ns : 0);
+  return ns ? enc_code_streams(ctx, lane, ck) : DSA_OK;
+}
+// host phase 3: the stream layout (threads over meshes; write_stream may throw like any part of the host coder)
+static void enc_stage_streams(EncChunk &ck) {
+  const EncLayout &L = ck.L;
+  hostutil::parallel_for(ck.n, [&](uint32_t i) {
+    if (!ck.good(i)) return;
+    for (uint32_t s = L.first_stream[i]; s < L.first_stream[i + 1]; ++s)       // (the context lists included)
+      if (L.streams[s].overflow) return ck.refuse(i, DSA_ERR_INVALID_DATA, "entropy coding failed");
+    synth::ByteWriter w;
+    const uint32_t s0 = L.first_stream[i];
+    try {
+      synth::MeshPlan &pl = ck.plans[i];
+      if (pl.valence) {                                        // the six context lists: their streams follow the attributes'
+        const uint32_t v0 = s0 + (uint32_t)pl.atts.size();
+        pl.ctx_given = true;
+        for (uint32_t k = 0; k < 6; ++k) {
+          pl.ctx_count[k] = L.streams[v0 + k].nv;
+          synth::ByteWriter bw;
+          if (L.streams[v0 + k].nv) enc_put_coded(bw, ck.splans[v0 + k], ck.rans[v0 + k], ck.bits[v0 + k], L.streams[v0 + k].method);
+          pl.ctx_coded[k].swap(bw.d);
+        }
+      }
+      synth::write_stream(w, ck.ins[i], pl,
+        [&](synth::ByteWriter &bw, size_t k) {
+          const dsa::EncStream &S = L.streams[s0 + k];
+          enc_write_attribute_values(bw, ck, s0 + (uint32_t)k, S.kind == 1 ? (int8_t)(S.prediction == 6 ? 6 : 0) : (int8_t)pl.atts[k].prediction);
+        },
+        [&](synth::ByteWriter &bw, size_t k) { enc_write_transform(bw, L.streams[s0 + k]); });
+    } catch (const std::exception &e) { return ck.refuse(i, DSA_ERR_INVALID_DATA, e.what()); }
+    ck.E->streams[i].swap(w.d);
+  });
 }
 
-// All entry points share one chunk path: `meshes` (dsa_encode_batch) or `corners` (dsa_encode_batch_corners / _ex), the other
-// null; `ex` (dsa_encode_batch_ex) the schemes beyond standard Edgebreaker + difference / parallelogram, else null.
-// `attrs` (dsa_encode_attributes_batch, dsa_encode_level_batch): meshes with an attribute list, both others null.
-// multi_parallelogram / traversal_method: the two options of dsa_encode_level_options, 0 from every other entry point.
-static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint32_t batch_n, const dsa_mesh_input *meshes, const dsa_mesh_corner_input *corners, const dsa_mesh_attr_input *attrs, const dsa_encode_options *options, const dsa_encode_options_ex *ex, dsa_encoded **out, int32_t multi_parallelogram = 0, int32_t traversal_method = 0);
-static dsa_status encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_mesh_corner_input *corners, const dsa_mesh_attr_input *attrs, const dsa_encode_options *options, const dsa_encode_options_ex *ex, dsa_encoded **out, int32_t multi_parallelogram = 0, int32_t traversal_method = 0);
+// Meshes base .. base + count of an Edgebreaker request, a chunk of a batch of batch_n, on a lane: the stages above in their order.
+static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, const EncRequest &rq, uint32_t base, uint32_t count, uint32_t batch_n, dsa_encoded **out) {
+  hostutil::TurnGuard turn(lane.upload_turn, lane.upload_chunk);      // (whatever happens below, the other chunks' uploads do not wait for this one's)
+  HIP_TRY(ctx, hipSetDevice(lane.device));
+  EncChunk ck(rq, base, count, batch_n);
+  if (!ck.E) return set_err(ctx, DSA_ERR_OUT_OF_MEMORY, "host allocation failed");
+  ck.E->ctx = ctx;
+  EncLap lap{&lane};
+  ENC_STAGE(enc_stage_plans(ctx, ck));
+  lap("host checks / plan");
+  enc_layout(ck);
+  if (!ck.L.streams.empty()) {
+    ENC_STAGE(enc_stage_uploads(ctx, lane, turn, ck));
+    lap("layout + uploads queued");
+    ENC_STAGE(enc_stage_connectivity(ctx, lane, turn, ck));
+    ENC_STAGE(enc_stage_attributes(ctx, lane, ck));
+    lap("device phases 0 + 1");
+    ENC_STAGE(enc_stage_conn_results(ctx, lane, ck));
+  }
+  lap("connectivity results");
+  ENC_STAGE(enc_stage_code(ctx, lane, ck, &lap));
+  lap("device phase 2 + downloads");
+  enc_stage_streams(ck);
+  lap("stream layout");
+  *out = ck.E.release();
+  return DSA_OK;
+}
+
+#include "dsa_encode_sequential.h"
+
 // The prediction methods the device coder writes; any other value would put a method byte in front of data it does not describe.
 static dsa_status check_schemes(dsa_context *ctx, const dsa_encode_options *o, const dsa_encode_options_ex *ex) {
   if (o && o->position_prediction != 0 && o->position_prediction != 1)
@@ -813,53 +1035,32 @@ static dsa_status check_schemes(dsa_context *ctx, const dsa_encode_options *o, c
     if (ex->reserved[k] != 0) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "dsa_encode_options_ex.reserved[%d] is not zero", k);
   return DSA_OK;
 }
-dsa_status dsa_encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_encode_options *options, dsa_encoded **out) {
-  if (!ctx || !out || (n && !meshes)) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "null argument");
-  if (check_schemes(ctx, options, nullptr) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
-  DSA_GUARD(ctx, encode_batch(ctx, n, meshes, nullptr, nullptr, options, nullptr, out));     // host vectors and threads inside: nothing may unwind into the caller
-}
-dsa_status dsa_encode_batch_corners(dsa_context *ctx, uint32_t n, const dsa_mesh_corner_input *meshes, const dsa_encode_options *options, dsa_encoded **out) {
-  if (!ctx || !out || (n && !meshes)) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "null argument");
-  if (check_schemes(ctx, options, nullptr) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
-  DSA_GUARD(ctx, encode_batch(ctx, n, nullptr, meshes, nullptr, options, nullptr, out));
-}
-dsa_status dsa_encode_batch_ex(dsa_context *ctx, uint32_t n, const dsa_mesh_corner_input *meshes, const dsa_encode_options_ex *options, dsa_encoded **out) {
-  if (!ctx || !out || (n && !meshes)) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "null argument");
-  dsa_encode_options_ex d;
-  dsa_encode_default_options_ex(&d);
-  if (options) d = *options;
-  if (check_schemes(ctx, &d.base, &d) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
-  DSA_GUARD(ctx, encode_batch(ctx, n, nullptr, meshes, nullptr, &d.base, &d, out));
-}
-dsa_status dsa_encode_attributes_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_encode_options_ex *options, dsa_encoded **out) {
-  if (!ctx || !out || (n && !meshes)) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "null argument");
-  dsa_encode_options_ex d;
-  dsa_encode_default_options_ex(&d);
-  if (options) d = *options;
-  if (check_schemes(ctx, &d.base, &d) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
-  DSA_GUARD(ctx, encode_batch(ctx, n, nullptr, nullptr, meshes, &d.base, &d, out));
-}
-void dsa_encode_default_level_options(dsa_encode_level_options *o) {
-  if (!o) return;
-  memset(o, 0, sizeof(*o));
-  dsa_encode_default_options_ex(&o->ex);
-}
-// The levels above the default: MultiParallelogram / ConstrainedMultiParallelogram in place of Parallelogram, prediction-degree
-// attribute order (dsa_encode_multi.h).  With both at 0 this is dsa_encode_attributes_batch.
-dsa_status dsa_encode_level_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_encode_level_options *options, dsa_encoded **out) {
-  if (!ctx || !out || (n && !meshes)) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "null argument");
-  dsa_encode_level_options d;
-  dsa_encode_default_level_options(&d);
-  if (options) d = *options;
-  if (check_schemes(ctx, &d.ex.base, &d.ex) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+// The option check of every entry point: the schemes, then the fields of the level / the sequential options, then their reserved
+// words.  (The prediction fields of `base` do not shape a sequential stream; values dsa_encode_batch refuses are refused all the
+// same.  The quantisation bits of a sequential call are checked here, those of an Edgebreaker call per chunk: enc_stage_plans.)
+static dsa_status enc_check_request(dsa_context *ctx, const EncRequest &rq) {
+  if (check_schemes(ctx, &rq.base(), rq.sequential ? nullptr : &rq.level.ex) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+  if (rq.sequential) {
+    const dsa_encode_sequential_options &d = rq.seq;
+    if (enc_check_bits(ctx, d.base) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+    if (d.geometry != 0 && d.geometry != 1)
+      return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "geometry %d: 1 (triangular mesh) or 0 (point cloud)", (int)d.geometry);
+    if (d.compress_connectivity != 0 && d.compress_connectivity != 1)
+      return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "compress_connectivity %d: 0 (raw indices) or 1 (compressed)", (int)d.compress_connectivity);
+    for (int k = 0; k < 6; ++k)
+      if (d.reserved[k] != 0) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "dsa_encode_sequential_options.reserved[%d] is not zero", k);
+    return DSA_OK;
+  }
+  const dsa_encode_level_options &d = rq.level;
   if (d.multi_parallelogram != 0 && d.multi_parallelogram != 2 && d.multi_parallelogram != 4 && d.multi_parallelogram != -1)
     return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "multi_parallelogram %d: 0 (off), 2 (MultiParallelogram), 4 (ConstrainedMultiParallelogram) or -1 (by speed and vertex count)", (int)d.multi_parallelogram);
   if (d.traversal_method != 0 && d.traversal_method != 1 && d.traversal_method != 2)
     return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "traversal_method %d: 0 (depth first), 1 (prediction degree for the positions' decoder) or 2 (for every decoder without interior seams)", (int)d.traversal_method);
   for (int k = 0; k < 6; ++k)
     if (d.reserved[k] != 0) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "dsa_encode_level_options.reserved[%d] is not zero", k);
-  DSA_GUARD(ctx, encode_batch(ctx, n, nullptr, nullptr, meshes, &d.ex.base, &d.ex, out, d.multi_parallelogram, d.traversal_method));
+  return DSA_OK;
 }
+
 // A batch is coded in chunks, several of them in flight (each on a lane of its own: stream + pinned staging + device memory).  The
 // device stages of a chunk are bound by latency -- the walks of k_enc_connectivity take a memory round trip per step, 0.1 - 0.2 s
 // whatever the number of meshes -- so the more chunks are under way the better: the uploads of the chunks go over the link one
@@ -869,7 +1070,6 @@ dsa_status dsa_encode_level_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_a
 // walks run, on a stream of their own.  Streams of one priority share four hardware queues, on which the kernels of different
 // streams wait for each other: four lanes, their walk streams at another priority.  Small batches are one chunk.
 // `code_chunk(sink, lane, base, count, &part)`: codes meshes base .. base + count of the batch on the lane.
-extern "C++" {
 template <class ChunkFn>
 static dsa_status encode_batch_chunks(dsa_context *ctx, uint32_t n, ChunkFn &&code_chunk, dsa_encoded **out) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -941,619 +1141,94 @@ static dsa_status encode_batch_chunks(dsa_context *ctx, uint32_t n, ChunkFn &&co
   *out = E.release();
   return DSA_OK;
 }
-}  // extern "C++"
-static dsa_status encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_mesh_corner_input *corners, const dsa_mesh_attr_input *attrs, const dsa_encode_options *options, const dsa_encode_options_ex *ex, dsa_encoded **out, int32_t multi_parallelogram, int32_t traversal_method) {
-  return encode_batch_chunks(ctx, n, [&](dsa_context *sink, EncLane &lane, uint32_t base, uint32_t cnt, dsa_encoded **part) {
-    return encode_chunk(sink, lane, cnt, n, meshes ? meshes + base : nullptr, corners ? corners + base : nullptr, attrs ? attrs + base : nullptr, options, ex, part, multi_parallelogram, traversal_method);
-  }, out);
+
+extern "C" {
+
+void dsa_encode_default_options(dsa_encode_options *o) {
+  if (!o) return;
+  synth::Options d;
+  o->position_bits = d.pos_bits; o->texcoord_bits = d.uv_bits; o->normal_bits = d.normal_bits;
+  o->single_connectivity = d.single_connectivity; o->symbol_scheme = d.force_scheme; o->compression_level = d.compression_level;
+  o->position_prediction = d.pos_prediction; o->texcoord_prediction = d.uv_prediction;
 }
-// The extras of a mesh with an attribute list as the host coder takes them (`ex` keeps them alive beside `in`); what the C structs
-// alone can say against them -- a reserved word -- is answered here, the rest by synth::extras_error.  "" when they can be written.
-static std::string enc_take_extras(const dsa_mesh_attr_input &am, std::vector<synth::ExtraAttr> &ex, synth::MeshIn &in) {
-  char buf[96];
-  if (am.reserved != 0) return "dsa_mesh_attr_input.reserved is not zero";
-  if (am.num_attributes && !am.attributes) return "attributes: the list is missing";
-  ex.resize(am.num_attributes);
-  for (uint32_t k = 0; k < am.num_attributes; ++k) {
-    const dsa_attribute_input &x = am.attributes[k];
-    for (int r = 0; r < 2; ++r)
-      if (x.reserved[r] != 0) { snprintf(buf, sizeof(buf), "attribute %u: reserved[%d] is not zero", k, r); return buf; }
-    ex[k].att_type = x.attribute_type; ex[k].data_type = x.data_type; ex[k].nc = x.num_components; ex[k].normalized = x.normalized;
-    ex[k].unique_id = x.unique_id; ex[k].bits = x.quantization_bits; ex[k].values = x.values;
-  }
-  in.extras = ex.data(); in.num_extras = am.num_attributes;
-  return synth::extras_error(in);
+void dsa_encode_default_options_ex(dsa_encode_options_ex *o) {
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  dsa_encode_default_options(&o->base);
 }
-// hist_cap of an integer extra: one-byte types by their range, wider ones by the values present (a pass over the values by the
-// host thread that checks the mesh's indices anyway): zig-zagged wrapped corrections lie in 0 .. max - min + 1
-static uint32_t enc_extra_hist_cap(const synth::PortableAttr &a, uint32_t rows) {
-  if (synth::data_type_size(a.data_type) == 1) return (1u << 8) + 2u;
-  const size_t total = (size_t)rows * (size_t)a.nc;
-  int32_t lo = 0, hi = 0;
-  if (a.data_type == 3) { const int16_t *p = (const int16_t *)a.extra_values; int16_t l = p[0], h = p[0]; for (size_t k = 1; k < total; ++k) { l = p[k] < l ? p[k] : l; h = p[k] > h ? p[k] : h; } lo = l; hi = h; }
-  else if (a.data_type == 4) { const uint16_t *p = (const uint16_t *)a.extra_values; uint16_t l = p[0], h = p[0]; for (size_t k = 1; k < total; ++k) { l = p[k] < l ? p[k] : l; h = p[k] > h ? p[k] : h; } lo = l; hi = h; }
-  else { const int32_t *p = (const int32_t *)a.extra_values; lo = hi = p[0]; for (size_t k = 1; k < total; ++k) { lo = p[k] < lo ? p[k] : lo; hi = p[k] > hi ? p[k] : hi; } }     // (uint32 by reinterpretation)
-  return dsa::enc_integer_hist_cap(lo, hi);
+void dsa_encode_default_level_options(dsa_encode_level_options *o) {
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  dsa_encode_default_options_ex(&o->ex);
 }
-static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, uint32_t n, uint32_t batch_n, const dsa_mesh_input *meshes_v, const dsa_mesh_corner_input *corners_v, const dsa_mesh_attr_input *attrs, const dsa_encode_options *options, const dsa_encode_options_ex *ex, dsa_encoded **out, int32_t multi_parallelogram, int32_t traversal_method) {
-  // mesh i of the chunk, whichever entry point it came through (corner(i): its corner form, null for dsa_encode_batch)
-  struct MeshRef {
-    const dsa_mesh_input *v; const dsa_mesh_corner_input *c; const dsa_mesh_attr_input *a;
-    const dsa_mesh_corner_input *corner(size_t i) const { return a ? &a[i].mesh : (c ? &c[i] : nullptr); }
-    const dsa_mesh_input &operator[](size_t i) const { return (a || c) ? corner(i)->mesh : v[i]; }
-  } meshes{meshes_v, corners_v, attrs};
-  const bool corners = corners_v != nullptr || attrs != nullptr;
-  std::vector<std::vector<synth::ExtraAttr>> extras(attrs ? n : 0);
-  std::vector<std::vector<uint32_t>> extra_cap(attrs ? n : 0);      // per attribute of the plan: hist_cap of an integer extra, else 0
-  hostutil::TurnGuard turn(lane.upload_turn, lane.upload_chunk);      // (whatever happens below, the other chunks' uploads do not wait for this one's)
-  HIP_TRY(ctx, hipSetDevice(lane.device));
-  dsa_encode_options od;
-  dsa_encode_default_options(&od);
-  if (options) od = *options;
-  if (od.position_bits < 1 || od.position_bits > 20 || od.texcoord_bits < 1 || od.texcoord_bits > 20 || od.normal_bits < 2 || od.normal_bits > 20)
-    return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "quantisation bits out of range (positions/texcoords 1..20, normals 2..20)");
-  synth::Options opt;
-  opt.pos_bits = od.position_bits; opt.uv_bits = od.texcoord_bits; opt.normal_bits = od.normal_bits;
-  opt.single_connectivity = od.single_connectivity; opt.force_scheme = od.symbol_scheme; opt.compression_level = od.compression_level;
-  opt.pos_prediction = od.position_prediction; opt.uv_prediction = od.texcoord_prediction;
-  opt.normal_prediction = ex ? ex->normal_prediction : 0;
-  opt.traversal_method = traversal_method;
-  // MultiParallelogram per mesh: the method asked for, or by the reference's rule (speed < 2 and at least 40 points)
-  auto multi_of = [&](uint32_t i) -> int32_t {
-    return multi_parallelogram == -1 ? ((opt.compression_level >= 9 && meshes[i].num_vertices >= 40) ? 4 : 0) : multi_parallelogram;
-  };
-  // the prediction-degree order beside the depth-first one: every mesh of the chunk (the positions' decoder takes it at least)
-  const bool want_pd = traversal_method != 0;
-  // valence symbols per mesh: asked for, or by the reference's rule (speed < 5 and not a tiny mesh)
-  const int32_t eb_method = ex ? ex->edgebreaker_method : 0;
-  auto valence_of = [&](uint32_t i) { return eb_method == 2 || (eb_method == -1 && opt.compression_level > 5 && meshes[i].num_faces >= 1000); };
-  // meshes of the chunk coded with valence symbols (the walks then record the start faces' times)
-  bool any_valence = false;
-  for (uint32_t i = 0; i < n; ++i) any_valence = any_valence || valence_of(i);
-  dsa_encoded *E = new (std::nothrow) dsa_encoded();
-  if (!E) return set_err(ctx, DSA_ERR_OUT_OF_MEMORY, "host allocation failed");
-  std::unique_ptr<dsa_encoded> E_owner(E);      // released into *out at the very end; every other exit frees it
-  E->ctx = ctx;
-  E->streams.resize(n); E->status.assign(n, DSA_OK); E->messages.resize(n);
-  // ---- host phase 1: connectivity, traversal order, operand entries (threads over meshes)
-  std::vector<synth::MeshPlan> plans(n);
-  std::vector<synth::MeshIn> ins(n);
-  std::vector<std::vector<uint32_t>> e2v(n);
-  std::vector<std::vector<int32_t>> ops(n);
-  std::vector<std::vector<uint32_t>> e2v_pd(want_pd ? n : 0);         // the same in prediction-degree order (host connectivity)
-  std::vector<std::vector<int32_t>> ops_pd(want_pd ? n : 0);
-  // attributes given per corner, host connectivity: per attribute its own entry -> value row, and its own operands when it is seamed
-  std::vector<std::vector<std::vector<uint32_t>>> att_e2v(n);
-  std::vector<std::vector<std::vector<int32_t>>> att_ops(n);
-  std::vector<std::vector<std::vector<uint32_t>>> att_opp(n);       // the same, prediction 5 / 6 of a seamed attribute: its table's opposites
-  // attribute k of plan `pl` reads the mesh's topology (TexCoordsPortable, GeometricNormal)
-  auto multi_scheme = [](const synth::PortableAttr &a) { return a.seq_type != 3 && (a.prediction == 2 || a.prediction == 4); };
-  auto topo_scheme = [&](const synth::PortableAttr &a) { return (a.seq_type == 2 && a.prediction == 5) || (a.seq_type == 3 && a.prediction == 6) || multi_scheme(a); };
-  // DSA_ENC_TIMING=1 (diagnostics): wall time of every phase on stderr
-  static const bool timing = getenv("DSA_ENC_TIMING") != nullptr;
-  auto t_last = std::chrono::steady_clock::now();
-  auto lap = [&](const char *what) {
-    if (!timing) return;
-    const auto now = std::chrono::steady_clock::now();
-    static const auto t_zero = now;
-    fprintf(stderr, "[dsa_encode_batch] lane %p at %9.2f ms: %-28s %8.2f ms\n", (void *)&lane, std::chrono::duration<double, std::milli>(now - t_zero).count(), what, std::chrono::duration<double, std::milli>(now - t_last).count());
-    t_last = now;
-  };
-  // Both device stages are the serial algorithms on one lane per mesh / per stream: a batch takes 150 - 250 ms (connectivity) and
-  // about 40 ms (plans) whatever its size, which the host threads beat on a small batch (measured: 64 meshes 84 ms on the host, 128 meshes 252 ms on the device).  Below 256 meshes the host does both
-  // (DSA_ENC_HOST_CONN / DSA_ENC_HOST_PLAN = 1 or 0 force one or the other; read per call: the tests compare the paths).
-  auto choice = [&](const char *name) { const char *e = getenv(name); return e ? atoi(e) != 0 : batch_n < 256; };
-  const bool host_conn = choice("DSA_ENC_HOST_CONN");
-  // meshes to a wave of the walks (k_enc_connectivity: one lane per mesh); DSA_ENC_WALK_LANES = 1 .. 64 for measurements
-  const uint32_t walk_lanes = [&]() { const char *e = getenv("DSA_ENC_WALK_LANES"); const int v = e ? atoi(e) : 0; return (uint32_t)(v >= 1 && v <= 64 ? v : 16); }();
-  const bool host_plan = choice("DSA_ENC_HOST_PLAN");
-  auto plan_one = [&](uint32_t i) {
-    const dsa_mesh_input &m = meshes[i];
-    synth::MeshIn &in = ins[i];
-    in.pos = m.positions; in.nv = m.num_vertices; in.faces = m.faces; in.nf = m.num_faces; in.normals = m.normals; in.uvs = m.texcoords;
-    in.generic = (m.generic && m.generic_components >= 1 && m.generic_components <= 4) ? m.generic : nullptr;
-    if (corners) {
-      const dsa_mesh_corner_input &cm = *meshes.corner(i);
-      if (m.generic && (m.generic_components < 1 || m.generic_components > 4)) { E->status[i] = DSA_ERR_INVALID_ARGUMENT; E->messages[i] = "generic attribute needs 1 - 4 components"; return; }
-      if ((cm.normal_corners && !m.normals) || (cm.texcoord_corners && !m.texcoords)) { E->status[i] = DSA_ERR_INVALID_ARGUMENT; E->messages[i] = "corner ids without their values"; return; }
-      in.normal_corners = cm.normal_corners; in.nn = cm.num_normals;
-      in.uv_corners = cm.texcoord_corners; in.nu = cm.num_texcoords;
-    }
-    if (attrs) {
-      const std::string why = enc_take_extras(attrs[i], extras[i], in);
-      if (!why.empty()) { E->status[i] = DSA_ERR_INVALID_ARGUMENT; E->messages[i] = why; return; }
-    }
-    // (the bounds of the integer extras' values, once the plan below has said which attributes there are)
-    auto extra_caps = [&]() {
-      if (!attrs) return;
-      extra_cap[i].assign(plans[i].atts.size(), 0);
-      for (size_t k = 0; k < plans[i].atts.size(); ++k)
-        if (plans[i].atts[k].extra_values && plans[i].atts[k].seq_type == 1) extra_cap[i][k] = enc_extra_hist_cap(plans[i].atts[k], m.num_vertices);
-    };
-    try {
-      synth::check(m.positions && m.faces && m.num_vertices >= 3 && m.num_faces >= 1, "mesh needs positions and faces");
-      for (size_t k = 0; k < (size_t)m.num_faces * 3; ++k) synth::check(m.faces[k] < m.num_vertices, "face index out of range");
-      if (in.normal_corners) for (size_t k = 0; k < (size_t)m.num_faces * 3; ++k) synth::check(in.normal_corners[k] < in.nn, "normal id out of range");
-      if (in.uv_corners) for (size_t k = 0; k < (size_t)m.num_faces * 3; ++k) synth::check(in.uv_corners[k] < in.nu, "texture coordinate id out of range");
-      synth::check(host_conn || (uint64_t)m.num_faces * 3 <= (uint64_t)dsa::EC_CORNER_MASK, "mesh too large for the device connectivity coder");
-      synth::Options mo = opt;                                   // (the components of the generic attribute are the mesh's own)
-      mo.generic_components = in.generic ? (int32_t)m.generic_components : 1;
-      mo.predictive_connectivity = valence_of(i) ? 2 : 0;
-      if (const int32_t mp = multi_of(i)) {                      // in place of Parallelogram (plan_attributes: the generic attribute and the extras follow the positions to method 4)
-        if (opt.pos_prediction == 1) mo.pos_prediction = mp;
-        if (opt.uv_prediction == 1) mo.uv_prediction = mp;
-      }
-      if (!host_conn) {                                          // the rest of the plan comes from the device
-        synth::check(!((in.normal_corners || in.uv_corners) && opt.single_connectivity), "attributes given per corner need a connectivity of their own (single_connectivity = 0)");
-        synth::check(!(in.normal_corners || in.uv_corners) || 24ull * m.num_faces + 16u < (1ull << 32), "mesh too large for the device connectivity coder");
-        synth::plan_attributes(in, mo, plans[i]);
-        extra_caps();
-        return;
-      }
-      synth::plan_mesh(in, mo, plans[i]);
-      extra_caps();
-      const synth::MeshPlan &pl = plans[i];
-      dsa::entry_maps(pl.ct, pl.seq, nullptr, e2v[i], &ops[i]);
-      if (want_pd) dsa::entry_maps(pl.ct, pl.seq_pd, nullptr, e2v_pd[i], &ops_pd[i]);
-      att_e2v[i].assign(pl.atts.size(), {}); att_ops[i].assign(pl.atts.size(), {});
-      for (size_t k = 1; k < pl.atts.size(); ++k) {
-        const uint32_t *ids = pl.atts[k].corner_value;
-        if (!ids) continue;
-        if (pl.seamed(k)) dsa::entry_maps(pl.conns[k], pl.seq_att[k], ids, att_e2v[i][k], &att_ops[i][k]);
-        else dsa::entry_maps(pl.ct, pl.uses_pd(k) ? pl.seq_pd : pl.seq, ids, att_e2v[i][k], nullptr);      // (the positions' operands)
-      }
-      att_opp[i].assign(pl.atts.size(), {});
-      for (size_t k = 1; k < pl.atts.size(); ++k) {
-        if (!pl.seamed(k) || !topo_scheme(pl.atts[k])) continue;
-        std::vector<uint32_t> &o = att_opp[i][k];
-        o.resize(pl.ct.nc());
-        for (uint32_t c = 0; c < pl.ct.nc(); ++c) o[c] = pl.conns[k].opposite(c);
-      }
-    } catch (const std::exception &e) { E->status[i] = DSA_ERR_INVALID_DATA; E->messages[i] = e.what(); }
-  };
-  hostutil::parallel_for(n, plan_one);          // capped thread count, every thread joined on every path (dsa_host_util.h)
-  lap("host checks / plan");
-  // ---- device layout
-  std::vector<dsa::EncStream> hs;
-  std::vector<dsa::EncConn> hc(host_conn ? 0 : n);
-  std::vector<dsa::EncSeam> hz;                   // device connectivity: one per (mesh, attribute given per corner)
-  std::vector<uint32_t> first_stream(n + 1, 0);
-  bool any_multi = false, any_crease = false;      // streams of the chunk predicted by method 2 / 4; by method 4
-  // value rows of attribute k of mesh i: its ids' row count when it is given per corner
-  auto rows_of = [&](uint32_t i, const synth::PortableAttr &a) -> uint32_t {
-    if (!a.corner_value) return meshes[i].num_vertices;
-    return a.att_type == 1 ? meshes.corner(i)->num_normals : meshes.corner(i)->num_texcoords;
-  };
-  auto ids_narrow = [&](uint32_t i, const synth::PortableAttr &a) { return rows_of(i, a) <= 65536; };
-  // What the host provides (faces, raw attribute values; with host connectivity the traversal order and operands) lies at the
-  // front of the arena in one run, so that it travels in a few large transfers out of pinned staging; everything else behind it.
-  auto al = [](uint64_t b) { return (b + 255) & ~255ull; };
-  uint64_t in_total = 0;
-  for (uint32_t i = 0; i < n; ++i) {
-    if (E->status[i] != DSA_OK) continue;
-    const uint64_t V = meshes[i].num_vertices, F = meshes[i].num_faces;
-    in_total += host_conn ? al(4 * V) + al(12 * V) : al((V <= 65536 ? 6 : 12) * F);      // (faces of a mesh of up to 65 536 vertices travel as 16-bit indices)
-    for (size_t k = 0; k < plans[i].atts.size(); ++k) {
-      const synth::PortableAttr &a = plans[i].atts[k];
-      in_total += al(4 * (uint64_t)rows_of(i, a) * (uint64_t)a.nc_out);
-      if (!a.corner_value) continue;
-      if (host_conn) { const uint64_t ent = att_e2v[i][k].size(); in_total += al(4 * ent) + (att_ops[i][k].empty() ? 0 : al(12 * ent)); }
-      else in_total += al((ids_narrow(i, a) ? 6 : 12) * F);          // the ids travel with the faces, narrowed like them
-    }
-    if (!host_conn) continue;
-    // host connectivity: the topology of TexCoordsPortable / GeometricNormal and the valence context lists travel too
-    const synth::MeshPlan &pl = plans[i];
-    bool needs_topo = false;
-    for (size_t k = 0; k < pl.atts.size(); ++k) {
-      needs_topo = needs_topo || topo_scheme(pl.atts[k]);
-      if (topo_scheme(pl.atts[k]) && pl.atts[k].corner_value && pl.seamed(k))
-        in_total += 2 * al(4 * pl.conns[k].c2v.size()) + 2 * al(4 * pl.seq_att[k].data_to_corner.size());
-    }
-    if (needs_topo) in_total += 2 * al(4 * pl.ct.c2v.size()) + 2 * al(4 * pl.seq.data_to_corner.size());
-    if (want_pd) in_total += al(4 * V) + al(12 * V) + 2 * al(4 * V);          // the second order: entry maps, and its topology view
-    if (pl.valence) for (int k = 0; k < 6; ++k) in_total += al(4 * pl.ctx_symbols[k].size());
-  }
-  uint64_t cur = in_total, cur_in = 0;
-  auto take = [&](uint64_t bytes) { uint64_t at = cur; cur = (cur + bytes + 255) & ~255ull; return at; };
-  auto take_in = [&](uint64_t bytes) { uint64_t at = cur_in; cur_in = (cur_in + bytes + 255) & ~255ull; return at; };
-  using Upload = EncUpload;
-  std::vector<Upload> uploads_a, uploads;          // phase A: what the walks need (the faces, the corner ids); the rest
-  uint32_t max_rows = 0;
-  std::vector<uint64_t> faces_at(n, 0);
-  std::vector<std::vector<uint64_t>> ids_at(n);
-  if (!host_conn)
-    for (uint32_t i = 0; i < n; ++i) {
-      if (E->status[i] != DSA_OK) continue;
-      // Half of what the walks wait for is the upload of the faces: indices below 65 536 are narrowed to 16 bits by the copy into
-      // pinned staging (which reads them anyway) and widened by the first kernel of the chunk.
-      const bool narrow = meshes[i].num_vertices <= 65536;
-      faces_at[i] = take_in((narrow ? 6ull : 12ull) * meshes[i].num_faces);
-      uploads_a.push_back({faces_at[i], meshes[i].faces, (narrow ? 6ull : 12ull) * meshes[i].num_faces, narrow});
-      // corner ids right behind (the seam kernels read them as they were uploaded: 16-bit where the row count allows)
-      ids_at[i].assign(plans[i].atts.size(), 0);
-      for (size_t k = 0; k < plans[i].atts.size(); ++k) {
-        const synth::PortableAttr &a = plans[i].atts[k];
-        if (!a.corner_value) continue;
-        const uint64_t bytes = (ids_narrow(i, a) ? 6ull : 12ull) * meshes[i].num_faces;
-        ids_at[i][k] = take_in(bytes);
-        uploads_a.push_back({ids_at[i][k], a.corner_value, bytes, ids_narrow(i, a)});
-      }
-    }
-  for (uint32_t i = 0; i < n; ++i) {
-    first_stream[i] = (uint32_t)hs.size();
-    if (E->status[i] != DSA_OK) continue;
-    const uint32_t V = meshes[i].num_vertices;
-    const uint64_t o_e2v = host_conn ? take_in(4ull * V) : take(4ull * V), o_ops = host_conn ? take_in(12ull * V) : take(12ull * V);
-    uint64_t o_e2v_pd = 0, o_ops_pd = 0;
-    if (want_pd) { o_e2v_pd = host_conn ? take_in(4ull * V) : take(4ull * V); o_ops_pd = host_conn ? take_in(12ull * V) : take(12ull * V); }
-    if (host_conn) {
-      uploads.push_back({o_e2v, e2v[i].data(), 4ull * V, false});
-      uploads.push_back({o_ops, ops[i].data(), 12ull * V, false});
-      if (want_pd) { uploads.push_back({o_e2v_pd, e2v_pd[i].data(), 4ull * V, false}); uploads.push_back({o_ops_pd, ops_pd[i].data(), 12ull * V, false}); }
-    } else {
-      const uint32_t F = meshes[i].num_faces;
-      dsa::EncConn &C = hc[i];
-      memset(&C, 0, sizeof(C));
-      C.F = F; C.V = V; C.split_cap = F; C.fail_key = 0xFFFFFFFFu;
-      if (V <= 65536) { C.faces_narrow = 1; C.faces16 = faces_at[i]; C.faces = take(12ull * F); } else C.faces = faces_at[i];
-      C.opp = take(12ull * F); C.voff = take(4ull * (V + 1)); C.vcur = take(4ull * V); C.vlist = take(12ull * F); C.vcorner = take(4ull * V);
-      C.vvis = take(V); C.frec = take(32ull * F);
-      C.stack = take(4ull * F); C.processed = take(4ull * F); C.init_corners = take(4ull * F);
-      C.symbols = take(F); C.start_bits = take(F); C.splits = take(12ull * C.split_cap);
-      C.d2c = take(4ull * V); C.v2d = take(4ull * V);
-      C.e2v = o_e2v; C.ops = o_ops;
-      if (want_pd) {
-        C.pd_d2c = take(4ull * V); C.pd_v2d = take(4ull * V); C.pd_e2v = o_e2v_pd; C.pd_ops = o_ops_pd;
-        C.pd_next = take(12ull * F); C.pd_degree = take(4ull * V); C.pd_fvis = take(F);
-      }
-      C.vstream = DSA_INVALID;
-      if (valence_of(i)) {
-        C.init_time = take(4ull * F); C.vtime = take(4ull * F); C.vval = take(4ull * ((uint64_t)V + F)); C.vc2v = take(12ull * F);
-        C.vctx = take(F); C.vsyms = take(4ull * F); C.vbl = take(F); C.vrans = take(4ull * F + 96); C.vbits = take(4ull * F + 96);
-      }
-    }
-    // TexCoordsPortable / GeometricNormal: the position table and order (device: the connectivity's; host: uploaded once per mesh)
-    uint64_t t_c2v = 0, t_opp = 0, t_d2c = 0, t_v2d = 0, t_d2c_pd = 0, t_v2d_pd = 0;
-    bool needs_topo = false;
-    for (const synth::PortableAttr &a : plans[i].atts) needs_topo = needs_topo || topo_scheme(a);
-    if (needs_topo && host_conn) {
-      const synth::MeshPlan &pl = plans[i];
-      t_c2v = take_in(4ull * pl.ct.c2v.size()); uploads.push_back({t_c2v, pl.ct.c2v.data(), 4ull * pl.ct.c2v.size(), false});
-      t_opp = take_in(4ull * pl.ct.opp.size()); uploads.push_back({t_opp, pl.ct.opp.data(), 4ull * pl.ct.opp.size(), false});
-      t_d2c = take_in(4ull * pl.seq.data_to_corner.size()); uploads.push_back({t_d2c, pl.seq.data_to_corner.data(), 4ull * pl.seq.data_to_corner.size(), false});
-      t_v2d = take_in(4ull * pl.seq.vertex_to_data.size()); uploads.push_back({t_v2d, pl.seq.vertex_to_data.data(), 4ull * pl.seq.vertex_to_data.size(), false});
-      if (want_pd) {
-        t_d2c_pd = take_in(4ull * pl.seq_pd.data_to_corner.size()); uploads.push_back({t_d2c_pd, pl.seq_pd.data_to_corner.data(), 4ull * pl.seq_pd.data_to_corner.size(), false});
-        t_v2d_pd = take_in(4ull * pl.seq_pd.vertex_to_data.size()); uploads.push_back({t_v2d_pd, pl.seq_pd.vertex_to_data.data(), 4ull * pl.seq_pd.vertex_to_data.size(), false});
-      }
-    } else if (needs_topo) { t_c2v = hc[i].faces; t_opp = hc[i].opp; t_d2c = hc[i].d2c; t_v2d = hc[i].v2d; t_d2c_pd = hc[i].pd_d2c; t_v2d_pd = hc[i].pd_v2d; }
-    for (size_t k = 0; k < plans[i].atts.size(); ++k) {
-      const synth::PortableAttr &a = plans[i].atts[k];
-      dsa::EncStream S;
-      memset(&S, 0, sizeof(S));
-      const bool integer = a.seq_type == 1;                  // the generic uint8 attribute, an integer extra
-      const void *src = a.extra_values ? a.extra_values
-                        : (a.att_type == 0 ? (const void *)meshes[i].positions : (a.att_type == 1 ? (const void *)meshes[i].normals : (integer ? (const void *)meshes[i].generic : (const void *)meshes[i].texcoords)));
-      // entries: V, or for an attribute given per corner as many as its walk has (host connectivity) / may have (device: 3F at
-      // most, k_enc_seam_operands sets the count)
-      const uint32_t rows = rows_of(i, a);
-      uint32_t entries = V, cap = V;
-      // the decoder of attribute k takes the prediction-degree order (MeshPlan::uses_pd; for an attribute given per corner on the
-      // device path: unless it turns out seamed -- k_enc_pd_corner_streams, k_enc_seam_topo)
-      const bool pd = want_pd && (host_conn ? plans[i].uses_pd(k) : (traversal_method == 2 || opt.single_connectivity != 0 || k == 0));
-      S.e2v = pd ? o_e2v_pd : o_e2v; S.ops = pd ? o_ops_pd : o_ops;
-      if (a.corner_value && host_conn) {
-        entries = cap = (uint32_t)att_e2v[i][k].size();
-        S.e2v = take_in(4ull * entries);
-        uploads.push_back({S.e2v, att_e2v[i][k].data(), 4ull * entries, false});
-        if (!att_ops[i][k].empty()) { S.ops = take_in(12ull * entries); uploads.push_back({S.ops, att_ops[i][k].data(), 12ull * entries, false}); }
-      } else if (a.corner_value) {
-        const uint32_t F = meshes[i].num_faces;
-        cap = 3u * F;
-        dsa::EncSeam Z;
-        memset(&Z, 0, sizeof(Z));
-        Z.mesh = i; Z.stream = (uint32_t)hs.size(); Z.ids = ids_at[i][k]; Z.ids_narrow = ids_narrow(i, a) ? 1u : 0u; Z.rows = rows;
-        Z.edge_seam = take(3ull * F); Z.vert_seam = take(V); Z.afirst = take(4ull * V); Z.aoff = take(4ull * (V + 1));
-        Z.c2av = take(12ull * F); Z.opp2 = take(12ull * F); Z.v2lm = take(12ull * F); Z.avis = take(3ull * F); Z.frec = take(32ull * F);
-        Z.stack = take(4ull * F); Z.d2c = take(12ull * F); Z.v2d = take(12ull * F); Z.e2v = take(12ull * F); Z.ops = take(36ull * F);
-        Z.rank = take(4ull * F); Z.rcorner = take(4ull * F); Z.eoff = take(4ull * (F + 1)); Z.bits = take(4ull * ((3ull * F + 31) / 32));
-        S.e2v = Z.e2v; S.ops = Z.ops;
-        S.pd_want = pd ? 1u : 0u;
-        hz.push_back(Z);
-      }
-      S.nv = entries; S.rows = rows; S.nc_out = (uint32_t)a.nc_out; S.nc = (uint32_t)a.nc; S.kind = a.seq_type == 3 ? 1u : (integer ? 2u : 0u);
-      S.bits = integer ? 9u : (uint32_t)a.bits; S.prediction = (uint32_t)a.prediction;      // (9: the zig-zagged corrections of bytes are below 512)
-      S.elem = integer ? (uint32_t)a.data_type : 0u;
-      const uint64_t src_bytes = (integer ? (uint64_t)synth::data_type_size(a.data_type) : 4ull) * rows * S.nc_out;
-      S.src = take_in(src_bytes);
-      uploads.push_back({S.src, src, src_bytes, false});
-      S.vals = take(4ull * rows * S.nc); S.d = take(4ull * cap * S.nc); S.syms = take(4ull * cap * S.nc); S.bl = take(cap);
-      max_rows = std::max(max_rows, std::max(rows, cap));
-      S.hist_cap = (1u << S.bits) + 2u;                      // zig-zag of a wrapped correction / a positive octahedral correction fits
-      if (attrs && extra_cap[i][k]) S.hist_cap = extra_cap[i][k];       // an integer extra: by the values present
-      S.hist_raw = take(4ull * S.hist_cap);
-      S.out_cap = 4u * cap * S.nc + 16u;                     // (tagged bit fields are at most 32 bits a symbol, a coded symbol at most 20 bits and the flush)
-      S.out_rans = take(S.out_cap); S.out_bits = take(S.out_cap);
-      const uint64_t table_cap = std::max<uint64_t>(S.hist_cap, 64);   // the tagged scheme's alphabet is 33 bit lengths
-      S.prob = take(4ull * table_cap); S.cum = take(4ull * table_cap);
-      S.plan_order = take(4ull * table_cap); S.plan_tmp = take(4ull * table_cap);
-      if (topo_scheme(a)) {
-        const bool multi = multi_scheme(a);
-        if (!multi) S.pos_vals = hs[first_stream[i]].vals;      // (the positions are attribute 0: their stream is the mesh's first)
-        S.t_c2p = S.t_c2a = t_c2v; S.t_opp = t_opp; S.t_d2c = pd ? t_d2c_pd : t_d2c; S.t_v2d = pd ? t_v2d_pd : t_v2d;
-        S.t_nc3 = 3u * meshes[i].num_faces;
-        if (host_conn && a.corner_value && plans[i].seamed(k)) {             // a seamed attribute's own table and order
-          const synth::MeshPlan &pl = plans[i];
-          const std::vector<uint32_t> &c2a = pl.conns[k].c2v, &o2 = att_opp[i][k], &d2c = pl.seq_att[k].data_to_corner;
-          const std::vector<int32_t> &v2d = pl.seq_att[k].vertex_to_data;
-          S.t_c2a = take_in(4ull * c2a.size()); uploads.push_back({S.t_c2a, c2a.data(), 4ull * c2a.size(), false});
-          S.t_opp = take_in(4ull * o2.size()); uploads.push_back({S.t_opp, o2.data(), 4ull * o2.size(), false});
-          S.t_d2c = take_in(4ull * d2c.size()); uploads.push_back({S.t_d2c, d2c.data(), 4ull * d2c.size(), false});
-          S.t_v2d = take_in(4ull * v2d.size()); uploads.push_back({S.t_v2d, v2d.data(), 4ull * v2d.size(), false});
-        }
-        if (multi) {
-          any_multi = true;
-          if (a.prediction == 4) {                               // found + crease flags per entry; the four crease lists
-            any_crease = true;
-            S.ori = take(cap);
-            S.flags = take(4ull * dsa::em_crease_words(cap, S.cr_at));
-          }
-        } else {
-          if (a.seq_type == 2) S.ori = take(cap);
-          S.flags = take(4ull * ((cap + 31) / 32));
-        }
-      }
-      hs.push_back(S);
-    }
-    // valence symbols: six more streams, the context lists (kind 3, one component, alphabet C S L R E).  Device connectivity: the
-    // lists' sizes and places are set by k_enc_val_split in the mesh's regions; host connectivity: the host coder's lists, uploaded.
-    if (valence_of(i)) {
-      if (!host_conn) hc[i].vstream = (uint32_t)hs.size();
-      for (int k = 0; k < 6; ++k) {
-        dsa::EncStream S;
-        memset(&S, 0, sizeof(S));
-        S.kind = 3; S.nc = S.nc_out = 1; S.bits = 3; S.hist_cap = 8;
-        S.hist_raw = take(4ull * S.hist_cap);
-        S.prob = take(4ull * 64); S.cum = take(4ull * 64); S.plan_order = take(4ull * 64); S.plan_tmp = take(4ull * 64);
-        if (host_conn) {
-          const std::vector<uint32_t> &list = plans[i].ctx_symbols[k];
-          const uint32_t cnt = (uint32_t)list.size();
-          S.nv = cnt;
-          if (cnt) { S.syms = take_in(4ull * cnt); uploads.push_back({S.syms, list.data(), 4ull * cnt, false}); }
-          S.bl = take(cnt); S.out_cap = 4u * cnt + 16u; S.out_rans = take(S.out_cap); S.out_bits = take(S.out_cap);
-        }
-        hs.push_back(S);
-      }
-    }
-  }
-  first_stream[n] = (uint32_t)hs.size();
-  const uint32_t ns = (uint32_t)hs.size();
-  uint8_t *arena = nullptr;
-  dsa::EncStream *d_streams = nullptr;
-  dsa::EncConn *d_conns = nullptr;
-  dsa::EncSeam *d_seams = nullptr;
-  const uint32_t nz = (uint32_t)hz.size();
-  auto cleanup = [&]() {};      // the lane owns its device memory (EncLane::Buf): nothing to release per chunk
-  auto gather = [&](std::vector<dsa::PackItem> &items, std::vector<uint8_t> &host, const uint8_t **view) { return enc_gather(lane, arena, items, host, view); };
-  if (ns) {
-    hipStream_t st = lane.st;
-    ENC_TRY(lane.arena.ensure(cur ? cur : 256));
-    ENC_TRY(lane.streams.ensure(sizeof(dsa::EncStream) * ns));
-    arena = (uint8_t *)lane.arena.p; d_streams = (dsa::EncStream *)lane.streams.p;
-    if (lane.walk_st) ENC_TRY(hipStreamSynchronize(lane.walk_st));     // (idle unless a previous chunk on this lane ended in an error)
-    ENC_TRY(hipMemsetAsync(arena, 0, cur, st));              // histograms start at zero
-    auto upload = [&](const std::vector<Upload> &ups) { return enc_upload(lane, arena, st, ups); };
-    turn.acquire_a();
-    ENC_TRY(upload(host_conn ? uploads : uploads_a));
-    if (host_conn) turn.release();
-    ENC_TRY(hipMemcpyAsync(d_streams, hs.data(), sizeof(dsa::EncStream) * ns, hipMemcpyHostToDevice, st));
-    const uint32_t gx = std::max(1u, std::min(64u, (max_rows + 2047) / 2048));
-    lap("layout + uploads queued");
-    // ---- device phase 0: corner table, Edgebreaker symbols, attribute order, operand entries (one wave per mesh); meshes that
-    // failed the host's checks have F = 0 and no arrays
-    if (!host_conn) {
-      ENC_TRY(lane.conns.ensure(sizeof(dsa::EncConn) * n));
-      d_conns = (dsa::EncConn *)lane.conns.p;
-      for (uint32_t i = 0; i < n; ++i) if (E->status[i] != DSA_OK) { memset(&hc[i], 0, sizeof(hc[i])); hc[i].status = dsa::ENC_ISOLATED; }
-      ENC_TRY(hipMemcpyAsync(d_conns, hc.data(), sizeof(dsa::EncConn) * n, hipMemcpyHostToDevice, st));
-      uint32_t maxf = 0;
-      for (uint32_t i = 0; i < n; ++i) maxf = std::max(maxf, hc[i].F);
-      const dim3 gt(std::max(1u, std::min(128u, (3u * maxf + 1023u) / 1024u)), n);        // table kernels: blocks per mesh x meshes
-      hipLaunchKernelGGL(dsa::k_enc_table_clear, gt, dim3(256), 0, st, arena, d_conns, n);
-      hipLaunchKernelGGL(dsa::k_enc_table_count, gt, dim3(256), 0, st, arena, d_conns, n);
-      hipLaunchKernelGGL(dsa::k_enc_table_offsets, dim3(n), dim3(WAVE), 0, st, arena, d_conns, n);
-      hipLaunchKernelGGL(dsa::k_enc_table_lists, gt, dim3(256), 0, st, arena, d_conns, n);
-      hipLaunchKernelGGL(dsa::k_enc_table_opposites, gt, dim3(256), 0, st, arena, d_conns, n);
-      hipLaunchKernelGGL(dsa::k_enc_table_corners, gt, dim3(256), 0, st, arena, d_conns, n);
-      // the walks on their stream; the attribute values travel and are quantised meanwhile
-      ENC_TRY(hipEventRecord(lane.tables_done, st));
-      ENC_TRY(hipStreamWaitEvent(lane.walk_st, lane.tables_done, 0));
-      hipLaunchKernelGGL(any_valence ? dsa::k_enc_connectivity_timed : dsa::k_enc_connectivity, dim3((n + walk_lanes - 1) / walk_lanes), dim3(WAVE), 0, lane.walk_st, arena, d_conns, n, walk_lanes);
-      if (want_pd) hipLaunchKernelGGL(dsa::k_enc_pd_walk, dim3((n + walk_lanes - 1) / walk_lanes), dim3(WAVE), 0, lane.walk_st, arena, d_conns, n, walk_lanes);
-      if (nz) {
-        // attributes given per corner: seams and attribute vertices beside the connectivity walk, the attribute walks behind it
-        ENC_TRY(lane.seams.ensure(sizeof(dsa::EncSeam) * nz));
-        d_seams = (dsa::EncSeam *)lane.seams.p;
-        ENC_TRY(hipMemcpyAsync(d_seams, hz.data(), sizeof(dsa::EncSeam) * nz, hipMemcpyHostToDevice, st));
-        const dim3 gz(gt.x, nz);
-        hipLaunchKernelGGL(dsa::k_enc_seam_edges, gz, dim3(256), 0, st, arena, d_conns, d_seams, nz);
-        hipLaunchKernelGGL(dsa::k_enc_seam_fans, gz, dim3(256), 0, st, arena, d_conns, d_seams, nz);
-        hipLaunchKernelGGL(dsa::k_enc_seam_offsets, dim3(nz), dim3(WAVE), 0, st, arena, d_conns, d_seams, nz);
-        hipLaunchKernelGGL(dsa::k_enc_seam_assign, gz, dim3(256), 0, st, arena, d_conns, d_seams, nz);
-        hipLaunchKernelGGL(dsa::k_enc_seam_records, gz, dim3(256), 0, st, arena, d_conns, d_seams, nz);
-        ENC_TRY(hipEventRecord(lane.seams_done, st));
-        ENC_TRY(hipStreamWaitEvent(lane.walk_st, lane.seams_done, 0));
-        hipLaunchKernelGGL(dsa::k_enc_seam_walk, dim3((nz + walk_lanes - 1) / walk_lanes), dim3(WAVE), 0, lane.walk_st, arena, d_conns, d_seams, nz, walk_lanes);
-      }
-      if (any_valence) {
-        // valence context lists behind the walks, on their stream: one more serial pass per mesh, then the lists into six streams
-        hipLaunchKernelGGL(dsa::k_enc_val_init, gt, dim3(256), 0, lane.walk_st, arena, d_conns, n);
-        hipLaunchKernelGGL(dsa::k_enc_valence, dim3((n + walk_lanes - 1) / walk_lanes), dim3(WAVE), 0, lane.walk_st, arena, d_conns, n, walk_lanes);
-        hipLaunchKernelGGL(dsa::k_enc_val_split<dsa::EncStream>, dim3(n), dim3(WAVE), 0, lane.walk_st, arena, d_conns, n, d_streams);
-      }
-      ENC_TRY(hipEventRecord(lane.walk_done, lane.walk_st));
-      turn.release();
-      turn.acquire_b();
-      ENC_TRY(upload(uploads));
-      turn.release();
-      hipLaunchKernelGGL(dsa::k_enc_bounds, dim3(ns), dim3(256), 0, st, arena, d_streams, ns);
-      hipLaunchKernelGGL(dsa::k_enc_quantize, dim3(gx, ns), dim3(256), 0, st, arena, d_streams, ns);
-      ENC_TRY(hipStreamWaitEvent(st, lane.walk_done, 0));
-      hipLaunchKernelGGL(dsa::k_enc_operands, gt, dim3(256), 0, st, arena, d_conns, n);
-      if (want_pd) hipLaunchKernelGGL(dsa::k_enc_pd_operands, gt, dim3(256), 0, st, arena, d_conns, n);
-      if (nz) {
-        const dim3 gz(gt.x, nz);
-        hipLaunchKernelGGL(dsa::k_enc_seam_operands<dsa::EncStream>, gz, dim3(256), 0, st, arena, d_conns, d_seams, nz, d_streams);
-        if (want_pd) hipLaunchKernelGGL(dsa::k_enc_pd_corner_streams<dsa::EncStream>, gz, dim3(256), 0, st, arena, d_conns, d_seams, nz, d_streams);
-        hipLaunchKernelGGL(dsa::k_enc_seam_topo<dsa::EncStream>, dim3((nz + 255) / 256), dim3(256), 0, st, d_conns, d_seams, nz, d_streams);
-        hipLaunchKernelGGL(dsa::k_enc_seam_rank, gz, dim3(256), 0, st, arena, d_conns, d_seams, nz);
-        hipLaunchKernelGGL(dsa::k_enc_seam_count, gz, dim3(256), 0, st, arena, d_conns, d_seams, nz);
-        hipLaunchKernelGGL(dsa::k_enc_seam_scan, dim3(nz), dim3(WAVE), 0, st, arena, d_conns, d_seams, nz);
-        hipLaunchKernelGGL(dsa::k_enc_seam_bits, gz, dim3(256), 0, st, arena, d_conns, d_seams, nz);
-      }
-    } else {
-      hipLaunchKernelGGL(dsa::k_enc_bounds, dim3(ns), dim3(256), 0, st, arena, d_streams, ns);
-      hipLaunchKernelGGL(dsa::k_enc_quantize, dim3(gx, ns), dim3(256), 0, st, arena, d_streams, ns);
-    }
-    // ---- device phase 1: quantise, order, correct, count
-    hipLaunchKernelGGL(dsa::k_enc_gather, dim3(ns), dim3(256), 0, st, arena, d_streams, ns);
-    hipLaunchKernelGGL(dsa::k_enc_corr, dim3(gx, ns), dim3(256), 0, st, arena, d_streams, ns);
-    if (any_multi) hipLaunchKernelGGL(dsa::k_enc_multi<dsa::EncStream>, dim3(gx, ns), dim3(256), 0, st, arena, d_streams, ns);
-    if (any_crease) hipLaunchKernelGGL(dsa::k_enc_crease<dsa::EncStream>, dim3(ns), dim3(WAVE), 0, st, arena, d_streams, ns);
-    hipLaunchKernelGGL(dsa::k_enc_orient, dim3(ns), dim3(WAVE), 0, st, arena, d_streams, ns);
-    hipLaunchKernelGGL(dsa::k_enc_list_stats, dim3(ns), dim3(256), 0, st, arena, d_streams, ns);
-    if (!host_plan) {       // device phase 2 follows at once: tables by k_enc_plan, no host round trip
-      hipLaunchKernelGGL(dsa::k_enc_plan, dim3((ns + WAVE - 1) / WAVE), dim3(WAVE), 0, st, arena, d_streams, ns, (int)opt.force_scheme, (int)opt.compression_level);
-      hipLaunchKernelGGL(dsa::k_enc_rans, dim3(ns), dim3(WAVE), 0, st, arena, d_streams, ns);
-    }
-    ENC_TRY(hipMemcpyAsync(hs.data(), d_streams, sizeof(dsa::EncStream) * ns, hipMemcpyDeviceToHost, st));
-    if (!host_conn) ENC_TRY(hipMemcpyAsync(hc.data(), d_conns, sizeof(dsa::EncConn) * n, hipMemcpyDeviceToHost, st));
-    if (nz) ENC_TRY(hipMemcpyAsync(hz.data(), d_seams, sizeof(dsa::EncSeam) * nz, hipMemcpyDeviceToHost, st));
-    ENC_TRY(hipStreamSynchronize(st));
-    lap("device phases 0 + 1");
-    if (!host_conn) {
-      // what the stream layout needs of the connectivity: symbols, start-face bits, split events, two counts
-      std::vector<dsa::PackItem> conn_items;
-      for (uint32_t i = 0; i < n; ++i) {
-        if (E->status[i] != DSA_OK) continue;
-        const dsa::EncConn &C = hc[i];
-        if (C.status != dsa::ENC_OK) {
-          E->status[i] = DSA_ERR_INVALID_DATA; E->messages[i] = dsa::enc_conn_message(C.status);
-          for (uint32_t sk = first_stream[i]; sk < first_stream[i + 1]; ++sk) hs[sk].overflow = 1;       // its attribute streams are not coded
-          continue;
-        }
-        conn_items.push_back({C.symbols, 0, C.num_symbols, i});
-        conn_items.push_back({C.start_bits, 0, C.num_start_bits, i});
-        conn_items.push_back({C.splits, 0, 12u * C.num_splits, i});
-        plans[i].interior_edges = (int64_t)C.interior_edges;
-      }
-      std::vector<uint8_t> unused;
-      const uint8_t *conn_host = nullptr;
-      ENC_ST(gather(conn_items, unused, &conn_host));
-      hostutil::parallel_for((uint32_t)(conn_items.size() / 3), [&](uint32_t m) {
-        const size_t k = 3 * (size_t)m;
-        const uint32_t i = conn_items[k].pad;
-        const dsa::EncConn &C = hc[i];
-        synth::EbResult &eb = plans[i].eb;
-        eb.num_split_symbols = C.num_split_symbols;
-        if (conn_items[k].len) eb.symbols.assign(conn_host + conn_items[k].packed_off, conn_host + conn_items[k].packed_off + conn_items[k].len);
-        if (conn_items[k + 1].len) eb.start_face_bits.assign(conn_host + conn_items[k + 1].packed_off, conn_host + conn_items[k + 1].packed_off + conn_items[k + 1].len);
-        eb.splits.resize(C.num_splits);
-        const uint32_t *sp = C.num_splits ? (const uint32_t *)(conn_host + conn_items[k + 2].packed_off) : nullptr;
-        for (size_t q = 0; q < eb.splits.size(); ++q) eb.splits[q] = {sp[3 * q], sp[3 * q + 1], sp[3 * q + 2]};
-      }, 8);
-      // attributes given per corner: a failed seam step fails its mesh; the seam bits of seamed attributes come down packed
-      std::vector<dsa::PackItem> seam_items;
-      for (uint32_t z = 0; z < nz; ++z) {
-        const dsa::EncSeam &Z = hz[z];
-        const uint32_t i = Z.mesh;
-        if (E->status[i] != DSA_OK) continue;
-        if (Z.status != dsa::ENC_SEAM_OK) {
-          E->status[i] = DSA_ERR_INVALID_DATA; E->messages[i] = dsa::enc_seam_message(Z.status);
-          for (uint32_t sk = first_stream[i]; sk < first_stream[i + 1]; ++sk) hs[sk].overflow = 1;
-          continue;
-        }
-        synth::MeshPlan &pl = plans[i];
-        if (pl.seamed_given.empty()) pl.seamed_given.assign(pl.atts.size(), 0);
-        pl.seamed_given[Z.stream - first_stream[i]] = Z.interior_seams ? 1 : 0;
-        if (Z.interior_seams) seam_items.push_back({Z.bits, 0, 4u * ((hc[i].interior_edges + 31u) / 32u), z});
-      }
-      std::vector<uint8_t> seam_host;
-      ENC_ST(gather(seam_items, seam_host, nullptr));
-      for (auto &it : seam_items) {
-        const dsa::EncSeam &Z = hz[it.pad];
-        synth::MeshPlan &pl = plans[Z.mesh];
-        if (E->status[Z.mesh] != DSA_OK) continue;
-        const uint32_t ne = hc[Z.mesh].interior_edges;
-        if (pl.seam_bits_given.empty()) pl.seam_bits_given.assign(pl.atts.size(), std::vector<uint8_t>(ne, 0));
-        std::vector<uint8_t> &b = pl.seam_bits_given[Z.stream - first_stream[Z.mesh]];
-        const uint32_t *words = (const uint32_t *)(seam_host.data() + it.packed_off);
-        for (uint32_t e = 0; e < ne; ++e) b[e] = (uint8_t)((words[e >> 5] >> (e & 31u)) & 1u);
-      }
-    }
-  }
-  lap("connectivity results");
-  // ---- host phase 2: scheme choice and rANS tables from the device statistics
-  std::vector<synth::SymbolPlan> splans(ns);
-  std::vector<int> stream_mesh(ns, 0);
-  for (uint32_t i = 0; i < n; ++i) for (uint32_t s = first_stream[i]; s < first_stream[i + 1]; ++s) stream_mesh[s] = (int)i;
-  if (host_plan) { const dsa_status ps = enc_host_plans(ctx, lane, arena, hs, stream_mesh, E, opt, splans); if (ps != DSA_OK) return ps; }
-  else enc_device_plan_errors(hs, stream_mesh, E);
-  lap("histograms + symbol plans");
-  // ---- device phase 2: entropy coding
-  std::vector<std::vector<uint8_t>> rans(ns), bits(ns), flag_bits(ns), crease(any_crease ? 4 * (size_t)ns : 0);
-  if (ns) { const dsa_status cs = enc_code_streams(ctx, lane, arena, d_streams, hs, stream_mesh, E, host_plan, splans, rans, bits, flag_bits, any_crease ? &crease : nullptr); if (cs != DSA_OK) return cs; }
-  lap("device phase 2 + downloads");
-  cleanup();
-  // ---- host phase 3: stream layout (threads over meshes; write_stream may throw like any part of the host coder)
-  auto layout_one = [&](uint32_t i) {
-    if (E->status[i] != DSA_OK) return;
-    bool bad = false;
-    for (uint32_t s = first_stream[i]; s < first_stream[i + 1]; ++s) bad = bad || hs[s].overflow;     // (the context lists included)
-    if (bad) { E->status[i] = DSA_ERR_INVALID_DATA; E->messages[i] = "entropy coding failed"; return; }
-    synth::ByteWriter w;
-    const uint32_t s0 = first_stream[i];
-    auto coded = [&](synth::ByteWriter &bw, uint32_t s) { enc_put_coded(bw, splans[s], rans[s], bits[s], hs[s].method); };
-    try {
-    synth::MeshPlan &pl = plans[i];
-    if (pl.valence) {                                        // the six context lists: their streams follow the attributes'
-      const uint32_t v0 = s0 + (uint32_t)pl.atts.size();
-      pl.ctx_given = true;
-      for (uint32_t k = 0; k < 6; ++k) {
-        pl.ctx_count[k] = hs[v0 + k].nv;
-        synth::ByteWriter bw;
-        if (hs[v0 + k].nv) coded(bw, v0 + k);
-        pl.ctx_coded[k].swap(bw.d);
-      }
-    }
-    synth::write_stream(w, ins[i], pl,
-      [&](synth::ByteWriter &bw, size_t k) {               // SequentialIntegerAttributeEncoder.cs:55-128
-        const dsa::EncStream &S = hs[s0 + k];
-        const synth::PortableAttr &a = pl.atts[k];
-        const bool geometric = S.kind == 1 && S.prediction == 6, portable = S.kind == 0 && S.prediction == 5;
-        if (S.kind == 1) { bw.i8(geometric ? 6 : 0); bw.i8(3); } else { bw.i8((int8_t)a.prediction); bw.i8(1); }
-        bw.u8(1);
-        coded(bw, s0 + (uint32_t)k);
-        if (portable) { bw.i32((int32_t)flag_bits[s0 + k].size()); synth::write_rabs(bw, flag_bits[s0 + k]); }
-        if (S.kind != 1 && S.prediction == 4)                  // ...ConstrainedMultiParallelogramEncoder.cs: the four crease lists
-          for (size_t j = 0; j < 4; ++j) { const std::vector<uint8_t> &cl = crease[4 * (s0 + k) + j]; bw.varint(cl.size()); if (!cl.empty()) synth::write_rabs(bw, cl); }
-        if (S.kind == 1) { const int32_t max_q = (1 << S.bits) - 1; bw.i32(max_q); bw.i32((max_q - 1) / 2); }
-        else { bw.i32(S.wrap_mn); bw.i32(S.wrap_mx); }
-        if (geometric) synth::write_rabs(bw, flag_bits[s0 + k]);
-      },
-      [&](synth::ByteWriter &bw, size_t k) {               // AttributeQuantizationTransform.cs:123-134 / AttributeOctahedronTransform.cs:44-47
-        const dsa::EncStream &S = hs[s0 + k];
-        if (S.kind == 0) { for (uint32_t c = 0; c < S.nc_out; ++c) bw.f32(S.qmin[c]); bw.f32(S.qrange); bw.u8((uint8_t)S.bits); }
-        else if (S.kind == 1) bw.u8((uint8_t)S.bits);            // (an integer attribute has no transform to describe)
-      });
-    } catch (const std::exception &e) { E->status[i] = DSA_ERR_INVALID_DATA; E->messages[i] = e.what(); return; }
-    E->streams[i].swap(w.d);
-  };
-  hostutil::parallel_for(n, layout_one);
-  lap("stream layout");
-  *out = E_owner.release();
-  return DSA_OK;
+void dsa_encode_sequential_default_options(dsa_encode_sequential_options *o) {
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  dsa_encode_default_options(&o->base);
+  o->geometry = 1;
+  o->compress_connectivity = 0;
 }
+
+// Every entry point: a request at the defaults, the caller's meshes and options into it, encode_request.
+static EncRequest enc_request(uint32_t n, bool sequential) {
+  EncRequest rq;
+  rq.n = n; rq.sequential = sequential;
+  dsa_encode_default_level_options(&rq.level);
+  dsa_encode_sequential_default_options(&rq.seq);
+  return rq;
+}
+static dsa_status encode_request(dsa_context *ctx, const EncRequest &rq, dsa_encoded **out) {
+  if (!ctx || !out || (rq.n && !rq.vertex && !rq.corners && !rq.listed)) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "null argument");
+  if (enc_check_request(ctx, rq) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+  DSA_GUARD(ctx, encode_batch_chunks(ctx, rq.n, [&](dsa_context *sink, EncLane &lane, uint32_t base, uint32_t cnt, dsa_encoded **part) {      // host vectors and threads inside: nothing may unwind into the caller
+    return rq.sequential ? encode_sequential_chunk(sink, lane, rq, base, cnt, rq.n, part) : encode_chunk(sink, lane, rq, base, cnt, rq.n, part);
+  }, out));
+}
+dsa_status dsa_encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_encode_options *options, dsa_encoded **out) {
+  EncRequest rq = enc_request(n, false);
+  rq.vertex = meshes;
+  if (options) rq.level.ex.base = *options;
+  return encode_request(ctx, rq, out);
+}
+dsa_status dsa_encode_batch_corners(dsa_context *ctx, uint32_t n, const dsa_mesh_corner_input *meshes, const dsa_encode_options *options, dsa_encoded **out) {
+  EncRequest rq = enc_request(n, false);
+  rq.corners = meshes;
+  if (options) rq.level.ex.base = *options;
+  return encode_request(ctx, rq, out);
+}
+dsa_status dsa_encode_batch_ex(dsa_context *ctx, uint32_t n, const dsa_mesh_corner_input *meshes, const dsa_encode_options_ex *options, dsa_encoded **out) {
+  EncRequest rq = enc_request(n, false);
+  rq.corners = meshes;
+  if (options) rq.level.ex = *options;
+  return encode_request(ctx, rq, out);
+}
+dsa_status dsa_encode_attributes_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_encode_options_ex *options, dsa_encoded **out) {
+  EncRequest rq = enc_request(n, false);
+  rq.listed = meshes;
+  if (options) rq.level.ex = *options;
+  return encode_request(ctx, rq, out);
+}
+// The levels above the default: MultiParallelogram / ConstrainedMultiParallelogram in place of Parallelogram, prediction-degree
+// attribute order (dsa_encode_multi.h).  With both at 0 this is dsa_encode_attributes_batch.
+dsa_status dsa_encode_level_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_encode_level_options *options, dsa_encoded **out) {
+  EncRequest rq = enc_request(n, false);
+  rq.listed = meshes;
+  if (options) rq.level = *options;
+  return encode_request(ctx, rq, out);
+}
+dsa_status dsa_encode_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_encode_sequential_options *options, dsa_encoded **out) {
+  EncRequest rq = enc_request(n, true);
+  rq.vertex = meshes;
+  if (options) rq.seq = *options;
+  return encode_request(ctx, rq, out);
+}
+dsa_status dsa_encode_attributes_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_encode_sequential_options *options, dsa_encoded **out) {
+  EncRequest rq = enc_request(n, true);
+  rq.listed = meshes;
+  if (options) rq.seq = *options;
+  return encode_request(ctx, rq, out);
+}
+
 
 uint32_t dsa_encoded_size(const dsa_encoded *e) { return e ? (uint32_t)e->streams.size() : 0; }
 
@@ -1569,7 +1244,6 @@ void dsa_encoded_free(dsa_encoded *e) { delete e; }
 
 }  // extern "C"
 
-#include "dsa_encode_sequential.h"
-
 #undef ENC_TRY
 #undef ENC_ST
+#undef ENC_STAGE

@@ -1,0 +1,580 @@
+// draco-sharp_amd/csrc/dsa_encode_layout.h  (included by dsa_encode.h)
+//
+// Encode direction, the part of a chunk's host work that needs no device and nothing of HIP (it compiles with plain g++ like
+// dsa_encode_host.h; tests/hostcheck/enclayout_host.cpp runs it under AddressSanitizer):
+//   EncRequest   a call of any encode entry point: the mesh array in the form it arrived, the options in their widest struct
+//   EncChunk     the state of one chunk of a request on its way through the stages of encode_chunk / encode_sequential_chunk
+//   enc_plan_mesh / enc_check_sequential_mesh   the host's checks of a mesh and its plan (what the threads over meshes run)
+//   enc_layout / enc_layout_sequential          the arena: EncStream / EncConn / EncSeam / EncSeqIdx records, upload lists, sizes
+// The arena is laid out by one allocator in two passes over the meshes: the first places what the host provides (faces, corner
+// ids, entry maps, topology views, source values, context lists) and lists it for upload, input_bytes is where it ends; the
+// second hands out everything the kernels write from there on.  No size is computed anywhere else.
+#pragma once
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <memory>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../include/draco_mi355x.h"
+#include "dsa_common.h"
+#include "dsa_encode_host.h"
+#include "dsa_encode_conn.h"
+#include "dsa_encode_seams.h"
+#include "dsa_encode_seqidx.h"
+#include "dsa_encode_schemes.h"
+#include "dsa_encode_multi.h"
+
+namespace dsa {
+
+struct EncStream {                 // one per (mesh, attribute); lives in device memory, mirrored on the host
+  uint64_t src;                    // f32 source values, vertex order, nc_out per vertex
+  uint64_t e2v, ops;               // per mesh: entry -> vertex; i32[3*entries] parallelogram operand entries (next, prev, opposite) or -1
+  uint64_t vals, d, syms, bl;      // i32[nv*nc] vertex order, i32[nv*nc] traversal order, u32[nv*nc] symbols, u8[nv] bit length per entry
+  uint64_t hist_raw;               // u32[hist_cap]
+  uint64_t out_rans, out_bits;     // coded bytes
+  uint64_t prob, cum;              // u32[num_symbols] (filled by the host between the two device phases)
+  uint32_t nv, nc_out, nc, kind;   // nv: entries; kind 0: quantised + wrap, 1: normals (octahedral, canonicalised delta), 2: integers + wrap (src: elements of
+                                   //   type `elem`), 3: a valence context list of the connectivity (syms given, nc 1; no values, no prediction)
+  uint32_t rows, rows_pad;         // value rows of `src` / `vals` (= nv, but for an attribute given per corner: its row count; k_enc_seam_operands sets nv)
+  uint32_t bits, prediction, hist_cap, out_cap;
+  float qmin[4], qrange;
+  int32_t wrap_mn, wrap_mx;
+  uint32_t max_value, overflow;
+  unsigned long long total_bl;
+  uint32_t hist_tag[33];
+  uint32_t method, precision_bits, num_symbols;
+  uint32_t rans_len, bits_len;
+  uint64_t plan_order, plan_tmp;   // u32[table_cap] each: scratch of k_enc_plan
+  uint32_t usbl, plan_status;      // raw scheme: unique-symbols bit length; dsa::plan::PLAN_* of k_enc_plan
+  // prediction 5 (TexCoordsPortable, kind 0) and 6 (GeometricNormal, kind 1): the topology view of dsa_encode_schemes.h (EncTopo)
+  // -- set by the host, for a seamed attribute on the device path by k_enc_seam_topo -> k_enc_corr
+  uint64_t pos_vals, t_c2p, t_c2a, t_opp, t_d2c, t_v2d;
+  uint64_t ori;                    // u8[cap] per entry 0 / 2 / 3 (TexCoordsPortable's branch and orientation) -- k_enc_corr -> k_enc_orient
+  uint64_t flags;                  // u32[(cap + 31) / 32] side bits, bit k of the list: orientations (delta-coded against true, last
+                                   //   entry first; k_enc_orient) or flips (entry order; k_enc_corr) -- -> download (write_rabs)
+  uint32_t t_nc3, num_flags;       // 3F; OUTPUT: bits in `flags`
+  // prediction 2 / 4 (MultiParallelogram, ConstrainedMultiParallelogram; kind 0 and 2; dsa_encode_multi.h): the topology view above;
+  // prediction 4: `ori` holds per entry the parallelograms found and their crease flags (k_enc_multi -> k_enc_crease), `flags` the
+  // four crease lists, list j packed from word cr_at[j] on, cr_n[j] bits (OUTPUT) -- k_enc_crease -> download (write_rabs)
+  uint32_t cr_at[4], cr_n[4];
+  uint32_t pd_want, pad_level;     // pd_want: an attribute given per corner whose decoder takes the prediction-degree order unless it is seamed
+  uint32_t linear, elem;           // linear: entry i is value row i (sequential streams, dsa_encode_sequential.h): `d` is `vals`, no e2v, no gather
+                                   // elem (kind 2): Draco's data type of `src`, 1 int8, 2 uint8, 3 int16, 4 uint16, 5 int32, 6 uint32
+};
+
+// The raw symbol scheme takes symbols below 2^18 (dsa_symbol_plan.h choose_scheme; symbol_stats of the host coder builds no
+// histogram of values beyond): no stream's histogram is larger than this, and a stream whose histogram has this size may hold
+// symbols beyond it (32-bit integer attributes with spread values) -- those are not counted, and k_enc_plan goes the tagged way.
+static const uint32_t ENC_RAW_SYMBOL_LIMIT = 1u << 18, ENC_HIST_CAP_LIMIT = ENC_RAW_SYMBOL_LIMIT + 2u;
+static_assert(ENC_HIST_CAP_LIMIT == EM_HIST_CAP_LIMIT, "k_enc_multi counts symbols like k_enc_corr");
+// hist_cap of an integer attribute whose values (as int32) span lo .. hi: zig-zagged wrapped corrections lie in 0 .. hi - lo + 1
+static inline uint32_t enc_integer_hist_cap(int32_t lo, int32_t hi) {
+  const uint64_t span = (uint64_t)((int64_t)hi - (int64_t)lo) + 3ull;
+  return (uint32_t)(span < ENC_HIST_CAP_LIMIT ? span : ENC_HIST_CAP_LIMIT);
+}
+
+// Value rows and entries of an attribute in traversal order (entry p: the value of the corner the walk reached it by; ids null:
+// the corner's vertex) and its parallelogram operand entries on table `ct` (MeshPredictionSchemeParallelogramEncoder.cs:35-56).
+template <class CT>
+static void entry_maps(const CT &ct, const synth::Sequence &seq, const uint32_t *ids, std::vector<uint32_t> &e2v, std::vector<int32_t> *ops) {
+  const uint32_t entries = (uint32_t)seq.data_to_corner.size();
+  e2v.resize(entries);
+  if (ops) ops->assign((size_t)3 * entries, -1);
+  for (uint32_t p = 0; p < entries; ++p) {
+    const uint32_t ci = seq.data_to_corner[p];
+    e2v[p] = ids ? ids[ci] : ct.vertex(ci);
+    if (p == 0 || !ops) continue;
+    const uint32_t oci = ct.opposite(ci);
+    if (oci == synth::kInvalid) continue;
+    const int32_t vo = seq.vertex_to_data[ct.vertex(oci)];
+    const int32_t vn = seq.vertex_to_data[ct.vertex(synth::CornerTable::next(oci))];
+    const int32_t vp = seq.vertex_to_data[ct.vertex(synth::CornerTable::prev(oci))];
+    if (vo < (int32_t)p && vn < (int32_t)p && vp < (int32_t)p) { (*ops)[3 * p] = vn; (*ops)[3 * p + 1] = vp; (*ops)[3 * p + 2] = vo; }
+  }
+}
+}  // namespace dsa
+
+struct dsa_encoded {
+  dsa_context *ctx = nullptr;
+  std::vector<std::vector<uint8_t>> streams;
+  std::vector<int32_t> status;
+  std::vector<std::string> messages;
+};
+
+// A call of an encode entry point.  The meshes in the form they arrived (one of the three pointers is set), the options in the
+// widest struct of their kind: what a narrower entry point does not have stays at its default, which every check passes.
+struct EncRequest {
+  uint32_t n = 0;
+  const dsa_mesh_input *vertex = nullptr;
+  const dsa_mesh_corner_input *corners = nullptr;
+  const dsa_mesh_attr_input *listed = nullptr;
+  bool sequential = false;
+  dsa_encode_level_options level;          // Edgebreaker streams
+  dsa_encode_sequential_options seq;       // sequential streams
+  const dsa_encode_options &base() const { return sequential ? seq.base : level.ex.base; }
+  const dsa_mesh_corner_input *corner(size_t i) const { return listed ? &listed[i].mesh : (corners ? &corners[i] : nullptr); }      // null for the per-vertex form
+  const dsa_mesh_input &mesh(size_t i) const { const dsa_mesh_corner_input *c = corner(i); return c ? c->mesh : vertex[i]; }
+  const dsa_mesh_attr_input *attr(size_t i) const { return listed ? &listed[i] : nullptr; }                                         // null unless listed
+};
+// the options as the host coder takes them (a sequential stream has no connectivity, prediction or traversal options)
+static synth::Options enc_synth_options(const EncRequest &rq) {
+  const dsa_encode_options &od = rq.base();
+  synth::Options opt;
+  opt.pos_bits = od.position_bits; opt.uv_bits = od.texcoord_bits; opt.normal_bits = od.normal_bits;
+  opt.force_scheme = od.symbol_scheme; opt.compression_level = od.compression_level;
+  if (rq.sequential) return opt;
+  opt.single_connectivity = od.single_connectivity; opt.pos_prediction = od.position_prediction; opt.uv_prediction = od.texcoord_prediction;
+  opt.normal_prediction = rq.level.ex.normal_prediction; opt.traversal_method = rq.level.traversal_method;
+  return opt;
+}
+
+struct EncUpload { uint64_t off; const void *src; size_t bytes; bool narrow; };       // narrow: src is u32[bytes / 2], the staging copy keeps the low halves
+// The arena, handed out in 256-byte aligned regions one behind the other.
+struct EncArena {
+  uint64_t cur = 0;
+  std::vector<std::pair<uint64_t, uint64_t>> *log = nullptr;      // (offset, bytes) of every region, for the host check of the layout
+  uint64_t take(uint64_t bytes) { const uint64_t at = cur; cur = (cur + bytes + 255) & ~255ull; if (log) log->push_back({at, bytes}); return at; }
+  uint64_t put(std::vector<EncUpload> &ups, const void *src, uint64_t bytes, bool narrow) { const uint64_t at = take(bytes); ups.push_back({at, src, (size_t)bytes, narrow}); return at; }
+};
+struct EncLayout {
+  std::vector<dsa::EncStream> streams;
+  std::vector<dsa::EncConn> conns;          // device connectivity: one per mesh (a mesh that failed the host's checks: F = 0, no arrays)
+  std::vector<dsa::EncSeam> seams;          // device connectivity: one per (mesh, attribute given per corner)
+  std::vector<dsa::EncSeqIdx> idx;          // sequential, compressed indices: one per mesh
+  std::vector<EncUpload> uploads_a, uploads;      // phase A: what the walks need (the faces, the corner ids; device connectivity only); the rest
+  std::vector<uint32_t> first_stream;       // streams of mesh i: first_stream[i] .. first_stream[i + 1]
+  uint64_t input_bytes = 0, total_bytes = 0;      // the uploads fill [0, input_bytes); the kernels' regions lie behind
+  uint32_t max_rows = 0, maxf = 0, max_count = 0; // grid sizes: value rows / entries of a stream, faces of a mesh, index symbols of a mesh
+  bool any_multi = false, any_crease = false, any_valence = false;      // streams predicted by method 2 / 4; by method 4; meshes coded with valence symbols
+};
+
+static inline bool enc_multi_scheme(const synth::PortableAttr &a) { return a.seq_type != 3 && (a.prediction == 2 || a.prediction == 4); }
+// the attribute reads the mesh's topology (TexCoordsPortable, GeometricNormal, the multi-parallelogram schemes)
+static inline bool enc_topo_scheme(const synth::PortableAttr &a) { return (a.seq_type == 2 && a.prediction == 5) || (a.seq_type == 3 && a.prediction == 6) || enc_multi_scheme(a); }
+
+struct EncChunk {
+  const EncRequest &rq;
+  uint32_t base, n, batch_n;               // meshes base .. base + n of the request's batch_n
+  synth::Options opt;
+  bool host_conn = false, host_plan = false, want_pd = false;     // connectivity / symbol plans by the host; the prediction-degree order beside the depth-first one
+  std::unique_ptr<dsa_encoded> E;           // per mesh: status, message and in the end the stream
+  std::vector<synth::MeshIn> ins;
+  std::vector<synth::MeshPlan> plans;       // (a sequential stream's: the attributes alone)
+  std::vector<std::vector<synth::ExtraAttr>> extras;
+  std::vector<std::vector<uint32_t>> extra_cap;                   // meshes with an attribute list, per attribute of the plan: hist_cap of an integer extra, else 0
+  // host connectivity: entry -> vertex and operand entries in depth-first and in prediction-degree order; per attribute given per
+  // corner its own entry -> value row, when it is seamed its own operands, with prediction 5 / 6 its table's opposites
+  std::vector<std::vector<uint32_t>> e2v, e2v_pd;
+  std::vector<std::vector<int32_t>> ops, ops_pd;
+  std::vector<std::vector<std::vector<uint32_t>>> att_e2v, att_opp;
+  std::vector<std::vector<std::vector<int32_t>>> att_ops;
+  EncLayout L;
+  std::vector<std::pair<uint64_t, uint64_t>> *region_log = nullptr;
+  // the device's side and what comes back from it
+  uint8_t *arena = nullptr;
+  dsa::EncStream *d_streams = nullptr;
+  dsa::EncConn *d_conns = nullptr;
+  dsa::EncSeam *d_seams = nullptr;
+  std::vector<int> stream_mesh;
+  std::vector<synth::SymbolPlan> splans;
+  std::vector<std::vector<uint8_t>> rans, bits, flag_bits, crease;      // per stream; crease[4 s + j]: list j of stream s
+
+  EncChunk(const EncRequest &r, uint32_t b, uint32_t cnt, uint32_t bn) : rq(r), base(b), n(cnt), batch_n(bn), opt(enc_synth_options(r)), E(new (std::nothrow) dsa_encoded()), ins(cnt), plans(cnt) {
+    if (!E) return;                        // (the chunk function answers)
+    E->streams.resize(n); E->status.assign(n, DSA_OK); E->messages.resize(n);
+    if (rq.listed) { extras.resize(n); extra_cap.resize(n); }
+  }
+  const dsa_mesh_input &mesh(uint32_t i) const { return rq.mesh(base + i); }
+  const dsa_mesh_corner_input *corner(uint32_t i) const { return rq.corner(base + i); }
+  bool good(uint32_t i) const { return E->status[i] == DSA_OK; }
+  void refuse(uint32_t i, dsa_status st, const std::string &why) { E->status[i] = st; E->messages[i] = why; }
+  // valence symbols per mesh: asked for, or by the reference's rule (speed < 5 and not a tiny mesh)
+  bool valence_of(uint32_t i) const { const int32_t m = rq.level.ex.edgebreaker_method; return !rq.sequential && (m == 2 || (m == -1 && opt.compression_level > 5 && mesh(i).num_faces >= 1000)); }
+  // MultiParallelogram per mesh: the method asked for, or by the reference's rule (speed < 2 and at least 40 points)
+  int32_t multi_of(uint32_t i) const { const int32_t m = rq.level.multi_parallelogram; return m == -1 ? ((opt.compression_level >= 9 && mesh(i).num_vertices >= 40) ? 4 : 0) : m; }
+  // value rows of an attribute of mesh i: its ids' row count when it is given per corner
+  uint32_t rows_of(uint32_t i, const synth::PortableAttr &a) const { return !a.corner_value ? mesh(i).num_vertices : (a.att_type == 1 ? corner(i)->num_normals : corner(i)->num_texcoords); }
+  bool ids_narrow(uint32_t i, const synth::PortableAttr &a) const { return rows_of(i, a) <= 65536; }
+  // the decoder of attribute k takes the prediction-degree order (MeshPlan::uses_pd; for an attribute given per corner on the
+  // device path: unless it turns out seamed -- k_enc_pd_corner_streams, k_enc_seam_topo)
+  bool uses_pd(uint32_t i, size_t k) const { return want_pd && (host_conn ? plans[i].uses_pd(k) : (opt.traversal_method == 2 || opt.single_connectivity != 0 || k == 0)); }
+  uint32_t hist_cap_of(uint32_t i, size_t k) const { return extra_cap.empty() ? 0u : extra_cap[i][k]; }
+};
+
+// The extras of a mesh with an attribute list as the host coder takes them (`ex` keeps them alive beside `in`); what the C structs
+// alone can say against them -- a reserved word -- is answered here, the rest by synth::extras_error.  "" when they can be written.
+static std::string enc_take_extras(const dsa_mesh_attr_input &am, std::vector<synth::ExtraAttr> &ex, synth::MeshIn &in) {
+  char buf[96];
+  if (am.reserved != 0) return "dsa_mesh_attr_input.reserved is not zero";
+  if (am.num_attributes && !am.attributes) return "attributes: the list is missing";
+  ex.resize(am.num_attributes);
+  for (uint32_t k = 0; k < am.num_attributes; ++k) {
+    const dsa_attribute_input &x = am.attributes[k];
+    for (int r = 0; r < 2; ++r)
+      if (x.reserved[r] != 0) { snprintf(buf, sizeof(buf), "attribute %u: reserved[%d] is not zero", k, r); return buf; }
+    ex[k].att_type = x.attribute_type; ex[k].data_type = x.data_type; ex[k].nc = x.num_components; ex[k].normalized = x.normalized;
+    ex[k].unique_id = x.unique_id; ex[k].bits = x.quantization_bits; ex[k].values = x.values;
+  }
+  in.extras = ex.data(); in.num_extras = am.num_attributes;
+  return synth::extras_error(in);
+}
+// hist_cap of an integer extra: one-byte types by their range, wider ones by the values present (a pass over the values by the
+// host thread that checks the mesh's indices anyway): zig-zagged wrapped corrections lie in 0 .. max - min + 1
+static uint32_t enc_extra_hist_cap(const synth::PortableAttr &a, uint32_t rows) {
+  if (synth::data_type_size(a.data_type) == 1) return (1u << 8) + 2u;
+  const size_t total = (size_t)rows * (size_t)a.nc;
+  int32_t lo = 0, hi = 0;
+  if (a.data_type == 3) { const int16_t *p = (const int16_t *)a.extra_values; int16_t l = p[0], h = p[0]; for (size_t k = 1; k < total; ++k) { l = p[k] < l ? p[k] : l; h = p[k] > h ? p[k] : h; } lo = l; hi = h; }
+  else if (a.data_type == 4) { const uint16_t *p = (const uint16_t *)a.extra_values; uint16_t l = p[0], h = p[0]; for (size_t k = 1; k < total; ++k) { l = p[k] < l ? p[k] : l; h = p[k] > h ? p[k] : h; } lo = l; hi = h; }
+  else { const int32_t *p = (const int32_t *)a.extra_values; lo = hi = p[0]; for (size_t k = 1; k < total; ++k) { lo = p[k] < lo ? p[k] : lo; hi = p[k] > hi ? p[k] : hi; } }     // (uint32 by reinterpretation)
+  return dsa::enc_integer_hist_cap(lo, hi);
+}
+// the bounds of the integer extras' values of mesh i, once its plan has said which attributes there are
+static void enc_extra_caps(EncChunk &ck, uint32_t i) {
+  if (!ck.rq.listed) return;
+  const std::vector<synth::PortableAttr> &atts = ck.plans[i].atts;
+  ck.extra_cap[i].assign(atts.size(), 0);
+  for (size_t k = 0; k < atts.size(); ++k)
+    if (atts[k].extra_values && atts[k].seq_type == 1) ck.extra_cap[i][k] = enc_extra_hist_cap(atts[k], ck.mesh(i).num_vertices);
+}
+
+// ---- Edgebreaker streams, host phase 1 for mesh i: the checks of everything the kernels index by, the attribute descriptors, and
+// with host connectivity the connectivity, traversal orders and entry maps
+static void enc_plan_mesh(EncChunk &ck, uint32_t i) {
+  const dsa_mesh_input &m = ck.mesh(i);
+  const synth::Options &opt = ck.opt;
+  synth::MeshIn &in = ck.ins[i];
+  in.pos = m.positions; in.nv = m.num_vertices; in.faces = m.faces; in.nf = m.num_faces; in.normals = m.normals; in.uvs = m.texcoords;
+  in.generic = (m.generic && m.generic_components >= 1 && m.generic_components <= 4) ? m.generic : nullptr;
+  if (const dsa_mesh_corner_input *cm = ck.corner(i)) {
+    if (m.generic && (m.generic_components < 1 || m.generic_components > 4)) return ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, "generic attribute needs 1 - 4 components");
+    if ((cm->normal_corners && !m.normals) || (cm->texcoord_corners && !m.texcoords)) return ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, "corner ids without their values");
+    in.normal_corners = cm->normal_corners; in.nn = cm->num_normals;
+    in.uv_corners = cm->texcoord_corners; in.nu = cm->num_texcoords;
+  }
+  if (ck.rq.listed) {
+    const std::string why = enc_take_extras(*ck.rq.attr(ck.base + i), ck.extras[i], in);
+    if (!why.empty()) return ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, why);
+  }
+  try {
+    synth::check(m.positions && m.faces && m.num_vertices >= 3 && m.num_faces >= 1, "mesh needs positions and faces");
+    for (size_t k = 0; k < (size_t)m.num_faces * 3; ++k) synth::check(m.faces[k] < m.num_vertices, "face index out of range");
+    if (in.normal_corners) for (size_t k = 0; k < (size_t)m.num_faces * 3; ++k) synth::check(in.normal_corners[k] < in.nn, "normal id out of range");
+    if (in.uv_corners) for (size_t k = 0; k < (size_t)m.num_faces * 3; ++k) synth::check(in.uv_corners[k] < in.nu, "texture coordinate id out of range");
+    synth::check(ck.host_conn || (uint64_t)m.num_faces * 3 <= (uint64_t)dsa::EC_CORNER_MASK, "mesh too large for the device connectivity coder");
+    synth::Options mo = opt;                                   // (the components of the generic attribute are the mesh's own)
+    mo.generic_components = in.generic ? (int32_t)m.generic_components : 1;
+    mo.predictive_connectivity = ck.valence_of(i) ? 2 : 0;
+    if (const int32_t mp = ck.multi_of(i)) {                   // in place of Parallelogram (plan_attributes: the generic attribute and the extras follow the positions to method 4)
+      if (opt.pos_prediction == 1) mo.pos_prediction = mp;
+      if (opt.uv_prediction == 1) mo.uv_prediction = mp;
+    }
+    synth::MeshPlan &pl = ck.plans[i];
+    if (!ck.host_conn) {                                       // the rest of the plan comes from the device
+      synth::check(!((in.normal_corners || in.uv_corners) && opt.single_connectivity), "attributes given per corner need a connectivity of their own (single_connectivity = 0)");
+      synth::check(!(in.normal_corners || in.uv_corners) || 24ull * m.num_faces + 16u < (1ull << 32), "mesh too large for the device connectivity coder");
+      synth::plan_attributes(in, mo, pl);
+      enc_extra_caps(ck, i);
+      return;
+    }
+    synth::plan_mesh(in, mo, pl);
+    enc_extra_caps(ck, i);
+    dsa::entry_maps(pl.ct, pl.seq, nullptr, ck.e2v[i], &ck.ops[i]);
+    if (ck.want_pd) dsa::entry_maps(pl.ct, pl.seq_pd, nullptr, ck.e2v_pd[i], &ck.ops_pd[i]);
+    ck.att_e2v[i].assign(pl.atts.size(), {}); ck.att_ops[i].assign(pl.atts.size(), {}); ck.att_opp[i].assign(pl.atts.size(), {});
+    for (size_t k = 1; k < pl.atts.size(); ++k) {
+      const uint32_t *ids = pl.atts[k].corner_value;
+      if (!ids) continue;
+      if (pl.seamed(k)) dsa::entry_maps(pl.conns[k], pl.seq_att[k], ids, ck.att_e2v[i][k], &ck.att_ops[i][k]);
+      else dsa::entry_maps(pl.ct, pl.uses_pd(k) ? pl.seq_pd : pl.seq, ids, ck.att_e2v[i][k], nullptr);      // (the positions' operands)
+      if (!pl.seamed(k) || !enc_topo_scheme(pl.atts[k])) continue;
+      std::vector<uint32_t> &o = ck.att_opp[i][k];
+      o.resize(pl.ct.nc());
+      for (uint32_t c = 0; c < pl.ct.nc(); ++c) o[c] = pl.conns[k].opposite(c);
+    }
+  } catch (const std::exception &e) { ck.refuse(i, DSA_ERR_INVALID_DATA, e.what()); }
+}
+// the chunk's switches and the vectors enc_plan_mesh fills (DSA_ENC_HOST_CONN / DSA_ENC_HOST_PLAN as the caller read them)
+static void enc_begin_plans(EncChunk &ck, bool host_conn, bool host_plan) {
+  ck.host_conn = host_conn; ck.host_plan = host_plan; ck.want_pd = ck.opt.traversal_method != 0;
+  if (!host_conn) return;
+  ck.e2v.resize(ck.n); ck.ops.resize(ck.n); ck.att_e2v.resize(ck.n); ck.att_ops.resize(ck.n); ck.att_opp.resize(ck.n);
+  if (ck.want_pd) { ck.e2v_pd.resize(ck.n); ck.ops_pd.resize(ck.n); }
+}
+
+// ---- sequential streams, the host's checks of mesh i (everything the kernels index by) and its attribute descriptors
+static void enc_check_sequential_mesh(EncChunk &ck, uint32_t i) {
+  const dsa_mesh_input &m = ck.mesh(i);
+  const bool is_mesh = ck.rq.seq.geometry == 1, compressed = is_mesh && ck.rq.seq.compress_connectivity == 1;
+  if (!m.positions || m.num_vertices == 0) return ck.refuse(i, DSA_ERR_INVALID_DATA, "positions are missing");
+  if (!is_mesh && m.num_faces != 0) return ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, "a point cloud has no faces (geometry = 0, num_faces != 0)");
+  if (is_mesh && (m.num_faces == 0 || !m.faces)) return ck.refuse(i, DSA_ERR_INVALID_DATA, "a mesh needs faces");
+  if (m.generic && (m.generic_components < 1 || m.generic_components > 4)) return ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, "generic attribute needs 1 - 4 components");
+  if (ck.rq.listed && (ck.corner(i)->normal_corners || ck.corner(i)->texcoord_corners))
+    return ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, "corner ids with a sequential stream: it has one value per point (normal_corners / texcoord_corners must be NULL)");
+  // (what the 32-bit sizes of a stream's regions hold: 4 bytes per component and symbol, and a margin)
+  if (m.num_vertices > (1u << 28) || (compressed && m.num_faces > (1u << 28))) return ck.refuse(i, DSA_ERR_INVALID_DATA, "mesh too large for the device coder");
+  if (is_mesh) {
+    uint32_t top = 0;
+    for (size_t k = 0, nk = (size_t)m.num_faces * 3; k < nk; ++k) top = m.faces[k] > top ? m.faces[k] : top;
+    if (top >= m.num_vertices) return ck.refuse(i, DSA_ERR_INVALID_DATA, "face index out of range");
+  }
+  synth::MeshIn &in = ck.ins[i];
+  in.pos = m.positions; in.nv = m.num_vertices; in.faces = is_mesh ? m.faces : nullptr; in.nf = is_mesh ? m.num_faces : 0;
+  in.normals = m.normals; in.uvs = m.texcoords; in.generic = m.generic;
+  synth::Options mo = ck.opt;
+  mo.generic_components = m.generic ? (int32_t)m.generic_components : 1;
+  if (ck.rq.listed) {
+    const std::string why = enc_take_extras(*ck.rq.attr(ck.base + i), ck.extras[i], in);
+    if (!why.empty()) return ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, why);
+  }
+  synth::plan_sequential_attributes(in, mo, ck.plans[i].atts);
+  enc_extra_caps(ck, i);
+}
+
+// ---- the regions of a stream, shared by both layouts
+// A value stream's description and its source values among the inputs (`rows` of them; S.nv, S.prediction, S.linear: the caller's).
+static void enc_value_stream_input(dsa::EncStream &S, const synth::PortableAttr &a, const dsa_mesh_input &m, uint32_t rows, EncArena &A, std::vector<EncUpload> &ups) {
+  const bool integer = a.seq_type == 1;                  // the generic uint8 attribute, an integer extra
+  const void *src = a.extra_values ? a.extra_values
+                    : (a.att_type == 0 ? (const void *)m.positions : (a.att_type == 1 ? (const void *)m.normals : (integer ? (const void *)m.generic : (const void *)m.texcoords)));
+  S.rows = rows; S.nc_out = (uint32_t)a.nc_out; S.nc = (uint32_t)a.nc; S.kind = a.seq_type == 3 ? 1u : (integer ? 2u : 0u);
+  S.bits = integer ? 9u : (uint32_t)a.bits;              // (9: the zig-zagged corrections of bytes are below 512)
+  S.elem = integer ? (uint32_t)a.data_type : 0u;
+  S.src = A.put(ups, src, (integer ? (uint64_t)synth::data_type_size(a.data_type) : 4ull) * rows * S.nc_out, false);
+}
+static void enc_table_regions(dsa::EncStream &S, EncArena &A) {
+  const uint64_t table_cap = std::max<uint64_t>(S.hist_cap, 64);   // the tagged scheme's alphabet is 33 bit lengths
+  S.prob = A.take(4ull * table_cap); S.cum = A.take(4ull * table_cap);
+  S.plan_order = A.take(4ull * table_cap); S.plan_tmp = A.take(4ull * table_cap);
+}
+// What the kernels write of a value stream of up to `cap` entries; hist_cap: of an integer extra by the values present, 0: by the bits.
+static void enc_value_stream_regions(dsa::EncStream &S, uint32_t cap, uint32_t hist_cap, EncArena &A) {
+  S.vals = A.take(4ull * S.rows * S.nc);
+  S.d = S.linear ? S.vals : A.take(4ull * cap * S.nc);   // linear order: the values are the entries
+  S.syms = A.take(4ull * cap * S.nc); S.bl = A.take(cap);
+  S.hist_cap = hist_cap ? hist_cap : (1u << S.bits) + 2u;        // zig-zag of a wrapped correction / a positive octahedral correction fits
+  S.hist_raw = A.take(4ull * S.hist_cap);
+  S.out_cap = 4u * cap * S.nc + 16u;                     // (tagged bit fields are at most 32 bits a symbol, a coded symbol at most 20 bits and the flush)
+  S.out_rans = A.take(S.out_cap); S.out_bits = A.take(S.out_cap);
+  enc_table_regions(S, A);
+}
+// A list stream (kind 3: one component, its symbols given) of `count` symbols below hist_cap, and its regions.  own: symbols, bit
+// lengths and coded bytes lie in regions of the stream's own (else a kernel points it at regions of its mesh and sets the count);
+// syms_given: the symbols are among the inputs.
+static void enc_list_stream(dsa::EncStream &S, uint32_t hist_cap, uint32_t count) { S.kind = 3; S.nc = S.nc_out = 1; S.hist_cap = hist_cap; S.nv = count; }
+static void enc_list_stream_regions(dsa::EncStream &S, EncArena &A, bool own, bool syms_given) {
+  S.hist_raw = A.take(4ull * S.hist_cap);
+  enc_table_regions(S, A);
+  if (!own) return;
+  if (!syms_given) S.syms = A.take(4ull * S.nv);
+  S.bl = A.take(S.nv); S.out_cap = 4u * S.nv + 16u; S.out_rans = A.take(S.out_cap); S.out_bits = A.take(S.out_cap);
+}
+// records of the chunk's streams, all zero, and first_stream from the streams each mesh that passed its checks has beside its attributes'
+static void enc_layout_begin(EncChunk &ck, uint32_t more_streams_of_valence, uint32_t more_streams) {
+  EncLayout &L = ck.L;
+  L.first_stream.assign(ck.n + 1, 0);
+  for (uint32_t i = 0; i < ck.n; ++i) {
+    L.any_valence = L.any_valence || ck.valence_of(i);
+    L.first_stream[i + 1] = L.first_stream[i] + (ck.good(i) ? (uint32_t)ck.plans[i].atts.size() + more_streams + (ck.valence_of(i) ? more_streams_of_valence : 0u) : 0u);
+  }
+  dsa::EncStream zero;
+  memset(&zero, 0, sizeof(zero));
+  L.streams.assign(L.first_stream[ck.n], zero);
+}
+
+// ---- the arena of a chunk of Edgebreaker streams
+static void enc_layout(EncChunk &ck) {
+  EncLayout &L = ck.L;
+  const uint32_t n = ck.n;
+  const bool host_conn = ck.host_conn, want_pd = ck.want_pd;
+  EncArena A;
+  A.log = ck.region_log;
+  enc_layout_begin(ck, 6, 0);
+  // inputs, phase A (device connectivity): the faces, and right behind them the corner ids (the seam kernels read them as they
+  // were uploaded).  Half of what the walks wait for is the upload of the faces: indices below 65 536 are narrowed to 16 bits by
+  // the copy into pinned staging (which reads them anyway) and widened by the first kernel of the chunk; the ids likewise.
+  if (!host_conn) {
+    dsa::EncConn none;
+    memset(&none, 0, sizeof(none));
+    none.status = dsa::ENC_ISOLATED;
+    L.conns.assign(n, none);
+  }
+  for (uint32_t i = 0; i < n && !host_conn; ++i) {
+    if (!ck.good(i)) continue;
+    const dsa_mesh_input &m = ck.mesh(i);
+    const std::vector<synth::PortableAttr> &atts = ck.plans[i].atts;
+    dsa::EncConn &C = L.conns[i];
+    C.status = dsa::ENC_OK;
+    C.F = m.num_faces; C.V = m.num_vertices; C.split_cap = C.F; C.fail_key = 0xFFFFFFFFu;
+    C.vstream = ck.valence_of(i) ? L.first_stream[i] + (uint32_t)atts.size() : DSA_INVALID;
+    C.faces_narrow = C.V <= 65536 ? 1u : 0u;
+    (C.faces_narrow ? C.faces16 : C.faces) = A.put(L.uploads_a, m.faces, (C.faces_narrow ? 6ull : 12ull) * C.F, C.faces_narrow != 0);
+    L.maxf = std::max(L.maxf, C.F);
+    for (size_t k = 0; k < atts.size(); ++k) {
+      if (!atts[k].corner_value) continue;
+      dsa::EncSeam Z;
+      memset(&Z, 0, sizeof(Z));
+      Z.mesh = i; Z.stream = L.first_stream[i] + (uint32_t)k; Z.ids_narrow = ck.ids_narrow(i, atts[k]) ? 1u : 0u; Z.rows = ck.rows_of(i, atts[k]);
+      Z.ids = A.put(L.uploads_a, atts[k].corner_value, (Z.ids_narrow ? 6ull : 12ull) * C.F, Z.ids_narrow != 0);
+      L.seams.push_back(Z);
+    }
+  }
+  // inputs, the rest: the source values of every stream; with host connectivity also the entry maps of the mesh (and of attributes
+  // given per corner), the topology views of the schemes that read them, and the valence context lists
+  for (uint32_t i = 0; i < n; ++i) {
+    if (!ck.good(i)) continue;
+    const dsa_mesh_input &m = ck.mesh(i);
+    const synth::MeshPlan &pl = ck.plans[i];
+    const uint32_t V = m.num_vertices, s0 = L.first_stream[i];
+    auto put = [&](const void *src, uint64_t bytes) { return A.put(L.uploads, src, bytes, false); };
+    uint64_t o_e2v[2] = {0, 0}, o_ops[2] = {0, 0}, t_c2v = 0, t_opp = 0, t_d2c[2] = {0, 0}, t_v2d[2] = {0, 0};       // [1]: in prediction-degree order
+    bool needs_topo = false;
+    for (const synth::PortableAttr &a : pl.atts) needs_topo = needs_topo || enc_topo_scheme(a);
+    if (host_conn) {
+      o_e2v[0] = put(ck.e2v[i].data(), 4ull * V); o_ops[0] = put(ck.ops[i].data(), 12ull * V);
+      if (want_pd) { o_e2v[1] = put(ck.e2v_pd[i].data(), 4ull * V); o_ops[1] = put(ck.ops_pd[i].data(), 12ull * V); }
+      if (needs_topo) {                                       // the position table and orders, once per mesh
+        t_c2v = put(pl.ct.c2v.data(), 4ull * pl.ct.c2v.size()); t_opp = put(pl.ct.opp.data(), 4ull * pl.ct.opp.size());
+        t_d2c[0] = put(pl.seq.data_to_corner.data(), 4ull * pl.seq.data_to_corner.size()); t_v2d[0] = put(pl.seq.vertex_to_data.data(), 4ull * pl.seq.vertex_to_data.size());
+        if (want_pd) { t_d2c[1] = put(pl.seq_pd.data_to_corner.data(), 4ull * pl.seq_pd.data_to_corner.size()); t_v2d[1] = put(pl.seq_pd.vertex_to_data.data(), 4ull * pl.seq_pd.vertex_to_data.size()); }
+      }
+    }
+    for (size_t k = 0; k < pl.atts.size(); ++k) {
+      const synth::PortableAttr &a = pl.atts[k];
+      dsa::EncStream &S = L.streams[s0 + k];
+      const bool pd = ck.uses_pd(i, k);
+      S.nv = V; S.prediction = (uint32_t)a.prediction;
+      if (host_conn) {
+        S.e2v = o_e2v[pd]; S.ops = o_ops[pd];
+        if (a.corner_value) {                                 // as many entries as its walk has, its own value rows, seamed: its own operands
+          S.nv = (uint32_t)ck.att_e2v[i][k].size();
+          S.e2v = put(ck.att_e2v[i][k].data(), 4ull * S.nv);
+          if (!ck.att_ops[i][k].empty()) S.ops = put(ck.att_ops[i][k].data(), 12ull * S.nv);
+        }
+      } else if (a.corner_value) S.pd_want = pd ? 1u : 0u;
+      enc_value_stream_input(S, a, m, ck.rows_of(i, a), A, L.uploads);
+      if (!host_conn || !enc_topo_scheme(a)) continue;
+      S.t_c2p = S.t_c2a = t_c2v; S.t_opp = t_opp; S.t_d2c = t_d2c[pd]; S.t_v2d = t_v2d[pd];
+      if (a.corner_value && pl.seamed(k)) {                   // a seamed attribute's own table and order
+        const std::vector<uint32_t> &c2a = pl.conns[k].c2v, &o2 = ck.att_opp[i][k], &d2c = pl.seq_att[k].data_to_corner;
+        const std::vector<int32_t> &v2d = pl.seq_att[k].vertex_to_data;
+        S.t_c2a = put(c2a.data(), 4ull * c2a.size()); S.t_opp = put(o2.data(), 4ull * o2.size());
+        S.t_d2c = put(d2c.data(), 4ull * d2c.size()); S.t_v2d = put(v2d.data(), 4ull * v2d.size());
+      }
+    }
+    // valence symbols: six more streams, the context lists (alphabet C S L R E).  Host connectivity: the host coder's lists.
+    for (uint32_t k = 0; k < 6 && ck.valence_of(i); ++k) {
+      dsa::EncStream &S = L.streams[s0 + pl.atts.size() + k];
+      const std::vector<uint32_t> &list = pl.ctx_symbols[k];
+      enc_list_stream(S, 8, host_conn ? (uint32_t)list.size() : 0u);
+      S.bits = 3;
+      if (host_conn && S.nv) S.syms = put(list.data(), 4ull * S.nv);
+    }
+  }
+  L.input_bytes = A.cur;
+  // everything the kernels write
+  size_t z = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (!ck.good(i)) continue;
+    const dsa_mesh_input &m = ck.mesh(i);
+    const std::vector<synth::PortableAttr> &atts = ck.plans[i].atts;
+    const uint64_t V = m.num_vertices, F = m.num_faces;
+    const uint32_t s0 = L.first_stream[i];
+    dsa::EncConn *C = host_conn ? nullptr : &L.conns[i];
+    if (C) {
+      if (C->faces_narrow) C->faces = A.take(12 * F);
+      C->opp = A.take(12 * F); C->voff = A.take(4 * (V + 1)); C->vcur = A.take(4 * V); C->vlist = A.take(12 * F); C->vcorner = A.take(4 * V);
+      C->vvis = A.take(V); C->frec = A.take(32 * F);
+      C->stack = A.take(4 * F); C->processed = A.take(4 * F); C->init_corners = A.take(4 * F);
+      C->symbols = A.take(F); C->start_bits = A.take(F); C->splits = A.take(12ull * C->split_cap);
+      C->d2c = A.take(4 * V); C->v2d = A.take(4 * V); C->e2v = A.take(4 * V); C->ops = A.take(12 * V);
+      if (want_pd) {
+        C->pd_d2c = A.take(4 * V); C->pd_v2d = A.take(4 * V); C->pd_e2v = A.take(4 * V); C->pd_ops = A.take(12 * V);
+        C->pd_next = A.take(12 * F); C->pd_degree = A.take(4 * V); C->pd_fvis = A.take(F);
+      }
+      if (ck.valence_of(i)) {
+        C->init_time = A.take(4 * F); C->vtime = A.take(4 * F); C->vval = A.take(4 * (V + F)); C->vc2v = A.take(12 * F);
+        C->vctx = A.take(F); C->vsyms = A.take(4 * F); C->vbl = A.take(F); C->vrans = A.take(4 * F + 96); C->vbits = A.take(4 * F + 96);
+      }
+    }
+    for (size_t k = 0; k < atts.size(); ++k) {
+      const synth::PortableAttr &a = atts[k];
+      dsa::EncStream &S = L.streams[s0 + k];
+      const bool pd = ck.uses_pd(i, k);
+      // entries: as the inputs said, or for an attribute given per corner on the device path as many as its walk may have (3F at
+      // most, k_enc_seam_operands sets the count)
+      uint32_t cap = S.nv;
+      if (C) { S.e2v = pd ? C->pd_e2v : C->e2v; S.ops = pd ? C->pd_ops : C->ops; }
+      if (C && a.corner_value) {
+        cap = 3u * (uint32_t)F;
+        dsa::EncSeam &Z = L.seams[z++];
+        Z.edge_seam = A.take(3 * F); Z.vert_seam = A.take(V); Z.afirst = A.take(4 * V); Z.aoff = A.take(4 * (V + 1));
+        Z.c2av = A.take(12 * F); Z.opp2 = A.take(12 * F); Z.v2lm = A.take(12 * F); Z.avis = A.take(3 * F); Z.frec = A.take(32 * F);
+        Z.stack = A.take(4 * F); Z.d2c = A.take(12 * F); Z.v2d = A.take(12 * F); Z.e2v = A.take(12 * F); Z.ops = A.take(36 * F);
+        Z.rank = A.take(4 * F); Z.rcorner = A.take(4 * F); Z.eoff = A.take(4 * (F + 1)); Z.bits = A.take(4 * ((3 * F + 31) / 32));
+        S.e2v = Z.e2v; S.ops = Z.ops;
+      }
+      enc_value_stream_regions(S, cap, ck.hist_cap_of(i, k), A);
+      L.max_rows = std::max(L.max_rows, std::max(S.rows, cap));
+      if (!enc_topo_scheme(a)) continue;
+      if (C) { S.t_c2p = S.t_c2a = C->faces; S.t_opp = C->opp; S.t_d2c = pd ? C->pd_d2c : C->d2c; S.t_v2d = pd ? C->pd_v2d : C->v2d; }      // the connectivity's own
+      S.t_nc3 = 3u * (uint32_t)F;
+      if (!enc_multi_scheme(a)) {
+        S.pos_vals = L.streams[s0].vals;                      // (the positions are attribute 0: their stream is the mesh's first)
+        if (a.seq_type == 2) S.ori = A.take(cap);
+        S.flags = A.take(4ull * ((cap + 31) / 32));
+        continue;
+      }
+      L.any_multi = true;
+      if (a.prediction != 4) continue;
+      L.any_crease = true;                                    // found + crease flags per entry; the four crease lists
+      S.ori = A.take(cap);
+      S.flags = A.take(4ull * dsa::em_crease_words(cap, S.cr_at));
+    }
+    // the context lists.  Device connectivity: their sizes and places are set by k_enc_val_split in the mesh's regions.
+    for (uint32_t k = 0; k < 6 && ck.valence_of(i); ++k) enc_list_stream_regions(L.streams[s0 + atts.size() + k], A, host_conn, host_conn);
+  }
+  L.total_bytes = A.cur;
+}
+
+// ---- the arena of a chunk of sequential streams: the attributes in point order, and with compressed indices the index stream
+// behind them, a list of 3F symbols below 2V given by k_enc_seq_indices from the faces (16-bit where every index fits)
+static void enc_layout_sequential(EncChunk &ck) {
+  EncLayout &L = ck.L;
+  const bool compressed = ck.rq.seq.geometry == 1 && ck.rq.seq.compress_connectivity == 1;
+  EncArena A;
+  A.log = ck.region_log;
+  enc_layout_begin(ck, 0, compressed ? 1 : 0);
+  for (uint32_t i = 0; i < ck.n; ++i) {
+    if (!ck.good(i)) continue;
+    const dsa_mesh_input &m = ck.mesh(i);
+    const std::vector<synth::PortableAttr> &atts = ck.plans[i].atts;
+    const uint32_t V = m.num_vertices, s0 = L.first_stream[i];
+    for (size_t k = 0; k < atts.size(); ++k) {
+      dsa::EncStream &S = L.streams[s0 + k];
+      S.nv = V; S.prediction = 0; S.linear = 1;
+      enc_value_stream_input(S, atts[k], m, V, A, L.uploads);
+    }
+    if (!compressed) continue;
+    dsa::EncSeqIdx X;
+    memset(&X, 0, sizeof(X));
+    X.count = 3u * m.num_faces; X.narrow = V <= 65536 ? 1u : 0u; X.stream = s0 + (uint32_t)atts.size();
+    X.faces = A.put(L.uploads, m.faces, (X.narrow ? 2ull : 4ull) * X.count, X.narrow != 0);
+    L.idx.push_back(X);
+    L.max_count = std::max(L.max_count, X.count);
+    enc_list_stream(L.streams[X.stream], 2u * V, X.count);
+  }
+  L.input_bytes = A.cur;
+  for (uint32_t i = 0; i < ck.n; ++i) {
+    if (!ck.good(i)) continue;
+    const uint32_t V = ck.mesh(i).num_vertices, s0 = L.first_stream[i], na = (uint32_t)ck.plans[i].atts.size();
+    for (uint32_t k = 0; k < na; ++k) enc_value_stream_regions(L.streams[s0 + k], V, ck.hist_cap_of(i, k), A);
+    L.max_rows = std::max(L.max_rows, V);
+    if (compressed) enc_list_stream_regions(L.streams[s0 + na], A, true, false);
+  }
+  L.total_bytes = A.cur;
+}

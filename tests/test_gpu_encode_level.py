@@ -374,6 +374,46 @@ def test_non_manifold_mesh_fails_alone(ctx, monkeypatch, host):
         assert st == 0 and g == cpu(m, cfg)
 
 
+@pytest.fixture(scope="module")
+def mixed():
+    """Meshes whose differences meet inside one chunk: either side of the valence rule (1000 faces) and of the multi-parallelogram
+    rule (40 points), attribute seams, an attribute list, a closed fan."""
+    pos, nrm, uv, faces = synth.make_mesh(synth.GRID, 23, 22, 5)
+    big = dsa.MeshData(pos, faces, nrm, uv)
+    small = []
+    for nx, ny in ((5, 6), (5, 5)):
+        pos, nrm, uv, faces = synth.make_mesh(synth.GRID, nx, ny, 9)
+        small.append(dsa.MeshData(pos, faces, nrm, uv))
+    meshes = [big, per_vertex_meshes()[1], small[0], small[1], corner_data(seamed_tuples()[2]), listed_meshes()[0], fan(50, True)]
+    assert len(big.faces) >= 1000 > len(meshes[1].faces) and len(small[0].positions) >= 40 > len(small[1].positions)
+    assert len(meshes[5].attributes) == 2
+    return meshes
+
+
+@BOTH_PATHS
+@pytest.mark.parametrize("chunk", [None, "3"])
+@pytest.mark.parametrize("traversal", [0, 2])
+def test_mixed_meshes_in_one_chunk(ctx, monkeypatch, host, chunk, traversal, mixed):
+    """The per-mesh conditions of the arena layout interleaved in one batch, in one chunk and in chunks of three, with a mesh that
+    fails its checks in the middle: every other stream is the CPU coder's."""
+    force_path(monkeypatch, host)
+    if chunk is None:
+        monkeypatch.delenv("DSA_ENC_CHUNK", raising=False)
+    else:
+        monkeypatch.setenv("DSA_ENC_CHUNK", chunk)
+    bad_faces = mixed[1].faces.copy()
+    bad_faces[3, 1] = len(mixed[1].positions) + 4
+    bad = dsa.MeshData(mixed[1].positions, bad_faces, mixed[1].normals, mixed[1].texcoords)
+    meshes = mixed[:4] + [bad] + mixed[4:]
+    cfg = dsa.Config(speed=1, edgebreaker_method=-1, multi_parallelogram=-1, traversal_method=traversal)
+    assert [multi_for(cfg, m) for m in mixed[:4]] == [4, 4, 4, 0]
+    got = encode(ctx, meshes, cfg)
+    assert got[4] == (native.DSA_ERR_INVALID_DATA, None)
+    for i, (m, (st, g)) in enumerate(zip(meshes, got)):
+        if i != 4:
+            assert st == 0 and g == cpu(m, cfg), i
+
+
 @BOTH_PATHS
 def test_both_options_off_is_the_attributes_entry_point(ctx, monkeypatch, host, groups):
     force_path(monkeypatch, host)

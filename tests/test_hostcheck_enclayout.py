@@ -1,0 +1,76 @@
+"""The encoder's arena layout (draco-sharp_amd/csrc/dsa_encode_layout.h: the per-mesh checks and plans, enc_layout for Edgebreaker
+streams, enc_layout_sequential for sequential ones) compiled for the host under AddressSanitizer + UBSan
+(tests/hostcheck/enclayout_host.cpp) and run on the host coder's plans: every region aligned and inside the arena, the uploads
+exactly the regions in front of input_bytes, everything the kernels write behind it, no two regions overlapping, every offset of
+a record a region handed out -- per vertex and with seamed UVs and normals, host and device connectivity, both attribute orders,
+predictions 1 / 4 / 5 / 6, valence on and off, a uint16 and a float32 extra, a mesh that fails its checks in the middle of the
+batch, and the sequential layout with raw indices, compressed indices and as a point cloud.  A check of the product source on
+CPU, not a CPU encode path."""
+import os
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+import draco_sharp_amd.synth as synth
+import meshutil
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+SRC = os.path.join(HERE, "hostcheck", "enclayout_host.cpp")
+SHAPES = ((synth.GRID, 6, 5), (synth.HOLES, 12, 9))
+
+
+@pytest.fixture(scope="module")
+def exe(tmp_path_factory):
+    out = str(tmp_path_factory.mktemp("enclayout") / "enclayout_host")      # always rebuilt: the sources under test change
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize=signed-integer-overflow",
+                    "-fno-sanitize-recover=undefined", "-o", out, SRC], check=True)
+    return out
+
+
+def run(exe, tmp_path, meshes):
+    """meshes: (nv, faces, normal (rows, ids) or None, uv (rows, ids) or None)"""
+    path = tmp_path / "meshes.bin"
+    with open(path, "wb") as f:
+        f.write(struct.pack("<I", len(meshes)))
+        for nv, faces, nid, uid in meshes:
+            faces = np.ascontiguousarray(faces, np.uint32).reshape(-1, 3)
+            f.write(struct.pack("<II", nv, len(faces)))
+            f.write(faces.tobytes())
+            f.write(struct.pack("<I", (1 if nid is not None else 0) | (2 if uid is not None else 0)))
+            for a in (nid, uid):
+                if a is not None:
+                    rows, ids = a
+                    f.write(struct.pack("<I", rows))
+                    f.write(np.ascontiguousarray(ids, np.uint32).tobytes())
+    r = subprocess.run([exe, str(path)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    return r.stdout
+
+
+def per_vertex():
+    out = []
+    for kind, nx, ny in SHAPES:
+        pos, _, _, faces = synth.make_mesh(kind, nx, ny, 1)
+        out.append((len(pos), faces, None, None))
+    return out
+
+
+def seamed():
+    out = []
+    for k, (kind, nx, ny) in enumerate(SHAPES):
+        pos, faces, nrm, nid, uv, uid = meshutil.seamed_mesh(synth, kind, nx, ny, 20 + k, normal_charts="island", uv_charts="stripes")
+        out.append((len(pos), faces, (len(nrm), nid), (len(uv), uid)))
+    return out
+
+
+def test_per_vertex_meshes(exe, tmp_path):
+    # without ids the per-vertex form of the request runs beside the other two: 3 forms x 32 settings x 2 chunks + 6 sequential chunks
+    out = run(exe, tmp_path, per_vertex())
+    assert "enclayout: 3 meshes, %d chunks laid out" % (3 * 32 * 2 + 6) in out, out
+
+
+def test_seamed_and_per_vertex_meshes_in_one_batch(exe, tmp_path):
+    out = run(exe, tmp_path, per_vertex() + seamed())
+    assert "enclayout: 5 meshes, %d chunks laid out" % (2 * 32 * 2 + 6) in out, out
