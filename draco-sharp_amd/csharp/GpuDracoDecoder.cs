@@ -119,6 +119,107 @@ public sealed unsafe class GpuDracoDecoder : IDisposable
         }
     }
 
+    /// <summary>One attribute of a VertexArrays result: a row per point.  Quantized rows (Quantization != null) hold the portable
+    /// integers of the stream as ushort; the header (dsa_batch_vertex_arrays) states the dequantisation.</summary>
+    public sealed class VertexAttributeArray
+    {
+        public GeometryAttributeType AttributeType;
+        public uint UniqueId;
+        public DataType DataType;           // of the stored elements: UInt16 for quantised rows
+        public int NumComponents;           // stored per row: 2 for octahedral normals in the quantised format
+        public int Stride;                  // bytes per row (quantised rows are padded to a multiple of 4)
+        public byte[] Data = [];            // NumPoints * Stride bytes
+        public (float[] Min, float Range, int Bits)? Quantization;
+    }
+
+    /// <summary>What a renderer draws: one index array (point ids) and one array per attribute with a row per point.</summary>
+    public sealed class VertexArrays
+    {
+        public int NumPoints;
+        public uint[]? Indices;             // 3 * faces; null for a point cloud
+        public VertexAttributeArray?[] Attributes = [];   // null: quantised with more than 16 bits -- take that attribute from DecodeBatch
+    }
+
+    /// <summary>Decodes independent .drc streams and returns per-point vertex arrays instead of PointAttribute objects with maps: the
+    /// gather Values[PointMap[p]] runs on the GPU behind the decode (k_vertex_arrays) and ONE transfer brings the rows to the host.
+    /// quantized: positions, texture coordinates and normals stay the integers of the stream (16 against 32 bytes per point for the
+    /// default attribute set).  A bad stream yields null in its place and its exception in errors.</summary>
+    public VertexArrays?[] DecodeVertexArrays(IReadOnlyList<byte[]> streams, bool quantized, out Exception?[] errors)
+    {
+        var handles = new System.Runtime.InteropServices.GCHandle[streams.Count];
+        var ptrs = new byte*[streams.Count];
+        var lens = new nuint[streams.Count];
+        IntPtr batch = IntPtr.Zero;
+        try
+        {
+            for (int i = 0; i < streams.Count; ++i)
+            {
+                handles[i] = System.Runtime.InteropServices.GCHandle.Alloc(streams[i], System.Runtime.InteropServices.GCHandleType.Pinned);
+                ptrs[i] = (byte*)handles[i].AddrOfPinnedObject();
+                lens[i] = (nuint)streams[i].Length;
+            }
+            fixed (byte** p = ptrs)
+            fixed (nuint* l = lens)
+            {
+                NativeMethods.Check(NativeMethods.dsa_batch_create(_ctx, (uint)streams.Count, p, l, out batch), _ctx, "dsa_batch_create");
+            }
+            NativeMethods.Check(NativeMethods.dsa_batch_decode(batch), _ctx, "dsa_batch_decode");
+            var request = new DsaVertexRequest { Format = quantized ? 1 : 0 };
+            NativeMethods.Check(NativeMethods.dsa_batch_vertex_arrays(batch, in request, null, 0), _ctx, "dsa_batch_vertex_arrays");
+            NativeMethods.Check(NativeMethods.dsa_batch_wait(batch), _ctx, "dsa_batch_wait");
+            var results = new VertexArrays?[streams.Count];
+            errors = new Exception?[streams.Count];
+            for (uint i = 0; i < streams.Count; ++i)
+            {
+                try { results[i] = MaterializeVertexArrays(batch, i); }
+                catch (Exception e) when (e is InvalidDataException or NotImplementedException) { errors[i] = e; }
+            }
+            return results;
+        }
+        finally
+        {
+            if (batch != IntPtr.Zero) NativeMethods.dsa_batch_free(batch);
+            foreach (var h in handles) if (h.IsAllocated) h.Free();
+        }
+    }
+
+    private VertexArrays MaterializeVertexArrays(IntPtr batch, uint mesh)
+    {
+        NativeMethods.Check(NativeMethods.dsa_batch_mesh_info(batch, mesh, out var info), _ctx, "dsa_batch_mesh_info");
+        NativeMethods.Check((DsaStatus)info.Status, IntPtr.Zero, $"stream {mesh}: decode failed (site {info.Detail})");
+        NativeMethods.Check(NativeMethods.dsa_batch_vertex_arrays_layout(batch, mesh, out var layout), _ctx, "dsa_batch_vertex_arrays_layout");
+        byte* block = (byte*)NativeMethods.dsa_batch_host_vertex_arrays(batch, layout.Block);
+        if (block == null) throw new InvalidOperationException("the vertex arrays are not on the host");
+        var result = new VertexArrays { NumPoints = (int)layout.NumPoints, Attributes = new VertexAttributeArray?[info.NumAttributes] };
+        if (layout.Indices != ulong.MaxValue)
+        {
+            result.Indices = new uint[layout.NumIndices];
+            if ((layout.Flags & 1) != 0) { var src = (ushort*)(block + layout.Indices); for (uint k = 0; k < layout.NumIndices; ++k) result.Indices[k] = src[k]; }
+            else { var src = (uint*)(block + layout.Indices); for (uint k = 0; k < layout.NumIndices; ++k) result.Indices[k] = src[k]; }
+        }
+        for (uint a = 0; a < info.NumAttributes; ++a)
+        {
+            var va = layout.Attribute(a);
+            if ((va.Flags & 1) != 0) continue;      // DSA_VA_ABSENT
+            NativeMethods.Check(NativeMethods.dsa_batch_attribute_info(batch, mesh, a, out var ai), _ctx, "dsa_batch_attribute_info");
+            var array = new VertexAttributeArray
+            {
+                AttributeType = (GeometryAttributeType)ai.AttributeType, UniqueId = ai.UniqueId, DataType = (DataType)va.DataType,
+                NumComponents = (int)va.NumComponents, Stride = (int)va.Stride, Data = new byte[(long)layout.NumPoints * va.Stride]
+            };
+            fixed (byte* d = array.Data) Buffer.MemoryCopy(block + va.Offset, d, array.Data.LongLength, array.Data.LongLength);
+            bool portable = (ai.DecoderType == 2 || ai.DecoderType == 3) && va.DataType == 4 && ai.DataType != 4;
+            if (portable)
+            {
+                var min = new float[ai.NumComponents];
+                for (int c = 0; c < min.Length && c < 4; ++c) min[c] = ai.MinValues[c];
+                array.Quantization = (min, ai.Range, ai.QuantizationBits);
+            }
+            result.Attributes[a] = array;
+        }
+        return result;
+    }
+
     private Draco Materialize(IntPtr batch, uint mesh) => Materialize(_ctx, batch, mesh);
 
     internal static Draco Materialize(IntPtr _ctx, IntPtr batch, uint mesh)

@@ -59,6 +59,42 @@ internal unsafe struct DsaMeshOutput       // byte offsets of a mesh's arrays in
     public fixed ulong PointMap[16];
 }
 
+// dsa_vertex_request (dsa_batch_vertex_arrays): one index array and one row per point and attribute, gathered on the device (32 bytes)
+[StructLayout(LayoutKind.Sequential)]
+internal unsafe struct DsaVertexRequest
+{
+    public int Format;              // 0 DSA_VA_VALUES: decoded values, 1 DSA_VA_QUANTIZED: quantised attributes as uint16 rows of portable integers
+    public uint Flags;              // 1 DSA_VA_DEVICE_ONLY: gather, no device -> host transfer
+    public uint AttributeTypes;     // bit t: attributes of GeometryAttributeType t; 0 = all
+    public fixed uint Reserved[5];  // zero
+}
+
+[StructLayout(LayoutKind.Sequential)]
+internal struct DsaVertexAttribute  // 24 bytes
+{
+    public ulong Offset;            // byte offset in the block; ulong.MaxValue when absent
+    public uint Stride;             // bytes per point
+    public int DataType;            // Draco.IO.Enums.DataType of the stored elements (UInt16 = 4 for quantised rows)
+    public uint NumComponents;      // stored per row (2 for octahedral normals in the quantised format)
+    public uint Flags;              // 1 DSA_VA_ABSENT: left out by the mask, or quantised with more than 16 bits
+}
+
+[StructLayout(LayoutKind.Sequential)]
+internal struct DsaMeshVertexArrays // 408 bytes
+{
+    public uint Block;              // 0, or 1 for a mesh decoded a second time
+    public uint Flags;              // 1 DSA_VA_INDICES_U16
+    public ulong Indices;           // ushort / uint [3 * faces]; ulong.MaxValue for a point cloud
+    public uint NumPoints, NumIndices;
+    public DsaVertexAttribute A0, A1, A2, A3, A4, A5, A6, A7, A8, A9, A10, A11, A12, A13, A14, A15;   // attributes[DSA_MAX_ATTRIBUTES]
+
+    internal unsafe DsaVertexAttribute Attribute(uint a)
+    {
+        if (a >= 16) throw new ArgumentOutOfRangeException(nameof(a));
+        fixed (DsaVertexAttribute* p = &A0) return p[a];
+    }
+}
+
 [StructLayout(LayoutKind.Sequential)]
 internal struct DsaEncodeOptions
 {
@@ -178,6 +214,12 @@ internal static unsafe partial class NativeMethods
     [DllImport(Lib)] internal static extern ulong dsa_batch_compact_bytes(IntPtr batch);
     [DllImport(Lib)] internal static extern IntPtr dsa_batch_host_output(IntPtr batch, uint block);
     [DllImport(Lib)] internal static extern DsaStatus dsa_batch_output_layout(IntPtr batch, uint mesh, out DsaMeshOutput layout);
+    // vertex arrays: per-point rows gathered on the device behind the decode, one transfer; added after ABI 4 (detect by the symbol)
+    [DllImport(Lib)] internal static extern ulong dsa_batch_vertex_arrays_bytes(IntPtr batch, in DsaVertexRequest request);
+    [DllImport(Lib)] internal static extern DsaStatus dsa_batch_vertex_arrays(IntPtr batch, in DsaVertexRequest request, void* dst, nuint dstBytes);
+    [DllImport(Lib)] internal static extern DsaStatus dsa_batch_vertex_arrays_layout(IntPtr batch, uint mesh, out DsaMeshVertexArrays layout);
+    [DllImport(Lib)] internal static extern IntPtr dsa_batch_host_vertex_arrays(IntPtr batch, uint block);
+    [DllImport(Lib)] internal static extern IntPtr dsa_batch_device_vertex_arrays(IntPtr batch, uint block);
     [DllImport(Lib)] internal static extern IntPtr dsa_host_alloc(nuint bytes);
     [DllImport(Lib)] internal static extern void dsa_host_free(IntPtr p);
     [DllImport(Lib)] internal static extern DsaStatus dsa_host_register(void* p, nuint bytes);

@@ -21,6 +21,7 @@
 #include "dsa_general.h"
 #include "dsa_host_parse.h"
 #include "dsa_host_util.h"
+#include "dsa_vertex_arrays.h"
 
 namespace {
 
@@ -30,9 +31,12 @@ static const char *kStageNames[DSA_NUM_STAGES] = {"locate", "connectivity", "tra
 // Kernels timed one by one (dsa_batch_kernel_times): an event pair around each on the stream it is launched on, so that a duration
 // here is a row of `rocprofv3 --kernel-trace --stats` (first launch of that kernel in the decode where a kernel is launched twice).
 enum { KT_CHAIN = 0, KT_CONNECTIVITY, KT_TRAVERSE, KT_SYMBOLS_EARLY, KT_SYMBOLS_LATE, KT_OCT_STREAMS, KT_PREDICT_WRAP_EARLY, KT_PREDICT_WRAP_LATE, KT_FACES,
-       KT_SEAM_TABLES, KT_TRAVERSE_ATT, KT_TEXCOORDS, KT_TAGS, KT_COUNT };
+       KT_SEAM_TABLES, KT_TRAVERSE_ATT, KT_TEXCOORDS, KT_TAGS,
+       KT_PACK_OUTPUT, KT_VERTEX_ARRAYS,      // behind the decode, on the download stream: timed when a compact download / vertex arrays are queued
+       KT_COUNT };
 static const char *kKernelNames[KT_COUNT] = {"k_chain", "k_connectivity", "k_traverse", "k_symbols_reg[early]", "k_symbols_reg[late]", "k_predict_oct_streams",
-                                             "k_predict_wrap[early]", "k_predict_wrap[late]", "k_faces", "k_seam_tables", "k_traverse_att", "k_texcoords", "k_tags"};
+                                             "k_predict_wrap[early]", "k_predict_wrap[late]", "k_faces", "k_seam_tables", "k_traverse_att", "k_texcoords", "k_tags",
+                                             "k_pack_output", "k_vertex_arrays"};
 
 
 }  // namespace
@@ -136,6 +140,7 @@ struct dsa_context {
   // pinning GBs of host memory cost as much as the decode itself.  Three of each: two batches in flight + one being built.
   struct Spare { uint8_t *p; uint64_t bytes; };
   std::vector<Spare> spare_arenas, spare_mirrors, spare_descs, spare_packed;   // spare_descs: pinned landing zones of the mesh descriptors; spare_packed: packed blocks of compact downloads
+  std::vector<Spare> spare_vertex;   // device blocks of vertex arrays (dsa_batch_vertex_arrays)
   static constexpr size_t kSpares = 3;
   // batches point at their context: a context destroyed first lives on until its last batch is freed
   std::atomic<int> live_batches{0};
@@ -206,6 +211,20 @@ struct dsa_batch {
   bool mirror_owned = false, download_queued = false, downloaded = false;
   // meshes the fast kernels handed back (DSA_SITE_RETRY_GENERAL): decoded again through the general path in a batch
   // of their own by dsa_batch_wait; every per-mesh accessor follows retry_index
+  // Vertex arrays (dsa_batch_vertex_arrays): a device block of their own [table of VaMesh | arrays], a pinned copy of the table, a
+  // host copy of the arrays (library-owned pinned mirror or the caller's buffer) and an event of their own -- a download and vertex
+  // arrays of one batch may be outstanding together.  The layout is made when the request arrives, from the host parse.
+  std::vector<VaMesh> va;                 // the table of the most recent request
+  dsa_vertex_request va_req = {};
+  uint64_t va_bytes = 0, va_table_bytes = 0;
+  uint8_t *d_va = nullptr;                // from the context's cache (spare_vertex)
+  uint64_t d_va_cap = 0;
+  uint8_t *va_pin = nullptr;              // pinned staging of the table (from spare_descs)
+  uint64_t va_pin_bytes = 0;
+  uint8_t *va_mirror = nullptr;
+  uint64_t va_mirror_bytes = 0;
+  bool va_mirror_owned = false, va_valid = false, va_queued = false, va_done = false;
+  hipEvent_t ev_va = nullptr;
   bool all_general = false;
   dsa_batch *retry = nullptr;
   std::vector<int32_t> retry_index;
@@ -395,20 +414,15 @@ dsa_status build_batch(dsa_context *ctx, uint32_t n, const uint8_t *const *strea
       const HostMesh &h = b->host[i];
       const MeshLayout &L = b->layouts[i];
       CompactMesh &c = b->compact[i];
-      c.u16 = L.cap_points <= 65536u ? 1u : 0u; c.pad = 0;
+      c.u16 = va_indices_u16(L.cap_points); c.pad = 0;
       c.faces = pcur;
       pcur = align_up(pcur + (uint64_t)L.cap_faces * (c.u16 ? 6 : 12), 64);
-      const bool identity = h.faces == 0 && !h.general;          // point clouds: linear sequencing, point i = entry i
-      int key_of[DSA_MAX_ATT];
+      uint8_t rep[DSA_MAX_ATT];
+      map_representatives(h, L.cap_attributes, rep);           // attributes decoded in one order share their map; point clouds have none
       for (uint32_t a = 0; a < DSA_MAX_ATT; ++a) c.map[a] = ~0ull;
       for (uint32_t a = 0; a < L.cap_attributes && a < DSA_MAX_ATT; ++a) {
-        if (identity) continue;
-        // attributes decoded in one traversal order share their map: all vertex attributes of a fast-path mesh, the attributes of
-        // one corner-attribute decoder; a general-path mesh keeps one map per attribute
-        key_of[a] = h.general ? 1000 + (int)a : (h.atts[a].corner ? 1 + (int)h.atts[a].dec : 0);
-        uint32_t rep = a;
-        for (uint32_t k = 0; k < a; ++k) if (key_of[k] == key_of[a]) { rep = k; break; }
-        if (rep != a) { c.map[a] = c.map[rep]; continue; }
+        if (rep[a] == MAP_REP_IDENTITY) continue;
+        if (rep[a] != a) { c.map[a] = c.map[rep[a]]; continue; }
         c.map[a] = pcur;
         pcur = align_up(pcur + 4ull * L.cap_points, 64);
       }
@@ -553,6 +567,7 @@ void dsa_context_destroy(dsa_context *ctx) {
   if (ctx->down) { (void)hipStreamSynchronize(ctx->down); (void)hipStreamDestroy(ctx->down); }
   drop_spares(ctx, ctx->spare_arenas, false);
   drop_spares(ctx, ctx->spare_packed, false);
+  drop_spares(ctx, ctx->spare_vertex, false);
   drop_spares(ctx, ctx->spare_mirrors, true);
   drop_spares(ctx, ctx->spare_descs, true);
   for (StreamSet &set : ctx->sets) set.destroy();
@@ -643,6 +658,8 @@ dsa_status dsa_batch_decode(dsa_batch *b) {
   if (b->download_queued && !b->downloaded) HIP_TRY(ctx, hipStreamWaitEvent(st, b->ev_down, 0));   // a download of the previous decode still reads the arena
   if (was_decoded) HIP_TRY(ctx, hipStreamWaitEvent(st, b->ev_done, 0));   // this batch's previous decode may still be running on the other stream set
   b->download_queued = false; b->downloaded = false;
+  if (b->va_queued && !b->va_done) HIP_TRY(ctx, hipStreamWaitEvent(st, b->ev_va, 0));               // so may its vertex arrays
+  b->va_valid = false;                                                                                 // a new decode invalidates them
   HIP_TRY(ctx, hipStreamWaitEvent(st, b->ev_uploaded, 0));           // the streams and layouts are in the arena
   HIP_TRY(ctx, hipMemsetAsync(b->d_descs, 0, sizeof(MeshDesc) * n, st));
   HIP_TRY(ctx, hipMemsetAsync(&b->d_globals->pool_cursor, 0, sizeof(unsigned long long) * 2, st));   // the table pool starts empty
@@ -1051,6 +1068,16 @@ dsa_status dsa_batch_decode(dsa_batch *b) {
 }
 
 static dsa_status batch_wait(dsa_batch *b);
+// k_pack_output / k_vertex_arrays run behind the decode, so their event pairs may be recorded after the results were collected
+static hipError_t late_kernel_times(dsa_batch *b) {
+  if (!b->ctx->profiling || !b->have_events) return hipSuccess;
+  for (int k : {KT_PACK_OUTPUT, KT_VERTEX_ARRAYS}) {
+    if (!b->k_timed[k]) continue;
+    const hipError_t e = hipEventElapsedTime(&b->kernel_ms[k], b->ev_k[k][0], b->ev_k[k][1]);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
 dsa_status dsa_batch_wait(dsa_batch *b) {
   if (!b) return DSA_ERR_INVALID_ARGUMENT;
   DSA_GUARD(b->ctx, batch_wait(b));
@@ -1061,12 +1088,15 @@ static dsa_status batch_wait(dsa_batch *b) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (b->collected) {                  // results are in; what can still be outstanding is a download queued since
     if (b->download_queued && !b->downloaded) { HIP_TRY(ctx, hipEventSynchronize(b->ev_down)); b->downloaded = true; }
+    if (b->va_valid && b->va_queued && !b->va_done) { HIP_TRY(ctx, hipEventSynchronize(b->ev_va)); b->va_done = true; }
+    HIP_TRY(ctx, late_kernel_times(b));
     if (b->retry) return dsa_batch_wait(b->retry);
     return DSA_OK;
   }
   // this batch's own events, not the streams: another batch of the context may be queued behind it
   HIP_TRY(ctx, hipEventSynchronize(b->ev_descs));
   if (b->download_queued) { HIP_TRY(ctx, hipEventSynchronize(b->ev_down)); b->downloaded = true; }
+  if (b->va_valid && b->va_queued) { HIP_TRY(ctx, hipEventSynchronize(b->ev_va)); b->va_done = true; }
   if (b->n) memcpy(b->descs.data(), b->descs_pin, sizeof(MeshDesc) * (size_t)b->n);
   if (ctx->profiling && b->have_events && b->n) {
     for (int i = 0; i < STG_TOTAL; ++i) HIP_TRY(ctx, hipEventElapsedTime(&b->stage_ms[i], b->ev[i], b->ev[i + 1]));
@@ -1104,6 +1134,7 @@ static dsa_status batch_wait(dsa_batch *b) {
       dsa_status st = build_batch(ctx, (uint32_t)again.size(), ptrs.data(), lens.data(), &rb, true);
       if (st == DSA_OK) st = dsa_batch_decode(rb);
       if (st == DSA_OK && b->download_queued) st = dsa_batch_download(rb, nullptr, 0);      // block 1 of the download
+      if (st == DSA_OK && b->va_valid && b->va_queued) st = dsa_batch_vertex_arrays(rb, &b->va_req, nullptr, 0);   // block 1 of the vertex arrays
       if (st == DSA_OK) st = dsa_batch_wait(rb);
       if (st != DSA_OK) { if (rb) dsa_batch_free(rb); b->collected = false; return st; }
       b->retry = rb;
@@ -1126,6 +1157,10 @@ void dsa_batch_free(dsa_batch *b) {
   if (b->ev_done) { if (b->decoded) (void)hipEventSynchronize(b->ev_done); (void)hipEventDestroy(b->ev_done); }
   if (b->ev_descs) { if (b->decoded) (void)hipEventSynchronize(b->ev_descs); (void)hipEventDestroy(b->ev_descs); }
   if (b->ev_down) { if (b->download_queued) (void)hipEventSynchronize(b->ev_down); (void)hipEventDestroy(b->ev_down); }
+  if (b->ev_va) { if (b->va_queued) (void)hipEventSynchronize(b->ev_va); (void)hipEventDestroy(b->ev_va); }
+  give_spare(b->ctx, b->ctx->spare_descs, b->va_pin, b->va_pin_bytes, [](uint8_t *p) { (void)hipHostFree(p); });
+  if (b->va_mirror && b->va_mirror_owned) give_spare(b->ctx, b->ctx->spare_mirrors, b->va_mirror, b->va_mirror_bytes, [](uint8_t *p) { (void)hipHostFree(p); });
+  give_spare(b->ctx, b->ctx->spare_vertex, b->d_va, b->d_va_cap, [](uint8_t *p) { (void)hipFree(p); });
   give_spare(b->ctx, b->ctx->spare_descs, (uint8_t *)b->descs_pin, b->descs_pin_bytes, [](uint8_t *p) { (void)hipHostFree(p); });
   if (b->mirror && b->mirror_owned) give_spare(b->ctx, b->ctx->spare_mirrors, b->mirror, b->mirror_bytes, [](uint8_t *p) { (void)hipHostFree(p); });
   give_spare(b->ctx, b->ctx->spare_arenas, b->arena, b->arena_cap, [](uint8_t *p) { (void)hipFree(p); });
@@ -1339,7 +1374,10 @@ static dsa_status batch_download(dsa_batch *b, void *dst, size_t dst_bytes, bool
     // the values as they are; faces and point maps packed by a kernel on the download stream (the copy of the values runs beside it)
     if (b->n && b->packed_bytes) {
       const uint32_t gx = std::max<uint32_t>(1, std::min<uint32_t>((b->max_faces + 16383) / 16384, 4));
+      const bool timed = ctx->profiling && b->have_events;
+      if (timed) (void)hipEventRecord(b->ev_k[KT_PACK_OUTPUT][0], ctx->down);
       hipLaunchKernelGGL(dsa::k_pack_output, dim3(gx, b->n), dim3(256), 0, ctx->down, b->arena, b->d_layouts, b->d_descs, b->n, b->d_compact, b->d_packed);
+      if (timed) { (void)hipEventRecord(b->ev_k[KT_PACK_OUTPUT][1], ctx->down); b->k_timed[KT_PACK_OUTPUT] = true; }
       HIP_TRY(ctx, hipGetLastError());
     }
     HIP_TRY(ctx, copy_down(b->mirror, b->arena + b->out_base + b->out_values, b->out_values_bytes));
@@ -1381,6 +1419,167 @@ dsa_status dsa_batch_output_layout(const dsa_batch *b, uint32_t mesh, dsa_mesh_o
   }
   out->faces = L.faces - src->out_base;
   for (uint32_t a = 0; a < L.cap_attributes && a < DSA_MAX_ATTRIBUTES; ++a) { out->values[a] = L.out[a] - src->out_base; out->point_map[a] = L.map[a] - src->out_base; }
+  return DSA_OK;
+}
+
+// ---- vertex arrays: per-point rows gathered on the device, one transfer (include/draco_mi355x.h, dsa_vertex_arrays.h)
+// Which field of a request the call refuses (nullptr: none).
+static const char *va_request_fault(const dsa_vertex_request *r) {
+  if (!r) return "request (null)";
+  if (r->format != DSA_VA_VALUES && r->format != DSA_VA_QUANTIZED) return "format";
+  if (r->flags & ~DSA_VA_DEVICE_ONLY) return "flags";
+  for (uint32_t w : r->reserved) if (w) return "reserved";
+  return nullptr;
+}
+// The table of a request and the size of its block: from the host parse and the capacities layout_mesh placed, nothing of the decode.
+static uint64_t va_layout_batch(const dsa_batch *b, const dsa_vertex_request &r, std::vector<VaMesh> *table) {
+  uint64_t cur = 0;
+  if (table) table->assign(b->n, VaMesh());
+  for (uint32_t i = 0; i < b->n; ++i) {
+    const HostMesh &h = b->host[i];
+    const MeshLayout &L = b->layouts[i];
+    uint8_t rep[DSA_MAX_ATT];
+    map_representatives(h, L.cap_attributes, rep);
+    VaAttrIn in[DSA_MAX_ATT] = {};
+    const uint32_t natt = std::min<uint32_t>(L.cap_attributes, DSA_MAX_ATT);
+    for (uint32_t a = 0; a < natt; ++a) in[a] = {h.atts[a].att_type, h.atts[a].data_type, h.atts[a].nc, h.atts[a].seq_type, rep[a]};
+    VaMesh m;
+    cur = va_layout_mesh(in, natt, L.cap_points, L.cap_faces, h.faces != 0, r.format, r.attribute_types, cur, m);
+    if (table) (*table)[i] = m;
+  }
+  return cur;
+}
+
+uint64_t dsa_batch_vertex_arrays_bytes(const dsa_batch *b, const dsa_vertex_request *request) {
+  if (!b || va_request_fault(request)) return 0;
+  try { return va_layout_batch(b, *request, nullptr); } catch (...) { return 0; }
+}
+
+static dsa_status batch_vertex_arrays(dsa_batch *b, const dsa_vertex_request *request, void *dst, size_t dst_bytes) {
+  dsa_context *ctx = b->ctx;
+  if (const char *field = va_request_fault(request)) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "dsa_vertex_request.%s is outside its values", field);
+  if (!b->decoded) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "dsa_batch_decode was not called");
+  if (b->va_valid && !b->va_done) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "the batch's vertex arrays are still in flight");
+  const dsa_vertex_request req = *request;
+  std::vector<VaMesh> table;
+  const uint64_t bytes = va_layout_batch(b, req, &table);
+  const bool to_host = !(req.flags & DSA_VA_DEVICE_ONLY);
+  if (to_host && dst && dst_bytes < bytes) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "destination smaller than the vertex arrays (dsa_batch_vertex_arrays_bytes)");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (!b->ev_va) HIP_TRY(ctx, hipEventCreateWithFlags(&b->ev_va, hipEventDisableTiming));
+  if (b->va_queued && !b->va_done) { HIP_TRY(ctx, hipEventSynchronize(b->ev_va)); b->va_done = true; }   // a request from before the batch was decoded again: its buffers are reused
+  const uint64_t table_bytes = align_up(sizeof(VaMesh) * (uint64_t)(b->n ? b->n : 1), 256);
+  const uint64_t need = table_bytes + (bytes ? bytes : 256);
+  if (!b->d_va || b->d_va_cap < need) {                      // the device block: from the context's cache, like the packed block
+    give_spare(ctx, ctx->spare_vertex, b->d_va, b->d_va_cap, [](uint8_t *p) { (void)hipFree(p); });
+    b->d_va = nullptr; b->d_va_cap = 0;
+    uint64_t cap = 0;
+    uint8_t *p = take_spare(ctx, ctx->spare_vertex, need, &cap);
+    if (!p) {
+      hipError_t e = hipMalloc((void **)&p, need);
+      if (e != hipSuccess) { (void)hipGetLastError(); drop_spares(ctx, ctx->spare_vertex, false); drop_spares(ctx, ctx->spare_packed, false); drop_spares(ctx, ctx->spare_arenas, false); e = hipMalloc((void **)&p, need); }
+      if (e != hipSuccess) { (void)hipGetLastError(); return set_err(ctx, DSA_ERR_OUT_OF_MEMORY, "vertex-array block of %llu bytes: %s", (unsigned long long)need, hipGetErrorString(e)); }
+      cap = need;
+    }
+    b->d_va = p; b->d_va_cap = cap;
+  }
+  if (!b->va_pin || b->va_pin_bytes < table_bytes) {         // pinned staging of the table, from the cache of descriptor zones
+    give_spare(ctx, ctx->spare_descs, b->va_pin, b->va_pin_bytes, [](uint8_t *p) { (void)hipHostFree(p); });
+    b->va_pin = nullptr; b->va_pin_bytes = 0;
+    uint8_t *p = take_spare(ctx, ctx->spare_descs, table_bytes, &b->va_pin_bytes);
+    if (!p) { HIP_TRY(ctx, hipHostMalloc((void **)&p, table_bytes, hipHostMallocDefault)); b->va_pin_bytes = table_bytes; }
+    b->va_pin = p;
+  }
+  if (to_host) {                                             // the host copy: the caller's memory or a pinned mirror of the library's
+    auto release = [](uint8_t *p) { (void)hipHostFree(p); };
+    if (dst) {
+      if (b->va_mirror && b->va_mirror_owned) give_spare(ctx, ctx->spare_mirrors, b->va_mirror, b->va_mirror_bytes, release);
+      b->va_mirror = (uint8_t *)dst; b->va_mirror_bytes = dst_bytes; b->va_mirror_owned = false;
+    } else if (!b->va_mirror || !b->va_mirror_owned || b->va_mirror_bytes < bytes) {
+      if (b->va_mirror && b->va_mirror_owned) give_spare(ctx, ctx->spare_mirrors, b->va_mirror, b->va_mirror_bytes, release);
+      b->va_mirror = nullptr;
+      const uint64_t want = bytes ? bytes : 256;
+      uint64_t got = 0;
+      uint8_t *p = take_spare(ctx, ctx->spare_mirrors, want, &got);
+      if (!p) {
+        hipError_t e = hipHostMalloc((void **)&p, want, hipHostMallocDefault);
+        if (e != hipSuccess) { (void)hipGetLastError(); drop_spares(ctx, ctx->spare_mirrors, true); e = hipHostMalloc((void **)&p, want, hipHostMallocDefault); }
+        if (e != hipSuccess) { (void)hipGetLastError(); return set_err(ctx, DSA_ERR_OUT_OF_MEMORY, "pinned host mirror of %llu bytes: %s", (unsigned long long)want, hipGetErrorString(e)); }
+        got = want;
+      }
+      b->va_mirror = p; b->va_mirror_bytes = got; b->va_mirror_owned = true;
+    }
+  }
+  b->va.swap(table);
+  b->va_req = req; b->va_bytes = bytes; b->va_table_bytes = table_bytes;
+  // the table goes up on the download stream (nothing of the decode stands in front of it there), then the kernel behind the decode
+  if (b->n) {
+    memcpy(b->va_pin, b->va.data(), sizeof(VaMesh) * (size_t)b->n);
+    HIP_TRY(ctx, hipMemcpyAsync(b->d_va, b->va_pin, sizeof(VaMesh) * (size_t)b->n, hipMemcpyHostToDevice, ctx->down));
+  }
+  HIP_TRY(ctx, hipStreamWaitEvent(ctx->down, b->ev_done, 0));
+  if (b->n && bytes) {
+    uint32_t max_points = 0;
+    for (uint32_t i = 0; i < b->n; ++i) max_points = std::max(max_points, b->layouts[i].cap_points);
+    // a bench-size mesh gets 16 blocks, a crowded batch of tiny meshes one each: either way the grid fills the device
+    const uint32_t gx = std::max<uint32_t>(1, std::min<uint32_t>((max_points + 8 * VA_CHUNK - 1) / (8 * VA_CHUNK), 16));
+    const bool timed = ctx->profiling && b->have_events;
+    if (timed) (void)hipEventRecord(b->ev_k[KT_VERTEX_ARRAYS][0], ctx->down);
+    hipLaunchKernelGGL(dsa::k_vertex_arrays, dim3(gx, b->n), dim3(VA_CHUNK), 0, ctx->down, b->arena, b->d_layouts, b->d_descs, b->n, (const VaMesh *)b->d_va, b->d_va + table_bytes);
+    if (timed) { (void)hipEventRecord(b->ev_k[KT_VERTEX_ARRAYS][1], ctx->down); b->k_timed[KT_VERTEX_ARRAYS] = true; }
+    HIP_TRY(ctx, hipGetLastError());
+    if (to_host) {
+      const uint64_t piece = 256ull << 20;                   // in pieces, as the download: the engine stays available to the batch behind
+      for (uint64_t at = 0; at < bytes; at += piece)
+        HIP_TRY(ctx, hipMemcpyAsync(b->va_mirror + at, b->d_va + table_bytes + at, (size_t)std::min(piece, bytes - at), hipMemcpyDeviceToHost, ctx->down));
+    }
+  }
+  HIP_TRY(ctx, hipEventRecord(b->ev_va, ctx->down));
+  b->va_valid = true; b->va_queued = true; b->va_done = false;
+  if (b->retry) return dsa_batch_vertex_arrays(b->retry, &req, nullptr, 0);       // block 1: the meshes decoded a second time
+  return DSA_OK;
+}
+dsa_status dsa_batch_vertex_arrays(dsa_batch *b, const dsa_vertex_request *request, void *dst, size_t dst_bytes) {
+  if (!b) return DSA_ERR_INVALID_ARGUMENT;
+  DSA_GUARD(b->ctx, batch_vertex_arrays(b, request, dst, dst_bytes));
+}
+
+const void *dsa_batch_host_vertex_arrays(const dsa_batch *b, uint32_t block) {
+  if (!b || !b->va_valid || !b->va_done) return nullptr;
+  if (block == 1) return b->retry ? dsa_batch_host_vertex_arrays(b->retry, 0) : nullptr;
+  return block == 0 && !(b->va_req.flags & DSA_VA_DEVICE_ONLY) ? b->va_mirror : nullptr;
+}
+const void *dsa_batch_device_vertex_arrays(const dsa_batch *b, uint32_t block) {
+  if (!b || !b->va_valid) return nullptr;
+  if (block == 1) return b->retry ? dsa_batch_device_vertex_arrays(b->retry, 0) : nullptr;
+  return block == 0 && b->d_va ? b->d_va + b->va_table_bytes : nullptr;
+}
+
+dsa_status dsa_batch_vertex_arrays_layout(const dsa_batch *b, uint32_t mesh, dsa_mesh_vertex_arrays *out) {
+  CHECK_MESH(b, mesh);
+  if (!out) return DSA_ERR_INVALID_ARGUMENT;
+  memset(out, 0, sizeof(*out));
+  const dsa_batch *src = b;
+  uint32_t m = mesh;
+  if (b->retry && b->retry_index[mesh] >= 0) { src = b->retry; m = (uint32_t)b->retry_index[mesh]; out->block = 1; }
+  if (!src->va_valid || m >= src->va.size()) return set_err(b->ctx, DSA_ERR_INVALID_ARGUMENT, "no vertex arrays were requested since the batch was decoded");
+  const MeshDesc &D = src->descs[m];
+  if (D.status != ST_OK) return set_err(b->ctx, (dsa_status)D.status, "mesh %u failed to decode", (unsigned)mesh);
+  const VaMesh &T = src->va[m];
+  out->flags = T.indices != VA_NONE && T.u16 ? DSA_VA_INDICES_U16 : 0u;
+  out->indices = T.indices;
+  out->num_points = std::min(D.num_points, T.cap_points);
+  out->num_indices = T.indices != VA_NONE ? 3u * std::min(D.num_faces, T.cap_faces) : 0u;
+  for (uint32_t a = 0; a < DSA_MAX_ATTRIBUTES; ++a) {
+    dsa_vertex_attribute &o = out->attributes[a];
+    o.offset = UINT64_MAX; o.flags = DSA_VA_ABSENT;
+    if (a >= D.num_attributes || a >= T.cap_attributes) continue;
+    const VaAttr &t = T.att[a];
+    o.stride = t.stride; o.data_type = t.data_type; o.num_components = t.nc;
+    uint32_t ne = 0;
+    if (!va_attr_written(t, D.att[a], src->layouts[m].out_cap[a], src->layouts[m].work_cap[a], &ne)) continue;     // the kernel's own test
+    o.offset = t.offset; o.flags = 0;
+  }
   return DSA_OK;
 }
 
@@ -1514,6 +1713,7 @@ dsa_status dsa_context_trim(dsa_context *ctx) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   drop_spares(ctx, ctx->spare_arenas, false);
   drop_spares(ctx, ctx->spare_packed, false);
+  drop_spares(ctx, ctx->spare_vertex, false);
   drop_spares(ctx, ctx->spare_mirrors, true);
   drop_spares(ctx, ctx->spare_descs, true);
   { std::lock_guard<std::mutex> g(ctx->mu); ctx->enc_lanes.clear(); }      // dsa_encode_batch is synchronous: its lanes are idle between calls

@@ -420,4 +420,21 @@ static inline uint64_t layout_mesh(const HostMesh &h, uint64_t stream_len, MeshL
   return cur;
 }
 
+// Which attributes of a mesh have one point map between them: attributes decoded in one traversal order share theirs -- all
+// per-vertex attributes of a fast-path mesh, the attributes of one corner-attribute decoder; a general-path mesh keeps one map per
+// attribute.  rep[a]: the first attribute with a's map (a itself: a's map is the one that is stored / read); MAP_REP_IDENTITY for a
+// point cloud (linear sequencing, point i = entry i: no map).  The compact download and the vertex arrays both go by this.
+#define MAP_REP_IDENTITY 0xFFu
+static inline void map_representatives(const HostMesh &h, uint32_t natt, uint8_t rep[DSA_MAX_ATT]) {
+  const bool identity = h.faces == 0 && !h.general;
+  int key_of[DSA_MAX_ATT];
+  for (uint32_t a = 0; a < DSA_MAX_ATT; ++a) rep[a] = MAP_REP_IDENTITY;
+  if (identity) return;
+  for (uint32_t a = 0; a < natt && a < DSA_MAX_ATT && a < h.atts.size(); ++a) {
+    key_of[a] = h.general ? 1000 + (int)a : (h.atts[a].corner ? 1 + (int)h.atts[a].dec : 0);
+    rep[a] = (uint8_t)a;
+    for (uint32_t k = 0; k < a; ++k) if (key_of[k] == key_of[a]) { rep[a] = (uint8_t)k; break; }
+  }
+}
+
 }  // namespace

@@ -1045,6 +1045,8 @@ __global__ __launch_bounds__(WAVE) void k_multipara(uint8_t *arena, const MeshLa
 
 }  // namespace dsa
 
+#include "dsa_vertex_arrays.h"
+
 namespace dsa {
 // k_pack_output: the packed block of a compact download (dsa_batch_download_compact) -- faces narrowed to uint16 where every point
 // id of the mesh fits, one point map per distinct map (CompactMesh).  Behind the decode, on the download stream.
@@ -1061,10 +1063,7 @@ __global__ __launch_bounds__(256) void k_pack_output(const uint8_t *arena, const
   const int32_t *faces = (const int32_t *)(arena + L.faces);
   if (c.u16) {
     uint32_t *dst = (uint32_t *)(packed + c.faces);                  // two corners to a word
-    for (uint32_t w = tid; w < (nc + 1) / 2; w += stride) {
-      const uint32_t lo = (uint32_t)faces[2 * w], hi = 2 * w + 1 < nc ? (uint32_t)faces[2 * w + 1] : 0u;
-      dst[w] = (lo & 0xFFFFu) | (hi << 16);
-    }
+    for (uint32_t w = tid; w < (nc + 1) / 2; w += stride) dst[w] = va_index_pair(faces, w, nc);     // (dsa_vertex_arrays.h: one narrowing for both)
   } else {
     int32_t *dst = (int32_t *)(packed + c.faces);
     for (uint32_t i = tid; i < nc; i += stride) dst[i] = faces[i];

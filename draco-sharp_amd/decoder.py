@@ -354,6 +354,126 @@ class Batch:
                 "point_map": None if lay.point_map[a] == native.NO_MAP else view(lay.point_map[a], info.num_points, np.uint32, (info.num_points,))})
         return out
 
+    # ---- vertex arrays (dsa_batch_vertex_arrays): one row per point, gathered on the device, one transfer
+    _VA_FORMATS = {"values": native.DSA_VA_VALUES, "quantized": native.DSA_VA_QUANTIZED}
+
+    def _vertex_request(self, format, attribute_types, device_only=False):
+        if format not in self._VA_FORMATS:
+            raise ValueError("format must be 'values' or 'quantized', not %r" % (format,))
+        mask = 0
+        if attribute_types is not None:
+            for t in ([attribute_types] if isinstance(attribute_types, int) else attribute_types):
+                if not 0 <= int(t) < 32:
+                    raise ValueError("attribute type %r outside 0..31" % (t,))
+                mask |= 1 << int(t)
+        return native.VertexRequest(self._VA_FORMATS[format], native.DSA_VA_DEVICE_ONLY if device_only else 0, mask)
+
+    def vertex_arrays_bytes(self, format="values", attribute_types=None):
+        """Bytes of the vertex-array block this request would make (block 0; fixed by the stream headers)."""
+        return int(self._L.dsa_batch_vertex_arrays_bytes(self._h, C.byref(self._vertex_request(format, attribute_types))))
+
+    def vertex_arrays(self, format="values", attribute_types=None, wait=True, device_only=False):
+        """Queues the gather of the batch's vertex arrays behind its kernels and ONE device -> host transfer of them
+        (dsa_batch_vertex_arrays): per mesh one index array and per attribute one array with a row per point, so that no caller
+        gathers Values[PointMap] on the host.  format "values": rows are the decoded values; "quantized": quantised attributes
+        (positions, texture coordinates, octahedral normals) as uint16 rows of their portable integers, to be dequantised with the
+        parameters vertex_views() returns.  attribute_types: GeometryAttributeType values to include (None: all).  device_only: gather,
+        but transfer nothing (device_vertex_views).  A download of the same batch may be outstanding as well."""
+        if not self._h:
+            raise DeviceException("the batch is closed")
+        req = self._vertex_request(format, attribute_types, device_only)
+        st = self._L.dsa_batch_vertex_arrays(self._h, C.byref(req), None, 0)
+        if st != 0:
+            _raise(st, self.ctx.error())
+        if wait:
+            self.wait()
+
+    def _vertex_layout(self, i):
+        info = self.mesh_info(i)
+        if info.status != 0:
+            _raise(info.status, "stream %d: decode failed (status %d, site %d)" % (i, info.status, info.detail))
+        lay = native.MeshVertexArrays()
+        st = self._L.dsa_batch_vertex_arrays_layout(self._h, i, C.byref(lay))
+        if st != 0:
+            _raise(st, self.ctx.error())
+        infos = []
+        for a in range(info.num_attributes):
+            ai = native.AttributeInfo()
+            st = self._L.dsa_batch_attribute_info(self._h, i, a, C.byref(ai))
+            if st != 0:
+                _raise(st, self.ctx.error())
+            infos.append(ai)
+        return info, lay, infos
+
+    @staticmethod
+    def _vertex_quantization(ai, va):
+        """(min, range, bits) of an attribute stored as portable integers, else None."""
+        if va.flags & native.DSA_VA_ABSENT or ai.decoder_type not in (2, 3) or va.data_type != 4 or ai.data_type == 4:
+            return None
+        return ([float(x) for x in list(ai.min_values)[: ai.num_components]], float(ai.range), int(ai.quantization_bits))
+
+    def vertex_views(self, i):
+        """Zero-copy numpy views of mesh i's vertex arrays in the host copy: {"indices": uint16 | uint32 [F, 3] (None for a point
+        cloud), "attributes": [{"info", "values": [points, components] (a strided view where the rows are padded; None when the
+        attribute is absent: left out by the mask, or quantised with more than 16 bits in the quantized format), "quantization":
+        (min, range, bits) for rows of portable integers, else None}]}.  Valid until the batch is closed, decoded again or asked
+        for vertex arrays again."""
+        info, lay, infos = self._vertex_layout(i)
+        base = self._L.dsa_batch_host_vertex_arrays(self._h, lay.block)
+        if not base:
+            raise RuntimeError("the batch has no vertex arrays on the host (Batch.vertex_arrays, then wait)")
+
+        def view(off, rows, cols, keep, dtype):
+            if rows == 0:
+                return np.zeros((0, keep), dtype)
+            nbytes = rows * cols * np.dtype(dtype).itemsize
+            return np.frombuffer((C.c_uint8 * nbytes).from_address(base + off), dtype, rows * cols).reshape(rows, cols)[:, :keep]
+
+        idt = np.uint16 if lay.flags & native.DSA_VA_INDICES_U16 else np.uint32
+        out = {"indices": None if lay.indices == native.VA_NONE else view(lay.indices, lay.num_indices // 3, 3, 3, idt), "attributes": []}
+        for a, ai in enumerate(infos):
+            va = lay.attributes[a]
+            values = None
+            if not va.flags & native.DSA_VA_ABSENT:
+                dt = np.dtype(_DT_NUMPY[va.data_type])
+                values = view(va.offset, lay.num_points, va.stride // dt.itemsize, va.num_components, dt)
+            out["attributes"].append({"info": ai, "values": values, "quantization": self._vertex_quantization(ai, va)})
+        return out
+
+    def device_vertex_views(self, i):
+        """vertex_views(i) as torch tensors over the device block (also after vertex_arrays(device_only=True)); uint16 / uint32
+        arrays as signed views of the same bits, as in device_views.  Valid until the batch is closed, decoded again or asked for
+        vertex arrays again."""
+        import torch
+        info, lay, infos = self._vertex_layout(i)
+        base = self._L.dsa_batch_device_vertex_arrays(self._h, lay.block)
+        if not base:
+            raise RuntimeError("the batch has no vertex arrays (Batch.vertex_arrays)")
+        dev = "cuda:%d" % self.ctx.device
+
+        class _Ptr:                                    # __cuda_array_interface__ v2 carrier
+            def __init__(self, ptr, shape, typestr):
+                self.__cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (int(ptr), False), "version": 2}
+
+        typestr = {1: "|i1", 2: "|u1", 3: "<i2", 4: "<i2", 5: "<i4", 6: "<i4", 9: "<f4"}
+        torch_dt = {"|i1": torch.int8, "|u1": torch.uint8, "<i2": torch.int16, "<i4": torch.int32, "<f4": torch.float32}
+
+        def view(off, rows, cols, keep, ts):
+            if rows == 0:
+                return torch.empty((0, keep), dtype=torch_dt[ts], device=dev)
+            return torch.as_tensor(_Ptr(base + off, (rows, cols), ts), device=dev)[:, :keep]
+
+        its = "<i2" if lay.flags & native.DSA_VA_INDICES_U16 else "<i4"
+        out = {"indices": None if lay.indices == native.VA_NONE else view(lay.indices, lay.num_indices // 3, 3, 3, its), "attributes": []}
+        for a, ai in enumerate(infos):
+            va = lay.attributes[a]
+            ts = typestr.get(va.data_type)
+            values = None
+            if not va.flags & native.DSA_VA_ABSENT and ts:
+                values = view(va.offset, lay.num_points, va.stride // int(ts[2]), va.num_components, ts)
+            out["attributes"].append({"info": ai, "values": values, "quantization": self._vertex_quantization(ai, va)})
+        return out
+
     @property
     def algorithmic_bytes(self):
         return int(self._L.dsa_batch_algorithmic_bytes(self._h))

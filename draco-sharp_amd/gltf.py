@@ -14,7 +14,7 @@ import struct
 
 import numpy as np
 
-from .decoder import Batch, InvalidDataException, default_context
+from .decoder import Batch, Draco, DracoHeader, InvalidDataException, Mesh, PointAttribute, default_context
 
 EXTENSION = "KHR_draco_mesh_compression"
 _GLB_MAGIC, _CHUNK_JSON, _CHUNK_BIN = 0x46546C67, 0x4E4F534A, 0x004E4942
@@ -150,10 +150,14 @@ def draco_primitives(asset):
 
 
 class DecodedPrimitive:
-    """indices: uint32[3 * faces] (point ids); attributes: semantic -> array[points, components]."""
+    """indices: uint32[3 * faces] (point ids); attributes: semantic -> array[points, components]; quantization: semantic ->
+    (min, range, bits) for the attributes load(quantized=True) returned as integers (dsa_batch_vertex_arrays in
+    include/draco_mi355x.h states the dequantisation).  draco: the stream as a Draco object whose attributes carry one value per
+    point (identity point maps)."""
 
-    def __init__(self, source, draco, indices, attributes):
+    def __init__(self, source, draco, indices, attributes, quantization=None):
         self.source, self.draco, self.indices, self.attributes = source, draco, indices, attributes
+        self.quantization = quantization or {}
 
 
 class GltfDracoLoader:
@@ -162,7 +166,11 @@ class GltfDracoLoader:
     def __init__(self, context=None):
         self.ctx = context or default_context()
 
-    def load(self, sources):
+    def load(self, sources, quantized=False):
+        """One batch, one decode, ONE download: the vertex arrays of the batch (Batch.vertex_arrays) are already what glTF wants,
+        a row per point.  quantized=True: positions, normals and texture coordinates stay the integers the stream carries (uint16;
+        normals as two octahedral coordinates) and DecodedPrimitive.quantization[semantic] is (min, range, bits) -- the form
+        KHR_mesh_quantization lets a renderer consume; an attribute quantised with more than 16 bits comes back as floats."""
         assets = [s if isinstance(s, GltfAsset) else read_asset(s) for s in sources]
         prims = [p for a in assets for p in draco_primitives(a)]
         results = [[] for _ in assets]
@@ -170,19 +178,24 @@ class GltfDracoLoader:
             return results
         batch = Batch(self.ctx, [p.stream for p in prims])
         try:
-            batch.decode()
+            batch.decode(wait=False)
+            batch.vertex_arrays("quantized" if quantized else "values")
             index_of = {id(a): i for i, a in enumerate(assets)}
             for i, p in enumerate(prims):
-                results[index_of[id(p.asset)]].append(self._expand(p, batch.result(i)))
+                views = batch.vertex_views(i)
+                if any(a["values"] is None for a in views["attributes"]):          # more than 16 bits: those rows as floats, the old way
+                    for a, att in zip(views["attributes"], batch.result(i).ConnectedData.Attributes):
+                        if a["values"] is None:
+                            a["values"] = att.Values[att.PointMap]
+                results[index_of[id(p.asset)]].append(self._expand(p, batch.mesh_info(i), views))
         finally:
             batch.close()
         return results
 
     @staticmethod
-    def _expand(p, draco):
+    def _expand(p, info, views):
         where = "%s: mesh %d primitive %d" % (p.asset.name, p.mesh, p.primitive)
-        geometry = draco.ConnectedData
-        if not hasattr(geometry, "Faces"):
+        if views["indices"] is None:
             raise InvalidDataException("%s: the stream is a point cloud" % where)
         accessors = p.asset.doc.get("accessors", [])
 
@@ -193,22 +206,31 @@ class GltfDracoLoader:
                 raise InvalidDataException("%s: %s accessor %d does not exist" % (where, what, index))
             return accessors[index]
 
-        indices = np.ascontiguousarray(geometry.Faces, np.uint32).reshape(-1)
+        indices = views["indices"].astype(np.uint32).reshape(-1)          # copies: the views die with the batch
         acc = accessor(p.indices_accessor, "indices")
         if acc is not None and int(acc.get("count", -1)) != indices.size:
             raise InvalidDataException("%s: indices accessor counts %s, the stream has %d" % (where, acc.get("count"), indices.size))
-        attributes = {}
+        ident = np.arange(info.num_points, dtype=np.uint32)
+        atts = []
+        for a in views["attributes"]:
+            att = PointAttribute(a["info"], np.array(a["values"]), ident, None)
+            att.UniqueEntriesCount, att.IsMappingIdentity = info.num_points, True
+            atts.append(att)
+        draco = Draco(DracoHeader(info), Mesh(atts, info.num_points, indices.reshape(-1, 3).astype(np.int32)))
+        attributes, quantization = {}, {}
         for semantic, uid in p.attribute_ids.items():
-            att = geometry.GetAttributeByUniqueId(uid)
-            if att is None:
+            k = next((k for k, a in enumerate(atts) if a.UniqueId == uid), None)
+            if k is None:
                 raise InvalidDataException("%s: no Draco attribute with unique id %d (%s)" % (where, uid, semantic))
-            values = att.Values[att.PointMap]                       # one value per point = per glTF vertex
+            values = atts[k].Values                                       # one value per point = per glTF vertex
             acc = accessor(p.accessors.get(semantic), semantic)
             if acc is not None:
-                if int(acc.get("count", -1)) != geometry.PointsCount:
-                    raise InvalidDataException("%s: %s accessor counts %s, the stream has %d points" % (where, semantic, acc.get("count"), geometry.PointsCount))
+                if int(acc.get("count", -1)) != info.num_points:
+                    raise InvalidDataException("%s: %s accessor counts %s, the stream has %d points" % (where, semantic, acc.get("count"), info.num_points))
                 nc = _TYPE_COMPONENTS.get(acc.get("type"))
-                if nc is not None and nc != values.shape[1]:
-                    raise InvalidDataException("%s: %s accessor is %s, the stream has %d components" % (where, semantic, acc.get("type"), values.shape[1]))
+                if nc is not None and nc != views["attributes"][k]["info"].num_components:
+                    raise InvalidDataException("%s: %s accessor is %s, the stream has %d components" % (where, semantic, acc.get("type"), views["attributes"][k]["info"].num_components))
             attributes[semantic] = values
-        return DecodedPrimitive(p, draco, indices, attributes)
+            if views["attributes"][k]["quantization"] is not None:
+                quantization[semantic] = views["attributes"][k]["quantization"]
+        return DecodedPrimitive(p, draco, indices, attributes, quantization)

@@ -11,6 +11,11 @@ DSA_OK, DSA_ERR_INVALID_DATA, DSA_ERR_NOT_IMPLEMENTED, DSA_ERR_INVALID_ARGUMENT,
 DSA_NUM_STAGES = 8
 DSA_OUTPUT_FACES_U16 = 1
 NO_MAP = 0xFFFFFFFFFFFFFFFF   # dsa_mesh_output.point_map: the identity map, not stored (compact download)
+DSA_VA_VALUES, DSA_VA_QUANTIZED = 0, 1      # dsa_vertex_request.format
+DSA_VA_DEVICE_ONLY = 1                      # dsa_vertex_request.flags
+DSA_VA_ABSENT = 1                           # dsa_vertex_attribute.flags
+DSA_VA_INDICES_U16 = 1                      # dsa_mesh_vertex_arrays.flags
+VA_NONE = 0xFFFFFFFFFFFFFFFF                # an array that is not in the block
 
 # every symbol include/draco_mi355x.h declares
 EXPORTS = [
@@ -20,6 +25,7 @@ EXPORTS = [
     "dsa_batch_attribute_info", "dsa_batch_copy_faces", "dsa_batch_copy_attribute_values", "dsa_batch_copy_point_map",
     "dsa_batch_copy_portable_values", "dsa_batch_device_faces", "dsa_batch_device_attribute_values",
     "dsa_batch_device_point_map", "dsa_batch_output_bytes", "dsa_batch_download", "dsa_batch_compact_bytes", "dsa_batch_download_compact", "dsa_batch_host_output", "dsa_batch_output_layout",
+    "dsa_batch_vertex_arrays_bytes", "dsa_batch_vertex_arrays", "dsa_batch_vertex_arrays_layout", "dsa_batch_host_vertex_arrays", "dsa_batch_device_vertex_arrays",
     "dsa_host_alloc", "dsa_host_free", "dsa_host_register", "dsa_host_unregister", "dsa_batch_copy_metadata", "dsa_batch_copy_debug", "dsa_context_set_profiling", "dsa_batch_stage_times",
     "dsa_batch_kernel_times", "dsa_context_trim", "dsa_context_schedule_note",
     "dsa_encode_default_options", "dsa_encode_batch", "dsa_encode_batch_corners",
@@ -99,6 +105,21 @@ class MeshOutput(C.Structure):
     _fields_ = [("block", C.c_uint32), ("flags", C.c_uint32), ("faces", C.c_uint64), ("values", C.c_uint64 * 16), ("point_map", C.c_uint64 * 16)]
 
 
+class VertexRequest(C.Structure):
+    """dsa_vertex_request: format (DSA_VA_VALUES / DSA_VA_QUANTIZED), flags (DSA_VA_DEVICE_ONLY), attribute_types (bit t: attributes of
+    GeometryAttributeType t; 0 = all)."""
+    _fields_ = [("format", C.c_int32), ("flags", C.c_uint32), ("attribute_types", C.c_uint32), ("reserved", C.c_uint32 * 5)]
+
+
+class VertexAttribute(C.Structure):
+    _fields_ = [("offset", C.c_uint64), ("stride", C.c_uint32), ("data_type", C.c_int32), ("num_components", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class MeshVertexArrays(C.Structure):
+    _fields_ = [("block", C.c_uint32), ("flags", C.c_uint32), ("indices", C.c_uint64), ("num_points", C.c_uint32), ("num_indices", C.c_uint32),
+                ("attributes", VertexAttribute * 16)]
+
+
 class AttributeInfo(C.Structure):
     _fields_ = [("attribute_type", C.c_int32), ("data_type", C.c_int32), ("num_components", C.c_int32),
                 ("normalized", C.c_int32), ("unique_id", C.c_uint32), ("num_entries", C.c_uint32),
@@ -162,6 +183,13 @@ def lib():
         L.dsa_batch_host_output.restype = vp
         L.dsa_batch_host_output.argtypes = [vp, u32]
         L.dsa_batch_output_layout.argtypes = [vp, u32, C.POINTER(MeshOutput)]
+        L.dsa_batch_vertex_arrays_bytes.restype = C.c_uint64
+        L.dsa_batch_vertex_arrays_bytes.argtypes = [vp, C.POINTER(VertexRequest)]
+        L.dsa_batch_vertex_arrays.argtypes = [vp, C.POINTER(VertexRequest), vp, C.c_size_t]
+        L.dsa_batch_vertex_arrays_layout.argtypes = [vp, u32, C.POINTER(MeshVertexArrays)]
+        for f in ("dsa_batch_host_vertex_arrays", "dsa_batch_device_vertex_arrays"):
+            getattr(L, f).restype = vp
+            getattr(L, f).argtypes = [vp, u32]
         L.dsa_host_alloc.restype = vp
         L.dsa_host_alloc.argtypes = [C.c_size_t]
         L.dsa_host_free.restype = None

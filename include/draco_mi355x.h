@@ -117,7 +117,7 @@ dsa_status dsa_batch_create_packed(dsa_context *ctx, uint32_t n, const uint8_t *
  * context created on a caller's stream runs every decode in that stream's order.
  * Decoding the same batch again waits for its previous decode. */
 dsa_status dsa_batch_decode(dsa_batch *batch);
-/* Waits for the decode (and for a download queued with dsa_batch_download) and collects
+/* Waits for the decode (and for a download / vertex arrays queued with dsa_batch_download / dsa_batch_vertex_arrays) and collects
  * the per-mesh results.  Waits for this batch only: another batch of the same context may
  * be queued behind it (upload of batch k+1 beside the kernels of batch k beside the
  * download of batch k-1 is the intended use; a context keeps up to three arenas and
@@ -174,6 +174,75 @@ uint64_t dsa_batch_compact_bytes(const dsa_batch *batch);
 dsa_status dsa_batch_download_compact(dsa_batch *batch, void *dst, size_t dst_bytes);
 const void *dsa_batch_host_output(const dsa_batch *batch, uint32_t block);   /* NULL until dsa_batch_wait has seen the download finish */
 dsa_status dsa_batch_output_layout(const dsa_batch *batch, uint32_t mesh, dsa_mesh_output *out);
+/* Vertex arrays: the results in the form a renderer draws -- per mesh ONE index array and per attribute ONE array with a row per
+ * point (= per glTF vertex), each in a block of its own beside the output block.  A HIP kernel behind the decode gathers the rows
+ * through the point maps (k_vertex_arrays), so that no map crosses the link and no caller gathers on the host; one transfer
+ * downloads the block.  Optional and for the whole batch; dsa_batch_download, _download_compact and every accessor above keep
+ * working on a batch that also made vertex arrays (a download and vertex arrays may be outstanding together).  Added after ABI 4
+ * without changing it: callers detect the feature by the symbol dsa_batch_vertex_arrays.
+ *   When: wherever dsa_batch_download may be called, also before dsa_batch_wait -- queued behind the batch's kernels on the
+ *     context's download stream; dsa_batch_wait waits for it too (upload k+1 beside kernels k beside download k-1 keeps one wait per
+ *     batch).  A second call while the first is in flight is refused (DSA_ERR_INVALID_ARGUMENT); a new dsa_batch_decode of the batch
+ *     invalidates the arrays.
+ *   Size: fixed when the request arrives, from the stream headers (attribute types and component counts, the counts of points
+ *     and faces): dsa_batch_vertex_arrays_bytes.  Every array is 64-byte aligned.  `dst` (pinned memory for the link's full rate)
+ *     must hold that many bytes; with dst == NULL the library uses a pinned mirror of its own (valid until dsa_batch_free, the next
+ *     dsa_batch_decode or the next request).
+ *   Indices: uint16 where the stream's header bounds the mesh to at most 65 536 points -- encoded vertices + split symbols, known
+ *     before the decode: the rule of the compact download -- (DSA_VA_INDICES_U16), else uint32.
+ *   DSA_VA_VALUES rows: exactly byte_stride bytes, the bytes of Values[PointMap[p]].
+ *   DSA_VA_QUANTIZED rows: an attribute whose decoder_type is 2 (quantisation) or 3 (octahedral normals) is stored as its portable
+ *     integers in uint16 rows -- num_components of them, 2 for normals -- with the stride rounded up to a multiple of 4 and zero
+ *     filled (what KHR_mesh_quantization lets a renderer consume).  Every other attribute is stored as under DSA_VA_VALUES.
+ *     Dequantisation, with the parameters dsa_batch_attribute_info returns, in float32 with two separate roundings:
+ *       decoder_type 2:  value[c] = min_values[c] + (float)q[c] * (range / (float)((1 << quantization_bits) - 1))
+ *       decoder_type 3:  (s, t) = q on the octahedron of quantization_bits bits (OctahedronToolBox.cs), in float32:
+ *                        k = 2 / (float)((1 << quantization_bits) - 2);  y = (float)s * k - 1;  z = (float)t * k - 1;
+ *                        x = 1 - |y| - |z|;  o = max(-x, 0);  y += y < 0 ? o : -o;  z += z < 0 ? o : -o;  n = x * x + y * y + z * z;
+ *                        value = (x, y, z) * (1 / sqrt((double)n)), each product in double and rounded to float32; (0, 0, 0) where n < 1e-6.
+ *     An attribute the decode finds quantised with MORE than 16 bits has no such rows: its array stays unwritten, the layout
+ *     reports it DSA_VA_ABSENT with offset UINT64_MAX (the space stays reserved: the layout is a function of the headers) and the
+ *     caller takes that attribute through DSA_VA_VALUES or the accessors above.
+ *   attribute_types: a mask that leaves an attribute out reserves nothing for it; the layout reports it absent.
+ *   An entry index of a point map that is not below the attribute's num_entries gives a row of zeros.
+ *   Meshes decoded a second time (decode_path 2) get their arrays from the retry batch as block 1, with the same request;
+ *     dsa_batch_wait queues that when it builds the retry batch.  Meshes the general path decodes in the first batch are gathered
+ *     like any other.  A failed mesh has no arrays: dsa_batch_vertex_arrays_layout returns its status.
+ *   A format or flag outside the values below or a non-zero reserved word fails the call with DSA_ERR_INVALID_ARGUMENT and
+ *     dsa_last_error names the field.
+ *   The pool (dsa_pool_*, below) exposes its batches as const dsa_batch *: its jobs cannot request vertex arrays. */
+#define DSA_VA_VALUES 0          /* rows = the attribute's decoded values */
+#define DSA_VA_QUANTIZED 1       /* attributes with decoder_type 2 / 3: the portable integers as uint16 rows; others as VALUES */
+#define DSA_VA_DEVICE_ONLY 1u    /* dsa_vertex_request.flags: gather, but queue no device -> host transfer */
+typedef struct dsa_vertex_request {
+  int32_t format;                /* DSA_VA_VALUES / DSA_VA_QUANTIZED */
+  uint32_t flags;                /* DSA_VA_DEVICE_ONLY or 0 */
+  uint32_t attribute_types;      /* bit t: include attributes of GeometryAttributeType t; 0 = all */
+  uint32_t reserved[5];          /* must be zero */
+} dsa_vertex_request;            /* 32 bytes */
+#define DSA_VA_ABSENT 1u         /* dsa_vertex_attribute.flags: not in the block (left out by the mask, or not representable) */
+typedef struct dsa_vertex_attribute {
+  uint64_t offset;               /* byte offset in the block; UINT64_MAX when absent */
+  uint32_t stride;               /* bytes per point */
+  int32_t data_type;             /* Draco DataType of the stored elements (uint16 = 4 for quantised rows) */
+  uint32_t num_components;       /* stored per row (2 for octahedral normals in the quantised format) */
+  uint32_t flags;                /* DSA_VA_ABSENT */
+} dsa_vertex_attribute;          /* 24 bytes */
+#define DSA_VA_INDICES_U16 1u
+typedef struct dsa_mesh_vertex_arrays {
+  uint32_t block;                /* 0, or 1 for a mesh decoded a second time, as in dsa_mesh_output */
+  uint32_t flags;                /* DSA_VA_INDICES_U16 */
+  uint64_t indices;              /* uint16 / uint32 [3 * num_faces]; UINT64_MAX for a point cloud */
+  uint32_t num_points, num_indices;
+  dsa_vertex_attribute attributes[DSA_MAX_ATTRIBUTES];
+} dsa_mesh_vertex_arrays;        /* 408 bytes */
+/* Bytes of block 0 for this request (0: no batch, or a request the call would refuse). */
+uint64_t dsa_batch_vertex_arrays_bytes(const dsa_batch *batch, const dsa_vertex_request *request);
+dsa_status dsa_batch_vertex_arrays(dsa_batch *batch, const dsa_vertex_request *request, void *dst, size_t dst_bytes);
+/* Where mesh `mesh`'s arrays lie in its block (after dsa_batch_wait; for the most recent request). */
+dsa_status dsa_batch_vertex_arrays_layout(const dsa_batch *batch, uint32_t mesh, dsa_mesh_vertex_arrays *out);
+const void *dsa_batch_host_vertex_arrays(const dsa_batch *batch, uint32_t block);     /* NULL until dsa_batch_wait has seen the transfer finish (always with DSA_VA_DEVICE_ONLY) */
+const void *dsa_batch_device_vertex_arrays(const dsa_batch *batch, uint32_t block);   /* valid until dsa_batch_free, the next dsa_batch_decode or the next request */
 /* Pinned host memory for download destinations (and for inputs a caller reuses). */
 void *dsa_host_alloc(size_t bytes);
 void dsa_host_free(void *p);
