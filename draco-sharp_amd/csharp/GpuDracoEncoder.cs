@@ -14,6 +14,10 @@
 // ConstrainedMultiParallelogram (4) replaces Parallelogram by it; with SpeedLadder set, Config.Speed chooses as the reference does --
 // ConstrainedMultiParallelogram at Speed < 2 for meshes of 40 points or more, prediction-degree order at Speed 0.  Neither set: the
 // calls and their bytes are what they were.
+// RepairTopology (dsa_encode_repair_batch, topology 1): meshes with degenerate faces, the same face twice, fins, faces turned over,
+// fans that meet at a vertex or unused vertices are coded on the corner table CornerTable(faces) builds (CornerTable.cs:28-43), as
+// DracoEncoder.Encode codes them, instead of failing; clean meshes give the same bytes.  A mesh in corner form that needs the
+// repair still fails (NotImplementedException).
 using System;
 using System.Collections.Generic;
 using System.IO;
@@ -30,6 +34,10 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
     /// <summary>Follow the reference's speed ladder above its default level (PredictionSchemeEncoderFactory.cs:63-71,
     /// MeshEdgeBreakerEncoder.cs:528-546) instead of writing the default level's schemes at every Speed.</summary>
     public bool SpeedLadder { get; set; }
+
+    /// <summary>Repair non-manifold, degenerate and isolated input as the reference's CornerTable does (CornerTable.cs:28-43)
+    /// instead of refusing it.</summary>
+    public bool RepairTopology { get; set; }
 
     public GpuDracoEncoder(int device = 0)
     {
@@ -149,7 +157,7 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
         {
             bool anyCorners = false, anyExtras = false;
             foreach (var m in meshes) { anyCorners = anyCorners || NeedsCornerForm(m); anyExtras = anyExtras || ExtraAttributes(m).Count > 0; }
-            if (anyExtras || multi != 0 || traversal != 0)
+            if (anyExtras || multi != 0 || traversal != 0 || RepairTopology)
             {
                 // the attribute list rides on the corner form (extras per vertex: the value of the last point of each position value)
                 var ain = new DsaMeshAttrInput[meshes.Count];
@@ -162,12 +170,21 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
                 ax.Base = opt;
                 ax.EdgebreakerMethod = ebMethod != unset ? ebMethod : 0;
                 ax.NormalPrediction = normalScheme != unset ? normalScheme : 0;
-                if (multi != 0 || traversal != 0)
+                if (multi != 0 || traversal != 0 || RepairTopology)
                 {
                     NativeMethods.dsa_encode_default_level_options(out var lv);
                     lv.Ex = ax;
                     lv.MultiParallelogram = multi;
                     lv.TraversalMethod = traversal;
+                    if (RepairTopology)
+                    {
+                        NativeMethods.dsa_encode_default_repair_options(out var rp);
+                        rp.Level = lv;
+                        rp.Topology = 1;
+                        fixed (DsaMeshAttrInput* p = ain)
+                            NativeMethods.Check(NativeMethods.dsa_encode_repair_batch(_ctx, (uint)meshes.Count, p, in rp, out encoded), _ctx, "dsa_encode_repair_batch");
+                        return Streams(encoded, meshes.Count);
+                    }
                     fixed (DsaMeshAttrInput* p = ain)
                         NativeMethods.Check(NativeMethods.dsa_encode_level_batch(_ctx, (uint)meshes.Count, p, in lv, out encoded), _ctx, "dsa_encode_level_batch");
                     return Streams(encoded, meshes.Count);

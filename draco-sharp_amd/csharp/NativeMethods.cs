@@ -125,6 +125,15 @@ internal unsafe struct DsaEncodeLevelOptions
     public fixed int Reserved[6];   // zero
 }
 
+// dsa_encode_repair_options (dsa_encode_repair_batch): the reference's corner table for meshes that are not clean (128 bytes)
+[StructLayout(LayoutKind.Sequential)]
+internal unsafe struct DsaEncodeRepairOptions
+{
+    public DsaEncodeLevelOptions Level;
+    public int Topology;            // 0 strict, 1 repair as CornerTable(faces) does (CornerTable.cs:28-43)
+    public fixed int Reserved[7];   // zero
+}
+
 // dsa_encode_sequential_options (dsa_encode_sequential_batch): sequential meshes and point clouds
 [StructLayout(LayoutKind.Sequential)]
 internal unsafe struct DsaEncodeSequentialOptions
@@ -242,6 +251,8 @@ internal static unsafe partial class NativeMethods
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_sequential_batch(IntPtr ctx, uint n, DsaMeshInput* meshes, in DsaEncodeSequentialOptions options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern void dsa_encode_default_level_options(out DsaEncodeLevelOptions options);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_level_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, in DsaEncodeLevelOptions options, out IntPtr encoded);
+    [DllImport(Lib)] internal static extern void dsa_encode_default_repair_options(out DsaEncodeRepairOptions options);
+    [DllImport(Lib)] internal static extern DsaStatus dsa_encode_repair_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, in DsaEncodeRepairOptions options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_attributes_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, in DsaEncodeOptionsEx options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_attributes_sequential_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, in DsaEncodeSequentialOptions options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern uint dsa_encoded_size(IntPtr encoded);

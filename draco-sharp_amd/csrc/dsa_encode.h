@@ -9,6 +9,7 @@
 // Split of the work:
 //   GPU   (dsa_encode_conn.h)  k_enc_connectivity corner table, Edgebreaker symbols, depth-first attribute order, parallelogram
 //                                                 operand entries, one wave per mesh (DSA_ENC_HOST_CONN=1: by the host coder)
+//   GPU   (dsa_encode_repair.h) k_enc_repair_*   dsa_encode_repair_batch: the reference's corner table for the meshes the kernels above refuse
 //   GPU   (this file)          k_enc_bounds      quantisation range per attribute   AttributeQuantizationTransform.cs:66-108
 //                              k_enc_quantize    floats -> portable ints, normals -> octahedral (s,t), typed integers -> int32   :136-177, OctahedronToolBox.cs:28-119
 //                              k_enc_gather      vertex order -> traversal order, wrap bounds           PredictionSchemeWrapTransform.cs:88-100
@@ -762,6 +763,78 @@ static dsa_status enc_stage_plans(dsa_context *ctx, EncChunk &ck) {
   hostutil::parallel_for(ck.n, [&](uint32_t i) { enc_plan_mesh(ck, i); });          // capped thread count, every thread joined on every path (dsa_host_util.h)
   return DSA_OK;
 }
+// a repair request on the device path (dsa_encode_repair.h): the repaired corner table of every mesh by the repair kernels, in
+// device memory of its own; the tables come back, the host counts degenerate faces and isolated vertices out
+// (CornerTable::from_repaired) and the layout that follows is that of the meshes at their real sizes.  Host connectivity: the
+// host coder repaired the table in enc_plan_mesh.
+static dsa_status enc_stage_repair(dsa_context *ctx, EncLane &lane, EncChunk &ck) {
+  if (!ck.rq.repair || ck.host_conn) return DSA_OK;
+  const uint32_t n = ck.n;
+  ck.rep.assign(n, synth::CornerTable());
+  std::vector<dsa::EncRepair> recs;
+  std::vector<uint32_t> mesh_of;
+  EncArena A;
+  uint32_t maxf = 1;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (!ck.good(i)) continue;
+    const dsa_mesh_input &m = ck.mesh(i);
+    const uint64_t F = m.num_faces, V = m.num_vertices;
+    dsa::EncRepair R;
+    memset(&R, 0, sizeof(R));
+    R.F = m.num_faces; R.V = m.num_vertices;
+    R.faces = A.take(12 * F); R.c2v = A.take(12 * F); R.opp = A.take(12 * F); R.parent = A.take(12 * F);
+    R.voff = A.take(4 * (V + 1)); R.vcur = A.take(4 * V); R.vlist = A.take(12 * F);
+    R.pend = A.take(3 * F); R.bvis = A.take(3 * F); R.cvis = A.take(3 * F); R.vvis = A.take(V); R.stamp = A.take(12 * V);
+    recs.push_back(R); mesh_of.push_back(i);
+    maxf = std::max(maxf, m.num_faces);
+  }
+  const uint32_t nr = (uint32_t)recs.size();
+  if (!nr) return DSA_OK;
+  hipStream_t st = lane.st;
+  ENC_TRY(lane.repair.ensure(A.cur));
+  ENC_TRY(lane.repair_recs.ensure(std::max(sizeof(dsa::EncRepair), sizeof(dsa::EncRepairRows)) * n));
+  uint8_t *arena = (uint8_t *)lane.repair.p;
+  dsa::EncRepair *d_recs = (dsa::EncRepair *)lane.repair_recs.p;
+  ENC_TRY(hipMemsetAsync(arena, 0, A.cur, st));
+  for (uint32_t r = 0; r < nr; ++r) ENC_TRY(hipMemcpyAsync(arena + recs[r].faces, ck.mesh(mesh_of[r]).faces, 12ull * recs[r].F, hipMemcpyHostToDevice, st));
+  ENC_TRY(hipMemcpyAsync(d_recs, recs.data(), sizeof(dsa::EncRepair) * nr, hipMemcpyHostToDevice, st));
+  const uint32_t walk_lanes = 16;
+  const dim3 gt(std::max(1u, std::min(128u, (3u * maxf + 1023u) / 1024u)), nr);
+  hipLaunchKernelGGL(dsa::k_enc_repair_mark, gt, dim3(256), 0, st, arena, d_recs, nr);
+  hipLaunchKernelGGL(dsa::k_enc_repair_offsets, dim3(nr), dim3(WAVE), 0, st, arena, d_recs, nr);
+  hipLaunchKernelGGL(dsa::k_enc_repair_lists, gt, dim3(256), 0, st, arena, d_recs, nr);
+  hipLaunchKernelGGL(dsa::k_enc_repair_opposites, gt, dim3(256), 0, st, arena, d_recs, nr);
+  hipLaunchKernelGGL(dsa::k_enc_repair_fans, dim3((nr + walk_lanes - 1) / walk_lanes), dim3(WAVE), 0, st, arena, d_recs, nr, walk_lanes);
+  ENC_TRY(hipGetLastError());
+  ENC_TRY(hipMemcpyAsync(recs.data(), d_recs, sizeof(dsa::EncRepair) * nr, hipMemcpyDeviceToHost, st));
+  ENC_TRY(hipStreamSynchronize(st));
+  std::vector<synth::CornerTable::Repaired> out(nr);
+  for (uint32_t r = 0; r < nr; ++r) {
+    const dsa::EncRepair &R = recs[r];
+    if (R.status != dsa::ENC_REPAIR_OK || R.num_vertices < R.V || R.num_vertices - R.V > 3ull * R.F) continue;
+    synth::CornerTable::Repaired &o = out[r];
+    o.c2v.resize(3ull * R.F); o.opp.resize(3ull * R.F); o.parent.resize(R.num_vertices - R.V);
+    ENC_TRY(hipMemcpyAsync(o.c2v.data(), arena + R.c2v, 12ull * R.F, hipMemcpyDeviceToHost, st));
+    ENC_TRY(hipMemcpyAsync(o.opp.data(), arena + R.opp, 12ull * R.F, hipMemcpyDeviceToHost, st));
+    if (!o.parent.empty()) ENC_TRY(hipMemcpyAsync(o.parent.data(), arena + R.parent, 4ull * o.parent.size(), hipMemcpyDeviceToHost, st));
+    o.num_vertices = R.num_vertices; o.isolated = R.isolated; o.degenerate = R.degenerate; o.breaks = R.breaks;
+  }
+  ENC_TRY(hipStreamSynchronize(st));
+  hostutil::parallel_for(nr, [&](uint32_t r) {
+    const uint32_t i = mesh_of[r];
+    const dsa::EncRepair &R = recs[r];
+    if (R.status != dsa::ENC_REPAIR_OK) return ck.refuse(i, DSA_ERR_INVALID_DATA, dsa::enc_repair_message(R.status));
+    if (out[r].c2v.empty()) return ck.refuse(i, DSA_ERR_INVALID_DATA, dsa::enc_repair_message(~0u));
+    try {
+      const dsa_mesh_input &m = ck.mesh(i);
+      synth::CornerTable &t = ck.rep[i];
+      t.from_repaired(out[r], m.faces, m.num_faces, m.num_vertices);
+      ck.c2row[i].resize(t.nc());
+      for (uint32_t c = 0; c < t.nc(); ++c) ck.c2row[i][c] = t.row[t.c2v[c]];
+    } catch (const std::exception &e) { ck.refuse(i, DSA_ERR_INVALID_DATA, e.what()); }
+  });
+  return DSA_OK;
+}
 // the lane's device memory for the layout, cleared (histograms start at zero); the first uploads (host connectivity: all of them;
 // else phase A, what the walks need) on the chunk's turn on the link; the stream records.  Shared with encode_sequential_chunk.
 static dsa_status enc_stage_uploads(dsa_context *ctx, EncLane &lane, hostutil::TurnGuard &turn, EncChunk &ck) {
@@ -796,8 +869,9 @@ static dsa_status enc_stage_connectivity(dsa_context *ctx, EncLane &lane, hostut
   hipLaunchKernelGGL(dsa::k_enc_table_count, gt, dim3(256), 0, st, arena, d_conns, n);
   hipLaunchKernelGGL(dsa::k_enc_table_offsets, dim3(n), dim3(WAVE), 0, st, arena, d_conns, n);
   hipLaunchKernelGGL(dsa::k_enc_table_lists, gt, dim3(256), 0, st, arena, d_conns, n);
-  hipLaunchKernelGGL(dsa::k_enc_table_opposites, gt, dim3(256), 0, st, arena, d_conns, n);
+  if (ck.rep.empty()) hipLaunchKernelGGL(dsa::k_enc_table_opposites, gt, dim3(256), 0, st, arena, d_conns, n);      // (a repaired table's opposites came with its faces)
   hipLaunchKernelGGL(dsa::k_enc_table_corners, gt, dim3(256), 0, st, arena, d_conns, n);
+  if (ck.rq.repair_scan) hipLaunchKernelGGL(dsa::k_enc_repair_scan, gt, dim3(256), 0, st, arena, d_conns, n);
   // the walks on their stream; the attribute values travel and are quantised meanwhile
   ENC_TRY(hipEventRecord(lane.tables_done, st));
   ENC_TRY(hipStreamWaitEvent(lane.walk_st, lane.tables_done, 0));
@@ -851,6 +925,12 @@ static dsa_status enc_stage_attributes(dsa_context *ctx, EncLane &lane, EncChunk
     ENC_TRY(hipStreamWaitEvent(st, lane.walk_done, 0));
     hipLaunchKernelGGL(dsa::k_enc_operands, gt, dim3(256), 0, st, arena, d_conns, n);
     if (ck.want_pd) hipLaunchKernelGGL(dsa::k_enc_pd_operands, gt, dim3(256), 0, st, arena, d_conns, n);
+    if (!ck.rep_rows.empty()) {                                // repaired tables: an entry reads the row of its vertex
+      const uint32_t nr = (uint32_t)ck.rep_rows.size();
+      ENC_TRY(lane.repair_recs.ensure(sizeof(dsa::EncRepairRows) * nr));
+      ENC_TRY(hipMemcpyAsync(lane.repair_recs.p, ck.rep_rows.data(), sizeof(dsa::EncRepairRows) * nr, hipMemcpyHostToDevice, st));
+      hipLaunchKernelGGL(dsa::k_enc_repair_rows, dim3(gx, nr), dim3(256), 0, st, arena, (const dsa::EncRepairRows *)lane.repair_recs.p, nr);
+    }
     if (nz) {
       hipLaunchKernelGGL(dsa::k_enc_seam_operands<dsa::EncStream>, gz, dim3(256), 0, st, arena, d_conns, d_seams, nz, d_streams);
       if (ck.want_pd) hipLaunchKernelGGL(dsa::k_enc_pd_corner_streams<dsa::EncStream>, gz, dim3(256), 0, st, arena, d_conns, d_seams, nz, d_streams);
@@ -906,6 +986,7 @@ static dsa_status enc_stage_conn_results(dsa_context *ctx, EncLane &lane, EncChu
     conn_items.push_back({C.start_bits, 0, C.num_start_bits, i});
     conn_items.push_back({C.splits, 0, 12u * C.num_splits, i});
     ck.plans[i].interior_edges = (int64_t)C.interior_edges;
+    if (!ck.rep.empty()) { ck.plans[i].coded_vertices = C.V; ck.plans[i].coded_faces = C.F; }
   }
   const uint8_t *conn_host = nullptr;
   ENC_ST(enc_gather(lane, ck.arena, conn_items, nullptr, &conn_host));
@@ -1000,6 +1081,8 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, const EncRequest
   EncLap lap{&lane};
   ENC_STAGE(enc_stage_plans(ctx, ck));
   lap("host checks / plan");
+  ENC_STAGE(enc_stage_repair(ctx, lane, ck));
+  if (ck.rq.repair) lap("topology repair");
   enc_layout(ck);
   if (!ck.L.streams.empty()) {
     ENC_STAGE(enc_stage_uploads(ctx, lane, turn, ck));
@@ -1177,12 +1260,52 @@ static EncRequest enc_request(uint32_t n, bool sequential) {
   dsa_encode_sequential_default_options(&rq.seq);
   return rq;
 }
-static dsa_status encode_request(dsa_context *ctx, const EncRequest &rq, dsa_encoded **out) {
+// batch_n: the size of the batch the request belongs to (what chooses between host and device connectivity); 0: the request's own
+static dsa_status encode_request(dsa_context *ctx, const EncRequest &rq, dsa_encoded **out, uint32_t batch_n = 0) {
   if (!ctx || !out || (rq.n && !rq.vertex && !rq.corners && !rq.listed)) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "null argument");
   if (enc_check_request(ctx, rq) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+  if (batch_n == 0) batch_n = rq.n;
   DSA_GUARD(ctx, encode_batch_chunks(ctx, rq.n, [&](dsa_context *sink, EncLane &lane, uint32_t base, uint32_t cnt, dsa_encoded **part) {      // host vectors and threads inside: nothing may unwind into the caller
-    return rq.sequential ? encode_sequential_chunk(sink, lane, rq, base, cnt, rq.n, part) : encode_chunk(sink, lane, rq, base, cnt, rq.n, part);
+    return rq.sequential ? encode_sequential_chunk(sink, lane, rq, base, cnt, rq.n, part) : encode_chunk(sink, lane, rq, base, cnt, batch_n, part);
   }, out));
+}
+// dsa_encode_repair_batch, topology = 1: the batch as dsa_encode_level_batch codes it; then the meshes refused for their topology
+// once more as a request of their own, on the repaired corner table (EncRequest::repair), their results into the first's places.
+// Clean meshes take the kernels they always took and nothing else.
+static bool enc_topology_refusal(const std::string &why) {
+  for (uint32_t s : {(uint32_t)dsa::ENC_DEGENERATE, (uint32_t)dsa::ENC_NONMANIFOLD_EDGE, (uint32_t)dsa::ENC_RING, (uint32_t)dsa::ENC_NONMANIFOLD_VERTEX, (uint32_t)dsa::ENC_ISOLATED})
+    if (why == dsa::enc_conn_message(s)) return true;
+  return false;
+}
+static dsa_status encode_repair_request(dsa_context *ctx, const EncRequest &request, dsa_encoded **out) {
+  EncRequest rq = request;
+  rq.repair_scan = true;
+  const dsa_status st = encode_request(ctx, rq, out);
+  if (st != DSA_OK || rq.n == 0) return st;
+  std::unique_ptr<dsa_encoded> E(*out);
+  *out = nullptr;
+  try {
+    std::vector<uint32_t> again;
+    std::vector<dsa_mesh_attr_input> sub;
+    for (uint32_t i = 0; i < rq.n; ++i) {
+      if (E->status[i] != DSA_ERR_INVALID_DATA) continue;
+      const dsa_mesh_input &m = rq.mesh(i);
+      if (m.positions && m.num_vertices >= 3 && m.num_faces == 0 && E->messages[i] == "mesh needs positions and faces") { E->messages[i] = "all triangles are degenerate"; continue; }
+      if (enc_topology_refusal(E->messages[i])) { again.push_back(i); sub.push_back(rq.listed[i]); }
+    }
+    if (!again.empty()) {
+      EncRequest r2 = rq;
+      r2.repair_scan = false; r2.repair = true; r2.n = (uint32_t)again.size(); r2.listed = sub.data();
+      dsa_encoded *second = nullptr;
+      const dsa_status s2 = encode_request(ctx, r2, &second, rq.n);
+      if (s2 != DSA_OK) return s2;
+      std::unique_ptr<dsa_encoded> E2(second);
+      for (uint32_t k = 0; k < r2.n; ++k) { E->streams[again[k]].swap(E2->streams[k]); E->status[again[k]] = E2->status[k]; E->messages[again[k]].swap(E2->messages[k]); }
+    }
+  } catch (const std::bad_alloc &) { return set_err(ctx, DSA_ERR_OUT_OF_MEMORY, "host allocation failed"); }
+  catch (...) { return set_err(ctx, DSA_ERR_DEVICE, "unexpected failure inside the library"); }
+  *out = E.release();
+  return DSA_OK;
 }
 dsa_status dsa_encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_encode_options *options, dsa_encoded **out) {
   EncRequest rq = enc_request(n, false);
@@ -1215,6 +1338,27 @@ dsa_status dsa_encode_level_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_a
   rq.listed = meshes;
   if (options) rq.level = *options;
   return encode_request(ctx, rq, out);
+}
+void dsa_encode_default_repair_options(dsa_encode_repair_options *o) {
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  dsa_encode_default_level_options(&o->level);
+}
+// dsa_encode_level_batch that also takes meshes with degenerate faces, non-manifold edges and vertices and isolated vertices
+// (topology = 1: the reference's corner table, dsa_encode_repair.h).  With topology 0 it is dsa_encode_level_batch.
+dsa_status dsa_encode_repair_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_encode_repair_options *options, dsa_encoded **out) {
+  EncRequest rq = enc_request(n, false);
+  rq.listed = meshes;
+  int32_t topology = 0;
+  if (options) {
+    if (options->topology != 0 && options->topology != 1)
+      return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "topology %d: 0 (strict) or 1 (the reference's corner table)", (int)options->topology);
+    for (int k = 0; k < 7; ++k)
+      if (options->reserved[k] != 0) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "dsa_encode_repair_options.reserved[%d] is not zero", k);
+    rq.level = options->level;
+    topology = options->topology;
+  }
+  return topology == 1 ? encode_repair_request(ctx, rq, out) : encode_request(ctx, rq, out);
 }
 dsa_status dsa_encode_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_encode_sequential_options *options, dsa_encoded **out) {
   EncRequest rq = enc_request(n, true);

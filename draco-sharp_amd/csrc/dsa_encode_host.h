@@ -302,6 +302,166 @@ struct CornerTable {
       check(reach[v] == count[v], "non-manifold vertex in input mesh");
     }
   }
+
+  // ---- repair mode: the reference's corner table (CornerTable.cs:28-43) in place of the checks above.
+  // What the three passes leave, over the caller's faces and vertex ids: c2v' (a fan behind the first of its vertex has a new
+  // vertex V, V + 1, ...), the opposites, the parent of every new vertex, and the counts the stream's header needs.
+  struct Repaired {
+    std::vector<uint32_t> c2v, opp, parent;      // u32[3F], u32[3F], u32[V' - V]
+    uint32_t num_vertices = 0, isolated = 0, degenerate = 0, breaks = 0;      // V'; unused vertices among the caller's V; faces with a repeated index; edges cut
+  };
+  // row[v]: the caller's value row of vertex v of this table (repair mode only; empty: the vertex is its own row)
+  std::vector<uint32_t> row;
+  bool needed_repair = false;      // build_repaired: the mesh is not one build() takes
+  uint32_t row_of(uint32_t v) const { return row.empty() ? v : row[v]; }
+
+  static void repair(const uint32_t *faces, uint32_t num_faces, uint32_t num_vertices, Repaired &r) {
+    const uint32_t ncor = num_faces * 3;
+    r.c2v.assign(faces, faces + (size_t)ncor);
+    r.opp.assign(ncor, kInvalid);
+    r.parent.clear();
+    r.isolated = r.degenerate = r.breaks = 0;
+    std::vector<uint32_t> &c2v = r.c2v, &opp = r.opp;
+    auto degenerate = [&](uint32_t f) { return c2v[3 * f] == c2v[3 * f + 1] || c2v[3 * f] == c2v[3 * f + 2] || c2v[3 * f + 1] == c2v[3 * f + 2]; };
+    std::vector<uint8_t> degen(num_faces, 0);
+    for (uint32_t f = 0; f < num_faces; ++f) if (degenerate(f)) { degen[f] = 1; ++r.degenerate; }
+    // ComputeOppositeCorners (:298-394), with the scan over the whole pending list of the sink vertex: corners in index order;
+    // corner c faces source -> sink and takes the earliest pending sink -> source whose face has another tip; else it waits at
+    // its source behind the entries already there.  (Degenerate faces were marked on the caller's indices, as :332-341 sees them.)
+    {
+      std::vector<uint32_t> off(num_vertices + 1, 0), cnt(num_vertices, 0);
+      for (uint32_t c = 0; c < ncor; ++c) ++off[c2v[c] + 1];
+      for (uint32_t v = 0; v < num_vertices; ++v) off[v + 1] += off[v];
+      std::vector<uint32_t> p_sink(ncor), p_corner(ncor);
+      for (uint32_t c = 0; c < ncor; ++c) {
+        if (degen[c / 3]) continue;
+        const uint32_t tip = c2v[c], source = c2v[next(c)], sink = c2v[prev(c)];
+        uint32_t found = kInvalid;
+        const uint32_t at = off[sink];
+        for (uint32_t i = 0; i < cnt[sink]; ++i) {
+          if (p_sink[at + i] != source || c2v[p_corner[at + i]] == tip) continue;
+          found = p_corner[at + i];
+          for (uint32_t j = i + 1; j < cnt[sink]; ++j) { p_sink[at + j - 1] = p_sink[at + j]; p_corner[at + j - 1] = p_corner[at + j]; }
+          --cnt[sink];
+          break;
+        }
+        if (found == kInvalid) { const uint32_t k = off[source] + cnt[source]++; p_sink[k] = sink; p_corner[k] = c; }
+        else { opp[c] = found; opp[found] = c; }
+      }
+    }
+    auto swing_l = [&](uint32_t c) { const uint32_t o = opp[next(c)]; return o == kInvalid ? kInvalid : next(o); };
+    auto swing_r = [&](uint32_t c) { const uint32_t o = opp[prev(c)]; return o == kInvalid ? kInvalid : prev(o); };
+    // BreakNonManifoldEdges (:396-469): around every fan, two edges that reach the same sink vertex and are not each other's
+    // opposite are cut on both sides; sweeps until one changes nothing, the visited marks kept from sweep to sweep.  (The walk
+    // ends at the fan's open end, as the loop it was ported from does; :466 tests the first corner, which never is invalid.)
+    {
+      std::vector<uint8_t> visited(ncor, 0);
+      std::vector<std::pair<uint32_t, uint32_t>> sinks;
+      bool updated;
+      do {
+        updated = false;
+        for (uint32_t c = 0; c < ncor; ++c) {
+          if (visited[c] || degen[c / 3]) continue;
+          sinks.clear();
+          uint32_t first = c, cur = c, nx = swing_l(cur);
+          while (nx != first && nx != kInvalid && !visited[nx]) { cur = nx; nx = swing_l(cur); }
+          first = cur;
+          do {
+            visited[cur] = 1;
+            const uint32_t sink_c = next(cur), sink_v = c2v[sink_c], edge_c = prev(cur);
+            bool cut = false;
+            for (const auto &s : sinks) {
+              if (s.first != sink_v) continue;
+              const uint32_t other = s.second, o_edge = opp[edge_c];
+              if (o_edge == other) continue;
+              const uint32_t o_other = opp[other];
+              if (o_edge != kInvalid) opp[o_edge] = kInvalid;
+              if (o_other != kInvalid) opp[o_other] = kInvalid;
+              opp[edge_c] = kInvalid; opp[other] = kInvalid;
+              cut = true;
+              break;
+            }
+            if (cut) { updated = true; ++r.breaks; break; }
+            sinks.push_back({c2v[prev(cur)], sink_c});
+            cur = swing_r(cur);
+          } while (cur != first && cur != kInvalid);
+        }
+      } while (updated);
+    }
+    // ComputeVertexCorners (:471-547): faces in index order; the first fan met keeps the vertex, every later one gets a new
+    // vertex with a parent; a vertex no fan reached is isolated.
+    {
+      std::vector<uint8_t> vvis(num_vertices, 0), cvis(ncor, 0);
+      uint32_t nv = num_vertices;
+      for (uint32_t f = 0; f < num_faces; ++f) {
+        if (degen[f]) continue;
+        for (uint32_t k = 0; k < 3; ++k) {
+          const uint32_t c = 3 * f + k;
+          if (cvis[c]) continue;
+          uint32_t v = c2v[c];
+          bool fresh = false;
+          if (vvis[v]) { r.parent.push_back(v); v = nv++; fresh = true; }
+          else vvis[v] = 1;
+          uint32_t act = c;
+          while (act != kInvalid) {
+            cvis[act] = 1;
+            if (fresh) c2v[act] = v;
+            act = swing_l(act);
+            if (act == c) break;
+          }
+          if (act == kInvalid) {
+            act = swing_r(c);
+            while (act != kInvalid) { cvis[act] = 1; if (fresh) c2v[act] = v; act = swing_r(act); }
+          }
+        }
+      }
+      for (uint32_t v = 0; v < num_vertices; ++v) if (!vvis[v]) ++r.isolated;
+      r.num_vertices = nv;
+    }
+  }
+
+  // The repaired table as every walk takes it: degenerate faces and isolated vertices counted out (faces and vertices keep their
+  // order, so start faces, holes and symbols are those of the reference's walk over the table with the gaps), opposites carried
+  // over from the repair -- matching the renumbered faces again would join edges the repair cut.
+  void build_repaired(const uint32_t *faces, uint32_t num_faces, uint32_t num_vertices) {
+    Repaired r;
+    repair(faces, num_faces, num_vertices, r);
+    from_repaired(r, faces, num_faces, num_vertices);
+  }
+  // (the device encoder's repair kernels give `r`: dsa_encode_repair.h)
+  void from_repaired(const Repaired &r, const uint32_t *faces, uint32_t num_faces, uint32_t num_vertices) {
+    check(r.degenerate < num_faces, "all triangles are degenerate");
+    needed_repair = r.degenerate != 0 || r.isolated != 0 || r.breaks != 0 || r.num_vertices != num_vertices;
+    std::vector<uint32_t> vmap(r.num_vertices, kInvalid), cmap((size_t)num_faces * 3, kInvalid);
+    uint32_t nf2 = 0;
+    for (uint32_t f = 0; f < num_faces; ++f) {
+      if (faces[3 * f] == faces[3 * f + 1] || faces[3 * f] == faces[3 * f + 2] || faces[3 * f + 1] == faces[3 * f + 2]) continue;
+      for (uint32_t k = 0; k < 3; ++k) { cmap[3 * f + k] = 3 * nf2 + k; vmap[r.c2v[3 * f + k]] = 0; }
+      ++nf2;
+    }
+    row.clear();
+    for (uint32_t v = 0; v < r.num_vertices; ++v) {
+      if (vmap[v] == kInvalid) continue;
+      vmap[v] = (uint32_t)row.size();
+      row.push_back(v < num_vertices ? v : r.parent[v - num_vertices]);
+    }
+    c2v.assign((size_t)nf2 * 3, kInvalid);
+    opp.assign((size_t)nf2 * 3, kInvalid);
+    for (uint32_t c = 0; c < num_faces * 3; ++c) {
+      if (cmap[c] == kInvalid) continue;
+      c2v[cmap[c]] = vmap[r.c2v[c]];
+      if (r.opp[c] != kInvalid) opp[cmap[c]] = cmap[r.opp[c]];
+    }
+    vcorner.assign(row.size(), kInvalid);
+    for (uint32_t c = 0; c < nc(); ++c) if (vcorner[c2v[c]] == kInvalid) vcorner[c2v[c]] = c;
+    for (uint32_t v = 0; v < nv(); ++v) {          // the left-most corner of a boundary vertex, as build() leaves it
+      const uint32_t first = vcorner[v];
+      uint32_t act = swing_left(first), c = first;
+      size_t guard = 0;
+      while (act != kInvalid && act != first) { c = act; act = swing_left(act); check(++guard < c2v.size(), "vertex ring does not close"); }
+      if (act != first) vcorner[v] = c;
+    }
+  }
 };
 
 // The connectivity of one attribute with seams (MeshAttributeCornerTable.cs, encoder side): the position corner
@@ -720,6 +880,8 @@ struct Options {
   int32_t generic_data_type = 2;     // element type of the generic attribute, Draco's ids: 1 int8, 2 uint8, 3 int16, 4 uint16, 5 int32,
                                      // 6 uint32 (joint indices, 16-bit colours, feature ids); the device encoder's generic attribute is
                                      // uint8, it writes the other types from MeshIn::extras (dsa_mesh_attr_input)
+  int32_t repair_topology = 0;       // 1: the reference's corner table (CornerTable::build_repaired) in place of the refusal of degenerate
+                                     // faces, non-manifold edges and vertices and isolated vertices; a clean mesh gives the same bytes
 };
 
 // Octahedral quantisation (OctahedronToolBox.cs:28-119)
@@ -926,7 +1088,7 @@ static void fill_extra_values(const PortableAttr &a, uint32_t nv, PortableAttr &
 // bitstream's 64-bit arithmetic).  Per-vertex attributes only: a data id's position is its vertex's.
 template <class CT>
 static void geometric_normal_prediction(const Octa &o, const CT &ct, const CornerTable &pos_ct, const std::vector<int32_t> &pos, uint32_t ci, int32_t v3[3]) {
-  auto P = [&](uint32_t c, int k) { return (int64_t)pos[(size_t)pos_ct.vertex(c) * 3 + k]; };
+  auto P = [&](uint32_t c, int k) { return (int64_t)pos[(size_t)pos_ct.row_of(pos_ct.vertex(c)) * 3 + k]; };
   uint64_t n[3] = {0, 0, 0};
   uint32_t c = ci;
   bool left = true;
@@ -994,7 +1156,7 @@ static void write_attribute_values(ByteWriter &w, const PortableAttr &a, const C
   std::vector<int32_t> d(entries * nc);
   for (size_t e = 0; e < entries; ++e) {
     const uint32_t corner = seq.data_to_corner[e];
-    const uint32_t v = a.corner_value ? a.corner_value[corner] : pos_ct.vertex(corner);
+    const uint32_t v = a.corner_value ? a.corner_value[corner] : pos_ct.row_of(pos_ct.vertex(corner));
     for (int c = 0; c < nc; ++c) d[e * nc + c] = a.vals[(size_t)v * nc + c];
   }
   std::vector<uint32_t> symbols(entries * nc);
@@ -1072,7 +1234,7 @@ static void write_attribute_values(ByteWriter &w, const PortableAttr &a, const C
       do { root = (root + number / root) / 2; } while (root * root > number);
       return root;
     };
-    auto P = [&](int32_t entry, int k) { return (int64_t)positions->vals[(size_t)pos_ct.vertex(seq.data_to_corner[entry]) * 3 + k]; };
+    auto P = [&](int32_t entry, int k) { return (int64_t)positions->vals[(size_t)pos_ct.row_of(pos_ct.vertex(seq.data_to_corner[entry])) * 3 + k]; };
     for (size_t p = entries; p-- > 0;) {
       const int32_t data_id = (int32_t)p;
       const uint32_t ci = seq.data_to_corner[p];
@@ -1285,6 +1447,7 @@ struct MeshPlan {
   bool single = false;
   uint32_t num_att_data = 0;
   int64_t interior_edges = -1;       // >= 0: given (connectivity coded on the device, no corner table here); else counted from ct
+  int64_t coded_vertices = -1, coded_faces = -1;      // >= 0: a repaired table's counts for the header (V' - isolated, F - degenerate); else the input's
 };
 // What of a plan does not depend on the connectivity: attribute descriptors and the options that shape the stream.
 static void plan_attributes(const MeshIn &in, const Options &opt, MeshPlan &pl) {
@@ -1303,18 +1466,27 @@ static void plan_attributes(const MeshIn &in, const Options &opt, MeshPlan &pl) 
   pl.traversal_method = opt.traversal_method;
 }
 static void plan_mesh(const MeshIn &in, const Options &opt, MeshPlan &pl) {
-  pl.ct.build(in.faces, in.nf, in.nv);
-  for (uint32_t v = 0; v < in.nv; ++v) check(pl.ct.vcorner[v] != kInvalid, "isolated vertex in input mesh");
+  if (opt.repair_topology) {
+    pl.ct.build_repaired(in.faces, in.nf, in.nv);
+    // (seam tables over a repaired table are not written yet: a mesh that needed no repair goes on as it always did)
+    check(!(in.normal_corners || in.uv_corners) || !pl.ct.needed_repair, "attributes given per corner over a mesh whose topology needs repair are not implemented");
+    if (!pl.ct.needed_repair) pl.ct.row.clear();
+    else { pl.coded_vertices = pl.ct.nv(); pl.coded_faces = pl.ct.nf(); }
+  } else {
+    pl.ct.build(in.faces, in.nf, in.nv);
+    for (uint32_t v = 0; v < in.nv; ++v) check(pl.ct.vcorner[v] != kInvalid, "isolated vertex in input mesh");
+  }
+  const uint32_t coded_vertices = pl.ct.nv();                  // (repair mode: V' - isolated)
   EbEncoder enc(pl.ct, pl.eb);
   enc.run();
   dfs_sequence(pl.ct, pl.eb.processed_corners, pl.seq);
-  check(pl.seq.data_to_corner.size() == in.nv, "traversal did not reach every vertex");
+  check(pl.seq.data_to_corner.size() == coded_vertices, "traversal did not reach every vertex");
   plan_attributes(in, opt, pl);
   if (pl.valence) valence_context_symbols(pl.ct, pl.eb, pl.ctx_symbols);
   if (pl.predictive) predictive_symbols(pl.ct, pl.eb, pl.explicit_symbols, pl.predictions);
   if (pl.traversal_method != 0) {
     prediction_degree_sequence(pl.ct, pl.eb.processed_corners, pl.seq_pd);
-    check(pl.seq_pd.data_to_corner.size() == in.nv, "traversal did not reach every vertex");
+    check(pl.seq_pd.data_to_corner.size() == coded_vertices, "traversal did not reach every vertex");
   }
   // attributes given per corner: their seams, their own vertices and traversal order (MeshEdgeBreakerEncoder.cs:403-414,
   // :545-566: the sequencer of a seamed attribute walks the attribute's corner table in the connectivity's face order)
@@ -1343,8 +1515,9 @@ static void write_stream(ByteWriter &w, const MeshIn &in, const MeshPlan &pl, Va
   w.d.insert(w.d.end(), {'D', 'R', 'A', 'C', 'O'});
   w.u8(2); w.u8(2); w.u8(1); w.u8(1); w.u16(0);
   w.u8(pl.valence ? 2 : (pl.predictive ? 1 : 0));   // Edgebreaker traversal: standard (DracoEncoder.cs:90), predictive or valence
-  w.varint(in.nv);
-  w.varint(in.nf);
+  // (a repaired table: the vertices and faces it codes, V' - isolated and F - degenerate; MeshEdgeBreakerEncoder.cs:46-47)
+  w.varint(pl.coded_vertices >= 0 ? (uint64_t)pl.coded_vertices : in.nv);
+  w.varint(pl.coded_faces >= 0 ? (uint64_t)pl.coded_faces : in.nf);
   w.u8((uint8_t)pl.num_att_data);
   w.varint(eb.symbols.size());
   w.varint(eb.num_split_symbols);

@@ -22,6 +22,7 @@
 #include "dsa_common.h"
 #include "dsa_encode_host.h"
 #include "dsa_encode_conn.h"
+#include "dsa_encode_repair.h"
 #include "dsa_encode_seams.h"
 #include "dsa_encode_seqidx.h"
 #include "dsa_encode_schemes.h"
@@ -112,6 +113,8 @@ struct EncRequest {
   const dsa_mesh_corner_input *corners = nullptr;
   const dsa_mesh_attr_input *listed = nullptr;
   bool sequential = false;
+  bool repair_scan = false;                // dsa_encode_repair_batch, topology = 1, the first pass: two faces turned against each other over the same vertices are refused too
+  bool repair = false;                     // dsa_encode_repair_batch, topology = 1, the second pass: the meshes the first pass refused for their topology, on the repaired corner table
   dsa_encode_level_options level;          // Edgebreaker streams
   dsa_encode_sequential_options seq;       // sequential streams
   const dsa_encode_options &base() const { return sequential ? seq.base : level.ex.base; }
@@ -128,6 +131,7 @@ static synth::Options enc_synth_options(const EncRequest &rq) {
   if (rq.sequential) return opt;
   opt.single_connectivity = od.single_connectivity; opt.pos_prediction = od.position_prediction; opt.uv_prediction = od.texcoord_prediction;
   opt.normal_prediction = rq.level.ex.normal_prediction; opt.traversal_method = rq.level.traversal_method;
+  opt.repair_topology = rq.repair ? 1 : 0;
   return opt;
 }
 
@@ -171,6 +175,12 @@ struct EncChunk {
   std::vector<std::vector<int32_t>> ops, ops_pd;
   std::vector<std::vector<std::vector<uint32_t>>> att_e2v, att_opp;
   std::vector<std::vector<std::vector<int32_t>>> att_ops;
+  // a repaired table (EncRequest::repair), per mesh: the value row of every corner (both paths: what the schemes that read the
+  // positions index them by); device connectivity: the table the repair kernels left, degenerate faces and isolated vertices
+  // counted out (ct.c2v, ct.opp, ct.row), which the layout uploads in place of the caller's faces
+  std::vector<std::vector<uint32_t>> c2row;
+  std::vector<synth::CornerTable> rep;
+  std::vector<dsa::EncRepairRows> rep_rows;
   EncLayout L;
   std::vector<std::pair<uint64_t, uint64_t>> *region_log = nullptr;
   // the device's side and what comes back from it
@@ -188,6 +198,9 @@ struct EncChunk {
     if (rq.listed) { extras.resize(n); extra_cap.resize(n); }
   }
   const dsa_mesh_input &mesh(uint32_t i) const { return rq.mesh(base + i); }
+  // vertices and faces of mesh i as the connectivity kernels and the streams see them
+  uint32_t coded_vertices(uint32_t i) const { return !rep.empty() ? rep[i].nv() : (plans[i].coded_vertices >= 0 ? (uint32_t)plans[i].coded_vertices : mesh(i).num_vertices); }
+  uint32_t coded_faces(uint32_t i) const { return !rep.empty() ? rep[i].nf() : (plans[i].coded_faces >= 0 ? (uint32_t)plans[i].coded_faces : mesh(i).num_faces); }
   const dsa_mesh_corner_input *corner(uint32_t i) const { return rq.corner(base + i); }
   bool good(uint32_t i) const { return E->status[i] == DSA_OK; }
   void refuse(uint32_t i, dsa_status st, const std::string &why) { E->status[i] = st; E->messages[i] = why; }
@@ -259,6 +272,9 @@ static void enc_plan_mesh(EncChunk &ck, uint32_t i) {
     const std::string why = enc_take_extras(*ck.rq.attr(ck.base + i), ck.extras[i], in);
     if (!why.empty()) return ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, why);
   }
+  // (every mesh of a repair request is one whose topology the first pass refused)
+  if (ck.rq.repair && (in.normal_corners || in.uv_corners))
+    return ck.refuse(i, DSA_ERR_NOT_IMPLEMENTED, "attributes given per corner (normal_corners / texcoord_corners) over a mesh whose topology needs repair are not implemented");
   try {
     synth::check(m.positions && m.faces && m.num_vertices >= 3 && m.num_faces >= 1, "mesh needs positions and faces");
     for (size_t k = 0; k < (size_t)m.num_faces * 3; ++k) synth::check(m.faces[k] < m.num_vertices, "face index out of range");
@@ -281,9 +297,17 @@ static void enc_plan_mesh(EncChunk &ck, uint32_t i) {
       return;
     }
     synth::plan_mesh(in, mo, pl);
+    if (ck.rq.repair_scan)                                     // (k_enc_repair_scan on the device path)
+      for (uint32_t c = 0; c < pl.ct.nc(); ++c) synth::check(pl.ct.opp[c] == synth::kInvalid || pl.ct.c2v[pl.ct.opp[c]] != pl.ct.c2v[c], dsa::enc_conn_message(dsa::ENC_NONMANIFOLD_EDGE));
     enc_extra_caps(ck, i);
     dsa::entry_maps(pl.ct, pl.seq, nullptr, ck.e2v[i], &ck.ops[i]);
     if (ck.want_pd) dsa::entry_maps(pl.ct, pl.seq_pd, nullptr, ck.e2v_pd[i], &ck.ops_pd[i]);
+    if (!pl.ct.row.empty()) {                                  // a repaired table: an entry reads the row of its vertex, the position of a corner is its row's
+      for (uint32_t &v : ck.e2v[i]) v = pl.ct.row[v];
+      if (ck.want_pd) for (uint32_t &v : ck.e2v_pd[i]) v = pl.ct.row[v];
+      ck.c2row[i].resize(pl.ct.nc());
+      for (uint32_t c = 0; c < pl.ct.nc(); ++c) ck.c2row[i][c] = pl.ct.row[pl.ct.c2v[c]];
+    }
     ck.att_e2v[i].assign(pl.atts.size(), {}); ck.att_ops[i].assign(pl.atts.size(), {}); ck.att_opp[i].assign(pl.atts.size(), {});
     for (size_t k = 1; k < pl.atts.size(); ++k) {
       const uint32_t *ids = pl.atts[k].corner_value;
@@ -300,6 +324,7 @@ static void enc_plan_mesh(EncChunk &ck, uint32_t i) {
 // the chunk's switches and the vectors enc_plan_mesh fills (DSA_ENC_HOST_CONN / DSA_ENC_HOST_PLAN as the caller read them)
 static void enc_begin_plans(EncChunk &ck, bool host_conn, bool host_plan) {
   ck.host_conn = host_conn; ck.host_plan = host_plan; ck.want_pd = ck.opt.traversal_method != 0;
+  if (ck.rq.repair) ck.c2row.resize(ck.n);
   if (!host_conn) return;
   ck.e2v.resize(ck.n); ck.ops.resize(ck.n); ck.att_e2v.resize(ck.n); ck.att_ops.resize(ck.n); ck.att_opp.resize(ck.n);
   if (ck.want_pd) { ck.e2v_pd.resize(ck.n); ck.ops_pd.resize(ck.n); }
@@ -409,10 +434,17 @@ static void enc_layout(EncChunk &ck) {
     const std::vector<synth::PortableAttr> &atts = ck.plans[i].atts;
     dsa::EncConn &C = L.conns[i];
     C.status = dsa::ENC_OK;
-    C.F = m.num_faces; C.V = m.num_vertices; C.split_cap = C.F; C.fail_key = 0xFFFFFFFFu;
+    C.F = ck.coded_faces(i); C.V = ck.coded_vertices(i); C.split_cap = C.F; C.fail_key = 0xFFFFFFFFu;
     C.vstream = ck.valence_of(i) ? L.first_stream[i] + (uint32_t)atts.size() : DSA_INVALID;
     C.faces_narrow = C.V <= 65536 ? 1u : 0u;
-    (C.faces_narrow ? C.faces16 : C.faces) = A.put(L.uploads_a, m.faces, (C.faces_narrow ? 6ull : 12ull) * C.F, C.faces_narrow != 0);
+    (C.faces_narrow ? C.faces16 : C.faces) = A.put(L.uploads_a, ck.rep.empty() ? m.faces : ck.rep[i].c2v.data(), (C.faces_narrow ? 6ull : 12ull) * C.F, C.faces_narrow != 0);
+    if (!ck.rep.empty()) {                                     // a repaired table: its opposites are given, and the row of every vertex
+      C.opp = A.put(L.uploads_a, ck.rep[i].opp.data(), 12ull * C.F, false);
+      dsa::EncRepairRows R;
+      memset(&R, 0, sizeof(R));
+      R.row = A.put(L.uploads_a, ck.rep[i].row.data(), 4ull * C.V, false); R.count = C.V; R.pad = i;
+      ck.rep_rows.push_back(R);
+    }
     L.maxf = std::max(L.maxf, C.F);
     for (size_t k = 0; k < atts.size(); ++k) {
       if (!atts[k].corner_value) continue;
@@ -429,8 +461,10 @@ static void enc_layout(EncChunk &ck) {
     if (!ck.good(i)) continue;
     const dsa_mesh_input &m = ck.mesh(i);
     const synth::MeshPlan &pl = ck.plans[i];
-    const uint32_t V = m.num_vertices, s0 = L.first_stream[i];
+    const uint32_t V = ck.coded_vertices(i), s0 = L.first_stream[i];
     auto put = [&](const void *src, uint64_t bytes) { return A.put(L.uploads, src, bytes, false); };
+    const bool repaired = ck.rq.repair && !ck.c2row[i].empty();
+    const uint64_t t_c2row = repaired ? put(ck.c2row[i].data(), 4ull * ck.c2row[i].size()) : 0;
     uint64_t o_e2v[2] = {0, 0}, o_ops[2] = {0, 0}, t_c2v = 0, t_opp = 0, t_d2c[2] = {0, 0}, t_v2d[2] = {0, 0};       // [1]: in prediction-degree order
     bool needs_topo = false;
     for (const synth::PortableAttr &a : pl.atts) needs_topo = needs_topo || enc_topo_scheme(a);
@@ -457,8 +491,10 @@ static void enc_layout(EncChunk &ck) {
         }
       } else if (a.corner_value) S.pd_want = pd ? 1u : 0u;
       enc_value_stream_input(S, a, m, ck.rows_of(i, a), A, L.uploads);
+      if (repaired && !host_conn) S.t_c2p = t_c2row;          // (kept below, where the connectivity's own regions become the stream's view)
       if (!host_conn || !enc_topo_scheme(a)) continue;
       S.t_c2p = S.t_c2a = t_c2v; S.t_opp = t_opp; S.t_d2c = t_d2c[pd]; S.t_v2d = t_v2d[pd];
+      if (repaired) S.t_c2p = t_c2row;
       if (a.corner_value && pl.seamed(k)) {                   // a seamed attribute's own table and order
         const std::vector<uint32_t> &c2a = pl.conns[k].c2v, &o2 = ck.att_opp[i][k], &d2c = pl.seq_att[k].data_to_corner;
         const std::vector<int32_t> &v2d = pl.seq_att[k].vertex_to_data;
@@ -477,17 +513,17 @@ static void enc_layout(EncChunk &ck) {
   }
   L.input_bytes = A.cur;
   // everything the kernels write
-  size_t z = 0;
+  size_t z = 0, rr = 0;
   for (uint32_t i = 0; i < n; ++i) {
     if (!ck.good(i)) continue;
-    const dsa_mesh_input &m = ck.mesh(i);
     const std::vector<synth::PortableAttr> &atts = ck.plans[i].atts;
-    const uint64_t V = m.num_vertices, F = m.num_faces;
+    const uint64_t V = ck.coded_vertices(i), F = ck.coded_faces(i);
     const uint32_t s0 = L.first_stream[i];
     dsa::EncConn *C = host_conn ? nullptr : &L.conns[i];
     if (C) {
       if (C->faces_narrow) C->faces = A.take(12 * F);
-      C->opp = A.take(12 * F); C->voff = A.take(4 * (V + 1)); C->vcur = A.take(4 * V); C->vlist = A.take(12 * F); C->vcorner = A.take(4 * V);
+      if (ck.rep.empty()) C->opp = A.take(12 * F);
+      C->voff = A.take(4 * (V + 1)); C->vcur = A.take(4 * V); C->vlist = A.take(12 * F); C->vcorner = A.take(4 * V);
       C->vvis = A.take(V); C->frec = A.take(32 * F);
       C->stack = A.take(4 * F); C->processed = A.take(4 * F); C->init_corners = A.take(4 * F);
       C->symbols = A.take(F); C->start_bits = A.take(F); C->splits = A.take(12ull * C->split_cap);
@@ -496,6 +532,7 @@ static void enc_layout(EncChunk &ck) {
         C->pd_d2c = A.take(4 * V); C->pd_v2d = A.take(4 * V); C->pd_e2v = A.take(4 * V); C->pd_ops = A.take(12 * V);
         C->pd_next = A.take(12 * F); C->pd_degree = A.take(4 * V); C->pd_fvis = A.take(F);
       }
+      if (!ck.rep.empty()) { dsa::EncRepairRows &R = ck.rep_rows[rr++]; R.e2v = C->e2v; R.pd_e2v = want_pd ? C->pd_e2v : 0; }      // (pushed above in this order)
       if (ck.valence_of(i)) {
         C->init_time = A.take(4 * F); C->vtime = A.take(4 * F); C->vval = A.take(4 * (V + F)); C->vc2v = A.take(12 * F);
         C->vctx = A.take(F); C->vsyms = A.take(4 * F); C->vbl = A.take(F); C->vrans = A.take(4 * F + 96); C->vbits = A.take(4 * F + 96);
@@ -521,7 +558,7 @@ static void enc_layout(EncChunk &ck) {
       enc_value_stream_regions(S, cap, ck.hist_cap_of(i, k), A);
       L.max_rows = std::max(L.max_rows, std::max(S.rows, cap));
       if (!enc_topo_scheme(a)) continue;
-      if (C) { S.t_c2p = S.t_c2a = C->faces; S.t_opp = C->opp; S.t_d2c = pd ? C->pd_d2c : C->d2c; S.t_v2d = pd ? C->pd_v2d : C->v2d; }      // the connectivity's own
+      if (C) { const uint64_t c2row = S.t_c2p; S.t_c2p = S.t_c2a = C->faces; S.t_opp = C->opp; S.t_d2c = pd ? C->pd_d2c : C->d2c; S.t_v2d = pd ? C->pd_v2d : C->v2d; if (!ck.rep.empty()) S.t_c2p = c2row; }      // the connectivity's own (a repaired table: positions by row)
       S.t_nc3 = 3u * (uint32_t)F;
       if (!enc_multi_scheme(a)) {
         S.pos_vals = L.streams[s0].vals;                      // (the positions are attribute 0: their stream is the mesh's first)

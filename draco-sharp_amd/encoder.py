@@ -32,7 +32,12 @@ class Config:
     MultiParallelogram, in place of Parallelogram (positions and the first UV set; with 4 and parallelogram positions also the
     generic attribute and the attribute list), -1 the reference's rule per mesh (4 at speed < 2 for meshes of 40 points or more);
     traversal_method 1 sequences the positions' decoder (every decoder under single_connectivity) in prediction-degree order, 2
-    every decoder without interior seams.  Sequential configs and point clouds refuse both: they predict by Difference in point order."""
+    every decoder without interior seams.  Sequential configs and point clouds refuse both: they predict by Difference in point order.
+
+    repair_topology (dsa_encode_repair_batch, topology 1): meshes with degenerate faces, the same face twice, fins, faces turned
+    over, fans that meet at a vertex or vertices no face uses are coded on the reference's repaired corner table (CornerTable.cs:
+    28-43) instead of being refused; clean meshes give the same bytes.  Edgebreaker streams only; attributes given per corner over
+    a mesh that needs the repair are not implemented."""
 
     EDGEBREAKER_METHODS = (0, 2, -1)
     POSITION_PREDICTIONS = (0, 1)
@@ -44,7 +49,7 @@ class Config:
 
     def __init__(self, position_bits=11, texcoord_bits=10, normal_bits=8, speed=5, single_connectivity=False,
                  symbol_scheme=-1, position_prediction=1, texcoord_prediction=1, edgebreaker_method=0, normal_prediction=0,
-                 encoding_method=1, compress_connectivity=False, multi_parallelogram=0, traversal_method=0):
+                 encoding_method=1, compress_connectivity=False, multi_parallelogram=0, traversal_method=0, repair_topology=False):
         for name, value, legal in (("encoding_method", encoding_method, self.ENCODING_METHODS),
                                    ("edgebreaker_method", edgebreaker_method, self.EDGEBREAKER_METHODS),
                                    ("position_prediction", position_prediction, self.POSITION_PREDICTIONS),
@@ -62,6 +67,9 @@ class Config:
         self.edgebreaker_method, self.normal_prediction = edgebreaker_method, normal_prediction
         self.encoding_method, self.compress_connectivity = encoding_method, bool(compress_connectivity)
         self.multi_parallelogram, self.traversal_method = multi_parallelogram, traversal_method
+        self.repair_topology = bool(repair_topology)
+        if self.repair_topology and self.sequential:
+            raise ValueError("repair_topology shapes Edgebreaker streams: a sequential stream takes any list of triangles as it is")
         if self.leveled and self.sequential:
             raise ValueError("multi_parallelogram / traversal_method shape Edgebreaker streams: a sequential stream predicts by Difference in point order")
 
@@ -87,6 +95,13 @@ class Config:
     def leveled(self):
         """True when an option only dsa_encode_level_batch takes is set."""
         return self.multi_parallelogram != 0 or self.traversal_method != 0
+
+    def _native_repair(self):
+        o = native.EncodeRepairOptions()
+        native.lib().dsa_encode_default_repair_options(C.byref(o))
+        o.level = self._native_level()
+        o.topology = 1 if self.repair_topology else 0
+        return o
 
     def _native_level(self):
         o = native.EncodeLevelOptions()
@@ -320,7 +335,8 @@ class DracoEncoder:
         ex = config.extended
         # the attribute-list entry point only when some mesh has a list; the corner entry point only when some mesh carries ids (or
         # an option needs dsa_encode_batch_ex, which takes the corner form); otherwise exactly the per-vertex call
-        level = config.leveled      # dsa_encode_level_batch takes the widest input: always dsa_mesh_attr_input, an empty list is legal
+        repair = getattr(config, "repair_topology", False)      # dsa_encode_repair_batch: the level call's input and options, and the topology switch
+        level = config.leveled or repair      # dsa_encode_level_batch takes the widest input: always dsa_mesh_attr_input, an empty list is legal
         listed = level or any(getattr(m, "attributes", None) for m in meshes)
         corners = listed or ex or any(getattr(m, "per_corner", False) for m in meshes)
         arr = ((native.MeshAttrInput if listed else (native.MeshCornerInput if corners else native.MeshInput)) * max(1, n))()
@@ -343,10 +359,10 @@ class DracoEncoder:
                 ci.texcoord_corners = uci.ctypes.data if uci is not None else None
                 ci.num_normals = len(m.normals) if m.normals is not None else 0
                 ci.num_texcoords = len(m.texcoords) if m.texcoords is not None else 0
-        opt = config._native_level() if level else (config._native_ex() if (ex or listed) else config._native())
+        opt = config._native_repair() if repair else config._native_level() if level else (config._native_ex() if (ex or listed) else config._native())
         h = C.c_void_p()
         t0 = time.perf_counter()
-        entry = L.dsa_encode_level_batch if level else L.dsa_encode_attributes_batch if listed else (L.dsa_encode_batch_ex if ex else (L.dsa_encode_batch_corners if corners else L.dsa_encode_batch))
+        entry = L.dsa_encode_repair_batch if repair else L.dsa_encode_level_batch if level else L.dsa_encode_attributes_batch if listed else (L.dsa_encode_batch_ex if ex else (L.dsa_encode_batch_corners if corners else L.dsa_encode_batch))
         st = entry(ctx._h, n, arr, C.byref(opt), C.byref(h))
         t1 = time.perf_counter()
         if st != 0:

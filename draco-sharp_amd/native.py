@@ -32,6 +32,7 @@ EXPORTS = [
     "dsa_encode_default_options_ex", "dsa_encode_batch_ex", "dsa_encode_sequential_default_options", "dsa_encode_sequential_batch",
     "dsa_encode_attributes_batch", "dsa_encode_attributes_sequential_batch",
     "dsa_encode_default_level_options", "dsa_encode_level_batch",
+    "dsa_encode_default_repair_options", "dsa_encode_repair_batch",
     "dsa_encoded_size", "dsa_encoded_stream", "dsa_encoded_free",
     "dsa_pool_create", "dsa_pool_destroy", "dsa_pool_size", "dsa_pool_last_error", "dsa_pool_decode", "dsa_pool_job_locate",
     "dsa_pool_job_chunks", "dsa_pool_job_free", "dsa_pool_plan",
@@ -57,6 +58,12 @@ class EncodeLevelOptions(C.Structure):
     dsa_encode_attributes_batch."""
     _fields_ = [("ex", EncodeOptionsEx), ("multi_parallelogram", C.c_int32), ("traversal_method", C.c_int32),
                 ("reserved", C.c_int32 * 6)]
+
+
+class EncodeRepairOptions(C.Structure):
+    """dsa_encode_repair_options: topology (0 strict, 1 the reference's corner table: degenerate faces, non-manifold edges and
+    vertices and isolated vertices are repaired, not refused) beside the options of dsa_encode_level_batch."""
+    _fields_ = [("level", EncodeLevelOptions), ("topology", C.c_int32), ("reserved", C.c_int32 * 7)]
 
 
 class EncodeSequentialOptions(C.Structure):
@@ -219,6 +226,10 @@ def lib():
         L.dsa_encode_default_level_options.argtypes = [C.POINTER(EncodeLevelOptions)]
         L.dsa_encode_default_level_options.restype = None
         L.dsa_encode_level_batch.argtypes = [vp, u32, C.POINTER(MeshAttrInput), C.POINTER(EncodeLevelOptions), C.POINTER(vp)]
+        if hasattr(L, "dsa_encode_repair_batch"):      # (DSA_LIB may name an older build for a same-box A/B; build() checks EXPORTS on the tree's own)
+            L.dsa_encode_default_repair_options.argtypes = [C.POINTER(EncodeRepairOptions)]
+            L.dsa_encode_default_repair_options.restype = None
+            L.dsa_encode_repair_batch.argtypes = [vp, u32, C.POINTER(MeshAttrInput), C.POINTER(EncodeRepairOptions), C.POINTER(vp)]
         L.dsa_encoded_size.restype = u32
         L.dsa_encoded_size.argtypes = [vp]
         L.dsa_encoded_stream.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(C.c_size_t)]

@@ -19,7 +19,7 @@ class Options(C.Structure):
                 ("compression_level", C.c_int32), ("pos_prediction", C.c_int32), ("uv_prediction", C.c_int32),
                 ("normal_prediction", C.c_int32), ("traversal_method", C.c_int32), ("predictive_connectivity", C.c_int32),
                 ("normal_transform", C.c_int32), ("raw_integers", C.c_int32), ("no_prediction", C.c_int32),
-                ("generic_components", C.c_int32), ("generic_data_type", C.c_int32)]
+                ("generic_components", C.c_int32), ("generic_data_type", C.c_int32), ("repair_topology", C.c_int32)]
 
 
 # element types of the generic attribute (CPU coder only): numpy dtype -> Draco's data type id

@@ -116,7 +116,7 @@ extern "C" {
 
 struct synth_options {
   int32_t pos_bits, uv_bits, normal_bits, single_connectivity, force_scheme, compression_level, pos_prediction, uv_prediction, normal_prediction, traversal_method, predictive_connectivity,
-      normal_transform, raw_integers, no_prediction, generic_components, generic_data_type;
+      normal_transform, raw_integers, no_prediction, generic_components, generic_data_type, repair_topology;
 };
 
 static thread_local char g_err[256];
@@ -131,6 +131,7 @@ static synth::Options to_opt(const synth_options *o) {
     r.normal_prediction = o->normal_prediction; r.traversal_method = o->traversal_method;
     r.predictive_connectivity = o->predictive_connectivity;
     r.normal_transform = o->normal_transform; r.raw_integers = o->raw_integers; r.no_prediction = o->no_prediction; r.generic_components = o->generic_components; r.generic_data_type = o->generic_data_type;
+    r.repair_topology = o->repair_topology;
   }
   return r;
 }
@@ -141,6 +142,7 @@ void synth_default_options(synth_options *o) {
   o->normal_prediction = d.normal_prediction; o->traversal_method = d.traversal_method;
   o->predictive_connectivity = d.predictive_connectivity;
   o->normal_transform = d.normal_transform; o->raw_integers = d.raw_integers; o->no_prediction = d.no_prediction; o->generic_components = d.generic_components; o->generic_data_type = d.generic_data_type;
+  o->repair_topology = d.repair_topology;
 }
 
 // Encodes one mesh.  normals/uvs/generic may be NULL.  *out is malloc'ed; free with synth_free.
@@ -148,6 +150,7 @@ int synth_encode_mesh(const float *pos, uint32_t nv, const uint32_t *faces, uint
                       const float *uvs, const void *generic, const synth_options *opt, uint8_t **out, size_t *out_len) {
   try {
     synth::MeshIn in{pos, nv, faces, nf, normals, uvs, generic};
+    if (opt && opt->repair_topology) for (size_t k = 0; k < (size_t)nf * 3; ++k) synth::check(faces[k] < nv, "face index out of range");
     std::vector<uint8_t> buf;
     synth::encode_mesh(in, to_opt(opt), buf);
     *out = (uint8_t *)malloc(buf.size());

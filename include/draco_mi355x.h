@@ -459,6 +459,38 @@ typedef struct dsa_encode_level_options {
 void dsa_encode_default_level_options(dsa_encode_level_options *options);
 dsa_status dsa_encode_level_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes,
                                   const dsa_encode_level_options *options, dsa_encoded **out);
+/* dsa_encode_level_batch for meshes that are not clean: the same face twice, fins, fans that meet at a vertex, faces turned
+ * over, faces with a repeated index, vertices no face uses -- what every other Edgebreaker call refuses mesh by mesh ("degenerate
+ * face", "non-manifold edge (duplicate half-edge)", "non-manifold vertex", "isolated vertex").
+ *   topology   0 strict: the bytes and the failures of dsa_encode_level_batch.
+ *              1 the reference's corner table, CornerTable(faces) (IO/Mesh/CornerTable.cs:28-43), over the position indices:
+ *       degenerate faces (two equal indices) take no part; corners are matched in index order, corner c facing a -> b with the
+ *       earliest still-pending b -> a of a face with another tip (the scan over the whole pending list: :346-371 as written
+ *       only looks at its first entry); BreakNonManifoldEdges (:396-469) cuts the edges of a fan that reach one vertex twice;
+ *       ComputeVertexCorners (:471-547) gives every fan of a vertex behind the first -- faces in index order -- a new vertex with
+ *       that vertex as its parent.  The stream codes V' - isolated points and F - degenerate faces
+ *       (MeshEdgeBreakerEncoder.cs:41-47); every attribute writes, for a vertex with a parent, the parent's row; quantisation
+ *       bounds are taken over all num_vertices rows passed, isolated ones included (AttributeQuantizationTransform.cs:66-100).
+ *       Everything else -- holes, start faces, symbols, split events, attribute orders, valence contexts, every prediction
+ *       scheme -- runs on the repaired table unchanged.
+ * A clean mesh gives the bytes of dsa_encode_level_batch with options.level, whatever `topology` is: the call codes the batch
+ * as that call does, and codes again, on the repaired table, only the meshes refused for one of the reasons above (repair
+ * kernels of their own, dsa_encode_repair.h; with host connectivity -- DSA_ENC_HOST_CONN, batches below 256 meshes -- the host
+ * coder's table).  Per mesh with topology = 1: every face degenerate or num_faces = 0 fails with DSA_ERR_INVALID_DATA ("all
+ * triangles are degenerate"); an index out of range, missing positions and the attribute-list checks fail as they do today; a
+ * mesh with normal_corners / texcoord_corners whose position table needs repair fails alone with DSA_ERR_NOT_IMPLEMENTED (seam
+ * tables over a repaired table are not written yet; with clean topology it is coded as by dsa_encode_level_batch).  topology
+ * outside {0, 1} or a non-zero reserved word fails the call with DSA_ERR_INVALID_ARGUMENT and dsa_last_error names the field.
+ * The streams are byte-identical to the CPU coder's with repair_topology = 1.  Added after ABI 4 without changing it: callers
+ * detect the feature by the symbol dsa_encode_repair_batch. */
+typedef struct dsa_encode_repair_options {
+  dsa_encode_level_options level;   /* as for dsa_encode_level_batch, same legal values */
+  int32_t topology;                 /* 0 strict (default), 1 the reference's corner table */
+  int32_t reserved[7];              /* must be zero */
+} dsa_encode_repair_options;
+void dsa_encode_default_repair_options(dsa_encode_repair_options *options);
+dsa_status dsa_encode_repair_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes,
+                                   const dsa_encode_repair_options *options, dsa_encoded **out);
 uint32_t dsa_encoded_size(const dsa_encoded *encoded);
 /* Bytes of stream `mesh` (owned by `encoded`, valid until dsa_encoded_free) or that mesh's failure status. */
 dsa_status dsa_encoded_stream(const dsa_encoded *encoded, uint32_t mesh, const uint8_t **bytes, size_t *length);
