@@ -39,6 +39,12 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
     /// instead of refusing it.</summary>
     public bool RepairTopology { get; set; }
 
+    /// <summary>Hand every mesh over as one row per point (the value of each attribute at the point, faces over points) and let the
+    /// library weld the points into vertices (dsa_encode_points_batch): points with byte-equal positions, generic and extra rows
+    /// are one vertex, normals and texture coordinates become corner attributes where a vertex has two of them.  For meshes whose
+    /// point-to-value maps were never deduplicated (a glTF primitive or an OBJ loaded row by row).  Unset: nothing changes.</summary>
+    public bool WeldPoints { get; set; }
+
     public GpuDracoEncoder(int device = 0)
     {
         NativeMethods.Check(NativeMethods.dsa_context_create(device, IntPtr.Zero, out _ctx), IntPtr.Zero, "dsa_context_create");
@@ -155,6 +161,37 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
         IntPtr encoded = IntPtr.Zero;
         try
         {
+            if (WeldPoints)
+            {
+                var pin = new DsaMeshAttrInput[meshes.Count];
+                for (int i = 0; i < meshes.Count; ++i)
+                {
+                    var m = meshes[i];
+                    ref DsaMeshInput mi = ref pin[i].Mesh.Mesh;
+                    mi.NumVertices = (uint)m.PointsCount;
+                    mi.NumFaces = (uint)m.FacesCount;
+                    mi.Positions = (float*)Pin(Floats(m, GeometryAttributeType.Position, 3), pins);
+                    mi.Normals = (float*)Pin(Floats(m, GeometryAttributeType.Normal, 3), pins);
+                    mi.Texcoords = (float*)Pin(Floats(m, GeometryAttributeType.TexCoord, 2), pins);
+                    var generic = Bytes(m, GeometryAttributeType.Generic, out uint genericComponents);
+                    mi.Generic = (byte*)Pin(generic, pins);
+                    mi.GenericComponents = generic == null ? 0 : genericComponents;
+                    var faces = new uint[m.FacesCount * 3];
+                    for (int f = 0; f < m.FacesCount; ++f) { var face = m.GetFace((uint)f); faces[3 * f] = (uint)face[0]; faces[3 * f + 1] = (uint)face[1]; faces[3 * f + 2] = (uint)face[2]; }
+                    mi.Faces = (uint*)Pin(faces, pins);
+                    Extras(m, null, (uint)m.PointsCount, ref pin[i], pins);      // (one row per point, as for a sequential stream)
+                }
+                NativeMethods.dsa_encode_default_repair_options(out var wp);
+                wp.Level.Ex.Base = opt;
+                wp.Level.Ex.EdgebreakerMethod = ebMethod != unset ? ebMethod : 0;
+                wp.Level.Ex.NormalPrediction = normalScheme != unset ? normalScheme : 0;
+                wp.Level.MultiParallelogram = multi;
+                wp.Level.TraversalMethod = traversal;
+                wp.Topology = RepairTopology ? 1 : 0;
+                fixed (DsaMeshAttrInput* p = pin)
+                    NativeMethods.Check(NativeMethods.dsa_encode_points_batch(_ctx, (uint)meshes.Count, p, in wp, out encoded), _ctx, "dsa_encode_points_batch");
+                return Streams(encoded, meshes.Count);
+            }
             bool anyCorners = false, anyExtras = false;
             foreach (var m in meshes) { anyCorners = anyCorners || NeedsCornerForm(m); anyExtras = anyExtras || ExtraAttributes(m).Count > 0; }
             if (anyExtras || multi != 0 || traversal != 0 || RepairTopology)

@@ -125,6 +125,19 @@ internal unsafe struct DsaEncodeLevelOptions
     public fixed int Reserved[6];   // zero
 }
 
+// dsa_welded_info (dsa_weld_batch): the weld of one mesh given as one row per point; the maps live in the handle (80 bytes)
+[StructLayout(LayoutKind.Sequential)]
+internal unsafe struct DsaWeldedInfo
+{
+    public int Status;
+    public uint NumPoints, NumVertices, NumNormals, NumTexcoords;
+    public uint NormalsPerVertex, TexcoordsPerVertex;
+    public uint Reserved;           // zero
+    public uint* VertexOfPoint, VertexPoint;
+    public uint* NormalOfPoint, NormalPoint;
+    public uint* TexcoordOfPoint, TexcoordPoint;
+}
+
 // dsa_encode_repair_options (dsa_encode_repair_batch): the reference's corner table for meshes that are not clean (128 bytes)
 [StructLayout(LayoutKind.Sequential)]
 internal unsafe struct DsaEncodeRepairOptions
@@ -253,6 +266,12 @@ internal static unsafe partial class NativeMethods
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_level_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, in DsaEncodeLevelOptions options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern void dsa_encode_default_repair_options(out DsaEncodeRepairOptions options);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_repair_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, in DsaEncodeRepairOptions options, out IntPtr encoded);
+    // meshes given as one row per point: the weld in front of dsa_encode_repair_batch, and the weld alone (detect by symbol)
+    [DllImport(Lib)] internal static extern DsaStatus dsa_encode_points_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, in DsaEncodeRepairOptions options, out IntPtr encoded);
+    [DllImport(Lib)] internal static extern DsaStatus dsa_weld_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, out IntPtr welded);
+    [DllImport(Lib)] internal static extern uint dsa_welded_size(IntPtr welded);
+    [DllImport(Lib)] internal static extern DsaStatus dsa_welded_mesh(IntPtr welded, uint mesh, out DsaWeldedInfo info);
+    [DllImport(Lib)] internal static extern void dsa_welded_free(IntPtr welded);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_attributes_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, in DsaEncodeOptionsEx options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_attributes_sequential_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, in DsaEncodeSequentialOptions options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern uint dsa_encoded_size(IntPtr encoded);

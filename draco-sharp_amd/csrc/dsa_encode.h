@@ -754,13 +754,120 @@ static dsa_status enc_check_bits(dsa_context *ctx, const dsa_encode_options &o) 
 static bool enc_host_choice(const char *name, uint32_t batch_n) { const char *e = getenv(name); return e ? atoi(e) != 0 : batch_n < 256; }
 
 // ---- the stages of encode_chunk, in their order
+// a weld request (dsa_encode_points_batch, dsa_weld_batch): the meshes arrive as one row per point; the weld of every mesh
+// (dsa_encode_weld.h; DSA_ENC_HOST_WELD, batches below 256 meshes: synth::weld_points on the host threads) into buffers the chunk
+// owns, and the chunk's mesh view pointed at them -- everything behind runs on the welded meshes as if the caller had passed them.
+// Device path: memory of its own per lane, the point arrays up on a turn of the link, the kernels, then counts, maps and welded
+// rows back (the welded rows cross the link again with the ordinary uploads: the layout reads host memory).
+static dsa_status enc_stage_weld(dsa_context *ctx, EncLane &lane, hostutil::TurnGuard &turn, EncChunk &ck) {
+  if (!ck.rq.weld) return DSA_OK;
+  const uint32_t n = ck.n;
+  ck.weld.assign(n, synth::Welded());
+  ck.weld_attrs.assign(n, {});
+  std::vector<std::vector<synth::WeldSeg>> keys(n);
+  hostutil::parallel_for(n, [&](uint32_t i) { enc_weld_check(ck, i, keys[i]); });
+  const bool on_host = enc_host_choice("DSA_ENC_HOST_WELD", ck.batch_n);
+  std::vector<dsa::EncWeld> recs;
+  std::vector<uint32_t> mesh_of;
+  std::vector<EncUpload> ups;
+  EncArena A;
+  uint32_t most = 1;
+  for (uint32_t i = 0; i < n && !on_host; ++i) {
+    if (!ck.good(i)) continue;
+    const dsa_mesh_input &m = ck.rq.listed[ck.base + i].mesh.mesh;
+    if (m.num_vertices > (1u << 28) || m.num_faces > (1u << 28)) { ck.refuse(i, DSA_ERR_INVALID_DATA, "mesh too large for the device weld"); continue; }
+    uint32_t row_bytes[dsa::EW_MAX_SEGS];
+    if (keys[i].size() + 2 > dsa::EW_MAX_SEGS) { ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, "too many attributes for the device weld"); continue; }
+    for (size_t g = 0; g < keys[i].size(); ++g) row_bytes[g] = keys[i][g].row_bytes;
+    dsa::EncWeld W = dsa::enc_weld_inputs([&](uint64_t bytes) { return A.take(bytes); }, m.num_vertices, m.num_faces, row_bytes, (uint32_t)keys[i].size(), m.normals != nullptr, m.texcoords != nullptr);
+    if (m.num_faces) ups.push_back({W.faces, m.faces, 12ull * m.num_faces, false});
+    for (size_t g = 0; g < keys[i].size() && m.num_vertices; ++g) ups.push_back({W.seg[g].src, keys[i][g].rows, (size_t)m.num_vertices * keys[i][g].row_bytes, false});
+    if (m.normals && m.num_vertices) ups.push_back({W.seg[W.set[1].first_seg].src, m.normals, 12ull * m.num_vertices, false});
+    if (m.texcoords && m.num_vertices) ups.push_back({W.seg[W.set[2].first_seg].src, m.texcoords, 8ull * m.num_vertices, false});
+    recs.push_back(W); mesh_of.push_back(i);
+    most = std::max(most, std::max(m.num_vertices, 3u * m.num_faces));
+  }
+  const uint64_t input_bytes = A.cur;                      // the uploads fill [0, input_bytes); the kernels' regions lie behind
+  for (dsa::EncWeld &W : recs) dsa::enc_weld_regions([&](uint64_t bytes) { return A.take(bytes); }, W);
+  if (on_host) {
+    hostutil::parallel_for(n, [&](uint32_t i) {
+      if (!ck.good(i)) return;
+      const dsa_mesh_input &m = ck.rq.listed[ck.base + i].mesh.mesh;
+      try { synth::weld_points(m.num_vertices, m.faces, m.num_faces, keys[i], m.normals, m.texcoords, ck.weld[i]); }
+      catch (const std::exception &e) { ck.refuse(i, DSA_ERR_INVALID_DATA, e.what()); }
+    });
+  } else if (!recs.empty()) {
+    const uint32_t nr = (uint32_t)recs.size();
+    // (ups is in arena order; a piece of enc_upload copies a whole stretch of the arena from pinned staging, gaps included: that
+    // is why no region a kernel expects at zero may lie among the inputs)
+    hipStream_t st = lane.st;
+    ENC_TRY(lane.weld.ensure(A.cur ? A.cur : 256));
+    ENC_TRY(lane.weld_recs.ensure(sizeof(dsa::EncWeld) * nr));
+    uint8_t *arena = (uint8_t *)lane.weld.p;
+    dsa::EncWeld *d_recs = (dsa::EncWeld *)lane.weld_recs.p;
+    if (A.cur > input_bytes) ENC_TRY(hipMemsetAsync(arena + input_bytes, 0, A.cur - input_bytes, st));
+    turn.acquire_free();
+    ENC_TRY(enc_upload(lane, arena, st, ups));
+    turn.release();
+    ENC_TRY(hipMemcpyAsync(d_recs, recs.data(), sizeof(dsa::EncWeld) * nr, hipMemcpyHostToDevice, st));
+    const uint32_t gx = std::max(1u, std::min(128u, (most + 1023u) / 1024u));
+    hipLaunchKernelGGL(dsa::k_enc_weld_mark, dim3(gx, nr), dim3(256), 0, st, arena, d_recs, nr);
+    hipLaunchKernelGGL(dsa::k_enc_weld_insert, dim3(gx, 3 * nr), dim3(256), 0, st, arena, d_recs, nr);
+    hipLaunchKernelGGL(dsa::k_enc_weld_scan, dim3(3 * nr), dim3(WAVE), 0, st, arena, d_recs, nr);
+    hipLaunchKernelGGL(dsa::k_enc_weld_assign, dim3(gx, 3 * nr), dim3(256), 0, st, arena, d_recs, nr);
+    hipLaunchKernelGGL(dsa::k_enc_weld_differs, dim3(gx, 2 * nr), dim3(256), 0, st, arena, d_recs, nr);
+    hipLaunchKernelGGL(dsa::k_enc_weld_gather, dim3(gx, nr), dim3(256), 0, st, arena, d_recs, nr);
+    ENC_TRY(hipGetLastError());
+    ENC_TRY(hipMemcpyAsync(recs.data(), d_recs, sizeof(dsa::EncWeld) * nr, hipMemcpyDeviceToHost, st));
+    ENC_TRY(hipStreamSynchronize(st));
+    // counts known: the maps, the faces and ids, the welded rows in one transfer
+    struct Dest { void *p; };
+    std::vector<dsa::PackItem> items;
+    std::vector<Dest> dest;
+    auto want32 = [&](std::vector<uint32_t> &v, uint64_t at, uint64_t count) { v.resize(count); if (count) { items.push_back({at, 0, (uint32_t)(4 * count), 0}); dest.push_back({v.data()}); } };
+    auto want8 = [&](std::vector<uint8_t> &v, uint64_t at, uint64_t bytes) { v.resize(bytes); if (bytes) { items.push_back({at, 0, (uint32_t)bytes, 0}); dest.push_back({v.data()}); } };
+    for (uint32_t r = 0; r < nr; ++r) {
+      const uint32_t i = mesh_of[r];
+      const dsa::EncWeld &W = recs[r];
+      if (W.status != dsa::ENC_WELD_OK || W.set[0].count > W.P || W.set[1].count > W.P || W.set[2].count > W.P) { ck.refuse(i, DSA_ERR_INVALID_DATA, dsa::enc_weld_message(W.status)); continue; }
+      synth::Welded &w = ck.weld[i];
+      w.P = W.P; w.F = W.F;
+      synth::WeldKeys *sets[3] = {&w.vertex, &w.normal, &w.texcoord};
+      for (uint32_t k = 0; k < 3; ++k) {
+        if (W.set[k].num_segs == 0) continue;
+        sets[k]->count = W.set[k].count;
+        want32(sets[k]->of_point, W.set[k].of, W.P);
+        want32(sets[k]->point, W.set[k].point, W.set[k].count);
+      }
+      const uint32_t V = W.set[0].count;
+      want32(w.faces, W.faces_out, 3ull * W.F);
+      w.vertex_rows.resize(W.set[0].num_segs);
+      for (uint32_t g = 0; g < W.set[0].num_segs; ++g) want8(w.vertex_rows[g], W.seg[g].dst, (uint64_t)V * W.seg[g].row_bytes);
+      w.normals_per_vertex = W.differs[0] == 0; w.texcoords_per_vertex = W.differs[1] == 0;
+      if (W.set[1].num_segs) {
+        want8(w.normal_rows, W.seg[W.set[1].first_seg].dst, 12ull * (W.differs[0] ? W.set[1].count : V));
+        if (W.differs[0]) want32(w.normal_corners, W.corners_out[0], 3ull * W.F);
+      }
+      if (W.set[2].num_segs) {
+        want8(w.texcoord_rows, W.seg[W.set[2].first_seg].dst, 8ull * (W.differs[1] ? W.set[2].count : V));
+        if (W.differs[1]) want32(w.texcoord_corners, W.corners_out[1], 3ull * W.F);
+      }
+    }
+    const uint8_t *host = nullptr;
+    ENC_ST(enc_gather(lane, arena, items, nullptr, &host));
+    hostutil::parallel_for((uint32_t)items.size(), [&](uint32_t k) { memcpy(dest[k].p, host + items[k].packed_off, items[k].len); }, 8);
+  }
+  ck.welded.resize(n);
+  for (uint32_t i = 0; i < n; ++i) enc_weld_view(ck, i);
+  return DSA_OK;
+}
 // host phase 1: checks, connectivity, traversal order, operand entries (threads over meshes)
 static dsa_status enc_stage_plans(dsa_context *ctx, EncChunk &ck) {
   // (the quantisation bits of an Edgebreaker call are checked here, per chunk: a call with n = 0 has no chunk and returns DSA_OK
   // whatever they are, while a sequential call checks them up front -- enc_check_request)
   if (enc_check_bits(ctx, ck.rq.base()) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
   enc_begin_plans(ck, enc_host_choice("DSA_ENC_HOST_CONN", ck.batch_n), enc_host_choice("DSA_ENC_HOST_PLAN", ck.batch_n));
-  hostutil::parallel_for(ck.n, [&](uint32_t i) { enc_plan_mesh(ck, i); });          // capped thread count, every thread joined on every path (dsa_host_util.h)
+  hostutil::parallel_for(ck.n, [&](uint32_t i) { if (ck.good(i)) enc_plan_mesh(ck, i); });          // (a mesh the weld refused stays refused) capped thread count, every thread joined on every path (dsa_host_util.h)
   return DSA_OK;
 }
 // a repair request on the device path (dsa_encode_repair.h): the repaired corner table of every mesh by the repair kernels, in
@@ -1079,6 +1186,8 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, const EncRequest
   if (!ck.E) return set_err(ctx, DSA_ERR_OUT_OF_MEMORY, "host allocation failed");
   ck.E->ctx = ctx;
   EncLap lap{&lane};
+  ENC_STAGE(enc_stage_weld(ctx, lane, turn, ck));
+  if (ck.rq.weld) lap("weld");
   ENC_STAGE(enc_stage_plans(ctx, ck));
   lap("host checks / plan");
   ENC_STAGE(enc_stage_repair(ctx, lane, ck));
@@ -1097,6 +1206,19 @@ static dsa_status encode_chunk(dsa_context *ctx, EncLane &lane, const EncRequest
   lap("device phase 2 + downloads");
   enc_stage_streams(ck);
   lap("stream layout");
+  *out = ck.E.release();
+  return DSA_OK;
+}
+
+// dsa_weld_batch: the weld stage alone; the weld of every mesh into the request's sink, the statuses into the chunk's result
+static dsa_status weld_chunk(dsa_context *ctx, EncLane &lane, const EncRequest &rq, uint32_t base, uint32_t count, uint32_t batch_n, dsa_encoded **out) {
+  hostutil::TurnGuard turn(lane.upload_turn, lane.upload_chunk);
+  HIP_TRY(ctx, hipSetDevice(lane.device));
+  EncChunk ck(rq, base, count, batch_n);
+  if (!ck.E) return set_err(ctx, DSA_ERR_OUT_OF_MEMORY, "host allocation failed");
+  ck.E->ctx = ctx;
+  ENC_STAGE(enc_stage_weld(ctx, lane, turn, ck));
+  for (uint32_t i = 0; i < count; ++i) if (ck.good(i)) std::swap((*rq.weld_sink)[base + i], ck.weld[i]);
   *out = ck.E.release();
   return DSA_OK;
 }
@@ -1266,6 +1388,7 @@ static dsa_status encode_request(dsa_context *ctx, const EncRequest &rq, dsa_enc
   if (enc_check_request(ctx, rq) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
   if (batch_n == 0) batch_n = rq.n;
   DSA_GUARD(ctx, encode_batch_chunks(ctx, rq.n, [&](dsa_context *sink, EncLane &lane, uint32_t base, uint32_t cnt, dsa_encoded **part) {      // host vectors and threads inside: nothing may unwind into the caller
+    if (rq.weld_sink) return weld_chunk(sink, lane, rq, base, cnt, batch_n, part);
     return rq.sequential ? encode_sequential_chunk(sink, lane, rq, base, cnt, rq.n, part) : encode_chunk(sink, lane, rq, base, cnt, batch_n, part);
   }, out));
 }
@@ -1360,6 +1483,75 @@ dsa_status dsa_encode_repair_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_
   }
   return topology == 1 ? encode_repair_request(ctx, rq, out) : encode_request(ctx, rq, out);
 }
+static dsa_status enc_repair_options_into(dsa_context *ctx, const dsa_encode_repair_options *options, EncRequest &rq, int32_t &topology) {
+  topology = 0;
+  if (!options) return DSA_OK;
+  if (options->topology != 0 && options->topology != 1)
+    return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "topology %d: 0 (strict) or 1 (the reference's corner table)", (int)options->topology);
+  for (int k = 0; k < 7; ++k)
+    if (options->reserved[k] != 0) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "dsa_encode_repair_options.reserved[%d] is not zero", k);
+  rq.level = options->level;
+  topology = options->topology;
+  return DSA_OK;
+}
+// dsa_encode_repair_batch for meshes given as one row per point: every chunk welds its meshes first (enc_stage_weld), the welded
+// meshes are coded as that call codes them.  With topology = 1 the meshes refused for their topology are welded again in the
+// second pass: they are the few, and the weld is cheap beside keeping every chunk's buffers alive.
+static dsa_status encode_points_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_encode_repair_options *options, dsa_encoded **out) {
+  EncRequest rq = enc_request(n, false);
+  rq.listed = meshes;
+  rq.weld = true;
+  int32_t topology = 0;
+  if (enc_repair_options_into(ctx, options, rq, topology) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+  return topology == 1 ? encode_repair_request(ctx, rq, out) : encode_request(ctx, rq, out);
+}
+dsa_status dsa_encode_points_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_encode_repair_options *options, dsa_encoded **out) {
+  DSA_GUARD(ctx, encode_points_batch(ctx, n, meshes, options, out));
+}
+struct dsa_welded {
+  dsa_context *ctx = nullptr;
+  std::vector<synth::Welded> meshes;
+  std::vector<int32_t> status;
+  std::vector<std::string> messages;
+};
+static dsa_status weld_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, dsa_welded **out) {
+  if (!ctx || !out || (n && !meshes)) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "null argument");
+  *out = nullptr;
+  std::unique_ptr<dsa_welded> W(new dsa_welded());
+  W->meshes.resize(n);
+  EncRequest rq = enc_request(n, false);
+  rq.listed = meshes;
+  rq.weld = true;
+  rq.weld_sink = &W->meshes;
+  dsa_encoded *E = nullptr;
+  const dsa_status st = encode_request(ctx, rq, &E);
+  if (st != DSA_OK) return st;
+  std::unique_ptr<dsa_encoded> owner(E);
+  W->ctx = ctx;
+  W->status.swap(E->status); W->messages.swap(E->messages);
+  *out = W.release();
+  return DSA_OK;
+}
+dsa_status dsa_weld_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, dsa_welded **out) {
+  DSA_GUARD(ctx, weld_batch(ctx, n, meshes, out));
+}
+uint32_t dsa_welded_size(const dsa_welded *w) { return w ? (uint32_t)w->meshes.size() : 0; }
+dsa_status dsa_welded_mesh(const dsa_welded *w, uint32_t mesh, dsa_welded_info *info) {
+  if (!w || !info || mesh >= w->meshes.size()) return DSA_ERR_INVALID_ARGUMENT;
+  memset(info, 0, sizeof(*info));
+  info->status = w->status[mesh];
+  if (w->status[mesh] != DSA_OK) return set_err(w->ctx, (dsa_status)w->status[mesh], "mesh %u: %s", mesh, w->messages[mesh].c_str());
+  const synth::Welded &m = w->meshes[mesh];
+  info->num_points = m.P; info->num_vertices = m.vertex.count; info->num_normals = m.normal.count; info->num_texcoords = m.texcoord.count;
+  info->normals_per_vertex = m.normals_per_vertex ? 1 : 0; info->texcoords_per_vertex = m.texcoords_per_vertex ? 1 : 0;
+  auto data = [](const std::vector<uint32_t> &v) { return v.empty() ? nullptr : v.data(); };
+  info->vertex_of_point = data(m.vertex.of_point); info->vertex_point = data(m.vertex.point);
+  info->normal_of_point = data(m.normal.of_point); info->normal_point = data(m.normal.point);
+  info->texcoord_of_point = data(m.texcoord.of_point); info->texcoord_point = data(m.texcoord.point);
+  return DSA_OK;
+}
+void dsa_welded_free(dsa_welded *w) { delete w; }
+
 dsa_status dsa_encode_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_encode_sequential_options *options, dsa_encoded **out) {
   EncRequest rq = enc_request(n, true);
   rq.vertex = meshes;

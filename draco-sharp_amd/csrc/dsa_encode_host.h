@@ -1633,6 +1633,116 @@ static void encode_mesh(const MeshIn &in, const Options &opt, std::vector<uint8_
   out.swap(w.d);
 }
 
+// ------------------------------------------------------------------ the weld of per-point input
+// A mesh given as one row per point (a glTF primitive, an OBJ after triangulation, Batch.vertex_arrays): a point is duplicated
+// wherever a UV chart or a hard edge passes.  The weld finds the vertices under the points and hands the mesh on in the form
+// encode_mesh takes: positions (and everything else that stays per vertex) per vertex, normals and texture coordinates as rows
+// with ids per corner.  This is the specification the kernels of dsa_encode_weld.h are held against:
+//   - a point is used when a face names it; unused points take no part and get kInvalid in every map;
+//   - two used points are one vertex when the rows of every segment of `vertex_key` (positions, the generic attribute, every
+//     listed attribute) are equal byte for byte (-0.0 is not +0.0, a NaN equals the NaN of the same bits);
+//   - the representative of a class is its point of smallest index, classes are numbered by ascending representative;
+//   - normals (12-byte rows) and texture coordinates (8-byte rows) likewise, each alone;
+//   - an attribute whose row id is the same for all points of every vertex is handed on per vertex: the row of each vertex's
+//     representative, no ids (what lets a table that needs repair keep its normals: seams over a repaired table are not written).
+struct WeldSeg { const void *rows; uint32_t row_bytes; };
+struct WeldKeys {                      // one key set: the classes of the used points under its segments
+  uint32_t count = 0;
+  std::vector<uint32_t> of_point, point;      // class of every point (kInvalid: unused); representative of every class
+};
+struct Welded {
+  uint32_t P = 0, F = 0;
+  WeldKeys vertex, normal, texcoord;   // (normal / texcoord: count 0 and empty maps when the mesh has none)
+  bool normals_per_vertex = true, texcoords_per_vertex = true;
+  std::vector<uint32_t> faces, normal_corners, texcoord_corners;      // 3F each; the id lists empty when per vertex
+  std::vector<std::vector<uint8_t>> vertex_rows;                       // per segment of the vertex key: V rows
+  std::vector<uint8_t> normal_rows, texcoord_rows;                     // V rows when per vertex, else N / T rows
+};
+static inline uint32_t weld_hash(const std::vector<WeldSeg> &segs, uint32_t p) {
+  uint32_t h = 0x9E3779B9u;
+  for (const WeldSeg &s : segs) {
+    const uint8_t *r = (const uint8_t *)s.rows + (size_t)p * s.row_bytes;
+    for (uint32_t k = 0; k < s.row_bytes; ++k) { h ^= r[k]; h *= 0x01000193u; }
+  }
+  return h ^ (h >> 15);
+}
+static inline bool weld_equal(const std::vector<WeldSeg> &segs, uint32_t p, uint32_t q) {
+  for (const WeldSeg &s : segs)
+    if (memcmp((const uint8_t *)s.rows + (size_t)p * s.row_bytes, (const uint8_t *)s.rows + (size_t)q * s.row_bytes, s.row_bytes) != 0) return false;
+  return true;
+}
+static void weld_classes(const std::vector<WeldSeg> &segs, const std::vector<uint8_t> &used, WeldKeys &out) {
+  const uint32_t P = (uint32_t)used.size();
+  uint32_t cap = 16;
+  while (cap < 2ull * P) cap <<= 1;
+  std::vector<uint32_t> table(cap, kInvalid);
+  out.count = 0;
+  out.of_point.assign(P, kInvalid);
+  out.point.clear();
+  for (uint32_t p = 0; p < P; ++p) {            // ascending: the point that opens a class is its representative
+    if (!used[p]) continue;
+    uint32_t s = weld_hash(segs, p) & (cap - 1);
+    while (table[s] != kInvalid && !weld_equal(segs, table[s], p)) s = (s + 1) & (cap - 1);
+    if (table[s] == kInvalid) { table[s] = p; out.of_point[p] = out.count++; out.point.push_back(p); }
+    else out.of_point[p] = out.of_point[table[s]];
+  }
+}
+static void weld_gather(const WeldSeg &s, const std::vector<uint32_t> &points, std::vector<uint8_t> &rows) {
+  rows.resize((size_t)points.size() * s.row_bytes);
+  for (size_t v = 0; v < points.size(); ++v) memcpy(rows.data() + v * s.row_bytes, (const uint8_t *)s.rows + (size_t)points[v] * s.row_bytes, s.row_bytes);
+}
+static void weld_points(uint32_t P, const uint32_t *faces, uint32_t F, const std::vector<WeldSeg> &vertex_key, const float *normals, const float *uvs, Welded &out) {
+  check(F == 0 || faces != nullptr, "mesh needs positions and faces");
+  for (const WeldSeg &s : vertex_key) check(P == 0 || s.rows != nullptr, "mesh needs positions and faces");
+  for (size_t k = 0; k < (size_t)F * 3; ++k) check(faces[k] < P, "face index out of range");      // (before anything indexes through the faces)
+  out.P = P; out.F = F;
+  std::vector<uint8_t> used(P, 0);
+  for (size_t k = 0; k < (size_t)F * 3; ++k) used[faces[k]] = 1;
+  weld_classes(vertex_key, used, out.vertex);
+  out.faces.resize((size_t)F * 3);
+  for (size_t k = 0; k < (size_t)F * 3; ++k) out.faces[k] = out.vertex.of_point[faces[k]];
+  out.vertex_rows.resize(vertex_key.size());
+  for (size_t g = 0; g < vertex_key.size(); ++g) weld_gather(vertex_key[g], out.vertex.point, out.vertex_rows[g]);
+  auto attribute = [&](const float *values, uint32_t row_bytes, WeldKeys &keys, bool &per_vertex, std::vector<uint32_t> &corners, std::vector<uint8_t> &rows) {
+    keys = WeldKeys(); per_vertex = true; corners.clear(); rows.clear();
+    if (!values) return;
+    const WeldSeg seg{values, row_bytes};
+    weld_classes({seg}, used, keys);
+    for (uint32_t p = 0; p < P; ++p)
+      if (used[p] && keys.of_point[p] != keys.of_point[out.vertex.point[out.vertex.of_point[p]]]) { per_vertex = false; break; }
+    if (per_vertex) return weld_gather(seg, out.vertex.point, rows);
+    weld_gather(seg, keys.point, rows);
+    corners.resize((size_t)F * 3);
+    for (size_t k = 0; k < (size_t)F * 3; ++k) corners[k] = keys.of_point[faces[k]];
+  };
+  attribute(normals, 12, out.normal, out.normals_per_vertex, out.normal_corners, out.normal_rows);
+  attribute(uvs, 8, out.texcoord, out.texcoords_per_vertex, out.texcoord_corners, out.texcoord_rows);
+}
+// The welded mesh as the coder takes it: `in` is the per-point input (its corner ids unset, nv read as P), `key` the segments of
+// its vertex key in the order positions, generic, extras (weld_vertex_key); `ex` receives the extras pointed at their welded rows.
+static std::vector<WeldSeg> weld_vertex_key(const MeshIn &in, size_t generic_row_bytes) {
+  std::vector<WeldSeg> key;
+  key.push_back({in.pos, 12u});
+  if (in.generic) key.push_back({in.generic, (uint32_t)generic_row_bytes});
+  for (uint32_t k = 0; k < in.num_extras; ++k) key.push_back({in.extras[k].values, (uint32_t)(data_type_size(in.extras[k].data_type) * in.extras[k].nc)});
+  return key;
+}
+static MeshIn welded_mesh_in(const MeshIn &in, const Welded &w, std::vector<ExtraAttr> &ex) {
+  MeshIn m = in;
+  size_t g = 0;
+  m.pos = (const float *)w.vertex_rows[g++].data(); m.nv = w.vertex.count;
+  m.faces = w.faces.data(); m.nf = w.F;
+  if (in.generic) m.generic = w.vertex_rows[g++].data();
+  ex.assign(in.extras, in.extras + in.num_extras);
+  for (uint32_t k = 0; k < in.num_extras; ++k) ex[k].values = w.vertex_rows[g++].data();
+  m.extras = ex.data();
+  m.normals = in.normals ? (const float *)w.normal_rows.data() : nullptr;
+  m.normal_corners = w.normals_per_vertex ? nullptr : w.normal_corners.data(); m.nn = w.normals_per_vertex ? 0 : w.normal.count;
+  m.uvs = in.uvs ? (const float *)w.texcoord_rows.data() : nullptr;
+  m.uv_corners = w.texcoords_per_vertex ? nullptr : w.texcoord_corners.data(); m.nu = w.texcoords_per_vertex ? 0 : w.texcoord.count;
+  return m;
+}
+
 // ------------------------------------------------------------------ sequential streams
 // Sequential mesh (Mesh/MeshSequentialEncoder.cs:9-121 with the bitstream's index widths) and sequential point cloud
 // (PointCloud/PointCloudSequentialEncoder.cs): faces as point indices, compressed (differences, sign in the LSB, through the

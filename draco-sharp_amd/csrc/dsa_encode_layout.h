@@ -23,6 +23,7 @@
 #include "dsa_encode_host.h"
 #include "dsa_encode_conn.h"
 #include "dsa_encode_repair.h"
+#include "dsa_encode_weld.h"
 #include "dsa_encode_seams.h"
 #include "dsa_encode_seqidx.h"
 #include "dsa_encode_schemes.h"
@@ -115,6 +116,8 @@ struct EncRequest {
   bool sequential = false;
   bool repair_scan = false;                // dsa_encode_repair_batch, topology = 1, the first pass: two faces turned against each other over the same vertices are refused too
   bool repair = false;                     // dsa_encode_repair_batch, topology = 1, the second pass: the meshes the first pass refused for their topology, on the repaired corner table
+  bool weld = false;                       // dsa_encode_points_batch / dsa_weld_batch: `listed` holds one row per point, every chunk welds its meshes first (enc_stage_weld)
+  std::vector<synth::Welded> *weld_sink = nullptr;      // dsa_weld_batch: receives the weld of every mesh, nothing is coded
   dsa_encode_level_options level;          // Edgebreaker streams
   dsa_encode_sequential_options seq;       // sequential streams
   const dsa_encode_options &base() const { return sequential ? seq.base : level.ex.base; }
@@ -181,6 +184,11 @@ struct EncChunk {
   std::vector<std::vector<uint32_t>> c2row;
   std::vector<synth::CornerTable> rep;
   std::vector<dsa::EncRepairRows> rep_rows;
+  // a weld request (EncRequest::weld): the weld of every mesh, in buffers of the chunk's own, and the welded meshes in the form
+  // every stage behind enc_stage_weld reads (mesh(i) / corner(i) / attr(i) point here instead of at the caller's arrays)
+  std::vector<synth::Welded> weld;
+  std::vector<std::vector<dsa_attribute_input>> weld_attrs;
+  std::vector<dsa_mesh_attr_input> welded;
   EncLayout L;
   std::vector<std::pair<uint64_t, uint64_t>> *region_log = nullptr;
   // the device's side and what comes back from it
@@ -197,11 +205,12 @@ struct EncChunk {
     E->streams.resize(n); E->status.assign(n, DSA_OK); E->messages.resize(n);
     if (rq.listed) { extras.resize(n); extra_cap.resize(n); }
   }
-  const dsa_mesh_input &mesh(uint32_t i) const { return rq.mesh(base + i); }
+  const dsa_mesh_input &mesh(uint32_t i) const { return welded.empty() ? rq.mesh(base + i) : welded[i].mesh.mesh; }
   // vertices and faces of mesh i as the connectivity kernels and the streams see them
   uint32_t coded_vertices(uint32_t i) const { return !rep.empty() ? rep[i].nv() : (plans[i].coded_vertices >= 0 ? (uint32_t)plans[i].coded_vertices : mesh(i).num_vertices); }
   uint32_t coded_faces(uint32_t i) const { return !rep.empty() ? rep[i].nf() : (plans[i].coded_faces >= 0 ? (uint32_t)plans[i].coded_faces : mesh(i).num_faces); }
-  const dsa_mesh_corner_input *corner(uint32_t i) const { return rq.corner(base + i); }
+  const dsa_mesh_corner_input *corner(uint32_t i) const { return welded.empty() ? rq.corner(base + i) : &welded[i].mesh; }
+  const dsa_mesh_attr_input *attr(uint32_t i) const { return welded.empty() ? rq.attr(base + i) : &welded[i]; }
   bool good(uint32_t i) const { return E->status[i] == DSA_OK; }
   void refuse(uint32_t i, dsa_status st, const std::string &why) { E->status[i] = st; E->messages[i] = why; }
   // valence symbols per mesh: asked for, or by the reference's rule (speed < 5 and not a tiny mesh)
@@ -254,6 +263,49 @@ static void enc_extra_caps(EncChunk &ck, uint32_t i) {
     if (atts[k].extra_values && atts[k].seq_type == 1) ck.extra_cap[i][k] = enc_extra_hist_cap(atts[k], ck.mesh(i).num_vertices);
 }
 
+// ---- a weld request, mesh i: what the weld itself indexes by is checked here, before anything reads through the faces (the
+// rest of the mesh is the coder's to judge, on the welded form).  The segments of the vertex key into `key`; false: refused.
+static bool enc_weld_check(EncChunk &ck, uint32_t i, std::vector<synth::WeldSeg> &key) {
+  const dsa_mesh_attr_input &am = ck.rq.listed[ck.base + i];
+  const dsa_mesh_input &m = am.mesh.mesh;
+  if (am.mesh.normal_corners || am.mesh.texcoord_corners) { ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, "per-point input takes no corner ids (normal_corners / texcoord_corners must be NULL)"); return false; }
+  if (m.generic && (m.generic_components < 1 || m.generic_components > 4)) { ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, "generic attribute needs 1 - 4 components"); return false; }
+  synth::MeshIn in{m.positions, m.num_vertices, m.faces, m.num_faces, m.normals, m.texcoords, m.generic};
+  std::vector<synth::ExtraAttr> ex;
+  const std::string why = enc_take_extras(am, ex, in);
+  if (!why.empty()) { ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, why); return false; }
+  if ((m.num_vertices && !m.positions) || (m.num_faces && !m.faces)) { ck.refuse(i, DSA_ERR_INVALID_DATA, "mesh needs positions and faces"); return false; }
+  for (size_t k = 0, nk = (size_t)m.num_faces * 3; k < nk; ++k)
+    if (m.faces[k] >= m.num_vertices) { ck.refuse(i, DSA_ERR_INVALID_DATA, "face index out of range"); return false; }
+  key = synth::weld_vertex_key(in, m.generic ? m.generic_components : 0);
+  return true;
+}
+// the welded mesh i in the C structs, pointed at ck.weld[i] (a refused mesh: an empty one, which nothing reads)
+static void enc_weld_view(EncChunk &ck, uint32_t i) {
+  dsa_mesh_attr_input &out = ck.welded[i];
+  memset(&out, 0, sizeof(out));
+  if (!ck.good(i)) return;
+  const dsa_mesh_attr_input &am = ck.rq.listed[ck.base + i];
+  const synth::Welded &w = ck.weld[i];
+  dsa_mesh_input &m = out.mesh.mesh;
+  size_t g = 0;
+  m.num_vertices = w.vertex.count; m.num_faces = w.F;
+  m.positions = (const float *)w.vertex_rows[g++].data();
+  m.faces = w.faces.data();
+  if (am.mesh.mesh.generic) { m.generic = w.vertex_rows[g++].data(); m.generic_components = am.mesh.mesh.generic_components; }
+  ck.weld_attrs[i].assign(am.attributes, am.attributes + am.num_attributes);
+  for (uint32_t k = 0; k < am.num_attributes; ++k) ck.weld_attrs[i][k].values = w.vertex_rows[g++].data();
+  out.attributes = ck.weld_attrs[i].data(); out.num_attributes = am.num_attributes;
+  if (am.mesh.mesh.normals) {
+    m.normals = (const float *)w.normal_rows.data();
+    if (!w.normals_per_vertex) { out.mesh.normal_corners = w.normal_corners.data(); out.mesh.num_normals = w.normal.count; }
+  }
+  if (am.mesh.mesh.texcoords) {
+    m.texcoords = (const float *)w.texcoord_rows.data();
+    if (!w.texcoords_per_vertex) { out.mesh.texcoord_corners = w.texcoord_corners.data(); out.mesh.num_texcoords = w.texcoord.count; }
+  }
+}
+
 // ---- Edgebreaker streams, host phase 1 for mesh i: the checks of everything the kernels index by, the attribute descriptors, and
 // with host connectivity the connectivity, traversal orders and entry maps
 static void enc_plan_mesh(EncChunk &ck, uint32_t i) {
@@ -269,7 +321,7 @@ static void enc_plan_mesh(EncChunk &ck, uint32_t i) {
     in.uv_corners = cm->texcoord_corners; in.nu = cm->num_texcoords;
   }
   if (ck.rq.listed) {
-    const std::string why = enc_take_extras(*ck.rq.attr(ck.base + i), ck.extras[i], in);
+    const std::string why = enc_take_extras(*ck.attr(i), ck.extras[i], in);
     if (!why.empty()) return ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, why);
   }
   // (every mesh of a repair request is one whose topology the first pass refused)

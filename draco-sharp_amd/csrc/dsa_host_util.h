@@ -162,6 +162,11 @@ struct UploadTurns {
     cv.wait(lk, [&] { return !busy && a_waiting == 0; });
     busy = true;
   }
+  void acquire_free() {                   // the link in no order of the chunks (the point arrays of a weld: in front of the chunk's own phase A)
+    std::unique_lock<std::mutex> lk(m);
+    cv.wait(lk, [&] { return !busy; });
+    busy = true;
+  }
   void finish_a(uint32_t chunk, bool held) {          // also for a chunk that never uploads (held = false)
     {
       std::lock_guard<std::mutex> lk(m);
@@ -176,13 +181,14 @@ struct UploadTurns {
 struct TurnGuard {                       // a turn is given back, and a phase A that never came is struck off, on every exit path
   UploadTurns *t;
   uint32_t chunk;
-  int held = 0;                          // 1: phase A, 2: phase B
+  int held = 0;                          // 1: phase A, 2: phase B or a free turn
   bool a_over = false;
   TurnGuard(UploadTurns *turns, uint32_t chunk_index) : t(turns), chunk(chunk_index) {}
   TurnGuard(const TurnGuard &) = delete;
   TurnGuard &operator=(const TurnGuard &) = delete;
   void acquire_a() { if (t && !held && !a_over) { t->acquire_a(chunk); held = 1; } }
   void acquire_b() { if (t && !held) { if (!a_over) { t->finish_a(chunk, false); a_over = true; } t->acquire_b(); held = 2; } }
+  void acquire_free() { if (t && !held) { t->acquire_free(); held = 2; } }
   void release() {
     if (!t) return;
     if (held == 1) { t->finish_a(chunk, true); a_over = true; }

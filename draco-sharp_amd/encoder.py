@@ -37,7 +37,13 @@ class Config:
     repair_topology (dsa_encode_repair_batch, topology 1): meshes with degenerate faces, the same face twice, fins, faces turned
     over, fans that meet at a vertex or vertices no face uses are coded on the reference's repaired corner table (CornerTable.cs:
     28-43) instead of being refused; clean meshes give the same bytes.  Edgebreaker streams only; attributes given per corner over
-    a mesh that needs the repair are not implemented."""
+    a mesh that needs the repair are not implemented.
+
+    weld_points (dsa_encode_points_batch): the rows of a MeshData are per point, not per vertex -- a glTF primitive, an OBJ after
+    triangulation, Batch.vertex_arrays: points are duplicated wherever a UV chart or a hard edge passes.  Points with byte-equal
+    positions, generic and attribute rows are welded into one vertex, normals and texture coordinates go on per corner (or per
+    vertex where no vertex has two), and the welded mesh is coded with the other options as they are.  Edgebreaker streams of
+    meshes without corner ids only."""
 
     EDGEBREAKER_METHODS = (0, 2, -1)
     POSITION_PREDICTIONS = (0, 1)
@@ -49,7 +55,7 @@ class Config:
 
     def __init__(self, position_bits=11, texcoord_bits=10, normal_bits=8, speed=5, single_connectivity=False,
                  symbol_scheme=-1, position_prediction=1, texcoord_prediction=1, edgebreaker_method=0, normal_prediction=0,
-                 encoding_method=1, compress_connectivity=False, multi_parallelogram=0, traversal_method=0, repair_topology=False):
+                 encoding_method=1, compress_connectivity=False, multi_parallelogram=0, traversal_method=0, repair_topology=False, weld_points=False):
         for name, value, legal in (("encoding_method", encoding_method, self.ENCODING_METHODS),
                                    ("edgebreaker_method", edgebreaker_method, self.EDGEBREAKER_METHODS),
                                    ("position_prediction", position_prediction, self.POSITION_PREDICTIONS),
@@ -72,6 +78,9 @@ class Config:
             raise ValueError("repair_topology shapes Edgebreaker streams: a sequential stream takes any list of triangles as it is")
         if self.leveled and self.sequential:
             raise ValueError("multi_parallelogram / traversal_method shape Edgebreaker streams: a sequential stream predicts by Difference in point order")
+        self.weld_points = bool(weld_points)
+        if self.weld_points and self.sequential:
+            raise ValueError("weld_points shapes Edgebreaker streams: a sequential stream keeps the caller's points as they are")
 
     @property
     def sequential(self):
@@ -310,13 +319,34 @@ class EncodedStreams:
         self.close()
 
 
+class WeldedMaps:
+    """dsa_welded_info of one mesh as numpy arrays (copies): num_points / num_vertices / num_normals / num_texcoords,
+    normals_per_vertex / texcoords_per_vertex, and vertex_of_point [P] (0xFFFFFFFF: a point no face names), vertex_point [V],
+    normal_of_point / normal_point, texcoord_of_point / texcoord_point (None when the mesh has no such attribute)."""
+
+    def __init__(self, info):
+        self.num_points, self.num_vertices = info.num_points, info.num_vertices
+        self.num_normals, self.num_texcoords = info.num_normals, info.num_texcoords
+        self.normals_per_vertex, self.texcoords_per_vertex = bool(info.normals_per_vertex), bool(info.texcoords_per_vertex)
+
+        def array(ptr, count):
+            return np.frombuffer(C.string_at(ptr, 4 * count), np.uint32).copy() if ptr and count else np.zeros(0, np.uint32)
+        self.vertex_of_point, self.vertex_point = array(info.vertex_of_point, info.num_points), array(info.vertex_point, info.num_vertices)
+        has_n, has_t = bool(info.normal_of_point) or info.num_normals > 0, bool(info.texcoord_of_point) or info.num_texcoords > 0
+        self.normal_of_point = array(info.normal_of_point, info.num_points) if has_n else None
+        self.normal_point = array(info.normal_point, info.num_normals) if has_n else None
+        self.texcoord_of_point = array(info.texcoord_of_point, info.num_points) if has_t else None
+        self.texcoord_point = array(info.texcoord_point, info.num_texcoords) if has_t else None
+
+
 class DracoEncoder:
     def __init__(self, context=None):
         self._ctx = context
 
-    def EncodeBatch(self, meshes, config=None):
+    def EncodeBatch(self, meshes, config=None, handle=False):
         """meshes: list of MeshData (or of PointCloudData) -> sequence of bytes (.drc streams, EncodedStreams).  A sequential
-        config (Config.sequential) and point clouds go through dsa_encode_sequential_batch.  A mesh that cannot be encoded raises."""
+        config (Config.sequential) and point clouds go through dsa_encode_sequential_batch.  A mesh that cannot be encoded raises
+        (TryEncodeBatch: the batch with its failures, mesh by mesh)."""
         n = len(meshes)
         config = config or Config()
         # what the batch is, before anything touches the device: meshes or point clouds, not both; a sequential stream has one
@@ -328,14 +358,20 @@ class DracoEncoder:
             raise ValueError("multi_parallelogram / traversal_method shape Edgebreaker streams: point clouds and sequential streams predict by Difference in point order")
         if (clouds or config.sequential) and any(getattr(m, "per_corner", False) for m in meshes):
             raise ValueError("attributes given per corner need Edgebreaker connectivity (encoding_method 1): a sequential stream has one value per point")
+        weld = getattr(config, "weld_points", False)
+        if weld and (clouds or config.sequential):
+            raise ValueError("weld_points shapes Edgebreaker streams of meshes: point clouds and sequential streams keep the caller's points")
+        if weld and any(getattr(m, "per_corner", False) for m in meshes):
+            raise ValueError("weld_points takes one row per point: normal_corners / texcoord_corners describe a mesh that is welded already")
         ctx = self._ctx or default_context()
         L = native.lib()
         if clouds or config.sequential:
-            return self._encode_sequential(ctx, meshes, config, 0 if clouds else 1)
+            return self._encode_sequential(ctx, meshes, config, 0 if clouds else 1, handle=handle)
         ex = config.extended
         # the attribute-list entry point only when some mesh has a list; the corner entry point only when some mesh carries ids (or
         # an option needs dsa_encode_batch_ex, which takes the corner form); otherwise exactly the per-vertex call
         repair = getattr(config, "repair_topology", False)      # dsa_encode_repair_batch: the level call's input and options, and the topology switch
+        repair = repair or weld               # dsa_encode_points_batch takes that call's input and options
         level = config.leveled or repair      # dsa_encode_level_batch takes the widest input: always dsa_mesh_attr_input, an empty list is legal
         listed = level or any(getattr(m, "attributes", None) for m in meshes)
         corners = listed or ex or any(getattr(m, "per_corner", False) for m in meshes)
@@ -362,17 +398,19 @@ class DracoEncoder:
         opt = config._native_repair() if repair else config._native_level() if level else (config._native_ex() if (ex or listed) else config._native())
         h = C.c_void_p()
         t0 = time.perf_counter()
-        entry = L.dsa_encode_repair_batch if repair else L.dsa_encode_level_batch if level else L.dsa_encode_attributes_batch if listed else (L.dsa_encode_batch_ex if ex else (L.dsa_encode_batch_corners if corners else L.dsa_encode_batch))
+        entry = L.dsa_encode_points_batch if weld else L.dsa_encode_repair_batch if repair else L.dsa_encode_level_batch if level else L.dsa_encode_attributes_batch if listed else (L.dsa_encode_batch_ex if ex else (L.dsa_encode_batch_corners if corners else L.dsa_encode_batch))
         st = entry(ctx._h, n, arr, C.byref(opt), C.byref(h))
         t1 = time.perf_counter()
         if st != 0:
             _raise(st, ctx.error())
+        if handle:
+            return ctx, h, n
         r = EncodedStreams(ctx, h, n)
         if os.environ.get("DSA_ENC_TIMING"):            # diagnostics, like the library's own phase clocks
             print("[EncodeBatch] native call %.1f ms, result handles %.1f ms" % ((t1 - t0) * 1e3, (time.perf_counter() - t1) * 1e3), flush=True)
         return r
 
-    def _encode_sequential(self, ctx, meshes, config, geometry):
+    def _encode_sequential(self, ctx, meshes, config, geometry, handle=False):
         L = native.lib()
         n = len(meshes)
         listed = any(getattr(m, "attributes", None) for m in meshes)
@@ -396,7 +434,68 @@ class DracoEncoder:
         st = entry(ctx._h, n, arr, C.byref(opt), C.byref(h))
         if st != 0:
             _raise(st, ctx.error())
-        return EncodedStreams(ctx, h, n)
+        return (ctx, h, n) if handle else EncodedStreams(ctx, h, n)
+
+    def TryEncodeBatch(self, meshes, config=None):
+        """EncodeBatch that keeps the meshes the encoder refuses: a list with, per mesh, the stream as bytes or the exception (its text says why)
+        that EncodeBatch would have raised for it.  A failure of the call itself still raises."""
+        ctx, h, n = self.EncodeBatch(meshes, config, handle=True)
+        L = native.lib()
+        out = []
+        p, ln = C.c_void_p(), C.c_size_t()
+        try:
+            for i in range(n):
+                st = L.dsa_encoded_stream(h, i, C.byref(p), C.byref(ln))
+                if st == 0:
+                    out.append(C.string_at(p, ln.value))
+                    continue
+                try:
+                    _raise(st, ctx.error())
+                except Exception as e:          # noqa: BLE001  (the exception is the result)
+                    out.append(e)
+        finally:
+            L.dsa_encoded_free(h)
+        return out
+
+    def WeldBatch(self, meshes):
+        """The weld of dsa_encode_points_batch alone (dsa_weld_batch): per MeshData given as one row per point a WeldedMaps with
+        the maps between points and vertices / normal rows / texture coordinate rows as numpy arrays -- what carries further
+        per-point data (morph targets) across the weld: row v of a welded array is row vertex_point[v] of the per-point one.  A
+        mesh that cannot be welded (a face index out of range) raises."""
+        if any(isinstance(m, PointCloudData) for m in meshes):
+            raise ValueError("the weld takes meshes: a point cloud has no faces that name its points")
+        if any(getattr(m, "per_corner", False) for m in meshes):
+            raise ValueError("the weld takes one row per point: normal_corners / texcoord_corners describe a mesh that is welded already")
+        ctx = self._ctx or default_context()
+        L = native.lib()
+        n = len(meshes)
+        arr = (native.MeshAttrInput * max(1, n))()
+        keep = []
+        for i, m in enumerate(meshes):
+            _fill_attr_input(arr[i], m, keep)
+            mi = arr[i].mesh.mesh
+            mi.num_vertices, mi.num_faces = len(m.positions), len(m.faces)
+            mi.positions, mi.faces = m.positions.ctypes.data, m.faces.ctypes.data
+            mi.normals = m.normals.ctypes.data if m.normals is not None else None
+            mi.texcoords = m.texcoords.ctypes.data if m.texcoords is not None else None
+            g = getattr(m, "generic", None)
+            mi.generic = g.ctypes.data if g is not None else None
+            mi.generic_components = g.shape[1] if g is not None else 0
+        h = C.c_void_p()
+        st = L.dsa_weld_batch(ctx._h, n, arr, C.byref(h))
+        if st != 0:
+            _raise(st, ctx.error())
+        try:
+            out = []
+            info = native.WeldedInfo()
+            for i in range(n):
+                st = L.dsa_welded_mesh(h, i, C.byref(info))
+                if st != 0:
+                    _raise(st, ctx.error())
+                out.append(WeldedMaps(info))
+            return out
+        finally:
+            L.dsa_welded_free(h)
 
     def Encode(self, mesh, config=None):
         return self.EncodeBatch([mesh], config)[0]

@@ -1,7 +1,9 @@
 """glTF 2.0 containers in front of the batch decode path: every primitive that carries KHR_draco_mesh_compression in
 any number of .gltf / .glb assets becomes one stream of one `Batch` (the caller on the input
 side of the path).  Only the container is handled here -- JSON, GLB chunks, buffers and buffer views; what is inside
-the buffer view goes to the GPU untouched.
+the buffer view goes to the GPU untouched.  GltfDracoWriter is the counterpart on the encode side: it compresses the TRIANGLES
+primitives of any number of assets in one EncodeBatch (Config(weld_points=True): a primitive is one row per point) and rewrites
+the documents with the extension.
 
 The extension object is `{"bufferView": i, "attributes": {"POSITION": id, ...}}`: the ids are Draco unique ids
 (PointCloud.GetAttributeByUniqueId), decoded values are per *point* and the faces are point indices, which is exactly
@@ -234,3 +236,279 @@ class GltfDracoLoader:
             if views["attributes"][k]["quantization"] is not None:
                 quantization[semantic] = views["attributes"][k]["quantization"]
         return DecodedPrimitive(p, draco, indices, attributes, quantization)
+
+
+# ------------------------------------------------------------------------------------------------------------ the writer
+_COMPONENT_DTYPES = {5120: np.int8, 5121: np.uint8, 5122: np.int16, 5123: np.uint16, 5125: np.uint32, 5126: np.float32}
+
+
+def read_accessor(asset, index):
+    """The elements of accessor `index` as an array [count, components] of its component type (byteStride honoured)."""
+    accessors = asset.doc.get("accessors", [])
+    if not isinstance(index, int) or not 0 <= index < len(accessors):
+        raise InvalidDataException("%s: accessor %r does not exist" % (asset.name, index))
+    acc = accessors[index]
+    dtype, nc = _COMPONENT_DTYPES.get(acc.get("componentType")), _TYPE_COMPONENTS.get(acc.get("type"))
+    if dtype is None or nc is None:
+        raise InvalidDataException("%s: accessor %d: unknown componentType / type" % (asset.name, index))
+    if "sparse" in acc or "bufferView" not in acc:
+        raise InvalidDataException("%s: accessor %d: sparse accessors and accessors without a buffer view are not read" % (asset.name, index))
+    count = int(acc.get("count", 0))
+    view = asset.doc.get("bufferViews", [])[acc["bufferView"]] if 0 <= acc["bufferView"] < len(asset.doc.get("bufferViews", [])) else None
+    data = asset.buffer_view(acc["bufferView"])
+    row = np.dtype(dtype).itemsize * nc
+    stride = int(view.get("byteStride", 0)) or row
+    off = int(acc.get("byteOffset", 0))
+    if count < 0 or stride < row or off < 0 or (count and off + (count - 1) * stride + row > len(data)):
+        raise InvalidDataException("%s: accessor %d leaves its buffer view" % (asset.name, index))
+    if count == 0:
+        return np.zeros((0, nc), dtype)
+    raw = np.frombuffer(data, np.uint8, (count - 1) * stride + row, off)
+    rows = np.lib.stride_tricks.as_strided(raw, (count, row), (stride, 1))
+    return np.ascontiguousarray(rows).view(dtype).reshape(count, nc)
+
+
+class PlannedPrimitive:
+    """A primitive the writer compresses: where it sits, its MeshData (one row per point, as the accessors give them) and the
+    Draco unique id of every semantic (the attribute's index in the stream)."""
+
+    def __init__(self, asset, mesh, primitive, data, attribute_ids):
+        self.asset, self.mesh, self.primitive, self.data, self.attribute_ids = asset, mesh, primitive, data, attribute_ids
+
+
+class SkippedPrimitive:
+    """A primitive that stays as it is, and why."""
+
+    def __init__(self, asset, mesh, primitive, reason):
+        self.asset, self.mesh, self.primitive, self.reason = asset, mesh, primitive, reason
+
+
+def _listed_semantic(semantic):
+    """attribute_type of a semantic that goes through the attribute list (2 colour, 3 texture coordinate, 4 generic), or None."""
+    head, _, n = semantic.rpartition("_")
+    if not n.isdigit():
+        return None
+    if head == "COLOR":
+        return 2
+    if head == "TEXCOORD":
+        return 3
+    return 4 if head in ("JOINTS", "WEIGHTS") else None
+
+
+def plan_compression(assets):
+    """Needs no device.  (planned, skipped): every TRIANGLES primitive with float32 VEC3 POSITION and indices becomes a MeshData
+    -- NORMAL (float32 VEC3) and TEXCOORD_0 (float32 VEC2) as built-ins, COLOR_n, JOINTS_n, WEIGHTS_n, TEXCOORD_n in other forms
+    through the attribute list in their component types -- every other primitive is skipped with the reason."""
+    from .encoder import Attribute, MeshData
+    planned, skipped = [], []
+    for asset in assets:
+        accessors = asset.doc.get("accessors", [])
+        for mi, mesh in enumerate(asset.doc.get("meshes", [])):
+            for pi, prim in enumerate(mesh.get("primitives", [])):
+                def skip(reason):
+                    skipped.append(SkippedPrimitive(asset, mi, pi, reason))
+                atts = prim.get("attributes", {})
+                if EXTENSION in prim.get("extensions", {}):
+                    skip("already compressed"); continue
+                if prim.get("mode", 4) != 4:
+                    skip("mode %d: only TRIANGLES (4) are compressed" % prim.get("mode")); continue
+                if prim.get("indices") is None:
+                    skip("no indices"); continue
+                if prim.get("targets"):
+                    skip("morph targets are not carried into the stream"); continue
+                if "POSITION" not in atts:
+                    skip("no POSITION"); continue
+
+                def form(semantic):
+                    a = accessors[atts[semantic]] if isinstance(atts[semantic], int) and 0 <= atts[semantic] < len(accessors) else {}
+                    return a.get("componentType"), a.get("type")
+                if form("POSITION") != (5126, "VEC3"):
+                    skip("POSITION is not float32 VEC3"); continue
+                try:
+                    pos = read_accessor(asset, atts["POSITION"])
+                    idx = read_accessor(asset, prim["indices"])
+                    if idx.shape[1] != 1 or idx.dtype not in (np.uint8, np.uint16, np.uint32) or len(idx) % 3 or len(idx) == 0:
+                        skip("indices are not a list of triangles"); continue
+                    normals = texcoords = None
+                    ids, listed, why = {"POSITION": 0}, [], None
+                    if "NORMAL" in atts and form("NORMAL") == (5126, "VEC3"):
+                        normals = read_accessor(asset, atts["NORMAL"])
+                        ids["NORMAL"] = len(ids)
+                    if "TEXCOORD_0" in atts and form("TEXCOORD_0") == (5126, "VEC2"):
+                        texcoords = read_accessor(asset, atts["TEXCOORD_0"])
+                        ids["TEXCOORD_0"] = len(ids)
+                    for semantic in atts:
+                        if semantic in ids:
+                            continue
+                        kind = _listed_semantic(semantic)
+                        if kind is None:
+                            why = "attribute %s is not compressed" % semantic
+                            break
+                        values = read_accessor(asset, atts[semantic])
+                        if values.shape[1] > 4:
+                            why = "attribute %s has more than 4 components" % semantic
+                            break
+                        ids[semantic] = len(ids)
+                        listed.append(Attribute(values, attribute_type=kind, normalized=bool(accessors[atts[semantic]].get("normalized", False))))
+                    if why is None and len(ids) > 16:
+                        why = "more than 16 attributes"
+                    rows = [normals, texcoords] + [a.values for a in listed]
+                    if why is None and any(r is not None and len(r) != len(pos) for r in rows):
+                        why = "attribute accessors of different counts"
+                    if why is not None:
+                        skip(why); continue
+                except InvalidDataException as e:
+                    skip(str(e)); continue
+                data = MeshData(pos, idx.astype(np.uint32).reshape(-1, 3), normals, texcoords, attributes=listed)
+                planned.append(PlannedPrimitive(asset, mi, pi, data, ids))
+    return planned, skipped
+
+
+def _references(doc, key, out):
+    if isinstance(doc, dict):
+        for k, v in doc.items():
+            if k == key and isinstance(v, int) and not isinstance(v, bool):
+                out.append((doc, k))
+            else:
+                _references(v, key, out)
+    elif isinstance(doc, list):
+        for v in doc:
+            _references(v, key, out)
+
+
+def _used_accessors(doc):
+    used = set()
+    for mesh in doc.get("meshes", []):
+        for prim in mesh.get("primitives", []):
+            used.update(v for v in prim.get("attributes", {}).values() if isinstance(v, int))
+            if isinstance(prim.get("indices"), int):
+                used.add(prim["indices"])
+            for t in prim.get("targets", []) or []:
+                used.update(v for v in t.values() if isinstance(v, int))
+    for anim in doc.get("animations", []):
+        for smp in anim.get("samplers", []):
+            used.update(v for v in (smp.get("input"), smp.get("output")) if isinstance(v, int))
+    for skin in doc.get("skins", []):
+        if isinstance(skin.get("inverseBindMatrices"), int):
+            used.add(skin["inverseBindMatrices"])
+    for node in doc.get("nodes", []):
+        for ext in (node.get("extensions") or {}).values():
+            if isinstance(ext, dict):
+                used.update(v for v in (ext.get("attributes") or {}).values() if isinstance(v, int))
+    return used
+
+
+def rewrite_asset(asset, coded):
+    """Needs no device.  The asset as GLB bytes with the primitives of `coded` -- {(mesh, primitive): (stream, num_points, num_faces,
+    {semantic: unique id})} -- carrying KHR_draco_mesh_compression: the stream in a buffer view of its own, accessors of the
+    decoded counts without buffer views (copies: an accessor may serve other primitives), extensionsUsed / extensionsRequired.
+    Accessors no primitive, animation or skin names any more lose their buffer views, buffer views nothing names are dropped, and
+    what is left is packed into the one binary chunk."""
+    doc = json.loads(json.dumps(asset.doc))
+    accessors = doc.setdefault("accessors", [])
+    views = doc.setdefault("bufferViews", [])
+    before = _used_accessors(doc)
+    streams = []
+    for (mi, pi), (stream, num_points, num_faces, ids) in sorted(coded.items()):
+        prim = doc["meshes"][mi]["primitives"][pi]
+
+        def fresh(index, count):
+            acc = {k: v for k, v in accessors[index].items() if k not in ("bufferView", "byteOffset", "sparse")}
+            acc["count"] = int(count)
+            accessors.append(acc)
+            return len(accessors) - 1
+        prim["attributes"] = {s: fresh(a, num_points) for s, a in prim["attributes"].items()}
+        prim["indices"] = fresh(prim["indices"], 3 * num_faces)
+        streams.append(bytes(stream))
+        views.append({"buffer": -1 - (len(streams) - 1), "byteLength": len(stream)})        # (negative: stream k, placed below)
+        prim.setdefault("extensions", {})[EXTENSION] = {"bufferView": len(views) - 1, "attributes": {s: int(i) for s, i in ids.items()}}
+    if coded:
+        for key in ("extensionsUsed", "extensionsRequired"):
+            if EXTENSION not in doc.setdefault(key, []):
+                doc[key].append(EXTENSION)
+    for index in before - _used_accessors(doc):
+        for k in ("bufferView", "byteOffset"):
+            accessors[index].pop(k, None)
+    refs = []
+    _references(doc, "bufferView", refs)
+    keep = sorted({d[k] for d, k in refs if 0 <= d[k] < len(views)})
+    renumber = {old: new for new, old in enumerate(keep)}
+    blob = bytearray()
+    packed = []
+    for old in keep:
+        v = dict(views[old])
+        data = streams[-1 - v["buffer"]] if v["buffer"] < 0 else asset.buffer_view(old)
+        while len(blob) % 4:
+            blob.append(0)
+        v["buffer"], v["byteOffset"], v["byteLength"] = 0, len(blob), len(data)
+        blob += data
+        packed.append(v)
+    for d, k in refs:
+        if d[k] in renumber:
+            d[k] = renumber[d[k]]
+    doc["bufferViews"] = packed
+    if not packed:
+        doc.pop("bufferViews")
+    doc["buffers"] = [{"byteLength": len(blob)}] if blob else []
+    if not doc["buffers"]:
+        doc.pop("buffers")
+    if not accessors:
+        doc.pop("accessors")
+    text = json.dumps(doc, separators=(",", ":")).encode("utf-8")
+    text += b" " * (-len(text) % 4)
+    blob += b"\0" * (-len(blob) % 4)
+    chunks = struct.pack("<II", len(text), _CHUNK_JSON) + text
+    if blob:
+        chunks += struct.pack("<II", len(blob), _CHUNK_BIN) + bytes(blob)
+    return struct.pack("<III", _GLB_MAGIC, 2, 12 + len(chunks)) + chunks
+
+
+class CompressedAsset:
+    """glb: the rewritten asset; compressed: [(mesh, primitive, stream bytes, points in the stream)]; skipped: [SkippedPrimitive],
+    the primitives that stayed as they were (outside what the writer compresses, or refused by the encoder) with the reason."""
+
+    def __init__(self, glb, compressed, skipped):
+        self.glb, self.compressed, self.skipped = glb, compressed, skipped
+
+
+class GltfDracoWriter:
+    """Compresses the TRIANGLES primitives of many assets in one batch on one GPU."""
+
+    def __init__(self, context=None):
+        self.ctx = context or default_context()
+
+    def compress(self, sources, config=None):
+        """sources: paths, bytes or GltfAssets.  One EncodeBatch with weld_points=True codes every planned primitive (the other
+        options of `config` as given); one decode batch of the result gives the accessor counts -- a stream can hold more points
+        than its primitive had where seams cross.  Returns a CompressedAsset per source."""
+        import copy
+        from .encoder import Config, DracoEncoder
+        assets = [s if isinstance(s, GltfAsset) else read_asset(s) for s in sources]
+        planned, skipped = plan_compression(assets)
+        cfg = copy.copy(config) if config is not None else Config()
+        cfg.weld_points = True
+        if cfg.sequential:
+            raise ValueError("the writer codes Edgebreaker streams (weld_points): a sequential config keeps the caller's points")
+        coded = {id(a): {} for a in assets}
+        if planned:
+            streams = DracoEncoder(self.ctx).TryEncodeBatch([p.data for p in planned], cfg)
+            good = [k for k, s in enumerate(streams) if isinstance(s, bytes)]
+            for k, s in enumerate(streams):
+                if not isinstance(s, bytes):
+                    skipped.append(SkippedPrimitive(planned[k].asset, planned[k].mesh, planned[k].primitive, "the encoder refused it: %s" % s))
+            if good:
+                batch = Batch(self.ctx, [streams[k] for k in good])
+                try:
+                    batch.decode()
+                    for j, k in enumerate(good):
+                        info = batch.mesh_info(j)
+                        p = planned[k]
+                        coded[id(p.asset)][(p.mesh, p.primitive)] = (streams[k], info.num_points, info.num_faces, p.attribute_ids)
+                finally:
+                    batch.close()
+        out = []
+        for a in assets:
+            mine = coded[id(a)]
+            out.append(CompressedAsset(rewrite_asset(a, mine), [(m, p, v[0], v[1]) for (m, p), v in sorted(mine.items())],
+                                       [s for s in skipped if s.asset is a]))
+        return out

@@ -33,6 +33,7 @@ EXPORTS = [
     "dsa_encode_attributes_batch", "dsa_encode_attributes_sequential_batch",
     "dsa_encode_default_level_options", "dsa_encode_level_batch",
     "dsa_encode_default_repair_options", "dsa_encode_repair_batch",
+    "dsa_encode_points_batch", "dsa_weld_batch", "dsa_welded_size", "dsa_welded_mesh", "dsa_welded_free",
     "dsa_encoded_size", "dsa_encoded_stream", "dsa_encoded_free",
     "dsa_pool_create", "dsa_pool_destroy", "dsa_pool_size", "dsa_pool_last_error", "dsa_pool_decode", "dsa_pool_job_locate",
     "dsa_pool_job_chunks", "dsa_pool_job_free", "dsa_pool_plan",
@@ -99,6 +100,16 @@ class MeshAttrInput(C.Structure):
     """dsa_mesh_attr_input: a mesh (or point cloud) with an attribute list."""
     _fields_ = [("mesh", MeshCornerInput), ("attributes", C.POINTER(AttributeInput)), ("num_attributes", C.c_uint32),
                 ("reserved", C.c_uint32)]
+
+
+class WeldedInfo(C.Structure):
+    """dsa_welded_info: the weld of one mesh given as one row per point -- counts, whether normals / texture coordinates collapse
+    to one row per vertex, and the six maps (host memory owned by the dsa_welded handle)."""
+    _fields_ = [("status", C.c_int32), ("num_points", C.c_uint32), ("num_vertices", C.c_uint32), ("num_normals", C.c_uint32),
+                ("num_texcoords", C.c_uint32), ("normals_per_vertex", C.c_uint32), ("texcoords_per_vertex", C.c_uint32),
+                ("reserved", C.c_uint32),
+                ("vertex_of_point", C.c_void_p), ("vertex_point", C.c_void_p), ("normal_of_point", C.c_void_p),
+                ("normal_point", C.c_void_p), ("texcoord_of_point", C.c_void_p), ("texcoord_point", C.c_void_p)]
 
 
 class MeshInfo(C.Structure):
@@ -230,6 +241,14 @@ def lib():
             L.dsa_encode_default_repair_options.argtypes = [C.POINTER(EncodeRepairOptions)]
             L.dsa_encode_default_repair_options.restype = None
             L.dsa_encode_repair_batch.argtypes = [vp, u32, C.POINTER(MeshAttrInput), C.POINTER(EncodeRepairOptions), C.POINTER(vp)]
+        if hasattr(L, "dsa_encode_points_batch"):
+            L.dsa_encode_points_batch.argtypes = [vp, u32, C.POINTER(MeshAttrInput), C.POINTER(EncodeRepairOptions), C.POINTER(vp)]
+            L.dsa_weld_batch.argtypes = [vp, u32, C.POINTER(MeshAttrInput), C.POINTER(vp)]
+            L.dsa_welded_size.restype = u32
+            L.dsa_welded_size.argtypes = [vp]
+            L.dsa_welded_mesh.argtypes = [vp, u32, C.POINTER(WeldedInfo)]
+            L.dsa_welded_free.argtypes = [vp]
+            L.dsa_welded_free.restype = None
         L.dsa_encoded_size.restype = u32
         L.dsa_encoded_size.argtypes = [vp]
         L.dsa_encoded_stream.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(C.c_size_t)]

@@ -135,6 +135,14 @@ def lib():
         L.synth_encode_attributes.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                               C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(ExtraInput), C.c_uint32,
                                               C.POINTER(Options), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+        L.synth_weld_points.restype = C.c_void_p
+        L.synth_weld_points.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.POINTER(ExtraInput), C.c_uint32, C.POINTER(Options)]
+        L.synth_welded_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        L.synth_welded_array.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+        L.synth_welded_free.argtypes = [C.c_void_p]
+        L.synth_encode_points.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.POINTER(ExtraInput), C.c_uint32, C.POINTER(Options), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
         L.synth_free.argtypes = [C.c_void_p]
         L.synth_make_mesh.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_uint32),
                                       C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -246,6 +254,98 @@ def encode_mesh_corners(pos, faces, normals=None, normal_corners=None, uvs=None,
                                      None if uv is None else uv.ctypes.data, 0 if uv is None else len(uv),
                                      None if uci is None else uci.ctypes.data, None if gen is None else gen.ctypes.data,
                                      C.byref(opt), C.byref(out), C.byref(n))
+    if rc:
+        raise RuntimeError(_err())
+    data = C.string_at(out, n.value)
+    L.synth_free(out)
+    return data
+
+
+class Welded:
+    """What weld_points returns.  Maps (uint32; 0xFFFFFFFF for a point no face names): vertex_of_point / normal_of_point /
+    texcoord_of_point [P], vertex_point [V] / normal_point [N] / texcoord_point [T] (the representative point of every class; the
+    normal / texcoord maps are None when the mesh has no such attribute).  The welded mesh: pos [V,3], faces [F,3], generic and
+    extra (rows of vertex_point), normals with normal_corners [F,3] (None and V rows when normals_per_vertex), uvs with
+    uv_corners likewise."""
+
+
+def _points_args(pos, faces, normals, uvs, generic, extra, opt):
+    pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+    faces = np.ascontiguousarray(faces, np.uint32).reshape(-1, 3)
+    nrm = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    uv = None if uvs is None else np.ascontiguousarray(uvs, np.float32).reshape(-1, 2)
+    opt = opt or options()
+    gen = None
+    if generic is not None:
+        gen, opt = _generic(generic, opt)
+        gen = gen.reshape(len(gen), -1)
+        if opt.generic_components != gen.shape[1]:          # the components are the array's own (a copy: the caller's options stay)
+            o2 = Options()
+            C.memmove(C.byref(o2), C.byref(opt), C.sizeof(Options))
+            o2.generic_components = gen.shape[1]
+            opt = o2
+    for a, name in ((nrm, "normals"), (uv, "uvs"), (gen, "generic")):
+        if a is not None and len(a) != len(pos):
+            raise ValueError("%s: one row per point" % name)
+    extra = [e if isinstance(e, Extra) else Extra(e) for e in (extra or [])]
+    return pos, faces, nrm, uv, gen, extra, _extras(extra, len(pos)), opt
+
+
+def weld_points(pos, faces, normals=None, uvs=None, generic=None, extra=None, opt=None):
+    """The weld of a mesh given as one row per point (dsa_encode_host.h weld_points): used points with byte-equal position,
+    generic and extra rows are one vertex; normals and uvs are welded each alone and handed on per corner, or per vertex where
+    no vertex has two of them.  Returns a Welded."""
+    L = lib()
+    pos, faces, nrm, uv, gen, extra, arr, opt = _points_args(pos, faces, normals, uvs, generic, extra, opt)
+    ptr = lambda a: None if a is None else a.ctypes.data          # noqa: E731
+    h = L.synth_weld_points(ptr(pos), len(pos), ptr(faces), len(faces), ptr(nrm), ptr(uv), ptr(gen), arr, len(extra), C.byref(opt))
+    if not h:
+        raise RuntimeError(_err())
+    try:
+        counts = (C.c_uint32 * 8)()
+        L.synth_welded_counts(h, counts)
+
+        def array(which, dtype):
+            data, nbytes = C.c_void_p(), C.c_size_t()
+            if L.synth_welded_array(h, which, C.byref(data), C.byref(nbytes)):
+                raise RuntimeError("synth_welded_array(%d)" % which)
+            return np.frombuffer(C.string_at(data, nbytes.value), dtype).copy() if nbytes.value else np.zeros(0, dtype)
+        w = Welded()
+        w.num_points, w.num_faces, w.num_vertices, w.num_normals, w.num_texcoords = [int(c) for c in counts[:5]]
+        w.normals_per_vertex, w.texcoords_per_vertex = bool(counts[5]), bool(counts[6])
+        w.vertex_of_point, w.vertex_point = array(0, np.uint32), array(1, np.uint32)
+        w.normal_of_point, w.normal_point = (array(2, np.uint32), array(3, np.uint32)) if nrm is not None else (None, None)
+        w.texcoord_of_point, w.texcoord_point = (array(4, np.uint32), array(5, np.uint32)) if uv is not None else (None, None)
+        w.faces = array(6, np.uint32).reshape(-1, 3)
+        w.normal_corners = None if w.normals_per_vertex else array(7, np.uint32).reshape(-1, 3)
+        w.uv_corners = None if w.texcoords_per_vertex else array(8, np.uint32).reshape(-1, 3)
+        w.normals = None if nrm is None else array(9, np.float32).reshape(-1, 3)
+        w.uvs = None if uv is None else array(10, np.float32).reshape(-1, 2)
+        g = 16
+        w.pos = array(g, np.float32).reshape(-1, 3)
+        g += 1
+        w.generic = None
+        if gen is not None:
+            w.generic = array(g, gen.dtype).reshape(-1, gen.shape[1])
+            g += 1
+        w.extra = []
+        for e in extra:
+            w.extra.append(array(g, e.values.dtype).reshape(-1, e.values.shape[1]))
+            g += 1
+        return w
+    finally:
+        L.synth_welded_free(h)
+
+
+def encode_mesh_points(pos, faces, normals=None, uvs=None, generic=None, extra=None, opt=None):
+    """weld_points followed by the coder of encode_mesh_corners on the welded mesh (extra: Extras with one row per point).  What
+    dsa_encode_points_batch must write."""
+    L = lib()
+    pos, faces, nrm, uv, gen, extra, arr, opt = _points_args(pos, faces, normals, uvs, generic, extra, opt)
+    ptr = lambda a: None if a is None else a.ctypes.data          # noqa: E731
+    out, n = C.c_void_p(), C.c_size_t()
+    rc = L.synth_encode_points(ptr(pos), len(pos), ptr(faces), len(faces), ptr(nrm), ptr(uv), ptr(gen), arr, len(extra), C.byref(opt),
+                               C.byref(out), C.byref(n))
     if rc:
         raise RuntimeError(_err())
     data = C.string_at(out, n.value)

@@ -15,6 +15,8 @@
 //   PredictionSchemes/*Encoder.cs, *EncodingTransform.cs
 // (each with the defects listed there corrected to the bitstream's semantics).
 // -----------------------------------------------------------------------------
+#include <memory>
+
 #include "../csrc/dsa_encode_host.h"
 
 namespace synth {
@@ -267,6 +269,82 @@ int synth_encode_attributes(int edgebreaker, const float *pos, uint32_t nv, cons
       for (size_t k = 0; k < (size_t)nf * 3; ++k) synth::check(faces[k] < nv, "face index out of range");
       synth::encode_sequential(in, to_opt(opt), geometry == 1, compressed != 0, buf);
     }
+    *out = (uint8_t *)malloc(buf.size() ? buf.size() : 1);
+    memcpy(*out, buf.data(), buf.size());
+    *out_len = buf.size();
+    return 0;
+  } catch (const std::exception &e) { snprintf(g_err, sizeof(g_err), "%s", e.what()); return 1; }
+}
+// Per-point input (one row per point in every value array, `faces` index points; dsa_encode_host.h weld_points): the weld alone,
+// and the weld followed by the Edgebreaker coder.  The generic attribute: nv rows of opt->generic_components elements of
+// opt->generic_data_type.
+struct synth_welded { synth::Welded w; };
+static synth::MeshIn points_in(const float *pos, uint32_t np, const uint32_t *faces, uint32_t nf, const float *normals, const float *uvs, const void *generic,
+                               const synth_extra *extras, uint32_t num_extras, std::vector<synth::ExtraAttr> &ex) {
+  ex.resize(num_extras);
+  for (uint32_t k = 0; k < num_extras; ++k) {
+    ex[k].att_type = extras[k].attribute_type; ex[k].data_type = extras[k].data_type; ex[k].nc = extras[k].num_components;
+    ex[k].normalized = extras[k].normalized; ex[k].unique_id = extras[k].unique_id; ex[k].bits = extras[k].quantization_bits;
+    ex[k].values = extras[k].values;
+  }
+  synth::MeshIn in{pos, np, faces, nf, normals, uvs, generic};
+  in.extras = ex.data(); in.num_extras = num_extras;
+  const std::string why = synth::extras_error(in);
+  synth::check(why.empty(), why.c_str());
+  return in;
+}
+static size_t generic_row_bytes(const synth::Options &o) {
+  synth::check(o.generic_components >= 1 && o.generic_components <= 4, "generic attribute needs 1 - 4 components");
+  return synth::data_type_size(o.generic_data_type) * (size_t)o.generic_components;
+}
+synth_welded *synth_weld_points(const float *pos, uint32_t np, const uint32_t *faces, uint32_t nf, const float *normals, const float *uvs,
+                                const void *generic, const synth_extra *extras, uint32_t num_extras, const synth_options *opt) {
+  try {
+    std::vector<synth::ExtraAttr> ex;
+    const synth::MeshIn in = points_in(pos, np, faces, nf, normals, uvs, generic, extras, num_extras, ex);
+    std::unique_ptr<synth_welded> h(new synth_welded());
+    synth::weld_points(np, faces, nf, synth::weld_vertex_key(in, generic ? generic_row_bytes(to_opt(opt)) : 0), normals, uvs, h->w);
+    return h.release();
+  } catch (const std::exception &e) { snprintf(g_err, sizeof(g_err), "%s", e.what()); return nullptr; }
+}
+// counts: P, F, V, N, T, normals per vertex, texcoords per vertex, segments of the vertex key
+void synth_welded_counts(const synth_welded *h, uint32_t counts[8]) {
+  const synth::Welded &w = h->w;
+  const uint32_t c[8] = {w.P, w.F, w.vertex.count, w.normal.count, w.texcoord.count, w.normals_per_vertex ? 1u : 0u, w.texcoords_per_vertex ? 1u : 0u, (uint32_t)w.vertex_rows.size()};
+  memcpy(counts, c, sizeof(c));
+}
+// which: 0 vertex_of_point, 1 vertex_point, 2 normal_of_point, 3 normal_point, 4 texcoord_of_point, 5 texcoord_point, 6 faces,
+// 7 normal_corners, 8 texcoord_corners, 9 normal rows, 10 texcoord rows, 16 + g: rows of segment g of the vertex key
+int synth_welded_array(const synth_welded *h, uint32_t which, const void **data, size_t *bytes) {
+  const synth::Welded &w = h->w;
+  auto u32 = [&](const std::vector<uint32_t> &v) { *data = v.data(); *bytes = 4 * v.size(); return 0; };
+  auto u8 = [&](const std::vector<uint8_t> &v) { *data = v.data(); *bytes = v.size(); return 0; };
+  switch (which) {
+    case 0: return u32(w.vertex.of_point); case 1: return u32(w.vertex.point);
+    case 2: return u32(w.normal.of_point); case 3: return u32(w.normal.point);
+    case 4: return u32(w.texcoord.of_point); case 5: return u32(w.texcoord.point);
+    case 6: return u32(w.faces); case 7: return u32(w.normal_corners); case 8: return u32(w.texcoord_corners);
+    case 9: return u8(w.normal_rows); case 10: return u8(w.texcoord_rows);
+    default: break;
+  }
+  if (which >= 16 && which - 16 < w.vertex_rows.size()) return u8(w.vertex_rows[which - 16]);
+  return 1;
+}
+void synth_welded_free(synth_welded *h) { delete h; }
+int synth_encode_points(const float *pos, uint32_t np, const uint32_t *faces, uint32_t nf, const float *normals, const float *uvs, const void *generic,
+                        const synth_extra *extras, uint32_t num_extras, const synth_options *opt, uint8_t **out, size_t *out_len) {
+  try {
+    std::vector<synth::ExtraAttr> ex, ex2;
+    const synth::MeshIn in = points_in(pos, np, faces, nf, normals, uvs, generic, extras, num_extras, ex);
+    const synth::Options o = to_opt(opt);
+    synth::Welded w;
+    synth::weld_points(np, faces, nf, synth::weld_vertex_key(in, generic ? generic_row_bytes(o) : 0), normals, uvs, w);
+    const synth::MeshIn m = synth::welded_mesh_in(in, w, ex2);
+    // (what the library's host checks say of a mesh the coder itself would not survive)
+    synth::check(!(o.repair_topology && pos && np >= 3 && nf == 0), "all triangles are degenerate");
+    synth::check(m.pos && m.faces && m.nv >= 3 && m.nf >= 1, "mesh needs positions and faces");
+    std::vector<uint8_t> buf;
+    synth::encode_mesh(m, o, buf);
     *out = (uint8_t *)malloc(buf.size() ? buf.size() : 1);
     memcpy(*out, buf.data(), buf.size());
     *out_len = buf.size();

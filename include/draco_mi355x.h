@@ -491,6 +491,46 @@ typedef struct dsa_encode_repair_options {
 void dsa_encode_default_repair_options(dsa_encode_repair_options *options);
 dsa_status dsa_encode_repair_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes,
                                    const dsa_encode_repair_options *options, dsa_encoded **out);
+/* Meshes given as one row per point -- a glTF primitive, an OBJ after triangulation, the output of dsa_batch_vertex_arrays: a
+ * point is duplicated wherever a UV chart or a hard edge passes.  `meshes` is read as: mesh.mesh.num_vertices points, every value
+ * array (positions, normals, texcoords, generic, every attribute of the list) with one row per point, faces over points;
+ * normal_corners / texcoord_corners NULL.  The weld in front of the coder (dsa_encode_weld.h on the device; DSA_ENC_HOST_WELD,
+ * batches below 256 meshes: the host threads):
+ *   - a point is used when a face names it; a face index >= num_vertices fails the mesh (DSA_ERR_INVALID_DATA, "face index out
+ *     of range") before anything is read through the faces;
+ *   - two used points are one vertex when their position rows, their mesh.generic rows and their rows in every attribute of the
+ *     list are equal byte for byte (floats as bit patterns: -0.0 is not +0.0, a NaN equals the NaN of the same payload);
+ *   - the representative of a vertex is its used point of smallest index; vertices are numbered by ascending representative;
+ *   - normals and texture coordinates are welded the same way, each alone, and go to the coder as rows with ids per corner --
+ *     unless no vertex has two of them: then as one row per vertex (the row of the vertex's representative), without ids.
+ * The welded mesh is coded as dsa_encode_repair_batch codes it, with the same options, and every per-mesh failure of that call
+ * stays (a face degenerate after the weld, a non-manifold edge or vertex under topology = 0, ids with single_connectivity = 1,
+ * seams over a table that needs repair: DSA_ERR_NOT_IMPLEMENTED).  A mesh with corner ids set fails alone with
+ * DSA_ERR_INVALID_ARGUMENT.  The streams are byte-identical to the CPU coder's on the welded mesh.  Added after ABI 4 without
+ * changing it: callers detect the feature by the symbol dsa_encode_points_batch. */
+dsa_status dsa_encode_points_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes,
+                                   const dsa_encode_repair_options *options, dsa_encoded **out);
+/* The weld alone: per mesh the maps between points and vertices / normal rows / texture coordinate rows, in host memory owned by
+ * the handle (valid until dsa_welded_free).  *_of_point[num_points]: the class of every point, 0xFFFFFFFF for a point no face
+ * names; *_point[count]: the representative point of every class -- what a caller carries further per-point data across the weld
+ * with (morph targets: row v of the welded array is row vertex_point[v] of the per-point one).  The normal / texcoord maps are
+ * NULL and their counts 0 when the mesh has no such attribute.  *_per_vertex: no vertex has two rows of the attribute (the
+ * coder then takes it per vertex). */
+typedef struct dsa_welded dsa_welded;
+typedef struct dsa_welded_info {
+  int32_t status;                        /* DSA_OK, or why the mesh could not be welded */
+  uint32_t num_points, num_vertices, num_normals, num_texcoords;
+  uint32_t normals_per_vertex, texcoords_per_vertex;
+  uint32_t reserved;                     /* zero */
+  const uint32_t *vertex_of_point, *vertex_point;
+  const uint32_t *normal_of_point, *normal_point;
+  const uint32_t *texcoord_of_point, *texcoord_point;
+} dsa_welded_info;                       /* 80 bytes */
+dsa_status dsa_weld_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, dsa_welded **out);
+uint32_t dsa_welded_size(const dsa_welded *welded);
+/* Fills `info` for mesh `mesh`; returns the mesh's status (a failed mesh: its status, dsa_last_error says why, the maps NULL). */
+dsa_status dsa_welded_mesh(const dsa_welded *welded, uint32_t mesh, dsa_welded_info *info);
+void dsa_welded_free(dsa_welded *welded);
 uint32_t dsa_encoded_size(const dsa_encoded *encoded);
 /* Bytes of stream `mesh` (owned by `encoded`, valid until dsa_encoded_free) or that mesh's failure status. */
 dsa_status dsa_encoded_stream(const dsa_encoded *encoded, uint32_t mesh, const uint8_t **bytes, size_t *length);
