@@ -45,6 +45,40 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
     /// point-to-value maps were never deduplicated (a glTF primitive or an OBJ loaded row by row).  Unset: nothing changes.</summary>
     public bool WeldPoints { get; set; }
 
+    // Quantisation grids (dsa_encode_grid_batch).  The reference's own options quantization_origin / quantization_range, set per
+    // attribute type for positions or texture coordinates, are honoured as explicit grids (SequentialQuantizationAttributeEncoder.cs:
+    // 19-23).  Groups, when set (one number per mesh of the batch), lets the meshes of one group share the grid of their positions:
+    // the tiles of a surface, the primitives of one glTF mesh.  Edgebreaker meshes; unset, the calls and their bytes are what they were.
+    public IReadOnlyList<uint> Groups { get; set; }
+
+    private static bool ExplicitGrid(Config config, GeometryAttributeType type, int components, ref DsaQuantizationGrid grid)
+    {
+        if (!config.IsAttributeOptionSet((int)type, ConfigOptionName.Attribute.QuantizationOrigin) || !config.IsAttributeOptionSet((int)type, ConfigOptionName.Attribute.QuantizationRange)) return false;
+        var origin = new List<float>(config.GetAttributeOptionValues<float>((int)type, ConfigOptionName.Attribute.QuantizationOrigin, components));
+        for (int c = 0; c < components && c < origin.Count; ++c) grid.Origin[c] = origin[c];
+        grid.Range = config.GetAttributeOption((int)type, ConfigOptionName.Attribute.QuantizationRange, 1.0f);
+        grid.Mode = 1;
+        return true;
+    }
+
+    // the grids of a batch, or null when no mesh has one
+    private DsaMeshGrids[] Grids(Config config, int count)
+    {
+        var probe = new DsaQuantizationGrid();
+        bool pos = ExplicitGrid(config, GeometryAttributeType.Position, 3, ref probe), uv = ExplicitGrid(config, GeometryAttributeType.TexCoord, 2, ref probe);
+        if (!pos && !uv && Groups == null) return null;
+        if (Groups != null && Groups.Count != count) throw new ArgumentException("Groups: one number per mesh of the batch");
+        var grids = new DsaMeshGrids[count];
+        for (int i = 0; i < count; ++i)
+        {
+            if (pos) ExplicitGrid(config, GeometryAttributeType.Position, 3, ref grids[i].Position);
+            else if (Groups != null) grids[i].Position.Mode = 2;
+            if (uv) ExplicitGrid(config, GeometryAttributeType.TexCoord, 2, ref grids[i].Texcoord);
+            grids[i].Group = Groups != null ? Groups[i] : 0;
+        }
+        return grids;
+    }
+
     public GpuDracoEncoder(int device = 0)
     {
         NativeMethods.Check(NativeMethods.dsa_context_create(device, IntPtr.Zero, out _ctx), IntPtr.Zero, "dsa_context_create");
@@ -188,13 +222,25 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
                 wp.Level.MultiParallelogram = multi;
                 wp.Level.TraversalMethod = traversal;
                 wp.Topology = RepairTopology ? 1 : 0;
+                var wg = Grids(config, meshes.Count);
+                if (wg != null)
+                {
+                    for (int i = 0; i < meshes.Count; ++i) if (pin[i].Mesh.Mesh.Texcoords == null) wg[i].Texcoord = default;
+                    NativeMethods.dsa_encode_default_grid_options(out var go);
+                    go.Repair = wp;
+                    go.WeldPoints = 1;
+                    fixed (DsaMeshAttrInput* p = pin) fixed (DsaMeshGrids* g = wg)
+                        NativeMethods.Check(NativeMethods.dsa_encode_grid_batch(_ctx, (uint)meshes.Count, p, g, in go, out encoded), _ctx, "dsa_encode_grid_batch");
+                    return Streams(encoded, meshes.Count);
+                }
                 fixed (DsaMeshAttrInput* p = pin)
                     NativeMethods.Check(NativeMethods.dsa_encode_points_batch(_ctx, (uint)meshes.Count, p, in wp, out encoded), _ctx, "dsa_encode_points_batch");
                 return Streams(encoded, meshes.Count);
             }
             bool anyCorners = false, anyExtras = false;
             foreach (var m in meshes) { anyCorners = anyCorners || NeedsCornerForm(m); anyExtras = anyExtras || ExtraAttributes(m).Count > 0; }
-            if (anyExtras || multi != 0 || traversal != 0 || RepairTopology)
+            var grids = Grids(config, meshes.Count);
+            if (anyExtras || multi != 0 || traversal != 0 || RepairTopology || grids != null)
             {
                 // the attribute list rides on the corner form (extras per vertex: the value of the last point of each position value)
                 var ain = new DsaMeshAttrInput[meshes.Count];
@@ -207,6 +253,18 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
                 ax.Base = opt;
                 ax.EdgebreakerMethod = ebMethod != unset ? ebMethod : 0;
                 ax.NormalPrediction = normalScheme != unset ? normalScheme : 0;
+                if (grids != null)
+                {
+                    for (int i = 0; i < meshes.Count; ++i) if (ain[i].Mesh.Mesh.Texcoords == null) grids[i].Texcoord = default;
+                    NativeMethods.dsa_encode_default_grid_options(out var go);
+                    go.Repair.Level.Ex = ax;
+                    go.Repair.Level.MultiParallelogram = multi;
+                    go.Repair.Level.TraversalMethod = traversal;
+                    go.Repair.Topology = RepairTopology ? 1 : 0;
+                    fixed (DsaMeshAttrInput* p = ain) fixed (DsaMeshGrids* g = grids)
+                        NativeMethods.Check(NativeMethods.dsa_encode_grid_batch(_ctx, (uint)meshes.Count, p, g, in go, out encoded), _ctx, "dsa_encode_grid_batch");
+                    return Streams(encoded, meshes.Count);
+                }
                 if (multi != 0 || traversal != 0 || RepairTopology)
                 {
                     NativeMethods.dsa_encode_default_level_options(out var lv);

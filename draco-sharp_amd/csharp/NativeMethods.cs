@@ -147,6 +147,35 @@ internal unsafe struct DsaEncodeRepairOptions
     public fixed int Reserved[7];   // zero
 }
 
+// dsa_quantization_grid: the grid of one quantised attribute (32 bytes)
+[StructLayout(LayoutKind.Sequential)]
+internal unsafe struct DsaQuantizationGrid
+{
+    public fixed float Origin[4];
+    public float Range;
+    public int Mode;                // 0 own bounds, 1 explicit (quantization_origin / quantization_range), 2 shared within Group
+    public fixed uint Reserved[2];  // zero
+}
+
+// dsa_mesh_grids: the grids of one mesh, parallel to DsaMeshAttrInput (80 bytes)
+[StructLayout(LayoutKind.Sequential)]
+internal unsafe struct DsaMeshGrids
+{
+    public DsaQuantizationGrid Position, Texcoord;
+    public DsaQuantizationGrid* Attributes;     // NumAttributes entries or null
+    public uint Group;
+    public uint Reserved;           // zero
+}
+
+// dsa_encode_grid_options (dsa_encode_grid_batch)
+[StructLayout(LayoutKind.Sequential)]
+internal unsafe struct DsaEncodeGridOptions
+{
+    public DsaEncodeRepairOptions Repair;
+    public int WeldPoints;          // 1: one row per point, as dsa_encode_points_batch
+    public fixed int Reserved[7];   // zero
+}
+
 // dsa_encode_sequential_options (dsa_encode_sequential_batch): sequential meshes and point clouds
 [StructLayout(LayoutKind.Sequential)]
 internal unsafe struct DsaEncodeSequentialOptions
@@ -268,6 +297,9 @@ internal static unsafe partial class NativeMethods
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_repair_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, in DsaEncodeRepairOptions options, out IntPtr encoded);
     // meshes given as one row per point: the weld in front of dsa_encode_repair_batch, and the weld alone (detect by symbol)
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_points_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, in DsaEncodeRepairOptions options, out IntPtr encoded);
+    [DllImport(Lib)] internal static extern void dsa_encode_default_grid_options(out DsaEncodeGridOptions options);
+    [DllImport(Lib)] internal static extern DsaStatus dsa_encode_grid_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, in DsaEncodeGridOptions options, out IntPtr encoded);
+    [DllImport(Lib)] internal static extern DsaStatus dsa_encode_grid_sequential_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, in DsaEncodeSequentialOptions options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern DsaStatus dsa_weld_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, out IntPtr welded);
     [DllImport(Lib)] internal static extern uint dsa_welded_size(IntPtr welded);
     [DllImport(Lib)] internal static extern DsaStatus dsa_welded_mesh(IntPtr welded, uint mesh, out DsaWeldedInfo info);

@@ -10,6 +10,7 @@
 //   GPU   (dsa_encode_conn.h)  k_enc_connectivity corner table, Edgebreaker symbols, depth-first attribute order, parallelogram
 //                                                 operand entries, one wave per mesh (DSA_ENC_HOST_CONN=1: by the host coder)
 //   GPU   (dsa_encode_repair.h) k_enc_repair_*   dsa_encode_repair_batch: the reference's corner table for the meshes the kernels above refuse
+//   GPU   (dsa_encode_grid.h)  k_enc_grid_*      dsa_encode_grid_batch: grids shared by a group reduced in front of the chunks; attributes on a given grid quantised and checked
 //   GPU   (this file)          k_enc_bounds      quantisation range per attribute   AttributeQuantizationTransform.cs:66-108
 //                              k_enc_quantize    floats -> portable ints, normals -> octahedral (s,t), typed integers -> int32   :136-177, OctahedronToolBox.cs:28-119
 //                              k_enc_gather      vertex order -> traversal order, wrap bounds           PredictionSchemeWrapTransform.cs:88-100
@@ -41,12 +42,16 @@ static const char *const ENC_RAW_BEYOND_MESSAGE = "symbol_scheme 1 (raw) forced 
 __device__ __forceinline__ uint32_t enc_msb(uint32_t v) { return 31u - (uint32_t)__builtin_clz(v); }
 __device__ __forceinline__ uint32_t enc_zigzag(int32_t v) { return v >= 0 ? (uint32_t)v << 1 : (((uint32_t)(-(v + 1))) << 1) | 1u; }
 
-// Quantisation range: per-component min / max, range = largest extent (1 if degenerate).
+// Quantisation range: per-component min / max, range = largest extent (1 if degenerate).  GRID: the chunk has streams on a grid
+// that is not their own bounds (EncStream::grid_mode; dsa_encode_grid.h) -- their records hold it already, and
+// k_enc_grid_quantize quantises them; a chunk without such streams launches <false>, the kernel it always ran.
+template <bool GRID>
 __global__ __launch_bounds__(256) void k_enc_bounds(uint8_t *arena, EncStream *streams, uint32_t ns) {
   const uint32_t si = blockIdx.x;
   if (si >= ns) return;
   EncStream &S = streams[si];
   if (S.kind != 0) return;
+  if (GRID && S.grid_mode != 0) return;
   __shared__ float s_mn[4][256], s_mx[4][256];
   const float *src = (const float *)(arena + S.src);
   const uint32_t nc = S.nc_out, tid = threadIdx.x;
@@ -97,10 +102,12 @@ __device__ void enc_oct_from_float(const float *in, int32_t bits, int32_t &s, in
   else if (t == 0 && s > center) s = center - (s - center);
 }
 
+template <bool GRID>      // (as for k_enc_bounds)
 __global__ __launch_bounds__(256) void k_enc_quantize(uint8_t *arena, EncStream *streams, uint32_t ns) {
   const uint32_t si = blockIdx.y;
   if (si >= ns) return;
   const EncStream &S = streams[si];
+  if (GRID && S.kind == 0 && S.grid_mode != 0) return;
   const float *src = (const float *)(arena + S.src);
   int32_t *vals = (int32_t *)(arena + S.vals);
   const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
@@ -1025,8 +1032,14 @@ static dsa_status enc_stage_attributes(dsa_context *ctx, EncLane &lane, EncChunk
   dsa::EncConn *d_conns = ck.d_conns;
   dsa::EncSeam *d_seams = ck.d_seams;
   const uint32_t gx = std::max(1u, std::min(64u, (L.max_rows + 2047) / 2048));
-  hipLaunchKernelGGL(dsa::k_enc_bounds, dim3(ns), dim3(256), 0, st, arena, d_streams, ns);
-  hipLaunchKernelGGL(dsa::k_enc_quantize, dim3(gx, ns), dim3(256), 0, st, arena, d_streams, ns);
+  if (!L.any_grid) {
+    hipLaunchKernelGGL(dsa::k_enc_bounds<false>, dim3(ns), dim3(256), 0, st, arena, d_streams, ns);
+    hipLaunchKernelGGL(dsa::k_enc_quantize<false>, dim3(gx, ns), dim3(256), 0, st, arena, d_streams, ns);
+  } else {                   // streams on a grid of the caller's or of their group: their bounds are given, their values are checked
+    hipLaunchKernelGGL(dsa::k_enc_bounds<true>, dim3(ns), dim3(256), 0, st, arena, d_streams, ns);
+    hipLaunchKernelGGL(dsa::k_enc_quantize<true>, dim3(gx, ns), dim3(256), 0, st, arena, d_streams, ns);
+    hipLaunchKernelGGL(dsa::k_enc_grid_quantize<dsa::EncStream>, dim3(gx, ns), dim3(256), 0, st, arena, d_streams, ns);
+  }
   if (device_conn) {
     const dim3 gt(std::max(1u, std::min(128u, (3u * L.maxf + 1023u) / 1024u)), n), gz(gt.x, nz);
     ENC_TRY(hipStreamWaitEvent(st, lane.walk_done, 0));
@@ -1134,12 +1147,31 @@ static dsa_status enc_stage_conn_results(dsa_context *ctx, EncLane &lane, EncChu
   }
   return DSA_OK;
 }
+// a stream on a grid with a value that is not finite or off the grid (k_enc_grid_quantize): its mesh is refused, in the host
+// coder's words, before anything is coded from it
+static void enc_grid_refusals(EncChunk &ck) {
+  if (!ck.L.any_grid) return;
+  for (uint32_t i = 0; i < ck.n; ++i) {
+    if (!ck.good(i)) continue;
+    const uint32_t s0 = ck.L.first_stream[i];
+    for (size_t k = 0; k < ck.plans[i].atts.size(); ++k) {
+      const dsa::EncStream &S = ck.L.streams[s0 + k];
+      if (S.kind != 0 || S.grid_mode == 0 || (S.grid_nonfinite == dsa::ENC_GRID_NO_ROW && S.grid_off == dsa::ENC_GRID_NO_ROW)) continue;
+      const synth::PortableAttr &a = ck.plans[i].atts[k];
+      const bool finite = S.grid_nonfinite == dsa::ENC_GRID_NO_ROW;
+      ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, synth::grid_row_message(synth::grid_slot_name(a.att_type, a.extra_index), finite ? S.grid_off : S.grid_nonfinite, finite));
+      for (uint32_t s = s0; s < ck.L.first_stream[i + 1]; ++s) ck.L.streams[s].overflow = 1;
+      break;
+    }
+  }
+}
 // host phase 2 and device phase 2, shared with encode_sequential_chunk: scheme choice and rANS tables from the device statistics
 // (by the host, or what k_enc_plan said), then the entropy coding and its downloads; `lap`, when given, between the two
 static dsa_status enc_stage_code(dsa_context *ctx, EncLane &lane, EncChunk &ck, EncLap *lap) {
   const uint32_t ns = (uint32_t)ck.L.streams.size();
   ck.splans.resize(ns); ck.stream_mesh.assign(ns, 0);
   for (uint32_t i = 0; i < ck.n; ++i) for (uint32_t s = ck.L.first_stream[i]; s < ck.L.first_stream[i + 1]; ++s) ck.stream_mesh[s] = (int)i;
+  enc_grid_refusals(ck);
   if (ck.host_plan) ENC_STAGE(enc_host_plans(ctx, lane, ck));
   else enc_device_plan_errors(ck);
   if (lap) (*lap)("histograms + symbol plans");
@@ -1266,6 +1298,24 @@ static dsa_status enc_check_request(dsa_context *ctx, const EncRequest &rq) {
   return DSA_OK;
 }
 
+// the context's lanes, `lanes` of them at least (kept between calls)
+static dsa_status enc_ensure_lanes(dsa_context *ctx, uint32_t lanes) {
+  while (ctx->enc_lanes.size() < lanes) {
+    std::unique_ptr<EncLane> l(new EncLane());
+    l->device = ctx->device;
+    int least = 0, greatest = 0;
+    (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
+    HIP_TRY(ctx, hipStreamCreateWithFlags(&l->st, hipStreamNonBlocking));
+    // (a priority has its own few hardware queues: the walk streams are dealt over two, so that four walks run side by side)
+    HIP_TRY(ctx, hipStreamCreateWithPriority(&l->walk_st, hipStreamNonBlocking, (ctx->enc_lanes.size() & 1) ? greatest : least));
+    HIP_TRY(ctx, hipEventCreateWithFlags(&l->tables_done, hipEventDisableTiming));
+    HIP_TRY(ctx, hipEventCreateWithFlags(&l->walk_done, hipEventDisableTiming));
+    HIP_TRY(ctx, hipEventCreateWithFlags(&l->seams_done, hipEventDisableTiming));
+    ctx->enc_lanes.push_back(std::move(l));
+  }
+  return DSA_OK;
+}
+
 // A batch is coded in chunks, several of them in flight (each on a lane of its own: stream + pinned staging + device memory).  The
 // device stages of a chunk are bound by latency -- the walks of k_enc_connectivity take a memory round trip per step, 0.1 - 0.2 s
 // whatever the number of meshes -- so the more chunks are under way the better: the uploads of the chunks go over the link one
@@ -1288,19 +1338,7 @@ static dsa_status encode_batch_chunks(dsa_context *ctx, uint32_t n, ChunkFn &&co
   // slow, 376 - 426 against 370 - 383 since); it helps 8192 meshes (605 against 680 ms) and costs 2048 (296 against 235).)
   std::vector<uint32_t> bounds(chunks + 1, 0);
   for (uint32_t c = 0; c <= chunks; ++c) bounds[c] = (uint32_t)std::min<uint64_t>(n, (uint64_t)c * chunk);
-  while (ctx->enc_lanes.size() < lanes) {
-    std::unique_ptr<EncLane> l(new EncLane());
-    l->device = ctx->device;
-    int least = 0, greatest = 0;
-    (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-    HIP_TRY(ctx, hipStreamCreateWithFlags(&l->st, hipStreamNonBlocking));
-    // (a priority has its own few hardware queues: the walk streams are dealt over two, so that four walks run side by side)
-    HIP_TRY(ctx, hipStreamCreateWithPriority(&l->walk_st, hipStreamNonBlocking, (ctx->enc_lanes.size() & 1) ? greatest : least));
-    HIP_TRY(ctx, hipEventCreateWithFlags(&l->tables_done, hipEventDisableTiming));
-    HIP_TRY(ctx, hipEventCreateWithFlags(&l->walk_done, hipEventDisableTiming));
-    HIP_TRY(ctx, hipEventCreateWithFlags(&l->seams_done, hipEventDisableTiming));
-    ctx->enc_lanes.push_back(std::move(l));
-  }
+  ENC_STAGE(enc_ensure_lanes(ctx, lanes));
   hostutil::UploadTurns upload_turn(chunks);
   for (uint32_t l = 0; l < lanes; ++l) ctx->enc_lanes[l]->upload_turn = &upload_turn;
   struct Unhook { dsa_context *c; ~Unhook() { for (auto &l : c->enc_lanes) l->upload_turn = nullptr; } } unhook{ctx};
@@ -1344,6 +1382,96 @@ static dsa_status encode_batch_chunks(dsa_context *ctx, uint32_t n, ChunkFn &&co
   }
   if (getenv("DSA_ENC_TIMING")) fprintf(stderr, "[dsa_encode_batch] batch of %u done\n", n);
   *out = E.release();
+  return DSA_OK;
+}
+
+
+// ---- shared grids (mode 2 of dsa_quantization_grid; dsa_encode_grid.h), once per request and in front of its chunks: a group may
+// span chunks and both passes of a repair request, and its grid must depend on the inputs alone.  Every (mesh, slot) of mode 2
+// whose attribute is there and quantised is an item; the items of one group number, slot and component count lie side by side
+// and are one group.  Their values go up through the staged upload of lane 0 in pieces of at most 256 MiB (they travel again
+// with the chunk that codes them: nothing of a chunk's arena exists yet), k_enc_grid_bounds takes every piece, k_enc_grid_fold
+// all groups at the end; the grids come back and every member's slot becomes mode 1 with its group's grid.
+static dsa_status enc_stage_grids(dsa_context *ctx, const EncRequest &rq, std::vector<EncMeshGrids> &grids) {
+  struct Member { uint32_t mesh, slot, nc, rows; const void *src; };
+  std::vector<Member> members;
+  for (uint32_t i = 0; i < rq.n; ++i) {
+    EncMeshGrids &g = grids[i];
+    if (g.error) continue;
+    const dsa_mesh_attr_input &am = rq.listed[i];
+    const dsa_mesh_input &m = am.mesh.mesh;
+    auto shared = [](const synth::Grid &x) { return x.mode == 2 && x.reserved[0] == 0 && x.reserved[1] == 0; };
+    auto take = [&](uint32_t slot, uint32_t nc, uint32_t rows, const void *src) {
+      if (!src || rows == 0) return;                          // (the mesh is refused for what is missing)
+      if (rows > (1u << 28)) { g.error = "mesh too large for a shared grid"; return; }
+      members.push_back({i, slot, nc, rows, src});
+    };
+    if (shared(g.slot[0])) take(0, 3, m.num_vertices, m.positions);
+    if (shared(g.slot[1]) && m.texcoords) take(1, 2, (am.mesh.texcoord_corners && !rq.weld && !rq.sequential) ? am.mesh.num_texcoords : m.num_vertices, m.texcoords);
+    for (uint32_t k = 0; k < am.num_attributes && k < synth::kMaxAttributes && am.attributes; ++k) {
+      const dsa_attribute_input &x = am.attributes[k];
+      if (shared(g.slot[2 + k]) && x.data_type == 9 && x.num_components >= 1 && x.num_components <= 4) take(2 + k, x.num_components, m.num_vertices, x.values);
+    }
+  }
+  if (members.empty()) return DSA_OK;
+  std::stable_sort(members.begin(), members.end(), [&](const Member &a, const Member &b) {
+    const uint32_t ga = grids[a.mesh].group, gb = grids[b.mesh].group;
+    return ga != gb ? ga < gb : (a.slot != b.slot ? a.slot < b.slot : a.nc < b.nc);
+  });
+  const uint32_t ni = (uint32_t)members.size();
+  std::vector<dsa::EncGridItem> items(ni);
+  std::vector<dsa::EncGridGroup> groups;
+  for (uint32_t k = 0; k < ni; ++k) {
+    const Member &b = members[k];
+    dsa::EncGridItem &I = items[k];
+    memset(&I, 0, sizeof(I));
+    I.rows = b.rows; I.nc = b.nc;
+    for (int c = 0; c < 4; ++c) I.mn[c] = 0xFFFFFFFFu;
+    const bool opens = k == 0 || grids[members[k - 1].mesh].group != grids[b.mesh].group || members[k - 1].slot != b.slot || members[k - 1].nc != b.nc;
+    if (opens) { dsa::EncGridGroup G; memset(&G, 0, sizeof(G)); G.first = k; G.nc = b.nc; groups.push_back(G); }
+    ++groups.back().count;
+  }
+  const uint32_t ng = (uint32_t)groups.size();
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ENC_STAGE(enc_ensure_lanes(ctx, 1));
+  EncLane &lane = *ctx->enc_lanes[0];
+  hipStream_t st = lane.st;
+  ENC_TRY(lane.items.ensure(sizeof(dsa::EncGridItem) * ni));
+  ENC_TRY(lane.packed.ensure(sizeof(dsa::EncGridGroup) * ng));
+  dsa::EncGridItem *d_items = (dsa::EncGridItem *)lane.items.p;
+  dsa::EncGridGroup *d_groups = (dsa::EncGridGroup *)lane.packed.p;
+  const uint64_t piece_cap = 256ull << 20;
+  const uint32_t piece_items = 32768;
+  for (uint32_t k0 = 0; k0 < ni;) {
+    EncArena A;
+    std::vector<EncUpload> ups;
+    uint32_t k1 = k0, most = 1;
+    while (k1 < ni && k1 - k0 < piece_items && (k1 == k0 || A.cur < piece_cap)) {
+      const Member &b = members[k1];
+      items[k1].src = A.put(ups, b.src, 4ull * b.rows * b.nc, false);
+      most = std::max(most, b.rows);
+      ++k1;
+    }
+    ENC_TRY(lane.arena.ensure(A.cur ? A.cur : 256));
+    ENC_TRY(enc_upload(lane, (uint8_t *)lane.arena.p, st, ups));
+    ENC_TRY(hipMemcpyAsync(d_items + k0, items.data() + k0, sizeof(dsa::EncGridItem) * (k1 - k0), hipMemcpyHostToDevice, st));
+    const uint32_t gx = std::max(1u, std::min(64u, (most + 2047u) / 2048u));
+    hipLaunchKernelGGL(dsa::k_enc_grid_bounds, dim3(gx, k1 - k0), dim3(256), 0, st, (const uint8_t *)lane.arena.p, d_items + k0, k1 - k0);
+    ENC_TRY(hipGetLastError());
+    ENC_TRY(hipStreamSynchronize(st));                       // (items and the arena are the next piece's)
+    k0 = k1;
+  }
+  ENC_TRY(hipMemcpyAsync(d_groups, groups.data(), sizeof(dsa::EncGridGroup) * ng, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(dsa::k_enc_grid_fold, dim3((ng + WAVE - 1) / WAVE), dim3(WAVE), 0, st, (const dsa::EncGridItem *)d_items, d_groups, ng);
+  ENC_TRY(hipGetLastError());
+  ENC_TRY(hipMemcpyAsync(groups.data(), d_groups, sizeof(dsa::EncGridGroup) * ng, hipMemcpyDeviceToHost, st));
+  ENC_TRY(hipStreamSynchronize(st));
+  for (const dsa::EncGridGroup &G : groups)
+    for (uint32_t k = G.first; k < G.first + G.count; ++k) {
+      synth::Grid &x = grids[members[k].mesh].slot[members[k].slot];
+      memcpy(x.origin, G.origin, sizeof(x.origin));
+      x.range = G.range; x.mode = 1;
+    }
   return DSA_OK;
 }
 
@@ -1410,15 +1538,16 @@ static dsa_status encode_repair_request(dsa_context *ctx, const EncRequest &requ
   try {
     std::vector<uint32_t> again;
     std::vector<dsa_mesh_attr_input> sub;
+    std::vector<EncMeshGrids> sub_grids;
     for (uint32_t i = 0; i < rq.n; ++i) {
       if (E->status[i] != DSA_ERR_INVALID_DATA) continue;
       const dsa_mesh_input &m = rq.mesh(i);
       if (m.positions && m.num_vertices >= 3 && m.num_faces == 0 && E->messages[i] == "mesh needs positions and faces") { E->messages[i] = "all triangles are degenerate"; continue; }
-      if (enc_topology_refusal(E->messages[i])) { again.push_back(i); sub.push_back(rq.listed[i]); }
+      if (enc_topology_refusal(E->messages[i])) { again.push_back(i); sub.push_back(rq.listed[i]); if (rq.grids) sub_grids.push_back(rq.grids[i]); }
     }
     if (!again.empty()) {
       EncRequest r2 = rq;
-      r2.repair_scan = false; r2.repair = true; r2.n = (uint32_t)again.size(); r2.listed = sub.data();
+      r2.repair_scan = false; r2.repair = true; r2.n = (uint32_t)again.size(); r2.listed = sub.data(); r2.grids = rq.grids ? sub_grids.data() : nullptr;
       dsa_encoded *second = nullptr;
       const dsa_status s2 = encode_request(ctx, r2, &second, rq.n);
       if (s2 != DSA_OK) return s2;
@@ -1507,6 +1636,60 @@ static dsa_status encode_points_batch(dsa_context *ctx, uint32_t n, const dsa_me
 }
 dsa_status dsa_encode_points_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_encode_repair_options *options, dsa_encoded **out) {
   DSA_GUARD(ctx, encode_points_batch(ctx, n, meshes, options, out));
+}
+
+// ---- quantisation grids given by the caller or shared within a group (dsa_encode_grid.h): the calls above with a grid per float
+// attribute.  The caller's grids are copied, the shared ones resolved once for the whole request (enc_stage_grids), and the
+// request goes the way it always went; without a grid that is not mode 0 it is the very request of the call it stands for.
+static dsa_status encode_grid_request(dsa_context *ctx, EncRequest &rq, const dsa_mesh_grids *grids, int32_t topology, dsa_encoded **out) {
+  if (!ctx || !out || (rq.n && !rq.listed)) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "null argument");
+  std::vector<EncMeshGrids> taken;
+  if (grids && rq.n) {
+    taken.resize(rq.n);
+    bool any = false;
+    for (uint32_t i = 0; i < rq.n; ++i) {
+      taken[i] = enc_take_grids(grids[i], rq.listed[i].num_attributes);
+      any = any || taken[i].error != nullptr;
+      for (const synth::Grid &g : taken[i].slot) any = any || g.mode != 0 || g.reserved[0] != 0 || g.reserved[1] != 0;
+    }
+    if (any) {
+      if (enc_check_request(ctx, rq) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+      ENC_STAGE(enc_stage_grids(ctx, rq, taken));
+      rq.grids = taken.data();
+    }
+  }
+  return topology == 1 ? encode_repair_request(ctx, rq, out) : encode_request(ctx, rq, out);
+}
+void dsa_encode_default_grid_options(dsa_encode_grid_options *o) {
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  dsa_encode_default_repair_options(&o->repair);
+}
+static dsa_status encode_grid_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_grid_options *options, dsa_encoded **out) {
+  EncRequest rq = enc_request(n, false);
+  rq.listed = meshes;
+  int32_t topology = 0;
+  if (options) {
+    if (options->weld_points != 0 && options->weld_points != 1)
+      return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "weld_points %d: 0 (rows per vertex) or 1 (rows per point)", (int)options->weld_points);
+    for (int k = 0; k < 7; ++k)
+      if (options->reserved[k] != 0) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "dsa_encode_grid_options.reserved[%d] is not zero", k);
+    if (enc_repair_options_into(ctx, &options->repair, rq, topology) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+    rq.weld = options->weld_points == 1;
+  }
+  return encode_grid_request(ctx, rq, grids, topology, out);
+}
+dsa_status dsa_encode_grid_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_grid_options *options, dsa_encoded **out) {
+  DSA_GUARD(ctx, encode_grid_batch(ctx, n, meshes, grids, options, out));
+}
+static dsa_status encode_grid_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_sequential_options *options, dsa_encoded **out) {
+  EncRequest rq = enc_request(n, true);
+  rq.listed = meshes;
+  if (options) rq.seq = *options;
+  return encode_grid_request(ctx, rq, grids, 0, out);
+}
+dsa_status dsa_encode_grid_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_sequential_options *options, dsa_encoded **out) {
+  DSA_GUARD(ctx, encode_grid_sequential_batch(ctx, n, meshes, grids, options, out));
 }
 struct dsa_welded {
   dsa_context *ctx = nullptr;

@@ -932,6 +932,70 @@ struct Octa {
   int make_positive(int x) const { return x < 0 ? x + max_q : x; }
 };
 
+// A quantisation grid given by the caller (the layout of dsa_quantization_grid): mode 0 the attribute's own bounds, 1 explicit
+// (origin per component, one range), 2 shared by the meshes of a group -- which whoever holds the batch resolves to mode 1
+// (shared_grid below); the coder of one mesh takes 0 and 1.
+struct Grid { float origin[4]; float range; int32_t mode; uint32_t reserved[2]; };
+static inline bool f32_finite(float f) { uint32_t u; memcpy(&u, &f, 4); return (u & 0x7F800000u) != 0x7F800000u; }
+// the attribute slots a grid can name, as the messages call them
+static inline std::string grid_slot_name(int att_type, int extra) {
+  if (extra >= 0) return "attribute " + std::to_string(extra);
+  return att_type == 0 ? "positions" : (att_type == 1 ? "normals" : (att_type == 3 ? "texcoords" : "generic"));
+}
+// Why grid `g` cannot shape an attribute of nc components ("" when it can); quantised: the attribute is one that has a grid.
+static std::string grid_error(const Grid &g, int nc, bool quantised, const std::string &name) {
+  char buf[160];
+  if (g.reserved[0] != 0 || g.reserved[1] != 0) return name + ": grid.reserved is not zero";
+  if (g.mode < 0 || g.mode > 2) { snprintf(buf, sizeof(buf), ": grid.mode %d: 0 (own bounds), 1 (explicit) or 2 (shared within the group)", (int)g.mode); return name + buf; }
+  if (g.mode != 0 && !quantised) { snprintf(buf, sizeof(buf), ": grid.mode %d on an attribute that is not quantised (normals and integer attributes have no grid)", (int)g.mode); return name + buf; }
+  if (g.mode != 1) return "";
+  if (!f32_finite(g.range) || !(g.range > 0.0f)) { snprintf(buf, sizeof(buf), ": grid.range %g: finite and above 0", (double)g.range); return name + buf; }
+  for (int c = 0; c < nc; ++c)
+    if (!f32_finite(g.origin[c])) { snprintf(buf, sizeof(buf), ": grid.origin[%d] is not finite", c); return name + buf; }
+  return "";
+}
+// the same for an attribute the mesh does not have: only mode 0 is legal
+static std::string grid_error_absent(const Grid &g, const std::string &name) {
+  Grid z = g;
+  z.mode = g.mode >= 1 && g.mode <= 2 ? 0 : g.mode;
+  const std::string why = grid_error(z, 0, true, name);
+  if (!why.empty() || g.mode == 0) return why;
+  return name + ": grid.mode " + std::to_string(g.mode) + " for an attribute the mesh does not have";
+}
+// The refusal of a mesh whose attribute does not fit its grid: the smallest row with a value that is not finite, else the
+// smallest row with a value whose integer lies outside 0 .. max_q.
+static inline std::string grid_row_message(const std::string &name, uint32_t row, bool finite) {
+  return name + ": row " + std::to_string(row) + (finite ? " lies off the quantisation grid" : " is not finite");
+}
+// -0.0 below +0.0, so that minima and maxima do not depend on the order they are taken in
+static inline uint32_t f32_order_key(float f) { uint32_t u; memcpy(&u, &f, 4); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
+static inline float f32_from_order_key(uint32_t k) { const uint32_t u = (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k; float f; memcpy(&f, &u, 4); return f; }
+// The grid of a group (mode 2): ComputeParameters over the union of `count` arrays of nc components -- minimum per component
+// over all rows of every array whose values are all finite, range the largest extent, 1 if that is 0.  False: no such array.
+static bool shared_grid(const float *const *arrays, const uint32_t *rows, uint32_t count, int nc, Grid &out) {
+  uint32_t mn[4] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, mx[4] = {0, 0, 0, 0};
+  bool any = false;
+  for (uint32_t k = 0; k < count; ++k) {
+    const size_t total = (size_t)rows[k] * nc;
+    bool finite = total > 0;
+    for (size_t i = 0; i < total && finite; ++i) finite = f32_finite(arrays[k][i]);
+    if (!finite) continue;
+    any = true;
+    for (size_t i = 0; i < total; ++i) { const uint32_t key = f32_order_key(arrays[k][i]); const int c = (int)(i % nc); if (key < mn[c]) mn[c] = key; if (key > mx[c]) mx[c] = key; }
+  }
+  memset(&out, 0, sizeof(out));
+  out.mode = 1; out.range = 1.0f;
+  if (!any) return false;
+  float range = 0.0f;
+  for (int c = 0; c < nc; ++c) {
+    out.origin[c] = f32_from_order_key(mn[c]);
+    volatile float d = f32_from_order_key(mx[c]) - out.origin[c];
+    if (d > range) range = d;
+  }
+  out.range = range == 0.0f ? 1.0f : range;
+  return true;
+}
+
 struct PortableAttr {
   int att_type, nc_out, nc;            // nc = portable components
   int seq_type;                        // 1 integer, 2 quantisation, 3 normals
@@ -943,10 +1007,41 @@ struct PortableAttr {
   int normalized = 0;                  // the descriptor's flag
   uint32_t unique_id = kInvalid;       // kInvalid: the attribute's index in the stream
   const void *extra_values = nullptr;  // an attribute of MeshIn::extras: its rows, nc elements of data_type each (else the built-in source)
+  const Grid *grid = nullptr;          // seq_type 2: the caller's grid (mode 1; null or mode 0: the attribute's own bounds)
+  int extra_index = -1;                // its index in MeshIn::extras (the messages name it)
 };
 
 // AttributeQuantizationTransform.cs:66-108,136-177 + Core/Quantizer.cs (E-1 corrected)
+// A grid of the caller's (a.grid, mode 1) takes the place of the bounds: the arithmetic is the same, and a value that is not
+// finite or whose integer leaves 0 .. max_q refuses the mesh (grid_row_message).
+static void quantize_on_grid(const float *src, uint32_t n, int nc, int bits, PortableAttr &a) {
+  const Grid &g = *a.grid;
+  const std::string name = grid_slot_name(a.att_type, a.extra_index);
+  const std::string why = grid_error(g, nc, true, name);
+  check(why.empty(), why.c_str());
+  check(g.mode == 1, (name + ": grid.mode 2 (shared) is resolved to an explicit grid by whoever holds the batch").c_str());
+  a.qmin.assign(g.origin, g.origin + nc);
+  a.qrange = g.range;
+  a.bits = bits;
+  const int32_t max_q = (1 << bits) - 1;
+  volatile float inv_delta = (float)max_q / a.qrange;
+  a.vals.assign((size_t)n * nc, 0);
+  uint32_t bad_finite = kInvalid, bad_off = kInvalid;
+  for (uint32_t i = 0; i < n; ++i)
+    for (int c = 0; c < nc; ++c) {
+      const float x = src[(size_t)i * nc + c];
+      if (!f32_finite(x)) { if (bad_finite == kInvalid) bad_finite = i; continue; }
+      volatile float v = x - a.qmin[c];
+      volatile float s = v * inv_delta;
+      const float f = std::floor(s + 0.5f);
+      if (!(f >= 0.0f && f <= (float)max_q)) { if (bad_off == kInvalid) bad_off = i; continue; }
+      a.vals[(size_t)i * nc + c] = (int32_t)f;
+    }
+  if (bad_finite != kInvalid) check(false, grid_row_message(name, bad_finite, false).c_str());
+  if (bad_off != kInvalid) check(false, grid_row_message(name, bad_off, true).c_str());
+}
 static void quantize(const float *src, uint32_t n, int nc, int bits, PortableAttr &a) {
+  if (a.grid && a.grid->mode != 0) return quantize_on_grid(src, n, nc, bits, a);
   a.qmin.assign(nc, 0);
   std::vector<float> mx(nc, 0);
   for (int c = 0; c < nc; ++c) { a.qmin[c] = src[c]; mx[c] = src[c]; }
@@ -1031,6 +1126,7 @@ struct ExtraAttr {
   uint32_t unique_id = kInvalid;     // kInvalid: the attribute's index in the stream
   int32_t bits = 0;                  // float32: 1..20; 0: uv_bits for a texture coordinate, else 8
   const void *values = nullptr;      // nv rows, packed
+  const Grid *grid = nullptr;        // float32: the caller's quantisation grid (null: its own bounds)
 };
 static const size_t kMaxAttributes = 16;   // DSA_MAX_ATTRIBUTES: what the decode direction takes
 static inline size_t data_type_size(int dt) { return (dt == 1 || dt == 2) ? 1 : ((dt == 3 || dt == 4) ? 2 : 4); }
@@ -1045,6 +1141,7 @@ struct MeshIn {
   const uint32_t *normal_corners = nullptr; uint32_t nn = 0;
   const uint32_t *uv_corners = nullptr; uint32_t nu = 0;
   const ExtraAttr *extras = nullptr; uint32_t num_extras = 0;      // written behind the attributes above, in list order
+  const Grid *pos_grid = nullptr, *uv_grid = nullptr;              // the caller's quantisation grids (null: the attribute's own bounds)
 };
 
 // Why the extras of a mesh cannot be written ("" when they can): the attribute's index in the list and the field.
@@ -1400,7 +1497,8 @@ static void plan_extra_attributes(const MeshIn &in, const Options &opt, int pred
     const ExtraAttr &x = in.extras[k];
     PortableAttr a;
     a.att_type = x.att_type; a.nc = a.nc_out = (int)x.nc; a.data_type = x.data_type; a.prediction = prediction;
-    a.unique_id = x.unique_id; a.extra_values = x.values;
+    a.unique_id = x.unique_id; a.extra_values = x.values; a.extra_index = (int)k;
+    if (x.grid) { const std::string why = grid_error(*x.grid, (int)x.nc, x.data_type == 9, grid_slot_name(x.att_type, (int)k)); check(why.empty(), why.c_str()); a.grid = x.grid; }
     if (x.data_type == 9) { a.seq_type = 2; a.bits = x.bits ? x.bits : (x.att_type == 3 ? opt.uv_bits : 8); }
     else { a.seq_type = 1; a.normalized = x.normalized; }
     atts.push_back(a);
@@ -1452,9 +1550,9 @@ struct MeshPlan {
 // What of a plan does not depend on the connectivity: attribute descriptors and the options that shape the stream.
 static void plan_attributes(const MeshIn &in, const Options &opt, MeshPlan &pl) {
   pl.atts.clear();
-  { PortableAttr a; a.att_type = 0; a.nc = a.nc_out = 3; a.seq_type = 2; a.data_type = 9; a.prediction = opt.pos_prediction; a.bits = opt.pos_bits; pl.atts.push_back(a); }
+  { PortableAttr a; a.att_type = 0; a.nc = a.nc_out = 3; a.seq_type = 2; a.data_type = 9; a.prediction = opt.pos_prediction; a.bits = opt.pos_bits; a.grid = in.pos_grid; pl.atts.push_back(a); }
   if (in.normals) { PortableAttr a; a.att_type = 1; a.nc_out = 3; a.nc = 2; a.seq_type = 3; a.data_type = 9; a.bits = opt.normal_bits; a.prediction = opt.normal_prediction == 6 ? 6 : 0; a.corner_value = in.normal_corners; pl.atts.push_back(a); }
-  if (in.uvs) { PortableAttr a; a.att_type = 3; a.nc = a.nc_out = 2; a.seq_type = 2; a.data_type = 9; a.prediction = opt.uv_prediction; a.bits = opt.uv_bits; a.corner_value = in.uv_corners; pl.atts.push_back(a); }
+  if (in.uvs) { PortableAttr a; a.att_type = 3; a.nc = a.nc_out = 2; a.seq_type = 2; a.data_type = 9; a.prediction = opt.uv_prediction; a.bits = opt.uv_bits; a.corner_value = in.uv_corners; a.grid = in.uvs ? in.uv_grid : nullptr; pl.atts.push_back(a); }
   // (the generic attribute takes the constrained multi-parallelogram scheme where the positions do: what an encoder at its highest levels writes)
   if (in.generic) { PortableAttr a; a.att_type = 4; a.nc = a.nc_out = opt.generic_components >= 1 && opt.generic_components <= 4 ? opt.generic_components : 1; a.seq_type = 1; a.data_type = opt.generic_data_type; a.prediction = opt.pos_prediction == 4 ? 4 : 1; pl.atts.push_back(a); }
   plan_extra_attributes(in, opt, opt.pos_prediction == 4 ? 4 : 1, pl.atts);
@@ -1752,9 +1850,9 @@ static MeshIn welded_mesh_in(const MeshIn &in, const Welded &w, std::vector<Extr
 // Attribute descriptors of a sequential stream: positions, normals, texture coordinates, the generic integer attribute; all Difference.
 static void plan_sequential_attributes(const MeshIn &in, const Options &opt, std::vector<PortableAttr> &atts) {
   atts.clear();
-  { PortableAttr a; a.att_type = 0; a.nc = a.nc_out = 3; a.seq_type = 2; a.data_type = 9; a.prediction = 0; a.bits = opt.pos_bits; atts.push_back(a); }
+  { PortableAttr a; a.att_type = 0; a.nc = a.nc_out = 3; a.seq_type = 2; a.data_type = 9; a.prediction = 0; a.bits = opt.pos_bits; a.grid = in.pos_grid; atts.push_back(a); }
   if (in.normals) { PortableAttr a; a.att_type = 1; a.nc_out = 3; a.nc = 2; a.seq_type = 3; a.data_type = 9; a.bits = opt.normal_bits; a.prediction = 0; atts.push_back(a); }
-  if (in.uvs) { PortableAttr a; a.att_type = 3; a.nc = a.nc_out = 2; a.seq_type = 2; a.data_type = 9; a.prediction = 0; a.bits = opt.uv_bits; atts.push_back(a); }
+  if (in.uvs) { PortableAttr a; a.att_type = 3; a.nc = a.nc_out = 2; a.seq_type = 2; a.data_type = 9; a.prediction = 0; a.bits = opt.uv_bits; a.grid = in.uv_grid; atts.push_back(a); }
   if (in.generic) { PortableAttr a; a.att_type = 4; a.nc = a.nc_out = opt.generic_components >= 1 && opt.generic_components <= 4 ? opt.generic_components : 1; a.seq_type = 1; a.data_type = opt.generic_data_type; a.prediction = 0; atts.push_back(a); }
   plan_extra_attributes(in, opt, 0, atts);
 }

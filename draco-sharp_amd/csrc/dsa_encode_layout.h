@@ -24,6 +24,7 @@
 #include "dsa_encode_conn.h"
 #include "dsa_encode_repair.h"
 #include "dsa_encode_weld.h"
+#include "dsa_encode_grid.h"
 #include "dsa_encode_seams.h"
 #include "dsa_encode_seqidx.h"
 #include "dsa_encode_schemes.h"
@@ -65,6 +66,10 @@ struct EncStream {                 // one per (mesh, attribute); lives in device
   uint32_t pd_want, pad_level;     // pd_want: an attribute given per corner whose decoder takes the prediction-degree order unless it is seamed
   uint32_t linear, elem;           // linear: entry i is value row i (sequential streams, dsa_encode_sequential.h): `d` is `vals`, no e2v, no gather
                                    // elem (kind 2): Draco's data type of `src`, 1 int8, 2 uint8, 3 int16, 4 uint16, 5 int32, 6 uint32
+  uint32_t grid_mode;              // kind 0: not 0: qmin / qrange are a grid given by the host (the caller's, or its group's), k_enc_grid_quantize in place
+                                   //   of k_enc_bounds and k_enc_quantize
+  uint32_t grid_nonfinite, grid_off;      // its smallest row with a value that is not finite / whose integer leaves 0 .. max_q (the host sets ENC_GRID_NO_ROW)
+  uint32_t grid_pad;
 };
 
 // The raw symbol scheme takes symbols below 2^18 (dsa_symbol_plan.h choose_scheme; symbol_stats of the host coder builds no
@@ -108,6 +113,25 @@ struct dsa_encoded {
 
 // A call of an encode entry point.  The meshes in the form they arrived (one of the three pointers is set), the options in the
 // widest struct of their kind: what a narrower entry point does not have stays at its default, which every check passes.
+// The grids of one mesh as a request carries them (dsa_mesh_grids copied, the attribute list's up to what a stream may hold):
+// slot 0 the positions, 1 the first UV set, 2 + k attribute k of the list.  enc_stage_grids turns mode 2 into mode 1 with the
+// group's grid before any chunk looks.
+static_assert(sizeof(synth::Grid) == sizeof(dsa_quantization_grid) && sizeof(dsa_quantization_grid) == 32 && sizeof(dsa_mesh_grids) == 80, "dsa_quantization_grid is the host coder's Grid");
+struct EncMeshGrids {
+  synth::Grid slot[2 + synth::kMaxAttributes];
+  uint32_t group = 0;
+  const char *error = nullptr;             // what the struct alone says against itself
+  EncMeshGrids() { memset(slot, 0, sizeof(slot)); }
+};
+static EncMeshGrids enc_take_grids(const dsa_mesh_grids &g, uint32_t num_attributes) {
+  EncMeshGrids out;
+  memcpy(&out.slot[0], &g.position, sizeof(synth::Grid));
+  memcpy(&out.slot[1], &g.texcoord, sizeof(synth::Grid));
+  for (uint32_t k = 0; k < num_attributes && k < synth::kMaxAttributes && g.attributes; ++k) memcpy(&out.slot[2 + k], &g.attributes[k], sizeof(synth::Grid));
+  out.group = g.group;
+  if (g.reserved != 0) out.error = "dsa_mesh_grids.reserved is not zero";
+  return out;
+}
 struct EncRequest {
   uint32_t n = 0;
   const dsa_mesh_input *vertex = nullptr;
@@ -118,6 +142,7 @@ struct EncRequest {
   bool repair = false;                     // dsa_encode_repair_batch, topology = 1, the second pass: the meshes the first pass refused for their topology, on the repaired corner table
   bool weld = false;                       // dsa_encode_points_batch / dsa_weld_batch: `listed` holds one row per point, every chunk welds its meshes first (enc_stage_weld)
   std::vector<synth::Welded> *weld_sink = nullptr;      // dsa_weld_batch: receives the weld of every mesh, nothing is coded
+  const EncMeshGrids *grids = nullptr;     // dsa_encode_grid_batch / _sequential_batch: parallel to `listed` (null: every attribute on its own bounds)
   dsa_encode_level_options level;          // Edgebreaker streams
   dsa_encode_sequential_options seq;       // sequential streams
   const dsa_encode_options &base() const { return sequential ? seq.base : level.ex.base; }
@@ -156,6 +181,7 @@ struct EncLayout {
   uint64_t input_bytes = 0, total_bytes = 0;      // the uploads fill [0, input_bytes); the kernels' regions lie behind
   uint32_t max_rows = 0, maxf = 0, max_count = 0; // grid sizes: value rows / entries of a stream, faces of a mesh, index symbols of a mesh
   bool any_multi = false, any_crease = false, any_valence = false;      // streams predicted by method 2 / 4; by method 4; meshes coded with valence symbols
+  bool any_grid = false;                    // streams on a grid that is not their own bounds (k_enc_grid_quantize)
 };
 
 static inline bool enc_multi_scheme(const synth::PortableAttr &a) { return a.seq_type != 3 && (a.prediction == 2 || a.prediction == 4); }
@@ -243,6 +269,21 @@ static std::string enc_take_extras(const dsa_mesh_attr_input &am, std::vector<sy
   in.extras = ex.data(); in.num_extras = am.num_attributes;
   return synth::extras_error(in);
 }
+// The grids of mesh i (null: none) against its attributes, and into `in` / `ex` for the plan; "" when they can be used.  Mode 2
+// has become mode 1 by now (enc_stage_grids).
+static std::string enc_take_mesh_grids(const EncMeshGrids *g, std::vector<synth::ExtraAttr> &ex, synth::MeshIn &in) {
+  if (!g) return "";
+  if (g->error) return g->error;
+  std::string why = synth::grid_error(g->slot[0], 3, true, "positions");
+  if (why.empty()) why = in.uvs ? synth::grid_error(g->slot[1], 2, true, "texcoords") : synth::grid_error_absent(g->slot[1], "texcoords");
+  for (uint32_t k = 0; k < in.num_extras && k < synth::kMaxAttributes && why.empty(); ++k)
+    why = synth::grid_error(g->slot[2 + k], (int)ex[k].nc, ex[k].data_type == 9, synth::grid_slot_name(ex[k].att_type, (int)k));
+  if (!why.empty()) return why;
+  in.pos_grid = &g->slot[0];
+  if (in.uvs) in.uv_grid = &g->slot[1];
+  for (uint32_t k = 0; k < in.num_extras && k < synth::kMaxAttributes; ++k) ex[k].grid = &g->slot[2 + k];
+  return "";
+}
 // hist_cap of an integer extra: one-byte types by their range, wider ones by the values present (a pass over the values by the
 // host thread that checks the mesh's indices anyway): zig-zagged wrapped corrections lie in 0 .. max - min + 1
 static uint32_t enc_extra_hist_cap(const synth::PortableAttr &a, uint32_t rows) {
@@ -321,7 +362,8 @@ static void enc_plan_mesh(EncChunk &ck, uint32_t i) {
     in.uv_corners = cm->texcoord_corners; in.nu = cm->num_texcoords;
   }
   if (ck.rq.listed) {
-    const std::string why = enc_take_extras(*ck.attr(i), ck.extras[i], in);
+    std::string why = enc_take_extras(*ck.attr(i), ck.extras[i], in);
+    if (why.empty()) why = enc_take_mesh_grids(ck.rq.grids ? &ck.rq.grids[ck.base + i] : nullptr, ck.extras[i], in);
     if (!why.empty()) return ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, why);
   }
   // (every mesh of a repair request is one whose topology the first pass refused)
@@ -405,7 +447,8 @@ static void enc_check_sequential_mesh(EncChunk &ck, uint32_t i) {
   synth::Options mo = ck.opt;
   mo.generic_components = m.generic ? (int32_t)m.generic_components : 1;
   if (ck.rq.listed) {
-    const std::string why = enc_take_extras(*ck.rq.attr(ck.base + i), ck.extras[i], in);
+    std::string why = enc_take_extras(*ck.rq.attr(ck.base + i), ck.extras[i], in);
+    if (why.empty()) why = enc_take_mesh_grids(ck.rq.grids ? &ck.rq.grids[ck.base + i] : nullptr, ck.extras[i], in);
     if (!why.empty()) return ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, why);
   }
   synth::plan_sequential_attributes(in, mo, ck.plans[i].atts);
@@ -421,6 +464,11 @@ static void enc_value_stream_input(dsa::EncStream &S, const synth::PortableAttr 
   S.rows = rows; S.nc_out = (uint32_t)a.nc_out; S.nc = (uint32_t)a.nc; S.kind = a.seq_type == 3 ? 1u : (integer ? 2u : 0u);
   S.bits = integer ? 9u : (uint32_t)a.bits;              // (9: the zig-zagged corrections of bytes are below 512)
   S.elem = integer ? (uint32_t)a.data_type : 0u;
+  if (S.kind == 0 && a.grid && a.grid->mode != 0) {      // the header's floats are the grid's
+    S.grid_mode = 1; S.grid_nonfinite = S.grid_off = dsa::ENC_GRID_NO_ROW;
+    for (uint32_t c = 0; c < S.nc_out && c < 4; ++c) S.qmin[c] = a.grid->origin[c];
+    S.qrange = a.grid->range;
+  }
   S.src = A.put(ups, src, (integer ? (uint64_t)synth::data_type_size(a.data_type) : 4ull) * rows * S.nc_out, false);
 }
 static void enc_table_regions(dsa::EncStream &S, EncArena &A) {
@@ -456,6 +504,7 @@ static void enc_layout_begin(EncChunk &ck, uint32_t more_streams_of_valence, uin
   L.first_stream.assign(ck.n + 1, 0);
   for (uint32_t i = 0; i < ck.n; ++i) {
     L.any_valence = L.any_valence || ck.valence_of(i);
+    for (size_t k = 0; ck.good(i) && k < ck.plans[i].atts.size(); ++k) { const synth::PortableAttr &a = ck.plans[i].atts[k]; L.any_grid = L.any_grid || (a.seq_type == 2 && a.grid && a.grid->mode != 0); }
     L.first_stream[i + 1] = L.first_stream[i] + (ck.good(i) ? (uint32_t)ck.plans[i].atts.size() + more_streams + (ck.valence_of(i) ? more_streams_of_valence : 0u) : 0u);
   }
   dsa::EncStream zero;

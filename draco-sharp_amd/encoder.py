@@ -137,6 +137,42 @@ class Config:
         return o
 
 
+class Grid:
+    """The quantisation grid of one float attribute (positions, the first UV set, a float32 Attribute) when it is not the
+    attribute's own bounding box -- the reference's quantization_origin / quantization_range.  Grid(origin, range): origin per
+    component and one range, written into the stream's header as they are; every value must be finite and quantise into
+    0 .. 2^bits - 1, else its mesh is refused.  Grid.shared(): the grid is taken over every mesh of the batch with the same
+    `group` that has the attribute, asks for a shared grid there and has the same component count (tiles of one surface, the
+    primitives of one glTF mesh): border vertices then decode to the same floats on both sides."""
+
+    def __init__(self, origin, range, mode=1):
+        o = np.atleast_1d(np.asarray(origin, np.float32)).ravel()
+        if not 1 <= len(o) <= 4:
+            raise ValueError("Grid: 1 - 4 origin components")
+        if mode == 1 and not (np.all(np.isfinite(o)) and np.isfinite(np.float32(range)) and np.float32(range) > 0):
+            raise ValueError("Grid: a finite origin and a finite range above 0")
+        self.origin, self.range, self.mode = o, np.float32(range), mode
+
+    @classmethod
+    def shared(cls):
+        return cls([0.0], 1.0, mode=2)
+
+    def _native(self, components):
+        g = native.QuantizationGrid()
+        if self.mode == 1 and len(self.origin) != components:
+            raise ValueError("Grid: %d origin components for an attribute of %d" % (len(self.origin), components))
+        for c, x in enumerate(self.origin):
+            g.origin[c] = x
+        g.range, g.mode = self.range, self.mode
+        return g
+
+
+def _check_grid(grid, name):
+    if grid is not None and not isinstance(grid, Grid):
+        raise ValueError("%s: a Grid or None" % name)
+    return grid
+
+
 ATTRIBUTE_DATA_TYPES = {np.dtype(np.int8): 1, np.dtype(np.uint8): 2, np.dtype(np.int16): 3, np.dtype(np.uint16): 4,
                         np.dtype(np.int32): 5, np.dtype(np.uint32): 6, np.dtype(np.float32): 9}      # Draco's DataType ids
 
@@ -148,8 +184,11 @@ class Attribute:
     1..20; 0: the texture coordinates' bits for attribute_type 3, else 8).  attribute_type 2 colour, 3 texture coordinate,
     4 generic; normalized goes into the descriptor of an integer attribute; unique_id None: the attribute's index in the stream."""
 
-    def __init__(self, values, attribute_type=4, normalized=False, unique_id=None, quantization_bits=0):
+    def __init__(self, values, attribute_type=4, normalized=False, unique_id=None, quantization_bits=0, grid=None):
         v = np.asarray(values)
+        self.grid = _check_grid(grid, "Attribute grid")           # float32 only: a Grid in place of the values' own bounds
+        if grid is not None and v.dtype != np.dtype(np.float32):
+            raise ValueError("Attribute grid: only float32 values are quantised; integer attributes have no grid")
         if v.dtype not in ATTRIBUTE_DATA_TYPES:
             raise ValueError("attribute values of dtype %s: one of int8, uint8, int16, uint16, int32, uint32, float32" % v.dtype)
         if v.ndim not in (1, 2) or len(v) == 0:
@@ -193,6 +232,39 @@ def _fill_attr_input(dst, m, keep):
     dst.attributes = arr
 
 
+def _set_grids(m, position_grid, texcoord_grid, group, texcoords):
+    """position_grid / texcoord_grid (a Grid or None: the attribute's own bounds) and the group number of shared grids."""
+    m.position_grid = _check_grid(position_grid, "position_grid")
+    m.texcoord_grid = _check_grid(texcoord_grid, "texcoord_grid")
+    if texcoord_grid is not None and texcoords is None:
+        raise ValueError("texcoord_grid without texcoords")
+    if int(group) != group or not 0 <= group <= 0xFFFFFFFF:
+        raise ValueError("group: a number 0 .. 2^32 - 1")
+    m.group = int(group)
+
+
+def _has_grid(m):
+    return (getattr(m, "position_grid", None) is not None or getattr(m, "texcoord_grid", None) is not None
+            or any(getattr(a, "grid", None) is not None for a in (getattr(m, "attributes", None) or [])))
+
+
+def _fill_grids(dst, m, keep):
+    """dsa_mesh_grids of mesh `m`; `keep` holds the ctypes array alive."""
+    if getattr(m, "position_grid", None) is not None:
+        dst.position = m.position_grid._native(3)
+    if getattr(m, "texcoord_grid", None) is not None:
+        dst.texcoord = m.texcoord_grid._native(2)
+    dst.group = getattr(m, "group", 0)
+    atts = getattr(m, "attributes", None) or []
+    if any(getattr(a, "grid", None) is not None for a in atts):
+        arr = (native.QuantizationGrid * len(atts))()
+        for k, a in enumerate(atts):
+            if getattr(a, "grid", None) is not None:
+                arr[k] = a.grid._native(a.values.shape[1])
+        keep.append(arr)
+        dst.attributes = arr
+
+
 class MeshData:
     """Triangle mesh with per-vertex attributes: positions (V,3) f32, faces (F,3) u32, optional normals (V,3), uvs (V,2) and one
     generic uint8 attribute of 1 - 4 components (V,) or (V,C): vertex colours, ids (ABI 4).  attributes: a list of Attribute
@@ -200,9 +272,14 @@ class MeshData:
 
     normal_corners / texcoord_corners (F,3) u32: the normals / texture coordinates given per corner -- row ids into `normals` /
     `texcoords`, which then hold as many rows as the ids need (UV charts, hard edges).  Edges whose end points carry different ids
-    on their two faces become attribute seams (dsa_encode_batch_corners)."""
+    on their two faces become attribute seams (dsa_encode_batch_corners).
 
-    def __init__(self, positions, faces, normals=None, texcoords=None, generic=None, normal_corners=None, texcoord_corners=None, attributes=None):
+    position_grid / texcoord_grid: a Grid in place of the attribute's own bounds (Attribute(..., grid=) for a float32 attribute
+    of the list); group: the meshes of a batch whose Grid.shared() attributes share one grid (dsa_encode_grid_batch)."""
+
+    def __init__(self, positions, faces, normals=None, texcoords=None, generic=None, normal_corners=None, texcoord_corners=None, attributes=None,
+                 position_grid=None, texcoord_grid=None, group=0):
+        _set_grids(self, position_grid, texcoord_grid, group, texcoords)
         self.positions = np.ascontiguousarray(positions, np.float32)
         self.attributes = _attributes(attributes, len(self.positions))
         self.faces = np.ascontiguousarray(faces, np.uint32)
@@ -245,7 +322,8 @@ class PointCloudData:
     attribute of 1 - 4 components (N,) or (N,C).  Written as a sequential point-cloud stream (dsa_encode_sequential_batch,
     geometry 0): point i of the stream is row i.  attributes: as for MeshData, one row per point."""
 
-    def __init__(self, positions, normals=None, texcoords=None, generic=None, attributes=None):
+    def __init__(self, positions, normals=None, texcoords=None, generic=None, attributes=None, position_grid=None, texcoord_grid=None, group=0):
+        _set_grids(self, position_grid, texcoord_grid, group, texcoords)
         self.positions = np.ascontiguousarray(positions, np.float32)
         self.attributes = _attributes(attributes, len(self.positions))
         self.faces = np.zeros((0, 3), np.uint32)
@@ -372,6 +450,8 @@ class DracoEncoder:
         # an option needs dsa_encode_batch_ex, which takes the corner form); otherwise exactly the per-vertex call
         repair = getattr(config, "repair_topology", False)      # dsa_encode_repair_batch: the level call's input and options, and the topology switch
         repair = repair or weld               # dsa_encode_points_batch takes that call's input and options
+        gridded = any(_has_grid(m) for m in meshes)      # dsa_encode_grid_batch: only when some grid is set; it takes the repair call's input
+        repair = repair or gridded
         level = config.leveled or repair      # dsa_encode_level_batch takes the widest input: always dsa_mesh_attr_input, an empty list is legal
         listed = level or any(getattr(m, "attributes", None) for m in meshes)
         corners = listed or ex or any(getattr(m, "per_corner", False) for m in meshes)
@@ -395,11 +475,20 @@ class DracoEncoder:
                 ci.texcoord_corners = uci.ctypes.data if uci is not None else None
                 ci.num_normals = len(m.normals) if m.normals is not None else 0
                 ci.num_texcoords = len(m.texcoords) if m.texcoords is not None else 0
-        opt = config._native_repair() if repair else config._native_level() if level else (config._native_ex() if (ex or listed) else config._native())
+        grids = None
+        if gridded:
+            grids = (native.MeshGrids * max(1, n))()
+            for i, m in enumerate(meshes):
+                _fill_grids(grids[i], m, keep)
+            gopt = native.EncodeGridOptions()
+            L.dsa_encode_default_grid_options(C.byref(gopt))
+            gopt.repair = config._native_repair()
+            gopt.weld_points = 1 if weld else 0
+        opt = gopt if gridded else config._native_repair() if repair else config._native_level() if level else (config._native_ex() if (ex or listed) else config._native())
         h = C.c_void_p()
         t0 = time.perf_counter()
         entry = L.dsa_encode_points_batch if weld else L.dsa_encode_repair_batch if repair else L.dsa_encode_level_batch if level else L.dsa_encode_attributes_batch if listed else (L.dsa_encode_batch_ex if ex else (L.dsa_encode_batch_corners if corners else L.dsa_encode_batch))
-        st = entry(ctx._h, n, arr, C.byref(opt), C.byref(h))
+        st = L.dsa_encode_grid_batch(ctx._h, n, arr, grids, C.byref(opt), C.byref(h)) if gridded else entry(ctx._h, n, arr, C.byref(opt), C.byref(h))
         t1 = time.perf_counter()
         if st != 0:
             _raise(st, ctx.error())
@@ -413,7 +502,8 @@ class DracoEncoder:
     def _encode_sequential(self, ctx, meshes, config, geometry, handle=False):
         L = native.lib()
         n = len(meshes)
-        listed = any(getattr(m, "attributes", None) for m in meshes)
+        gridded = any(_has_grid(m) for m in meshes)      # dsa_encode_grid_sequential_batch: only when some grid is set; it takes the attribute-list input
+        listed = gridded or any(getattr(m, "attributes", None) for m in meshes)
         arr = ((native.MeshAttrInput if listed else native.MeshInput) * max(1, n))()
         keep = []
         for i, m in enumerate(meshes):
@@ -431,7 +521,13 @@ class DracoEncoder:
         opt = config._native_sequential(geometry)
         h = C.c_void_p()
         entry = L.dsa_encode_attributes_sequential_batch if listed else L.dsa_encode_sequential_batch
-        st = entry(ctx._h, n, arr, C.byref(opt), C.byref(h))
+        if gridded:
+            grids = (native.MeshGrids * max(1, n))()
+            for i, m in enumerate(meshes):
+                _fill_grids(grids[i], m, keep)
+            st = L.dsa_encode_grid_sequential_batch(ctx._h, n, arr, grids, C.byref(opt), C.byref(h))
+        else:
+            st = entry(ctx._h, n, arr, C.byref(opt), C.byref(h))
         if st != 0:
             _raise(st, ctx.error())
         return (ctx, h, n) if handle else EncodedStreams(ctx, h, n)

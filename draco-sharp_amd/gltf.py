@@ -295,15 +295,22 @@ def _listed_semantic(semantic):
     return 4 if head in ("JOINTS", "WEIGHTS") else None
 
 
-def plan_compression(assets):
+def plan_compression(assets, shared_grid=None):
     """Needs no device.  (planned, skipped): every TRIANGLES primitive with float32 VEC3 POSITION and indices becomes a MeshData
     -- NORMAL (float32 VEC3) and TEXCOORD_0 (float32 VEC2) as built-ins, COLOR_n, JOINTS_n, WEIGHTS_n, TEXCOORD_n in other forms
-    through the attribute list in their component types -- every other primitive is skipped with the reason."""
-    from .encoder import Attribute, MeshData
+    through the attribute list in their component types -- every other primitive is skipped with the reason.
+    shared_grid="mesh": the planned primitives of one glTF mesh, and only those, are one group whose positions share a quantisation
+    grid (Grid.shared(): a vertex on the cut between two primitives decodes to the same floats in both); None: every primitive
+    on its own bounds."""
+    from .encoder import Attribute, Grid, MeshData
+    if shared_grid not in (None, "mesh"):
+        raise ValueError("shared_grid %r: None or \"mesh\"" % (shared_grid,))
     planned, skipped = [], []
+    groups = 0
     for asset in assets:
         accessors = asset.doc.get("accessors", [])
         for mi, mesh in enumerate(asset.doc.get("meshes", [])):
+            groups += 1                                      # (group 0 is what a mesh without one has)
             for pi, prim in enumerate(mesh.get("primitives", [])):
                 def skip(reason):
                     skipped.append(SkippedPrimitive(asset, mi, pi, reason))
@@ -359,7 +366,10 @@ def plan_compression(assets):
                         skip(why); continue
                 except InvalidDataException as e:
                     skip(str(e)); continue
-                data = MeshData(pos, idx.astype(np.uint32).reshape(-1, 3), normals, texcoords, attributes=listed)
+                if shared_grid == "mesh":
+                    data = MeshData(pos, idx.astype(np.uint32).reshape(-1, 3), normals, texcoords, attributes=listed, position_grid=Grid.shared(), group=groups)
+                else:
+                    data = MeshData(pos, idx.astype(np.uint32).reshape(-1, 3), normals, texcoords, attributes=listed)
                 planned.append(PlannedPrimitive(asset, mi, pi, data, ids))
     return planned, skipped
 
@@ -477,14 +487,15 @@ class GltfDracoWriter:
     def __init__(self, context=None):
         self.ctx = context or default_context()
 
-    def compress(self, sources, config=None):
-        """sources: paths, bytes or GltfAssets.  One EncodeBatch with weld_points=True codes every planned primitive (the other
+    def compress(self, sources, config=None, shared_grid=None):
+        """sources: paths, bytes or GltfAssets.  shared_grid="mesh": the primitives of one glTF mesh share the quantisation grid of
+        their positions (plan_compression), so that the mesh does not crack along the cuts between them; None: today's bytes.  One EncodeBatch with weld_points=True codes every planned primitive (the other
         options of `config` as given); one decode batch of the result gives the accessor counts -- a stream can hold more points
         than its primitive had where seams cross.  Returns a CompressedAsset per source."""
         import copy
         from .encoder import Config, DracoEncoder
         assets = [s if isinstance(s, GltfAsset) else read_asset(s) for s in sources]
-        planned, skipped = plan_compression(assets)
+        planned, skipped = plan_compression(assets, shared_grid)
         cfg = copy.copy(config) if config is not None else Config()
         cfg.weld_points = True
         if cfg.sequential:

@@ -34,6 +34,7 @@ EXPORTS = [
     "dsa_encode_default_level_options", "dsa_encode_level_batch",
     "dsa_encode_default_repair_options", "dsa_encode_repair_batch",
     "dsa_encode_points_batch", "dsa_weld_batch", "dsa_welded_size", "dsa_welded_mesh", "dsa_welded_free",
+    "dsa_encode_default_grid_options", "dsa_encode_grid_batch", "dsa_encode_grid_sequential_batch",
     "dsa_encoded_size", "dsa_encoded_stream", "dsa_encoded_free",
     "dsa_pool_create", "dsa_pool_destroy", "dsa_pool_size", "dsa_pool_last_error", "dsa_pool_decode", "dsa_pool_job_locate",
     "dsa_pool_job_chunks", "dsa_pool_job_free", "dsa_pool_plan",
@@ -100,6 +101,23 @@ class MeshAttrInput(C.Structure):
     """dsa_mesh_attr_input: a mesh (or point cloud) with an attribute list."""
     _fields_ = [("mesh", MeshCornerInput), ("attributes", C.POINTER(AttributeInput)), ("num_attributes", C.c_uint32),
                 ("reserved", C.c_uint32)]
+
+
+class QuantizationGrid(C.Structure):
+    """dsa_quantization_grid: mode 0 the attribute's own bounds, 1 explicit (origin per component, one range), 2 shared by the
+    meshes of a group."""
+    _fields_ = [("origin", C.c_float * 4), ("range", C.c_float), ("mode", C.c_int32), ("reserved", C.c_uint32 * 2)]
+
+
+class MeshGrids(C.Structure):
+    """dsa_mesh_grids: the grids of one mesh (positions, the first UV set, the attribute list) and its group."""
+    _fields_ = [("position", QuantizationGrid), ("texcoord", QuantizationGrid), ("attributes", C.POINTER(QuantizationGrid)),
+                ("group", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class EncodeGridOptions(C.Structure):
+    """dsa_encode_grid_options: the options of dsa_encode_repair_batch, and weld_points (1: the input of dsa_encode_points_batch)."""
+    _fields_ = [("repair", EncodeRepairOptions), ("weld_points", C.c_int32), ("reserved", C.c_int32 * 7)]
 
 
 class WeldedInfo(C.Structure):
@@ -249,6 +267,11 @@ def lib():
             L.dsa_welded_mesh.argtypes = [vp, u32, C.POINTER(WeldedInfo)]
             L.dsa_welded_free.argtypes = [vp]
             L.dsa_welded_free.restype = None
+        if hasattr(L, "dsa_encode_grid_batch"):
+            L.dsa_encode_default_grid_options.argtypes = [C.POINTER(EncodeGridOptions)]
+            L.dsa_encode_default_grid_options.restype = None
+            L.dsa_encode_grid_batch.argtypes = [vp, u32, C.POINTER(MeshAttrInput), C.POINTER(MeshGrids), C.POINTER(EncodeGridOptions), C.POINTER(vp)]
+            L.dsa_encode_grid_sequential_batch.argtypes = [vp, u32, C.POINTER(MeshAttrInput), C.POINTER(MeshGrids), C.POINTER(EncodeSequentialOptions), C.POINTER(vp)]
         L.dsa_encoded_size.restype = u32
         L.dsa_encoded_size.argtypes = [vp]
         L.dsa_encoded_stream.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(C.c_size_t)]

@@ -37,13 +37,52 @@ class ExtraInput(C.Structure):
                 ("unique_id", C.c_uint32), ("quantization_bits", C.c_int32), ("values", C.c_void_p)]
 
 
+class Grid(C.Structure):
+    """A quantisation grid given by the caller (dsa_quantization_grid): mode 0 the attribute's own bounds, 1 explicit."""
+    _fields_ = [("origin", C.c_float * 4), ("range", C.c_float), ("mode", C.c_int32), ("reserved", C.c_uint32 * 2)]
+
+
+class GridsInput(C.Structure):
+    """synth_grids: the grids of the positions, the first UV set and the extras of one mesh."""
+    _fields_ = [("position", Grid), ("texcoord", Grid), ("attributes", C.POINTER(Grid))]
+
+
+def grid(origin, range, mode=1):
+    """An explicit grid: origin per component (1 - 4 floats) and one range."""
+    g = Grid()
+    o = np.asarray(origin, np.float32).ravel()
+    if not 1 <= len(o) <= 4:
+        raise ValueError("a grid has 1 to 4 origin components")
+    for c, x in enumerate(o):
+        g.origin[c] = x
+    g.range, g.mode = np.float32(range), mode
+    return g
+
+
+def shared_grid(arrays):
+    """The grid a group of meshes shares for one attribute slot (mode 2 of the device encoder), as an explicit grid: minimum per
+    component over all rows of every array (N, nc) whose values are all finite, range the largest extent, 1 if that is 0."""
+    arrays = [np.ascontiguousarray(a, np.float32) for a in arrays]
+    arrays = [a.reshape(len(a), -1) for a in arrays]
+    if not arrays or any(a.shape[1] != arrays[0].shape[1] for a in arrays):
+        raise ValueError("shared_grid: arrays of one component count")
+    ptrs = (C.c_void_p * len(arrays))(*[a.ctypes.data for a in arrays])
+    rows = (C.c_uint32 * len(arrays))(*[len(a) for a in arrays])
+    g = Grid()
+    L = lib()
+    if L.synth_shared_grid(ptrs, rows, len(arrays), arrays[0].shape[1], C.byref(g)):
+        raise RuntimeError(_err())
+    return g
+
+
 class Extra:
     """One more per-vertex attribute for the `extra=[...]` of the encode calls: values (V,) or (V, 1..4) of int8 / uint8 / int16 /
     uint16 / int32 / uint32 (coded as they are) or float32 (quantised to quantization_bits; 0: uv_bits for attribute_type 3, else
     8).  attribute_type 2 colour, 3 texture coordinate, 4 generic; unique_id None: the attribute's index in the stream.
     data_type / num_components override what the array says (the refusal tests)."""
 
-    def __init__(self, values, attribute_type=4, normalized=False, unique_id=None, quantization_bits=0, data_type=None, num_components=None):
+    def __init__(self, values, attribute_type=4, normalized=False, unique_id=None, quantization_bits=0, data_type=None, num_components=None, grid=None):
+        self.grid = grid                      # float32: a Grid (encode_grid), None: its own bounds
         v = np.asarray(values)
         if v.dtype not in GENERIC_DATA_TYPES and v.dtype != np.dtype(np.float32):
             raise ValueError("extra attribute: dtype %s is none of int8 ... uint32, float32" % v.dtype)
@@ -143,6 +182,10 @@ def lib():
         L.synth_welded_free.argtypes = [C.c_void_p]
         L.synth_encode_points.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.POINTER(ExtraInput), C.c_uint32, C.POINTER(Options), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+        L.synth_encode_grid.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                        C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(ExtraInput), C.c_uint32,
+                                        C.POINTER(GridsInput), C.POINTER(Options), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+        L.synth_shared_grid.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_uint32, C.c_int, C.POINTER(Grid)]
         L.synth_free.argtypes = [C.c_void_p]
         L.synth_make_mesh.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_uint32),
                                       C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -346,6 +389,44 @@ def encode_mesh_points(pos, faces, normals=None, uvs=None, generic=None, extra=N
     out, n = C.c_void_p(), C.c_size_t()
     rc = L.synth_encode_points(ptr(pos), len(pos), ptr(faces), len(faces), ptr(nrm), ptr(uv), ptr(gen), arr, len(extra), C.byref(opt),
                                C.byref(out), C.byref(n))
+    if rc:
+        raise RuntimeError(_err())
+    data = C.string_at(out, n.value)
+    L.synth_free(out)
+    return data
+
+
+def encode_grid(pos, faces=None, normals=None, uvs=None, generic=None, extra=None, opt=None, form=1, normal_corners=None, uv_corners=None,
+                geometry=1, compressed=False, pos_grid=None, uv_grid=None):
+    """Any stream of this module with quantisation grids given by the caller: pos_grid / uv_grid / Extra.grid are Grids (grid(),
+    shared_grid()) or None for the attribute's own bounds.  form 1: the arguments of encode_mesh_corners (Edgebreaker); form 0:
+    of encode_sequential (geometry 1) / encode_point_cloud_attributes (geometry 0, faces None); form 2: of encode_mesh_points
+    (one row per point).  Without a grid the bytes are those calls'.  What dsa_encode_grid_batch /
+    dsa_encode_grid_sequential_batch must write."""
+    L = lib()
+    pos, fc, nrm, uv, gen, extra, arr, opt = _points_args(pos, np.zeros((0, 3), np.uint32) if faces is None else faces, normals if normal_corners is None else None,
+                                                          uvs if uv_corners is None else None, generic, extra, opt)
+    if normal_corners is not None:
+        nrm = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    if uv_corners is not None:
+        uv = np.ascontiguousarray(uvs, np.float32).reshape(-1, 2)
+    nci = None if normal_corners is None else np.ascontiguousarray(normal_corners, np.uint32)
+    uci = None if uv_corners is None else np.ascontiguousarray(uv_corners, np.uint32)
+    gi = GridsInput()
+    if pos_grid is not None:
+        gi.position = pos_grid
+    if uv_grid is not None:
+        gi.texcoord = uv_grid
+    ga = (Grid * max(1, len(extra)))()
+    for k, e in enumerate(extra):
+        if e.grid is not None:
+            ga[k] = e.grid
+    gi.attributes = ga
+    ptr = lambda a: None if a is None else a.ctypes.data          # noqa: E731
+    out, n = C.c_void_p(), C.c_size_t()
+    rc = L.synth_encode_grid(form, ptr(pos), len(pos), ptr(fc) if len(fc) else None, len(fc), ptr(nrm), 0 if nrm is None else len(nrm), ptr(nci),
+                             ptr(uv), 0 if uv is None else len(uv), ptr(uci), ptr(gen), geometry, 1 if compressed else 0, arr, len(extra),
+                             C.byref(gi), C.byref(opt), C.byref(out), C.byref(n))
     if rc:
         raise RuntimeError(_err())
     data = C.string_at(out, n.value)

@@ -351,6 +351,65 @@ int synth_encode_points(const float *pos, uint32_t np, const uint32_t *faces, ui
     return 0;
   } catch (const std::exception &e) { snprintf(g_err, sizeof(g_err), "%s", e.what()); return 1; }
 }
+// Any of the streams above with quantisation grids given by the caller (dsa_encode_host.h Grid, the layout of
+// dsa_quantization_grid): `grids` null or its entries mode 0: the bytes of the calls above.  form 0: synth_encode_attributes'
+// sequential arguments, 1: its Edgebreaker arguments, 2: synth_encode_points' (one row per point, corner ids unset).
+struct synth_grids { synth::Grid position, texcoord; const synth::Grid *attributes; };      // attributes: num_extras entries or NULL
+int synth_encode_grid(int form, const float *pos, uint32_t nv, const uint32_t *faces, uint32_t nf, const float *normals, uint32_t nn,
+                      const uint32_t *normal_corners, const float *uvs, uint32_t nu, const uint32_t *uv_corners, const void *generic,
+                      int geometry, int compressed, const synth_extra *extras, uint32_t num_extras, const synth_grids *grids,
+                      const synth_options *opt, uint8_t **out, size_t *out_len) {
+  try {
+    synth::check(form >= 0 && form <= 2, "form: 0 (sequential), 1 (Edgebreaker) or 2 (one row per point)");
+    std::vector<synth::ExtraAttr> ex, ex2;
+    synth::MeshIn in = points_in(pos, nv, faces, nf, normals, uvs, generic, extras, num_extras, ex);
+    if (grids) {
+      in.pos_grid = &grids->position;
+      if (uvs) in.uv_grid = &grids->texcoord;
+      else { const std::string why = synth::grid_error_absent(grids->texcoord, "texcoords"); synth::check(why.empty(), why.c_str()); }
+      for (uint32_t k = 0; k < num_extras && grids->attributes; ++k) ex[k].grid = &grids->attributes[k];
+    }
+    const synth::Options o = to_opt(opt);
+    std::vector<uint8_t> buf;
+    if (form == 0) {
+      synth::check(!normal_corners && !uv_corners, "a sequential stream has one value per point");
+      synth::check(geometry == 0 || geometry == 1, "geometry: 1 (triangular mesh) or 0 (point cloud)");
+      synth::check(geometry == 1 || nf == 0, "a point cloud has no faces");
+      synth::check(pos != nullptr && nv > 0, "positions are missing");
+      synth::check(geometry == 0 || (faces != nullptr && nf > 0), "a mesh needs faces");
+      for (size_t k = 0; k < (size_t)nf * 3; ++k) synth::check(faces[k] < nv, "face index out of range");
+      synth::encode_sequential(in, o, geometry == 1, compressed != 0, buf);
+    } else if (form == 1) {
+      in.normal_corners = normals ? normal_corners : nullptr; in.nn = nn;
+      in.uv_corners = uvs ? uv_corners : nullptr; in.nu = nu;
+      for (size_t k = 0; k < (size_t)nf * 3; ++k) {
+        synth::check(faces[k] < nv, "face index out of range");
+        synth::check(!in.normal_corners || in.normal_corners[k] < nn, "normal id out of range");
+        synth::check(!in.uv_corners || in.uv_corners[k] < nu, "texture coordinate id out of range");
+      }
+      synth::encode_mesh(in, o, buf);
+    } else {
+      synth::Welded w;
+      synth::weld_points(nv, faces, nf, synth::weld_vertex_key(in, generic ? generic_row_bytes(o) : 0), normals, uvs, w);
+      const synth::MeshIn m = synth::welded_mesh_in(in, w, ex2);
+      synth::check(!(o.repair_topology && pos && nv >= 3 && nf == 0), "all triangles are degenerate");
+      synth::check(m.pos && m.faces && m.nv >= 3 && m.nf >= 1, "mesh needs positions and faces");
+      synth::encode_mesh(m, o, buf);
+    }
+    *out = (uint8_t *)malloc(buf.size() ? buf.size() : 1);
+    memcpy(*out, buf.data(), buf.size());
+    *out_len = buf.size();
+    return 0;
+  } catch (const std::exception &e) { snprintf(g_err, sizeof(g_err), "%s", e.what()); return 1; }
+}
+// The grid a group of meshes shares (mode 2; dsa_encode_host.h shared_grid): over `count` arrays of rows[k] rows of nc floats.
+// Returns 0 and the grid as an explicit one (mode 1), or 1 when no array is free of values that are not finite.
+int synth_shared_grid(const float *const *arrays, const uint32_t *rows, uint32_t count, int nc, synth::Grid *out) {
+  if (nc < 1 || nc > 4) { snprintf(g_err, sizeof(g_err), "a grid has 1 to 4 components"); return 1; }
+  if (synth::shared_grid(arrays, rows, count, nc, *out)) return 0;
+  snprintf(g_err, sizeof(g_err), "no array of the group is free of values that are not finite");
+  return 1;
+}
 void synth_free(uint8_t *p) { free(p); }
 
 // Procedural mesh: returns counts; call once with NULL outputs to size, then again to fill.

@@ -531,6 +531,54 @@ uint32_t dsa_welded_size(const dsa_welded *welded);
 /* Fills `info` for mesh `mesh`; returns the mesh's status (a failed mesh: its status, dsa_last_error says why, the maps NULL). */
 dsa_status dsa_welded_mesh(const dsa_welded *welded, uint32_t mesh, dsa_welded_info *info);
 void dsa_welded_free(dsa_welded *welded);
+/* Quantisation grids given by the caller (the reference's quantization_origin / quantization_range per attribute:
+ * SequentialQuantizationAttributeEncoder.cs:19-23, AttributeQuantizationTransform.SetParameters) or shared by the meshes of a
+ * batch, for the attributes that are quantised: positions, the first UV set, float32 attributes of the list.  Normals
+ * (octahedral) and integer attributes have no grid.
+ *   mode 0   the attribute's own bounds (minimum per component, range the largest extent): what every other call does.
+ *   mode 1   explicit: origin[c] per component and one range; the stream's header carries exactly those floats.  The values are
+ *       quantised as always, q = floor((v - origin[c]) * (max_q / range) + 0.5) with every step rounded to float32 and
+ *       max_q = 2^bits - 1.  A mesh fails alone with DSA_ERR_INVALID_ARGUMENT when a value of the attribute is not finite or
+ *       its q lies outside [0, max_q] (the check is on the integer: a value that rounds onto the last cell is inside).  The
+ *       message names the attribute and a row: the smallest row with a value that is not finite, else the smallest row with a
+ *       value off the grid ("positions: row 7 is not finite", "attribute 2: row 40 lies off the quantisation grid").
+ *   mode 2   shared: for one attribute slot (positions, the first UV set, attribute k of the list) the grid is taken over every
+ *       mesh of the batch with the same `group`, that attribute present, mode 2 there and the same component count: minimum per
+ *       component over all rows passed (num_vertices rows; num_texcoords rows of texcoords given per corner; every point of
+ *       dsa_encode_points input, used or not), range the largest extent, 1 if that is 0.  -0.0 is below +0.0.  A mesh with a
+ *       value there that is not finite takes no part in the grid (and fails alone as under mode 1); every other mesh takes
+ *       part, also one that fails a later check, so the grid depends on the inputs alone, never on chunks or passes.  With the
+ *       grid known the attribute is coded exactly as under mode 1 with that grid.
+ * Per mesh, DSA_ERR_INVALID_ARGUMENT with the field in the message: a mode outside 0 - 2, a range that is not finite or <= 0
+ * or an origin that is not finite (mode 1), a mode other than 0 for normals or an integer attribute or an attribute the mesh
+ * does not have, a reserved word that is not zero.  Origin components beyond the attribute's are not read.
+ * With grids == NULL or every mode 0 the streams are byte for byte those of dsa_encode_repair_batch / dsa_encode_points_batch
+ * (weld_points = 1) / dsa_encode_attributes_sequential_batch with the same options.  Added after ABI 4 without changing it:
+ * callers detect the feature by the symbol dsa_encode_grid_batch. */
+typedef struct dsa_quantization_grid {
+  float origin[4];
+  float range;
+  int32_t mode;                            /* 0 own bounds, 1 explicit, 2 shared within `group` */
+  uint32_t reserved[2];                    /* must be zero */
+} dsa_quantization_grid;                   /* 32 bytes */
+typedef struct dsa_mesh_grids {
+  dsa_quantization_grid position, texcoord;
+  const dsa_quantization_grid *attributes; /* num_attributes entries parallel to dsa_mesh_attr_input.attributes, or NULL: all mode 0 */
+  uint32_t group;                          /* mode 2: the meshes that share a grid */
+  uint32_t reserved;                       /* must be zero */
+} dsa_mesh_grids;                          /* 80 bytes */
+typedef struct dsa_encode_grid_options {
+  dsa_encode_repair_options repair;        /* as for dsa_encode_repair_batch, same legal values */
+  int32_t weld_points;                     /* 0 (default); 1: `meshes` are one row per point, as for dsa_encode_points_batch */
+  int32_t reserved[7];                     /* must be zero */
+} dsa_encode_grid_options;
+void dsa_encode_default_grid_options(dsa_encode_grid_options *options);
+/* `grids` is parallel to `meshes` (or NULL). */
+dsa_status dsa_encode_grid_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids,
+                                 const dsa_encode_grid_options *options, dsa_encoded **out);
+/* The same for sequential meshes and point clouds (dsa_encode_attributes_sequential_batch). */
+dsa_status dsa_encode_grid_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids,
+                                            const dsa_encode_sequential_options *options, dsa_encoded **out);
 uint32_t dsa_encoded_size(const dsa_encoded *encoded);
 /* Bytes of stream `mesh` (owned by `encoded`, valid until dsa_encoded_free) or that mesh's failure status. */
 dsa_status dsa_encoded_stream(const dsa_encoded *encoded, uint32_t mesh, const uint8_t **bytes, size_t *length);
