@@ -17,7 +17,8 @@
 // RepairTopology (dsa_encode_repair_batch, topology 1): meshes with degenerate faces, the same face twice, fins, faces turned over,
 // fans that meet at a vertex or unused vertices are coded on the corner table CornerTable(faces) builds (CornerTable.cs:28-43), as
 // DracoEncoder.Encode codes them, instead of failing; clean meshes give the same bytes.  A mesh in corner form that needs the
-// repair still fails (NotImplementedException).
+// repair still fails (NotImplementedException) unless RepairSeams is set (dsa_encode_seam_repair_batch, corner_repair 1): then its
+// normals and texture coordinates are coded over the repaired table, as DracoEncoder.Encode codes them.
 using System;
 using System.Collections.Generic;
 using System.IO;
@@ -38,6 +39,11 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
     /// <summary>Repair non-manifold, degenerate and isolated input as the reference's CornerTable does (CornerTable.cs:28-43)
     /// instead of refusing it.</summary>
     public bool RepairTopology { get; set; }
+
+    /// <summary>With RepairTopology: also code meshes in corner form (UV charts, hard edges; with WeldPoints, what the weld makes of
+    /// them) whose topology needs the repair, instead of failing them with NotImplementedException
+    /// (dsa_encode_seam_repair_batch).  Unset: nothing changes.</summary>
+    public bool RepairSeams { get; set; }
 
     /// <summary>Hand every mesh over as one row per point (the value of each attribute at the point, faces over points) and let the
     /// library weld the points into vertices (dsa_encode_points_batch): points with byte-equal positions, generic and extra rows
@@ -190,6 +196,7 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
         else if (SpeedLadder && posScheme == unset) multi = -1;
         if (multi != 0 && uvScheme == multi) opt.TexcoordPrediction = 1;
         if (SpeedLadder && config.Speed == 0) traversal = 1;
+        if (RepairSeams && !RepairTopology) throw new ArgumentException("RepairSeams codes attributes over the repaired corner table: it needs RepairTopology");
         var inputs = new DsaMeshInput[meshes.Count];
         var pins = new List<GCHandle>();
         IntPtr encoded = IntPtr.Zero;
@@ -223,9 +230,19 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
                 wp.Level.TraversalMethod = traversal;
                 wp.Topology = RepairTopology ? 1 : 0;
                 var wg = Grids(config, meshes.Count);
+                if (wg != null) for (int i = 0; i < meshes.Count; ++i) if (pin[i].Mesh.Mesh.Texcoords == null) wg[i].Texcoord = default;
+                if (RepairSeams)
+                {
+                    NativeMethods.dsa_encode_default_seam_repair_options(out var so);
+                    so.Grid.Repair = wp;
+                    so.Grid.WeldPoints = 1;
+                    so.CornerRepair = 1;
+                    fixed (DsaMeshAttrInput* p = pin) fixed (DsaMeshGrids* g = wg)
+                        NativeMethods.Check(NativeMethods.dsa_encode_seam_repair_batch(_ctx, (uint)meshes.Count, p, g, in so, out encoded), _ctx, "dsa_encode_seam_repair_batch");
+                    return Streams(encoded, meshes.Count);
+                }
                 if (wg != null)
                 {
-                    for (int i = 0; i < meshes.Count; ++i) if (pin[i].Mesh.Mesh.Texcoords == null) wg[i].Texcoord = default;
                     NativeMethods.dsa_encode_default_grid_options(out var go);
                     go.Repair = wp;
                     go.WeldPoints = 1;
@@ -253,9 +270,21 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
                 ax.Base = opt;
                 ax.EdgebreakerMethod = ebMethod != unset ? ebMethod : 0;
                 ax.NormalPrediction = normalScheme != unset ? normalScheme : 0;
+                if (grids != null) for (int i = 0; i < meshes.Count; ++i) if (ain[i].Mesh.Mesh.Texcoords == null) grids[i].Texcoord = default;
+                if (RepairSeams)
+                {
+                    NativeMethods.dsa_encode_default_seam_repair_options(out var so);
+                    so.Grid.Repair.Level.Ex = ax;
+                    so.Grid.Repair.Level.MultiParallelogram = multi;
+                    so.Grid.Repair.Level.TraversalMethod = traversal;
+                    so.Grid.Repair.Topology = 1;
+                    so.CornerRepair = 1;
+                    fixed (DsaMeshAttrInput* p = ain) fixed (DsaMeshGrids* g = grids)
+                        NativeMethods.Check(NativeMethods.dsa_encode_seam_repair_batch(_ctx, (uint)meshes.Count, p, g, in so, out encoded), _ctx, "dsa_encode_seam_repair_batch");
+                    return Streams(encoded, meshes.Count);
+                }
                 if (grids != null)
                 {
-                    for (int i = 0; i < meshes.Count; ++i) if (ain[i].Mesh.Mesh.Texcoords == null) grids[i].Texcoord = default;
                     NativeMethods.dsa_encode_default_grid_options(out var go);
                     go.Repair.Level.Ex = ax;
                     go.Repair.Level.MultiParallelogram = multi;

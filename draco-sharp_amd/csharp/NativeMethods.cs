@@ -176,6 +176,15 @@ internal unsafe struct DsaEncodeGridOptions
     public fixed int Reserved[7];   // zero
 }
 
+// dsa_encode_seam_repair_options (dsa_encode_seam_repair_batch)
+[StructLayout(LayoutKind.Sequential)]
+internal unsafe struct DsaEncodeSeamRepairOptions
+{
+    public DsaEncodeGridOptions Grid;
+    public int CornerRepair;        // 1: attributes given per corner are coded over a mesh whose topology needs the repair (needs Topology 1)
+    public fixed int Reserved[7];   // zero
+}
+
 // dsa_encode_sequential_options (dsa_encode_sequential_batch): sequential meshes and point clouds
 [StructLayout(LayoutKind.Sequential)]
 internal unsafe struct DsaEncodeSequentialOptions
@@ -299,6 +308,8 @@ internal static unsafe partial class NativeMethods
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_points_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, in DsaEncodeRepairOptions options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern void dsa_encode_default_grid_options(out DsaEncodeGridOptions options);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_grid_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, in DsaEncodeGridOptions options, out IntPtr encoded);
+    [DllImport(Lib)] internal static extern void dsa_encode_default_seam_repair_options(out DsaEncodeSeamRepairOptions options);
+    [DllImport(Lib)] internal static extern DsaStatus dsa_encode_seam_repair_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, in DsaEncodeSeamRepairOptions options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_grid_sequential_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, in DsaEncodeSequentialOptions options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern DsaStatus dsa_weld_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, out IntPtr welded);
     [DllImport(Lib)] internal static extern uint dsa_welded_size(IntPtr welded);

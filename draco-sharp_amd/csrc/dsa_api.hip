@@ -70,7 +70,7 @@ struct EncLane {
       return hipSuccess;
     }
     ~Buf() { if (p) (void)hipFree(p); }
-  } arena, streams, conns, seams, packed, items, repair, repair_recs, weld, weld_recs;      // (repair / weld: the arenas of the repair and weld kernels, dsa_encode_repair.h, dsa_encode_weld.h)
+  } arena, streams, conns, seams, packed, items, repair, repair_recs, repair_ids, weld, weld_recs;      // (repair / weld: the arenas of the repair and weld kernels, dsa_encode_repair.h, dsa_encode_weld.h)
   ~EncLane() {
     if (walk_st) { (void)hipStreamSynchronize(walk_st); (void)hipStreamDestroy(walk_st); }
     if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }

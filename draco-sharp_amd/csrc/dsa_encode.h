@@ -886,9 +886,12 @@ static dsa_status enc_stage_repair(dsa_context *ctx, EncLane &lane, EncChunk &ck
   const uint32_t n = ck.n;
   ck.rep.assign(n, synth::CornerTable());
   std::vector<dsa::EncRepair> recs;
+  std::vector<dsa::EncRepairIds> id_recs;      // attributes given per corner (EncRequest::corner_repair): their ids go up with the faces, the ids of the coded faces stay on the device for the layout
+  std::vector<const uint32_t *> id_src;
   std::vector<uint32_t> mesh_of;
   EncArena A;
   uint32_t maxf = 1;
+  if (ck.rq.corner_repair) ck.rep_ids.assign(n, {});
   for (uint32_t i = 0; i < n; ++i) {
     if (!ck.good(i)) continue;
     const dsa_mesh_input &m = ck.mesh(i);
@@ -899,29 +902,51 @@ static dsa_status enc_stage_repair(dsa_context *ctx, EncLane &lane, EncChunk &ck
     R.faces = A.take(12 * F); R.c2v = A.take(12 * F); R.opp = A.take(12 * F); R.parent = A.take(12 * F);
     R.voff = A.take(4 * (V + 1)); R.vcur = A.take(4 * V); R.vlist = A.take(12 * F);
     R.pend = A.take(3 * F); R.bvis = A.take(3 * F); R.cvis = A.take(3 * F); R.vvis = A.take(V); R.stamp = A.take(12 * V);
+    const std::vector<synth::PortableAttr> &atts = ck.plans[i].atts;
+    for (size_t k = 0; ck.rq.corner_repair && k < atts.size(); ++k) {
+      if (!atts[k].corner_value) continue;
+      if (!R.fmap) { R.fmap = A.take(4 * F); ck.rep_ids[i].assign(atts.size(), EncChunk::kNoIds); }
+      dsa::EncRepairIds I;
+      memset(&I, 0, sizeof(I));
+      I.rep = (uint32_t)recs.size(); I.rows = ck.rows_of(i, atts[k]); I.narrow = ck.ids_narrow(i, atts[k]) ? 1u : 0u; I.att_type = (uint32_t)atts[k].att_type;
+      I.src = A.take(12 * F); I.dst = A.take((I.narrow ? 6 : 12) * F);
+      ck.rep_ids[i][k] = I.dst;
+      id_recs.push_back(I); id_src.push_back(atts[k].corner_value);
+    }
     recs.push_back(R); mesh_of.push_back(i);
     maxf = std::max(maxf, m.num_faces);
   }
-  const uint32_t nr = (uint32_t)recs.size();
+  const uint32_t nr = (uint32_t)recs.size(), ni = (uint32_t)id_recs.size();
   if (!nr) return DSA_OK;
   hipStream_t st = lane.st;
   ENC_TRY(lane.repair.ensure(A.cur));
   ENC_TRY(lane.repair_recs.ensure(std::max(sizeof(dsa::EncRepair), sizeof(dsa::EncRepairRows)) * n));
+  if (ni) ENC_TRY(lane.repair_ids.ensure(sizeof(dsa::EncRepairIds) * ni));
   uint8_t *arena = (uint8_t *)lane.repair.p;
   dsa::EncRepair *d_recs = (dsa::EncRepair *)lane.repair_recs.p;
+  dsa::EncRepairIds *d_ids = (dsa::EncRepairIds *)lane.repair_ids.p;
   ENC_TRY(hipMemsetAsync(arena, 0, A.cur, st));
   for (uint32_t r = 0; r < nr; ++r) ENC_TRY(hipMemcpyAsync(arena + recs[r].faces, ck.mesh(mesh_of[r]).faces, 12ull * recs[r].F, hipMemcpyHostToDevice, st));
+  for (uint32_t q = 0; q < ni; ++q) ENC_TRY(hipMemcpyAsync(arena + id_recs[q].src, id_src[q], 12ull * recs[id_recs[q].rep].F, hipMemcpyHostToDevice, st));
   ENC_TRY(hipMemcpyAsync(d_recs, recs.data(), sizeof(dsa::EncRepair) * nr, hipMemcpyHostToDevice, st));
+  if (ni) ENC_TRY(hipMemcpyAsync(d_ids, id_recs.data(), sizeof(dsa::EncRepairIds) * ni, hipMemcpyHostToDevice, st));
   const uint32_t walk_lanes = 16;
   const dim3 gt(std::max(1u, std::min(128u, (3u * maxf + 1023u) / 1024u)), nr);
   hipLaunchKernelGGL(dsa::k_enc_repair_mark, gt, dim3(256), 0, st, arena, d_recs, nr);
+  if (ni) {                  // (in front of the break pass: it marks the corners it visits in the array the scan reads)
+    hipLaunchKernelGGL(dsa::k_enc_repair_face_scan, dim3(nr), dim3(WAVE), 0, st, arena, d_recs, nr);
+    hipLaunchKernelGGL(dsa::k_enc_repair_ids, dim3(gt.x, ni), dim3(256), 0, st, arena, d_recs, d_ids, ni);
+  }
   hipLaunchKernelGGL(dsa::k_enc_repair_offsets, dim3(nr), dim3(WAVE), 0, st, arena, d_recs, nr);
   hipLaunchKernelGGL(dsa::k_enc_repair_lists, gt, dim3(256), 0, st, arena, d_recs, nr);
   hipLaunchKernelGGL(dsa::k_enc_repair_opposites, gt, dim3(256), 0, st, arena, d_recs, nr);
   hipLaunchKernelGGL(dsa::k_enc_repair_fans, dim3((nr + walk_lanes - 1) / walk_lanes), dim3(WAVE), 0, st, arena, d_recs, nr, walk_lanes);
   ENC_TRY(hipGetLastError());
   ENC_TRY(hipMemcpyAsync(recs.data(), d_recs, sizeof(dsa::EncRepair) * nr, hipMemcpyDeviceToHost, st));
+  if (ni) ENC_TRY(hipMemcpyAsync(id_recs.data(), d_ids, sizeof(dsa::EncRepairIds) * ni, hipMemcpyDeviceToHost, st));
   ENC_TRY(hipStreamSynchronize(st));
+  for (const dsa::EncRepairIds &I : id_recs)      // (the host's checks saw every id before; the kernel's answer is the same one)
+    if (I.bad && ck.good(mesh_of[I.rep])) ck.refuse(mesh_of[I.rep], DSA_ERR_INVALID_DATA, I.att_type == 1 ? "normal id out of range" : "texture coordinate id out of range");
   std::vector<synth::CornerTable::Repaired> out(nr);
   for (uint32_t r = 0; r < nr; ++r) {
     const dsa::EncRepair &R = recs[r];
@@ -937,12 +962,14 @@ static dsa_status enc_stage_repair(dsa_context *ctx, EncLane &lane, EncChunk &ck
   hostutil::parallel_for(nr, [&](uint32_t r) {
     const uint32_t i = mesh_of[r];
     const dsa::EncRepair &R = recs[r];
+    if (!ck.good(i)) return;
     if (R.status != dsa::ENC_REPAIR_OK) return ck.refuse(i, DSA_ERR_INVALID_DATA, dsa::enc_repair_message(R.status));
     if (out[r].c2v.empty()) return ck.refuse(i, DSA_ERR_INVALID_DATA, dsa::enc_repair_message(~0u));
     try {
       const dsa_mesh_input &m = ck.mesh(i);
       synth::CornerTable &t = ck.rep[i];
       t.from_repaired(out[r], m.faces, m.num_faces, m.num_vertices);
+      synth::check(!R.fmap || R.coded_faces == t.nf(), dsa::enc_repair_message(~0u));      // (the ids were compacted over the faces the scan kept)
       ck.c2row[i].resize(t.nc());
       for (uint32_t c = 0; c < t.nc(); ++c) ck.c2row[i][c] = t.row[t.c2v[c]];
     } catch (const std::exception &e) { ck.refuse(i, DSA_ERR_INVALID_DATA, e.what()); }
@@ -962,6 +989,14 @@ static dsa_status enc_stage_uploads(dsa_context *ctx, EncLane &lane, hostutil::T
   turn.acquire_a();
   ENC_TRY(enc_upload(lane, ck.arena, lane.st, all ? L.uploads : L.uploads_a));
   if (all) turn.release();
+  if (!L.copies_a.empty()) {      // the ids of the coded faces, device to device from the repair arena (behind the upload: a piece of it covers the gaps between its regions)
+    static_assert(sizeof(EncCopy) == sizeof(dsa::PackItem) && offsetof(EncCopy, src_off) == offsetof(dsa::PackItem, packed_off) && offsetof(EncCopy, bytes) == offsetof(dsa::PackItem, len), "EncCopy is a PackItem");
+    const uint32_t nc = (uint32_t)L.copies_a.size();        // (the layout's: alive until the chunk ends)
+    ENC_TRY(lane.items.ensure(sizeof(dsa::PackItem) * nc));
+    ENC_TRY(hipMemcpyAsync(lane.items.p, L.copies_a.data(), sizeof(dsa::PackItem) * nc, hipMemcpyHostToDevice, lane.st));
+    hipLaunchKernelGGL(dsa::k_enc_unpack, dim3(nc), dim3(256), 0, lane.st, ck.arena, (const uint8_t *)lane.repair.p, (const dsa::PackItem *)lane.items.p, nc);
+    ENC_TRY(hipGetLastError());
+  }
   ENC_TRY(hipMemcpyAsync(ck.d_streams, L.streams.data(), sizeof(dsa::EncStream) * L.streams.size(), hipMemcpyHostToDevice, lane.st));
   return DSA_OK;
 }
@@ -1665,9 +1700,10 @@ void dsa_encode_default_grid_options(dsa_encode_grid_options *o) {
   memset(o, 0, sizeof(*o));
   dsa_encode_default_repair_options(&o->repair);
 }
-static dsa_status encode_grid_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_grid_options *options, dsa_encoded **out) {
+static dsa_status encode_grid_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_grid_options *options, dsa_encoded **out, bool corner_repair = false) {
   EncRequest rq = enc_request(n, false);
   rq.listed = meshes;
+  rq.corner_repair = corner_repair;
   int32_t topology = 0;
   if (options) {
     if (options->weld_points != 0 && options->weld_points != 1)
@@ -1681,6 +1717,27 @@ static dsa_status encode_grid_batch(dsa_context *ctx, uint32_t n, const dsa_mesh
 }
 dsa_status dsa_encode_grid_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_grid_options *options, dsa_encoded **out) {
   DSA_GUARD(ctx, encode_grid_batch(ctx, n, meshes, grids, options, out));
+}
+// ---- dsa_encode_grid_batch with attributes given per corner coded over a repaired table (EncRequest::corner_repair; the second
+// pass of encode_repair_request, dsa_encode_repair.h: k_enc_repair_face_scan, k_enc_repair_ids).  With corner_repair = 0 it is
+// dsa_encode_grid_batch.
+void dsa_encode_default_seam_repair_options(dsa_encode_seam_repair_options *o) {
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  dsa_encode_default_grid_options(&o->grid);
+}
+static dsa_status encode_seam_repair_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_seam_repair_options *options, dsa_encoded **out) {
+  if (!options) return encode_grid_batch(ctx, n, meshes, grids, nullptr, out);
+  if (options->corner_repair != 0 && options->corner_repair != 1)
+    return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "corner_repair %d: 0 (refused as ever) or 1 (coded over the repaired table)", (int)options->corner_repair);
+  for (int k = 0; k < 7; ++k)
+    if (options->reserved[k] != 0) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "dsa_encode_seam_repair_options.reserved[%d] is not zero", k);
+  if (options->corner_repair == 1 && options->grid.repair.topology != 1)
+    return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "corner_repair 1 needs topology 1 (the reference's corner table), topology is %d", (int)options->grid.repair.topology);
+  return encode_grid_batch(ctx, n, meshes, grids, &options->grid, out, options->corner_repair == 1);
+}
+dsa_status dsa_encode_seam_repair_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_seam_repair_options *options, dsa_encoded **out) {
+  DSA_GUARD(ctx, encode_seam_repair_batch(ctx, n, meshes, grids, options, out));
 }
 static dsa_status encode_grid_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_sequential_options *options, dsa_encoded **out) {
   EncRequest rq = enc_request(n, true);

@@ -313,6 +313,7 @@ struct CornerTable {
   // row[v]: the caller's value row of vertex v of this table (repair mode only; empty: the vertex is its own row)
   std::vector<uint32_t> row;
   bool needed_repair = false;      // build_repaired: the mesh is not one build() takes
+  std::vector<uint32_t> cmap;      // from_repaired: source corner -> coded corner, kInvalid on a degenerate face (u32[3F])
   uint32_t row_of(uint32_t v) const { return row.empty() ? v : row[v]; }
 
   static void repair(const uint32_t *faces, uint32_t num_faces, uint32_t num_vertices, Repaired &r) {
@@ -432,7 +433,8 @@ struct CornerTable {
   void from_repaired(const Repaired &r, const uint32_t *faces, uint32_t num_faces, uint32_t num_vertices) {
     check(r.degenerate < num_faces, "all triangles are degenerate");
     needed_repair = r.degenerate != 0 || r.isolated != 0 || r.breaks != 0 || r.num_vertices != num_vertices;
-    std::vector<uint32_t> vmap(r.num_vertices, kInvalid), cmap((size_t)num_faces * 3, kInvalid);
+    std::vector<uint32_t> vmap(r.num_vertices, kInvalid);
+    cmap.assign((size_t)num_faces * 3, kInvalid);
     uint32_t nf2 = 0;
     for (uint32_t f = 0; f < num_faces; ++f) {
       if (faces[3 * f] == faces[3 * f + 1] || faces[3 * f] == faces[3 * f + 2] || faces[3 * f + 1] == faces[3 * f + 2]) continue;
@@ -882,6 +884,7 @@ struct Options {
                                      // uint8, it writes the other types from MeshIn::extras (dsa_mesh_attr_input)
   int32_t repair_topology = 0;       // 1: the reference's corner table (CornerTable::build_repaired) in place of the refusal of degenerate
                                      // faces, non-manifold edges and vertices and isolated vertices; a clean mesh gives the same bytes
+                                     // 2: as 1, and attributes given per corner are coded over the repaired table (1 refuses them)
 };
 
 // Octahedral quantisation (OctahedronToolBox.cs:28-119)
@@ -1546,6 +1549,18 @@ struct MeshPlan {
   uint32_t num_att_data = 0;
   int64_t interior_edges = -1;       // >= 0: given (connectivity coded on the device, no corner table here); else counted from ct
   int64_t coded_vertices = -1, coded_faces = -1;      // >= 0: a repaired table's counts for the header (V' - isolated, F - degenerate); else the input's
+  // repair_topology = 2 over a mesh that needed repair: per attribute with ids, the ids of the coded faces (the source's
+  // non-degenerate faces in source order), which the attribute's corner_value then points at
+  std::vector<std::vector<uint32_t>> coded_ids;
+  void compact_ids() {
+    coded_ids.assign(atts.size(), std::vector<uint32_t>());
+    for (size_t k = 1; k < atts.size(); ++k) {
+      if (!atts[k].corner_value) continue;
+      coded_ids[k].resize(ct.nc());
+      for (size_t c = 0; c < ct.cmap.size(); ++c) if (ct.cmap[c] != kInvalid) coded_ids[k][ct.cmap[c]] = atts[k].corner_value[c];
+      atts[k].corner_value = coded_ids[k].data();
+    }
+  }
 };
 // What of a plan does not depend on the connectivity: attribute descriptors and the options that shape the stream.
 static void plan_attributes(const MeshIn &in, const Options &opt, MeshPlan &pl) {
@@ -1567,7 +1582,7 @@ static void plan_mesh(const MeshIn &in, const Options &opt, MeshPlan &pl) {
   if (opt.repair_topology) {
     pl.ct.build_repaired(in.faces, in.nf, in.nv);
     // (seam tables over a repaired table are not written yet: a mesh that needed no repair goes on as it always did)
-    check(!(in.normal_corners || in.uv_corners) || !pl.ct.needed_repair, "attributes given per corner over a mesh whose topology needs repair are not implemented");
+    check(!(in.normal_corners || in.uv_corners) || !pl.ct.needed_repair || opt.repair_topology == 2, "attributes given per corner over a mesh whose topology needs repair are not implemented");
     if (!pl.ct.needed_repair) pl.ct.row.clear();
     else { pl.coded_vertices = pl.ct.nv(); pl.coded_faces = pl.ct.nf(); }
   } else {
@@ -1580,6 +1595,7 @@ static void plan_mesh(const MeshIn &in, const Options &opt, MeshPlan &pl) {
   dfs_sequence(pl.ct, pl.eb.processed_corners, pl.seq);
   check(pl.seq.data_to_corner.size() == coded_vertices, "traversal did not reach every vertex");
   plan_attributes(in, opt, pl);
+  if (opt.repair_topology == 2 && pl.ct.needed_repair) pl.compact_ids();      // (value 1 has refused above)
   if (pl.valence) valence_context_symbols(pl.ct, pl.eb, pl.ctx_symbols);
   if (pl.predictive) predictive_symbols(pl.ct, pl.eb, pl.explicit_symbols, pl.predictions);
   if (pl.traversal_method != 0) {

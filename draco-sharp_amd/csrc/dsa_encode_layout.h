@@ -140,6 +140,7 @@ struct EncRequest {
   bool sequential = false;
   bool repair_scan = false;                // dsa_encode_repair_batch, topology = 1, the first pass: two faces turned against each other over the same vertices are refused too
   bool repair = false;                     // dsa_encode_repair_batch, topology = 1, the second pass: the meshes the first pass refused for their topology, on the repaired corner table
+  bool corner_repair = false;              // dsa_encode_seam_repair_batch, corner_repair = 1: the second pass codes attributes given per corner over the repaired table (else it refuses them)
   bool weld = false;                       // dsa_encode_points_batch / dsa_weld_batch: `listed` holds one row per point, every chunk welds its meshes first (enc_stage_weld)
   std::vector<synth::Welded> *weld_sink = nullptr;      // dsa_weld_batch: receives the weld of every mesh, nothing is coded
   const EncMeshGrids *grids = nullptr;     // dsa_encode_grid_batch / _sequential_batch: parallel to `listed` (null: every attribute on its own bounds)
@@ -159,10 +160,11 @@ static synth::Options enc_synth_options(const EncRequest &rq) {
   if (rq.sequential) return opt;
   opt.single_connectivity = od.single_connectivity; opt.pos_prediction = od.position_prediction; opt.uv_prediction = od.texcoord_prediction;
   opt.normal_prediction = rq.level.ex.normal_prediction; opt.traversal_method = rq.level.traversal_method;
-  opt.repair_topology = rq.repair ? 1 : 0;
+  opt.repair_topology = rq.repair ? (rq.corner_repair ? 2 : 1) : 0;
   return opt;
 }
 
+struct EncCopy { uint64_t off, src_off; uint32_t bytes, pad; };      // a region filled from the lane's repair arena (enc_stage_uploads), not from host memory; the layout of dsa::PackItem
 struct EncUpload { uint64_t off; const void *src; size_t bytes; bool narrow; };       // narrow: src is u32[bytes / 2], the staging copy keeps the low halves
 // The arena, handed out in 256-byte aligned regions one behind the other.
 struct EncArena {
@@ -176,6 +178,7 @@ struct EncLayout {
   std::vector<dsa::EncConn> conns;          // device connectivity: one per mesh (a mesh that failed the host's checks: F = 0, no arrays)
   std::vector<dsa::EncSeam> seams;          // device connectivity: one per (mesh, attribute given per corner)
   std::vector<dsa::EncSeqIdx> idx;          // sequential, compressed indices: one per mesh
+  std::vector<EncCopy> copies_a;            // phase A, a repaired table with corner ids: the ids of the coded faces, which k_enc_repair_ids left on the device
   std::vector<EncUpload> uploads_a, uploads;      // phase A: what the walks need (the faces, the corner ids; device connectivity only); the rest
   std::vector<uint32_t> first_stream;       // streams of mesh i: first_stream[i] .. first_stream[i + 1]
   uint64_t input_bytes = 0, total_bytes = 0;      // the uploads fill [0, input_bytes); the kernels' regions lie behind
@@ -209,6 +212,10 @@ struct EncChunk {
   // counted out (ct.c2v, ct.opp, ct.row), which the layout uploads in place of the caller's faces
   std::vector<std::vector<uint32_t>> c2row;
   std::vector<synth::CornerTable> rep;
+  // ... and with corner ids (EncRequest::corner_repair), per mesh and attribute of the plan: where in the lane's repair arena the ids
+  // of the coded faces lie, in the width ids_narrow says (kNoIds: the attribute has no ids)
+  static constexpr uint64_t kNoIds = ~0ull;
+  std::vector<std::vector<uint64_t>> rep_ids;
   std::vector<dsa::EncRepairRows> rep_rows;
   // a weld request (EncRequest::weld): the weld of every mesh, in buffers of the chunk's own, and the welded meshes in the form
   // every stage behind enc_stage_weld reads (mesh(i) / corner(i) / attr(i) point here instead of at the caller's arrays)
@@ -367,7 +374,7 @@ static void enc_plan_mesh(EncChunk &ck, uint32_t i) {
     if (!why.empty()) return ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, why);
   }
   // (every mesh of a repair request is one whose topology the first pass refused)
-  if (ck.rq.repair && (in.normal_corners || in.uv_corners))
+  if (ck.rq.repair && !ck.rq.corner_repair && (in.normal_corners || in.uv_corners))
     return ck.refuse(i, DSA_ERR_NOT_IMPLEMENTED, "attributes given per corner (normal_corners / texcoord_corners) over a mesh whose topology needs repair are not implemented");
   try {
     synth::check(m.positions && m.faces && m.num_vertices >= 3 && m.num_faces >= 1, "mesh needs positions and faces");
@@ -552,7 +559,11 @@ static void enc_layout(EncChunk &ck) {
       dsa::EncSeam Z;
       memset(&Z, 0, sizeof(Z));
       Z.mesh = i; Z.stream = L.first_stream[i] + (uint32_t)k; Z.ids_narrow = ck.ids_narrow(i, atts[k]) ? 1u : 0u; Z.rows = ck.rows_of(i, atts[k]);
-      Z.ids = A.put(L.uploads_a, atts[k].corner_value, (Z.ids_narrow ? 6ull : 12ull) * C.F, Z.ids_narrow != 0);
+      const uint64_t id_bytes = (Z.ids_narrow ? 6ull : 12ull) * C.F;
+      if (!ck.rep_ids.empty() && k < ck.rep_ids[i].size() && ck.rep_ids[i][k] != EncChunk::kNoIds) {      // (atts[k].corner_value is the caller's array, over the source's faces)
+        Z.ids = A.take(id_bytes);
+        L.copies_a.push_back({Z.ids, ck.rep_ids[i][k], (uint32_t)id_bytes, 0});
+      } else Z.ids = A.put(L.uploads_a, atts[k].corner_value, id_bytes, Z.ids_narrow != 0);
       L.seams.push_back(Z);
     }
   }

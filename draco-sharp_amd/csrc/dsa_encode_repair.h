@@ -10,6 +10,9 @@
 // degenerate faces and the isolated vertices out and lays the mesh out at its real size; from there it takes the kernels of
 // dsa_encode_conn.h like any other mesh, its opposites given (k_enc_table_opposites would join edges the repair cut) and its value
 // rows read through the row of every vertex (k_enc_repair_rows).  Clean meshes never come here.
+// Attributes given per corner (dsa_encode_seam_repair_batch, corner_repair = 1) come along: their ids go up with the faces,
+// k_enc_repair_face_scan / k_enc_repair_ids leave the ids of the coded faces on the device, in the width the layout takes them, and
+// enc_stage_uploads copies them into the chunk's arena; the seam kernels (dsa_encode_seams.h) then run over the repaired chunk.
 //
 // Grid-parallel (blocks per mesh x meshes): the marks of degenerate faces, corners by vertex, the matching, the isolated count.
 //   The half-edges of one undirected edge interact with no others: the thread of the edge's first corner replays the edge's queue
@@ -38,6 +41,9 @@ struct EncRepair {                 // one per mesh; device memory, mirrored on t
   uint32_t F, V;
   uint32_t num_vertices, isolated, degenerate, breaks;     // OUTPUT
   uint32_t status, detail;
+  // attributes given per corner over the repaired table (dsa_encode_seam_repair_batch, corner_repair = 1; 0 / unset otherwise)
+  uint64_t fmap;                   // u32[F] OUTPUT of k_enc_repair_face_scan: the coded index of a source face, INVALID for a degenerate one
+  uint32_t coded_faces, pad;       // OUTPUT: F - degenerate, as the scan counted them
 };
 enum { ENC_REPAIR_OK = 0, ENC_REPAIR_BOUND = 1 };
 static inline const char *enc_repair_message(uint32_t status) {
@@ -70,6 +76,65 @@ __global__ __launch_bounds__(256) void k_enc_repair_mark(uint8_t *arena, EncRepa
     atomicAdd(&voff[a + 1], 1u); atomicAdd(&voff[b + 1], 1u); atomicAdd(&voff[c + 1], 1u);
   }
   if (degenerate) atomicAdd(&E->degenerate, degenerate);
+}
+
+// ---- attributes given per corner over a repaired table: the ids of the coded faces.  The table the layout takes has the
+// degenerate faces counted out (CornerTable::from_repaired: the source's other faces in source order), so the id of source corner
+// 3f + k belongs at 3f' + k.  The scan: one wave per mesh over the marks k_enc_repair_mark left (bvis of a face's first corner;
+// launched before the break pass, which marks what it visits), 64 faces a round by ballot.  Then one thread per source corner of
+// every (mesh, attribute with ids) record: the id checked against the attribute's row count (the host coder's "id out of range",
+// degenerate faces included) and stored narrow or wide by the layout's rule (EncChunk::ids_narrow: rows <= 65 536 -> u16).
+struct EncRepairIds {              // one per (mesh, attribute with ids); device memory, mirrored on the host
+  uint64_t src;                    // u32[3F] input: the caller's id per source corner
+  uint64_t dst;                    // u16[3F'] / u32[3F'] OUTPUT (room for 3F)
+  uint32_t rep;                    // the mesh's EncRepair
+  uint32_t rows, narrow;           // value rows of the attribute; 1: u16 output
+  uint32_t att_type;               // 1 normals, 3 texture coordinates (which message a bad id earns)
+  uint32_t bad, pad;               // OUTPUT: 1 an id is not below `rows`
+};
+__global__ __launch_bounds__(WAVE) void k_enc_repair_face_scan(uint8_t *arena, EncRepair *reps, uint32_t n) {
+  const uint32_t mesh = blockIdx.x, lane = threadIdx.x;
+  if (mesh >= n) return;
+  EncRepair *E = &reps[mesh];
+  if (E->status != ENC_REPAIR_OK || !E->fmap) return;
+  const uint32_t F = E->F;
+  const uint8_t *bvis = arena + E->bvis;
+  uint32_t *fmap = (uint32_t *)(arena + E->fmap);
+  uint32_t base = 0;
+#if defined(__HIPCC__)
+  const uint64_t below = (1ull << lane) - 1ull;
+  for (uint32_t f0 = 0; f0 < F; f0 += WAVE) {
+    const uint32_t f = f0 + lane;
+    const bool kept = f < F && bvis[3u * f] == 0;
+    const uint64_t km = __ballot(kept);
+    if (f < F) fmap[f] = kept ? base + (uint32_t)__popcll(km & below) : DSA_INVALID;
+    base += (uint32_t)__popcll(km);
+  }
+#else       // the sanitizer build of tests/hostcheck runs the lanes of a wave one after the other: lane 0 counts
+  if (lane == 0) for (uint32_t f = 0; f < F; ++f) fmap[f] = bvis[3u * f] == 0 ? base++ : DSA_INVALID;
+#endif
+  if (lane == 0) E->coded_faces = base;
+}
+__global__ __launch_bounds__(256) void k_enc_repair_ids(uint8_t *arena, const EncRepair *reps, EncRepairIds *ids, uint32_t n) {
+  const uint32_t r = blockIdx.y;
+  if (r >= n) return;
+  EncRepairIds *I = &ids[r];
+  const EncRepair *E = &reps[I->rep];
+  if (E->status != ENC_REPAIR_OK || !E->fmap) return;
+  const uint32_t NC = 3u * E->F, rows = I->rows;
+  const uint32_t *fmap = (const uint32_t *)(arena + E->fmap), *src = (const uint32_t *)(arena + I->src);
+  uint16_t *dst16 = (uint16_t *)(arena + I->dst);
+  uint32_t *dst32 = (uint32_t *)(arena + I->dst);
+  const bool narrow = I->narrow != 0;
+  bool bad = false;
+  for (uint32_t c = blockIdx.x * blockDim.x + threadIdx.x; c < NC; c += gridDim.x * blockDim.x) {
+    const uint32_t id = src[c], f = c / 3u, to = fmap[f];
+    if (id >= rows) { bad = true; continue; }
+    if (to == DSA_INVALID) continue;
+    const uint32_t at = 3u * to + (c - 3u * f);                // (to < F' <= F: inside the room for 3F)
+    if (narrow) dst16[at] = (uint16_t)id; else dst32[at] = id;
+  }
+  if (bad) I->bad = 1;                                         // (every writer stores the same word)
 }
 
 // exclusive prefix sum, one wave per mesh (k_enc_table_offsets on these records); a vertex without a corner is isolated

@@ -37,7 +37,11 @@ class Config:
     repair_topology (dsa_encode_repair_batch, topology 1): meshes with degenerate faces, the same face twice, fins, faces turned
     over, fans that meet at a vertex or vertices no face uses are coded on the reference's repaired corner table (CornerTable.cs:
     28-43) instead of being refused; clean meshes give the same bytes.  Edgebreaker streams only; attributes given per corner over
-    a mesh that needs the repair are not implemented.
+    a mesh that needs the repair are refused as not implemented, unless repair_seams is set.
+
+    repair_seams (dsa_encode_seam_repair_batch, corner_repair 1; needs repair_topology): a mesh that needs the repair and carries
+    normal_corners / texcoord_corners -- or, with weld_points, UV charts and hard edges -- is coded: the ids of the faces that are
+    not degenerate over the repaired table, its cut edges boundaries of every attribute.  Every other mesh gives the bytes it gave.
 
     weld_points (dsa_encode_points_batch): the rows of a MeshData are per point, not per vertex -- a glTF primitive, an OBJ after
     triangulation, Batch.vertex_arrays: points are duplicated wherever a UV chart or a hard edge passes.  Points with byte-equal
@@ -55,7 +59,8 @@ class Config:
 
     def __init__(self, position_bits=11, texcoord_bits=10, normal_bits=8, speed=5, single_connectivity=False,
                  symbol_scheme=-1, position_prediction=1, texcoord_prediction=1, edgebreaker_method=0, normal_prediction=0,
-                 encoding_method=1, compress_connectivity=False, multi_parallelogram=0, traversal_method=0, repair_topology=False, weld_points=False):
+                 encoding_method=1, compress_connectivity=False, multi_parallelogram=0, traversal_method=0, repair_topology=False, weld_points=False,
+                 repair_seams=False):
         for name, value, legal in (("encoding_method", encoding_method, self.ENCODING_METHODS),
                                    ("edgebreaker_method", edgebreaker_method, self.EDGEBREAKER_METHODS),
                                    ("position_prediction", position_prediction, self.POSITION_PREDICTIONS),
@@ -78,6 +83,9 @@ class Config:
             raise ValueError("repair_topology shapes Edgebreaker streams: a sequential stream takes any list of triangles as it is")
         if self.leveled and self.sequential:
             raise ValueError("multi_parallelogram / traversal_method shape Edgebreaker streams: a sequential stream predicts by Difference in point order")
+        self.repair_seams = bool(repair_seams)
+        if self.repair_seams and not self.repair_topology:
+            raise ValueError("repair_seams codes attributes given per corner over the repaired corner table: it needs repair_topology=True")
         self.weld_points = bool(weld_points)
         if self.weld_points and self.sequential:
             raise ValueError("weld_points shapes Edgebreaker streams: a sequential stream keeps the caller's points as they are")
@@ -476,14 +484,26 @@ class DracoEncoder:
                 ci.num_normals = len(m.normals) if m.normals is not None else 0
                 ci.num_texcoords = len(m.texcoords) if m.texcoords is not None else 0
         grids = None
+        seams = getattr(config, "repair_seams", False)      # dsa_encode_seam_repair_batch: the grid call's input and options (grids or none), and the corner switch
         if gridded:
             grids = (native.MeshGrids * max(1, n))()
             for i, m in enumerate(meshes):
                 _fill_grids(grids[i], m, keep)
+        if gridded or seams:
             gopt = native.EncodeGridOptions()
             L.dsa_encode_default_grid_options(C.byref(gopt))
             gopt.repair = config._native_repair()
             gopt.weld_points = 1 if weld else 0
+        if seams:
+            sopt = native.EncodeSeamRepairOptions()
+            L.dsa_encode_default_seam_repair_options(C.byref(sopt))
+            sopt.grid = gopt
+            sopt.corner_repair = 1
+            h = C.c_void_p()
+            st = L.dsa_encode_seam_repair_batch(ctx._h, n, arr, grids, C.byref(sopt), C.byref(h))
+            if st != 0:
+                _raise(st, ctx.error())
+            return (ctx, h, n) if handle else EncodedStreams(ctx, h, n)
         opt = gopt if gridded else config._native_repair() if repair else config._native_level() if level else (config._native_ex() if (ex or listed) else config._native())
         h = C.c_void_p()
         t0 = time.perf_counter()

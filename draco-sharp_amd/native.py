@@ -35,6 +35,7 @@ EXPORTS = [
     "dsa_encode_default_repair_options", "dsa_encode_repair_batch",
     "dsa_encode_points_batch", "dsa_weld_batch", "dsa_welded_size", "dsa_welded_mesh", "dsa_welded_free",
     "dsa_encode_default_grid_options", "dsa_encode_grid_batch", "dsa_encode_grid_sequential_batch",
+    "dsa_encode_default_seam_repair_options", "dsa_encode_seam_repair_batch",
     "dsa_encoded_size", "dsa_encoded_stream", "dsa_encoded_free",
     "dsa_pool_create", "dsa_pool_destroy", "dsa_pool_size", "dsa_pool_last_error", "dsa_pool_decode", "dsa_pool_job_locate",
     "dsa_pool_job_chunks", "dsa_pool_job_free", "dsa_pool_plan",
@@ -118,6 +119,12 @@ class MeshGrids(C.Structure):
 class EncodeGridOptions(C.Structure):
     """dsa_encode_grid_options: the options of dsa_encode_repair_batch, and weld_points (1: the input of dsa_encode_points_batch)."""
     _fields_ = [("repair", EncodeRepairOptions), ("weld_points", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+class EncodeSeamRepairOptions(C.Structure):
+    """dsa_encode_seam_repair_options: the options of dsa_encode_grid_batch, and corner_repair (1: attributes given per corner are
+    coded over a mesh whose topology needs the repair; needs topology 1)."""
+    _fields_ = [("grid", EncodeGridOptions), ("corner_repair", C.c_int32), ("reserved", C.c_int32 * 7)]
 
 
 class WeldedInfo(C.Structure):
@@ -272,6 +279,10 @@ def lib():
             L.dsa_encode_default_grid_options.restype = None
             L.dsa_encode_grid_batch.argtypes = [vp, u32, C.POINTER(MeshAttrInput), C.POINTER(MeshGrids), C.POINTER(EncodeGridOptions), C.POINTER(vp)]
             L.dsa_encode_grid_sequential_batch.argtypes = [vp, u32, C.POINTER(MeshAttrInput), C.POINTER(MeshGrids), C.POINTER(EncodeSequentialOptions), C.POINTER(vp)]
+        if hasattr(L, "dsa_encode_seam_repair_batch"):
+            L.dsa_encode_default_seam_repair_options.argtypes = [C.POINTER(EncodeSeamRepairOptions)]
+            L.dsa_encode_default_seam_repair_options.restype = None
+            L.dsa_encode_seam_repair_batch.argtypes = [vp, u32, C.POINTER(MeshAttrInput), C.POINTER(MeshGrids), C.POINTER(EncodeSeamRepairOptions), C.POINTER(vp)]
         L.dsa_encoded_size.restype = u32
         L.dsa_encoded_size.argtypes = [vp]
         L.dsa_encoded_stream.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(C.c_size_t)]

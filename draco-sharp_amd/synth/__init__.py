@@ -199,6 +199,8 @@ def lib():
 
 
 def options(**kw):
+    """synth_options with the given fields set.  repair_topology: 0 strict, 1 the reference's repaired corner table, 2 as 1 and
+    attributes given per corner (encode_mesh_corners, encode_mesh_points, encode_grid) are coded over it (1 refuses them)."""
     o = Options()
     lib().synth_default_options(C.byref(o))
     for k, v in kw.items():

@@ -478,8 +478,9 @@ dsa_status dsa_encode_level_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_a
  * kernels of their own, dsa_encode_repair.h; with host connectivity -- DSA_ENC_HOST_CONN, batches below 256 meshes -- the host
  * coder's table).  Per mesh with topology = 1: every face degenerate or num_faces = 0 fails with DSA_ERR_INVALID_DATA ("all
  * triangles are degenerate"); an index out of range, missing positions and the attribute-list checks fail as they do today; a
- * mesh with normal_corners / texcoord_corners whose position table needs repair fails alone with DSA_ERR_NOT_IMPLEMENTED (seam
- * tables over a repaired table are not written yet; with clean topology it is coded as by dsa_encode_level_batch).  topology
+ * mesh with normal_corners / texcoord_corners whose position table needs repair fails alone with DSA_ERR_NOT_IMPLEMENTED (this
+ * call writes no seam tables over a repaired table, dsa_encode_seam_repair_batch does; with clean topology it is coded as by
+ * dsa_encode_level_batch).  topology
  * outside {0, 1} or a non-zero reserved word fails the call with DSA_ERR_INVALID_ARGUMENT and dsa_last_error names the field.
  * The streams are byte-identical to the CPU coder's with repair_topology = 1.  Added after ABI 4 without changing it: callers
  * detect the feature by the symbol dsa_encode_repair_batch. */
@@ -505,7 +506,7 @@ dsa_status dsa_encode_repair_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_
  *     unless no vertex has two of them: then as one row per vertex (the row of the vertex's representative), without ids.
  * The welded mesh is coded as dsa_encode_repair_batch codes it, with the same options, and every per-mesh failure of that call
  * stays (a face degenerate after the weld, a non-manifold edge or vertex under topology = 0, ids with single_connectivity = 1,
- * seams over a table that needs repair: DSA_ERR_NOT_IMPLEMENTED).  A mesh with corner ids set fails alone with
+ * seams over a table that needs repair: DSA_ERR_NOT_IMPLEMENTED -- see dsa_encode_seam_repair_batch).  A mesh with corner ids set fails alone with
  * DSA_ERR_INVALID_ARGUMENT.  The streams are byte-identical to the CPU coder's on the welded mesh.  Added after ABI 4 without
  * changing it: callers detect the feature by the symbol dsa_encode_points_batch. */
 dsa_status dsa_encode_points_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes,
@@ -576,6 +577,26 @@ void dsa_encode_default_grid_options(dsa_encode_grid_options *options);
 /* `grids` is parallel to `meshes` (or NULL). */
 dsa_status dsa_encode_grid_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids,
                                  const dsa_encode_grid_options *options, dsa_encoded **out);
+/* dsa_encode_grid_batch that also codes attributes given per corner over a mesh whose topology needs the repair -- the asset from
+ * the wild: UV charts and hard edges, and a doubled face, a fin, a sliver with a repeated index, a bow-tie, a two-sided sheet.
+ * corner_repair = 1 (needs grid.repair.topology = 1, else the call fails with DSA_ERR_INVALID_ARGUMENT): such a mesh, which the
+ * calls above refuse with DSA_ERR_NOT_IMPLEMENTED, is coded on the repaired table: the ids of the faces that are not degenerate,
+ * in source order, the attribute seams over the repaired table's edges (an edge the repair cut is a boundary), positions read
+ * through the row of every vertex.  Row counts and quantisation bounds stay those of all rows passed.  An id not below its row
+ * count fails the mesh alone ("normal id out of range" / "texture coordinate id out of range"), degenerate faces included.  With
+ * weld_points = 1 the input is one row per point, else normal_corners / texcoord_corners are the caller's.  Meshes that need no
+ * repair, and every mesh under corner_repair = 0, give the bytes and the messages of dsa_encode_grid_batch.  corner_repair
+ * outside {0, 1} or a non-zero reserved word fails the call.  The streams are byte-identical to the CPU coder's with
+ * repair_topology = 2.  single_connectivity with ids stays refused.  Added after ABI 4 without changing it: callers detect the
+ * feature by the symbol dsa_encode_seam_repair_batch. */
+typedef struct dsa_encode_seam_repair_options {
+  dsa_encode_grid_options grid;            /* as for dsa_encode_grid_batch, same legal values */
+  int32_t corner_repair;                   /* 0 (default): per-corner attributes over a mesh that needs repair are refused as ever; 1: coded */
+  int32_t reserved[7];                     /* must be zero */
+} dsa_encode_seam_repair_options;
+void dsa_encode_default_seam_repair_options(dsa_encode_seam_repair_options *options);
+dsa_status dsa_encode_seam_repair_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids,
+                                        const dsa_encode_seam_repair_options *options, dsa_encoded **out);
 /* The same for sequential meshes and point clouds (dsa_encode_attributes_sequential_batch). */
 dsa_status dsa_encode_grid_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids,
                                             const dsa_encode_sequential_options *options, dsa_encoded **out);
