@@ -781,7 +781,7 @@ static dsa_status enc_stage_weld(dsa_context *ctx, EncLane &lane, hostutil::Turn
   uint32_t most = 1;
   for (uint32_t i = 0; i < n && !on_host; ++i) {
     if (!ck.good(i)) continue;
-    const dsa_mesh_input &m = ck.rq.listed[ck.base + i].mesh.mesh;
+    const dsa_mesh_input &m = ck.rq.mesh(ck.base + i);
     if (m.num_vertices > (1u << 28) || m.num_faces > (1u << 28)) { ck.refuse(i, DSA_ERR_INVALID_DATA, "mesh too large for the device weld"); continue; }
     uint32_t row_bytes[dsa::EW_MAX_SEGS];
     if (keys[i].size() + 2 > dsa::EW_MAX_SEGS) { ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, "too many attributes for the device weld"); continue; }
@@ -799,7 +799,7 @@ static dsa_status enc_stage_weld(dsa_context *ctx, EncLane &lane, hostutil::Turn
   if (on_host) {
     hostutil::parallel_for(n, [&](uint32_t i) {
       if (!ck.good(i)) return;
-      const dsa_mesh_input &m = ck.rq.listed[ck.base + i].mesh.mesh;
+      const dsa_mesh_input &m = ck.rq.mesh(ck.base + i);
       try { synth::weld_points(m.num_vertices, m.faces, m.num_faces, keys[i], m.normals, m.texcoords, ck.weld[i]); }
       catch (const std::exception &e) { ck.refuse(i, DSA_ERR_INVALID_DATA, e.what()); }
     });
@@ -871,7 +871,7 @@ static dsa_status enc_stage_weld(dsa_context *ctx, EncLane &lane, hostutil::Turn
 // host phase 1: checks, connectivity, traversal order, operand entries (threads over meshes)
 static dsa_status enc_stage_plans(dsa_context *ctx, EncChunk &ck) {
   // (the quantisation bits of an Edgebreaker call are checked here, per chunk: a call with n = 0 has no chunk and returns DSA_OK
-  // whatever they are, while a sequential call checks them up front -- enc_check_request)
+  // whatever they are, while a sequential call checks them up front -- enc_check_options)
   if (enc_check_bits(ctx, ck.rq.base()) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
   enc_begin_plans(ck, enc_host_choice("DSA_ENC_HOST_CONN", ck.batch_n), enc_host_choice("DSA_ENC_HOST_PLAN", ck.batch_n));
   hostutil::parallel_for(ck.n, [&](uint32_t i) { if (ck.good(i)) enc_plan_mesh(ck, i); });          // (a mesh the weld refused stays refused) capped thread count, every thread joined on every path (dsa_host_util.h)
@@ -1292,46 +1292,56 @@ static dsa_status weld_chunk(dsa_context *ctx, EncLane &lane, const EncRequest &
 
 #include "dsa_encode_sequential.h"
 
-// The prediction methods the device coder writes; any other value would put a method byte in front of data it does not describe.
-static dsa_status check_schemes(dsa_context *ctx, const dsa_encode_options *o, const dsa_encode_options_ex *ex) {
-  if (o && o->position_prediction != 0 && o->position_prediction != 1)
-    return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "position_prediction %d: the encoder writes 0 (difference) or 1 (parallelogram)", (int)o->position_prediction);
-  if (o && o->texcoord_prediction != 0 && o->texcoord_prediction != 1 && o->texcoord_prediction != 5)
-    return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "texcoord_prediction %d: the encoder writes 0 (difference), 1 (parallelogram) or 5 (TexCoordsPortable)", (int)o->texcoord_prediction);
-  if (!ex) return DSA_OK;
-  if (ex->edgebreaker_method != 0 && ex->edgebreaker_method != 2 && ex->edgebreaker_method != -1)
-    return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "edgebreaker_method %d: 0 (standard), 2 (valence) or -1 (by speed and face count)", (int)ex->edgebreaker_method);
-  if (ex->normal_prediction != 0 && ex->normal_prediction != 6)
-    return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "normal_prediction %d: 0 (difference) or 6 (GeometricNormal)", (int)ex->normal_prediction);
-  for (int k = 0; k < 6; ++k)
-    if (ex->reserved[k] != 0) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "dsa_encode_options_ex.reserved[%d] is not zero", k);
+// ---- the option check of every entry point, each layer once and the outermost first.  ENC_REFUSE: the call fails with this text.
+#define ENC_REFUSE(...) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, __VA_ARGS__)
+#define ENC_RESERVED(o, count, name) for (int k = 0; k < (count); ++k) if ((o).reserved[k] != 0) ENC_REFUSE(name ".reserved[%d] is not zero", k)
+// The prediction methods of `base` the device coder writes; any other value would put a method byte in front of data it does not
+// describe.  (They do not shape a sequential stream; values dsa_encode_batch refuses are refused all the same.)
+static dsa_status enc_check_base(dsa_context *ctx, const dsa_encode_options &o) {
+  if (o.position_prediction != 0 && o.position_prediction != 1)
+    ENC_REFUSE("position_prediction %d: the encoder writes 0 (difference) or 1 (parallelogram)", (int)o.position_prediction);
+  if (o.texcoord_prediction != 0 && o.texcoord_prediction != 1 && o.texcoord_prediction != 5)
+    ENC_REFUSE("texcoord_prediction %d: the encoder writes 0 (difference), 1 (parallelogram) or 5 (TexCoordsPortable)", (int)o.texcoord_prediction);
   return DSA_OK;
 }
-// The option check of every entry point: the schemes, then the fields of the level / the sequential options, then their reserved
-// words.  (The prediction fields of `base` do not shape a sequential stream; values dsa_encode_batch refuses are refused all the
-// same.  The quantisation bits of a sequential call are checked here, those of an Edgebreaker call per chunk: enc_stage_plans.)
-static dsa_status enc_check_request(dsa_context *ctx, const EncRequest &rq) {
-  if (check_schemes(ctx, &rq.base(), rq.sequential ? nullptr : &rq.level.ex) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
-  if (rq.sequential) {
-    const dsa_encode_sequential_options &d = rq.seq;
-    if (enc_check_bits(ctx, d.base) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
-    if (d.geometry != 0 && d.geometry != 1)
-      return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "geometry %d: 1 (triangular mesh) or 0 (point cloud)", (int)d.geometry);
-    if (d.compress_connectivity != 0 && d.compress_connectivity != 1)
-      return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "compress_connectivity %d: 0 (raw indices) or 1 (compressed)", (int)d.compress_connectivity);
-    for (int k = 0; k < 6; ++k)
-      if (d.reserved[k] != 0) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "dsa_encode_sequential_options.reserved[%d] is not zero", k);
-    return DSA_OK;
-  }
-  const dsa_encode_level_options &d = rq.level;
+// Edgebreaker streams: the widest options, in which every narrower entry point has left what it does not have at its default.
+// (The quantisation bits are checked per chunk: enc_stage_plans.)
+static dsa_status enc_check_options(dsa_context *ctx, const dsa_encode_seam_repair_options &s, bool null_argument) {
+  const dsa_encode_grid_options &g = s.grid;
+  const dsa_encode_repair_options &r = g.repair;
+  const dsa_encode_level_options &d = r.level;
+  const dsa_encode_options_ex &ex = d.ex;
+  if (s.corner_repair != 0 && s.corner_repair != 1) ENC_REFUSE("corner_repair %d: 0 (refused as ever) or 1 (coded over the repaired table)", (int)s.corner_repair);
+  ENC_RESERVED(s, 7, "dsa_encode_seam_repair_options");
+  if (s.corner_repair == 1 && r.topology != 1) ENC_REFUSE("corner_repair 1 needs topology 1 (the reference's corner table), topology is %d", (int)r.topology);
+  if (g.weld_points != 0 && g.weld_points != 1) ENC_REFUSE("weld_points %d: 0 (rows per vertex) or 1 (rows per point)", (int)g.weld_points);
+  ENC_RESERVED(g, 7, "dsa_encode_grid_options");
+  if (r.topology != 0 && r.topology != 1) ENC_REFUSE("topology %d: 0 (strict) or 1 (the reference's corner table)", (int)r.topology);
+  ENC_RESERVED(r, 7, "dsa_encode_repair_options");
+  if (null_argument) ENC_REFUSE("null argument");
+  if (enc_check_base(ctx, ex.base) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+  if (ex.edgebreaker_method != 0 && ex.edgebreaker_method != 2 && ex.edgebreaker_method != -1)
+    ENC_REFUSE("edgebreaker_method %d: 0 (standard), 2 (valence) or -1 (by speed and face count)", (int)ex.edgebreaker_method);
+  if (ex.normal_prediction != 0 && ex.normal_prediction != 6) ENC_REFUSE("normal_prediction %d: 0 (difference) or 6 (GeometricNormal)", (int)ex.normal_prediction);
+  ENC_RESERVED(ex, 6, "dsa_encode_options_ex");
   if (d.multi_parallelogram != 0 && d.multi_parallelogram != 2 && d.multi_parallelogram != 4 && d.multi_parallelogram != -1)
-    return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "multi_parallelogram %d: 0 (off), 2 (MultiParallelogram), 4 (ConstrainedMultiParallelogram) or -1 (by speed and vertex count)", (int)d.multi_parallelogram);
+    ENC_REFUSE("multi_parallelogram %d: 0 (off), 2 (MultiParallelogram), 4 (ConstrainedMultiParallelogram) or -1 (by speed and vertex count)", (int)d.multi_parallelogram);
   if (d.traversal_method != 0 && d.traversal_method != 1 && d.traversal_method != 2)
-    return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "traversal_method %d: 0 (depth first), 1 (prediction degree for the positions' decoder) or 2 (for every decoder without interior seams)", (int)d.traversal_method);
-  for (int k = 0; k < 6; ++k)
-    if (d.reserved[k] != 0) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "dsa_encode_level_options.reserved[%d] is not zero", k);
+    ENC_REFUSE("traversal_method %d: 0 (depth first), 1 (prediction degree for the positions' decoder) or 2 (for every decoder without interior seams)", (int)d.traversal_method);
+  ENC_RESERVED(d, 6, "dsa_encode_level_options");
   return DSA_OK;
 }
+// sequential streams (their quantisation bits are checked here, up front)
+static dsa_status enc_check_options(dsa_context *ctx, const dsa_encode_sequential_options &d, bool null_argument) {
+  if (null_argument) ENC_REFUSE("null argument");
+  if (enc_check_base(ctx, d.base) != DSA_OK || enc_check_bits(ctx, d.base) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+  if (d.geometry != 0 && d.geometry != 1) ENC_REFUSE("geometry %d: 1 (triangular mesh) or 0 (point cloud)", (int)d.geometry);
+  if (d.compress_connectivity != 0 && d.compress_connectivity != 1) ENC_REFUSE("compress_connectivity %d: 0 (raw indices) or 1 (compressed)", (int)d.compress_connectivity);
+  ENC_RESERVED(d, 6, "dsa_encode_sequential_options");
+  return DSA_OK;
+}
+#undef ENC_RESERVED
+#undef ENC_REFUSE
 
 // the context's lanes, `lanes` of them at least (kept between calls)
 static dsa_status enc_ensure_lanes(dsa_context *ctx, uint32_t lanes) {
@@ -1433,7 +1443,7 @@ static dsa_status enc_stage_grids(dsa_context *ctx, const EncRequest &rq, std::v
   for (uint32_t i = 0; i < rq.n; ++i) {
     EncMeshGrids &g = grids[i];
     if (g.error) continue;
-    const dsa_mesh_attr_input &am = rq.listed[i];
+    const dsa_mesh_attr_input &am = rq.attr(i);
     const dsa_mesh_input &m = am.mesh.mesh;
     auto shared = [](const synth::Grid &x) { return x.mode == 2 && x.reserved[0] == 0 && x.reserved[1] == 0; };
     auto take = [&](uint32_t slot, uint32_t nc, uint32_t rows, const void *src) {
@@ -1510,6 +1520,99 @@ static dsa_status enc_stage_grids(dsa_context *ctx, const EncRequest &rq, std::v
   return DSA_OK;
 }
 
+// A checked request through its chunks.  batch_n: the size of the batch the request belongs to (what chooses between host and
+// device connectivity); 0: the request's own
+static dsa_status encode_request(dsa_context *ctx, const EncRequest &rq, dsa_encoded **out, uint32_t batch_n = 0) {
+  if (batch_n == 0) batch_n = rq.n;
+  return encode_batch_chunks(ctx, rq.n, [&](dsa_context *sink, EncLane &lane, uint32_t base, uint32_t cnt, dsa_encoded **part) {
+    if (rq.weld_sink) return weld_chunk(sink, lane, rq, base, cnt, batch_n, part);
+    return rq.sequential ? encode_sequential_chunk(sink, lane, rq, base, cnt, rq.n, part) : encode_chunk(sink, lane, rq, base, cnt, batch_n, part);
+  }, out);
+}
+// dsa_encode_repair_batch, topology = 1: the batch as dsa_encode_level_batch codes it; then the meshes refused for their topology
+// once more as a request of their own, on the repaired corner table (EncRequest::repair), their results into the first's places.
+// Clean meshes take the kernels they always took and nothing else.
+static bool enc_topology_refusal(const std::string &why) {
+  for (uint32_t s : {(uint32_t)dsa::ENC_DEGENERATE, (uint32_t)dsa::ENC_NONMANIFOLD_EDGE, (uint32_t)dsa::ENC_RING, (uint32_t)dsa::ENC_NONMANIFOLD_VERTEX, (uint32_t)dsa::ENC_ISOLATED})
+    if (why == dsa::enc_conn_message(s)) return true;
+  return false;
+}
+static dsa_status encode_repair_request(dsa_context *ctx, const EncRequest &request, dsa_encoded **out) {
+  EncRequest rq = request;
+  rq.repair_scan = true;
+  const dsa_status st = encode_request(ctx, rq, out);
+  if (st != DSA_OK || rq.n == 0) return st;
+  std::unique_ptr<dsa_encoded> E(*out);
+  *out = nullptr;
+  std::vector<uint32_t> again;
+  std::vector<dsa_mesh_attr_input> sub;
+  std::vector<EncMeshGrids> sub_grids;
+  for (uint32_t i = 0; i < rq.n; ++i) {
+    if (E->status[i] != DSA_ERR_INVALID_DATA) continue;
+    const dsa_mesh_input &m = rq.mesh(i);
+    if (m.positions && m.num_vertices >= 3 && m.num_faces == 0 && E->messages[i] == "mesh needs positions and faces") { E->messages[i] = "all triangles are degenerate"; continue; }
+    if (enc_topology_refusal(E->messages[i])) { again.push_back(i); sub.push_back(rq.attr(i)); if (rq.grids) sub_grids.push_back(rq.grids[i]); }
+  }
+  if (!again.empty()) {
+    EncRequest r2 = rq;
+    r2.repair_scan = false; r2.repair = true; r2.n = (uint32_t)again.size(); r2.meshes = sub.data(); r2.grids = rq.grids ? sub_grids.data() : nullptr;
+    dsa_encoded *second = nullptr;
+    const dsa_status s2 = encode_request(ctx, r2, &second, rq.n);
+    if (s2 != DSA_OK) return s2;
+    std::unique_ptr<dsa_encoded> E2(second);
+    for (uint32_t k = 0; k < r2.n; ++k) { E->streams[again[k]].swap(E2->streams[k]); E->status[again[k]] = E2->status[k]; E->messages[again[k]].swap(E2->messages[k]); }
+  }
+  *out = E.release();
+  return DSA_OK;
+}
+
+// ---- Every entry point: the widest options of its kind at their defaults, the layer the caller passed copied in, the meshes in
+// the widest form, and one way on under DSA_GUARD (host vectors and threads inside: nothing may unwind into the caller): the
+// option check, the caller's grids copied and the shared ones resolved once for the whole request (enc_stage_grids;
+// dsa_encode_grid.h), then the request through its chunks -- with topology 1 through both passes of encode_repair_request.
+// Each wider call with its added fields at their defaults is the very request of the narrower one.
+static dsa_status encode_checked(dsa_context *ctx, EncRequest &rq, const dsa_mesh_grids *grids, bool repair, dsa_encoded **out) {
+  std::vector<EncMeshGrids> taken;
+  if (grids && rq.n) {
+    taken.resize(rq.n);
+    bool any = false;
+    for (uint32_t i = 0; i < rq.n; ++i) {
+      taken[i] = enc_take_grids(grids[i], rq.attr(i).num_attributes);
+      any = any || taken[i].error != nullptr;
+      for (const synth::Grid &g : taken[i].slot) any = any || g.mode != 0 || g.reserved[0] != 0 || g.reserved[1] != 0;
+    }
+    if (any) {                                               // (else it is the very request of the call without grids)
+      ENC_STAGE(enc_stage_grids(ctx, rq, taken));
+      rq.grids = taken.data();
+    }
+  }
+  return repair ? encode_repair_request(ctx, rq, out) : encode_request(ctx, rq, out);
+}
+static dsa_status encode_edgebreaker(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_seam_repair_options &o,
+                                     dsa_encoded **out, bool drop_generic_outside_1_4 = false) {
+  if (enc_check_options(ctx, o, !ctx || !out || (n && !meshes)) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+  EncRequest rq;
+  rq.n = n; rq.meshes = meshes; rq.drop_generic_outside_1_4 = drop_generic_outside_1_4;
+  rq.level = o.grid.repair.level;
+  rq.weld = o.grid.weld_points == 1; rq.corner_repair = o.corner_repair == 1;
+  return encode_checked(ctx, rq, grids, o.grid.repair.topology == 1, out);
+}
+static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_sequential_options *options, dsa_encoded **out) {
+  EncRequest rq;
+  rq.n = n; rq.meshes = meshes; rq.sequential = true;
+  dsa_encode_sequential_default_options(&rq.seq);
+  if (options) rq.seq = *options;
+  if (enc_check_options(ctx, rq.seq, !ctx || !out || (n && !meshes)) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+  return encode_checked(ctx, rq, grids, false, out);
+}
+// the array of a narrower entry point widened, owned by the call
+template <class Mesh>
+static dsa_status encode_edgebreaker_narrow(dsa_context *ctx, uint32_t n, const Mesh *meshes, const dsa_encode_seam_repair_options &o, dsa_encoded **out, bool drop_generic_outside_1_4 = false) {
+  const std::vector<dsa_mesh_attr_input> wide = enc_widen(meshes, n);
+  return encode_edgebreaker(ctx, n, wide.empty() ? nullptr : wide.data(), nullptr, o, out, drop_generic_outside_1_4);
+}
+static dsa_encode_seam_repair_options enc_default_options() { dsa_encode_seam_repair_options o; dsa_encode_default_seam_repair_options(&o); return o; }
+
 extern "C" {
 
 void dsa_encode_default_options(dsa_encode_options *o) {
@@ -1536,218 +1639,86 @@ void dsa_encode_sequential_default_options(dsa_encode_sequential_options *o) {
   o->geometry = 1;
   o->compress_connectivity = 0;
 }
-
-// Every entry point: a request at the defaults, the caller's meshes and options into it, encode_request.
-static EncRequest enc_request(uint32_t n, bool sequential) {
-  EncRequest rq;
-  rq.n = n; rq.sequential = sequential;
-  dsa_encode_default_level_options(&rq.level);
-  dsa_encode_sequential_default_options(&rq.seq);
-  return rq;
-}
-// batch_n: the size of the batch the request belongs to (what chooses between host and device connectivity); 0: the request's own
-static dsa_status encode_request(dsa_context *ctx, const EncRequest &rq, dsa_encoded **out, uint32_t batch_n = 0) {
-  if (!ctx || !out || (rq.n && !rq.vertex && !rq.corners && !rq.listed)) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "null argument");
-  if (enc_check_request(ctx, rq) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
-  if (batch_n == 0) batch_n = rq.n;
-  DSA_GUARD(ctx, encode_batch_chunks(ctx, rq.n, [&](dsa_context *sink, EncLane &lane, uint32_t base, uint32_t cnt, dsa_encoded **part) {      // host vectors and threads inside: nothing may unwind into the caller
-    if (rq.weld_sink) return weld_chunk(sink, lane, rq, base, cnt, batch_n, part);
-    return rq.sequential ? encode_sequential_chunk(sink, lane, rq, base, cnt, rq.n, part) : encode_chunk(sink, lane, rq, base, cnt, batch_n, part);
-  }, out));
-}
-// dsa_encode_repair_batch, topology = 1: the batch as dsa_encode_level_batch codes it; then the meshes refused for their topology
-// once more as a request of their own, on the repaired corner table (EncRequest::repair), their results into the first's places.
-// Clean meshes take the kernels they always took and nothing else.
-static bool enc_topology_refusal(const std::string &why) {
-  for (uint32_t s : {(uint32_t)dsa::ENC_DEGENERATE, (uint32_t)dsa::ENC_NONMANIFOLD_EDGE, (uint32_t)dsa::ENC_RING, (uint32_t)dsa::ENC_NONMANIFOLD_VERTEX, (uint32_t)dsa::ENC_ISOLATED})
-    if (why == dsa::enc_conn_message(s)) return true;
-  return false;
-}
-static dsa_status encode_repair_request(dsa_context *ctx, const EncRequest &request, dsa_encoded **out) {
-  EncRequest rq = request;
-  rq.repair_scan = true;
-  const dsa_status st = encode_request(ctx, rq, out);
-  if (st != DSA_OK || rq.n == 0) return st;
-  std::unique_ptr<dsa_encoded> E(*out);
-  *out = nullptr;
-  try {
-    std::vector<uint32_t> again;
-    std::vector<dsa_mesh_attr_input> sub;
-    std::vector<EncMeshGrids> sub_grids;
-    for (uint32_t i = 0; i < rq.n; ++i) {
-      if (E->status[i] != DSA_ERR_INVALID_DATA) continue;
-      const dsa_mesh_input &m = rq.mesh(i);
-      if (m.positions && m.num_vertices >= 3 && m.num_faces == 0 && E->messages[i] == "mesh needs positions and faces") { E->messages[i] = "all triangles are degenerate"; continue; }
-      if (enc_topology_refusal(E->messages[i])) { again.push_back(i); sub.push_back(rq.listed[i]); if (rq.grids) sub_grids.push_back(rq.grids[i]); }
-    }
-    if (!again.empty()) {
-      EncRequest r2 = rq;
-      r2.repair_scan = false; r2.repair = true; r2.n = (uint32_t)again.size(); r2.listed = sub.data(); r2.grids = rq.grids ? sub_grids.data() : nullptr;
-      dsa_encoded *second = nullptr;
-      const dsa_status s2 = encode_request(ctx, r2, &second, rq.n);
-      if (s2 != DSA_OK) return s2;
-      std::unique_ptr<dsa_encoded> E2(second);
-      for (uint32_t k = 0; k < r2.n; ++k) { E->streams[again[k]].swap(E2->streams[k]); E->status[again[k]] = E2->status[k]; E->messages[again[k]].swap(E2->messages[k]); }
-    }
-  } catch (const std::bad_alloc &) { return set_err(ctx, DSA_ERR_OUT_OF_MEMORY, "host allocation failed"); }
-  catch (...) { return set_err(ctx, DSA_ERR_DEVICE, "unexpected failure inside the library"); }
-  *out = E.release();
-  return DSA_OK;
-}
-dsa_status dsa_encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_encode_options *options, dsa_encoded **out) {
-  EncRequest rq = enc_request(n, false);
-  rq.vertex = meshes;
-  if (options) rq.level.ex.base = *options;
-  return encode_request(ctx, rq, out);
-}
-dsa_status dsa_encode_batch_corners(dsa_context *ctx, uint32_t n, const dsa_mesh_corner_input *meshes, const dsa_encode_options *options, dsa_encoded **out) {
-  EncRequest rq = enc_request(n, false);
-  rq.corners = meshes;
-  if (options) rq.level.ex.base = *options;
-  return encode_request(ctx, rq, out);
-}
-dsa_status dsa_encode_batch_ex(dsa_context *ctx, uint32_t n, const dsa_mesh_corner_input *meshes, const dsa_encode_options_ex *options, dsa_encoded **out) {
-  EncRequest rq = enc_request(n, false);
-  rq.corners = meshes;
-  if (options) rq.level.ex = *options;
-  return encode_request(ctx, rq, out);
-}
-dsa_status dsa_encode_attributes_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_encode_options_ex *options, dsa_encoded **out) {
-  EncRequest rq = enc_request(n, false);
-  rq.listed = meshes;
-  if (options) rq.level.ex = *options;
-  return encode_request(ctx, rq, out);
-}
-// The levels above the default: MultiParallelogram / ConstrainedMultiParallelogram in place of Parallelogram, prediction-degree
-// attribute order (dsa_encode_multi.h).  With both at 0 this is dsa_encode_attributes_batch.
-dsa_status dsa_encode_level_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_encode_level_options *options, dsa_encoded **out) {
-  EncRequest rq = enc_request(n, false);
-  rq.listed = meshes;
-  if (options) rq.level = *options;
-  return encode_request(ctx, rq, out);
-}
 void dsa_encode_default_repair_options(dsa_encode_repair_options *o) {
   if (!o) return;
   memset(o, 0, sizeof(*o));
   dsa_encode_default_level_options(&o->level);
-}
-// dsa_encode_level_batch that also takes meshes with degenerate faces, non-manifold edges and vertices and isolated vertices
-// (topology = 1: the reference's corner table, dsa_encode_repair.h).  With topology 0 it is dsa_encode_level_batch.
-dsa_status dsa_encode_repair_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_encode_repair_options *options, dsa_encoded **out) {
-  EncRequest rq = enc_request(n, false);
-  rq.listed = meshes;
-  int32_t topology = 0;
-  if (options) {
-    if (options->topology != 0 && options->topology != 1)
-      return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "topology %d: 0 (strict) or 1 (the reference's corner table)", (int)options->topology);
-    for (int k = 0; k < 7; ++k)
-      if (options->reserved[k] != 0) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "dsa_encode_repair_options.reserved[%d] is not zero", k);
-    rq.level = options->level;
-    topology = options->topology;
-  }
-  return topology == 1 ? encode_repair_request(ctx, rq, out) : encode_request(ctx, rq, out);
-}
-static dsa_status enc_repair_options_into(dsa_context *ctx, const dsa_encode_repair_options *options, EncRequest &rq, int32_t &topology) {
-  topology = 0;
-  if (!options) return DSA_OK;
-  if (options->topology != 0 && options->topology != 1)
-    return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "topology %d: 0 (strict) or 1 (the reference's corner table)", (int)options->topology);
-  for (int k = 0; k < 7; ++k)
-    if (options->reserved[k] != 0) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "dsa_encode_repair_options.reserved[%d] is not zero", k);
-  rq.level = options->level;
-  topology = options->topology;
-  return DSA_OK;
-}
-// dsa_encode_repair_batch for meshes given as one row per point: every chunk welds its meshes first (enc_stage_weld), the welded
-// meshes are coded as that call codes them.  With topology = 1 the meshes refused for their topology are welded again in the
-// second pass: they are the few, and the weld is cheap beside keeping every chunk's buffers alive.
-static dsa_status encode_points_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_encode_repair_options *options, dsa_encoded **out) {
-  EncRequest rq = enc_request(n, false);
-  rq.listed = meshes;
-  rq.weld = true;
-  int32_t topology = 0;
-  if (enc_repair_options_into(ctx, options, rq, topology) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
-  return topology == 1 ? encode_repair_request(ctx, rq, out) : encode_request(ctx, rq, out);
-}
-dsa_status dsa_encode_points_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_encode_repair_options *options, dsa_encoded **out) {
-  DSA_GUARD(ctx, encode_points_batch(ctx, n, meshes, options, out));
-}
-
-// ---- quantisation grids given by the caller or shared within a group (dsa_encode_grid.h): the calls above with a grid per float
-// attribute.  The caller's grids are copied, the shared ones resolved once for the whole request (enc_stage_grids), and the
-// request goes the way it always went; without a grid that is not mode 0 it is the very request of the call it stands for.
-static dsa_status encode_grid_request(dsa_context *ctx, EncRequest &rq, const dsa_mesh_grids *grids, int32_t topology, dsa_encoded **out) {
-  if (!ctx || !out || (rq.n && !rq.listed)) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "null argument");
-  std::vector<EncMeshGrids> taken;
-  if (grids && rq.n) {
-    taken.resize(rq.n);
-    bool any = false;
-    for (uint32_t i = 0; i < rq.n; ++i) {
-      taken[i] = enc_take_grids(grids[i], rq.listed[i].num_attributes);
-      any = any || taken[i].error != nullptr;
-      for (const synth::Grid &g : taken[i].slot) any = any || g.mode != 0 || g.reserved[0] != 0 || g.reserved[1] != 0;
-    }
-    if (any) {
-      if (enc_check_request(ctx, rq) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
-      ENC_STAGE(enc_stage_grids(ctx, rq, taken));
-      rq.grids = taken.data();
-    }
-  }
-  return topology == 1 ? encode_repair_request(ctx, rq, out) : encode_request(ctx, rq, out);
 }
 void dsa_encode_default_grid_options(dsa_encode_grid_options *o) {
   if (!o) return;
   memset(o, 0, sizeof(*o));
   dsa_encode_default_repair_options(&o->repair);
 }
-static dsa_status encode_grid_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_grid_options *options, dsa_encoded **out, bool corner_repair = false) {
-  EncRequest rq = enc_request(n, false);
-  rq.listed = meshes;
-  rq.corner_repair = corner_repair;
-  int32_t topology = 0;
-  if (options) {
-    if (options->weld_points != 0 && options->weld_points != 1)
-      return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "weld_points %d: 0 (rows per vertex) or 1 (rows per point)", (int)options->weld_points);
-    for (int k = 0; k < 7; ++k)
-      if (options->reserved[k] != 0) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "dsa_encode_grid_options.reserved[%d] is not zero", k);
-    if (enc_repair_options_into(ctx, &options->repair, rq, topology) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
-    rq.weld = options->weld_points == 1;
-  }
-  return encode_grid_request(ctx, rq, grids, topology, out);
-}
-dsa_status dsa_encode_grid_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_grid_options *options, dsa_encoded **out) {
-  DSA_GUARD(ctx, encode_grid_batch(ctx, n, meshes, grids, options, out));
-}
-// ---- dsa_encode_grid_batch with attributes given per corner coded over a repaired table (EncRequest::corner_repair; the second
-// pass of encode_repair_request, dsa_encode_repair.h: k_enc_repair_face_scan, k_enc_repair_ids).  With corner_repair = 0 it is
-// dsa_encode_grid_batch.
 void dsa_encode_default_seam_repair_options(dsa_encode_seam_repair_options *o) {
   if (!o) return;
   memset(o, 0, sizeof(*o));
   dsa_encode_default_grid_options(&o->grid);
 }
-static dsa_status encode_seam_repair_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_seam_repair_options *options, dsa_encoded **out) {
-  if (!options) return encode_grid_batch(ctx, n, meshes, grids, nullptr, out);
-  if (options->corner_repair != 0 && options->corner_repair != 1)
-    return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "corner_repair %d: 0 (refused as ever) or 1 (coded over the repaired table)", (int)options->corner_repair);
-  for (int k = 0; k < 7; ++k)
-    if (options->reserved[k] != 0) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "dsa_encode_seam_repair_options.reserved[%d] is not zero", k);
-  if (options->corner_repair == 1 && options->grid.repair.topology != 1)
-    return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "corner_repair 1 needs topology 1 (the reference's corner table), topology is %d", (int)options->grid.repair.topology);
-  return encode_grid_batch(ctx, n, meshes, grids, &options->grid, out, options->corner_repair == 1);
+
+dsa_status dsa_encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_encode_options *options, dsa_encoded **out) {
+  dsa_encode_seam_repair_options o = enc_default_options();
+  if (options) o.grid.repair.level.ex.base = *options;
+  DSA_GUARD(ctx, encode_edgebreaker_narrow(ctx, n, meshes, o, out, true));      // (EncRequest::drop_generic_outside_1_4: this entry alone)
 }
+dsa_status dsa_encode_batch_corners(dsa_context *ctx, uint32_t n, const dsa_mesh_corner_input *meshes, const dsa_encode_options *options, dsa_encoded **out) {
+  dsa_encode_seam_repair_options o = enc_default_options();
+  if (options) o.grid.repair.level.ex.base = *options;
+  DSA_GUARD(ctx, encode_edgebreaker_narrow(ctx, n, meshes, o, out));
+}
+dsa_status dsa_encode_batch_ex(dsa_context *ctx, uint32_t n, const dsa_mesh_corner_input *meshes, const dsa_encode_options_ex *options, dsa_encoded **out) {
+  dsa_encode_seam_repair_options o = enc_default_options();
+  if (options) o.grid.repair.level.ex = *options;
+  DSA_GUARD(ctx, encode_edgebreaker_narrow(ctx, n, meshes, o, out));
+}
+dsa_status dsa_encode_attributes_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_encode_options_ex *options, dsa_encoded **out) {
+  dsa_encode_seam_repair_options o = enc_default_options();
+  if (options) o.grid.repair.level.ex = *options;
+  DSA_GUARD(ctx, encode_edgebreaker(ctx, n, meshes, nullptr, o, out));
+}
+// The levels above the default: MultiParallelogram / ConstrainedMultiParallelogram in place of Parallelogram, prediction-degree
+// attribute order (dsa_encode_multi.h).
+dsa_status dsa_encode_level_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_encode_level_options *options, dsa_encoded **out) {
+  dsa_encode_seam_repair_options o = enc_default_options();
+  if (options) o.grid.repair.level = *options;
+  DSA_GUARD(ctx, encode_edgebreaker(ctx, n, meshes, nullptr, o, out));
+}
+// ... that also takes meshes with degenerate faces, non-manifold edges and vertices and isolated vertices (topology = 1: the
+// reference's corner table, dsa_encode_repair.h).
+dsa_status dsa_encode_repair_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_encode_repair_options *options, dsa_encoded **out) {
+  dsa_encode_seam_repair_options o = enc_default_options();
+  if (options) o.grid.repair = *options;
+  DSA_GUARD(ctx, encode_edgebreaker(ctx, n, meshes, nullptr, o, out));
+}
+// dsa_encode_repair_batch for meshes given as one row per point: every chunk welds its meshes first (enc_stage_weld), the welded
+// meshes are coded as that call codes them.  With topology = 1 the meshes refused for their topology are welded again in the
+// second pass: they are the few, and the weld is cheap beside keeping every chunk's buffers alive.
+dsa_status dsa_encode_points_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_encode_repair_options *options, dsa_encoded **out) {
+  dsa_encode_seam_repair_options o = enc_default_options();
+  if (options) o.grid.repair = *options;
+  o.grid.weld_points = 1;
+  DSA_GUARD(ctx, encode_edgebreaker(ctx, n, meshes, nullptr, o, out));
+}
+// ... with a quantisation grid per float attribute, given by the caller or shared within a group (dsa_encode_grid.h).
+dsa_status dsa_encode_grid_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_grid_options *options, dsa_encoded **out) {
+  dsa_encode_seam_repair_options o = enc_default_options();
+  if (options) o.grid = *options;
+  DSA_GUARD(ctx, encode_edgebreaker(ctx, n, meshes, grids, o, out));
+}
+// ... with attributes given per corner coded over a repaired table (EncRequest::corner_repair; the second pass of
+// encode_repair_request, dsa_encode_repair.h: k_enc_repair_face_scan, k_enc_repair_ids).
 dsa_status dsa_encode_seam_repair_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_seam_repair_options *options, dsa_encoded **out) {
-  DSA_GUARD(ctx, encode_seam_repair_batch(ctx, n, meshes, grids, options, out));
+  DSA_GUARD(ctx, encode_edgebreaker(ctx, n, meshes, grids, options ? *options : enc_default_options(), out));
 }
-static dsa_status encode_grid_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_sequential_options *options, dsa_encoded **out) {
-  EncRequest rq = enc_request(n, true);
-  rq.listed = meshes;
-  if (options) rq.seq = *options;
-  return encode_grid_request(ctx, rq, grids, 0, out);
+dsa_status dsa_encode_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_encode_sequential_options *options, dsa_encoded **out) {
+  DSA_GUARD(ctx, [&] { const std::vector<dsa_mesh_attr_input> wide = enc_widen(meshes, n); return encode_sequential(ctx, n, wide.empty() ? nullptr : wide.data(), nullptr, options, out); }());
+}
+dsa_status dsa_encode_attributes_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_encode_sequential_options *options, dsa_encoded **out) {
+  DSA_GUARD(ctx, encode_sequential(ctx, n, meshes, nullptr, options, out));
 }
 dsa_status dsa_encode_grid_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_sequential_options *options, dsa_encoded **out) {
-  DSA_GUARD(ctx, encode_grid_sequential_batch(ctx, n, meshes, grids, options, out));
+  DSA_GUARD(ctx, encode_sequential(ctx, n, meshes, grids, options, out));
 }
+
 struct dsa_welded {
   dsa_context *ctx = nullptr;
   std::vector<synth::Welded> meshes;
@@ -1759,8 +1730,9 @@ static dsa_status weld_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_i
   *out = nullptr;
   std::unique_ptr<dsa_welded> W(new dsa_welded());
   W->meshes.resize(n);
-  EncRequest rq = enc_request(n, false);
-  rq.listed = meshes;
+  EncRequest rq;
+  rq.n = n; rq.meshes = meshes;
+  dsa_encode_default_level_options(&rq.level);
   rq.weld = true;
   rq.weld_sink = &W->meshes;
   dsa_encoded *E = nullptr;
@@ -1791,19 +1763,6 @@ dsa_status dsa_welded_mesh(const dsa_welded *w, uint32_t mesh, dsa_welded_info *
   return DSA_OK;
 }
 void dsa_welded_free(dsa_welded *w) { delete w; }
-
-dsa_status dsa_encode_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_encode_sequential_options *options, dsa_encoded **out) {
-  EncRequest rq = enc_request(n, true);
-  rq.vertex = meshes;
-  if (options) rq.seq = *options;
-  return encode_request(ctx, rq, out);
-}
-dsa_status dsa_encode_attributes_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_encode_sequential_options *options, dsa_encoded **out) {
-  EncRequest rq = enc_request(n, true);
-  rq.listed = meshes;
-  if (options) rq.seq = *options;
-  return encode_request(ctx, rq, out);
-}
 
 
 uint32_t dsa_encoded_size(const dsa_encoded *e) { return e ? (uint32_t)e->streams.size() : 0; }

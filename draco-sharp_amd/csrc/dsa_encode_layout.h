@@ -2,7 +2,7 @@
 //
 // Encode direction, the part of a chunk's host work that needs no device and nothing of HIP (it compiles with plain g++ like
 // dsa_encode_host.h; tests/hostcheck/enclayout_host.cpp runs it under AddressSanitizer):
-//   EncRequest   a call of any encode entry point: the mesh array in the form it arrived, the options in their widest struct
+//   EncRequest   a call of any encode entry point: the mesh array in its widest form (enc_widen), the options in their widest struct
 //   EncChunk     the state of one chunk of a request on its way through the stages of encode_chunk / encode_sequential_chunk
 //   enc_plan_mesh / enc_check_sequential_mesh   the host's checks of a mesh and its plan (what the threads over meshes run)
 //   enc_layout / enc_layout_sequential          the arena: EncStream / EncConn / EncSeam / EncSeqIdx records, upload lists, sizes
@@ -111,8 +111,8 @@ struct dsa_encoded {
   std::vector<std::string> messages;
 };
 
-// A call of an encode entry point.  The meshes in the form they arrived (one of the three pointers is set), the options in the
-// widest struct of their kind: what a narrower entry point does not have stays at its default, which every check passes.
+// A call of an encode entry point.  The meshes in the widest form (a narrower array is widened once, enc_widen), the options in
+// the widest struct of their kind: what a narrower entry point does not have stays empty / at its default, which every check passes.
 // The grids of one mesh as a request carries them (dsa_mesh_grids copied, the attribute list's up to what a stream may hold):
 // slot 0 the positions, 1 the first UV set, 2 + k attribute k of the list.  enc_stage_grids turns mode 2 into mode 1 with the
 // group's grid before any chunk looks.
@@ -134,23 +134,35 @@ static EncMeshGrids enc_take_grids(const dsa_mesh_grids &g, uint32_t num_attribu
 }
 struct EncRequest {
   uint32_t n = 0;
-  const dsa_mesh_input *vertex = nullptr;
-  const dsa_mesh_corner_input *corners = nullptr;
-  const dsa_mesh_attr_input *listed = nullptr;
+  const dsa_mesh_attr_input *meshes = nullptr;
   bool sequential = false;
+  // dsa_encode_batch alone, kept from the time it had a mesh form of its own: a `generic` pointer whose generic_components lies
+  // outside 1 .. 4 is dropped and the mesh coded without the attribute.  Every other Edgebreaker entry refuses such a mesh
+  // ("generic attribute needs 1 - 4 components"), and so does every sequential one, dsa_encode_sequential_batch included.
+  bool drop_generic_outside_1_4 = false;
   bool repair_scan = false;                // dsa_encode_repair_batch, topology = 1, the first pass: two faces turned against each other over the same vertices are refused too
   bool repair = false;                     // dsa_encode_repair_batch, topology = 1, the second pass: the meshes the first pass refused for their topology, on the repaired corner table
   bool corner_repair = false;              // dsa_encode_seam_repair_batch, corner_repair = 1: the second pass codes attributes given per corner over the repaired table (else it refuses them)
-  bool weld = false;                       // dsa_encode_points_batch / dsa_weld_batch: `listed` holds one row per point, every chunk welds its meshes first (enc_stage_weld)
+  bool weld = false;                       // dsa_encode_points_batch / dsa_weld_batch: `meshes` holds one row per point, every chunk welds its meshes first (enc_stage_weld)
   std::vector<synth::Welded> *weld_sink = nullptr;      // dsa_weld_batch: receives the weld of every mesh, nothing is coded
-  const EncMeshGrids *grids = nullptr;     // dsa_encode_grid_batch / _sequential_batch: parallel to `listed` (null: every attribute on its own bounds)
-  dsa_encode_level_options level;          // Edgebreaker streams
-  dsa_encode_sequential_options seq;       // sequential streams
+  const EncMeshGrids *grids = nullptr;     // dsa_encode_grid_batch / _sequential_batch: parallel to `meshes` (null: every attribute on its own bounds)
+  dsa_encode_level_options level{};        // Edgebreaker streams
+  dsa_encode_sequential_options seq{};     // sequential streams
   const dsa_encode_options &base() const { return sequential ? seq.base : level.ex.base; }
-  const dsa_mesh_corner_input *corner(size_t i) const { return listed ? &listed[i].mesh : (corners ? &corners[i] : nullptr); }      // null for the per-vertex form
-  const dsa_mesh_input &mesh(size_t i) const { const dsa_mesh_corner_input *c = corner(i); return c ? c->mesh : vertex[i]; }
-  const dsa_mesh_attr_input *attr(size_t i) const { return listed ? &listed[i] : nullptr; }                                         // null unless listed
+  const dsa_mesh_attr_input &attr(size_t i) const { return meshes[i]; }
+  const dsa_mesh_corner_input &corner(size_t i) const { return meshes[i].mesh; }
+  const dsa_mesh_input &mesh(size_t i) const { return meshes[i].mesh.mesh; }
 };
+// The array of an entry point that takes dsa_mesh_input or dsa_mesh_corner_input in the request's form: no ids, no list (null: empty).
+static inline void enc_wide(dsa_mesh_attr_input &w, const dsa_mesh_corner_input &m) { w.mesh = m; }
+static inline void enc_wide(dsa_mesh_attr_input &w, const dsa_mesh_input &m) { w.mesh.mesh = m; }
+template <class Mesh>
+static std::vector<dsa_mesh_attr_input> enc_widen(const Mesh *meshes, uint32_t n) {
+  std::vector<dsa_mesh_attr_input> wide(meshes ? n : 0);
+  if (!wide.empty()) memset(wide.data(), 0, sizeof(dsa_mesh_attr_input) * wide.size());
+  for (uint32_t i = 0; i < wide.size(); ++i) enc_wide(wide[i], meshes[i]);
+  return wide;
+}
 // the options as the host coder takes them (a sequential stream has no connectivity, prediction or traversal options)
 static synth::Options enc_synth_options(const EncRequest &rq) {
   const dsa_encode_options &od = rq.base();
@@ -200,7 +212,7 @@ struct EncChunk {
   std::vector<synth::MeshIn> ins;
   std::vector<synth::MeshPlan> plans;       // (a sequential stream's: the attributes alone)
   std::vector<std::vector<synth::ExtraAttr>> extras;
-  std::vector<std::vector<uint32_t>> extra_cap;                   // meshes with an attribute list, per attribute of the plan: hist_cap of an integer extra, else 0
+  std::vector<std::vector<uint32_t>> extra_cap;                   // per mesh and attribute of the plan: hist_cap of an integer extra, else 0
   // host connectivity: entry -> vertex and operand entries in depth-first and in prediction-degree order; per attribute given per
   // corner its own entry -> value row, when it is seamed its own operands, with prediction 5 / 6 its table's opposites
   std::vector<std::vector<uint32_t>> e2v, e2v_pd;
@@ -233,17 +245,16 @@ struct EncChunk {
   std::vector<synth::SymbolPlan> splans;
   std::vector<std::vector<uint8_t>> rans, bits, flag_bits, crease;      // per stream; crease[4 s + j]: list j of stream s
 
-  EncChunk(const EncRequest &r, uint32_t b, uint32_t cnt, uint32_t bn) : rq(r), base(b), n(cnt), batch_n(bn), opt(enc_synth_options(r)), E(new (std::nothrow) dsa_encoded()), ins(cnt), plans(cnt) {
+  EncChunk(const EncRequest &r, uint32_t b, uint32_t cnt, uint32_t bn) : rq(r), base(b), n(cnt), batch_n(bn), opt(enc_synth_options(r)), E(new (std::nothrow) dsa_encoded()), ins(cnt), plans(cnt), extras(cnt), extra_cap(cnt) {
     if (!E) return;                        // (the chunk function answers)
     E->streams.resize(n); E->status.assign(n, DSA_OK); E->messages.resize(n);
-    if (rq.listed) { extras.resize(n); extra_cap.resize(n); }
   }
-  const dsa_mesh_input &mesh(uint32_t i) const { return welded.empty() ? rq.mesh(base + i) : welded[i].mesh.mesh; }
+  const dsa_mesh_attr_input &attr(uint32_t i) const { return welded.empty() ? rq.attr(base + i) : welded[i]; }
+  const dsa_mesh_corner_input &corner(uint32_t i) const { return attr(i).mesh; }
+  const dsa_mesh_input &mesh(uint32_t i) const { return attr(i).mesh.mesh; }
   // vertices and faces of mesh i as the connectivity kernels and the streams see them
   uint32_t coded_vertices(uint32_t i) const { return !rep.empty() ? rep[i].nv() : (plans[i].coded_vertices >= 0 ? (uint32_t)plans[i].coded_vertices : mesh(i).num_vertices); }
   uint32_t coded_faces(uint32_t i) const { return !rep.empty() ? rep[i].nf() : (plans[i].coded_faces >= 0 ? (uint32_t)plans[i].coded_faces : mesh(i).num_faces); }
-  const dsa_mesh_corner_input *corner(uint32_t i) const { return welded.empty() ? rq.corner(base + i) : &welded[i].mesh; }
-  const dsa_mesh_attr_input *attr(uint32_t i) const { return welded.empty() ? rq.attr(base + i) : &welded[i]; }
   bool good(uint32_t i) const { return E->status[i] == DSA_OK; }
   void refuse(uint32_t i, dsa_status st, const std::string &why) { E->status[i] = st; E->messages[i] = why; }
   // valence symbols per mesh: asked for, or by the reference's rule (speed < 5 and not a tiny mesh)
@@ -251,15 +262,15 @@ struct EncChunk {
   // MultiParallelogram per mesh: the method asked for, or by the reference's rule (speed < 2 and at least 40 points)
   int32_t multi_of(uint32_t i) const { const int32_t m = rq.level.multi_parallelogram; return m == -1 ? ((opt.compression_level >= 9 && mesh(i).num_vertices >= 40) ? 4 : 0) : m; }
   // value rows of an attribute of mesh i: its ids' row count when it is given per corner
-  uint32_t rows_of(uint32_t i, const synth::PortableAttr &a) const { return !a.corner_value ? mesh(i).num_vertices : (a.att_type == 1 ? corner(i)->num_normals : corner(i)->num_texcoords); }
+  uint32_t rows_of(uint32_t i, const synth::PortableAttr &a) const { return !a.corner_value ? mesh(i).num_vertices : (a.att_type == 1 ? corner(i).num_normals : corner(i).num_texcoords); }
   bool ids_narrow(uint32_t i, const synth::PortableAttr &a) const { return rows_of(i, a) <= 65536; }
   // the decoder of attribute k takes the prediction-degree order (MeshPlan::uses_pd; for an attribute given per corner on the
   // device path: unless it turns out seamed -- k_enc_pd_corner_streams, k_enc_seam_topo)
   bool uses_pd(uint32_t i, size_t k) const { return want_pd && (host_conn ? plans[i].uses_pd(k) : (opt.traversal_method == 2 || opt.single_connectivity != 0 || k == 0)); }
-  uint32_t hist_cap_of(uint32_t i, size_t k) const { return extra_cap.empty() ? 0u : extra_cap[i][k]; }
+  uint32_t hist_cap_of(uint32_t i, size_t k) const { return extra_cap[i][k]; }      // (0: by the attribute's bits)
 };
 
-// The extras of a mesh with an attribute list as the host coder takes them (`ex` keeps them alive beside `in`); what the C structs
+// The attribute list of a mesh as the host coder takes it (`ex` keeps them alive beside `in`); what the C structs
 // alone can say against them -- a reserved word -- is answered here, the rest by synth::extras_error.  "" when they can be written.
 static std::string enc_take_extras(const dsa_mesh_attr_input &am, std::vector<synth::ExtraAttr> &ex, synth::MeshIn &in) {
   char buf[96];
@@ -304,7 +315,6 @@ static uint32_t enc_extra_hist_cap(const synth::PortableAttr &a, uint32_t rows) 
 }
 // the bounds of the integer extras' values of mesh i, once its plan has said which attributes there are
 static void enc_extra_caps(EncChunk &ck, uint32_t i) {
-  if (!ck.rq.listed) return;
   const std::vector<synth::PortableAttr> &atts = ck.plans[i].atts;
   ck.extra_cap[i].assign(atts.size(), 0);
   for (size_t k = 0; k < atts.size(); ++k)
@@ -314,7 +324,7 @@ static void enc_extra_caps(EncChunk &ck, uint32_t i) {
 // ---- a weld request, mesh i: what the weld itself indexes by is checked here, before anything reads through the faces (the
 // rest of the mesh is the coder's to judge, on the welded form).  The segments of the vertex key into `key`; false: refused.
 static bool enc_weld_check(EncChunk &ck, uint32_t i, std::vector<synth::WeldSeg> &key) {
-  const dsa_mesh_attr_input &am = ck.rq.listed[ck.base + i];
+  const dsa_mesh_attr_input &am = ck.rq.attr(ck.base + i);
   const dsa_mesh_input &m = am.mesh.mesh;
   if (am.mesh.normal_corners || am.mesh.texcoord_corners) { ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, "per-point input takes no corner ids (normal_corners / texcoord_corners must be NULL)"); return false; }
   if (m.generic && (m.generic_components < 1 || m.generic_components > 4)) { ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, "generic attribute needs 1 - 4 components"); return false; }
@@ -333,7 +343,7 @@ static void enc_weld_view(EncChunk &ck, uint32_t i) {
   dsa_mesh_attr_input &out = ck.welded[i];
   memset(&out, 0, sizeof(out));
   if (!ck.good(i)) return;
-  const dsa_mesh_attr_input &am = ck.rq.listed[ck.base + i];
+  const dsa_mesh_attr_input &am = ck.rq.attr(ck.base + i);
   const synth::Welded &w = ck.weld[i];
   dsa_mesh_input &m = out.mesh.mesh;
   size_t g = 0;
@@ -361,18 +371,18 @@ static void enc_plan_mesh(EncChunk &ck, uint32_t i) {
   const synth::Options &opt = ck.opt;
   synth::MeshIn &in = ck.ins[i];
   in.pos = m.positions; in.nv = m.num_vertices; in.faces = m.faces; in.nf = m.num_faces; in.normals = m.normals; in.uvs = m.texcoords;
-  in.generic = (m.generic && m.generic_components >= 1 && m.generic_components <= 4) ? m.generic : nullptr;
-  if (const dsa_mesh_corner_input *cm = ck.corner(i)) {
-    if (m.generic && (m.generic_components < 1 || m.generic_components > 4)) return ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, "generic attribute needs 1 - 4 components");
-    if ((cm->normal_corners && !m.normals) || (cm->texcoord_corners && !m.texcoords)) return ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, "corner ids without their values");
-    in.normal_corners = cm->normal_corners; in.nn = cm->num_normals;
-    in.uv_corners = cm->texcoord_corners; in.nu = cm->num_texcoords;
+  in.generic = m.generic;
+  if (m.generic && (m.generic_components < 1 || m.generic_components > 4)) {
+    if (!ck.rq.drop_generic_outside_1_4) return ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, "generic attribute needs 1 - 4 components");
+    in.generic = nullptr;
   }
-  if (ck.rq.listed) {
-    std::string why = enc_take_extras(*ck.attr(i), ck.extras[i], in);
-    if (why.empty()) why = enc_take_mesh_grids(ck.rq.grids ? &ck.rq.grids[ck.base + i] : nullptr, ck.extras[i], in);
-    if (!why.empty()) return ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, why);
-  }
+  const dsa_mesh_corner_input &cm = ck.corner(i);
+  if ((cm.normal_corners && !m.normals) || (cm.texcoord_corners && !m.texcoords)) return ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, "corner ids without their values");
+  in.normal_corners = cm.normal_corners; in.nn = cm.num_normals;
+  in.uv_corners = cm.texcoord_corners; in.nu = cm.num_texcoords;
+  std::string why = enc_take_extras(ck.attr(i), ck.extras[i], in);
+  if (why.empty()) why = enc_take_mesh_grids(ck.rq.grids ? &ck.rq.grids[ck.base + i] : nullptr, ck.extras[i], in);
+  if (!why.empty()) return ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, why);
   // (every mesh of a repair request is one whose topology the first pass refused)
   if (ck.rq.repair && !ck.rq.corner_repair && (in.normal_corners || in.uv_corners))
     return ck.refuse(i, DSA_ERR_NOT_IMPLEMENTED, "attributes given per corner (normal_corners / texcoord_corners) over a mesh whose topology needs repair are not implemented");
@@ -439,7 +449,7 @@ static void enc_check_sequential_mesh(EncChunk &ck, uint32_t i) {
   if (!is_mesh && m.num_faces != 0) return ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, "a point cloud has no faces (geometry = 0, num_faces != 0)");
   if (is_mesh && (m.num_faces == 0 || !m.faces)) return ck.refuse(i, DSA_ERR_INVALID_DATA, "a mesh needs faces");
   if (m.generic && (m.generic_components < 1 || m.generic_components > 4)) return ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, "generic attribute needs 1 - 4 components");
-  if (ck.rq.listed && (ck.corner(i)->normal_corners || ck.corner(i)->texcoord_corners))
+  if (ck.corner(i).normal_corners || ck.corner(i).texcoord_corners)
     return ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, "corner ids with a sequential stream: it has one value per point (normal_corners / texcoord_corners must be NULL)");
   // (what the 32-bit sizes of a stream's regions hold: 4 bytes per component and symbol, and a margin)
   if (m.num_vertices > (1u << 28) || (compressed && m.num_faces > (1u << 28))) return ck.refuse(i, DSA_ERR_INVALID_DATA, "mesh too large for the device coder");
@@ -453,11 +463,9 @@ static void enc_check_sequential_mesh(EncChunk &ck, uint32_t i) {
   in.normals = m.normals; in.uvs = m.texcoords; in.generic = m.generic;
   synth::Options mo = ck.opt;
   mo.generic_components = m.generic ? (int32_t)m.generic_components : 1;
-  if (ck.rq.listed) {
-    std::string why = enc_take_extras(*ck.rq.attr(ck.base + i), ck.extras[i], in);
-    if (why.empty()) why = enc_take_mesh_grids(ck.rq.grids ? &ck.rq.grids[ck.base + i] : nullptr, ck.extras[i], in);
-    if (!why.empty()) return ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, why);
-  }
+  std::string why = enc_take_extras(ck.attr(i), ck.extras[i], in);
+  if (why.empty()) why = enc_take_mesh_grids(ck.rq.grids ? &ck.rq.grids[ck.base + i] : nullptr, ck.extras[i], in);
+  if (!why.empty()) return ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, why);
   synth::plan_sequential_attributes(in, mo, ck.plans[i].atts);
   enc_extra_caps(ck, i);
 }

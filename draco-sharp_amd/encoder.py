@@ -273,6 +273,42 @@ def _fill_grids(dst, m, keep):
         dst.attributes = arr
 
 
+def _native_meshes(meshes, form=None):
+    """The native arrays of a list of MeshData / PointCloudData: (array of `form`, dsa_mesh_grids array or None, keep).  `form`
+    is native.MeshAttrInput -- what every call of this module passes: corner ids and the attribute list where a mesh has them --
+    or, for a caller of the narrower entry points, native.MeshCornerInput / native.MeshInput, which leave out what they cannot
+    say.  The grids are there when some mesh sets one.  `keep` holds the ctypes arrays alive; the numpy arrays are the meshes'."""
+    form = form or native.MeshAttrInput
+    n = len(meshes)
+    arr = (form * max(1, n))()
+    keep = []
+    for i, m in enumerate(meshes):
+        ci = arr[i].mesh if form is native.MeshAttrInput else arr[i]
+        mi = arr[i] if form is native.MeshInput else ci.mesh
+        mi.num_vertices, mi.num_faces = len(m.positions), len(m.faces)
+        mi.positions = m.positions.ctypes.data
+        mi.faces = m.faces.ctypes.data if len(m.faces) else None
+        mi.normals = m.normals.ctypes.data if m.normals is not None else None
+        mi.texcoords = m.texcoords.ctypes.data if m.texcoords is not None else None
+        g = getattr(m, "generic", None)
+        mi.generic = g.ctypes.data if g is not None else None
+        mi.generic_components = g.shape[1] if g is not None else 0
+        if form is not native.MeshInput:
+            nci, uci = getattr(m, "normal_corners", None), getattr(m, "texcoord_corners", None)
+            ci.normal_corners = nci.ctypes.data if nci is not None else None
+            ci.texcoord_corners = uci.ctypes.data if uci is not None else None
+            ci.num_normals = len(m.normals) if m.normals is not None else 0
+            ci.num_texcoords = len(m.texcoords) if m.texcoords is not None else 0
+        if form is native.MeshAttrInput:
+            _fill_attr_input(arr[i], m, keep)
+    grids = None
+    if any(_has_grid(m) for m in meshes):
+        grids = (native.MeshGrids * max(1, n))()
+        for i, m in enumerate(meshes):
+            _fill_grids(grids[i], m, keep)
+    return arr, grids, keep
+
+
 class MeshData:
     """Triangle mesh with per-vertex attributes: positions (V,3) f32, faces (F,3) u32, optional normals (V,3), uvs (V,2) and one
     generic uint8 attribute of 1 - 4 components (V,) or (V,C): vertex colours, ids (ABI 4).  attributes: a list of Attribute
@@ -431,7 +467,8 @@ class DracoEncoder:
 
     def EncodeBatch(self, meshes, config=None, handle=False):
         """meshes: list of MeshData (or of PointCloudData) -> sequence of bytes (.drc streams, EncodedStreams).  A sequential
-        config (Config.sequential) and point clouds go through dsa_encode_sequential_batch.  A mesh that cannot be encoded raises
+        config (Config.sequential) and point clouds go through dsa_encode_grid_sequential_batch, every other batch through
+        dsa_encode_seam_repair_batch.  A mesh that cannot be encoded raises
         (TryEncodeBatch: the batch with its failures, mesh by mesh)."""
         n = len(meshes)
         config = config or Config()
@@ -453,62 +490,17 @@ class DracoEncoder:
         L = native.lib()
         if clouds or config.sequential:
             return self._encode_sequential(ctx, meshes, config, 0 if clouds else 1, handle=handle)
-        ex = config.extended
-        # the attribute-list entry point only when some mesh has a list; the corner entry point only when some mesh carries ids (or
-        # an option needs dsa_encode_batch_ex, which takes the corner form); otherwise exactly the per-vertex call
-        repair = getattr(config, "repair_topology", False)      # dsa_encode_repair_batch: the level call's input and options, and the topology switch
-        repair = repair or weld               # dsa_encode_points_batch takes that call's input and options
-        gridded = any(_has_grid(m) for m in meshes)      # dsa_encode_grid_batch: only when some grid is set; it takes the repair call's input
-        repair = repair or gridded
-        level = config.leveled or repair      # dsa_encode_level_batch takes the widest input: always dsa_mesh_attr_input, an empty list is legal
-        listed = level or any(getattr(m, "attributes", None) for m in meshes)
-        corners = listed or ex or any(getattr(m, "per_corner", False) for m in meshes)
-        arr = ((native.MeshAttrInput if listed else (native.MeshCornerInput if corners else native.MeshInput)) * max(1, n))()
-        keep = []
-        for i, m in enumerate(meshes):
-            if listed:
-                _fill_attr_input(arr[i], m, keep)
-            ci = arr[i].mesh if listed else arr[i]
-            mi = ci.mesh if corners else arr[i]
-            mi.num_vertices, mi.num_faces = len(m.positions), len(m.faces)
-            mi.positions, mi.faces = m.positions.ctypes.data, m.faces.ctypes.data
-            mi.normals = m.normals.ctypes.data if m.normals is not None else None
-            mi.texcoords = m.texcoords.ctypes.data if m.texcoords is not None else None
-            g = getattr(m, "generic", None)
-            mi.generic = g.ctypes.data if g is not None else None
-            mi.generic_components = g.shape[1] if g is not None else 0
-            if corners:
-                nci, uci = getattr(m, "normal_corners", None), getattr(m, "texcoord_corners", None)
-                ci.normal_corners = nci.ctypes.data if nci is not None else None
-                ci.texcoord_corners = uci.ctypes.data if uci is not None else None
-                ci.num_normals = len(m.normals) if m.normals is not None else 0
-                ci.num_texcoords = len(m.texcoords) if m.texcoords is not None else 0
-        grids = None
-        seams = getattr(config, "repair_seams", False)      # dsa_encode_seam_repair_batch: the grid call's input and options (grids or none), and the corner switch
-        if gridded:
-            grids = (native.MeshGrids * max(1, n))()
-            for i, m in enumerate(meshes):
-                _fill_grids(grids[i], m, keep)
-        if gridded or seams:
-            gopt = native.EncodeGridOptions()
-            L.dsa_encode_default_grid_options(C.byref(gopt))
-            gopt.repair = config._native_repair()
-            gopt.weld_points = 1 if weld else 0
-        if seams:
-            sopt = native.EncodeSeamRepairOptions()
-            L.dsa_encode_default_seam_repair_options(C.byref(sopt))
-            sopt.grid = gopt
-            sopt.corner_repair = 1
-            h = C.c_void_p()
-            st = L.dsa_encode_seam_repair_batch(ctx._h, n, arr, grids, C.byref(sopt), C.byref(h))
-            if st != 0:
-                _raise(st, ctx.error())
-            return (ctx, h, n) if handle else EncodedStreams(ctx, h, n)
-        opt = gopt if gridded else config._native_repair() if repair else config._native_level() if level else (config._native_ex() if (ex or listed) else config._native())
+        # every Edgebreaker batch through the widest entry point: with the fields a Config leaves alone at their defaults, empty
+        # attribute lists and no grids it is the very request of the narrower calls (include/draco_mi355x.h)
+        arr, grids, keep = _native_meshes(meshes)
+        opt = native.EncodeSeamRepairOptions()
+        L.dsa_encode_default_seam_repair_options(C.byref(opt))
+        opt.grid.repair = config._native_repair()
+        opt.grid.weld_points = 1 if weld else 0
+        opt.corner_repair = 1 if getattr(config, "repair_seams", False) else 0
         h = C.c_void_p()
         t0 = time.perf_counter()
-        entry = L.dsa_encode_points_batch if weld else L.dsa_encode_repair_batch if repair else L.dsa_encode_level_batch if level else L.dsa_encode_attributes_batch if listed else (L.dsa_encode_batch_ex if ex else (L.dsa_encode_batch_corners if corners else L.dsa_encode_batch))
-        st = L.dsa_encode_grid_batch(ctx._h, n, arr, grids, C.byref(opt), C.byref(h)) if gridded else entry(ctx._h, n, arr, C.byref(opt), C.byref(h))
+        st = L.dsa_encode_seam_repair_batch(ctx._h, n, arr, grids, C.byref(opt), C.byref(h))
         t1 = time.perf_counter()
         if st != 0:
             _raise(st, ctx.error())
@@ -520,34 +512,11 @@ class DracoEncoder:
         return r
 
     def _encode_sequential(self, ctx, meshes, config, geometry, handle=False):
-        L = native.lib()
         n = len(meshes)
-        gridded = any(_has_grid(m) for m in meshes)      # dsa_encode_grid_sequential_batch: only when some grid is set; it takes the attribute-list input
-        listed = gridded or any(getattr(m, "attributes", None) for m in meshes)
-        arr = ((native.MeshAttrInput if listed else native.MeshInput) * max(1, n))()
-        keep = []
-        for i, m in enumerate(meshes):
-            if listed:
-                _fill_attr_input(arr[i], m, keep)
-            mi = arr[i].mesh.mesh if listed else arr[i]
-            mi.num_vertices, mi.num_faces = len(m.positions), len(m.faces)
-            mi.positions = m.positions.ctypes.data
-            mi.faces = m.faces.ctypes.data if len(m.faces) else None
-            mi.normals = m.normals.ctypes.data if m.normals is not None else None
-            mi.texcoords = m.texcoords.ctypes.data if m.texcoords is not None else None
-            g = getattr(m, "generic", None)
-            mi.generic = g.ctypes.data if g is not None else None
-            mi.generic_components = g.shape[1] if g is not None else 0
+        arr, grids, keep = _native_meshes(meshes)
         opt = config._native_sequential(geometry)
         h = C.c_void_p()
-        entry = L.dsa_encode_attributes_sequential_batch if listed else L.dsa_encode_sequential_batch
-        if gridded:
-            grids = (native.MeshGrids * max(1, n))()
-            for i, m in enumerate(meshes):
-                _fill_grids(grids[i], m, keep)
-            st = L.dsa_encode_grid_sequential_batch(ctx._h, n, arr, grids, C.byref(opt), C.byref(h))
-        else:
-            st = entry(ctx._h, n, arr, C.byref(opt), C.byref(h))
+        st = native.lib().dsa_encode_grid_sequential_batch(ctx._h, n, arr, grids, C.byref(opt), C.byref(h))
         if st != 0:
             _raise(st, ctx.error())
         return (ctx, h, n) if handle else EncodedStreams(ctx, h, n)
@@ -585,18 +554,7 @@ class DracoEncoder:
         ctx = self._ctx or default_context()
         L = native.lib()
         n = len(meshes)
-        arr = (native.MeshAttrInput * max(1, n))()
-        keep = []
-        for i, m in enumerate(meshes):
-            _fill_attr_input(arr[i], m, keep)
-            mi = arr[i].mesh.mesh
-            mi.num_vertices, mi.num_faces = len(m.positions), len(m.faces)
-            mi.positions, mi.faces = m.positions.ctypes.data, m.faces.ctypes.data
-            mi.normals = m.normals.ctypes.data if m.normals is not None else None
-            mi.texcoords = m.texcoords.ctypes.data if m.texcoords is not None else None
-            g = getattr(m, "generic", None)
-            mi.generic = g.ctypes.data if g is not None else None
-            mi.generic_components = g.shape[1] if g is not None else 0
+        arr, _, keep = _native_meshes(meshes)
         h = C.c_void_p()
         st = L.dsa_weld_batch(ctx._h, n, arr, C.byref(h))
         if st != 0:

@@ -11,6 +11,8 @@
 //   - every offset in an EncStream / EncConn / EncSeam / EncSeqIdx record is 0 or a region handed out, and the regions whose
 //     sizes the record states (src, hist_raw, out_rans, out_bits, the tables) have them;
 //   - a mesh that fails its checks has no streams and no arrays, and the others are laid out around it.
+// Outside the counted chunks: the per-vertex and the corner form, widened by the library (enc_widen), lay a batch without ids out
+// exactly like the widest form without its attribute list; and what each form answers to a generic attribute of 5 components.
 // Nothing here is linked into the product.
 //
 //   enclayout_host <meshes.bin>   file: u32 count, then per mesh u32 nv, u32 nf, u32 faces[3 nf], u32 mask (bit 0 normal ids,
@@ -188,7 +190,7 @@ int main(int argc, char **argv) {
     batch.push_back(meshes[i]);
   }
   std::vector<dsa_mesh_attr_input> listed(n);
-  std::vector<dsa_mesh_corner_input> corners(n);
+  std::vector<dsa_mesh_corner_input> corners(n);            // forms 1 and 0, which the library widens (enc_widen): no attribute list
   std::vector<dsa_mesh_input> vertex(n);
   std::vector<std::vector<float>> pos(n), nrm(n), uv(n), weights(n);
   std::vector<std::vector<uint8_t>> generic(n);
@@ -228,7 +230,8 @@ int main(int argc, char **argv) {
             EncRequest rq;
             default_options(rq);
             rq.n = n;
-            if (form == 0) rq.vertex = vertex.data(); else if (form == 1) rq.corners = corners.data(); else rq.listed = listed.data();
+            const std::vector<dsa_mesh_attr_input> wide = form == 0 ? enc_widen(vertex.data(), n) : (form == 1 ? enc_widen(corners.data(), n) : listed);
+            rq.meshes = wide.data();
             rq.level.multi_parallelogram = (scheme & 1) ? 4 : 0;
             if (scheme & 2) { rq.level.ex.base.texcoord_prediction = 5; rq.level.ex.normal_prediction = 6; }
             rq.level.ex.edgebreaker_method = valence ? 2 : 0;
@@ -269,7 +272,8 @@ int main(int argc, char **argv) {
         lst[i].mesh.mesh.normals = vtx[i].normals = nrm[i].data(); lst[i].mesh.mesh.texcoords = vtx[i].texcoords = uv[i].data();
         if (mode == 2) lst[i].mesh.mesh.num_faces = vtx[i].num_faces = 0;
       }
-      if (form == 0) rq.vertex = vtx.data(); else rq.listed = lst.data();
+      const std::vector<dsa_mesh_attr_input> wide = form == 0 ? enc_widen(vtx.data(), n) : lst;
+      rq.meshes = wide.data();
       char name[160];
       snprintf(name, sizeof(name), "sequential form %d mode %d", form, mode);
       g_case = name;
@@ -282,6 +286,73 @@ int main(int argc, char **argv) {
       if (ck.L.idx.size() != (mode == 1 ? n - 1 : 0)) { fprintf(stderr, "%s: %zu index records\n", name, ck.L.idx.size()); return 1; }
       ++chunks; regions += (uint32_t)log.size();
     }
+  // ---- widening changes nothing in the layout: without ids, forms 0 and 1 against form 2 without its extras, region for region
+  // and record for record (Edgebreaker on both connectivity paths and sequential; a chunk that starts inside the request)
+  if (!any_ids) {
+    std::vector<dsa_mesh_attr_input> bare = listed;
+    for (dsa_mesh_attr_input &am : bare) { am.attributes = nullptr; am.num_attributes = 0; }
+    for (int path = 0; path < 3; ++path) {                     // 0 / 1: Edgebreaker, device / host connectivity; 2: sequential
+      Log want_log;
+      std::vector<dsa::EncStream> want;
+      for (int form = 2; form >= 0; --form) {
+        char name[96];
+        snprintf(name, sizeof(name), "widened form %d against form 2, path %d", form, path);
+        g_case = name;
+        EncRequest rq;
+        default_options(rq);
+        rq.n = n; rq.sequential = path == 2;
+        const std::vector<dsa_mesh_attr_input> wide = form == 0 ? enc_widen(vertex.data(), n) : (form == 1 ? enc_widen(corners.data(), n) : bare);
+        rq.meshes = wide.data();
+        EncChunk ck(rq, 1, n - 1, n);
+        Log log;
+        ck.region_log = &log;
+        if (path == 2) { for (uint32_t i = 0; i < n - 1; ++i) enc_check_sequential_mesh(ck, i); enc_layout_sequential(ck); }
+        else { enc_begin_plans(ck, path == 1, true); for (uint32_t i = 0; i < n - 1; ++i) enc_plan_mesh(ck, i); enc_layout(ck); }
+        if (form == 2) { want_log = log; want = ck.L.streams; continue; }
+        if (log != want_log) { fprintf(stderr, "%s: the regions differ\n", name); return 1; }
+        if (ck.L.streams.size() != want.size() || (!want.empty() && memcmp(ck.L.streams.data(), want.data(), sizeof(dsa::EncStream) * want.size()) != 0)) { fprintf(stderr, "%s: the stream records differ\n", name); return 1; }
+      }
+    }
+  }
+  // ---- a generic attribute of 5 components, on one mesh: dsa_encode_batch's request (EncRequest::drop_generic_outside_1_4) plans
+  // the mesh as if `generic` were NULL, every other Edgebreaker request and every sequential one refuses it
+  {
+    const char *refusal = "generic attribute needs 1 - 4 components";
+    dsa_mesh_input with5 = vertex[0], without = vertex[0];
+    with5.generic = generic[0].data(); with5.generic_components = 5;
+    without.generic = nullptr; without.generic_components = 0;
+    dsa_mesh_corner_input with5c = corners[0];
+    with5c.mesh = with5;
+    dsa_mesh_attr_input with5l = listed[0];
+    with5l.mesh.mesh = with5;
+    size_t atts_without = 0;
+    for (int c = 0; c < 5; ++c) {                              // 0: without the attribute; 1: dsa_encode_batch's request; 2 - 4: forms 0 - 2 of every other entry
+      char name[96];
+      snprintf(name, sizeof(name), "generic_components 5, case %d", c);
+      g_case = name;
+      for (int path = 0; path < 3; ++path) {                   // as above
+        EncRequest rq;
+        default_options(rq);
+        rq.n = 1; rq.sequential = path == 2;
+        rq.drop_generic_outside_1_4 = c == 1;
+        const std::vector<dsa_mesh_attr_input> wide = c == 0 ? enc_widen(&without, 1) : (c <= 2 ? enc_widen(&with5, 1) : (c == 3 ? enc_widen(&with5c, 1) : std::vector<dsa_mesh_attr_input>(1, with5l)));
+        rq.meshes = wide.data();
+        EncChunk ck(rq, 0, 1, 1);
+        Log log;
+        ck.region_log = &log;
+        if (path == 2) { enc_check_sequential_mesh(ck, 0); enc_layout_sequential(ck); }
+        else { enc_begin_plans(ck, path == 1, true); enc_plan_mesh(ck, 0); enc_layout(ck); }
+        if (c == 0 || (c == 1 && path != 2)) {
+          if (!check_layout(ck, log, -1)) return 1;
+          if (c == 0 && path == 0) atts_without = ck.plans[0].atts.size();
+          if (path != 2 && ck.plans[0].atts.size() != atts_without) { fprintf(stderr, "%s: %zu attributes, %zu without the generic one\n", name, ck.plans[0].atts.size(), atts_without); return 1; }
+        } else if (ck.good(0) || ck.E->status[0] != DSA_ERR_INVALID_ARGUMENT || ck.E->messages[0] != refusal) {
+          fprintf(stderr, "%s path %d: status %d '%s'\n", name, path, (int)ck.E->status[0], ck.E->messages[0].c_str());
+          return 1;
+        }
+      }
+    }
+  }
   printf("enclayout: %u meshes, %u chunks laid out, %u regions checked\n", n, chunks, regions);
   return 0;
 }

@@ -153,33 +153,44 @@ def _mesh(corners=False):
 
 
 def test_encode_batch_takes_the_new_entry_point_only_when_asked(recorder):
+    """EncodeBatch reaches every Edgebreaker batch through dsa_encode_seam_repair_batch: what is asked for is what the options
+    say, and nothing that is not asked for is switched on."""
     r, ctx = recorder
     enc = dsa.DracoEncoder(ctx)
-    want = {(False, False): "dsa_encode_repair_batch", (True, False): "dsa_encode_points_batch"}
+
+    def the_call():
+        assert [c[0] for c in r.calls] == ["dsa_encode_seam_repair_batch"]
+        _, n, _, grids, opt, _ = r.calls[0][1]
+        o = opt._obj
+        assert n == 1 and list(o.reserved) == [0] * 7 and list(o.grid.reserved) == [0] * 7 and list(o.grid.repair.reserved) == [0] * 7
+        return grids, o
     for weld in (False, True):
         for corners in ((False, True) if not weld else (False,)):
-            # today's routing, untouched
+            # without the switch: the request of dsa_encode_repair_batch / dsa_encode_points_batch
             del r.calls[:]
             enc.EncodeBatch([_mesh(corners)], dsa.Config(repair_topology=True, weld_points=weld), handle=True)
-            assert [c[0] for c in r.calls] == [want[(weld, False)]]
+            grids, o = the_call()
+            assert grids is None and o.corner_repair == 0 and o.grid.repair.topology == 1 and o.grid.weld_points == (1 if weld else 0)
             # the new switch
             del r.calls[:]
             enc.EncodeBatch([_mesh(corners)], dsa.Config(repair_topology=True, weld_points=weld, repair_seams=True), handle=True)
-            assert [c[0] for c in r.calls] == ["dsa_encode_seam_repair_batch"]
-            _, n, _, grids, opt, _ = r.calls[0][1]
-            o = opt._obj
-            assert n == 1 and grids is None and o.corner_repair == 1 and o.grid.repair.topology == 1 and o.grid.weld_points == (1 if weld else 0)
-            assert list(o.reserved) == [0] * 7
+            grids, o = the_call()
+            assert grids is None and o.corner_repair == 1 and o.grid.repair.topology == 1 and o.grid.weld_points == (1 if weld else 0)
     # a grid rides along
     del r.calls[:]
     m = _mesh(True)
     m.position_grid = dsa.Grid([0, 0, 0], 2.0)
     enc.EncodeBatch([m], dsa.Config(repair_topology=True, repair_seams=True), handle=True)
-    assert [c[0] for c in r.calls] == ["dsa_encode_seam_repair_batch"] and r.calls[0][1][3] is not None
+    grids, o = the_call()
+    assert grids is not None and o.corner_repair == 1
     del r.calls[:]
     enc.EncodeBatch([m], dsa.Config(repair_topology=True), handle=True)
-    assert [c[0] for c in r.calls] == ["dsa_encode_grid_batch"]
-    # nothing set: the per-vertex call, as ever
+    grids, o = the_call()
+    assert grids is not None and o.corner_repair == 0 and o.grid.repair.topology == 1      # (the request of dsa_encode_grid_batch)
+    # nothing set: every added field at its default, the request of the per-vertex call as ever
     del r.calls[:]
     enc.EncodeBatch([_mesh()], dsa.Config(), handle=True)
-    assert [c[0] for c in r.calls] == ["dsa_encode_batch"]
+    grids, o = the_call()
+    assert grids is None and (o.corner_repair, o.grid.weld_points, o.grid.repair.topology) == (0, 0, 0)
+    lv = o.grid.repair.level
+    assert (lv.multi_parallelogram, lv.traversal_method, lv.ex.edgebreaker_method, lv.ex.normal_prediction) == (0, 0, 0, 0)

@@ -7,6 +7,7 @@ import struct
 import numpy as np
 import pytest
 
+import encodecall
 import attrcases as A
 import irregular
 import oracle
@@ -14,7 +15,6 @@ import typedcases as T
 import draco_sharp_amd as dsa
 import draco_sharp_amd.synth as synth
 from draco_sharp_amd import native
-from draco_sharp_amd.encoder import _fill_attr_input
 
 pytestmark = pytest.mark.gpu
 
@@ -60,51 +60,13 @@ def cpu(m, cfg):
                                      extra=extras_of(m))
 
 
-def fill(arr_i, m, keep):
-    """A dsa_mesh_attr_input from MeshData / PointCloudData."""
-    _fill_attr_input(arr_i, m, keep)
-    ci = arr_i.mesh
-    mi = ci.mesh
-    mi.num_vertices, mi.num_faces = len(m.positions), len(m.faces)
-    mi.positions = m.positions.ctypes.data
-    mi.faces = m.faces.ctypes.data if len(m.faces) else None
-    mi.normals = m.normals.ctypes.data if m.normals is not None else None
-    mi.texcoords = m.texcoords.ctypes.data if m.texcoords is not None else None
-    mi.generic = m.generic.ctypes.data if m.generic is not None else None
-    mi.generic_components = m.generic.shape[1] if m.generic is not None else 0
-    nci, uci = getattr(m, "normal_corners", None), getattr(m, "texcoord_corners", None)
-    ci.normal_corners = nci.ctypes.data if nci is not None else None
-    ci.texcoord_corners = uci.ctypes.data if uci is not None else None
-    ci.num_normals = len(m.normals) if m.normals is not None else 0
-    ci.num_texcoords = len(m.texcoords) if m.texcoords is not None else 0
-
-
 def raw(ctx, meshes, cfg, geometry=1, edit=None, opt=None):
     """The entry point cfg asks for, straight: (call status, [(status, bytes or the mesh's message)]).  edit(arr, keep): changes
     to the native array before the call."""
-    L = native.lib()
-    n = len(meshes)
-    arr = (native.MeshAttrInput * max(1, n))()
-    keep = []
-    for i, m in enumerate(meshes):
-        fill(arr[i], m, keep)
-    if edit:
-        edit(arr, keep)
     sequential = geometry == 0 or cfg.sequential
     if opt is None:
         opt = cfg._native_sequential(geometry) if sequential else cfg._native_ex()
-    h = C.c_void_p()
-    entry = L.dsa_encode_attributes_sequential_batch if sequential else L.dsa_encode_attributes_batch
-    st = entry(ctx._h, n, arr, C.byref(opt), C.byref(h))
-    if st != 0:
-        return st, None
-    out = []
-    p, ln = C.c_void_p(), C.c_size_t()
-    for i in range(n):
-        s = L.dsa_encoded_stream(h, i, C.byref(p), C.byref(ln))
-        out.append((s, C.string_at(p, ln.value) if s == 0 else ctx.error()))
-    L.dsa_encoded_free(h)
-    return st, out
+    return encodecall.call(ctx, "dsa_encode_attributes_sequential_batch" if sequential else "dsa_encode_attributes_batch", meshes, opt, edit=edit)
 
 
 def check_equal(ctx, meshes, cfg, names=None, geometry=1):

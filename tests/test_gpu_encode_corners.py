@@ -2,12 +2,12 @@
 ids per face corner become attribute seams (seam bits, the attribute's own corner table and order, corner attributes).  The
 device coder must write, byte for byte, the stream of the CPU coder (synth.encode_mesh_corners) on both connectivity paths,
 round-trip through the GPU decoder's wave-per-mesh kernels, and fail mesh by mesh where the CPU coder refuses."""
-import ctypes as C
 import os
 
 import numpy as np
 import pytest
 
+import encodecall
 import oracle
 import draco_sharp_amd as dsa
 import draco_sharp_amd.synth as synth
@@ -55,33 +55,12 @@ def data(mesh):
 
 def raw_encode(ctx, meshes, cfg=None, corners=True):
     """(status, bytes) per mesh straight from the C-ABI: a failure stays with its mesh."""
-    L = native.lib()
-    n = len(meshes)
-    arr = ((native.MeshCornerInput if corners else native.MeshInput) * n)()
-    for i, m in enumerate(meshes):
-        mi = arr[i].mesh if corners else arr[i]
-        mi.num_vertices, mi.num_faces = len(m.positions), len(m.faces)
-        mi.positions, mi.faces = m.positions.ctypes.data, m.faces.ctypes.data
-        mi.normals = m.normals.ctypes.data if m.normals is not None else None
-        mi.texcoords = m.texcoords.ctypes.data if m.texcoords is not None else None
-        g = m.generic
-        mi.generic = g.ctypes.data if g is not None else None
-        mi.generic_components = getattr(m, "generic_components_override", g.shape[1] if g is not None else 0)
-        if corners:
-            arr[i].normal_corners = m.normal_corners.ctypes.data if m.normal_corners is not None else None
-            arr[i].texcoord_corners = m.texcoord_corners.ctypes.data if m.texcoord_corners is not None else None
-            arr[i].num_normals = len(m.normals) if m.normals is not None else 0
-            arr[i].num_texcoords = len(m.texcoords) if m.texcoords is not None else 0
-    opt = (cfg or dsa.Config())._native()
-    h = C.c_void_p()
-    st = (L.dsa_encode_batch_corners if corners else L.dsa_encode_batch)(ctx._h, n, arr, C.byref(opt), C.byref(h))
+    def edit(arr, keep):
+        for i, m in enumerate(meshes):
+            if hasattr(m, "generic_components_override"):
+                (arr[i].mesh if corners else arr[i]).generic_components = m.generic_components_override
+    st, out = encodecall.call(ctx, "dsa_encode_batch_corners" if corners else "dsa_encode_batch", meshes, (cfg or dsa.Config())._native(), edit=edit, messages=False)
     assert st == 0, ctx.error()
-    out = []
-    p, ln = C.c_void_p(), C.c_size_t()
-    for i in range(n):
-        s = L.dsa_encoded_stream(h, i, C.byref(p), C.byref(ln))
-        out.append((s, C.string_at(p, ln.value) if s == 0 else None))
-    L.dsa_encoded_free(h)
     return out
 
 

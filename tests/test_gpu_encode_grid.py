@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import encodecall
 import defects
 import gridcases as gc
 import irregular
@@ -238,26 +239,10 @@ def test_refusals_in_a_batch_of_eight(ctx, monkeypatch, host):
     assert np.array_equal(np.float32(a.q_min[:3]), o4) and np.float32(a.q_range) == r4
 
 
-def raw(ctx, entry, arr, n, *args):
-    L = native.lib()
-    h = C.c_void_p()
-    assert getattr(L, entry)(ctx._h, n, arr, *args, C.byref(h)) == 0, ctx.error()
-    out = []
-    p, ln = C.c_void_p(), C.c_size_t()
-    for i in range(n):
-        s = L.dsa_encoded_stream(h, i, C.byref(p), C.byref(ln))
-        out.append((s, C.string_at(p, ln.value) if s == 0 else ctx.error()))
-    L.dsa_encoded_free(h)
+def raw(ctx, entry, meshes, opt, *grids):
+    st, out = encodecall.call(ctx, entry, meshes, opt, *grids)
+    assert st == 0, ctx.error()
     return out
-
-
-def fill(arr, meshes):
-    for i, m in enumerate(meshes):
-        mi = arr[i].mesh.mesh
-        mi.num_vertices, mi.num_faces = len(m.positions), len(m.faces)
-        mi.positions = m.positions.ctypes.data
-        mi.faces = m.faces.ctypes.data if len(m.faces) else None
-        mi.texcoords = m.texcoords.ctypes.data if m.texcoords is not None else None
 
 
 @BOTH_PATHS
@@ -267,27 +252,23 @@ def test_mode_0_through_the_new_calls_is_the_call_it_stands_beside(ctx, monkeypa
     tiles = [c for c, _ in gc.tiles()]
     meshes = [dsa.MeshData(c.pos, c.faces, texcoords=c.uvs) for c in tiles] + [damaged_tile(1)]
     n = len(meshes)
-    arr = (native.MeshAttrInput * n)()
-    fill(arr, meshes)
     zero = (native.MeshGrids * n)()
     for weld in (0, 1):
         ro = dsa.Config(repair_topology=True, multi_parallelogram=4)._native_repair()
         go = native.EncodeGridOptions()
         L.dsa_encode_default_grid_options(C.byref(go))
         go.repair, go.weld_points = ro, weld
-        want = raw(ctx, "dsa_encode_points_batch" if weld else "dsa_encode_repair_batch", arr, n, C.byref(ro))
+        want = raw(ctx, "dsa_encode_points_batch" if weld else "dsa_encode_repair_batch", meshes, ro)
         assert all(s == 0 for s, _ in want)
-        assert raw(ctx, "dsa_encode_grid_batch", arr, n, None, C.byref(go)) == want
-        assert raw(ctx, "dsa_encode_grid_batch", arr, n, zero, C.byref(go)) == want
+        assert raw(ctx, "dsa_encode_grid_batch", meshes, go, None) == want
+        assert raw(ctx, "dsa_encode_grid_batch", meshes, go, zero) == want
     clouds = [dsa.PointCloudData(p) for p in gc.cloud_chunks()]
     for geometry, ms in ((1, meshes[:4]), (0, clouds)):
-        arr = (native.MeshAttrInput * len(ms))()
-        fill(arr, ms)
         so = dsa.Config(encoding_method=0)._native_sequential(geometry)
-        want = raw(ctx, "dsa_encode_attributes_sequential_batch", arr, len(ms), C.byref(so))
+        want = raw(ctx, "dsa_encode_attributes_sequential_batch", ms, so)
         assert all(s == 0 for s, _ in want)
-        assert raw(ctx, "dsa_encode_grid_sequential_batch", arr, len(ms), None, C.byref(so)) == want
-        assert raw(ctx, "dsa_encode_grid_sequential_batch", arr, len(ms), zero, C.byref(so)) == want
+        assert raw(ctx, "dsa_encode_grid_sequential_batch", ms, so, None) == want
+        assert raw(ctx, "dsa_encode_grid_sequential_batch", ms, so, zero) == want
 
 
 def test_a_point_cloud_in_four_chunks_shares_one_grid(ctx):
@@ -308,8 +289,6 @@ def test_argument_failures_per_mesh(ctx):
     c = gc.voxel()
     m = dsa.MeshData(c.pos, c.faces)
     n = 6
-    arr = (native.MeshAttrInput * n)()
-    fill(arr, [m] * n)
     grids = (native.MeshGrids * n)()
     grids[0].position.mode = 7
     grids[1].position.mode, grids[1].position.range = 1, 0.0
@@ -319,7 +298,7 @@ def test_argument_failures_per_mesh(ctx):
     grids[5].position.reserved[0] = 1
     go = native.EncodeGridOptions()
     L.dsa_encode_default_grid_options(C.byref(go))
-    got = raw(ctx, "dsa_encode_grid_batch", arr, n, grids, C.byref(go))
+    got = raw(ctx, "dsa_encode_grid_batch", [m] * n, go, grids)
     assert [s for s, _ in got] == [native.DSA_ERR_INVALID_ARGUMENT] * n
     for (_, text), field in zip(got, ("positions: grid.mode 7", "positions: grid.range 0", "positions: grid.origin[2] is not finite",
                                       "texcoords: grid.mode 2 for an attribute the mesh does not have", "dsa_mesh_grids.reserved is not zero",

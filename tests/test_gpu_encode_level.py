@@ -8,6 +8,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import encodecall
 import irregular
 import oracle
 import draco_sharp_amd as dsa
@@ -63,53 +64,10 @@ def cpu(m, cfg):
     return synth.encode_mesh(m.positions, m.faces, m.normals, m.texcoords, generic=m.generic, opt=opt_of(cfg, m), extra=extra)
 
 
-def fill(arr, keep, meshes):
-    for i, m in enumerate(meshes):
-        atts = m.attributes
-        arr[i].num_attributes = len(atts)
-        if atts:
-            a = (native.AttributeInput * len(atts))()
-            for k, x in enumerate(atts):
-                a[k].attribute_type, a[k].data_type, a[k].num_components = x.attribute_type, x.data_type, x.values.shape[1]
-                a[k].normalized = 1 if x.normalized else 0
-                a[k].unique_id = native.UNIQUE_ID_DEFAULT if x.unique_id is None else x.unique_id
-                a[k].quantization_bits = x.quantization_bits
-                a[k].values = x.values.ctypes.data
-            keep.append(a)
-            arr[i].attributes = a
-        ci = arr[i].mesh
-        mi = ci.mesh
-        mi.num_vertices, mi.num_faces = len(m.positions), len(m.faces)
-        mi.positions, mi.faces = m.positions.ctypes.data, m.faces.ctypes.data
-        mi.normals = m.normals.ctypes.data if m.normals is not None else None
-        mi.texcoords = m.texcoords.ctypes.data if m.texcoords is not None else None
-        mi.generic = m.generic.ctypes.data if m.generic is not None else None
-        mi.generic_components = m.generic.shape[1] if m.generic is not None else 0
-        ci.normal_corners = m.normal_corners.ctypes.data if m.normal_corners is not None else None
-        ci.texcoord_corners = m.texcoord_corners.ctypes.data if m.texcoord_corners is not None else None
-        ci.num_normals = len(m.normals) if m.normals is not None else 0
-        ci.num_texcoords = len(m.texcoords) if m.texcoords is not None else 0
-
-
 def raw(ctx, meshes, opt, entry="dsa_encode_level_batch"):
     """(call status, [(status, bytes) per mesh]) from dsa_encode_level_batch (opt: an EncodeLevelOptions) or another entry point
     that takes dsa_mesh_attr_input."""
-    L = native.lib()
-    n = len(meshes)
-    arr = (native.MeshAttrInput * max(1, n))()
-    keep = []
-    fill(arr, keep, meshes)
-    h = C.c_void_p()
-    st = getattr(L, entry)(ctx._h, n, arr, C.byref(opt), C.byref(h))
-    if st != 0:
-        return st, None
-    out = []
-    p, ln = C.c_void_p(), C.c_size_t()
-    for i in range(n):
-        s = L.dsa_encoded_stream(h, i, C.byref(p), C.byref(ln))
-        out.append((s, C.string_at(p, ln.value) if s == 0 else None))
-    L.dsa_encoded_free(h)
-    return st, out
+    return encodecall.call(ctx, entry, meshes, opt, messages=False)
 
 
 def encode(ctx, meshes, cfg):

@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import encodecall
 import defects
 import draco_sharp_amd as dsa
 import draco_sharp_amd.synth as synth
@@ -17,7 +18,7 @@ import oracle
 import seamdefects as sd
 import weldcases
 from draco_sharp_amd import native
-from test_gpu_encode_points import LEVELS as POINT_LEVELS, fill, opt_of
+from test_gpu_encode_points import LEVELS as POINT_LEVELS, opt_of
 
 pytestmark = pytest.mark.gpu
 
@@ -66,25 +67,13 @@ def cpu(m, cfg, value=2):
 
 def encode(ctx, meshes, cfg, corner_repair=1, entry="dsa_encode_seam_repair_batch"):
     """[(status, bytes or the refusal's text) per mesh] through the new call (or dsa_encode_grid_batch with the same grid options)"""
-    L = native.lib()
-    n = len(meshes)
-    arr = (native.MeshAttrInput * max(1, n))()
-    keep = []
-    fill(arr, keep, meshes)
     so = native.EncodeSeamRepairOptions()
-    L.dsa_encode_default_seam_repair_options(C.byref(so))
+    native.lib().dsa_encode_default_seam_repair_options(C.byref(so))
     so.grid.repair = cfg._native_repair()
     so.grid.weld_points = 1 if cfg.weld_points else 0
     so.corner_repair = corner_repair
-    h = C.c_void_p()
-    st = getattr(L, entry)(ctx._h, n, arr, None, C.byref(so if entry == "dsa_encode_seam_repair_batch" else so.grid), C.byref(h))
+    st, out = encodecall.call(ctx, entry, meshes, so if entry == "dsa_encode_seam_repair_batch" else so.grid, grids=None)
     assert st == 0, ctx.error()
-    out = []
-    p, ln = C.c_void_p(), C.c_size_t()
-    for i in range(n):
-        s = L.dsa_encoded_stream(h, i, C.byref(p), C.byref(ln))
-        out.append((s, C.string_at(p, ln.value) if s == 0 else ctx.error()))
-    L.dsa_encoded_free(h)
     return out
 
 

@@ -8,6 +8,7 @@ import itertools
 import numpy as np
 import pytest
 
+import encodecall
 import draco_sharp_amd as dsa
 import draco_sharp_amd.synth as synth
 import irregular
@@ -42,29 +43,7 @@ def cpu(m, cfg):
 
 def raw_seq(ctx, meshes, opt):
     """dsa_encode_sequential_batch with an EncodeSequentialOptions: (call status, [(status, bytes or None)])."""
-    L = native.lib()
-    n = len(meshes)
-    arr = (native.MeshInput * max(1, n))()
-    for i, m in enumerate(meshes):
-        mi = arr[i]
-        mi.num_vertices, mi.num_faces = len(m.positions), len(m.faces)
-        mi.positions = m.positions.ctypes.data
-        mi.faces = m.faces.ctypes.data if len(m.faces) else None
-        mi.normals = m.normals.ctypes.data if m.normals is not None else None
-        mi.texcoords = m.texcoords.ctypes.data if m.texcoords is not None else None
-        mi.generic = m.generic.ctypes.data if m.generic is not None else None
-        mi.generic_components = m.generic.shape[1] if m.generic is not None else 0
-    h = C.c_void_p()
-    st = L.dsa_encode_sequential_batch(ctx._h, n, arr, C.byref(opt) if opt is not None else None, C.byref(h))
-    if st != 0:
-        return st, None
-    out = []
-    p, ln = C.c_void_p(), C.c_size_t()
-    for i in range(n):
-        s = L.dsa_encoded_stream(h, i, C.byref(p), C.byref(ln))
-        out.append((s, C.string_at(p, ln.value) if s == 0 else None))
-    L.dsa_encoded_free(h)
-    return st, out
+    return encodecall.call(ctx, "dsa_encode_sequential_batch", meshes, opt, messages=False)
 
 
 def encode(ctx, meshes, cfg, geometry=1):

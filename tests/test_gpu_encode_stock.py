@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import encodecall
 import oracle
 import draco_sharp_amd as dsa
 import draco_sharp_amd.synth as synth
@@ -62,30 +63,7 @@ def cpu(m, cfg):
 
 def raw_ex(ctx, meshes, opt):
     """(status, bytes) per mesh from dsa_encode_batch_ex; opt: an EncodeOptionsEx.  Returns (call status, list)."""
-    L = native.lib()
-    n = len(meshes)
-    arr = (native.MeshCornerInput * max(1, n))()
-    for i, m in enumerate(meshes):
-        mi = arr[i].mesh
-        mi.num_vertices, mi.num_faces = len(m.positions), len(m.faces)
-        mi.positions, mi.faces = m.positions.ctypes.data, m.faces.ctypes.data
-        mi.normals = m.normals.ctypes.data if m.normals is not None else None
-        mi.texcoords = m.texcoords.ctypes.data if m.texcoords is not None else None
-        arr[i].normal_corners = m.normal_corners.ctypes.data if m.normal_corners is not None else None
-        arr[i].texcoord_corners = m.texcoord_corners.ctypes.data if m.texcoord_corners is not None else None
-        arr[i].num_normals = len(m.normals) if m.normals is not None else 0
-        arr[i].num_texcoords = len(m.texcoords) if m.texcoords is not None else 0
-    h = C.c_void_p()
-    st = L.dsa_encode_batch_ex(ctx._h, n, arr, C.byref(opt), C.byref(h))
-    if st != 0:
-        return st, None
-    out = []
-    p, ln = C.c_void_p(), C.c_size_t()
-    for i in range(n):
-        s = L.dsa_encoded_stream(h, i, C.byref(p), C.byref(ln))
-        out.append((s, C.string_at(p, ln.value) if s == 0 else None))
-    L.dsa_encoded_free(h)
-    return st, out
+    return encodecall.call(ctx, "dsa_encode_batch_ex", meshes, opt, messages=False)
 
 
 def encode(ctx, meshes, cfg):

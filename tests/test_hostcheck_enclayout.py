@@ -4,7 +4,10 @@ streams, enc_layout_sequential for sequential ones) compiled for the host under 
 exactly the regions in front of input_bytes, everything the kernels write behind it, no two regions overlapping, every offset of
 a record a region handed out -- per vertex and with seamed UVs and normals, host and device connectivity, both attribute orders,
 predictions 1 / 4 / 5 / 6, valence on and off, a uint16 and a float32 extra, a mesh that fails its checks in the middle of the
-batch, and the sequential layout with raw indices, compressed indices and as a point cloud.  A check of the product source on
+batch, and the sequential layout with raw indices, compressed indices and as a point cloud.  The per-vertex and the corner form
+go through the library's own widening (enc_widen); beside the counted chunks the program checks that a widened batch is laid out
+region for region and record for record like the widest form without its list, and pins what each form answers to a generic
+attribute of 5 components (dsa_encode_batch's request drops it, every other refuses the mesh).  A check of the product source on
 CPU, not a CPU encode path."""
 import os
 import struct

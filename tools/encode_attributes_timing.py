@@ -19,7 +19,7 @@ sys.path.insert(0, ROOT)
 import draco_sharp_amd as dsa  # noqa: E402
 import draco_sharp_amd.synth as synth  # noqa: E402
 from draco_sharp_amd import native  # noqa: E402
-from draco_sharp_amd.encoder import _fill_attr_input  # noqa: E402
+from draco_sharp_amd.encoder import _native_meshes  # noqa: E402
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
 ctx = dsa.Context(0)
@@ -44,20 +44,9 @@ listed = [dsa.MeshData(p, f, nr, u, attributes=extras[i]) for i, (p, nr, u, f) i
 keep = []
 
 
-def corner_input(dst, m):
-    mi = dst.mesh
-    mi.num_vertices, mi.num_faces = len(m.positions), len(m.faces)
-    mi.positions, mi.faces = m.positions.ctypes.data, m.faces.ctypes.data
-    mi.normals, mi.texcoords = m.normals.ctypes.data, m.texcoords.ctypes.data
-
-
 def arrays(meshes, with_list):
-    arr = ((native.MeshAttrInput if with_list else native.MeshCornerInput) * n)()
-    for i in range(n):
-        m = meshes[i % 16]
-        if with_list:
-            _fill_attr_input(arr[i], m, keep)
-        corner_input(arr[i].mesh if with_list else arr[i], m)
+    arr, _, alive = _native_meshes([meshes[i % 16] for i in range(n)], native.MeshAttrInput if with_list else native.MeshCornerInput)
+    keep.append(alive)
     return arr
 
 

@@ -26,17 +26,14 @@ rounds = int(args[1]) if len(args) > 1 else 3
 
 import draco_sharp_amd as dsa  # noqa: E402
 import draco_sharp_amd.synth as synth  # noqa: E402
+import encodecall  # noqa: E402
 from draco_sharp_amd import native  # noqa: E402
 
 ctx = dsa.Context(0)
 L = native.lib()
 plain = [synth.make_mesh(synth.GRID, 128, 256, 1000 + i) for i in range(16)]
 meshes = [dsa.MeshData(plain[i % 16][0], plain[i % 16][3], plain[i % 16][1], plain[i % 16][2]) for i in range(n)]
-arr = (native.MeshAttrInput * n)()
-for i, m in enumerate(meshes):
-    mi = arr[i].mesh.mesh
-    mi.num_vertices, mi.num_faces = len(m.positions), len(m.faces)
-    mi.positions, mi.faces, mi.normals, mi.texcoords = m.positions.ctypes.data, m.faces.ctypes.data, m.normals.ctypes.data, m.texcoords.ctypes.data
+arr = encodecall.arrays(meshes)[0]
 
 
 def bounds(arrays):

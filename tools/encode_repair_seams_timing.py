@@ -45,6 +45,7 @@ if not stages_only:
               % (float(call.group(1)), repair_ms, weld_ms, chunk_ms, 100.0 * repair_ms / chunk_ms, 100.0 * weld_ms / chunk_ms), flush=True)
 
 import defects  # noqa: E402
+import encodecall  # noqa: E402
 import draco_sharp_amd as dsa  # noqa: E402
 import draco_sharp_amd.synth as synth  # noqa: E402
 import irregular  # noqa: E402
@@ -71,13 +72,7 @@ print("per mesh: %d points, %d faces clean; %d points, %d faces with 50 defects"
 
 
 def inputs(meshes):
-    arr = (native.MeshAttrInput * n)()
-    for i in range(n):
-        m = meshes[i % 16]
-        mi = arr[i].mesh.mesh
-        mi.num_vertices, mi.num_faces = len(m.positions), len(m.faces)
-        mi.positions, mi.faces, mi.normals, mi.texcoords = m.positions.ctypes.data, m.faces.ctypes.data, m.normals.ctypes.data, m.texcoords.ctypes.data
-    return arr
+    return encodecall.arrays([meshes[i % 16] for i in range(n)])[0]
 
 
 cfg = dsa.Config(repair_topology=True, repair_seams=True, weld_points=True)

@@ -42,6 +42,7 @@ if not stages_only:
               % (float(call.group(1)), repair_ms, chunk_ms, 100.0 * repair_ms / chunk_ms), flush=True)
 
 import defects  # noqa: E402
+import encodecall  # noqa: E402
 import draco_sharp_amd as dsa  # noqa: E402
 import draco_sharp_amd.synth as synth  # noqa: E402
 from draco_sharp_amd import native  # noqa: E402
@@ -61,12 +62,7 @@ for i in range(5, n, 16):
 
 
 def inputs(meshes):
-    arr = (native.MeshAttrInput * len(meshes))()
-    for i, m in enumerate(meshes):
-        mi = arr[i].mesh.mesh
-        mi.num_vertices, mi.num_faces = len(m.positions), len(m.faces)
-        mi.positions, mi.faces, mi.normals, mi.texcoords = m.positions.ctypes.data, m.faces.ctypes.data, m.normals.ctypes.data, m.texcoords.ctypes.data
-    return arr
+    return encodecall.arrays(meshes)[0]
 
 
 cfg = dsa.Config()

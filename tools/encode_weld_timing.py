@@ -42,6 +42,7 @@ if not stages_only:
               % (float(call.group(1)), weld_ms, chunk_ms, 100.0 * weld_ms / chunk_ms), flush=True)
 
 import draco_sharp_amd as dsa  # noqa: E402
+import encodecall  # noqa: E402
 import draco_sharp_amd.synth as synth  # noqa: E402
 import irregular  # noqa: E402
 import weldcases  # noqa: E402
@@ -63,27 +64,12 @@ print("per mesh: %d points -> %d vertices, %d uv rows; the weld stage moves %.0f
       "the welded rows then go up again with the ordinary uploads" % (len(points[0].positions), len(welded[0].positions), len(welded[0].texcoords), up / 1024, down / 1024), flush=True)
 
 
-def inputs(meshes):
-    arr = (native.MeshAttrInput * n)()
-    for i in range(n):
-        m = meshes[i % 16]
-        ci = arr[i].mesh
-        mi = ci.mesh
-        mi.num_vertices, mi.num_faces = len(m.positions), len(m.faces)
-        mi.positions, mi.faces, mi.normals, mi.texcoords = m.positions.ctypes.data, m.faces.ctypes.data, m.normals.ctypes.data, m.texcoords.ctypes.data
-        if m.texcoord_corners is not None:
-            ci.texcoord_corners, ci.num_texcoords = m.texcoord_corners.ctypes.data, len(m.texcoords)
-        if m.normal_corners is not None:
-            ci.normal_corners, ci.num_normals = m.normal_corners.ctypes.data, len(m.normals)
-    return arr
+def inputs(meshes, form=None):
+    return encodecall.arrays([meshes[i % 16] for i in range(n)], form)[0]
 
 
 def corner_inputs(meshes):
-    arr = (native.MeshCornerInput * n)()
-    full = inputs(meshes)
-    for i in range(n):
-        arr[i] = full[i].mesh
-    return arr
+    return inputs(meshes, native.MeshCornerInput)
 
 
 cfg = dsa.Config()
