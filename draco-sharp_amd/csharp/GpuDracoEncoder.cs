@@ -19,6 +19,11 @@
 // DracoEncoder.Encode codes them, instead of failing; clean meshes give the same bytes.  A mesh in corner form that needs the
 // repair still fails (NotImplementedException) unless RepairSeams is set (dsa_encode_seam_repair_batch, corner_repair 1): then its
 // normals and texture coordinates are coded over the repaired table, as DracoEncoder.Encode codes them.
+// CornerAttributes / WeldAttributes (dsa_encode_corner_attributes_batch): the attributes beyond the built-in slots -- a second UV set,
+// colours, feature ids -- may have seams of their own.  CornerAttributes: in corner form, such an attribute whose point-to-value map
+// differs from the positions' keeps its own values with an id per corner taken from that map.  WeldAttributes (with WeldPoints): the
+// library welds every such attribute alone instead of making it part of the vertex key.  Neither set: the calls and their bytes are
+// what they were.  (Like the rest of this file, written against the header and not compiled in the build image.)
 using System;
 using System.Collections.Generic;
 using System.IO;
@@ -50,6 +55,17 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
     /// are one vertex, normals and texture coordinates become corner attributes where a vertex has two of them.  For meshes whose
     /// point-to-value maps were never deduplicated (a glTF primitive or an OBJ loaded row by row).  Unset: nothing changes.</summary>
     public bool WeldPoints { get; set; }
+
+    /// <summary>With WeldPoints: weld every attribute beyond the built-in slots alone, like normals and texture coordinates, instead
+    /// of making its rows part of the vertex key (dsa_encode_corner_attributes_batch, weld_attributes 1): a lightmap UV set or a
+    /// colour with a hard edge then cuts its own connectivity only.  An attribute past index 7 of the stream stays in the key.
+    /// Unset: nothing changes.</summary>
+    public bool WeldAttributes { get; set; }
+
+    /// <summary>In corner form: an attribute beyond the built-in slots whose point-to-value map differs from the positions' keeps its
+    /// own values, with an id per corner taken from that map (dsa_encode_corner_attributes_batch), instead of one value per position
+    /// value.  The attribute must lie at index 1 to 7 of the stream.  Unset: nothing changes.</summary>
+    public bool CornerAttributes { get; set; }
 
     // Quantisation grids (dsa_encode_grid_batch).  The reference's own options quantization_origin / quantization_range, set per
     // attribute type for positions or texture coordinates, are honoured as explicit grids (SequentialQuantizationAttributeEncoder.cs:
@@ -197,6 +213,7 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
         if (multi != 0 && uvScheme == multi) opt.TexcoordPrediction = 1;
         if (SpeedLadder && config.Speed == 0) traversal = 1;
         if (RepairSeams && !RepairTopology) throw new ArgumentException("RepairSeams codes attributes over the repaired corner table: it needs RepairTopology");
+        if (WeldAttributes && !WeldPoints) throw new ArgumentException("WeldAttributes welds the attributes of per-point input each alone: it needs WeldPoints");
         var inputs = new DsaMeshInput[meshes.Count];
         var pins = new List<GCHandle>();
         IntPtr encoded = IntPtr.Zero;
@@ -231,6 +248,17 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
                 wp.Topology = RepairTopology ? 1 : 0;
                 var wg = Grids(config, meshes.Count);
                 if (wg != null) for (int i = 0; i < meshes.Count; ++i) if (pin[i].Mesh.Mesh.Texcoords == null) wg[i].Texcoord = default;
+                if (WeldAttributes)
+                {
+                    NativeMethods.dsa_encode_default_corner_attributes_options(out var co);
+                    co.SeamRepair.Grid.Repair = wp;
+                    co.SeamRepair.Grid.WeldPoints = 1;
+                    co.SeamRepair.CornerRepair = RepairSeams ? 1 : 0;
+                    co.WeldAttributes = 1;
+                    fixed (DsaMeshAttrInput* p = pin) fixed (DsaMeshGrids* g = wg)
+                        NativeMethods.Check(NativeMethods.dsa_encode_corner_attributes_batch(_ctx, (uint)meshes.Count, p, g, null, in co, out encoded), _ctx, "dsa_encode_corner_attributes_batch");
+                    return Streams(encoded, meshes.Count);
+                }
                 if (RepairSeams)
                 {
                     NativeMethods.dsa_encode_default_seam_repair_options(out var so);
@@ -261,16 +289,31 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
             {
                 // the attribute list rides on the corner form (extras per vertex: the value of the last point of each position value)
                 var ain = new DsaMeshAttrInput[meshes.Count];
+                var acorners = CornerAttributes && anyExtras ? new DsaMeshAttributeCorners[meshes.Count] : null;
+                bool anyAttributeIds = false;
                 for (int i = 0; i < meshes.Count; ++i)
                 {
                     CornerForm(meshes[i], ref ain[i].Mesh, pins);
-                    Extras(meshes[i], meshes[i].GetNamedAttribute(GeometryAttributeType.Position), ain[i].Mesh.Mesh.NumVertices, ref ain[i], pins);
+                    if (acorners == null) Extras(meshes[i], meshes[i].GetNamedAttribute(GeometryAttributeType.Position), ain[i].Mesh.Mesh.NumVertices, ref ain[i], pins);
+                    else anyAttributeIds = CornerExtras(meshes[i], ain[i].Mesh.Mesh.NumVertices, ref ain[i], ref acorners[i], pins) || anyAttributeIds;
                 }
                 NativeMethods.dsa_encode_default_options_ex(out var ax);
                 ax.Base = opt;
                 ax.EdgebreakerMethod = ebMethod != unset ? ebMethod : 0;
                 ax.NormalPrediction = normalScheme != unset ? normalScheme : 0;
                 if (grids != null) for (int i = 0; i < meshes.Count; ++i) if (ain[i].Mesh.Mesh.Texcoords == null) grids[i].Texcoord = default;
+                if (anyAttributeIds)
+                {
+                    NativeMethods.dsa_encode_default_corner_attributes_options(out var co);
+                    co.SeamRepair.Grid.Repair.Level.Ex = ax;
+                    co.SeamRepair.Grid.Repair.Level.MultiParallelogram = multi;
+                    co.SeamRepair.Grid.Repair.Level.TraversalMethod = traversal;
+                    co.SeamRepair.Grid.Repair.Topology = RepairTopology ? 1 : 0;
+                    co.SeamRepair.CornerRepair = RepairSeams ? 1 : 0;
+                    fixed (DsaMeshAttrInput* p = ain) fixed (DsaMeshGrids* g = grids) fixed (DsaMeshAttributeCorners* c = acorners)
+                        NativeMethods.Check(NativeMethods.dsa_encode_corner_attributes_batch(_ctx, (uint)meshes.Count, p, g, c, in co, out encoded), _ctx, "dsa_encode_corner_attributes_batch");
+                    return Streams(encoded, meshes.Count);
+                }
                 if (RepairSeams)
                 {
                     NativeMethods.dsa_encode_default_seam_repair_options(out var so);
@@ -537,6 +580,46 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
         }
         dst.Attributes = (DsaAttributeInput*)Pin(list, pins);
         dst.NumAttributes = (uint)extras.Count;
+    }
+
+    // Extras() for the corner form with CornerAttributes: an attribute whose point-to-value map differs from the positions' keeps its
+    // own values (one packed row per value index) and gets an id per corner from that map; every other attribute is per vertex as in
+    // Extras().  Returns whether any attribute got ids.
+    private static bool CornerExtras(Mesh.Mesh m, uint nv, ref DsaMeshAttrInput dst, ref DsaMeshAttributeCorners corners, List<GCHandle> pins)
+    {
+        var pa = m.GetNamedAttribute(GeometryAttributeType.Position)!;
+        Extras(m, pa, nv, ref dst, pins);
+        var extras = ExtraAttributes(m);
+        if (extras.Count == 0) return false;
+        var list = new DsaAttributeCorners[extras.Count];
+        bool any = false;
+        for (int k = 0; k < extras.Count; ++k)
+        {
+            var a = extras[k];
+            bool separate = false;
+            for (uint p = 0; p < m.PointsCount && !separate; ++p) separate = a.MappedIndex(p) != pa.MappedIndex(p);
+            if (!separate) continue;
+            var ids = new uint[m.FacesCount * 3];
+            uint rows = 0;
+            for (int f = 0; f < m.FacesCount; ++f)
+            {
+                var face = m.GetFace((uint)f);
+                for (int c = 0; c < 3; ++c) { ids[3 * f + c] = a.MappedIndex((uint)face[c]); rows = Math.Max(rows, ids[3 * f + c] + 1); }
+            }
+            int row = ElementSize(a.DataType) * a.NumComponents;
+            var bytes = new byte[rows * row];
+            for (uint v = 0; v < rows; ++v)
+            {
+                long src = a.ByteOffset + (long)v * a.ByteStride;
+                for (int b = 0; b < row; ++b) bytes[(long)v * row + b] = a.Buffer!.Read<byte>((int)(src + b));
+            }
+            dst.Attributes[k].Values = (void*)Pin(bytes, pins);
+            list[k].Corners = (uint*)Pin(ids, pins);
+            list[k].NumRows = rows;
+            any = true;
+        }
+        if (any) corners.Attributes = (DsaAttributeCorners*)Pin(list, pins);
+        return any;
     }
 
     private static IntPtr Pin(Array? a, List<GCHandle> pins)

@@ -185,6 +185,32 @@ internal unsafe struct DsaEncodeSeamRepairOptions
     public fixed int Reserved[7];   // zero
 }
 
+// dsa_attribute_corners: row ids per corner for one attribute of the list (16 bytes)
+[StructLayout(LayoutKind.Sequential)]
+internal unsafe struct DsaAttributeCorners
+{
+    public uint* Corners;           // 3 * NumFaces row ids into the attribute's Values, or null: per vertex
+    public uint NumRows;            // rows of Values when Corners is set
+    public uint Reserved;           // zero
+}
+
+// dsa_mesh_attribute_corners: the ids of the listed attributes of one mesh, parallel to DsaMeshAttrInput (16 bytes)
+[StructLayout(LayoutKind.Sequential)]
+internal unsafe struct DsaMeshAttributeCorners
+{
+    public DsaAttributeCorners* Attributes;     // NumAttributes entries or null
+    public fixed uint Reserved[2];  // zero
+}
+
+// dsa_encode_corner_attributes_options (dsa_encode_corner_attributes_batch)
+[StructLayout(LayoutKind.Sequential)]
+internal unsafe struct DsaEncodeCornerAttributesOptions
+{
+    public DsaEncodeSeamRepairOptions SeamRepair;
+    public int WeldAttributes;      // 1: with WeldPoints every listed attribute is welded alone, like normals and texture coordinates
+    public fixed int Reserved[7];   // zero
+}
+
 // dsa_encode_sequential_options (dsa_encode_sequential_batch): sequential meshes and point clouds
 [StructLayout(LayoutKind.Sequential)]
 internal unsafe struct DsaEncodeSequentialOptions
@@ -310,6 +336,8 @@ internal static unsafe partial class NativeMethods
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_grid_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, in DsaEncodeGridOptions options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern void dsa_encode_default_seam_repair_options(out DsaEncodeSeamRepairOptions options);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_seam_repair_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, in DsaEncodeSeamRepairOptions options, out IntPtr encoded);
+    [DllImport(Lib)] internal static extern void dsa_encode_default_corner_attributes_options(out DsaEncodeCornerAttributesOptions options);
+    [DllImport(Lib)] internal static extern DsaStatus dsa_encode_corner_attributes_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, DsaMeshAttributeCorners* corners, in DsaEncodeCornerAttributesOptions options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_grid_sequential_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, in DsaEncodeSequentialOptions options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern DsaStatus dsa_weld_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, out IntPtr welded);
     [DllImport(Lib)] internal static extern uint dsa_welded_size(IntPtr welded);

@@ -766,8 +766,69 @@ static bool enc_host_choice(const char *name, uint32_t batch_n) { const char *e 
 // owns, and the chunk's mesh view pointed at them -- everything behind runs on the welded meshes as if the caller had passed them.
 // Device path: memory of its own per lane, the point arrays up on a turn of the link, the kernels, then counts, maps and welded
 // rows back (the welded rows cross the link again with the ordinary uploads: the layout reads host memory).
+// ---- what the two weld stages share (Rec: dsa::EncWeld, or dsa::EncWeldList of dsa_encode_weld_list.h)
+// the per-point arrays of mesh `m` that both record types hold alike into the upload list: faces, the vertex key's segments, normals,
+// texture coordinates (W.seg[g] / W.set[1] / W.set[2]); false: the mesh is too large for the device weld and is refused
+static bool enc_weld_sizes_fit(EncChunk &ck, uint32_t i, const dsa_mesh_input &m, size_t segments, size_t listed) {
+  if (m.num_vertices > (1u << 28) || m.num_faces > (1u << 28)) { ck.refuse(i, DSA_ERR_INVALID_DATA, "mesh too large for the device weld"); return false; }
+  if (segments + listed + 2 > dsa::EW_MAX_SEGS || listed > dsa::EWL_MAX_LISTED) { ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, "too many attributes for the device weld"); return false; }
+  return true;
+}
+template <class Rec>
+static void enc_weld_uploads(std::vector<EncUpload> &ups, const Rec &W, const dsa_mesh_input &m, const std::vector<synth::WeldSeg> &key) {
+  if (m.num_faces) ups.push_back({W.faces, m.faces, 12ull * m.num_faces, false});
+  for (size_t g = 0; g < key.size() && m.num_vertices; ++g) ups.push_back({W.seg[g].src, key[g].rows, (size_t)m.num_vertices * key[g].row_bytes, false});
+  if (m.normals && m.num_vertices) ups.push_back({W.seg[W.set[1].first_seg].src, m.normals, 12ull * m.num_vertices, false});
+  if (m.texcoords && m.num_vertices) ups.push_back({W.seg[W.set[2].first_seg].src, m.texcoords, 8ull * m.num_vertices, false});
+}
+// the lane's weld memory of `total` bytes, cleared behind the inputs; the uploads on a turn of the link; the records up
+// (ups is in arena order; a piece of enc_upload copies a whole stretch of the arena from pinned staging, gaps included: that is
+// why no region a kernel expects at zero may lie among the inputs)
+template <class Rec>
+static dsa_status enc_weld_begin(dsa_context *ctx, EncLane &lane, hostutil::TurnGuard &turn, uint64_t total, uint64_t input_bytes, const std::vector<EncUpload> &ups,
+                                 const std::vector<Rec> &recs, uint8_t **arena, Rec **d_recs) {
+  ENC_TRY(lane.weld.ensure(total ? total : 256));
+  ENC_TRY(lane.weld_recs.ensure(sizeof(Rec) * recs.size()));
+  *arena = (uint8_t *)lane.weld.p;
+  *d_recs = (Rec *)lane.weld_recs.p;
+  if (total > input_bytes) ENC_TRY(hipMemsetAsync(*arena + input_bytes, 0, total - input_bytes, lane.st));
+  turn.acquire_free();
+  ENC_TRY(enc_upload(lane, *arena, lane.st, ups));
+  turn.release();
+  ENC_TRY(hipMemcpyAsync(*d_recs, recs.data(), sizeof(Rec) * recs.size(), hipMemcpyHostToDevice, lane.st));
+  return DSA_OK;
+}
+// ... the launches checked, the records down
+template <class Rec>
+static dsa_status enc_weld_records(dsa_context *ctx, EncLane &lane, std::vector<Rec> &recs, const Rec *d_recs) {
+  ENC_TRY(hipGetLastError());
+  ENC_TRY(hipMemcpyAsync(recs.data(), d_recs, sizeof(Rec) * recs.size(), hipMemcpyDeviceToHost, lane.st));
+  ENC_TRY(hipStreamSynchronize(lane.st));
+  return DSA_OK;
+}
+// counts known: the maps, the faces and ids, the welded rows in one transfer
+struct EncWeldFetch {
+  std::vector<dsa::PackItem> items;
+  std::vector<void *> dest;
+  void want32(std::vector<uint32_t> &v, uint64_t at, uint64_t count) { v.resize(count); if (count) { items.push_back({at, 0, (uint32_t)(4 * count), 0}); dest.push_back(v.data()); } }
+  void want8(std::vector<uint8_t> &v, uint64_t at, uint64_t bytes) { v.resize(bytes); if (bytes) { items.push_back({at, 0, (uint32_t)bytes, 0}); dest.push_back(v.data()); } }
+  // a key set's maps; one behind the vertex's: its rows (row_bytes each: the set's own classes when some vertex has two, else V) and then its ids
+  void want_keys(synth::WeldKeys &keys, const dsa::EncWeldSet &S, uint32_t P) { keys.count = S.count; want32(keys.of_point, S.of, P); want32(keys.point, S.point, S.count); }
+  void want_attribute(const dsa::EncWeldSet &S, const dsa::EncWeldSeg &seg, bool seamed, uint32_t V, uint32_t F, uint64_t corners_at, std::vector<uint8_t> &rows, std::vector<uint32_t> &corners) {
+    want8(rows, seg.dst, (uint64_t)seg.row_bytes * (seamed ? S.count : V));
+    if (seamed) want32(corners, corners_at, 3ull * F);
+  }
+  dsa_status run(dsa_context *ctx, EncLane &lane, const uint8_t *arena) {
+    const uint8_t *host = nullptr;
+    ENC_ST(enc_gather(lane, arena, items, nullptr, &host));
+    hostutil::parallel_for((uint32_t)items.size(), [&](uint32_t k) { memcpy(dest[k], host + items[k].packed_off, items[k].len); }, 8);
+    return DSA_OK;
+  }
+};
+static dsa_status enc_stage_weld_list(dsa_context *ctx, EncLane &lane, hostutil::TurnGuard &turn, EncChunk &ck);
 static dsa_status enc_stage_weld(dsa_context *ctx, EncLane &lane, hostutil::TurnGuard &turn, EncChunk &ck) {
   if (!ck.rq.weld) return DSA_OK;
+  if (ck.rq.weld_attributes) return enc_stage_weld_list(ctx, lane, turn, ck);
   const uint32_t n = ck.n;
   ck.weld.assign(n, synth::Welded());
   ck.weld_attrs.assign(n, {});
@@ -782,15 +843,11 @@ static dsa_status enc_stage_weld(dsa_context *ctx, EncLane &lane, hostutil::Turn
   for (uint32_t i = 0; i < n && !on_host; ++i) {
     if (!ck.good(i)) continue;
     const dsa_mesh_input &m = ck.rq.mesh(ck.base + i);
-    if (m.num_vertices > (1u << 28) || m.num_faces > (1u << 28)) { ck.refuse(i, DSA_ERR_INVALID_DATA, "mesh too large for the device weld"); continue; }
+    if (!enc_weld_sizes_fit(ck, i, m, keys[i].size(), 0)) continue;
     uint32_t row_bytes[dsa::EW_MAX_SEGS];
-    if (keys[i].size() + 2 > dsa::EW_MAX_SEGS) { ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, "too many attributes for the device weld"); continue; }
     for (size_t g = 0; g < keys[i].size(); ++g) row_bytes[g] = keys[i][g].row_bytes;
     dsa::EncWeld W = dsa::enc_weld_inputs([&](uint64_t bytes) { return A.take(bytes); }, m.num_vertices, m.num_faces, row_bytes, (uint32_t)keys[i].size(), m.normals != nullptr, m.texcoords != nullptr);
-    if (m.num_faces) ups.push_back({W.faces, m.faces, 12ull * m.num_faces, false});
-    for (size_t g = 0; g < keys[i].size() && m.num_vertices; ++g) ups.push_back({W.seg[g].src, keys[i][g].rows, (size_t)m.num_vertices * keys[i][g].row_bytes, false});
-    if (m.normals && m.num_vertices) ups.push_back({W.seg[W.set[1].first_seg].src, m.normals, 12ull * m.num_vertices, false});
-    if (m.texcoords && m.num_vertices) ups.push_back({W.seg[W.set[2].first_seg].src, m.texcoords, 8ull * m.num_vertices, false});
+    enc_weld_uploads(ups, W, m, keys[i]);
     recs.push_back(W); mesh_of.push_back(i);
     most = std::max(most, std::max(m.num_vertices, 3u * m.num_faces));
   }
@@ -805,18 +862,10 @@ static dsa_status enc_stage_weld(dsa_context *ctx, EncLane &lane, hostutil::Turn
     });
   } else if (!recs.empty()) {
     const uint32_t nr = (uint32_t)recs.size();
-    // (ups is in arena order; a piece of enc_upload copies a whole stretch of the arena from pinned staging, gaps included: that
-    // is why no region a kernel expects at zero may lie among the inputs)
     hipStream_t st = lane.st;
-    ENC_TRY(lane.weld.ensure(A.cur ? A.cur : 256));
-    ENC_TRY(lane.weld_recs.ensure(sizeof(dsa::EncWeld) * nr));
-    uint8_t *arena = (uint8_t *)lane.weld.p;
-    dsa::EncWeld *d_recs = (dsa::EncWeld *)lane.weld_recs.p;
-    if (A.cur > input_bytes) ENC_TRY(hipMemsetAsync(arena + input_bytes, 0, A.cur - input_bytes, st));
-    turn.acquire_free();
-    ENC_TRY(enc_upload(lane, arena, st, ups));
-    turn.release();
-    ENC_TRY(hipMemcpyAsync(d_recs, recs.data(), sizeof(dsa::EncWeld) * nr, hipMemcpyHostToDevice, st));
+    uint8_t *arena = nullptr;
+    dsa::EncWeld *d_recs = nullptr;
+    ENC_STAGE(enc_weld_begin(ctx, lane, turn, A.cur, input_bytes, ups, recs, &arena, &d_recs));
     const uint32_t gx = std::max(1u, std::min(128u, (most + 1023u) / 1024u));
     hipLaunchKernelGGL(dsa::k_enc_weld_mark, dim3(gx, nr), dim3(256), 0, st, arena, d_recs, nr);
     hipLaunchKernelGGL(dsa::k_enc_weld_insert, dim3(gx, 3 * nr), dim3(256), 0, st, arena, d_recs, nr);
@@ -824,15 +873,8 @@ static dsa_status enc_stage_weld(dsa_context *ctx, EncLane &lane, hostutil::Turn
     hipLaunchKernelGGL(dsa::k_enc_weld_assign, dim3(gx, 3 * nr), dim3(256), 0, st, arena, d_recs, nr);
     hipLaunchKernelGGL(dsa::k_enc_weld_differs, dim3(gx, 2 * nr), dim3(256), 0, st, arena, d_recs, nr);
     hipLaunchKernelGGL(dsa::k_enc_weld_gather, dim3(gx, nr), dim3(256), 0, st, arena, d_recs, nr);
-    ENC_TRY(hipGetLastError());
-    ENC_TRY(hipMemcpyAsync(recs.data(), d_recs, sizeof(dsa::EncWeld) * nr, hipMemcpyDeviceToHost, st));
-    ENC_TRY(hipStreamSynchronize(st));
-    // counts known: the maps, the faces and ids, the welded rows in one transfer
-    struct Dest { void *p; };
-    std::vector<dsa::PackItem> items;
-    std::vector<Dest> dest;
-    auto want32 = [&](std::vector<uint32_t> &v, uint64_t at, uint64_t count) { v.resize(count); if (count) { items.push_back({at, 0, (uint32_t)(4 * count), 0}); dest.push_back({v.data()}); } };
-    auto want8 = [&](std::vector<uint8_t> &v, uint64_t at, uint64_t bytes) { v.resize(bytes); if (bytes) { items.push_back({at, 0, (uint32_t)bytes, 0}); dest.push_back({v.data()}); } };
+    ENC_STAGE(enc_weld_records(ctx, lane, recs, d_recs));
+    EncWeldFetch fetch;
     for (uint32_t r = 0; r < nr; ++r) {
       const uint32_t i = mesh_of[r];
       const dsa::EncWeld &W = recs[r];
@@ -840,29 +882,106 @@ static dsa_status enc_stage_weld(dsa_context *ctx, EncLane &lane, hostutil::Turn
       synth::Welded &w = ck.weld[i];
       w.P = W.P; w.F = W.F;
       synth::WeldKeys *sets[3] = {&w.vertex, &w.normal, &w.texcoord};
-      for (uint32_t k = 0; k < 3; ++k) {
-        if (W.set[k].num_segs == 0) continue;
-        sets[k]->count = W.set[k].count;
-        want32(sets[k]->of_point, W.set[k].of, W.P);
-        want32(sets[k]->point, W.set[k].point, W.set[k].count);
-      }
+      for (uint32_t k = 0; k < 3; ++k) if (W.set[k].num_segs) fetch.want_keys(*sets[k], W.set[k], W.P);
       const uint32_t V = W.set[0].count;
-      want32(w.faces, W.faces_out, 3ull * W.F);
+      fetch.want32(w.faces, W.faces_out, 3ull * W.F);
       w.vertex_rows.resize(W.set[0].num_segs);
-      for (uint32_t g = 0; g < W.set[0].num_segs; ++g) want8(w.vertex_rows[g], W.seg[g].dst, (uint64_t)V * W.seg[g].row_bytes);
+      for (uint32_t g = 0; g < W.set[0].num_segs; ++g) fetch.want8(w.vertex_rows[g], W.seg[g].dst, (uint64_t)V * W.seg[g].row_bytes);
       w.normals_per_vertex = W.differs[0] == 0; w.texcoords_per_vertex = W.differs[1] == 0;
-      if (W.set[1].num_segs) {
-        want8(w.normal_rows, W.seg[W.set[1].first_seg].dst, 12ull * (W.differs[0] ? W.set[1].count : V));
-        if (W.differs[0]) want32(w.normal_corners, W.corners_out[0], 3ull * W.F);
-      }
-      if (W.set[2].num_segs) {
-        want8(w.texcoord_rows, W.seg[W.set[2].first_seg].dst, 8ull * (W.differs[1] ? W.set[2].count : V));
-        if (W.differs[1]) want32(w.texcoord_corners, W.corners_out[1], 3ull * W.F);
+      if (W.set[1].num_segs) fetch.want_attribute(W.set[1], W.seg[W.set[1].first_seg], W.differs[0] != 0, V, W.F, W.corners_out[0], w.normal_rows, w.normal_corners);
+      if (W.set[2].num_segs) fetch.want_attribute(W.set[2], W.seg[W.set[2].first_seg], W.differs[1] != 0, V, W.F, W.corners_out[1], w.texcoord_rows, w.texcoord_corners);
+    }
+    ENC_STAGE(fetch.run(ctx, lane, arena));
+  }
+  ck.welded.resize(n);
+  ck.weld_corners.assign(n, {});
+  for (uint32_t i = 0; i < n; ++i) enc_weld_view(ck, i);
+  return DSA_OK;
+}
+// ... with every listed attribute a key set of its own (dsa_encode_corner_attributes_batch, weld_attributes = 1;
+// dsa_encode_weld_list.h): the same stage over 3 + L key sets per mesh.  DSA_ENC_HOST_WELD and the under-256-meshes rule as above.
+static dsa_status enc_stage_weld_list(dsa_context *ctx, EncLane &lane, hostutil::TurnGuard &turn, EncChunk &ck) {
+  const uint32_t n = ck.n;
+  ck.weld.assign(n, synth::Welded());
+  ck.weld_attrs.assign(n, {});
+  ck.weld_corners.assign(n, {});
+  std::vector<std::vector<synth::WeldSeg>> keys(n), listed(n);
+  hostutil::parallel_for(n, [&](uint32_t i) { enc_weld_check(ck, i, keys[i], &listed[i]); });
+  const bool on_host = enc_host_choice("DSA_ENC_HOST_WELD", ck.batch_n);
+  std::vector<dsa::EncWeldList> recs;
+  std::vector<uint32_t> mesh_of;
+  std::vector<EncUpload> ups;
+  EncArena A;
+  uint32_t most = 1, sets = 3;
+  for (uint32_t i = 0; i < n && !on_host; ++i) {
+    if (!ck.good(i)) continue;
+    const dsa_mesh_input &m = ck.rq.mesh(ck.base + i);
+    if (!enc_weld_sizes_fit(ck, i, m, keys[i].size(), listed[i].size())) continue;
+    uint32_t row_bytes[dsa::EW_MAX_SEGS], listed_bytes[dsa::EWL_MAX_LISTED];
+    for (size_t g = 0; g < keys[i].size(); ++g) row_bytes[g] = keys[i][g].row_bytes;
+    for (size_t j = 0; j < listed[i].size(); ++j) listed_bytes[j] = listed[i][j].row_bytes;
+    dsa::EncWeldList W = dsa::enc_wlist_inputs([&](uint64_t bytes) { return A.take(bytes); }, m.num_vertices, m.num_faces, row_bytes, (uint32_t)keys[i].size(), m.normals != nullptr,
+                                               m.texcoords != nullptr, listed_bytes, (uint32_t)listed[i].size());
+    enc_weld_uploads(ups, W, m, keys[i]);
+    for (size_t j = 0; j < listed[i].size() && m.num_vertices; ++j) ups.push_back({W.seg[W.set[3 + j].first_seg].src, listed[i][j].rows, (size_t)m.num_vertices * listed[i][j].row_bytes, false});
+    recs.push_back(W); mesh_of.push_back(i);
+    most = std::max(most, std::max(m.num_vertices, 3u * m.num_faces));
+    sets = std::max(sets, W.num_sets);
+  }
+  const uint64_t input_bytes = A.cur;                      // the uploads fill [0, input_bytes); the kernels' regions lie behind
+  for (dsa::EncWeldList &W : recs) dsa::enc_wlist_regions([&](uint64_t bytes) { return A.take(bytes); }, W);
+  if (on_host) {
+    hostutil::parallel_for(n, [&](uint32_t i) {
+      if (!ck.good(i)) return;
+      const dsa_mesh_input &m = ck.rq.mesh(ck.base + i);
+      try { synth::weld_points(m.num_vertices, m.faces, m.num_faces, keys[i], m.normals, m.texcoords, ck.weld[i], listed[i]); }
+      catch (const std::exception &e) { ck.refuse(i, DSA_ERR_INVALID_DATA, e.what()); }
+    });
+  } else if (!recs.empty()) {
+    const uint32_t nr = (uint32_t)recs.size();
+    hipStream_t st = lane.st;
+    uint8_t *arena = nullptr;
+    dsa::EncWeldList *d_recs = nullptr;
+    ENC_STAGE(enc_weld_begin(ctx, lane, turn, A.cur, input_bytes, ups, recs, &arena, &d_recs));
+    const uint32_t gx = std::max(1u, std::min(128u, (most + 1023u) / 1024u));
+    // (grid y: meshes x key sets, in slices of at most 65 535 rows)
+    const uint32_t per = std::max(1u, 65535u / sets);
+    for (uint32_t r0 = 0; r0 < nr; r0 += per) {
+      const uint32_t cnt = std::min(per, nr - r0);
+      hipLaunchKernelGGL(dsa::k_enc_wlist_mark, dim3(gx, cnt), dim3(256), 0, st, arena, d_recs + r0, cnt);
+      hipLaunchKernelGGL(dsa::k_enc_wlist_insert, dim3(gx, sets * cnt), dim3(256), 0, st, arena, d_recs + r0, cnt, sets);
+      hipLaunchKernelGGL(dsa::k_enc_wlist_scan, dim3(sets * cnt), dim3(WAVE), 0, st, arena, d_recs + r0, cnt, sets);
+      hipLaunchKernelGGL(dsa::k_enc_wlist_assign, dim3(gx, sets * cnt), dim3(256), 0, st, arena, d_recs + r0, cnt, sets);
+      hipLaunchKernelGGL(dsa::k_enc_wlist_differs, dim3(gx, sets * cnt), dim3(256), 0, st, arena, d_recs + r0, cnt, sets);
+      hipLaunchKernelGGL(dsa::k_enc_wlist_gather, dim3(gx, sets * cnt), dim3(256), 0, st, arena, d_recs + r0, cnt, sets);
+    }
+    ENC_STAGE(enc_weld_records(ctx, lane, recs, d_recs));
+    EncWeldFetch fetch;
+    for (uint32_t r = 0; r < nr; ++r) {
+      const uint32_t i = mesh_of[r];
+      const dsa::EncWeldList &W = recs[r];
+      bool sane = W.status == dsa::ENC_WELD_OK;
+      for (uint32_t k = 0; k < W.num_sets; ++k) sane = sane && W.set[k].count <= W.P;
+      if (!sane) { ck.refuse(i, DSA_ERR_INVALID_DATA, dsa::enc_weld_message(W.status)); continue; }
+      synth::Welded &w = ck.weld[i];
+      w.P = W.P; w.F = W.F;
+      w.listed.assign(W.num_sets - 3u, synth::Welded::Listed());
+      const uint32_t V = W.set[0].count;
+      fetch.want32(w.faces, W.faces_out, 3ull * W.F);
+      w.vertex_rows.resize(W.set[0].num_segs);
+      for (uint32_t g = 0; g < W.set[0].num_segs; ++g) fetch.want8(w.vertex_rows[g], W.seg[g].dst, (uint64_t)V * W.seg[g].row_bytes);
+      for (uint32_t k = 0; k < W.num_sets; ++k) {
+        const dsa::EncWeldSet &S = W.set[k];
+        if (S.num_segs == 0) continue;
+        fetch.want_keys(k == 0 ? w.vertex : (k == 1 ? w.normal : (k == 2 ? w.texcoord : w.listed[k - 3u].keys)), S, W.P);
+        if (k == 0) continue;
+        const bool seamed = W.differs[k] != 0;
+        (k == 1 ? w.normals_per_vertex : (k == 2 ? w.texcoords_per_vertex : w.listed[k - 3u].per_vertex)) = !seamed;
+        fetch.want_attribute(S, W.seg[S.first_seg], seamed, V, W.F, W.corners_out[k], k == 1 ? w.normal_rows : (k == 2 ? w.texcoord_rows : w.listed[k - 3u].rows),
+                             k == 1 ? w.normal_corners : (k == 2 ? w.texcoord_corners : w.listed[k - 3u].corners));
       }
     }
-    const uint8_t *host = nullptr;
-    ENC_ST(enc_gather(lane, arena, items, nullptr, &host));
-    hostutil::parallel_for((uint32_t)items.size(), [&](uint32_t k) { memcpy(dest[k].p, host + items[k].packed_off, items[k].len); }, 8);
+    ENC_STAGE(fetch.run(ctx, lane, arena));
   }
   ck.welded.resize(n);
   for (uint32_t i = 0; i < n; ++i) enc_weld_view(ck, i);
@@ -908,7 +1027,7 @@ static dsa_status enc_stage_repair(dsa_context *ctx, EncLane &lane, EncChunk &ck
       if (!R.fmap) { R.fmap = A.take(4 * F); ck.rep_ids[i].assign(atts.size(), EncChunk::kNoIds); }
       dsa::EncRepairIds I;
       memset(&I, 0, sizeof(I));
-      I.rep = (uint32_t)recs.size(); I.rows = ck.rows_of(i, atts[k]); I.narrow = ck.ids_narrow(i, atts[k]) ? 1u : 0u; I.att_type = (uint32_t)atts[k].att_type;
+      I.rep = (uint32_t)recs.size(); I.rows = ck.rows_of(i, atts[k]); I.narrow = ck.ids_narrow(i, atts[k]) ? 1u : 0u; I.att_type = atts[k].extra_index >= 0 ? 0x100u + (uint32_t)atts[k].extra_index : (uint32_t)atts[k].att_type;
       I.src = A.take(12 * F); I.dst = A.take((I.narrow ? 6 : 12) * F);
       ck.rep_ids[i][k] = I.dst;
       id_recs.push_back(I); id_src.push_back(atts[k].corner_value);
@@ -946,7 +1065,8 @@ static dsa_status enc_stage_repair(dsa_context *ctx, EncLane &lane, EncChunk &ck
   if (ni) ENC_TRY(hipMemcpyAsync(id_recs.data(), d_ids, sizeof(dsa::EncRepairIds) * ni, hipMemcpyDeviceToHost, st));
   ENC_TRY(hipStreamSynchronize(st));
   for (const dsa::EncRepairIds &I : id_recs)      // (the host's checks saw every id before; the kernel's answer is the same one)
-    if (I.bad && ck.good(mesh_of[I.rep])) ck.refuse(mesh_of[I.rep], DSA_ERR_INVALID_DATA, I.att_type == 1 ? "normal id out of range" : "texture coordinate id out of range");
+    if (I.bad && ck.good(mesh_of[I.rep]))
+      ck.refuse(mesh_of[I.rep], DSA_ERR_INVALID_DATA, I.att_type >= 0x100u ? "attribute " + std::to_string(I.att_type - 0x100u) + " id out of range" : std::string(I.att_type == 1 ? "normal id out of range" : "texture coordinate id out of range"));
   std::vector<synth::CornerTable::Repaired> out(nr);
   for (uint32_t r = 0; r < nr; ++r) {
     const dsa::EncRepair &R = recs[r];
@@ -1306,11 +1426,15 @@ static dsa_status enc_check_base(dsa_context *ctx, const dsa_encode_options &o) 
 }
 // Edgebreaker streams: the widest options, in which every narrower entry point has left what it does not have at its default.
 // (The quantisation bits are checked per chunk: enc_stage_plans.)
-static dsa_status enc_check_options(dsa_context *ctx, const dsa_encode_seam_repair_options &s, bool null_argument) {
+static dsa_status enc_check_options(dsa_context *ctx, const dsa_encode_corner_attributes_options &c, bool null_argument) {
+  const dsa_encode_seam_repair_options &s = c.seam_repair;
   const dsa_encode_grid_options &g = s.grid;
   const dsa_encode_repair_options &r = g.repair;
   const dsa_encode_level_options &d = r.level;
   const dsa_encode_options_ex &ex = d.ex;
+  if (c.weld_attributes != 0 && c.weld_attributes != 1) ENC_REFUSE("weld_attributes %d: 0 (listed attributes in the vertex key) or 1 (listed attributes welded alone)", (int)c.weld_attributes);
+  ENC_RESERVED(c, 7, "dsa_encode_corner_attributes_options");
+  if (c.weld_attributes == 1 && g.weld_points != 1) ENC_REFUSE("weld_attributes 1 needs weld_points 1 (rows per point), weld_points is %d", (int)g.weld_points);
   if (s.corner_repair != 0 && s.corner_repair != 1) ENC_REFUSE("corner_repair %d: 0 (refused as ever) or 1 (coded over the repaired table)", (int)s.corner_repair);
   ENC_RESERVED(s, 7, "dsa_encode_seam_repair_options");
   if (s.corner_repair == 1 && r.topology != 1) ENC_REFUSE("corner_repair 1 needs topology 1 (the reference's corner table), topology is %d", (int)r.topology);
@@ -1455,7 +1579,9 @@ static dsa_status enc_stage_grids(dsa_context *ctx, const EncRequest &rq, std::v
     if (shared(g.slot[1]) && m.texcoords) take(1, 2, (am.mesh.texcoord_corners && !rq.weld && !rq.sequential) ? am.mesh.num_texcoords : m.num_vertices, m.texcoords);
     for (uint32_t k = 0; k < am.num_attributes && k < synth::kMaxAttributes && am.attributes; ++k) {
       const dsa_attribute_input &x = am.attributes[k];
-      if (shared(g.slot[2 + k]) && x.data_type == 9 && x.num_components >= 1 && x.num_components <= 4) take(2 + k, x.num_components, m.num_vertices, x.values);
+      // (an attribute given per corner: over the rows its ids index, like the texture coordinates above)
+      const dsa_attribute_corners *ac = (rq.att_corners && !rq.weld && !rq.sequential && rq.att_corners[i].attributes) ? &rq.att_corners[i].attributes[k] : nullptr;
+      if (shared(g.slot[2 + k]) && x.data_type == 9 && x.num_components >= 1 && x.num_components <= 4) take(2 + k, x.num_components, (ac && ac->corners) ? ac->num_rows : m.num_vertices, x.values);
     }
   }
   if (members.empty()) return DSA_OK;
@@ -1547,15 +1673,16 @@ static dsa_status encode_repair_request(dsa_context *ctx, const EncRequest &requ
   std::vector<uint32_t> again;
   std::vector<dsa_mesh_attr_input> sub;
   std::vector<EncMeshGrids> sub_grids;
+  std::vector<dsa_mesh_attribute_corners> sub_corners;
   for (uint32_t i = 0; i < rq.n; ++i) {
     if (E->status[i] != DSA_ERR_INVALID_DATA) continue;
     const dsa_mesh_input &m = rq.mesh(i);
     if (m.positions && m.num_vertices >= 3 && m.num_faces == 0 && E->messages[i] == "mesh needs positions and faces") { E->messages[i] = "all triangles are degenerate"; continue; }
-    if (enc_topology_refusal(E->messages[i])) { again.push_back(i); sub.push_back(rq.attr(i)); if (rq.grids) sub_grids.push_back(rq.grids[i]); }
+    if (enc_topology_refusal(E->messages[i])) { again.push_back(i); sub.push_back(rq.attr(i)); if (rq.grids) sub_grids.push_back(rq.grids[i]); if (rq.att_corners) sub_corners.push_back(rq.att_corners[i]); }
   }
   if (!again.empty()) {
     EncRequest r2 = rq;
-    r2.repair_scan = false; r2.repair = true; r2.n = (uint32_t)again.size(); r2.meshes = sub.data(); r2.grids = rq.grids ? sub_grids.data() : nullptr;
+    r2.repair_scan = false; r2.repair = true; r2.n = (uint32_t)again.size(); r2.meshes = sub.data(); r2.grids = rq.grids ? sub_grids.data() : nullptr; r2.att_corners = rq.att_corners ? sub_corners.data() : nullptr;
     dsa_encoded *second = nullptr;
     const dsa_status s2 = encode_request(ctx, r2, &second, rq.n);
     if (s2 != DSA_OK) return s2;
@@ -1588,13 +1715,15 @@ static dsa_status encode_checked(dsa_context *ctx, EncRequest &rq, const dsa_mes
   }
   return repair ? encode_repair_request(ctx, rq, out) : encode_request(ctx, rq, out);
 }
-static dsa_status encode_edgebreaker(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_seam_repair_options &o,
-                                     dsa_encoded **out, bool drop_generic_outside_1_4 = false) {
-  if (enc_check_options(ctx, o, !ctx || !out || (n && !meshes)) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+static dsa_status encode_edgebreaker(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_corner_attributes_options &c,
+                                     dsa_encoded **out, bool drop_generic_outside_1_4 = false, const dsa_mesh_attribute_corners *corners = nullptr) {
+  if (enc_check_options(ctx, c, !ctx || !out || (n && !meshes)) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+  const dsa_encode_seam_repair_options &o = c.seam_repair;
   EncRequest rq;
   rq.n = n; rq.meshes = meshes; rq.drop_generic_outside_1_4 = drop_generic_outside_1_4;
   rq.level = o.grid.repair.level;
   rq.weld = o.grid.weld_points == 1; rq.corner_repair = o.corner_repair == 1;
+  rq.att_corners = n ? corners : nullptr; rq.weld_attributes = c.weld_attributes == 1;
   return encode_checked(ctx, rq, grids, o.grid.repair.topology == 1, out);
 }
 static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_sequential_options *options, dsa_encoded **out) {
@@ -1607,11 +1736,11 @@ static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh
 }
 // the array of a narrower entry point widened, owned by the call
 template <class Mesh>
-static dsa_status encode_edgebreaker_narrow(dsa_context *ctx, uint32_t n, const Mesh *meshes, const dsa_encode_seam_repair_options &o, dsa_encoded **out, bool drop_generic_outside_1_4 = false) {
+static dsa_status encode_edgebreaker_narrow(dsa_context *ctx, uint32_t n, const Mesh *meshes, const dsa_encode_corner_attributes_options &o, dsa_encoded **out, bool drop_generic_outside_1_4 = false) {
   const std::vector<dsa_mesh_attr_input> wide = enc_widen(meshes, n);
   return encode_edgebreaker(ctx, n, wide.empty() ? nullptr : wide.data(), nullptr, o, out, drop_generic_outside_1_4);
 }
-static dsa_encode_seam_repair_options enc_default_options() { dsa_encode_seam_repair_options o; dsa_encode_default_seam_repair_options(&o); return o; }
+static dsa_encode_corner_attributes_options enc_default_options() { dsa_encode_corner_attributes_options o; dsa_encode_default_corner_attributes_options(&o); return o; }
 
 extern "C" {
 
@@ -1654,60 +1783,73 @@ void dsa_encode_default_seam_repair_options(dsa_encode_seam_repair_options *o) {
   memset(o, 0, sizeof(*o));
   dsa_encode_default_grid_options(&o->grid);
 }
+void dsa_encode_default_corner_attributes_options(dsa_encode_corner_attributes_options *o) {
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  dsa_encode_default_seam_repair_options(&o->seam_repair);
+}
 
 dsa_status dsa_encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_encode_options *options, dsa_encoded **out) {
-  dsa_encode_seam_repair_options o = enc_default_options();
-  if (options) o.grid.repair.level.ex.base = *options;
+  dsa_encode_corner_attributes_options o = enc_default_options();
+  if (options) o.seam_repair.grid.repair.level.ex.base = *options;
   DSA_GUARD(ctx, encode_edgebreaker_narrow(ctx, n, meshes, o, out, true));      // (EncRequest::drop_generic_outside_1_4: this entry alone)
 }
 dsa_status dsa_encode_batch_corners(dsa_context *ctx, uint32_t n, const dsa_mesh_corner_input *meshes, const dsa_encode_options *options, dsa_encoded **out) {
-  dsa_encode_seam_repair_options o = enc_default_options();
-  if (options) o.grid.repair.level.ex.base = *options;
+  dsa_encode_corner_attributes_options o = enc_default_options();
+  if (options) o.seam_repair.grid.repair.level.ex.base = *options;
   DSA_GUARD(ctx, encode_edgebreaker_narrow(ctx, n, meshes, o, out));
 }
 dsa_status dsa_encode_batch_ex(dsa_context *ctx, uint32_t n, const dsa_mesh_corner_input *meshes, const dsa_encode_options_ex *options, dsa_encoded **out) {
-  dsa_encode_seam_repair_options o = enc_default_options();
-  if (options) o.grid.repair.level.ex = *options;
+  dsa_encode_corner_attributes_options o = enc_default_options();
+  if (options) o.seam_repair.grid.repair.level.ex = *options;
   DSA_GUARD(ctx, encode_edgebreaker_narrow(ctx, n, meshes, o, out));
 }
 dsa_status dsa_encode_attributes_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_encode_options_ex *options, dsa_encoded **out) {
-  dsa_encode_seam_repair_options o = enc_default_options();
-  if (options) o.grid.repair.level.ex = *options;
+  dsa_encode_corner_attributes_options o = enc_default_options();
+  if (options) o.seam_repair.grid.repair.level.ex = *options;
   DSA_GUARD(ctx, encode_edgebreaker(ctx, n, meshes, nullptr, o, out));
 }
 // The levels above the default: MultiParallelogram / ConstrainedMultiParallelogram in place of Parallelogram, prediction-degree
 // attribute order (dsa_encode_multi.h).
 dsa_status dsa_encode_level_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_encode_level_options *options, dsa_encoded **out) {
-  dsa_encode_seam_repair_options o = enc_default_options();
-  if (options) o.grid.repair.level = *options;
+  dsa_encode_corner_attributes_options o = enc_default_options();
+  if (options) o.seam_repair.grid.repair.level = *options;
   DSA_GUARD(ctx, encode_edgebreaker(ctx, n, meshes, nullptr, o, out));
 }
 // ... that also takes meshes with degenerate faces, non-manifold edges and vertices and isolated vertices (topology = 1: the
 // reference's corner table, dsa_encode_repair.h).
 dsa_status dsa_encode_repair_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_encode_repair_options *options, dsa_encoded **out) {
-  dsa_encode_seam_repair_options o = enc_default_options();
-  if (options) o.grid.repair = *options;
+  dsa_encode_corner_attributes_options o = enc_default_options();
+  if (options) o.seam_repair.grid.repair = *options;
   DSA_GUARD(ctx, encode_edgebreaker(ctx, n, meshes, nullptr, o, out));
 }
 // dsa_encode_repair_batch for meshes given as one row per point: every chunk welds its meshes first (enc_stage_weld), the welded
 // meshes are coded as that call codes them.  With topology = 1 the meshes refused for their topology are welded again in the
 // second pass: they are the few, and the weld is cheap beside keeping every chunk's buffers alive.
 dsa_status dsa_encode_points_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_encode_repair_options *options, dsa_encoded **out) {
-  dsa_encode_seam_repair_options o = enc_default_options();
-  if (options) o.grid.repair = *options;
-  o.grid.weld_points = 1;
+  dsa_encode_corner_attributes_options o = enc_default_options();
+  if (options) o.seam_repair.grid.repair = *options;
+  o.seam_repair.grid.weld_points = 1;
   DSA_GUARD(ctx, encode_edgebreaker(ctx, n, meshes, nullptr, o, out));
 }
 // ... with a quantisation grid per float attribute, given by the caller or shared within a group (dsa_encode_grid.h).
 dsa_status dsa_encode_grid_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_grid_options *options, dsa_encoded **out) {
-  dsa_encode_seam_repair_options o = enc_default_options();
-  if (options) o.grid = *options;
+  dsa_encode_corner_attributes_options o = enc_default_options();
+  if (options) o.seam_repair.grid = *options;
   DSA_GUARD(ctx, encode_edgebreaker(ctx, n, meshes, grids, o, out));
 }
 // ... with attributes given per corner coded over a repaired table (EncRequest::corner_repair; the second pass of
 // encode_repair_request, dsa_encode_repair.h: k_enc_repair_face_scan, k_enc_repair_ids).
 dsa_status dsa_encode_seam_repair_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_seam_repair_options *options, dsa_encoded **out) {
-  DSA_GUARD(ctx, encode_edgebreaker(ctx, n, meshes, grids, options ? *options : enc_default_options(), out));
+  dsa_encode_corner_attributes_options o = enc_default_options();
+  if (options) o.seam_repair = *options;
+  DSA_GUARD(ctx, encode_edgebreaker(ctx, n, meshes, grids, o, out));
+}
+// ... with row ids per corner for the attributes of the list, given by the caller (EncRequest::att_corners) or found by the weld
+// with every listed attribute a key set of its own (EncRequest::weld_attributes; dsa_encode_weld_list.h).
+dsa_status dsa_encode_corner_attributes_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids,
+                                              const dsa_mesh_attribute_corners *corners, const dsa_encode_corner_attributes_options *options, dsa_encoded **out) {
+  DSA_GUARD(ctx, encode_edgebreaker(ctx, n, meshes, grids, options ? *options : enc_default_options(), out, false, corners));
 }
 dsa_status dsa_encode_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_encode_sequential_options *options, dsa_encoded **out) {
   DSA_GUARD(ctx, [&] { const std::vector<dsa_mesh_attr_input> wide = enc_widen(meshes, n); return encode_sequential(ctx, n, wide.empty() ? nullptr : wide.data(), nullptr, options, out); }());

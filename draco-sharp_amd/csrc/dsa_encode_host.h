@@ -1012,6 +1012,7 @@ struct PortableAttr {
   const void *extra_values = nullptr;  // an attribute of MeshIn::extras: its rows, nc elements of data_type each (else the built-in source)
   const Grid *grid = nullptr;          // seq_type 2: the caller's grid (mode 1; null or mode 0: the attribute's own bounds)
   int extra_index = -1;                // its index in MeshIn::extras (the messages name it)
+  uint32_t extra_rows = 0;             // an attribute of MeshIn::extras given per corner: the rows of extra_values (corner_value indexes them)
 };
 
 // AttributeQuantizationTransform.cs:66-108,136-177 + Core/Quantizer.cs (E-1 corrected)
@@ -1119,8 +1120,12 @@ static int32_t generic_value(const void *g, size_t k, int dt) {
   }
 }
 
-// One more per-vertex attribute behind the built-in ones (positions, normals, texture coordinates, the generic attribute):
+// One more attribute behind the built-in ones (positions, normals, texture coordinates, the generic attribute):
 // colours, joints and weights, a second UV set, feature ids.  Integer element types are coded as they are, float32 quantised.
+// Per vertex, or -- like normals and texture coordinates -- per corner: `corners` holds a row id per corner of the faces into
+// `values` (`rows` of them), and an interior edge across which the ids differ is a seam of this attribute alone (lightmap charts,
+// a colour with a hard edge).  This library's decoder takes corner attributes for attribute data 0 to 6, so ids are for the
+// attributes at indices 1 to 7 of the stream (extras_error).
 struct ExtraAttr {
   int32_t att_type = 4;              // 2 colour, 3 texture coordinate, 4 generic
   int32_t data_type = 2;             // Draco's ids: 1 int8 ... 6 uint32, 9 float32
@@ -1130,8 +1135,11 @@ struct ExtraAttr {
   int32_t bits = 0;                  // float32: 1..20; 0: uv_bits for a texture coordinate, else 8
   const void *values = nullptr;      // nv rows, packed
   const Grid *grid = nullptr;        // float32: the caller's quantisation grid (null: its own bounds)
+  const uint32_t *corners = nullptr; // 3 * nf row ids into `values`, or null: one row per vertex
+  uint32_t rows = 0;                 // rows of `values` when `corners` is set
 };
 static const size_t kMaxAttributes = 16;   // DSA_MAX_ATTRIBUTES: what the decode direction takes
+static const size_t kMaxCornerAttributeIndex = 7;      // the last index of the stream whose attribute may have a connectivity of its own (attribute data 0 to 6)
 static inline size_t data_type_size(int dt) { return (dt == 1 || dt == 2) ? 1 : ((dt == 3 || dt == 4) ? 2 : 4); }
 
 struct MeshIn {
@@ -1173,6 +1181,24 @@ static std::string extras_error(const MeshIn &in) {
       const uint32_t other = j < builtins ? j : (in.extras[j - builtins].unique_id == kInvalid ? j : in.extras[j - builtins].unique_id);
       if (other == uid) { snprintf(buf, sizeof(buf), "attribute %u: unique_id %u is the id of attribute %u of the stream", k, uid, j); return buf; }
     }
+    if (x.corners && builtins + k > kMaxCornerAttributeIndex) {
+      snprintf(buf, sizeof(buf), "attribute %u: corner ids on attribute %zu of the stream: corner attributes are decoded for attributes 1 to %zu", k, builtins + k, kMaxCornerAttributeIndex);
+      return buf;
+    }
+  }
+  return "";
+}
+static inline bool extras_have_corners(const MeshIn &in) {
+  for (uint32_t k = 0; k < in.num_extras && in.extras; ++k) if (in.extras[k].corners) return true;
+  return false;
+}
+// An id of a listed attribute at or above its row count refuses the mesh ("" when every id names a row).
+static std::string extras_id_error(const MeshIn &in) {
+  for (uint32_t k = 0; k < in.num_extras && in.extras; ++k) {
+    const ExtraAttr &x = in.extras[k];
+    if (!x.corners) continue;
+    for (size_t c = 0; c < (size_t)in.nf * 3; ++c)
+      if (x.corners[c] >= x.rows) return "attribute " + std::to_string(k) + " id out of range";
   }
   return "";
 }
@@ -1501,6 +1527,7 @@ static void plan_extra_attributes(const MeshIn &in, const Options &opt, int pred
     PortableAttr a;
     a.att_type = x.att_type; a.nc = a.nc_out = (int)x.nc; a.data_type = x.data_type; a.prediction = prediction;
     a.unique_id = x.unique_id; a.extra_values = x.values; a.extra_index = (int)k;
+    a.corner_value = x.corners; a.extra_rows = x.corners ? x.rows : 0;
     if (x.grid) { const std::string why = grid_error(*x.grid, (int)x.nc, x.data_type == 9, grid_slot_name(x.att_type, (int)k)); check(why.empty(), why.c_str()); a.grid = x.grid; }
     if (x.data_type == 9) { a.seq_type = 2; a.bits = x.bits ? x.bits : (x.att_type == 3 ? opt.uv_bits : 8); }
     else { a.seq_type = 1; a.normalized = x.normalized; }
@@ -1582,7 +1609,7 @@ static void plan_mesh(const MeshIn &in, const Options &opt, MeshPlan &pl) {
   if (opt.repair_topology) {
     pl.ct.build_repaired(in.faces, in.nf, in.nv);
     // (seam tables over a repaired table are not written yet: a mesh that needed no repair goes on as it always did)
-    check(!(in.normal_corners || in.uv_corners) || !pl.ct.needed_repair || opt.repair_topology == 2, "attributes given per corner over a mesh whose topology needs repair are not implemented");
+    check(!(in.normal_corners || in.uv_corners || extras_have_corners(in)) || !pl.ct.needed_repair || opt.repair_topology == 2, "attributes given per corner over a mesh whose topology needs repair are not implemented");
     if (!pl.ct.needed_repair) pl.ct.row.clear();
     else { pl.coded_vertices = pl.ct.nv(); pl.coded_faces = pl.ct.nf(); }
   } else {
@@ -1727,7 +1754,7 @@ static void encode_mesh(const MeshIn &in, const Options &opt, std::vector<uint8_
   MeshPlan pl;
   plan_mesh(in, opt, pl);
   for (auto &a : pl.atts) {
-    if (a.extra_values) fill_extra_values(a, in.nv, a);
+    if (a.extra_values) fill_extra_values(a, a.corner_value ? a.extra_rows : in.nv, a);
     else if (a.att_type == 0) quantize(in.pos, in.nv, 3, opt.pos_bits, a);
     else if (a.att_type == 1) {
       const uint32_t n = in.normal_corners ? in.nn : in.nv;
@@ -1758,7 +1785,11 @@ static void encode_mesh(const MeshIn &in, const Options &opt, std::vector<uint8_
 //   - the representative of a class is its point of smallest index, classes are numbered by ascending representative;
 //   - normals (12-byte rows) and texture coordinates (8-byte rows) likewise, each alone;
 //   - an attribute whose row id is the same for all points of every vertex is handed on per vertex: the row of each vertex's
-//     representative, no ids (what lets a table that needs repair keep its normals: seams over a repaired table are not written).
+//     representative, no ids (what lets a table that needs repair keep its normals: seams over a repaired table are not written);
+//   - weld_attributes: every listed attribute that may have a connectivity of its own in the stream (its index there is at most
+//     kMaxCornerAttributeIndex: weld_listed_alone) leaves the vertex key and is a key set of its own, welded like normals and texture
+//     coordinates (`listed`, in list order).  The vertex key is then positions + the generic attribute + the listed attributes
+//     behind that index.  A lightmap UV set or a colour with a hard edge then cuts its own connectivity only.
 struct WeldSeg { const void *rows; uint32_t row_bytes; };
 struct WeldKeys {                      // one key set: the classes of the used points under its segments
   uint32_t count = 0;
@@ -1771,6 +1802,9 @@ struct Welded {
   std::vector<uint32_t> faces, normal_corners, texcoord_corners;      // 3F each; the id lists empty when per vertex
   std::vector<std::vector<uint8_t>> vertex_rows;                       // per segment of the vertex key: V rows
   std::vector<uint8_t> normal_rows, texcoord_rows;                     // V rows when per vertex, else N / T rows
+  // weld_attributes: per listed attribute welded alone, in list order
+  struct Listed { WeldKeys keys; bool per_vertex = true; std::vector<uint32_t> corners; std::vector<uint8_t> rows; };
+  std::vector<Listed> listed;
 };
 static inline uint32_t weld_hash(const std::vector<WeldSeg> &segs, uint32_t p) {
   uint32_t h = 0x9E3779B9u;
@@ -1805,9 +1839,11 @@ static void weld_gather(const WeldSeg &s, const std::vector<uint32_t> &points, s
   rows.resize((size_t)points.size() * s.row_bytes);
   for (size_t v = 0; v < points.size(); ++v) memcpy(rows.data() + v * s.row_bytes, (const uint8_t *)s.rows + (size_t)points[v] * s.row_bytes, s.row_bytes);
 }
-static void weld_points(uint32_t P, const uint32_t *faces, uint32_t F, const std::vector<WeldSeg> &vertex_key, const float *normals, const float *uvs, Welded &out) {
+static void weld_points(uint32_t P, const uint32_t *faces, uint32_t F, const std::vector<WeldSeg> &vertex_key, const float *normals, const float *uvs, Welded &out,
+                        const std::vector<WeldSeg> &listed = std::vector<WeldSeg>()) {
   check(F == 0 || faces != nullptr, "mesh needs positions and faces");
   for (const WeldSeg &s : vertex_key) check(P == 0 || s.rows != nullptr, "mesh needs positions and faces");
+  for (const WeldSeg &s : listed) check(P == 0 || s.rows != nullptr, "mesh needs positions and faces");
   for (size_t k = 0; k < (size_t)F * 3; ++k) check(faces[k] < P, "face index out of range");      // (before anything indexes through the faces)
   out.P = P; out.F = F;
   std::vector<uint8_t> used(P, 0);
@@ -1817,7 +1853,7 @@ static void weld_points(uint32_t P, const uint32_t *faces, uint32_t F, const std
   for (size_t k = 0; k < (size_t)F * 3; ++k) out.faces[k] = out.vertex.of_point[faces[k]];
   out.vertex_rows.resize(vertex_key.size());
   for (size_t g = 0; g < vertex_key.size(); ++g) weld_gather(vertex_key[g], out.vertex.point, out.vertex_rows[g]);
-  auto attribute = [&](const float *values, uint32_t row_bytes, WeldKeys &keys, bool &per_vertex, std::vector<uint32_t> &corners, std::vector<uint8_t> &rows) {
+  auto attribute = [&](const void *values, uint32_t row_bytes, WeldKeys &keys, bool &per_vertex, std::vector<uint32_t> &corners, std::vector<uint8_t> &rows) {
     keys = WeldKeys(); per_vertex = true; corners.clear(); rows.clear();
     if (!values) return;
     const WeldSeg seg{values, row_bytes};
@@ -1831,14 +1867,25 @@ static void weld_points(uint32_t P, const uint32_t *faces, uint32_t F, const std
   };
   attribute(normals, 12, out.normal, out.normals_per_vertex, out.normal_corners, out.normal_rows);
   attribute(uvs, 8, out.texcoord, out.texcoords_per_vertex, out.texcoord_corners, out.texcoord_rows);
+  out.listed.assign(listed.size(), Welded::Listed());
+  for (size_t j = 0; j < listed.size(); ++j) attribute(listed[j].rows, listed[j].row_bytes, out.listed[j].keys, out.listed[j].per_vertex, out.listed[j].corners, out.listed[j].rows);
 }
 // The welded mesh as the coder takes it: `in` is the per-point input (its corner ids unset, nv read as P), `key` the segments of
 // its vertex key in the order positions, generic, extras (weld_vertex_key); `ex` receives the extras pointed at their welded rows.
-static std::vector<WeldSeg> weld_vertex_key(const MeshIn &in, size_t generic_row_bytes) {
+// weld_attributes: is attribute k of the list welded alone (its index in the stream is one a corner attribute may have)
+static inline bool weld_listed_alone(const MeshIn &in, uint32_t k) {
+  return 1 + (in.normals ? 1 : 0) + (in.uvs ? 1 : 0) + (in.generic ? 1 : 0) + (size_t)k <= kMaxCornerAttributeIndex;
+}
+static std::vector<WeldSeg> weld_vertex_key(const MeshIn &in, size_t generic_row_bytes, bool weld_attributes = false, std::vector<WeldSeg> *listed = nullptr) {
   std::vector<WeldSeg> key;
   key.push_back({in.pos, 12u});
   if (in.generic) key.push_back({in.generic, (uint32_t)generic_row_bytes});
-  for (uint32_t k = 0; k < in.num_extras; ++k) key.push_back({in.extras[k].values, (uint32_t)(data_type_size(in.extras[k].data_type) * in.extras[k].nc)});
+  if (listed) listed->clear();
+  for (uint32_t k = 0; k < in.num_extras; ++k) {
+    const WeldSeg seg{in.extras[k].values, (uint32_t)(data_type_size(in.extras[k].data_type) * in.extras[k].nc)};
+    if (weld_attributes && listed && weld_listed_alone(in, k)) listed->push_back(seg);
+    else key.push_back(seg);
+  }
   return key;
 }
 static MeshIn welded_mesh_in(const MeshIn &in, const Welded &w, std::vector<ExtraAttr> &ex) {
@@ -1848,7 +1895,13 @@ static MeshIn welded_mesh_in(const MeshIn &in, const Welded &w, std::vector<Extr
   m.faces = w.faces.data(); m.nf = w.F;
   if (in.generic) m.generic = w.vertex_rows[g++].data();
   ex.assign(in.extras, in.extras + in.num_extras);
-  for (uint32_t k = 0; k < in.num_extras; ++k) ex[k].values = w.vertex_rows[g++].data();
+  // (the listed attributes welded alone are the first w.listed.size() of the list: weld_listed_alone is monotone in k)
+  for (uint32_t k = 0; k < in.num_extras; ++k) {
+    if (k >= w.listed.size()) { ex[k].values = w.vertex_rows[g++].data(); continue; }
+    const Welded::Listed &l = w.listed[k];
+    ex[k].values = l.rows.data();
+    ex[k].corners = l.per_vertex ? nullptr : l.corners.data(); ex[k].rows = l.per_vertex ? 0 : l.keys.count;
+  }
   m.extras = ex.data();
   m.normals = in.normals ? (const float *)w.normal_rows.data() : nullptr;
   m.normal_corners = w.normals_per_vertex ? nullptr : w.normal_corners.data(); m.nn = w.normals_per_vertex ? 0 : w.normal.count;
@@ -1915,6 +1968,7 @@ static void write_sequential_stream(ByteWriter &w, bool mesh, uint32_t nv, uint3
 // The CPU coder of both kinds: `mesh` false writes a point cloud of in.nv points (in.faces is not read).
 static void encode_sequential(const MeshIn &in, const Options &opt, bool mesh, bool compressed, std::vector<uint8_t> &out) {
   std::vector<PortableAttr> atts;
+  check(!extras_have_corners(in), "a sequential stream has one value per point");
   plan_sequential_attributes(in, opt, atts);
   for (auto &a : atts) {
     if (a.extra_values) fill_extra_values(a, in.nv, a);

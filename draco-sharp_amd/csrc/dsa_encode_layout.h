@@ -24,6 +24,7 @@
 #include "dsa_encode_conn.h"
 #include "dsa_encode_repair.h"
 #include "dsa_encode_weld.h"
+#include "dsa_encode_weld_list.h"
 #include "dsa_encode_grid.h"
 #include "dsa_encode_seams.h"
 #include "dsa_encode_seqidx.h"
@@ -146,6 +147,8 @@ struct EncRequest {
   bool weld = false;                       // dsa_encode_points_batch / dsa_weld_batch: `meshes` holds one row per point, every chunk welds its meshes first (enc_stage_weld)
   std::vector<synth::Welded> *weld_sink = nullptr;      // dsa_weld_batch: receives the weld of every mesh, nothing is coded
   const EncMeshGrids *grids = nullptr;     // dsa_encode_grid_batch / _sequential_batch: parallel to `meshes` (null: every attribute on its own bounds)
+  const dsa_mesh_attribute_corners *att_corners = nullptr;      // dsa_encode_corner_attributes_batch: parallel to `meshes` (null: the listed attributes are per vertex)
+  bool weld_attributes = false;            // ... weld_attributes = 1: the listed attributes are key sets of their own in the weld (dsa_encode_weld_list.h)
   dsa_encode_level_options level{};        // Edgebreaker streams
   dsa_encode_sequential_options seq{};     // sequential streams
   const dsa_encode_options &base() const { return sequential ? seq.base : level.ex.base; }
@@ -233,6 +236,7 @@ struct EncChunk {
   // every stage behind enc_stage_weld reads (mesh(i) / corner(i) / attr(i) point here instead of at the caller's arrays)
   std::vector<synth::Welded> weld;
   std::vector<std::vector<dsa_attribute_input>> weld_attrs;
+  std::vector<std::vector<dsa_attribute_corners>> weld_corners;      // weld_attributes: the ids of the listed attributes welded alone (empty: none has two rows at a vertex)
   std::vector<dsa_mesh_attr_input> welded;
   EncLayout L;
   std::vector<std::pair<uint64_t, uint64_t>> *region_log = nullptr;
@@ -252,6 +256,11 @@ struct EncChunk {
   const dsa_mesh_attr_input &attr(uint32_t i) const { return welded.empty() ? rq.attr(base + i) : welded[i]; }
   const dsa_mesh_corner_input &corner(uint32_t i) const { return attr(i).mesh; }
   const dsa_mesh_input &mesh(uint32_t i) const { return attr(i).mesh.mesh; }
+  // the row ids of the listed attributes of mesh i (null: all per vertex): the caller's, or after a weld the weld's
+  const dsa_attribute_corners *att_corners(uint32_t i) const {
+    if (!welded.empty()) return i < weld_corners.size() && !weld_corners[i].empty() ? weld_corners[i].data() : nullptr;
+    return rq.att_corners ? rq.att_corners[base + i].attributes : nullptr;
+  }
   // vertices and faces of mesh i as the connectivity kernels and the streams see them
   uint32_t coded_vertices(uint32_t i) const { return !rep.empty() ? rep[i].nv() : (plans[i].coded_vertices >= 0 ? (uint32_t)plans[i].coded_vertices : mesh(i).num_vertices); }
   uint32_t coded_faces(uint32_t i) const { return !rep.empty() ? rep[i].nf() : (plans[i].coded_faces >= 0 ? (uint32_t)plans[i].coded_faces : mesh(i).num_faces); }
@@ -262,7 +271,10 @@ struct EncChunk {
   // MultiParallelogram per mesh: the method asked for, or by the reference's rule (speed < 2 and at least 40 points)
   int32_t multi_of(uint32_t i) const { const int32_t m = rq.level.multi_parallelogram; return m == -1 ? ((opt.compression_level >= 9 && mesh(i).num_vertices >= 40) ? 4 : 0) : m; }
   // value rows of an attribute of mesh i: its ids' row count when it is given per corner
-  uint32_t rows_of(uint32_t i, const synth::PortableAttr &a) const { return !a.corner_value ? mesh(i).num_vertices : (a.att_type == 1 ? corner(i).num_normals : corner(i).num_texcoords); }
+  uint32_t rows_of(uint32_t i, const synth::PortableAttr &a) const {
+    if (!a.corner_value) return mesh(i).num_vertices;
+    return a.extra_values ? a.extra_rows : (a.att_type == 1 ? corner(i).num_normals : corner(i).num_texcoords);
+  }
   bool ids_narrow(uint32_t i, const synth::PortableAttr &a) const { return rows_of(i, a) <= 65536; }
   // the decoder of attribute k takes the prediction-degree order (MeshPlan::uses_pd; for an attribute given per corner on the
   // device path: unless it turns out seamed -- k_enc_pd_corner_streams, k_enc_seam_topo)
@@ -272,7 +284,7 @@ struct EncChunk {
 
 // The attribute list of a mesh as the host coder takes it (`ex` keeps them alive beside `in`); what the C structs
 // alone can say against them -- a reserved word -- is answered here, the rest by synth::extras_error.  "" when they can be written.
-static std::string enc_take_extras(const dsa_mesh_attr_input &am, std::vector<synth::ExtraAttr> &ex, synth::MeshIn &in) {
+static std::string enc_take_extras(const dsa_mesh_attr_input &am, std::vector<synth::ExtraAttr> &ex, synth::MeshIn &in, const dsa_attribute_corners *corners = nullptr) {
   char buf[96];
   if (am.reserved != 0) return "dsa_mesh_attr_input.reserved is not zero";
   if (am.num_attributes && !am.attributes) return "attributes: the list is missing";
@@ -283,6 +295,9 @@ static std::string enc_take_extras(const dsa_mesh_attr_input &am, std::vector<sy
       if (x.reserved[r] != 0) { snprintf(buf, sizeof(buf), "attribute %u: reserved[%d] is not zero", k, r); return buf; }
     ex[k].att_type = x.attribute_type; ex[k].data_type = x.data_type; ex[k].nc = x.num_components; ex[k].normalized = x.normalized;
     ex[k].unique_id = x.unique_id; ex[k].bits = x.quantization_bits; ex[k].values = x.values;
+    if (!corners) continue;
+    if (corners[k].reserved != 0) { snprintf(buf, sizeof(buf), "attribute %u: dsa_attribute_corners.reserved is not zero", k); return buf; }
+    if (corners[k].corners) { ex[k].corners = corners[k].corners; ex[k].rows = corners[k].num_rows; }
   }
   in.extras = ex.data(); in.num_extras = am.num_attributes;
   return synth::extras_error(in);
@@ -318,15 +333,21 @@ static void enc_extra_caps(EncChunk &ck, uint32_t i) {
   const std::vector<synth::PortableAttr> &atts = ck.plans[i].atts;
   ck.extra_cap[i].assign(atts.size(), 0);
   for (size_t k = 0; k < atts.size(); ++k)
-    if (atts[k].extra_values && atts[k].seq_type == 1) ck.extra_cap[i][k] = enc_extra_hist_cap(atts[k], ck.mesh(i).num_vertices);
+    if (atts[k].extra_values && atts[k].seq_type == 1) ck.extra_cap[i][k] = enc_extra_hist_cap(atts[k], ck.rows_of(i, atts[k]));
 }
 
 // ---- a weld request, mesh i: what the weld itself indexes by is checked here, before anything reads through the faces (the
 // rest of the mesh is the coder's to judge, on the welded form).  The segments of the vertex key into `key`; false: refused.
-static bool enc_weld_check(EncChunk &ck, uint32_t i, std::vector<synth::WeldSeg> &key) {
+static bool enc_weld_check(EncChunk &ck, uint32_t i, std::vector<synth::WeldSeg> &key, std::vector<synth::WeldSeg> *listed = nullptr) {
   const dsa_mesh_attr_input &am = ck.rq.attr(ck.base + i);
   const dsa_mesh_input &m = am.mesh.mesh;
   if (am.mesh.normal_corners || am.mesh.texcoord_corners) { ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, "per-point input takes no corner ids (normal_corners / texcoord_corners must be NULL)"); return false; }
+  if (ck.rq.att_corners) {
+    const dsa_mesh_attribute_corners &mc = ck.rq.att_corners[ck.base + i];
+    if (mc.reserved[0] != 0 || mc.reserved[1] != 0) { ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, "dsa_mesh_attribute_corners.reserved is not zero"); return false; }
+    for (uint32_t k = 0; mc.attributes && k < am.num_attributes; ++k)
+      if (mc.attributes[k].corners) { ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, "per-point input takes no corner ids (the corners of attribute " + std::to_string(k) + " must be NULL)"); return false; }
+  }
   if (m.generic && (m.generic_components < 1 || m.generic_components > 4)) { ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, "generic attribute needs 1 - 4 components"); return false; }
   synth::MeshIn in{m.positions, m.num_vertices, m.faces, m.num_faces, m.normals, m.texcoords, m.generic};
   std::vector<synth::ExtraAttr> ex;
@@ -335,7 +356,7 @@ static bool enc_weld_check(EncChunk &ck, uint32_t i, std::vector<synth::WeldSeg>
   if ((m.num_vertices && !m.positions) || (m.num_faces && !m.faces)) { ck.refuse(i, DSA_ERR_INVALID_DATA, "mesh needs positions and faces"); return false; }
   for (size_t k = 0, nk = (size_t)m.num_faces * 3; k < nk; ++k)
     if (m.faces[k] >= m.num_vertices) { ck.refuse(i, DSA_ERR_INVALID_DATA, "face index out of range"); return false; }
-  key = synth::weld_vertex_key(in, m.generic ? m.generic_components : 0);
+  key = synth::weld_vertex_key(in, m.generic ? m.generic_components : 0, ck.rq.weld_attributes, listed);
   return true;
 }
 // the welded mesh i in the C structs, pointed at ck.weld[i] (a refused mesh: an empty one, which nothing reads)
@@ -352,7 +373,16 @@ static void enc_weld_view(EncChunk &ck, uint32_t i) {
   m.faces = w.faces.data();
   if (am.mesh.mesh.generic) { m.generic = w.vertex_rows[g++].data(); m.generic_components = am.mesh.mesh.generic_components; }
   ck.weld_attrs[i].assign(am.attributes, am.attributes + am.num_attributes);
-  for (uint32_t k = 0; k < am.num_attributes; ++k) ck.weld_attrs[i][k].values = w.vertex_rows[g++].data();
+  // (the listed attributes welded alone are the first w.listed.size() of the list; the rest stayed in the vertex key)
+  bool any_ids = false;
+  for (const synth::Welded::Listed &l : w.listed) any_ids = any_ids || !l.per_vertex;
+  if (any_ids) { dsa_attribute_corners none; memset(&none, 0, sizeof(none)); ck.weld_corners[i].assign(am.num_attributes, none); }
+  for (uint32_t k = 0; k < am.num_attributes; ++k) {
+    if (k >= w.listed.size()) { ck.weld_attrs[i][k].values = w.vertex_rows[g++].data(); continue; }
+    const synth::Welded::Listed &l = w.listed[k];
+    ck.weld_attrs[i][k].values = l.rows.data();
+    if (!l.per_vertex) { ck.weld_corners[i][k].corners = l.corners.data(); ck.weld_corners[i][k].num_rows = l.keys.count; }
+  }
   out.attributes = ck.weld_attrs[i].data(); out.num_attributes = am.num_attributes;
   if (am.mesh.mesh.normals) {
     m.normals = (const float *)w.normal_rows.data();
@@ -380,17 +410,21 @@ static void enc_plan_mesh(EncChunk &ck, uint32_t i) {
   if ((cm.normal_corners && !m.normals) || (cm.texcoord_corners && !m.texcoords)) return ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, "corner ids without their values");
   in.normal_corners = cm.normal_corners; in.nn = cm.num_normals;
   in.uv_corners = cm.texcoord_corners; in.nu = cm.num_texcoords;
-  std::string why = enc_take_extras(ck.attr(i), ck.extras[i], in);
+  std::string why;
+  if (ck.welded.empty() && ck.rq.att_corners && (ck.rq.att_corners[ck.base + i].reserved[0] != 0 || ck.rq.att_corners[ck.base + i].reserved[1] != 0)) why = "dsa_mesh_attribute_corners.reserved is not zero";
+  if (why.empty()) why = enc_take_extras(ck.attr(i), ck.extras[i], in, ck.att_corners(i));
   if (why.empty()) why = enc_take_mesh_grids(ck.rq.grids ? &ck.rq.grids[ck.base + i] : nullptr, ck.extras[i], in);
   if (!why.empty()) return ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, why);
+  const bool listed_ids = synth::extras_have_corners(in);
   // (every mesh of a repair request is one whose topology the first pass refused)
-  if (ck.rq.repair && !ck.rq.corner_repair && (in.normal_corners || in.uv_corners))
+  if (ck.rq.repair && !ck.rq.corner_repair && (in.normal_corners || in.uv_corners || listed_ids))
     return ck.refuse(i, DSA_ERR_NOT_IMPLEMENTED, "attributes given per corner (normal_corners / texcoord_corners) over a mesh whose topology needs repair are not implemented");
   try {
     synth::check(m.positions && m.faces && m.num_vertices >= 3 && m.num_faces >= 1, "mesh needs positions and faces");
     for (size_t k = 0; k < (size_t)m.num_faces * 3; ++k) synth::check(m.faces[k] < m.num_vertices, "face index out of range");
     if (in.normal_corners) for (size_t k = 0; k < (size_t)m.num_faces * 3; ++k) synth::check(in.normal_corners[k] < in.nn, "normal id out of range");
     if (in.uv_corners) for (size_t k = 0; k < (size_t)m.num_faces * 3; ++k) synth::check(in.uv_corners[k] < in.nu, "texture coordinate id out of range");
+    if (listed_ids) { const std::string bad = synth::extras_id_error(in); synth::check(bad.empty(), bad.c_str()); }
     synth::check(ck.host_conn || (uint64_t)m.num_faces * 3 <= (uint64_t)dsa::EC_CORNER_MASK, "mesh too large for the device connectivity coder");
     synth::Options mo = opt;                                   // (the components of the generic attribute are the mesh's own)
     mo.generic_components = in.generic ? (int32_t)m.generic_components : 1;
@@ -401,8 +435,8 @@ static void enc_plan_mesh(EncChunk &ck, uint32_t i) {
     }
     synth::MeshPlan &pl = ck.plans[i];
     if (!ck.host_conn) {                                       // the rest of the plan comes from the device
-      synth::check(!((in.normal_corners || in.uv_corners) && opt.single_connectivity), "attributes given per corner need a connectivity of their own (single_connectivity = 0)");
-      synth::check(!(in.normal_corners || in.uv_corners) || 24ull * m.num_faces + 16u < (1ull << 32), "mesh too large for the device connectivity coder");
+      synth::check(!((in.normal_corners || in.uv_corners || listed_ids) && opt.single_connectivity), "attributes given per corner need a connectivity of their own (single_connectivity = 0)");
+      synth::check(!(in.normal_corners || in.uv_corners || listed_ids) || 24ull * m.num_faces + 16u < (1ull << 32), "mesh too large for the device connectivity coder");
       synth::plan_attributes(in, mo, pl);
       enc_extra_caps(ck, i);
       return;

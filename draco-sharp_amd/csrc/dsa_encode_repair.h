@@ -89,7 +89,7 @@ struct EncRepairIds {              // one per (mesh, attribute with ids); device
   uint64_t dst;                    // u16[3F'] / u32[3F'] OUTPUT (room for 3F)
   uint32_t rep;                    // the mesh's EncRepair
   uint32_t rows, narrow;           // value rows of the attribute; 1: u16 output
-  uint32_t att_type;               // 1 normals, 3 texture coordinates (which message a bad id earns)
+  uint32_t att_type;               // 1 normals, 3 texture coordinates, 0x100 + k attribute k of the list (which message a bad id earns)
   uint32_t bad, pad;               // OUTPUT: 1 an id is not below `rows`
 };
 __global__ __launch_bounds__(WAVE) void k_enc_repair_face_scan(uint8_t *arena, EncRepair *reps, uint32_t n) {

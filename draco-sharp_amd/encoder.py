@@ -47,7 +47,12 @@ class Config:
     triangulation, Batch.vertex_arrays: points are duplicated wherever a UV chart or a hard edge passes.  Points with byte-equal
     positions, generic and attribute rows are welded into one vertex, normals and texture coordinates go on per corner (or per
     vertex where no vertex has two), and the welded mesh is coded with the other options as they are.  Edgebreaker streams of
-    meshes without corner ids only."""
+    meshes without corner ids only.
+
+    weld_attributes (dsa_encode_corner_attributes_batch; needs weld_points): the attributes of the list leave the vertex key and
+    are welded each alone, like normals and texture coordinates -- a lightmap UV set with its own charts or a colour with a hard
+    edge then cuts its own connectivity only, and positions are not duplicated along its seams.  An attribute whose index in the
+    stream is above 7 stays in the vertex key (the decoder takes corner attributes for attribute data 0 to 6)."""
 
     EDGEBREAKER_METHODS = (0, 2, -1)
     POSITION_PREDICTIONS = (0, 1)
@@ -60,7 +65,7 @@ class Config:
     def __init__(self, position_bits=11, texcoord_bits=10, normal_bits=8, speed=5, single_connectivity=False,
                  symbol_scheme=-1, position_prediction=1, texcoord_prediction=1, edgebreaker_method=0, normal_prediction=0,
                  encoding_method=1, compress_connectivity=False, multi_parallelogram=0, traversal_method=0, repair_topology=False, weld_points=False,
-                 repair_seams=False):
+                 repair_seams=False, weld_attributes=False):
         for name, value, legal in (("encoding_method", encoding_method, self.ENCODING_METHODS),
                                    ("edgebreaker_method", edgebreaker_method, self.EDGEBREAKER_METHODS),
                                    ("position_prediction", position_prediction, self.POSITION_PREDICTIONS),
@@ -89,6 +94,9 @@ class Config:
         self.weld_points = bool(weld_points)
         if self.weld_points and self.sequential:
             raise ValueError("weld_points shapes Edgebreaker streams: a sequential stream keeps the caller's points as they are")
+        self.weld_attributes = bool(weld_attributes)
+        if self.weld_attributes and not self.weld_points:
+            raise ValueError("weld_attributes welds the listed attributes of per-point input each alone: it needs weld_points=True")
 
     @property
     def sequential(self):
@@ -190,10 +198,14 @@ class Attribute:
     WEIGHTS_0, a second UV set, feature ids.  values (V,) or (V, 1..4); the element type is the array's: int8, uint8, int16,
     uint16, int32, uint32 (coded as they are; 32-bit values within +-2^27 as int32) or float32 (quantised to quantization_bits,
     1..20; 0: the texture coordinates' bits for attribute_type 3, else 8).  attribute_type 2 colour, 3 texture coordinate,
-    4 generic; normalized goes into the descriptor of an integer attribute; unique_id None: the attribute's index in the stream."""
+    4 generic; normalized goes into the descriptor of an integer attribute; unique_id None: the attribute's index in the stream.
+    corners (F, 3): the attribute given per corner -- row ids into `values`, which then hold as many rows as the ids need (a
+    lightmap set with its own charts, a colour with a hard edge); edges across which the ids differ are seams of this attribute
+    alone (dsa_encode_corner_attributes_batch).  The attribute's index in the stream must be at most 7."""
 
-    def __init__(self, values, attribute_type=4, normalized=False, unique_id=None, quantization_bits=0, grid=None):
+    def __init__(self, values, attribute_type=4, normalized=False, unique_id=None, quantization_bits=0, grid=None, corners=None):
         v = np.asarray(values)
+        self.corners = corners                                    # (checked against the faces by MeshData)
         self.grid = _check_grid(grid, "Attribute grid")           # float32 only: a Grid in place of the values' own bounds
         if grid is not None and v.dtype != np.dtype(np.float32):
             raise ValueError("Attribute grid: only float32 values are quantised; integer attributes have no grid")
@@ -217,10 +229,44 @@ def _attributes(attributes, rows):
     for k, a in enumerate(attributes or []):
         if not isinstance(a, Attribute):
             a = Attribute(a)
-        if len(a.values) != rows:
+        if getattr(a, "corners", None) is None and len(a.values) != rows:
             raise ValueError("attribute %d: one row per vertex (%d rows for %d vertices)" % (k, len(a.values), rows))
         out.append(a)
     return out
+
+
+def _attribute_ids(attributes, faces):
+    """Attribute.corners of a mesh's list checked like MeshData._ids and made (F, 3) uint32."""
+    for k, a in enumerate(attributes):
+        if getattr(a, "corners", None) is None:
+            continue
+        name = "attribute %d corners" % k
+        ids = np.asarray(a.corners)
+        if ids.shape != (len(faces), 3) and ids.size != 3 * len(faces):
+            raise ValueError("%s: one id per face corner, shape (F, 3)" % name)
+        if ids.size and (np.issubdtype(ids.dtype, np.signedinteger) and ids.min() < 0):
+            raise ValueError("%s: ids are row numbers, not negative" % name)
+        ids = np.ascontiguousarray(ids.reshape(len(faces), 3), np.uint32)
+        if ids.size and int(ids.max()) >= len(a.values):
+            raise ValueError("%s: id %d out of range (%d rows)" % (name, int(ids.max()), len(a.values)))
+        a.corners = ids
+
+
+def _has_attribute_ids(m):
+    return any(getattr(a, "corners", None) is not None for a in (getattr(m, "attributes", None) or []))
+
+
+def _fill_attribute_corners(dst, m, keep):
+    """dsa_mesh_attribute_corners of mesh `m`; `keep` holds the ctypes array alive."""
+    atts = getattr(m, "attributes", None) or []
+    if not _has_attribute_ids(m):
+        return
+    arr = (native.AttributeCorners * len(atts))()
+    for k, a in enumerate(atts):
+        if getattr(a, "corners", None) is not None:
+            arr[k].corners, arr[k].num_rows = a.corners.ctypes.data, len(a.values)
+    keep.append(arr)
+    dst.attributes = arr
 
 
 def _fill_attr_input(dst, m, keep):
@@ -316,7 +362,8 @@ class MeshData:
 
     normal_corners / texcoord_corners (F,3) u32: the normals / texture coordinates given per corner -- row ids into `normals` /
     `texcoords`, which then hold as many rows as the ids need (UV charts, hard edges).  Edges whose end points carry different ids
-    on their two faces become attribute seams (dsa_encode_batch_corners).
+    on their two faces become attribute seams (dsa_encode_batch_corners).  Attribute(..., corners=) gives an attribute of the list
+    per corner in the same way (dsa_encode_corner_attributes_batch).
 
     position_grid / texcoord_grid: a Grid in place of the attribute's own bounds (Attribute(..., grid=) for a float32 attribute
     of the list); group: the meshes of a batch whose Grid.shared() attributes share one grid (dsa_encode_grid_batch)."""
@@ -327,6 +374,7 @@ class MeshData:
         self.positions = np.ascontiguousarray(positions, np.float32)
         self.attributes = _attributes(attributes, len(self.positions))
         self.faces = np.ascontiguousarray(faces, np.uint32)
+        _attribute_ids(self.attributes, self.faces)
         self.normals = None if normals is None else np.ascontiguousarray(normals, np.float32)
         self.texcoords = None if texcoords is None else np.ascontiguousarray(texcoords, np.float32)
         self.normal_corners = self._ids(normal_corners, self.normals, 3, "normal")
@@ -358,7 +406,7 @@ class MeshData:
 
     @property
     def per_corner(self):
-        return getattr(self, "normal_corners", None) is not None or getattr(self, "texcoord_corners", None) is not None
+        return getattr(self, "normal_corners", None) is not None or getattr(self, "texcoord_corners", None) is not None or _has_attribute_ids(self)
 
 
 class PointCloudData:
@@ -370,6 +418,8 @@ class PointCloudData:
         _set_grids(self, position_grid, texcoord_grid, group, texcoords)
         self.positions = np.ascontiguousarray(positions, np.float32)
         self.attributes = _attributes(attributes, len(self.positions))
+        if _has_attribute_ids(self):
+            raise ValueError("attribute corners need the faces of a mesh: a point cloud has one value per point")
         self.faces = np.zeros((0, 3), np.uint32)
         self.normals = None if normals is None else np.ascontiguousarray(normals, np.float32)
         self.texcoords = None if texcoords is None else np.ascontiguousarray(texcoords, np.float32)
@@ -468,7 +518,8 @@ class DracoEncoder:
     def EncodeBatch(self, meshes, config=None, handle=False):
         """meshes: list of MeshData (or of PointCloudData) -> sequence of bytes (.drc streams, EncodedStreams).  A sequential
         config (Config.sequential) and point clouds go through dsa_encode_grid_sequential_batch, every other batch through
-        dsa_encode_seam_repair_batch.  A mesh that cannot be encoded raises
+        dsa_encode_seam_repair_batch -- or, when an Attribute carries corners or config.weld_attributes is set, through
+        dsa_encode_corner_attributes_batch, which takes both.  A mesh that cannot be encoded raises
         (TryEncodeBatch: the batch with its failures, mesh by mesh)."""
         n = len(meshes)
         config = config or Config()
@@ -486,6 +537,8 @@ class DracoEncoder:
             raise ValueError("weld_points shapes Edgebreaker streams of meshes: point clouds and sequential streams keep the caller's points")
         if weld and any(getattr(m, "per_corner", False) for m in meshes):
             raise ValueError("weld_points takes one row per point: normal_corners / texcoord_corners describe a mesh that is welded already")
+        if getattr(config, "weld_attributes", False) and not weld:
+            raise ValueError("weld_attributes welds the listed attributes of per-point input each alone: it needs weld_points=True")
         ctx = self._ctx or default_context()
         L = native.lib()
         if clouds or config.sequential:
@@ -499,8 +552,20 @@ class DracoEncoder:
         opt.grid.weld_points = 1 if weld else 0
         opt.corner_repair = 1 if getattr(config, "repair_seams", False) else 0
         h = C.c_void_p()
+        weld_attributes = getattr(config, "weld_attributes", False)
         t0 = time.perf_counter()
-        st = L.dsa_encode_seam_repair_batch(ctx._h, n, arr, grids, C.byref(opt), C.byref(h))
+        if weld_attributes or any(_has_attribute_ids(m) for m in meshes):
+            # ids on attributes of the list, or the list welded attribute by attribute: the one call that takes them
+            wide = native.EncodeCornerAttributesOptions()
+            L.dsa_encode_default_corner_attributes_options(C.byref(wide))
+            wide.seam_repair = opt
+            wide.weld_attributes = 1 if weld_attributes else 0
+            corners = (native.MeshAttributeCorners * max(1, n))()
+            for i, m in enumerate(meshes):
+                _fill_attribute_corners(corners[i], m, keep)
+            st = L.dsa_encode_corner_attributes_batch(ctx._h, n, arr, grids, corners, C.byref(wide), C.byref(h))
+        else:
+            st = L.dsa_encode_seam_repair_batch(ctx._h, n, arr, grids, C.byref(opt), C.byref(h))
         t1 = time.perf_counter()
         if st != 0:
             _raise(st, ctx.error())

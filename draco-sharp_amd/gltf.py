@@ -491,7 +491,10 @@ class GltfDracoWriter:
         """sources: paths, bytes or GltfAssets.  shared_grid="mesh": the primitives of one glTF mesh share the quantisation grid of
         their positions (plan_compression), so that the mesh does not crack along the cuts between them; None: today's bytes.  One EncodeBatch with weld_points=True codes every planned primitive (the other
         options of `config` as given); one decode batch of the result gives the accessor counts -- a stream can hold more points
-        than its primitive had where seams cross.  Returns a CompressedAsset per source."""
+        than its primitive had where seams cross.  Config(weld_points=True, weld_attributes=True): the attributes of the list
+        (TEXCOORD_1 with lightmap charts of its own, COLOR_0 with a hard edge) are welded each alone instead of being part of the
+        vertex key, so their seams do not duplicate positions, normals and TEXCOORD_0; the extension's attribute ids and the accessor
+        counts follow the stream as ever.  Returns a CompressedAsset per source."""
         import copy
         from .encoder import Config, DracoEncoder
         assets = [s if isinstance(s, GltfAsset) else read_asset(s) for s in sources]

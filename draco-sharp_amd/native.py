@@ -36,6 +36,7 @@ EXPORTS = [
     "dsa_encode_points_batch", "dsa_weld_batch", "dsa_welded_size", "dsa_welded_mesh", "dsa_welded_free",
     "dsa_encode_default_grid_options", "dsa_encode_grid_batch", "dsa_encode_grid_sequential_batch",
     "dsa_encode_default_seam_repair_options", "dsa_encode_seam_repair_batch",
+    "dsa_encode_default_corner_attributes_options", "dsa_encode_corner_attributes_batch",
     "dsa_encoded_size", "dsa_encoded_stream", "dsa_encoded_free",
     "dsa_pool_create", "dsa_pool_destroy", "dsa_pool_size", "dsa_pool_last_error", "dsa_pool_decode", "dsa_pool_job_locate",
     "dsa_pool_job_chunks", "dsa_pool_job_free", "dsa_pool_plan",
@@ -125,6 +126,22 @@ class EncodeSeamRepairOptions(C.Structure):
     """dsa_encode_seam_repair_options: the options of dsa_encode_grid_batch, and corner_repair (1: attributes given per corner are
     coded over a mesh whose topology needs the repair; needs topology 1)."""
     _fields_ = [("grid", EncodeGridOptions), ("corner_repair", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+class AttributeCorners(C.Structure):
+    """dsa_attribute_corners: row ids per corner for one attribute of the list (corners NULL: per vertex)."""
+    _fields_ = [("corners", C.c_void_p), ("num_rows", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class MeshAttributeCorners(C.Structure):
+    """dsa_mesh_attribute_corners: the ids of the listed attributes of one mesh (attributes NULL: all per vertex)."""
+    _fields_ = [("attributes", C.POINTER(AttributeCorners)), ("reserved", C.c_uint32 * 2)]
+
+
+class EncodeCornerAttributesOptions(C.Structure):
+    """dsa_encode_corner_attributes_options: the options of dsa_encode_seam_repair_batch, and weld_attributes (1: with weld_points
+    every listed attribute is welded alone, like normals and texture coordinates)."""
+    _fields_ = [("seam_repair", EncodeSeamRepairOptions), ("weld_attributes", C.c_int32), ("reserved", C.c_int32 * 7)]
 
 
 class WeldedInfo(C.Structure):
@@ -283,6 +300,11 @@ def lib():
             L.dsa_encode_default_seam_repair_options.argtypes = [C.POINTER(EncodeSeamRepairOptions)]
             L.dsa_encode_default_seam_repair_options.restype = None
             L.dsa_encode_seam_repair_batch.argtypes = [vp, u32, C.POINTER(MeshAttrInput), C.POINTER(MeshGrids), C.POINTER(EncodeSeamRepairOptions), C.POINTER(vp)]
+        if hasattr(L, "dsa_encode_corner_attributes_batch"):
+            L.dsa_encode_default_corner_attributes_options.argtypes = [C.POINTER(EncodeCornerAttributesOptions)]
+            L.dsa_encode_default_corner_attributes_options.restype = None
+            L.dsa_encode_corner_attributes_batch.argtypes = [vp, u32, C.POINTER(MeshAttrInput), C.POINTER(MeshGrids), C.POINTER(MeshAttributeCorners),
+                                                             C.POINTER(EncodeCornerAttributesOptions), C.POINTER(vp)]
         L.dsa_encoded_size.restype = u32
         L.dsa_encoded_size.argtypes = [vp]
         L.dsa_encoded_stream.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(C.c_size_t)]

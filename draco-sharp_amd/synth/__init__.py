@@ -37,6 +37,11 @@ class ExtraInput(C.Structure):
                 ("unique_id", C.c_uint32), ("quantization_bits", C.c_int32), ("values", C.c_void_p)]
 
 
+class ExtraCornersInput(C.Structure):
+    """synth_extra_corners: row ids per corner for one attribute of an ExtraInput list (corners NULL: one row per vertex)."""
+    _fields_ = [("corners", C.c_void_p), ("num_rows", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class Grid(C.Structure):
     """A quantisation grid given by the caller (dsa_quantization_grid): mode 0 the attribute's own bounds, 1 explicit."""
     _fields_ = [("origin", C.c_float * 4), ("range", C.c_float), ("mode", C.c_int32), ("reserved", C.c_uint32 * 2)]
@@ -79,10 +84,15 @@ class Extra:
     """One more per-vertex attribute for the `extra=[...]` of the encode calls: values (V,) or (V, 1..4) of int8 / uint8 / int16 /
     uint16 / int32 / uint32 (coded as they are) or float32 (quantised to quantization_bits; 0: uv_bits for attribute_type 3, else
     8).  attribute_type 2 colour, 3 texture coordinate, 4 generic; unique_id None: the attribute's index in the stream.
-    data_type / num_components override what the array says (the refusal tests)."""
+    data_type / num_components override what the array says (the refusal tests).
+    corners: (F, 3) row ids into `values`, which then holds any number of rows -- the attribute is given per corner, and an interior
+    edge across which the ids differ is a seam of this attribute alone (Edgebreaker streams; the attribute's index in the stream must
+    be at most 7).  rows overrides the row count the ids are held against (the refusal tests)."""
 
-    def __init__(self, values, attribute_type=4, normalized=False, unique_id=None, quantization_bits=0, data_type=None, num_components=None, grid=None):
+    def __init__(self, values, attribute_type=4, normalized=False, unique_id=None, quantization_bits=0, data_type=None, num_components=None, grid=None,
+                 corners=None, rows=None):
         self.grid = grid                      # float32: a Grid (encode_grid), None: its own bounds
+        self.corners = None if corners is None else np.ascontiguousarray(corners, np.uint32)
         v = np.asarray(values)
         if v.dtype not in GENERIC_DATA_TYPES and v.dtype != np.dtype(np.float32):
             raise ValueError("extra attribute: dtype %s is none of int8 ... uint32, float32" % v.dtype)
@@ -94,13 +104,28 @@ class Extra:
         self.normalized = int(normalized)
         self.unique_id = UNIQUE_ID_DEFAULT if unique_id is None else unique_id
         self.quantization_bits = quantization_bits
+        self.rows = len(self.values) if rows is None else rows
+
+
+def _extra_corners(extra, nf):
+    """The synth_extra_corners array of a list of Extra, None when none of them has ids."""
+    if not any(e.corners is not None for e in extra):
+        return None
+    arr = (ExtraCornersInput * max(1, len(extra)))()
+    for k, e in enumerate(extra):
+        if e.corners is None:
+            continue
+        if e.corners.size != 3 * nf:
+            raise ValueError("extra attribute %d: one id per corner of `faces`" % k)
+        arr[k].corners, arr[k].num_rows = e.corners.ctypes.data, e.rows
+    return arr
 
 
 def _extras(extra, nv):
     """The synth_extra array of a list of Extra; the Extras own the value arrays, keep them beside it."""
     arr = (ExtraInput * max(1, len(extra)))()
     for k, e in enumerate(extra):
-        if len(e.values) != nv:
+        if e.corners is None and len(e.values) != nv:
             raise ValueError("extra attribute %d: one row per vertex" % k)
         arr[k].attribute_type, arr[k].data_type, arr[k].num_components = e.attribute_type, e.data_type, e.num_components
         arr[k].normalized, arr[k].unique_id, arr[k].quantization_bits = e.normalized, e.unique_id, e.quantization_bits
@@ -130,11 +155,17 @@ def _encode_attributes(edgebreaker, pos, faces, nrm, nci, uv, uci, generic, geom
                 opt = o2
     extra = [e if isinstance(e, Extra) else Extra(e) for e in extra]
     arr = _extras(extra, len(pos))
+    ec = _extra_corners(extra, 0 if faces is None else len(faces))
     ptr = lambda a: None if a is None else a.ctypes.data          # noqa: E731
     out, n = C.c_void_p(), C.c_size_t()
-    rc = L.synth_encode_attributes(1 if edgebreaker else 0, ptr(pos), len(pos), ptr(faces), 0 if faces is None else len(faces),
-                                   ptr(nrm), 0 if nrm is None else len(nrm), ptr(nci), ptr(uv), 0 if uv is None else len(uv), ptr(uci),
-                                   ptr(gen), geometry, 1 if compressed else 0, arr, len(extra), C.byref(opt), C.byref(out), C.byref(n))
+    if ec is None:
+        rc = L.synth_encode_attributes(1 if edgebreaker else 0, ptr(pos), len(pos), ptr(faces), 0 if faces is None else len(faces),
+                                       ptr(nrm), 0 if nrm is None else len(nrm), ptr(nci), ptr(uv), 0 if uv is None else len(uv), ptr(uci),
+                                       ptr(gen), geometry, 1 if compressed else 0, arr, len(extra), C.byref(opt), C.byref(out), C.byref(n))
+    else:
+        rc = L.synth_encode_corner_attributes(1 if edgebreaker else 0, ptr(pos), len(pos), ptr(faces), 0 if faces is None else len(faces),
+                                              ptr(nrm), 0 if nrm is None else len(nrm), ptr(nci), ptr(uv), 0 if uv is None else len(uv), ptr(uci),
+                                              ptr(gen), geometry, 1 if compressed else 0, arr, ec, len(extra), C.byref(opt), C.byref(out), C.byref(n))
     if rc:
         raise RuntimeError(_err())
     data = C.string_at(out, n.value)
@@ -174,6 +205,20 @@ def lib():
         L.synth_encode_attributes.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                               C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(ExtraInput), C.c_uint32,
                                               C.POINTER(Options), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+        L.synth_encode_corner_attributes.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                     C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(ExtraInput), C.POINTER(ExtraCornersInput),
+                                                     C.c_uint32, C.POINTER(Options), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+        L.synth_weld_points_attributes.restype = C.c_void_p
+        L.synth_weld_points_attributes.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.POINTER(ExtraInput), C.c_uint32, C.POINTER(Options), C.c_int]
+        L.synth_welded_listed.restype = C.c_uint32
+        L.synth_welded_listed.argtypes = [C.c_void_p]
+        L.synth_welded_listed_counts.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+        L.synth_encode_points_attributes.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.POINTER(ExtraInput), C.c_uint32, C.POINTER(Options), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+        L.synth_encode_corner_attributes_grid.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                          C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(ExtraInput), C.POINTER(ExtraCornersInput),
+                                                          C.c_uint32, C.POINTER(GridsInput), C.POINTER(Options), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
         L.synth_weld_points.restype = C.c_void_p
         L.synth_weld_points.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.POINTER(ExtraInput), C.c_uint32, C.POINTER(Options)]
@@ -311,7 +356,8 @@ class Welded:
     texcoord_of_point [P], vertex_point [V] / normal_point [N] / texcoord_point [T] (the representative point of every class; the
     normal / texcoord maps are None when the mesh has no such attribute).  The welded mesh: pos [V,3], faces [F,3], generic and
     extra (rows of vertex_point), normals with normal_corners [F,3] (None and V rows when normals_per_vertex), uvs with
-    uv_corners likewise."""
+    uv_corners likewise.  weld_attributes: extra_corners[k] [F,3] / extra_of_point[k] [P] / extra_point[k] of a listed attribute
+    welded alone that some vertex has two rows of (extra[k] then holds the attribute's own rows), else None."""
 
 
 def _points_args(pos, faces, normals, uvs, generic, extra, opt):
@@ -336,14 +382,22 @@ def _points_args(pos, faces, normals, uvs, generic, extra, opt):
     return pos, faces, nrm, uv, gen, extra, _extras(extra, len(pos)), opt
 
 
-def weld_points(pos, faces, normals=None, uvs=None, generic=None, extra=None, opt=None):
+def _no_point_ids(extra):
+    if any(e.corners is not None for e in extra):
+        raise ValueError("per-point input takes no corner ids")
+
+
+def weld_points(pos, faces, normals=None, uvs=None, generic=None, extra=None, opt=None, weld_attributes=False):
     """The weld of a mesh given as one row per point (dsa_encode_host.h weld_points): used points with byte-equal position,
     generic and extra rows are one vertex; normals and uvs are welded each alone and handed on per corner, or per vertex where
-    no vertex has two of them.  Returns a Welded."""
+    no vertex has two of them.  weld_attributes: every extra whose index in the stream is at most 7 leaves the vertex key and is
+    welded alone like normals and uvs.  Returns a Welded."""
     L = lib()
     pos, faces, nrm, uv, gen, extra, arr, opt = _points_args(pos, faces, normals, uvs, generic, extra, opt)
+    _no_point_ids(extra)
     ptr = lambda a: None if a is None else a.ctypes.data          # noqa: E731
-    h = L.synth_weld_points(ptr(pos), len(pos), ptr(faces), len(faces), ptr(nrm), ptr(uv), ptr(gen), arr, len(extra), C.byref(opt))
+    h = L.synth_weld_points_attributes(ptr(pos), len(pos), ptr(faces), len(faces), ptr(nrm), ptr(uv), ptr(gen), arr, len(extra), C.byref(opt),
+                                       1 if weld_attributes else 0)
     if not h:
         raise RuntimeError(_err())
     try:
@@ -373,24 +427,37 @@ def weld_points(pos, faces, normals=None, uvs=None, generic=None, extra=None, op
         if gen is not None:
             w.generic = array(g, gen.dtype).reshape(-1, gen.shape[1])
             g += 1
-        w.extra = []
-        for e in extra:
+        w.extra, w.extra_corners, w.extra_of_point, w.extra_point = [], [], [], []
+        alone = int(L.synth_welded_listed(h))
+        for k, e in enumerate(extra):
+            if k < alone:
+                lc = (C.c_uint32 * 2)()
+                L.synth_welded_listed_counts(h, k, lc)
+                w.extra.append(array(64 + 4 * k + 3, e.values.dtype).reshape(-1, e.values.shape[1]))
+                w.extra_corners.append(None if lc[1] else array(64 + 4 * k + 2, np.uint32).reshape(-1, 3))
+                w.extra_of_point.append(array(64 + 4 * k, np.uint32))
+                w.extra_point.append(array(64 + 4 * k + 1, np.uint32))
+                continue
             w.extra.append(array(g, e.values.dtype).reshape(-1, e.values.shape[1]))
+            w.extra_corners.append(None)
+            w.extra_of_point.append(None)
+            w.extra_point.append(None)
             g += 1
         return w
     finally:
         L.synth_welded_free(h)
 
 
-def encode_mesh_points(pos, faces, normals=None, uvs=None, generic=None, extra=None, opt=None):
+def encode_mesh_points(pos, faces, normals=None, uvs=None, generic=None, extra=None, opt=None, weld_attributes=False):
     """weld_points followed by the coder of encode_mesh_corners on the welded mesh (extra: Extras with one row per point).  What
-    dsa_encode_points_batch must write."""
+    dsa_encode_points_batch must write; with weld_attributes what dsa_encode_corner_attributes_batch must."""
     L = lib()
     pos, faces, nrm, uv, gen, extra, arr, opt = _points_args(pos, faces, normals, uvs, generic, extra, opt)
+    _no_point_ids(extra)
     ptr = lambda a: None if a is None else a.ctypes.data          # noqa: E731
     out, n = C.c_void_p(), C.c_size_t()
-    rc = L.synth_encode_points(ptr(pos), len(pos), ptr(faces), len(faces), ptr(nrm), ptr(uv), ptr(gen), arr, len(extra), C.byref(opt),
-                               C.byref(out), C.byref(n))
+    rc = L.synth_encode_points_attributes(ptr(pos), len(pos), ptr(faces), len(faces), ptr(nrm), ptr(uv), ptr(gen), arr, len(extra), C.byref(opt),
+                                          1 if weld_attributes else 0, C.byref(out), C.byref(n))
     if rc:
         raise RuntimeError(_err())
     data = C.string_at(out, n.value)
@@ -399,7 +466,7 @@ def encode_mesh_points(pos, faces, normals=None, uvs=None, generic=None, extra=N
 
 
 def encode_grid(pos, faces=None, normals=None, uvs=None, generic=None, extra=None, opt=None, form=1, normal_corners=None, uv_corners=None,
-                geometry=1, compressed=False, pos_grid=None, uv_grid=None):
+                geometry=1, compressed=False, pos_grid=None, uv_grid=None, weld_attributes=False):
     """Any stream of this module with quantisation grids given by the caller: pos_grid / uv_grid / Extra.grid are Grids (grid(),
     shared_grid()) or None for the attribute's own bounds.  form 1: the arguments of encode_mesh_corners (Edgebreaker); form 0:
     of encode_sequential (geometry 1) / encode_point_cloud_attributes (geometry 0, faces None); form 2: of encode_mesh_points
@@ -426,9 +493,15 @@ def encode_grid(pos, faces=None, normals=None, uvs=None, generic=None, extra=Non
     gi.attributes = ga
     ptr = lambda a: None if a is None else a.ctypes.data          # noqa: E731
     out, n = C.c_void_p(), C.c_size_t()
-    rc = L.synth_encode_grid(form, ptr(pos), len(pos), ptr(fc) if len(fc) else None, len(fc), ptr(nrm), 0 if nrm is None else len(nrm), ptr(nci),
-                             ptr(uv), 0 if uv is None else len(uv), ptr(uci), ptr(gen), geometry, 1 if compressed else 0, arr, len(extra),
-                             C.byref(gi), C.byref(opt), C.byref(out), C.byref(n))
+    ec = _extra_corners(extra, len(fc))
+    if ec is None and not weld_attributes:
+        rc = L.synth_encode_grid(form, ptr(pos), len(pos), ptr(fc) if len(fc) else None, len(fc), ptr(nrm), 0 if nrm is None else len(nrm), ptr(nci),
+                                 ptr(uv), 0 if uv is None else len(uv), ptr(uci), ptr(gen), geometry, 1 if compressed else 0, arr, len(extra),
+                                 C.byref(gi), C.byref(opt), C.byref(out), C.byref(n))
+    else:
+        rc = L.synth_encode_corner_attributes_grid(form, ptr(pos), len(pos), ptr(fc) if len(fc) else None, len(fc), ptr(nrm), 0 if nrm is None else len(nrm),
+                                                   ptr(nci), ptr(uv), 0 if uv is None else len(uv), ptr(uci), ptr(gen), geometry, 1 if compressed else 0,
+                                                   arr, ec, len(extra), C.byref(gi), C.byref(opt), 1 if weld_attributes else 0, C.byref(out), C.byref(n))
     if rc:
         raise RuntimeError(_err())
     data = C.string_at(out, n.value)

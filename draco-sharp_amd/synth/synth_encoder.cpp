@@ -237,16 +237,20 @@ struct synth_extra {
   int32_t quantization_bits;
   const void *values;
 };
-int synth_encode_attributes(int edgebreaker, const float *pos, uint32_t nv, const uint32_t *faces, uint32_t nf, const float *normals, uint32_t nn,
-                            const uint32_t *normal_corners, const float *uvs, uint32_t nu, const uint32_t *uv_corners, const void *generic,
-                            int geometry, int compressed, const synth_extra *extras, uint32_t num_extras, const synth_options *opt,
-                            uint8_t **out, size_t *out_len) {
+// Row ids per corner for the attributes of a synth_extra list (parallel to it; the layout of dsa_attribute_corners): corners NULL:
+// that attribute has one row per vertex.
+struct synth_extra_corners { const uint32_t *corners; uint32_t num_rows, reserved; };
+static int encode_attributes(int edgebreaker, const float *pos, uint32_t nv, const uint32_t *faces, uint32_t nf, const float *normals, uint32_t nn,
+                             const uint32_t *normal_corners, const float *uvs, uint32_t nu, const uint32_t *uv_corners, const void *generic,
+                             int geometry, int compressed, const synth_extra *extras, const synth_extra_corners *extra_corners, uint32_t num_extras,
+                             const synth_options *opt, uint8_t **out, size_t *out_len) {
   try {
     std::vector<synth::ExtraAttr> ex(num_extras);
     for (uint32_t k = 0; k < num_extras; ++k) {
       ex[k].att_type = extras[k].attribute_type; ex[k].data_type = extras[k].data_type; ex[k].nc = extras[k].num_components;
       ex[k].normalized = extras[k].normalized; ex[k].unique_id = extras[k].unique_id; ex[k].bits = extras[k].quantization_bits;
       ex[k].values = extras[k].values;
+      if (extra_corners && extra_corners[k].corners) { ex[k].corners = extra_corners[k].corners; ex[k].rows = extra_corners[k].num_rows; }
     }
     synth::MeshIn in{pos, nv, faces, nf, normals, uvs, generic};
     in.extras = ex.data(); in.num_extras = num_extras;
@@ -259,9 +263,10 @@ int synth_encode_attributes(int edgebreaker, const float *pos, uint32_t nv, cons
         synth::check(!in.normal_corners || in.normal_corners[k] < nn, "normal id out of range");
         synth::check(!in.uv_corners || in.uv_corners[k] < nu, "texture coordinate id out of range");
       }
+      { const std::string why = synth::extras_id_error(in); synth::check(why.empty(), why.c_str()); }
       synth::encode_mesh(in, to_opt(opt), buf);
     } else {
-      synth::check(!normal_corners && !uv_corners, "a sequential stream has one value per point");
+      synth::check(!normal_corners && !uv_corners && !synth::extras_have_corners(in), "a sequential stream has one value per point");
       synth::check(geometry == 0 || geometry == 1, "geometry: 1 (triangular mesh) or 0 (point cloud)");
       synth::check(geometry == 1 || nf == 0, "a point cloud has no faces");
       synth::check(pos != nullptr && nv > 0, "positions are missing");
@@ -274,6 +279,19 @@ int synth_encode_attributes(int edgebreaker, const float *pos, uint32_t nv, cons
     *out_len = buf.size();
     return 0;
   } catch (const std::exception &e) { snprintf(g_err, sizeof(g_err), "%s", e.what()); return 1; }
+}
+int synth_encode_attributes(int edgebreaker, const float *pos, uint32_t nv, const uint32_t *faces, uint32_t nf, const float *normals, uint32_t nn,
+                            const uint32_t *normal_corners, const float *uvs, uint32_t nu, const uint32_t *uv_corners, const void *generic,
+                            int geometry, int compressed, const synth_extra *extras, uint32_t num_extras, const synth_options *opt,
+                            uint8_t **out, size_t *out_len) {
+  return encode_attributes(edgebreaker, pos, nv, faces, nf, normals, nn, normal_corners, uvs, nu, uv_corners, generic, geometry, compressed, extras, nullptr, num_extras, opt, out, out_len);
+}
+// ... with row ids per corner for attributes of the list (extra_corners: num_extras entries or NULL).
+int synth_encode_corner_attributes(int edgebreaker, const float *pos, uint32_t nv, const uint32_t *faces, uint32_t nf, const float *normals, uint32_t nn,
+                                   const uint32_t *normal_corners, const float *uvs, uint32_t nu, const uint32_t *uv_corners, const void *generic,
+                                   int geometry, int compressed, const synth_extra *extras, const synth_extra_corners *extra_corners, uint32_t num_extras,
+                                   const synth_options *opt, uint8_t **out, size_t *out_len) {
+  return encode_attributes(edgebreaker, pos, nv, faces, nf, normals, nn, normal_corners, uvs, nu, uv_corners, generic, geometry, compressed, extras, extra_corners, num_extras, opt, out, out_len);
 }
 // Per-point input (one row per point in every value array, `faces` index points; dsa_encode_host.h weld_points): the weld alone,
 // and the weld followed by the Edgebreaker coder.  The generic attribute: nv rows of opt->generic_components elements of
@@ -297,15 +315,27 @@ static size_t generic_row_bytes(const synth::Options &o) {
   synth::check(o.generic_components >= 1 && o.generic_components <= 4, "generic attribute needs 1 - 4 components");
   return synth::data_type_size(o.generic_data_type) * (size_t)o.generic_components;
 }
-synth_welded *synth_weld_points(const float *pos, uint32_t np, const uint32_t *faces, uint32_t nf, const float *normals, const float *uvs,
-                                const void *generic, const synth_extra *extras, uint32_t num_extras, const synth_options *opt) {
+// weld_attributes != 0: the listed attributes a stream may carry per corner are key sets of their own (dsa_encode_host.h weld_points)
+synth_welded *synth_weld_points_attributes(const float *pos, uint32_t np, const uint32_t *faces, uint32_t nf, const float *normals, const float *uvs,
+                                           const void *generic, const synth_extra *extras, uint32_t num_extras, const synth_options *opt, int weld_attributes) {
   try {
     std::vector<synth::ExtraAttr> ex;
     const synth::MeshIn in = points_in(pos, np, faces, nf, normals, uvs, generic, extras, num_extras, ex);
     std::unique_ptr<synth_welded> h(new synth_welded());
-    synth::weld_points(np, faces, nf, synth::weld_vertex_key(in, generic ? generic_row_bytes(to_opt(opt)) : 0), normals, uvs, h->w);
+    std::vector<synth::WeldSeg> listed;
+    const std::vector<synth::WeldSeg> key = synth::weld_vertex_key(in, generic ? generic_row_bytes(to_opt(opt)) : 0, weld_attributes != 0, &listed);
+    synth::weld_points(np, faces, nf, key, normals, uvs, h->w, listed);
     return h.release();
   } catch (const std::exception &e) { snprintf(g_err, sizeof(g_err), "%s", e.what()); return nullptr; }
+}
+synth_welded *synth_weld_points(const float *pos, uint32_t np, const uint32_t *faces, uint32_t nf, const float *normals, const float *uvs,
+                                const void *generic, const synth_extra *extras, uint32_t num_extras, const synth_options *opt) {
+  return synth_weld_points_attributes(pos, np, faces, nf, normals, uvs, generic, extras, num_extras, opt, 0);
+}
+// the listed attributes welded alone: how many; of attribute j its row count and whether it stayed per vertex
+uint32_t synth_welded_listed(const synth_welded *h) { return (uint32_t)h->w.listed.size(); }
+void synth_welded_listed_counts(const synth_welded *h, uint32_t j, uint32_t counts[2]) {
+  counts[0] = h->w.listed[j].keys.count; counts[1] = h->w.listed[j].per_vertex ? 1u : 0u;
 }
 // counts: P, F, V, N, T, normals per vertex, texcoords per vertex, segments of the vertex key
 void synth_welded_counts(const synth_welded *h, uint32_t counts[8]) {
@@ -314,7 +344,8 @@ void synth_welded_counts(const synth_welded *h, uint32_t counts[8]) {
   memcpy(counts, c, sizeof(c));
 }
 // which: 0 vertex_of_point, 1 vertex_point, 2 normal_of_point, 3 normal_point, 4 texcoord_of_point, 5 texcoord_point, 6 faces,
-// 7 normal_corners, 8 texcoord_corners, 9 normal rows, 10 texcoord rows, 16 + g: rows of segment g of the vertex key
+// 7 normal_corners, 8 texcoord_corners, 9 normal rows, 10 texcoord rows, 16 + g: rows of segment g of the vertex key,
+// 64 + 4 j + 0 .. 3: of listed attribute j welded alone (synth_weld_points_attributes) its of_point, point, corners, rows
 int synth_welded_array(const synth_welded *h, uint32_t which, const void **data, size_t *bytes) {
   const synth::Welded &w = h->w;
   auto u32 = [&](const std::vector<uint32_t> &v) { *data = v.data(); *bytes = 4 * v.size(); return 0; };
@@ -328,17 +359,30 @@ int synth_welded_array(const synth_welded *h, uint32_t which, const void **data,
     default: break;
   }
   if (which >= 16 && which - 16 < w.vertex_rows.size()) return u8(w.vertex_rows[which - 16]);
+  // 64 + 4 j + 0 .. 3: of listed attribute j welded alone its of_point, point, corners, rows
+  if (which >= 64 && (which - 64) / 4 < w.listed.size()) {
+    const synth::Welded::Listed &l = w.listed[(which - 64) / 4];
+    switch ((which - 64) % 4) { case 0: return u32(l.keys.of_point); case 1: return u32(l.keys.point); case 2: return u32(l.corners); default: return u8(l.rows); }
+  }
   return 1;
 }
 void synth_welded_free(synth_welded *h) { delete h; }
+int synth_encode_points_attributes(const float *pos, uint32_t np, const uint32_t *faces, uint32_t nf, const float *normals, const float *uvs, const void *generic,
+                                   const synth_extra *extras, uint32_t num_extras, const synth_options *opt, int weld_attributes, uint8_t **out, size_t *out_len);
 int synth_encode_points(const float *pos, uint32_t np, const uint32_t *faces, uint32_t nf, const float *normals, const float *uvs, const void *generic,
                         const synth_extra *extras, uint32_t num_extras, const synth_options *opt, uint8_t **out, size_t *out_len) {
+  return synth_encode_points_attributes(pos, np, faces, nf, normals, uvs, generic, extras, num_extras, opt, 0, out, out_len);
+}
+int synth_encode_points_attributes(const float *pos, uint32_t np, const uint32_t *faces, uint32_t nf, const float *normals, const float *uvs, const void *generic,
+                                   const synth_extra *extras, uint32_t num_extras, const synth_options *opt, int weld_attributes, uint8_t **out, size_t *out_len) {
   try {
     std::vector<synth::ExtraAttr> ex, ex2;
     const synth::MeshIn in = points_in(pos, np, faces, nf, normals, uvs, generic, extras, num_extras, ex);
     const synth::Options o = to_opt(opt);
     synth::Welded w;
-    synth::weld_points(np, faces, nf, synth::weld_vertex_key(in, generic ? generic_row_bytes(o) : 0), normals, uvs, w);
+    std::vector<synth::WeldSeg> listed;
+    const std::vector<synth::WeldSeg> key = synth::weld_vertex_key(in, generic ? generic_row_bytes(o) : 0, weld_attributes != 0, &listed);
+    synth::weld_points(np, faces, nf, key, normals, uvs, w, listed);
     const synth::MeshIn m = synth::welded_mesh_in(in, w, ex2);
     // (what the library's host checks say of a mesh the coder itself would not survive)
     synth::check(!(o.repair_topology && pos && np >= 3 && nf == 0), "all triangles are degenerate");
@@ -355,14 +399,20 @@ int synth_encode_points(const float *pos, uint32_t np, const uint32_t *faces, ui
 // dsa_quantization_grid): `grids` null or its entries mode 0: the bytes of the calls above.  form 0: synth_encode_attributes'
 // sequential arguments, 1: its Edgebreaker arguments, 2: synth_encode_points' (one row per point, corner ids unset).
 struct synth_grids { synth::Grid position, texcoord; const synth::Grid *attributes; };      // attributes: num_extras entries or NULL
-int synth_encode_grid(int form, const float *pos, uint32_t nv, const uint32_t *faces, uint32_t nf, const float *normals, uint32_t nn,
-                      const uint32_t *normal_corners, const float *uvs, uint32_t nu, const uint32_t *uv_corners, const void *generic,
-                      int geometry, int compressed, const synth_extra *extras, uint32_t num_extras, const synth_grids *grids,
-                      const synth_options *opt, uint8_t **out, size_t *out_len) {
+static int encode_grid(int form, const float *pos, uint32_t nv, const uint32_t *faces, uint32_t nf, const float *normals, uint32_t nn,
+                       const uint32_t *normal_corners, const float *uvs, uint32_t nu, const uint32_t *uv_corners, const void *generic,
+                       int geometry, int compressed, const synth_extra *extras, const synth_extra_corners *extra_corners, uint32_t num_extras,
+                       const synth_grids *grids, const synth_options *opt, int weld_attributes, uint8_t **out, size_t *out_len) {
   try {
     synth::check(form >= 0 && form <= 2, "form: 0 (sequential), 1 (Edgebreaker) or 2 (one row per point)");
     std::vector<synth::ExtraAttr> ex, ex2;
     synth::MeshIn in = points_in(pos, nv, faces, nf, normals, uvs, generic, extras, num_extras, ex);
+    for (uint32_t k = 0; k < num_extras && extra_corners; ++k)
+      if (extra_corners[k].corners) {
+        synth::check(form == 1, form == 0 ? "a sequential stream has one value per point" : "per-point input takes no corner ids");
+        ex[k].corners = extra_corners[k].corners; ex[k].rows = extra_corners[k].num_rows;
+      }
+    { const std::string why = synth::extras_error(in); synth::check(why.empty(), why.c_str()); }
     if (grids) {
       in.pos_grid = &grids->position;
       if (uvs) in.uv_grid = &grids->texcoord;
@@ -387,10 +437,13 @@ int synth_encode_grid(int form, const float *pos, uint32_t nv, const uint32_t *f
         synth::check(!in.normal_corners || in.normal_corners[k] < nn, "normal id out of range");
         synth::check(!in.uv_corners || in.uv_corners[k] < nu, "texture coordinate id out of range");
       }
+      { const std::string why = synth::extras_id_error(in); synth::check(why.empty(), why.c_str()); }
       synth::encode_mesh(in, o, buf);
     } else {
       synth::Welded w;
-      synth::weld_points(nv, faces, nf, synth::weld_vertex_key(in, generic ? generic_row_bytes(o) : 0), normals, uvs, w);
+      std::vector<synth::WeldSeg> listed;
+      const std::vector<synth::WeldSeg> key = synth::weld_vertex_key(in, generic ? generic_row_bytes(o) : 0, weld_attributes != 0, &listed);
+      synth::weld_points(nv, faces, nf, key, normals, uvs, w, listed);
       const synth::MeshIn m = synth::welded_mesh_in(in, w, ex2);
       synth::check(!(o.repair_topology && pos && nv >= 3 && nf == 0), "all triangles are degenerate");
       synth::check(m.pos && m.faces && m.nv >= 3 && m.nf >= 1, "mesh needs positions and faces");
@@ -401,6 +454,19 @@ int synth_encode_grid(int form, const float *pos, uint32_t nv, const uint32_t *f
     *out_len = buf.size();
     return 0;
   } catch (const std::exception &e) { snprintf(g_err, sizeof(g_err), "%s", e.what()); return 1; }
+}
+int synth_encode_grid(int form, const float *pos, uint32_t nv, const uint32_t *faces, uint32_t nf, const float *normals, uint32_t nn,
+                      const uint32_t *normal_corners, const float *uvs, uint32_t nu, const uint32_t *uv_corners, const void *generic,
+                      int geometry, int compressed, const synth_extra *extras, uint32_t num_extras, const synth_grids *grids,
+                      const synth_options *opt, uint8_t **out, size_t *out_len) {
+  return encode_grid(form, pos, nv, faces, nf, normals, nn, normal_corners, uvs, nu, uv_corners, generic, geometry, compressed, extras, nullptr, num_extras, grids, opt, 0, out, out_len);
+}
+// ... with row ids per corner for attributes of the list (form 1) or the listed attributes welded alone (form 2, weld_attributes != 0)
+int synth_encode_corner_attributes_grid(int form, const float *pos, uint32_t nv, const uint32_t *faces, uint32_t nf, const float *normals, uint32_t nn,
+                                        const uint32_t *normal_corners, const float *uvs, uint32_t nu, const uint32_t *uv_corners, const void *generic,
+                                        int geometry, int compressed, const synth_extra *extras, const synth_extra_corners *extra_corners, uint32_t num_extras,
+                                        const synth_grids *grids, const synth_options *opt, int weld_attributes, uint8_t **out, size_t *out_len) {
+  return encode_grid(form, pos, nv, faces, nf, normals, nn, normal_corners, uvs, nu, uv_corners, generic, geometry, compressed, extras, extra_corners, num_extras, grids, opt, weld_attributes, out, out_len);
 }
 // The grid a group of meshes shares (mode 2; dsa_encode_host.h shared_grid): over `count` arrays of rows[k] rows of nc floats.
 // Returns 0 and the grid as an explicit one (mode 1), or 1 when no array is free of values that are not finite.

@@ -500,7 +500,9 @@ dsa_status dsa_encode_repair_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_
  *   - a point is used when a face names it; a face index >= num_vertices fails the mesh (DSA_ERR_INVALID_DATA, "face index out
  *     of range") before anything is read through the faces;
  *   - two used points are one vertex when their position rows, their mesh.generic rows and their rows in every attribute of the
- *     list are equal byte for byte (floats as bit patterns: -0.0 is not +0.0, a NaN equals the NaN of the same payload);
+ *     list are equal byte for byte (floats as bit patterns: -0.0 is not +0.0, a NaN equals the NaN of the same payload) -- so an
+ *     attribute of the list that jumps across an edge cuts the positions there; dsa_encode_corner_attributes_batch with
+ *     weld_attributes = 1 welds the listed attributes alone instead;
  *   - the representative of a vertex is its used point of smallest index; vertices are numbered by ascending representative;
  *   - normals and texture coordinates are welded the same way, each alone, and go to the coder as rows with ids per corner --
  *     unless no vertex has two of them: then as one row per vertex (the row of the vertex's representative), without ids.
@@ -597,6 +599,48 @@ typedef struct dsa_encode_seam_repair_options {
 void dsa_encode_default_seam_repair_options(dsa_encode_seam_repair_options *options);
 dsa_status dsa_encode_seam_repair_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids,
                                         const dsa_encode_seam_repair_options *options, dsa_encoded **out);
+/* dsa_encode_seam_repair_batch that takes row ids per corner for the attributes of the list too (TEXCOORD_1 with its own chart
+ * layout, COLOR_0 with a hard edge, feature ids): seams beyond normals and the first UV set.
+ *   corners[i].attributes[k] (parallel to meshes[i].attributes; `corners`, or a mesh's `attributes`, NULL: none) gives attribute k
+ *   3 * num_faces row ids into its `values`, which then hold num_rows rows.  An interior edge across which the ids differ is a seam
+ *   of that attribute alone; the attribute is written as a corner attribute with a connectivity of its own when it has such an
+ *   edge, else per vertex.  Its prediction stays the one mesh.generic gets (the positions' family), over its own corner table when
+ *   it has interior seams.  Quantisation bounds, integer bounds and shared grids (mode 2) are taken over its num_rows rows.
+ *   mesh.generic stays per vertex.  Everything corner_repair = 1 does for normals and texture coordinates holds for these ids too.
+ *   weld_attributes = 1 (needs grid.weld_points = 1): every listed attribute leaves the vertex key of the weld (see
+ *   dsa_encode_points_batch) and is a key set of its own, welded like normals and texture coordinates: the vertex key is then
+ *   positions + mesh.generic, and a listed attribute goes on per corner when some vertex has two of its rows, else per vertex with
+ *   the representative's row and no ids.  A lightmap set then cuts its own connectivity only and the surface stays watertight.
+ *   This library's decoder takes corner attributes for attribute data 0 to 6, so: a listed attribute whose index in the stream
+ *   (positions 0, then normals, texcoords, generic where present, then the list) is above 7 stays in the vertex key under
+ *   weld_attributes = 1, and explicit ids on such an attribute fail the mesh alone with DSA_ERR_INVALID_ARGUMENT ("attribute k:
+ *   corner ids on attribute j of the stream ...").
+ * Per mesh: an id at or above num_rows: DSA_ERR_INVALID_DATA "attribute k id out of range" (degenerate faces included); explicit
+ * ids together with weld_points: DSA_ERR_INVALID_ARGUMENT as for the built-in ids; a non-zero reserved word of either struct:
+ * DSA_ERR_INVALID_ARGUMENT; ids with single_connectivity stay refused.  The call fails with DSA_ERR_INVALID_ARGUMENT for
+ * weld_attributes outside {0, 1}, weld_attributes = 1 without weld_points, or a non-zero reserved word of the options.  With
+ * corners == NULL and weld_attributes = 0 streams and messages are byte for byte those of dsa_encode_seam_repair_batch.  The
+ * streams are byte-identical to the CPU coder's.  dsa_weld_batch has no such mode: callers of weld_attributes get the streams.
+ * Added after ABI 4 without changing it: callers detect the feature by the symbol dsa_encode_corner_attributes_batch. */
+typedef struct dsa_attribute_corners {
+  const uint32_t *corners;                 /* 3 * num_faces row ids into the attribute's values, or NULL: per vertex */
+  uint32_t num_rows;                       /* rows of `values` when corners != NULL */
+  uint32_t reserved;                       /* must be zero */
+} dsa_attribute_corners;                   /* 16 bytes */
+typedef struct dsa_mesh_attribute_corners {
+  const dsa_attribute_corners *attributes; /* num_attributes entries parallel to dsa_mesh_attr_input.attributes, or NULL */
+  uint32_t reserved[2];                    /* must be zero */
+} dsa_mesh_attribute_corners;              /* 16 bytes */
+typedef struct dsa_encode_corner_attributes_options {
+  dsa_encode_seam_repair_options seam_repair; /* as for dsa_encode_seam_repair_batch, same legal values */
+  int32_t weld_attributes;                 /* 0 (default): today's vertex key; 1: listed attributes welded alone; needs weld_points */
+  int32_t reserved[7];                     /* must be zero */
+} dsa_encode_corner_attributes_options;
+void dsa_encode_default_corner_attributes_options(dsa_encode_corner_attributes_options *options);
+/* `grids` and `corners` are parallel to `meshes` (or NULL). */
+dsa_status dsa_encode_corner_attributes_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids,
+                                              const dsa_mesh_attribute_corners *corners, const dsa_encode_corner_attributes_options *options,
+                                              dsa_encoded **out);
 /* The same for sequential meshes and point clouds (dsa_encode_attributes_sequential_batch). */
 dsa_status dsa_encode_grid_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids,
                                             const dsa_encode_sequential_options *options, dsa_encoded **out);
