@@ -57,20 +57,7 @@ struct EncLane {
   hipEvent_t seams_done = nullptr;                   // attributes given per corner: the seam tables are built, the attribute walks may start
   // device memory of the lane, grown on demand and kept: hipMalloc / hipFree wait for every stream of the device, which would
   // put the chunks of a batch back in single file
-  struct Buf {
-    void *p = nullptr; uint64_t cap = 0;
-    hipError_t ensure(uint64_t bytes) {
-      if (bytes <= cap) return hipSuccess;
-      if (p) (void)hipFree(p);
-      p = nullptr; cap = 0;
-      const uint64_t want = bytes + bytes / 4;
-      hipError_t e = hipMalloc(&p, want);
-      if (e != hipSuccess) { (void)hipGetLastError(); p = nullptr; e = hipMalloc(&p, bytes); if (e == hipSuccess) cap = bytes; else p = nullptr; return e; }
-      cap = want;
-      return hipSuccess;
-    }
-    ~Buf() { if (p) (void)hipFree(p); }
-  } arena, streams, conns, seams, packed, items, repair, repair_recs, repair_ids, weld, weld_recs;      // (repair / weld: the arenas of the repair and weld kernels, dsa_encode_repair.h, dsa_encode_weld.h)
+  hostutil::DeviceBuf arena, streams, conns, seams, packed, items, repair, repair_recs, repair_ids, weld, weld_recs;      // (repair / weld: the arenas of the repair and weld kernels, dsa_encode_repair.h, dsa_encode_weld.h)
   ~EncLane() {
     if (walk_st) { (void)hipStreamSynchronize(walk_st); (void)hipStreamDestroy(walk_st); }
     if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
@@ -136,18 +123,19 @@ struct dsa_context {
   // staged into the other).
   hostutil::Staging stage[2];
   int stage_next = 0;
-  // Arenas and pinned mirrors of freed batches are kept for the next batch of the context: hipMalloc / hipFree of tens of GB and
-  // pinning GBs of host memory cost as much as the decode itself.  Three of each: two batches in flight + one being built.
-  struct Spare { uint8_t *p; uint64_t bytes; };
-  std::vector<Spare> spare_arenas, spare_mirrors, spare_descs, spare_packed;   // spare_descs: pinned landing zones of the mesh descriptors; spare_packed: packed blocks of compact downloads
-  std::vector<Spare> spare_vertex;   // device blocks of vertex arrays (dsa_batch_vertex_arrays)
-  static constexpr size_t kSpares = 3;
+  // The caches below, stage_next and next_set are touched by dsa_batch_create / _download / _free, which the pool calls from its
+  // worker threads and from whichever thread frees a job while the next decode runs (dsa_pool.h): one lock for all of them.
+  std::mutex mu;
+  // Arenas and pinned mirrors of freed batches are kept for the next batch of the context (dsa_spares.h).
+  spares::SpareCache spare_arenas{&mu, hostutil::kDeviceMem};
+  spares::SpareCache spare_packed{&mu, hostutil::kDeviceMem};     // packed blocks of compact downloads
+  spares::SpareCache spare_vertex{&mu, hostutil::kDeviceMem};     // device blocks of vertex arrays (dsa_batch_vertex_arrays)
+  spares::SpareCache spare_mirrors{&mu, hostutil::kPinnedMem};    // host copies of output blocks and vertex arrays
+  spares::SpareCache spare_descs{&mu, hostutil::kPinnedMem};      // landing zones of the mesh descriptors, staging of vertex-array tables
+  spares::SpareCache *const caches[5] = {&spare_arenas, &spare_packed, &spare_vertex, &spare_mirrors, &spare_descs};
   // batches point at their context: a context destroyed first lives on until its last batch is freed
   std::atomic<int> live_batches{0};
   std::atomic<bool> doomed{false};
-  // The caches above, stage_next and next_set are touched by dsa_batch_create / _download / _free, which the pool calls from its
-  // worker threads and from whichever thread frees a job while the next decode runs (dsa_pool.h): one lock for all of them.
-  std::mutex mu;
   std::vector<std::unique_ptr<EncLane>> enc_lanes;    // kept between dsa_encode_batch calls (pinning their staging costs more than a small batch)
   // k_register_gate holds the late symbol kernel back by asking for more registers than a SIMD has left beside four chain waves and
   // three entropy decoders.  That is occupancy arithmetic on THIS build's register counts: checked once per context (gate_check),
@@ -156,6 +144,10 @@ struct dsa_context {
   std::string gate_note;
   std::string sched_note;     // gate_note + what the context's most recent decode left out of the schedule (dsa_context_schedule_note)
 };
+
+// The host copy of a batch's output block or vertex arrays: the caller's buffer, or a pinned mirror of the library's from the
+// context's cache (place / release, below).
+struct HostCopy { uint8_t *p = nullptr; uint64_t bytes = 0; bool owned = false; };
 
 struct dsa_batch {
   dsa_context *ctx = nullptr;
@@ -203,14 +195,10 @@ struct dsa_batch {
   // per-batch ordering between the copy streams and the kernels (a second batch may be queued on the same context meanwhile,
   // so nothing here waits for a whole stream)
   hipEvent_t ev_uploaded = nullptr, ev_done = nullptr, ev_descs = nullptr, ev_down = nullptr;
-  MeshDesc *descs_pin = nullptr;     // pinned landing zone of the descriptors
+  uint8_t *descs_pin = nullptr;      // pinned landing zone of the descriptors
   uint64_t descs_pin_bytes = 0;
-  // host copy of the output block: a library-owned pinned mirror or the caller's buffer
-  uint8_t *mirror = nullptr;
-  uint64_t mirror_bytes = 0;
-  bool mirror_owned = false, download_queued = false, downloaded = false;
-  // meshes the fast kernels handed back (DSA_SITE_RETRY_GENERAL): decoded again through the general path in a batch
-  // of their own by dsa_batch_wait; every per-mesh accessor follows retry_index
+  HostCopy mirror;                   // host copy of the output block
+  bool download_queued = false, downloaded = false;
   // Vertex arrays (dsa_batch_vertex_arrays): a device block of their own [table of VaMesh | arrays], a pinned copy of the table, a
   // host copy of the arrays (library-owned pinned mirror or the caller's buffer) and an event of their own -- a download and vertex
   // arrays of one batch may be outstanding together.  The layout is made when the request arrives, from the host parse.
@@ -221,11 +209,12 @@ struct dsa_batch {
   uint64_t d_va_cap = 0;
   uint8_t *va_pin = nullptr;              // pinned staging of the table (from spare_descs)
   uint64_t va_pin_bytes = 0;
-  uint8_t *va_mirror = nullptr;
-  uint64_t va_mirror_bytes = 0;
-  bool va_mirror_owned = false, va_valid = false, va_queued = false, va_done = false;
+  HostCopy va_mirror;
+  bool va_valid = false, va_queued = false, va_done = false;
   hipEvent_t ev_va = nullptr;
   bool all_general = false;
+  // meshes the fast kernels handed back (DSA_SITE_RETRY_GENERAL): decoded again through the general path in a batch
+  // of their own by dsa_batch_wait; every per-mesh accessor follows retry_index (locate)
   dsa_batch *retry = nullptr;
   std::vector<int32_t> retry_index;
 };
@@ -250,51 +239,43 @@ dsa_status set_err(dsa_context *ctx, dsa_status st, const char *fmt, ...) {
                                          "%s failed: %s", #call, hipGetErrorString(e_));          \
   } while (0)
 
-// Arena / mirror caches of a context (see dsa_context).
-uint8_t *take_spare(dsa_context *ctx, std::vector<dsa_context::Spare> &spares, uint64_t need, uint64_t *got) {
-  std::lock_guard<std::mutex> g(ctx->mu);
-  int best = -1;
-  for (size_t k = 0; k < spares.size(); ++k)
-    if (spares[k].bytes >= need && (best < 0 || spares[k].bytes < spares[(size_t)best].bytes)) best = (int)k;
-  if (best < 0) return nullptr;
-  uint8_t *p = spares[(size_t)best].p;
-  *got = spares[(size_t)best].bytes;
-  spares.erase(spares.begin() + best);
-  return p;
+// A block for a batch from one of the context's caches, by the rules of dsa_spares.h; `what`: the text of a failure.
+dsa_status get_block(dsa_context *ctx, spares::SpareCache &cache, uint64_t need, spares::Grow grow, std::initializer_list<spares::SpareCache *> give_way,
+                     const char *what, uint8_t **p, uint64_t *cap) {
+  const spares::Acquired a = spares::acquire(cache, need, grow, give_way);
+  if (a.err) return set_err(ctx, DSA_ERR_OUT_OF_MEMORY, what, (unsigned long long)grow(need), hipGetErrorString((hipError_t)a.err));
+  *p = a.p; *cap = a.cap;
+  return DSA_OK;
 }
-template <class FreeFn>
-void give_spare(dsa_context *ctx, std::vector<dsa_context::Spare> &spares, uint8_t *p, uint64_t bytes, FreeFn release) {
-  if (!p) return;
-  std::lock_guard<std::mutex> g(ctx->mu);
-  try { spares.push_back({p, bytes}); } catch (...) { release(p); return; }
-  while (spares.size() > dsa_context::kSpares) {       // drop the smallest
-    size_t s = 0;
-    for (size_t k = 1; k < spares.size(); ++k) if (spares[k].bytes < spares[s].bytes) s = k;
-    release(spares[s].p);
-    spares.erase(spares.begin() + (ptrdiff_t)s);
+// The pinned zones of mesh descriptors and vertex-array tables have a cache of their own (hipHostMalloc / hipHostFree wait for the
+// device: with another batch in flight they would serialise the pipeline); nothing gives way for these few KB.
+const char *const kZoneText = "pinned descriptor zone of %llu bytes: %s";
+// Where a host copy of `need` bytes goes: the caller's `dst`, or a mirror of the library's -- the one the batch has, if large
+// enough, else one from the context's cache.  A mirror that is not used goes back to the cache.
+void release(dsa_context *ctx, HostCopy &h) {
+  if (h.owned) ctx->spare_mirrors.give(h.p, h.bytes);
+  h = HostCopy();
+}
+dsa_status place(dsa_context *ctx, HostCopy &h, void *dst, uint64_t dst_bytes, uint64_t need) {
+  if (!dst && h.owned && h.bytes >= need) return DSA_OK;
+  release(ctx, h);
+  if (dst) { h.p = (uint8_t *)dst; h.bytes = dst_bytes; return DSA_OK; }
+  const dsa_status st = get_block(ctx, ctx->spare_mirrors, need, spares::grow_floor256, {&ctx->spare_mirrors}, "pinned host mirror of %llu bytes: %s", &h.p, &h.bytes);
+  h.owned = st == DSA_OK;
+  return st;
+}
+// device -> host on the download stream, in pieces, so that a transfer of gigabytes does not hold the engine against the
+// descriptors of the batch behind it
+hipError_t copy_down(dsa_context *ctx, uint8_t *to, const uint8_t *from, uint64_t bytes) {
+  const uint64_t piece = 256ull << 20;
+  for (uint64_t at = 0; at < bytes; at += piece) {
+    const hipError_t e = hipMemcpyAsync(to + at, from + at, (size_t)std::min(piece, bytes - at), hipMemcpyDeviceToHost, ctx->down);
+    if (e != hipSuccess) return e;
   }
+  return hipSuccess;
 }
-void drop_spares(dsa_context *ctx, std::vector<dsa_context::Spare> &spares, bool pinned) {
-  std::lock_guard<std::mutex> g(ctx->mu);
-  for (auto &sp : spares) { if (pinned) (void)hipHostFree(sp.p); else (void)hipFree(sp.p); }
-  spares.clear();
-}
-hipError_t arena_alloc(dsa_context *ctx, uint64_t need, uint8_t **out, uint64_t *cap) {
-  if (uint8_t *p = take_spare(ctx, ctx->spare_arenas, need, cap)) { *out = p; return hipSuccess; }
-  hipError_t e = hipMalloc((void **)out, need);
-  if (e != hipSuccess) {     // what the context keeps idle may be what is in the way: spare arenas, then the encoder's lanes
-    (void)hipGetLastError();
-    drop_spares(ctx, ctx->spare_arenas, false);
-    e = hipMalloc((void **)out, need);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      { std::lock_guard<std::mutex> g(ctx->mu); ctx->enc_lanes.clear(); }
-      e = hipMalloc((void **)out, need);
-    }
-  }
-  *cap = need;
-  return e;
-}
+// the packed part of a compact host copy: [values sub-block | packed block]
+uint64_t packed_at(const dsa_batch *b) { return align_up(b->out_values_bytes, 4096); }
 
 // The launch flags the product schedule runs with (dsa_batch_decode), as the predicates of dsa_needs.h read them; OS_FLAG is added
 // per decode.  A -DDSA_EXPERIMENTS build varies them from the environment, and does not prune its schedule.
@@ -335,7 +316,7 @@ dsa_status build_batch(dsa_context *ctx, uint32_t n, const uint8_t *const *strea
   // Regions of every mesh behind the streams.  When the arena does not fit the device, the mesh with the largest
   // claim is set aside (per-mesh DSA_ERR_OUT_OF_MEMORY: a header may claim far more elements than its stream can
   // carry) and the rest is laid out again, so that one stream cannot take the batch down.
-  hipError_t e = hipSuccess;
+  int e = 0;
   std::vector<uint64_t> claim(n, 0);
   for (;;) {
     cur = scratch_begin;
@@ -386,16 +367,17 @@ dsa_status build_batch(dsa_context *ctx, uint32_t n, const uint8_t *const *strea
       for (uint32_t a = 0; a < L.cap_attributes; ++a) { L.out[a] += b->out_base + b->out_values; L.map[a] += b->out_base + out_maps; }
     }
     b->arena_bytes = b->out_base + align_up(b->out_bytes, 256) + 256;
-    e = arena_alloc(ctx, b->arena_bytes, &b->arena, &b->arena_cap);
-    if (e == hipSuccess) break;
-    (void)hipGetLastError();
-    b->arena = nullptr;
+    // what the context keeps idle may be what is in the way: spare arenas, then the encoder's lanes
+    const spares::Acquired got = spares::acquire(ctx->spare_arenas, b->arena_bytes, spares::grow_exact, {&ctx->spare_arenas},
+                                                 [ctx]() { std::lock_guard<std::mutex> g(ctx->mu); ctx->enc_lanes.clear(); });
+    b->arena = got.p; b->arena_cap = got.cap; e = got.err;
+    if (!e) break;
     uint32_t worst = 0;
     for (uint32_t i = 1; i < n; ++i) if (claim[i] > claim[worst]) worst = i;
     if (n == 0 || b->host[worst].status != 0 || claim[worst] <= (64ull << 20)) break;   // nothing left to set aside: the batch itself is too large
     b->host[worst].status = DSA_ERR_OUT_OF_MEMORY;
   }
-  if (e != hipSuccess) return set_err(ctx, DSA_ERR_OUT_OF_MEMORY, "hipMalloc of %llu-byte arena failed: %s", (unsigned long long)b->arena_bytes, hipGetErrorString(e));
+  if (e) return set_err(ctx, DSA_ERR_OUT_OF_MEMORY, "hipMalloc of %llu-byte arena failed: %s", (unsigned long long)b->arena_bytes, hipGetErrorString((hipError_t)e));
   {   // what the needs walk of every mesh asks of the schedule, now that the capacities the predicates read are placed
     for (int k = 0; k < 2; ++k) b->mesh_needs[k].assign(n, NEED_ALL);
     for (uint32_t i = 0; i < n; ++i) {         // (a few predicates per attribute: not worth threads)
@@ -434,13 +416,7 @@ dsa_status build_batch(dsa_context *ctx, uint32_t n, const uint8_t *const *strea
   HIP_TRY(ctx, hipEventCreateWithFlags(&b->ev_done, hipEventDisableTiming));
   HIP_TRY(ctx, hipEventCreateWithFlags(&b->ev_descs, hipEventDisableTiming));
   HIP_TRY(ctx, hipEventCreateWithFlags(&b->ev_down, hipEventDisableTiming));
-  {   // pinned landing zone of the descriptors, from the context's cache (hipHostMalloc / hipHostFree wait for the device: with
-      // another batch in flight they would serialise the pipeline)
-    const uint64_t need = sizeof(MeshDesc) * (uint64_t)(n ? n : 1);
-    uint8_t *p = take_spare(ctx, ctx->spare_descs, need, &b->descs_pin_bytes);
-    if (!p) { HIP_TRY(ctx, hipHostMalloc((void **)&p, need + need / 2, hipHostMallocDefault)); b->descs_pin_bytes = need + need / 2; }
-    b->descs_pin = (MeshDesc *)p;
-  }
+  if (dsa_status st = get_block(ctx, ctx->spare_descs, sizeof(MeshDesc) * (uint64_t)(n ? n : 1), spares::grow_half, {}, kZoneText, &b->descs_pin, &b->descs_pin_bytes)) return st;
   // ---- upload: layouts, globals and all streams staged in pinned memory (host threads), one DMA on the upload stream.  The
   // caller's buffers are not referenced once this function returns; the kernels wait for ev_uploaded, the host does not.
   {
@@ -565,11 +541,7 @@ void dsa_context_destroy(dsa_context *ctx) {
   (void)hipSetDevice(ctx->device);
   if (ctx->up) { (void)hipStreamSynchronize(ctx->up); (void)hipStreamDestroy(ctx->up); }
   if (ctx->down) { (void)hipStreamSynchronize(ctx->down); (void)hipStreamDestroy(ctx->down); }
-  drop_spares(ctx, ctx->spare_arenas, false);
-  drop_spares(ctx, ctx->spare_packed, false);
-  drop_spares(ctx, ctx->spare_vertex, false);
-  drop_spares(ctx, ctx->spare_mirrors, true);
-  drop_spares(ctx, ctx->spare_descs, true);
+  for (spares::SpareCache *c : ctx->caches) c->drop();
   for (StreamSet &set : ctx->sets) set.destroy();
   if (ctx->last_done) (void)hipEventDestroy(ctx->last_done);
   delete ctx;
@@ -1158,14 +1130,14 @@ void dsa_batch_free(dsa_batch *b) {
   if (b->ev_descs) { if (b->decoded) (void)hipEventSynchronize(b->ev_descs); (void)hipEventDestroy(b->ev_descs); }
   if (b->ev_down) { if (b->download_queued) (void)hipEventSynchronize(b->ev_down); (void)hipEventDestroy(b->ev_down); }
   if (b->ev_va) { if (b->va_queued) (void)hipEventSynchronize(b->ev_va); (void)hipEventDestroy(b->ev_va); }
-  give_spare(b->ctx, b->ctx->spare_descs, b->va_pin, b->va_pin_bytes, [](uint8_t *p) { (void)hipHostFree(p); });
-  if (b->va_mirror && b->va_mirror_owned) give_spare(b->ctx, b->ctx->spare_mirrors, b->va_mirror, b->va_mirror_bytes, [](uint8_t *p) { (void)hipHostFree(p); });
-  give_spare(b->ctx, b->ctx->spare_vertex, b->d_va, b->d_va_cap, [](uint8_t *p) { (void)hipFree(p); });
-  give_spare(b->ctx, b->ctx->spare_descs, (uint8_t *)b->descs_pin, b->descs_pin_bytes, [](uint8_t *p) { (void)hipHostFree(p); });
-  if (b->mirror && b->mirror_owned) give_spare(b->ctx, b->ctx->spare_mirrors, b->mirror, b->mirror_bytes, [](uint8_t *p) { (void)hipHostFree(p); });
-  give_spare(b->ctx, b->ctx->spare_arenas, b->arena, b->arena_cap, [](uint8_t *p) { (void)hipFree(p); });
-  give_spare(b->ctx, b->ctx->spare_packed, b->d_packed, b->d_packed_cap, [](uint8_t *p) { (void)hipFree(p); });
   dsa_context *ctx = b->ctx;
+  ctx->spare_descs.give(b->va_pin, b->va_pin_bytes);
+  release(ctx, b->va_mirror);
+  ctx->spare_vertex.give(b->d_va, b->d_va_cap);
+  ctx->spare_descs.give(b->descs_pin, b->descs_pin_bytes);
+  release(ctx, b->mirror);
+  ctx->spare_arenas.give(b->arena, b->arena_cap);
+  ctx->spare_packed.give(b->d_packed, b->d_packed_cap);
   delete b;
   bool last;
   { std::lock_guard<std::mutex> g(ctx->mu); last = --ctx->live_batches == 0 && ctx->doomed.load(); }
@@ -1191,14 +1163,13 @@ uint64_t dsa_batch_algorithmic_bytes(const dsa_batch *b) {
   return total;
 }
 
-// a mesh that was decoded again lives in the retry batch
-#define FOLLOW_RETRY(b, mesh, call)                                                                  \
-  if ((b) && (b)->retry && (mesh) < (b)->n && (b)->retry_index[mesh] >= 0) {                         \
-    const dsa_batch *rb_ = (b)->retry;                                                               \
-    const uint32_t rm_ = (uint32_t)(b)->retry_index[mesh];                                           \
-    (void)rb_; (void)rm_;                                                                            \
-    return call;                                                                                     \
-  }
+// Where a mesh's results are: in the batch itself (block 0), or, for a mesh that was decoded again, in the retry batch under its
+// index there (block 1).  Every per-mesh accessor locates, then checks, then answers.
+struct Located { const dsa_batch *b; uint32_t mesh; uint32_t block; };
+static Located locate(const dsa_batch *b, uint32_t mesh) {
+  if (b && b->retry && mesh < b->n && b->retry_index[mesh] >= 0) return {b->retry, (uint32_t)b->retry_index[mesh], 1u};
+  return {b, mesh, 0u};
+}
 #define CHECK_MESH(b, mesh)                                                                         \
   if (!(b)) return DSA_ERR_INVALID_ARGUMENT;                                                        \
   if (!(b)->collected) return set_err((b)->ctx, DSA_ERR_INVALID_ARGUMENT, "results not collected: call dsa_batch_wait"); \
@@ -1209,7 +1180,7 @@ uint64_t dsa_batch_algorithmic_bytes(const dsa_batch *b) {
   if ((a) >= (b)->descs[mesh].num_attributes) return set_err((b)->ctx, DSA_ERR_INVALID_ARGUMENT, "attribute index %u out of range", (unsigned)(a));
 
 dsa_status dsa_batch_mesh_info(const dsa_batch *b, uint32_t mesh, dsa_mesh_info *out) {
-  FOLLOW_RETRY(b, mesh, dsa_batch_mesh_info(rb_, rm_, out));
+  const Located at = locate(b, mesh); b = at.b; mesh = at.mesh;
   CHECK_MESH(b, mesh);
   if (!out) return DSA_ERR_INVALID_ARGUMENT;
   const MeshDesc &D = b->descs[mesh];
@@ -1224,7 +1195,7 @@ dsa_status dsa_batch_mesh_info(const dsa_batch *b, uint32_t mesh, dsa_mesh_info 
 }
 
 dsa_status dsa_batch_attribute_info(const dsa_batch *b, uint32_t mesh, uint32_t a, dsa_attribute_info *out) {
-  FOLLOW_RETRY(b, mesh, dsa_batch_attribute_info(rb_, rm_, a, out));
+  const Located at = locate(b, mesh); b = at.b; mesh = at.mesh;
   CHECK_ATTR(b, mesh, a);
   if (!out) return DSA_ERR_INVALID_ARGUMENT;
   const AttrDesc &A = b->descs[mesh].att[a];
@@ -1241,7 +1212,7 @@ static dsa_status copy_out(const dsa_batch *b, void *dst, uint64_t off, uint64_t
   if (!dst) return DSA_ERR_INVALID_ARGUMENT;
   if (bytes == 0) return DSA_OK;
   if (b->downloaded && !b->mirror_compact && off >= b->out_base && off + bytes <= b->out_base + b->out_bytes) {     // already on the host
-    memcpy(dst, b->mirror + (off - b->out_base), (size_t)bytes);
+    memcpy(dst, b->mirror.p + (off - b->out_base), (size_t)bytes);
     return DSA_OK;
   }
   HIP_TRY(b->ctx, hipSetDevice(b->ctx->device));
@@ -1250,13 +1221,13 @@ static dsa_status copy_out(const dsa_batch *b, void *dst, uint64_t off, uint64_t
 }
 
 dsa_status dsa_batch_copy_faces(const dsa_batch *b, uint32_t mesh, int32_t *dst) {
-  FOLLOW_RETRY(b, mesh, dsa_batch_copy_faces(rb_, rm_, dst));
+  const Located at = locate(b, mesh); b = at.b; mesh = at.mesh;
   CHECK_MESH(b, mesh);
   if (b->descs[mesh].status != ST_OK) return set_err(b->ctx, (dsa_status)b->descs[mesh].status, "mesh %u failed to decode", mesh);
   if (b->downloaded && b->mirror_compact) {          // from the packed host copy: widened
     if (!dst) return DSA_ERR_INVALID_ARGUMENT;
     const CompactMesh &c = b->compact[mesh];
-    const uint8_t *src = b->mirror + align_up(b->out_values_bytes, 4096) + c.faces;
+    const uint8_t *src = b->mirror.p + packed_at(b) + c.faces;
     const size_t ncorn = 3ull * b->descs[mesh].num_faces;
     if (c.u16) for (size_t i = 0; i < ncorn; ++i) dst[i] = (int32_t)((const uint16_t *)src)[i];
     else memcpy(dst, src, 4 * ncorn);
@@ -1265,31 +1236,31 @@ dsa_status dsa_batch_copy_faces(const dsa_batch *b, uint32_t mesh, int32_t *dst)
   return copy_out(b, dst, b->layouts[mesh].faces, 12ull * b->descs[mesh].num_faces);
 }
 dsa_status dsa_batch_copy_attribute_values(const dsa_batch *b, uint32_t mesh, uint32_t a, void *dst) {
-  FOLLOW_RETRY(b, mesh, dsa_batch_copy_attribute_values(rb_, rm_, a, dst));
+  const Located at = locate(b, mesh); b = at.b; mesh = at.mesh;
   CHECK_ATTR(b, mesh, a);
   const AttrDesc &A = b->descs[mesh].att[a];
   if (b->downloaded && b->mirror_compact) {          // the values sub-block heads the compact host copy
     if (!dst) return DSA_ERR_INVALID_ARGUMENT;
-    memcpy(dst, b->mirror + (b->layouts[mesh].out[a] - b->out_base - b->out_values), (size_t)A.num_entries * A.nc * dt_len(A.data_type));
+    memcpy(dst, b->mirror.p + (b->layouts[mesh].out[a] - b->out_base - b->out_values), (size_t)A.num_entries * A.nc * dt_len(A.data_type));
     return DSA_OK;
   }
   return copy_out(b, dst, b->layouts[mesh].out[a], (uint64_t)A.num_entries * A.nc * dt_len(A.data_type));
 }
 dsa_status dsa_batch_copy_point_map(const dsa_batch *b, uint32_t mesh, uint32_t a, uint32_t *dst) {
-  FOLLOW_RETRY(b, mesh, dsa_batch_copy_point_map(rb_, rm_, a, dst));
+  const Located at = locate(b, mesh); b = at.b; mesh = at.mesh;
   CHECK_ATTR(b, mesh, a);
   if (b->downloaded && b->mirror_compact) {
     if (!dst) return DSA_ERR_INVALID_ARGUMENT;
     const CompactMesh &c = b->compact[mesh];
     const uint32_t npts = b->descs[mesh].num_points;
     if (c.map[a] == ~0ull) for (uint32_t p = 0; p < npts; ++p) dst[p] = p;
-    else memcpy(dst, b->mirror + align_up(b->out_values_bytes, 4096) + c.map[a], 4ull * npts);
+    else memcpy(dst, b->mirror.p + packed_at(b) + c.map[a], 4ull * npts);
     return DSA_OK;
   }
   return copy_out(b, dst, b->layouts[mesh].map[a], 4ull * b->descs[mesh].num_points);
 }
 dsa_status dsa_batch_copy_portable_values(const dsa_batch *b, uint32_t mesh, uint32_t a, int32_t *dst) {
-  FOLLOW_RETRY(b, mesh, dsa_batch_copy_portable_values(rb_, rm_, a, dst));
+  const Located at = locate(b, mesh); b = at.b; mesh = at.mesh;
   CHECK_ATTR(b, mesh, a);
   const AttrDesc &A = b->descs[mesh].att[a];
   if (A.source == SRC_BYTES) return set_err(b->ctx, DSA_ERR_INVALID_ARGUMENT, "generic attributes have no portable form");
@@ -1297,17 +1268,17 @@ dsa_status dsa_batch_copy_portable_values(const dsa_batch *b, uint32_t mesh, uin
 }
 
 const int32_t *dsa_batch_device_faces(const dsa_batch *b, uint32_t mesh) {
-  FOLLOW_RETRY(b, mesh, dsa_batch_device_faces(rb_, rm_));
+  const Located at = locate(b, mesh); b = at.b; mesh = at.mesh;
   if (!b || mesh >= b->n || !b->collected || b->descs[mesh].status != ST_OK) return nullptr;
   return (const int32_t *)(b->arena + b->layouts[mesh].faces);
 }
 const void *dsa_batch_device_attribute_values(const dsa_batch *b, uint32_t mesh, uint32_t a) {
-  FOLLOW_RETRY(b, mesh, dsa_batch_device_attribute_values(rb_, rm_, a));
+  const Located at = locate(b, mesh); b = at.b; mesh = at.mesh;
   if (!b || mesh >= b->n || !b->collected || b->descs[mesh].status != ST_OK || a >= b->descs[mesh].num_attributes) return nullptr;
   return b->arena + b->layouts[mesh].out[a];
 }
 const uint32_t *dsa_batch_device_point_map(const dsa_batch *b, uint32_t mesh, uint32_t a) {
-  FOLLOW_RETRY(b, mesh, dsa_batch_device_point_map(rb_, rm_, a));
+  const Located at = locate(b, mesh); b = at.b; mesh = at.mesh;
   if (!b || mesh >= b->n || !b->collected || b->descs[mesh].status != ST_OK || a >= b->descs[mesh].num_attributes) return nullptr;
   return (const uint32_t *)(b->arena + b->layouts[mesh].map[a]);
 }
@@ -1315,17 +1286,8 @@ const uint32_t *dsa_batch_device_point_map(const dsa_batch *b, uint32_t mesh, ui
 // ---- whole-batch results on the host: one transfer of the output block
 uint64_t dsa_batch_output_bytes(const dsa_batch *b) { return b ? b->out_bytes : 0; }
 
-uint64_t dsa_batch_compact_bytes(const dsa_batch *b) { return b ? align_up(b->out_values_bytes, 4096) + b->packed_bytes : 0; }
+uint64_t dsa_batch_compact_bytes(const dsa_batch *b) { return b ? packed_at(b) + b->packed_bytes : 0; }
 
-static dsa_status batch_download(dsa_batch *b, void *dst, size_t dst_bytes, bool compact);
-dsa_status dsa_batch_download(dsa_batch *b, void *dst, size_t dst_bytes) {
-  if (!b) return DSA_ERR_INVALID_ARGUMENT;
-  DSA_GUARD(b->ctx, batch_download(b, dst, dst_bytes, false));
-}
-dsa_status dsa_batch_download_compact(dsa_batch *b, void *dst, size_t dst_bytes) {
-  if (!b) return DSA_ERR_INVALID_ARGUMENT;
-  DSA_GUARD(b->ctx, batch_download(b, dst, dst_bytes, true));
-}
 static dsa_status batch_download(dsa_batch *b, void *dst, size_t dst_bytes, bool compact) {
   dsa_context *ctx = b->ctx;
   if (!b->decoded) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "dsa_batch_decode was not called");
@@ -1333,43 +1295,11 @@ static dsa_status batch_download(dsa_batch *b, void *dst, size_t dst_bytes, bool
   const uint64_t host_bytes = compact ? dsa_batch_compact_bytes(b) : b->out_bytes;
   if (dst && dst_bytes < host_bytes) return set_err(ctx, DSA_ERR_INVALID_ARGUMENT, "destination smaller than the host copy (dsa_batch_output_bytes / dsa_batch_compact_bytes)");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (compact && !b->d_packed && b->packed_bytes) {     // the packed block: from the context's cache, like arenas
-    uint64_t cap = 0;
-    uint8_t *p = take_spare(ctx, ctx->spare_packed, b->packed_bytes, &cap);
-    if (!p) {
-      hipError_t e = hipMalloc((void **)&p, b->packed_bytes);
-      if (e != hipSuccess) { (void)hipGetLastError(); drop_spares(ctx, ctx->spare_packed, false); drop_spares(ctx, ctx->spare_arenas, false); e = hipMalloc((void **)&p, b->packed_bytes); }
-      if (e != hipSuccess) { (void)hipGetLastError(); return set_err(ctx, DSA_ERR_OUT_OF_MEMORY, "packed block of %llu bytes: %s", (unsigned long long)b->packed_bytes, hipGetErrorString(e)); }
-      cap = b->packed_bytes;
-    }
-    b->d_packed = p; b->d_packed_cap = cap;
-  }
-  if (b->mirror && b->mirror_owned && dst) { give_spare(ctx, ctx->spare_mirrors, b->mirror, b->mirror_bytes, [](uint8_t *p) { (void)hipHostFree(p); }); b->mirror = nullptr; }
-  if (dst) { b->mirror = (uint8_t *)dst; b->mirror_bytes = dst_bytes; b->mirror_owned = false; }
-  else if (!b->mirror || !b->mirror_owned || b->mirror_bytes < host_bytes) {
-    if (b->mirror && b->mirror_owned) { give_spare(ctx, ctx->spare_mirrors, b->mirror, b->mirror_bytes, [](uint8_t *p) { (void)hipHostFree(p); }); b->mirror = nullptr; }
-    const uint64_t need = host_bytes ? host_bytes : 256;
-    uint64_t got = 0;
-    uint8_t *p = take_spare(ctx, ctx->spare_mirrors, need, &got);
-    if (!p) {
-      hipError_t e = hipHostMalloc((void **)&p, need, hipHostMallocDefault);
-      if (e != hipSuccess) { (void)hipGetLastError(); drop_spares(ctx, ctx->spare_mirrors, true); e = hipHostMalloc((void **)&p, need, hipHostMallocDefault); }
-      if (e != hipSuccess) { (void)hipGetLastError(); return set_err(ctx, DSA_ERR_OUT_OF_MEMORY, "pinned host mirror of %llu bytes: %s", (unsigned long long)need, hipGetErrorString(e)); }
-      got = need;
-    }
-    b->mirror = p; b->mirror_bytes = got; b->mirror_owned = true;
-  }
+  if (compact && !b->d_packed && b->packed_bytes)       // the packed block: from the context's cache, like arenas
+    if (dsa_status st = get_block(ctx, ctx->spare_packed, b->packed_bytes, spares::grow_exact, {&ctx->spare_packed, &ctx->spare_arenas}, "packed block of %llu bytes: %s", &b->d_packed, &b->d_packed_cap)) return st;
+  if (dsa_status st = place(ctx, b->mirror, dst, dst_bytes, host_bytes)) return st;
   HIP_TRY(ctx, hipStreamWaitEvent(ctx->down, b->ev_done, 0));
-  // in pieces, so that a transfer of gigabytes does not hold the engine against the descriptors of the batch behind it
-  const uint64_t piece = 256ull << 20;
-  auto copy_down = [&](uint8_t *to, const uint8_t *from, uint64_t bytes) -> hipError_t {
-    for (uint64_t at = 0; at < bytes; at += piece) {
-      const hipError_t e = hipMemcpyAsync(to + at, from + at, (size_t)std::min(piece, bytes - at), hipMemcpyDeviceToHost, ctx->down);
-      if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-  };
-  if (!compact) HIP_TRY(ctx, copy_down(b->mirror, b->arena + b->out_base, b->out_bytes));
+  if (!compact) HIP_TRY(ctx, copy_down(ctx, b->mirror.p, b->arena + b->out_base, b->out_bytes));
   else {
     // the values as they are; faces and point maps packed by a kernel on the download stream (the copy of the values runs beside it)
     if (b->n && b->packed_bytes) {
@@ -1380,8 +1310,8 @@ static dsa_status batch_download(dsa_batch *b, void *dst, size_t dst_bytes, bool
       if (timed) { (void)hipEventRecord(b->ev_k[KT_PACK_OUTPUT][1], ctx->down); b->k_timed[KT_PACK_OUTPUT] = true; }
       HIP_TRY(ctx, hipGetLastError());
     }
-    HIP_TRY(ctx, copy_down(b->mirror, b->arena + b->out_base + b->out_values, b->out_values_bytes));
-    HIP_TRY(ctx, copy_down(b->mirror + align_up(b->out_values_bytes, 4096), b->d_packed, b->packed_bytes));
+    HIP_TRY(ctx, copy_down(ctx, b->mirror.p, b->arena + b->out_base + b->out_values, b->out_values_bytes));
+    HIP_TRY(ctx, copy_down(ctx, b->mirror.p + packed_at(b), b->d_packed, b->packed_bytes));
   }
   HIP_TRY(ctx, hipEventRecord(b->ev_down, ctx->down));
   b->download_queued = true;
@@ -1390,25 +1320,33 @@ static dsa_status batch_download(dsa_batch *b, void *dst, size_t dst_bytes, bool
   if (b->retry && !b->retry->download_queued) return dsa_batch_download(b->retry, nullptr, 0);   // block 1: the meshes decoded a second time (always the full layout)
   return DSA_OK;
 }
+dsa_status dsa_batch_download(dsa_batch *b, void *dst, size_t dst_bytes) {
+  if (!b) return DSA_ERR_INVALID_ARGUMENT;
+  DSA_GUARD(b->ctx, batch_download(b, dst, dst_bytes, false));
+}
+dsa_status dsa_batch_download_compact(dsa_batch *b, void *dst, size_t dst_bytes) {
+  if (!b) return DSA_ERR_INVALID_ARGUMENT;
+  DSA_GUARD(b->ctx, batch_download(b, dst, dst_bytes, true));
+}
 
 const void *dsa_batch_host_output(const dsa_batch *b, uint32_t block) {
   if (!b || !b->downloaded) return nullptr;
-  if (block == 0) return b->mirror;
-  if (block == 1 && b->retry && b->retry->downloaded) return b->retry->mirror;
+  if (block == 0) return b->mirror.p;
+  if (block == 1 && b->retry && b->retry->downloaded) return b->retry->mirror.p;
   return nullptr;
 }
 
 dsa_status dsa_batch_output_layout(const dsa_batch *b, uint32_t mesh, dsa_mesh_output *out) {
-  CHECK_MESH(b, mesh);
+  const Located at = locate(b, mesh);
+  const dsa_batch *src = at.b; const uint32_t m = at.mesh;
+  CHECK_MESH(src, m);
   if (!out) return DSA_ERR_INVALID_ARGUMENT;
   memset(out, 0, sizeof(*out));
-  const dsa_batch *src = b;
-  uint32_t m = mesh;
-  if (b->retry && b->retry_index[mesh] >= 0) { src = b->retry; m = (uint32_t)b->retry_index[mesh]; out->block = 1; }
+  out->block = at.block;
   const MeshLayout &L = src->layouts[m];
   if (src->mirror_compact && src->download_queued) {       // the host copy of a compact download: [values sub-block | packed block]
     const CompactMesh &c = src->compact[m];
-    const uint64_t pk = align_up(src->out_values_bytes, 4096);
+    const uint64_t pk = packed_at(src);
     out->flags = c.u16 ? DSA_OUTPUT_FACES_U16 : 0u;
     out->faces = pk + c.faces;
     for (uint32_t a = 0; a < L.cap_attributes && a < DSA_MAX_ATTRIBUTES; ++a) {
@@ -1471,45 +1409,16 @@ static dsa_status batch_vertex_arrays(dsa_batch *b, const dsa_vertex_request *re
   const uint64_t table_bytes = align_up(sizeof(VaMesh) * (uint64_t)(b->n ? b->n : 1), 256);
   const uint64_t need = table_bytes + (bytes ? bytes : 256);
   if (!b->d_va || b->d_va_cap < need) {                      // the device block: from the context's cache, like the packed block
-    give_spare(ctx, ctx->spare_vertex, b->d_va, b->d_va_cap, [](uint8_t *p) { (void)hipFree(p); });
+    ctx->spare_vertex.give(b->d_va, b->d_va_cap);
     b->d_va = nullptr; b->d_va_cap = 0;
-    uint64_t cap = 0;
-    uint8_t *p = take_spare(ctx, ctx->spare_vertex, need, &cap);
-    if (!p) {
-      hipError_t e = hipMalloc((void **)&p, need);
-      if (e != hipSuccess) { (void)hipGetLastError(); drop_spares(ctx, ctx->spare_vertex, false); drop_spares(ctx, ctx->spare_packed, false); drop_spares(ctx, ctx->spare_arenas, false); e = hipMalloc((void **)&p, need); }
-      if (e != hipSuccess) { (void)hipGetLastError(); return set_err(ctx, DSA_ERR_OUT_OF_MEMORY, "vertex-array block of %llu bytes: %s", (unsigned long long)need, hipGetErrorString(e)); }
-      cap = need;
-    }
-    b->d_va = p; b->d_va_cap = cap;
+    if (dsa_status st = get_block(ctx, ctx->spare_vertex, need, spares::grow_exact, {&ctx->spare_vertex, &ctx->spare_packed, &ctx->spare_arenas}, "vertex-array block of %llu bytes: %s", &b->d_va, &b->d_va_cap)) return st;
   }
   if (!b->va_pin || b->va_pin_bytes < table_bytes) {         // pinned staging of the table, from the cache of descriptor zones
-    give_spare(ctx, ctx->spare_descs, b->va_pin, b->va_pin_bytes, [](uint8_t *p) { (void)hipHostFree(p); });
+    ctx->spare_descs.give(b->va_pin, b->va_pin_bytes);
     b->va_pin = nullptr; b->va_pin_bytes = 0;
-    uint8_t *p = take_spare(ctx, ctx->spare_descs, table_bytes, &b->va_pin_bytes);
-    if (!p) { HIP_TRY(ctx, hipHostMalloc((void **)&p, table_bytes, hipHostMallocDefault)); b->va_pin_bytes = table_bytes; }
-    b->va_pin = p;
+    if (dsa_status st = get_block(ctx, ctx->spare_descs, table_bytes, spares::grow_exact, {}, kZoneText, &b->va_pin, &b->va_pin_bytes)) return st;
   }
-  if (to_host) {                                             // the host copy: the caller's memory or a pinned mirror of the library's
-    auto release = [](uint8_t *p) { (void)hipHostFree(p); };
-    if (dst) {
-      if (b->va_mirror && b->va_mirror_owned) give_spare(ctx, ctx->spare_mirrors, b->va_mirror, b->va_mirror_bytes, release);
-      b->va_mirror = (uint8_t *)dst; b->va_mirror_bytes = dst_bytes; b->va_mirror_owned = false;
-    } else if (!b->va_mirror || !b->va_mirror_owned || b->va_mirror_bytes < bytes) {
-      if (b->va_mirror && b->va_mirror_owned) give_spare(ctx, ctx->spare_mirrors, b->va_mirror, b->va_mirror_bytes, release);
-      b->va_mirror = nullptr;
-      const uint64_t want = bytes ? bytes : 256;
-      uint64_t got = 0;
-      uint8_t *p = take_spare(ctx, ctx->spare_mirrors, want, &got);
-      if (!p) {
-        hipError_t e = hipHostMalloc((void **)&p, want, hipHostMallocDefault);
-        if (e != hipSuccess) { (void)hipGetLastError(); drop_spares(ctx, ctx->spare_mirrors, true); e = hipHostMalloc((void **)&p, want, hipHostMallocDefault); }
-        if (e != hipSuccess) { (void)hipGetLastError(); return set_err(ctx, DSA_ERR_OUT_OF_MEMORY, "pinned host mirror of %llu bytes: %s", (unsigned long long)want, hipGetErrorString(e)); }
-        got = want;
-      }
-      b->va_mirror = p; b->va_mirror_bytes = got; b->va_mirror_owned = true;
-    }
-  }
+  if (to_host) if (dsa_status st = place(ctx, b->va_mirror, dst, dst_bytes, bytes)) return st;
   b->va.swap(table);
   b->va_req = req; b->va_bytes = bytes; b->va_table_bytes = table_bytes;
   // the table goes up on the download stream (nothing of the decode stands in front of it there), then the kernel behind the decode
@@ -1528,11 +1437,7 @@ static dsa_status batch_vertex_arrays(dsa_batch *b, const dsa_vertex_request *re
     hipLaunchKernelGGL(dsa::k_vertex_arrays, dim3(gx, b->n), dim3(VA_CHUNK), 0, ctx->down, b->arena, b->d_layouts, b->d_descs, b->n, (const VaMesh *)b->d_va, b->d_va + table_bytes);
     if (timed) { (void)hipEventRecord(b->ev_k[KT_VERTEX_ARRAYS][1], ctx->down); b->k_timed[KT_VERTEX_ARRAYS] = true; }
     HIP_TRY(ctx, hipGetLastError());
-    if (to_host) {
-      const uint64_t piece = 256ull << 20;                   // in pieces, as the download: the engine stays available to the batch behind
-      for (uint64_t at = 0; at < bytes; at += piece)
-        HIP_TRY(ctx, hipMemcpyAsync(b->va_mirror + at, b->d_va + table_bytes + at, (size_t)std::min(piece, bytes - at), hipMemcpyDeviceToHost, ctx->down));
-    }
+    if (to_host) HIP_TRY(ctx, copy_down(ctx, b->va_mirror.p, b->d_va + table_bytes, bytes));
   }
   HIP_TRY(ctx, hipEventRecord(b->ev_va, ctx->down));
   b->va_valid = true; b->va_queued = true; b->va_done = false;
@@ -1547,7 +1452,7 @@ dsa_status dsa_batch_vertex_arrays(dsa_batch *b, const dsa_vertex_request *reque
 const void *dsa_batch_host_vertex_arrays(const dsa_batch *b, uint32_t block) {
   if (!b || !b->va_valid || !b->va_done) return nullptr;
   if (block == 1) return b->retry ? dsa_batch_host_vertex_arrays(b->retry, 0) : nullptr;
-  return block == 0 && !(b->va_req.flags & DSA_VA_DEVICE_ONLY) ? b->va_mirror : nullptr;
+  return block == 0 && !(b->va_req.flags & DSA_VA_DEVICE_ONLY) ? b->va_mirror.p : nullptr;
 }
 const void *dsa_batch_device_vertex_arrays(const dsa_batch *b, uint32_t block) {
   if (!b || !b->va_valid) return nullptr;
@@ -1556,12 +1461,12 @@ const void *dsa_batch_device_vertex_arrays(const dsa_batch *b, uint32_t block) {
 }
 
 dsa_status dsa_batch_vertex_arrays_layout(const dsa_batch *b, uint32_t mesh, dsa_mesh_vertex_arrays *out) {
-  CHECK_MESH(b, mesh);
+  const Located at = locate(b, mesh);
+  const dsa_batch *src = at.b; const uint32_t m = at.mesh;
+  CHECK_MESH(src, m);
   if (!out) return DSA_ERR_INVALID_ARGUMENT;
   memset(out, 0, sizeof(*out));
-  const dsa_batch *src = b;
-  uint32_t m = mesh;
-  if (b->retry && b->retry_index[mesh] >= 0) { src = b->retry; m = (uint32_t)b->retry_index[mesh]; out->block = 1; }
+  out->block = at.block;
   if (!src->va_valid || m >= src->va.size()) return set_err(b->ctx, DSA_ERR_INVALID_ARGUMENT, "no vertex arrays were requested since the batch was decoded");
   const MeshDesc &D = src->descs[m];
   if (D.status != ST_OK) return set_err(b->ctx, (dsa_status)D.status, "mesh %u failed to decode", (unsigned)mesh);
@@ -1602,7 +1507,7 @@ dsa_status dsa_host_unregister(void *p) {
 }
 
 dsa_status dsa_batch_copy_metadata(const dsa_batch *b, uint32_t mesh, uint8_t *dst, size_t dst_bytes, size_t *length) {
-  FOLLOW_RETRY(b, mesh, dsa_batch_copy_metadata(rb_, rm_, dst, dst_bytes, length));
+  const Located at = locate(b, mesh); b = at.b; mesh = at.mesh;
   if (!b || mesh >= b->n || !length) return DSA_ERR_INVALID_ARGUMENT;
   const HostMesh &h = b->host[mesh];
   *length = h.meta_len;
@@ -1627,7 +1532,7 @@ dsa_status dsa_batch_copy_debug(const dsa_batch *b, uint32_t mesh, int what, voi
     }
     return DSA_OK;
   }
-  FOLLOW_RETRY(b, mesh, dsa_batch_copy_debug(rb_, rm_, what, dst, dst_bytes, written));
+  const Located at = locate(b, mesh); b = at.b; mesh = at.mesh;
   CHECK_MESH(b, mesh);
   const MeshDesc &D = b->descs[mesh];
   if (D.status != ST_OK && what != 4) return set_err(b->ctx, (dsa_status)D.status, "mesh %u failed to decode", mesh);
@@ -1711,11 +1616,7 @@ const char *dsa_context_schedule_note(const dsa_context *ctx) { return ctx ? (ct
 dsa_status dsa_context_trim(dsa_context *ctx) {
   if (!ctx) return DSA_ERR_INVALID_ARGUMENT;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  drop_spares(ctx, ctx->spare_arenas, false);
-  drop_spares(ctx, ctx->spare_packed, false);
-  drop_spares(ctx, ctx->spare_vertex, false);
-  drop_spares(ctx, ctx->spare_mirrors, true);
-  drop_spares(ctx, ctx->spare_descs, true);
+  for (spares::SpareCache *c : ctx->caches) c->drop();
   { std::lock_guard<std::mutex> g(ctx->mu); ctx->enc_lanes.clear(); }      // dsa_encode_batch is synchronous: its lanes are idle between calls
   return DSA_OK;
 }

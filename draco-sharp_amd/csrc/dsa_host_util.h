@@ -19,6 +19,8 @@
 #include <thread>
 #include <vector>
 
+#include "dsa_spares.h"
+
 namespace hostutil {
 
 // Threads a call may start: the cores this process may run on (a rank of an 8-process job sees its share when the launcher pins
@@ -94,12 +96,22 @@ inline void parallel_memcpy(void *dst, const void *src, size_t bytes) {
 // Owners: released on every exit path of the function that holds them.
 struct DeviceBuf {
   void *p = nullptr;
+  uint64_t cap = 0;
   DeviceBuf() = default;
   DeviceBuf(const DeviceBuf &) = delete;
   DeviceBuf &operator=(const DeviceBuf &) = delete;
   ~DeviceBuf() { reset(); }
-  void reset() { if (p) (void)hipFree(p); p = nullptr; }
-  hipError_t alloc(size_t bytes) { reset(); return hipMalloc(&p, bytes ? bytes : 256); }
+  void reset() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+  // at least `bytes`, contents not kept; grows by a quarter, and settles for exactly `bytes` where that much is not to be had
+  hipError_t ensure(uint64_t bytes) {
+    if (bytes <= cap) return hipSuccess;
+    reset();
+    const uint64_t want = bytes + bytes / 4;
+    hipError_t e = hipMalloc(&p, want);
+    if (e != hipSuccess) { (void)hipGetLastError(); p = nullptr; e = hipMalloc(&p, bytes); if (e == hipSuccess) cap = bytes; else p = nullptr; return e; }
+    cap = want;
+    return hipSuccess;
+  }
   template <class T> T *as() const { return (T *)p; }
 };
 struct PinnedBuf {
@@ -121,6 +133,14 @@ struct PinnedBuf {
     return hipSuccess;
   }
 };
+
+// The two allocators behind the context's caches (dsa_spares.h).  A failed allocation leaves no sticky error behind: the next
+// hipGetLastError() check behind a kernel launch would report it.
+inline int device_alloc(void **p, uint64_t bytes) { const hipError_t e = hipMalloc(p, bytes); if (e != hipSuccess) (void)hipGetLastError(); return (int)e; }
+inline int pinned_alloc(void **p, uint64_t bytes) { const hipError_t e = hipHostMalloc(p, bytes, hipHostMallocDefault); if (e != hipSuccess) (void)hipGetLastError(); return (int)e; }
+inline void device_release(void *p) { (void)hipFree(p); }
+inline void pinned_release(void *p) { (void)hipHostFree(p); }
+constexpr spares::Backend kDeviceMem{device_alloc, device_release}, kPinnedMem{pinned_alloc, pinned_release};
 
 // A pinned staging buffer with the event that says when the DMA reading it has finished: the next user waits for that
 // event instead of for the stream.
