@@ -61,6 +61,16 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
     /// colour with a hard edge then cuts its own connectivity only.  An attribute past index 7 of the stream stays in the key.
     /// Unset: nothing changes.</summary>
     public bool WeldAttributes { get; set; }
+    // TrackRows (dsa_encode_rows_batch, track_rows = 1): the encoder keeps, per stream and attribute, which row of the input every
+    // entry of the stream carries -- the value index in the form the encoder is given (an attribute's own MappedIndex where it goes
+    // per corner, the positions' where it goes per vertex), with WeldPoints the point of the per-point input; sequential streams and point clouds: the identity.  EntryRows(i) returns them
+    // after Encode.  The streams are the bytes they are without it.  What carries morph targets across the weld and Edgebreaker's
+    // renumbering.
+    public bool TrackRows { get; set; }
+    private uint[][][] _entryRows;
+    // Of stream i of the most recent Encode with TrackRows: per attribute of the stream (positions, then normals, texture coordinates,
+    // generic where present, then the others) the row of the input every entry carries.
+    public uint[][] EntryRows(int i) => _entryRows != null && i >= 0 && i < _entryRows.Length ? _entryRows[i] : throw new InvalidOperationException("no entry rows: set TrackRows before Encode");
 
     /// <summary>In corner form: an attribute beyond the built-in slots whose point-to-value map differs from the positions' keeps its
     /// own values, with an id per corner taken from that map (dsa_encode_corner_attributes_batch), instead of one value per position
@@ -214,6 +224,7 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
         if (SpeedLadder && config.Speed == 0) traversal = 1;
         if (RepairSeams && !RepairTopology) throw new ArgumentException("RepairSeams codes attributes over the repaired corner table: it needs RepairTopology");
         if (WeldAttributes && !WeldPoints) throw new ArgumentException("WeldAttributes welds the attributes of per-point input each alone: it needs WeldPoints");
+        _entryRows = null;
         var inputs = new DsaMeshInput[meshes.Count];
         var pins = new List<GCHandle>();
         IntPtr encoded = IntPtr.Zero;
@@ -248,13 +259,22 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
                 wp.Topology = RepairTopology ? 1 : 0;
                 var wg = Grids(config, meshes.Count);
                 if (wg != null) for (int i = 0; i < meshes.Count; ++i) if (pin[i].Mesh.Mesh.Texcoords == null) wg[i].Texcoord = default;
-                if (WeldAttributes)
+                if (WeldAttributes || TrackRows)
                 {
                     NativeMethods.dsa_encode_default_corner_attributes_options(out var co);
                     co.SeamRepair.Grid.Repair = wp;
                     co.SeamRepair.Grid.WeldPoints = 1;
                     co.SeamRepair.CornerRepair = RepairSeams ? 1 : 0;
-                    co.WeldAttributes = 1;
+                    if (WeldAttributes) co.WeldAttributes = 1;
+                    if (TrackRows)
+                    {
+                        NativeMethods.dsa_encode_default_rows_options(out var ro);
+                        ro.CornerAttributes = co;
+                        ro.TrackRows = 1;
+                        fixed (DsaMeshAttrInput* p = pin) fixed (DsaMeshGrids* g = wg)
+                            NativeMethods.Check(NativeMethods.dsa_encode_rows_batch(_ctx, (uint)meshes.Count, p, g, null, in ro, out encoded), _ctx, "dsa_encode_rows_batch");
+                        return Streams(encoded, meshes.Count);
+                    }
                     fixed (DsaMeshAttrInput* p = pin) fixed (DsaMeshGrids* g = wg)
                         NativeMethods.Check(NativeMethods.dsa_encode_corner_attributes_batch(_ctx, (uint)meshes.Count, p, g, null, in co, out encoded), _ctx, "dsa_encode_corner_attributes_batch");
                     return Streams(encoded, meshes.Count);
@@ -285,7 +305,7 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
             bool anyCorners = false, anyExtras = false;
             foreach (var m in meshes) { anyCorners = anyCorners || NeedsCornerForm(m); anyExtras = anyExtras || ExtraAttributes(m).Count > 0; }
             var grids = Grids(config, meshes.Count);
-            if (anyExtras || multi != 0 || traversal != 0 || RepairTopology || grids != null)
+            if (anyExtras || multi != 0 || traversal != 0 || RepairTopology || grids != null || TrackRows)
             {
                 // the attribute list rides on the corner form (extras per vertex: the value of the last point of each position value)
                 var ain = new DsaMeshAttrInput[meshes.Count];
@@ -302,7 +322,7 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
                 ax.EdgebreakerMethod = ebMethod != unset ? ebMethod : 0;
                 ax.NormalPrediction = normalScheme != unset ? normalScheme : 0;
                 if (grids != null) for (int i = 0; i < meshes.Count; ++i) if (ain[i].Mesh.Mesh.Texcoords == null) grids[i].Texcoord = default;
-                if (anyAttributeIds)
+                if (anyAttributeIds || TrackRows)
                 {
                     NativeMethods.dsa_encode_default_corner_attributes_options(out var co);
                     co.SeamRepair.Grid.Repair.Level.Ex = ax;
@@ -310,6 +330,15 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
                     co.SeamRepair.Grid.Repair.Level.TraversalMethod = traversal;
                     co.SeamRepair.Grid.Repair.Topology = RepairTopology ? 1 : 0;
                     co.SeamRepair.CornerRepair = RepairSeams ? 1 : 0;
+                    if (TrackRows)
+                    {
+                        NativeMethods.dsa_encode_default_rows_options(out var ro);
+                        ro.CornerAttributes = co;
+                        ro.TrackRows = 1;
+                        fixed (DsaMeshAttrInput* p = ain) fixed (DsaMeshGrids* g = grids) fixed (DsaMeshAttributeCorners* c = acorners)
+                            NativeMethods.Check(NativeMethods.dsa_encode_rows_batch(_ctx, (uint)meshes.Count, p, g, c, in ro, out encoded), _ctx, "dsa_encode_rows_batch");
+                        return Streams(encoded, meshes.Count);
+                    }
                     fixed (DsaMeshAttrInput* p = ain) fixed (DsaMeshGrids* g = grids) fixed (DsaMeshAttributeCorners* c = acorners)
                         NativeMethods.Check(NativeMethods.dsa_encode_corner_attributes_batch(_ctx, (uint)meshes.Count, p, g, c, in co, out encoded), _ctx, "dsa_encode_corner_attributes_batch");
                     return Streams(encoded, meshes.Count);
@@ -412,6 +441,26 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
         {
             NativeMethods.Check(NativeMethods.dsa_encoded_stream(encoded, i, out var bytes, out var length), _ctx, $"mesh {i}");
             result[i] = new ReadOnlySpan<byte>(bytes, (int)length).ToArray();
+        }
+        if (TrackRows) _entryRows = Rows(encoded, count);      // (a sequential handle answers with the identity)
+        return result;
+    }
+
+    // dsa_encoded_entry_rows of every stream, for the attributes dsa_encoded_attributes counts
+    private uint[][][] Rows(IntPtr encoded, int count)
+    {
+        var result = new uint[count][][];
+        for (uint i = 0; i < count; ++i)
+        {
+            NativeMethods.Check(NativeMethods.dsa_encoded_attributes(encoded, i, out uint attributes), _ctx, $"mesh {i}");
+            result[i] = new uint[attributes][];
+            for (uint a = 0; a < attributes; ++a)
+            {
+                NativeMethods.Check(NativeMethods.dsa_encoded_entry_rows(encoded, i, a, null, 0, out uint entries), _ctx, $"mesh {i}");
+                result[i][a] = new uint[entries];
+                fixed (uint* r = result[i][a])
+                    NativeMethods.Check(NativeMethods.dsa_encoded_entry_rows(encoded, i, a, r, (nuint)entries, out entries), _ctx, $"mesh {i}");
+            }
         }
         return result;
     }

@@ -211,6 +211,15 @@ internal unsafe struct DsaEncodeCornerAttributesOptions
     public fixed int Reserved[7];   // zero
 }
 
+// dsa_encode_rows_options (dsa_encode_rows_batch)
+[StructLayout(LayoutKind.Sequential)]
+internal unsafe struct DsaEncodeRowsOptions
+{
+    public DsaEncodeCornerAttributesOptions CornerAttributes;
+    public int TrackRows;           // 1: the handle keeps, per stream and attribute, the row of the caller's arrays every entry carries
+    public fixed int Reserved[7];   // zero
+}
+
 // dsa_encode_sequential_options (dsa_encode_sequential_batch): sequential meshes and point clouds
 [StructLayout(LayoutKind.Sequential)]
 internal unsafe struct DsaEncodeSequentialOptions
@@ -346,6 +355,10 @@ internal static unsafe partial class NativeMethods
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_attributes_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, in DsaEncodeOptionsEx options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_attributes_sequential_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, in DsaEncodeSequentialOptions options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern uint dsa_encoded_size(IntPtr encoded);
+    [DllImport(Lib)] internal static extern void dsa_encode_default_rows_options(out DsaEncodeRowsOptions options);
+    [DllImport(Lib)] internal static extern DsaStatus dsa_encode_rows_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, DsaMeshAttributeCorners* corners, in DsaEncodeRowsOptions options, out IntPtr encoded);
+    [DllImport(Lib)] internal static extern DsaStatus dsa_encoded_entry_rows(IntPtr encoded, uint mesh, uint attribute, uint* dst, nuint capacity, out uint count);
+    [DllImport(Lib)] internal static extern DsaStatus dsa_encoded_attributes(IntPtr encoded, uint mesh, out uint count);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encoded_stream(IntPtr encoded, uint mesh, out byte* bytes, out nuint length);
     [DllImport(Lib)] internal static extern void dsa_encoded_free(IntPtr encoded);
 

@@ -22,6 +22,7 @@
 #include "dsa_host_parse.h"
 #include "dsa_host_util.h"
 #include "dsa_vertex_arrays.h"
+#include "dsa_encode_rows.h"
 
 namespace {
 
@@ -57,7 +58,7 @@ struct EncLane {
   hipEvent_t seams_done = nullptr;                   // attributes given per corner: the seam tables are built, the attribute walks may start
   // device memory of the lane, grown on demand and kept: hipMalloc / hipFree wait for every stream of the device, which would
   // put the chunks of a batch back in single file
-  hostutil::DeviceBuf arena, streams, conns, seams, packed, items, repair, repair_recs, repair_ids, weld, weld_recs;      // (repair / weld: the arenas of the repair and weld kernels, dsa_encode_repair.h, dsa_encode_weld.h)
+  hostutil::DeviceBuf arena, streams, conns, seams, packed, items, repair, repair_recs, repair_ids, weld, weld_recs, rows;      // (repair / weld: the arenas of the repair and weld kernels, dsa_encode_repair.h, dsa_encode_weld.h)
   ~EncLane() {
     if (walk_st) { (void)hipStreamSynchronize(walk_st); (void)hipStreamDestroy(walk_st); }
     if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
@@ -212,6 +213,22 @@ struct dsa_batch {
   HostCopy va_mirror;
   bool va_valid = false, va_queued = false, va_done = false;
   hipEvent_t ev_va = nullptr;
+  // Source rows (dsa_batch_source_rows; dsa_source_rows.h), shaped like the vertex arrays: a device block of their own [table of
+  // SrcRowsMesh | tracked entry rows | arrays], pinned staging of what goes up, a host copy of the arrays, an event of their own.
+  // The request stays (the handle it names must live until dsa_batch_wait): the retry batch takes its share of it.
+  std::vector<dsa::SrcRowsMesh> sr;       // the table of the most recent request
+  std::vector<int32_t> sr_status;         // per mesh: DSA_OK, or why it has no arrays
+  const dsa_encoded *sr_encoded = nullptr;
+  std::vector<uint32_t> sr_map;           // mesh -> stream of sr_encoded
+  uint64_t sr_bytes = 0, sr_head_bytes = 0;
+  uint8_t *d_sr = nullptr;                // from the context's cache (spare_vertex)
+  uint64_t d_sr_cap = 0;
+  uint8_t *sr_pin = nullptr;              // pinned staging of table + entry rows (from spare_mirrors)
+  uint64_t sr_pin_bytes = 0;
+  HostCopy sr_mirror;
+  bool sr_to_host = true;
+  bool sr_valid = false, sr_queued = false, sr_done = false;
+  hipEvent_t ev_sr = nullptr;
   bool all_general = false;
   // meshes the fast kernels handed back (DSA_SITE_RETRY_GENERAL): decoded again through the general path in a batch
   // of their own by dsa_batch_wait; every per-mesh accessor follows retry_index (locate)
@@ -632,6 +649,8 @@ dsa_status dsa_batch_decode(dsa_batch *b) {
   b->download_queued = false; b->downloaded = false;
   if (b->va_queued && !b->va_done) HIP_TRY(ctx, hipStreamWaitEvent(st, b->ev_va, 0));               // so may its vertex arrays
   b->va_valid = false;                                                                                 // a new decode invalidates them
+  if (b->sr_queued && !b->sr_done) HIP_TRY(ctx, hipStreamWaitEvent(st, b->ev_sr, 0));               // its source rows read the maps
+  b->sr_valid = false;
   HIP_TRY(ctx, hipStreamWaitEvent(st, b->ev_uploaded, 0));           // the streams and layouts are in the arena
   HIP_TRY(ctx, hipMemsetAsync(b->d_descs, 0, sizeof(MeshDesc) * n, st));
   HIP_TRY(ctx, hipMemsetAsync(&b->d_globals->pool_cursor, 0, sizeof(unsigned long long) * 2, st));   // the table pool starts empty
@@ -1040,6 +1059,7 @@ dsa_status dsa_batch_decode(dsa_batch *b) {
 }
 
 static dsa_status batch_wait(dsa_batch *b);
+static dsa_status batch_source_rows_retry(dsa_batch *b, dsa_batch *rb, const std::vector<uint32_t> &again);      // dsa_source_rows.h
 // k_pack_output / k_vertex_arrays run behind the decode, so their event pairs may be recorded after the results were collected
 static hipError_t late_kernel_times(dsa_batch *b) {
   if (!b->ctx->profiling || !b->have_events) return hipSuccess;
@@ -1061,6 +1081,7 @@ static dsa_status batch_wait(dsa_batch *b) {
   if (b->collected) {                  // results are in; what can still be outstanding is a download queued since
     if (b->download_queued && !b->downloaded) { HIP_TRY(ctx, hipEventSynchronize(b->ev_down)); b->downloaded = true; }
     if (b->va_valid && b->va_queued && !b->va_done) { HIP_TRY(ctx, hipEventSynchronize(b->ev_va)); b->va_done = true; }
+    if (b->sr_valid && b->sr_queued && !b->sr_done) { HIP_TRY(ctx, hipEventSynchronize(b->ev_sr)); b->sr_done = true; }
     HIP_TRY(ctx, late_kernel_times(b));
     if (b->retry) return dsa_batch_wait(b->retry);
     return DSA_OK;
@@ -1069,6 +1090,7 @@ static dsa_status batch_wait(dsa_batch *b) {
   HIP_TRY(ctx, hipEventSynchronize(b->ev_descs));
   if (b->download_queued) { HIP_TRY(ctx, hipEventSynchronize(b->ev_down)); b->downloaded = true; }
   if (b->va_valid && b->va_queued) { HIP_TRY(ctx, hipEventSynchronize(b->ev_va)); b->va_done = true; }
+  if (b->sr_valid && b->sr_queued) { HIP_TRY(ctx, hipEventSynchronize(b->ev_sr)); b->sr_done = true; }
   if (b->n) memcpy(b->descs.data(), b->descs_pin, sizeof(MeshDesc) * (size_t)b->n);
   if (ctx->profiling && b->have_events && b->n) {
     for (int i = 0; i < STG_TOTAL; ++i) HIP_TRY(ctx, hipEventElapsedTime(&b->stage_ms[i], b->ev[i], b->ev[i + 1]));
@@ -1107,6 +1129,7 @@ static dsa_status batch_wait(dsa_batch *b) {
       if (st == DSA_OK) st = dsa_batch_decode(rb);
       if (st == DSA_OK && b->download_queued) st = dsa_batch_download(rb, nullptr, 0);      // block 1 of the download
       if (st == DSA_OK && b->va_valid && b->va_queued) st = dsa_batch_vertex_arrays(rb, &b->va_req, nullptr, 0);   // block 1 of the vertex arrays
+      if (st == DSA_OK && b->sr_valid && b->sr_queued) st = batch_source_rows_retry(b, rb, again);       // block 1 of the source rows
       if (st == DSA_OK) st = dsa_batch_wait(rb);
       if (st != DSA_OK) { if (rb) dsa_batch_free(rb); b->collected = false; return st; }
       b->retry = rb;
@@ -1130,7 +1153,11 @@ void dsa_batch_free(dsa_batch *b) {
   if (b->ev_descs) { if (b->decoded) (void)hipEventSynchronize(b->ev_descs); (void)hipEventDestroy(b->ev_descs); }
   if (b->ev_down) { if (b->download_queued) (void)hipEventSynchronize(b->ev_down); (void)hipEventDestroy(b->ev_down); }
   if (b->ev_va) { if (b->va_queued) (void)hipEventSynchronize(b->ev_va); (void)hipEventDestroy(b->ev_va); }
+  if (b->ev_sr) { if (b->sr_queued) (void)hipEventSynchronize(b->ev_sr); (void)hipEventDestroy(b->ev_sr); }
   dsa_context *ctx = b->ctx;
+  ctx->spare_mirrors.give(b->sr_pin, b->sr_pin_bytes);
+  release(ctx, b->sr_mirror);
+  ctx->spare_vertex.give(b->d_sr, b->d_sr_cap);
   ctx->spare_descs.give(b->va_pin, b->va_pin_bytes);
   release(ctx, b->va_mirror);
   ctx->spare_vertex.give(b->d_va, b->d_va_cap);
@@ -1630,4 +1657,5 @@ dsa_status dsa_batch_stage_times(const dsa_batch *b, float ms[DSA_NUM_STAGES], c
 }  // extern "C"
 
 #include "dsa_encode.h"
+#include "dsa_source_rows.h"
 #include "dsa_pool.h"

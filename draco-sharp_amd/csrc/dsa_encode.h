@@ -22,6 +22,7 @@
 //                                                stream (dsa_symbol_plan.h, the code the host coder runs)   SymbolEncoding.cs:8-40, RAnsSymbolEncoder.cs:15-123
 //   host  (dsa_encode_host.h)  input checks; at the end the stream layout: bit-packing of the Edgebreaker symbols, table bytes, section order
 //                              (threads over meshes).  DSA_ENC_HOST_PLAN=1: the symbol plans by the host between the two device phases.
+//   GPU   (dsa_encode_rows.h)  k_enc_entry_rows  dsa_encode_rows_batch, track_rows = 1: the row of the caller's arrays every entry carries
 //         (dsa_encode_layout.h) the request of an entry point, the state of a chunk, the per-mesh checks and plans, the arena layout
 // Every entry point fills an EncRequest and calls encode_request; a chunk of it goes through the stages of encode_chunk (or of
 // encode_sequential_chunk, dsa_encode_sequential.h) on a lane.
@@ -653,6 +654,9 @@ static dsa_status enc_code_streams(dsa_context *ctx, EncLane &lane, EncChunk &ck
   }
   // coded bytes of every stream (and, when k_enc_plan made them, the probability tables: the stream carries them)
   // and the side bits of TexCoordsPortable / GeometricNormal, packed
+  // (track_rows: a fifth piece per stream, its entry rows -- k_enc_entry_rows has run behind the attribute kernels)
+  const bool track = !ck.L.rows_of_stream.empty();
+  const size_t per = track ? 5 : 4;
   std::vector<dsa::PackItem> items;
   for (uint32_t s = 0; s < ns; ++s) {
     if (hs[s].overflow || E->status[stream_mesh[s]] != DSA_OK) continue;
@@ -662,12 +666,17 @@ static dsa_status enc_code_streams(dsa_context *ctx, EncLane &lane, EncChunk &ck
     items.push_back({hs[s].prob, 0, host_plan ? 0u : 4u * hs[s].num_symbols, s});
     const bool creased = hs[s].kind != 1 && hs[s].prediction == 4;      // (its `flags` hold the four crease lists: below)
     items.push_back({hs[s].flags, 0, hs[s].flags && !creased ? 4u * ((hs[s].num_flags + 31u) / 32u) : 0u, s});
+    if (track) {
+      const dsa::EncRows *R = ck.L.rows_of_stream[s] != DSA_INVALID ? &ck.L.rows[ck.L.rows_of_stream[s]] : nullptr;
+      items.push_back({R ? R->out : 0, 0, R ? 4u * std::min(hs[s].nv, R->cap) : 0u, s});
+    }
   }
   const uint8_t *host = nullptr;
   ENC_ST(enc_gather(lane, arena, items, nullptr, &host));
-  hostutil::parallel_for((uint32_t)(items.size() / 4), [&](uint32_t m) {
-    const size_t k = 4 * (size_t)m;
+  hostutil::parallel_for((uint32_t)(items.size() / per), [&](uint32_t m) {
+    const size_t k = per * (size_t)m;
     const uint32_t s = items[k].pad;
+    if (track && items[k + 4].len) { const uint32_t *r = (const uint32_t *)(host + items[k + 4].packed_off); ck.entry_rows[s].assign(r, r + items[k + 4].len / 4u); }
     if (items[k].len) rans[s].assign(host + items[k].packed_off, host + items[k].packed_off + items[k].len);
     if (items[k + 1].len) bits[s].assign(host + items[k + 1].packed_off, host + items[k + 1].packed_off + items[k + 1].len);
     if (hs[s].flags && !(hs[s].kind != 1 && hs[s].prediction == 4)) {
@@ -1235,6 +1244,12 @@ static dsa_status enc_stage_attributes(dsa_context *ctx, EncLane &lane, EncChunk
     hipLaunchKernelGGL(dsa::k_enc_plan, dim3((ns + WAVE - 1) / WAVE), dim3(WAVE), 0, st, arena, d_streams, ns, (int)ck.opt.force_scheme, (int)ck.opt.compression_level);
     hipLaunchKernelGGL(dsa::k_enc_rans, dim3(ns), dim3(WAVE), 0, st, arena, d_streams, ns);
   }
+  if (!L.rows.empty()) {     // track_rows: entry -> value row (-> point of a weld request), where the orders still lie (dsa_encode_rows.h)
+    const uint32_t nr = (uint32_t)L.rows.size();
+    ENC_TRY(lane.rows.ensure(sizeof(dsa::EncRows) * nr));
+    ENC_TRY(hipMemcpyAsync(lane.rows.p, L.rows.data(), sizeof(dsa::EncRows) * nr, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(dsa::k_enc_entry_rows<dsa::EncStream>, dim3(gx, nr), dim3(256), 0, st, arena, (const dsa::EncRows *)lane.rows.p, nr, (const dsa::EncStream *)d_streams);
+  }
   if (sequential) ENC_TRY(hipGetLastError());
   ENC_TRY(hipMemcpyAsync(L.streams.data(), d_streams, sizeof(dsa::EncStream) * ns, hipMemcpyDeviceToHost, st));
   if (device_conn) ENC_TRY(hipMemcpyAsync(L.conns.data(), d_conns, sizeof(dsa::EncConn) * n, hipMemcpyDeviceToHost, st));
@@ -1331,6 +1346,7 @@ static dsa_status enc_stage_code(dsa_context *ctx, EncLane &lane, EncChunk &ck, 
   else enc_device_plan_errors(ck);
   if (lap) (*lap)("histograms + symbol plans");
   ck.rans.resize(ns); ck.bits.resize(ns); ck.flag_bits.resize(ns); ck.crease.resize(ck.L.any_crease ? 4 * (size_t)ns : 0);
+  if (!ck.L.rows_of_stream.empty()) ck.entry_rows.resize(ns);
   return ns ? enc_code_streams(ctx, lane, ck) : DSA_OK;
 }
 // host phase 3: the stream layout (threads over meshes; write_stream may throw like any part of the host coder)
@@ -1362,6 +1378,10 @@ static void enc_stage_streams(EncChunk &ck) {
         [&](synth::ByteWriter &bw, size_t k) { enc_write_transform(bw, L.streams[s0 + k]); });
     } catch (const std::exception &e) { return ck.refuse(i, DSA_ERR_INVALID_DATA, e.what()); }
     ck.E->streams[i].swap(w.d);
+    if (!ck.entry_rows.empty()) {                             // (a mesh that failed has none: its status answers)
+      ck.E->rows[i].resize(ck.plans[i].atts.size());
+      for (size_t k = 0; k < ck.E->rows[i].size(); ++k) ck.E->rows[i][k].swap(ck.entry_rows[s0 + k]);
+    }
   });
 }
 
@@ -1426,12 +1446,15 @@ static dsa_status enc_check_base(dsa_context *ctx, const dsa_encode_options &o) 
 }
 // Edgebreaker streams: the widest options, in which every narrower entry point has left what it does not have at its default.
 // (The quantisation bits are checked per chunk: enc_stage_plans.)
-static dsa_status enc_check_options(dsa_context *ctx, const dsa_encode_corner_attributes_options &c, bool null_argument) {
+static dsa_status enc_check_options(dsa_context *ctx, const dsa_encode_rows_options &w, bool null_argument) {
+  const dsa_encode_corner_attributes_options &c = w.corner_attributes;
   const dsa_encode_seam_repair_options &s = c.seam_repair;
   const dsa_encode_grid_options &g = s.grid;
   const dsa_encode_repair_options &r = g.repair;
   const dsa_encode_level_options &d = r.level;
   const dsa_encode_options_ex &ex = d.ex;
+  if (w.track_rows != 0 && w.track_rows != 1) ENC_REFUSE("track_rows %d: 0 (nothing kept) or 1 (the handle keeps the entry rows of every stream)", (int)w.track_rows);
+  ENC_RESERVED(w, 7, "dsa_encode_rows_options");
   if (c.weld_attributes != 0 && c.weld_attributes != 1) ENC_REFUSE("weld_attributes %d: 0 (listed attributes in the vertex key) or 1 (listed attributes welded alone)", (int)c.weld_attributes);
   ENC_RESERVED(c, 7, "dsa_encode_corner_attributes_options");
   if (c.weld_attributes == 1 && g.weld_points != 1) ENC_REFUSE("weld_attributes 1 needs weld_points 1 (rows per point), weld_points is %d", (int)g.weld_points);
@@ -1495,7 +1518,7 @@ static dsa_status enc_ensure_lanes(dsa_context *ctx, uint32_t lanes) {
 // streams wait for each other: four lanes, their walk streams at another priority.  Small batches are one chunk.
 // `code_chunk(sink, lane, base, count, &part)`: codes meshes base .. base + count of the batch on the lane.
 template <class ChunkFn>
-static dsa_status encode_batch_chunks(dsa_context *ctx, uint32_t n, ChunkFn &&code_chunk, dsa_encoded **out) {
+static dsa_status encode_batch_chunks(dsa_context *ctx, uint32_t n, ChunkFn &&code_chunk, dsa_encoded **out, int rows_kind = dsa_encoded::ROWS_NONE) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const uint32_t max_lanes = [&]() { const char *e = getenv("DSA_ENC_LANES"); const int v = e ? atoi(e) : 0; return (uint32_t)(v >= 1 && v <= 16 ? v : 4); }();
   const uint32_t chunk_max = [&]() { const char *e = getenv("DSA_ENC_CHUNK"); const int v = e ? atoi(e) : 0; return (uint32_t)(v >= 1 ? v : 0); }();
@@ -1514,6 +1537,7 @@ static dsa_status encode_batch_chunks(dsa_context *ctx, uint32_t n, ChunkFn &&co
   std::unique_ptr<dsa_encoded> E(new dsa_encoded());
   E->ctx = ctx;
   E->streams.resize(n); E->status.assign(n, DSA_OK); E->messages.resize(n);
+  E->keep_rows(rows_kind, n);
   std::atomic<uint32_t> next{0};
   std::atomic<int> failed{DSA_OK};
   std::vector<std::string> errs(lanes);
@@ -1535,7 +1559,7 @@ static dsa_status encode_batch_chunks(dsa_context *ctx, uint32_t n, ChunkFn &&co
         if (getenv("DSA_ENC_TIMING")) fprintf(stderr, "[dsa_encode_batch] chunk %u (%u meshes) returned after %8.2f ms\n", c, cnt, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_chunk).count());
         if (st != DSA_OK) { errs[l] = sink.err; int ok = DSA_OK; failed.compare_exchange_strong(ok, st); break; }
         std::unique_ptr<dsa_encoded> owner(part);
-        for (uint32_t i = 0; i < cnt; ++i) { E->streams[base + i].swap(part->streams[i]); E->status[base + i] = part->status[i]; E->messages[base + i].swap(part->messages[i]); }
+        for (uint32_t i = 0; i < cnt; ++i) E->take(base + i, *part, i);
       }
     } catch (const std::bad_alloc &) { int ok = DSA_OK; failed.compare_exchange_strong(ok, DSA_ERR_OUT_OF_MEMORY); }
     catch (...) { int ok = DSA_OK; failed.compare_exchange_strong(ok, DSA_ERR_DEVICE); }
@@ -1653,7 +1677,7 @@ static dsa_status encode_request(dsa_context *ctx, const EncRequest &rq, dsa_enc
   return encode_batch_chunks(ctx, rq.n, [&](dsa_context *sink, EncLane &lane, uint32_t base, uint32_t cnt, dsa_encoded **part) {
     if (rq.weld_sink) return weld_chunk(sink, lane, rq, base, cnt, batch_n, part);
     return rq.sequential ? encode_sequential_chunk(sink, lane, rq, base, cnt, rq.n, part) : encode_chunk(sink, lane, rq, base, cnt, batch_n, part);
-  }, out);
+  }, out, rq.rows_kind());
 }
 // dsa_encode_repair_batch, topology = 1: the batch as dsa_encode_level_batch codes it; then the meshes refused for their topology
 // once more as a request of their own, on the repaired corner table (EncRequest::repair), their results into the first's places.
@@ -1687,7 +1711,7 @@ static dsa_status encode_repair_request(dsa_context *ctx, const EncRequest &requ
     const dsa_status s2 = encode_request(ctx, r2, &second, rq.n);
     if (s2 != DSA_OK) return s2;
     std::unique_ptr<dsa_encoded> E2(second);
-    for (uint32_t k = 0; k < r2.n; ++k) { E->streams[again[k]].swap(E2->streams[k]); E->status[again[k]] = E2->status[k]; E->messages[again[k]].swap(E2->messages[k]); }
+    for (uint32_t k = 0; k < r2.n; ++k) E->take(again[k], *E2, k);
   }
   *out = E.release();
   return DSA_OK;
@@ -1715,15 +1739,17 @@ static dsa_status encode_checked(dsa_context *ctx, EncRequest &rq, const dsa_mes
   }
   return repair ? encode_repair_request(ctx, rq, out) : encode_request(ctx, rq, out);
 }
-static dsa_status encode_edgebreaker(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_corner_attributes_options &c,
+static dsa_status encode_edgebreaker(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_rows_options &w,
                                      dsa_encoded **out, bool drop_generic_outside_1_4 = false, const dsa_mesh_attribute_corners *corners = nullptr) {
-  if (enc_check_options(ctx, c, !ctx || !out || (n && !meshes)) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+  if (enc_check_options(ctx, w, !ctx || !out || (n && !meshes)) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+  const dsa_encode_corner_attributes_options &c = w.corner_attributes;
   const dsa_encode_seam_repair_options &o = c.seam_repair;
   EncRequest rq;
   rq.n = n; rq.meshes = meshes; rq.drop_generic_outside_1_4 = drop_generic_outside_1_4;
   rq.level = o.grid.repair.level;
   rq.weld = o.grid.weld_points == 1; rq.corner_repair = o.corner_repair == 1;
   rq.att_corners = n ? corners : nullptr; rq.weld_attributes = c.weld_attributes == 1;
+  rq.track_rows = w.track_rows == 1;
   return encode_checked(ctx, rq, grids, o.grid.repair.topology == 1, out);
 }
 static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_sequential_options *options, dsa_encoded **out) {
@@ -1736,11 +1762,11 @@ static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh
 }
 // the array of a narrower entry point widened, owned by the call
 template <class Mesh>
-static dsa_status encode_edgebreaker_narrow(dsa_context *ctx, uint32_t n, const Mesh *meshes, const dsa_encode_corner_attributes_options &o, dsa_encoded **out, bool drop_generic_outside_1_4 = false) {
+static dsa_status encode_edgebreaker_narrow(dsa_context *ctx, uint32_t n, const Mesh *meshes, const dsa_encode_rows_options &o, dsa_encoded **out, bool drop_generic_outside_1_4 = false) {
   const std::vector<dsa_mesh_attr_input> wide = enc_widen(meshes, n);
   return encode_edgebreaker(ctx, n, wide.empty() ? nullptr : wide.data(), nullptr, o, out, drop_generic_outside_1_4);
 }
-static dsa_encode_corner_attributes_options enc_default_options() { dsa_encode_corner_attributes_options o; dsa_encode_default_corner_attributes_options(&o); return o; }
+static dsa_encode_rows_options enc_default_options() { dsa_encode_rows_options o; dsa_encode_default_rows_options(&o); return o; }
 
 extern "C" {
 
@@ -1788,67 +1814,80 @@ void dsa_encode_default_corner_attributes_options(dsa_encode_corner_attributes_o
   memset(o, 0, sizeof(*o));
   dsa_encode_default_seam_repair_options(&o->seam_repair);
 }
+void dsa_encode_default_rows_options(dsa_encode_rows_options *o) {
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  dsa_encode_default_corner_attributes_options(&o->corner_attributes);
+}
 
 dsa_status dsa_encode_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_encode_options *options, dsa_encoded **out) {
-  dsa_encode_corner_attributes_options o = enc_default_options();
-  if (options) o.seam_repair.grid.repair.level.ex.base = *options;
+  dsa_encode_rows_options o = enc_default_options();
+  if (options) o.corner_attributes.seam_repair.grid.repair.level.ex.base = *options;
   DSA_GUARD(ctx, encode_edgebreaker_narrow(ctx, n, meshes, o, out, true));      // (EncRequest::drop_generic_outside_1_4: this entry alone)
 }
 dsa_status dsa_encode_batch_corners(dsa_context *ctx, uint32_t n, const dsa_mesh_corner_input *meshes, const dsa_encode_options *options, dsa_encoded **out) {
-  dsa_encode_corner_attributes_options o = enc_default_options();
-  if (options) o.seam_repair.grid.repair.level.ex.base = *options;
+  dsa_encode_rows_options o = enc_default_options();
+  if (options) o.corner_attributes.seam_repair.grid.repair.level.ex.base = *options;
   DSA_GUARD(ctx, encode_edgebreaker_narrow(ctx, n, meshes, o, out));
 }
 dsa_status dsa_encode_batch_ex(dsa_context *ctx, uint32_t n, const dsa_mesh_corner_input *meshes, const dsa_encode_options_ex *options, dsa_encoded **out) {
-  dsa_encode_corner_attributes_options o = enc_default_options();
-  if (options) o.seam_repair.grid.repair.level.ex = *options;
+  dsa_encode_rows_options o = enc_default_options();
+  if (options) o.corner_attributes.seam_repair.grid.repair.level.ex = *options;
   DSA_GUARD(ctx, encode_edgebreaker_narrow(ctx, n, meshes, o, out));
 }
 dsa_status dsa_encode_attributes_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_encode_options_ex *options, dsa_encoded **out) {
-  dsa_encode_corner_attributes_options o = enc_default_options();
-  if (options) o.seam_repair.grid.repair.level.ex = *options;
+  dsa_encode_rows_options o = enc_default_options();
+  if (options) o.corner_attributes.seam_repair.grid.repair.level.ex = *options;
   DSA_GUARD(ctx, encode_edgebreaker(ctx, n, meshes, nullptr, o, out));
 }
 // The levels above the default: MultiParallelogram / ConstrainedMultiParallelogram in place of Parallelogram, prediction-degree
 // attribute order (dsa_encode_multi.h).
 dsa_status dsa_encode_level_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_encode_level_options *options, dsa_encoded **out) {
-  dsa_encode_corner_attributes_options o = enc_default_options();
-  if (options) o.seam_repair.grid.repair.level = *options;
+  dsa_encode_rows_options o = enc_default_options();
+  if (options) o.corner_attributes.seam_repair.grid.repair.level = *options;
   DSA_GUARD(ctx, encode_edgebreaker(ctx, n, meshes, nullptr, o, out));
 }
 // ... that also takes meshes with degenerate faces, non-manifold edges and vertices and isolated vertices (topology = 1: the
 // reference's corner table, dsa_encode_repair.h).
 dsa_status dsa_encode_repair_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_encode_repair_options *options, dsa_encoded **out) {
-  dsa_encode_corner_attributes_options o = enc_default_options();
-  if (options) o.seam_repair.grid.repair = *options;
+  dsa_encode_rows_options o = enc_default_options();
+  if (options) o.corner_attributes.seam_repair.grid.repair = *options;
   DSA_GUARD(ctx, encode_edgebreaker(ctx, n, meshes, nullptr, o, out));
 }
 // dsa_encode_repair_batch for meshes given as one row per point: every chunk welds its meshes first (enc_stage_weld), the welded
 // meshes are coded as that call codes them.  With topology = 1 the meshes refused for their topology are welded again in the
 // second pass: they are the few, and the weld is cheap beside keeping every chunk's buffers alive.
 dsa_status dsa_encode_points_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_encode_repair_options *options, dsa_encoded **out) {
-  dsa_encode_corner_attributes_options o = enc_default_options();
-  if (options) o.seam_repair.grid.repair = *options;
-  o.seam_repair.grid.weld_points = 1;
+  dsa_encode_rows_options o = enc_default_options();
+  if (options) o.corner_attributes.seam_repair.grid.repair = *options;
+  o.corner_attributes.seam_repair.grid.weld_points = 1;
   DSA_GUARD(ctx, encode_edgebreaker(ctx, n, meshes, nullptr, o, out));
 }
 // ... with a quantisation grid per float attribute, given by the caller or shared within a group (dsa_encode_grid.h).
 dsa_status dsa_encode_grid_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_grid_options *options, dsa_encoded **out) {
-  dsa_encode_corner_attributes_options o = enc_default_options();
-  if (options) o.seam_repair.grid = *options;
+  dsa_encode_rows_options o = enc_default_options();
+  if (options) o.corner_attributes.seam_repair.grid = *options;
   DSA_GUARD(ctx, encode_edgebreaker(ctx, n, meshes, grids, o, out));
 }
 // ... with attributes given per corner coded over a repaired table (EncRequest::corner_repair; the second pass of
 // encode_repair_request, dsa_encode_repair.h: k_enc_repair_face_scan, k_enc_repair_ids).
 dsa_status dsa_encode_seam_repair_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_seam_repair_options *options, dsa_encoded **out) {
-  dsa_encode_corner_attributes_options o = enc_default_options();
-  if (options) o.seam_repair = *options;
+  dsa_encode_rows_options o = enc_default_options();
+  if (options) o.corner_attributes.seam_repair = *options;
   DSA_GUARD(ctx, encode_edgebreaker(ctx, n, meshes, grids, o, out));
 }
 // ... with row ids per corner for the attributes of the list, given by the caller (EncRequest::att_corners) or found by the weld
 // with every listed attribute a key set of its own (EncRequest::weld_attributes; dsa_encode_weld_list.h).
 dsa_status dsa_encode_corner_attributes_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids,
                                               const dsa_mesh_attribute_corners *corners, const dsa_encode_corner_attributes_options *options, dsa_encoded **out) {
+  dsa_encode_rows_options o = enc_default_options();
+  if (options) o.corner_attributes = *options;
+  DSA_GUARD(ctx, encode_edgebreaker(ctx, n, meshes, grids, o, out, false, corners));
+}
+// ... whose handle also keeps, with track_rows = 1, the row of the caller's value arrays every entry of every stream carries
+// (EncRequest::track_rows; dsa_encode_rows.h: k_enc_entry_rows behind the attribute kernels of every chunk).
+dsa_status dsa_encode_rows_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids,
+                                 const dsa_mesh_attribute_corners *corners, const dsa_encode_rows_options *options, dsa_encoded **out) {
   DSA_GUARD(ctx, encode_edgebreaker(ctx, n, meshes, grids, options ? *options : enc_default_options(), out, false, corners));
 }
 dsa_status dsa_encode_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_input *meshes, const dsa_encode_sequential_options *options, dsa_encoded **out) {
@@ -1914,6 +1953,34 @@ dsa_status dsa_encoded_stream(const dsa_encoded *e, uint32_t mesh, const uint8_t
   if (e->status[mesh] != DSA_OK) return set_err(e->ctx, (dsa_status)e->status[mesh], "mesh %u: %s", mesh, e->messages[mesh].c_str());
   *bytes = e->streams[mesh].data();
   *length = e->streams[mesh].size();
+  return DSA_OK;
+}
+
+// How many attributes stream `mesh` has entry rows for (what bounds `attribute` below).
+dsa_status dsa_encoded_attributes(const dsa_encoded *e, uint32_t mesh, uint32_t *count) {
+  if (!e || mesh >= e->streams.size() || !count) return DSA_ERR_INVALID_ARGUMENT;
+  *count = 0;
+  if (e->status[mesh] != DSA_OK) return set_err(e->ctx, (dsa_status)e->status[mesh], "mesh %u: %s", mesh, e->messages[mesh].c_str());
+  if (e->rows_kind == dsa_encoded::ROWS_NONE) return set_err(e->ctx, DSA_ERR_INVALID_ARGUMENT, "the entry rows of this handle were not kept: encode with dsa_encode_rows_batch and track_rows = 1");
+  *count = e->rows_kind == dsa_encoded::ROWS_LINEAR ? e->linear[mesh].first : (uint32_t)e->rows[mesh].size();
+  return DSA_OK;
+}
+// The entry rows of attribute `attribute` of stream `mesh`: a sequential handle answers with the identity, an Edgebreaker handle
+// with what track_rows kept.
+dsa_status dsa_encoded_entry_rows(const dsa_encoded *e, uint32_t mesh, uint32_t attribute, uint32_t *dst, size_t capacity, uint32_t *count) {
+  if (!e || mesh >= e->streams.size() || !count) return DSA_ERR_INVALID_ARGUMENT;
+  *count = 0;
+  if (e->status[mesh] != DSA_OK) return set_err(e->ctx, (dsa_status)e->status[mesh], "mesh %u: %s", mesh, e->messages[mesh].c_str());
+  if (e->rows_kind == dsa_encoded::ROWS_NONE) return set_err(e->ctx, DSA_ERR_INVALID_ARGUMENT, "the entry rows of this handle were not kept: encode with dsa_encode_rows_batch and track_rows = 1");
+  const bool linear = e->rows_kind == dsa_encoded::ROWS_LINEAR;
+  const uint32_t attributes = linear ? e->linear[mesh].first : (uint32_t)e->rows[mesh].size();
+  if (attribute >= attributes) return set_err(e->ctx, DSA_ERR_INVALID_ARGUMENT, "mesh %u: attribute %u of %u", mesh, attribute, attributes);
+  const uint32_t entries = linear ? e->linear[mesh].second : (uint32_t)e->rows[mesh][attribute].size();
+  *count = entries;
+  if (!dst) return DSA_OK;
+  if (capacity < entries) return set_err(e->ctx, DSA_ERR_INVALID_ARGUMENT, "mesh %u, attribute %u: %u entry rows, room for %llu", mesh, attribute, entries, (unsigned long long)capacity);
+  if (linear) for (uint32_t i = 0; i < entries; ++i) dst[i] = i;
+  else if (entries) memcpy(dst, e->rows[mesh][attribute].data(), 4ull * entries);
   return DSA_OK;
 }
 

@@ -1773,6 +1773,27 @@ static void encode_mesh(const MeshIn &in, const Options &opt, std::vector<uint8_
                [&](ByteWriter &bw, size_t i) { write_attribute_transform(bw, pl.atts[i]); });
   out.swap(w.d);
 }
+// Entry rows (dsa_encoded_entry_rows; track_rows of dsa_encode_rows_batch): per attribute of the stream, in stream order, the row
+// of the value array passed for it whose bytes entry e of the stream carries -- the loop by which write_attribute_values fills
+// its values in entry order, with the row kept instead of the value.  A vertex the repair made reads its root parent's row
+// (CornerTable::row_of); isolated vertices and degenerate faces have no entries.  What the device's k_enc_entry_rows is held to.
+static void plan_entry_rows(const MeshPlan &pl, std::vector<std::vector<uint32_t>> &rows) {
+  rows.assign(pl.atts.size(), std::vector<uint32_t>());
+  for (size_t k = 0; k < pl.atts.size(); ++k) {
+    const PortableAttr &a = pl.atts[k];
+    const Sequence &seq = pl.seq_of(k);
+    rows[k].resize(seq.data_to_corner.size());
+    for (size_t e = 0; e < rows[k].size(); ++e) {
+      const uint32_t corner = seq.data_to_corner[e];
+      rows[k][e] = a.corner_value ? a.corner_value[corner] : pl.ct.row_of(pl.ct.vertex(corner));
+    }
+  }
+}
+static void entry_rows(const MeshIn &in, const Options &opt, std::vector<std::vector<uint32_t>> &rows) {
+  MeshPlan pl;
+  plan_mesh(in, opt, pl);
+  plan_entry_rows(pl, rows);
+}
 
 // ------------------------------------------------------------------ the weld of per-point input
 // A mesh given as one row per point (a glTF primitive, an OBJ after triangulation, Batch.vertex_arrays): a point is duplicated
@@ -1908,6 +1929,24 @@ static MeshIn welded_mesh_in(const MeshIn &in, const Welded &w, std::vector<Extr
   m.uvs = in.uvs ? (const float *)w.texcoord_rows.data() : nullptr;
   m.uv_corners = w.texcoords_per_vertex ? nullptr : w.texcoord_corners.data(); m.nu = w.texcoords_per_vertex ? 0 : w.texcoord.count;
   return m;
+}
+// Entry rows of a welded mesh: row r of the array the coder got for attribute `a` is the row of which point of the caller's --
+// the representative of class r of the attribute's own key set where it went on with ids per corner, of vertex r where it went
+// on per vertex (positions, the generic attribute, the listed attributes of the vertex key, and every set no vertex has two of).
+static const std::vector<uint32_t> &weld_row_points(const Welded &w, const PortableAttr &a) {
+  if (a.extra_index >= 0) return (size_t)a.extra_index < w.listed.size() && !w.listed[a.extra_index].per_vertex ? w.listed[a.extra_index].keys.point : w.vertex.point;
+  if (a.att_type == 1 && !w.normals_per_vertex) return w.normal.point;
+  if (a.att_type == 3 && !w.texcoords_per_vertex) return w.texcoord.point;
+  return w.vertex.point;
+}
+static void welded_entry_rows(const MeshIn &welded, const Welded &w, const Options &opt, std::vector<std::vector<uint32_t>> &rows) {
+  MeshPlan pl;
+  plan_mesh(welded, opt, pl);
+  plan_entry_rows(pl, rows);
+  for (size_t k = 0; k < rows.size(); ++k) {
+    const std::vector<uint32_t> &point = weld_row_points(w, pl.atts[k]);
+    for (uint32_t &r : rows[k]) r = point[r];
+  }
 }
 
 // ------------------------------------------------------------------ sequential streams

@@ -30,6 +30,7 @@
 #include "dsa_encode_seqidx.h"
 #include "dsa_encode_schemes.h"
 #include "dsa_encode_multi.h"
+#include "dsa_encode_rows.h"
 
 namespace dsa {
 
@@ -110,6 +111,19 @@ struct dsa_encoded {
   std::vector<std::vector<uint8_t>> streams;
   std::vector<int32_t> status;
   std::vector<std::string> messages;
+  // entry rows (dsa_encoded_entry_rows).  ROWS_TRACKED: rows[mesh][attribute of the stream], kept by a call with track_rows = 1
+  // (dsa_encode_rows.h); ROWS_LINEAR: a sequential call, entry i is row i, and linear[mesh] = (attributes, points) is all it takes
+  enum { ROWS_NONE = 0, ROWS_TRACKED = 1, ROWS_LINEAR = 2 };
+  int rows_kind = ROWS_NONE;
+  std::vector<std::vector<std::vector<uint32_t>>> rows;
+  std::vector<std::pair<uint32_t, uint32_t>> linear;
+  void keep_rows(int kind, size_t n) { rows_kind = kind; if (kind == ROWS_TRACKED) rows.resize(n); if (kind == ROWS_LINEAR) linear.resize(n); }
+  // mesh `from` of `part` into place `to`: stream, status, message and what it has of rows
+  void take(size_t to, dsa_encoded &part, size_t from) {
+    streams[to].swap(part.streams[from]); status[to] = part.status[from]; messages[to].swap(part.messages[from]);
+    if (rows_kind == ROWS_TRACKED && from < part.rows.size()) rows[to].swap(part.rows[from]);
+    if (rows_kind == ROWS_LINEAR && from < part.linear.size()) linear[to] = part.linear[from];
+  }
 };
 
 // A call of an encode entry point.  The meshes in the widest form (a narrower array is widened once, enc_widen), the options in
@@ -149,6 +163,8 @@ struct EncRequest {
   const EncMeshGrids *grids = nullptr;     // dsa_encode_grid_batch / _sequential_batch: parallel to `meshes` (null: every attribute on its own bounds)
   const dsa_mesh_attribute_corners *att_corners = nullptr;      // dsa_encode_corner_attributes_batch: parallel to `meshes` (null: the listed attributes are per vertex)
   bool weld_attributes = false;            // ... weld_attributes = 1: the listed attributes are key sets of their own in the weld (dsa_encode_weld_list.h)
+  bool track_rows = false;                 // dsa_encode_rows_batch, track_rows = 1: the handle keeps the entry rows of every stream (dsa_encode_rows.h)
+  int rows_kind() const { return weld_sink ? dsa_encoded::ROWS_NONE : (sequential ? dsa_encoded::ROWS_LINEAR : (track_rows ? dsa_encoded::ROWS_TRACKED : dsa_encoded::ROWS_NONE)); }
   dsa_encode_level_options level{};        // Edgebreaker streams
   dsa_encode_sequential_options seq{};     // sequential streams
   const dsa_encode_options &base() const { return sequential ? seq.base : level.ex.base; }
@@ -193,6 +209,8 @@ struct EncLayout {
   std::vector<dsa::EncConn> conns;          // device connectivity: one per mesh (a mesh that failed the host's checks: F = 0, no arrays)
   std::vector<dsa::EncSeam> seams;          // device connectivity: one per (mesh, attribute given per corner)
   std::vector<dsa::EncSeqIdx> idx;          // sequential, compressed indices: one per mesh
+  std::vector<dsa::EncRows> rows;           // EncRequest::track_rows: one per (mesh, attribute), in stream order
+  std::vector<uint32_t> rows_of_stream;     // ... per stream its record in `rows` (DSA_INVALID: a context list); empty without track_rows
   std::vector<EncCopy> copies_a;            // phase A, a repaired table with corner ids: the ids of the coded faces, which k_enc_repair_ids left on the device
   std::vector<EncUpload> uploads_a, uploads;      // phase A: what the walks need (the faces, the corner ids; device connectivity only); the rest
   std::vector<uint32_t> first_stream;       // streams of mesh i: first_stream[i] .. first_stream[i + 1]
@@ -248,10 +266,12 @@ struct EncChunk {
   std::vector<int> stream_mesh;
   std::vector<synth::SymbolPlan> splans;
   std::vector<std::vector<uint8_t>> rans, bits, flag_bits, crease;      // per stream; crease[4 s + j]: list j of stream s
+  std::vector<std::vector<uint32_t>> entry_rows;                        // per stream (EncRequest::track_rows)
 
   EncChunk(const EncRequest &r, uint32_t b, uint32_t cnt, uint32_t bn) : rq(r), base(b), n(cnt), batch_n(bn), opt(enc_synth_options(r)), E(new (std::nothrow) dsa_encoded()), ins(cnt), plans(cnt), extras(cnt), extra_cap(cnt) {
     if (!E) return;                        // (the chunk function answers)
     E->streams.resize(n); E->status.assign(n, DSA_OK); E->messages.resize(n);
+    E->keep_rows(r.rows_kind(), n);
   }
   const dsa_mesh_attr_input &attr(uint32_t i) const { return welded.empty() ? rq.attr(base + i) : welded[i]; }
   const dsa_mesh_corner_input &corner(uint32_t i) const { return attr(i).mesh; }
@@ -559,6 +579,7 @@ static void enc_layout_begin(EncChunk &ck, uint32_t more_streams_of_valence, uin
   dsa::EncStream zero;
   memset(&zero, 0, sizeof(zero));
   L.streams.assign(L.first_stream[ck.n], zero);
+  if (ck.rq.track_rows && !ck.rq.sequential) L.rows_of_stream.assign(L.streams.size(), DSA_INVALID);
 }
 
 // ---- the arena of a chunk of Edgebreaker streams
@@ -630,6 +651,24 @@ static void enc_layout(EncChunk &ck) {
         t_d2c[0] = put(pl.seq.data_to_corner.data(), 4ull * pl.seq.data_to_corner.size()); t_v2d[0] = put(pl.seq.vertex_to_data.data(), 4ull * pl.seq.vertex_to_data.size());
         if (want_pd) { t_d2c[1] = put(pl.seq_pd.data_to_corner.data(), 4ull * pl.seq_pd.data_to_corner.size()); t_v2d[1] = put(pl.seq_pd.vertex_to_data.data(), 4ull * pl.seq_pd.vertex_to_data.size()); }
       }
+    }
+    // track_rows: a record per attribute; over a welded mesh the representative points of its rows go up, every key set's once
+    const std::vector<uint32_t> *row_points[2 + synth::kMaxAttributes * 2] = {};
+    uint64_t row_points_at[2 + synth::kMaxAttributes * 2] = {};
+    size_t num_row_points = 0;
+    for (size_t k = 0; ck.rq.track_rows && k < pl.atts.size(); ++k) {
+      dsa::EncRows R;
+      memset(&R, 0, sizeof(R));
+      R.stream = s0 + (uint32_t)k;
+      if (!ck.welded.empty()) {
+        const std::vector<uint32_t> *point = &synth::weld_row_points(ck.weld[i], pl.atts[k]);
+        size_t q = 0;
+        while (q < num_row_points && row_points[q] != point) ++q;
+        if (q == num_row_points) { row_points[q] = point; row_points_at[q] = put(point->data(), 4ull * point->size()); ++num_row_points; }
+        R.point = row_points_at[q]; R.num_points = (uint32_t)point->size();
+      }
+      L.rows_of_stream[R.stream] = (uint32_t)L.rows.size();
+      L.rows.push_back(R);
     }
     for (size_t k = 0; k < pl.atts.size(); ++k) {
       const synth::PortableAttr &a = pl.atts[k];
@@ -710,6 +749,7 @@ static void enc_layout(EncChunk &ck) {
         S.e2v = Z.e2v; S.ops = Z.ops;
       }
       enc_value_stream_regions(S, cap, ck.hist_cap_of(i, k), A);
+      if (ck.rq.track_rows) { dsa::EncRows &R = L.rows[L.rows_of_stream[s0 + k]]; R.cap = cap; R.out = A.take(4ull * cap); }
       L.max_rows = std::max(L.max_rows, std::max(S.rows, cap));
       if (!enc_topo_scheme(a)) continue;
       if (C) { const uint64_t c2row = S.t_c2p; S.t_c2p = S.t_c2a = C->faces; S.t_opp = C->opp; S.t_d2c = pd ? C->pd_d2c : C->d2c; S.t_v2d = pd ? C->pd_v2d : C->v2d; if (!ck.rep.empty()) S.t_c2p = c2row; }      // the connectivity's own (a repaired table: positions by row)

@@ -50,6 +50,7 @@ static dsa_status encode_sequential_chunk(dsa_context *ctx, EncLane &lane, const
   ck.host_plan = enc_host_choice("DSA_ENC_HOST_PLAN", batch_n);
   hostutil::parallel_for(count, [&](uint32_t i) { enc_check_sequential_mesh(ck, i); });
   enc_layout_sequential(ck);
+  for (uint32_t i = 0; i < count; ++i) if (ck.good(i)) ck.E->linear[i] = {(uint32_t)ck.plans[i].atts.size(), ck.mesh(i).num_vertices};      // (dsa_encoded_entry_rows: entry i is row i)
   if (!ck.L.streams.empty()) {
     ENC_STAGE(enc_stage_uploads(ctx, lane, turn, ck));
     ENC_STAGE(enc_stage_attributes(ctx, lane, ck));

@@ -474,6 +474,65 @@ class Batch:
             out["attributes"].append({"info": ai, "values": values, "quantization": self._vertex_quantization(ai, va)})
         return out
 
+    # ---- source rows (dsa_batch_source_rows): which row of the encoder's input every point carries, gathered on the device
+    def source_rows(self, encoded, encoded_mesh=None, wait=True, device_only=False):
+        """For a batch made from the streams of `encoded` (the EncodedStreams of EncodeBatch with Config(track_rows=True), or of a
+        sequential config): per mesh a list with one uint32 array per attribute of the stream, element p the row of the array the
+        encoder was given for that attribute which point p of the decoded mesh carries (with weld_points: the point of the
+        per-point arrays) -- rows[a][p] = entry_rows[a][point_map[a][p]], gathered on the device behind the batch's kernels and
+        brought down in ONE transfer.  encoded_mesh[i]: the stream of `encoded` mesh i was created from (None: stream i).
+        Returns the list (views of the library's host copy; with device_only torch tensors over the device block, nothing is
+        transferred), a mesh that has no arrays -- it failed, or its stream is not the one named -- represented by the exception
+        that says why; with wait=False None: source_row_views(i) after wait().  `encoded` must stay open until then.  Valid until
+        the batch is closed, decoded again or asked for source rows again."""
+        if not self._h:
+            raise DeviceException("the batch is closed")
+        if getattr(encoded, "_h", None) is None:
+            raise ValueError("source_rows takes the open EncodedStreams the batch's streams came from")
+        em = None
+        if encoded_mesh is not None:
+            em = np.ascontiguousarray(encoded_mesh, np.uint32)
+            if em.shape != (self.n,):
+                raise ValueError("encoded_mesh: one stream index per mesh of the batch")
+        self._rows_of = (encoded, em)                    # (the library reads the handle until the wait is over)
+        st = self._L.dsa_batch_source_rows(self._h, encoded._h, None if em is None else em.ctypes.data, None,
+                                           native.DSA_SOURCE_ROWS_DEVICE_ONLY if device_only else 0)
+        if st != 0:
+            _raise(st, self.ctx.error())
+        if not wait:
+            return None
+        self.wait()
+        out = []
+        for i in range(self.n):
+            try:
+                out.append(self.source_row_views(i, device=device_only))
+            except Exception as e:          # noqa: BLE001  (the exception is the mesh's result)
+                out.append(e)
+        return out
+
+    def source_row_views(self, i, device=False):
+        """The arrays of mesh i of the most recent source_rows(): a list of uint32[num_points] per attribute, zero-copy views of the
+        host copy, or with device=True torch int32 tensors (the same bits) over the device block (as for device_views, torch.cuda
+        must have been initialised before the first Context of the process)."""
+        lay = native.MeshSourceRows()
+        st = self._L.dsa_batch_source_rows_layout(self._h, i, C.byref(lay))
+        if st != 0:
+            _raise(st, self.ctx.error())
+        base = (self._L.dsa_batch_device_source_rows if device else self._L.dsa_batch_host_source_rows)(self._h, lay.block)
+        if not base:
+            raise RuntimeError("the batch has no source rows %s (Batch.source_rows, then wait)" % ("on the device" if device else "on the host"))
+        if device:
+            import torch
+            dev = "cuda:%d" % self.ctx.device
+
+            class _Ptr:                                    # __cuda_array_interface__ v2 carrier
+                def __init__(self, ptr, shape):
+                    self.__cuda_array_interface__ = {"shape": shape, "typestr": "<i4", "data": (int(ptr), False), "version": 2}
+            return [torch.as_tensor(_Ptr(base + lay.rows[a], (lay.num_points,)), device=dev) if lay.num_points else torch.empty((0,), dtype=torch.int32, device=dev)
+                    for a in range(lay.num_attributes)]
+        return [np.frombuffer((C.c_uint8 * (4 * lay.num_points)).from_address(base + lay.rows[a]), np.uint32, lay.num_points) if lay.num_points else np.zeros(0, np.uint32)
+                for a in range(lay.num_attributes)]
+
     @property
     def algorithmic_bytes(self):
         return int(self._L.dsa_batch_algorithmic_bytes(self._h))

@@ -52,7 +52,12 @@ class Config:
     weld_attributes (dsa_encode_corner_attributes_batch; needs weld_points): the attributes of the list leave the vertex key and
     are welded each alone, like normals and texture coordinates -- a lightmap UV set with its own charts or a colour with a hard
     edge then cuts its own connectivity only, and positions are not duplicated along its seams.  An attribute whose index in the
-    stream is above 7 stays in the vertex key (the decoder takes corner attributes for attribute data 0 to 6)."""
+    stream is above 7 stays in the vertex key (the decoder takes corner attributes for attribute data 0 to 6).
+
+    track_rows (dsa_encode_rows_batch): the result keeps, per stream and attribute, which row of the arrays passed every entry of
+    the stream carries (EncodedStreams.entry_rows) -- what carries morph targets or simulation state across Edgebreaker's
+    renumbering, the repair's new vertices and the weld.  The streams are the bytes they are without it; 4 bytes per entry and
+    attribute are kept.  Sequential streams need no tracking: their entry i is row i."""
 
     EDGEBREAKER_METHODS = (0, 2, -1)
     POSITION_PREDICTIONS = (0, 1)
@@ -65,7 +70,7 @@ class Config:
     def __init__(self, position_bits=11, texcoord_bits=10, normal_bits=8, speed=5, single_connectivity=False,
                  symbol_scheme=-1, position_prediction=1, texcoord_prediction=1, edgebreaker_method=0, normal_prediction=0,
                  encoding_method=1, compress_connectivity=False, multi_parallelogram=0, traversal_method=0, repair_topology=False, weld_points=False,
-                 repair_seams=False, weld_attributes=False):
+                 repair_seams=False, weld_attributes=False, track_rows=False):
         for name, value, legal in (("encoding_method", encoding_method, self.ENCODING_METHODS),
                                    ("edgebreaker_method", edgebreaker_method, self.EDGEBREAKER_METHODS),
                                    ("position_prediction", position_prediction, self.POSITION_PREDICTIONS),
@@ -97,6 +102,7 @@ class Config:
         self.weld_attributes = bool(weld_attributes)
         if self.weld_attributes and not self.weld_points:
             raise ValueError("weld_attributes welds the listed attributes of per-point input each alone: it needs weld_points=True")
+        self.track_rows = bool(track_rows)
 
     @property
     def sequential(self):
@@ -443,6 +449,7 @@ class EncodedStreams:
 
     def __init__(self, ctx, handle, n):
         L = native.lib()
+        self._ctx = ctx
         self._h, self._free = handle, L.dsa_encoded_free
         self._ptr, self._len, self._cache = [0] * n, [0] * n, [None] * n
         p, ln = C.c_void_p(), C.c_size_t()
@@ -481,6 +488,15 @@ class EncodedStreams:
     def __eq__(self, other):
         return len(self) == len(other) and all(a == b for a, b in zip(self, other))
 
+    def entry_rows(self, i):
+        """Of stream i a list with one uint32 array per attribute of the stream (positions, then normals, texture coordinates,
+        generic where present, then the attribute list): element e is the row of the array passed for that attribute whose bytes
+        entry e of the stream carries -- with weld_points a point of the per-point arrays.  Needs Config(track_rows=True), or a
+        sequential stream (the identity); dsa_encoded_entry_rows."""
+        if self._h is None:
+            raise ValueError("the encoded batch was closed")
+        return _entry_rows(self._ctx, self._h, i + len(self) if i < 0 else i)
+
     def close(self):
         """Releases the library's buffers (streams already taken stay valid)."""
         if self._h is not None:
@@ -489,6 +505,49 @@ class EncodedStreams:
 
     def __del__(self):
         self.close()
+
+
+class TriedStreams(list):
+    """What TryEncodeBatch returns: per mesh the stream or the exception; `encoded`: with keep=True the open handle, else None."""
+    encoded = None
+
+
+class _EncodedHandle:
+    """An encoded batch some of whose meshes may have failed (TryEncodeBatch(keep=True)): what Batch.source_rows and entry_rows need."""
+
+    def __init__(self, ctx, handle):
+        self._ctx, self._h = ctx, handle
+
+    def entry_rows(self, i):
+        return _entry_rows(self._ctx, self._h, i)
+
+    def close(self):
+        if self._h is not None:
+            native.lib().dsa_encoded_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+
+def _entry_rows(ctx, handle, i):
+    """dsa_encoded_entry_rows of mesh i for every attribute dsa_encoded_attributes counts."""
+    L = native.lib()
+    count = C.c_uint32()
+    st = L.dsa_encoded_attributes(handle, i, C.byref(count))
+    if st != 0:
+        _raise(st, ctx.error())
+    out = []
+    for a in range(count.value):
+        st = L.dsa_encoded_entry_rows(handle, i, a, None, 0, C.byref(count))
+        if st != 0:
+            _raise(st, ctx.error())
+        rows = np.empty(count.value, np.uint32)
+        st = L.dsa_encoded_entry_rows(handle, i, a, rows.ctypes.data, len(rows), C.byref(count))
+        if st != 0:
+            _raise(st, ctx.error())
+        out.append(rows)
+    return out
 
 
 class WeldedMaps:
@@ -554,8 +613,10 @@ class DracoEncoder:
         h = C.c_void_p()
         weld_attributes = getattr(config, "weld_attributes", False)
         t0 = time.perf_counter()
-        if weld_attributes or any(_has_attribute_ids(m) for m in meshes):
-            # ids on attributes of the list, or the list welded attribute by attribute: the one call that takes them
+        track_rows = getattr(config, "track_rows", False)
+        if track_rows or weld_attributes or any(_has_attribute_ids(m) for m in meshes):
+            # ids on attributes of the list, or the list welded attribute by attribute: the one call that takes them -- and, with
+            # track_rows, the one beyond it whose handle keeps the entry rows
             wide = native.EncodeCornerAttributesOptions()
             L.dsa_encode_default_corner_attributes_options(C.byref(wide))
             wide.seam_repair = opt
@@ -563,7 +624,14 @@ class DracoEncoder:
             corners = (native.MeshAttributeCorners * max(1, n))()
             for i, m in enumerate(meshes):
                 _fill_attribute_corners(corners[i], m, keep)
-            st = L.dsa_encode_corner_attributes_batch(ctx._h, n, arr, grids, corners, C.byref(wide), C.byref(h))
+            if track_rows:
+                widest = native.EncodeRowsOptions()
+                L.dsa_encode_default_rows_options(C.byref(widest))
+                widest.corner_attributes = wide
+                widest.track_rows = 1
+                st = L.dsa_encode_rows_batch(ctx._h, n, arr, grids, corners, C.byref(widest), C.byref(h))
+            else:
+                st = L.dsa_encode_corner_attributes_batch(ctx._h, n, arr, grids, corners, C.byref(wide), C.byref(h))
         else:
             st = L.dsa_encode_seam_repair_batch(ctx._h, n, arr, grids, C.byref(opt), C.byref(h))
         t1 = time.perf_counter()
@@ -586,12 +654,13 @@ class DracoEncoder:
             _raise(st, ctx.error())
         return (ctx, h, n) if handle else EncodedStreams(ctx, h, n)
 
-    def TryEncodeBatch(self, meshes, config=None):
+    def TryEncodeBatch(self, meshes, config=None, keep=False):
         """EncodeBatch that keeps the meshes the encoder refuses: a list with, per mesh, the stream as bytes or the exception (its text says why)
-        that EncodeBatch would have raised for it.  A failure of the call itself still raises."""
+        that EncodeBatch would have raised for it.  A failure of the call itself still raises.  keep=True: the list is a TriedStreams
+        whose `encoded` is the open handle (entry_rows(i), close(); what Batch.source_rows takes), which the caller closes."""
         ctx, h, n = self.EncodeBatch(meshes, config, handle=True)
         L = native.lib()
-        out = []
+        out = TriedStreams()
         p, ln = C.c_void_p(), C.c_size_t()
         try:
             for i in range(n):
@@ -603,8 +672,11 @@ class DracoEncoder:
                     _raise(st, ctx.error())
                 except Exception as e:          # noqa: BLE001  (the exception is the result)
                     out.append(e)
+            if keep:
+                out.encoded, h = _EncodedHandle(ctx, h), None
         finally:
-            L.dsa_encoded_free(h)
+            if h is not None:
+                L.dsa_encoded_free(h)
         return out
 
     def WeldBatch(self, meshes):

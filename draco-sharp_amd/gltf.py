@@ -272,8 +272,9 @@ class PlannedPrimitive:
     """A primitive the writer compresses: where it sits, its MeshData (one row per point, as the accessors give them) and the
     Draco unique id of every semantic (the attribute's index in the stream)."""
 
-    def __init__(self, asset, mesh, primitive, data, attribute_ids):
+    def __init__(self, asset, mesh, primitive, data, attribute_ids, targets=None):
         self.asset, self.mesh, self.primitive, self.data, self.attribute_ids = asset, mesh, primitive, data, attribute_ids
+        self.targets = targets or []        # morph targets: per target {semantic: deltas, one row per point of the primitive}
 
 
 class SkippedPrimitive:
@@ -295,13 +296,27 @@ def _listed_semantic(semantic):
     return 4 if head in ("JOINTS", "WEIGHTS") else None
 
 
-def plan_compression(assets, shared_grid=None):
+def _weld_conflict(key_rows, deltas, used):
+    """Do two used points whose rows in every array of `key_rows` are byte-equal have different rows in `deltas`?  (The weld joins
+    such points, and the stream carries the row of one of them: the other's delta would be lost.)"""
+    key = np.concatenate([np.ascontiguousarray(k).view(np.uint8).reshape(len(k), -1) for k in key_rows], axis=1)[used]
+    d = np.ascontiguousarray(deltas).view(np.uint8).reshape(len(deltas), -1)[used]
+    _, first, inverse = np.unique(key, axis=0, return_index=True, return_inverse=True)
+    return bool((d != d[first[inverse.reshape(-1)]]).any())
+
+
+def plan_compression(assets, shared_grid=None, weld_attributes=False):
     """Needs no device.  (planned, skipped): every TRIANGLES primitive with float32 VEC3 POSITION and indices becomes a MeshData
     -- NORMAL (float32 VEC3) and TEXCOORD_0 (float32 VEC2) as built-ins, COLOR_n, JOINTS_n, WEIGHTS_n, TEXCOORD_n in other forms
     through the attribute list in their component types -- every other primitive is skipped with the reason.
     shared_grid="mesh": the planned primitives of one glTF mesh, and only those, are one group whose positions share a quantisation
     grid (Grid.shared(): a vertex on the cut between two primitives decodes to the same floats in both); None: every primitive
-    on its own bounds."""
+    on its own bounds.
+    Morph targets (`targets`) ride beside the stream: the writer carries their deltas across the encode by the rows the encoder
+    tracks (GltfDracoWriter.compress).  A primitive is skipped when a target names a semantic that has no base attribute of that
+    name in the stream, or with "morph target k of S differs between points the weld joins" when two points whose rows in the key
+    set S is welded by are byte-equal have different deltas (weld_attributes: as the Config of the encode will have it -- the
+    attributes of the list are then key sets of their own, else part of the positions' key)."""
     from .encoder import Attribute, Grid, MeshData
     if shared_grid not in (None, "mesh"):
         raise ValueError("shared_grid %r: None or \"mesh\"" % (shared_grid,))
@@ -321,8 +336,6 @@ def plan_compression(assets, shared_grid=None):
                     skip("mode %d: only TRIANGLES (4) are compressed" % prim.get("mode")); continue
                 if prim.get("indices") is None:
                     skip("no indices"); continue
-                if prim.get("targets"):
-                    skip("morph targets are not carried into the stream"); continue
                 if "POSITION" not in atts:
                     skip("no POSITION"); continue
 
@@ -362,6 +375,34 @@ def plan_compression(assets, shared_grid=None):
                     rows = [normals, texcoords] + [a.values for a in listed]
                     if why is None and any(r is not None and len(r) != len(pos) for r in rows):
                         why = "attribute accessors of different counts"
+                    targets, used = [], None
+                    if why is None and prim.get("targets"):      # (the points the faces name: what the weld looks at)
+                        used = np.unique(idx.astype(np.int64))
+                        if int(used.max()) >= len(pos):
+                            why = "morph targets over indices out of range"
+                    for k, target in enumerate(prim.get("targets") or []):
+                        if why is not None:
+                            break
+                        deltas = {}
+                        for semantic, accessor in target.items():
+                            if semantic not in ids:
+                                why = "morph target %d of %s: no base attribute of that name in the stream" % (k, semantic)
+                                break
+                            d = read_accessor(asset, accessor)
+                            if len(d) != len(pos):
+                                why = "attribute accessors of different counts"
+                                break
+                            # the key set the semantic is welded by: its own rows, or for what stays in the vertex key that key
+                            in_key = [pos] + [a.values for j, a in enumerate(listed) if not weld_attributes or 1 + (normals is not None) + (texcoords is not None) + j > 7]
+                            own = {"NORMAL": normals, "TEXCOORD_0": texcoords}.get(semantic)
+                            if own is None and semantic != "POSITION":
+                                j = ids[semantic] - 1 - (normals is not None) - (texcoords is not None)
+                                own = listed[j].values if weld_attributes and ids[semantic] <= 7 else None
+                            if _weld_conflict(in_key if own is None else [own], d, used):
+                                why = "morph target %d of %s differs between points the weld joins" % (k, semantic)
+                                break
+                            deltas[semantic] = d
+                        targets.append(deltas)
                     if why is not None:
                         skip(why); continue
                 except InvalidDataException as e:
@@ -370,7 +411,7 @@ def plan_compression(assets, shared_grid=None):
                     data = MeshData(pos, idx.astype(np.uint32).reshape(-1, 3), normals, texcoords, attributes=listed, position_grid=Grid.shared(), group=groups)
                 else:
                     data = MeshData(pos, idx.astype(np.uint32).reshape(-1, 3), normals, texcoords, attributes=listed)
-                planned.append(PlannedPrimitive(asset, mi, pi, data, ids))
+                planned.append(PlannedPrimitive(asset, mi, pi, data, ids, targets))
     return planned, skipped
 
 
@@ -410,7 +451,8 @@ def _used_accessors(doc):
 
 def rewrite_asset(asset, coded):
     """Needs no device.  The asset as GLB bytes with the primitives of `coded` -- {(mesh, primitive): (stream, num_points, num_faces,
-    {semantic: unique id})} -- carrying KHR_draco_mesh_compression: the stream in a buffer view of its own, accessors of the
+    {semantic: unique id})}, with morph targets a fifth element [{semantic: deltas, one row per point of the stream}] that is
+    written as uncompressed accessors of num_points rows (min / max recomputed) -- carrying KHR_draco_mesh_compression: the stream in a buffer view of its own, accessors of the
     decoded counts without buffer views (copies: an accessor may serve other primitives), extensionsUsed / extensionsRequired.
     Accessors no primitive, animation or skin names any more lose their buffer views, buffer views nothing names are dropped, and
     what is left is packed into the one binary chunk."""
@@ -419,7 +461,8 @@ def rewrite_asset(asset, coded):
     views = doc.setdefault("bufferViews", [])
     before = _used_accessors(doc)
     streams = []
-    for (mi, pi), (stream, num_points, num_faces, ids) in sorted(coded.items()):
+    for (mi, pi), entry in sorted(coded.items()):
+        stream, num_points, num_faces, ids = entry[:4]
         prim = doc["meshes"][mi]["primitives"][pi]
 
         def fresh(index, count):
@@ -432,6 +475,18 @@ def rewrite_asset(asset, coded):
         streams.append(bytes(stream))
         views.append({"buffer": -1 - (len(streams) - 1), "byteLength": len(stream)})        # (negative: stream k, placed below)
         prim.setdefault("extensions", {})[EXTENSION] = {"bufferView": len(views) - 1, "attributes": {s: int(i) for s, i in ids.items()}}
+        for k, deltas in enumerate(entry[4] if len(entry) > 4 else []):
+            for semantic, rows in deltas.items():
+                rows = np.ascontiguousarray(rows)
+                acc = {key: v for key, v in accessors[prim["targets"][k][semantic]].items() if key not in ("bufferView", "byteOffset", "sparse", "min", "max")}
+                acc["count"] = int(num_points)
+                if len(rows) and (semantic == "POSITION" or "min" in accessors[prim["targets"][k][semantic]]):
+                    acc["min"], acc["max"] = rows.min(axis=0).tolist(), rows.max(axis=0).tolist()
+                streams.append(rows.tobytes())
+                views.append({"buffer": -1 - (len(streams) - 1), "byteLength": rows.nbytes})
+                acc["bufferView"] = len(views) - 1
+                accessors.append(acc)
+                prim["targets"][k][semantic] = len(accessors) - 1
     if coded:
         for key in ("extensionsUsed", "extensionsRequired"):
             if EXTENSION not in doc.setdefault(key, []):
@@ -494,32 +549,46 @@ class GltfDracoWriter:
         than its primitive had where seams cross.  Config(weld_points=True, weld_attributes=True): the attributes of the list
         (TEXCOORD_1 with lightmap charts of its own, COLOR_0 with a hard edge) are welded each alone instead of being part of the
         vertex key, so their seams do not duplicate positions, normals and TEXCOORD_0; the extension's attribute ids and the accessor
-        counts follow the stream as ever.  Returns a CompressedAsset per source."""
+        counts follow the stream as ever.  A primitive with morph targets is coded with track_rows: Batch.source_rows on the decode
+        batch says which point of the primitive every point of the stream carries, and every target accessor is rewritten,
+        uncompressed, with num_points rows delta[rows[S][p]] (plan_compression skips what cannot be carried).  Returns a
+        CompressedAsset per source."""
         import copy
         from .encoder import Config, DracoEncoder
         assets = [s if isinstance(s, GltfAsset) else read_asset(s) for s in sources]
-        planned, skipped = plan_compression(assets, shared_grid)
         cfg = copy.copy(config) if config is not None else Config()
         cfg.weld_points = True
+        planned, skipped = plan_compression(assets, shared_grid, getattr(cfg, "weld_attributes", False))
+        cfg.track_rows = any(p.targets for p in planned)
         if cfg.sequential:
             raise ValueError("the writer codes Edgebreaker streams (weld_points): a sequential config keeps the caller's points")
         coded = {id(a): {} for a in assets}
         if planned:
-            streams = DracoEncoder(self.ctx).TryEncodeBatch([p.data for p in planned], cfg)
-            good = [k for k, s in enumerate(streams) if isinstance(s, bytes)]
-            for k, s in enumerate(streams):
-                if not isinstance(s, bytes):
-                    skipped.append(SkippedPrimitive(planned[k].asset, planned[k].mesh, planned[k].primitive, "the encoder refused it: %s" % s))
-            if good:
-                batch = Batch(self.ctx, [streams[k] for k in good])
-                try:
+            streams = DracoEncoder(self.ctx).TryEncodeBatch([p.data for p in planned], cfg, keep=cfg.track_rows)
+            encoded, batch = streams.encoded, None
+            try:
+                good = [k for k, s in enumerate(streams) if isinstance(s, bytes)]
+                for k, s in enumerate(streams):
+                    if not isinstance(s, bytes):
+                        skipped.append(SkippedPrimitive(planned[k].asset, planned[k].mesh, planned[k].primitive, "the encoder refused it: %s" % s))
+                if good:
+                    batch = Batch(self.ctx, [streams[k] for k in good])
                     batch.decode()
+                    rows = batch.source_rows(encoded, encoded_mesh=good) if encoded is not None else None
                     for j, k in enumerate(good):
                         info = batch.mesh_info(j)
                         p = planned[k]
-                        coded[id(p.asset)][(p.mesh, p.primitive)] = (streams[k], info.num_points, info.num_faces, p.attribute_ids)
-                finally:
+                        moved = []
+                        if p.targets:
+                            if isinstance(rows[j], Exception):
+                                raise rows[j]
+                            moved = [{s: d[rows[j][p.attribute_ids[s]].astype(np.int64)] for s, d in t.items()} for t in p.targets]
+                        coded[id(p.asset)][(p.mesh, p.primitive)] = (streams[k], info.num_points, info.num_faces, p.attribute_ids, moved)
+            finally:
+                if batch is not None:
                     batch.close()
+                if encoded is not None:
+                    encoded.close()
         out = []
         for a in assets:
             mine = coded[id(a)]

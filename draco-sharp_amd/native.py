@@ -16,6 +16,7 @@ DSA_VA_DEVICE_ONLY = 1                      # dsa_vertex_request.flags
 DSA_VA_ABSENT = 1                           # dsa_vertex_attribute.flags
 DSA_VA_INDICES_U16 = 1                      # dsa_mesh_vertex_arrays.flags
 VA_NONE = 0xFFFFFFFFFFFFFFFF                # an array that is not in the block
+DSA_SOURCE_ROWS_DEVICE_ONLY = C.c_size_t(-1).value      # dsa_batch_source_rows: dst NULL with this dst_bytes: no host copy
 
 # every symbol include/draco_mi355x.h declares
 EXPORTS = [
@@ -26,6 +27,7 @@ EXPORTS = [
     "dsa_batch_copy_portable_values", "dsa_batch_device_faces", "dsa_batch_device_attribute_values",
     "dsa_batch_device_point_map", "dsa_batch_output_bytes", "dsa_batch_download", "dsa_batch_compact_bytes", "dsa_batch_download_compact", "dsa_batch_host_output", "dsa_batch_output_layout",
     "dsa_batch_vertex_arrays_bytes", "dsa_batch_vertex_arrays", "dsa_batch_vertex_arrays_layout", "dsa_batch_host_vertex_arrays", "dsa_batch_device_vertex_arrays",
+    "dsa_batch_source_rows_bytes", "dsa_batch_source_rows", "dsa_batch_source_rows_layout", "dsa_batch_host_source_rows", "dsa_batch_device_source_rows",
     "dsa_host_alloc", "dsa_host_free", "dsa_host_register", "dsa_host_unregister", "dsa_batch_copy_metadata", "dsa_batch_copy_debug", "dsa_context_set_profiling", "dsa_batch_stage_times",
     "dsa_batch_kernel_times", "dsa_context_trim", "dsa_context_schedule_note",
     "dsa_encode_default_options", "dsa_encode_batch", "dsa_encode_batch_corners",
@@ -37,6 +39,7 @@ EXPORTS = [
     "dsa_encode_default_grid_options", "dsa_encode_grid_batch", "dsa_encode_grid_sequential_batch",
     "dsa_encode_default_seam_repair_options", "dsa_encode_seam_repair_batch",
     "dsa_encode_default_corner_attributes_options", "dsa_encode_corner_attributes_batch",
+    "dsa_encode_default_rows_options", "dsa_encode_rows_batch", "dsa_encoded_entry_rows", "dsa_encoded_attributes",
     "dsa_encoded_size", "dsa_encoded_stream", "dsa_encoded_free",
     "dsa_pool_create", "dsa_pool_destroy", "dsa_pool_size", "dsa_pool_last_error", "dsa_pool_decode", "dsa_pool_job_locate",
     "dsa_pool_job_chunks", "dsa_pool_job_free", "dsa_pool_plan",
@@ -144,6 +147,12 @@ class EncodeCornerAttributesOptions(C.Structure):
     _fields_ = [("seam_repair", EncodeSeamRepairOptions), ("weld_attributes", C.c_int32), ("reserved", C.c_int32 * 7)]
 
 
+class EncodeRowsOptions(C.Structure):
+    """dsa_encode_rows_options: the options of dsa_encode_corner_attributes_batch, and track_rows (1: the handle keeps, per stream
+    and attribute, the row of the caller's arrays every entry carries: dsa_encoded_entry_rows)."""
+    _fields_ = [("corner_attributes", EncodeCornerAttributesOptions), ("track_rows", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
 class WeldedInfo(C.Structure):
     """dsa_welded_info: the weld of one mesh given as one row per point -- counts, whether normals / texture coordinates collapse
     to one row per vertex, and the six maps (host memory owned by the dsa_welded handle)."""
@@ -178,6 +187,11 @@ class VertexAttribute(C.Structure):
 class MeshVertexArrays(C.Structure):
     _fields_ = [("block", C.c_uint32), ("flags", C.c_uint32), ("indices", C.c_uint64), ("num_points", C.c_uint32), ("num_indices", C.c_uint32),
                 ("attributes", VertexAttribute * 16)]
+
+
+class MeshSourceRows(C.Structure):
+    """dsa_mesh_source_rows: where the arrays of one mesh lie in the block of dsa_batch_source_rows."""
+    _fields_ = [("block", C.c_uint32), ("num_points", C.c_uint32), ("num_attributes", C.c_uint32), ("reserved", C.c_uint32), ("rows", C.c_uint64 * 16)]
 
 
 class AttributeInfo(C.Structure):
@@ -250,6 +264,14 @@ def lib():
         for f in ("dsa_batch_host_vertex_arrays", "dsa_batch_device_vertex_arrays"):
             getattr(L, f).restype = vp
             getattr(L, f).argtypes = [vp, u32]
+        if hasattr(L, "dsa_batch_source_rows"):
+            L.dsa_batch_source_rows_bytes.restype = C.c_uint64
+            L.dsa_batch_source_rows_bytes.argtypes = [vp, vp, vp]
+            L.dsa_batch_source_rows.argtypes = [vp, vp, vp, vp, C.c_size_t]
+            L.dsa_batch_source_rows_layout.argtypes = [vp, u32, C.POINTER(MeshSourceRows)]
+            for f in ("dsa_batch_host_source_rows", "dsa_batch_device_source_rows"):
+                getattr(L, f).restype = vp
+                getattr(L, f).argtypes = [vp, u32]
         L.dsa_host_alloc.restype = vp
         L.dsa_host_alloc.argtypes = [C.c_size_t]
         L.dsa_host_free.restype = None
@@ -305,6 +327,13 @@ def lib():
             L.dsa_encode_default_corner_attributes_options.restype = None
             L.dsa_encode_corner_attributes_batch.argtypes = [vp, u32, C.POINTER(MeshAttrInput), C.POINTER(MeshGrids), C.POINTER(MeshAttributeCorners),
                                                              C.POINTER(EncodeCornerAttributesOptions), C.POINTER(vp)]
+        if hasattr(L, "dsa_encode_rows_batch"):
+            L.dsa_encode_default_rows_options.argtypes = [C.POINTER(EncodeRowsOptions)]
+            L.dsa_encode_default_rows_options.restype = None
+            L.dsa_encode_rows_batch.argtypes = [vp, u32, C.POINTER(MeshAttrInput), C.POINTER(MeshGrids), C.POINTER(MeshAttributeCorners),
+                                                C.POINTER(EncodeRowsOptions), C.POINTER(vp)]
+            L.dsa_encoded_entry_rows.argtypes = [vp, u32, u32, vp, C.c_size_t, C.POINTER(u32)]
+            L.dsa_encoded_attributes.argtypes = [vp, u32, C.POINTER(u32)]
         L.dsa_encoded_size.restype = u32
         L.dsa_encoded_size.argtypes = [vp]
         L.dsa_encoded_stream.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(C.c_size_t)]

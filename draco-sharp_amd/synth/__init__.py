@@ -219,6 +219,9 @@ def lib():
         L.synth_encode_corner_attributes_grid.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                                           C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(ExtraInput), C.POINTER(ExtraCornersInput),
                                                           C.c_uint32, C.POINTER(GridsInput), C.POINTER(Options), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+        L.synth_entry_rows.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                       C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(ExtraInput), C.POINTER(ExtraCornersInput),
+                                       C.c_uint32, C.POINTER(Options), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.synth_weld_points.restype = C.c_void_p
         L.synth_weld_points.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.POINTER(ExtraInput), C.c_uint32, C.POINTER(Options)]
@@ -507,6 +510,37 @@ def encode_grid(pos, faces=None, normals=None, uvs=None, generic=None, extra=Non
     data = C.string_at(out, n.value)
     L.synth_free(out)
     return data
+
+
+def entry_rows(pos, faces=None, normals=None, uvs=None, generic=None, extra=None, opt=None, form=1, normal_corners=None, uv_corners=None,
+               geometry=1, weld_attributes=False):
+    """The entry rows of the stream encode_grid writes for the same arguments: a list with one uint32 array per attribute of the
+    stream (positions, then normals, texture coordinates, generic where present, then `extra`), element e the row of the value array
+    passed for that attribute whose bytes entry e of the stream carries.  form 1: the vertex, or the row id of an attribute given
+    per corner; with opt.repair_topology a vertex the repair made reads its root parent's row.  form 2 (one row per point): the
+    point whose row was read -- the representative of the attribute's key set, of the vertex where the attribute went on per vertex.
+    form 0: the identity.  What dsa_encoded_entry_rows must report."""
+    L = lib()
+    pos, fc, nrm, uv, gen, extra, arr, opt = _points_args(pos, np.zeros((0, 3), np.uint32) if faces is None else faces, normals if normal_corners is None else None,
+                                                          uvs if uv_corners is None else None, generic, extra, opt)
+    if normal_corners is not None:
+        nrm = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    if uv_corners is not None:
+        uv = np.ascontiguousarray(uvs, np.float32).reshape(-1, 2)
+    nci = None if normal_corners is None else np.ascontiguousarray(normal_corners, np.uint32)
+    uci = None if uv_corners is None else np.ascontiguousarray(uv_corners, np.uint32)
+    ptr = lambda a: None if a is None else a.ctypes.data          # noqa: E731
+    out, counts, na = C.c_void_p(), (C.c_uint32 * 32)(), C.c_uint32()
+    rc = L.synth_entry_rows(form, ptr(pos), len(pos), ptr(fc) if len(fc) else None, len(fc), ptr(nrm), 0 if nrm is None else len(nrm), ptr(nci),
+                            ptr(uv), 0 if uv is None else len(uv), ptr(uci), ptr(gen), geometry, arr, _extra_corners(extra, len(fc)), len(extra),
+                            C.byref(opt), 1 if weld_attributes else 0, C.byref(out), counts, C.byref(na))
+    if rc:
+        raise RuntimeError(_err())
+    total = sum(counts[a] for a in range(na.value))
+    flat = np.frombuffer(C.string_at(out, 4 * total), np.uint32).copy() if total else np.zeros(0, np.uint32)
+    L.synth_free(out)
+    ends = np.cumsum([counts[a] for a in range(na.value)]).tolist()
+    return [flat[e - counts[a]:e] for a, e in enumerate(ends)]
 
 
 def encode_mesh_sequential(pos, faces, normals=None, uvs=None, compressed=True, opt=None):

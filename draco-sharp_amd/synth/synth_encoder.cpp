@@ -402,7 +402,8 @@ struct synth_grids { synth::Grid position, texcoord; const synth::Grid *attribut
 static int encode_grid(int form, const float *pos, uint32_t nv, const uint32_t *faces, uint32_t nf, const float *normals, uint32_t nn,
                        const uint32_t *normal_corners, const float *uvs, uint32_t nu, const uint32_t *uv_corners, const void *generic,
                        int geometry, int compressed, const synth_extra *extras, const synth_extra_corners *extra_corners, uint32_t num_extras,
-                       const synth_grids *grids, const synth_options *opt, int weld_attributes, uint8_t **out, size_t *out_len) {
+                       const synth_grids *grids, const synth_options *opt, int weld_attributes, uint8_t **out, size_t *out_len,
+                       std::vector<std::vector<uint32_t>> *rows = nullptr) {      // rows: the entry rows of the stream in place of its bytes (synth_entry_rows)
   try {
     synth::check(form >= 0 && form <= 2, "form: 0 (sequential), 1 (Edgebreaker) or 2 (one row per point)");
     std::vector<synth::ExtraAttr> ex, ex2;
@@ -428,6 +429,13 @@ static int encode_grid(int form, const float *pos, uint32_t nv, const uint32_t *
       synth::check(pos != nullptr && nv > 0, "positions are missing");
       synth::check(geometry == 0 || (faces != nullptr && nf > 0), "a mesh needs faces");
       for (size_t k = 0; k < (size_t)nf * 3; ++k) synth::check(faces[k] < nv, "face index out of range");
+      if (rows) {                                              // linear order: entry i is row i of every attribute
+        std::vector<synth::PortableAttr> atts;
+        synth::check(!synth::extras_have_corners(in), "a sequential stream has one value per point");
+        synth::plan_sequential_attributes(in, o, atts);
+        rows->assign(atts.size(), std::vector<uint32_t>(nv));
+        for (auto &r : *rows) for (uint32_t v = 0; v < nv; ++v) r[v] = v;
+      } else
       synth::encode_sequential(in, o, geometry == 1, compressed != 0, buf);
     } else if (form == 1) {
       in.normal_corners = normals ? normal_corners : nullptr; in.nn = nn;
@@ -438,7 +446,7 @@ static int encode_grid(int form, const float *pos, uint32_t nv, const uint32_t *
         synth::check(!in.uv_corners || in.uv_corners[k] < nu, "texture coordinate id out of range");
       }
       { const std::string why = synth::extras_id_error(in); synth::check(why.empty(), why.c_str()); }
-      synth::encode_mesh(in, o, buf);
+      if (rows) synth::entry_rows(in, o, *rows); else synth::encode_mesh(in, o, buf);
     } else {
       synth::Welded w;
       std::vector<synth::WeldSeg> listed;
@@ -447,8 +455,9 @@ static int encode_grid(int form, const float *pos, uint32_t nv, const uint32_t *
       const synth::MeshIn m = synth::welded_mesh_in(in, w, ex2);
       synth::check(!(o.repair_topology && pos && nv >= 3 && nf == 0), "all triangles are degenerate");
       synth::check(m.pos && m.faces && m.nv >= 3 && m.nf >= 1, "mesh needs positions and faces");
-      synth::encode_mesh(m, o, buf);
+      if (rows) synth::welded_entry_rows(m, w, o, *rows); else synth::encode_mesh(m, o, buf);
     }
+    if (rows) return 0;
     *out = (uint8_t *)malloc(buf.size() ? buf.size() : 1);
     memcpy(*out, buf.data(), buf.size());
     *out_len = buf.size();
@@ -467,6 +476,24 @@ int synth_encode_corner_attributes_grid(int form, const float *pos, uint32_t nv,
                                         int geometry, int compressed, const synth_extra *extras, const synth_extra_corners *extra_corners, uint32_t num_extras,
                                         const synth_grids *grids, const synth_options *opt, int weld_attributes, uint8_t **out, size_t *out_len) {
   return encode_grid(form, pos, nv, faces, nf, normals, nn, normal_corners, uvs, nu, uv_corners, generic, geometry, compressed, extras, extra_corners, num_extras, grids, opt, weld_attributes, out, out_len);
+}
+// The entry rows of the stream synth_encode_corner_attributes_grid writes for the same arguments (dsa_encode_host.h entry_rows /
+// welded_entry_rows; grids do not move an entry): counts[a] entries for attribute a of the stream, a < *num_attributes <= 32, all
+// of them back to back in *out (uint32, freed with synth_free).  form 2: rows are points of the caller's.
+int synth_entry_rows(int form, const float *pos, uint32_t nv, const uint32_t *faces, uint32_t nf, const float *normals, uint32_t nn,
+                     const uint32_t *normal_corners, const float *uvs, uint32_t nu, const uint32_t *uv_corners, const void *generic,
+                     int geometry, const synth_extra *extras, const synth_extra_corners *extra_corners, uint32_t num_extras,
+                     const synth_options *opt, int weld_attributes, uint32_t **out, uint32_t *counts, uint32_t *num_attributes) {
+  std::vector<std::vector<uint32_t>> rows;
+  if (encode_grid(form, pos, nv, faces, nf, normals, nn, normal_corners, uvs, nu, uv_corners, generic, geometry, 0, extras, extra_corners, num_extras, nullptr, opt, weld_attributes, nullptr, nullptr, &rows)) return 1;
+  if (rows.size() > 32) { snprintf(g_err, sizeof(g_err), "more than 32 attributes"); return 1; }
+  size_t total = 0;
+  for (size_t a = 0; a < rows.size(); ++a) { counts[a] = (uint32_t)rows[a].size(); total += rows[a].size(); }
+  *num_attributes = (uint32_t)rows.size();
+  *out = (uint32_t *)malloc(total ? 4 * total : 4);
+  size_t at = 0;
+  for (auto &r : rows) { if (!r.empty()) memcpy(*out + at, r.data(), 4 * r.size()); at += r.size(); }
+  return 0;
 }
 // The grid a group of meshes shares (mode 2; dsa_encode_host.h shared_grid): over `count` arrays of rows[k] rows of nc floats.
 // Returns 0 and the grid as an explicit one (mode 1), or 1 when no array is free of values that are not finite.

@@ -641,12 +641,74 @@ void dsa_encode_default_corner_attributes_options(dsa_encode_corner_attributes_o
 dsa_status dsa_encode_corner_attributes_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids,
                                               const dsa_mesh_attribute_corners *corners, const dsa_encode_corner_attributes_options *options,
                                               dsa_encoded **out);
+/* dsa_encode_corner_attributes_batch whose handle can tell which row of the caller's arrays every entry of a stream carries, so
+ * that data which does not travel in the stream (morph targets, simulation state, another LOD's skinning) can be carried across an
+ * encode: Edgebreaker renumbers vertices, the weld merges points, the repair adds vertices with parents.
+ *   track_rows = 1: the handle keeps, per coded mesh and attribute of the stream (positions 0, then normals, texcoords, generic
+ *   where present, then the list), entry_rows[a], uint32[entries of a]: the index of the row of the caller's value array for `a`
+ *   whose bytes the encoder read for entry e -- the vertex index of an attribute given per vertex; the row id of an attribute given
+ *   per corner (normal_corners / texcoord_corners / dsa_attribute_corners), seamed or not; over a repaired table (topology = 1,
+ *   corner_repair = 1) for a vertex the repair made the row read, its root parent's, and nothing for isolated vertices and
+ *   degenerate faces, which have no entries; with weld_points = 1 a POINT of the caller's per-point arrays, the one whose row was
+ *   read: the representative (smallest index) of the row's class in the key set of the attribute, or of its vertex where the
+ *   attribute went to the coder per vertex -- with weld_attributes = 1 the listed attributes by their own sets.  Entries are in the
+ *   order the decoder of the attribute produces them (depth first, prediction degree, or a seamed attribute's own walk), which is
+ *   what the point maps of a decoded mesh index: rows of point p = entry_rows[a][map[a][p]] (dsa_batch_device_point_map).
+ *   Costs 4 bytes per entry and attribute in the handle, and one kernel per chunk (k_enc_entry_rows) whose output leaves the device
+ *   with the coded bytes.  track_rows = 0: the bytes, the messages and the work of dsa_encode_corner_attributes_batch.
+ * track_rows outside {0, 1} or a non-zero reserved word fails the call with DSA_ERR_INVALID_ARGUMENT and dsa_last_error names
+ * the field.  Added after ABI 4 without changing it: callers detect the feature by the symbol dsa_encode_rows_batch. */
+typedef struct dsa_encode_rows_options {
+  dsa_encode_corner_attributes_options corner_attributes; /* as for dsa_encode_corner_attributes_batch, same legal values */
+  int32_t track_rows;                      /* 0 (default): nothing kept; 1: the handle keeps the entry rows */
+  int32_t reserved[7];                     /* must be zero */
+} dsa_encode_rows_options;
+void dsa_encode_default_rows_options(dsa_encode_rows_options *options);
+dsa_status dsa_encode_rows_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids,
+                                 const dsa_mesh_attribute_corners *corners, const dsa_encode_rows_options *options, dsa_encoded **out);
 /* The same for sequential meshes and point clouds (dsa_encode_attributes_sequential_batch). */
 dsa_status dsa_encode_grid_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids,
                                             const dsa_encode_sequential_options *options, dsa_encoded **out);
+/* The rows of a decoded batch per POINT: for every mesh of `batch` and every attribute a of its stream,
+ *     rows[a][p] = entry_rows[a][map[a][p]]          (map: the decoder's point -> entry map, dsa_batch_device_point_map)
+ * -- which row of the arrays given to the encoder point p carries, gathered on the device (k_source_rows) so that neither the maps
+ * nor an array per mesh cross the link.  `encoded` is the handle the streams came from: of dsa_encode_rows_batch with track_rows =
+ * 1, or of a sequential call (entry i is row i); a handle without rows fails the call with DSA_ERR_INVALID_ARGUMENT (the message
+ * names track_rows).  encoded_mesh[i] names the stream of `encoded` that mesh i of the batch was created from; NULL: stream i.
+ * Shaped like dsa_batch_vertex_arrays: the work is queued on the download stream behind the batch's kernels, dsa_batch_wait waits
+ * for it, the result is one block of 64-byte aligned uint32 arrays (dsa_batch_source_rows_bytes; dst NULL: a pinned mirror of the
+ * library's, dsa_batch_host_source_rows; dst NULL with dst_bytes = DSA_SOURCE_ROWS_DEVICE_ONLY: no host copy, the block stays on the
+ * device, dsa_batch_device_source_rows), and dsa_batch_source_rows_layout says where the arrays of a mesh lie.  `encoded` must stay
+ * alive until dsa_batch_wait has returned.  A point whose entry lies at or beyond the tracked ones reads 0xFFFFFFFF; a point cloud's
+ * identity map is honoured without a stored map.  A mesh fails alone -- nothing is written for it, and the layout call returns
+ * its status -- when it failed to decode, when its stream failed to encode, or with DSA_ERR_INVALID_ARGUMENT when its compressed
+ * length, its attribute count or an attribute's entry count is not that of the stream named (length and attribute count are
+ * known at the call: such a mesh has no room in the block; the entry counts are known behind the decode: the kernel then leaves the
+ * mesh's room unwritten).  Meshes on decode_path 2 have theirs in block 1,
+ * from the retry batch, as the vertex arrays do.  A new decode of the batch invalidates the arrays.  Batches a pool owns
+ * (dsa_pool_*) are const and take no request.  Added after ABI 4 without changing it: callers detect the feature by the symbol. */
+#define DSA_SOURCE_ROWS_DEVICE_ONLY (~(size_t)0)
+typedef struct dsa_mesh_source_rows {
+  uint32_t block;                          /* 0: the batch's block; 1: the block of the meshes decoded a second time */
+  uint32_t num_points, num_attributes;
+  uint32_t reserved;                       /* zero */
+  uint64_t rows[DSA_MAX_ATTRIBUTES];       /* offset inside the block of uint32[num_points]; UINT64_MAX: no such attribute */
+} dsa_mesh_source_rows;                    /* 144 bytes */
+uint64_t dsa_batch_source_rows_bytes(const dsa_batch *batch, const dsa_encoded *encoded, const uint32_t *encoded_mesh);
+dsa_status dsa_batch_source_rows(dsa_batch *batch, const dsa_encoded *encoded, const uint32_t *encoded_mesh, void *dst, size_t dst_bytes);
+dsa_status dsa_batch_source_rows_layout(const dsa_batch *batch, uint32_t mesh, dsa_mesh_source_rows *out);
+const void *dsa_batch_host_source_rows(const dsa_batch *batch, uint32_t block);
+const void *dsa_batch_device_source_rows(const dsa_batch *batch, uint32_t block);
 uint32_t dsa_encoded_size(const dsa_encoded *encoded);
 /* Bytes of stream `mesh` (owned by `encoded`, valid until dsa_encoded_free) or that mesh's failure status. */
 dsa_status dsa_encoded_stream(const dsa_encoded *encoded, uint32_t mesh, const uint8_t **bytes, size_t *length);
+/* The entry rows of attribute `attribute` (its index in the stream) of stream `mesh`: *count receives the number of entries, and
+ * dst, when not NULL, `*count` rows (capacity: the room in dst, in rows; too little: DSA_ERR_INVALID_ARGUMENT, *count set).  A
+ * failed mesh returns its own status.  A handle of a sequential call answers with the identity (entry i is row i).  A handle of
+ * an Edgebreaker call made without track_rows = 1 returns DSA_ERR_INVALID_ARGUMENT and dsa_last_error names track_rows. */
+dsa_status dsa_encoded_entry_rows(const dsa_encoded *encoded, uint32_t mesh, uint32_t attribute, uint32_t *dst, size_t capacity, uint32_t *count);
+/* The number of attributes stream `mesh` has entry rows for (`attribute` above runs below it); the same statuses. */
+dsa_status dsa_encoded_attributes(const dsa_encoded *encoded, uint32_t mesh, uint32_t *count);
 void dsa_encoded_free(dsa_encoded *encoded);
 
 /* ------------------------------------------------------------------------------------------------------------
