@@ -770,48 +770,47 @@ static dsa_status enc_check_bits(dsa_context *ctx, const dsa_encode_options &o) 
 static bool enc_host_choice(const char *name, uint32_t batch_n) { const char *e = getenv(name); return e ? atoi(e) != 0 : batch_n < 256; }
 
 // ---- the stages of encode_chunk, in their order
-// a weld request (dsa_encode_points_batch, dsa_weld_batch): the meshes arrive as one row per point; the weld of every mesh
+// a weld request (dsa_encode_points_batch, dsa_weld_batch, dsa_encode_corner_attributes_batch over per-point input): the meshes
+// arrive as one row per point; the weld of every mesh
 // (dsa_encode_weld.h; DSA_ENC_HOST_WELD, batches below 256 meshes: synth::weld_points on the host threads) into buffers the chunk
 // owns, and the chunk's mesh view pointed at them -- everything behind runs on the welded meshes as if the caller had passed them.
 // Device path: memory of its own per lane, the point arrays up on a turn of the link, the kernels, then counts, maps and welded
 // rows back (the welded rows cross the link again with the ordinary uploads: the layout reads host memory).
-// ---- what the two weld stages share (Rec: dsa::EncWeld, or dsa::EncWeldList of dsa_encode_weld_list.h)
-// the per-point arrays of mesh `m` that both record types hold alike into the upload list: faces, the vertex key's segments, normals,
-// texture coordinates (W.seg[g] / W.set[1] / W.set[2]); false: the mesh is too large for the device weld and is refused
+// false: the mesh is too large for the device weld and is refused
 static bool enc_weld_sizes_fit(EncChunk &ck, uint32_t i, const dsa_mesh_input &m, size_t segments, size_t listed) {
   if (m.num_vertices > (1u << 28) || m.num_faces > (1u << 28)) { ck.refuse(i, DSA_ERR_INVALID_DATA, "mesh too large for the device weld"); return false; }
-  if (segments + listed + 2 > dsa::EW_MAX_SEGS || listed > dsa::EWL_MAX_LISTED) { ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, "too many attributes for the device weld"); return false; }
+  if (segments + listed + 2 > dsa::EW_MAX_SEGS || listed > dsa::EW_MAX_LISTED) { ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, "too many attributes for the device weld"); return false; }
   return true;
 }
-template <class Rec>
-static void enc_weld_uploads(std::vector<EncUpload> &ups, const Rec &W, const dsa_mesh_input &m, const std::vector<synth::WeldSeg> &key) {
+// the per-point arrays of mesh `m` into the upload list, in the order of enc_weld_inputs: faces, the vertex key's segments, normals,
+// texture coordinates, the listed attributes welded alone (W.seg[g] / W.set[1] / W.set[2] / W.set[3 + j])
+static void enc_weld_uploads(std::vector<EncUpload> &ups, const dsa::EncWeld &W, const dsa_mesh_input &m, const std::vector<synth::WeldSeg> &key, const std::vector<synth::WeldSeg> &listed) {
   if (m.num_faces) ups.push_back({W.faces, m.faces, 12ull * m.num_faces, false});
   for (size_t g = 0; g < key.size() && m.num_vertices; ++g) ups.push_back({W.seg[g].src, key[g].rows, (size_t)m.num_vertices * key[g].row_bytes, false});
   if (m.normals && m.num_vertices) ups.push_back({W.seg[W.set[1].first_seg].src, m.normals, 12ull * m.num_vertices, false});
   if (m.texcoords && m.num_vertices) ups.push_back({W.seg[W.set[2].first_seg].src, m.texcoords, 8ull * m.num_vertices, false});
+  for (size_t j = 0; j < listed.size() && m.num_vertices; ++j) ups.push_back({W.seg[W.set[3 + j].first_seg].src, listed[j].rows, (size_t)m.num_vertices * listed[j].row_bytes, false});
 }
 // the lane's weld memory of `total` bytes, cleared behind the inputs; the uploads on a turn of the link; the records up
 // (ups is in arena order; a piece of enc_upload copies a whole stretch of the arena from pinned staging, gaps included: that is
 // why no region a kernel expects at zero may lie among the inputs)
-template <class Rec>
 static dsa_status enc_weld_begin(dsa_context *ctx, EncLane &lane, hostutil::TurnGuard &turn, uint64_t total, uint64_t input_bytes, const std::vector<EncUpload> &ups,
-                                 const std::vector<Rec> &recs, uint8_t **arena, Rec **d_recs) {
+                                 const std::vector<dsa::EncWeld> &recs, uint8_t **arena, dsa::EncWeld **d_recs) {
   ENC_TRY(lane.weld.ensure(total ? total : 256));
-  ENC_TRY(lane.weld_recs.ensure(sizeof(Rec) * recs.size()));
+  ENC_TRY(lane.weld_recs.ensure(sizeof(dsa::EncWeld) * recs.size()));
   *arena = (uint8_t *)lane.weld.p;
-  *d_recs = (Rec *)lane.weld_recs.p;
+  *d_recs = (dsa::EncWeld *)lane.weld_recs.p;
   if (total > input_bytes) ENC_TRY(hipMemsetAsync(*arena + input_bytes, 0, total - input_bytes, lane.st));
   turn.acquire_free();
   ENC_TRY(enc_upload(lane, *arena, lane.st, ups));
   turn.release();
-  ENC_TRY(hipMemcpyAsync(*d_recs, recs.data(), sizeof(Rec) * recs.size(), hipMemcpyHostToDevice, lane.st));
+  ENC_TRY(hipMemcpyAsync(*d_recs, recs.data(), sizeof(dsa::EncWeld) * recs.size(), hipMemcpyHostToDevice, lane.st));
   return DSA_OK;
 }
 // ... the launches checked, the records down
-template <class Rec>
-static dsa_status enc_weld_records(dsa_context *ctx, EncLane &lane, std::vector<Rec> &recs, const Rec *d_recs) {
+static dsa_status enc_weld_records(dsa_context *ctx, EncLane &lane, std::vector<dsa::EncWeld> &recs, const dsa::EncWeld *d_recs) {
   ENC_TRY(hipGetLastError());
-  ENC_TRY(hipMemcpyAsync(recs.data(), d_recs, sizeof(Rec) * recs.size(), hipMemcpyDeviceToHost, lane.st));
+  ENC_TRY(hipMemcpyAsync(recs.data(), d_recs, sizeof(dsa::EncWeld) * recs.size(), hipMemcpyDeviceToHost, lane.st));
   ENC_TRY(hipStreamSynchronize(lane.st));
   return DSA_OK;
 }
@@ -834,82 +833,10 @@ struct EncWeldFetch {
     return DSA_OK;
   }
 };
-static dsa_status enc_stage_weld_list(dsa_context *ctx, EncLane &lane, hostutil::TurnGuard &turn, EncChunk &ck);
+// 3 + L key sets per mesh: listed[i] holds the L attributes of the list welded alone (dsa_encode_corner_attributes_batch with
+// weld_attributes = 1), none for dsa_encode_points_batch and dsa_weld_batch
 static dsa_status enc_stage_weld(dsa_context *ctx, EncLane &lane, hostutil::TurnGuard &turn, EncChunk &ck) {
   if (!ck.rq.weld) return DSA_OK;
-  if (ck.rq.weld_attributes) return enc_stage_weld_list(ctx, lane, turn, ck);
-  const uint32_t n = ck.n;
-  ck.weld.assign(n, synth::Welded());
-  ck.weld_attrs.assign(n, {});
-  std::vector<std::vector<synth::WeldSeg>> keys(n);
-  hostutil::parallel_for(n, [&](uint32_t i) { enc_weld_check(ck, i, keys[i]); });
-  const bool on_host = enc_host_choice("DSA_ENC_HOST_WELD", ck.batch_n);
-  std::vector<dsa::EncWeld> recs;
-  std::vector<uint32_t> mesh_of;
-  std::vector<EncUpload> ups;
-  EncArena A;
-  uint32_t most = 1;
-  for (uint32_t i = 0; i < n && !on_host; ++i) {
-    if (!ck.good(i)) continue;
-    const dsa_mesh_input &m = ck.rq.mesh(ck.base + i);
-    if (!enc_weld_sizes_fit(ck, i, m, keys[i].size(), 0)) continue;
-    uint32_t row_bytes[dsa::EW_MAX_SEGS];
-    for (size_t g = 0; g < keys[i].size(); ++g) row_bytes[g] = keys[i][g].row_bytes;
-    dsa::EncWeld W = dsa::enc_weld_inputs([&](uint64_t bytes) { return A.take(bytes); }, m.num_vertices, m.num_faces, row_bytes, (uint32_t)keys[i].size(), m.normals != nullptr, m.texcoords != nullptr);
-    enc_weld_uploads(ups, W, m, keys[i]);
-    recs.push_back(W); mesh_of.push_back(i);
-    most = std::max(most, std::max(m.num_vertices, 3u * m.num_faces));
-  }
-  const uint64_t input_bytes = A.cur;                      // the uploads fill [0, input_bytes); the kernels' regions lie behind
-  for (dsa::EncWeld &W : recs) dsa::enc_weld_regions([&](uint64_t bytes) { return A.take(bytes); }, W);
-  if (on_host) {
-    hostutil::parallel_for(n, [&](uint32_t i) {
-      if (!ck.good(i)) return;
-      const dsa_mesh_input &m = ck.rq.mesh(ck.base + i);
-      try { synth::weld_points(m.num_vertices, m.faces, m.num_faces, keys[i], m.normals, m.texcoords, ck.weld[i]); }
-      catch (const std::exception &e) { ck.refuse(i, DSA_ERR_INVALID_DATA, e.what()); }
-    });
-  } else if (!recs.empty()) {
-    const uint32_t nr = (uint32_t)recs.size();
-    hipStream_t st = lane.st;
-    uint8_t *arena = nullptr;
-    dsa::EncWeld *d_recs = nullptr;
-    ENC_STAGE(enc_weld_begin(ctx, lane, turn, A.cur, input_bytes, ups, recs, &arena, &d_recs));
-    const uint32_t gx = std::max(1u, std::min(128u, (most + 1023u) / 1024u));
-    hipLaunchKernelGGL(dsa::k_enc_weld_mark, dim3(gx, nr), dim3(256), 0, st, arena, d_recs, nr);
-    hipLaunchKernelGGL(dsa::k_enc_weld_insert, dim3(gx, 3 * nr), dim3(256), 0, st, arena, d_recs, nr);
-    hipLaunchKernelGGL(dsa::k_enc_weld_scan, dim3(3 * nr), dim3(WAVE), 0, st, arena, d_recs, nr);
-    hipLaunchKernelGGL(dsa::k_enc_weld_assign, dim3(gx, 3 * nr), dim3(256), 0, st, arena, d_recs, nr);
-    hipLaunchKernelGGL(dsa::k_enc_weld_differs, dim3(gx, 2 * nr), dim3(256), 0, st, arena, d_recs, nr);
-    hipLaunchKernelGGL(dsa::k_enc_weld_gather, dim3(gx, nr), dim3(256), 0, st, arena, d_recs, nr);
-    ENC_STAGE(enc_weld_records(ctx, lane, recs, d_recs));
-    EncWeldFetch fetch;
-    for (uint32_t r = 0; r < nr; ++r) {
-      const uint32_t i = mesh_of[r];
-      const dsa::EncWeld &W = recs[r];
-      if (W.status != dsa::ENC_WELD_OK || W.set[0].count > W.P || W.set[1].count > W.P || W.set[2].count > W.P) { ck.refuse(i, DSA_ERR_INVALID_DATA, dsa::enc_weld_message(W.status)); continue; }
-      synth::Welded &w = ck.weld[i];
-      w.P = W.P; w.F = W.F;
-      synth::WeldKeys *sets[3] = {&w.vertex, &w.normal, &w.texcoord};
-      for (uint32_t k = 0; k < 3; ++k) if (W.set[k].num_segs) fetch.want_keys(*sets[k], W.set[k], W.P);
-      const uint32_t V = W.set[0].count;
-      fetch.want32(w.faces, W.faces_out, 3ull * W.F);
-      w.vertex_rows.resize(W.set[0].num_segs);
-      for (uint32_t g = 0; g < W.set[0].num_segs; ++g) fetch.want8(w.vertex_rows[g], W.seg[g].dst, (uint64_t)V * W.seg[g].row_bytes);
-      w.normals_per_vertex = W.differs[0] == 0; w.texcoords_per_vertex = W.differs[1] == 0;
-      if (W.set[1].num_segs) fetch.want_attribute(W.set[1], W.seg[W.set[1].first_seg], W.differs[0] != 0, V, W.F, W.corners_out[0], w.normal_rows, w.normal_corners);
-      if (W.set[2].num_segs) fetch.want_attribute(W.set[2], W.seg[W.set[2].first_seg], W.differs[1] != 0, V, W.F, W.corners_out[1], w.texcoord_rows, w.texcoord_corners);
-    }
-    ENC_STAGE(fetch.run(ctx, lane, arena));
-  }
-  ck.welded.resize(n);
-  ck.weld_corners.assign(n, {});
-  for (uint32_t i = 0; i < n; ++i) enc_weld_view(ck, i);
-  return DSA_OK;
-}
-// ... with every listed attribute a key set of its own (dsa_encode_corner_attributes_batch, weld_attributes = 1;
-// dsa_encode_weld_list.h): the same stage over 3 + L key sets per mesh.  DSA_ENC_HOST_WELD and the under-256-meshes rule as above.
-static dsa_status enc_stage_weld_list(dsa_context *ctx, EncLane &lane, hostutil::TurnGuard &turn, EncChunk &ck) {
   const uint32_t n = ck.n;
   ck.weld.assign(n, synth::Welded());
   ck.weld_attrs.assign(n, {});
@@ -917,7 +844,7 @@ static dsa_status enc_stage_weld_list(dsa_context *ctx, EncLane &lane, hostutil:
   std::vector<std::vector<synth::WeldSeg>> keys(n), listed(n);
   hostutil::parallel_for(n, [&](uint32_t i) { enc_weld_check(ck, i, keys[i], &listed[i]); });
   const bool on_host = enc_host_choice("DSA_ENC_HOST_WELD", ck.batch_n);
-  std::vector<dsa::EncWeldList> recs;
+  std::vector<dsa::EncWeld> recs;
   std::vector<uint32_t> mesh_of;
   std::vector<EncUpload> ups;
   EncArena A;
@@ -926,19 +853,18 @@ static dsa_status enc_stage_weld_list(dsa_context *ctx, EncLane &lane, hostutil:
     if (!ck.good(i)) continue;
     const dsa_mesh_input &m = ck.rq.mesh(ck.base + i);
     if (!enc_weld_sizes_fit(ck, i, m, keys[i].size(), listed[i].size())) continue;
-    uint32_t row_bytes[dsa::EW_MAX_SEGS], listed_bytes[dsa::EWL_MAX_LISTED];
+    uint32_t row_bytes[dsa::EW_MAX_SEGS], listed_bytes[dsa::EW_MAX_LISTED];
     for (size_t g = 0; g < keys[i].size(); ++g) row_bytes[g] = keys[i][g].row_bytes;
     for (size_t j = 0; j < listed[i].size(); ++j) listed_bytes[j] = listed[i][j].row_bytes;
-    dsa::EncWeldList W = dsa::enc_wlist_inputs([&](uint64_t bytes) { return A.take(bytes); }, m.num_vertices, m.num_faces, row_bytes, (uint32_t)keys[i].size(), m.normals != nullptr,
-                                               m.texcoords != nullptr, listed_bytes, (uint32_t)listed[i].size());
-    enc_weld_uploads(ups, W, m, keys[i]);
-    for (size_t j = 0; j < listed[i].size() && m.num_vertices; ++j) ups.push_back({W.seg[W.set[3 + j].first_seg].src, listed[i][j].rows, (size_t)m.num_vertices * listed[i][j].row_bytes, false});
+    dsa::EncWeld W = dsa::enc_weld_inputs([&](uint64_t bytes) { return A.take(bytes); }, m.num_vertices, m.num_faces, row_bytes, (uint32_t)keys[i].size(), m.normals != nullptr,
+                                          m.texcoords != nullptr, listed_bytes, (uint32_t)listed[i].size());
+    enc_weld_uploads(ups, W, m, keys[i], listed[i]);
     recs.push_back(W); mesh_of.push_back(i);
     most = std::max(most, std::max(m.num_vertices, 3u * m.num_faces));
     sets = std::max(sets, W.num_sets);
   }
   const uint64_t input_bytes = A.cur;                      // the uploads fill [0, input_bytes); the kernels' regions lie behind
-  for (dsa::EncWeldList &W : recs) dsa::enc_wlist_regions([&](uint64_t bytes) { return A.take(bytes); }, W);
+  for (dsa::EncWeld &W : recs) dsa::enc_weld_regions([&](uint64_t bytes) { return A.take(bytes); }, W);
   if (on_host) {
     hostutil::parallel_for(n, [&](uint32_t i) {
       if (!ck.good(i)) return;
@@ -950,25 +876,16 @@ static dsa_status enc_stage_weld_list(dsa_context *ctx, EncLane &lane, hostutil:
     const uint32_t nr = (uint32_t)recs.size();
     hipStream_t st = lane.st;
     uint8_t *arena = nullptr;
-    dsa::EncWeldList *d_recs = nullptr;
+    dsa::EncWeld *d_recs = nullptr;
     ENC_STAGE(enc_weld_begin(ctx, lane, turn, A.cur, input_bytes, ups, recs, &arena, &d_recs));
     const uint32_t gx = std::max(1u, std::min(128u, (most + 1023u) / 1024u));
-    // (grid y: meshes x key sets, in slices of at most 65 535 rows)
-    const uint32_t per = std::max(1u, 65535u / sets);
-    for (uint32_t r0 = 0; r0 < nr; r0 += per) {
-      const uint32_t cnt = std::min(per, nr - r0);
-      hipLaunchKernelGGL(dsa::k_enc_wlist_mark, dim3(gx, cnt), dim3(256), 0, st, arena, d_recs + r0, cnt);
-      hipLaunchKernelGGL(dsa::k_enc_wlist_insert, dim3(gx, sets * cnt), dim3(256), 0, st, arena, d_recs + r0, cnt, sets);
-      hipLaunchKernelGGL(dsa::k_enc_wlist_scan, dim3(sets * cnt), dim3(WAVE), 0, st, arena, d_recs + r0, cnt, sets);
-      hipLaunchKernelGGL(dsa::k_enc_wlist_assign, dim3(gx, sets * cnt), dim3(256), 0, st, arena, d_recs + r0, cnt, sets);
-      hipLaunchKernelGGL(dsa::k_enc_wlist_differs, dim3(gx, sets * cnt), dim3(256), 0, st, arena, d_recs + r0, cnt, sets);
-      hipLaunchKernelGGL(dsa::k_enc_wlist_gather, dim3(gx, sets * cnt), dim3(256), 0, st, arena, d_recs + r0, cnt, sets);
-    }
+    dsa::enc_weld_launch([st](auto kernel, uint32_t grid_x, uint32_t grid_y, uint32_t block, auto... args) { hipLaunchKernelGGL(kernel, dim3(grid_x, grid_y), dim3(block), 0, st, args...); },
+                         arena, d_recs, nr, sets, gx);
     ENC_STAGE(enc_weld_records(ctx, lane, recs, d_recs));
     EncWeldFetch fetch;
     for (uint32_t r = 0; r < nr; ++r) {
       const uint32_t i = mesh_of[r];
-      const dsa::EncWeldList &W = recs[r];
+      const dsa::EncWeld &W = recs[r];
       bool sane = W.status == dsa::ENC_WELD_OK;
       for (uint32_t k = 0; k < W.num_sets; ++k) sane = sane && W.set[k].count <= W.P;
       if (!sane) { ck.refuse(i, DSA_ERR_INVALID_DATA, dsa::enc_weld_message(W.status)); continue; }
@@ -982,12 +899,12 @@ static dsa_status enc_stage_weld_list(dsa_context *ctx, EncLane &lane, hostutil:
       for (uint32_t k = 0; k < W.num_sets; ++k) {
         const dsa::EncWeldSet &S = W.set[k];
         if (S.num_segs == 0) continue;
-        fetch.want_keys(k == 0 ? w.vertex : (k == 1 ? w.normal : (k == 2 ? w.texcoord : w.listed[k - 3u].keys)), S, W.P);
-        if (k == 0) continue;
+        if (k == 0) { fetch.want_keys(w.vertex, S, W.P); continue; }
+        const synth::Welded::KeySet a = w.key_set(k);
         const bool seamed = W.differs[k] != 0;
-        (k == 1 ? w.normals_per_vertex : (k == 2 ? w.texcoords_per_vertex : w.listed[k - 3u].per_vertex)) = !seamed;
-        fetch.want_attribute(S, W.seg[S.first_seg], seamed, V, W.F, W.corners_out[k], k == 1 ? w.normal_rows : (k == 2 ? w.texcoord_rows : w.listed[k - 3u].rows),
-                             k == 1 ? w.normal_corners : (k == 2 ? w.texcoord_corners : w.listed[k - 3u].corners));
+        fetch.want_keys(a.keys, S, W.P);
+        a.per_vertex = !seamed;
+        fetch.want_attribute(S, W.seg[S.first_seg], seamed, V, W.F, W.corners_out[k], a.rows, a.corners);
       }
     }
     ENC_STAGE(fetch.run(ctx, lane, arena));
@@ -1877,7 +1794,7 @@ dsa_status dsa_encode_seam_repair_batch(dsa_context *ctx, uint32_t n, const dsa_
   DSA_GUARD(ctx, encode_edgebreaker(ctx, n, meshes, grids, o, out));
 }
 // ... with row ids per corner for the attributes of the list, given by the caller (EncRequest::att_corners) or found by the weld
-// with every listed attribute a key set of its own (EncRequest::weld_attributes; dsa_encode_weld_list.h).
+// with every listed attribute a key set of its own (EncRequest::weld_attributes; dsa_encode_weld.h with L > 0).
 dsa_status dsa_encode_corner_attributes_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids,
                                               const dsa_mesh_attribute_corners *corners, const dsa_encode_corner_attributes_options *options, dsa_encoded **out) {
   dsa_encode_rows_options o = enc_default_options();

@@ -1826,6 +1826,14 @@ struct Welded {
   // weld_attributes: per listed attribute welded alone, in list order
   struct Listed { WeldKeys keys; bool per_vertex = true; std::vector<uint32_t> corners; std::vector<uint8_t> rows; };
   std::vector<Listed> listed;
+  // key set k >= 1 (1 the normal, 2 the texture coordinate, 3 + j listed attribute j, which `listed` must hold by then)
+  struct KeySet { WeldKeys &keys; bool &per_vertex; std::vector<uint32_t> &corners; std::vector<uint8_t> &rows; };
+  KeySet key_set(uint32_t k) {
+    if (k == 1) return {normal, normals_per_vertex, normal_corners, normal_rows};
+    if (k == 2) return {texcoord, texcoords_per_vertex, texcoord_corners, texcoord_rows};
+    Listed &l = listed[k - 3u];
+    return {l.keys, l.per_vertex, l.corners, l.rows};
+  }
 };
 static inline uint32_t weld_hash(const std::vector<WeldSeg> &segs, uint32_t p) {
   uint32_t h = 0x9E3779B9u;
@@ -1874,22 +1882,20 @@ static void weld_points(uint32_t P, const uint32_t *faces, uint32_t F, const std
   for (size_t k = 0; k < (size_t)F * 3; ++k) out.faces[k] = out.vertex.of_point[faces[k]];
   out.vertex_rows.resize(vertex_key.size());
   for (size_t g = 0; g < vertex_key.size(); ++g) weld_gather(vertex_key[g], out.vertex.point, out.vertex_rows[g]);
-  auto attribute = [&](const void *values, uint32_t row_bytes, WeldKeys &keys, bool &per_vertex, std::vector<uint32_t> &corners, std::vector<uint8_t> &rows) {
-    keys = WeldKeys(); per_vertex = true; corners.clear(); rows.clear();
-    if (!values) return;
-    const WeldSeg seg{values, row_bytes};
-    weld_classes({seg}, used, keys);
-    for (uint32_t p = 0; p < P; ++p)
-      if (used[p] && keys.of_point[p] != keys.of_point[out.vertex.point[out.vertex.of_point[p]]]) { per_vertex = false; break; }
-    if (per_vertex) return weld_gather(seg, out.vertex.point, rows);
-    weld_gather(seg, keys.point, rows);
-    corners.resize((size_t)F * 3);
-    for (size_t k = 0; k < (size_t)F * 3; ++k) corners[k] = keys.of_point[faces[k]];
-  };
-  attribute(normals, 12, out.normal, out.normals_per_vertex, out.normal_corners, out.normal_rows);
-  attribute(uvs, 8, out.texcoord, out.texcoords_per_vertex, out.texcoord_corners, out.texcoord_rows);
   out.listed.assign(listed.size(), Welded::Listed());
-  for (size_t j = 0; j < listed.size(); ++j) attribute(listed[j].rows, listed[j].row_bytes, out.listed[j].keys, out.listed[j].per_vertex, out.listed[j].corners, out.listed[j].rows);
+  for (uint32_t k = 1; k < 3 + listed.size(); ++k) {
+    const WeldSeg seg = k == 1 ? WeldSeg{normals, 12u} : (k == 2 ? WeldSeg{uvs, 8u} : listed[k - 3u]);
+    const Welded::KeySet a = out.key_set(k);
+    a.keys = WeldKeys(); a.per_vertex = true; a.corners.clear(); a.rows.clear();
+    if (!seg.rows) continue;
+    weld_classes({seg}, used, a.keys);
+    for (uint32_t p = 0; p < P; ++p)
+      if (used[p] && a.keys.of_point[p] != a.keys.of_point[out.vertex.point[out.vertex.of_point[p]]]) { a.per_vertex = false; break; }
+    if (a.per_vertex) { weld_gather(seg, out.vertex.point, a.rows); continue; }
+    weld_gather(seg, a.keys.point, a.rows);
+    a.corners.resize((size_t)F * 3);
+    for (size_t c = 0; c < (size_t)F * 3; ++c) a.corners[c] = a.keys.of_point[faces[c]];
+  }
 }
 // The welded mesh as the coder takes it: `in` is the per-point input (its corner ids unset, nv read as P), `key` the segments of
 // its vertex key in the order positions, generic, extras (weld_vertex_key); `ex` receives the extras pointed at their welded rows.

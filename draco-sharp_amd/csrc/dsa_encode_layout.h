@@ -24,7 +24,6 @@
 #include "dsa_encode_conn.h"
 #include "dsa_encode_repair.h"
 #include "dsa_encode_weld.h"
-#include "dsa_encode_weld_list.h"
 #include "dsa_encode_grid.h"
 #include "dsa_encode_seams.h"
 #include "dsa_encode_seqidx.h"
@@ -162,7 +161,7 @@ struct EncRequest {
   std::vector<synth::Welded> *weld_sink = nullptr;      // dsa_weld_batch: receives the weld of every mesh, nothing is coded
   const EncMeshGrids *grids = nullptr;     // dsa_encode_grid_batch / _sequential_batch: parallel to `meshes` (null: every attribute on its own bounds)
   const dsa_mesh_attribute_corners *att_corners = nullptr;      // dsa_encode_corner_attributes_batch: parallel to `meshes` (null: the listed attributes are per vertex)
-  bool weld_attributes = false;            // ... weld_attributes = 1: the listed attributes are key sets of their own in the weld (dsa_encode_weld_list.h)
+  bool weld_attributes = false;            // ... weld_attributes = 1: the listed attributes are key sets of their own in the weld (dsa_encode_weld.h: 3 + L key sets)
   bool track_rows = false;                 // dsa_encode_rows_batch, track_rows = 1: the handle keeps the entry rows of every stream (dsa_encode_rows.h)
   int rows_kind() const { return weld_sink ? dsa_encoded::ROWS_NONE : (sequential ? dsa_encoded::ROWS_LINEAR : (track_rows ? dsa_encoded::ROWS_TRACKED : dsa_encoded::ROWS_NONE)); }
   dsa_encode_level_options level{};        // Edgebreaker streams

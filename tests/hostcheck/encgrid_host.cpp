@@ -23,26 +23,9 @@
 #include "../../draco-sharp_amd/csrc/dsa_types.h"
 #include "../../draco-sharp_amd/csrc/dsa_encode_host.h"
 
-// ---- what the kernels use of the HIP language, for one thread at a time
-struct Dim3 { uint32_t x = 1, y = 1, z = 1; };
-static Dim3 blockIdx, threadIdx, blockDim, gridDim;
-#define __global__
-#define __launch_bounds__(x)
-static inline uint32_t atomicMin(uint32_t *p, uint32_t v) { const uint32_t old = *p; if (v < old) *p = v; return old; }
-static inline uint32_t atomicMax(uint32_t *p, uint32_t v) { const uint32_t old = *p; if (v > old) *p = v; return old; }
+#include "hip_on_host.h"
 
 #include "../../draco-sharp_amd/csrc/dsa_encode_grid.h"
-
-template <class K, class... A>
-static void launch(K kernel, uint32_t gx, uint32_t gy, uint32_t block, bool backwards, A... args) {
-  gridDim.x = gx; gridDim.y = gy; blockDim.x = block;
-  for (uint32_t by = 0; by < gy; ++by)
-    for (uint32_t b = 0; b < gx; ++b)
-      for (uint32_t t = 0; t < block; ++t) {
-        blockIdx.x = backwards ? gx - 1 - b : b; blockIdx.y = by; threadIdx.x = backwards ? block - 1 - t : t;
-        kernel(args...);
-      }
-}
 
 struct In { uint32_t group = 0, nc = 0, rows = 0, bits = 0; float origin[4] = {0, 0, 0, 0}, range = 0; std::vector<float> v; };
 // what k_enc_grid_quantize reads of a stream's record

@@ -26,20 +26,7 @@
 #include "../../draco-sharp_amd/csrc/dsa_common.h"
 #include "../../draco-sharp_amd/csrc/dsa_types.h"
 
-// ---- what the kernel headers use of the HIP language (nothing of them runs here)
-struct uint4 { uint32_t x, y, z, w; };
-static inline uint4 make_uint4(uint32_t x, uint32_t y, uint32_t z, uint32_t w) { return uint4{x, y, z, w}; }
-struct Dim3 { uint32_t x = 1, y = 1, z = 1; };
-static Dim3 blockIdx, threadIdx, blockDim, gridDim;
-#define __global__
-#define __launch_bounds__(x)
-#define __shared__ static
-static inline uint32_t atomicCAS(uint32_t *p, uint32_t cmp, uint32_t val) { const uint32_t old = *p; if (old == cmp) *p = val; return old; }
-static inline uint32_t atomicAdd(uint32_t *p, uint32_t v) { const uint32_t old = *p; *p = old + v; return old; }
-static inline unsigned long long atomicAdd(unsigned long long *p, unsigned long long v) { const unsigned long long old = *p; *p = old + v; return old; }
-static inline uint32_t atomicMin(uint32_t *p, uint32_t v) { const uint32_t old = *p; if (v < old) *p = v; return old; }
-static inline uint32_t atomicMax(uint32_t *p, uint32_t v) { const uint32_t old = *p; if (v > old) *p = v; return old; }
-static inline uint32_t atomicOr(uint32_t *p, uint32_t v) { const uint32_t old = *p; *p = old | v; return old; }
+#include "hip_on_host.h"
 
 #include "../../draco-sharp_amd/csrc/dsa_encode_layout.h"
 
@@ -364,7 +351,7 @@ int main(int argc, char **argv) {
         Log log;
         ck.region_log = &log;
         ck.weld.assign(n, synth::Welded()); ck.weld_attrs.assign(n, {}); ck.weld_corners.assign(n, {});
-        for (uint32_t i = 0; i < n; ++i) {                      // (the host path of enc_stage_weld_list)
+        for (uint32_t i = 0; i < n; ++i) {                      // (the host path of enc_stage_weld)
           std::vector<synth::WeldSeg> key, listed;
           if (!enc_weld_check(ck, i, key, &listed)) { fprintf(stderr, "%s: mesh %u: %s\n", name, i, ck.E->messages[i].c_str()); return 1; }
           const dsa_mesh_input &m = rq.mesh(i);

@@ -21,30 +21,12 @@
 #include "../../draco-sharp_amd/csrc/dsa_types.h"
 #include "../../draco-sharp_amd/csrc/dsa_encode_host.h"
 
-// ---- what the kernels use of the HIP language, for one thread at a time
-struct uint4 { uint32_t x, y, z, w; };
-static inline uint4 make_uint4(uint32_t x, uint32_t y, uint32_t z, uint32_t w) { return uint4{x, y, z, w}; }
-struct Dim3 { uint32_t x = 1, y = 1, z = 1; };
-static Dim3 blockIdx, threadIdx, blockDim, gridDim;
-#define __global__
-#define __launch_bounds__(x)
-static inline uint32_t atomicCAS(uint32_t *p, uint32_t cmp, uint32_t val) { const uint32_t old = *p; if (old == cmp) *p = val; return old; }
-static inline uint32_t atomicAdd(uint32_t *p, uint32_t v) { const uint32_t old = *p; *p = old + v; return old; }
-static inline uint32_t atomicMin(uint32_t *p, uint32_t v) { const uint32_t old = *p; if (v < old) *p = v; return old; }
-static inline uint32_t atomicOr(uint32_t *p, uint32_t v) { const uint32_t old = *p; *p = old | v; return old; }
+#include "hip_on_host.h"
 
 #include "../../draco-sharp_amd/csrc/dsa_encode_conn.h"
 #include "../../draco-sharp_amd/csrc/dsa_encode_seams.h"
 
 struct StreamStub { uint32_t nv; uint64_t ops; };       // the fields of dsa_encode.h's EncStream that k_enc_seam_operands sets
-
-template <class K, class... A>
-static void launch(K kernel, uint32_t gx, uint32_t gy, uint32_t block, A... args) {
-  gridDim.x = gx; gridDim.y = gy; blockDim.x = block;
-  for (uint32_t by = 0; by < gy; ++by)
-    for (uint32_t bx = 0; bx < gx; ++bx)
-      for (uint32_t t = 0; t < block; ++t) { blockIdx.x = bx; blockIdx.y = by; threadIdx.x = t; kernel(args...); }
-}
 
 int main(int argc, char **argv) {
   if (argc < 2) { fprintf(stderr, "usage: encseams_host <meshes.bin>\n"); return 2; }

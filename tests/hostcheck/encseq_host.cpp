@@ -19,10 +19,7 @@
 #include "../../draco-sharp_amd/csrc/dsa_common.h"
 #include "../../draco-sharp_amd/csrc/dsa_encode_host.h"
 
-// ---- what the phases use of the HIP language, for one thread at a time
-static inline uint32_t atomicAdd(uint32_t *p, uint32_t v) { const uint32_t old = *p; *p = old + v; return old; }
-static inline unsigned long long atomicAdd(unsigned long long *p, unsigned long long v) { const unsigned long long old = *p; *p = old + v; return old; }
-static inline uint32_t atomicMax(uint32_t *p, uint32_t v) { const uint32_t old = *p; if (v > old) *p = v; return old; }
+#include "hip_on_host.h"
 
 #include "../../draco-sharp_amd/csrc/dsa_encode_seqidx.h"
 

@@ -1,5 +1,5 @@
 """Encode direction, listed attributes given per corner (dsa_encode_corner_attributes_batch): explicit ids on attributes of the list
-and the weld with every listed attribute a key set of its own (the kernels of dsa_encode_weld_list.h), byte for byte against the
+and the weld with every listed attribute a key set of its own (dsa_encode_weld.h over 3 + L key sets), byte for byte against the
 CPU coder (synth.Extra(corners=), synth.encode_mesh_points(weld_attributes=True)) on both connectivity paths (DSA_ENC_HOST_CONN /
 DSA_ENC_HOST_PLAN) and both weld paths (DSA_ENC_HOST_WELD), with its refusals word for word; the same streams decoded on the device
 against the oracle and the pin of tests/cornerattrcases.py; the call without ids against dsa_encode_seam_repair_batch; crowded
@@ -202,6 +202,46 @@ def test_weld_attributes_keeps_the_surface_and_decodes_to_the_pin(ctx, monkeypat
         used = np.unique(m.faces)
         assert sd.header_counts(g)[0] == len(np.unique(m.positions[used].view(np.uint32), axis=0)), b.name      # the stream's vertices: the distinct positions
     round_trip(ctx, [g for _, g in got], [K.pin(b) for b in WELDED], [b.name for b in WELDED])
+
+
+def test_no_listed_attribute_welds_like_the_points_call(ctx, monkeypatch):
+    """The device weld of both calls is one set of kernels: per-point meshes without a listed attribute give the same bytes through
+    dsa_encode_points_batch (three key sets) and through this call with weld_attributes = 1 (3 + L key sets, L = 0), the CPU
+    coder's; and still do beside a mesh with two listed attributes in the middle of the batch, which sizes the grid for five."""
+    import weldcases
+    force_paths(monkeypatch, "0", None)
+    small = [c for c in weldcases.small_cases() if not c.refused and not c.weld_only]
+    plain = [c for c in small if not c.extra]
+    assert len(plain) == len(small) - 1 > 40 and any(c.generic is not None for c in plain)      # (all but "colours-split")
+    cfg = dsa.Config(weld_points=True)
+
+    def data(c, listed=()):
+        return dsa.MeshData(c.pos, c.faces, c.normals, c.uvs, generic=c.generic, attributes=[dsa.Attribute(a, attribute_type=4) for a in listed])
+
+    def want_of(c, listed=()):
+        o = opt_of(cfg)
+        o.generic_components = c.generic.shape[1] if c.generic is not None else 1
+        return synth.encode_mesh_points(c.pos, c.faces, c.normals, c.uvs, c.generic, [synth.Extra(a, attribute_type=4) for a in listed] or None, o, weld_attributes=bool(listed))
+    names = [c.name for c in plain]
+    want = [want_of(c) for c in plain]
+    st, points = encodecall.call(ctx, "dsa_encode_points_batch", [data(c) for c in plain], cfg._native_repair())
+    assert st == 0, ctx.error()
+    alone = encode(ctx, [data(c) for c in plain], cfg, weld_attributes=True)
+    assert len(points) == len(alone) == len(want) == len(plain)
+    same(names, points, want)
+    same(names, alone, want)
+    assert points == alone
+    # one mesh with two listed attributes in the middle: the first the same for all points of a vertex, the second not
+    c = next(c for c in small if c.name == "colours-split")
+    key = np.ascontiguousarray(c.pos, np.float32).view(np.uint32).astype(np.uint64).sum(axis=1)
+    listed = [np.ascontiguousarray((key % 251).astype(np.uint8)[:, None]), np.ascontiguousarray(c.extra[0])]
+    w = want_of(c, listed)
+    assert sd.header_counts(w)[0] == len(np.unique(c.pos[np.unique(c.faces)].view(np.uint32), axis=0))      # (the colour cuts no vertex)
+    h = len(plain) // 2
+    mixed = encode(ctx, [data(c) for c in plain[:h]] + [data(c, listed)] + [data(c) for c in plain[h:]], cfg, weld_attributes=True)
+    assert len(mixed) == len(plain) + 1
+    same(names[:h] + [c.name] + names[h:], mixed, want[:h] + [w] + want[h:])
+    assert mixed[:h] + mixed[h + 1:] == points
 
 
 def test_without_ids_it_is_the_seam_repair_call(ctx, monkeypatch):
