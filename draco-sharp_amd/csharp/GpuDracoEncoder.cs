@@ -67,6 +67,12 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
     // after Encode.  The streams are the bytes they are without it.  What carries morph targets across the weld and Edgebreaker's
     // renumbering.
     public bool TrackRows { get; set; }
+    // PointOrder (dsa_encode_ordered_sequential_batch): 0 the points of a sequential stream or point cloud in the caller's order; 1 in
+    // Morton order of their quantised positions, found on the device -- entry e of every attribute carries row perm[e] of the input,
+    // faces are written through the inverse; EntryRows(i) returns perm for every attribute.  The format gives the order of a
+    // sequential stream no meaning, and a scan or a shuffled sample codes to half its size or less this way.  Edgebreaker streams
+    // order their own entries: with 1 an Edgebreaker encode throws.
+    public int PointOrder { get; set; }
     private uint[][][] _entryRows;
     // Of stream i of the most recent Encode with TrackRows: per attribute of the stream (positions, then normals, texture coordinates,
     // generic where present, then the others) the row of the input every entry carries.
@@ -171,6 +177,17 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
                     inputs[i].Faces = (uint*)Pin(faces, pins);
                 }
             }
+            if (PointOrder != 0)
+            {
+                NativeMethods.dsa_encode_default_order_options(out var oo);
+                oo.Sequential = so;
+                oo.PointOrder = PointOrder;
+                var ain = new DsaMeshAttrInput[items.Count];
+                for (int i = 0; i < items.Count; ++i) { ain[i].Mesh.Mesh = inputs[i]; Extras(items[i], null, (uint)items[i].PointsCount, ref ain[i], pins); }
+                fixed (DsaMeshAttrInput* p = ain)
+                    NativeMethods.Check(NativeMethods.dsa_encode_ordered_sequential_batch(_ctx, (uint)items.Count, p, null, in oo, out encoded), _ctx, "dsa_encode_ordered_sequential_batch");
+                return Streams(encoded, items.Count);
+            }
             if (anyExtras)
             {
                 var ain = new DsaMeshAttrInput[items.Count];
@@ -200,6 +217,7 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
             for (int i = 0; i < meshes.Count; ++i) items[i] = meshes[i];
             return EncodeSequential(items, config, 1);
         }
+        if (PointOrder != 0) throw new ArgumentException("PointOrder needs a sequential stream (EncodingMethod SequentialEncoding, or point clouds): Edgebreaker orders its own entries");
         NativeMethods.dsa_encode_default_options(out var opt);
         // per-attribute-type options are keyed by (int)GeometryAttributeType (Config.cs:55-62)
         opt.PositionBits = config.GetAttributeOption((int)GeometryAttributeType.Position, ConfigOptionName.Attribute.QuantizationBits, opt.PositionBits);
@@ -442,7 +460,7 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
             NativeMethods.Check(NativeMethods.dsa_encoded_stream(encoded, i, out var bytes, out var length), _ctx, $"mesh {i}");
             result[i] = new ReadOnlySpan<byte>(bytes, (int)length).ToArray();
         }
-        if (TrackRows) _entryRows = Rows(encoded, count);      // (a sequential handle answers with the identity)
+        if (TrackRows || PointOrder != 0) _entryRows = Rows(encoded, count);      // (a sequential handle answers with the identity, or with the point order)
         return result;
     }
 

@@ -230,6 +230,15 @@ internal unsafe struct DsaEncodeSequentialOptions
     public fixed int Reserved[6];       // zero
 }
 
+// dsa_encode_order_options (dsa_encode_ordered_sequential_batch)
+[StructLayout(LayoutKind.Sequential)]
+internal unsafe struct DsaEncodeOrderOptions
+{
+    public DsaEncodeSequentialOptions Sequential;
+    public int PointOrder;          // 0: the caller's order; 1: Morton order of the quantised positions, the handle keeps the permutation
+    public fixed int Reserved[7];   // zero
+}
+
 [StructLayout(LayoutKind.Sequential)]
 internal unsafe struct DsaMeshInput
 {
@@ -356,6 +365,8 @@ internal static unsafe partial class NativeMethods
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_attributes_sequential_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, in DsaEncodeSequentialOptions options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern uint dsa_encoded_size(IntPtr encoded);
     [DllImport(Lib)] internal static extern void dsa_encode_default_rows_options(out DsaEncodeRowsOptions options);
+    [DllImport(Lib)] internal static extern void dsa_encode_default_order_options(out DsaEncodeOrderOptions options);
+    [DllImport(Lib)] internal static extern DsaStatus dsa_encode_ordered_sequential_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, in DsaEncodeOrderOptions options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_rows_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, DsaMeshAttributeCorners* corners, in DsaEncodeRowsOptions options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encoded_entry_rows(IntPtr encoded, uint mesh, uint attribute, uint* dst, nuint capacity, out uint count);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encoded_attributes(IntPtr encoded, uint mesh, out uint count);

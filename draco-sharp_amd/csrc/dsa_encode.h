@@ -23,6 +23,8 @@
 //   host  (dsa_encode_host.h)  input checks; at the end the stream layout: bit-packing of the Edgebreaker symbols, table bytes, section order
 //                              (threads over meshes).  DSA_ENC_HOST_PLAN=1: the symbol plans by the host between the two device phases.
 //   GPU   (dsa_encode_rows.h)  k_enc_entry_rows  dsa_encode_rows_batch, track_rows = 1: the row of the caller's arrays every entry carries
+//   GPU   (dsa_encode_order.h) k_enc_order_*     dsa_encode_ordered_sequential_batch, point_order = 1: Morton keys and a segmented radix sort
+//                                                over all clouds of a chunk, between k_enc_quantize and k_enc_gather
 //         (dsa_encode_layout.h) the request of an entry point, the state of a chunk, the per-mesh checks and plans, the arena layout
 // Every entry point fills an EncRequest and calls encode_request; a chunk of it goes through the stages of encode_chunk (or of
 // encode_sequential_chunk, dsa_encode_sequential.h) on a lane.
@@ -655,8 +657,9 @@ static dsa_status enc_code_streams(dsa_context *ctx, EncLane &lane, EncChunk &ck
   // coded bytes of every stream (and, when k_enc_plan made them, the probability tables: the stream carries them)
   // and the side bits of TexCoordsPortable / GeometricNormal, packed
   // (track_rows: a fifth piece per stream, its entry rows -- k_enc_entry_rows has run behind the attribute kernels)
-  const bool track = !ck.L.rows_of_stream.empty();
-  const size_t per = track ? 5 : 4;
+  // (point_order: the fifth piece of a mesh's first stream is the permutation its streams share -- dsa_encode_order.h)
+  const bool track = !ck.L.rows_of_stream.empty(), ordered = !ck.L.ord.empty();
+  const size_t per = track || ordered ? 5 : 4;
   std::vector<dsa::PackItem> items;
   for (uint32_t s = 0; s < ns; ++s) {
     if (hs[s].overflow || E->status[stream_mesh[s]] != DSA_OK) continue;
@@ -669,6 +672,9 @@ static dsa_status enc_code_streams(dsa_context *ctx, EncLane &lane, EncChunk &ck
     if (track) {
       const dsa::EncRows *R = ck.L.rows_of_stream[s] != DSA_INVALID ? &ck.L.rows[ck.L.rows_of_stream[s]] : nullptr;
       items.push_back({R ? R->out : 0, 0, R ? 4u * std::min(hs[s].nv, R->cap) : 0u, s});
+    } else if (ordered) {
+      const bool first = s == ck.L.first_stream[stream_mesh[s]];
+      items.push_back({hs[s].e2v, 0, first ? 4u * hs[s].nv : 0u, s});
     }
   }
   const uint8_t *host = nullptr;
@@ -676,7 +682,7 @@ static dsa_status enc_code_streams(dsa_context *ctx, EncLane &lane, EncChunk &ck
   hostutil::parallel_for((uint32_t)(items.size() / per), [&](uint32_t m) {
     const size_t k = per * (size_t)m;
     const uint32_t s = items[k].pad;
-    if (track && items[k + 4].len) { const uint32_t *r = (const uint32_t *)(host + items[k + 4].packed_off); ck.entry_rows[s].assign(r, r + items[k + 4].len / 4u); }
+    if (per == 5 && items[k + 4].len) { const uint32_t *r = (const uint32_t *)(host + items[k + 4].packed_off); ck.entry_rows[s].assign(r, r + items[k + 4].len / 4u); }
     if (items[k].len) rans[s].assign(host + items[k].packed_off, host + items[k].packed_off + items[k].len);
     if (items[k + 1].len) bits[s].assign(host + items[k + 1].packed_off, host + items[k + 1].packed_off + items[k + 1].len);
     if (hs[s].flags && !(hs[s].kind != 1 && hs[s].prediction == 4)) {
@@ -1113,6 +1119,8 @@ static dsa_status enc_stage_attributes(dsa_context *ctx, EncLane &lane, EncChunk
   dsa::EncConn *d_conns = ck.d_conns;
   dsa::EncSeam *d_seams = ck.d_seams;
   const uint32_t gx = std::max(1u, std::min(64u, (L.max_rows + 2047) / 2048));
+  bool order_timing = false;
+  EncLap order_lap{&lane};
   if (!L.any_grid) {
     hipLaunchKernelGGL(dsa::k_enc_bounds<false>, dim3(ns), dim3(256), 0, st, arena, d_streams, ns);
     hipLaunchKernelGGL(dsa::k_enc_quantize<false>, dim3(gx, ns), dim3(256), 0, st, arena, d_streams, ns);
@@ -1141,6 +1149,18 @@ static dsa_status enc_stage_attributes(dsa_context *ctx, EncLane &lane, EncChunk
       hipLaunchKernelGGL(dsa::k_enc_seam_scan, dim3(nz), dim3(WAVE), 0, st, arena, d_conns, d_seams, nz);
       hipLaunchKernelGGL(dsa::k_enc_seam_bits, gz, dim3(256), 0, st, arena, d_conns, d_seams, nz);
     }
+  }
+  if (!L.ord.empty()) {      // point_order: the permutation of every cloud behind the quantisers, in front of the gather (dsa_encode_order.h)
+    // DSA_ENC_TIMING (read per chunk: tools/encode_order_timing.py times one leg of a process): the stream is drained around the
+    // order kernels and behind the stage, and the three laps say what share of the chunk's device time the order takes
+    order_timing = getenv("DSA_ENC_TIMING") != nullptr;
+    if (order_timing) { ENC_TRY(hipStreamSynchronize(st)); order_lap("uploads + quantisers"); }
+    const uint32_t gf = L.max_count ? std::max(1u, std::min(64u, (L.max_count + 1023u) / 1024u)) : 0u;
+    dsa::enc_order_launch([st](auto kernel, uint32_t grid_x, uint32_t grid_y, uint32_t block, auto... args) { hipLaunchKernelGGL(kernel, dim3(grid_x, grid_y), dim3(block), 0, st, args...); },
+                          arena, (const dsa::EncOrder *)(arena + L.ord_at), (uint32_t)L.ord.size(), (const dsa::EncOrderTile *)(arena + L.ord_tiles_at), (uint32_t)L.ord_tiles.size(),
+                          L.ord_passes, ck.rq.seq.geometry == 1, gf);
+    ENC_TRY(hipGetLastError());
+    if (order_timing) { ENC_TRY(hipStreamSynchronize(st)); order_lap("point order"); }
   }
   hipLaunchKernelGGL(dsa::k_enc_gather, dim3(ns), dim3(256), 0, st, arena, d_streams, ns);
   hipLaunchKernelGGL(dsa::k_enc_corr, dim3(gx, ns), dim3(256), 0, st, arena, d_streams, ns);
@@ -1172,6 +1192,7 @@ static dsa_status enc_stage_attributes(dsa_context *ctx, EncLane &lane, EncChunk
   if (device_conn) ENC_TRY(hipMemcpyAsync(L.conns.data(), d_conns, sizeof(dsa::EncConn) * n, hipMemcpyDeviceToHost, st));
   if (nz) ENC_TRY(hipMemcpyAsync(L.seams.data(), d_seams, sizeof(dsa::EncSeam) * nz, hipMemcpyDeviceToHost, st));
   ENC_TRY(hipStreamSynchronize(st));
+  if (order_timing) order_lap("gather to entropy coding");
   return DSA_OK;
 }
 // a mesh the device refused: its status, and its attribute streams are not coded
@@ -1263,7 +1284,7 @@ static dsa_status enc_stage_code(dsa_context *ctx, EncLane &lane, EncChunk &ck, 
   else enc_device_plan_errors(ck);
   if (lap) (*lap)("histograms + symbol plans");
   ck.rans.resize(ns); ck.bits.resize(ns); ck.flag_bits.resize(ns); ck.crease.resize(ck.L.any_crease ? 4 * (size_t)ns : 0);
-  if (!ck.L.rows_of_stream.empty()) ck.entry_rows.resize(ns);
+  if (!ck.L.rows_of_stream.empty() || !ck.L.ord.empty()) ck.entry_rows.resize(ns);
   return ns ? enc_code_streams(ctx, lane, ck) : DSA_OK;
 }
 // host phase 3: the stream layout (threads over meshes; write_stream may throw like any part of the host coder)
@@ -1403,6 +1424,12 @@ static dsa_status enc_check_options(dsa_context *ctx, const dsa_encode_sequentia
   if (d.compress_connectivity != 0 && d.compress_connectivity != 1) ENC_REFUSE("compress_connectivity %d: 0 (raw indices) or 1 (compressed)", (int)d.compress_connectivity);
   ENC_RESERVED(d, 6, "dsa_encode_sequential_options");
   return DSA_OK;
+}
+// ... in an order of the encoder's choosing (dsa_encode_order.h)
+static dsa_status enc_check_options(dsa_context *ctx, const dsa_encode_order_options &o, bool null_argument) {
+  if (o.point_order != 0 && o.point_order != 1) ENC_REFUSE("point_order %d: 0 (the caller's order) or 1 (Morton order of the quantised positions)", (int)o.point_order);
+  ENC_RESERVED(o, 7, "dsa_encode_order_options");
+  return enc_check_options(ctx, o.sequential, null_argument);
 }
 #undef ENC_RESERVED
 #undef ENC_REFUSE
@@ -1669,13 +1696,18 @@ static dsa_status encode_edgebreaker(dsa_context *ctx, uint32_t n, const dsa_mes
   rq.track_rows = w.track_rows == 1;
   return encode_checked(ctx, rq, grids, o.grid.repair.topology == 1, out);
 }
-static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_sequential_options *options, dsa_encoded **out) {
+static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_order_options &o, dsa_encoded **out) {
+  if (enc_check_options(ctx, o, !ctx || !out || (n && !meshes)) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
   EncRequest rq;
   rq.n = n; rq.meshes = meshes; rq.sequential = true;
-  dsa_encode_sequential_default_options(&rq.seq);
-  if (options) rq.seq = *options;
-  if (enc_check_options(ctx, rq.seq, !ctx || !out || (n && !meshes)) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+  rq.seq = o.sequential; rq.point_order = o.point_order == 1;
   return encode_checked(ctx, rq, grids, false, out);
+}
+static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_sequential_options *options, dsa_encoded **out) {
+  dsa_encode_order_options o;
+  dsa_encode_default_order_options(&o);
+  if (options) o.sequential = *options;
+  return encode_sequential(ctx, n, meshes, grids, o, out);
 }
 // the array of a narrower entry point widened, owned by the call
 template <class Mesh>
@@ -1710,6 +1742,11 @@ void dsa_encode_sequential_default_options(dsa_encode_sequential_options *o) {
   dsa_encode_default_options(&o->base);
   o->geometry = 1;
   o->compress_connectivity = 0;
+}
+void dsa_encode_default_order_options(dsa_encode_order_options *o) {
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  dsa_encode_sequential_default_options(&o->sequential);
 }
 void dsa_encode_default_repair_options(dsa_encode_repair_options *o) {
   if (!o) return;
@@ -1816,6 +1853,11 @@ dsa_status dsa_encode_attributes_sequential_batch(dsa_context *ctx, uint32_t n, 
 dsa_status dsa_encode_grid_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_sequential_options *options, dsa_encoded **out) {
   DSA_GUARD(ctx, encode_sequential(ctx, n, meshes, grids, options, out));
 }
+// ... with the points of every stream in an order of the encoder's choosing (point_order = 1: Morton order of the quantised
+// positions, found on the device -- dsa_encode_order.h); point_order = 0 is the very request of the call above.
+dsa_status dsa_encode_ordered_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_order_options *options, dsa_encoded **out) {
+  DSA_GUARD(ctx, [&] { dsa_encode_order_options o; dsa_encode_default_order_options(&o); if (options) o = *options; return encode_sequential(ctx, n, meshes, grids, o, out); }());
+}
 
 struct dsa_welded {
   dsa_context *ctx = nullptr;
@@ -1879,25 +1921,25 @@ dsa_status dsa_encoded_attributes(const dsa_encoded *e, uint32_t mesh, uint32_t 
   *count = 0;
   if (e->status[mesh] != DSA_OK) return set_err(e->ctx, (dsa_status)e->status[mesh], "mesh %u: %s", mesh, e->messages[mesh].c_str());
   if (e->rows_kind == dsa_encoded::ROWS_NONE) return set_err(e->ctx, DSA_ERR_INVALID_ARGUMENT, "the entry rows of this handle were not kept: encode with dsa_encode_rows_batch and track_rows = 1");
-  *count = e->rows_kind == dsa_encoded::ROWS_LINEAR ? e->linear[mesh].first : (uint32_t)e->rows[mesh].size();
+  *count = e->row_attributes(mesh);
   return DSA_OK;
 }
-// The entry rows of attribute `attribute` of stream `mesh`: a sequential handle answers with the identity, an Edgebreaker handle
-// with what track_rows kept.
+// The entry rows of attribute `attribute` of stream `mesh`: a sequential handle answers with the identity (with point_order = 1:
+// with the permutation, the same for every attribute), an Edgebreaker handle with what track_rows kept.
 dsa_status dsa_encoded_entry_rows(const dsa_encoded *e, uint32_t mesh, uint32_t attribute, uint32_t *dst, size_t capacity, uint32_t *count) {
   if (!e || mesh >= e->streams.size() || !count) return DSA_ERR_INVALID_ARGUMENT;
   *count = 0;
   if (e->status[mesh] != DSA_OK) return set_err(e->ctx, (dsa_status)e->status[mesh], "mesh %u: %s", mesh, e->messages[mesh].c_str());
   if (e->rows_kind == dsa_encoded::ROWS_NONE) return set_err(e->ctx, DSA_ERR_INVALID_ARGUMENT, "the entry rows of this handle were not kept: encode with dsa_encode_rows_batch and track_rows = 1");
-  const bool linear = e->rows_kind == dsa_encoded::ROWS_LINEAR;
-  const uint32_t attributes = linear ? e->linear[mesh].first : (uint32_t)e->rows[mesh].size();
+  const uint32_t attributes = e->row_attributes(mesh);
   if (attribute >= attributes) return set_err(e->ctx, DSA_ERR_INVALID_ARGUMENT, "mesh %u: attribute %u of %u", mesh, attribute, attributes);
-  const uint32_t entries = linear ? e->linear[mesh].second : (uint32_t)e->rows[mesh][attribute].size();
+  const uint32_t entries = e->row_entries(mesh, attribute);
+  const uint32_t *rows = e->row_data(mesh, attribute);
   *count = entries;
   if (!dst) return DSA_OK;
   if (capacity < entries) return set_err(e->ctx, DSA_ERR_INVALID_ARGUMENT, "mesh %u, attribute %u: %u entry rows, room for %llu", mesh, attribute, entries, (unsigned long long)capacity);
-  if (linear) for (uint32_t i = 0; i < entries; ++i) dst[i] = i;
-  else if (entries) memcpy(dst, e->rows[mesh][attribute].data(), 4ull * entries);
+  if (!rows) for (uint32_t i = 0; i < entries; ++i) dst[i] = i;
+  else if (entries) memcpy(dst, rows, 4ull * entries);
   return DSA_OK;
 }
 

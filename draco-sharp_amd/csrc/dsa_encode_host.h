@@ -2050,6 +2050,28 @@ static void encode_mesh_sequential(const MeshIn &in, const Options &opt, bool co
   m.generic = nullptr;
   encode_sequential(m, opt, true, compressed, out);
 }
+// Morton order of the points of a sequential stream (dsa_encode_ordered_sequential_batch, point_order = 1; the device's kernels
+// are dsa_encode_order.h): with q the integers the position stream codes (quantize: own bounds, or `grid` with mode 1) and B = bits,
+// key(r) = sum over b < B, c < 3 of ((uint32(q[r][c]) >> b) & 1) << (3 b + 2 - c); perm lists the rows in ascending (key, row).
+static inline uint64_t point_order_key(const int32_t *q, int bits) {
+  uint64_t key = 0;
+  for (int b = 0; b < bits; ++b)
+    for (int c = 0; c < 3; ++c) key |= (uint64_t)(((uint32_t)q[c] >> b) & 1u) << (3 * b + 2 - c);
+  return key;
+}
+static void point_order(const float *pos, uint32_t n, int bits, const Grid *grid, std::vector<uint32_t> &perm) {
+  check(bits >= 1 && bits <= 20, "quantisation bits out of range (positions/texcoords 1..20, normals 2..20)");
+  check(pos != nullptr && n > 0, "positions are missing");
+  PortableAttr a;
+  a.att_type = 0; a.nc = a.nc_out = 3; a.seq_type = 2; a.grid = grid;
+  quantize(pos, n, 3, bits, a);
+  std::vector<uint64_t> key(n);
+  for (uint32_t r = 0; r < n; ++r) key[r] = point_order_key(a.vals.data() + (size_t)3 * r, bits);
+  perm.resize(n);
+  for (uint32_t r = 0; r < n; ++r) perm[r] = r;
+  std::stable_sort(perm.begin(), perm.end(), [&](uint32_t x, uint32_t y) { return key[x] < key[y]; });
+}
+
 // Point cloud, sequential (BASELINE config 1), positions only: int32 num_points, one attributes decoder, positions quantised,
 // Difference + Wrap in linear order, always through the symbol coder.
 static void encode_point_cloud(const float *pos, uint32_t n, const Options &opt, std::vector<uint8_t> &out) {

@@ -30,6 +30,7 @@
 #include "dsa_encode_schemes.h"
 #include "dsa_encode_multi.h"
 #include "dsa_encode_rows.h"
+#include "dsa_encode_order.h"
 
 namespace dsa {
 
@@ -111,17 +112,25 @@ struct dsa_encoded {
   std::vector<int32_t> status;
   std::vector<std::string> messages;
   // entry rows (dsa_encoded_entry_rows).  ROWS_TRACKED: rows[mesh][attribute of the stream], kept by a call with track_rows = 1
-  // (dsa_encode_rows.h); ROWS_LINEAR: a sequential call, entry i is row i, and linear[mesh] = (attributes, points) is all it takes
-  enum { ROWS_NONE = 0, ROWS_TRACKED = 1, ROWS_LINEAR = 2 };
+  // (dsa_encode_rows.h); ROWS_LINEAR: a sequential call, entry i is row i, and linear[mesh] = (attributes, points) is all it takes;
+  // ROWS_ORDERED: a sequential call with point_order = 1 (dsa_encode_order.h): linear[mesh] as before, and order[mesh] the
+  // permutation every attribute of the stream went through, kept once
+  enum { ROWS_NONE = 0, ROWS_TRACKED = 1, ROWS_LINEAR = 2, ROWS_ORDERED = 3 };
   int rows_kind = ROWS_NONE;
   std::vector<std::vector<std::vector<uint32_t>>> rows;
   std::vector<std::pair<uint32_t, uint32_t>> linear;
-  void keep_rows(int kind, size_t n) { rows_kind = kind; if (kind == ROWS_TRACKED) rows.resize(n); if (kind == ROWS_LINEAR) linear.resize(n); }
+  std::vector<std::vector<uint32_t>> order;
+  void keep_rows(int kind, size_t n) { rows_kind = kind; if (kind == ROWS_TRACKED) rows.resize(n); if (kind == ROWS_LINEAR || kind == ROWS_ORDERED) linear.resize(n); if (kind == ROWS_ORDERED) order.resize(n); }
+  // attributes of stream `mesh` with entry rows; entries of attribute a; their rows (null: entry e is row e)
+  uint32_t row_attributes(size_t mesh) const { return rows_kind == ROWS_TRACKED ? (uint32_t)rows[mesh].size() : linear[mesh].first; }
+  uint32_t row_entries(size_t mesh, uint32_t a) const { return rows_kind == ROWS_TRACKED ? (uint32_t)rows[mesh][a].size() : linear[mesh].second; }
+  const uint32_t *row_data(size_t mesh, uint32_t a) const { return rows_kind == ROWS_TRACKED ? rows[mesh][a].data() : (rows_kind == ROWS_ORDERED ? order[mesh].data() : nullptr); }
   // mesh `from` of `part` into place `to`: stream, status, message and what it has of rows
   void take(size_t to, dsa_encoded &part, size_t from) {
     streams[to].swap(part.streams[from]); status[to] = part.status[from]; messages[to].swap(part.messages[from]);
     if (rows_kind == ROWS_TRACKED && from < part.rows.size()) rows[to].swap(part.rows[from]);
-    if (rows_kind == ROWS_LINEAR && from < part.linear.size()) linear[to] = part.linear[from];
+    if ((rows_kind == ROWS_LINEAR || rows_kind == ROWS_ORDERED) && from < part.linear.size()) linear[to] = part.linear[from];
+    if (rows_kind == ROWS_ORDERED && from < part.order.size()) order[to].swap(part.order[from]);
   }
 };
 
@@ -163,7 +172,8 @@ struct EncRequest {
   const dsa_mesh_attribute_corners *att_corners = nullptr;      // dsa_encode_corner_attributes_batch: parallel to `meshes` (null: the listed attributes are per vertex)
   bool weld_attributes = false;            // ... weld_attributes = 1: the listed attributes are key sets of their own in the weld (dsa_encode_weld.h: 3 + L key sets)
   bool track_rows = false;                 // dsa_encode_rows_batch, track_rows = 1: the handle keeps the entry rows of every stream (dsa_encode_rows.h)
-  int rows_kind() const { return weld_sink ? dsa_encoded::ROWS_NONE : (sequential ? dsa_encoded::ROWS_LINEAR : (track_rows ? dsa_encoded::ROWS_TRACKED : dsa_encoded::ROWS_NONE)); }
+  bool point_order = false;                // dsa_encode_ordered_sequential_batch, point_order = 1: the points of every stream in Morton order (dsa_encode_order.h)
+  int rows_kind() const { return weld_sink ? dsa_encoded::ROWS_NONE : (sequential ? (point_order ? dsa_encoded::ROWS_ORDERED : dsa_encoded::ROWS_LINEAR) : (track_rows ? dsa_encoded::ROWS_TRACKED : dsa_encoded::ROWS_NONE)); }
   dsa_encode_level_options level{};        // Edgebreaker streams
   dsa_encode_sequential_options seq{};     // sequential streams
   const dsa_encode_options &base() const { return sequential ? seq.base : level.ex.base; }
@@ -194,6 +204,7 @@ static synth::Options enc_synth_options(const EncRequest &rq) {
   return opt;
 }
 
+static_assert(ORD_TILE == DSA_ENCODE_ORDER_TILE, "the header tells the sort's tile size");
 struct EncCopy { uint64_t off, src_off; uint32_t bytes, pad; };      // a region filled from the lane's repair arena (enc_stage_uploads), not from host memory; the layout of dsa::PackItem
 struct EncUpload { uint64_t off; const void *src; size_t bytes; bool narrow; };       // narrow: src is u32[bytes / 2], the staging copy keeps the low halves
 // The arena, handed out in 256-byte aligned regions one behind the other.
@@ -217,6 +228,12 @@ struct EncLayout {
   uint32_t max_rows = 0, maxf = 0, max_count = 0; // grid sizes: value rows / entries of a stream, faces of a mesh, index symbols of a mesh
   bool any_multi = false, any_crease = false, any_valence = false;      // streams predicted by method 2 / 4; by method 4; meshes coded with valence symbols
   bool any_grid = false;                    // streams on a grid that is not their own bounds (k_enc_grid_quantize)
+  // EncRequest::point_order (dsa_encode_order.h): one record per mesh that passed its checks and the (cloud, tile) pairs of all of
+  // them, both among the uploads at ord_at / ord_tiles_at
+  std::vector<dsa::EncOrder> ord;
+  std::vector<dsa::EncOrderTile> ord_tiles;
+  uint64_t ord_at = 0, ord_tiles_at = 0;
+  uint32_t ord_passes = 0;
 };
 
 static inline bool enc_multi_scheme(const synth::PortableAttr &a) { return a.seq_type != 3 && (a.prediction == 2 || a.prediction == 4); }
@@ -773,9 +790,12 @@ static void enc_layout(EncChunk &ck) {
 
 // ---- the arena of a chunk of sequential streams: the attributes in point order, and with compressed indices the index stream
 // behind them, a list of 3F symbols below 2V given by k_enc_seq_indices from the faces (16-bit where every index fits)
+// EncRequest::point_order: no stream is linear -- every value stream of a cloud reads its entries through one shared entry -> row
+// map, the permutation the sort kernels of dsa_encode_order.h leave (their records and tile list among the uploads, their
+// regions among what the kernels write).  Without it nothing here moves.
 static void enc_layout_sequential(EncChunk &ck) {
   EncLayout &L = ck.L;
-  const bool compressed = ck.rq.seq.geometry == 1 && ck.rq.seq.compress_connectivity == 1;
+  const bool is_mesh = ck.rq.seq.geometry == 1, compressed = is_mesh && ck.rq.seq.compress_connectivity == 1, ordered = ck.rq.point_order;
   EncArena A;
   A.log = ck.region_log;
   enc_layout_begin(ck, 0, compressed ? 1 : 0);
@@ -786,8 +806,15 @@ static void enc_layout_sequential(EncChunk &ck) {
     const uint32_t V = m.num_vertices, s0 = L.first_stream[i];
     for (size_t k = 0; k < atts.size(); ++k) {
       dsa::EncStream &S = L.streams[s0 + k];
-      S.nv = V; S.prediction = 0; S.linear = 1;
+      S.nv = V; S.prediction = 0; S.linear = ordered ? 0u : 1u;
       enc_value_stream_input(S, atts[k], m, V, A, L.uploads);
+    }
+    if (ordered) {
+      dsa::EncOrder O;
+      memset(&O, 0, sizeof(O));
+      O.n = V; O.tiles = (V + ORD_TILE - 1u) / ORD_TILE; O.bits = (uint32_t)ck.opt.pos_bits;
+      for (uint32_t t = 0; t < O.tiles; ++t) L.ord_tiles.push_back({(uint32_t)L.ord.size(), t});
+      L.ord.push_back(O);
     }
     if (!compressed) continue;
     dsa::EncSeqIdx X;
@@ -797,12 +824,26 @@ static void enc_layout_sequential(EncChunk &ck) {
     L.idx.push_back(X);
     L.max_count = std::max(L.max_count, X.count);
     enc_list_stream(L.streams[X.stream], 2u * V, X.count);
+    if (ordered) { dsa::EncOrder &O = L.ord.back(); O.faces = X.faces; O.count = X.count; O.narrow = X.narrow; }
+  }
+  if (!L.ord.empty()) {                                        // (the vectors are complete: their storage stays where it is until the upload)
+    L.ord_passes = dsa::enc_order_passes((uint32_t)ck.opt.pos_bits);
+    L.ord_at = A.put(L.uploads, L.ord.data(), sizeof(dsa::EncOrder) * L.ord.size(), false);
+    L.ord_tiles_at = A.put(L.uploads, L.ord_tiles.data(), sizeof(dsa::EncOrderTile) * L.ord_tiles.size(), false);
   }
   L.input_bytes = A.cur;
-  for (uint32_t i = 0; i < ck.n; ++i) {
+  for (uint32_t i = 0, o = 0; i < ck.n; ++i) {
     if (!ck.good(i)) continue;
     const uint32_t V = ck.mesh(i).num_vertices, s0 = L.first_stream[i], na = (uint32_t)ck.plans[i].atts.size();
+    if (ordered) {                                             // the sort's regions; the buffer its last pass writes is the streams' map
+      dsa::EncOrder &O = L.ord[o++];
+      for (int b = 0; b < 2; ++b) { O.key[b] = A.take(8ull * V); O.row[b] = A.take(4ull * V); }
+      O.hist = A.take(4ull * ORD_RADIX * O.tiles);
+      if (is_mesh) O.rank = A.take(4ull * V);
+      for (uint32_t k = 0; k < na; ++k) L.streams[s0 + k].e2v = O.row[L.ord_passes & 1u];
+    }
     for (uint32_t k = 0; k < na; ++k) enc_value_stream_regions(L.streams[s0 + k], V, ck.hist_cap_of(i, k), A);
+    if (ordered) L.ord[o - 1].vals = L.streams[s0].vals;      // (the positions are attribute 0: their stream is the mesh's first)
     L.max_rows = std::max(L.max_rows, V);
     if (compressed) enc_list_stream_regions(L.streams[s0 + na], A, true, false);
   }

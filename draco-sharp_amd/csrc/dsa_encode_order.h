@@ -1,0 +1,222 @@
+// draco-sharp_amd/csrc/dsa_encode_order.h  (included by dsa_encode_layout.h, whose layout hands out the regions below)
+//
+// Encode direction, dsa_encode_ordered_sequential_batch with point_order = 1: the points of every sequential stream of a chunk in
+// Morton order of their quantised positions.  With q[r][c] the integer the position stream codes for component c of row r (the
+// `vals` k_enc_quantize / k_enc_grid_quantize wrote) and B = position_bits,
+//     key(r) = sum over b < B, c < 3 of ((uint32(q[r][c]) >> b) & 1) << (3 b + 2 - c)        (x the top bit of each triple)
+// and perm lists the rows in ascending (key, row): entry e of every attribute of the stream carries row perm[e], a face index f is
+// written rank[f], rank the inverse of perm.  Only the low B bits of an integer are read, so whatever the quantiser left of a value
+// the call does not check (a NaN under own bounds) still gives a permutation.  The host coder's twin is synth::point_order
+// (dsa_encode_host.h); tests/hostcheck/encorder_host.cpp holds the two against each other under the sanitizers.
+//
+// A segmented, stable, least-significant-digit radix sort of (key, row) over all clouds of the chunk at once: 8 bits a pass,
+// ceil(3 B / 8) passes (11 bits: 5, 20 bits: 8), keys and rows in double buffers.  The grid of every step is the chunk's list of
+// (cloud, tile) pairs, a tile ORD_TILE consecutive entries of one cloud, so that a launch covers clouds of one point and of millions
+// side by side and nothing is launched per cloud:
+//   k_enc_order_keys      a thread per point: the key by shift-and-mask spreading (no loop over bits), row = its index
+//   per pass
+//   k_enc_order_hist      a wave per tile: the digits of its entries counted in LDS (counts do not depend on who adds first),
+//                         written to hist[digit * tiles + tile] of the cloud
+//   k_enc_order_scan      a wave per cloud: exclusive scan of its histogram in (digit, tile) order -- where every (digit, tile) starts
+//   k_enc_order_scatter   a wave per tile, 64 consecutive entries a step in entry order: the lanes of equal digit find each other by
+//                         8 ballots, a lane's place is the tile's running count of its digit (LDS, read by all, advanced by the
+//                         lowest lane of each digit) plus the lanes of its digit below it.  No atomic decides a place: the
+//                         sort is stable, ties go to the smaller row, the order is a function of the input alone.
+//   k_enc_order_rank      meshes: rank[perm[e]] = e
+//   k_enc_order_faces     compressed indices: the faces in the arena through rank, in front of k_enc_seq_indices (raw indices are
+//                         laid out by the host from the perm that comes back among the chunk's packed pieces)
+// The last pass writes the rows into the region the cloud's streams read as their entry -> row map (EncStream::e2v, linear = 0):
+// k_enc_gather behind it puts every attribute in the order.  Nothing between the quantisers and k_enc_gather goes through the host.
+// Every cloud fits the same three steps a pass; a one-workgroup LDS sort for clouds of one tile was not built (DESIGN.md 7.3 has
+// what the crowded batch of small clouds costs).
+//
+// Wave64 throughout: the tile steps are blocks of one wave (__launch_bounds__(64)), so their barriers order LDS within a wave and
+// many tiles share a CU.  gfx950, hipcc -O3 (VGPR / SGPR / LDS bytes per block): k_enc_order_keys 16 / 26 / 0, hist 11 / 32 /
+// 1024, scan 26 / 24 / 0, scatter 16 / 55 / 1024, rank 6 / 20 / 0, faces 8 / 21 / 0; no scratch, no spills, 8 waves per SIMD.
+// The host check runs a grid thread by thread, where lanes cannot meet: the three wave steps have a serial form for it (lane 0
+// does the tile's or the cloud's work in entry order, as k_enc_weld_scan has) -- records, tile list, regions, pass structure, keys,
+// rank and remap are the product's as they run; the ballots and shuffles themselves are held to the host coder by
+// tests/test_gpu_encode_order.py alone.
+#pragma once
+#include <stdint.h>
+
+namespace dsa {
+
+#define ORD_TILE 1024u             // entries of a tile: 16 steps of one wave
+#define ORD_RADIX 256u             // 8 bits a pass
+#define ORD_SCAN_PER 8u            // histogram entries a lane of k_enc_order_scan sums per step
+
+struct EncOrder {                  // one per cloud of the chunk; in the arena, among the uploads
+  uint64_t vals;                   // i32[3 n]: the position stream's integers, row order
+  uint64_t key[2];                 // u64[n] each: pass p reads [p & 1], writes [(p + 1) & 1]
+  uint64_t row[2];                 // u32[n] each, likewise; row[passes & 1] is the e2v of the cloud's streams: OUTPUT perm
+  uint64_t hist;                   // u32[ORD_RADIX * tiles]: of the pass under way, digit-major
+  uint64_t rank;                   // u32[n] OUTPUT (meshes; else 0): the entry of every row
+  uint64_t faces;                  // compressed indices: u16[count] (narrow) or u32[count], remapped in place; else count 0
+  uint32_t n, tiles;               // points; (n + ORD_TILE - 1) / ORD_TILE
+  uint32_t bits, count;            // position_bits; 3F corners to remap
+  uint32_t narrow, pad;
+};
+struct EncOrderTile { uint32_t cloud, tile; };
+
+static inline uint32_t enc_order_passes(uint32_t bits) { return (3u * bits + 7u) / 8u; }
+
+// bit b of the low 21 bits of x to bit 3 b
+__device__ __forceinline__ uint64_t ord_spread(uint32_t v) {
+  uint64_t x = v & 0x1FFFFFu;
+  x = (x | x << 32) & 0x001F00000000FFFFull;
+  x = (x | x << 16) & 0x001F0000FF0000FFull;
+  x = (x | x << 8) & 0x100F00F00F00F00Full;
+  x = (x | x << 4) & 0x10C30C30C30C30C3ull;
+  x = (x | x << 2) & 0x1249249249249249ull;
+  return x;
+}
+__device__ __forceinline__ uint64_t ord_key(const int32_t *q, uint32_t bits) {
+  const uint32_t mask = (1u << bits) - 1u;                     // (bits 1 .. 20: enc_check_bits)
+  return ord_spread((uint32_t)q[0] & mask) << 2 | ord_spread((uint32_t)q[1] & mask) << 1 | ord_spread((uint32_t)q[2] & mask);
+}
+
+__global__ __launch_bounds__(256) void k_enc_order_keys(uint8_t *arena, const EncOrder *clouds, const EncOrderTile *tiles, uint32_t nt) {
+  if (blockIdx.x >= nt) return;
+  const EncOrderTile T = tiles[blockIdx.x];
+  const EncOrder &O = clouds[T.cloud];
+  const int32_t *vals = (const int32_t *)(arena + O.vals);
+  uint64_t *key = (uint64_t *)(arena + O.key[0]);
+  uint32_t *row = (uint32_t *)(arena + O.row[0]);
+  const uint32_t end = O.n - T.tile * ORD_TILE < ORD_TILE ? O.n : (T.tile + 1u) * ORD_TILE;
+  for (uint32_t r = T.tile * ORD_TILE + threadIdx.x; r < end; r += blockDim.x) { key[r] = ord_key(vals + 3ull * r, O.bits); row[r] = r; }
+}
+
+__device__ __forceinline__ uint32_t ord_digit(uint64_t key, uint32_t pass) { return (uint32_t)(key >> (8u * pass)) & (ORD_RADIX - 1u); }
+
+__global__ __launch_bounds__(WAVE) void k_enc_order_hist(uint8_t *arena, const EncOrder *clouds, const EncOrderTile *tiles, uint32_t nt, uint32_t pass) {
+  if (blockIdx.x >= nt) return;
+  const EncOrderTile T = tiles[blockIdx.x];
+  const EncOrder &O = clouds[T.cloud];
+  const uint64_t *key = (const uint64_t *)(arena + O.key[pass & 1u]);
+  uint32_t *hist = (uint32_t *)(arena + O.hist);
+  const uint32_t lane = threadIdx.x, e0 = T.tile * ORD_TILE, end = O.n - e0 < ORD_TILE ? O.n : e0 + ORD_TILE;
+#if defined(__HIPCC__)
+  __shared__ uint32_t s_count[ORD_RADIX];
+  for (uint32_t d = lane; d < ORD_RADIX; d += WAVE) s_count[d] = 0;
+  __syncthreads();
+  for (uint32_t e = e0 + lane; e < end; e += WAVE) atomicAdd(&s_count[ord_digit(key[e], pass)], 1u);
+  __syncthreads();
+  for (uint32_t d = lane; d < ORD_RADIX; d += WAVE) hist[(size_t)d * O.tiles + T.tile] = s_count[d];
+#else       // the sanitizer build of tests/hostcheck/encorder_host.cpp runs the lanes of a wave one after the other: lane 0 counts
+  if (lane != 0) return;
+  for (uint32_t d = 0; d < ORD_RADIX; ++d) hist[(size_t)d * O.tiles + T.tile] = 0;
+  for (uint32_t e = e0; e < end; ++e) hist[(size_t)ord_digit(key[e], pass) * O.tiles + T.tile] += 1u;
+#endif
+}
+
+// one wave per cloud: blockIdx.x = cloud
+__global__ __launch_bounds__(WAVE) void k_enc_order_scan(uint8_t *arena, const EncOrder *clouds, uint32_t nc) {
+  if (blockIdx.x >= nc) return;
+  const EncOrder &O = clouds[blockIdx.x];
+  uint32_t *hist = (uint32_t *)(arena + O.hist);
+  const uint32_t total = ORD_RADIX * O.tiles, lane = threadIdx.x;        // (tiles <= 2^18: the layout takes clouds of up to 2^28 points)
+  uint32_t base = 0;
+#if defined(__HIPCC__)
+  for (uint32_t i0 = 0; i0 < total; i0 += WAVE * ORD_SCAN_PER) {        // (total is a multiple of ORD_SCAN_PER: a lane's run is inside or outside)
+    const uint32_t i = i0 + lane * ORD_SCAN_PER;
+    uint32_t x[ORD_SCAN_PER], sum = 0;
+    for (uint32_t k = 0; k < ORD_SCAN_PER; ++k) { x[k] = i < total ? hist[i + k] : 0u; sum += x[k]; }
+    uint32_t incl = sum;
+    for (int d = 1; d < WAVE; d <<= 1) { const uint32_t y = (uint32_t)__shfl_up((int)incl, d, WAVE); if ((int)lane >= d) incl += y; }
+    uint32_t at = base + incl - sum;
+    if (i < total) for (uint32_t k = 0; k < ORD_SCAN_PER; ++k) { hist[i + k] = at; at += x[k]; }
+    base += (uint32_t)__shfl((int)incl, WAVE - 1, WAVE);
+  }
+#else       // (as k_enc_order_hist: lane 0 sums)
+  if (lane != 0) return;
+  for (uint32_t i = 0; i < total; ++i) { const uint32_t x = hist[i]; hist[i] = base; base += x; }
+#endif
+}
+
+__global__ __launch_bounds__(WAVE) void k_enc_order_scatter(uint8_t *arena, const EncOrder *clouds, const EncOrderTile *tiles, uint32_t nt, uint32_t pass) {
+  if (blockIdx.x >= nt) return;
+  const EncOrderTile T = tiles[blockIdx.x];
+  const EncOrder &O = clouds[T.cloud];
+  const uint64_t *key = (const uint64_t *)(arena + O.key[pass & 1u]);
+  const uint32_t *row = (const uint32_t *)(arena + O.row[pass & 1u]);
+  uint64_t *key_out = (uint64_t *)(arena + O.key[(pass + 1u) & 1u]);
+  uint32_t *row_out = (uint32_t *)(arena + O.row[(pass + 1u) & 1u]);
+  const uint32_t *hist = (const uint32_t *)(arena + O.hist);
+  const uint32_t lane = threadIdx.x, e0 = T.tile * ORD_TILE, end = O.n - e0 < ORD_TILE ? O.n : e0 + ORD_TILE;
+#if defined(__HIPCC__)
+  __shared__ uint32_t s_next[ORD_RADIX];                       // where the tile's next entry of every digit goes
+  for (uint32_t d = lane; d < ORD_RADIX; d += WAVE) s_next[d] = hist[(size_t)d * O.tiles + T.tile];
+  __syncthreads();
+  const unsigned long long below = (1ull << lane) - 1ull;
+  for (uint32_t s0 = e0; s0 < end; s0 += WAVE) {               // (uniform: every lane takes every step)
+    const uint32_t e = s0 + lane;
+    const bool valid = e < end;
+    const uint64_t k = valid ? key[e] : 0ull;
+    const uint32_t r = valid ? row[e] : 0u, d = ord_digit(k, pass);
+    unsigned long long same = __ballot(valid);                 // the lanes of this lane's digit
+    for (uint32_t b = 0; b < 8u; ++b) {
+      const bool bit = ((d >> b) & 1u) != 0;
+      const unsigned long long with = __ballot(valid && bit);
+      same &= bit ? with : ~with;
+    }
+    const uint32_t at = valid ? s_next[d] : 0u;
+    __syncthreads();                                           // (every lane has read before a digit's lowest lane advances its count)
+    if (valid && (same & below) == 0ull) s_next[d] = at + (uint32_t)__popcll(same);
+    __syncthreads();
+    const uint32_t to = at + (uint32_t)__popcll(same & below);
+    if (valid && to < O.n) { key_out[to] = k; row_out[to] = r; }      // (to < n by the scan: the comparison keeps a fault elsewhere inside the cloud's buffers)
+  }
+#else       // (as k_enc_order_hist: lane 0 places the tile's entries in their order)
+  if (lane != 0) return;
+  uint32_t next[ORD_RADIX];
+  for (uint32_t d = 0; d < ORD_RADIX; ++d) next[d] = hist[(size_t)d * O.tiles + T.tile];
+  for (uint32_t e = e0; e < end; ++e) { const uint32_t to = next[ord_digit(key[e], pass)]++; key_out[to] = key[e]; row_out[to] = row[e]; }
+#endif
+}
+
+__global__ __launch_bounds__(256) void k_enc_order_rank(uint8_t *arena, const EncOrder *clouds, const EncOrderTile *tiles, uint32_t nt, uint32_t passes) {
+  if (blockIdx.x >= nt) return;
+  const EncOrderTile T = tiles[blockIdx.x];
+  const EncOrder &O = clouds[T.cloud];
+  if (O.rank == 0) return;
+  const uint32_t *perm = (const uint32_t *)(arena + O.row[passes & 1u]);
+  uint32_t *rank = (uint32_t *)(arena + O.rank);
+  const uint32_t end = O.n - T.tile * ORD_TILE < ORD_TILE ? O.n : (T.tile + 1u) * ORD_TILE;
+  for (uint32_t e = T.tile * ORD_TILE + threadIdx.x; e < end; e += blockDim.x) { const uint32_t r = perm[e]; if (r < O.n) rank[r] = e; }
+}
+
+// grid (blocks over corners, clouds); indices out of range never come here: the host refuses such a mesh before the launch
+__global__ __launch_bounds__(256) void k_enc_order_faces(uint8_t *arena, const EncOrder *clouds, uint32_t nc) {
+  if (blockIdx.y >= nc) return;
+  const EncOrder &O = clouds[blockIdx.y];
+  if (O.count == 0 || O.rank == 0) return;
+  const uint32_t *rank = (const uint32_t *)(arena + O.rank);
+  uint16_t *f16 = (uint16_t *)(arena + O.faces);
+  uint32_t *f32 = (uint32_t *)(arena + O.faces);
+  const bool narrow = O.narrow != 0;
+  for (uint32_t c = blockIdx.x * blockDim.x + threadIdx.x; c < O.count; c += gridDim.x * blockDim.x) {
+    const uint32_t f = narrow ? (uint32_t)f16[c] : f32[c];
+    if (f >= O.n) continue;
+    if (narrow) f16[c] = (uint16_t)rank[f]; else f32[c] = rank[f];
+  }
+}
+
+// The steps over `nc` clouds and their `nt` tiles: launch(kernel, grid x, grid y, block, arguments...) is hipLaunchKernelGGL on the
+// lane's stream in enc_stage_attributes and the thread-by-thread loop in the host check.  gx_faces: blocks over the corners of the
+// chunk's largest mesh with compressed indices (0: no mesh has any); any_rank: the chunk codes meshes.
+template <class Launch>
+static inline void enc_order_launch(Launch &&launch, uint8_t *arena, const EncOrder *clouds, uint32_t nc, const EncOrderTile *tiles, uint32_t nt,
+                                    uint32_t passes, bool any_rank, uint32_t gx_faces) {
+  if (nc == 0 || nt == 0) return;
+  launch(k_enc_order_keys, nt, 1u, 256u, arena, clouds, tiles, nt);
+  for (uint32_t p = 0; p < passes; ++p) {
+    launch(k_enc_order_hist, nt, 1u, (uint32_t)WAVE, arena, clouds, tiles, nt, p);
+    launch(k_enc_order_scan, nc, 1u, (uint32_t)WAVE, arena, clouds, nc);
+    launch(k_enc_order_scatter, nt, 1u, (uint32_t)WAVE, arena, clouds, tiles, nt, p);
+  }
+  if (any_rank) launch(k_enc_order_rank, nt, 1u, 256u, arena, clouds, tiles, nt, passes);
+  if (any_rank && gx_faces) launch(k_enc_order_faces, gx_faces, nc, 256u, arena, clouds, nc);
+}
+
+}  // namespace dsa

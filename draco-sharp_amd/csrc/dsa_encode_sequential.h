@@ -9,6 +9,8 @@
 //          the caller's array into the stream
 //   GPU    k_enc_bounds / k_enc_quantize / k_enc_gather (linear: bounds only) / k_enc_corr   the attributes in point order,
 //                                Difference + wrap, canonicalised octahedral delta (Attributes/LinearSequencer.cs: entry i = point i)
+//          k_enc_order_*         dsa_encode_ordered_sequential_batch, point_order = 1: the points in Morton order behind the quantisers
+//                                (dsa_encode_order.h) -- k_enc_gather then puts every attribute in it, the faces go through its inverse
 //          k_enc_seq_indices     compressed indices: symbols and their statistics (dsa_encode_seqidx.h)
 //          k_enc_plan / k_enc_rans   every stream, the index stream as a list whose symbols are given (kind 3)
 //   host   stream layout (synth::write_sequential_stream)
@@ -26,17 +28,29 @@ static void enc_stage_sequential_streams(EncChunk &ck) {
     const std::vector<synth::PortableAttr> &atts = ck.plans[i].atts;
     const uint32_t s0 = L.first_stream[i], si = s0 + (uint32_t)atts.size();
     const dsa_mesh_input &m = ck.mesh(i);
+    // point_order: the permutation came back with the coded pieces; raw indices are laid out through its inverse
+    const bool ordered = !L.ord.empty();
+    std::vector<uint32_t> ranked;
+    if (ordered && is_mesh && !compressed) {
+      const std::vector<uint32_t> &perm = ck.entry_rows[s0];
+      if (perm.size() != m.num_vertices) return ck.refuse(i, DSA_ERR_DEVICE, "the point order did not come back");
+      std::vector<uint32_t> rank(perm.size(), 0);
+      for (uint32_t e = 0; e < perm.size(); ++e) if (perm[e] < rank.size()) rank[perm[e]] = e;
+      ranked.resize((size_t)m.num_faces * 3);
+      for (size_t k = 0; k < ranked.size(); ++k) ranked[k] = rank[m.faces[k]];
+    }
     synth::ByteWriter w;
     try {
       synth::write_sequential_stream(w, is_mesh, m.num_vertices, is_mesh ? m.num_faces : 0, compressed, atts,
         [&](synth::ByteWriter &bw) {               // (raw indices never travel: narrowed from the caller's array into the stream)
           if (compressed) enc_put_coded(bw, ck.splans[si], ck.rans[si], ck.bits[si], L.streams[si].method);
-          else synth::write_raw_indices(bw, m.faces, (size_t)m.num_faces * 3, m.num_vertices);
+          else synth::write_raw_indices(bw, ordered ? ranked.data() : m.faces, (size_t)m.num_faces * 3, m.num_vertices);
         },
         [&](synth::ByteWriter &bw, size_t k) { enc_write_attribute_values(bw, ck, s0 + (uint32_t)k, 0); },      // Difference
         [&](synth::ByteWriter &bw, size_t k) { enc_write_transform(bw, L.streams[s0 + k]); });
     } catch (const std::exception &e) { return ck.refuse(i, DSA_ERR_INVALID_DATA, e.what()); }
     ck.E->streams[i].swap(w.d);
+    if (ordered) ck.E->order[i].swap(ck.entry_rows[s0]);
   });
 }
 // Meshes base .. base + count of a sequential request on a lane, through the stages it shares with encode_chunk.  No stage waits for

@@ -1,7 +1,7 @@
 // draco-sharp_amd/csrc/dsa_source_rows.h  (included by dsa_api.hip, behind dsa_encode.h)
 //
 // dsa_batch_source_rows: for a batch decoded from the streams of an encode that kept its entry rows (dsa_encode_rows_batch,
-// track_rows = 1; a sequential handle: the identity), per mesh and attribute one uint32 array with a row per POINT -- which row of
+// track_rows = 1; a sequential handle: the identity, or with point_order = 1 the stored permutation), per mesh and attribute one uint32 array with a row per POINT -- which row of
 // the arrays the encoder was given the point carries.  Shaped like the vertex arrays (dsa_batch_vertex_arrays): a device block of
 // the batch's own [table of SrcRowsMesh | the tracked entry rows | the arrays], filled from pinned staging in one transfer on the
 // download stream, k_source_rows (dsa_encode_rows.h) behind the decode's kernels, the arrays down in one transfer, an event of their
@@ -20,12 +20,12 @@ static int32_t sr_mesh_status(const dsa_batch *b, uint32_t i, const dsa_encoded 
   if (e->status[em] != DSA_OK) return e->status[em];
   const MeshLayout &L = b->layouts[i];
   if (e->streams[em].size() != L.stream_len) return DSA_ERR_INVALID_ARGUMENT;
-  const uint32_t attributes = e->rows_kind == dsa_encoded::ROWS_LINEAR ? e->linear[em].first : (uint32_t)e->rows[em].size();
+  const uint32_t attributes = e->row_attributes(em);
   if (attributes != L.cap_attributes || attributes > DSA_MAX_ATT) return DSA_ERR_INVALID_ARGUMENT;
   return DSA_OK;
 }
 static uint32_t sr_entries(const dsa_encoded *e, uint32_t em, uint32_t a) {
-  return e->rows_kind == dsa_encoded::ROWS_LINEAR ? e->linear[em].second : (uint32_t)e->rows[em][a].size();
+  return e->row_entries(em, a);
 }
 // The table and the sizes of the block's parts: head = table + tracked entry rows (what goes up), then the arrays (what comes down).
 struct SrcRowsPlan { std::vector<dsa::SrcRowsMesh> table; std::vector<int32_t> status; uint64_t table_bytes = 0, head_bytes = 0, bytes = 0; };
@@ -98,7 +98,7 @@ static dsa_status batch_source_rows(dsa_batch *b, const dsa_encoded *e, const ui
   hostutil::parallel_for(b->n, [&](uint32_t i) {
     const dsa::SrcRowsMesh &T = b->sr[i];
     for (uint32_t a = 0; a < T.num_attributes; ++a)
-      if (T.att[a].rows != dsa::SRC_ROWS_IDENTITY && T.att[a].num_rows) memcpy(b->sr_pin + T.att[a].rows, e->rows[b->sr_map[i]][a].data(), 4ull * T.att[a].num_rows);
+      if (T.att[a].rows != dsa::SRC_ROWS_IDENTITY && T.att[a].num_rows) memcpy(b->sr_pin + T.att[a].rows, e->row_data(b->sr_map[i], a), 4ull * T.att[a].num_rows);
   }, 64);
   HIP_TRY(ctx, hipMemcpyAsync(b->d_sr, b->sr_pin, P.head_bytes, hipMemcpyHostToDevice, ctx->down));
   HIP_TRY(ctx, hipStreamWaitEvent(ctx->down, b->ev_done, 0));

@@ -57,7 +57,14 @@ class Config:
     track_rows (dsa_encode_rows_batch): the result keeps, per stream and attribute, which row of the arrays passed every entry of
     the stream carries (EncodedStreams.entry_rows) -- what carries morph targets or simulation state across Edgebreaker's
     renumbering, the repair's new vertices and the weld.  The streams are the bytes they are without it; 4 bytes per entry and
-    attribute are kept.  Sequential streams need no tracking: their entry i is row i."""
+    attribute are kept.  Sequential streams need no tracking: their entry i is row i.
+
+    point_order (dsa_encode_ordered_sequential_batch): 0 the points of a sequential stream in the caller's order; 1
+    (POINT_ORDER_MORTON) in Morton order of their quantised positions, found on the device -- entry e of every attribute carries
+    row perm[e] of the caller's arrays, faces are written through the inverse.  The format gives the order of a sequential stream
+    no meaning, and a scan or a shuffled sample codes to half its size or less this way.  EncodedStreams.entry_rows(i) returns
+    perm (the same for every attribute) and Batch.source_rows carries side data across.  Sequential streams and point clouds
+    only: Edgebreaker orders its own entries."""
 
     EDGEBREAKER_METHODS = (0, 2, -1)
     POSITION_PREDICTIONS = (0, 1)
@@ -66,18 +73,20 @@ class Config:
     ENCODING_METHODS = (1, 0, -1)
     MULTI_PARALLELOGRAMS = (0, 2, 4, -1)
     TRAVERSAL_METHODS = (0, 1, 2)
+    POINT_ORDERS = (native.POINT_ORDER_CALLER, native.POINT_ORDER_MORTON)
 
     def __init__(self, position_bits=11, texcoord_bits=10, normal_bits=8, speed=5, single_connectivity=False,
                  symbol_scheme=-1, position_prediction=1, texcoord_prediction=1, edgebreaker_method=0, normal_prediction=0,
                  encoding_method=1, compress_connectivity=False, multi_parallelogram=0, traversal_method=0, repair_topology=False, weld_points=False,
-                 repair_seams=False, weld_attributes=False, track_rows=False):
+                 repair_seams=False, weld_attributes=False, track_rows=False, point_order=0):
         for name, value, legal in (("encoding_method", encoding_method, self.ENCODING_METHODS),
                                    ("edgebreaker_method", edgebreaker_method, self.EDGEBREAKER_METHODS),
                                    ("position_prediction", position_prediction, self.POSITION_PREDICTIONS),
                                    ("texcoord_prediction", texcoord_prediction, self.TEXCOORD_PREDICTIONS),
                                    ("normal_prediction", normal_prediction, self.NORMAL_PREDICTIONS),
                                    ("multi_parallelogram", multi_parallelogram, self.MULTI_PARALLELOGRAMS),
-                                   ("traversal_method", traversal_method, self.TRAVERSAL_METHODS)):
+                                   ("traversal_method", traversal_method, self.TRAVERSAL_METHODS),
+                                   ("point_order", point_order, self.POINT_ORDERS)):
             if value not in legal:
                 raise ValueError("%s %r: the encoder writes one of %s" % (name, value, legal))
         self.position_bits, self.texcoord_bits, self.normal_bits = position_bits, texcoord_bits, normal_bits
@@ -103,6 +112,7 @@ class Config:
         if self.weld_attributes and not self.weld_points:
             raise ValueError("weld_attributes welds the listed attributes of per-point input each alone: it needs weld_points=True")
         self.track_rows = bool(track_rows)
+        self.point_order = point_order
 
     @property
     def sequential(self):
@@ -115,6 +125,13 @@ class Config:
         o.base = self._native()
         o.geometry = geometry
         o.compress_connectivity = 1 if (self.compress_connectivity and geometry == 1) else 0
+        return o
+
+    def _native_order(self, geometry):
+        o = native.EncodeOrderOptions()
+        native.lib().dsa_encode_default_order_options(C.byref(o))
+        o.sequential = self._native_sequential(geometry)
+        o.point_order = self.point_order
         return o
 
     @property
@@ -492,7 +509,7 @@ class EncodedStreams:
         """Of stream i a list with one uint32 array per attribute of the stream (positions, then normals, texture coordinates,
         generic where present, then the attribute list): element e is the row of the array passed for that attribute whose bytes
         entry e of the stream carries -- with weld_points a point of the per-point arrays.  Needs Config(track_rows=True), or a
-        sequential stream (the identity); dsa_encoded_entry_rows."""
+        sequential stream (the identity; with Config(point_order=1) the permutation, for every attribute); dsa_encoded_entry_rows."""
         if self._h is None:
             raise ValueError("the encoded batch was closed")
         return _entry_rows(self._ctx, self._h, i + len(self) if i < 0 else i)
@@ -591,6 +608,8 @@ class DracoEncoder:
             raise ValueError("multi_parallelogram / traversal_method shape Edgebreaker streams: point clouds and sequential streams predict by Difference in point order")
         if (clouds or config.sequential) and any(getattr(m, "per_corner", False) for m in meshes):
             raise ValueError("attributes given per corner need Edgebreaker connectivity (encoding_method 1): a sequential stream has one value per point")
+        if getattr(config, "point_order", 0) != 0 and not (clouds or config.sequential):
+            raise ValueError("point_order needs a sequential stream (encoding_method 0, or point clouds): Edgebreaker orders its own entries")
         weld = getattr(config, "weld_points", False)
         if weld and (clouds or config.sequential):
             raise ValueError("weld_points shapes Edgebreaker streams of meshes: point clouds and sequential streams keep the caller's points")
@@ -647,9 +666,13 @@ class DracoEncoder:
     def _encode_sequential(self, ctx, meshes, config, geometry, handle=False):
         n = len(meshes)
         arr, grids, keep = _native_meshes(meshes)
-        opt = config._native_sequential(geometry)
         h = C.c_void_p()
-        st = native.lib().dsa_encode_grid_sequential_batch(ctx._h, n, arr, grids, C.byref(opt), C.byref(h))
+        if getattr(config, "point_order", 0) != 0:      # (the plain case keeps arriving through the call it always took)
+            opt = config._native_order(geometry)
+            st = native.lib().dsa_encode_ordered_sequential_batch(ctx._h, n, arr, grids, C.byref(opt), C.byref(h))
+        else:
+            opt = config._native_sequential(geometry)
+            st = native.lib().dsa_encode_grid_sequential_batch(ctx._h, n, arr, grids, C.byref(opt), C.byref(h))
         if st != 0:
             _raise(st, ctx.error())
         return (ctx, h, n) if handle else EncodedStreams(ctx, h, n)

@@ -40,6 +40,7 @@ EXPORTS = [
     "dsa_encode_default_seam_repair_options", "dsa_encode_seam_repair_batch",
     "dsa_encode_default_corner_attributes_options", "dsa_encode_corner_attributes_batch",
     "dsa_encode_default_rows_options", "dsa_encode_rows_batch", "dsa_encoded_entry_rows", "dsa_encoded_attributes",
+    "dsa_encode_default_order_options", "dsa_encode_ordered_sequential_batch",
     "dsa_encoded_size", "dsa_encoded_stream", "dsa_encoded_free",
     "dsa_pool_create", "dsa_pool_destroy", "dsa_pool_size", "dsa_pool_last_error", "dsa_pool_decode", "dsa_pool_job_locate",
     "dsa_pool_job_chunks", "dsa_pool_job_free", "dsa_pool_plan",
@@ -78,6 +79,16 @@ class EncodeSequentialOptions(C.Structure):
     clouds (geometry 0) beside the quantisation bits, symbol_scheme and compression_level of dsa_encode_batch."""
     _fields_ = [("base", EncodeOptions), ("geometry", C.c_int32), ("compress_connectivity", C.c_int32),
                 ("reserved", C.c_int32 * 6)]
+
+
+POINT_ORDER_CALLER, POINT_ORDER_MORTON = 0, 1      # dsa_encode_order_options.point_order
+ENCODE_ORDER_TILE = 1024                            # DSA_ENCODE_ORDER_TILE: entries of a tile of the sort behind POINT_ORDER_MORTON
+
+
+class EncodeOrderOptions(C.Structure):
+    """dsa_encode_order_options: the options of dsa_encode_grid_sequential_batch, and point_order (1: the points of every stream in
+    Morton order of their quantised positions; the handle keeps the permutation: dsa_encoded_entry_rows)."""
+    _fields_ = [("sequential", EncodeSequentialOptions), ("point_order", C.c_int32), ("reserved", C.c_int32 * 7)]
 
 
 class MeshInput(C.Structure):
@@ -334,6 +345,10 @@ def lib():
                                                 C.POINTER(EncodeRowsOptions), C.POINTER(vp)]
             L.dsa_encoded_entry_rows.argtypes = [vp, u32, u32, vp, C.c_size_t, C.POINTER(u32)]
             L.dsa_encoded_attributes.argtypes = [vp, u32, C.POINTER(u32)]
+        if hasattr(L, "dsa_encode_ordered_sequential_batch"):
+            L.dsa_encode_default_order_options.argtypes = [C.POINTER(EncodeOrderOptions)]
+            L.dsa_encode_default_order_options.restype = None
+            L.dsa_encode_ordered_sequential_batch.argtypes = [vp, u32, C.POINTER(MeshAttrInput), C.POINTER(MeshGrids), C.POINTER(EncodeOrderOptions), C.POINTER(vp)]
         L.dsa_encoded_size.restype = u32
         L.dsa_encoded_size.argtypes = [vp]
         L.dsa_encoded_stream.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(C.c_size_t)]

@@ -233,6 +233,7 @@ def lib():
         L.synth_encode_grid.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                         C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(ExtraInput), C.c_uint32,
                                         C.POINTER(GridsInput), C.POINTER(Options), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+        L.synth_point_order.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(Grid), C.c_void_p]
         L.synth_shared_grid.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_uint32, C.c_int, C.POINTER(Grid)]
         L.synth_free.argtypes = [C.c_void_p]
         L.synth_make_mesh.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_uint32),
@@ -510,6 +511,42 @@ def encode_grid(pos, faces=None, normals=None, uvs=None, generic=None, extra=Non
     data = C.string_at(out, n.value)
     L.synth_free(out)
     return data
+
+
+def point_order(pos, bits, grid=None):
+    """The Morton order of the points `pos` (N, 3) at `bits` position bits: uint32 perm, the rows in ascending (key, row) with
+    key = the bits of the quantised x, y, z interleaved, x the top bit of every triple.  Quantised as the coder does it: on the
+    positions' own bounds, or on `grid` (grid(), shared_grid()).  The order of dsa_encode_ordered_sequential_batch, point_order = 1."""
+    L = lib()
+    pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+    perm = np.zeros(len(pos), np.uint32)
+    if L.synth_point_order(pos.ctypes.data, len(pos), int(bits), None if grid is None else C.byref(grid), perm.ctypes.data):
+        raise RuntimeError(_err())
+    return perm
+
+
+def encode_ordered(pos, faces=None, normals=None, uvs=None, generic=None, extra=None, opt=None, geometry=1, compressed=False,
+                   pos_grid=None, uv_grid=None):
+    """encode_grid with form=0 for the input in Morton order: (stream, perm) with perm = point_order(pos, opt.pos_bits, pos_grid),
+    every per-point array taken at [perm] and the faces through the inverse of perm.  What
+    dsa_encode_ordered_sequential_batch with point_order = 1 must write, and the rows its handle must report."""
+    opt = opt or options()
+    perm = point_order(pos, opt.pos_bits, pos_grid)
+    take = lambda a: None if a is None else np.ascontiguousarray(np.asarray(a).reshape(len(perm), -1)[perm])      # noqa: E731
+    ex = []
+    for e in (extra or []):
+        e = e if isinstance(e, Extra) else Extra(e)
+        ex.append(Extra(e.values[perm], attribute_type=e.attribute_type, normalized=bool(e.normalized), unique_id=e.unique_id,
+                        quantization_bits=e.quantization_bits, data_type=e.data_type, num_components=e.num_components, grid=e.grid))
+    fc = None
+    if faces is not None:
+        rank = np.zeros(len(perm), np.uint32)
+        rank[perm] = np.arange(len(perm), dtype=np.uint32)
+        fc = rank[np.ascontiguousarray(faces, np.uint32)]
+    gen = None if generic is None else (np.asarray(generic)[perm])
+    data = encode_grid(take(pos), fc, take(normals), take(uvs), gen, ex, opt, form=0, geometry=geometry, compressed=compressed,
+                       pos_grid=pos_grid, uv_grid=uv_grid)
+    return data, perm
 
 
 def entry_rows(pos, faces=None, normals=None, uvs=None, generic=None, extra=None, opt=None, form=1, normal_corners=None, uv_corners=None,

@@ -503,6 +503,16 @@ int synth_shared_grid(const float *const *arrays, const uint32_t *rows, uint32_t
   snprintf(g_err, sizeof(g_err), "no array of the group is free of values that are not finite");
   return 1;
 }
+// The Morton order of `n` points at `bits` position bits (dsa_encode_host.h point_order): perm[n], ascending (key, row); grid NULL
+// or mode 0: the positions' own bounds.
+int synth_point_order(const float *pos, uint32_t n, int bits, const synth::Grid *grid, uint32_t *perm) {
+  try {
+    std::vector<uint32_t> p;
+    synth::point_order(pos, n, bits, grid, p);
+    memcpy(perm, p.data(), 4 * p.size());
+    return 0;
+  } catch (const std::exception &e) { snprintf(g_err, sizeof(g_err), "%s", e.what()); return 1; }
+}
 void synth_free(uint8_t *p) { free(p); }
 
 // Procedural mesh: returns counts; call once with NULL outputs to size, then again to fill.

@@ -669,6 +669,34 @@ dsa_status dsa_encode_rows_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_at
 /* The same for sequential meshes and point clouds (dsa_encode_attributes_sequential_batch). */
 dsa_status dsa_encode_grid_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids,
                                             const dsa_encode_sequential_options *options, dsa_encoded **out);
+/* dsa_encode_grid_sequential_batch with the points of every stream in an order of the encoder's choosing.  A sequential stream
+ * codes its points in the order they come in, Difference + wrap from one to the next, and the format gives that order no meaning:
+ * a scan, a particle set or a shuffled sample codes little better than noise as given, and to half its size or less in an order
+ * that keeps neighbours together.
+ *   point_order = 1: Morton order of the quantised positions.  With q[r][c] the integer the stream codes for component c of
+ *   position row r (on the attribute's own bounds, the caller's grid or its group's, whichever applies) and B = position_bits,
+ *       key(r) = sum over b < B, c < 3 of ((uint32(q[r][c]) >> b) & 1) << (3 b + 2 - c)      (x the top bit of every triple)
+ *   and perm lists the rows in ascending (key(r), r): ties go to the smaller row, so the order is a function of the input alone.
+ *   Entry e of EVERY attribute of the stream carries row perm[e] of the caller's array for that attribute; with geometry 1 every
+ *   face index f is written rank[f], rank the inverse of perm, faces and the corners within a face in the caller's order.  The
+ *   stream is byte for byte that of dsa_encode_grid_sequential_batch for positions[perm], normals[perm], ... every listed
+ *   attribute[perm] and rank[faces] with the same options and grids: an ordinary sequential Draco 2.2 stream.  The order is found
+ *   on the device (a key per point and a segmented radix sort over all clouds of a chunk, ceil(3 B / 8) passes).  The handle keeps
+ *   perm per coded stream, 4 bytes per point: dsa_encoded_entry_rows returns it for every attribute of the stream, and
+ *   dsa_batch_source_rows works with such a handle as with one of dsa_encode_rows_batch.  Every refusal of a mesh keeps its
+ *   status and text, and a refused mesh fails alone.
+ *   point_order = 0: the bytes, the messages, the work and the identity rows of dsa_encode_grid_sequential_batch.
+ * point_order outside {0, 1} or a non-zero reserved word fails the call with DSA_ERR_INVALID_ARGUMENT and dsa_last_error names
+ * the field.  Added after ABI 4 without changing it: callers detect the feature by the symbol dsa_encode_ordered_sequential_batch. */
+#define DSA_ENCODE_ORDER_TILE 1024u       /* entries of a tile of the sort (what a test of its edges is sized by) */
+typedef struct dsa_encode_order_options {
+  dsa_encode_sequential_options sequential; /* as for dsa_encode_grid_sequential_batch, same legal values */
+  int32_t point_order;                     /* 0 (default): the caller's order; 1: Morton order of the quantised positions */
+  int32_t reserved[7];                     /* must be zero */
+} dsa_encode_order_options;
+void dsa_encode_default_order_options(dsa_encode_order_options *options);
+dsa_status dsa_encode_ordered_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids,
+                                               const dsa_encode_order_options *options, dsa_encoded **out);
 /* The rows of a decoded batch per POINT: for every mesh of `batch` and every attribute a of its stream,
  *     rows[a][p] = entry_rows[a][map[a][p]]          (map: the decoder's point -> entry map, dsa_batch_device_point_map)
  * -- which row of the arrays given to the encoder point p carries, gathered on the device (k_source_rows) so that neither the maps
