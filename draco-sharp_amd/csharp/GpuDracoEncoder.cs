@@ -73,6 +73,15 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
     // sequential stream no meaning, and a scan or a shuffled sample codes to half its size or less this way.  Edgebreaker streams
     // order their own entries: with 1 an Edgebreaker encode throws.
     public int PointOrder { get; set; }
+    // MergePoints (dsa_encode_merged_sequential_batch): 0 every point is coded; 1 one point per occupied cell of the position grid of a
+    // point cloud -- of the points whose quantised positions are equal the one with the smallest row stays, entry j of every attribute
+    // carries row kept[j], every quantised attribute keeps the bounds of all input rows.  EntryRows(i) returns kept for every
+    // attribute, RowEntries(i) the entry of the cell of every input row.  Needs PointOrder 1; point clouds only: merging the points of
+    // a mesh would collapse its faces, and an encode of meshes throws.
+    public int MergePoints { get; set; }
+    private uint[][] _rowEntries;
+    // Of stream i of the most recent Encode with MergePoints: for every input row the entry of the stream whose cell the row lies in.
+    public uint[] RowEntries(int i) => _rowEntries != null && i >= 0 && i < _rowEntries.Length ? _rowEntries[i] : throw new InvalidOperationException("no row entries: set MergePoints before Encode");
     private uint[][][] _entryRows;
     // Of stream i of the most recent Encode with TrackRows: per attribute of the stream (positions, then normals, texture coordinates,
     // generic where present, then the others) the row of the input every entry carries.
@@ -177,6 +186,28 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
                     inputs[i].Faces = (uint*)Pin(faces, pins);
                 }
             }
+            if (MergePoints != 0)
+            {
+                if (geometry != 0) throw new ArgumentException("MergePoints takes point clouds: merging the points of a mesh would collapse its faces and lose its seams");
+                NativeMethods.dsa_encode_default_merge_options(out var mo);
+                mo.Order.Sequential = so;
+                mo.Order.PointOrder = PointOrder;
+                mo.MergePoints = MergePoints;
+                var ain = new DsaMeshAttrInput[items.Count];
+                for (int i = 0; i < items.Count; ++i) { ain[i].Mesh.Mesh = inputs[i]; Extras(items[i], null, (uint)items[i].PointsCount, ref ain[i], pins); }
+                fixed (DsaMeshAttrInput* p = ain)
+                    NativeMethods.Check(NativeMethods.dsa_encode_merged_sequential_batch(_ctx, (uint)items.Count, p, null, in mo, out encoded), _ctx, "dsa_encode_merged_sequential_batch");
+                var merged = Streams(encoded, items.Count);
+                _rowEntries = new uint[items.Count][];
+                for (uint i = 0; i < items.Count; ++i)
+                {
+                    NativeMethods.Check(NativeMethods.dsa_encoded_row_entries(encoded, i, null, 0, out uint rows), _ctx, $"mesh {i}");
+                    _rowEntries[i] = new uint[rows];
+                    fixed (uint* r = _rowEntries[i])
+                        NativeMethods.Check(NativeMethods.dsa_encoded_row_entries(encoded, i, r, (nuint)rows, out rows), _ctx, $"mesh {i}");
+                }
+                return merged;
+            }
             if (PointOrder != 0)
             {
                 NativeMethods.dsa_encode_default_order_options(out var oo);
@@ -217,6 +248,7 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
             for (int i = 0; i < meshes.Count; ++i) items[i] = meshes[i];
             return EncodeSequential(items, config, 1);
         }
+        if (MergePoints != 0) throw new ArgumentException("MergePoints takes point clouds: merging the points of a mesh would collapse its faces and lose its seams");
         if (PointOrder != 0) throw new ArgumentException("PointOrder needs a sequential stream (EncodingMethod SequentialEncoding, or point clouds): Edgebreaker orders its own entries");
         NativeMethods.dsa_encode_default_options(out var opt);
         // per-attribute-type options are keyed by (int)GeometryAttributeType (Config.cs:55-62)
@@ -460,6 +492,7 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
             NativeMethods.Check(NativeMethods.dsa_encoded_stream(encoded, i, out var bytes, out var length), _ctx, $"mesh {i}");
             result[i] = new ReadOnlySpan<byte>(bytes, (int)length).ToArray();
         }
+        _rowEntries = null;
         if (TrackRows || PointOrder != 0) _entryRows = Rows(encoded, count);      // (a sequential handle answers with the identity, or with the point order)
         return result;
     }

@@ -239,6 +239,15 @@ internal unsafe struct DsaEncodeOrderOptions
     public fixed int Reserved[7];   // zero
 }
 
+// dsa_encode_merge_options (dsa_encode_merged_sequential_batch)
+[StructLayout(LayoutKind.Sequential)]
+internal unsafe struct DsaEncodeMergeOptions
+{
+    public DsaEncodeOrderOptions Order;
+    public int MergePoints;         // 0: every point is coded; 1: one point per occupied cell of the position grid (point clouds, PointOrder 1)
+    public fixed int Reserved[7];   // zero
+}
+
 [StructLayout(LayoutKind.Sequential)]
 internal unsafe struct DsaMeshInput
 {
@@ -367,6 +376,9 @@ internal static unsafe partial class NativeMethods
     [DllImport(Lib)] internal static extern void dsa_encode_default_rows_options(out DsaEncodeRowsOptions options);
     [DllImport(Lib)] internal static extern void dsa_encode_default_order_options(out DsaEncodeOrderOptions options);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_ordered_sequential_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, in DsaEncodeOrderOptions options, out IntPtr encoded);
+    [DllImport(Lib)] internal static extern void dsa_encode_default_merge_options(out DsaEncodeMergeOptions options);
+    [DllImport(Lib)] internal static extern DsaStatus dsa_encode_merged_sequential_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, in DsaEncodeMergeOptions options, out IntPtr encoded);
+    [DllImport(Lib)] internal static extern DsaStatus dsa_encoded_row_entries(IntPtr encoded, uint mesh, uint* dst, nuint capacity, out uint count);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_rows_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, DsaMeshAttributeCorners* corners, in DsaEncodeRowsOptions options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encoded_entry_rows(IntPtr encoded, uint mesh, uint attribute, uint* dst, nuint capacity, out uint count);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encoded_attributes(IntPtr encoded, uint mesh, out uint count);

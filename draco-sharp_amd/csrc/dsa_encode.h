@@ -25,6 +25,8 @@
 //   GPU   (dsa_encode_rows.h)  k_enc_entry_rows  dsa_encode_rows_batch, track_rows = 1: the row of the caller's arrays every entry carries
 //   GPU   (dsa_encode_order.h) k_enc_order_*     dsa_encode_ordered_sequential_batch, point_order = 1: Morton keys and a segmented radix sort
 //                                                over all clouds of a chunk, between k_enc_quantize and k_enc_gather
+//                              k_enc_merge_*     dsa_encode_merged_sequential_batch, merge_points = 1: one point per cell of the position grid,
+//                                                the heads of the runs of equal keys behind the sort; nv of the cloud's streams falls on the device
 //         (dsa_encode_layout.h) the request of an entry point, the state of a chunk, the per-mesh checks and plans, the arena layout
 // Every entry point fills an EncRequest and calls encode_request; a chunk of it goes through the stages of encode_chunk (or of
 // encode_sequential_chunk, dsa_encode_sequential.h) on a lane.
@@ -657,9 +659,10 @@ static dsa_status enc_code_streams(dsa_context *ctx, EncLane &lane, EncChunk &ck
   // coded bytes of every stream (and, when k_enc_plan made them, the probability tables: the stream carries them)
   // and the side bits of TexCoordsPortable / GeometricNormal, packed
   // (track_rows: a fifth piece per stream, its entry rows -- k_enc_entry_rows has run behind the attribute kernels)
-  // (point_order: the fifth piece of a mesh's first stream is the permutation its streams share -- dsa_encode_order.h)
-  const bool track = !ck.L.rows_of_stream.empty(), ordered = !ck.L.ord.empty();
-  const size_t per = track || ordered ? 5 : 4;
+  // (point_order: the fifth piece of a mesh's first stream is the permutation its streams share -- dsa_encode_order.h; with
+  // merge_points the kept rows, nv of them as the records say, and a sixth piece, row_entries of all its input rows)
+  const bool track = !ck.L.rows_of_stream.empty(), ordered = !ck.L.ord.empty(), merge = ck.L.merge;
+  const size_t per = merge ? 6 : (track || ordered ? 5 : 4);
   std::vector<dsa::PackItem> items;
   for (uint32_t s = 0; s < ns; ++s) {
     if (hs[s].overflow || E->status[stream_mesh[s]] != DSA_OK) continue;
@@ -675,6 +678,7 @@ static dsa_status enc_code_streams(dsa_context *ctx, EncLane &lane, EncChunk &ck
     } else if (ordered) {
       const bool first = s == ck.L.first_stream[stream_mesh[s]];
       items.push_back({hs[s].e2v, 0, first ? 4u * hs[s].nv : 0u, s});
+      if (merge) { const dsa::EncOrder &O = ck.L.ord[ck.L.ord_of_mesh[stream_mesh[s]]]; items.push_back({O.cells, 0, first ? 4u * O.n : 0u, s}); }
     }
   }
   const uint8_t *host = nullptr;
@@ -682,7 +686,8 @@ static dsa_status enc_code_streams(dsa_context *ctx, EncLane &lane, EncChunk &ck
   hostutil::parallel_for((uint32_t)(items.size() / per), [&](uint32_t m) {
     const size_t k = per * (size_t)m;
     const uint32_t s = items[k].pad;
-    if (per == 5 && items[k + 4].len) { const uint32_t *r = (const uint32_t *)(host + items[k + 4].packed_off); ck.entry_rows[s].assign(r, r + items[k + 4].len / 4u); }
+    if (per == 6 && items[k + 5].len) { const uint32_t *r = (const uint32_t *)(host + items[k + 5].packed_off); ck.row_cells[s].assign(r, r + items[k + 5].len / 4u); }
+    if (per >= 5 && items[k + 4].len) { const uint32_t *r = (const uint32_t *)(host + items[k + 4].packed_off); ck.entry_rows[s].assign(r, r + items[k + 4].len / 4u); }
     if (items[k].len) rans[s].assign(host + items[k].packed_off, host + items[k].packed_off + items[k].len);
     if (items[k + 1].len) bits[s].assign(host + items[k + 1].packed_off, host + items[k + 1].packed_off + items[k + 1].len);
     if (hs[s].flags && !(hs[s].kind != 1 && hs[s].prediction == 4)) {
@@ -1152,7 +1157,8 @@ static dsa_status enc_stage_attributes(dsa_context *ctx, EncLane &lane, EncChunk
   }
   if (!L.ord.empty()) {      // point_order: the permutation of every cloud behind the quantisers, in front of the gather (dsa_encode_order.h)
     // DSA_ENC_TIMING (read per chunk: tools/encode_order_timing.py times one leg of a process): the stream is drained around the
-    // order kernels and behind the stage, and the three laps say what share of the chunk's device time the order takes
+    // order kernels and behind the stage, and the three laps say what share of the chunk's device time the order takes (with
+    // merge_points a fourth around the merge kernels: tools/encode_merge_timing.py)
     order_timing = getenv("DSA_ENC_TIMING") != nullptr;
     if (order_timing) { ENC_TRY(hipStreamSynchronize(st)); order_lap("uploads + quantisers"); }
     const uint32_t gf = L.max_count ? std::max(1u, std::min(64u, (L.max_count + 1023u) / 1024u)) : 0u;
@@ -1161,6 +1167,13 @@ static dsa_status enc_stage_attributes(dsa_context *ctx, EncLane &lane, EncChunk
                           L.ord_passes, ck.rq.seq.geometry == 1, gf);
     ENC_TRY(hipGetLastError());
     if (order_timing) { ENC_TRY(hipStreamSynchronize(st)); order_lap("point order"); }
+    if (L.merge) {             // merge_points: one point per cell, behind the sort; nv of the cloud's streams falls to the cells it has
+      dsa::enc_merge_launch([st](auto kernel, uint32_t grid_x, uint32_t grid_y, uint32_t block, auto... args) { hipLaunchKernelGGL(kernel, dim3(grid_x, grid_y), dim3(block), 0, st, args...); },
+                            arena, (dsa::EncOrder *)(arena + L.ord_at), (uint32_t)L.ord.size(), (const dsa::EncOrderTile *)(arena + L.ord_tiles_at), (uint32_t)L.ord_tiles.size(),
+                            L.ord_passes, d_streams, ns);
+      ENC_TRY(hipGetLastError());
+      if (order_timing) { ENC_TRY(hipStreamSynchronize(st)); order_lap("point merge"); }
+    }
   }
   hipLaunchKernelGGL(dsa::k_enc_gather, dim3(ns), dim3(256), 0, st, arena, d_streams, ns);
   hipLaunchKernelGGL(dsa::k_enc_corr, dim3(gx, ns), dim3(256), 0, st, arena, d_streams, ns);
@@ -1285,6 +1298,7 @@ static dsa_status enc_stage_code(dsa_context *ctx, EncLane &lane, EncChunk &ck, 
   if (lap) (*lap)("histograms + symbol plans");
   ck.rans.resize(ns); ck.bits.resize(ns); ck.flag_bits.resize(ns); ck.crease.resize(ck.L.any_crease ? 4 * (size_t)ns : 0);
   if (!ck.L.rows_of_stream.empty() || !ck.L.ord.empty()) ck.entry_rows.resize(ns);
+  if (ck.L.merge) ck.row_cells.resize(ns);
   return ns ? enc_code_streams(ctx, lane, ck) : DSA_OK;
 }
 // host phase 3: the stream layout (threads over meshes; write_stream may throw like any part of the host coder)
@@ -1431,6 +1445,14 @@ static dsa_status enc_check_options(dsa_context *ctx, const dsa_encode_order_opt
   ENC_RESERVED(o, 7, "dsa_encode_order_options");
   return enc_check_options(ctx, o.sequential, null_argument);
 }
+// ... with one point per cell of the position grid (dsa_encode_order.h)
+static dsa_status enc_check_options(dsa_context *ctx, const dsa_encode_merge_options &o, bool null_argument) {
+  if (o.merge_points != 0 && o.merge_points != 1) ENC_REFUSE("merge_points %d: 0 (every point is coded) or 1 (one point per occupied cell of the position grid)", (int)o.merge_points);
+  if (o.merge_points == 1 && o.order.point_order != 1) ENC_REFUSE("merge_points 1 needs point_order 1 (it was %d): the points of a cell are found side by side in the Morton order", (int)o.order.point_order);
+  if (o.merge_points == 1 && o.order.sequential.geometry != 0) ENC_REFUSE("merge_points 1 needs geometry 0 (it was %d): merging the points of a mesh would collapse its faces and lose its seams", (int)o.order.sequential.geometry);
+  ENC_RESERVED(o, 7, "dsa_encode_merge_options");
+  return enc_check_options(ctx, o.order, null_argument);
+}
 #undef ENC_RESERVED
 #undef ENC_REFUSE
 
@@ -1462,7 +1484,7 @@ static dsa_status enc_ensure_lanes(dsa_context *ctx, uint32_t lanes) {
 // streams wait for each other: four lanes, their walk streams at another priority.  Small batches are one chunk.
 // `code_chunk(sink, lane, base, count, &part)`: codes meshes base .. base + count of the batch on the lane.
 template <class ChunkFn>
-static dsa_status encode_batch_chunks(dsa_context *ctx, uint32_t n, ChunkFn &&code_chunk, dsa_encoded **out, int rows_kind = dsa_encoded::ROWS_NONE) {
+static dsa_status encode_batch_chunks(dsa_context *ctx, uint32_t n, ChunkFn &&code_chunk, dsa_encoded **out, int rows_kind = dsa_encoded::ROWS_NONE, bool merged = false) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const uint32_t max_lanes = [&]() { const char *e = getenv("DSA_ENC_LANES"); const int v = e ? atoi(e) : 0; return (uint32_t)(v >= 1 && v <= 16 ? v : 4); }();
   const uint32_t chunk_max = [&]() { const char *e = getenv("DSA_ENC_CHUNK"); const int v = e ? atoi(e) : 0; return (uint32_t)(v >= 1 ? v : 0); }();
@@ -1482,6 +1504,7 @@ static dsa_status encode_batch_chunks(dsa_context *ctx, uint32_t n, ChunkFn &&co
   E->ctx = ctx;
   E->streams.resize(n); E->status.assign(n, DSA_OK); E->messages.resize(n);
   E->keep_rows(rows_kind, n);
+  if (merged) E->keep_cells(n);
   std::atomic<uint32_t> next{0};
   std::atomic<int> failed{DSA_OK};
   std::vector<std::string> errs(lanes);
@@ -1621,7 +1644,7 @@ static dsa_status encode_request(dsa_context *ctx, const EncRequest &rq, dsa_enc
   return encode_batch_chunks(ctx, rq.n, [&](dsa_context *sink, EncLane &lane, uint32_t base, uint32_t cnt, dsa_encoded **part) {
     if (rq.weld_sink) return weld_chunk(sink, lane, rq, base, cnt, batch_n, part);
     return rq.sequential ? encode_sequential_chunk(sink, lane, rq, base, cnt, rq.n, part) : encode_chunk(sink, lane, rq, base, cnt, batch_n, part);
-  }, out, rq.rows_kind());
+  }, out, rq.rows_kind(), rq.merged());
 }
 // dsa_encode_repair_batch, topology = 1: the batch as dsa_encode_level_batch codes it; then the meshes refused for their topology
 // once more as a request of their own, on the repaired corner table (EncRequest::repair), their results into the first's places.
@@ -1696,12 +1719,19 @@ static dsa_status encode_edgebreaker(dsa_context *ctx, uint32_t n, const dsa_mes
   rq.track_rows = w.track_rows == 1;
   return encode_checked(ctx, rq, grids, o.grid.repair.topology == 1, out);
 }
-static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_order_options &o, dsa_encoded **out) {
-  if (enc_check_options(ctx, o, !ctx || !out || (n && !meshes)) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_merge_options &m, dsa_encoded **out) {
+  if (enc_check_options(ctx, m, !ctx || !out || (n && !meshes)) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+  const dsa_encode_order_options &o = m.order;
   EncRequest rq;
   rq.n = n; rq.meshes = meshes; rq.sequential = true;
-  rq.seq = o.sequential; rq.point_order = o.point_order == 1;
+  rq.seq = o.sequential; rq.point_order = o.point_order == 1; rq.merge_points = m.merge_points == 1;
   return encode_checked(ctx, rq, grids, false, out);
+}
+static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_order_options &o, dsa_encoded **out) {
+  dsa_encode_merge_options m;
+  dsa_encode_default_merge_options(&m);
+  m.order = o;
+  return encode_sequential(ctx, n, meshes, grids, m, out);
 }
 static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_sequential_options *options, dsa_encoded **out) {
   dsa_encode_order_options o;
@@ -1747,6 +1777,11 @@ void dsa_encode_default_order_options(dsa_encode_order_options *o) {
   if (!o) return;
   memset(o, 0, sizeof(*o));
   dsa_encode_sequential_default_options(&o->sequential);
+}
+void dsa_encode_default_merge_options(dsa_encode_merge_options *o) {
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  dsa_encode_default_order_options(&o->order);
 }
 void dsa_encode_default_repair_options(dsa_encode_repair_options *o) {
   if (!o) return;
@@ -1858,6 +1893,11 @@ dsa_status dsa_encode_grid_sequential_batch(dsa_context *ctx, uint32_t n, const 
 dsa_status dsa_encode_ordered_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_order_options *options, dsa_encoded **out) {
   DSA_GUARD(ctx, [&] { dsa_encode_order_options o; dsa_encode_default_order_options(&o); if (options) o = *options; return encode_sequential(ctx, n, meshes, grids, o, out); }());
 }
+// ... and of point clouds one point per occupied cell of the position grid (merge_points = 1: the heads of the runs of equal keys
+// behind the sort, compacted on the device -- dsa_encode_order.h); merge_points = 0 is the very request of the call above.
+dsa_status dsa_encode_merged_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_merge_options *options, dsa_encoded **out) {
+  DSA_GUARD(ctx, [&] { dsa_encode_merge_options o; dsa_encode_default_merge_options(&o); if (options) o = *options; return encode_sequential(ctx, n, meshes, grids, o, out); }());
+}
 
 struct dsa_welded {
   dsa_context *ctx = nullptr;
@@ -1922,6 +1962,19 @@ dsa_status dsa_encoded_attributes(const dsa_encoded *e, uint32_t mesh, uint32_t 
   if (e->status[mesh] != DSA_OK) return set_err(e->ctx, (dsa_status)e->status[mesh], "mesh %u: %s", mesh, e->messages[mesh].c_str());
   if (e->rows_kind == dsa_encoded::ROWS_NONE) return set_err(e->ctx, DSA_ERR_INVALID_ARGUMENT, "the entry rows of this handle were not kept: encode with dsa_encode_rows_batch and track_rows = 1");
   *count = e->row_attributes(mesh);
+  return DSA_OK;
+}
+// The entry of the cell of every input row of stream `mesh` (merge_points = 1): row_entries[r] = j with key(kept[j]) = key(r).
+dsa_status dsa_encoded_row_entries(const dsa_encoded *e, uint32_t mesh, uint32_t *dst, size_t capacity, uint32_t *count) {
+  if (!e || mesh >= e->streams.size() || !count) return DSA_ERR_INVALID_ARGUMENT;
+  *count = 0;
+  if (e->status[mesh] != DSA_OK) return set_err(e->ctx, (dsa_status)e->status[mesh], "mesh %u: %s", mesh, e->messages[mesh].c_str());
+  if (!e->merged) return set_err(e->ctx, DSA_ERR_INVALID_ARGUMENT, "the row entries of this handle were not kept: encode with dsa_encode_merged_sequential_batch and merge_points = 1");
+  const std::vector<uint32_t> &cells = e->cells[mesh];
+  *count = (uint32_t)cells.size();
+  if (!dst) return DSA_OK;
+  if (capacity < cells.size()) return set_err(e->ctx, DSA_ERR_INVALID_ARGUMENT, "mesh %u: %u row entries, room for %llu", mesh, (uint32_t)cells.size(), (unsigned long long)capacity);
+  if (!cells.empty()) memcpy(dst, cells.data(), 4ull * cells.size());
   return DSA_OK;
 }
 // The entry rows of attribute `attribute` of stream `mesh`: a sequential handle answers with the identity (with point_order = 1:

@@ -2071,6 +2071,27 @@ static void point_order(const float *pos, uint32_t n, int bits, const Grid *grid
   for (uint32_t r = 0; r < n; ++r) perm[r] = r;
   std::stable_sort(perm.begin(), perm.end(), [&](uint32_t x, uint32_t y) { return key[x] < key[y]; });
 }
+// One point per occupied cell of the position grid (dsa_encode_merged_sequential_batch, merge_points = 1; the device's kernels are
+// k_enc_merge_* of dsa_encode_order.h): with key and perm as above, entry e of the sorted order is a head iff e == 0 or
+// key[perm[e]] != key[perm[e - 1]]; kept lists perm[e] over the heads in sorted order (the sort is stable: the smallest row of
+// every cell), row_entries[r] is the index in kept of the cell of row r.
+static void merge_points(const float *pos, uint32_t n, int bits, const Grid *grid, std::vector<uint32_t> &kept, std::vector<uint32_t> &row_entries) {
+  check(bits >= 1 && bits <= 20, "quantisation bits out of range (positions/texcoords 1..20, normals 2..20)");
+  check(pos != nullptr && n > 0, "positions are missing");
+  PortableAttr a;
+  a.att_type = 0; a.nc = a.nc_out = 3; a.seq_type = 2; a.grid = grid;
+  quantize(pos, n, 3, bits, a);
+  std::vector<uint64_t> key(n);
+  for (uint32_t r = 0; r < n; ++r) key[r] = point_order_key(a.vals.data() + (size_t)3 * r, bits);
+  std::vector<uint32_t> perm(n);
+  for (uint32_t r = 0; r < n; ++r) perm[r] = r;
+  std::stable_sort(perm.begin(), perm.end(), [&](uint32_t x, uint32_t y) { return key[x] < key[y]; });
+  kept.clear(); row_entries.assign(n, 0);
+  for (uint32_t e = 0; e < n; ++e) {
+    if (e == 0 || key[perm[e]] != key[perm[e - 1]]) kept.push_back(perm[e]);
+    row_entries[perm[e]] = (uint32_t)kept.size() - 1u;
+  }
+}
 
 // Point cloud, sequential (BASELINE config 1), positions only: int32 num_points, one attributes decoder, positions quantised,
 // Difference + Wrap in linear order, always through the symbol coder.

@@ -114,13 +114,16 @@ struct dsa_encoded {
   // entry rows (dsa_encoded_entry_rows).  ROWS_TRACKED: rows[mesh][attribute of the stream], kept by a call with track_rows = 1
   // (dsa_encode_rows.h); ROWS_LINEAR: a sequential call, entry i is row i, and linear[mesh] = (attributes, points) is all it takes;
   // ROWS_ORDERED: a sequential call with point_order = 1 (dsa_encode_order.h): linear[mesh] as before, and order[mesh] the
-  // permutation every attribute of the stream went through, kept once
+  // permutation every attribute of the stream went through, kept once -- with merge_points = 1 the kept rows, linear[mesh].second
+  // of them, and cells[mesh] the entry of the cell of every input row (dsa_encoded_row_entries); `merged` says which
   enum { ROWS_NONE = 0, ROWS_TRACKED = 1, ROWS_LINEAR = 2, ROWS_ORDERED = 3 };
   int rows_kind = ROWS_NONE;
   std::vector<std::vector<std::vector<uint32_t>>> rows;
   std::vector<std::pair<uint32_t, uint32_t>> linear;
-  std::vector<std::vector<uint32_t>> order;
+  std::vector<std::vector<uint32_t>> order, cells;
+  bool merged = false;
   void keep_rows(int kind, size_t n) { rows_kind = kind; if (kind == ROWS_TRACKED) rows.resize(n); if (kind == ROWS_LINEAR || kind == ROWS_ORDERED) linear.resize(n); if (kind == ROWS_ORDERED) order.resize(n); }
+  void keep_cells(size_t n) { merged = true; cells.resize(n); }
   // attributes of stream `mesh` with entry rows; entries of attribute a; their rows (null: entry e is row e)
   uint32_t row_attributes(size_t mesh) const { return rows_kind == ROWS_TRACKED ? (uint32_t)rows[mesh].size() : linear[mesh].first; }
   uint32_t row_entries(size_t mesh, uint32_t a) const { return rows_kind == ROWS_TRACKED ? (uint32_t)rows[mesh][a].size() : linear[mesh].second; }
@@ -131,6 +134,7 @@ struct dsa_encoded {
     if (rows_kind == ROWS_TRACKED && from < part.rows.size()) rows[to].swap(part.rows[from]);
     if ((rows_kind == ROWS_LINEAR || rows_kind == ROWS_ORDERED) && from < part.linear.size()) linear[to] = part.linear[from];
     if (rows_kind == ROWS_ORDERED && from < part.order.size()) order[to].swap(part.order[from]);
+    if (merged && from < part.cells.size()) cells[to].swap(part.cells[from]);
   }
 };
 
@@ -173,6 +177,8 @@ struct EncRequest {
   bool weld_attributes = false;            // ... weld_attributes = 1: the listed attributes are key sets of their own in the weld (dsa_encode_weld.h: 3 + L key sets)
   bool track_rows = false;                 // dsa_encode_rows_batch, track_rows = 1: the handle keeps the entry rows of every stream (dsa_encode_rows.h)
   bool point_order = false;                // dsa_encode_ordered_sequential_batch, point_order = 1: the points of every stream in Morton order (dsa_encode_order.h)
+  bool merge_points = false;               // dsa_encode_merged_sequential_batch, merge_points = 1 (with point_order, point clouds): one point per cell of the position grid
+  bool merged() const { return sequential && point_order && merge_points && !weld_sink; }
   int rows_kind() const { return weld_sink ? dsa_encoded::ROWS_NONE : (sequential ? (point_order ? dsa_encoded::ROWS_ORDERED : dsa_encoded::ROWS_LINEAR) : (track_rows ? dsa_encoded::ROWS_TRACKED : dsa_encoded::ROWS_NONE)); }
   dsa_encode_level_options level{};        // Edgebreaker streams
   dsa_encode_sequential_options seq{};     // sequential streams
@@ -234,6 +240,8 @@ struct EncLayout {
   std::vector<dsa::EncOrderTile> ord_tiles;
   uint64_t ord_at = 0, ord_tiles_at = 0;
   uint32_t ord_passes = 0;
+  bool merge = false;                       // EncRequest::merge_points: the records say so, the streams read kept in place of perm
+  std::vector<uint32_t> ord_of_mesh;        // ... the record of mesh i of the chunk (DSA_INVALID: it has none)
 };
 
 static inline bool enc_multi_scheme(const synth::PortableAttr &a) { return a.seq_type != 3 && (a.prediction == 2 || a.prediction == 4); }
@@ -283,11 +291,13 @@ struct EncChunk {
   std::vector<synth::SymbolPlan> splans;
   std::vector<std::vector<uint8_t>> rans, bits, flag_bits, crease;      // per stream; crease[4 s + j]: list j of stream s
   std::vector<std::vector<uint32_t>> entry_rows;                        // per stream (EncRequest::track_rows)
+  std::vector<std::vector<uint32_t>> row_cells;                         // per stream, a cloud's first alone (EncRequest::merge_points): row_entries
 
   EncChunk(const EncRequest &r, uint32_t b, uint32_t cnt, uint32_t bn) : rq(r), base(b), n(cnt), batch_n(bn), opt(enc_synth_options(r)), E(new (std::nothrow) dsa_encoded()), ins(cnt), plans(cnt), extras(cnt), extra_cap(cnt) {
     if (!E) return;                        // (the chunk function answers)
     E->streams.resize(n); E->status.assign(n, DSA_OK); E->messages.resize(n);
     E->keep_rows(r.rows_kind(), n);
+    if (r.merged()) E->keep_cells(n);
   }
   const dsa_mesh_attr_input &attr(uint32_t i) const { return welded.empty() ? rq.attr(base + i) : welded[i]; }
   const dsa_mesh_corner_input &corner(uint32_t i) const { return attr(i).mesh; }
@@ -793,9 +803,14 @@ static void enc_layout(EncChunk &ck) {
 // EncRequest::point_order: no stream is linear -- every value stream of a cloud reads its entries through one shared entry -> row
 // map, the permutation the sort kernels of dsa_encode_order.h leave (their records and tile list among the uploads, their
 // regions among what the kernels write).  Without it nothing here moves.
+// EncRequest::merge_points: the map is the other row buffer, where k_enc_merge_compact leaves the kept rows, and a region of 4
+// bytes per point takes row_entries; every region stays sized for the points that came in, k_enc_merge_scan lowers nv below them.
 static void enc_layout_sequential(EncChunk &ck) {
   EncLayout &L = ck.L;
   const bool is_mesh = ck.rq.seq.geometry == 1, compressed = is_mesh && ck.rq.seq.compress_connectivity == 1, ordered = ck.rq.point_order;
+  const bool merge = ordered && !is_mesh && ck.rq.merge_points;
+  L.merge = merge;
+  if (merge) L.ord_of_mesh.assign(ck.n, DSA_INVALID);
   EncArena A;
   A.log = ck.region_log;
   enc_layout_begin(ck, 0, compressed ? 1 : 0);
@@ -813,6 +828,7 @@ static void enc_layout_sequential(EncChunk &ck) {
       dsa::EncOrder O;
       memset(&O, 0, sizeof(O));
       O.n = V; O.tiles = (V + ORD_TILE - 1u) / ORD_TILE; O.bits = (uint32_t)ck.opt.pos_bits;
+      if (merge) { O.merge = 1; O.stream0 = s0; O.streams = (uint32_t)atts.size(); L.ord_of_mesh[i] = (uint32_t)L.ord.size(); }
       for (uint32_t t = 0; t < O.tiles; ++t) L.ord_tiles.push_back({(uint32_t)L.ord.size(), t});
       L.ord.push_back(O);
     }
@@ -840,7 +856,8 @@ static void enc_layout_sequential(EncChunk &ck) {
       for (int b = 0; b < 2; ++b) { O.key[b] = A.take(8ull * V); O.row[b] = A.take(4ull * V); }
       O.hist = A.take(4ull * ORD_RADIX * O.tiles);
       if (is_mesh) O.rank = A.take(4ull * V);
-      for (uint32_t k = 0; k < na; ++k) L.streams[s0 + k].e2v = O.row[L.ord_passes & 1u];
+      if (merge) O.cells = A.take(4ull * V);
+      for (uint32_t k = 0; k < na; ++k) L.streams[s0 + k].e2v = O.row[(L.ord_passes + (merge ? 1u : 0u)) & 1u];
     }
     for (uint32_t k = 0; k < na; ++k) enc_value_stream_regions(L.streams[s0 + k], V, ck.hist_cap_of(i, k), A);
     if (ordered) L.ord[o - 1].vals = L.streams[s0].vals;      // (the positions are attribute 0: their stream is the mesh's first)

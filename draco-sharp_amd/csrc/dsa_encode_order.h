@@ -37,6 +37,26 @@
 // does the tile's or the cloud's work in entry order, as k_enc_weld_scan has) -- records, tile list, regions, pass structure, keys,
 // rank and remap are the product's as they run; the ballots and shuffles themselves are held to the host coder by
 // tests/test_gpu_encode_order.py alone.
+//
+// dsa_encode_merged_sequential_batch with merge_points = 1 (point clouds): one point per occupied cell of the position grid.  The
+// cell of a point is its key, and behind the sort the points of a cell are adjacent: entry e of the sorted order is a head iff
+// e == 0 or key[perm[e]] != key[perm[e - 1]]; kept lists perm[e] over the heads in sorted order, m of them (the sort is stable:
+// kept[j] is the smallest row of its cell), and row_entries[r] is the j whose cell row r lies in.  Three steps behind the last
+// scatter pass and in front of k_enc_gather, on the same (cloud, tile) list:
+//   k_enc_merge_heads     a wave per tile: head flags from the sorted keys (entry e0 of a tile reads key[e0 - 1] of the tile in
+//                         front: the sorted buffers are only read from here on), a ballot and a popcount per 64 entries, the
+//                         tile's head count to hist[tile] (the histograms are done with)
+//   k_enc_merge_scan      a wave per cloud: exclusive scan of the tile counts (the shuffle scan of k_enc_order_scan), m into the
+//                         cloud's record and into nv of every stream of the cloud in the device's EncStream records -- what
+//                         k_enc_gather and everything behind it read, and what the host reads when the records come back
+//   k_enc_merge_compact   a wave per tile: kept[tile base + heads below me] = row[e] for heads, row_entries[row[e]] = the head at or
+//                         before e for every entry; lane offsets from the ballots, a running count over the tile's 16 steps.  Not
+//                         in place (tile t writes at or below t * ORD_TILE, into the range an earlier tile may not have read yet):
+//                         kept goes to the other row buffer, row[(passes + 1) & 1], which the layout makes the streams' e2v.
+// No atomic decides a place: kept and row_entries are functions of the input alone.  The host coder's twin is synth::merge_points;
+// tests/hostcheck/encmerge_host.cpp runs the serial forms against it, tests/test_gpu_encode_merge.py the ballots and shuffles.
+// gfx950, hipcc -O3 (VGPR / SGPR / LDS bytes per block): k_enc_merge_heads 12 / 24 / 0, scan 16 / 29 / 0, compact 16 / 27 / 0; no
+// scratch, no spills, 8 waves per SIMD.
 #pragma once
 #include <stdint.h>
 
@@ -50,12 +70,16 @@ struct EncOrder {                  // one per cloud of the chunk; in the arena, 
   uint64_t vals;                   // i32[3 n]: the position stream's integers, row order
   uint64_t key[2];                 // u64[n] each: pass p reads [p & 1], writes [(p + 1) & 1]
   uint64_t row[2];                 // u32[n] each, likewise; row[passes & 1] is the e2v of the cloud's streams: OUTPUT perm
+                                   //   (merge: row[(passes + 1) & 1] is, OUTPUT kept[m])
   uint64_t hist;                   // u32[ORD_RADIX * tiles]: of the pass under way, digit-major
   uint64_t rank;                   // u32[n] OUTPUT (meshes; else 0): the entry of every row
   uint64_t faces;                  // compressed indices: u16[count] (narrow) or u32[count], remapped in place; else count 0
   uint32_t n, tiles;               // points; (n + ORD_TILE - 1) / ORD_TILE
   uint32_t bits, count;            // position_bits; 3F corners to remap
-  uint32_t narrow, pad;
+  uint32_t narrow, merge;          // merge: merge_points = 1, the three fields below are set
+  uint64_t cells;                  // u32[n] OUTPUT (merge; else 0): row_entries, the entry of the cell of every row
+  uint32_t stream0, streams;       // the cloud's value streams among the chunk's EncStream records: k_enc_merge_scan lowers their nv
+  uint32_t m, pad;                 // OUTPUT (merge): occupied cells
 };
 struct EncOrderTile { uint32_t cloud, tile; };
 
@@ -217,6 +241,105 @@ static inline void enc_order_launch(Launch &&launch, uint8_t *arena, const EncOr
   }
   if (any_rank) launch(k_enc_order_rank, nt, 1u, 256u, arena, clouds, tiles, nt, passes);
   if (any_rank && gx_faces) launch(k_enc_order_faces, gx_faces, nc, 256u, arena, clouds, nc);
+}
+
+// ---- merge_points (the header comment has the contract)
+__global__ __launch_bounds__(WAVE) void k_enc_merge_heads(uint8_t *arena, const EncOrder *clouds, const EncOrderTile *tiles, uint32_t nt, uint32_t passes) {
+  if (blockIdx.x >= nt) return;
+  const EncOrderTile T = tiles[blockIdx.x];
+  const EncOrder &O = clouds[T.cloud];
+  if (!O.merge) return;
+  const uint64_t *key = (const uint64_t *)(arena + O.key[passes & 1u]);
+  uint32_t *counts = (uint32_t *)(arena + O.hist);
+  const uint32_t lane = threadIdx.x, e0 = T.tile * ORD_TILE, end = O.n - e0 < ORD_TILE ? O.n : e0 + ORD_TILE;
+  uint32_t heads = 0;
+#if defined(__HIPCC__)
+  for (uint32_t s0 = e0; s0 < end; s0 += WAVE) {               // (uniform: every lane takes every step)
+    const uint32_t e = s0 + lane;
+    const bool valid = e < end;
+    const bool head = valid && (e == 0u || key[e] != key[e - 1u]);
+    heads += (uint32_t)__popcll(__ballot(head));
+  }
+  if (lane == 0) counts[T.tile] = heads;
+#else       // (as k_enc_order_hist: lane 0 counts)
+  if (lane != 0) return;
+  for (uint32_t e = e0; e < end; ++e) heads += e == 0u || key[e] != key[e - 1u] ? 1u : 0u;
+  counts[T.tile] = heads;
+#endif
+}
+
+// one wave per cloud: blockIdx.x = cloud (Stream: dsa_encode_layout.h's EncStream, which is defined behind this file)
+template <class Stream>
+__global__ __launch_bounds__(WAVE) void k_enc_merge_scan(uint8_t *arena, EncOrder *clouds, uint32_t nc, Stream *streams, uint32_t ns) {
+  if (blockIdx.x >= nc) return;
+  EncOrder &O = clouds[blockIdx.x];
+  if (!O.merge) return;
+  uint32_t *counts = (uint32_t *)(arena + O.hist);
+  const uint32_t lane = threadIdx.x;
+  uint32_t base = 0;
+#if defined(__HIPCC__)
+  for (uint32_t t0 = 0; t0 < O.tiles; t0 += WAVE) {
+    const uint32_t t = t0 + lane, x = t < O.tiles ? counts[t] : 0u;
+    uint32_t incl = x;
+    for (int d = 1; d < WAVE; d <<= 1) { const uint32_t y = (uint32_t)__shfl_up((int)incl, d, WAVE); if ((int)lane >= d) incl += y; }
+    if (t < O.tiles) counts[t] = base + incl - x;
+    base += (uint32_t)__shfl((int)incl, WAVE - 1, WAVE);
+  }
+  const uint32_t m = base < O.n ? base : O.n;                  // (m <= n by the counts: the comparison keeps a fault elsewhere inside the streams' regions)
+  if (lane == 0) O.m = m;
+  for (uint32_t k = lane; k < O.streams; k += WAVE) if (O.stream0 + k < ns) streams[O.stream0 + k].nv = m;
+#else       // (as k_enc_order_hist: lane 0 sums)
+  if (lane != 0) return;
+  for (uint32_t t = 0; t < O.tiles; ++t) { const uint32_t x = counts[t]; counts[t] = base; base += x; }
+  const uint32_t m = base < O.n ? base : O.n;
+  O.m = m;
+  for (uint32_t k = 0; k < O.streams; ++k) if (O.stream0 + k < ns) streams[O.stream0 + k].nv = m;
+#endif
+}
+
+__global__ __launch_bounds__(WAVE) void k_enc_merge_compact(uint8_t *arena, const EncOrder *clouds, const EncOrderTile *tiles, uint32_t nt, uint32_t passes) {
+  if (blockIdx.x >= nt) return;
+  const EncOrderTile T = tiles[blockIdx.x];
+  const EncOrder &O = clouds[T.cloud];
+  if (!O.merge) return;
+  const uint64_t *key = (const uint64_t *)(arena + O.key[passes & 1u]);
+  const uint32_t *row = (const uint32_t *)(arena + O.row[passes & 1u]);
+  uint32_t *kept = (uint32_t *)(arena + O.row[(passes + 1u) & 1u]);
+  uint32_t *cells = (uint32_t *)(arena + O.cells);
+  const uint32_t lane = threadIdx.x, e0 = T.tile * ORD_TILE, end = O.n - e0 < ORD_TILE ? O.n : e0 + ORD_TILE;
+  uint32_t next = ((const uint32_t *)(arena + O.hist))[T.tile];       // the heads in front of the tile, then of the step
+#if defined(__HIPCC__)
+  const unsigned long long below = (1ull << lane) - 1ull;
+  for (uint32_t s0 = e0; s0 < end; s0 += WAVE) {               // (uniform: every lane takes every step)
+    const uint32_t e = s0 + lane;
+    const bool valid = e < end;
+    const bool head = valid && (e == 0u || key[e] != key[e - 1u]);
+    const unsigned long long heads = __ballot(head);
+    const uint32_t at = next + (uint32_t)__popcll(heads & below);       // heads in front of this entry
+    const uint32_t r = valid ? row[e] : 0u;
+    if (head && at < O.n) kept[at] = r;
+    // the head at or before e: entry 0 of a cloud is a head, so at + head >= 1 for every valid entry
+    if (valid && r < O.n) cells[r] = at + (head ? 1u : 0u) - 1u;
+    next += (uint32_t)__popcll(heads);
+  }
+#else       // (as k_enc_order_hist: lane 0 places the tile's entries in their order)
+  if (lane != 0) return;
+  for (uint32_t e = e0; e < end; ++e) {
+    const bool head = e == 0u || key[e] != key[e - 1u];
+    if (head) kept[next++] = row[e];
+    cells[row[e]] = next - 1u;
+  }
+#endif
+}
+
+// The merge behind enc_order_launch, on the same lists; `streams` the chunk's ns EncStream records on the device.
+template <class Launch, class Stream>
+static inline void enc_merge_launch(Launch &&launch, uint8_t *arena, EncOrder *clouds, uint32_t nc, const EncOrderTile *tiles, uint32_t nt, uint32_t passes,
+                                    Stream *streams, uint32_t ns) {
+  if (nc == 0 || nt == 0) return;
+  launch(k_enc_merge_heads, nt, 1u, (uint32_t)WAVE, arena, (const EncOrder *)clouds, tiles, nt, passes);
+  launch(k_enc_merge_scan<Stream>, nc, 1u, (uint32_t)WAVE, arena, clouds, nc, streams, ns);
+  launch(k_enc_merge_compact, nt, 1u, (uint32_t)WAVE, arena, (const EncOrder *)clouds, tiles, nt, passes);
 }
 
 }  // namespace dsa

@@ -11,6 +11,8 @@
 //                                Difference + wrap, canonicalised octahedral delta (Attributes/LinearSequencer.cs: entry i = point i)
 //          k_enc_order_*         dsa_encode_ordered_sequential_batch, point_order = 1: the points in Morton order behind the quantisers
 //                                (dsa_encode_order.h) -- k_enc_gather then puts every attribute in it, the faces go through its inverse
+//          k_enc_merge_*         dsa_encode_merged_sequential_batch, merge_points = 1 (point clouds): one point per cell behind the sort;
+//                                nv of the cloud's streams falls on the device, the host reads it from the records that come back
 //          k_enc_seq_indices     compressed indices: symbols and their statistics (dsa_encode_seqidx.h)
 //          k_enc_plan / k_enc_rans   every stream, the index stream as a list whose symbols are given (kind 3)
 //   host   stream layout (synth::write_sequential_stream)
@@ -39,9 +41,14 @@ static void enc_stage_sequential_streams(EncChunk &ck) {
       ranked.resize((size_t)m.num_faces * 3);
       for (size_t k = 0; k < ranked.size(); ++k) ranked[k] = rank[m.faces[k]];
     }
+    // merge_points: the stream codes the cells the device found (k_enc_merge_scan lowered nv of every stream of the cloud alike)
+    const bool merge = L.merge;
+    const uint32_t points = merge ? L.streams[s0].nv : m.num_vertices;
+    if (merge && (ck.entry_rows[s0].size() != points || ck.row_cells[s0].size() != m.num_vertices || points == 0 || points > m.num_vertices))
+      return ck.refuse(i, DSA_ERR_DEVICE, "the merged points did not come back");
     synth::ByteWriter w;
     try {
-      synth::write_sequential_stream(w, is_mesh, m.num_vertices, is_mesh ? m.num_faces : 0, compressed, atts,
+      synth::write_sequential_stream(w, is_mesh, points, is_mesh ? m.num_faces : 0, compressed, atts,
         [&](synth::ByteWriter &bw) {               // (raw indices never travel: narrowed from the caller's array into the stream)
           if (compressed) enc_put_coded(bw, ck.splans[si], ck.rans[si], ck.bits[si], L.streams[si].method);
           else synth::write_raw_indices(bw, ordered ? ranked.data() : m.faces, (size_t)m.num_faces * 3, m.num_vertices);
@@ -51,6 +58,7 @@ static void enc_stage_sequential_streams(EncChunk &ck) {
     } catch (const std::exception &e) { return ck.refuse(i, DSA_ERR_INVALID_DATA, e.what()); }
     ck.E->streams[i].swap(w.d);
     if (ordered) ck.E->order[i].swap(ck.entry_rows[s0]);
+    if (merge) { ck.E->linear[i].second = points; ck.E->cells[i].swap(ck.row_cells[s0]); }
   });
 }
 // Meshes base .. base + count of a sequential request on a lane, through the stages it shares with encode_chunk.  No stage waits for

@@ -1,7 +1,7 @@
 // draco-sharp_amd/csrc/dsa_source_rows.h  (included by dsa_api.hip, behind dsa_encode.h)
 //
 // dsa_batch_source_rows: for a batch decoded from the streams of an encode that kept its entry rows (dsa_encode_rows_batch,
-// track_rows = 1; a sequential handle: the identity, or with point_order = 1 the stored permutation), per mesh and attribute one uint32 array with a row per POINT -- which row of
+// track_rows = 1; a sequential handle: the identity, or with point_order = 1 the stored permutation, with merge_points = 1 the kept rows), per mesh and attribute one uint32 array with a row per POINT -- which row of
 // the arrays the encoder was given the point carries.  Shaped like the vertex arrays (dsa_batch_vertex_arrays): a device block of
 // the batch's own [table of SrcRowsMesh | the tracked entry rows | the arrays], filled from pinned staging in one transfer on the
 // download stream, k_source_rows (dsa_encode_rows.h) behind the decode's kernels, the arrays down in one transfer, an event of their

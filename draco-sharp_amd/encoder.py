@@ -64,7 +64,15 @@ class Config:
     row perm[e] of the caller's arrays, faces are written through the inverse.  The format gives the order of a sequential stream
     no meaning, and a scan or a shuffled sample codes to half its size or less this way.  EncodedStreams.entry_rows(i) returns
     perm (the same for every attribute) and Batch.source_rows carries side data across.  Sequential streams and point clouds
-    only: Edgebreaker orders its own entries."""
+    only: Edgebreaker orders its own entries.
+
+    merge_points (dsa_encode_merged_sequential_batch): 0 every point is coded; 1 (MERGE_CELLS) one point per occupied cell of the
+    position grid -- of the points whose quantised positions are equal the one with the smallest row stays, entry j of every
+    attribute carries row kept[j], and every quantised attribute keeps the bounds of all input rows.  With Grid(origin, range) on
+    the positions the voxel is range / (2^position_bits - 1).  EncodedStreams.entry_rows(i) returns kept (for every attribute),
+    EncodedStreams.row_entries(i) the entry of the cell of every input row (what averages colours or counts points per cell).
+    Point clouds only, under a sequential config with point_order=POINT_ORDER_MORTON: the points of a cell lie side by side in
+    that order, and merging the points of a mesh would collapse its faces."""
 
     EDGEBREAKER_METHODS = (0, 2, -1)
     POSITION_PREDICTIONS = (0, 1)
@@ -74,11 +82,12 @@ class Config:
     MULTI_PARALLELOGRAMS = (0, 2, 4, -1)
     TRAVERSAL_METHODS = (0, 1, 2)
     POINT_ORDERS = (native.POINT_ORDER_CALLER, native.POINT_ORDER_MORTON)
+    MERGE_POINTS = (native.MERGE_NONE, native.MERGE_CELLS)
 
     def __init__(self, position_bits=11, texcoord_bits=10, normal_bits=8, speed=5, single_connectivity=False,
                  symbol_scheme=-1, position_prediction=1, texcoord_prediction=1, edgebreaker_method=0, normal_prediction=0,
                  encoding_method=1, compress_connectivity=False, multi_parallelogram=0, traversal_method=0, repair_topology=False, weld_points=False,
-                 repair_seams=False, weld_attributes=False, track_rows=False, point_order=0):
+                 repair_seams=False, weld_attributes=False, track_rows=False, point_order=0, merge_points=0):
         for name, value, legal in (("encoding_method", encoding_method, self.ENCODING_METHODS),
                                    ("edgebreaker_method", edgebreaker_method, self.EDGEBREAKER_METHODS),
                                    ("position_prediction", position_prediction, self.POSITION_PREDICTIONS),
@@ -86,7 +95,8 @@ class Config:
                                    ("normal_prediction", normal_prediction, self.NORMAL_PREDICTIONS),
                                    ("multi_parallelogram", multi_parallelogram, self.MULTI_PARALLELOGRAMS),
                                    ("traversal_method", traversal_method, self.TRAVERSAL_METHODS),
-                                   ("point_order", point_order, self.POINT_ORDERS)):
+                                   ("point_order", point_order, self.POINT_ORDERS),
+                                   ("merge_points", merge_points, self.MERGE_POINTS)):
             if value not in legal:
                 raise ValueError("%s %r: the encoder writes one of %s" % (name, value, legal))
         self.position_bits, self.texcoord_bits, self.normal_bits = position_bits, texcoord_bits, normal_bits
@@ -113,6 +123,9 @@ class Config:
             raise ValueError("weld_attributes welds the listed attributes of per-point input each alone: it needs weld_points=True")
         self.track_rows = bool(track_rows)
         self.point_order = point_order
+        self.merge_points = merge_points
+        if self.merge_points != 0 and not (self.sequential and self.point_order == native.POINT_ORDER_MORTON):
+            raise ValueError("merge_points keeps one point per cell of the position grid: it needs a sequential config (encoding_method 0) with point_order=POINT_ORDER_MORTON")
 
     @property
     def sequential(self):
@@ -132,6 +145,13 @@ class Config:
         native.lib().dsa_encode_default_order_options(C.byref(o))
         o.sequential = self._native_sequential(geometry)
         o.point_order = self.point_order
+        return o
+
+    def _native_merge(self, geometry):
+        o = native.EncodeMergeOptions()
+        native.lib().dsa_encode_default_merge_options(C.byref(o))
+        o.order = self._native_order(geometry)
+        o.merge_points = self.merge_points
         return o
 
     @property
@@ -514,6 +534,14 @@ class EncodedStreams:
             raise ValueError("the encoded batch was closed")
         return _entry_rows(self._ctx, self._h, i + len(self) if i < 0 else i)
 
+    def row_entries(self, i):
+        """Of stream i of an encode with Config(merge_points=MERGE_CELLS) a uint32 array with one element per input row: the entry
+        of the stream whose cell the row lies in (entry_rows(i)[a][row_entries(i)[r]] is the kept row of r's cell);
+        dsa_encoded_row_entries."""
+        if self._h is None:
+            raise ValueError("the encoded batch was closed")
+        return _row_entries(self._ctx, self._h, i + len(self) if i < 0 else i)
+
     def close(self):
         """Releases the library's buffers (streams already taken stay valid)."""
         if self._h is not None:
@@ -537,6 +565,9 @@ class _EncodedHandle:
 
     def entry_rows(self, i):
         return _entry_rows(self._ctx, self._h, i)
+
+    def row_entries(self, i):
+        return _row_entries(self._ctx, self._h, i)
 
     def close(self):
         if self._h is not None:
@@ -565,6 +596,20 @@ def _entry_rows(ctx, handle, i):
             _raise(st, ctx.error())
         out.append(rows)
     return out
+
+
+def _row_entries(ctx, handle, i):
+    """dsa_encoded_row_entries of mesh i."""
+    L = native.lib()
+    count = C.c_uint32()
+    st = L.dsa_encoded_row_entries(handle, i, None, 0, C.byref(count))
+    if st != 0:
+        _raise(st, ctx.error())
+    cells = np.empty(count.value, np.uint32)
+    st = L.dsa_encoded_row_entries(handle, i, cells.ctypes.data, len(cells), C.byref(count))
+    if st != 0:
+        _raise(st, ctx.error())
+    return cells
 
 
 class WeldedMaps:
@@ -610,6 +655,8 @@ class DracoEncoder:
             raise ValueError("attributes given per corner need Edgebreaker connectivity (encoding_method 1): a sequential stream has one value per point")
         if getattr(config, "point_order", 0) != 0 and not (clouds or config.sequential):
             raise ValueError("point_order needs a sequential stream (encoding_method 0, or point clouds): Edgebreaker orders its own entries")
+        if getattr(config, "merge_points", 0) != 0 and not clouds:
+            raise ValueError("merge_points takes point clouds (PointCloudData): merging the points of a mesh would collapse its faces and lose its seams")
         weld = getattr(config, "weld_points", False)
         if weld and (clouds or config.sequential):
             raise ValueError("weld_points shapes Edgebreaker streams of meshes: point clouds and sequential streams keep the caller's points")
@@ -667,7 +714,10 @@ class DracoEncoder:
         n = len(meshes)
         arr, grids, keep = _native_meshes(meshes)
         h = C.c_void_p()
-        if getattr(config, "point_order", 0) != 0:      # (the plain case keeps arriving through the call it always took)
+        if getattr(config, "merge_points", 0) != 0:     # (the widest call only when its option is set)
+            opt = config._native_merge(geometry)
+            st = native.lib().dsa_encode_merged_sequential_batch(ctx._h, n, arr, grids, C.byref(opt), C.byref(h))
+        elif getattr(config, "point_order", 0) != 0:    # (the plain case keeps arriving through the call it always took)
             opt = config._native_order(geometry)
             st = native.lib().dsa_encode_ordered_sequential_batch(ctx._h, n, arr, grids, C.byref(opt), C.byref(h))
         else:

@@ -41,6 +41,7 @@ EXPORTS = [
     "dsa_encode_default_corner_attributes_options", "dsa_encode_corner_attributes_batch",
     "dsa_encode_default_rows_options", "dsa_encode_rows_batch", "dsa_encoded_entry_rows", "dsa_encoded_attributes",
     "dsa_encode_default_order_options", "dsa_encode_ordered_sequential_batch",
+    "dsa_encode_default_merge_options", "dsa_encode_merged_sequential_batch", "dsa_encoded_row_entries",
     "dsa_encoded_size", "dsa_encoded_stream", "dsa_encoded_free",
     "dsa_pool_create", "dsa_pool_destroy", "dsa_pool_size", "dsa_pool_last_error", "dsa_pool_decode", "dsa_pool_job_locate",
     "dsa_pool_job_chunks", "dsa_pool_job_free", "dsa_pool_plan",
@@ -89,6 +90,16 @@ class EncodeOrderOptions(C.Structure):
     """dsa_encode_order_options: the options of dsa_encode_grid_sequential_batch, and point_order (1: the points of every stream in
     Morton order of their quantised positions; the handle keeps the permutation: dsa_encoded_entry_rows)."""
     _fields_ = [("sequential", EncodeSequentialOptions), ("point_order", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+MERGE_NONE, MERGE_CELLS = 0, 1                      # dsa_encode_merge_options.merge_points
+
+
+class EncodeMergeOptions(C.Structure):
+    """dsa_encode_merge_options: the options of dsa_encode_ordered_sequential_batch, and merge_points (1: one point per occupied
+    cell of the position grid of a point cloud; the handle keeps the kept rows and the entry of every input row:
+    dsa_encoded_entry_rows, dsa_encoded_row_entries)."""
+    _fields_ = [("order", EncodeOrderOptions), ("merge_points", C.c_int32), ("reserved", C.c_int32 * 7)]
 
 
 class MeshInput(C.Structure):
@@ -349,6 +360,11 @@ def lib():
             L.dsa_encode_default_order_options.argtypes = [C.POINTER(EncodeOrderOptions)]
             L.dsa_encode_default_order_options.restype = None
             L.dsa_encode_ordered_sequential_batch.argtypes = [vp, u32, C.POINTER(MeshAttrInput), C.POINTER(MeshGrids), C.POINTER(EncodeOrderOptions), C.POINTER(vp)]
+        if hasattr(L, "dsa_encode_merged_sequential_batch"):
+            L.dsa_encode_default_merge_options.argtypes = [C.POINTER(EncodeMergeOptions)]
+            L.dsa_encode_default_merge_options.restype = None
+            L.dsa_encode_merged_sequential_batch.argtypes = [vp, u32, C.POINTER(MeshAttrInput), C.POINTER(MeshGrids), C.POINTER(EncodeMergeOptions), C.POINTER(vp)]
+            L.dsa_encoded_row_entries.argtypes = [vp, u32, vp, C.c_size_t, C.POINTER(u32)]
         L.dsa_encoded_size.restype = u32
         L.dsa_encoded_size.argtypes = [vp]
         L.dsa_encoded_stream.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(C.c_size_t)]

@@ -234,6 +234,7 @@ def lib():
                                         C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(ExtraInput), C.c_uint32,
                                         C.POINTER(GridsInput), C.POINTER(Options), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
         L.synth_point_order.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(Grid), C.c_void_p]
+        L.synth_merge_points.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(Grid), C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]
         L.synth_shared_grid.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_uint32, C.c_int, C.POINTER(Grid)]
         L.synth_free.argtypes = [C.c_void_p]
         L.synth_make_mesh.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_uint32),
@@ -547,6 +548,62 @@ def encode_ordered(pos, faces=None, normals=None, uvs=None, generic=None, extra=
     data = encode_grid(take(pos), fc, take(normals), take(uvs), gen, ex, opt, form=0, geometry=geometry, compressed=compressed,
                        pos_grid=pos_grid, uv_grid=uv_grid)
     return data, perm
+
+
+def merge_points(pos, bits, grid=None):
+    """One point per occupied cell of the position grid: (kept, row_entries) for the points `pos` (N, 3) at `bits` position bits,
+    quantised as point_order quantises them.  With perm = point_order(pos, bits, grid) and key the interleaved bits, entry e is a
+    head iff e == 0 or key[perm[e]] != key[perm[e - 1]]; kept (uint32, m) lists perm[e] over the heads in sorted order -- the
+    smallest row of every cell -- and row_entries (uint32, N) holds for every row the index in kept of its cell.  What
+    dsa_encode_merged_sequential_batch with merge_points = 1 keeps."""
+    L = lib()
+    pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+    kept = np.zeros(len(pos), np.uint32)
+    cells = np.zeros(len(pos), np.uint32)
+    m = C.c_uint32()
+    if L.synth_merge_points(pos.ctypes.data, len(pos), int(bits), None if grid is None else C.byref(grid), kept.ctypes.data, C.byref(m), cells.ctypes.data):
+        raise RuntimeError(_err())
+    return kept[:m.value].copy(), cells
+
+
+def bounds_grid(values):
+    """The explicit grid equal to the own bounds of `values` (N, nc) float32: origin the minimum per component, range the largest
+    extent in float32 arithmetic, 1 where that is 0 -- what the coder finds for an attribute without a grid."""
+    v = np.ascontiguousarray(values, np.float32)
+    v = v.reshape(len(v), -1)
+    mn, mx = v.min(axis=0), v.max(axis=0)
+    rng = np.float32(np.max((mx - mn).astype(np.float32)))
+    return grid(mn, rng if rng != 0 else np.float32(1.0))
+
+
+def merged_arguments(pos, normals=None, uvs=None, generic=None, extra=None, opt=None, pos_grid=None, uv_grid=None):
+    """The arguments of the plain call that writes a merged stream: (kept, row_entries, kwargs for encode_grid(form=0, geometry=0))
+    -- every per-point array at [kept], every quantised attribute on an explicit grid equal to the bounds of ALL its rows (the
+    grid given, where one was)."""
+    opt = opt or options()
+    kept, cells = merge_points(pos, opt.pos_bits, pos_grid)
+    take = lambda a, nc: None if a is None else np.ascontiguousarray(np.asarray(a).reshape(-1, nc)[kept])      # noqa: E731
+    ex = []
+    for e in (extra or []):
+        e = e if isinstance(e, Extra) else Extra(e)
+        g = e.grid
+        if g is None and e.values.dtype == np.dtype(np.float32):
+            g = bounds_grid(e.values)
+        ex.append(Extra(e.values[kept], attribute_type=e.attribute_type, normalized=bool(e.normalized), unique_id=e.unique_id,
+                        quantization_bits=e.quantization_bits, data_type=e.data_type, num_components=e.num_components, grid=g))
+    pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+    kw = dict(pos=pos[kept], normals=take(normals, 3), uvs=take(uvs, 2), generic=None if generic is None else np.asarray(generic)[kept],
+              extra=ex, opt=opt, pos_grid=pos_grid if pos_grid is not None else bounds_grid(pos),
+              uv_grid=uv_grid if uv_grid is not None or uvs is None else bounds_grid(np.asarray(uvs, np.float32).reshape(-1, 2)))
+    return kept, cells, kw
+
+
+def encode_merged(pos, normals=None, uvs=None, generic=None, extra=None, opt=None, pos_grid=None, uv_grid=None):
+    """encode_grid(form=0, geometry=0) of one point per occupied cell: (stream, kept, row_entries), merged_arguments coded.  What
+    dsa_encode_merged_sequential_batch with merge_points = 1 must write, and the rows its handle must report."""
+    kept, cells, kw = merged_arguments(pos, normals, uvs, generic, extra, opt, pos_grid, uv_grid)
+    p = kw.pop("pos")
+    return encode_grid(p, None, form=0, geometry=0, **kw), kept, cells
 
 
 def entry_rows(pos, faces=None, normals=None, uvs=None, generic=None, extra=None, opt=None, form=1, normal_corners=None, uv_corners=None,

@@ -513,6 +513,17 @@ int synth_point_order(const float *pos, uint32_t n, int bits, const synth::Grid 
     return 0;
   } catch (const std::exception &e) { snprintf(g_err, sizeof(g_err), "%s", e.what()); return 1; }
 }
+// One point per occupied cell (dsa_encode_host.h merge_points): kept[*m] (room for n), row_entries[n].
+int synth_merge_points(const float *pos, uint32_t n, int bits, const synth::Grid *grid, uint32_t *kept, uint32_t *m, uint32_t *row_entries) {
+  try {
+    std::vector<uint32_t> k, c;
+    synth::merge_points(pos, n, bits, grid, k, c);
+    memcpy(kept, k.data(), 4 * k.size());
+    memcpy(row_entries, c.data(), 4 * c.size());
+    *m = (uint32_t)k.size();
+    return 0;
+  } catch (const std::exception &e) { snprintf(g_err, sizeof(g_err), "%s", e.what()); return 1; }
+}
 void synth_free(uint8_t *p) { free(p); }
 
 // Procedural mesh: returns counts; call once with NULL outputs to size, then again to fill.

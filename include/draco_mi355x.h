@@ -697,6 +697,47 @@ typedef struct dsa_encode_order_options {
 void dsa_encode_default_order_options(dsa_encode_order_options *options);
 dsa_status dsa_encode_ordered_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids,
                                                const dsa_encode_order_options *options, dsa_encoded **out);
+/* dsa_encode_ordered_sequential_batch that codes one point per occupied quantisation cell of a point cloud.  A scan, a merged set
+ * of sweeps or a particle set at 11 - 14 position bits puts many points into one cell of the position grid; the stream would code
+ * every one of them (a zero correction per component and a full set of attribute values) and the decoder would hand back points
+ * whose positions are bit-identical.  With an explicit dsa_quantization_grid (origin, range) the caller chooses the voxel:
+ * range / (2^position_bits - 1).
+ *   merge_points = 1 (taken only with point_order = 1 and geometry 0): with key(r) and perm (the rows in ascending (key, row)) as
+ *   documented for point_order = 1, entry e of the sorted order is a head iff e == 0 or key[perm[e]] != key[perm[e - 1]]; kept is
+ *   the list of perm[e] over the heads in sorted order, m = its length.  The sort is stable, so kept[j] is the smallest input row
+ *   of its cell, and the result is a function of the input alone.  The cell IS the key, built from the low position_bits bits of
+ *   the quantised integers: two rows merge exactly when the plain ordered call would give them equal keys, and no other notion of
+ *   equality is introduced.  A value on a grid that the call refuses today is still refused, with its own text.
+ *   The stream codes m points; entry j of EVERY attribute carries row kept[j] of the caller's array for that attribute.  Bounds
+ *   and quantisers run in front of the merge, so every quantised attribute (positions, the UV set, float attributes of the list)
+ *   keeps the bounds of ALL input rows, not of the kept ones: the stream is byte for byte that of
+ *   dsa_encode_grid_sequential_batch (geometry 0) for positions[kept], normals[kept], ... every listed attribute[kept] with every
+ *   quantised attribute on an explicit grid equal to the bounds of all its rows (origin = the per-component minima, range = the
+ *   largest extent, 1 where that is 0) -- where a grid was given or shared, on that grid.  Integer attributes and octahedral
+ *   normals carry no bounds.  (A stream on its own bounds and one on the equal explicit grid have identical headers.)
+ *   The handle: dsa_encoded_entry_rows returns kept for every attribute, count m; dsa_encoded_row_entries returns for every input
+ *   row r the entry j whose cell r lies in (key(kept[j]) == key(r)), count n -- what averages colours, votes labels or counts the
+ *   points per cell without redoing the quantisation; 4 bytes per input row in the handle, with merge_points = 1 only, on any
+ *   other handle DSA_ERR_INVALID_ARGUMENT and dsa_last_error names merge_points.  dsa_batch_source_rows works with a merged handle
+ *   as with an ordered one; the entry count is m.  Found on the device behind the sort (head flags by ballot, a scan of the tiles'
+ *   counts, a compaction without atomics; dsa_encode_order.h).  A refused cloud fails alone, with the status and text it has today.
+ *   merge_points = 0: the bytes, the messages, the work and the rows of dsa_encode_ordered_sequential_batch.
+ * Fails the call with DSA_ERR_INVALID_ARGUMENT before any mesh is looked at, dsa_last_error naming the field: merge_points outside
+ * {0, 1}; merge_points = 1 with point_order != 1; merge_points = 1 with geometry != 0 (merging the points of a sequential mesh
+ * would collapse faces and lose seams: meshes are not taken); a non-zero reserved word.  Refusals of the nested option structs
+ * keep their own words.  Added after ABI 4 without changing it: callers detect the feature by the symbol
+ * dsa_encode_merged_sequential_batch. */
+typedef struct dsa_encode_merge_options {
+  dsa_encode_order_options order;          /* as for dsa_encode_ordered_sequential_batch, same legal values */
+  int32_t merge_points;                    /* 0 (default): every point is coded; 1: one point per occupied cell of the position grid */
+  int32_t reserved[7];                     /* must be zero */
+} dsa_encode_merge_options;
+void dsa_encode_default_merge_options(dsa_encode_merge_options *options);
+dsa_status dsa_encode_merged_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids,
+                                              const dsa_encode_merge_options *options, dsa_encoded **out);
+/* Of stream `mesh` of a handle of dsa_encode_merged_sequential_batch with merge_points = 1: row_entries, uint32[n], one per input
+ * row (above).  dst NULL: the count alone; capacity in elements. */
+dsa_status dsa_encoded_row_entries(const dsa_encoded *encoded, uint32_t mesh, uint32_t *dst, size_t capacity, uint32_t *count);
 /* The rows of a decoded batch per POINT: for every mesh of `batch` and every attribute a of its stream,
  *     rows[a][p] = entry_rows[a][map[a][p]]          (map: the decoder's point -> entry map, dsa_batch_device_point_map)
  * -- which row of the arrays given to the encoder point p carries, gathered on the device (k_source_rows) so that neither the maps
