@@ -7,4 +7,4 @@ __version__ = "0.1.0"
 from .decoder import (Batch, Context, DataBuffer, DeviceException, Draco, DracoDecoder, DracoHeader, DracoMetadata,  # noqa: E402,F401
                       InvalidDataException, Mesh, MetadataElement, PointAttribute, PointCloud, Pool, PoolJob, parse_metadata, pool_plan)
 from .encoder import Attribute, Config, DracoEncoder, Grid, MeshData, PointCloudData, WeldedMaps  # noqa: E402,F401
-from .native import ENCODE_ORDER_TILE, MERGE_CELLS, MERGE_NONE, POINT_ORDER_CALLER, POINT_ORDER_MORTON  # noqa: E402,F401
+from .native import ENCODE_MAX_PARTS, ENCODE_ORDER_TILE, MERGE_CELLS, MERGE_NONE, POINT_ORDER_CALLER, POINT_ORDER_MORTON  # noqa: E402,F401

@@ -82,6 +82,24 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
     private uint[][] _rowEntries;
     // Of stream i of the most recent Encode with MergePoints: for every input row the entry of the stream whose cell the row lies in.
     public uint[] RowEntries(int i) => _rowEntries != null && i >= 0 && i < _rowEntries.Length ? _rowEntries[i] : throw new InvalidOperationException("no row entries: set MergePoints before Encode");
+    // PartPoints (dsa_encode_split_sequential_batch): 0 one stream per cloud; N >= 1 the Morton order of every point cloud cut into
+    // ceil(n / N) parts of at most N points, each an ordinary point-cloud stream on the cloud's one quantisation grid.  Encode then
+    // returns one array per STREAM (the inputs in order, the parts of an input in order); Parts(i) names the streams of input i,
+    // PartInfo(s) says which part stream s is and gives the box of its points, EntryRows(s) its slice of the order.  Needs
+    // PointOrder 1 and MergePoints 0; point clouds only: a part of a mesh would need its faces cut, and an encode of meshes throws.
+    public int PartPoints { get; set; }
+    public struct PartBox
+    {
+        public uint Input, Part, Parts, FirstEntry, NumPoints, PositionBits;
+        public int[] QMin, QMax;         // per component, over the position integers the stream codes
+        public float[] BoxMin, BoxMax;   // what the decoder returns for them: the box of the part's decoded positions
+    }
+    private (uint First, uint Count)[] _parts;
+    private PartBox[] _partInfo;
+    // Of input i of the most recent Encode with PartPoints: its streams, first and count.
+    public (uint First, uint Count) Parts(int i) => _parts != null && i >= 0 && i < _parts.Length ? _parts[i] : throw new InvalidOperationException("no parts: set PartPoints before Encode");
+    // Of stream s of the most recent Encode with PartPoints: which part it is, and its box.
+    public PartBox PartInfo(int s) => _partInfo != null && s >= 0 && s < _partInfo.Length ? _partInfo[s] : throw new InvalidOperationException("no parts: set PartPoints before Encode");
     private uint[][][] _entryRows;
     // Of stream i of the most recent Encode with TrackRows: per attribute of the stream (positions, then normals, texture coordinates,
     // generic where present, then the others) the row of the input every entry carries.
@@ -186,6 +204,34 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
                     inputs[i].Faces = (uint*)Pin(faces, pins);
                 }
             }
+            if (PartPoints != 0)
+            {
+                if (geometry != 0) throw new ArgumentException("PartPoints takes point clouds: a part of a mesh would need its faces cut");
+                NativeMethods.dsa_encode_default_split_options(out var po);
+                po.Merge.Order.Sequential = so;
+                po.Merge.Order.PointOrder = PointOrder;
+                po.Merge.MergePoints = MergePoints;
+                po.PartPoints = PartPoints;
+                var ain = new DsaMeshAttrInput[items.Count];
+                for (int i = 0; i < items.Count; ++i) { ain[i].Mesh.Mesh = inputs[i]; Extras(items[i], null, (uint)items[i].PointsCount, ref ain[i], pins); }
+                fixed (DsaMeshAttrInput* p = ain)
+                    NativeMethods.Check(NativeMethods.dsa_encode_split_sequential_batch(_ctx, (uint)items.Count, p, null, in po, out encoded), _ctx, "dsa_encode_split_sequential_batch");
+                int streams = (int)NativeMethods.dsa_encoded_size(encoded);
+                var split = Streams(encoded, streams);
+                var parts = new (uint First, uint Count)[items.Count];
+                for (uint i = 0; i < items.Count; ++i)
+                    NativeMethods.Check(NativeMethods.dsa_encoded_parts(encoded, i, out parts[i].First, out parts[i].Count), _ctx, $"input {i}");
+                var info = new PartBox[streams];
+                for (uint s = 0; s < streams; ++s)
+                {
+                    NativeMethods.Check(NativeMethods.dsa_encoded_part_info(encoded, s, out var pi), _ctx, $"stream {s}");
+                    info[s] = new PartBox { Input = pi.Input, Part = pi.Part, Parts = pi.Parts, FirstEntry = pi.FirstEntry, NumPoints = pi.NumPoints, PositionBits = pi.PositionBits,
+                                            QMin = new[] { pi.QMin[0], pi.QMin[1], pi.QMin[2] }, QMax = new[] { pi.QMax[0], pi.QMax[1], pi.QMax[2] },
+                                            BoxMin = new[] { pi.BoxMin[0], pi.BoxMin[1], pi.BoxMin[2] }, BoxMax = new[] { pi.BoxMax[0], pi.BoxMax[1], pi.BoxMax[2] } };
+                }
+                _parts = parts; _partInfo = info;
+                return split;
+            }
             if (MergePoints != 0)
             {
                 if (geometry != 0) throw new ArgumentException("MergePoints takes point clouds: merging the points of a mesh would collapse its faces and lose its seams");
@@ -248,6 +294,7 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
             for (int i = 0; i < meshes.Count; ++i) items[i] = meshes[i];
             return EncodeSequential(items, config, 1);
         }
+        if (PartPoints != 0) throw new ArgumentException("PartPoints takes point clouds: a part of a mesh would need its faces cut");
         if (MergePoints != 0) throw new ArgumentException("MergePoints takes point clouds: merging the points of a mesh would collapse its faces and lose its seams");
         if (PointOrder != 0) throw new ArgumentException("PointOrder needs a sequential stream (EncodingMethod SequentialEncoding, or point clouds): Edgebreaker orders its own entries");
         NativeMethods.dsa_encode_default_options(out var opt);
@@ -492,7 +539,7 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
             NativeMethods.Check(NativeMethods.dsa_encoded_stream(encoded, i, out var bytes, out var length), _ctx, $"mesh {i}");
             result[i] = new ReadOnlySpan<byte>(bytes, (int)length).ToArray();
         }
-        _rowEntries = null;
+        _rowEntries = null; _parts = null; _partInfo = null;
         if (TrackRows || PointOrder != 0) _entryRows = Rows(encoded, count);      // (a sequential handle answers with the identity, or with the point order)
         return result;
     }

@@ -248,6 +248,29 @@ internal unsafe struct DsaEncodeMergeOptions
     public fixed int Reserved[7];   // zero
 }
 
+// dsa_encode_split_options (dsa_encode_split_sequential_batch)
+[StructLayout(LayoutKind.Sequential)]
+internal unsafe struct DsaEncodeSplitOptions
+{
+    public DsaEncodeMergeOptions Merge;
+    public int PartPoints;          // 0: one stream per cloud; N >= 1: the Morton order in parts of at most N points (point clouds, PointOrder 1, MergePoints 0)
+    public fixed int Reserved[7];   // zero
+}
+
+// dsa_part_info (dsa_encoded_part_info)
+[StructLayout(LayoutKind.Sequential)]
+internal unsafe struct DsaPartInfo
+{
+    public uint Input, Part, Parts; // which cloud of the call, which of its parts, how many it has
+    public uint FirstEntry, NumPoints;
+    public uint PositionBits;
+    public fixed int QMin[3];
+    public fixed int QMax[3];
+    public fixed float BoxMin[3];
+    public fixed float BoxMax[3];
+    public fixed uint Reserved[2];  // zero
+}
+
 [StructLayout(LayoutKind.Sequential)]
 internal unsafe struct DsaMeshInput
 {
@@ -379,6 +402,10 @@ internal static unsafe partial class NativeMethods
     [DllImport(Lib)] internal static extern void dsa_encode_default_merge_options(out DsaEncodeMergeOptions options);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_merged_sequential_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, in DsaEncodeMergeOptions options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encoded_row_entries(IntPtr encoded, uint mesh, uint* dst, nuint capacity, out uint count);
+    [DllImport(Lib)] internal static extern void dsa_encode_default_split_options(out DsaEncodeSplitOptions options);
+    [DllImport(Lib)] internal static extern DsaStatus dsa_encode_split_sequential_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, in DsaEncodeSplitOptions options, out IntPtr encoded);
+    [DllImport(Lib)] internal static extern DsaStatus dsa_encoded_parts(IntPtr encoded, uint input, out uint firstStream, out uint count);
+    [DllImport(Lib)] internal static extern DsaStatus dsa_encoded_part_info(IntPtr encoded, uint stream, out DsaPartInfo info);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_rows_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, DsaMeshAttributeCorners* corners, in DsaEncodeRowsOptions options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encoded_entry_rows(IntPtr encoded, uint mesh, uint attribute, uint* dst, nuint capacity, out uint count);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encoded_attributes(IntPtr encoded, uint mesh, out uint count);

@@ -27,6 +27,8 @@
 //                                                over all clouds of a chunk, between k_enc_quantize and k_enc_gather
 //                              k_enc_merge_*     dsa_encode_merged_sequential_batch, merge_points = 1: one point per cell of the position grid,
 //                                                the heads of the runs of equal keys behind the sort; nv of the cloud's streams falls on the device
+//                              k_enc_part_bounds dsa_encode_split_sequential_batch, part_points >= 1: the sorted order in parts, a set of stream
+//                                                records each; the box of every part's position integers behind the sort
 //         (dsa_encode_layout.h) the request of an entry point, the state of a chunk, the per-mesh checks and plans, the arena layout
 // Every entry point fills an EncRequest and calls encode_request; a chunk of it goes through the stages of encode_chunk (or of
 // encode_sequential_chunk, dsa_encode_sequential.h) on a lane.
@@ -55,7 +57,7 @@ __global__ __launch_bounds__(256) void k_enc_bounds(uint8_t *arena, EncStream *s
   const uint32_t si = blockIdx.x;
   if (si >= ns) return;
   EncStream &S = streams[si];
-  if (S.kind != 0) return;
+  if (S.kind != 0 || S.part != 0) return;         // (a part behind the first of a split cloud: the first part's bounds are the cloud's)
   if (GRID && S.grid_mode != 0) return;
   __shared__ float s_mn[4][256], s_mx[4][256];
   const float *src = (const float *)(arena + S.src);
@@ -112,6 +114,7 @@ __global__ __launch_bounds__(256) void k_enc_quantize(uint8_t *arena, EncStream 
   const uint32_t si = blockIdx.y;
   if (si >= ns) return;
   const EncStream &S = streams[si];
+  if (S.part != 0) return;                        // (a part behind the first of a split cloud: `vals` are the first part's)
   if (GRID && S.kind == 0 && S.grid_mode != 0) return;
   const float *src = (const float *)(arena + S.src);
   int32_t *vals = (int32_t *)(arena + S.vals);
@@ -661,8 +664,10 @@ static dsa_status enc_code_streams(dsa_context *ctx, EncLane &lane, EncChunk &ck
   // (track_rows: a fifth piece per stream, its entry rows -- k_enc_entry_rows has run behind the attribute kernels)
   // (point_order: the fifth piece of a mesh's first stream is the permutation its streams share -- dsa_encode_order.h; with
   // merge_points the kept rows, nv of them as the records say, and a sixth piece, row_entries of all its input rows)
-  const bool track = !ck.L.rows_of_stream.empty(), ordered = !ck.L.ord.empty(), merge = ck.L.merge;
-  const size_t per = merge ? 6 : (track || ordered ? 5 : 4);
+  // (part_points: the fifth piece of a cloud's first stream is the whole permutation, whose slices its parts' streams read, the
+  // sixth the records of its parts with their boxes)
+  const bool track = !ck.L.rows_of_stream.empty(), ordered = !ck.L.ord.empty(), merge = ck.L.merge, split = ck.L.split;
+  const size_t per = merge || split ? 6 : (track || ordered ? 5 : 4);
   std::vector<dsa::PackItem> items;
   for (uint32_t s = 0; s < ns; ++s) {
     if (hs[s].overflow || E->status[stream_mesh[s]] != DSA_OK) continue;
@@ -677,7 +682,8 @@ static dsa_status enc_code_streams(dsa_context *ctx, EncLane &lane, EncChunk &ck
       items.push_back({R ? R->out : 0, 0, R ? 4u * std::min(hs[s].nv, R->cap) : 0u, s});
     } else if (ordered) {
       const bool first = s == ck.L.first_stream[stream_mesh[s]];
-      items.push_back({hs[s].e2v, 0, first ? 4u * hs[s].nv : 0u, s});
+      items.push_back({hs[s].e2v, 0, first ? 4u * (split ? ck.L.ord[ck.L.ord_of_mesh[stream_mesh[s]]].n : hs[s].nv) : 0u, s});
+      if (split) items.push_back({ck.L.parts_at + sizeof(dsa::EncPart) * ck.L.part_of_mesh[stream_mesh[s]], 0, first ? (uint32_t)sizeof(dsa::EncPart) * ck.num_parts((uint32_t)stream_mesh[s]) : 0u, s});
       if (merge) { const dsa::EncOrder &O = ck.L.ord[ck.L.ord_of_mesh[stream_mesh[s]]]; items.push_back({O.cells, 0, first ? 4u * O.n : 0u, s}); }
     }
   }
@@ -686,7 +692,8 @@ static dsa_status enc_code_streams(dsa_context *ctx, EncLane &lane, EncChunk &ck
   hostutil::parallel_for((uint32_t)(items.size() / per), [&](uint32_t m) {
     const size_t k = per * (size_t)m;
     const uint32_t s = items[k].pad;
-    if (per == 6 && items[k + 5].len) { const uint32_t *r = (const uint32_t *)(host + items[k + 5].packed_off); ck.row_cells[s].assign(r, r + items[k + 5].len / 4u); }
+    if (split && items[k + 5].len) { const dsa::EncPart *r = (const dsa::EncPart *)(host + items[k + 5].packed_off); ck.part_boxes[s].assign(r, r + items[k + 5].len / sizeof(dsa::EncPart)); }
+    else if (per == 6 && items[k + 5].len) { const uint32_t *r = (const uint32_t *)(host + items[k + 5].packed_off); ck.row_cells[s].assign(r, r + items[k + 5].len / 4u); }
     if (per >= 5 && items[k + 4].len) { const uint32_t *r = (const uint32_t *)(host + items[k + 4].packed_off); ck.entry_rows[s].assign(r, r + items[k + 4].len / 4u); }
     if (items[k].len) rans[s].assign(host + items[k].packed_off, host + items[k].packed_off + items[k].len);
     if (items[k + 1].len) bits[s].assign(host + items[k + 1].packed_off, host + items[k + 1].packed_off + items[k + 1].len);
@@ -1126,13 +1133,18 @@ static dsa_status enc_stage_attributes(dsa_context *ctx, EncLane &lane, EncChunk
   const uint32_t gx = std::max(1u, std::min(64u, (L.max_rows + 2047) / 2048));
   bool order_timing = false;
   EncLap order_lap{&lane};
+  // a grid of (gx, streams) blocks, in slices of what the y of a grid holds: a split cloud of many parts has more streams than that
+  // (every other chunk: one launch, as ever)
+  auto over_streams = [&](auto kernel) {
+    for (uint32_t s = 0; s < ns; s += 65535u) { const uint32_t cnt = std::min(65535u, ns - s); hipLaunchKernelGGL(kernel, dim3(gx, cnt), dim3(256), 0, st, arena, d_streams + s, cnt); }
+  };
   if (!L.any_grid) {
     hipLaunchKernelGGL(dsa::k_enc_bounds<false>, dim3(ns), dim3(256), 0, st, arena, d_streams, ns);
-    hipLaunchKernelGGL(dsa::k_enc_quantize<false>, dim3(gx, ns), dim3(256), 0, st, arena, d_streams, ns);
+    over_streams(dsa::k_enc_quantize<false>);
   } else {                   // streams on a grid of the caller's or of their group: their bounds are given, their values are checked
     hipLaunchKernelGGL(dsa::k_enc_bounds<true>, dim3(ns), dim3(256), 0, st, arena, d_streams, ns);
-    hipLaunchKernelGGL(dsa::k_enc_quantize<true>, dim3(gx, ns), dim3(256), 0, st, arena, d_streams, ns);
-    hipLaunchKernelGGL(dsa::k_enc_grid_quantize<dsa::EncStream>, dim3(gx, ns), dim3(256), 0, st, arena, d_streams, ns);
+    over_streams(dsa::k_enc_quantize<true>);
+    over_streams(dsa::k_enc_grid_quantize<dsa::EncStream>);
   }
   if (device_conn) {
     const dim3 gt(std::max(1u, std::min(128u, (3u * L.maxf + 1023u) / 1024u)), n), gz(gt.x, nz);
@@ -1174,9 +1186,16 @@ static dsa_status enc_stage_attributes(dsa_context *ctx, EncLane &lane, EncChunk
       ENC_TRY(hipGetLastError());
       if (order_timing) { ENC_TRY(hipStreamSynchronize(st)); order_lap("point merge"); }
     }
+    if (L.split) {             // part_points: the box of every part's position integers, behind the sort (the parts' streams read their slices of it as they are)
+      dsa::enc_part_launch([st](auto kernel, uint32_t grid_x, uint32_t grid_y, uint32_t block, auto... args) { hipLaunchKernelGGL(kernel, dim3(grid_x, grid_y), dim3(block), 0, st, args...); },
+                           arena, (const dsa::EncOrder *)(arena + L.ord_at), (uint32_t)L.ord.size(), (dsa::EncPart *)(arena + L.parts_at), (uint32_t)L.parts.size(),
+                           (const dsa::EncPartTile *)(arena + L.part_tiles_at), (uint32_t)L.part_tiles.size(), L.ord_passes);
+      ENC_TRY(hipGetLastError());
+      if (order_timing) { ENC_TRY(hipStreamSynchronize(st)); order_lap("part boxes"); }
+    }
   }
   hipLaunchKernelGGL(dsa::k_enc_gather, dim3(ns), dim3(256), 0, st, arena, d_streams, ns);
-  hipLaunchKernelGGL(dsa::k_enc_corr, dim3(gx, ns), dim3(256), 0, st, arena, d_streams, ns);
+  over_streams(dsa::k_enc_corr);
   if (L.any_multi) hipLaunchKernelGGL(dsa::k_enc_multi<dsa::EncStream>, dim3(gx, ns), dim3(256), 0, st, arena, d_streams, ns);
   if (L.any_crease) hipLaunchKernelGGL(dsa::k_enc_crease<dsa::EncStream>, dim3(ns), dim3(WAVE), 0, st, arena, d_streams, ns);
   if (!sequential) {
@@ -1299,6 +1318,7 @@ static dsa_status enc_stage_code(dsa_context *ctx, EncLane &lane, EncChunk &ck, 
   ck.rans.resize(ns); ck.bits.resize(ns); ck.flag_bits.resize(ns); ck.crease.resize(ck.L.any_crease ? 4 * (size_t)ns : 0);
   if (!ck.L.rows_of_stream.empty() || !ck.L.ord.empty()) ck.entry_rows.resize(ns);
   if (ck.L.merge) ck.row_cells.resize(ns);
+  if (ck.L.split) ck.part_boxes.resize(ns);
   return ns ? enc_code_streams(ctx, lane, ck) : DSA_OK;
 }
 // host phase 3: the stream layout (threads over meshes; write_stream may throw like any part of the host coder)
@@ -1453,6 +1473,15 @@ static dsa_status enc_check_options(dsa_context *ctx, const dsa_encode_merge_opt
   ENC_RESERVED(o, 7, "dsa_encode_merge_options");
   return enc_check_options(ctx, o.order, null_argument);
 }
+// ... or the sorted order in parts of bounded size (dsa_encode_order.h)
+static dsa_status enc_check_options(dsa_context *ctx, const dsa_encode_split_options &o, bool null_argument) {
+  if (o.part_points < 0) ENC_REFUSE("part_points %d: 0 (one stream per cloud) or the largest number of points of a part, 1 and above", (int)o.part_points);
+  if (o.part_points >= 1 && o.merge.order.point_order != 1) ENC_REFUSE("part_points %d needs point_order 1 (it was %d): parts are runs of the Morton order", (int)o.part_points, (int)o.merge.order.point_order);
+  if (o.part_points >= 1 && o.merge.order.sequential.geometry != 0) ENC_REFUSE("part_points %d needs geometry 0 (it was %d): a part of a mesh would need its faces cut", (int)o.part_points, (int)o.merge.order.sequential.geometry);
+  if (o.part_points >= 1 && o.merge.merge_points == 1) ENC_REFUSE("part_points %d with merge_points 1: the number of kept points, and so of parts, is known only on the device (not built)", (int)o.part_points);
+  ENC_RESERVED(o, 7, "dsa_encode_split_options");
+  return enc_check_options(ctx, o.merge, null_argument);
+}
 #undef ENC_RESERVED
 #undef ENC_REFUSE
 
@@ -1484,7 +1513,7 @@ static dsa_status enc_ensure_lanes(dsa_context *ctx, uint32_t lanes) {
 // streams wait for each other: four lanes, their walk streams at another priority.  Small batches are one chunk.
 // `code_chunk(sink, lane, base, count, &part)`: codes meshes base .. base + count of the batch on the lane.
 template <class ChunkFn>
-static dsa_status encode_batch_chunks(dsa_context *ctx, uint32_t n, ChunkFn &&code_chunk, dsa_encoded **out, int rows_kind = dsa_encoded::ROWS_NONE, bool merged = false) {
+static dsa_status encode_batch_chunks(dsa_context *ctx, uint32_t n, ChunkFn &&code_chunk, dsa_encoded **out, int rows_kind = dsa_encoded::ROWS_NONE, bool merged = false, bool split = false) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const uint32_t max_lanes = [&]() { const char *e = getenv("DSA_ENC_LANES"); const int v = e ? atoi(e) : 0; return (uint32_t)(v >= 1 && v <= 16 ? v : 4); }();
   const uint32_t chunk_max = [&]() { const char *e = getenv("DSA_ENC_CHUNK"); const int v = e ? atoi(e) : 0; return (uint32_t)(v >= 1 ? v : 0); }();
@@ -1505,6 +1534,7 @@ static dsa_status encode_batch_chunks(dsa_context *ctx, uint32_t n, ChunkFn &&co
   E->streams.resize(n); E->status.assign(n, DSA_OK); E->messages.resize(n);
   E->keep_rows(rows_kind, n);
   if (merged) E->keep_cells(n);
+  if (split) E->keep_parts(n);
   std::atomic<uint32_t> next{0};
   std::atomic<int> failed{DSA_OK};
   std::vector<std::string> errs(lanes);
@@ -1541,6 +1571,7 @@ static dsa_status encode_batch_chunks(dsa_context *ctx, uint32_t n, ChunkFn &&co
     return set_err(ctx, (dsa_status)failed.load(), "encoding failed");
   }
   if (getenv("DSA_ENC_TIMING")) fprintf(stderr, "[dsa_encode_batch] batch of %u done\n", n);
+  if (split) E->flatten_parts();                   // from an entry per input to an entry per stream
   *out = E.release();
   return DSA_OK;
 }
@@ -1644,7 +1675,7 @@ static dsa_status encode_request(dsa_context *ctx, const EncRequest &rq, dsa_enc
   return encode_batch_chunks(ctx, rq.n, [&](dsa_context *sink, EncLane &lane, uint32_t base, uint32_t cnt, dsa_encoded **part) {
     if (rq.weld_sink) return weld_chunk(sink, lane, rq, base, cnt, batch_n, part);
     return rq.sequential ? encode_sequential_chunk(sink, lane, rq, base, cnt, rq.n, part) : encode_chunk(sink, lane, rq, base, cnt, batch_n, part);
-  }, out, rq.rows_kind(), rq.merged());
+  }, out, rq.rows_kind(), rq.merged(), rq.split());
 }
 // dsa_encode_repair_batch, topology = 1: the batch as dsa_encode_level_batch codes it; then the meshes refused for their topology
 // once more as a request of their own, on the repaired corner table (EncRequest::repair), their results into the first's places.
@@ -1719,13 +1750,20 @@ static dsa_status encode_edgebreaker(dsa_context *ctx, uint32_t n, const dsa_mes
   rq.track_rows = w.track_rows == 1;
   return encode_checked(ctx, rq, grids, o.grid.repair.topology == 1, out);
 }
-static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_merge_options &m, dsa_encoded **out) {
-  if (enc_check_options(ctx, m, !ctx || !out || (n && !meshes)) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_split_options &s, dsa_encoded **out) {
+  if (enc_check_options(ctx, s, !ctx || !out || (n && !meshes)) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+  const dsa_encode_merge_options &m = s.merge;
   const dsa_encode_order_options &o = m.order;
   EncRequest rq;
   rq.n = n; rq.meshes = meshes; rq.sequential = true;
-  rq.seq = o.sequential; rq.point_order = o.point_order == 1; rq.merge_points = m.merge_points == 1;
+  rq.seq = o.sequential; rq.point_order = o.point_order == 1; rq.merge_points = m.merge_points == 1; rq.part_points = (uint32_t)s.part_points;
   return encode_checked(ctx, rq, grids, false, out);
+}
+static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_merge_options &m, dsa_encoded **out) {
+  dsa_encode_split_options s;
+  dsa_encode_default_split_options(&s);
+  s.merge = m;
+  return encode_sequential(ctx, n, meshes, grids, s, out);
 }
 static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_order_options &o, dsa_encoded **out) {
   dsa_encode_merge_options m;
@@ -1782,6 +1820,11 @@ void dsa_encode_default_merge_options(dsa_encode_merge_options *o) {
   if (!o) return;
   memset(o, 0, sizeof(*o));
   dsa_encode_default_order_options(&o->order);
+}
+void dsa_encode_default_split_options(dsa_encode_split_options *o) {
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  dsa_encode_default_merge_options(&o->merge);
 }
 void dsa_encode_default_repair_options(dsa_encode_repair_options *o) {
   if (!o) return;
@@ -1898,6 +1941,11 @@ dsa_status dsa_encode_ordered_sequential_batch(dsa_context *ctx, uint32_t n, con
 dsa_status dsa_encode_merged_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_merge_options *options, dsa_encoded **out) {
   DSA_GUARD(ctx, [&] { dsa_encode_merge_options o; dsa_encode_default_merge_options(&o); if (options) o = *options; return encode_sequential(ctx, n, meshes, grids, o, out); }());
 }
+// ... or the sorted order of every point cloud in parts of at most part_points points, a stream and a box each (part_points >= 1:
+// dsa_encode_order.h); part_points = 0 is the very request of the call above.
+dsa_status dsa_encode_split_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_split_options *options, dsa_encoded **out) {
+  DSA_GUARD(ctx, [&] { dsa_encode_split_options o; dsa_encode_default_split_options(&o); if (options) o = *options; return encode_sequential(ctx, n, meshes, grids, o, out); }());
+}
 
 struct dsa_welded {
   dsa_context *ctx = nullptr;
@@ -1975,6 +2023,25 @@ dsa_status dsa_encoded_row_entries(const dsa_encoded *e, uint32_t mesh, uint32_t
   if (!dst) return DSA_OK;
   if (capacity < cells.size()) return set_err(e->ctx, DSA_ERR_INVALID_ARGUMENT, "mesh %u: %u row entries, room for %llu", mesh, (uint32_t)cells.size(), (unsigned long long)capacity);
   if (!cells.empty()) memcpy(dst, cells.data(), 4ull * cells.size());
+  return DSA_OK;
+}
+// The stream slots of input `input`: of a split handle what flatten_parts laid out, of any other the input's own.
+dsa_status dsa_encoded_parts(const dsa_encoded *e, uint32_t input, uint32_t *first_stream, uint32_t *count) {
+  if (!e || !first_stream || !count) return DSA_ERR_INVALID_ARGUMENT;
+  *first_stream = 0; *count = 0;
+  const size_t inputs = e->part_first.empty() ? e->streams.size() : e->part_first.size() - 1;
+  if (input >= inputs) return DSA_ERR_INVALID_ARGUMENT;
+  if (e->part_first.empty()) { *first_stream = input; *count = 1; return DSA_OK; }
+  *first_stream = e->part_first[input]; *count = e->part_first[input + 1] - e->part_first[input];
+  return DSA_OK;
+}
+// Which part stream `stream` is, and the box of its points (part_points >= 1).
+dsa_status dsa_encoded_part_info(const dsa_encoded *e, uint32_t stream, dsa_part_info *out) {
+  if (!e || stream >= e->streams.size() || !out) return DSA_ERR_INVALID_ARGUMENT;
+  memset(out, 0, sizeof(*out));
+  if (!e->split) return set_err(e->ctx, DSA_ERR_INVALID_ARGUMENT, "this handle has no parts: encode with dsa_encode_split_sequential_batch and part_points >= 1");
+  if (e->status[stream] != DSA_OK) return set_err(e->ctx, (dsa_status)e->status[stream], "mesh %u: %s", stream, e->messages[stream].c_str());
+  *out = e->part_info[stream];
   return DSA_OK;
 }
 // The entry rows of attribute `attribute` of stream `mesh`: a sequential handle answers with the identity (with point_order = 1:

@@ -2092,6 +2092,42 @@ static void merge_points(const float *pos, uint32_t n, int bits, const Grid *gri
     row_entries[perm[e]] = (uint32_t)kept.size() - 1u;
   }
 }
+// The sorted order of a cloud in parts of at most part_points points (dsa_encode_split_sequential_batch, part_points >= 1): P =
+// ceil(n / part_points) parts, part p sorted entries [floor(p n / P), floor((p + 1) n / P)), in 64 bits -- 1 .. part_points points
+// each, sizes that differ by at most one.  part_points 0: one part.
+static inline uint64_t split_count(uint32_t n, uint32_t part_points) { return part_points ? ((uint64_t)n + part_points - 1u) / part_points : 1u; }
+static inline uint32_t split_bound(uint32_t n, uint64_t parts, uint64_t p) { return (uint32_t)(p * (uint64_t)n / parts); }
+static void split_parts(uint32_t n, uint32_t part_points, std::vector<std::pair<uint32_t, uint32_t>> &ranges) {
+  check(n > 0, "positions are missing");
+  const uint64_t parts = split_count(n, part_points);
+  ranges.resize((size_t)parts);
+  for (uint64_t p = 0; p < parts; ++p) ranges[(size_t)p] = {split_bound(n, parts, p), split_bound(n, parts, p + 1)};
+}
+// ... and what the device finds per part behind the sort (k_enc_part_bounds of dsa_encode_order.h): perm as point_order gives it,
+// and per part and component the minimum and maximum of the integers the position stream codes, qmin / qmax[3 p + c].
+static void part_boxes(const float *pos, uint32_t n, int bits, const Grid *grid, uint32_t part_points, std::vector<uint32_t> &perm,
+                       std::vector<std::pair<uint32_t, uint32_t>> &ranges, std::vector<int32_t> &qmin, std::vector<int32_t> &qmax) {
+  point_order(pos, n, bits, grid, perm);
+  split_parts(n, part_points, ranges);
+  PortableAttr a;
+  a.att_type = 0; a.nc = a.nc_out = 3; a.seq_type = 2; a.grid = grid;
+  quantize(pos, n, 3, bits, a);
+  qmin.assign(3 * ranges.size(), INT32_MAX); qmax.assign(3 * ranges.size(), INT32_MIN);
+  for (size_t p = 0; p < ranges.size(); ++p)
+    for (uint32_t e = ranges[p].first; e < ranges[p].second; ++e)
+      for (int c = 0; c < 3; ++c) {
+        const int32_t x = a.vals[(size_t)3 * perm[e] + c];
+        qmin[3 * p + c] = std::min(qmin[3 * p + c], x); qmax[3 * p + c] = std::max(qmax[3 * p + c], x);
+      }
+}
+// The float this library's decoder returns for integer q of a component on a grid (k_finalize, Dequantizer.cs:15-23): every step
+// rounded to float32, no fused multiply-add.
+static inline float dequantized(int32_t q, float origin, float range, int bits) {
+  volatile float delta = range / (float)(int32_t)((1u << bits) - 1u);
+  volatile float prod = (float)q * delta;
+  volatile float out = prod + origin;
+  return out;
+}
 
 // Point cloud, sequential (BASELINE config 1), positions only: int32 num_points, one attributes decoder, positions quantised,
 // Difference + Wrap in linear order, always through the symbol coder.

@@ -71,7 +71,8 @@ struct EncStream {                 // one per (mesh, attribute); lives in device
   uint32_t grid_mode;              // kind 0: not 0: qmin / qrange are a grid given by the host (the caller's, or its group's), k_enc_grid_quantize in place
                                    //   of k_enc_bounds and k_enc_quantize
   uint32_t grid_nonfinite, grid_off;      // its smallest row with a value that is not finite / whose integer leaves 0 .. max_q (the host sets ENC_GRID_NO_ROW)
-  uint32_t grid_pad;
+  uint32_t part;                   // not 0: the stream of a part behind the first of a split cloud (dsa_encode_order.h): src, vals and the quantiser's
+                                   //   floats are the first part's: k_enc_bounds / k_enc_quantize leave it alone, and so does k_enc_grid_quantize (its grid_mode is 0)
 };
 
 // The raw symbol scheme takes symbols below 2^18 (dsa_symbol_plan.h choose_scheme; symbol_stats of the host coder builds no
@@ -122,12 +123,25 @@ struct dsa_encoded {
   std::vector<std::pair<uint32_t, uint32_t>> linear;
   std::vector<std::vector<uint32_t>> order, cells;
   bool merged = false;
+  // dsa_encode_split_sequential_batch with part_points >= 1 (`split`).  While the chunks run the handle has one entry per input, and
+  // parts[input] holds the streams of its parts; flatten_parts then makes it one entry per STREAM: part_first[input] names an input's
+  // slots (one for a refused input), part_info[stream] says which part it is, and order[] keeps perm once per cloud, in the slot
+  // of its first part -- row_data serves every part its slice.
+  struct Part { std::vector<uint8_t> stream; dsa_part_info info; };
+  bool split = false;
+  std::vector<std::vector<Part>> parts;
+  std::vector<uint32_t> part_first;
+  std::vector<dsa_part_info> part_info;
+  void keep_parts(size_t n) { split = true; parts.resize(n); }
   void keep_rows(int kind, size_t n) { rows_kind = kind; if (kind == ROWS_TRACKED) rows.resize(n); if (kind == ROWS_LINEAR || kind == ROWS_ORDERED) linear.resize(n); if (kind == ROWS_ORDERED) order.resize(n); }
   void keep_cells(size_t n) { merged = true; cells.resize(n); }
   // attributes of stream `mesh` with entry rows; entries of attribute a; their rows (null: entry e is row e)
   uint32_t row_attributes(size_t mesh) const { return rows_kind == ROWS_TRACKED ? (uint32_t)rows[mesh].size() : linear[mesh].first; }
   uint32_t row_entries(size_t mesh, uint32_t a) const { return rows_kind == ROWS_TRACKED ? (uint32_t)rows[mesh][a].size() : linear[mesh].second; }
-  const uint32_t *row_data(size_t mesh, uint32_t a) const { return rows_kind == ROWS_TRACKED ? rows[mesh][a].data() : (rows_kind == ROWS_ORDERED ? order[mesh].data() : nullptr); }
+  const uint32_t *row_data(size_t mesh, uint32_t a) const {
+    if (rows_kind == ROWS_ORDERED && !part_info.empty()) return order[part_first[part_info[mesh].input]].data() + part_info[mesh].first_entry;
+    return rows_kind == ROWS_TRACKED ? rows[mesh][a].data() : (rows_kind == ROWS_ORDERED ? order[mesh].data() : nullptr);
+  }
   // mesh `from` of `part` into place `to`: stream, status, message and what it has of rows
   void take(size_t to, dsa_encoded &part, size_t from) {
     streams[to].swap(part.streams[from]); status[to] = part.status[from]; messages[to].swap(part.messages[from]);
@@ -135,6 +149,32 @@ struct dsa_encoded {
     if ((rows_kind == ROWS_LINEAR || rows_kind == ROWS_ORDERED) && from < part.linear.size()) linear[to] = part.linear[from];
     if (rows_kind == ROWS_ORDERED && from < part.order.size()) order[to].swap(part.order[from]);
     if (merged && from < part.cells.size()) cells[to].swap(part.cells[from]);
+    if (split && from < part.parts.size()) parts[to].swap(part.parts[from]);
+  }
+  void flatten_parts() {
+    const size_t n = streams.size();
+    part_first.assign(n + 1, 0);
+    for (size_t i = 0; i < n; ++i) {
+      if (status[i] == DSA_OK && parts[i].empty()) { status[i] = DSA_ERR_DEVICE; messages[i] = "the parts did not come back"; }
+      part_first[i + 1] = part_first[i] + (status[i] == DSA_OK ? (uint32_t)parts[i].size() : 1u);
+    }
+    const size_t total = part_first[n];
+    std::vector<std::vector<uint8_t>> s2(total);
+    std::vector<int32_t> st2(total, DSA_OK);
+    std::vector<std::string> m2(total);
+    std::vector<std::pair<uint32_t, uint32_t>> l2(total);
+    std::vector<std::vector<uint32_t>> o2(total);
+    dsa_part_info none;
+    memset(&none, 0, sizeof(none));
+    part_info.assign(total, none);
+    for (size_t i = 0; i < n; ++i) {
+      const size_t f = part_first[i];
+      if (status[i] != DSA_OK) { st2[f] = status[i]; m2[f].swap(messages[i]); part_info[f].input = (uint32_t)i; part_info[f].parts = 1; continue; }
+      o2[f].swap(order[i]);
+      for (size_t p = 0; p < parts[i].size(); ++p) { s2[f + p].swap(parts[i][p].stream); part_info[f + p] = parts[i][p].info; l2[f + p] = {linear[i].first, parts[i][p].info.num_points}; }
+    }
+    streams.swap(s2); status.swap(st2); messages.swap(m2); linear.swap(l2); order.swap(o2);
+    parts.clear();
   }
 };
 
@@ -179,6 +219,8 @@ struct EncRequest {
   bool point_order = false;                // dsa_encode_ordered_sequential_batch, point_order = 1: the points of every stream in Morton order (dsa_encode_order.h)
   bool merge_points = false;               // dsa_encode_merged_sequential_batch, merge_points = 1 (with point_order, point clouds): one point per cell of the position grid
   bool merged() const { return sequential && point_order && merge_points && !weld_sink; }
+  uint32_t part_points = 0;                // dsa_encode_split_sequential_batch, part_points >= 1 (with point_order, point clouds, no merge): the sorted order in parts of at most so many points
+  bool split() const { return sequential && point_order && !merge_points && part_points >= 1 && seq.geometry == 0 && !weld_sink; }
   int rows_kind() const { return weld_sink ? dsa_encoded::ROWS_NONE : (sequential ? (point_order ? dsa_encoded::ROWS_ORDERED : dsa_encoded::ROWS_LINEAR) : (track_rows ? dsa_encoded::ROWS_TRACKED : dsa_encoded::ROWS_NONE)); }
   dsa_encode_level_options level{};        // Edgebreaker streams
   dsa_encode_sequential_options seq{};     // sequential streams
@@ -241,7 +283,14 @@ struct EncLayout {
   uint64_t ord_at = 0, ord_tiles_at = 0;
   uint32_t ord_passes = 0;
   bool merge = false;                       // EncRequest::merge_points: the records say so, the streams read kept in place of perm
-  std::vector<uint32_t> ord_of_mesh;        // ... the record of mesh i of the chunk (DSA_INVALID: it has none)
+  std::vector<uint32_t> ord_of_mesh;        // merge or split: the record of mesh i of the chunk (DSA_INVALID: it has none)
+  // EncRequest::split: a record per part of every cloud (the parts of a cloud side by side, part_of_mesh[i] its first) and the
+  // (part, tile) pairs of all of them, both among the uploads
+  bool split = false;
+  std::vector<dsa::EncPart> parts;
+  std::vector<dsa::EncPartTile> part_tiles;
+  std::vector<uint32_t> part_of_mesh;
+  uint64_t parts_at = 0, part_tiles_at = 0;
 };
 
 static inline bool enc_multi_scheme(const synth::PortableAttr &a) { return a.seq_type != 3 && (a.prediction == 2 || a.prediction == 4); }
@@ -292,12 +341,16 @@ struct EncChunk {
   std::vector<std::vector<uint8_t>> rans, bits, flag_bits, crease;      // per stream; crease[4 s + j]: list j of stream s
   std::vector<std::vector<uint32_t>> entry_rows;                        // per stream (EncRequest::track_rows)
   std::vector<std::vector<uint32_t>> row_cells;                         // per stream, a cloud's first alone (EncRequest::merge_points): row_entries
+  std::vector<uint32_t> parts;                                          // EncRequest::split, per mesh: how many parts it is coded in (enc_check_sequential_mesh)
+  std::vector<std::vector<dsa::EncPart>> part_boxes;                    // ... per stream, a cloud's first alone: the records of its parts as k_enc_part_bounds left them
+  uint32_t num_parts(uint32_t i) const { return parts.empty() ? 1u : parts[i]; }
 
   EncChunk(const EncRequest &r, uint32_t b, uint32_t cnt, uint32_t bn) : rq(r), base(b), n(cnt), batch_n(bn), opt(enc_synth_options(r)), E(new (std::nothrow) dsa_encoded()), ins(cnt), plans(cnt), extras(cnt), extra_cap(cnt) {
     if (!E) return;                        // (the chunk function answers)
     E->streams.resize(n); E->status.assign(n, DSA_OK); E->messages.resize(n);
     E->keep_rows(r.rows_kind(), n);
     if (r.merged()) E->keep_cells(n);
+    if (r.split()) { E->keep_parts(n); parts.assign(n, 1u); }
   }
   const dsa_mesh_attr_input &attr(uint32_t i) const { return welded.empty() ? rq.attr(base + i) : welded[i]; }
   const dsa_mesh_corner_input &corner(uint32_t i) const { return attr(i).mesh; }
@@ -548,6 +601,14 @@ static void enc_check_sequential_mesh(EncChunk &ck, uint32_t i) {
   if (!why.empty()) return ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, why);
   synth::plan_sequential_attributes(in, mo, ck.plans[i].atts);
   enc_extra_caps(ck, i);
+  if (!ck.rq.split()) return;
+  const uint64_t parts = synth::split_count(m.num_vertices, ck.rq.part_points);
+  if (parts > DSA_ENCODE_MAX_PARTS) {
+    char buf[160];
+    snprintf(buf, sizeof(buf), "part_points %u cuts the cloud's n = %u points into %llu parts: at most %u (DSA_ENCODE_MAX_PARTS)", ck.rq.part_points, m.num_vertices, (unsigned long long)parts, DSA_ENCODE_MAX_PARTS);
+    return ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, buf);
+  }
+  ck.parts[i] = (uint32_t)parts;
 }
 
 // ---- the regions of a stream, shared by both layouts
@@ -572,8 +633,9 @@ static void enc_table_regions(dsa::EncStream &S, EncArena &A) {
   S.plan_order = A.take(4ull * table_cap); S.plan_tmp = A.take(4ull * table_cap);
 }
 // What the kernels write of a value stream of up to `cap` entries; hist_cap: of an integer extra by the values present, 0: by the bits.
-static void enc_value_stream_regions(dsa::EncStream &S, uint32_t cap, uint32_t hist_cap, EncArena &A) {
-  S.vals = A.take(4ull * S.rows * S.nc);
+// vals: not 0: where the values lie already (a part behind the first of a split cloud).
+static void enc_value_stream_regions(dsa::EncStream &S, uint32_t cap, uint32_t hist_cap, EncArena &A, uint64_t vals = 0) {
+  S.vals = vals ? vals : A.take(4ull * S.rows * S.nc);
   S.d = S.linear ? S.vals : A.take(4ull * cap * S.nc);   // linear order: the values are the entries
   S.syms = A.take(4ull * cap * S.nc); S.bl = A.take(cap);
   S.hist_cap = hist_cap ? hist_cap : (1u << S.bits) + 2u;        // zig-zag of a wrapped correction / a positive octahedral correction fits
@@ -600,7 +662,7 @@ static void enc_layout_begin(EncChunk &ck, uint32_t more_streams_of_valence, uin
   for (uint32_t i = 0; i < ck.n; ++i) {
     L.any_valence = L.any_valence || ck.valence_of(i);
     for (size_t k = 0; ck.good(i) && k < ck.plans[i].atts.size(); ++k) { const synth::PortableAttr &a = ck.plans[i].atts[k]; L.any_grid = L.any_grid || (a.seq_type == 2 && a.grid && a.grid->mode != 0); }
-    L.first_stream[i + 1] = L.first_stream[i] + (ck.good(i) ? (uint32_t)ck.plans[i].atts.size() + more_streams + (ck.valence_of(i) ? more_streams_of_valence : 0u) : 0u);
+    L.first_stream[i + 1] = L.first_stream[i] + (ck.good(i) ? ((uint32_t)ck.plans[i].atts.size() + more_streams + (ck.valence_of(i) ? more_streams_of_valence : 0u)) * ck.num_parts(i) : 0u);
   }
   dsa::EncStream zero;
   memset(&zero, 0, sizeof(zero));
@@ -805,12 +867,15 @@ static void enc_layout(EncChunk &ck) {
 // regions among what the kernels write).  Without it nothing here moves.
 // EncRequest::merge_points: the map is the other row buffer, where k_enc_merge_compact leaves the kept rows, and a region of 4
 // bytes per point takes row_entries; every region stays sized for the points that came in, k_enc_merge_scan lowers nv below them.
+// EncRequest::split: a cloud of P parts has P sets of stream records (stream s0 + p * attributes + k: attribute k of part p) on one
+// set of source values and integers; the EncPart records and their (part, tile) pairs go up beside the sort's.
 static void enc_layout_sequential(EncChunk &ck) {
   EncLayout &L = ck.L;
   const bool is_mesh = ck.rq.seq.geometry == 1, compressed = is_mesh && ck.rq.seq.compress_connectivity == 1, ordered = ck.rq.point_order;
-  const bool merge = ordered && !is_mesh && ck.rq.merge_points;
-  L.merge = merge;
-  if (merge) L.ord_of_mesh.assign(ck.n, DSA_INVALID);
+  const bool merge = ordered && !is_mesh && ck.rq.merge_points, split = ck.rq.split();
+  L.merge = merge; L.split = split;
+  if (merge || split) L.ord_of_mesh.assign(ck.n, DSA_INVALID);
+  if (split) L.part_of_mesh.assign(ck.n, DSA_INVALID);
   EncArena A;
   A.log = ck.region_log;
   enc_layout_begin(ck, 0, compressed ? 1 : 0);
@@ -828,8 +893,20 @@ static void enc_layout_sequential(EncChunk &ck) {
       dsa::EncOrder O;
       memset(&O, 0, sizeof(O));
       O.n = V; O.tiles = (V + ORD_TILE - 1u) / ORD_TILE; O.bits = (uint32_t)ck.opt.pos_bits;
-      if (merge) { O.merge = 1; O.stream0 = s0; O.streams = (uint32_t)atts.size(); L.ord_of_mesh[i] = (uint32_t)L.ord.size(); }
+      if (merge) { O.merge = 1; O.stream0 = s0; O.streams = (uint32_t)atts.size(); }
+      if (merge || split) L.ord_of_mesh[i] = (uint32_t)L.ord.size();
       for (uint32_t t = 0; t < O.tiles; ++t) L.ord_tiles.push_back({(uint32_t)L.ord.size(), t});
+      if (split) {                                             // the parts of the cloud: their sizes need nothing of the device
+        L.part_of_mesh[i] = (uint32_t)L.parts.size();
+        for (uint32_t p = 0, np = ck.num_parts(i); p < np; ++p) {
+          dsa::EncPart P;
+          memset(&P, 0, sizeof(P));
+          P.cloud = (uint32_t)L.ord.size(); P.lo = synth::split_bound(V, np, p); P.n = synth::split_bound(V, np, p + 1u) - P.lo;
+          for (int c = 0; c < 3; ++c) { P.qmin[c] = INT32_MAX; P.qmax[c] = INT32_MIN; }
+          for (uint32_t t = 0, nt = (P.n + ORD_TILE - 1u) / ORD_TILE; t < nt; ++t) L.part_tiles.push_back({(uint32_t)L.parts.size(), t});
+          L.parts.push_back(P);
+        }
+      }
       L.ord.push_back(O);
     }
     if (!compressed) continue;
@@ -847,6 +924,10 @@ static void enc_layout_sequential(EncChunk &ck) {
     L.ord_at = A.put(L.uploads, L.ord.data(), sizeof(dsa::EncOrder) * L.ord.size(), false);
     L.ord_tiles_at = A.put(L.uploads, L.ord_tiles.data(), sizeof(dsa::EncOrderTile) * L.ord_tiles.size(), false);
   }
+  if (!L.parts.empty()) {
+    L.parts_at = A.put(L.uploads, L.parts.data(), sizeof(dsa::EncPart) * L.parts.size(), false);
+    L.part_tiles_at = A.put(L.uploads, L.part_tiles.data(), sizeof(dsa::EncPartTile) * L.part_tiles.size(), false);
+  }
   L.input_bytes = A.cur;
   for (uint32_t i = 0, o = 0; i < ck.n; ++i) {
     if (!ck.good(i)) continue;
@@ -859,6 +940,20 @@ static void enc_layout_sequential(EncChunk &ck) {
       if (merge) O.cells = A.take(4ull * V);
       for (uint32_t k = 0; k < na; ++k) L.streams[s0 + k].e2v = O.row[(L.ord_passes + (merge ? 1u : 0u)) & 1u];
     }
+    if (split) {
+      // a set of records per part: the first part's with the part's entries -- a slice of the sorted rows -- and regions of the
+      // part's size; the values are the cloud's, quantised once
+      const dsa::EncOrder &O = L.ord[o - 1];
+      for (uint32_t p = 0, np = ck.num_parts(i); p < np; ++p) {
+        const dsa::EncPart &P = L.parts[L.part_of_mesh[i] + p];
+        for (uint32_t k = 0; k < na; ++k) {
+          dsa::EncStream &S = L.streams[s0 + p * na + k];
+          if (p) { S = L.streams[s0 + k]; S.part = 1; S.grid_mode = 0; }      // (grid_mode 0: k_enc_grid_quantize passes it by too; the header's floats are the first part's)
+          S.nv = P.n; S.e2v = O.row[L.ord_passes & 1u] + 4ull * P.lo;
+          enc_value_stream_regions(S, P.n, ck.hist_cap_of(i, k), A, p ? L.streams[s0 + k].vals : 0);
+        }
+      }
+    } else
     for (uint32_t k = 0; k < na; ++k) enc_value_stream_regions(L.streams[s0 + k], V, ck.hist_cap_of(i, k), A);
     if (ordered) L.ord[o - 1].vals = L.streams[s0].vals;      // (the positions are attribute 0: their stream is the mesh's first)
     L.max_rows = std::max(L.max_rows, V);

@@ -57,6 +57,21 @@
 // tests/hostcheck/encmerge_host.cpp runs the serial forms against it, tests/test_gpu_encode_merge.py the ballots and shuffles.
 // gfx950, hipcc -O3 (VGPR / SGPR / LDS bytes per block): k_enc_merge_heads 12 / 24 / 0, scan 16 / 29 / 0, compact 16 / 27 / 0; no
 // scratch, no spills, 8 waves per SIMD.
+//
+// dsa_encode_split_sequential_batch with part_points = N >= 1 (point clouds, no merge): the sorted order of a cloud cut into P =
+// ceil(n / N) parts, part p sorted entries [floor(p n / P), floor((p + 1) n / P)), each coded as a stream of its own.  Sizes are the
+// host's to know before anything runs: the layout gives every part its own set of EncStream records whose e2v is the cloud's sorted
+// row buffer at 4 lo_p and whose nv is the part's size, on the cloud's one `src` and `vals` (quantised once: EncStream::part), and
+// k_enc_gather and everything behind it run per part as they are.  One step of this file's own, behind the last scatter pass:
+//   k_enc_part_bounds     a wave per (part, tile) pair of a list the layout builds, a tile up to ORD_TILE consecutive entries of one
+//                         part, so that parts of one point and of a million share a launch: per component the minimum and maximum of
+//                         vals[3 row[e] + c] over the tile, a wave reduction by shuffles, then an integer atomicMin / atomicMax of
+//                         lane 0 into the part's record (EncPart, which the layout initialises).  Minimum and maximum commute: the
+//                         result is a function of the input alone, and here too no atomic decides a place.  No loop waits on
+//                         another block.
+// The records leave the device among the chunk's packed pieces, as perm does.  The host coder's twin is synth::split_parts /
+// synth::part_boxes; tests/hostcheck/encsplit_host.cpp runs the serial form against it, tests/test_gpu_encode_split.py the shuffles.
+// gfx950, hipcc -O3 (VGPR / SGPR / LDS bytes per block): k_enc_part_bounds 18 / 22 / 0; no scratch, no spills, 8 waves per SIMD.
 #pragma once
 #include <stdint.h>
 
@@ -82,6 +97,13 @@ struct EncOrder {                  // one per cloud of the chunk; in the arena, 
   uint32_t m, pad;                 // OUTPUT (merge): occupied cells
 };
 struct EncOrderTile { uint32_t cloud, tile; };
+struct EncPart {                   // one per part of a split cloud, the parts of a cloud side by side; in the arena, among the uploads
+  uint32_t cloud;                  // its cloud among the chunk's EncOrder records
+  uint32_t lo, n;                  // sorted entries lo .. lo + n of the cloud
+  int32_t qmin[3], qmax[3];        // OUTPUT per component over vals of the part's rows (the layout sets INT32_MAX / INT32_MIN)
+  uint32_t pad;
+};
+struct EncPartTile { uint32_t part, tile; };
 
 static inline uint32_t enc_order_passes(uint32_t bits) { return (3u * bits + 7u) / 8u; }
 
@@ -340,6 +362,49 @@ static inline void enc_merge_launch(Launch &&launch, uint8_t *arena, EncOrder *c
   launch(k_enc_merge_heads, nt, 1u, (uint32_t)WAVE, arena, (const EncOrder *)clouds, tiles, nt, passes);
   launch(k_enc_merge_scan<Stream>, nc, 1u, (uint32_t)WAVE, arena, clouds, nc, streams, ns);
   launch(k_enc_merge_compact, nt, 1u, (uint32_t)WAVE, arena, (const EncOrder *)clouds, tiles, nt, passes);
+}
+
+// ---- part_points (the header comment has the contract): grid = the chunk's (part, tile) pairs, one wave each
+__global__ __launch_bounds__(WAVE) void k_enc_part_bounds(uint8_t *arena, const EncOrder *clouds, uint32_t nc, EncPart *parts, uint32_t np, const EncPartTile *tiles, uint32_t nt,
+                                                          uint32_t passes) {
+  if (blockIdx.x >= nt) return;
+  const EncPartTile T = tiles[blockIdx.x];
+  if (T.part >= np) return;
+  EncPart &P = parts[T.part];
+  if (P.cloud >= nc) return;
+  const EncOrder &O = clouds[P.cloud];
+  const uint32_t t0 = T.tile * ORD_TILE;
+  if (t0 >= P.n || P.lo > O.n || P.n > O.n - P.lo) return;       // (never by the layout: the comparisons keep a fault elsewhere inside the cloud's buffers)
+  const int32_t *vals = (const int32_t *)(arena + O.vals);
+  const uint32_t *row = (const uint32_t *)(arena + O.row[passes & 1u]);
+  const uint32_t lane = threadIdx.x, e0 = P.lo + t0, end = P.lo + (P.n - t0 < ORD_TILE ? P.n : t0 + ORD_TILE);
+  int32_t mn[3] = {0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF}, mx[3] = {(int32_t)0x80000000, (int32_t)0x80000000, (int32_t)0x80000000};
+#if defined(__HIPCC__)
+  for (uint32_t e = e0 + lane; e < end; e += WAVE) {
+    const uint32_t r = row[e];
+    if (r >= O.n) continue;
+    for (uint32_t c = 0; c < 3u; ++c) { const int32_t x = vals[3ull * r + c]; mn[c] = x < mn[c] ? x : mn[c]; mx[c] = x > mx[c] ? x : mx[c]; }
+  }
+  for (uint32_t c = 0; c < 3u; ++c)
+    for (int d = WAVE / 2; d >= 1; d >>= 1) {
+      const int32_t a = __shfl_xor(mn[c], d, WAVE), b = __shfl_xor(mx[c], d, WAVE);
+      mn[c] = a < mn[c] ? a : mn[c]; mx[c] = b > mx[c] ? b : mx[c];
+    }
+  if (lane == 0) for (uint32_t c = 0; c < 3u; ++c) { atomicMin(&P.qmin[c], mn[c]); atomicMax(&P.qmax[c], mx[c]); }
+#else       // (as k_enc_order_hist: lane 0 takes the tile's entries in their order)
+  if (lane != 0) return;
+  for (uint32_t e = e0; e < end; ++e)
+    for (uint32_t c = 0; c < 3u; ++c) { const int32_t x = vals[3ull * row[e] + c]; mn[c] = x < mn[c] ? x : mn[c]; mx[c] = x > mx[c] ? x : mx[c]; }
+  for (uint32_t c = 0; c < 3u; ++c) { P.qmin[c] = mn[c] < P.qmin[c] ? mn[c] : P.qmin[c]; P.qmax[c] = mx[c] > P.qmax[c] ? mx[c] : P.qmax[c]; }
+#endif
+}
+
+// The part boxes behind enc_order_launch: `parts` the chunk's np EncPart records, `tiles` its nt (part, tile) pairs.
+template <class Launch>
+static inline void enc_part_launch(Launch &&launch, uint8_t *arena, const EncOrder *clouds, uint32_t nc, EncPart *parts, uint32_t np, const EncPartTile *tiles, uint32_t nt,
+                                   uint32_t passes) {
+  if (nc == 0 || np == 0 || nt == 0) return;
+  launch(k_enc_part_bounds, nt, 1u, (uint32_t)WAVE, arena, clouds, nc, parts, np, tiles, nt, passes);
 }
 
 }  // namespace dsa

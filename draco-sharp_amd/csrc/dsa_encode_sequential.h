@@ -13,12 +13,46 @@
 //                                (dsa_encode_order.h) -- k_enc_gather then puts every attribute in it, the faces go through its inverse
 //          k_enc_merge_*         dsa_encode_merged_sequential_batch, merge_points = 1 (point clouds): one point per cell behind the sort;
 //                                nv of the cloud's streams falls on the device, the host reads it from the records that come back
+//          k_enc_part_bounds     dsa_encode_split_sequential_batch, part_points >= 1 (point clouds): a set of stream records per part of the
+//                                sorted order, and the box of every part's position integers; the host writes a stream per part
 //          k_enc_seq_indices     compressed indices: symbols and their statistics (dsa_encode_seqidx.h)
 //          k_enc_plan / k_enc_rans   every stream, the index stream as a list whose symbols are given (kind 3)
 //   host   stream layout (synth::write_sequential_stream)
 // The bytes are the CPU coder's (synth::encode_sequential; tests/test_gpu_encode_sequential.py compares them).
 #pragma once
 
+// part_points: the streams of the parts of cloud i -- each a point cloud of its own, its quantised attributes on the cloud's grid
+// (the first part's records hold the floats) -- and what the handle says of every part
+static void enc_write_parts(EncChunk &ck, uint32_t i) {
+  const EncLayout &L = ck.L;
+  const std::vector<synth::PortableAttr> &atts = ck.plans[i].atts;
+  const uint32_t s0 = L.first_stream[i], na = (uint32_t)atts.size(), np = ck.num_parts(i), V = ck.mesh(i).num_vertices;
+  if (ck.entry_rows[s0].size() != V || ck.part_boxes[s0].size() != np) return ck.refuse(i, DSA_ERR_DEVICE, "the point order and the part boxes did not come back");
+  const dsa::EncStream &pos = L.streams[s0];
+  std::vector<dsa_encoded::Part> parts(np);
+  for (uint32_t p = 0; p < np; ++p) {
+    const dsa::EncPart &P = ck.part_boxes[s0][p], &laid = L.parts[L.part_of_mesh[i] + p];
+    const uint32_t sp = s0 + p * na;
+    if (P.lo != laid.lo || P.n != laid.n || P.n == 0 || P.qmin[0] > P.qmax[0]) return ck.refuse(i, DSA_ERR_DEVICE, "the point order and the part boxes did not come back");
+    synth::ByteWriter w;
+    try {
+      synth::write_sequential_stream(w, false, P.n, 0, false, atts, [](synth::ByteWriter &) {},
+        [&](synth::ByteWriter &bw, size_t k) { enc_write_attribute_values(bw, ck, sp + (uint32_t)k, 0); },
+        [&](synth::ByteWriter &bw, size_t k) { enc_write_transform(bw, L.streams[s0 + k]); });
+    } catch (const std::exception &e) { return ck.refuse(i, DSA_ERR_INVALID_DATA, e.what()); }
+    parts[p].stream.swap(w.d);
+    dsa_part_info &info = parts[p].info;
+    memset(&info, 0, sizeof(info));
+    info.input = ck.base + i; info.part = p; info.parts = np; info.first_entry = P.lo; info.num_points = P.n; info.position_bits = pos.bits;
+    for (int c = 0; c < 3; ++c) {
+      info.qmin[c] = P.qmin[c]; info.qmax[c] = P.qmax[c];
+      info.box_min[c] = synth::dequantized(P.qmin[c], pos.qmin[c], pos.qrange, (int)pos.bits);
+      info.box_max[c] = synth::dequantized(P.qmax[c], pos.qmin[c], pos.qrange, (int)pos.bits);
+    }
+  }
+  ck.E->parts[i].swap(parts);
+  ck.E->order[i].swap(ck.entry_rows[s0]);
+}
 // the stream layout of a chunk (threads over meshes)
 static void enc_stage_sequential_streams(EncChunk &ck) {
   const EncLayout &L = ck.L;
@@ -27,6 +61,7 @@ static void enc_stage_sequential_streams(EncChunk &ck) {
     if (!ck.good(i)) return;
     for (uint32_t s = L.first_stream[i]; s < L.first_stream[i + 1]; ++s)
       if (L.streams[s].overflow) return ck.refuse(i, DSA_ERR_INVALID_DATA, "entropy coding failed");
+    if (L.split) return enc_write_parts(ck, i);
     const std::vector<synth::PortableAttr> &atts = ck.plans[i].atts;
     const uint32_t s0 = L.first_stream[i], si = s0 + (uint32_t)atts.size();
     const dsa_mesh_input &m = ck.mesh(i);

@@ -72,7 +72,15 @@ class Config:
     the positions the voxel is range / (2^position_bits - 1).  EncodedStreams.entry_rows(i) returns kept (for every attribute),
     EncodedStreams.row_entries(i) the entry of the cell of every input row (what averages colours or counts points per cell).
     Point clouds only, under a sequential config with point_order=POINT_ORDER_MORTON: the points of a cell lie side by side in
-    that order, and merging the points of a mesh would collapse its faces."""
+    that order, and merging the points of a mesh would collapse its faces.
+
+    part_points (dsa_encode_split_sequential_batch): 0 one stream per cloud; N >= 1 the Morton order of every point cloud cut into
+    P = ceil(n / N) parts of at most N points, part p sorted entries [floor(p n / P), floor((p + 1) n / P)), each an ordinary
+    point-cloud stream of its own on the cloud's one quantisation grid -- streams that encode and decode side by side, fit
+    together without cracks, and come with a box each.  The EncodedStreams then runs over STREAMS (inputs in order, the parts of
+    an input in order): parts(i) is the range of input i's streams, part_info(s) says which part stream s is and gives its box,
+    entry_rows(s) its slice of the order.  Point clouds only, under a sequential config with point_order=POINT_ORDER_MORTON and
+    without merge_points."""
 
     EDGEBREAKER_METHODS = (0, 2, -1)
     POSITION_PREDICTIONS = (0, 1)
@@ -87,7 +95,7 @@ class Config:
     def __init__(self, position_bits=11, texcoord_bits=10, normal_bits=8, speed=5, single_connectivity=False,
                  symbol_scheme=-1, position_prediction=1, texcoord_prediction=1, edgebreaker_method=0, normal_prediction=0,
                  encoding_method=1, compress_connectivity=False, multi_parallelogram=0, traversal_method=0, repair_topology=False, weld_points=False,
-                 repair_seams=False, weld_attributes=False, track_rows=False, point_order=0, merge_points=0):
+                 repair_seams=False, weld_attributes=False, track_rows=False, point_order=0, merge_points=0, part_points=0):
         for name, value, legal in (("encoding_method", encoding_method, self.ENCODING_METHODS),
                                    ("edgebreaker_method", edgebreaker_method, self.EDGEBREAKER_METHODS),
                                    ("position_prediction", position_prediction, self.POSITION_PREDICTIONS),
@@ -126,6 +134,11 @@ class Config:
         self.merge_points = merge_points
         if self.merge_points != 0 and not (self.sequential and self.point_order == native.POINT_ORDER_MORTON):
             raise ValueError("merge_points keeps one point per cell of the position grid: it needs a sequential config (encoding_method 0) with point_order=POINT_ORDER_MORTON")
+        self.part_points = int(part_points)
+        if self.part_points < 0 or self.part_points > 2**31 - 1:
+            raise ValueError("part_points %r: 0 (one stream per cloud) or the largest number of points of a part" % (part_points,))
+        if self.part_points != 0 and (not (self.sequential and self.point_order == native.POINT_ORDER_MORTON) or self.merge_points != 0):
+            raise ValueError("part_points cuts the Morton order of a point cloud into parts: it needs a sequential config (encoding_method 0) with point_order=POINT_ORDER_MORTON and no merge_points")
 
     @property
     def sequential(self):
@@ -152,6 +165,13 @@ class Config:
         native.lib().dsa_encode_default_merge_options(C.byref(o))
         o.order = self._native_order(geometry)
         o.merge_points = self.merge_points
+        return o
+
+    def _native_split(self, geometry):
+        o = native.EncodeSplitOptions()
+        native.lib().dsa_encode_default_split_options(C.byref(o))
+        o.merge = self._native_merge(geometry)
+        o.part_points = self.part_points
         return o
 
     @property
@@ -542,6 +562,25 @@ class EncodedStreams:
             raise ValueError("the encoded batch was closed")
         return _row_entries(self._ctx, self._h, i + len(self) if i < 0 else i)
 
+    def parts(self, i):
+        """The streams of input i of the encode as a range: with Config(part_points=N) its parts in order, else range(i, i + 1);
+        dsa_encoded_parts."""
+        if self._h is None:
+            raise ValueError("the encoded batch was closed")
+        first, count = C.c_uint32(), C.c_uint32()
+        st = native.lib().dsa_encoded_parts(self._h, i, C.byref(first), C.byref(count))
+        if st != 0:
+            _raise(st, "no input %r" % (i,))
+        return range(first.value, first.value + count.value)
+
+    def part_info(self, s):
+        """Of stream s of an encode with Config(part_points=N) a native.PartInfo: input, part, parts, first_entry, num_points,
+        position_bits, qmin / qmax (the position integers the stream codes, per component) and box_min / box_max (the floats the
+        decoder returns for them: bit for bit the box of the part's decoded positions); dsa_encoded_part_info."""
+        if self._h is None:
+            raise ValueError("the encoded batch was closed")
+        return _part_info(self._ctx, self._h, s + len(self) if s < 0 else s)
+
     def close(self):
         """Releases the library's buffers (streams already taken stay valid)."""
         if self._h is not None:
@@ -568,6 +607,9 @@ class _EncodedHandle:
 
     def row_entries(self, i):
         return _row_entries(self._ctx, self._h, i)
+
+    def part_info(self, s):
+        return _part_info(self._ctx, self._h, s)
 
     def close(self):
         if self._h is not None:
@@ -610,6 +652,15 @@ def _row_entries(ctx, handle, i):
     if st != 0:
         _raise(st, ctx.error())
     return cells
+
+
+def _part_info(ctx, handle, s):
+    """dsa_encoded_part_info of stream s."""
+    info = native.PartInfo()
+    st = native.lib().dsa_encoded_part_info(handle, s, C.byref(info))
+    if st != 0:
+        _raise(st, ctx.error())
+    return info
 
 
 class WeldedMaps:
@@ -655,6 +706,8 @@ class DracoEncoder:
             raise ValueError("attributes given per corner need Edgebreaker connectivity (encoding_method 1): a sequential stream has one value per point")
         if getattr(config, "point_order", 0) != 0 and not (clouds or config.sequential):
             raise ValueError("point_order needs a sequential stream (encoding_method 0, or point clouds): Edgebreaker orders its own entries")
+        if getattr(config, "part_points", 0) != 0 and not clouds:
+            raise ValueError("part_points takes point clouds (PointCloudData): a part of a mesh would need its faces cut")
         if getattr(config, "merge_points", 0) != 0 and not clouds:
             raise ValueError("merge_points takes point clouds (PointCloudData): merging the points of a mesh would collapse its faces and lose its seams")
         weld = getattr(config, "weld_points", False)
@@ -714,7 +767,12 @@ class DracoEncoder:
         n = len(meshes)
         arr, grids, keep = _native_meshes(meshes)
         h = C.c_void_p()
-        if getattr(config, "merge_points", 0) != 0:     # (the widest call only when its option is set)
+        if getattr(config, "part_points", 0) != 0:      # (the widest call only when its option is set: the handle then has a slot per stream)
+            opt = config._native_split(geometry)
+            st = native.lib().dsa_encode_split_sequential_batch(ctx._h, n, arr, grids, C.byref(opt), C.byref(h))
+            if st == 0:
+                n = native.lib().dsa_encoded_size(h)
+        elif getattr(config, "merge_points", 0) != 0:   # (the widest call only when its option is set)
             opt = config._native_merge(geometry)
             st = native.lib().dsa_encode_merged_sequential_batch(ctx._h, n, arr, grids, C.byref(opt), C.byref(h))
         elif getattr(config, "point_order", 0) != 0:    # (the plain case keeps arriving through the call it always took)

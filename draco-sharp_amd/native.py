@@ -42,6 +42,7 @@ EXPORTS = [
     "dsa_encode_default_rows_options", "dsa_encode_rows_batch", "dsa_encoded_entry_rows", "dsa_encoded_attributes",
     "dsa_encode_default_order_options", "dsa_encode_ordered_sequential_batch",
     "dsa_encode_default_merge_options", "dsa_encode_merged_sequential_batch", "dsa_encoded_row_entries",
+    "dsa_encode_default_split_options", "dsa_encode_split_sequential_batch", "dsa_encoded_parts", "dsa_encoded_part_info",
     "dsa_encoded_size", "dsa_encoded_stream", "dsa_encoded_free",
     "dsa_pool_create", "dsa_pool_destroy", "dsa_pool_size", "dsa_pool_last_error", "dsa_pool_decode", "dsa_pool_job_locate",
     "dsa_pool_job_chunks", "dsa_pool_job_free", "dsa_pool_plan",
@@ -100,6 +101,23 @@ class EncodeMergeOptions(C.Structure):
     cell of the position grid of a point cloud; the handle keeps the kept rows and the entry of every input row:
     dsa_encoded_entry_rows, dsa_encoded_row_entries)."""
     _fields_ = [("order", EncodeOrderOptions), ("merge_points", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+ENCODE_MAX_PARTS = 65536                            # DSA_ENCODE_MAX_PARTS: parts of one cloud
+
+
+class EncodeSplitOptions(C.Structure):
+    """dsa_encode_split_options: the options of dsa_encode_merged_sequential_batch, and part_points (N >= 1: the Morton order of
+    every point cloud in parts of at most N points, a stream each; the handle has a slot per stream: dsa_encoded_parts,
+    dsa_encoded_part_info)."""
+    _fields_ = [("merge", EncodeMergeOptions), ("part_points", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+class PartInfo(C.Structure):
+    """dsa_part_info: which part of which input a stream of a split encode is, and the box of its points."""
+    _fields_ = [("input", C.c_uint32), ("part", C.c_uint32), ("parts", C.c_uint32), ("first_entry", C.c_uint32), ("num_points", C.c_uint32),
+                ("position_bits", C.c_uint32), ("qmin", C.c_int32 * 3), ("qmax", C.c_int32 * 3), ("box_min", C.c_float * 3),
+                ("box_max", C.c_float * 3), ("reserved", C.c_uint32 * 2)]
 
 
 class MeshInput(C.Structure):
@@ -365,6 +383,12 @@ def lib():
             L.dsa_encode_default_merge_options.restype = None
             L.dsa_encode_merged_sequential_batch.argtypes = [vp, u32, C.POINTER(MeshAttrInput), C.POINTER(MeshGrids), C.POINTER(EncodeMergeOptions), C.POINTER(vp)]
             L.dsa_encoded_row_entries.argtypes = [vp, u32, vp, C.c_size_t, C.POINTER(u32)]
+        if hasattr(L, "dsa_encode_split_sequential_batch"):
+            L.dsa_encode_default_split_options.argtypes = [C.POINTER(EncodeSplitOptions)]
+            L.dsa_encode_default_split_options.restype = None
+            L.dsa_encode_split_sequential_batch.argtypes = [vp, u32, C.POINTER(MeshAttrInput), C.POINTER(MeshGrids), C.POINTER(EncodeSplitOptions), C.POINTER(vp)]
+            L.dsa_encoded_parts.argtypes = [vp, u32, C.POINTER(u32), C.POINTER(u32)]
+            L.dsa_encoded_part_info.argtypes = [vp, u32, C.POINTER(PartInfo)]
         L.dsa_encoded_size.restype = u32
         L.dsa_encoded_size.argtypes = [vp]
         L.dsa_encoded_stream.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(C.c_size_t)]

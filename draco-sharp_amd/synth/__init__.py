@@ -235,6 +235,8 @@ def lib():
                                         C.POINTER(GridsInput), C.POINTER(Options), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
         L.synth_point_order.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(Grid), C.c_void_p]
         L.synth_merge_points.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(Grid), C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]
+        L.synth_split_parts.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.synth_part_boxes.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(Grid), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.synth_shared_grid.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_uint32, C.c_int, C.POINTER(Grid)]
         L.synth_free.argtypes = [C.c_void_p]
         L.synth_make_mesh.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_uint32),
@@ -604,6 +606,74 @@ def encode_merged(pos, normals=None, uvs=None, generic=None, extra=None, opt=Non
     kept, cells, kw = merged_arguments(pos, normals, uvs, generic, extra, opt, pos_grid, uv_grid)
     p = kw.pop("pos")
     return encode_grid(p, None, form=0, geometry=0, **kw), kept, cells
+
+
+def split_parts(n, part_points):
+    """The sorted order of a cloud of n points in parts of at most part_points points: an (P, 2) uint32 array of [lo, hi) with P =
+    ceil(n / part_points) and part p = [floor(p n / P), floor((p + 1) n / P)) -- every part 1 .. part_points points, sizes that
+    differ by at most one.  part_points 0: one part.  The ranges of dsa_encode_split_sequential_batch."""
+    L = lib()
+    parts = C.c_uint64()
+    if L.synth_split_parts(int(n), int(part_points), None, 0, C.byref(parts)):
+        raise RuntimeError(_err())
+    ranges = np.zeros((parts.value, 2), np.uint32)
+    if L.synth_split_parts(int(n), int(part_points), ranges.ctypes.data, len(ranges), C.byref(parts)):
+        raise RuntimeError(_err())
+    return ranges
+
+
+def part_boxes(pos, bits, part_points, grid=None):
+    """(perm, ranges, qmin, qmax) of the parts of the points `pos` (N, 3): perm = point_order(pos, bits, grid), ranges =
+    split_parts(N, part_points), and qmin / qmax (P, 3) int32 the minimum and maximum per component of the integers the position
+    stream codes for rows perm[lo:hi]."""
+    L = lib()
+    pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+    ranges = split_parts(len(pos), part_points)
+    perm = np.zeros(len(pos), np.uint32)
+    qmin, qmax = np.zeros((len(ranges), 3), np.int32), np.zeros((len(ranges), 3), np.int32)
+    if L.synth_part_boxes(pos.ctypes.data, len(pos), int(bits), None if grid is None else C.byref(grid), int(part_points), perm.ctypes.data,
+                          qmin.ctypes.data, qmax.ctypes.data):
+        raise RuntimeError(_err())
+    return perm, ranges, qmin, qmax
+
+
+def split_arguments(pos, normals=None, uvs=None, generic=None, extra=None, opt=None, pos_grid=None, uv_grid=None, part_points=0):
+    """Per part of a split cloud the arguments of the plain call that writes its stream: [(rows, qmin, qmax, kwargs for
+    encode_grid(form=0, geometry=0))] -- every per-point array at [rows] = perm[lo:hi], every quantised attribute on an explicit
+    grid equal to the bounds of ALL the cloud's rows (the grid given, where one was)."""
+    opt = opt or options()
+    perm, ranges, qmin, qmax = part_boxes(pos, opt.pos_bits, part_points, pos_grid)
+    pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+    pg = pos_grid if pos_grid is not None else bounds_grid(pos)
+    ug = uv_grid if uv_grid is not None or uvs is None else bounds_grid(np.asarray(uvs, np.float32).reshape(-1, 2))
+    extras = []
+    for e in (extra or []):
+        e = e if isinstance(e, Extra) else Extra(e)
+        g = e.grid
+        if g is None and e.values.dtype == np.dtype(np.float32):
+            g = bounds_grid(e.values)
+        extras.append((e, g))
+    out = []
+    for p, (lo, hi) in enumerate(ranges):
+        rows = perm[lo:hi]
+        take = lambda a, nc: None if a is None else np.ascontiguousarray(np.asarray(a).reshape(-1, nc)[rows])      # noqa: E731
+        ex = [Extra(e.values[rows], attribute_type=e.attribute_type, normalized=bool(e.normalized), unique_id=e.unique_id,
+                    quantization_bits=e.quantization_bits, data_type=e.data_type, num_components=e.num_components, grid=g) for e, g in extras]
+        kw = dict(pos=pos[rows], normals=take(normals, 3), uvs=take(uvs, 2), generic=None if generic is None else np.asarray(generic)[rows],
+                  extra=ex, opt=opt, pos_grid=pg, uv_grid=ug)
+        out.append((rows, qmin[p], qmax[p], kw))
+    return out
+
+
+def encode_split(pos, normals=None, uvs=None, generic=None, extra=None, opt=None, pos_grid=None, uv_grid=None, part_points=0):
+    """The Morton order of a point cloud in parts of at most part_points points, each coded as a point cloud of its own on the
+    cloud's grid: [(stream, rows, qmin, qmax)], split_arguments coded.  What dsa_encode_split_sequential_batch with part_points >= 1
+    must write, and what its handle must report for every part."""
+    out = []
+    for rows, qmin, qmax, kw in split_arguments(pos, normals, uvs, generic, extra, opt, pos_grid, uv_grid, part_points):
+        p = kw.pop("pos")
+        out.append((encode_grid(p, None, form=0, geometry=0, **kw), rows, qmin, qmax))
+    return out
 
 
 def entry_rows(pos, faces=None, normals=None, uvs=None, generic=None, extra=None, opt=None, form=1, normal_corners=None, uv_corners=None,

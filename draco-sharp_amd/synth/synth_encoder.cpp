@@ -524,6 +524,33 @@ int synth_merge_points(const float *pos, uint32_t n, int bits, const synth::Grid
     return 0;
   } catch (const std::exception &e) { snprintf(g_err, sizeof(g_err), "%s", e.what()); return 1; }
 }
+// The sorted order of n points in parts of at most part_points (dsa_encode_host.h split_parts): *parts of them, and where `ranges`
+// is given (room for 2 * capacity) lo and hi of every part.
+int synth_split_parts(uint32_t n, uint32_t part_points, uint32_t *ranges, uint64_t capacity, uint64_t *parts) {
+  try {
+    synth::check(n > 0, "positions are missing");
+    *parts = synth::split_count(n, part_points);
+    if (!ranges) return 0;
+    synth::check(capacity >= *parts, "split_parts: no room for the ranges");
+    std::vector<std::pair<uint32_t, uint32_t>> r;
+    synth::split_parts(n, part_points, r);
+    for (size_t p = 0; p < r.size(); ++p) { ranges[2 * p] = r[p].first; ranges[2 * p + 1] = r[p].second; }
+    return 0;
+  } catch (const std::exception &e) { snprintf(g_err, sizeof(g_err), "%s", e.what()); return 1; }
+}
+// ... with the order and the box of every part's position integers (part_boxes): perm[n], qmin / qmax[3 * parts].
+int synth_part_boxes(const float *pos, uint32_t n, int bits, const synth::Grid *grid, uint32_t part_points, uint32_t *perm, int32_t *qmin, int32_t *qmax) {
+  try {
+    std::vector<uint32_t> pm;
+    std::vector<std::pair<uint32_t, uint32_t>> r;
+    std::vector<int32_t> mn, mx;
+    synth::part_boxes(pos, n, bits, grid, part_points, pm, r, mn, mx);
+    memcpy(perm, pm.data(), 4 * pm.size());
+    memcpy(qmin, mn.data(), 4 * mn.size());
+    memcpy(qmax, mx.data(), 4 * mx.size());
+    return 0;
+  } catch (const std::exception &e) { snprintf(g_err, sizeof(g_err), "%s", e.what()); return 1; }
+}
 void synth_free(uint8_t *p) { free(p); }
 
 // Procedural mesh: returns counts; call once with NULL outputs to size, then again to fill.

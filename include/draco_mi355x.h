@@ -738,6 +738,63 @@ dsa_status dsa_encode_merged_sequential_batch(dsa_context *ctx, uint32_t n, cons
 /* Of stream `mesh` of a handle of dsa_encode_merged_sequential_batch with merge_points = 1: row_entries, uint32[n], one per input
  * row (above).  dst NULL: the count alone; capacity in elements. */
 dsa_status dsa_encoded_row_entries(const dsa_encoded *encoded, uint32_t mesh, uint32_t *dst, size_t capacity, uint32_t *count);
+/* dsa_encode_merged_sequential_batch that cuts the Morton order of a point cloud into parts of bounded size, each a stream of its
+ * own.  Both directions of the library code a stream on one wave, which suits a batch of many small streams and is the wrong shape
+ * for one cloud of millions of points; a run of consecutive entries of the Morton order is a spatially compact set of points, and a
+ * sequential stream of it is an ordinary Draco 2.2 point cloud.  The parts of a cloud share its one quantisation grid, so they
+ * encode and decode side by side, fit together without cracks, and each comes with a box to cull or stream by.
+ *   part_points = N >= 1 (taken only with point_order = 1, geometry 0 and merge_points = 0): with perm the rows in ascending
+ *   (key, row) as documented for point_order = 1 and n the cloud's points, P = ceil(n / N) and part p is sorted entries
+ *   [floor(p n / P), floor((p + 1) n / P)), computed in 64 bits: every part has 1 .. N points, sizes differ by at most one, and the
+ *   result is a function of the input alone.  Part p is coded as a point cloud of its own; entry j of EVERY attribute carries row
+ *   perm[lo_p + j].  Bounds and quantisers run once per cloud, in front of the sort, so every quantised attribute of every part
+ *   (positions, the UV set, float attributes of the list) keeps the bounds of ALL the cloud's rows, or the grid that was given or
+ *   shared: the stream of part p is byte for byte that of dsa_encode_grid_sequential_batch (geometry 0) for positions[perm[lo:hi]],
+ *   normals[...], every listed attribute[...] with every quantised attribute on an explicit grid equal to the bounds of all its rows
+ *   (origin = the per-component minima, range = the largest extent, 1 where that is 0).  With P = 1 that is the stream of the
+ *   ordered call.  Integer attributes and octahedral normals carry no bounds; wrap bounds, symbol statistics, scheme choice and
+ *   tables are each part's own.
+ *   The handle: dsa_encoded_size is the number of STREAMS -- the inputs in call order, the parts of one input in order p.  An input
+ *   that is refused fails alone with the status and text it has today and occupies one stream slot, which returns that status.
+ *   dsa_encoded_parts names the slots of an input (on a handle of any other call: first_stream = input, count = 1).
+ *   dsa_encoded_entry_rows(stream, a) returns perm[lo_p:hi_p] for every attribute (perm is kept once per cloud),
+ *   dsa_batch_source_rows works with the handle as with an ordered one (encoded_mesh[i] names a stream), dsa_encoded_row_entries
+ *   stays refused.  dsa_encoded_part_info fills dsa_part_info: qmin / qmax are, per component, the minimum and maximum of the
+ *   position integers the part's stream codes (found on the device behind the sort: k_enc_part_bounds, dsa_encode_order.h), box_min /
+ *   box_max the floats this library's decoder returns for them on the part's grid -- float(q) * (range / float(2^position_bits - 1))
+ *   + origin, every step rounded to float32 -- and since that is monotone in the integer, bit for bit the minimum and maximum of the
+ *   part's decoded positions.  On a handle made without part_points >= 1 it returns DSA_ERR_INVALID_ARGUMENT and dsa_last_error
+ *   names part_points.
+ *   A cloud with ceil(n / N) > DSA_ENCODE_MAX_PARTS fails alone with DSA_ERR_INVALID_ARGUMENT; the message names part_points, n and
+ *   the limit.
+ *   part_points = 0: the bytes, the messages, the work, the rows and the handle shape of dsa_encode_merged_sequential_batch.
+ * Fails the call with DSA_ERR_INVALID_ARGUMENT before any mesh is looked at, dsa_last_error naming the field: part_points < 0;
+ * part_points >= 1 with point_order != 1 (parts are runs of the Morton order); with geometry != 0 (a part of a mesh would need its
+ * faces cut); with merge_points = 1; a non-zero reserved word.  Refusals of the nested option structs keep their own words.
+ * Not built: parts with merge_points = 1 (the number of kept points, and so of parts, is known only on the device; the merged call
+ * already lowers nv there and the same step could size parts -- a follow-up), parts of sequential meshes, parts of the caller's
+ * order (point_order = 0), a joined vertex-array layout of the parts on the decode side.
+ * Added after ABI 4 without changing it: callers detect the feature by the symbol dsa_encode_split_sequential_batch. */
+#define DSA_ENCODE_MAX_PARTS 65536u        /* parts of one cloud */
+typedef struct dsa_encode_split_options {
+  dsa_encode_merge_options merge;          /* as for dsa_encode_merged_sequential_batch, same legal values */
+  int32_t part_points;                     /* 0 (default): one stream per cloud; N >= 1: parts of at most N points */
+  int32_t reserved[7];                     /* must be zero */
+} dsa_encode_split_options;
+void dsa_encode_default_split_options(dsa_encode_split_options *options);
+dsa_status dsa_encode_split_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids,
+                                             const dsa_encode_split_options *options, dsa_encoded **out);
+/* The stream slots of input `input` of the call that made the handle: first_stream .. first_stream + count. */
+dsa_status dsa_encoded_parts(const dsa_encoded *encoded, uint32_t input, uint32_t *first_stream, uint32_t *count);
+typedef struct dsa_part_info {
+  uint32_t input, part, parts;             /* which cloud of the call, which of its parts, how many it has */
+  uint32_t first_entry, num_points;        /* the part is sorted entries first_entry .. first_entry + num_points of the cloud */
+  uint32_t position_bits;
+  int32_t qmin[3], qmax[3];                /* per component, over the position integers the part's stream codes */
+  float box_min[3], box_max[3];            /* what the decoder returns for qmin / qmax */
+  uint32_t reserved[2];                    /* zero */
+} dsa_part_info;
+dsa_status dsa_encoded_part_info(const dsa_encoded *encoded, uint32_t stream, dsa_part_info *out);
 /* The rows of a decoded batch per POINT: for every mesh of `batch` and every attribute a of its stream,
  *     rows[a][p] = entry_rows[a][map[a][p]]          (map: the decoder's point -> entry map, dsa_batch_device_point_map)
  * -- which row of the arrays given to the encoder point p carries, gathered on the device (k_source_rows) so that neither the maps
