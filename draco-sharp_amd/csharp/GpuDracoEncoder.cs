@@ -88,6 +88,12 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
     // PartInfo(s) says which part stream s is and gives the box of its points, EntryRows(s) its slice of the order.  Needs
     // PointOrder 1 and MergePoints 0; point clouds only: a part of a mesh would need its faces cut, and an encode of meshes throws.
     public int PartPoints { get; set; }
+    // PartCells (dsa_encode_cell_parts_sequential_batch): parts WITH MergePoints.  0 no parts; N >= 1 the kept order of every point
+    // cloud -- one point per quantisation cell, m of them, a number only the device knows -- cut into ceil(m / N) parts of at most N
+    // kept points, sized on the device.  Encode returns one array per STREAM as with PartPoints; Parts(i), PartInfo(s) (FirstEntry /
+    // NumPoints in kept order) and EntryRows(s) serve the parts, RowEntries(Parts(i).First) the cloud's row entries in the global
+    // kept order.  Needs PointOrder 1 and MergePoints 1, and PartPoints 0; point clouds only.
+    public int PartCells { get; set; }
     public struct PartBox
     {
         public uint Input, Part, Parts, FirstEntry, NumPoints, PositionBits;
@@ -204,9 +210,9 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
                     inputs[i].Faces = (uint*)Pin(faces, pins);
                 }
             }
-            if (PartPoints != 0)
+            if (PartPoints != 0 || PartCells != 0)
             {
-                if (geometry != 0) throw new ArgumentException("PartPoints takes point clouds: a part of a mesh would need its faces cut");
+                if (geometry != 0) throw new ArgumentException((PartCells != 0 ? "PartCells" : "PartPoints") + " takes point clouds: a part of a mesh would need its faces cut");
                 NativeMethods.dsa_encode_default_split_options(out var po);
                 po.Merge.Order.Sequential = so;
                 po.Merge.Order.PointOrder = PointOrder;
@@ -214,6 +220,15 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
                 po.PartPoints = PartPoints;
                 var ain = new DsaMeshAttrInput[items.Count];
                 for (int i = 0; i < items.Count; ++i) { ain[i].Mesh.Mesh = inputs[i]; Extras(items[i], null, (uint)items[i].PointsCount, ref ain[i], pins); }
+                if (PartCells != 0)             // (the widest call only when its option is set)
+                {
+                    NativeMethods.dsa_encode_default_cell_parts_options(out var co);
+                    co.Split = po;
+                    co.PartCells = PartCells;
+                    fixed (DsaMeshAttrInput* p = ain)
+                        NativeMethods.Check(NativeMethods.dsa_encode_cell_parts_sequential_batch(_ctx, (uint)items.Count, p, null, in co, out encoded), _ctx, "dsa_encode_cell_parts_sequential_batch");
+                }
+                else
                 fixed (DsaMeshAttrInput* p = ain)
                     NativeMethods.Check(NativeMethods.dsa_encode_split_sequential_batch(_ctx, (uint)items.Count, p, null, in po, out encoded), _ctx, "dsa_encode_split_sequential_batch");
                 int streams = (int)NativeMethods.dsa_encoded_size(encoded);
@@ -230,6 +245,18 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
                                             BoxMin = new[] { pi.BoxMin[0], pi.BoxMin[1], pi.BoxMin[2] }, BoxMax = new[] { pi.BoxMax[0], pi.BoxMax[1], pi.BoxMax[2] } };
                 }
                 _parts = parts; _partInfo = info;
+                if (PartCells != 0)             // the row entries of every cloud, in the global kept order: kept with its first stream
+                {
+                    _rowEntries = new uint[streams][];
+                    for (int i = 0; i < items.Count; ++i)
+                    {
+                        uint s = parts[i].First;
+                        NativeMethods.Check(NativeMethods.dsa_encoded_row_entries(encoded, s, null, 0, out uint rows), _ctx, $"stream {s}");
+                        _rowEntries[s] = new uint[rows];
+                        fixed (uint* r = _rowEntries[s])
+                            NativeMethods.Check(NativeMethods.dsa_encoded_row_entries(encoded, s, r, (nuint)rows, out rows), _ctx, $"stream {s}");
+                    }
+                }
                 return split;
             }
             if (MergePoints != 0)
@@ -294,6 +321,7 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
             for (int i = 0; i < meshes.Count; ++i) items[i] = meshes[i];
             return EncodeSequential(items, config, 1);
         }
+        if (PartCells != 0) throw new ArgumentException("PartCells takes point clouds: a part of a mesh would need its faces cut");
         if (PartPoints != 0) throw new ArgumentException("PartPoints takes point clouds: a part of a mesh would need its faces cut");
         if (MergePoints != 0) throw new ArgumentException("MergePoints takes point clouds: merging the points of a mesh would collapse its faces and lose its seams");
         if (PointOrder != 0) throw new ArgumentException("PointOrder needs a sequential stream (EncodingMethod SequentialEncoding, or point clouds): Edgebreaker orders its own entries");

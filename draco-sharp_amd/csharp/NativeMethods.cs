@@ -257,6 +257,15 @@ internal unsafe struct DsaEncodeSplitOptions
     public fixed int Reserved[7];   // zero
 }
 
+// dsa_encode_cell_parts_options (dsa_encode_cell_parts_sequential_batch)
+[StructLayout(LayoutKind.Sequential)]
+internal unsafe struct DsaEncodeCellPartsOptions
+{
+    public DsaEncodeSplitOptions Split;
+    public int PartCells;           // 0: the request of the split call; N >= 1: the KEPT order of MergePoints in parts of at most N points (point clouds, PointOrder 1, MergePoints 1, PartPoints 0)
+    public fixed int Reserved[7];   // zero
+}
+
 // dsa_part_info (dsa_encoded_part_info)
 [StructLayout(LayoutKind.Sequential)]
 internal unsafe struct DsaPartInfo
@@ -404,6 +413,8 @@ internal static unsafe partial class NativeMethods
     [DllImport(Lib)] internal static extern DsaStatus dsa_encoded_row_entries(IntPtr encoded, uint mesh, uint* dst, nuint capacity, out uint count);
     [DllImport(Lib)] internal static extern void dsa_encode_default_split_options(out DsaEncodeSplitOptions options);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_split_sequential_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, in DsaEncodeSplitOptions options, out IntPtr encoded);
+    [DllImport(Lib)] internal static extern void dsa_encode_default_cell_parts_options(out DsaEncodeCellPartsOptions options);
+    [DllImport(Lib)] internal static extern DsaStatus dsa_encode_cell_parts_sequential_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, in DsaEncodeCellPartsOptions options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encoded_parts(IntPtr encoded, uint input, out uint firstStream, out uint count);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encoded_part_info(IntPtr encoded, uint stream, out DsaPartInfo info);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_rows_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, DsaMeshAttributeCorners* corners, in DsaEncodeRowsOptions options, out IntPtr encoded);

@@ -29,6 +29,8 @@
 //                                                the heads of the runs of equal keys behind the sort; nv of the cloud's streams falls on the device
 //                              k_enc_part_bounds dsa_encode_split_sequential_batch, part_points >= 1: the sorted order in parts, a set of stream
 //                                                records each; the box of every part's position integers behind the sort
+//                              k_enc_part_cells  dsa_encode_cell_parts_sequential_batch, part_cells >= 1: both -- the KEPT order in parts, whose
+//                                                number and sizes follow from m on the device: part slots, sized behind k_enc_merge_scan
 //         (dsa_encode_layout.h) the request of an entry point, the state of a chunk, the per-mesh checks and plans, the arena layout
 // Every entry point fills an EncRequest and calls encode_request; a chunk of it goes through the stages of encode_chunk (or of
 // encode_sequential_chunk, dsa_encode_sequential.h) on a lane.
@@ -666,11 +668,15 @@ static dsa_status enc_code_streams(dsa_context *ctx, EncLane &lane, EncChunk &ck
   // merge_points the kept rows, nv of them as the records say, and a sixth piece, row_entries of all its input rows)
   // (part_points: the fifth piece of a cloud's first stream is the whole permutation, whose slices its parts' streams read, the
   // sixth the records of its parts with their boxes)
-  const bool track = !ck.L.rows_of_stream.empty(), ordered = !ck.L.ord.empty(), merge = ck.L.merge, split = ck.L.split;
-  const size_t per = merge || split ? 6 : (track || ordered ? 5 : 4);
+  // (part_cells: both -- the fifth piece the kept rows of the whole cloud, m of them as the sizes of its slots add up, the sixth the
+  // records of its live parts, a seventh row_entries; an empty slot -- an empty list by then, ENC_PART_SIZED in its record -- has no
+  // piece at all)
+  const bool track = !ck.L.rows_of_stream.empty(), ordered = !ck.L.ord.empty(), merge = ck.L.merge, split = ck.L.split, cell_parts = ck.L.cell_parts;
+  const size_t per = merge && split ? 7 : (merge || split ? 6 : (track || ordered ? 5 : 4)), cells_piece = split ? 6 : 5;
   std::vector<dsa::PackItem> items;
   for (uint32_t s = 0; s < ns; ++s) {
     if (hs[s].overflow || E->status[stream_mesh[s]] != DSA_OK) continue;
+    if ((hs[s].part & dsa::ENC_PART_SIZED) != 0u && hs[s].nv == 0u) continue;
     if (hs[s].kind == 1 && hs[s].prediction == 6) hs[s].num_flags = hs[s].nv;
     items.push_back({hs[s].out_rans, 0, hs[s].rans_len, s});
     items.push_back({hs[s].out_bits, 0, hs[s].bits_len, s});
@@ -682,8 +688,10 @@ static dsa_status enc_code_streams(dsa_context *ctx, EncLane &lane, EncChunk &ck
       items.push_back({R ? R->out : 0, 0, R ? 4u * std::min(hs[s].nv, R->cap) : 0u, s});
     } else if (ordered) {
       const bool first = s == ck.L.first_stream[stream_mesh[s]];
-      items.push_back({hs[s].e2v, 0, first ? 4u * (split ? ck.L.ord[ck.L.ord_of_mesh[stream_mesh[s]]].n : hs[s].nv) : 0u, s});
-      if (split) items.push_back({ck.L.parts_at + sizeof(dsa::EncPart) * ck.L.part_of_mesh[stream_mesh[s]], 0, first ? (uint32_t)sizeof(dsa::EncPart) * ck.num_parts((uint32_t)stream_mesh[s]) : 0u, s});
+      uint32_t order_rows = split ? ck.L.ord[ck.L.ord_of_mesh[stream_mesh[s]]].n : hs[s].nv, part_records = ck.num_parts((uint32_t)stream_mesh[s]);
+      if (cell_parts && first) part_records = ck.live_parts((uint32_t)stream_mesh[s], &order_rows);
+      items.push_back({hs[s].e2v, 0, first ? 4u * order_rows : 0u, s});
+      if (split) items.push_back({ck.L.parts_at + sizeof(dsa::EncPart) * ck.L.part_of_mesh[stream_mesh[s]], 0, first ? (uint32_t)sizeof(dsa::EncPart) * part_records : 0u, s});
       if (merge) { const dsa::EncOrder &O = ck.L.ord[ck.L.ord_of_mesh[stream_mesh[s]]]; items.push_back({O.cells, 0, first ? 4u * O.n : 0u, s}); }
     }
   }
@@ -693,7 +701,7 @@ static dsa_status enc_code_streams(dsa_context *ctx, EncLane &lane, EncChunk &ck
     const size_t k = per * (size_t)m;
     const uint32_t s = items[k].pad;
     if (split && items[k + 5].len) { const dsa::EncPart *r = (const dsa::EncPart *)(host + items[k + 5].packed_off); ck.part_boxes[s].assign(r, r + items[k + 5].len / sizeof(dsa::EncPart)); }
-    else if (per == 6 && items[k + 5].len) { const uint32_t *r = (const uint32_t *)(host + items[k + 5].packed_off); ck.row_cells[s].assign(r, r + items[k + 5].len / 4u); }
+    if (merge && items[k + cells_piece].len) { const uint32_t *r = (const uint32_t *)(host + items[k + cells_piece].packed_off); ck.row_cells[s].assign(r, r + items[k + cells_piece].len / 4u); }
     if (per >= 5 && items[k + 4].len) { const uint32_t *r = (const uint32_t *)(host + items[k + 4].packed_off); ck.entry_rows[s].assign(r, r + items[k + 4].len / 4u); }
     if (items[k].len) rans[s].assign(host + items[k].packed_off, host + items[k].packed_off + items[k].len);
     if (items[k + 1].len) bits[s].assign(host + items[k + 1].packed_off, host + items[k + 1].packed_off + items[k + 1].len);
@@ -1186,6 +1194,11 @@ static dsa_status enc_stage_attributes(dsa_context *ctx, EncLane &lane, EncChunk
       ENC_TRY(hipGetLastError());
       if (order_timing) { ENC_TRY(hipStreamSynchronize(st)); order_lap("point merge"); }
     }
+    if (L.cell_parts) {        // part_cells: the kept order in parts -- k_enc_merge_scan has left m, the sizes of the part slots follow from it on the device
+      dsa::enc_part_cells_launch([st](auto kernel, uint32_t grid_x, uint32_t grid_y, uint32_t block, auto... args) { hipLaunchKernelGGL(kernel, dim3(grid_x, grid_y), dim3(block), 0, st, args...); },
+                                 (dsa::EncOrder *)(arena + L.ord_at), (uint32_t)L.ord.size(), (dsa::EncPart *)(arena + L.parts_at), (uint32_t)L.parts.size(), d_streams, ns, L.ord_passes);
+      ENC_TRY(hipGetLastError());
+    }
     if (L.split) {             // part_points: the box of every part's position integers, behind the sort (the parts' streams read their slices of it as they are)
       dsa::enc_part_launch([st](auto kernel, uint32_t grid_x, uint32_t grid_y, uint32_t block, auto... args) { hipLaunchKernelGGL(kernel, dim3(grid_x, grid_y), dim3(block), 0, st, args...); },
                            arena, (const dsa::EncOrder *)(arena + L.ord_at), (uint32_t)L.ord.size(), (dsa::EncPart *)(arena + L.parts_at), (uint32_t)L.parts.size(),
@@ -1482,6 +1495,17 @@ static dsa_status enc_check_options(dsa_context *ctx, const dsa_encode_split_opt
   ENC_RESERVED(o, 7, "dsa_encode_split_options");
   return enc_check_options(ctx, o.merge, null_argument);
 }
+// ... or the kept order of merge_points in parts of bounded size, sized on the device (dsa_encode_order.h)
+static dsa_status enc_check_options(dsa_context *ctx, const dsa_encode_cell_parts_options &o, bool null_argument) {
+  const dsa_encode_merge_options &m = o.split.merge;
+  if (o.part_cells < 0) ENC_REFUSE("part_cells %d: 0 (the request of dsa_encode_split_sequential_batch) or the largest number of kept points of a part, 1 and above", (int)o.part_cells);
+  if (o.part_cells >= 1 && m.merge_points != 1) ENC_REFUSE("part_cells %d needs merge_points 1 (it was %d): parts of the points as they came in are part_points", (int)o.part_cells, (int)m.merge_points);
+  if (o.part_cells >= 1 && m.order.point_order != 1) ENC_REFUSE("part_cells %d needs point_order 1 (it was %d): parts are runs of the Morton order", (int)o.part_cells, (int)m.order.point_order);
+  if (o.part_cells >= 1 && m.order.sequential.geometry != 0) ENC_REFUSE("part_cells %d needs geometry 0 (it was %d): a part of a mesh would need its faces cut", (int)o.part_cells, (int)m.order.sequential.geometry);
+  if (o.part_cells >= 1 && o.split.part_points != 0) ENC_REFUSE("part_cells %d with part_points %d: one of the two sizes the parts", (int)o.part_cells, (int)o.split.part_points);
+  ENC_RESERVED(o, 7, "dsa_encode_cell_parts_options");
+  return enc_check_options(ctx, o.split, null_argument);
+}
 #undef ENC_RESERVED
 #undef ENC_REFUSE
 
@@ -1750,14 +1774,21 @@ static dsa_status encode_edgebreaker(dsa_context *ctx, uint32_t n, const dsa_mes
   rq.track_rows = w.track_rows == 1;
   return encode_checked(ctx, rq, grids, o.grid.repair.topology == 1, out);
 }
-static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_split_options &s, dsa_encoded **out) {
-  if (enc_check_options(ctx, s, !ctx || !out || (n && !meshes)) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_cell_parts_options &c, dsa_encoded **out) {
+  if (enc_check_options(ctx, c, !ctx || !out || (n && !meshes)) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+  const dsa_encode_split_options &s = c.split;
   const dsa_encode_merge_options &m = s.merge;
   const dsa_encode_order_options &o = m.order;
   EncRequest rq;
   rq.n = n; rq.meshes = meshes; rq.sequential = true;
-  rq.seq = o.sequential; rq.point_order = o.point_order == 1; rq.merge_points = m.merge_points == 1; rq.part_points = (uint32_t)s.part_points;
+  rq.seq = o.sequential; rq.point_order = o.point_order == 1; rq.merge_points = m.merge_points == 1; rq.part_points = (uint32_t)s.part_points; rq.part_cells = (uint32_t)c.part_cells;
   return encode_checked(ctx, rq, grids, false, out);
+}
+static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_split_options &s, dsa_encoded **out) {
+  dsa_encode_cell_parts_options c;
+  dsa_encode_default_cell_parts_options(&c);
+  c.split = s;
+  return encode_sequential(ctx, n, meshes, grids, c, out);
 }
 static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_merge_options &m, dsa_encoded **out) {
   dsa_encode_split_options s;
@@ -1825,6 +1856,11 @@ void dsa_encode_default_split_options(dsa_encode_split_options *o) {
   if (!o) return;
   memset(o, 0, sizeof(*o));
   dsa_encode_default_merge_options(&o->merge);
+}
+void dsa_encode_default_cell_parts_options(dsa_encode_cell_parts_options *o) {
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  dsa_encode_default_split_options(&o->split);
 }
 void dsa_encode_default_repair_options(dsa_encode_repair_options *o) {
   if (!o) return;
@@ -1946,6 +1982,11 @@ dsa_status dsa_encode_merged_sequential_batch(dsa_context *ctx, uint32_t n, cons
 dsa_status dsa_encode_split_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_split_options *options, dsa_encoded **out) {
   DSA_GUARD(ctx, [&] { dsa_encode_split_options o; dsa_encode_default_split_options(&o); if (options) o = *options; return encode_sequential(ctx, n, meshes, grids, o, out); }());
 }
+// ... or, with merge_points = 1, the KEPT order in parts of at most part_cells points, sized on the device (part_cells >= 1:
+// k_enc_part_cells, dsa_encode_order.h); part_cells = 0 is the very request of the call above.
+dsa_status dsa_encode_cell_parts_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_cell_parts_options *options, dsa_encoded **out) {
+  DSA_GUARD(ctx, [&] { dsa_encode_cell_parts_options o; dsa_encode_default_cell_parts_options(&o); if (options) o = *options; return encode_sequential(ctx, n, meshes, grids, o, out); }());
+}
 
 struct dsa_welded {
   dsa_context *ctx = nullptr;
@@ -2018,6 +2059,9 @@ dsa_status dsa_encoded_row_entries(const dsa_encoded *e, uint32_t mesh, uint32_t
   *count = 0;
   if (e->status[mesh] != DSA_OK) return set_err(e->ctx, (dsa_status)e->status[mesh], "mesh %u: %s", mesh, e->messages[mesh].c_str());
   if (!e->merged) return set_err(e->ctx, DSA_ERR_INVALID_ARGUMENT, "the row entries of this handle were not kept: encode with dsa_encode_merged_sequential_batch and merge_points = 1");
+  if (!e->part_info.empty() && e->part_first[e->part_info[mesh].input] != mesh)      // (part_cells: row_entries are the cloud's, kept with its first part)
+    return set_err(e->ctx, DSA_ERR_INVALID_ARGUMENT, "stream %u is part %u of input %u: the row entries of a cloud in parts are kept once, ask its first stream, %u", mesh, e->part_info[mesh].part,
+                   e->part_info[mesh].input, e->part_first[e->part_info[mesh].input]);
   const std::vector<uint32_t> &cells = e->cells[mesh];
   *count = (uint32_t)cells.size();
   if (!dst) return DSA_OK;

@@ -2120,6 +2120,24 @@ static void part_boxes(const float *pos, uint32_t n, int bits, const Grid *grid,
         qmin[3 * p + c] = std::min(qmin[3 * p + c], x); qmax[3 * p + c] = std::max(qmax[3 * p + c], x);
       }
 }
+// The KEPT order of a cloud in parts of at most part_cells points (dsa_encode_cell_parts_sequential_batch, part_cells >= 1; the
+// device sizes them in k_enc_part_cells of dsa_encode_order.h): merge_points, then split_parts over the m kept entries in place of
+// the n rows, and per part and component the minimum and maximum of the position integers of rows kept[lo:hi], qmin / qmax[3 p + c].
+static void cell_parts(const float *pos, uint32_t n, int bits, const Grid *grid, uint32_t part_cells, std::vector<uint32_t> &kept, std::vector<uint32_t> &row_entries,
+                       std::vector<std::pair<uint32_t, uint32_t>> &ranges, std::vector<int32_t> &qmin, std::vector<int32_t> &qmax) {
+  merge_points(pos, n, bits, grid, kept, row_entries);
+  split_parts((uint32_t)kept.size(), part_cells, ranges);
+  PortableAttr a;
+  a.att_type = 0; a.nc = a.nc_out = 3; a.seq_type = 2; a.grid = grid;
+  quantize(pos, n, 3, bits, a);
+  qmin.assign(3 * ranges.size(), INT32_MAX); qmax.assign(3 * ranges.size(), INT32_MIN);
+  for (size_t p = 0; p < ranges.size(); ++p)
+    for (uint32_t e = ranges[p].first; e < ranges[p].second; ++e)
+      for (int c = 0; c < 3; ++c) {
+        const int32_t x = a.vals[(size_t)3 * kept[e] + c];
+        qmin[3 * p + c] = std::min(qmin[3 * p + c], x); qmax[3 * p + c] = std::max(qmax[3 * p + c], x);
+      }
+}
 // The float this library's decoder returns for integer q of a component on a grid (k_finalize, Dequantizer.cs:15-23): every step
 // rounded to float32, no fused multiply-add.
 static inline float dequantized(int32_t q, float origin, float range, int bits) {

@@ -73,7 +73,16 @@ struct EncStream {                 // one per (mesh, attribute); lives in device
   uint32_t grid_nonfinite, grid_off;      // its smallest row with a value that is not finite / whose integer leaves 0 .. max_q (the host sets ENC_GRID_NO_ROW)
   uint32_t part;                   // not 0: the stream of a part behind the first of a split cloud (dsa_encode_order.h): src, vals and the quantiser's
                                    //   floats are the first part's: k_enc_bounds / k_enc_quantize leave it alone, and so does k_enc_grid_quantize (its grid_mode is 0)
+                                   //   ENC_PART_SIZED set: a part slot whose nv the device decides (k_enc_part_cells), 0 where the cloud has fewer parts
 };
+// EncStream::part of a part behind the first: ENC_PART_BEHIND, and with sizes of the device's ENC_PART_SIZED as well -- the one
+// layout in which a value stream can be empty (a zero-point cloud is refused at the door).  Such a slot must be passed by: no
+// kernel and no host step may touch its regions, and it has no piece among the downloads.  k_enc_part_cells therefore turns the
+// records of an empty slot into what every step passes by already, an empty list (kind 3, nv 0: k_enc_gather and k_enc_corr return
+// on the kind, k_enc_plan, k_enc_rans and the host's plans on the empty list), so that not one instruction of those kernels
+// changes: a test of this flag in the prologue of k_enc_rans moved its serial loop and cost the merged call of a 1 Mi-point stream
+// 8 %.  The flag itself tells the piece packer, on the host, to emit nothing for the record.
+static const uint32_t ENC_PART_BEHIND = 1u, ENC_PART_SIZED = 2u;
 
 // The raw symbol scheme takes symbols below 2^18 (dsa_symbol_plan.h choose_scheme; symbol_stats of the host coder builds no
 // histogram of values beyond): no stream's histogram is larger than this, and a stream whose histogram has this size may hold
@@ -163,7 +172,7 @@ struct dsa_encoded {
     std::vector<int32_t> st2(total, DSA_OK);
     std::vector<std::string> m2(total);
     std::vector<std::pair<uint32_t, uint32_t>> l2(total);
-    std::vector<std::vector<uint32_t>> o2(total);
+    std::vector<std::vector<uint32_t>> o2(total), c2(merged ? total : 0);      // (part_cells: row_entries once per cloud, in the slot of its first part)
     dsa_part_info none;
     memset(&none, 0, sizeof(none));
     part_info.assign(total, none);
@@ -171,9 +180,11 @@ struct dsa_encoded {
       const size_t f = part_first[i];
       if (status[i] != DSA_OK) { st2[f] = status[i]; m2[f].swap(messages[i]); part_info[f].input = (uint32_t)i; part_info[f].parts = 1; continue; }
       o2[f].swap(order[i]);
+      if (merged) c2[f].swap(cells[i]);
       for (size_t p = 0; p < parts[i].size(); ++p) { s2[f + p].swap(parts[i][p].stream); part_info[f + p] = parts[i][p].info; l2[f + p] = {linear[i].first, parts[i][p].info.num_points}; }
     }
     streams.swap(s2); status.swap(st2); messages.swap(m2); linear.swap(l2); order.swap(o2);
+    if (merged) cells.swap(c2);
     parts.clear();
   }
 };
@@ -220,7 +231,10 @@ struct EncRequest {
   bool merge_points = false;               // dsa_encode_merged_sequential_batch, merge_points = 1 (with point_order, point clouds): one point per cell of the position grid
   bool merged() const { return sequential && point_order && merge_points && !weld_sink; }
   uint32_t part_points = 0;                // dsa_encode_split_sequential_batch, part_points >= 1 (with point_order, point clouds, no merge): the sorted order in parts of at most so many points
-  bool split() const { return sequential && point_order && !merge_points && part_points >= 1 && seq.geometry == 0 && !weld_sink; }
+  uint32_t part_cells = 0;                 // dsa_encode_cell_parts_sequential_batch, part_cells >= 1 (with point_order and merge_points, point clouds): the KEPT order in parts of at most so many points
+  bool cell_parts() const { return sequential && point_order && merge_points && part_cells >= 1 && part_points == 0 && seq.geometry == 0 && !weld_sink; }
+  bool split() const { return (sequential && point_order && !merge_points && part_points >= 1 && seq.geometry == 0 && !weld_sink) || cell_parts(); }
+  uint32_t part_size() const { return cell_parts() ? part_cells : part_points; }      // N of either
   int rows_kind() const { return weld_sink ? dsa_encoded::ROWS_NONE : (sequential ? (point_order ? dsa_encoded::ROWS_ORDERED : dsa_encoded::ROWS_LINEAR) : (track_rows ? dsa_encoded::ROWS_TRACKED : dsa_encoded::ROWS_NONE)); }
   dsa_encode_level_options level{};        // Edgebreaker streams
   dsa_encode_sequential_options seq{};     // sequential streams
@@ -287,6 +301,7 @@ struct EncLayout {
   // EncRequest::split: a record per part of every cloud (the parts of a cloud side by side, part_of_mesh[i] its first) and the
   // (part, tile) pairs of all of them, both among the uploads
   bool split = false;
+  bool cell_parts = false;                  // EncRequest::cell_parts: split and merge, a cloud's records are part SLOTS the device sizes (k_enc_part_cells)
   std::vector<dsa::EncPart> parts;
   std::vector<dsa::EncPartTile> part_tiles;
   std::vector<uint32_t> part_of_mesh;
@@ -343,7 +358,15 @@ struct EncChunk {
   std::vector<std::vector<uint32_t>> row_cells;                         // per stream, a cloud's first alone (EncRequest::merge_points): row_entries
   std::vector<uint32_t> parts;                                          // EncRequest::split, per mesh: how many parts it is coded in (enc_check_sequential_mesh)
   std::vector<std::vector<dsa::EncPart>> part_boxes;                    // ... per stream, a cloud's first alone: the records of its parts as k_enc_part_bounds left them
-  uint32_t num_parts(uint32_t i) const { return parts.empty() ? 1u : parts[i]; }
+  uint32_t num_parts(uint32_t i) const { return parts.empty() ? 1u : parts[i]; }        // (part_cells: the slots laid out, ceil(n / part_cells))
+  // part_cells: the parts the device made of cloud i -- the slots in front whose records came back with points -- and their points, m
+  uint32_t live_parts(uint32_t i, uint32_t *points = nullptr) const {
+    const uint32_t s0 = L.first_stream[i], na = (uint32_t)plans[i].atts.size();
+    uint32_t live = 0, m = 0;
+    for (uint32_t p = 0, np = num_parts(i); p < np && L.streams[s0 + p * na].nv != 0u; ++p) { ++live; m += L.streams[s0 + p * na].nv; }
+    if (points) *points = m;
+    return live;
+  }
 
   EncChunk(const EncRequest &r, uint32_t b, uint32_t cnt, uint32_t bn) : rq(r), base(b), n(cnt), batch_n(bn), opt(enc_synth_options(r)), E(new (std::nothrow) dsa_encoded()), ins(cnt), plans(cnt), extras(cnt), extra_cap(cnt) {
     if (!E) return;                        // (the chunk function answers)
@@ -602,7 +625,12 @@ static void enc_check_sequential_mesh(EncChunk &ck, uint32_t i) {
   synth::plan_sequential_attributes(in, mo, ck.plans[i].atts);
   enc_extra_caps(ck, i);
   if (!ck.rq.split()) return;
-  const uint64_t parts = synth::split_count(m.num_vertices, ck.rq.part_points);
+  const uint64_t parts = synth::split_count(m.num_vertices, ck.rq.part_size());
+  if (parts > DSA_ENCODE_MAX_PARTS && ck.rq.cell_parts()) {       // (the host bounds the parts by the points that came in: the kept ones are the device's to count)
+    char buf[200];
+    snprintf(buf, sizeof(buf), "part_cells %u may cut the cloud's n = %u points into %llu parts: at most %u (DSA_ENCODE_MAX_PARTS)", ck.rq.part_cells, m.num_vertices, (unsigned long long)parts, DSA_ENCODE_MAX_PARTS);
+    return ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, buf);
+  }
   if (parts > DSA_ENCODE_MAX_PARTS) {
     char buf[160];
     snprintf(buf, sizeof(buf), "part_points %u cuts the cloud's n = %u points into %llu parts: at most %u (DSA_ENCODE_MAX_PARTS)", ck.rq.part_points, m.num_vertices, (unsigned long long)parts, DSA_ENCODE_MAX_PARTS);
@@ -869,11 +897,15 @@ static void enc_layout(EncChunk &ck) {
 // bytes per point takes row_entries; every region stays sized for the points that came in, k_enc_merge_scan lowers nv below them.
 // EncRequest::split: a cloud of P parts has P sets of stream records (stream s0 + p * attributes + k: attribute k of part p) on one
 // set of source values and integers; the EncPart records and their (part, tile) pairs go up beside the sort's.
+// EncRequest::cell_parts (split and merge): P is the device's to know, so a cloud has P_max = ceil(n / part_cells) part SLOTS, each
+// with records, regions and tiles for min(part_cells, n) points -- under n + part_cells points per attribute in all; the streams' map
+// is the kept buffer, as with the merge, and k_enc_part_cells writes every slot's lo, n, nv and e2v.
 static void enc_layout_sequential(EncChunk &ck) {
   EncLayout &L = ck.L;
   const bool is_mesh = ck.rq.seq.geometry == 1, compressed = is_mesh && ck.rq.seq.compress_connectivity == 1, ordered = ck.rq.point_order;
   const bool merge = ordered && !is_mesh && ck.rq.merge_points, split = ck.rq.split();
-  L.merge = merge; L.split = split;
+  const bool cell_parts = ck.rq.cell_parts();
+  L.merge = merge; L.split = split; L.cell_parts = cell_parts;
   if (merge || split) L.ord_of_mesh.assign(ck.n, DSA_INVALID);
   if (split) L.part_of_mesh.assign(ck.n, DSA_INVALID);
   EncArena A;
@@ -898,12 +930,15 @@ static void enc_layout_sequential(EncChunk &ck) {
       for (uint32_t t = 0; t < O.tiles; ++t) L.ord_tiles.push_back({(uint32_t)L.ord.size(), t});
       if (split) {                                             // the parts of the cloud: their sizes need nothing of the device
         L.part_of_mesh[i] = (uint32_t)L.parts.size();
+        // (part_cells: the slots of the cloud, lo and n the device's to write -- k_enc_part_cells -- and tiles for the most a slot can hold)
+        if (cell_parts) { O.part_cells = ck.rq.part_cells; O.part0 = (uint32_t)L.parts.size(); O.part_slots = ck.num_parts(i); }
         for (uint32_t p = 0, np = ck.num_parts(i); p < np; ++p) {
           dsa::EncPart P;
           memset(&P, 0, sizeof(P));
-          P.cloud = (uint32_t)L.ord.size(); P.lo = synth::split_bound(V, np, p); P.n = synth::split_bound(V, np, p + 1u) - P.lo;
+          P.cloud = (uint32_t)L.ord.size();
+          if (!cell_parts) { P.lo = synth::split_bound(V, np, p); P.n = synth::split_bound(V, np, p + 1u) - P.lo; }
           for (int c = 0; c < 3; ++c) { P.qmin[c] = INT32_MAX; P.qmax[c] = INT32_MIN; }
-          for (uint32_t t = 0, nt = (P.n + ORD_TILE - 1u) / ORD_TILE; t < nt; ++t) L.part_tiles.push_back({(uint32_t)L.parts.size(), t});
+          for (uint32_t t = 0, nt = ((cell_parts ? std::min(ck.rq.part_cells, V) : P.n) + ORD_TILE - 1u) / ORD_TILE; t < nt; ++t) L.part_tiles.push_back({(uint32_t)L.parts.size(), t});
           L.parts.push_back(P);
         }
       }
@@ -948,7 +983,12 @@ static void enc_layout_sequential(EncChunk &ck) {
         const dsa::EncPart &P = L.parts[L.part_of_mesh[i] + p];
         for (uint32_t k = 0; k < na; ++k) {
           dsa::EncStream &S = L.streams[s0 + p * na + k];
-          if (p) { S = L.streams[s0 + k]; S.part = 1; S.grid_mode = 0; }      // (grid_mode 0: k_enc_grid_quantize passes it by too; the header's floats are the first part's)
+          if (p) { S = L.streams[s0 + k]; S.part = dsa::ENC_PART_BEHIND; S.grid_mode = 0; }      // (grid_mode 0: k_enc_grid_quantize passes it by too; the header's floats are the first part's)
+          if (cell_parts) {                                    // a slot: nv and e2v are the device's to write; regions for the most it can hold
+            if (p) { S.part |= dsa::ENC_PART_SIZED; S.nv = 0; }
+            enc_value_stream_regions(S, std::min(ck.rq.part_cells, V), ck.hist_cap_of(i, k), A, p ? L.streams[s0 + k].vals : 0);
+            continue;
+          }
           S.nv = P.n; S.e2v = O.row[L.ord_passes & 1u] + 4ull * P.lo;
           enc_value_stream_regions(S, P.n, ck.hist_cap_of(i, k), A, p ? L.streams[s0 + k].vals : 0);
         }

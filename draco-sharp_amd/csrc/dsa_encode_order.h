@@ -72,6 +72,25 @@
 // The records leave the device among the chunk's packed pieces, as perm does.  The host coder's twin is synth::split_parts /
 // synth::part_boxes; tests/hostcheck/encsplit_host.cpp runs the serial form against it, tests/test_gpu_encode_split.py the shuffles.
 // gfx950, hipcc -O3 (VGPR / SGPR / LDS bytes per block): k_enc_part_bounds 18 / 22 / 0; no scratch, no spills, 8 waves per SIMD.
+//
+// dsa_encode_cell_parts_sequential_batch with part_cells = N >= 1 (point clouds, merge_points = 1): the KEPT order of a cloud -- m
+// entries, a number the host does not know -- cut into P = ceil(m / N) parts, part p kept entries [floor(p m / P), floor((p + 1) m /
+// P)).  The host can only bound P by P_max = ceil(n / N): the layout lays out P_max part slots per cloud, each with its EncPart
+// record, its set of EncStream records, regions for min(N, n) points and (part, tile) pairs for as many, and one step sizes them:
+//   k_enc_part_cells      a thread per slot, behind k_enc_merge_scan (which knows m) and in front of k_enc_part_bounds and
+//                         k_enc_gather: P, lo_p and n_p from m and N of the cloud's record in 64 bits, lo / n into the slot's
+//                         EncPart, nv = n_p and e2v = kept + 4 lo_p into every EncStream of the slot; a slot p >= P gets n = nv = 0
+//                         and kind 3 (k_enc_merge_scan's nv = m lands in slot 0's records only, which this step writes too).  No lane needs
+//                         another: the kernel has no shuffle, no LDS, no atomic, waits for nothing, and the host check runs it
+//                         thread by thread as it stands.  Every value is a function of the input alone.
+// k_enc_part_bounds then reads lo / n from the records on the device and the kept buffer in place of the sorted one (EncOrder::merge
+// says so); the tiles of a slot beyond its size return at once.  A slot with nv = 0 is an empty value stream, which only this layout
+// makes: its records carry ENC_PART_SIZED (dsa_encode_layout.h), and k_enc_part_cells makes them empty lists (kind 3), which
+// k_enc_gather, k_enc_corr, k_enc_plan, k_enc_rans and the host's plans pass by as they are, without touching a region; the piece
+// packer skips them by the flag.  P and the sizes come back in the stream records at the end of the stage, as m does for the merge.
+// The host coder's twin is synth::cell_parts; tests/hostcheck/enccellparts_host.cpp runs the steps in the product's layout against
+// it, tests/test_gpu_encode_cell_parts.py the device's.
+// gfx950, hipcc -O3 (VGPR / SGPR / LDS bytes per block): k_enc_part_cells 25 / 18 / 0; no scratch, no spills, 8 waves per SIMD.
 #pragma once
 #include <stdint.h>
 
@@ -94,8 +113,9 @@ struct EncOrder {                  // one per cloud of the chunk; in the arena, 
   uint32_t narrow, merge;          // merge: merge_points = 1, the three fields below are set
   uint64_t cells;                  // u32[n] OUTPUT (merge; else 0): row_entries, the entry of the cell of every row
   uint32_t stream0, streams;       // the cloud's value streams among the chunk's EncStream records: k_enc_merge_scan lowers their nv
-  uint32_t m, pad;                 // OUTPUT (merge): occupied cells
-};
+  uint32_t m, part_cells;          // OUTPUT (merge): occupied cells; part_cells: not 0: the kept points in parts of at most so many (k_enc_part_cells),
+  uint32_t part0, part_slots;      //   the cloud's part_slots = ceil(n / part_cells) EncPart records from part0 on, slot p with `streams` stream records
+};                                 //   from stream0 + p * streams on
 struct EncOrderTile { uint32_t cloud, tile; };
 struct EncPart {                   // one per part of a split cloud, the parts of a cloud side by side; in the arena, among the uploads
   uint32_t cloud;                  // its cloud among the chunk's EncOrder records
@@ -364,6 +384,30 @@ static inline void enc_merge_launch(Launch &&launch, uint8_t *arena, EncOrder *c
   launch(k_enc_merge_compact, nt, 1u, (uint32_t)WAVE, arena, (const EncOrder *)clouds, tiles, nt, passes);
 }
 
+// ---- part_cells (the header comment has the contract): a thread per part slot of the chunk, behind k_enc_merge_scan
+template <class Stream>
+__global__ __launch_bounds__(WAVE) void k_enc_part_cells(EncOrder *clouds, uint32_t nc, EncPart *parts, uint32_t np, Stream *streams, uint32_t ns, uint32_t passes) {
+  const uint32_t i = blockIdx.x * WAVE + threadIdx.x;
+  if (i >= np) return;
+  EncPart &P = parts[i];
+  if (P.cloud >= nc) return;
+  const EncOrder &O = clouds[P.cloud];
+  if (O.part_cells == 0u || i < O.part0 || i - O.part0 >= O.part_slots) return;       // (never by the layout)
+  const uint64_t p = i - O.part0, m = O.m < O.n ? O.m : O.n, live = (m + O.part_cells - 1u) / O.part_cells;
+  uint32_t lo = 0, cnt = 0;
+  if (p < live) { lo = (uint32_t)(p * m / live); cnt = (uint32_t)((p + 1u) * m / live) - lo; }      // (64 bits: p m < 2^16 2^28)
+  P.lo = lo; P.n = cnt;
+  const uint64_t kept = O.row[(passes + 1u) & 1u] + 4ull * lo, s0 = (uint64_t)O.stream0 + p * O.streams;
+  for (uint32_t k = 0; k < O.streams; ++k) if (s0 + k < ns) { Stream &S = streams[s0 + k]; S.nv = cnt; S.e2v = kept; if (cnt == 0u) S.kind = 3u; }      // (empty: an empty list, which every step passes by)
+}
+
+// The part sizes behind enc_merge_launch and in front of enc_part_launch: `parts` the chunk's np EncPart records (slots).
+template <class Launch, class Stream>
+static inline void enc_part_cells_launch(Launch &&launch, EncOrder *clouds, uint32_t nc, EncPart *parts, uint32_t np, Stream *streams, uint32_t ns, uint32_t passes) {
+  if (nc == 0 || np == 0) return;
+  launch(k_enc_part_cells<Stream>, (np + (uint32_t)WAVE - 1u) / (uint32_t)WAVE, 1u, (uint32_t)WAVE, clouds, nc, parts, np, streams, ns, passes);
+}
+
 // ---- part_points (the header comment has the contract): grid = the chunk's (part, tile) pairs, one wave each
 __global__ __launch_bounds__(WAVE) void k_enc_part_bounds(uint8_t *arena, const EncOrder *clouds, uint32_t nc, EncPart *parts, uint32_t np, const EncPartTile *tiles, uint32_t nt,
                                                           uint32_t passes) {
@@ -376,7 +420,7 @@ __global__ __launch_bounds__(WAVE) void k_enc_part_bounds(uint8_t *arena, const 
   const uint32_t t0 = T.tile * ORD_TILE;
   if (t0 >= P.n || P.lo > O.n || P.n > O.n - P.lo) return;       // (never by the layout: the comparisons keep a fault elsewhere inside the cloud's buffers)
   const int32_t *vals = (const int32_t *)(arena + O.vals);
-  const uint32_t *row = (const uint32_t *)(arena + O.row[passes & 1u]);
+  const uint32_t *row = (const uint32_t *)(arena + O.row[(passes + (O.merge ? 1u : 0u)) & 1u]);     // (merge: the parts are runs of the kept rows)
   const uint32_t lane = threadIdx.x, e0 = P.lo + t0, end = P.lo + (P.n - t0 < ORD_TILE ? P.n : t0 + ORD_TILE);
   int32_t mn[3] = {0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF}, mx[3] = {(int32_t)0x80000000, (int32_t)0x80000000, (int32_t)0x80000000};
 #if defined(__HIPCC__)

@@ -15,6 +15,8 @@
 //                                nv of the cloud's streams falls on the device, the host reads it from the records that come back
 //          k_enc_part_bounds     dsa_encode_split_sequential_batch, part_points >= 1 (point clouds): a set of stream records per part of the
 //                                sorted order, and the box of every part's position integers; the host writes a stream per part
+//          k_enc_part_cells      dsa_encode_cell_parts_sequential_batch, part_cells >= 1 (point clouds, merge_points = 1): part slots whose
+//                                sizes the device writes behind k_enc_merge_scan; the host writes a stream per slot that came back with points
 //          k_enc_seq_indices     compressed indices: symbols and their statistics (dsa_encode_seqidx.h)
 //          k_enc_plan / k_enc_rans   every stream, the index stream as a list whose symbols are given (kind 3)
 //   host   stream layout (synth::write_sequential_stream)
@@ -26,14 +28,20 @@
 static void enc_write_parts(EncChunk &ck, uint32_t i) {
   const EncLayout &L = ck.L;
   const std::vector<synth::PortableAttr> &atts = ck.plans[i].atts;
-  const uint32_t s0 = L.first_stream[i], na = (uint32_t)atts.size(), np = ck.num_parts(i), V = ck.mesh(i).num_vertices;
+  // (part_cells: the parts the device made of the slots, over the m kept rows; row_entries of all input rows beside them)
+  const bool cells = L.cell_parts;
+  uint32_t V = ck.mesh(i).num_vertices;
+  const uint32_t s0 = L.first_stream[i], na = (uint32_t)atts.size(), rows = V, np = cells ? ck.live_parts(i, &V) : ck.num_parts(i);
+  if (cells && (np == 0 || V == 0 || V > rows || np != synth::split_count(V, ck.rq.part_cells) || ck.row_cells[s0].size() != rows)) return ck.refuse(i, DSA_ERR_DEVICE, "the merged points and their parts did not come back");
   if (ck.entry_rows[s0].size() != V || ck.part_boxes[s0].size() != np) return ck.refuse(i, DSA_ERR_DEVICE, "the point order and the part boxes did not come back");
   const dsa::EncStream &pos = L.streams[s0];
   std::vector<dsa_encoded::Part> parts(np);
   for (uint32_t p = 0; p < np; ++p) {
-    const dsa::EncPart &P = ck.part_boxes[s0][p], &laid = L.parts[L.part_of_mesh[i] + p];
+    const dsa::EncPart &P = ck.part_boxes[s0][p];
+    dsa::EncPart laid = L.parts[L.part_of_mesh[i] + p];
+    if (cells) { laid.lo = synth::split_bound(V, np, p); laid.n = synth::split_bound(V, np, p + 1u) - laid.lo; }
     const uint32_t sp = s0 + p * na;
-    if (P.lo != laid.lo || P.n != laid.n || P.n == 0 || P.qmin[0] > P.qmax[0]) return ck.refuse(i, DSA_ERR_DEVICE, "the point order and the part boxes did not come back");
+    if (P.lo != laid.lo || P.n != laid.n || L.streams[sp].nv != P.n || P.n == 0 || P.qmin[0] > P.qmax[0]) return ck.refuse(i, DSA_ERR_DEVICE, "the point order and the part boxes did not come back");
     synth::ByteWriter w;
     try {
       synth::write_sequential_stream(w, false, P.n, 0, false, atts, [](synth::ByteWriter &) {},
@@ -52,6 +60,7 @@ static void enc_write_parts(EncChunk &ck, uint32_t i) {
   }
   ck.E->parts[i].swap(parts);
   ck.E->order[i].swap(ck.entry_rows[s0]);
+  if (cells) ck.E->cells[i].swap(ck.row_cells[s0]);
 }
 // the stream layout of a chunk (threads over meshes)
 static void enc_stage_sequential_streams(EncChunk &ck) {

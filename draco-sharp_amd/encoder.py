@@ -80,7 +80,15 @@ class Config:
     together without cracks, and come with a box each.  The EncodedStreams then runs over STREAMS (inputs in order, the parts of
     an input in order): parts(i) is the range of input i's streams, part_info(s) says which part stream s is and gives its box,
     entry_rows(s) its slice of the order.  Point clouds only, under a sequential config with point_order=POINT_ORDER_MORTON and
-    without merge_points."""
+    without merge_points.
+
+    part_cells (dsa_encode_cell_parts_sequential_batch): parts WITH merge_points=MERGE_CELLS.  0 no parts; N >= 1 the kept order of
+    every point cloud -- kept[0 .. m) as merge_points defines it, m a number only the device knows -- cut into P = ceil(m / N) parts
+    of at most N kept points, part p kept entries [floor(p m / P), floor((p + 1) m / P)), each an ordinary point-cloud stream on the
+    cloud's one quantisation grid (the bounds of all n input rows).  The EncodedStreams runs over STREAMS as with part_points:
+    parts(i), part_info(s) (first_entry / num_points in kept order) and entry_rows(s) = kept[lo:hi]; row_entries(parts(i)[0]) is the
+    cloud's row_entries in the global kept order, row_parts(i) turns it into (part, entry) per input row.  Needs a sequential config
+    with point_order=POINT_ORDER_MORTON and merge_points=MERGE_CELLS, and no part_points."""
 
     EDGEBREAKER_METHODS = (0, 2, -1)
     POSITION_PREDICTIONS = (0, 1)
@@ -95,7 +103,7 @@ class Config:
     def __init__(self, position_bits=11, texcoord_bits=10, normal_bits=8, speed=5, single_connectivity=False,
                  symbol_scheme=-1, position_prediction=1, texcoord_prediction=1, edgebreaker_method=0, normal_prediction=0,
                  encoding_method=1, compress_connectivity=False, multi_parallelogram=0, traversal_method=0, repair_topology=False, weld_points=False,
-                 repair_seams=False, weld_attributes=False, track_rows=False, point_order=0, merge_points=0, part_points=0):
+                 repair_seams=False, weld_attributes=False, track_rows=False, point_order=0, merge_points=0, part_points=0, part_cells=0):
         for name, value, legal in (("encoding_method", encoding_method, self.ENCODING_METHODS),
                                    ("edgebreaker_method", edgebreaker_method, self.EDGEBREAKER_METHODS),
                                    ("position_prediction", position_prediction, self.POSITION_PREDICTIONS),
@@ -140,6 +148,13 @@ class Config:
         if self.part_points != 0 and (not (self.sequential and self.point_order == native.POINT_ORDER_MORTON) or self.merge_points != 0):
             raise ValueError("part_points cuts the Morton order of a point cloud into parts: it needs a sequential config (encoding_method 0) with point_order=POINT_ORDER_MORTON and no merge_points")
 
+        self.part_cells = int(part_cells)
+        if self.part_cells < 0 or self.part_cells > 2**31 - 1:
+            raise ValueError("part_cells %r: 0 (no parts) or the largest number of kept points of a part" % (part_cells,))
+        if self.part_cells != 0 and not (self.sequential and self.point_order == native.POINT_ORDER_MORTON and self.merge_points == native.MERGE_CELLS):
+            raise ValueError("part_cells cuts the kept order of merge_points into parts: it needs a sequential config (encoding_method 0) with point_order=POINT_ORDER_MORTON and merge_points=MERGE_CELLS")
+        # (part_cells together with part_points never gets here: part_points has refused the merge_points that part_cells needs)
+
     @property
     def sequential(self):
         """True when meshes are written as sequential streams: asked for, or by the reference's rule at speed 10."""
@@ -172,6 +187,13 @@ class Config:
         native.lib().dsa_encode_default_split_options(C.byref(o))
         o.merge = self._native_merge(geometry)
         o.part_points = self.part_points
+        return o
+
+    def _native_cell_parts(self, geometry):
+        o = native.EncodeCellPartsOptions()
+        native.lib().dsa_encode_default_cell_parts_options(C.byref(o))
+        o.split = self._native_split(geometry)
+        o.part_cells = self.part_cells
         return o
 
     @property
@@ -562,9 +584,19 @@ class EncodedStreams:
             raise ValueError("the encoded batch was closed")
         return _row_entries(self._ctx, self._h, i + len(self) if i < 0 else i)
 
+    def row_parts(self, i):
+        """Of input i of an encode with Config(merge_points=MERGE_CELLS, part_cells=N): (part, entry), two uint32 arrays with one
+        element per input row -- the part of the input whose stream codes the row's cell (stream parts(i)[part]) and the entry of
+        that stream; searchsorted of the parts' first_entry in the cloud's row_entries, and the difference."""
+        r = self.parts(i)
+        cells = self.row_entries(r[0])
+        first = np.array([self.part_info(s).first_entry for s in r], np.uint32)
+        part = (np.searchsorted(first, cells, side="right") - 1).astype(np.uint32)
+        return part, (cells - first[part]).astype(np.uint32)
+
     def parts(self, i):
-        """The streams of input i of the encode as a range: with Config(part_points=N) its parts in order, else range(i, i + 1);
-        dsa_encoded_parts."""
+        """The streams of input i of the encode as a range: with Config(part_points=N) or Config(part_cells=N) its parts in order,
+        else range(i, i + 1); dsa_encoded_parts."""
         if self._h is None:
             raise ValueError("the encoded batch was closed")
         first, count = C.c_uint32(), C.c_uint32()
@@ -706,6 +738,8 @@ class DracoEncoder:
             raise ValueError("attributes given per corner need Edgebreaker connectivity (encoding_method 1): a sequential stream has one value per point")
         if getattr(config, "point_order", 0) != 0 and not (clouds or config.sequential):
             raise ValueError("point_order needs a sequential stream (encoding_method 0, or point clouds): Edgebreaker orders its own entries")
+        if getattr(config, "part_cells", 0) != 0 and not clouds:
+            raise ValueError("part_cells takes point clouds (PointCloudData): a part of a mesh would need its faces cut")
         if getattr(config, "part_points", 0) != 0 and not clouds:
             raise ValueError("part_points takes point clouds (PointCloudData): a part of a mesh would need its faces cut")
         if getattr(config, "merge_points", 0) != 0 and not clouds:
@@ -767,7 +801,12 @@ class DracoEncoder:
         n = len(meshes)
         arr, grids, keep = _native_meshes(meshes)
         h = C.c_void_p()
-        if getattr(config, "part_points", 0) != 0:      # (the widest call only when its option is set: the handle then has a slot per stream)
+        if getattr(config, "part_cells", 0) != 0:       # (the widest call only when its option is set: the handle then has a slot per stream)
+            opt = config._native_cell_parts(geometry)
+            st = native.lib().dsa_encode_cell_parts_sequential_batch(ctx._h, n, arr, grids, C.byref(opt), C.byref(h))
+            if st == 0:
+                n = native.lib().dsa_encoded_size(h)
+        elif getattr(config, "part_points", 0) != 0:    # (the widest call only when its option is set: the handle then has a slot per stream)
             opt = config._native_split(geometry)
             st = native.lib().dsa_encode_split_sequential_batch(ctx._h, n, arr, grids, C.byref(opt), C.byref(h))
             if st == 0:

@@ -43,6 +43,7 @@ EXPORTS = [
     "dsa_encode_default_order_options", "dsa_encode_ordered_sequential_batch",
     "dsa_encode_default_merge_options", "dsa_encode_merged_sequential_batch", "dsa_encoded_row_entries",
     "dsa_encode_default_split_options", "dsa_encode_split_sequential_batch", "dsa_encoded_parts", "dsa_encoded_part_info",
+    "dsa_encode_default_cell_parts_options", "dsa_encode_cell_parts_sequential_batch",
     "dsa_encoded_size", "dsa_encoded_stream", "dsa_encoded_free",
     "dsa_pool_create", "dsa_pool_destroy", "dsa_pool_size", "dsa_pool_last_error", "dsa_pool_decode", "dsa_pool_job_locate",
     "dsa_pool_job_chunks", "dsa_pool_job_free", "dsa_pool_plan",
@@ -111,6 +112,12 @@ class EncodeSplitOptions(C.Structure):
     every point cloud in parts of at most N points, a stream each; the handle has a slot per stream: dsa_encoded_parts,
     dsa_encoded_part_info)."""
     _fields_ = [("merge", EncodeMergeOptions), ("part_points", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+class EncodeCellPartsOptions(C.Structure):
+    """dsa_encode_cell_parts_options: the options of dsa_encode_split_sequential_batch, and part_cells (N >= 1, with merge_points = 1:
+    the KEPT order of every point cloud in parts of at most N points, sized on the device; the handle is shaped like a split one)."""
+    _fields_ = [("split", EncodeSplitOptions), ("part_cells", C.c_int32), ("reserved", C.c_int32 * 7)]
 
 
 class PartInfo(C.Structure):
@@ -389,6 +396,10 @@ def lib():
             L.dsa_encode_split_sequential_batch.argtypes = [vp, u32, C.POINTER(MeshAttrInput), C.POINTER(MeshGrids), C.POINTER(EncodeSplitOptions), C.POINTER(vp)]
             L.dsa_encoded_parts.argtypes = [vp, u32, C.POINTER(u32), C.POINTER(u32)]
             L.dsa_encoded_part_info.argtypes = [vp, u32, C.POINTER(PartInfo)]
+        if hasattr(L, "dsa_encode_cell_parts_sequential_batch"):
+            L.dsa_encode_default_cell_parts_options.argtypes = [C.POINTER(EncodeCellPartsOptions)]
+            L.dsa_encode_default_cell_parts_options.restype = None
+            L.dsa_encode_cell_parts_sequential_batch.argtypes = [vp, u32, C.POINTER(MeshAttrInput), C.POINTER(MeshGrids), C.POINTER(EncodeCellPartsOptions), C.POINTER(vp)]
         L.dsa_encoded_size.restype = u32
         L.dsa_encoded_size.argtypes = [vp]
         L.dsa_encoded_stream.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(C.c_size_t)]

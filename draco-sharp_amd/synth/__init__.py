@@ -1,6 +1,7 @@
 """Synthetic inputs: procedural meshes and a CPU writer of Draco v2.2 streams
 (ctypes binding of libdsa_synth.so).  Used by tests and bench.py to make .drc
 inputs; not part of the decode path."""
+import collections
 import ctypes as C
 import os
 import subprocess
@@ -237,6 +238,8 @@ def lib():
         L.synth_merge_points.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(Grid), C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]
         L.synth_split_parts.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         L.synth_part_boxes.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(Grid), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.synth_cell_parts.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(Grid), C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         L.synth_shared_grid.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_uint32, C.c_int, C.POINTER(Grid)]
         L.synth_free.argtypes = [C.c_void_p]
         L.synth_make_mesh.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_uint32),
@@ -674,6 +677,48 @@ def encode_split(pos, normals=None, uvs=None, generic=None, extra=None, opt=None
         p = kw.pop("pos")
         out.append((encode_grid(p, None, form=0, geometry=0, **kw), rows, qmin, qmax))
     return out
+
+
+def cell_parts(pos, bits, part_cells, grid=None):
+    """(kept, row_entries, ranges, qmin, qmax) of the points `pos` (N, 3): kept / row_entries = merge_points(pos, bits, grid), ranges =
+    split_parts(len(kept), part_cells) -- parts of the KEPT order -- and qmin / qmax (P, 3) int32 the minimum and maximum per
+    component of the integers the position stream codes for rows kept[lo:hi]."""
+    L = lib()
+    pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+    kept, cells = np.zeros(len(pos), np.uint32), np.zeros(len(pos), np.uint32)
+    m, parts = C.c_uint32(), C.c_uint64()
+    grid = None if grid is None else C.byref(grid)
+    if L.synth_cell_parts(pos.ctypes.data, len(pos), int(bits), grid, int(part_cells), kept.ctypes.data, C.byref(m), cells.ctypes.data, None, None, None, 0, C.byref(parts)):
+        raise RuntimeError(_err())
+    ranges = np.zeros((parts.value, 2), np.uint32)
+    qmin, qmax = np.zeros((parts.value, 3), np.int32), np.zeros((parts.value, 3), np.int32)
+    if L.synth_cell_parts(pos.ctypes.data, len(pos), int(bits), grid, int(part_cells), kept.ctypes.data, C.byref(m), cells.ctypes.data, ranges.ctypes.data,
+                          qmin.ctypes.data, qmax.ctypes.data, len(ranges), C.byref(parts)):
+        raise RuntimeError(_err())
+    return kept[:m.value].copy(), cells, ranges, qmin, qmax
+
+
+CellParts = collections.namedtuple("CellParts", "streams kept row_entries ranges qmin qmax")
+
+
+def encode_cell_parts(pos, normals=None, uvs=None, generic=None, extra=None, opt=None, pos_grid=None, uv_grid=None, part_cells=0):
+    """One point per occupied cell, and the kept order in parts of at most part_cells points, each coded as a point cloud of its own
+    on the cloud's grid: CellParts(streams, kept, row_entries, ranges, qmin, qmax) with merged_arguments' rows and grids -- every
+    per-point array at [kept[lo:hi]], every quantised attribute on an explicit grid equal to the bounds of ALL input rows (the grid
+    given, where one was).  What dsa_encode_cell_parts_sequential_batch with part_cells >= 1 must write, and what its handle must
+    report."""
+    opt = opt or options()
+    kept, cells, ranges, qmin, qmax = cell_parts(pos, opt.pos_bits, part_cells, pos_grid)
+    _, _, kw = merged_arguments(pos, normals, uvs, generic, extra, opt, pos_grid, uv_grid)
+    p = kw.pop("pos")
+    streams = []
+    for lo, hi in ranges:
+        take = lambda a: None if a is None else np.ascontiguousarray(a[lo:hi])          # noqa: E731
+        ex = [Extra(e.values[lo:hi], attribute_type=e.attribute_type, normalized=bool(e.normalized), unique_id=e.unique_id,
+                    quantization_bits=e.quantization_bits, data_type=e.data_type, num_components=e.num_components, grid=e.grid) for e in kw["extra"]]
+        streams.append(encode_grid(take(p), None, normals=take(kw["normals"]), uvs=take(kw["uvs"]), generic=take(kw["generic"]), extra=ex, opt=opt,
+                                   form=0, geometry=0, pos_grid=kw["pos_grid"], uv_grid=kw["uv_grid"]))
+    return CellParts(streams, kept, cells, ranges, qmin, qmax)
 
 
 def entry_rows(pos, faces=None, normals=None, uvs=None, generic=None, extra=None, opt=None, form=1, normal_corners=None, uv_corners=None,

@@ -551,6 +551,26 @@ int synth_part_boxes(const float *pos, uint32_t n, int bits, const synth::Grid *
     return 0;
   } catch (const std::exception &e) { snprintf(g_err, sizeof(g_err), "%s", e.what()); return 1; }
 }
+// The kept order of merge_points in parts of at most part_cells (cell_parts): kept[n] of which *m are set, row_entries[n], and where
+// `ranges` is given (room for 2 * capacity) lo and hi of the *parts parts with their boxes, qmin / qmax[3 * capacity].
+int synth_cell_parts(const float *pos, uint32_t n, int bits, const synth::Grid *grid, uint32_t part_cells, uint32_t *kept, uint32_t *m, uint32_t *row_entries,
+                     uint32_t *ranges, int32_t *qmin, int32_t *qmax, uint64_t capacity, uint64_t *parts) {
+  try {
+    std::vector<uint32_t> k, c;
+    std::vector<std::pair<uint32_t, uint32_t>> r;
+    std::vector<int32_t> mn, mx;
+    synth::cell_parts(pos, n, bits, grid, part_cells, k, c, r, mn, mx);
+    *m = (uint32_t)k.size(); *parts = r.size();
+    memcpy(kept, k.data(), 4 * k.size());
+    memcpy(row_entries, c.data(), 4 * c.size());
+    if (!ranges) return 0;
+    synth::check(capacity >= r.size(), "cell_parts: no room for the ranges");
+    for (size_t p = 0; p < r.size(); ++p) { ranges[2 * p] = r[p].first; ranges[2 * p + 1] = r[p].second; }
+    memcpy(qmin, mn.data(), 4 * mn.size());
+    memcpy(qmax, mx.data(), 4 * mx.size());
+    return 0;
+  } catch (const std::exception &e) { snprintf(g_err, sizeof(g_err), "%s", e.what()); return 1; }
+}
 void synth_free(uint8_t *p) { free(p); }
 
 // Procedural mesh: returns counts; call once with NULL outputs to size, then again to fill.

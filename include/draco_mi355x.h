@@ -795,6 +795,42 @@ typedef struct dsa_part_info {
   uint32_t reserved[2];                    /* zero */
 } dsa_part_info;
 dsa_status dsa_encoded_part_info(const dsa_encoded *encoded, uint32_t stream, dsa_part_info *out);
+/* dsa_encode_split_sequential_batch for the combination it refuses: one point per quantisation cell (merge_points = 1) AND parts of
+ * bounded size -- what a large scan needs, which without the merge codes many bit-identical points per cell and without the parts
+ * runs its one merged stream on one wave in both directions.  The number of kept points, and so of parts, is known only on the
+ * device; here the parts are sized there (k_enc_part_cells, dsa_encode_order.h, behind the step that already lowers nv), and
+ * nothing goes through the host in between: built here.
+ *   part_cells = N >= 1 (taken only with point_order = 1, geometry 0, merge_points = 1 and split.part_points = 0): with kept[0 .. m)
+ *   and row_entries exactly what merge_points = 1 defines for the cloud, P = ceil(m / N) and part p is kept entries
+ *   [floor(p m / P), floor((p + 1) m / P)), computed in 64 bits -- the rule of part_points applied to m in place of n: every part has
+ *   1 .. N points, sizes differ by at most one.  Part p is an ordinary Draco 2.2 point-cloud stream; entry j of every attribute
+ *   carries row kept[lo_p + j].  Bounds and quantisers run once per cloud, in front of the sort, so every quantised attribute of
+ *   every part is on the bounds of ALL n input rows (or the grid given or shared), and the parts fit together without cracks: the
+ *   stream of part p is byte for byte what dsa_encode_split_sequential_batch writes for part p of the input rows[kept] on explicit
+ *   grids equal to those bounds.  Wrap bounds, symbol statistics, scheme choice and tables are each part's own.
+ *   The handle is shaped like a split handle: a slot per STREAM, inputs in call order, the parts of an input in order p; a refused
+ *   input keeps one slot and fails alone.  dsa_encoded_parts names the slots of an input; dsa_encoded_part_info(s) gives first_entry
+ *   / num_points in KEPT order, qmin / qmax and box_min / box_max as for split parts (the box is bit for bit the box of the part's
+ *   decoded positions); dsa_encoded_entry_rows(s, a) returns kept[lo_p:hi_p]; dsa_encoded_row_entries on the FIRST slot of an input
+ *   returns the cloud's row_entries in the global kept order (uint32[n]), on a later slot of the input it is refused and the message
+ *   names the first slot.  The part and local entry of input row r are searchsorted(first_entry, row_entries[r]) and the difference.
+ *   dsa_batch_source_rows works per slot, as with a split handle.
+ *   A cloud with ceil(n / N) > DSA_ENCODE_MAX_PARTS fails alone with DSA_ERR_INVALID_ARGUMENT (the host can only bound P by n); the
+ *   message names part_cells, n and the limit.
+ *   part_cells = 0: the bytes, the messages, the work, the rows and the handle shape of dsa_encode_split_sequential_batch.
+ * Fails the call with DSA_ERR_INVALID_ARGUMENT before any mesh is looked at, dsa_last_error naming the field: part_cells < 0;
+ * part_cells >= 1 with merge_points != 1, with point_order != 1, with geometry != 0, with part_points != 0; a non-zero reserved
+ * word.  Refusals of the nested option structs keep their own words.
+ * Not built: parts of sequential meshes, parts of the caller's order, a joined vertex-array layout of the parts on the decode side.
+ * Added after ABI 4 without changing it: callers detect the feature by the symbol dsa_encode_cell_parts_sequential_batch. */
+typedef struct dsa_encode_cell_parts_options {
+  dsa_encode_split_options split;          /* as for dsa_encode_split_sequential_batch, same legal values */
+  int32_t part_cells;                      /* 0 (default): the very request of the split call; N >= 1: parts of at most N kept points */
+  int32_t reserved[7];                     /* must be zero */
+} dsa_encode_cell_parts_options;
+void dsa_encode_default_cell_parts_options(dsa_encode_cell_parts_options *options);
+dsa_status dsa_encode_cell_parts_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids,
+                                                  const dsa_encode_cell_parts_options *options, dsa_encoded **out);
 /* The rows of a decoded batch per POINT: for every mesh of `batch` and every attribute a of its stream,
  *     rows[a][p] = entry_rows[a][map[a][p]]          (map: the decoder's point -> entry map, dsa_batch_device_point_map)
  * -- which row of the arrays given to the encoder point p carries, gathered on the device (k_source_rows) so that neither the maps
