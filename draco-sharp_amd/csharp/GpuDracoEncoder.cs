@@ -94,6 +94,20 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
     // NumPoints in kept order) and EntryRows(s) serve the parts, RowEntries(Parts(i).First) the cloud's row entries in the global
     // kept order.  Needs PointOrder 1 and MergePoints 1, and PartPoints 0; point clouds only.
     public int PartCells { get; set; }
+    // LodBaseBits (dsa_encode_lod_sequential_batch): additive levels of detail WITH PartCells.  0 no levels; D in 1 .. position bits
+    // puts the kept points of every cloud into L = position bits - D + 1 levels -- levels 0 .. l together are exactly one point per
+    // occupied cell of the grid with D + l bits per axis, the cell's first point in Morton order -- and cuts every level into parts
+    // of at most PartCells points.  The streams of an input are the parts of level 0, then of level 1, ...; Parts(i), PartInfo(s),
+    // EntryRows(s) and RowEntries(Parts(i).First) count in LOD order (kept by level, then by position in kept); LodInfo(s) says
+    // which level stream s belongs to.  Needs PartCells >= 1 (and so PointOrder 1 and MergePoints 1); point clouds only.
+    public int LodBaseBits { get; set; }
+    public struct LodLevel
+    {
+        public uint Input, Level, Levels, CellBits, LevelFirstStream, LevelStreams, LevelPoints, PartInLevel;
+    }
+    private LodLevel[] _lodInfo;
+    // Of stream s of the most recent Encode with LodBaseBits: which level it belongs to, and the streams and points of that level.
+    public LodLevel LodInfo(int s) => _lodInfo != null && s >= 0 && s < _lodInfo.Length ? _lodInfo[s] : throw new InvalidOperationException("no levels: set LodBaseBits before Encode");
     public struct PartBox
     {
         public uint Input, Part, Parts, FirstEntry, NumPoints, PositionBits;
@@ -210,6 +224,7 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
                     inputs[i].Faces = (uint*)Pin(faces, pins);
                 }
             }
+            if (LodBaseBits != 0 && PartCells == 0) throw new ArgumentException("LodBaseBits needs PartCells >= 1: every level is cut into parts of at most PartCells points");
             if (PartPoints != 0 || PartCells != 0)
             {
                 if (geometry != 0) throw new ArgumentException((PartCells != 0 ? "PartCells" : "PartPoints") + " takes point clouds: a part of a mesh would need its faces cut");
@@ -220,7 +235,16 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
                 po.PartPoints = PartPoints;
                 var ain = new DsaMeshAttrInput[items.Count];
                 for (int i = 0; i < items.Count; ++i) { ain[i].Mesh.Mesh = inputs[i]; Extras(items[i], null, (uint)items[i].PointsCount, ref ain[i], pins); }
-                if (PartCells != 0)             // (the widest call only when its option is set)
+                if (LodBaseBits != 0)           // (the widest call only when its option is set)
+                {
+                    NativeMethods.dsa_encode_default_lod_options(out var lo);
+                    lo.CellParts.Split = po;
+                    lo.CellParts.PartCells = PartCells;
+                    lo.LodBaseBits = LodBaseBits;
+                    fixed (DsaMeshAttrInput* p = ain)
+                        NativeMethods.Check(NativeMethods.dsa_encode_lod_sequential_batch(_ctx, (uint)items.Count, p, null, in lo, out encoded), _ctx, "dsa_encode_lod_sequential_batch");
+                }
+                else if (PartCells != 0)        // (the widest call only when its option is set)
                 {
                     NativeMethods.dsa_encode_default_cell_parts_options(out var co);
                     co.Split = po;
@@ -245,6 +269,16 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
                                             BoxMin = new[] { pi.BoxMin[0], pi.BoxMin[1], pi.BoxMin[2] }, BoxMax = new[] { pi.BoxMax[0], pi.BoxMax[1], pi.BoxMax[2] } };
                 }
                 _parts = parts; _partInfo = info;
+                if (LodBaseBits != 0)
+                {
+                    _lodInfo = new LodLevel[streams];
+                    for (uint s = 0; s < streams; ++s)
+                    {
+                        NativeMethods.Check(NativeMethods.dsa_encoded_lod_info(encoded, s, out var li), _ctx, $"stream {s}");
+                        _lodInfo[s] = new LodLevel { Input = li.Input, Level = li.Level, Levels = li.Levels, CellBits = li.CellBits, LevelFirstStream = li.LevelFirstStream,
+                                                     LevelStreams = li.LevelStreams, LevelPoints = li.LevelPoints, PartInLevel = li.PartInLevel };
+                    }
+                }
                 if (PartCells != 0)             // the row entries of every cloud, in the global kept order: kept with its first stream
                 {
                     _rowEntries = new uint[streams][];
@@ -321,6 +355,7 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
             for (int i = 0; i < meshes.Count; ++i) items[i] = meshes[i];
             return EncodeSequential(items, config, 1);
         }
+        if (LodBaseBits != 0) throw new ArgumentException("LodBaseBits takes point clouds: levels of meshes are not built");
         if (PartCells != 0) throw new ArgumentException("PartCells takes point clouds: a part of a mesh would need its faces cut");
         if (PartPoints != 0) throw new ArgumentException("PartPoints takes point clouds: a part of a mesh would need its faces cut");
         if (MergePoints != 0) throw new ArgumentException("MergePoints takes point clouds: merging the points of a mesh would collapse its faces and lose its seams");
@@ -567,7 +602,7 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
             NativeMethods.Check(NativeMethods.dsa_encoded_stream(encoded, i, out var bytes, out var length), _ctx, $"mesh {i}");
             result[i] = new ReadOnlySpan<byte>(bytes, (int)length).ToArray();
         }
-        _rowEntries = null; _parts = null; _partInfo = null;
+        _rowEntries = null; _parts = null; _partInfo = null; _lodInfo = null;
         if (TrackRows || PointOrder != 0) _entryRows = Rows(encoded, count);      // (a sequential handle answers with the identity, or with the point order)
         return result;
     }

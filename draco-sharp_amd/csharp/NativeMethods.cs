@@ -266,6 +266,28 @@ internal unsafe struct DsaEncodeCellPartsOptions
     public fixed int Reserved[7];   // zero
 }
 
+// dsa_encode_lod_options (dsa_encode_lod_sequential_batch)
+[StructLayout(LayoutKind.Sequential)]
+internal unsafe struct DsaEncodeLodOptions
+{
+    public DsaEncodeCellPartsOptions CellParts;
+    public int LodBaseBits;         // 0: the request of the cell-parts call; D >= 1: additive levels of detail of the kept points, level 0 on the grid of D bits per axis (needs PartCells >= 1)
+    public fixed int Reserved[7];   // zero
+}
+
+// dsa_lod_info (dsa_encoded_lod_info)
+[StructLayout(LayoutKind.Sequential)]
+internal unsafe struct DsaLodInfo
+{
+    public uint Input;
+    public uint Level, Levels;
+    public uint CellBits;
+    public uint LevelFirstStream, LevelStreams;
+    public uint LevelPoints;
+    public uint PartInLevel;
+    public fixed uint Reserved[4];  // zero
+}
+
 // dsa_part_info (dsa_encoded_part_info)
 [StructLayout(LayoutKind.Sequential)]
 internal unsafe struct DsaPartInfo
@@ -415,6 +437,9 @@ internal static unsafe partial class NativeMethods
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_split_sequential_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, in DsaEncodeSplitOptions options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern void dsa_encode_default_cell_parts_options(out DsaEncodeCellPartsOptions options);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_cell_parts_sequential_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, in DsaEncodeCellPartsOptions options, out IntPtr encoded);
+    [DllImport(Lib)] internal static extern void dsa_encode_default_lod_options(out DsaEncodeLodOptions options);
+    [DllImport(Lib)] internal static extern DsaStatus dsa_encode_lod_sequential_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, in DsaEncodeLodOptions options, out IntPtr encoded);
+    [DllImport(Lib)] internal static extern DsaStatus dsa_encoded_lod_info(IntPtr encoded, uint stream, out DsaLodInfo info);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encoded_parts(IntPtr encoded, uint input, out uint firstStream, out uint count);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encoded_part_info(IntPtr encoded, uint stream, out DsaPartInfo info);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_rows_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, DsaMeshAttributeCorners* corners, in DsaEncodeRowsOptions options, out IntPtr encoded);

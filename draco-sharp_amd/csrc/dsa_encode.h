@@ -31,6 +31,8 @@
 //                                                records each; the box of every part's position integers behind the sort
 //                              k_enc_part_cells  dsa_encode_cell_parts_sequential_batch, part_cells >= 1: both -- the KEPT order in parts, whose
 //                                                number and sizes follow from m on the device: part slots, sized behind k_enc_merge_scan
+//                              k_enc_lod_*       dsa_encode_lod_sequential_batch, lod_base_bits >= 1: the kept order by (level, kept), every
+//                                                level in parts: levels, scan, scatter, row entries and the slots, in place of k_enc_part_cells
 //         (dsa_encode_layout.h) the request of an entry point, the state of a chunk, the per-mesh checks and plans, the arena layout
 // Every entry point fills an EncRequest and calls encode_request; a chunk of it goes through the stages of encode_chunk (or of
 // encode_sequential_chunk, dsa_encode_sequential.h) on a lane.
@@ -1194,6 +1196,13 @@ static dsa_status enc_stage_attributes(dsa_context *ctx, EncLane &lane, EncChunk
       ENC_TRY(hipGetLastError());
       if (order_timing) { ENC_TRY(hipStreamSynchronize(st)); order_lap("point merge"); }
     }
+    if (L.lod) {               // lod_base_bits: the kept order by (level, kept) and the parts of every level, in place of the step below
+      dsa::enc_lod_launch([st](auto kernel, uint32_t grid_x, uint32_t grid_y, uint32_t block, auto... args) { hipLaunchKernelGGL(kernel, dim3(grid_x, grid_y), dim3(block), 0, st, args...); },
+                          arena, (const dsa::EncOrder *)(arena + L.ord_at), (uint32_t)L.ord.size(), (const dsa::EncOrderTile *)(arena + L.ord_tiles_at), (uint32_t)L.ord_tiles.size(),
+                          L.ord_passes, (dsa::EncPart *)(arena + L.parts_at), (uint32_t)L.parts.size(), d_streams, ns);
+      ENC_TRY(hipGetLastError());
+      if (order_timing) { ENC_TRY(hipStreamSynchronize(st)); order_lap("levels"); }
+    } else
     if (L.cell_parts) {        // part_cells: the kept order in parts -- k_enc_merge_scan has left m, the sizes of the part slots follow from it on the device
       dsa::enc_part_cells_launch([st](auto kernel, uint32_t grid_x, uint32_t grid_y, uint32_t block, auto... args) { hipLaunchKernelGGL(kernel, dim3(grid_x, grid_y), dim3(block), 0, st, args...); },
                                  (dsa::EncOrder *)(arena + L.ord_at), (uint32_t)L.ord.size(), (dsa::EncPart *)(arena + L.parts_at), (uint32_t)L.parts.size(), d_streams, ns, L.ord_passes);
@@ -1506,6 +1515,21 @@ static dsa_status enc_check_options(dsa_context *ctx, const dsa_encode_cell_part
   ENC_RESERVED(o, 7, "dsa_encode_cell_parts_options");
   return enc_check_options(ctx, o.split, null_argument);
 }
+// ... or that order by (level, kept), every level in parts (dsa_encode_order.h)
+static dsa_status enc_check_options(dsa_context *ctx, const dsa_encode_lod_options &o, bool null_argument) {
+  const dsa_encode_cell_parts_options &c = o.cell_parts;
+  const dsa_encode_merge_options &m = c.split.merge;
+  const int bits = (int)m.order.sequential.base.position_bits;
+  if (o.lod_base_bits < 0) ENC_REFUSE("lod_base_bits %d: 0 (the request of dsa_encode_cell_parts_sequential_batch) or the bits per axis of the grid of level 0, 1 .. position_bits", (int)o.lod_base_bits);
+  if (o.lod_base_bits >= 1 && c.part_cells == 0) ENC_REFUSE("lod_base_bits %d needs part_cells >= 1 (it was 0): every level is cut into parts of at most part_cells points", (int)o.lod_base_bits);
+  if (o.lod_base_bits >= 1 && m.merge_points != 1) ENC_REFUSE("lod_base_bits %d needs merge_points 1 (it was %d): the levels are levels of the kept points", (int)o.lod_base_bits, (int)m.merge_points);
+  if (o.lod_base_bits >= 1 && m.order.point_order != 1) ENC_REFUSE("lod_base_bits %d needs point_order 1 (it was %d): the level of a point follows from its neighbour in the Morton order", (int)o.lod_base_bits, (int)m.order.point_order);
+  if (o.lod_base_bits >= 1 && m.order.sequential.geometry != 0) ENC_REFUSE("lod_base_bits %d needs geometry 0 (it was %d): levels of meshes are not built", (int)o.lod_base_bits, (int)m.order.sequential.geometry);
+  ENC_RESERVED(o, 7, "dsa_encode_lod_options");
+  if (enc_check_options(ctx, c, null_argument) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+  if (o.lod_base_bits > bits) ENC_REFUSE("lod_base_bits %d is above position_bits %d: level 0 cannot be finer than the quantisation grid", (int)o.lod_base_bits, bits);
+  return DSA_OK;
+}
 #undef ENC_RESERVED
 #undef ENC_REFUSE
 
@@ -1774,15 +1798,24 @@ static dsa_status encode_edgebreaker(dsa_context *ctx, uint32_t n, const dsa_mes
   rq.track_rows = w.track_rows == 1;
   return encode_checked(ctx, rq, grids, o.grid.repair.topology == 1, out);
 }
-static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_cell_parts_options &c, dsa_encoded **out) {
-  if (enc_check_options(ctx, c, !ctx || !out || (n && !meshes)) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_lod_options &l, dsa_encoded **out) {
+  if (enc_check_options(ctx, l, !ctx || !out || (n && !meshes)) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+  const dsa_encode_cell_parts_options &c = l.cell_parts;
   const dsa_encode_split_options &s = c.split;
   const dsa_encode_merge_options &m = s.merge;
   const dsa_encode_order_options &o = m.order;
   EncRequest rq;
   rq.n = n; rq.meshes = meshes; rq.sequential = true;
-  rq.seq = o.sequential; rq.point_order = o.point_order == 1; rq.merge_points = m.merge_points == 1; rq.part_points = (uint32_t)s.part_points; rq.part_cells = (uint32_t)c.part_cells;
-  return encode_checked(ctx, rq, grids, false, out);
+  rq.seq = o.sequential; rq.point_order = o.point_order == 1; rq.merge_points = m.merge_points == 1; rq.part_points = (uint32_t)s.part_points; rq.part_cells = (uint32_t)c.part_cells; rq.lod_base_bits = (uint32_t)l.lod_base_bits;
+  const dsa_status st = encode_checked(ctx, rq, grids, false, out);
+  if (st == DSA_OK && rq.lod()) (*out)->lod_bits = rq.lod_base_bits;
+  return st;
+}
+static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_cell_parts_options &c, dsa_encoded **out) {
+  dsa_encode_lod_options l;
+  dsa_encode_default_lod_options(&l);
+  l.cell_parts = c;
+  return encode_sequential(ctx, n, meshes, grids, l, out);
 }
 static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_split_options &s, dsa_encoded **out) {
   dsa_encode_cell_parts_options c;
@@ -1861,6 +1894,11 @@ void dsa_encode_default_cell_parts_options(dsa_encode_cell_parts_options *o) {
   if (!o) return;
   memset(o, 0, sizeof(*o));
   dsa_encode_default_split_options(&o->split);
+}
+void dsa_encode_default_lod_options(dsa_encode_lod_options *o) {
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  dsa_encode_default_cell_parts_options(&o->cell_parts);
 }
 void dsa_encode_default_repair_options(dsa_encode_repair_options *o) {
   if (!o) return;
@@ -1987,6 +2025,11 @@ dsa_status dsa_encode_split_sequential_batch(dsa_context *ctx, uint32_t n, const
 dsa_status dsa_encode_cell_parts_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_cell_parts_options *options, dsa_encoded **out) {
   DSA_GUARD(ctx, [&] { dsa_encode_cell_parts_options o; dsa_encode_default_cell_parts_options(&o); if (options) o = *options; return encode_sequential(ctx, n, meshes, grids, o, out); }());
 }
+// ... or, with lod_base_bits >= 1, that order by (level, kept) and every level in parts (k_enc_lod_*, dsa_encode_order.h);
+// lod_base_bits = 0 is the very request of the call above.
+dsa_status dsa_encode_lod_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_lod_options *options, dsa_encoded **out) {
+  DSA_GUARD(ctx, [&] { dsa_encode_lod_options o; dsa_encode_default_lod_options(&o); if (options) o = *options; return encode_sequential(ctx, n, meshes, grids, o, out); }());
+}
 
 struct dsa_welded {
   dsa_context *ctx = nullptr;
@@ -2086,6 +2129,15 @@ dsa_status dsa_encoded_part_info(const dsa_encoded *e, uint32_t stream, dsa_part
   if (!e->split) return set_err(e->ctx, DSA_ERR_INVALID_ARGUMENT, "this handle has no parts: encode with dsa_encode_split_sequential_batch and part_points >= 1");
   if (e->status[stream] != DSA_OK) return set_err(e->ctx, (dsa_status)e->status[stream], "mesh %u: %s", stream, e->messages[stream].c_str());
   *out = e->part_info[stream];
+  return DSA_OK;
+}
+// Which level stream `stream` belongs to (lod_base_bits >= 1).
+dsa_status dsa_encoded_lod_info(const dsa_encoded *e, uint32_t stream, dsa_lod_info *out) {
+  if (!e || stream >= e->streams.size() || !out) return DSA_ERR_INVALID_ARGUMENT;
+  memset(out, 0, sizeof(*out));
+  if (e->lod_bits == 0 || e->lod_info.size() != e->streams.size()) return set_err(e->ctx, DSA_ERR_INVALID_ARGUMENT, "this handle has no levels: encode with dsa_encode_lod_sequential_batch and lod_base_bits >= 1");
+  if (e->status[stream] != DSA_OK) return set_err(e->ctx, (dsa_status)e->status[stream], "mesh %u: %s", stream, e->messages[stream].c_str());
+  *out = e->lod_info[stream];
   return DSA_OK;
 }
 // The entry rows of attribute `attribute` of stream `mesh`: a sequential handle answers with the identity (with point_order = 1:

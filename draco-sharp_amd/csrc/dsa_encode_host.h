@@ -2138,6 +2138,50 @@ static void cell_parts(const float *pos, uint32_t n, int bits, const Grid *grid,
         qmin[3 * p + c] = std::min(qmin[3 * p + c], x); qmax[3 * p + c] = std::max(qmax[3 * p + c], x);
       }
 }
+// Additive levels of detail of the kept points (dsa_encode_lod_sequential_batch, lod_base_bits = D >= 1; the device's kernels are
+// k_enc_lod_* of dsa_encode_order.h): with kept and key as merge_points has them, level(0) = 0 and for j >= 1 level(j) = max(0,
+// c + 1 - D), c the leading bit-triples out of `bits` that key(kept[j]) and key(kept[j - 1]) share.  lod is kept in ascending
+// (level, position in kept), row_entries the lod entry of the cell of every row; level l is cut by the rule of split_parts applied
+// to its m_l points (an empty level has no part), ranges / levels / qmin / qmax say where every part lies in lod, which level it
+// belongs to and the box of its position integers.
+static void lod_parts(const float *pos, uint32_t n, int bits, const Grid *grid, uint32_t part_cells, int base_bits, std::vector<uint32_t> &lod, std::vector<uint32_t> &row_entries,
+                      std::vector<std::pair<uint32_t, uint32_t>> &ranges, std::vector<uint32_t> &levels, std::vector<int32_t> &qmin, std::vector<int32_t> &qmax) {
+  check(base_bits >= 1 && base_bits <= bits, "lod_base_bits out of range (1 .. position bits)");
+  check(part_cells >= 1, "lod_base_bits needs part_cells >= 1");
+  std::vector<uint32_t> kept;
+  merge_points(pos, n, bits, grid, kept, row_entries);
+  PortableAttr a;
+  a.att_type = 0; a.nc = a.nc_out = 3; a.seq_type = 2; a.grid = grid;
+  quantize(pos, n, 3, bits, a);
+  const uint32_t m = (uint32_t)kept.size(), L = (uint32_t)(bits - base_bits + 1);
+  std::vector<uint32_t> level(m, 0), count(L, 0), place(m, 0);
+  for (uint32_t j = 1; j < m; ++j) {
+    const uint64_t x = point_order_key(a.vals.data() + (size_t)3 * kept[j], bits), y = point_order_key(a.vals.data() + (size_t)3 * kept[j - 1], bits);
+    int c = 0;
+    while (c < bits && (x >> (3 * (bits - 1 - c))) == (y >> (3 * (bits - 1 - c)))) ++c;
+    level[j] = (uint32_t)std::max(0, c + 1 - base_bits);
+    check(level[j] < L, "lod_parts: two kept points share a cell");
+  }
+  for (uint32_t j = 0; j < m; ++j) ++count[level[j]];
+  std::vector<uint32_t> base(L + 1, 0);
+  for (uint32_t l = 0; l < L; ++l) base[l + 1] = base[l] + count[l];
+  std::vector<uint32_t> next(base.begin(), base.end() - 1);
+  lod.resize(m);
+  for (uint32_t j = 0; j < m; ++j) { place[j] = next[level[j]]++; lod[place[j]] = kept[j]; }
+  for (uint32_t r = 0; r < n; ++r) row_entries[r] = place[row_entries[r]];
+  ranges.clear(); levels.clear();
+  for (uint32_t l = 0; l < L; ++l) {
+    const uint64_t parts = count[l] ? split_count(count[l], part_cells) : 0u;
+    for (uint64_t p = 0; p < parts; ++p) { ranges.push_back({base[l] + split_bound(count[l], parts, p), base[l] + split_bound(count[l], parts, p + 1)}); levels.push_back(l); }
+  }
+  qmin.assign(3 * ranges.size(), INT32_MAX); qmax.assign(3 * ranges.size(), INT32_MIN);
+  for (size_t p = 0; p < ranges.size(); ++p)
+    for (uint32_t e = ranges[p].first; e < ranges[p].second; ++e)
+      for (int c = 0; c < 3; ++c) {
+        const int32_t x = a.vals[(size_t)3 * lod[e] + c];
+        qmin[3 * p + c] = std::min(qmin[3 * p + c], x); qmax[3 * p + c] = std::max(qmax[3 * p + c], x);
+      }
+}
 // The float this library's decoder returns for integer q of a component on a grid (k_finalize, Dequantizer.cs:15-23): every step
 // rounded to float32, no fused multiply-add.
 static inline float dequantized(int32_t q, float origin, float range, int bits) {

@@ -136,7 +136,11 @@ struct dsa_encoded {
   // parts[input] holds the streams of its parts; flatten_parts then makes it one entry per STREAM: part_first[input] names an input's
   // slots (one for a refused input), part_info[stream] says which part it is, and order[] keeps perm once per cloud, in the slot
   // of its first part -- row_data serves every part its slice.
-  struct Part { std::vector<uint8_t> stream; dsa_part_info info; };
+  // (lod_base_bits >= 1: `lod` of a part says which level it is, level_first_stream counted from the input's first slot until
+  // flatten_parts; lod_info[stream] then answers dsa_encoded_lod_info, and lod_bits says the handle has levels)
+  struct Part { std::vector<uint8_t> stream; dsa_part_info info; dsa_lod_info lod; };
+  uint32_t lod_bits = 0;
+  std::vector<dsa_lod_info> lod_info;
   bool split = false;
   std::vector<std::vector<Part>> parts;
   std::vector<uint32_t> part_first;
@@ -176,12 +180,18 @@ struct dsa_encoded {
     dsa_part_info none;
     memset(&none, 0, sizeof(none));
     part_info.assign(total, none);
+    dsa_lod_info no_level;
+    memset(&no_level, 0, sizeof(no_level));
+    lod_info.assign(total, no_level);
     for (size_t i = 0; i < n; ++i) {
       const size_t f = part_first[i];
       if (status[i] != DSA_OK) { st2[f] = status[i]; m2[f].swap(messages[i]); part_info[f].input = (uint32_t)i; part_info[f].parts = 1; continue; }
       o2[f].swap(order[i]);
       if (merged) c2[f].swap(cells[i]);
-      for (size_t p = 0; p < parts[i].size(); ++p) { s2[f + p].swap(parts[i][p].stream); part_info[f + p] = parts[i][p].info; l2[f + p] = {linear[i].first, parts[i][p].info.num_points}; }
+      for (size_t p = 0; p < parts[i].size(); ++p) {
+        s2[f + p].swap(parts[i][p].stream); part_info[f + p] = parts[i][p].info; l2[f + p] = {linear[i].first, parts[i][p].info.num_points};
+        lod_info[f + p] = parts[i][p].lod; lod_info[f + p].level_first_stream += (uint32_t)f;
+      }
     }
     streams.swap(s2); status.swap(st2); messages.swap(m2); linear.swap(l2); order.swap(o2);
     if (merged) cells.swap(c2);
@@ -235,6 +245,9 @@ struct EncRequest {
   bool cell_parts() const { return sequential && point_order && merge_points && part_cells >= 1 && part_points == 0 && seq.geometry == 0 && !weld_sink; }
   bool split() const { return (sequential && point_order && !merge_points && part_points >= 1 && seq.geometry == 0 && !weld_sink) || cell_parts(); }
   uint32_t part_size() const { return cell_parts() ? part_cells : part_points; }      // N of either
+  uint32_t lod_base_bits = 0;              // dsa_encode_lod_sequential_batch, lod_base_bits D >= 1 (with part_cells): the kept order by (level, kept), every level in parts
+  bool lod() const { return cell_parts() && lod_base_bits >= 1; }
+  uint32_t lod_levels() const { return lod() ? (uint32_t)seq.base.position_bits - lod_base_bits + 1u : 1u; }      // L (D <= position_bits: enc_check_options)
   int rows_kind() const { return weld_sink ? dsa_encoded::ROWS_NONE : (sequential ? (point_order ? dsa_encoded::ROWS_ORDERED : dsa_encoded::ROWS_LINEAR) : (track_rows ? dsa_encoded::ROWS_TRACKED : dsa_encoded::ROWS_NONE)); }
   dsa_encode_level_options level{};        // Edgebreaker streams
   dsa_encode_sequential_options seq{};     // sequential streams
@@ -302,6 +315,7 @@ struct EncLayout {
   // (part, tile) pairs of all of them, both among the uploads
   bool split = false;
   bool cell_parts = false;                  // EncRequest::cell_parts: split and merge, a cloud's records are part SLOTS the device sizes (k_enc_part_cells)
+  bool lod = false;                         // EncRequest::lod: cell_parts whose slots are the parts of the cloud's levels (k_enc_lod_parts)
   std::vector<dsa::EncPart> parts;
   std::vector<dsa::EncPartTile> part_tiles;
   std::vector<uint32_t> part_of_mesh;
@@ -625,7 +639,14 @@ static void enc_check_sequential_mesh(EncChunk &ck, uint32_t i) {
   synth::plan_sequential_attributes(in, mo, ck.plans[i].atts);
   enc_extra_caps(ck, i);
   if (!ck.rq.split()) return;
-  const uint64_t parts = synth::split_count(m.num_vertices, ck.rq.part_size());
+  // (lod_base_bits: a level more can cost a slot more -- sum ceil(m_l / N) <= ceil(m / N) + non-empty levels - 1)
+  const uint64_t parts = synth::split_count(m.num_vertices, ck.rq.part_size()) + (ck.rq.lod_levels() - 1u);
+  if (parts > DSA_ENCODE_MAX_PARTS && ck.rq.lod()) {
+    char buf[240];
+    snprintf(buf, sizeof(buf), "lod_base_bits %u with part_cells %u may cut the cloud's n = %u points into %llu parts (ceil(n / part_cells) + %u levels - 1): at most %u (DSA_ENCODE_MAX_PARTS)",
+             ck.rq.lod_base_bits, ck.rq.part_cells, m.num_vertices, (unsigned long long)parts, ck.rq.lod_levels(), DSA_ENCODE_MAX_PARTS);
+    return ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, buf);
+  }
   if (parts > DSA_ENCODE_MAX_PARTS && ck.rq.cell_parts()) {       // (the host bounds the parts by the points that came in: the kept ones are the device's to count)
     char buf[200];
     snprintf(buf, sizeof(buf), "part_cells %u may cut the cloud's n = %u points into %llu parts: at most %u (DSA_ENCODE_MAX_PARTS)", ck.rq.part_cells, m.num_vertices, (unsigned long long)parts, DSA_ENCODE_MAX_PARTS);
@@ -900,12 +921,14 @@ static void enc_layout(EncChunk &ck) {
 // EncRequest::cell_parts (split and merge): P is the device's to know, so a cloud has P_max = ceil(n / part_cells) part SLOTS, each
 // with records, regions and tiles for min(part_cells, n) points -- under n + part_cells points per attribute in all; the streams' map
 // is the kept buffer, as with the merge, and k_enc_part_cells writes every slot's lo, n, nv and e2v.
+// EncRequest::lod (cell_parts with levels): ceil(n / part_cells) + L - 1 slots, the streams' map is the lod buffer, which with pos takes
+// the sort's dead key buffer; a level table per cloud among the kernels' regions; k_enc_lod_parts writes the slots.
 static void enc_layout_sequential(EncChunk &ck) {
   EncLayout &L = ck.L;
   const bool is_mesh = ck.rq.seq.geometry == 1, compressed = is_mesh && ck.rq.seq.compress_connectivity == 1, ordered = ck.rq.point_order;
   const bool merge = ordered && !is_mesh && ck.rq.merge_points, split = ck.rq.split();
   const bool cell_parts = ck.rq.cell_parts();
-  L.merge = merge; L.split = split; L.cell_parts = cell_parts;
+  L.merge = merge; L.split = split; L.cell_parts = cell_parts; L.lod = ck.rq.lod();
   if (merge || split) L.ord_of_mesh.assign(ck.n, DSA_INVALID);
   if (split) L.part_of_mesh.assign(ck.n, DSA_INVALID);
   EncArena A;
@@ -931,7 +954,7 @@ static void enc_layout_sequential(EncChunk &ck) {
       if (split) {                                             // the parts of the cloud: their sizes need nothing of the device
         L.part_of_mesh[i] = (uint32_t)L.parts.size();
         // (part_cells: the slots of the cloud, lo and n the device's to write -- k_enc_part_cells -- and tiles for the most a slot can hold)
-        if (cell_parts) { O.part_cells = ck.rq.part_cells; O.part0 = (uint32_t)L.parts.size(); O.part_slots = ck.num_parts(i); }
+        if (cell_parts) { O.part_cells = ck.rq.part_cells; O.part0 = (uint32_t)L.parts.size(); O.part_slots = ck.num_parts(i); O.lod_bits = L.lod ? ck.rq.lod_base_bits : 0u; }
         for (uint32_t p = 0, np = ck.num_parts(i); p < np; ++p) {
           dsa::EncPart P;
           memset(&P, 0, sizeof(P));
@@ -973,6 +996,8 @@ static void enc_layout_sequential(EncChunk &ck) {
       O.hist = A.take(4ull * ORD_RADIX * O.tiles);
       if (is_mesh) O.rank = A.take(4ull * V);
       if (merge) O.cells = A.take(4ull * V);
+      // (lod_base_bits: lod and pos in the key buffer the last pass read -- dead behind the merge, two u32[n] -- and the level table)
+      if (L.lod) { O.lod_rows = O.key[(L.ord_passes + 1u) & 1u]; O.lod_table = A.take(sizeof(dsa::EncLodTable)); }
       for (uint32_t k = 0; k < na; ++k) L.streams[s0 + k].e2v = O.row[(L.ord_passes + (merge ? 1u : 0u)) & 1u];
     }
     if (split) {

@@ -91,6 +91,40 @@
 // The host coder's twin is synth::cell_parts; tests/hostcheck/enccellparts_host.cpp runs the steps in the product's layout against
 // it, tests/test_gpu_encode_cell_parts.py the device's.
 // gfx950, hipcc -O3 (VGPR / SGPR / LDS bytes per block): k_enc_part_cells 25 / 18 / 0; no scratch, no spills, 8 waves per SIMD.
+//
+// dsa_encode_lod_sequential_batch with lod_base_bits = D >= 1 (point clouds, merge_points = 1, part_cells = N >= 1): additive levels
+// of detail of the kept points.  The kept keys are distinct and ascending; with c(j) the leading bit-triples, out of B = bits, that
+// key(kept[j]) and key(kept[j - 1]) share -- c = B - ceil(bitlength(key[j] ^ key[j - 1]) / 3) -- level(0) = 0 and level(j) = max(0,
+// c(j) + 1 - D), L = B - D + 1 <= ORD_LOD_LEVELS levels.  Levels 0 .. l together are one point per occupied cell of the grid with D + l
+// bits per axis, the cell's first point in Morton order.  lod is kept in ascending (level, position in kept); level l, m_l points from
+// base_l on, is cut by the rule of part_cells applied to m_l, and the slots of a cloud are the parts of level 0, then of level 1, ...
+// (an empty level has none).  sum ceil(m_l / N) <= ceil(m / N) + (non-empty levels - 1): the layout lays out ceil(n / N) + L - 1 slots.
+// Five steps behind enc_merge_launch, in place of k_enc_part_cells and in front of k_enc_part_bounds and k_enc_gather, on the merge's
+// (cloud, tile) list with tiles over KEPT entries (a tile at or beyond m returns at once):
+//   k_enc_lod_levels      a wave per tile: the level of every kept entry of the tile from ord_key of vals at kept[j] and kept[j - 1]
+//                         (entry 0 of a tile reads the last kept row of the tile in front: kept is only read from here on), kept in
+//                         pos[j] for the scatter; the tile's count per level by one ballot a level, to hist[level * tiles + tile]
+//                         (the histograms are done with, and L <= 20 fits the 256 digits)
+//   k_enc_lod_scan        a wave per cloud: exclusive scan of the counts in (level, tile) order over the tiles that hold kept
+//                         entries (the shuffle scan of k_enc_merge_scan), then m_l and base_l of every level into the cloud's
+//                         EncLodTable, a record of the kernels' own beside the cloud's
+//   k_enc_lod_scatter     a wave per tile, 64 consecutive entries a step in entry order: the lanes of equal level find each other by
+//                         5 ballots, a lane's place is the (level, tile) start plus the tile's running count of the level (LDS) plus
+//                         the lanes of its level below it, as in k_enc_order_scatter; lod[place] = kept[j], pos[j] = place.  Not in
+//                         place: lod and pos are the two u32[n] of the key buffer the last sort pass did not write, dead behind the
+//                         merge (EncOrder::lod_rows).  No atomic decides a place: the result is a function of the input alone.
+//   k_enc_lod_cells       a thread per input row: cells[r] = pos[cells[r]], row_entries from kept order to lod order
+//   k_enc_lod_parts       a thread per slot, no shuffle, LDS or atomic: it walks the at most 20 level counts to its level and part,
+//                         writes lo / n into the slot's EncPart and the level into its pad word, nv and e2v = lod + 4 lo into every
+//                         EncStream of the slot; a slot beyond the live ones gets n = nv = 0 and kind 3, exactly as k_enc_part_cells
+//                         makes it.
+// k_enc_part_bounds reads the lod buffer for such clouds (EncOrder::lod_bits says so).  k_enc_gather, k_enc_corr, k_enc_plan and
+// k_enc_rans are untouched: an empty slot goes through the ENC_PART_SIZED / kind 3 path of part_cells.  The host reads levels and
+// sizes from the EncPart records that come back and holds them to the rule (enc_write_parts).  The host coder's twin is
+// synth::lod_parts; tests/hostcheck/enclod_host.cpp runs the serial forms in the product's layout against it,
+// tests/test_gpu_encode_lod.py the ballots and shuffles.
+// gfx950, hipcc -O3 (VGPR / SGPR / LDS bytes per block): k_enc_lod_levels 26 / 33 / 0, scan 21 / 33 / 0, scatter 16 / 43 / 128, cells
+// 6 / 20 / 0, parts 44 / 19 / 0 (k_enc_part_bounds stays 18 / 22 / 0); no scratch, no spills, 8 waves per SIMD.
 #pragma once
 #include <stdint.h>
 
@@ -115,15 +149,22 @@ struct EncOrder {                  // one per cloud of the chunk; in the arena, 
   uint32_t stream0, streams;       // the cloud's value streams among the chunk's EncStream records: k_enc_merge_scan lowers their nv
   uint32_t m, part_cells;          // OUTPUT (merge): occupied cells; part_cells: not 0: the kept points in parts of at most so many (k_enc_part_cells),
   uint32_t part0, part_slots;      //   the cloud's part_slots = ceil(n / part_cells) EncPart records from part0 on, slot p with `streams` stream records
-};                                 //   from stream0 + p * streams on
+                                   //   from stream0 + p * streams on
+  uint32_t lod_bits, lod_pad;      // lod_base_bits D (0: no levels); not 0: part_slots = ceil(n / part_cells) + bits - D and the two fields below are set
+  uint64_t lod_rows;               // u32[n] OUTPUT lod[m], the kept rows in (level, kept) order -- the e2v of the cloud's streams -- and behind it u32[n] pos[m],
+                                   //   the place of every kept entry in lod: the key buffer the last sort pass did not write, key[(passes + 1) & 1]
+  uint64_t lod_table;              // EncLodTable OUTPUT: points and first lod entry of every level
+};
 struct EncOrderTile { uint32_t cloud, tile; };
 struct EncPart {                   // one per part of a split cloud, the parts of a cloud side by side; in the arena, among the uploads
   uint32_t cloud;                  // its cloud among the chunk's EncOrder records
   uint32_t lo, n;                  // sorted entries lo .. lo + n of the cloud
   int32_t qmin[3], qmax[3];        // OUTPUT per component over vals of the part's rows (the layout sets INT32_MAX / INT32_MIN)
-  uint32_t pad;
+  uint32_t pad;                    // OUTPUT (lod_base_bits >= 1): the level of the slot (k_enc_lod_parts); else 0
 };
 struct EncPartTile { uint32_t part, tile; };
+#define ORD_LOD_LEVELS 20u         // position_bits is at most 20 (enc_check_bits): L = bits - D + 1 <= 20
+struct EncLodTable { uint32_t count[ORD_LOD_LEVELS], base[ORD_LOD_LEVELS]; };      // m_l and base_l of a cloud (k_enc_lod_scan), zero from L on
 
 static inline uint32_t enc_order_passes(uint32_t bits) { return (3u * bits + 7u) / 8u; }
 
@@ -408,6 +449,189 @@ static inline void enc_part_cells_launch(Launch &&launch, EncOrder *clouds, uint
   launch(k_enc_part_cells<Stream>, (np + (uint32_t)WAVE - 1u) / (uint32_t)WAVE, 1u, (uint32_t)WAVE, clouds, nc, parts, np, streams, ns, passes);
 }
 
+// ---- lod_base_bits (the header comment has the contract): behind enc_merge_launch, in place of enc_part_cells_launch
+// The level of a kept point from its key and the key of the kept point in front of it: c leading bit-triples in common out of
+// `bits`, level max(0, c + 1 - D).  (Equal keys never come here, the kept keys are distinct: the comparison keeps the level below L.)
+__device__ __forceinline__ uint32_t ord_lod_level(uint64_t a, uint64_t b, uint32_t bits, uint32_t base_bits) {
+  const uint64_t x = a ^ b;
+#if defined(__HIPCC__)
+  const uint32_t len = x ? 64u - (uint32_t)__clzll((long long)x) : 0u;
+#else
+  const uint32_t len = x ? 64u - (uint32_t)__builtin_clzll(x) : 0u;
+#endif
+  const uint32_t triples = (len + 2u) / 3u, c = triples < bits ? bits - triples : 0u, top = bits - base_bits;
+  const uint32_t level = c + 1u > base_bits ? c + 1u - base_bits : 0u;
+  return level < top ? level : top;
+}
+
+// grid = the chunk's (cloud, tile) pairs, tiles over KEPT entries
+__global__ __launch_bounds__(WAVE) void k_enc_lod_levels(uint8_t *arena, const EncOrder *clouds, const EncOrderTile *tiles, uint32_t nt, uint32_t passes) {
+  if (blockIdx.x >= nt) return;
+  const EncOrderTile T = tiles[blockIdx.x];
+  const EncOrder &O = clouds[T.cloud];
+  if (O.lod_bits == 0u || O.lod_bits > O.bits || O.bits - O.lod_bits >= ORD_LOD_LEVELS) return;
+  const uint32_t m = O.m < O.n ? O.m : O.n, e0 = T.tile * ORD_TILE;
+  if (e0 >= m) return;
+  const uint32_t lane = threadIdx.x, end = m - e0 < ORD_TILE ? m : e0 + ORD_TILE, levels = O.bits - O.lod_bits + 1u;
+  const int32_t *vals = (const int32_t *)(arena + O.vals);
+  const uint32_t *kept = (const uint32_t *)(arena + O.row[(passes + 1u) & 1u]);
+  uint32_t *pos = (uint32_t *)(arena + O.lod_rows) + O.n;       // (the level of every kept entry until k_enc_lod_scatter puts its place there)
+  uint32_t *hist = (uint32_t *)(arena + O.hist);
+#if defined(__HIPCC__)
+  uint32_t mine = 0;                                           // lane l: the tile's entries of level l
+  for (uint32_t s0 = e0; s0 < end; s0 += WAVE) {               // (uniform: every lane takes every step)
+    const uint32_t j = s0 + lane;
+    const bool valid = j < end;
+    uint32_t level = 0;
+    if (valid && j != 0u) {
+      const uint32_t r = kept[j], q = kept[j - 1u];
+      if (r < O.n && q < O.n) level = ord_lod_level(ord_key(vals + 3ull * r, O.bits), ord_key(vals + 3ull * q, O.bits), O.bits, O.lod_bits);
+    }
+    if (valid) pos[j] = level;
+    for (uint32_t l = 0; l < levels; ++l) {
+      const uint32_t c = (uint32_t)__popcll(__ballot(valid && level == l));
+      if (lane == l) mine += c;
+    }
+  }
+  if (lane < levels) hist[(size_t)lane * O.tiles + T.tile] = mine;
+#else       // (as k_enc_order_hist: lane 0 counts)
+  if (lane != 0) return;
+  for (uint32_t l = 0; l < levels; ++l) hist[(size_t)l * O.tiles + T.tile] = 0;
+  for (uint32_t j = e0; j < end; ++j) {
+    const uint32_t level = j == 0u ? 0u : ord_lod_level(ord_key(vals + 3ull * kept[j], O.bits), ord_key(vals + 3ull * kept[j - 1u], O.bits), O.bits, O.lod_bits);
+    pos[j] = level;
+    hist[(size_t)level * O.tiles + T.tile] += 1u;
+  }
+#endif
+}
+
+// one wave per cloud: blockIdx.x = cloud.  The counts of the tiles that hold kept entries, in (level, tile) order.
+__global__ __launch_bounds__(WAVE) void k_enc_lod_scan(uint8_t *arena, const EncOrder *clouds, uint32_t nc) {
+  if (blockIdx.x >= nc) return;
+  const EncOrder &O = clouds[blockIdx.x];
+  if (O.lod_bits == 0u || O.lod_bits > O.bits || O.bits - O.lod_bits >= ORD_LOD_LEVELS) return;
+  const uint32_t m = O.m < O.n ? O.m : O.n, live = (m + ORD_TILE - 1u) / ORD_TILE, levels = O.bits - O.lod_bits + 1u;
+  const uint32_t total = levels * live, lane = threadIdx.x;     // (live <= 2^18, levels <= 20)
+  uint32_t *hist = (uint32_t *)(arena + O.hist);
+  EncLodTable &table = *(EncLodTable *)(arena + O.lod_table);
+  uint32_t base = 0;
+#if defined(__HIPCC__)
+  for (uint32_t i0 = 0; i0 < total; i0 += WAVE) {
+    const uint32_t i = i0 + lane, l = i < total ? i / live : 0u;
+    const size_t at = (size_t)l * O.tiles + (i - l * live);
+    const uint32_t x = i < total ? hist[at] : 0u;
+    uint32_t incl = x;
+    for (int d = 1; d < WAVE; d <<= 1) { const uint32_t y = (uint32_t)__shfl_up((int)incl, d, WAVE); if ((int)lane >= d) incl += y; }
+    if (i < total) hist[at] = base + incl - x;
+    base += (uint32_t)__shfl((int)incl, WAVE - 1, WAVE);
+  }
+  __syncthreads();                                             // (the starts written above, read below by other lanes of the wave)
+  if (lane < ORD_LOD_LEVELS) {
+    const uint32_t first = lane < levels && live ? hist[(size_t)lane * O.tiles] : 0u, next = lane + 1u < levels && live ? hist[(size_t)(lane + 1u) * O.tiles] : base;
+    table.base[lane] = lane < levels ? first : 0u;
+    table.count[lane] = lane < levels ? next - first : 0u;
+  }
+#else       // (as k_enc_order_hist: lane 0 sums)
+  if (lane != 0) return;
+  for (uint32_t l = 0; l < ORD_LOD_LEVELS; ++l) { table.base[l] = 0; table.count[l] = 0; }
+  for (uint32_t l = 0; l < levels; ++l) {
+    table.base[l] = base;
+    for (uint32_t t = 0; t < live; ++t) { const uint32_t x = hist[(size_t)l * O.tiles + t]; hist[(size_t)l * O.tiles + t] = base; base += x; }
+    table.count[l] = base - table.base[l];
+  }
+#endif
+}
+
+__global__ __launch_bounds__(WAVE) void k_enc_lod_scatter(uint8_t *arena, const EncOrder *clouds, const EncOrderTile *tiles, uint32_t nt, uint32_t passes) {
+  if (blockIdx.x >= nt) return;
+  const EncOrderTile T = tiles[blockIdx.x];
+  const EncOrder &O = clouds[T.cloud];
+  if (O.lod_bits == 0u || O.lod_bits > O.bits || O.bits - O.lod_bits >= ORD_LOD_LEVELS) return;
+  const uint32_t m = O.m < O.n ? O.m : O.n, e0 = T.tile * ORD_TILE;
+  if (e0 >= m) return;
+  const uint32_t lane = threadIdx.x, end = m - e0 < ORD_TILE ? m : e0 + ORD_TILE, levels = O.bits - O.lod_bits + 1u;
+  const uint32_t *kept = (const uint32_t *)(arena + O.row[(passes + 1u) & 1u]);
+  uint32_t *lod = (uint32_t *)(arena + O.lod_rows), *pos = lod + O.n;
+  const uint32_t *hist = (const uint32_t *)(arena + O.hist);
+#if defined(__HIPCC__)
+  __shared__ uint32_t s_next[32];                              // where the tile's next entry of every level goes
+  if (lane < 32u) s_next[lane] = lane < levels ? hist[(size_t)lane * O.tiles + T.tile] : 0u;
+  __syncthreads();
+  const unsigned long long below = (1ull << lane) - 1ull;
+  for (uint32_t s0 = e0; s0 < end; s0 += WAVE) {               // (uniform: every lane takes every step)
+    const uint32_t j = s0 + lane;
+    const bool valid = j < end;
+    const uint32_t r = valid ? kept[j] : 0u, seen = valid ? pos[j] : 0u, level = seen < levels ? seen : levels - 1u;
+    unsigned long long same = __ballot(valid);                 // the lanes of this lane's level
+    for (uint32_t b = 0; b < 5u; ++b) {
+      const bool bit = ((level >> b) & 1u) != 0;
+      const unsigned long long with = __ballot(valid && bit);
+      same &= bit ? with : ~with;
+    }
+    const uint32_t at = valid ? s_next[level] : 0u;
+    __syncthreads();                                           // (every lane has read before a level's lowest lane advances its count)
+    if (valid && (same & below) == 0ull) s_next[level] = at + (uint32_t)__popcll(same);
+    __syncthreads();
+    const uint32_t to = at + (uint32_t)__popcll(same & below);
+    if (valid && to < O.n) { lod[to] = r; pos[j] = to; }       // (to < m by the scan: the comparison keeps a fault elsewhere inside the cloud's buffers)
+  }
+#else       // (as k_enc_order_hist: lane 0 places the tile's entries in their order)
+  if (lane != 0) return;
+  uint32_t next[ORD_LOD_LEVELS];
+  for (uint32_t l = 0; l < levels; ++l) next[l] = hist[(size_t)l * O.tiles + T.tile];
+  for (uint32_t j = e0; j < end; ++j) { const uint32_t to = next[pos[j]]++; lod[to] = kept[j]; pos[j] = to; }
+#endif
+}
+
+// a thread per input row: row_entries from kept order to lod order
+__global__ __launch_bounds__(256) void k_enc_lod_cells(uint8_t *arena, const EncOrder *clouds, const EncOrderTile *tiles, uint32_t nt) {
+  if (blockIdx.x >= nt) return;
+  const EncOrderTile T = tiles[blockIdx.x];
+  const EncOrder &O = clouds[T.cloud];
+  if (O.lod_bits == 0u || O.cells == 0) return;
+  const uint32_t m = O.m < O.n ? O.m : O.n;
+  uint32_t *cells = (uint32_t *)(arena + O.cells);
+  const uint32_t *pos = (const uint32_t *)(arena + O.lod_rows) + O.n;
+  const uint32_t end = O.n - T.tile * ORD_TILE < ORD_TILE ? O.n : (T.tile + 1u) * ORD_TILE;
+  for (uint32_t r = T.tile * ORD_TILE + threadIdx.x; r < end; r += blockDim.x) { const uint32_t j = cells[r]; if (j < m) cells[r] = pos[j]; }
+}
+
+// a thread per part slot of the chunk: k_enc_part_cells with a level table
+template <class Stream>
+__global__ __launch_bounds__(WAVE) void k_enc_lod_parts(uint8_t *arena, const EncOrder *clouds, uint32_t nc, EncPart *parts, uint32_t np, Stream *streams, uint32_t ns) {
+  const uint32_t i = blockIdx.x * WAVE + threadIdx.x;
+  if (i >= np) return;
+  EncPart &P = parts[i];
+  if (P.cloud >= nc) return;
+  const EncOrder &O = clouds[P.cloud];
+  if (O.lod_bits == 0u || O.lod_bits > O.bits || O.bits - O.lod_bits >= ORD_LOD_LEVELS || O.part_cells == 0u || i < O.part0 || i - O.part0 >= O.part_slots) return;       // (never by the layout)
+  const EncLodTable &table = *(const EncLodTable *)(arena + O.lod_table);
+  const uint32_t levels = O.bits - O.lod_bits + 1u;
+  uint64_t p = i - O.part0;
+  uint32_t lo = 0, cnt = 0, level = 0;
+  for (uint32_t l = 0; l < levels; ++l) {
+    const uint64_t ml = table.count[l], live = (ml + O.part_cells - 1u) / O.part_cells;
+    if (p < live) { lo = table.base[l] + (uint32_t)(p * ml / live); cnt = (uint32_t)((p + 1u) * ml / live) - (uint32_t)(p * ml / live); level = l; break; }      // (64 bits: p m < 2^16 2^28)
+    p -= live;
+  }
+  if (lo > O.n || cnt > O.n - lo) { lo = 0; cnt = 0; level = 0; }      // (never by the scan: the comparison keeps a fault elsewhere inside the cloud's buffers)
+  P.lo = lo; P.n = cnt; P.pad = level;
+  const uint64_t rows = O.lod_rows + 4ull * lo, s0 = (uint64_t)O.stream0 + (uint64_t)(i - O.part0) * O.streams;
+  for (uint32_t k = 0; k < O.streams; ++k) if (s0 + k < ns) { Stream &S = streams[s0 + k]; S.nv = cnt; S.e2v = rows; if (cnt == 0u) S.kind = 3u; }      // (empty: an empty list, which every step passes by)
+}
+
+// The levels behind enc_merge_launch and in front of enc_part_launch, on the merge's lists and the chunk's np EncPart records (slots).
+template <class Launch, class Stream>
+static inline void enc_lod_launch(Launch &&launch, uint8_t *arena, const EncOrder *clouds, uint32_t nc, const EncOrderTile *tiles, uint32_t nt, uint32_t passes,
+                                  EncPart *parts, uint32_t np, Stream *streams, uint32_t ns) {
+  if (nc == 0 || nt == 0 || np == 0) return;
+  launch(k_enc_lod_levels, nt, 1u, (uint32_t)WAVE, arena, clouds, tiles, nt, passes);
+  launch(k_enc_lod_scan, nc, 1u, (uint32_t)WAVE, arena, clouds, nc);
+  launch(k_enc_lod_scatter, nt, 1u, (uint32_t)WAVE, arena, clouds, tiles, nt, passes);
+  launch(k_enc_lod_cells, nt, 1u, 256u, arena, clouds, tiles, nt);
+  launch(k_enc_lod_parts<Stream>, (np + (uint32_t)WAVE - 1u) / (uint32_t)WAVE, 1u, (uint32_t)WAVE, arena, clouds, nc, parts, np, streams, ns);
+}
+
 // ---- part_points (the header comment has the contract): grid = the chunk's (part, tile) pairs, one wave each
 __global__ __launch_bounds__(WAVE) void k_enc_part_bounds(uint8_t *arena, const EncOrder *clouds, uint32_t nc, EncPart *parts, uint32_t np, const EncPartTile *tiles, uint32_t nt,
                                                           uint32_t passes) {
@@ -420,7 +644,8 @@ __global__ __launch_bounds__(WAVE) void k_enc_part_bounds(uint8_t *arena, const 
   const uint32_t t0 = T.tile * ORD_TILE;
   if (t0 >= P.n || P.lo > O.n || P.n > O.n - P.lo) return;       // (never by the layout: the comparisons keep a fault elsewhere inside the cloud's buffers)
   const int32_t *vals = (const int32_t *)(arena + O.vals);
-  const uint32_t *row = (const uint32_t *)(arena + O.row[(passes + (O.merge ? 1u : 0u)) & 1u]);     // (merge: the parts are runs of the kept rows)
+  // (merge: the parts are runs of the kept rows; lod_bits: of the kept rows in (level, kept) order)
+  const uint32_t *row = (const uint32_t *)(arena + (O.lod_bits ? O.lod_rows : O.row[(passes + (O.merge ? 1u : 0u)) & 1u]));
   const uint32_t lane = threadIdx.x, e0 = P.lo + t0, end = P.lo + (P.n - t0 < ORD_TILE ? P.n : t0 + ORD_TILE);
   int32_t mn[3] = {0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF}, mx[3] = {(int32_t)0x80000000, (int32_t)0x80000000, (int32_t)0x80000000};
 #if defined(__HIPCC__)

@@ -17,6 +17,8 @@
 //                                sorted order, and the box of every part's position integers; the host writes a stream per part
 //          k_enc_part_cells      dsa_encode_cell_parts_sequential_batch, part_cells >= 1 (point clouds, merge_points = 1): part slots whose
 //                                sizes the device writes behind k_enc_merge_scan; the host writes a stream per slot that came back with points
+//          k_enc_lod_*           dsa_encode_lod_sequential_batch, lod_base_bits >= 1: the kept rows by (level, kept) and the slots as the parts
+//                                of every level, in place of k_enc_part_cells; the host reads the level of every slot from its record
 //          k_enc_seq_indices     compressed indices: symbols and their statistics (dsa_encode_seqidx.h)
 //          k_enc_plan / k_enc_rans   every stream, the index stream as a list whose symbols are given (kind 3)
 //   host   stream layout (synth::write_sequential_stream)
@@ -32,14 +34,37 @@ static void enc_write_parts(EncChunk &ck, uint32_t i) {
   const bool cells = L.cell_parts;
   uint32_t V = ck.mesh(i).num_vertices;
   const uint32_t s0 = L.first_stream[i], na = (uint32_t)atts.size(), rows = V, np = cells ? ck.live_parts(i, &V) : ck.num_parts(i);
-  if (cells && (np == 0 || V == 0 || V > rows || np != synth::split_count(V, ck.rq.part_cells) || ck.row_cells[s0].size() != rows)) return ck.refuse(i, DSA_ERR_DEVICE, "the merged points and their parts did not come back");
+  const bool lod = L.lod;
+  if (cells && (np == 0 || V == 0 || V > rows || (!lod && np != synth::split_count(V, ck.rq.part_cells)) || ck.row_cells[s0].size() != rows)) return ck.refuse(i, DSA_ERR_DEVICE, "the merged points and their parts did not come back");
   if (ck.entry_rows[s0].size() != V || ck.part_boxes[s0].size() != np) return ck.refuse(i, DSA_ERR_DEVICE, "the point order and the part boxes did not come back");
+  // lod_base_bits: the slots are the parts of level 0, then of level 1, ...; the records say which level (EncPart::pad), and the
+  // points and parts of a level follow from them -- every level cut by the rule of part_cells, the levels side by side in lod order
+  const uint32_t levels = ck.rq.lod_levels();
+  std::vector<uint32_t> level_points(levels, 0), level_parts(levels, 0), level_first(levels, 0), level_base(levels, 0);
+  if (lod) {
+    for (uint32_t p = 0; p < np; ++p) {
+      const dsa::EncPart &P = ck.part_boxes[s0][p];
+      if (P.pad >= levels || (p && P.pad < ck.part_boxes[s0][p - 1].pad)) return ck.refuse(i, DSA_ERR_DEVICE, "the levels of the parts did not come back");
+      if (level_parts[P.pad]++ == 0) { level_first[P.pad] = p; level_base[P.pad] = P.lo; }
+      level_points[P.pad] += P.n;
+    }
+    uint32_t at = 0;
+    for (uint32_t l = 0; l < levels; ++l) {
+      if (level_parts[l] != synth::split_count(level_points[l], ck.rq.part_cells) || (level_parts[l] && level_base[l] != at)) return ck.refuse(i, DSA_ERR_DEVICE, "the levels of the parts did not come back");
+      if (level_parts[l] == 0) { level_base[l] = at; level_first[l] = l ? level_first[l - 1] + level_parts[l - 1] : 0u; }
+      at += level_points[l];
+    }
+  }
   const dsa::EncStream &pos = L.streams[s0];
   std::vector<dsa_encoded::Part> parts(np);
   for (uint32_t p = 0; p < np; ++p) {
     const dsa::EncPart &P = ck.part_boxes[s0][p];
     dsa::EncPart laid = L.parts[L.part_of_mesh[i] + p];
-    if (cells) { laid.lo = synth::split_bound(V, np, p); laid.n = synth::split_bound(V, np, p + 1u) - laid.lo; }
+    if (cells && !lod) { laid.lo = synth::split_bound(V, np, p); laid.n = synth::split_bound(V, np, p + 1u) - laid.lo; }
+    if (lod) {
+      const uint32_t l = P.pad, q = p - level_first[l];
+      laid.lo = level_base[l] + synth::split_bound(level_points[l], level_parts[l], q); laid.n = level_base[l] + synth::split_bound(level_points[l], level_parts[l], q + 1u) - laid.lo;
+    }
     const uint32_t sp = s0 + p * na;
     if (P.lo != laid.lo || P.n != laid.n || L.streams[sp].nv != P.n || P.n == 0 || P.qmin[0] > P.qmax[0]) return ck.refuse(i, DSA_ERR_DEVICE, "the point order and the part boxes did not come back");
     synth::ByteWriter w;
@@ -57,6 +82,11 @@ static void enc_write_parts(EncChunk &ck, uint32_t i) {
       info.box_min[c] = synth::dequantized(P.qmin[c], pos.qmin[c], pos.qrange, (int)pos.bits);
       info.box_max[c] = synth::dequantized(P.qmax[c], pos.qmin[c], pos.qrange, (int)pos.bits);
     }
+    dsa_lod_info &li = parts[p].lod;
+    memset(&li, 0, sizeof(li));
+    if (!lod) continue;
+    li.input = ck.base + i; li.level = P.pad; li.levels = levels; li.cell_bits = ck.rq.lod_base_bits + P.pad;
+    li.level_first_stream = level_first[P.pad]; li.level_streams = level_parts[P.pad]; li.level_points = level_points[P.pad]; li.part_in_level = p - level_first[P.pad];
   }
   ck.E->parts[i].swap(parts);
   ck.E->order[i].swap(ck.entry_rows[s0]);

@@ -88,7 +88,15 @@ class Config:
     cloud's one quantisation grid (the bounds of all n input rows).  The EncodedStreams runs over STREAMS as with part_points:
     parts(i), part_info(s) (first_entry / num_points in kept order) and entry_rows(s) = kept[lo:hi]; row_entries(parts(i)[0]) is the
     cloud's row_entries in the global kept order, row_parts(i) turns it into (part, entry) per input row.  Needs a sequential config
-    with point_order=POINT_ORDER_MORTON and merge_points=MERGE_CELLS, and no part_points."""
+    with point_order=POINT_ORDER_MORTON and merge_points=MERGE_CELLS, and no part_points.
+
+    lod_base_bits (dsa_encode_lod_sequential_batch): additive levels of detail WITH part_cells.  0 no levels; D in 1 .. position_bits
+    puts the kept points of every cloud into L = position_bits - D + 1 levels -- levels 0 .. l together are exactly one point per
+    occupied cell of the grid with D + l bits per axis, the cell's first point in Morton order -- and cuts every level into parts of
+    at most part_cells points (part_cells >= n: one stream per level).  The streams of an input are the parts of level 0, then of
+    level 1, ...; parts(i), part_info(s), entry_rows(s), row_entries(parts(i)[0]) and row_parts(i) count in LOD order (kept by
+    ascending (level, position in kept)); lod_info(s) says which level stream s belongs to, levels(i) gives the streams of every
+    level.  Needs part_cells >= 1 (and so point_order=POINT_ORDER_MORTON and merge_points=MERGE_CELLS)."""
 
     EDGEBREAKER_METHODS = (0, 2, -1)
     POSITION_PREDICTIONS = (0, 1)
@@ -103,7 +111,8 @@ class Config:
     def __init__(self, position_bits=11, texcoord_bits=10, normal_bits=8, speed=5, single_connectivity=False,
                  symbol_scheme=-1, position_prediction=1, texcoord_prediction=1, edgebreaker_method=0, normal_prediction=0,
                  encoding_method=1, compress_connectivity=False, multi_parallelogram=0, traversal_method=0, repair_topology=False, weld_points=False,
-                 repair_seams=False, weld_attributes=False, track_rows=False, point_order=0, merge_points=0, part_points=0, part_cells=0):
+                 repair_seams=False, weld_attributes=False, track_rows=False, point_order=0, merge_points=0, part_points=0, part_cells=0,
+                 lod_base_bits=0):
         for name, value, legal in (("encoding_method", encoding_method, self.ENCODING_METHODS),
                                    ("edgebreaker_method", edgebreaker_method, self.EDGEBREAKER_METHODS),
                                    ("position_prediction", position_prediction, self.POSITION_PREDICTIONS),
@@ -155,6 +164,15 @@ class Config:
             raise ValueError("part_cells cuts the kept order of merge_points into parts: it needs a sequential config (encoding_method 0) with point_order=POINT_ORDER_MORTON and merge_points=MERGE_CELLS")
         # (part_cells together with part_points never gets here: part_points has refused the merge_points that part_cells needs)
 
+        self.lod_base_bits = int(lod_base_bits)
+        if self.lod_base_bits < 0:
+            raise ValueError("lod_base_bits %r: 0 (no levels) or the bits per axis of the grid of level 0, 1 .. position_bits" % (lod_base_bits,))
+        if self.lod_base_bits > self.position_bits:
+            raise ValueError("lod_base_bits %r is above position_bits %r: level 0 cannot be finer than the quantisation grid" % (lod_base_bits, self.position_bits))
+        if self.lod_base_bits != 0 and self.part_cells == 0:
+            raise ValueError("lod_base_bits puts the kept points of merge_points into levels and cuts every level into parts: it needs part_cells >= 1 "
+                             "(a sequential config with point_order=POINT_ORDER_MORTON and merge_points=MERGE_CELLS)")
+
     @property
     def sequential(self):
         """True when meshes are written as sequential streams: asked for, or by the reference's rule at speed 10."""
@@ -194,6 +212,13 @@ class Config:
         native.lib().dsa_encode_default_cell_parts_options(C.byref(o))
         o.split = self._native_split(geometry)
         o.part_cells = self.part_cells
+        return o
+
+    def _native_lod(self, geometry):
+        o = native.EncodeLodOptions()
+        native.lib().dsa_encode_default_lod_options(C.byref(o))
+        o.cell_parts = self._native_cell_parts(geometry)
+        o.lod_base_bits = self.lod_base_bits
         return o
 
     @property
@@ -613,6 +638,25 @@ class EncodedStreams:
             raise ValueError("the encoded batch was closed")
         return _part_info(self._ctx, self._h, s + len(self) if s < 0 else s)
 
+    def lod_info(self, s):
+        """Of stream s of an encode with Config(lod_base_bits=D) a native.LodInfo: input, level, levels (L), cell_bits (D + level),
+        level_first_stream / level_streams (the streams of its level), level_points and part_in_level; dsa_encoded_lod_info."""
+        if self._h is None:
+            raise ValueError("the encoded batch was closed")
+        return _lod_info(self._ctx, self._h, s + len(self) if s < 0 else s)
+
+    def levels(self, i):
+        """The streams of input i of an encode with Config(lod_base_bits=D) per level: a list of L ranges of streams, level 0 first,
+        an empty range for a level without points."""
+        r = self.parts(i)
+        out, s = [], r.start
+        for level in range(self.lod_info(s).levels):
+            info = self.lod_info(s) if s < r.stop else None
+            count = info.level_streams if info is not None and info.level == level else 0
+            out.append(range(s, s + count))
+            s += count
+        return out
+
     def close(self):
         """Releases the library's buffers (streams already taken stay valid)."""
         if self._h is not None:
@@ -690,6 +734,15 @@ def _part_info(ctx, handle, s):
     """dsa_encoded_part_info of stream s."""
     info = native.PartInfo()
     st = native.lib().dsa_encoded_part_info(handle, s, C.byref(info))
+    if st != 0:
+        _raise(st, ctx.error())
+    return info
+
+
+def _lod_info(ctx, handle, s):
+    """dsa_encoded_lod_info of stream s."""
+    info = native.LodInfo()
+    st = native.lib().dsa_encoded_lod_info(handle, s, C.byref(info))
     if st != 0:
         _raise(st, ctx.error())
     return info
@@ -801,7 +854,12 @@ class DracoEncoder:
         n = len(meshes)
         arr, grids, keep = _native_meshes(meshes)
         h = C.c_void_p()
-        if getattr(config, "part_cells", 0) != 0:       # (the widest call only when its option is set: the handle then has a slot per stream)
+        if getattr(config, "lod_base_bits", 0) != 0:    # (the widest call only when its option is set)
+            opt = config._native_lod(geometry)
+            st = native.lib().dsa_encode_lod_sequential_batch(ctx._h, n, arr, grids, C.byref(opt), C.byref(h))
+            if st == 0:
+                n = native.lib().dsa_encoded_size(h)
+        elif getattr(config, "part_cells", 0) != 0:     # (the widest call only when its option is set: the handle then has a slot per stream)
             opt = config._native_cell_parts(geometry)
             st = native.lib().dsa_encode_cell_parts_sequential_batch(ctx._h, n, arr, grids, C.byref(opt), C.byref(h))
             if st == 0:

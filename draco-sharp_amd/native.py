@@ -44,6 +44,7 @@ EXPORTS = [
     "dsa_encode_default_merge_options", "dsa_encode_merged_sequential_batch", "dsa_encoded_row_entries",
     "dsa_encode_default_split_options", "dsa_encode_split_sequential_batch", "dsa_encoded_parts", "dsa_encoded_part_info",
     "dsa_encode_default_cell_parts_options", "dsa_encode_cell_parts_sequential_batch",
+    "dsa_encode_default_lod_options", "dsa_encode_lod_sequential_batch", "dsa_encoded_lod_info",
     "dsa_encoded_size", "dsa_encoded_stream", "dsa_encoded_free",
     "dsa_pool_create", "dsa_pool_destroy", "dsa_pool_size", "dsa_pool_last_error", "dsa_pool_decode", "dsa_pool_job_locate",
     "dsa_pool_job_chunks", "dsa_pool_job_free", "dsa_pool_plan",
@@ -118,6 +119,20 @@ class EncodeCellPartsOptions(C.Structure):
     """dsa_encode_cell_parts_options: the options of dsa_encode_split_sequential_batch, and part_cells (N >= 1, with merge_points = 1:
     the KEPT order of every point cloud in parts of at most N points, sized on the device; the handle is shaped like a split one)."""
     _fields_ = [("split", EncodeSplitOptions), ("part_cells", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+class EncodeLodOptions(C.Structure):
+    """dsa_encode_lod_options: the options of dsa_encode_cell_parts_sequential_batch, and lod_base_bits (D >= 1, with part_cells >= 1:
+    the kept points of every cloud in additive levels of detail, level 0 one point per cell of the grid with D bits per axis, every
+    level in parts of at most part_cells points; the handle is shaped like a cell-parts one)."""
+    _fields_ = [("cell_parts", EncodeCellPartsOptions), ("lod_base_bits", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+class LodInfo(C.Structure):
+    """dsa_lod_info: which level of which input a stream of an encode with lod_base_bits >= 1 belongs to."""
+    _fields_ = [("input", C.c_uint32), ("level", C.c_uint32), ("levels", C.c_uint32), ("cell_bits", C.c_uint32),
+                ("level_first_stream", C.c_uint32), ("level_streams", C.c_uint32), ("level_points", C.c_uint32), ("part_in_level", C.c_uint32),
+                ("reserved", C.c_uint32 * 4)]
 
 
 class PartInfo(C.Structure):
@@ -400,6 +415,11 @@ def lib():
             L.dsa_encode_default_cell_parts_options.argtypes = [C.POINTER(EncodeCellPartsOptions)]
             L.dsa_encode_default_cell_parts_options.restype = None
             L.dsa_encode_cell_parts_sequential_batch.argtypes = [vp, u32, C.POINTER(MeshAttrInput), C.POINTER(MeshGrids), C.POINTER(EncodeCellPartsOptions), C.POINTER(vp)]
+        if hasattr(L, "dsa_encode_lod_sequential_batch"):
+            L.dsa_encode_default_lod_options.argtypes = [C.POINTER(EncodeLodOptions)]
+            L.dsa_encode_default_lod_options.restype = None
+            L.dsa_encode_lod_sequential_batch.argtypes = [vp, u32, C.POINTER(MeshAttrInput), C.POINTER(MeshGrids), C.POINTER(EncodeLodOptions), C.POINTER(vp)]
+            L.dsa_encoded_lod_info.argtypes = [vp, u32, C.POINTER(LodInfo)]
         L.dsa_encoded_size.restype = u32
         L.dsa_encoded_size.argtypes = [vp]
         L.dsa_encoded_stream.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(C.c_size_t)]

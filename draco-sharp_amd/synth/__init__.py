@@ -240,6 +240,8 @@ def lib():
         L.synth_part_boxes.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(Grid), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.synth_cell_parts.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(Grid), C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.synth_lod_parts.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(Grid), C.c_uint32, C.c_int, C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         L.synth_shared_grid.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_uint32, C.c_int, C.POINTER(Grid)]
         L.synth_free.argtypes = [C.c_void_p]
         L.synth_make_mesh.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_uint32),
@@ -719,6 +721,58 @@ def encode_cell_parts(pos, normals=None, uvs=None, generic=None, extra=None, opt
         streams.append(encode_grid(take(p), None, normals=take(kw["normals"]), uvs=take(kw["uvs"]), generic=take(kw["generic"]), extra=ex, opt=opt,
                                    form=0, geometry=0, pos_grid=kw["pos_grid"], uv_grid=kw["uv_grid"]))
     return CellParts(streams, kept, cells, ranges, qmin, qmax)
+
+
+def lod_parts(pos, bits, part_cells, lod_base_bits, grid=None):
+    """(lod, row_entries, ranges, levels, qmin, qmax) of the points `pos` (N, 3): lod the kept rows of merge_points in ascending
+    (level, position in kept) -- level(0) = 0, level(j) = max(0, c + 1 - lod_base_bits) with c the leading bit-triples the keys of
+    kept[j] and kept[j - 1] share -- row_entries the lod entry of the cell of every row, ranges (P, 2) the parts of every level in
+    turn (split_parts of the level's points, an empty level has none), levels (P,) the level of every part, qmin / qmax (P, 3) int32
+    the box of the position integers of rows lod[lo:hi]."""
+    L = lib()
+    pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+    lod, cells = np.zeros(len(pos), np.uint32), np.zeros(len(pos), np.uint32)
+    m, parts = C.c_uint32(), C.c_uint64()
+    grid = None if grid is None else C.byref(grid)
+    if L.synth_lod_parts(pos.ctypes.data, len(pos), int(bits), grid, int(part_cells), int(lod_base_bits), lod.ctypes.data, C.byref(m), cells.ctypes.data,
+                         None, None, None, None, 0, C.byref(parts)):
+        raise RuntimeError(_err())
+    ranges, levels = np.zeros((parts.value, 2), np.uint32), np.zeros(parts.value, np.uint32)
+    qmin, qmax = np.zeros((parts.value, 3), np.int32), np.zeros((parts.value, 3), np.int32)
+    if L.synth_lod_parts(pos.ctypes.data, len(pos), int(bits), grid, int(part_cells), int(lod_base_bits), lod.ctypes.data, C.byref(m), cells.ctypes.data,
+                         ranges.ctypes.data, levels.ctypes.data, qmin.ctypes.data, qmax.ctypes.data, len(ranges), C.byref(parts)):
+        raise RuntimeError(_err())
+    return lod[:m.value].copy(), cells, ranges, levels, qmin, qmax
+
+
+LodParts = collections.namedtuple("LodParts", "streams kept row_entries ranges qmin qmax level levels")
+
+
+def encode_lod_parts(pos, normals=None, uvs=None, generic=None, extra=None, opt=None, pos_grid=None, uv_grid=None, part_cells=0, lod_base_bits=0):
+    """Additive levels of detail of the kept points, every level in parts of at most part_cells points, each part coded as a point
+    cloud of its own on the cloud's grid: what encode_cell_parts returns with `kept` the rows in LOD order (ranges and row_entries
+    count in it), plus `level` per stream and `levels` = L = position bits - lod_base_bits + 1.  Every per-point array at
+    [lod[lo:hi]], every quantised attribute on an explicit grid equal to the bounds of ALL input rows (the grid given, where one
+    was).  What dsa_encode_lod_sequential_batch with lod_base_bits >= 1 must write, and what its handle must report.
+    lod_base_bits 0: encode_cell_parts, every stream of level 0 of 1."""
+    opt = opt or options()
+    if lod_base_bits == 0:
+        cp = encode_cell_parts(pos, normals, uvs, generic, extra, opt, pos_grid, uv_grid, part_cells)
+        return LodParts(*cp, level=np.zeros(len(cp.streams), np.uint32), levels=1)
+    lod, cells, ranges, level, qmin, qmax = lod_parts(pos, opt.pos_bits, part_cells, lod_base_bits, pos_grid)
+    kept, _, kw = merged_arguments(pos, normals, uvs, generic, extra, opt, pos_grid, uv_grid)
+    at = np.zeros(int(kept.max()) + 1, np.int64)
+    at[kept] = np.arange(len(kept))
+    idx = at[lod]                                # where in kept (the order of merged_arguments' arrays) every lod entry lies
+    p = kw.pop("pos")
+    streams = []
+    for lo, hi in ranges:
+        take = lambda a: None if a is None else np.ascontiguousarray(a[idx[lo:hi]])          # noqa: E731
+        ex = [Extra(e.values[idx[lo:hi]], attribute_type=e.attribute_type, normalized=bool(e.normalized), unique_id=e.unique_id,
+                    quantization_bits=e.quantization_bits, data_type=e.data_type, num_components=e.num_components, grid=e.grid) for e in kw["extra"]]
+        streams.append(encode_grid(take(p), None, normals=take(kw["normals"]), uvs=take(kw["uvs"]), generic=take(kw["generic"]), extra=ex, opt=opt,
+                                   form=0, geometry=0, pos_grid=kw["pos_grid"], uv_grid=kw["uv_grid"]))
+    return LodParts(streams, lod, cells, ranges, qmin, qmax, level, opt.pos_bits - lod_base_bits + 1)
 
 
 def entry_rows(pos, faces=None, normals=None, uvs=None, generic=None, extra=None, opt=None, form=1, normal_corners=None, uv_corners=None,

@@ -571,6 +571,27 @@ int synth_cell_parts(const float *pos, uint32_t n, int bits, const synth::Grid *
     return 0;
   } catch (const std::exception &e) { snprintf(g_err, sizeof(g_err), "%s", e.what()); return 1; }
 }
+// The kept points by (level, kept) and every level in parts of at most part_cells (lod_parts): lod[n] of which *m are set,
+// row_entries[n], and where `ranges` is given (room for 2 * capacity) lo and hi of the *parts parts in lod order with their level
+// (levels[capacity]) and their boxes, qmin / qmax[3 * capacity].
+int synth_lod_parts(const float *pos, uint32_t n, int bits, const synth::Grid *grid, uint32_t part_cells, int base_bits, uint32_t *lod, uint32_t *m, uint32_t *row_entries,
+                    uint32_t *ranges, uint32_t *levels, int32_t *qmin, int32_t *qmax, uint64_t capacity, uint64_t *parts) {
+  try {
+    std::vector<uint32_t> k, c, lv;
+    std::vector<std::pair<uint32_t, uint32_t>> r;
+    std::vector<int32_t> mn, mx;
+    synth::lod_parts(pos, n, bits, grid, part_cells, base_bits, k, c, r, lv, mn, mx);
+    *m = (uint32_t)k.size(); *parts = r.size();
+    memcpy(lod, k.data(), 4 * k.size());
+    memcpy(row_entries, c.data(), 4 * c.size());
+    if (!ranges) return 0;
+    synth::check(capacity >= r.size(), "lod_parts: no room for the ranges");
+    for (size_t p = 0; p < r.size(); ++p) { ranges[2 * p] = r[p].first; ranges[2 * p + 1] = r[p].second; levels[p] = lv[p]; }
+    memcpy(qmin, mn.data(), 4 * mn.size());
+    memcpy(qmax, mx.data(), 4 * mx.size());
+    return 0;
+  } catch (const std::exception &e) { snprintf(g_err, sizeof(g_err), "%s", e.what()); return 1; }
+}
 void synth_free(uint8_t *p) { free(p); }
 
 // Procedural mesh: returns counts; call once with NULL outputs to size, then again to fill.

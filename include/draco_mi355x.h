@@ -831,6 +831,61 @@ typedef struct dsa_encode_cell_parts_options {
 void dsa_encode_default_cell_parts_options(dsa_encode_cell_parts_options *options);
 dsa_status dsa_encode_cell_parts_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids,
                                                   const dsa_encode_cell_parts_options *options, dsa_encoded **out);
+/* dsa_encode_cell_parts_sequential_batch with a coarse-to-fine order: additive levels of detail of every merged point cloud, on the
+ * device.  A consumer of tiled scans (3D Tiles "ADD" refinement, progressive download) takes a few thousand points that cover the
+ * whole cloud first, then the points that refine it, each piece an ordinary stream with a box.
+ *   lod_base_bits = D, 1 <= D <= B = position_bits (taken only with point_order = 1, geometry 0, merge_points = 1 and part_cells =
+ *   N >= 1; one stream per level is part_cells >= n).  With kept[0 .. m) and key() exactly what merge_points = 1 defines for the
+ *   cloud (keys distinct and ascending): for j >= 1, c(j) is the number of leading bit-triples, out of the B triples of a key, that
+ *   key(kept[j]) and key(kept[j - 1]) have in common, c = B - ceil(bitlength(key[j] ^ key[j - 1]) / 3) in 0 .. B - 1; level(0) = 0 and
+ *   level(j) = max(0, c(j) + 1 - D).  The cloud has L = B - D + 1 levels, 0 .. L - 1.  The points of levels 0 .. l together are
+ *   exactly one point per occupied cell of the grid with D + l bits per axis (the cell of a point: the top 3 (D + l) bits of its
+ *   key), the cell's first point in Morton order -- so the representative of a coarse cell is also the representative of the finer
+ *   cells that contain it -- and all levels together are the kept points.  D = B puts every point in level 0: the streams are byte
+ *   for byte those of part_cells.
+ *   lod[0 .. m) is kept in ascending (level, position in kept), a stable partition; m_l the points of level l, level l is
+ *   lod[base_l .. base_l + m_l).  Level l is cut by the rule of part_cells applied to m_l: P_l = ceil(m_l / N), part p of level l is
+ *   entries [base_l + floor(p m_l / P_l), base_l + floor((p + 1) m_l / P_l)), computed in 64 bits; an empty level has no part.  The
+ *   stream slots of an input are the parts of level 0, then those of level 1, and so on.  Every slot is an ordinary Draco 2.2
+ *   point-cloud stream; entry j of every attribute carries row lod[lo + j].  Bounds and quantisers run once per cloud, in front of
+ *   the sort: every stream is byte for byte what dsa_encode_grid_sequential_batch (geometry 0) writes for rows[lod[lo:hi]] with
+ *   every quantised attribute on an explicit grid equal to the bounds of ALL n input rows (or the grid given or shared).  Wrap
+ *   bounds, symbol statistics, scheme choice and tables are each stream's own.
+ *   The handle is shaped like a cell-parts handle, with "kept order" read as "lod order": dsa_encoded_parts and
+ *   dsa_encoded_part_info (first_entry / num_points in lod order, part / parts over all slots of the input, the boxes bit for bit the
+ *   box of the slot's decoded positions), dsa_encoded_entry_rows(s, a) = lod[lo:hi], dsa_encoded_row_entries on an input's first
+ *   slot (for every input row the lod-order entry of its cell), dsa_batch_source_rows per slot.  dsa_part_info is unchanged, its
+ *   reserved words stay zero; dsa_encoded_lod_info(encoded, stream, out) says which level a slot belongs to.  On a handle made
+ *   without lod_base_bits >= 1 it returns DSA_ERR_INVALID_ARGUMENT and the message names lod_base_bits.
+ *   The host can bound the slots only by S_max = ceil(n / N) + L - 1 (sum ceil(m_l / N) <= ceil(m / N) + non-empty levels - 1): the
+ *   layout reserves S_max slots and the device sizes them (k_enc_lod_parts, dsa_encode_order.h).  A cloud with S_max >
+ *   DSA_ENCODE_MAX_PARTS fails alone with DSA_ERR_INVALID_ARGUMENT; the message names lod_base_bits, part_cells, n and the limit.  A
+ *   refused cloud keeps one slot.
+ *   lod_base_bits = 0: the bytes, the messages, the work, the rows and the handle shape of dsa_encode_cell_parts_sequential_batch.
+ * Fails the call with DSA_ERR_INVALID_ARGUMENT before any mesh is looked at, dsa_last_error naming the field: lod_base_bits < 0;
+ * lod_base_bits > position_bits; lod_base_bits >= 1 with part_cells = 0, or without merge_points = 1 / point_order = 1 / geometry 0;
+ * a non-zero reserved word.  Refusals of the nested option structs keep their own words.
+ * Not built: a representative nearest the cell centre instead of first in Morton order; levels of sequential meshes; levels
+ * without the merge; a joined decode-side layout of the levels.
+ * Added after ABI 4 without changing it: callers detect the feature by the symbol dsa_encode_lod_sequential_batch. */
+typedef struct dsa_encode_lod_options {
+  dsa_encode_cell_parts_options cell_parts; /* as for dsa_encode_cell_parts_sequential_batch, same legal values */
+  int32_t lod_base_bits;                   /* 0 (default): the very request of the cell-parts call; D >= 1: levels, level 0 on the grid of D bits per axis */
+  int32_t reserved[7];                     /* must be zero */
+} dsa_encode_lod_options;
+void dsa_encode_default_lod_options(dsa_encode_lod_options *options);
+dsa_status dsa_encode_lod_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids,
+                                           const dsa_encode_lod_options *options, dsa_encoded **out);
+typedef struct dsa_lod_info {
+  uint32_t input;                          /* the input the stream belongs to */
+  uint32_t level, levels;                  /* its level, and L = position_bits - lod_base_bits + 1 */
+  uint32_t cell_bits;                      /* lod_base_bits + level: levels 0 .. level are one point per cell of the grid with so many bits per axis */
+  uint32_t level_first_stream, level_streams;      /* the stream slots of this level */
+  uint32_t level_points;                   /* m_l */
+  uint32_t part_in_level;                  /* stream - level_first_stream */
+  uint32_t reserved[4];                    /* zero */
+} dsa_lod_info;
+dsa_status dsa_encoded_lod_info(const dsa_encoded *encoded, uint32_t stream, dsa_lod_info *out);
 /* The rows of a decoded batch per POINT: for every mesh of `batch` and every attribute a of its stream,
  *     rows[a][p] = entry_rows[a][map[a][p]]          (map: the decoder's point -> entry map, dsa_batch_device_point_map)
  * -- which row of the arrays given to the encoder point p carries, gathered on the device (k_source_rows) so that neither the maps
