@@ -56,6 +56,15 @@ __device__ __forceinline__ uint32_t enc_zigzag(int32_t v) { return v >= 0 ? (uin
 // Quantisation range: per-component min / max, range = largest extent (1 if degenerate).  GRID: the chunk has streams on a grid
 // that is not their own bounds (EncStream::grid_mode; dsa_encode_grid.h) -- their records hold it already, and
 // k_enc_grid_quantize quantises them; a chunk without such streams launches <false>, the kernel it always ran.
+// The minimum of a component carries the bits of the FIRST row that attains it, as the serial strict compare of the reference
+// and of the host coder leaves it (synth::quantize): the header holds those four bytes, and -0.0 == +0.0 attains the same
+// minimum with another sign.  So a minimum travels with its row, and of two equal minima the one of the smaller row stays --
+// whatever the block shape and the order of the folds.  The maximum needs no such rule: only max - min is used.
+// The smallest row with a value that is not finite lands in grid_nonfinite (ENC_GRID_NO_ROW: none), and the host refuses the mesh
+// (enc_quantiser_refusals); the bounds of such a stream mean nothing.
+// Cost of the rows and the finite check against the kernel without them: 27 VGPRs in place of 22 (4 rows, 1 bad row) and 13 KiB
+// of LDS a block in place of 8 (u32[4][256] rows and u32[256] bad rows beside the two f32[4][256]); no scratch, 8 waves / SIMD
+// and one block per stream as before (profiles/README.md: the encode legs stay within their run-to-run spread).
 template <bool GRID>
 __global__ __launch_bounds__(256) void k_enc_bounds(uint8_t *arena, EncStream *streams, uint32_t ns) {
   const uint32_t si = blockIdx.x;
@@ -64,18 +73,31 @@ __global__ __launch_bounds__(256) void k_enc_bounds(uint8_t *arena, EncStream *s
   if (S.kind != 0 || S.part != 0) return;         // (a part behind the first of a split cloud: the first part's bounds are the cloud's)
   if (GRID && S.grid_mode != 0) return;
   __shared__ float s_mn[4][256], s_mx[4][256];
+  __shared__ uint32_t s_row[4][256], s_bad[256];
   const float *src = (const float *)(arena + S.src);
   const uint32_t nc = S.nc_out, tid = threadIdx.x;
   float mn[4], mx[4];
-  for (uint32_t c = 0; c < 4; ++c) { mn[c] = src[c < nc ? c : 0]; mx[c] = mn[c]; }
-  for (uint32_t v = tid; v < S.rows; v += 256)
-    for (uint32_t c = 0; c < nc; ++c) { const float x = src[(size_t)v * nc + c]; if (x < mn[c]) mn[c] = x; if (x > mx[c]) mx[c] = x; }
-  for (uint32_t c = 0; c < 4; ++c) { s_mn[c][tid] = mn[c]; s_mx[c][tid] = mx[c]; }
+  uint32_t row[4], bad = ENC_GRID_NO_ROW;
+  for (uint32_t c = 0; c < 4; ++c) { mn[c] = src[c < nc ? c : 0]; mx[c] = mn[c]; row[c] = 0; }
+  for (uint32_t v = tid; v < S.rows; v += 256)      // (rows ascend: the strict compare keeps the thread's first)
+    for (uint32_t c = 0; c < nc; ++c) {
+      const float x = src[(size_t)v * nc + c];
+      if (x < mn[c]) { mn[c] = x; row[c] = v; }
+      if (x > mx[c]) mx[c] = x;
+      if ((__float_as_uint(x) & 0x7F800000u) == 0x7F800000u && bad == ENC_GRID_NO_ROW) bad = v;
+    }
+  for (uint32_t c = 0; c < 4; ++c) { s_mn[c][tid] = mn[c]; s_mx[c][tid] = mx[c]; s_row[c][tid] = row[c]; }
+  s_bad[tid] = bad;
   __syncthreads();
   for (uint32_t h = 128; h >= 1; h >>= 1) {
-    if (tid < h) for (uint32_t c = 0; c < 4; ++c) {
-      if (s_mn[c][tid + h] < s_mn[c][tid]) s_mn[c][tid] = s_mn[c][tid + h];
-      if (s_mx[c][tid + h] > s_mx[c][tid]) s_mx[c][tid] = s_mx[c][tid + h];
+    if (tid < h) {
+      for (uint32_t c = 0; c < 4; ++c) {
+        const float o = s_mn[c][tid + h], m = s_mn[c][tid];
+        const uint32_t orow = s_row[c][tid + h];
+        if (o < m || (o == m && orow < s_row[c][tid])) { s_mn[c][tid] = o; s_row[c][tid] = orow; }
+        if (s_mx[c][tid + h] > s_mx[c][tid]) s_mx[c][tid] = s_mx[c][tid + h];
+      }
+      if (s_bad[tid + h] < s_bad[tid]) s_bad[tid] = s_bad[tid + h];
     }
     __syncthreads();
   }
@@ -84,6 +106,7 @@ __global__ __launch_bounds__(256) void k_enc_bounds(uint8_t *arena, EncStream *s
     for (uint32_t c = 0; c < nc; ++c) { S.qmin[c] = s_mn[c][0]; const float dlt = __fsub_rn(s_mx[c][0], s_mn[c][0]); if (dlt > range) range = dlt; }
     if (range == 0.0f) range = 1.0f;
     S.qrange = range;
+    S.grid_nonfinite = s_bad[0];
   }
 }
 
@@ -126,9 +149,13 @@ __global__ __launch_bounds__(256) void k_enc_quantize(uint8_t *arena, EncStream 
   if (S.kind == 0) {                // Quantizer: floor((v - min) * (max_q / range) + 0.5), every step rounded to f32
     const float inv_delta = __fdiv_rn((float)(int32_t)((1u << S.bits) - 1u), S.qrange);
     const uint32_t nc = S.nc_out, total = S.rows * nc;
+    // What the host refuses the mesh for behind this stage (enc_quantiser_refusals: a value that is not finite, a range that is
+    // not or that max_q does not divide finitely) shows here as a sum that is not finite: it is written as 0, as
+    // k_enc_grid_quantize writes an offending value, so that the kernels behind stay among integers of 0 .. max_q.
     for (uint32_t i = tid; i < total; i += stride) {
       const float v = __fsub_rn(src[i], S.qmin[i % nc]);
-      vals[i] = (int32_t)floorf(__fadd_rn(__fmul_rn(v, inv_delta), 0.5f));
+      const float t = __fadd_rn(__fmul_rn(v, inv_delta), 0.5f);
+      vals[i] = (__float_as_uint(t) & 0x7F800000u) == 0x7F800000u ? 0 : (int32_t)floorf(t);
     }
   } else if (S.kind == 2) {         // an integer attribute: its values as they are (SequentialIntegerAttributeEncoder.cs: no transform)
     // rows are packed at itemsize * nc (a 2-byte type of 3 components is not 4-byte aligned per row): one element per lane and
@@ -1309,19 +1336,25 @@ static dsa_status enc_stage_conn_results(dsa_context *ctx, EncLane &lane, EncChu
   }
   return DSA_OK;
 }
-// a stream on a grid with a value that is not finite or off the grid (k_enc_grid_quantize): its mesh is refused, in the host
-// coder's words, before anything is coded from it
-static void enc_grid_refusals(EncChunk &ck) {
-  if (!ck.L.any_grid) return;
+// a quantised stream the quantiser cannot take: its mesh is refused, in the host coder's words (synth::quantize,
+// synth::quantize_on_grid), before anything is coded from it -- the first such attribute of the mesh answers.  On a grid a value
+// that is not finite or off the grid (k_enc_grid_quantize); under own bounds a value that is not finite (k_enc_bounds), else a
+// range that is not finite or so small that max_q / range is not (the bounds as they came back)
+static void enc_quantiser_refusals(EncChunk &ck) {
   for (uint32_t i = 0; i < ck.n; ++i) {
     if (!ck.good(i)) continue;
     const uint32_t s0 = ck.L.first_stream[i];
     for (size_t k = 0; k < ck.plans[i].atts.size(); ++k) {
       const dsa::EncStream &S = ck.L.streams[s0 + k];
-      if (S.kind != 0 || S.grid_mode == 0 || (S.grid_nonfinite == dsa::ENC_GRID_NO_ROW && S.grid_off == dsa::ENC_GRID_NO_ROW)) continue;
+      if (S.kind != 0) continue;
       const synth::PortableAttr &a = ck.plans[i].atts[k];
+      const std::string name = synth::grid_slot_name(a.att_type, a.extra_index);
       const bool finite = S.grid_nonfinite == dsa::ENC_GRID_NO_ROW;
-      ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, synth::grid_row_message(synth::grid_slot_name(a.att_type, a.extra_index), finite ? S.grid_off : S.grid_nonfinite, finite));
+      std::string why;
+      if (!finite || (S.grid_mode != 0 && S.grid_off != dsa::ENC_GRID_NO_ROW)) why = synth::grid_row_message(name, finite ? S.grid_off : S.grid_nonfinite, finite);
+      else if (S.grid_mode == 0 && !synth::quant_range_ok(S.qrange, (int)S.bits)) why = synth::quant_range_message(name, S.qrange, (int)S.bits);
+      if (why.empty()) continue;
+      ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, why);
       for (uint32_t s = s0; s < ck.L.first_stream[i + 1]; ++s) ck.L.streams[s].overflow = 1;
       break;
     }
@@ -1333,7 +1366,7 @@ static dsa_status enc_stage_code(dsa_context *ctx, EncLane &lane, EncChunk &ck, 
   const uint32_t ns = (uint32_t)ck.L.streams.size();
   ck.splans.resize(ns); ck.stream_mesh.assign(ns, 0);
   for (uint32_t i = 0; i < ck.n; ++i) for (uint32_t s = ck.L.first_stream[i]; s < ck.L.first_stream[i + 1]; ++s) ck.stream_mesh[s] = (int)i;
-  enc_grid_refusals(ck);
+  enc_quantiser_refusals(ck);
   if (ck.host_plan) ENC_STAGE(enc_host_plans(ctx, lane, ck));
   else enc_device_plan_errors(ck);
   if (lap) (*lap)("histograms + symbol plans");

@@ -1044,8 +1044,26 @@ static void quantize_on_grid(const float *src, uint32_t n, int nc, int bits, Por
   if (bad_finite != kInvalid) check(false, grid_row_message(name, bad_finite, false).c_str());
   if (bad_off != kInvalid) check(false, grid_row_message(name, bad_off, true).c_str());
 }
+// The attribute's own bounds can refuse a mesh too.  A value that is not finite does, in the words of a grid (the reference
+// throws "NaN values are not supported", AttributeQuantizationTransform.cs:82,96): grid_row_message with the smallest such row.
+// So does a range the bit depth cannot carry: the extent max - min overflowed to infinity, or max_q / range did (a range
+// below about max_q * 2.9e-39) -- every integer would be what an undefined float-to-int cast makes of an infinity or a NaN.
+static inline bool quant_range_ok(float range, int bits) {
+  volatile float inv_delta = (float)((1 << bits) - 1) / range;
+  return f32_finite(range) && f32_finite(inv_delta);
+}
+static inline std::string quant_range_message(const std::string &name, float range, int bits) {
+  char buf[160];
+  snprintf(buf, sizeof(buf), ": the range %g of its values cannot carry %d quantisation bits (the range and (2^bits - 1) / range must be finite)", (double)range, bits);
+  return name + buf;
+}
+// The minimum of a component carries the bits of the first row that attains it (a strict compare, taken serially, as the
+// reference takes it: `MinValues[c] > v`, :76-92), which decides the sign of a zero minimum in the header.
 static void quantize(const float *src, uint32_t n, int nc, int bits, PortableAttr &a) {
   if (a.grid && a.grid->mode != 0) return quantize_on_grid(src, n, nc, bits, a);
+  const std::string name = grid_slot_name(a.att_type, a.extra_index);
+  for (size_t i = 0, total = (size_t)n * nc; i < total; ++i)
+    if (!f32_finite(src[i])) check(false, grid_row_message(name, (uint32_t)(i / nc), false).c_str());
   a.qmin.assign(nc, 0);
   std::vector<float> mx(nc, 0);
   for (int c = 0; c < nc; ++c) { a.qmin[c] = src[c]; mx[c] = src[c]; }
@@ -1055,6 +1073,7 @@ static void quantize(const float *src, uint32_t n, int nc, int bits, PortableAtt
   for (int c = 0; c < nc; ++c) { float d = mx[c] - a.qmin[c]; if (d > a.qrange) a.qrange = d; }
   if (a.qrange == 0.0f) a.qrange = 1.0f;
   a.bits = bits;
+  if (!quant_range_ok(a.qrange, bits)) check(false, quant_range_message(name, a.qrange, bits).c_str());
   int32_t max_q = (1 << bits) - 1;
   volatile float inv_delta = (float)max_q / a.qrange;
   a.vals.resize((size_t)n * nc);

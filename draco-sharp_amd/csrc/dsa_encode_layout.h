@@ -70,7 +70,8 @@ struct EncStream {                 // one per (mesh, attribute); lives in device
                                    // elem (kind 2): Draco's data type of `src`, 1 int8, 2 uint8, 3 int16, 4 uint16, 5 int32, 6 uint32
   uint32_t grid_mode;              // kind 0: not 0: qmin / qrange are a grid given by the host (the caller's, or its group's), k_enc_grid_quantize in place
                                    //   of k_enc_bounds and k_enc_quantize
-  uint32_t grid_nonfinite, grid_off;      // its smallest row with a value that is not finite / whose integer leaves 0 .. max_q (the host sets ENC_GRID_NO_ROW)
+  uint32_t grid_nonfinite, grid_off;      // kind 0: its smallest row with a value that is not finite (on a grid or under own bounds: k_enc_bounds) / on a grid: whose
+                                   //   integer leaves 0 .. max_q (the host sets ENC_GRID_NO_ROW)
   uint32_t part;                   // not 0: the stream of a part behind the first of a split cloud (dsa_encode_order.h): src, vals and the quantiser's
                                    //   floats are the first part's: k_enc_bounds / k_enc_quantize leave it alone, and so does k_enc_grid_quantize (its grid_mode is 0)
                                    //   ENC_PART_SIZED set: a part slot whose nv the device decides (k_enc_part_cells), 0 where the cloud has fewer parts
@@ -669,8 +670,9 @@ static void enc_value_stream_input(dsa::EncStream &S, const synth::PortableAttr 
   S.rows = rows; S.nc_out = (uint32_t)a.nc_out; S.nc = (uint32_t)a.nc; S.kind = a.seq_type == 3 ? 1u : (integer ? 2u : 0u);
   S.bits = integer ? 9u : (uint32_t)a.bits;              // (9: the zig-zagged corrections of bytes are below 512)
   S.elem = integer ? (uint32_t)a.data_type : 0u;
+  S.grid_nonfinite = S.grid_off = dsa::ENC_GRID_NO_ROW;  // (own bounds: k_enc_bounds writes grid_nonfinite; a grid: k_enc_grid_quantize both)
   if (S.kind == 0 && a.grid && a.grid->mode != 0) {      // the header's floats are the grid's
-    S.grid_mode = 1; S.grid_nonfinite = S.grid_off = dsa::ENC_GRID_NO_ROW;
+    S.grid_mode = 1;
     for (uint32_t c = 0; c < S.nc_out && c < 4; ++c) S.qmin[c] = a.grid->origin[c];
     S.qrange = a.grid->range;
   }

@@ -5,8 +5,8 @@
 // `vals` k_enc_quantize / k_enc_grid_quantize wrote) and B = position_bits,
 //     key(r) = sum over b < B, c < 3 of ((uint32(q[r][c]) >> b) & 1) << (3 b + 2 - c)        (x the top bit of each triple)
 // and perm lists the rows in ascending (key, row): entry e of every attribute of the stream carries row perm[e], a face index f is
-// written rank[f], rank the inverse of perm.  Only the low B bits of an integer are read, so whatever the quantiser left of a value
-// the call does not check (a NaN under own bounds) still gives a permutation.  The host coder's twin is synth::point_order
+// written rank[f], rank the inverse of perm.  Only the low B bits of an integer are read, so whatever the quantiser left of a cloud
+// the host refuses behind this stage (a value that is not finite, a range the bits cannot carry) still gives a permutation.  The host coder's twin is synth::point_order
 // (dsa_encode_host.h); tests/hostcheck/encorder_host.cpp holds the two against each other under the sanitizers.
 //
 // A segmented, stable, least-significant-digit radix sort of (key, row) over all clouds of the chunk at once: 8 bits a pass,

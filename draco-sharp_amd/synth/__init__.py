@@ -537,7 +537,10 @@ def encode_ordered(pos, faces=None, normals=None, uvs=None, generic=None, extra=
                    pos_grid=None, uv_grid=None):
     """encode_grid with form=0 for the input in Morton order: (stream, perm) with perm = point_order(pos, opt.pos_bits, pos_grid),
     every per-point array taken at [perm] and the faces through the inverse of perm.  What
-    dsa_encode_ordered_sequential_batch with point_order = 1 must write, and the rows its handle must report."""
+    dsa_encode_ordered_sequential_batch with point_order = 1 must write, and the rows its handle must report.  (One difference, by
+    design: an attribute on its own bounds whose minimum is attained by a -0.0 and a +0.0 gets the sign of the first of them in
+    the order coded here, the device that of the first in the caller's order -- its bounds are the caller's rows', as in every
+    split or merged call; bounds_grid of the caller's array as an explicit grid gives the device's header.)"""
     opt = opt or options()
     perm = point_order(pos, opt.pos_bits, pos_grid)
     take = lambda a: None if a is None else np.ascontiguousarray(np.asarray(a).reshape(len(perm), -1)[perm])      # noqa: E731
@@ -578,8 +581,10 @@ def bounds_grid(values):
     extent in float32 arithmetic, 1 where that is 0 -- what the coder finds for an attribute without a grid."""
     v = np.ascontiguousarray(values, np.float32)
     v = v.reshape(len(v), -1)
-    mn, mx = v.min(axis=0), v.max(axis=0)
-    rng = np.float32(np.max((mx - mn).astype(np.float32)))
+    # (the minimum of a component is the value of the first row that attains it, as the coder's serial compare leaves it: that
+    # decides the sign of a zero minimum, which np.min does not define)
+    mn = np.array([col[np.flatnonzero(col == col.min())[0]] for col in v.T], np.float32)
+    rng = np.float32(np.max((v.max(axis=0) - mn).astype(np.float32)))
     return grid(mn, rng if rng != 0 else np.float32(1.0))
 
 

@@ -538,7 +538,13 @@ void dsa_welded_free(dsa_welded *welded);
  * SequentialQuantizationAttributeEncoder.cs:19-23, AttributeQuantizationTransform.SetParameters) or shared by the meshes of a
  * batch, for the attributes that are quantised: positions, the first UV set, float32 attributes of the list.  Normals
  * (octahedral) and integer attributes have no grid.
- *   mode 0   the attribute's own bounds (minimum per component, range the largest extent): what every other call does.
+ *   mode 0   the attribute's own bounds (minimum per component, range the largest extent, 1 if that is 0): what every other call
+ *       does.  The minimum of a component carries the bits of the first of the caller's rows that attains it (rows [5, -0.0, +0.0]
+ *       put 0x80000000 into the header), in the caller's order also where point_order sorts the entries.  A mesh fails alone
+ *       with DSA_ERR_INVALID_ARGUMENT when a value of the attribute is not finite ("positions: row 417 is not finite": the
+ *       smallest such row, the words of mode 1), else when the range cannot carry the bit depth -- the extent overflowed to
+ *       infinity, or (2^bits - 1) / range did (a range below about 2^bits * 2.9e-39): "positions: the range 9.97e-40 of its
+ *       values cannot carry 11 quantisation bits (...)".  The first such attribute of the mesh answers.
  *   mode 1   explicit: origin[c] per component and one range; the stream's header carries exactly those floats.  The values are
  *       quantised as always, q = floor((v - origin[c]) * (max_q / range) + 0.5) with every step rounded to float32 and
  *       max_q = 2^bits - 1.  A mesh fails alone with DSA_ERR_INVALID_ARGUMENT when a value of the attribute is not finite or

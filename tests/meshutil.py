@@ -28,6 +28,12 @@ def oct_quantize(normals, bits):
     "Octahedral quantise"): scale to L1 norm 1 (double arithmetic), x and y rounded times the centre value, z by the
     remainder with the two fix-ups, then (s, t) with the canonicalisation of the edge cases.  Independent of the stream
     writer's C++ (draco-sharp_amd/csrc/dsa_encode_host.h)."""
+    return oct_quantize_rules(normals, bits)[0]
+
+
+def oct_quantize_rules(normals, bits):
+    """oct_quantize, and beside the (s, t) per row which canonicalisation rule fired: 0 none, 1 the three corners, 2 s == 0,
+    3 s == max_value, 4 t == max_value, 5 t == 0; and the (s, t) before the rules (tests/quantcases.py)."""
     v = np.asarray(normals, np.float64)
     max_value = (1 << bits) - 2
     center = max_value // 2
@@ -46,21 +52,27 @@ def oct_quantize(normals, bits):
     # CanonicalizeOctahedralCoords, first matching rule wins
     out_s, out_t = s.copy(), t.copy()
     done = np.zeros(len(s), bool)
+    rule = np.zeros(len(s), np.int64)
     r = ((s == 0) & (t == 0)) | ((s == 0) & (t == max_value)) | ((s == max_value) & (t == 0))
     out_s[r], out_t[r] = max_value, max_value
     done |= r
+    rule[r] = 1
     r = ~done & (s == 0) & (t > center)
     out_t[r] = center - (t[r] - center)
     done |= r
+    rule[r] = 2
     r = ~done & (s == max_value) & (t < center)
     out_t[r] = center + (center - t[r])
     done |= r
+    rule[r] = 3
     r = ~done & (t == max_value) & (s < center)
     out_s[r] = center + (center - s[r])
     done |= r
+    rule[r] = 4
     r = ~done & (t == 0) & (s > center)
     out_s[r] = center - (s[r] - center)
-    return np.stack([out_s, out_t], axis=1)
+    rule[r] = 5
+    return np.stack([out_s, out_t], axis=1), rule, np.stack([s, t], axis=1)
 
 
 def source_corner_faces(pos, normals, uvs, faces, pos_bits=11, normal_bits=8, uv_bits=10):
