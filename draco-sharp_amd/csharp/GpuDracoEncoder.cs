@@ -108,6 +108,13 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
     private LodLevel[] _lodInfo;
     // Of stream s of the most recent Encode with LodBaseBits: which level it belongs to, and the streams and points of that level.
     public LodLevel LodInfo(int s) => _lodInfo != null && s >= 0 && s < _lodInfo.Length ? _lodInfo[s] : throw new InvalidOperationException("no levels: set LodBaseBits before Encode");
+    // MeanAttributes (dsa_encode_mean_sequential_batch): the mean of the cell WITH MergePoints.  0 every attribute of a kept point
+    // carries its own row; bit a set: attribute a of the stream (0 positions, then normals, texture coordinates, the generic attribute
+    // and the listed attributes, those the cloud has) carries, per component, floor((2 S + cnt) / (2 cnt)) over the cnt input rows of
+    // the cell, S the sum of the integers the plain call codes for them -- the exact mean, ties upwards, whatever the order of the
+    // rows.  Positions and normals carry no mean: a cloud whose mask names them, or an attribute it does not have, fails alone.
+    // PartCells and LodBaseBits compose with it; EntryRows, RowEntries, PartInfo and LodInfo are unchanged.  Needs MergePoints 1.
+    public uint MeanAttributes { get; set; }
     public struct PartBox
     {
         public uint Input, Part, Parts, FirstEntry, NumPoints, PositionBits;
@@ -224,6 +231,7 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
                     inputs[i].Faces = (uint*)Pin(faces, pins);
                 }
             }
+            if (MeanAttributes != 0 && MergePoints != 1) throw new ArgumentException("MeanAttributes needs MergePoints 1: the mean is the mean over the points of a cell");
             if (LodBaseBits != 0 && PartCells == 0) throw new ArgumentException("LodBaseBits needs PartCells >= 1: every level is cut into parts of at most PartCells points");
             if (PartPoints != 0 || PartCells != 0)
             {
@@ -235,7 +243,17 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
                 po.PartPoints = PartPoints;
                 var ain = new DsaMeshAttrInput[items.Count];
                 for (int i = 0; i < items.Count; ++i) { ain[i].Mesh.Mesh = inputs[i]; Extras(items[i], null, (uint)items[i].PointsCount, ref ain[i], pins); }
-                if (LodBaseBits != 0)           // (the widest call only when its option is set)
+                if (MeanAttributes != 0)        // (the widest call only when its option is set)
+                {
+                    NativeMethods.dsa_encode_default_mean_options(out var eo);
+                    eo.Lod.CellParts.Split = po;
+                    eo.Lod.CellParts.PartCells = PartCells;
+                    eo.Lod.LodBaseBits = LodBaseBits;
+                    eo.MeanAttributes = MeanAttributes;
+                    fixed (DsaMeshAttrInput* p = ain)
+                        NativeMethods.Check(NativeMethods.dsa_encode_mean_sequential_batch(_ctx, (uint)items.Count, p, null, in eo, out encoded), _ctx, "dsa_encode_mean_sequential_batch");
+                }
+                else if (LodBaseBits != 0)      // (the widest call only when its option is set)
                 {
                     NativeMethods.dsa_encode_default_lod_options(out var lo);
                     lo.CellParts.Split = po;
@@ -302,6 +320,15 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
                 mo.MergePoints = MergePoints;
                 var ain = new DsaMeshAttrInput[items.Count];
                 for (int i = 0; i < items.Count; ++i) { ain[i].Mesh.Mesh = inputs[i]; Extras(items[i], null, (uint)items[i].PointsCount, ref ain[i], pins); }
+                if (MeanAttributes != 0)        // (the widest call only when its option is set)
+                {
+                    NativeMethods.dsa_encode_default_mean_options(out var eo);
+                    eo.Lod.CellParts.Split.Merge = mo;
+                    eo.MeanAttributes = MeanAttributes;
+                    fixed (DsaMeshAttrInput* p = ain)
+                        NativeMethods.Check(NativeMethods.dsa_encode_mean_sequential_batch(_ctx, (uint)items.Count, p, null, in eo, out encoded), _ctx, "dsa_encode_mean_sequential_batch");
+                }
+                else
                 fixed (DsaMeshAttrInput* p = ain)
                     NativeMethods.Check(NativeMethods.dsa_encode_merged_sequential_batch(_ctx, (uint)items.Count, p, null, in mo, out encoded), _ctx, "dsa_encode_merged_sequential_batch");
                 var merged = Streams(encoded, items.Count);

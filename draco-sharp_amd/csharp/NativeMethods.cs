@@ -275,6 +275,15 @@ internal unsafe struct DsaEncodeLodOptions
     public fixed int Reserved[7];   // zero
 }
 
+// dsa_encode_mean_options (dsa_encode_mean_sequential_batch)
+[StructLayout(LayoutKind.Sequential)]
+internal unsafe struct DsaEncodeMeanOptions
+{
+    public DsaEncodeLodOptions Lod;
+    public uint MeanAttributes;     // 0: the request of the lod call; bit a: attribute a of the stream carries the exact mean of its cell's rows (needs MergePoints 1)
+    public fixed int Reserved[7];   // zero
+}
+
 // dsa_lod_info (dsa_encoded_lod_info)
 [StructLayout(LayoutKind.Sequential)]
 internal unsafe struct DsaLodInfo
@@ -440,6 +449,8 @@ internal static unsafe partial class NativeMethods
     [DllImport(Lib)] internal static extern void dsa_encode_default_lod_options(out DsaEncodeLodOptions options);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_lod_sequential_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, in DsaEncodeLodOptions options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encoded_lod_info(IntPtr encoded, uint stream, out DsaLodInfo info);
+    [DllImport(Lib)] internal static extern void dsa_encode_default_mean_options(out DsaEncodeMeanOptions options);
+    [DllImport(Lib)] internal static extern DsaStatus dsa_encode_mean_sequential_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, in DsaEncodeMeanOptions options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encoded_parts(IntPtr encoded, uint input, out uint firstStream, out uint count);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encoded_part_info(IntPtr encoded, uint stream, out DsaPartInfo info);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_rows_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, DsaMeshAttributeCorners* corners, in DsaEncodeRowsOptions options, out IntPtr encoded);

@@ -33,6 +33,8 @@
 //                                                number and sizes follow from m on the device: part slots, sized behind k_enc_merge_scan
 //                              k_enc_lod_*       dsa_encode_lod_sequential_batch, lod_base_bits >= 1: the kept order by (level, kept), every
 //                                                level in parts: levels, scan, scatter, row entries and the slots, in place of k_enc_part_cells
+//                              k_enc_mean_*      dsa_encode_mean_sequential_batch, mean_attributes != 0: the mean of the cell into the masked
+//                                                attributes' integers at every kept row, behind the merge
 //         (dsa_encode_layout.h) the request of an entry point, the state of a chunk, the per-mesh checks and plans, the arena layout
 // Every entry point fills an EncRequest and calls encode_request; a chunk of it goes through the stages of encode_chunk (or of
 // encode_sequential_chunk, dsa_encode_sequential.h) on a lane.
@@ -1223,6 +1225,14 @@ static dsa_status enc_stage_attributes(dsa_context *ctx, EncLane &lane, EncChunk
       ENC_TRY(hipGetLastError());
       if (order_timing) { ENC_TRY(hipStreamSynchronize(st)); order_lap("point merge"); }
     }
+    if (!L.means.empty()) {    // mean_attributes: the mean of the cell into vals at every kept row, in front of everything that reads vals or turns row_entries into lod order
+      ENC_TRY(hipMemsetAsync(arena + L.mean_zero_at, 0, L.mean_zero_bytes, st));
+      dsa::enc_mean_launch([st](auto kernel, uint32_t grid_x, uint32_t grid_y, uint32_t block, auto... args) { hipLaunchKernelGGL(kernel, dim3(grid_x, grid_y), dim3(block), 0, st, args...); },
+                           arena, (const dsa::EncOrder *)(arena + L.ord_at), (uint32_t)L.ord.size(), (const dsa::EncOrderTile *)(arena + L.ord_tiles_at), (uint32_t)L.ord_tiles.size(),
+                           L.ord_passes, (const dsa::EncMeanCloud *)(arena + L.mean_clouds_at), (const dsa::EncMean *)(arena + L.means_at), (uint32_t)L.means.size(), L.mean_most);
+      ENC_TRY(hipGetLastError());
+      if (order_timing) { ENC_TRY(hipStreamSynchronize(st)); order_lap("cell means"); }
+    }
     if (L.lod) {               // lod_base_bits: the kept order by (level, kept) and the parts of every level, in place of the step below
       dsa::enc_lod_launch([st](auto kernel, uint32_t grid_x, uint32_t grid_y, uint32_t block, auto... args) { hipLaunchKernelGGL(kernel, dim3(grid_x, grid_y), dim3(block), 0, st, args...); },
                           arena, (const dsa::EncOrder *)(arena + L.ord_at), (uint32_t)L.ord.size(), (const dsa::EncOrderTile *)(arena + L.ord_tiles_at), (uint32_t)L.ord_tiles.size(),
@@ -1563,6 +1573,14 @@ static dsa_status enc_check_options(dsa_context *ctx, const dsa_encode_lod_optio
   if (o.lod_base_bits > bits) ENC_REFUSE("lod_base_bits %d is above position_bits %d: level 0 cannot be finer than the quantisation grid", (int)o.lod_base_bits, bits);
   return DSA_OK;
 }
+// ... with the mean of the cell in the masked attributes of the kept points (dsa_encode_order.h)
+static dsa_status enc_check_options(dsa_context *ctx, const dsa_encode_mean_options &o, bool null_argument) {
+  const dsa_encode_merge_options &m = o.lod.cell_parts.split.merge;
+  if (o.mean_attributes != 0 && m.merge_points != 1) ENC_REFUSE("mean_attributes 0x%x needs merge_points 1 (it was %d): the mean is the mean over the points of a cell", (unsigned)o.mean_attributes, (int)m.merge_points);
+  if (o.mean_attributes >> DSA_MAX_ATTRIBUTES) ENC_REFUSE("mean_attributes 0x%x: a bit at or above %d (DSA_MAX_ATTRIBUTES) names no attribute of a stream", (unsigned)o.mean_attributes, (int)DSA_MAX_ATTRIBUTES);
+  ENC_RESERVED(o, 7, "dsa_encode_mean_options");
+  return enc_check_options(ctx, o.lod, null_argument);
+}
 #undef ENC_RESERVED
 #undef ENC_REFUSE
 
@@ -1831,8 +1849,9 @@ static dsa_status encode_edgebreaker(dsa_context *ctx, uint32_t n, const dsa_mes
   rq.track_rows = w.track_rows == 1;
   return encode_checked(ctx, rq, grids, o.grid.repair.topology == 1, out);
 }
-static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_lod_options &l, dsa_encoded **out) {
-  if (enc_check_options(ctx, l, !ctx || !out || (n && !meshes)) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_mean_options &a, dsa_encoded **out) {
+  if (enc_check_options(ctx, a, !ctx || !out || (n && !meshes)) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+  const dsa_encode_lod_options &l = a.lod;
   const dsa_encode_cell_parts_options &c = l.cell_parts;
   const dsa_encode_split_options &s = c.split;
   const dsa_encode_merge_options &m = s.merge;
@@ -1840,9 +1859,16 @@ static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh
   EncRequest rq;
   rq.n = n; rq.meshes = meshes; rq.sequential = true;
   rq.seq = o.sequential; rq.point_order = o.point_order == 1; rq.merge_points = m.merge_points == 1; rq.part_points = (uint32_t)s.part_points; rq.part_cells = (uint32_t)c.part_cells; rq.lod_base_bits = (uint32_t)l.lod_base_bits;
+  rq.mean_attributes = a.mean_attributes;
   const dsa_status st = encode_checked(ctx, rq, grids, false, out);
   if (st == DSA_OK && rq.lod()) (*out)->lod_bits = rq.lod_base_bits;
   return st;
+}
+static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_lod_options &l, dsa_encoded **out) {
+  dsa_encode_mean_options a;
+  dsa_encode_default_mean_options(&a);
+  a.lod = l;
+  return encode_sequential(ctx, n, meshes, grids, a, out);
 }
 static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_cell_parts_options &c, dsa_encoded **out) {
   dsa_encode_lod_options l;
@@ -1932,6 +1958,11 @@ void dsa_encode_default_lod_options(dsa_encode_lod_options *o) {
   if (!o) return;
   memset(o, 0, sizeof(*o));
   dsa_encode_default_cell_parts_options(&o->cell_parts);
+}
+void dsa_encode_default_mean_options(dsa_encode_mean_options *o) {
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  dsa_encode_default_lod_options(&o->lod);
 }
 void dsa_encode_default_repair_options(dsa_encode_repair_options *o) {
   if (!o) return;
@@ -2062,6 +2093,11 @@ dsa_status dsa_encode_cell_parts_sequential_batch(dsa_context *ctx, uint32_t n, 
 // lod_base_bits = 0 is the very request of the call above.
 dsa_status dsa_encode_lod_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_lod_options *options, dsa_encoded **out) {
   DSA_GUARD(ctx, [&] { dsa_encode_lod_options o; dsa_encode_default_lod_options(&o); if (options) o = *options; return encode_sequential(ctx, n, meshes, grids, o, out); }());
+}
+// ... or, with mean_attributes != 0, the mean of the cell in the masked attributes of every kept point (k_enc_mean_*, dsa_encode_order.h);
+// mean_attributes = 0 is the very request of the call above.
+dsa_status dsa_encode_mean_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_mean_options *options, dsa_encoded **out) {
+  DSA_GUARD(ctx, [&] { dsa_encode_mean_options o; dsa_encode_default_mean_options(&o); if (options) o = *options; return encode_sequential(ctx, n, meshes, grids, o, out); }());
 }
 
 struct dsa_welded {

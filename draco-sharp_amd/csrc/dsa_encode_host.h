@@ -1013,6 +1013,7 @@ struct PortableAttr {
   const Grid *grid = nullptr;          // seq_type 2: the caller's grid (mode 1; null or mode 0: the attribute's own bounds)
   int extra_index = -1;                // its index in MeshIn::extras (the messages name it)
   uint32_t extra_rows = 0;             // an attribute of MeshIn::extras given per corner: the rows of extra_values (corner_value indexes them)
+  const int32_t *portable = nullptr;   // seq_type 2: the integers to code, one row per value id, in place of the quantiser's output (bounds and grid as the floats give them)
 };
 
 // AttributeQuantizationTransform.cs:66-108,136-177 + Core/Quantizer.cs (E-1 corrected)
@@ -1156,6 +1157,7 @@ struct ExtraAttr {
   const Grid *grid = nullptr;        // float32: the caller's quantisation grid (null: its own bounds)
   const uint32_t *corners = nullptr; // 3 * nf row ids into `values`, or null: one row per vertex
   uint32_t rows = 0;                 // rows of `values` when `corners` is set
+  const int32_t *portable = nullptr; // float32: the integers to code in place of the quantiser's output (merge_means' twin), bounds and grid untouched
 };
 static const size_t kMaxAttributes = 16;   // DSA_MAX_ATTRIBUTES: what the decode direction takes
 static const size_t kMaxCornerAttributeIndex = 7;      // the last index of the stream whose attribute may have a connectivity of its own (attribute data 0 to 6)
@@ -1172,6 +1174,7 @@ struct MeshIn {
   const uint32_t *uv_corners = nullptr; uint32_t nu = 0;
   const ExtraAttr *extras = nullptr; uint32_t num_extras = 0;      // written behind the attributes above, in list order
   const Grid *pos_grid = nullptr, *uv_grid = nullptr;              // the caller's quantisation grids (null: the attribute's own bounds)
+  const int32_t *uv_portable = nullptr;                            // sequential streams: the integers `uvs` is coded as, in place of the quantiser's output (ExtraAttr::portable)
 };
 
 // Why the extras of a mesh cannot be written ("" when they can): the attribute's index in the list and the field.
@@ -1547,6 +1550,7 @@ static void plan_extra_attributes(const MeshIn &in, const Options &opt, int pred
     a.att_type = x.att_type; a.nc = a.nc_out = (int)x.nc; a.data_type = x.data_type; a.prediction = prediction;
     a.unique_id = x.unique_id; a.extra_values = x.values; a.extra_index = (int)k;
     a.corner_value = x.corners; a.extra_rows = x.corners ? x.rows : 0;
+    if (x.data_type == 9) a.portable = x.portable;
     if (x.grid) { const std::string why = grid_error(*x.grid, (int)x.nc, x.data_type == 9, grid_slot_name(x.att_type, (int)k)); check(why.empty(), why.c_str()); a.grid = x.grid; }
     if (x.data_type == 9) { a.seq_type = 2; a.bits = x.bits ? x.bits : (x.att_type == 3 ? opt.uv_bits : 8); }
     else { a.seq_type = 1; a.normalized = x.normalized; }
@@ -1554,7 +1558,12 @@ static void plan_extra_attributes(const MeshIn &in, const Options &opt, int pred
   }
 }
 static void fill_extra_values(const PortableAttr &a, uint32_t nv, PortableAttr &out) {
-  if (a.seq_type == 2) { quantize((const float *)a.extra_values, nv, a.nc, a.bits, out); return; }
+  if (a.seq_type == 2) {
+    const int32_t *portable = a.portable;                      // (a and out may be one object)
+    quantize((const float *)a.extra_values, nv, a.nc, a.bits, out);
+    if (portable) out.vals.assign(portable, portable + (size_t)nv * a.nc);       // the header is the floats', the integers are given
+    return;
+  }
   out.vals.resize((size_t)nv * a.nc);
   for (size_t k = 0; k < (size_t)nv * a.nc; ++k) out.vals[k] = generic_value(a.extra_values, k, a.data_type);
 }
@@ -2041,7 +2050,7 @@ static void encode_sequential(const MeshIn &in, const Options &opt, bool mesh, b
       Octa o(opt.normal_bits);
       a.vals.resize((size_t)in.nv * 2);
       for (uint32_t v = 0; v < in.nv; ++v) { int s, t; o.from_float_vector(in.normals + (size_t)v * 3, s, t); a.vals[(size_t)v * 2] = s; a.vals[(size_t)v * 2 + 1] = t; }
-    } else if (a.att_type == 3) quantize(in.uvs, in.nv, 2, opt.uv_bits, a);
+    } else if (a.att_type == 3) { quantize(in.uvs, in.nv, 2, opt.uv_bits, a); if (in.uv_portable) a.vals.assign(in.uv_portable, in.uv_portable + (size_t)in.nv * 2); }
     else { a.vals.resize((size_t)in.nv * a.nc); for (size_t k = 0; k < (size_t)in.nv * a.nc; ++k) a.vals[k] = generic_value(in.generic, k, a.data_type); }
   }
   // linear order: entry i = point i.  write_attribute_values wants a corner table and a sequence: an identity stand-in
@@ -2109,6 +2118,33 @@ static void merge_points(const float *pos, uint32_t n, int bits, const Grid *gri
   for (uint32_t e = 0; e < n; ++e) {
     if (e == 0 || key[perm[e]] != key[perm[e - 1]]) kept.push_back(perm[e]);
     row_entries[perm[e]] = (uint32_t)kept.size() - 1u;
+  }
+}
+// The mean of every cell in an attribute of the kept points (dsa_encode_mean_sequential_batch, a bit of mean_attributes; the device's
+// kernels are k_enc_mean_* of dsa_encode_order.h): q[n * nc] the integers the plain call codes for the rows -- the quantiser's output
+// or the elements widened to int32 -- row_entries and m as merge_points has them; means[m * nc], entry j component c = floor((2 S +
+// cnt) / (2 cnt)) with S the sum of q[r][c] over the cnt rows r of cell j, in 64 bits with floor division: the exact mean, ties
+// toward +infinity, a function of the set of rows.
+static inline int32_t cell_mean(int64_t sum, uint32_t cnt) {
+  const int64_t num = 2 * sum + (int64_t)cnt, den = 2 * (int64_t)cnt;
+  int64_t q = num / den;
+  if (num % den < 0) --q;
+  return (int32_t)q;
+}
+static void merge_means(const int32_t *q, uint32_t n, int nc, const std::vector<uint32_t> &row_entries, uint32_t m, std::vector<int32_t> &means) {
+  check(q != nullptr && n > 0 && nc >= 1 && nc <= 4 && row_entries.size() == n, "merge_means: n rows of 1 - 4 integers and their row entries");
+  std::vector<int64_t> sum((size_t)m * nc, 0);
+  std::vector<uint32_t> cnt(m, 0);
+  for (uint32_t r = 0; r < n; ++r) {
+    const uint32_t j = row_entries[r];
+    check(j < m, "merge_means: a row entry at or above m");
+    ++cnt[j];
+    for (int c = 0; c < nc; ++c) sum[(size_t)j * nc + c] += q[(size_t)r * nc + c];
+  }
+  means.resize((size_t)m * nc);
+  for (uint32_t j = 0; j < m; ++j) {
+    check(cnt[j] >= 1, "merge_means: a cell without rows");
+    for (int c = 0; c < nc; ++c) means[(size_t)j * nc + c] = cell_mean(sum[(size_t)j * nc + c], cnt[j]);
   }
 }
 // The sorted order of a cloud in parts of at most part_points points (dsa_encode_split_sequential_batch, part_points >= 1): P =

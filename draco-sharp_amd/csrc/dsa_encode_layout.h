@@ -249,6 +249,8 @@ struct EncRequest {
   uint32_t lod_base_bits = 0;              // dsa_encode_lod_sequential_batch, lod_base_bits D >= 1 (with part_cells): the kept order by (level, kept), every level in parts
   bool lod() const { return cell_parts() && lod_base_bits >= 1; }
   uint32_t lod_levels() const { return lod() ? (uint32_t)seq.base.position_bits - lod_base_bits + 1u : 1u; }      // L (D <= position_bits: enc_check_options)
+  uint32_t mean_attributes = 0;            // dsa_encode_mean_sequential_batch (with merge_points): bit a: attribute a of the stream carries the mean of its cell (k_enc_mean_*)
+  bool means() const { return merged() && seq.geometry == 0 && mean_attributes != 0; }
   int rows_kind() const { return weld_sink ? dsa_encoded::ROWS_NONE : (sequential ? (point_order ? dsa_encoded::ROWS_ORDERED : dsa_encoded::ROWS_LINEAR) : (track_rows ? dsa_encoded::ROWS_TRACKED : dsa_encoded::ROWS_NONE)); }
   dsa_encode_level_options level{};        // Edgebreaker streams
   dsa_encode_sequential_options seq{};     // sequential streams
@@ -321,6 +323,13 @@ struct EncLayout {
   std::vector<dsa::EncPartTile> part_tiles;
   std::vector<uint32_t> part_of_mesh;
   uint64_t parts_at = 0, part_tiles_at = 0;
+  // EncRequest::means: a record per cloud (parallel to `ord`) and per masked stream, both among the uploads; mean_stream[k] the
+  // stream of record k; the sums and counts are one range of the arena, zeroed on the stream in front of k_enc_mean_sum
+  std::vector<dsa::EncMeanCloud> mean_clouds;
+  std::vector<dsa::EncMean> means;
+  std::vector<uint32_t> mean_stream;
+  uint64_t mean_clouds_at = 0, means_at = 0, mean_zero_at = 0, mean_zero_bytes = 0;
+  uint32_t mean_most = 0;                   // the most masked streams a cloud of the chunk has: the y of the mean kernels' grid
 };
 
 static inline bool enc_multi_scheme(const synth::PortableAttr &a) { return a.seq_type != 3 && (a.prediction == 2 || a.prediction == 4); }
@@ -639,6 +648,18 @@ static void enc_check_sequential_mesh(EncChunk &ck, uint32_t i) {
   if (!why.empty()) return ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, why);
   synth::plan_sequential_attributes(in, mo, ck.plans[i].atts);
   enc_extra_caps(ck, i);
+  if (ck.rq.means()) {       // mean_attributes: every set bit names an attribute of this cloud's stream that can carry a mean
+    const std::vector<synth::PortableAttr> &atts = ck.plans[i].atts;
+    char buf[240];
+    for (uint32_t a = 0; a < 32u; ++a) {
+      if (!((ck.rq.mean_attributes >> a) & 1u)) continue;
+      if (a >= atts.size()) snprintf(buf, sizeof(buf), "mean_attributes 0x%x: bit %u names attribute %u of the stream, which has %zu attributes", ck.rq.mean_attributes, a, a, atts.size());
+      else if (a == 0) snprintf(buf, sizeof(buf), "mean_attributes 0x%x: bit 0 names attribute 0, the positions: they are equal inside a cell and are never averaged", ck.rq.mean_attributes);
+      else if (atts[a].seq_type == 3) snprintf(buf, sizeof(buf), "mean_attributes 0x%x: bit %u names attribute %u, the normals: mean normals are not built (octahedral integers do not average across the fold)", ck.rq.mean_attributes, a, a);
+      else continue;
+      return ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, buf);
+    }
+  }
   if (!ck.rq.split()) return;
   // (lod_base_bits: a level more can cost a slot more -- sum ceil(m_l / N) <= ceil(m / N) + non-empty levels - 1)
   const uint64_t parts = synth::split_count(m.num_vertices, ck.rq.part_size()) + (ck.rq.lod_levels() - 1u);
@@ -925,6 +946,9 @@ static void enc_layout(EncChunk &ck) {
 // is the kept buffer, as with the merge, and k_enc_part_cells writes every slot's lo, n, nv and e2v.
 // EncRequest::lod (cell_parts with levels): ceil(n / part_cells) + L - 1 slots, the streams' map is the lod buffer, which with pos takes
 // the sort's dead key buffer; a level table per cloud among the kernels' regions; k_enc_lod_parts writes the slots.
+// EncRequest::means (merge with mean_attributes): an EncMeanCloud per cloud and an EncMean per masked stream among the uploads; behind
+// every other region a u32[n] count region per cloud and an i64[n nc] sum region per masked stream, one range that is zeroed on the
+// stream in front of k_enc_mean_sum.  No region is reused and nothing else grows.
 static void enc_layout_sequential(EncChunk &ck) {
   EncLayout &L = ck.L;
   const bool is_mesh = ck.rq.seq.geometry == 1, compressed = is_mesh && ck.rq.seq.compress_connectivity == 1, ordered = ck.rq.point_order;
@@ -952,6 +976,21 @@ static void enc_layout_sequential(EncChunk &ck) {
       O.n = V; O.tiles = (V + ORD_TILE - 1u) / ORD_TILE; O.bits = (uint32_t)ck.opt.pos_bits;
       if (merge) { O.merge = 1; O.stream0 = s0; O.streams = (uint32_t)atts.size(); }
       if (merge || split) L.ord_of_mesh[i] = (uint32_t)L.ord.size();
+      if (ck.rq.means()) {                                     // the masked streams of the cloud (the first part's: the parts share its vals)
+        dsa::EncMeanCloud MC;
+        memset(&MC, 0, sizeof(MC));
+        MC.first = (uint32_t)L.means.size();
+        for (uint32_t k = 1; k < atts.size() && k < 32u; ++k) {
+          if (!((ck.rq.mean_attributes >> k) & 1u)) continue;
+          dsa::EncMean M;
+          memset(&M, 0, sizeof(M));
+          M.nc = L.streams[s0 + k].nc;
+          L.means.push_back(M); L.mean_stream.push_back(s0 + k);
+          ++MC.count;
+        }
+        L.mean_most = std::max(L.mean_most, MC.count);
+        L.mean_clouds.push_back(MC);
+      }
       for (uint32_t t = 0; t < O.tiles; ++t) L.ord_tiles.push_back({(uint32_t)L.ord.size(), t});
       if (split) {                                             // the parts of the cloud: their sizes need nothing of the device
         L.part_of_mesh[i] = (uint32_t)L.parts.size();
@@ -983,6 +1022,10 @@ static void enc_layout_sequential(EncChunk &ck) {
     L.ord_passes = dsa::enc_order_passes((uint32_t)ck.opt.pos_bits);
     L.ord_at = A.put(L.uploads, L.ord.data(), sizeof(dsa::EncOrder) * L.ord.size(), false);
     L.ord_tiles_at = A.put(L.uploads, L.ord_tiles.data(), sizeof(dsa::EncOrderTile) * L.ord_tiles.size(), false);
+  }
+  if (!L.means.empty()) {
+    L.mean_clouds_at = A.put(L.uploads, L.mean_clouds.data(), sizeof(dsa::EncMeanCloud) * L.mean_clouds.size(), false);
+    L.means_at = A.put(L.uploads, L.means.data(), sizeof(dsa::EncMean) * L.means.size(), false);
   }
   if (!L.parts.empty()) {
     L.parts_at = A.put(L.uploads, L.parts.data(), sizeof(dsa::EncPart) * L.parts.size(), false);
@@ -1025,6 +1068,17 @@ static void enc_layout_sequential(EncChunk &ck) {
     if (ordered) L.ord[o - 1].vals = L.streams[s0].vals;      // (the positions are attribute 0: their stream is the mesh's first)
     L.max_rows = std::max(L.max_rows, V);
     if (compressed) enc_list_stream_regions(L.streams[s0 + na], A, true, false);
+  }
+  if (!L.means.empty()) {                                      // the counts of every cloud and the sums of every masked stream: one range, zeroed as one
+    L.mean_zero_at = A.cur;
+    for (size_t o = 0; o < L.mean_clouds.size(); ++o) {
+      dsa::EncMeanCloud &MC = L.mean_clouds[o];
+      if (MC.count == 0) continue;
+      const uint64_t V = L.ord[o].n;
+      MC.cnt = A.take(4ull * V);
+      for (uint32_t k = MC.first; k < MC.first + MC.count; ++k) { dsa::EncMean &M = L.means[k]; M.vals = L.streams[L.mean_stream[k]].vals; M.acc = A.take(8ull * V * M.nc); }
+    }
+    L.mean_zero_bytes = A.cur - L.mean_zero_at;
   }
   L.total_bytes = A.cur;
 }

@@ -125,6 +125,30 @@
 // tests/test_gpu_encode_lod.py the ballots and shuffles.
 // gfx950, hipcc -O3 (VGPR / SGPR / LDS bytes per block): k_enc_lod_levels 26 / 33 / 0, scan 21 / 33 / 0, scatter 16 / 43 / 128, cells
 // 6 / 20 / 0, parts 44 / 19 / 0 (k_enc_part_bounds stays 18 / 22 / 0); no scratch, no spills, 8 waves per SIMD.
+//
+// dsa_encode_mean_sequential_batch with mean_attributes != 0 (point clouds, merge_points = 1): entry j of a masked attribute carries
+// mean = floor((2 S + cnt) / (2 cnt)), S the sum over the cnt rows of cell j of the integer the plain call codes for the row, in 64
+// bits -- the exact mean, ties toward +infinity, a function of the set of rows.  The mean is written into the stream's `vals` at row
+// kept[j], which is what k_enc_gather and everything behind it read: merged streams, cell parts and levels take it as they are (the
+// part streams of a cloud share the first part's vals).  Two steps behind enc_merge_launch and in front of k_enc_part_cells, k_enc_lod_*
+// (which turn cells[] into lod order), k_enc_part_bounds and k_enc_gather, on the merge's (cloud, tile) list with the cloud's masked
+// streams in blockIdx.y (a cloud has at most DSA_MAX_ATTRIBUTES streams: one launch, no slices); launched only when the chunk has
+// a masked stream:
+//   k_enc_mean_sum        a wave per (tile, masked stream), 64 sorted entries a step: head flags from the sorted keys as
+//                         k_enc_merge_compact makes them; per component a segmented inclusive sum of vals[nc row[e] + c] across the
+//                         wave in int64 by shuffles, a lane adding what lies d below only while that is inside its run (the run's
+//                         first lane of the step from one ballot and a count of leading zeros); the last lane of every (run, step)
+//                         adds its sum to acc[nc j + c], j = cells[row[e]], by a 64-bit integer atomicAdd, and -- the cloud's
+//                         first masked stream alone -- its rows to cnt[j].  Integer adds commute: no atomic decides a place or a
+//                         value.  A run of a million duplicates costs one atomic a step, not a row.
+//   k_enc_mean_store      a thread per (kept entry, component), tiles over KEPT entries: vals[nc kept[j] + c] = the mean of acc and
+//                         cnt; a cell of one row keeps its value.  A pass of its own: kept[j]'s value is an addend of the first.
+// acc (i64[n nc] per masked stream) and cnt (u32[n] per cloud) are regions of their own at the end of the arena, one range that one
+// memset on the stream zeroes in front of the sum; no region is reused (the histograms are too small, the key buffers are the
+// lod's), nothing else grows.  The records are EncMean / EncMeanCloud, among the uploads: EncOrder is as it was, and so is every
+// kernel above.  The host coder's twin is synth::merge_means; tests/hostcheck/encmeans_host.cpp runs the serial forms in the
+// product's layout against it, tests/test_gpu_encode_means.py the ballots, shuffles and atomics.
+// gfx950, hipcc -O3 (VGPR / SGPR / LDS bytes per block): k_enc_mean_sum 24 / 45 / 0, store 23 / 29 / 0; no scratch, no spills, 8 waves per SIMD.
 #pragma once
 #include <stdint.h>
 
@@ -165,6 +189,9 @@ struct EncPart {                   // one per part of a split cloud, the parts o
 struct EncPartTile { uint32_t part, tile; };
 #define ORD_LOD_LEVELS 20u         // position_bits is at most 20 (enc_check_bits): L = bits - D + 1 <= 20
 struct EncLodTable { uint32_t count[ORD_LOD_LEVELS], base[ORD_LOD_LEVELS]; };      // m_l and base_l of a cloud (k_enc_lod_scan), zero from L on
+// mean_attributes: records of the mean kernels' own, so that EncOrder and the kernels that index it stay as they are
+struct EncMean { uint64_t vals, acc; uint32_t nc, pad; };       // one per masked stream, a cloud's side by side: the stream's vals i32[n nc], its sums i64[n nc], its components
+struct EncMeanCloud { uint64_t cnt; uint32_t first, count; };   // one per EncOrder record: the rows of every cell u32[n]; its `count` EncMean records from `first` on (0: none)
 
 static inline uint32_t enc_order_passes(uint32_t bits) { return (3u * bits + 7u) / 8u; }
 
@@ -423,6 +450,101 @@ static inline void enc_merge_launch(Launch &&launch, uint8_t *arena, EncOrder *c
   launch(k_enc_merge_heads, nt, 1u, (uint32_t)WAVE, arena, (const EncOrder *)clouds, tiles, nt, passes);
   launch(k_enc_merge_scan<Stream>, nc, 1u, (uint32_t)WAVE, arena, clouds, nc, streams, ns);
   launch(k_enc_merge_compact, nt, 1u, (uint32_t)WAVE, arena, (const EncOrder *)clouds, tiles, nt, passes);
+}
+
+// ---- mean_attributes (the header comment has the contract): behind enc_merge_launch, in front of everything that reads `vals`
+// floor((2 S + cnt) / (2 cnt)) in 64 bits: the exact mean of cnt >= 1 integers whose sum is S, ties toward +infinity
+// (|S| <= 2^28 rows of 2^31: 2 S + cnt fits)
+__device__ __forceinline__ int32_t ord_mean(int64_t sum, uint32_t cnt) {
+  const int64_t num = 2 * sum + (int64_t)cnt, den = 2 * (int64_t)cnt;
+  int64_t q = num / den;
+  if (num % den < 0) --q;                                      // (C++ division truncates toward zero)
+  return (int32_t)q;
+}
+
+// grid = (the chunk's (cloud, tile) pairs, the most masked streams a cloud has): one wave per (tile, masked stream)
+__global__ __launch_bounds__(WAVE) void k_enc_mean_sum(uint8_t *arena, const EncOrder *clouds, const EncOrderTile *tiles, uint32_t nt, uint32_t passes,
+                                                       const EncMeanCloud *mclouds, const EncMean *means, uint32_t nm) {
+  if (blockIdx.x >= nt) return;
+  const EncOrderTile T = tiles[blockIdx.x];
+  const EncOrder &O = clouds[T.cloud];
+  const EncMeanCloud C = mclouds[T.cloud];
+  if (!O.merge || blockIdx.y >= C.count || C.first + blockIdx.y >= nm) return;
+  const EncMean M = means[C.first + blockIdx.y];
+  if (M.nc == 0u || M.nc > 4u) return;                         // (never by the layout)
+  const uint32_t *row = (const uint32_t *)(arena + O.row[passes & 1u]);
+  const uint32_t *cells = (const uint32_t *)(arena + O.cells);
+  const int32_t *vals = (const int32_t *)(arena + M.vals);
+  unsigned long long *acc = (unsigned long long *)(arena + M.acc);       // (two's complement: the sums are signed)
+  uint32_t *cnt = (uint32_t *)(arena + C.cnt);
+  const bool counts = blockIdx.y == 0u;                        // the cloud's first masked stream counts the rows of every cell
+  const uint32_t lane = threadIdx.x, nc = M.nc, e0 = T.tile * ORD_TILE, end = O.n - e0 < ORD_TILE ? O.n : e0 + ORD_TILE;
+#if defined(__HIPCC__)
+  const uint64_t *key = (const uint64_t *)(arena + O.key[passes & 1u]);
+  const unsigned long long upto = (2ull << lane) - 1ull;       // the lanes at or below this one
+  for (uint32_t s0 = e0; s0 < end; s0 += WAVE) {               // (uniform: every lane takes every step)
+    const uint32_t e = s0 + lane;
+    const bool valid = e < end;
+    const bool head = valid && (e == 0u || key[e] != key[e - 1u]);
+    const unsigned long long heads = __ballot(head), live = __ballot(valid);
+    // the lane this lane's run begins at inside the step: the head at or below it, lane 0 for a run that came in from the step in front
+    const unsigned long long mine = heads & upto;
+    const uint32_t start = mine ? 63u - (uint32_t)__clzll((long long)mine) : 0u;
+    // the last lane of (run, step): the lane above is a head, or holds no entry, or there is none
+    const unsigned long long above = (live >> lane) >> 1, head_above = (heads >> lane) >> 1;
+    const bool last = valid && ((above & 1ull) == 0ull || (head_above & 1ull) != 0ull);
+    const uint32_t r = valid ? row[e] : 0u;
+    const bool ok = valid && r < O.n;
+    const uint32_t j = ok ? cells[r] : 0xFFFFFFFFu;
+    for (uint32_t c = 0; c < nc; ++c) {                        // (uniform)
+      long long x = ok ? (long long)vals[(size_t)nc * r + c] : 0ll;
+      for (uint32_t d = 1; d < (uint32_t)WAVE; d <<= 1) { const long long y = __shfl_up(x, d, WAVE); if (lane >= start + d) x += y; }
+      if (last && j < O.n) atomicAdd(&acc[(size_t)nc * j + c], (unsigned long long)x);
+    }
+    if (counts && last && j < O.n) atomicAdd(&cnt[j], lane - start + 1u);
+  }
+#else       // (as k_enc_order_hist: lane 0 takes the tile's entries in their order)
+  if (lane != 0) return;
+  for (uint32_t e = e0; e < end; ++e) {
+    const uint32_t r = row[e], j = cells[r];
+    for (uint32_t c = 0; c < nc; ++c) acc[(size_t)nc * j + c] += (unsigned long long)(long long)vals[(size_t)nc * r + c];
+    if (counts) cnt[j] += 1u;
+  }
+#endif
+}
+
+// grid as above, tiles over KEPT entries: a thread per (kept entry, component).  No lane needs another: the host check runs it as it stands.
+__global__ __launch_bounds__(256) void k_enc_mean_store(uint8_t *arena, const EncOrder *clouds, const EncOrderTile *tiles, uint32_t nt, uint32_t passes,
+                                                        const EncMeanCloud *mclouds, const EncMean *means, uint32_t nm) {
+  if (blockIdx.x >= nt) return;
+  const EncOrderTile T = tiles[blockIdx.x];
+  const EncOrder &O = clouds[T.cloud];
+  const EncMeanCloud C = mclouds[T.cloud];
+  if (!O.merge || blockIdx.y >= C.count || C.first + blockIdx.y >= nm) return;
+  const EncMean M = means[C.first + blockIdx.y];
+  if (M.nc == 0u || M.nc > 4u) return;                         // (never by the layout)
+  const uint32_t m = O.m < O.n ? O.m : O.n, e0 = T.tile * ORD_TILE;
+  if (e0 >= m) return;
+  const uint32_t nc = M.nc, total = (m - e0 < ORD_TILE ? m - e0 : ORD_TILE) * nc;
+  const uint32_t *kept = (const uint32_t *)(arena + O.row[(passes + 1u) & 1u]);
+  const long long *acc = (const long long *)(arena + M.acc);
+  const uint32_t *cnt = (const uint32_t *)(arena + C.cnt);
+  int32_t *vals = (int32_t *)(arena + M.vals);
+  for (uint32_t i = threadIdx.x; i < total; i += blockDim.x) {
+    const uint32_t j = e0 + i / nc, c = i % nc, r = kept[j], rows = cnt[j];
+    if (r >= O.n || rows == 0u) continue;                      // (never by the merge: the comparisons keep a fault elsewhere inside the stream's values)
+    if (rows > 1u) vals[(size_t)nc * r + c] = ord_mean((int64_t)acc[(size_t)nc * j + c], rows);       // (a cell of one point keeps its value)
+  }
+}
+
+// The means behind enc_merge_launch, on its lists: `mclouds` one record per cloud, `means` the chunk's nm masked streams, gy the most
+// a cloud has.  The accumulators and counts are zero when this is called (one memset on the stream in the product).
+template <class Launch>
+static inline void enc_mean_launch(Launch &&launch, uint8_t *arena, const EncOrder *clouds, uint32_t nc, const EncOrderTile *tiles, uint32_t nt, uint32_t passes,
+                                   const EncMeanCloud *mclouds, const EncMean *means, uint32_t nm, uint32_t gy) {
+  if (nc == 0 || nt == 0 || nm == 0 || gy == 0) return;
+  launch(k_enc_mean_sum, nt, gy, (uint32_t)WAVE, arena, clouds, tiles, nt, passes, mclouds, means, nm);
+  launch(k_enc_mean_store, nt, gy, 256u, arena, clouds, tiles, nt, passes, mclouds, means, nm);
 }
 
 // ---- part_cells (the header comment has the contract): a thread per part slot of the chunk, behind k_enc_merge_scan

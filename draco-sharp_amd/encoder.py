@@ -96,7 +96,15 @@ class Config:
     at most part_cells points (part_cells >= n: one stream per level).  The streams of an input are the parts of level 0, then of
     level 1, ...; parts(i), part_info(s), entry_rows(s), row_entries(parts(i)[0]) and row_parts(i) count in LOD order (kept by
     ascending (level, position in kept)); lod_info(s) says which level stream s belongs to, levels(i) gives the streams of every
-    level.  Needs part_cells >= 1 (and so point_order=POINT_ORDER_MORTON and merge_points=MERGE_CELLS)."""
+    level.  Needs part_cells >= 1 (and so point_order=POINT_ORDER_MORTON and merge_points=MERGE_CELLS).
+
+    mean_attributes (dsa_encode_mean_sequential_batch): the mean of the cell WITH merge_points=MERGE_CELLS.  0 every attribute of a
+    kept point carries its own row; a mask (bit a: attribute a of the stream -- 0 positions, then normals, texture coordinates, the
+    generic attribute and the attribute list, those the cloud has), a list of such indices, or "all" (every attribute of the cloud
+    but positions and normals; the clouds of a call must then have the same attributes): those attributes carry, per component,
+    floor((2 S + cnt) / (2 cnt)) over the cnt input rows of the cell, S the sum of the integers the plain call codes for them -- the
+    exact mean, ties upwards, whatever the order of the rows.  Positions and normals carry no mean.  part_cells and lod_base_bits
+    compose with it; entry_rows, row_entries, part_info and lod_info are unchanged, cell_counts(i) counts the rows of every cell."""
 
     EDGEBREAKER_METHODS = (0, 2, -1)
     POSITION_PREDICTIONS = (0, 1)
@@ -112,7 +120,7 @@ class Config:
                  symbol_scheme=-1, position_prediction=1, texcoord_prediction=1, edgebreaker_method=0, normal_prediction=0,
                  encoding_method=1, compress_connectivity=False, multi_parallelogram=0, traversal_method=0, repair_topology=False, weld_points=False,
                  repair_seams=False, weld_attributes=False, track_rows=False, point_order=0, merge_points=0, part_points=0, part_cells=0,
-                 lod_base_bits=0):
+                 lod_base_bits=0, mean_attributes=0):
         for name, value, legal in (("encoding_method", encoding_method, self.ENCODING_METHODS),
                                    ("edgebreaker_method", edgebreaker_method, self.EDGEBREAKER_METHODS),
                                    ("position_prediction", position_prediction, self.POSITION_PREDICTIONS),
@@ -172,6 +180,48 @@ class Config:
         if self.lod_base_bits != 0 and self.part_cells == 0:
             raise ValueError("lod_base_bits puts the kept points of merge_points into levels and cuts every level into parts: it needs part_cells >= 1 "
                              "(a sequential config with point_order=POINT_ORDER_MORTON and merge_points=MERGE_CELLS)")
+
+        if isinstance(mean_attributes, str):
+            if mean_attributes != "all":
+                raise ValueError("mean_attributes %r: a mask, a list of attribute indices of the stream, or \"all\"" % (mean_attributes,))
+            self.mean_attributes = "all"
+        else:
+            if isinstance(mean_attributes, (list, tuple, set, frozenset)):
+                if any(int(a) != a or a < 0 for a in mean_attributes):
+                    raise ValueError("mean_attributes %r: attribute indices of the stream, 0 and above" % (mean_attributes,))
+                mask = 0
+                for a in mean_attributes:
+                    mask |= 1 << int(a)
+            else:
+                mask = int(mean_attributes)
+            if mask < 0 or mask >> native.MAX_ATTRIBUTES:
+                raise ValueError("mean_attributes %r: a bit at or above %d names no attribute of a stream" % (mean_attributes, native.MAX_ATTRIBUTES))
+            if mask & 1:
+                raise ValueError("mean_attributes %r: attribute 0 holds the positions, which are equal inside a cell and are never averaged" % (mean_attributes,))
+            self.mean_attributes = mask
+        if self.mean_attributes != 0 and self.merge_points != native.MERGE_CELLS:
+            raise ValueError("mean_attributes takes the mean over the points of a cell: it needs merge_points=MERGE_CELLS "
+                             "(a sequential config with point_order=POINT_ORDER_MORTON)")
+
+    def _mean_mask(self, meshes):
+        """mean_attributes as the mask of a call over `meshes`: "all" is every attribute but positions and normals, and needs clouds
+        with the same attributes."""
+        if self.mean_attributes != "all":
+            return self.mean_attributes
+        masks = set()
+        for m in meshes:
+            count = 1 + (m.normals is not None) + (m.texcoords is not None) + (m.generic is not None) + len(m.attributes)
+            masks.add(((1 << count) - 1) & ~1 & ~(2 if m.normals is not None else 0))
+        if len(masks) > 1:
+            raise ValueError("mean_attributes=\"all\" is one mask for the call: its clouds must have the same attributes (give a mask per call otherwise)")
+        return masks.pop() if masks else 0
+
+    def _native_mean(self, geometry, meshes):
+        o = native.EncodeMeanOptions()
+        native.lib().dsa_encode_default_mean_options(C.byref(o))
+        o.lod = self._native_lod(geometry)
+        o.mean_attributes = self._mean_mask(meshes)
+        return o
 
     @property
     def sequential(self):
@@ -609,6 +659,14 @@ class EncodedStreams:
             raise ValueError("the encoded batch was closed")
         return _row_entries(self._ctx, self._h, i + len(self) if i < 0 else i)
 
+    def cell_counts(self, i):
+        """Of stream i of an encode with Config(merge_points=MERGE_CELLS) (with parts: of an input's first stream) a uint32 array with
+        one element per kept point of the cloud: the input rows of its cell, np.bincount of row_entries(i) -- what a mean of
+        Config(mean_attributes=...) was taken over."""
+        cells = self.row_entries(i)
+        m = int(cells.max()) + 1 if len(cells) else 0       # (every kept point has a row: its own)
+        return np.bincount(cells, minlength=m).astype(np.uint32)
+
     def row_parts(self, i):
         """Of input i of an encode with Config(merge_points=MERGE_CELLS, part_cells=N): (part, entry), two uint32 arrays with one
         element per input row -- the part of the input whose stream codes the row's cell (stream parts(i)[part]) and the entry of
@@ -854,7 +912,12 @@ class DracoEncoder:
         n = len(meshes)
         arr, grids, keep = _native_meshes(meshes)
         h = C.c_void_p()
-        if getattr(config, "lod_base_bits", 0) != 0:    # (the widest call only when its option is set)
+        if getattr(config, "mean_attributes", 0) != 0 and config._mean_mask(meshes) != 0:       # (the widest call only when its option is set)
+            opt = config._native_mean(geometry, meshes)
+            st = native.lib().dsa_encode_mean_sequential_batch(ctx._h, n, arr, grids, C.byref(opt), C.byref(h))
+            if st == 0:
+                n = native.lib().dsa_encoded_size(h)
+        elif getattr(config, "lod_base_bits", 0) != 0:  # (the widest call only when its option is set)
             opt = config._native_lod(geometry)
             st = native.lib().dsa_encode_lod_sequential_batch(ctx._h, n, arr, grids, C.byref(opt), C.byref(h))
             if st == 0:

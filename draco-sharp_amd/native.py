@@ -45,6 +45,7 @@ EXPORTS = [
     "dsa_encode_default_split_options", "dsa_encode_split_sequential_batch", "dsa_encoded_parts", "dsa_encoded_part_info",
     "dsa_encode_default_cell_parts_options", "dsa_encode_cell_parts_sequential_batch",
     "dsa_encode_default_lod_options", "dsa_encode_lod_sequential_batch", "dsa_encoded_lod_info",
+    "dsa_encode_default_mean_options", "dsa_encode_mean_sequential_batch",
     "dsa_encoded_size", "dsa_encoded_stream", "dsa_encoded_free",
     "dsa_pool_create", "dsa_pool_destroy", "dsa_pool_size", "dsa_pool_last_error", "dsa_pool_decode", "dsa_pool_job_locate",
     "dsa_pool_job_chunks", "dsa_pool_job_free", "dsa_pool_plan",
@@ -106,6 +107,7 @@ class EncodeMergeOptions(C.Structure):
 
 
 ENCODE_MAX_PARTS = 65536                            # DSA_ENCODE_MAX_PARTS: parts of one cloud
+MAX_ATTRIBUTES = 16                                 # DSA_MAX_ATTRIBUTES: attributes of a stream
 
 
 class EncodeSplitOptions(C.Structure):
@@ -126,6 +128,13 @@ class EncodeLodOptions(C.Structure):
     the kept points of every cloud in additive levels of detail, level 0 one point per cell of the grid with D bits per axis, every
     level in parts of at most part_cells points; the handle is shaped like a cell-parts one)."""
     _fields_ = [("cell_parts", EncodeCellPartsOptions), ("lod_base_bits", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+class EncodeMeanOptions(C.Structure):
+    """dsa_encode_mean_options: the options of dsa_encode_lod_sequential_batch, and mean_attributes (with merge_points = 1: bit a set:
+    attribute a of the stream carries, per component, the exact mean of the integers of the rows of the cell, ties upwards; positions
+    and normals carry none)."""
+    _fields_ = [("lod", EncodeLodOptions), ("mean_attributes", C.c_uint32), ("reserved", C.c_int32 * 7)]
 
 
 class LodInfo(C.Structure):
@@ -420,6 +429,10 @@ def lib():
             L.dsa_encode_default_lod_options.restype = None
             L.dsa_encode_lod_sequential_batch.argtypes = [vp, u32, C.POINTER(MeshAttrInput), C.POINTER(MeshGrids), C.POINTER(EncodeLodOptions), C.POINTER(vp)]
             L.dsa_encoded_lod_info.argtypes = [vp, u32, C.POINTER(LodInfo)]
+        if hasattr(L, "dsa_encode_mean_sequential_batch"):
+            L.dsa_encode_default_mean_options.argtypes = [C.POINTER(EncodeMeanOptions)]
+            L.dsa_encode_default_mean_options.restype = None
+            L.dsa_encode_mean_sequential_batch.argtypes = [vp, u32, C.POINTER(MeshAttrInput), C.POINTER(MeshGrids), C.POINTER(EncodeMeanOptions), C.POINTER(vp)]
         L.dsa_encoded_size.restype = u32
         L.dsa_encoded_size.argtypes = [vp]
         L.dsa_encoded_stream.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(C.c_size_t)]

@@ -88,11 +88,13 @@ class Extra:
     data_type / num_components override what the array says (the refusal tests).
     corners: (F, 3) row ids into `values`, which then holds any number of rows -- the attribute is given per corner, and an interior
     edge across which the ids differ is a seam of this attribute alone (Edgebreaker streams; the attribute's index in the stream must
-    be at most 7).  rows overrides the row count the ids are held against (the refusal tests)."""
+    be at most 7).  rows overrides the row count the ids are held against (the refusal tests).
+    portable: float32 values, encode_grid(form=0): int32 (V, nc) coded in place of the quantiser's output, bounds and grid untouched."""
 
     def __init__(self, values, attribute_type=4, normalized=False, unique_id=None, quantization_bits=0, data_type=None, num_components=None, grid=None,
-                 corners=None, rows=None):
+                 corners=None, rows=None, portable=None):
         self.grid = grid                      # float32: a Grid (encode_grid), None: its own bounds
+        self.portable = None if portable is None else np.ascontiguousarray(portable, np.int32).reshape(len(portable), -1)
         self.corners = None if corners is None else np.ascontiguousarray(corners, np.uint32)
         v = np.asarray(values)
         if v.dtype not in GENERIC_DATA_TYPES and v.dtype != np.dtype(np.float32):
@@ -234,6 +236,10 @@ def lib():
         L.synth_encode_grid.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                         C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(ExtraInput), C.c_uint32,
                                         C.POINTER(GridsInput), C.POINTER(Options), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+        L.synth_encode_grid_portable.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ExtraInput), C.c_uint32, C.POINTER(GridsInput),
+                                                 C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(Options), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+        L.synth_quantized.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.POINTER(Grid), C.c_void_p]
+        L.synth_merge_means.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]
         L.synth_point_order.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(Grid), C.c_void_p]
         L.synth_merge_points.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(Grid), C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]
         L.synth_split_parts.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
@@ -478,12 +484,13 @@ def encode_mesh_points(pos, faces, normals=None, uvs=None, generic=None, extra=N
 
 
 def encode_grid(pos, faces=None, normals=None, uvs=None, generic=None, extra=None, opt=None, form=1, normal_corners=None, uv_corners=None,
-                geometry=1, compressed=False, pos_grid=None, uv_grid=None, weld_attributes=False):
+                geometry=1, compressed=False, pos_grid=None, uv_grid=None, weld_attributes=False, uv_portable=None):
     """Any stream of this module with quantisation grids given by the caller: pos_grid / uv_grid / Extra.grid are Grids (grid(),
     shared_grid()) or None for the attribute's own bounds.  form 1: the arguments of encode_mesh_corners (Edgebreaker); form 0:
     of encode_sequential (geometry 1) / encode_point_cloud_attributes (geometry 0, faces None); form 2: of encode_mesh_points
     (one row per point).  Without a grid the bytes are those calls'.  What dsa_encode_grid_batch /
-    dsa_encode_grid_sequential_batch must write."""
+    dsa_encode_grid_sequential_batch must write.  uv_portable (N, 2) int32 / Extra.portable (form 0, point clouds): the integers
+    coded for that quantised attribute in place of the quantiser's output, the header's bounds or grid as the floats give them."""
     L = lib()
     pos, fc, nrm, uv, gen, extra, arr, opt = _points_args(pos, np.zeros((0, 3), np.uint32) if faces is None else faces, normals if normal_corners is None else None,
                                                           uvs if uv_corners is None else None, generic, extra, opt)
@@ -506,7 +513,17 @@ def encode_grid(pos, faces=None, normals=None, uvs=None, generic=None, extra=Non
     ptr = lambda a: None if a is None else a.ctypes.data          # noqa: E731
     out, n = C.c_void_p(), C.c_size_t()
     ec = _extra_corners(extra, len(fc))
-    if ec is None and not weld_attributes:
+    if uv_portable is not None or any(e.portable is not None for e in extra):
+        if form != 0 or geometry != 0 or len(fc) or ec is not None:
+            raise ValueError("portable integers go with a point cloud (form 0, geometry 0)")
+        up = None if uv_portable is None else np.ascontiguousarray(uv_portable, np.int32).reshape(len(pos), 2)
+        for k, e in enumerate(extra):
+            if e.portable is not None and e.portable.shape != (len(pos), e.num_components):
+                raise ValueError("extra attribute %d: portable holds one row of num_components integers per point" % k)
+        ep = (C.c_void_p * max(1, len(extra)))(*[None if e.portable is None else e.portable.ctypes.data for e in extra])
+        rc = L.synth_encode_grid_portable(ptr(pos), len(pos), ptr(nrm), ptr(uv), ptr(gen), arr, len(extra), C.byref(gi), ptr(up), ep, C.byref(opt),
+                                          C.byref(out), C.byref(n))
+    elif ec is None and not weld_attributes:
         rc = L.synth_encode_grid(form, ptr(pos), len(pos), ptr(fc) if len(fc) else None, len(fc), ptr(nrm), 0 if nrm is None else len(nrm), ptr(nci),
                                  ptr(uv), 0 if uv is None else len(uv), ptr(uci), ptr(gen), geometry, 1 if compressed else 0, arr, len(extra),
                                  C.byref(gi), C.byref(opt), C.byref(out), C.byref(n))
@@ -588,32 +605,94 @@ def bounds_grid(values):
     return grid(mn, rng if rng != 0 else np.float32(1.0))
 
 
-def merged_arguments(pos, normals=None, uvs=None, generic=None, extra=None, opt=None, pos_grid=None, uv_grid=None):
+def quantized(values, bits, grid=None):
+    """The integers (N, nc) int32 the coder quantises `values` (N, nc) float32 to at `bits` bits: on their own bounds, or on `grid`."""
+    L = lib()
+    v = np.ascontiguousarray(values, np.float32)
+    v = v.reshape(len(v), -1)
+    out = np.zeros(v.shape, np.int32)
+    if L.synth_quantized(v.ctypes.data, len(v), v.shape[1], int(bits), None if grid is None else C.byref(grid), out.ctypes.data):
+        raise RuntimeError(_err())
+    return out
+
+
+def merge_means(q, row_entries, m):
+    """The mean of every cell: q (N, nc) int32 the integers the plain call codes for the rows, row_entries (N,) below m as
+    merge_points has them; (m, nc) int32, entry j component c = floor((2 S + cnt) / (2 cnt)) over the cnt rows of cell j with sum S,
+    in 64 bits -- the exact mean, ties toward +infinity.  What dsa_encode_mean_sequential_batch codes for a masked attribute."""
+    L = lib()
+    q = np.ascontiguousarray(q, np.int32)
+    q = q.reshape(len(q), -1)
+    cells = np.ascontiguousarray(row_entries, np.uint32)
+    out = np.zeros((int(m), q.shape[1]), np.int32)
+    if L.synth_merge_means(q.ctypes.data, len(q), q.shape[1], cells.ctypes.data, int(m), out.ctypes.data):
+        raise RuntimeError(_err())
+    return out
+
+
+def _extra_rows(e, rows, grid=None):
+    """Extra e with its rows (and its portable integers) taken at `rows` (an index array or a slice); grid: in place of e.grid."""
+    return Extra(e.values[rows], attribute_type=e.attribute_type, normalized=bool(e.normalized), unique_id=e.unique_id,
+                 quantization_bits=e.quantization_bits, data_type=e.data_type, num_components=e.num_components, grid=e.grid if grid is None else grid,
+                 portable=None if e.portable is None else e.portable[rows])
+
+
+def merged_arguments(pos, normals=None, uvs=None, generic=None, extra=None, opt=None, pos_grid=None, uv_grid=None, mean_attributes=0):
     """The arguments of the plain call that writes a merged stream: (kept, row_entries, kwargs for encode_grid(form=0, geometry=0))
     -- every per-point array at [kept], every quantised attribute on an explicit grid equal to the bounds of ALL its rows (the
-    grid given, where one was)."""
+    grid given, where one was).  mean_attributes: bit a: attribute a of the stream (0 positions, then normals, uvs, generic and the
+    extras, those given) carries merge_means of its cell in place of row kept[j] -- an integer attribute as the mean array, a
+    quantised one as portable integers (uv_portable / Extra.portable) on the unchanged grid."""
     opt = opt or options()
     kept, cells = merge_points(pos, opt.pos_bits, pos_grid)
+    m = len(kept)
+    index = 1 + (normals is not None)                       # the stream's attribute index of the next attribute
+    if mean_attributes & 1 or (normals is not None and mean_attributes & 2):
+        raise ValueError("mean_attributes: positions and normals carry no mean")
     take = lambda a, nc: None if a is None else np.ascontiguousarray(np.asarray(a).reshape(-1, nc)[kept])      # noqa: E731
+    pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+    ug = uv_grid if uv_grid is not None or uvs is None else bounds_grid(np.asarray(uvs, np.float32).reshape(-1, 2))
+    uv_portable = None
+    if uvs is not None:
+        if (mean_attributes >> index) & 1:
+            uv_portable = merge_means(quantized(np.asarray(uvs, np.float32).reshape(-1, 2), opt.uv_bits, ug), cells, m)
+        index += 1
+    gen = None if generic is None else np.asarray(generic)[kept]
+    if generic is not None:
+        if (mean_attributes >> index) & 1:
+            g = np.asarray(generic)
+            gen = merge_means(g.reshape(len(g), -1).astype(np.int32), cells, m).astype(g.dtype).reshape((m,) + g.shape[1:])
+        index += 1
     ex = []
     for e in (extra or []):
         e = e if isinstance(e, Extra) else Extra(e)
         g = e.grid
-        if g is None and e.values.dtype == np.dtype(np.float32):
+        is_float = e.values.dtype == np.dtype(np.float32)
+        if g is None and is_float:
             g = bounds_grid(e.values)
-        ex.append(Extra(e.values[kept], attribute_type=e.attribute_type, normalized=bool(e.normalized), unique_id=e.unique_id,
-                        quantization_bits=e.quantization_bits, data_type=e.data_type, num_components=e.num_components, grid=g))
-    pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
-    kw = dict(pos=pos[kept], normals=take(normals, 3), uvs=take(uvs, 2), generic=None if generic is None else np.asarray(generic)[kept],
-              extra=ex, opt=opt, pos_grid=pos_grid if pos_grid is not None else bounds_grid(pos),
-              uv_grid=uv_grid if uv_grid is not None or uvs is None else bounds_grid(np.asarray(uvs, np.float32).reshape(-1, 2)))
+        x = _extra_rows(e, kept, g)
+        if (mean_attributes >> index) & 1:
+            if is_float:
+                bits = e.quantization_bits or (opt.uv_bits if e.attribute_type == 3 else 8)
+                x.portable = merge_means(quantized(e.values, bits, g), cells, m)
+            else:
+                x.values = np.ascontiguousarray(merge_means(e.values.astype(np.int64).astype(np.int32), cells, m).astype(e.values.dtype))
+        ex.append(x)
+        index += 1
+    if mean_attributes >> index:
+        raise ValueError("mean_attributes: a bit names an attribute the stream does not have")
+    kw = dict(pos=pos[kept], normals=take(normals, 3), uvs=take(uvs, 2), generic=gen,
+              extra=ex, opt=opt, pos_grid=pos_grid if pos_grid is not None else bounds_grid(pos), uv_grid=ug)
+    if uv_portable is not None:
+        kw["uv_portable"] = uv_portable
     return kept, cells, kw
 
 
-def encode_merged(pos, normals=None, uvs=None, generic=None, extra=None, opt=None, pos_grid=None, uv_grid=None):
+def encode_merged(pos, normals=None, uvs=None, generic=None, extra=None, opt=None, pos_grid=None, uv_grid=None, mean_attributes=0):
     """encode_grid(form=0, geometry=0) of one point per occupied cell: (stream, kept, row_entries), merged_arguments coded.  What
-    dsa_encode_merged_sequential_batch with merge_points = 1 must write, and the rows its handle must report."""
-    kept, cells, kw = merged_arguments(pos, normals, uvs, generic, extra, opt, pos_grid, uv_grid)
+    dsa_encode_merged_sequential_batch with merge_points = 1 must write, and the rows its handle must report; with mean_attributes
+    what dsa_encode_mean_sequential_batch must."""
+    kept, cells, kw = merged_arguments(pos, normals, uvs, generic, extra, opt, pos_grid, uv_grid, mean_attributes)
     p = kw.pop("pos")
     return encode_grid(p, None, form=0, geometry=0, **kw), kept, cells
 
@@ -708,7 +787,7 @@ def cell_parts(pos, bits, part_cells, grid=None):
 CellParts = collections.namedtuple("CellParts", "streams kept row_entries ranges qmin qmax")
 
 
-def encode_cell_parts(pos, normals=None, uvs=None, generic=None, extra=None, opt=None, pos_grid=None, uv_grid=None, part_cells=0):
+def encode_cell_parts(pos, normals=None, uvs=None, generic=None, extra=None, opt=None, pos_grid=None, uv_grid=None, part_cells=0, mean_attributes=0):
     """One point per occupied cell, and the kept order in parts of at most part_cells points, each coded as a point cloud of its own
     on the cloud's grid: CellParts(streams, kept, row_entries, ranges, qmin, qmax) with merged_arguments' rows and grids -- every
     per-point array at [kept[lo:hi]], every quantised attribute on an explicit grid equal to the bounds of ALL input rows (the grid
@@ -716,15 +795,14 @@ def encode_cell_parts(pos, normals=None, uvs=None, generic=None, extra=None, opt
     report."""
     opt = opt or options()
     kept, cells, ranges, qmin, qmax = cell_parts(pos, opt.pos_bits, part_cells, pos_grid)
-    _, _, kw = merged_arguments(pos, normals, uvs, generic, extra, opt, pos_grid, uv_grid)
+    _, _, kw = merged_arguments(pos, normals, uvs, generic, extra, opt, pos_grid, uv_grid, mean_attributes)
     p = kw.pop("pos")
     streams = []
     for lo, hi in ranges:
         take = lambda a: None if a is None else np.ascontiguousarray(a[lo:hi])          # noqa: E731
-        ex = [Extra(e.values[lo:hi], attribute_type=e.attribute_type, normalized=bool(e.normalized), unique_id=e.unique_id,
-                    quantization_bits=e.quantization_bits, data_type=e.data_type, num_components=e.num_components, grid=e.grid) for e in kw["extra"]]
+        ex = [_extra_rows(e, slice(lo, hi)) for e in kw["extra"]]
         streams.append(encode_grid(take(p), None, normals=take(kw["normals"]), uvs=take(kw["uvs"]), generic=take(kw["generic"]), extra=ex, opt=opt,
-                                   form=0, geometry=0, pos_grid=kw["pos_grid"], uv_grid=kw["uv_grid"]))
+                                   form=0, geometry=0, pos_grid=kw["pos_grid"], uv_grid=kw["uv_grid"], uv_portable=take(kw.get("uv_portable"))))
     return CellParts(streams, kept, cells, ranges, qmin, qmax)
 
 
@@ -753,7 +831,8 @@ def lod_parts(pos, bits, part_cells, lod_base_bits, grid=None):
 LodParts = collections.namedtuple("LodParts", "streams kept row_entries ranges qmin qmax level levels")
 
 
-def encode_lod_parts(pos, normals=None, uvs=None, generic=None, extra=None, opt=None, pos_grid=None, uv_grid=None, part_cells=0, lod_base_bits=0):
+def encode_lod_parts(pos, normals=None, uvs=None, generic=None, extra=None, opt=None, pos_grid=None, uv_grid=None, part_cells=0, lod_base_bits=0,
+                     mean_attributes=0):
     """Additive levels of detail of the kept points, every level in parts of at most part_cells points, each part coded as a point
     cloud of its own on the cloud's grid: what encode_cell_parts returns with `kept` the rows in LOD order (ranges and row_entries
     count in it), plus `level` per stream and `levels` = L = position bits - lod_base_bits + 1.  Every per-point array at
@@ -762,10 +841,10 @@ def encode_lod_parts(pos, normals=None, uvs=None, generic=None, extra=None, opt=
     lod_base_bits 0: encode_cell_parts, every stream of level 0 of 1."""
     opt = opt or options()
     if lod_base_bits == 0:
-        cp = encode_cell_parts(pos, normals, uvs, generic, extra, opt, pos_grid, uv_grid, part_cells)
+        cp = encode_cell_parts(pos, normals, uvs, generic, extra, opt, pos_grid, uv_grid, part_cells, mean_attributes)
         return LodParts(*cp, level=np.zeros(len(cp.streams), np.uint32), levels=1)
     lod, cells, ranges, level, qmin, qmax = lod_parts(pos, opt.pos_bits, part_cells, lod_base_bits, pos_grid)
-    kept, _, kw = merged_arguments(pos, normals, uvs, generic, extra, opt, pos_grid, uv_grid)
+    kept, _, kw = merged_arguments(pos, normals, uvs, generic, extra, opt, pos_grid, uv_grid, mean_attributes)
     at = np.zeros(int(kept.max()) + 1, np.int64)
     at[kept] = np.arange(len(kept))
     idx = at[lod]                                # where in kept (the order of merged_arguments' arrays) every lod entry lies
@@ -773,10 +852,9 @@ def encode_lod_parts(pos, normals=None, uvs=None, generic=None, extra=None, opt=
     streams = []
     for lo, hi in ranges:
         take = lambda a: None if a is None else np.ascontiguousarray(a[idx[lo:hi]])          # noqa: E731
-        ex = [Extra(e.values[idx[lo:hi]], attribute_type=e.attribute_type, normalized=bool(e.normalized), unique_id=e.unique_id,
-                    quantization_bits=e.quantization_bits, data_type=e.data_type, num_components=e.num_components, grid=e.grid) for e in kw["extra"]]
+        ex = [_extra_rows(e, idx[lo:hi]) for e in kw["extra"]]
         streams.append(encode_grid(take(p), None, normals=take(kw["normals"]), uvs=take(kw["uvs"]), generic=take(kw["generic"]), extra=ex, opt=opt,
-                                   form=0, geometry=0, pos_grid=kw["pos_grid"], uv_grid=kw["uv_grid"]))
+                                   form=0, geometry=0, pos_grid=kw["pos_grid"], uv_grid=kw["uv_grid"], uv_portable=take(kw.get("uv_portable"))))
     return LodParts(streams, lod, cells, ranges, qmin, qmax, level, opt.pos_bits - lod_base_bits + 1)
 
 

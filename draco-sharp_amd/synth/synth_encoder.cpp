@@ -403,7 +403,8 @@ static int encode_grid(int form, const float *pos, uint32_t nv, const uint32_t *
                        const uint32_t *normal_corners, const float *uvs, uint32_t nu, const uint32_t *uv_corners, const void *generic,
                        int geometry, int compressed, const synth_extra *extras, const synth_extra_corners *extra_corners, uint32_t num_extras,
                        const synth_grids *grids, const synth_options *opt, int weld_attributes, uint8_t **out, size_t *out_len,
-                       std::vector<std::vector<uint32_t>> *rows = nullptr) {      // rows: the entry rows of the stream in place of its bytes (synth_entry_rows)
+                       std::vector<std::vector<uint32_t>> *rows = nullptr,       // rows: the entry rows of the stream in place of its bytes (synth_entry_rows)
+                       const int32_t *uv_portable = nullptr, const int32_t *const *extra_portable = nullptr) {      // form 0: integers in place of the quantiser's output (synth_encode_grid_portable)
   try {
     synth::check(form >= 0 && form <= 2, "form: 0 (sequential), 1 (Edgebreaker) or 2 (one row per point)");
     std::vector<synth::ExtraAttr> ex, ex2;
@@ -414,6 +415,9 @@ static int encode_grid(int form, const float *pos, uint32_t nv, const uint32_t *
         ex[k].corners = extra_corners[k].corners; ex[k].rows = extra_corners[k].num_rows;
       }
     { const std::string why = synth::extras_error(in); synth::check(why.empty(), why.c_str()); }
+    synth::check(form == 0 || (!uv_portable && !extra_portable), "portable integers go with a sequential stream (form 0)");
+    in.uv_portable = uvs ? uv_portable : nullptr;
+    for (uint32_t k = 0; k < num_extras && extra_portable; ++k) ex[k].portable = extra_portable[k];
     if (grids) {
       in.pos_grid = &grids->position;
       if (uvs) in.uv_grid = &grids->texcoord;
@@ -470,7 +474,35 @@ int synth_encode_grid(int form, const float *pos, uint32_t nv, const uint32_t *f
                       const synth_options *opt, uint8_t **out, size_t *out_len) {
   return encode_grid(form, pos, nv, faces, nf, normals, nn, normal_corners, uvs, nu, uv_corners, generic, geometry, compressed, extras, nullptr, num_extras, grids, opt, 0, out, out_len);
 }
-// ... with row ids per corner for attributes of the list (form 1) or the listed attributes welded alone (form 2, weld_attributes != 0)
+// synth_encode_grid, form 0, with integers given in place of the quantiser's output: uv_portable (nv rows of 2, or NULL) for the
+// texture coordinates, extra_portable (NULL, or num_extras pointers, each NULL or nv rows of the attribute's components) for float32
+// attributes of the list.  Bounds, grids and the stream's header are what the floats give; only the coded integers are replaced.
+int synth_encode_grid_portable(const float *pos, uint32_t nv, const float *normals, const float *uvs, const void *generic, const synth_extra *extras, uint32_t num_extras,
+                               const synth_grids *grids, const int32_t *uv_portable, const int32_t *const *extra_portable, const synth_options *opt, uint8_t **out, size_t *out_len) {
+  return encode_grid(0, pos, nv, nullptr, 0, normals, normals ? nv : 0, nullptr, uvs, uvs ? nv : 0, nullptr, generic, 0, 0, extras, nullptr, num_extras, grids, opt, 0, out, out_len, nullptr,
+                     uv_portable, extra_portable);
+}
+// The integers the coder quantises `n` rows of `nc` floats to at `bits` bits (dsa_encode_host.h quantize): on their own bounds, or on `grid`.
+int synth_quantized(const float *values, uint32_t n, int nc, int bits, const synth::Grid *grid, int32_t *out) {
+  try {
+    synth::check(values != nullptr && n > 0 && nc >= 1 && nc <= 4 && bits >= 1 && bits <= 20, "quantized: n rows of 1 - 4 floats at 1 - 20 bits");
+    synth::PortableAttr a;
+    a.att_type = 4; a.nc = a.nc_out = nc; a.seq_type = 2; a.grid = grid;
+    synth::quantize(values, n, nc, bits, a);
+    memcpy(out, a.vals.data(), 4 * a.vals.size());
+    return 0;
+  } catch (const std::exception &e) { snprintf(g_err, sizeof(g_err), "%s", e.what()); return 1; }
+}
+// The mean of every cell (dsa_encode_host.h merge_means): q[n * nc], row_entries[n] below m; means[m * nc].
+int synth_merge_means(const int32_t *q, uint32_t n, int nc, const uint32_t *row_entries, uint32_t m, int32_t *means) {
+  try {
+    std::vector<int32_t> out;
+    synth::merge_means(q, n, nc, std::vector<uint32_t>(row_entries, row_entries + n), m, out);
+    memcpy(means, out.data(), 4 * out.size());
+    return 0;
+  } catch (const std::exception &e) { snprintf(g_err, sizeof(g_err), "%s", e.what()); return 1; }
+}
+// synth_encode_grid with row ids per corner for attributes of the list (form 1) or the listed attributes welded alone (form 2, weld_attributes != 0)
 int synth_encode_corner_attributes_grid(int form, const float *pos, uint32_t nv, const uint32_t *faces, uint32_t nf, const float *normals, uint32_t nn,
                                         const uint32_t *normal_corners, const float *uvs, uint32_t nu, const uint32_t *uv_corners, const void *generic,
                                         int geometry, int compressed, const synth_extra *extras, const synth_extra_corners *extra_corners, uint32_t num_extras,

@@ -892,6 +892,47 @@ typedef struct dsa_lod_info {
   uint32_t reserved[4];                    /* zero */
 } dsa_lod_info;
 dsa_status dsa_encoded_lod_info(const dsa_encoded *encoded, uint32_t stream, dsa_lod_info *out);
+/* dsa_encode_lod_sequential_batch with the mean of every cell in chosen attributes of its kept point: what a voxel-grid downsample
+ * does to colour, intensity or a UV, on the device.  With merge_points = 1 alone entry j of every attribute carries row kept[j], the
+ * smallest input row of the cell: for anything but the position that is the value of whichever point came first in the caller's
+ * rows.  Here the masked attributes carry the mean over all rows of the cell instead.
+ *   mean_attributes: bit a set: attribute a of the STREAM (0 the positions, then normals, texture coordinates, the generic
+ *   attribute and the listed attributes, those the cloud has) carries the cell's mean.  Taken only with merge_points = 1 (and so
+ *   point_order = 1, geometry 0); part_cells and lod_base_bits compose with it unchanged.
+ *   key, perm, kept[0 .. m) and row_entries are exactly what merge_points = 1 defines.  R(j) = { r : row_entries[r] == j }, cnt =
+ *   |R(j)|.  For every masked attribute a and component c, q_a[r][c] is the integer the plain call codes for row r: the quantiser's
+ *   output on the cloud's bounds or grid for a quantised float attribute, the element widened to int32 for an integer attribute.
+ *   Entry j carries
+ *       mean = floor((2 S + cnt) / (2 cnt)),   S = sum over r in R(j) of q_a[r][c],
+ *   in 64-bit signed arithmetic with floor division: the exact mean, ties toward +infinity; a cell of one point keeps its value.
+ *   Pure integer arithmetic: a function of the SET of rows of the cell, not of their order, bit-identical on host and device.  The
+ *   mean lies between the minimum and the maximum of its addends, so bounds, grids, histogram sizes, the range of the wrap bounds
+ *   and every refusal are those of the call without the mask.  An attribute without its bit carries row kept[j]; positions are
+ *   never touched (they are equal inside a cell).
+ *   Every stream is byte for byte what the same call with mean_attributes = 0 writes for an input whose masked attributes hold, at
+ *   row kept[j], values whose coded integers are the means: for an integer attribute the mean array itself, for a quantised one the
+ *   mean integers on the unchanged bounds or grid.  The handle is unchanged in shape: dsa_encoded_entry_rows is kept / lod slices
+ *   (the row the entry's unmasked attributes carry), dsa_encoded_row_entries, dsa_encoded_part_info, dsa_encoded_lod_info and
+ *   dsa_batch_source_rows work as before; the number of rows of cell j is the count of j in row_entries.
+ *   mean_attributes = 0: the bytes, the messages, the work, the rows and the handle shape of dsa_encode_lod_sequential_batch.
+ * Fails the call with DSA_ERR_INVALID_ARGUMENT before any mesh is looked at, dsa_last_error naming the field: mean_attributes != 0
+ * without merge_points = 1; a bit at or above DSA_MAX_ATTRIBUTES; a non-zero reserved word.  Refusals of the nested option structs
+ * keep their own words.  A cloud fails alone with DSA_ERR_INVALID_ARGUMENT (it keeps one slot; the message names mean_attributes
+ * and the attribute) when a set bit names the positions, the normals, or an attribute its stream does not have.
+ * On the device two kernels behind the merge (k_enc_mean_sum 24 VGPR / 45 SGPR, k_enc_mean_store 23 / 29; no LDS, no scratch;
+ * dsa_encode_order.h) take 0.6 ms of a 64 ms call for a 4 Mi-point scan with a colour and a float attribute in 256 parts, against 264 ms
+ * for download, host means and a second encode.
+ * Not built: mean normals (octahedral integers do not average across the fold, a vector sum needs a fixed-point rule of its own);
+ * weighted means; means per coarser lod cell (a level's point carries the mean of its finest cell); a vote for label attributes.
+ * Added after ABI 4 without changing it: callers detect the feature by the symbol dsa_encode_mean_sequential_batch. */
+typedef struct dsa_encode_mean_options {
+  dsa_encode_lod_options lod;              /* as for dsa_encode_lod_sequential_batch, same legal values */
+  uint32_t mean_attributes;                /* 0 (default): the very request of the lod call; bit a: attribute a of the stream carries the cell's mean */
+  int32_t reserved[7];                     /* must be zero */
+} dsa_encode_mean_options;
+void dsa_encode_default_mean_options(dsa_encode_mean_options *options);
+dsa_status dsa_encode_mean_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids,
+                                            const dsa_encode_mean_options *options, dsa_encoded **out);
 /* The rows of a decoded batch per POINT: for every mesh of `batch` and every attribute a of its stream,
  *     rows[a][p] = entry_rows[a][map[a][p]]          (map: the decoder's point -> entry map, dsa_batch_device_point_map)
  * -- which row of the arrays given to the encoder point p carries, gathered on the device (k_source_rows) so that neither the maps

@@ -1,0 +1,61 @@
+"""The encoder's mean kernels (draco-sharp_amd/csrc/dsa_encode_order.h: k_enc_mean_sum, k_enc_mean_store, behind the product's sort
+and merge and under the product's launch sequences, in the arena of the product's layout) compiled for the host under
+AddressSanitizer + UBSan (tests/hostcheck/encmeans_host.cpp) and held against the host coder (synth::merge_points,
+synth::merge_means) on every case of tests/mergecases.py, with one and with two masked streams per cloud, the threads run forwards
+and backwards, the arena's gaps poisoned and the sums and counts filled with a pattern until the product's memset.  A check of the
+product source on CPU, not a CPU encode path of the product."""
+import os
+import re
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+import mergecases
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+SRC = os.path.join(HERE, "hostcheck", "encmeans_host.cpp")
+
+
+@pytest.fixture(scope="module")
+def exe(tmp_path_factory):
+    out = str(tmp_path_factory.mktemp("encmeans") / "encmeans_host")      # always rebuilt: the sources under test change
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize=signed-integer-overflow",
+                    "-fno-sanitize-recover=undefined", "-o", out, SRC], check=True)
+    return out
+
+
+def write(path, cases):
+    with open(path, "wb") as f:
+        f.write(struct.pack("<I", len(cases)))
+        for c in cases:
+            f.write(struct.pack("<IIII", len(c.pos), c.bits, int(c.grid is not None), 0))
+            f.write(np.ascontiguousarray(c.pos, np.float32).tobytes())
+            if c.grid is not None:
+                f.write(np.float32(list(c.grid[0]) + [c.grid[1]]).tobytes())
+
+
+def run(exe, tmp_path, cases):
+    path = tmp_path / "cases.bin"
+    write(path, cases)
+    r = subprocess.run([exe, str(path)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    points = sum(len(c.pos) for c in cases)
+    cells = sum(len(mergecases.pin(c.pos, c.bits, c.grid)[0]) for c in cases)
+    # two masks, forwards and backwards
+    assert "encmeans: %d cases in " % len(cases) in r.stdout and "(%d points, %d cells, " % (4 * points, 4 * cells) in r.stdout, r.stdout
+    return int(re.search(r"(\d+) sums beyond 32 bits", r.stdout).group(1))
+
+
+def test_every_case(exe, tmp_path):
+    cases = mergecases.cases()
+    assert len({c.bits for c in cases}) >= 3 and any(c.grid is None for c in cases) and any(c.name == "tile-with-no-head" for c in cases)
+    assert run(exe, tmp_path, cases) > 100              # runs whose sums a 32-bit accumulator cannot hold
+
+
+def test_a_large_cloud(exe, tmp_path):
+    """about 70 000 points in 2 049 cells: 69 tiles, most of them without a head"""
+    c = mergecases.large()
+    assert 60000 < len(c.pos) < 80000
+    run(exe, tmp_path, [c])
