@@ -1213,45 +1213,15 @@ static dsa_status enc_stage_attributes(dsa_context *ctx, EncLane &lane, EncChunk
     order_timing = getenv("DSA_ENC_TIMING") != nullptr;
     if (order_timing) { ENC_TRY(hipStreamSynchronize(st)); order_lap("uploads + quantisers"); }
     const uint32_t gf = L.max_count ? std::max(1u, std::min(64u, (L.max_count + 1023u) / 1024u)) : 0u;
-    dsa::enc_order_launch([st](auto kernel, uint32_t grid_x, uint32_t grid_y, uint32_t block, auto... args) { hipLaunchKernelGGL(kernel, dim3(grid_x, grid_y), dim3(block), 0, st, args...); },
-                          arena, (const dsa::EncOrder *)(arena + L.ord_at), (uint32_t)L.ord.size(), (const dsa::EncOrderTile *)(arena + L.ord_tiles_at), (uint32_t)L.ord_tiles.size(),
-                          L.ord_passes, ck.rq.seq.geometry == 1, gf);
-    ENC_TRY(hipGetLastError());
-    if (order_timing) { ENC_TRY(hipStreamSynchronize(st)); order_lap("point order"); }
-    if (L.merge) {             // merge_points: one point per cell, behind the sort; nv of the cloud's streams falls to the cells it has
-      dsa::enc_merge_launch([st](auto kernel, uint32_t grid_x, uint32_t grid_y, uint32_t block, auto... args) { hipLaunchKernelGGL(kernel, dim3(grid_x, grid_y), dim3(block), 0, st, args...); },
-                            arena, (dsa::EncOrder *)(arena + L.ord_at), (uint32_t)L.ord.size(), (const dsa::EncOrderTile *)(arena + L.ord_tiles_at), (uint32_t)L.ord_tiles.size(),
-                            L.ord_passes, d_streams, ns);
-      ENC_TRY(hipGetLastError());
-      if (order_timing) { ENC_TRY(hipStreamSynchronize(st)); order_lap("point merge"); }
-    }
-    if (!L.means.empty()) {    // mean_attributes: the mean of the cell into vals at every kept row, in front of everything that reads vals or turns row_entries into lod order
-      ENC_TRY(hipMemsetAsync(arena + L.mean_zero_at, 0, L.mean_zero_bytes, st));
-      dsa::enc_mean_launch([st](auto kernel, uint32_t grid_x, uint32_t grid_y, uint32_t block, auto... args) { hipLaunchKernelGGL(kernel, dim3(grid_x, grid_y), dim3(block), 0, st, args...); },
-                           arena, (const dsa::EncOrder *)(arena + L.ord_at), (uint32_t)L.ord.size(), (const dsa::EncOrderTile *)(arena + L.ord_tiles_at), (uint32_t)L.ord_tiles.size(),
-                           L.ord_passes, (const dsa::EncMeanCloud *)(arena + L.mean_clouds_at), (const dsa::EncMean *)(arena + L.means_at), (uint32_t)L.means.size(), L.mean_most);
-      ENC_TRY(hipGetLastError());
-      if (order_timing) { ENC_TRY(hipStreamSynchronize(st)); order_lap("cell means"); }
-    }
-    if (L.lod) {               // lod_base_bits: the kept order by (level, kept) and the parts of every level, in place of the step below
-      dsa::enc_lod_launch([st](auto kernel, uint32_t grid_x, uint32_t grid_y, uint32_t block, auto... args) { hipLaunchKernelGGL(kernel, dim3(grid_x, grid_y), dim3(block), 0, st, args...); },
-                          arena, (const dsa::EncOrder *)(arena + L.ord_at), (uint32_t)L.ord.size(), (const dsa::EncOrderTile *)(arena + L.ord_tiles_at), (uint32_t)L.ord_tiles.size(),
-                          L.ord_passes, (dsa::EncPart *)(arena + L.parts_at), (uint32_t)L.parts.size(), d_streams, ns);
-      ENC_TRY(hipGetLastError());
-      if (order_timing) { ENC_TRY(hipStreamSynchronize(st)); order_lap("levels"); }
-    } else
-    if (L.cell_parts) {        // part_cells: the kept order in parts -- k_enc_merge_scan has left m, the sizes of the part slots follow from it on the device
-      dsa::enc_part_cells_launch([st](auto kernel, uint32_t grid_x, uint32_t grid_y, uint32_t block, auto... args) { hipLaunchKernelGGL(kernel, dim3(grid_x, grid_y), dim3(block), 0, st, args...); },
-                                 (dsa::EncOrder *)(arena + L.ord_at), (uint32_t)L.ord.size(), (dsa::EncPart *)(arena + L.parts_at), (uint32_t)L.parts.size(), d_streams, ns, L.ord_passes);
-      ENC_TRY(hipGetLastError());
-    }
-    if (L.split) {             // part_points: the box of every part's position integers, behind the sort (the parts' streams read their slices of it as they are)
-      dsa::enc_part_launch([st](auto kernel, uint32_t grid_x, uint32_t grid_y, uint32_t block, auto... args) { hipLaunchKernelGGL(kernel, dim3(grid_x, grid_y), dim3(block), 0, st, args...); },
-                           arena, (const dsa::EncOrder *)(arena + L.ord_at), (uint32_t)L.ord.size(), (dsa::EncPart *)(arena + L.parts_at), (uint32_t)L.parts.size(),
-                           (const dsa::EncPartTile *)(arena + L.part_tiles_at), (uint32_t)L.part_tiles.size(), L.ord_passes);
-      ENC_TRY(hipGetLastError());
-      if (order_timing) { ENC_TRY(hipStreamSynchronize(st)); order_lap("part boxes"); }
-    }
+    // the stage's one launch sequence (enc_order_stage, dsa_encode_layout.h); `said`: what the first call of it that failed left
+    dsa_status said = DSA_OK;
+    auto zero = [&](uint64_t off, uint64_t bytes) -> dsa_status { ENC_TRY(hipMemsetAsync(arena + off, 0, bytes, st)); return DSA_OK; };
+    auto behind = [&](const char *lap) -> dsa_status { ENC_TRY(hipGetLastError()); if (order_timing && lap) { ENC_TRY(hipStreamSynchronize(st)); order_lap(lap); } return DSA_OK; };
+    if (!enc_order_stage([st](auto kernel, uint32_t grid_x, uint32_t grid_y, uint32_t block, auto... args) { hipLaunchKernelGGL(kernel, dim3(grid_x, grid_y), dim3(block), 0, st, args...); },
+                         [&](uint64_t off, uint64_t bytes) { if (said == DSA_OK) said = zero(off, bytes); },
+                         [&](const char *lap) { if (said == DSA_OK) said = behind(lap); return said == DSA_OK; },
+                         L, ck.rq.seq.geometry == 1, gf, arena, d_streams, ns))
+      return said;
   }
   hipLaunchKernelGGL(dsa::k_enc_gather, dim3(ns), dim3(256), 0, st, arena, d_streams, ns);
   over_streams(dsa::k_enc_corr);

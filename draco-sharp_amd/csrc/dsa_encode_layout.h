@@ -318,7 +318,7 @@ struct EncLayout {
   // (part, tile) pairs of all of them, both among the uploads
   bool split = false;
   bool cell_parts = false;                  // EncRequest::cell_parts: split and merge, a cloud's records are part SLOTS the device sizes (k_enc_part_cells)
-  bool lod = false;                         // EncRequest::lod: cell_parts whose slots are the parts of the cloud's levels (k_enc_lod_parts)
+  bool lod = false;                         // EncRequest::lod: cell_parts whose slots are the parts of the cloud's levels (k_enc_lod_*, then k_enc_part_cells)
   std::vector<dsa::EncPart> parts;
   std::vector<dsa::EncPartTile> part_tiles;
   std::vector<uint32_t> part_of_mesh;
@@ -331,6 +331,69 @@ struct EncLayout {
   uint64_t mean_clouds_at = 0, means_at = 0, mean_zero_at = 0, mean_zero_bytes = 0;
   uint32_t mean_most = 0;                   // the most masked streams a cloud of the chunk has: the y of the mean kernels' grid
 };
+
+// ---- the point-order stage of a chunk whose layout has order records (dsa_encode_order.h has the kernels and their contracts): the
+// one launch sequence, which enc_stage_attributes runs on the device and every host check of these kernels thread by thread.
+//   launch(kernel, grid x, grid y, block, arguments...)   hipLaunchKernelGGL on the lane's stream; the thread-by-thread loop
+//   zero(offset, bytes)                                   hipMemsetAsync on that stream; memset
+//   after(name)                                           behind every group of kernels: the product asks for a launch error and, under
+//                                                         DSA_ENC_TIMING, drains the stream and prints the lap `name` (nullptr: a group
+//                                                         without a lap of its own, its time is part of the next lap).  False ends
+//                                                         the stage, which then returns false.
+// meshes: the chunk codes meshes (rank); gx_faces: blocks over the corners of its largest mesh with compressed indices (0: no mesh
+// has any).  `streams`: the chunk's ns EncStream records where the kernels read and write them.
+template <class Launch, class Zero, class After>
+static inline bool enc_order_stage(Launch &&launch, Zero &&zero, After &&after, const EncLayout &L, bool meshes, uint32_t gx_faces,
+                                   uint8_t *arena, dsa::EncStream *streams, uint32_t ns) {
+  const uint32_t nc = (uint32_t)L.ord.size(), nt = (uint32_t)L.ord_tiles.size(), np = (uint32_t)L.parts.size(), npt = (uint32_t)L.part_tiles.size();
+  const uint32_t nm = (uint32_t)L.means.size(), wave = (uint32_t)WAVE;
+  if (nc == 0 || nt == 0) return true;
+  dsa::EncOrder *clouds = (dsa::EncOrder *)(arena + L.ord_at);
+  const dsa::EncOrderTile *tiles = (const dsa::EncOrderTile *)(arena + L.ord_tiles_at);
+  dsa::EncPart *parts = (dsa::EncPart *)(arena + L.parts_at);
+  const dsa::EncPartTile *part_tiles = (const dsa::EncPartTile *)(arena + L.part_tiles_at);
+  const dsa::EncMeanCloud *mclouds = (const dsa::EncMeanCloud *)(arena + L.mean_clouds_at);
+  const dsa::EncMean *means = (const dsa::EncMean *)(arena + L.means_at);
+  // the permutation of every cloud, behind the quantisers and in front of the gather
+  launch(dsa::k_enc_order_keys, nt, 1u, 256u, arena, clouds, tiles, nt);
+  for (uint32_t p = 0; p < L.ord_passes; ++p) {
+    launch(dsa::k_enc_order_hist, nt, 1u, wave, arena, clouds, tiles, nt, p);
+    launch(dsa::k_enc_order_scan, nc, 1u, wave, arena, clouds, nc);
+    launch(dsa::k_enc_order_scatter, nt, 1u, wave, arena, clouds, tiles, nt, p);
+  }
+  if (meshes) launch(dsa::k_enc_order_rank, nt, 1u, 256u, arena, clouds, tiles, nt);
+  if (meshes && gx_faces) launch(dsa::k_enc_order_faces, gx_faces, nc, 256u, arena, clouds, nc);
+  if (!after("point order")) return false;
+  if (L.merge) {               // merge_points: one point per cell, behind the sort; nv of the cloud's streams falls to the cells it has
+    launch(dsa::k_enc_merge_heads, nt, 1u, wave, arena, clouds, tiles, nt);
+    launch(dsa::k_enc_merge_scan<dsa::EncStream>, nc, 1u, wave, arena, clouds, nc, streams, ns);
+    launch(dsa::k_enc_merge_compact, nt, 1u, wave, arena, clouds, tiles, nt);
+    if (!after("point merge")) return false;
+  }
+  if (!L.means.empty()) {      // mean_attributes: the mean of the cell into vals at every kept row, in front of everything that reads vals or turns row_entries into lod order
+    zero(L.mean_zero_at, L.mean_zero_bytes);
+    if (L.mean_most) {
+      launch(dsa::k_enc_mean_sum, nt, L.mean_most, wave, arena, clouds, tiles, nt, mclouds, means, nm);
+      launch(dsa::k_enc_mean_store, nt, L.mean_most, 256u, arena, clouds, tiles, nt, mclouds, means, nm);
+    }
+    if (!after("cell means")) return false;
+  }
+  if (L.lod && np) {           // lod_base_bits: the kept order by (level, kept); the slot sizer below cuts every level into its parts
+    launch(dsa::k_enc_lod_levels, nt, 1u, wave, arena, clouds, tiles, nt);
+    launch(dsa::k_enc_lod_scan, nc, 1u, wave, arena, clouds, nc);
+    launch(dsa::k_enc_lod_scatter, nt, 1u, wave, arena, clouds, tiles, nt);
+    launch(dsa::k_enc_lod_cells, nt, 1u, 256u, arena, clouds, tiles, nt);
+  }
+  if (L.cell_parts) {          // part_cells: k_enc_merge_scan has left m (k_enc_lod_scan the points of every level), the sizes of the part slots follow from it on the device
+    if (np) launch(dsa::k_enc_part_cells<dsa::EncStream>, (np + wave - 1u) / wave, 1u, wave, arena, clouds, nc, parts, np, streams, ns);
+    if (!after(L.lod ? "levels" : nullptr)) return false;
+  }
+  if (L.split) {               // part_points: the box of every part's position integers, behind the sort (the parts' streams read their slices of it as they are)
+    if (np && npt) launch(dsa::k_enc_part_bounds, npt, 1u, wave, arena, clouds, nc, parts, np, part_tiles, npt);
+    if (!after("part boxes")) return false;
+  }
+  return true;
+}
 
 static inline bool enc_multi_scheme(const synth::PortableAttr &a) { return a.seq_type != 3 && (a.prediction == 2 || a.prediction == 4); }
 // the attribute reads the mesh's topology (TexCoordsPortable, GeometricNormal, the multi-parallelogram schemes)
@@ -945,7 +1008,7 @@ static void enc_layout(EncChunk &ck) {
 // with records, regions and tiles for min(part_cells, n) points -- under n + part_cells points per attribute in all; the streams' map
 // is the kept buffer, as with the merge, and k_enc_part_cells writes every slot's lo, n, nv and e2v.
 // EncRequest::lod (cell_parts with levels): ceil(n / part_cells) + L - 1 slots, the streams' map is the lod buffer, which with pos takes
-// the sort's dead key buffer; a level table per cloud among the kernels' regions; k_enc_lod_parts writes the slots.
+// the sort's dead key buffer; a level table per cloud among the kernels' regions; k_enc_part_cells writes the slots from it.
 // EncRequest::means (merge with mean_attributes): an EncMeanCloud per cloud and an EncMean per masked stream among the uploads; behind
 // every other region a u32[n] count region per cloud and an i64[n nc] sum region per masked stream, one range that is zeroed on the
 // stream in front of k_enc_mean_sum.  No region is reused and nothing else grows.
@@ -973,7 +1036,7 @@ static void enc_layout_sequential(EncChunk &ck) {
     if (ordered) {
       dsa::EncOrder O;
       memset(&O, 0, sizeof(O));
-      O.n = V; O.tiles = (V + ORD_TILE - 1u) / ORD_TILE; O.bits = (uint32_t)ck.opt.pos_bits;
+      O.n = V; O.tiles = (V + ORD_TILE - 1u) / ORD_TILE; O.bits = (uint32_t)ck.opt.pos_bits; O.last = dsa::enc_order_passes(O.bits) & 1u;
       if (merge) { O.merge = 1; O.stream0 = s0; O.streams = (uint32_t)atts.size(); }
       if (merge || split) L.ord_of_mesh[i] = (uint32_t)L.ord.size();
       if (ck.rq.means()) {                                     // the masked streams of the cloud (the first part's: the parts share its vals)
@@ -1042,8 +1105,8 @@ static void enc_layout_sequential(EncChunk &ck) {
       if (is_mesh) O.rank = A.take(4ull * V);
       if (merge) O.cells = A.take(4ull * V);
       // (lod_base_bits: lod and pos in the key buffer the last pass read -- dead behind the merge, two u32[n] -- and the level table)
-      if (L.lod) { O.lod_rows = O.key[(L.ord_passes + 1u) & 1u]; O.lod_table = A.take(sizeof(dsa::EncLodTable)); }
-      for (uint32_t k = 0; k < na; ++k) L.streams[s0 + k].e2v = O.row[(L.ord_passes + (merge ? 1u : 0u)) & 1u];
+      if (L.lod) { O.lod_rows = O.key[O.last ^ 1u]; O.lod_table = A.take(sizeof(dsa::EncLodTable)); }
+      for (uint32_t k = 0; k < na; ++k) L.streams[s0 + k].e2v = merge ? dsa::ord_kept(O) : dsa::ord_sorted(O).row;
     }
     if (split) {
       // a set of records per part: the first part's with the part's entries -- a slice of the sorted rows -- and regions of the
@@ -1059,7 +1122,7 @@ static void enc_layout_sequential(EncChunk &ck) {
             enc_value_stream_regions(S, std::min(ck.rq.part_cells, V), ck.hist_cap_of(i, k), A, p ? L.streams[s0 + k].vals : 0);
             continue;
           }
-          S.nv = P.n; S.e2v = O.row[L.ord_passes & 1u] + 4ull * P.lo;
+          S.nv = P.n; S.e2v = dsa::ord_sorted(O).row + 4ull * P.lo;
           enc_value_stream_regions(S, P.n, ck.hist_cap_of(i, k), A, p ? L.streams[s0 + k].vals : 0);
         }
       }

@@ -29,10 +29,13 @@
 // k_enc_gather behind it puts every attribute in the order.  Nothing between the quantisers and k_enc_gather goes through the host.
 // Every cloud fits the same three steps a pass; a one-workgroup LDS sort for clouds of one tile was not built (DESIGN.md 7.3 has
 // what the crowded batch of small clouds costs).
+// The order of all steps of this file -- the sort, then the merge, the means, the levels, the part sizes and the part boxes where the
+// request has them -- is written down once, in enc_order_stage (dsa_encode_layout.h), which the product and every host check run.
+// Which buffer of a pair a step reads follows from EncOrder::last alone (ord_sorted, ord_kept, ord_part_rows below).
 //
 // Wave64 throughout: the tile steps are blocks of one wave (__launch_bounds__(64)), so their barriers order LDS within a wave and
-// many tiles share a CU.  gfx950, hipcc -O3 (VGPR / SGPR / LDS bytes per block): k_enc_order_keys 16 / 26 / 0, hist 11 / 32 /
-// 1024, scan 26 / 24 / 0, scatter 16 / 55 / 1024, rank 6 / 20 / 0, faces 8 / 21 / 0; no scratch, no spills, 8 waves per SIMD.
+// many tiles share a CU.  gfx950, hipcc -O3 (VGPR / SGPR / LDS bytes per block): k_enc_order_keys 16 / 26 / 0, hist 11 / 34 /
+// 1024, scan 26 / 24 / 0, scatter 16 / 57 / 1024, rank 6 / 19 / 0, faces 8 / 21 / 0; no scratch, no spills, 8 waves per SIMD.
 // The host check runs a grid thread by thread, where lanes cannot meet: the three wave steps have a serial form for it (lane 0
 // does the tile's or the cloud's work in entry order, as k_enc_weld_scan has) -- records, tile list, regions, pass structure, keys,
 // rank and remap are the product's as they run; the ballots and shuffles themselves are held to the host coder by
@@ -52,10 +55,10 @@
 //   k_enc_merge_compact   a wave per tile: kept[tile base + heads below me] = row[e] for heads, row_entries[row[e]] = the head at or
 //                         before e for every entry; lane offsets from the ballots, a running count over the tile's 16 steps.  Not
 //                         in place (tile t writes at or below t * ORD_TILE, into the range an earlier tile may not have read yet):
-//                         kept goes to the other row buffer, row[(passes + 1) & 1], which the layout makes the streams' e2v.
+//                         kept goes to the other row buffer (ord_kept), which the layout makes the streams' e2v.
 // No atomic decides a place: kept and row_entries are functions of the input alone.  The host coder's twin is synth::merge_points;
 // tests/hostcheck/encmerge_host.cpp runs the serial forms against it, tests/test_gpu_encode_merge.py the ballots and shuffles.
-// gfx950, hipcc -O3 (VGPR / SGPR / LDS bytes per block): k_enc_merge_heads 12 / 24 / 0, scan 16 / 29 / 0, compact 16 / 27 / 0; no
+// gfx950, hipcc -O3 (VGPR / SGPR / LDS bytes per block): k_enc_merge_heads 12 / 25 / 0, scan 16 / 29 / 0, compact 14 / 27 / 0; no
 // scratch, no spills, 8 waves per SIMD.
 //
 // dsa_encode_split_sequential_batch with part_points = N >= 1 (point clouds, no merge): the sorted order of a cloud cut into P =
@@ -90,7 +93,7 @@
 // packer skips them by the flag.  P and the sizes come back in the stream records at the end of the stage, as m does for the merge.
 // The host coder's twin is synth::cell_parts; tests/hostcheck/enccellparts_host.cpp runs the steps in the product's layout against
 // it, tests/test_gpu_encode_cell_parts.py the device's.
-// gfx950, hipcc -O3 (VGPR / SGPR / LDS bytes per block): k_enc_part_cells 25 / 18 / 0; no scratch, no spills, 8 waves per SIMD.
+// gfx950, hipcc -O3 (VGPR / SGPR / LDS bytes per block): k_enc_part_cells 44 / 23 / 0 (the walk over the levels); no scratch, no spills, 8 waves per SIMD.
 //
 // dsa_encode_lod_sequential_batch with lod_base_bits = D >= 1 (point clouds, merge_points = 1, part_cells = N >= 1): additive levels
 // of detail of the kept points.  The kept keys are distinct and ascending; with c(j) the leading bit-triples, out of B = bits, that
@@ -99,7 +102,7 @@
 // bits per axis, the cell's first point in Morton order.  lod is kept in ascending (level, position in kept); level l, m_l points from
 // base_l on, is cut by the rule of part_cells applied to m_l, and the slots of a cloud are the parts of level 0, then of level 1, ...
 // (an empty level has none).  sum ceil(m_l / N) <= ceil(m / N) + (non-empty levels - 1): the layout lays out ceil(n / N) + L - 1 slots.
-// Five steps behind enc_merge_launch, in place of k_enc_part_cells and in front of k_enc_part_bounds and k_enc_gather, on the merge's
+// Four steps behind the merge, in front of k_enc_part_cells, k_enc_part_bounds and k_enc_gather, on the merge's
 // (cloud, tile) list with tiles over KEPT entries (a tile at or beyond m returns at once):
 //   k_enc_lod_levels      a wave per tile: the level of every kept entry of the tile from ord_key of vals at kept[j] and kept[j - 1]
 //                         (entry 0 of a tile reads the last kept row of the tile in front: kept is only read from here on), kept in
@@ -114,24 +117,24 @@
 //                         place: lod and pos are the two u32[n] of the key buffer the last sort pass did not write, dead behind the
 //                         merge (EncOrder::lod_rows).  No atomic decides a place: the result is a function of the input alone.
 //   k_enc_lod_cells       a thread per input row: cells[r] = pos[cells[r]], row_entries from kept order to lod order
-//   k_enc_lod_parts       a thread per slot, no shuffle, LDS or atomic: it walks the at most 20 level counts to its level and part,
-//                         writes lo / n into the slot's EncPart and the level into its pad word, nv and e2v = lod + 4 lo into every
-//                         EncStream of the slot; a slot beyond the live ones gets n = nv = 0 and kind 3, exactly as k_enc_part_cells
-//                         makes it.
+// and k_enc_part_cells behind them, the one slot sizer: for such a cloud a thread walks the at most 20 level counts of the table to
+// its level and part, writes lo / n into the slot's EncPart and the level into its pad word, nv and e2v = lod + 4 lo into every
+// EncStream of the slot; a slot beyond the live ones gets n = nv = 0 and kind 3.  A cloud without levels is the same walk over one
+// level of m entries from 0 on, read from the cloud's record (it has no table).
 // k_enc_part_bounds reads the lod buffer for such clouds (EncOrder::lod_bits says so).  k_enc_gather, k_enc_corr, k_enc_plan and
 // k_enc_rans are untouched: an empty slot goes through the ENC_PART_SIZED / kind 3 path of part_cells.  The host reads levels and
 // sizes from the EncPart records that come back and holds them to the rule (enc_write_parts).  The host coder's twin is
 // synth::lod_parts; tests/hostcheck/enclod_host.cpp runs the serial forms in the product's layout against it,
 // tests/test_gpu_encode_lod.py the ballots and shuffles.
-// gfx950, hipcc -O3 (VGPR / SGPR / LDS bytes per block): k_enc_lod_levels 26 / 33 / 0, scan 21 / 33 / 0, scatter 16 / 43 / 128, cells
-// 6 / 20 / 0, parts 44 / 19 / 0 (k_enc_part_bounds stays 18 / 22 / 0); no scratch, no spills, 8 waves per SIMD.
+// gfx950, hipcc -O3 (VGPR / SGPR / LDS bytes per block): k_enc_lod_levels 24 / 35 / 0, scan 22 / 37 / 0, scatter 14 / 44 / 128, cells
+// 6 / 20 / 0 (k_enc_part_bounds stays 18 / 22 / 0); no scratch, no spills, 8 waves per SIMD.
 //
 // dsa_encode_mean_sequential_batch with mean_attributes != 0 (point clouds, merge_points = 1): entry j of a masked attribute carries
 // mean = floor((2 S + cnt) / (2 cnt)), S the sum over the cnt rows of cell j of the integer the plain call codes for the row, in 64
 // bits -- the exact mean, ties toward +infinity, a function of the set of rows.  The mean is written into the stream's `vals` at row
 // kept[j], which is what k_enc_gather and everything behind it read: merged streams, cell parts and levels take it as they are (the
-// part streams of a cloud share the first part's vals).  Two steps behind enc_merge_launch and in front of k_enc_part_cells, k_enc_lod_*
-// (which turn cells[] into lod order), k_enc_part_bounds and k_enc_gather, on the merge's (cloud, tile) list with the cloud's masked
+// part streams of a cloud share the first part's vals).  Two steps behind the merge and in front of k_enc_lod_*
+// (which turn cells[] into lod order), k_enc_part_cells, k_enc_part_bounds and k_enc_gather, on the merge's (cloud, tile) list with the cloud's masked
 // streams in blockIdx.y (a cloud has at most DSA_MAX_ATTRIBUTES streams: one launch, no slices); launched only when the chunk has
 // a masked stream:
 //   k_enc_mean_sum        a wave per (tile, masked stream), 64 sorted entries a step: head flags from the sorted keys as
@@ -161,8 +164,8 @@ namespace dsa {
 struct EncOrder {                  // one per cloud of the chunk; in the arena, among the uploads
   uint64_t vals;                   // i32[3 n]: the position stream's integers, row order
   uint64_t key[2];                 // u64[n] each: pass p reads [p & 1], writes [(p + 1) & 1]
-  uint64_t row[2];                 // u32[n] each, likewise; row[passes & 1] is the e2v of the cloud's streams: OUTPUT perm
-                                   //   (merge: row[(passes + 1) & 1] is, OUTPUT kept[m])
+  uint64_t row[2];                 // u32[n] each, likewise; row[last] is the e2v of the cloud's streams: OUTPUT perm
+                                   //   (merge: row[last ^ 1] is, OUTPUT kept[m])
   uint64_t hist;                   // u32[ORD_RADIX * tiles]: of the pass under way, digit-major
   uint64_t rank;                   // u32[n] OUTPUT (meshes; else 0): the entry of every row
   uint64_t faces;                  // compressed indices: u16[count] (narrow) or u32[count], remapped in place; else count 0
@@ -174,9 +177,10 @@ struct EncOrder {                  // one per cloud of the chunk; in the arena, 
   uint32_t m, part_cells;          // OUTPUT (merge): occupied cells; part_cells: not 0: the kept points in parts of at most so many (k_enc_part_cells),
   uint32_t part0, part_slots;      //   the cloud's part_slots = ceil(n / part_cells) EncPart records from part0 on, slot p with `streams` stream records
                                    //   from stream0 + p * streams on
-  uint32_t lod_bits, lod_pad;      // lod_base_bits D (0: no levels); not 0: part_slots = ceil(n / part_cells) + bits - D and the two fields below are set
+  uint32_t lod_bits, last;         // lod_base_bits D (0: no levels); not 0: part_slots = ceil(n / part_cells) + bits - D and the two fields below are set
+                                   //   last: the buffer of each pair the last sort pass wrote, passes & 1 (ord_sorted / ord_kept / ord_part_rows below)
   uint64_t lod_rows;               // u32[n] OUTPUT lod[m], the kept rows in (level, kept) order -- the e2v of the cloud's streams -- and behind it u32[n] pos[m],
-                                   //   the place of every kept entry in lod: the key buffer the last sort pass did not write, key[(passes + 1) & 1]
+                                   //   the place of every kept entry in lod: the key buffer the last sort pass did not write, key[last ^ 1]
   uint64_t lod_table;              // EncLodTable OUTPUT: points and first lod entry of every level
 };
 struct EncOrderTile { uint32_t cloud, tile; };
@@ -184,7 +188,7 @@ struct EncPart {                   // one per part of a split cloud, the parts o
   uint32_t cloud;                  // its cloud among the chunk's EncOrder records
   uint32_t lo, n;                  // sorted entries lo .. lo + n of the cloud
   int32_t qmin[3], qmax[3];        // OUTPUT per component over vals of the part's rows (the layout sets INT32_MAX / INT32_MIN)
-  uint32_t pad;                    // OUTPUT (lod_base_bits >= 1): the level of the slot (k_enc_lod_parts); else 0
+  uint32_t pad;                    // OUTPUT (lod_base_bits >= 1): the level of the slot (k_enc_part_cells); else 0
 };
 struct EncPartTile { uint32_t part, tile; };
 #define ORD_LOD_LEVELS 20u         // position_bits is at most 20 (enc_check_bits): L = bits - D + 1 <= 20
@@ -194,6 +198,50 @@ struct EncMean { uint64_t vals, acc; uint32_t nc, pad; };       // one per maske
 struct EncMeanCloud { uint64_t cnt; uint32_t first, count; };   // one per EncOrder record: the rows of every cell u32[n]; its `count` EncMean records from `first` on (0: none)
 
 static inline uint32_t enc_order_passes(uint32_t bits) { return (3u * bits + 7u) / 8u; }
+
+// The buffers behind the sort, named once for the kernels, the layout and the host checks (offsets into the arena):
+struct EncSorted { uint64_t key, row; };
+// the key / row pair the last pass wrote: the sorted keys and perm
+__host__ __device__ __forceinline__ EncSorted ord_sorted(const EncOrder &O) { return EncSorted{O.key[O.last & 1u], O.row[O.last & 1u]}; }
+// merge: kept, in the row buffer the last pass read
+__host__ __device__ __forceinline__ uint64_t ord_kept(const EncOrder &O) { return O.row[(O.last & 1u) ^ 1u]; }
+// the rows the parts of a cloud are runs of: lod with levels, else kept with the merge, else perm
+__host__ __device__ __forceinline__ uint64_t ord_part_rows(const EncOrder &O) { return O.lod_bits ? O.lod_rows : O.merge ? ord_kept(O) : ord_sorted(O).row; }
+
+// Tile T of cloud O over its first `limit` entries (O.n; O.m for tiles over KEPT entries -- never beyond n: the comparison keeps a
+// fault elsewhere inside the cloud's buffers): entries e0 .. end.  False for a tile at or beyond the limit.
+__device__ __forceinline__ bool ord_tile(const EncOrder &O, const EncOrderTile &T, uint32_t limit, uint32_t &e0, uint32_t &end) {
+  if (limit > O.n) limit = O.n;
+  e0 = T.tile * ORD_TILE;
+  if (e0 >= limit) return false;
+  end = limit - e0 < ORD_TILE ? limit : e0 + ORD_TILE;
+  return true;
+}
+// entry e of a cloud's sorted keys begins a cell
+__device__ __forceinline__ bool ord_head(const uint64_t *key, uint32_t e) { return e == 0u || key[e] != key[e - 1u]; }
+// the levels of a cloud, L = bits - D + 1; 0: none (no lod_base_bits, or -- never by the layout -- one the table cannot hold)
+__device__ __forceinline__ uint32_t ord_lod_levels(const EncOrder &O) {
+  return O.lod_bits == 0u || O.lod_bits > O.bits || O.bits - O.lod_bits >= ORD_LOD_LEVELS ? 0u : O.bits - O.lod_bits + 1u;
+}
+#if defined(__HIPCC__)
+// the inclusive sum of x over the lanes of the wave from lane `start` up to this one (start 0: over all lanes below and this one)
+template <class X>
+__device__ __forceinline__ X ord_wave_incl(X x, uint32_t lane, uint32_t start = 0u) {
+  for (uint32_t d = 1; d < (uint32_t)WAVE; d <<= 1) { const X y = __shfl_up(x, d, WAVE); if (lane >= start + d) x += y; }
+  return x;
+}
+// the valid lanes whose low BITS bits of `value` equal this lane's, by BITS ballots
+template <uint32_t BITS>
+__device__ __forceinline__ unsigned long long ord_match(uint32_t value, bool valid) {
+  unsigned long long same = __ballot(valid);
+  for (uint32_t b = 0; b < BITS; ++b) {
+    const bool bit = ((value >> b) & 1u) != 0;
+    const unsigned long long with = __ballot(valid && bit);
+    same &= bit ? with : ~with;
+  }
+  return same;
+}
+#endif
 
 // bit b of the low 21 bits of x to bit 3 b
 __device__ __forceinline__ uint64_t ord_spread(uint32_t v) {
@@ -217,8 +265,9 @@ __global__ __launch_bounds__(256) void k_enc_order_keys(uint8_t *arena, const En
   const int32_t *vals = (const int32_t *)(arena + O.vals);
   uint64_t *key = (uint64_t *)(arena + O.key[0]);
   uint32_t *row = (uint32_t *)(arena + O.row[0]);
-  const uint32_t end = O.n - T.tile * ORD_TILE < ORD_TILE ? O.n : (T.tile + 1u) * ORD_TILE;
-  for (uint32_t r = T.tile * ORD_TILE + threadIdx.x; r < end; r += blockDim.x) { key[r] = ord_key(vals + 3ull * r, O.bits); row[r] = r; }
+  uint32_t e0, end;
+  if (!ord_tile(O, T, O.n, e0, end)) return;
+  for (uint32_t r = e0 + threadIdx.x; r < end; r += blockDim.x) { key[r] = ord_key(vals + 3ull * r, O.bits); row[r] = r; }
 }
 
 __device__ __forceinline__ uint32_t ord_digit(uint64_t key, uint32_t pass) { return (uint32_t)(key >> (8u * pass)) & (ORD_RADIX - 1u); }
@@ -229,7 +278,9 @@ __global__ __launch_bounds__(WAVE) void k_enc_order_hist(uint8_t *arena, const E
   const EncOrder &O = clouds[T.cloud];
   const uint64_t *key = (const uint64_t *)(arena + O.key[pass & 1u]);
   uint32_t *hist = (uint32_t *)(arena + O.hist);
-  const uint32_t lane = threadIdx.x, e0 = T.tile * ORD_TILE, end = O.n - e0 < ORD_TILE ? O.n : e0 + ORD_TILE;
+  uint32_t e0, end;
+  if (!ord_tile(O, T, O.n, e0, end)) return;
+  const uint32_t lane = threadIdx.x;
 #if defined(__HIPCC__)
   __shared__ uint32_t s_count[ORD_RADIX];
   for (uint32_t d = lane; d < ORD_RADIX; d += WAVE) s_count[d] = 0;
@@ -256,8 +307,7 @@ __global__ __launch_bounds__(WAVE) void k_enc_order_scan(uint8_t *arena, const E
     const uint32_t i = i0 + lane * ORD_SCAN_PER;
     uint32_t x[ORD_SCAN_PER], sum = 0;
     for (uint32_t k = 0; k < ORD_SCAN_PER; ++k) { x[k] = i < total ? hist[i + k] : 0u; sum += x[k]; }
-    uint32_t incl = sum;
-    for (int d = 1; d < WAVE; d <<= 1) { const uint32_t y = (uint32_t)__shfl_up((int)incl, d, WAVE); if ((int)lane >= d) incl += y; }
+    const uint32_t incl = ord_wave_incl(sum, lane);
     uint32_t at = base + incl - sum;
     if (i < total) for (uint32_t k = 0; k < ORD_SCAN_PER; ++k) { hist[i + k] = at; at += x[k]; }
     base += (uint32_t)__shfl((int)incl, WAVE - 1, WAVE);
@@ -277,7 +327,9 @@ __global__ __launch_bounds__(WAVE) void k_enc_order_scatter(uint8_t *arena, cons
   uint64_t *key_out = (uint64_t *)(arena + O.key[(pass + 1u) & 1u]);
   uint32_t *row_out = (uint32_t *)(arena + O.row[(pass + 1u) & 1u]);
   const uint32_t *hist = (const uint32_t *)(arena + O.hist);
-  const uint32_t lane = threadIdx.x, e0 = T.tile * ORD_TILE, end = O.n - e0 < ORD_TILE ? O.n : e0 + ORD_TILE;
+  uint32_t e0, end;
+  if (!ord_tile(O, T, O.n, e0, end)) return;
+  const uint32_t lane = threadIdx.x;
 #if defined(__HIPCC__)
   __shared__ uint32_t s_next[ORD_RADIX];                       // where the tile's next entry of every digit goes
   for (uint32_t d = lane; d < ORD_RADIX; d += WAVE) s_next[d] = hist[(size_t)d * O.tiles + T.tile];
@@ -288,12 +340,7 @@ __global__ __launch_bounds__(WAVE) void k_enc_order_scatter(uint8_t *arena, cons
     const bool valid = e < end;
     const uint64_t k = valid ? key[e] : 0ull;
     const uint32_t r = valid ? row[e] : 0u, d = ord_digit(k, pass);
-    unsigned long long same = __ballot(valid);                 // the lanes of this lane's digit
-    for (uint32_t b = 0; b < 8u; ++b) {
-      const bool bit = ((d >> b) & 1u) != 0;
-      const unsigned long long with = __ballot(valid && bit);
-      same &= bit ? with : ~with;
-    }
+    const unsigned long long same = ord_match<8>(d, valid);    // the lanes of this lane's digit
     const uint32_t at = valid ? s_next[d] : 0u;
     __syncthreads();                                           // (every lane has read before a digit's lowest lane advances its count)
     if (valid && (same & below) == 0ull) s_next[d] = at + (uint32_t)__popcll(same);
@@ -309,15 +356,15 @@ __global__ __launch_bounds__(WAVE) void k_enc_order_scatter(uint8_t *arena, cons
 #endif
 }
 
-__global__ __launch_bounds__(256) void k_enc_order_rank(uint8_t *arena, const EncOrder *clouds, const EncOrderTile *tiles, uint32_t nt, uint32_t passes) {
+__global__ __launch_bounds__(256) void k_enc_order_rank(uint8_t *arena, const EncOrder *clouds, const EncOrderTile *tiles, uint32_t nt) {
   if (blockIdx.x >= nt) return;
   const EncOrderTile T = tiles[blockIdx.x];
   const EncOrder &O = clouds[T.cloud];
-  if (O.rank == 0) return;
-  const uint32_t *perm = (const uint32_t *)(arena + O.row[passes & 1u]);
+  uint32_t e0, end;
+  if (O.rank == 0 || !ord_tile(O, T, O.n, e0, end)) return;
+  const uint32_t *perm = (const uint32_t *)(arena + ord_sorted(O).row);
   uint32_t *rank = (uint32_t *)(arena + O.rank);
-  const uint32_t end = O.n - T.tile * ORD_TILE < ORD_TILE ? O.n : (T.tile + 1u) * ORD_TILE;
-  for (uint32_t e = T.tile * ORD_TILE + threadIdx.x; e < end; e += blockDim.x) { const uint32_t r = perm[e]; if (r < O.n) rank[r] = e; }
+  for (uint32_t e = e0 + threadIdx.x; e < end; e += blockDim.x) { const uint32_t r = perm[e]; if (r < O.n) rank[r] = e; }
 }
 
 // grid (blocks over corners, clouds); indices out of range never come here: the host refuses such a mesh before the launch
@@ -336,44 +383,27 @@ __global__ __launch_bounds__(256) void k_enc_order_faces(uint8_t *arena, const E
   }
 }
 
-// The steps over `nc` clouds and their `nt` tiles: launch(kernel, grid x, grid y, block, arguments...) is hipLaunchKernelGGL on the
-// lane's stream in enc_stage_attributes and the thread-by-thread loop in the host check.  gx_faces: blocks over the corners of the
-// chunk's largest mesh with compressed indices (0: no mesh has any); any_rank: the chunk codes meshes.
-template <class Launch>
-static inline void enc_order_launch(Launch &&launch, uint8_t *arena, const EncOrder *clouds, uint32_t nc, const EncOrderTile *tiles, uint32_t nt,
-                                    uint32_t passes, bool any_rank, uint32_t gx_faces) {
-  if (nc == 0 || nt == 0) return;
-  launch(k_enc_order_keys, nt, 1u, 256u, arena, clouds, tiles, nt);
-  for (uint32_t p = 0; p < passes; ++p) {
-    launch(k_enc_order_hist, nt, 1u, (uint32_t)WAVE, arena, clouds, tiles, nt, p);
-    launch(k_enc_order_scan, nc, 1u, (uint32_t)WAVE, arena, clouds, nc);
-    launch(k_enc_order_scatter, nt, 1u, (uint32_t)WAVE, arena, clouds, tiles, nt, p);
-  }
-  if (any_rank) launch(k_enc_order_rank, nt, 1u, 256u, arena, clouds, tiles, nt, passes);
-  if (any_rank && gx_faces) launch(k_enc_order_faces, gx_faces, nc, 256u, arena, clouds, nc);
-}
-
 // ---- merge_points (the header comment has the contract)
-__global__ __launch_bounds__(WAVE) void k_enc_merge_heads(uint8_t *arena, const EncOrder *clouds, const EncOrderTile *tiles, uint32_t nt, uint32_t passes) {
+__global__ __launch_bounds__(WAVE) void k_enc_merge_heads(uint8_t *arena, const EncOrder *clouds, const EncOrderTile *tiles, uint32_t nt) {
   if (blockIdx.x >= nt) return;
   const EncOrderTile T = tiles[blockIdx.x];
   const EncOrder &O = clouds[T.cloud];
-  if (!O.merge) return;
-  const uint64_t *key = (const uint64_t *)(arena + O.key[passes & 1u]);
+  uint32_t e0, end;
+  if (!O.merge || !ord_tile(O, T, O.n, e0, end)) return;
+  const uint64_t *key = (const uint64_t *)(arena + ord_sorted(O).key);
   uint32_t *counts = (uint32_t *)(arena + O.hist);
-  const uint32_t lane = threadIdx.x, e0 = T.tile * ORD_TILE, end = O.n - e0 < ORD_TILE ? O.n : e0 + ORD_TILE;
+  const uint32_t lane = threadIdx.x;
   uint32_t heads = 0;
 #if defined(__HIPCC__)
   for (uint32_t s0 = e0; s0 < end; s0 += WAVE) {               // (uniform: every lane takes every step)
     const uint32_t e = s0 + lane;
-    const bool valid = e < end;
-    const bool head = valid && (e == 0u || key[e] != key[e - 1u]);
+    const bool head = e < end && ord_head(key, e);
     heads += (uint32_t)__popcll(__ballot(head));
   }
   if (lane == 0) counts[T.tile] = heads;
 #else       // (as k_enc_order_hist: lane 0 counts)
   if (lane != 0) return;
-  for (uint32_t e = e0; e < end; ++e) heads += e == 0u || key[e] != key[e - 1u] ? 1u : 0u;
+  for (uint32_t e = e0; e < end; ++e) heads += ord_head(key, e) ? 1u : 0u;
   counts[T.tile] = heads;
 #endif
 }
@@ -389,9 +419,7 @@ __global__ __launch_bounds__(WAVE) void k_enc_merge_scan(uint8_t *arena, EncOrde
   uint32_t base = 0;
 #if defined(__HIPCC__)
   for (uint32_t t0 = 0; t0 < O.tiles; t0 += WAVE) {
-    const uint32_t t = t0 + lane, x = t < O.tiles ? counts[t] : 0u;
-    uint32_t incl = x;
-    for (int d = 1; d < WAVE; d <<= 1) { const uint32_t y = (uint32_t)__shfl_up((int)incl, d, WAVE); if ((int)lane >= d) incl += y; }
+    const uint32_t t = t0 + lane, x = t < O.tiles ? counts[t] : 0u, incl = ord_wave_incl(x, lane);
     if (t < O.tiles) counts[t] = base + incl - x;
     base += (uint32_t)__shfl((int)incl, WAVE - 1, WAVE);
   }
@@ -407,23 +435,24 @@ __global__ __launch_bounds__(WAVE) void k_enc_merge_scan(uint8_t *arena, EncOrde
 #endif
 }
 
-__global__ __launch_bounds__(WAVE) void k_enc_merge_compact(uint8_t *arena, const EncOrder *clouds, const EncOrderTile *tiles, uint32_t nt, uint32_t passes) {
+__global__ __launch_bounds__(WAVE) void k_enc_merge_compact(uint8_t *arena, const EncOrder *clouds, const EncOrderTile *tiles, uint32_t nt) {
   if (blockIdx.x >= nt) return;
   const EncOrderTile T = tiles[blockIdx.x];
   const EncOrder &O = clouds[T.cloud];
-  if (!O.merge) return;
-  const uint64_t *key = (const uint64_t *)(arena + O.key[passes & 1u]);
-  const uint32_t *row = (const uint32_t *)(arena + O.row[passes & 1u]);
-  uint32_t *kept = (uint32_t *)(arena + O.row[(passes + 1u) & 1u]);
+  uint32_t e0, end;
+  if (!O.merge || !ord_tile(O, T, O.n, e0, end)) return;
+  const uint64_t *key = (const uint64_t *)(arena + ord_sorted(O).key);
+  const uint32_t *row = (const uint32_t *)(arena + ord_sorted(O).row);
+  uint32_t *kept = (uint32_t *)(arena + ord_kept(O));
   uint32_t *cells = (uint32_t *)(arena + O.cells);
-  const uint32_t lane = threadIdx.x, e0 = T.tile * ORD_TILE, end = O.n - e0 < ORD_TILE ? O.n : e0 + ORD_TILE;
+  const uint32_t lane = threadIdx.x;
   uint32_t next = ((const uint32_t *)(arena + O.hist))[T.tile];       // the heads in front of the tile, then of the step
 #if defined(__HIPCC__)
   const unsigned long long below = (1ull << lane) - 1ull;
   for (uint32_t s0 = e0; s0 < end; s0 += WAVE) {               // (uniform: every lane takes every step)
     const uint32_t e = s0 + lane;
     const bool valid = e < end;
-    const bool head = valid && (e == 0u || key[e] != key[e - 1u]);
+    const bool head = valid && ord_head(key, e);
     const unsigned long long heads = __ballot(head);
     const uint32_t at = next + (uint32_t)__popcll(heads & below);       // heads in front of this entry
     const uint32_t r = valid ? row[e] : 0u;
@@ -435,24 +464,13 @@ __global__ __launch_bounds__(WAVE) void k_enc_merge_compact(uint8_t *arena, cons
 #else       // (as k_enc_order_hist: lane 0 places the tile's entries in their order)
   if (lane != 0) return;
   for (uint32_t e = e0; e < end; ++e) {
-    const bool head = e == 0u || key[e] != key[e - 1u];
-    if (head) kept[next++] = row[e];
+    if (ord_head(key, e)) kept[next++] = row[e];
     cells[row[e]] = next - 1u;
   }
 #endif
 }
 
-// The merge behind enc_order_launch, on the same lists; `streams` the chunk's ns EncStream records on the device.
-template <class Launch, class Stream>
-static inline void enc_merge_launch(Launch &&launch, uint8_t *arena, EncOrder *clouds, uint32_t nc, const EncOrderTile *tiles, uint32_t nt, uint32_t passes,
-                                    Stream *streams, uint32_t ns) {
-  if (nc == 0 || nt == 0) return;
-  launch(k_enc_merge_heads, nt, 1u, (uint32_t)WAVE, arena, (const EncOrder *)clouds, tiles, nt, passes);
-  launch(k_enc_merge_scan<Stream>, nc, 1u, (uint32_t)WAVE, arena, clouds, nc, streams, ns);
-  launch(k_enc_merge_compact, nt, 1u, (uint32_t)WAVE, arena, (const EncOrder *)clouds, tiles, nt, passes);
-}
-
-// ---- mean_attributes (the header comment has the contract): behind enc_merge_launch, in front of everything that reads `vals`
+// ---- mean_attributes (the header comment has the contract): behind the merge, in front of everything that reads `vals`
 // floor((2 S + cnt) / (2 cnt)) in 64 bits: the exact mean of cnt >= 1 integers whose sum is S, ties toward +infinity
 // (|S| <= 2^28 rows of 2^31: 2 S + cnt fits)
 __device__ __forceinline__ int32_t ord_mean(int64_t sum, uint32_t cnt) {
@@ -463,29 +481,30 @@ __device__ __forceinline__ int32_t ord_mean(int64_t sum, uint32_t cnt) {
 }
 
 // grid = (the chunk's (cloud, tile) pairs, the most masked streams a cloud has): one wave per (tile, masked stream)
-__global__ __launch_bounds__(WAVE) void k_enc_mean_sum(uint8_t *arena, const EncOrder *clouds, const EncOrderTile *tiles, uint32_t nt, uint32_t passes,
+__global__ __launch_bounds__(WAVE) void k_enc_mean_sum(uint8_t *arena, const EncOrder *clouds, const EncOrderTile *tiles, uint32_t nt,
                                                        const EncMeanCloud *mclouds, const EncMean *means, uint32_t nm) {
   if (blockIdx.x >= nt) return;
   const EncOrderTile T = tiles[blockIdx.x];
   const EncOrder &O = clouds[T.cloud];
   const EncMeanCloud C = mclouds[T.cloud];
-  if (!O.merge || blockIdx.y >= C.count || C.first + blockIdx.y >= nm) return;
+  uint32_t e0, end;
+  if (!O.merge || blockIdx.y >= C.count || C.first + blockIdx.y >= nm || !ord_tile(O, T, O.n, e0, end)) return;
   const EncMean M = means[C.first + blockIdx.y];
   if (M.nc == 0u || M.nc > 4u) return;                         // (never by the layout)
-  const uint32_t *row = (const uint32_t *)(arena + O.row[passes & 1u]);
+  const uint32_t *row = (const uint32_t *)(arena + ord_sorted(O).row);
   const uint32_t *cells = (const uint32_t *)(arena + O.cells);
   const int32_t *vals = (const int32_t *)(arena + M.vals);
   unsigned long long *acc = (unsigned long long *)(arena + M.acc);       // (two's complement: the sums are signed)
   uint32_t *cnt = (uint32_t *)(arena + C.cnt);
   const bool counts = blockIdx.y == 0u;                        // the cloud's first masked stream counts the rows of every cell
-  const uint32_t lane = threadIdx.x, nc = M.nc, e0 = T.tile * ORD_TILE, end = O.n - e0 < ORD_TILE ? O.n : e0 + ORD_TILE;
+  const uint32_t lane = threadIdx.x, nc = M.nc;
 #if defined(__HIPCC__)
-  const uint64_t *key = (const uint64_t *)(arena + O.key[passes & 1u]);
+  const uint64_t *key = (const uint64_t *)(arena + ord_sorted(O).key);
   const unsigned long long upto = (2ull << lane) - 1ull;       // the lanes at or below this one
   for (uint32_t s0 = e0; s0 < end; s0 += WAVE) {               // (uniform: every lane takes every step)
     const uint32_t e = s0 + lane;
     const bool valid = e < end;
-    const bool head = valid && (e == 0u || key[e] != key[e - 1u]);
+    const bool head = valid && ord_head(key, e);
     const unsigned long long heads = __ballot(head), live = __ballot(valid);
     // the lane this lane's run begins at inside the step: the head at or below it, lane 0 for a run that came in from the step in front
     const unsigned long long mine = heads & upto;
@@ -497,8 +516,7 @@ __global__ __launch_bounds__(WAVE) void k_enc_mean_sum(uint8_t *arena, const Enc
     const bool ok = valid && r < O.n;
     const uint32_t j = ok ? cells[r] : 0xFFFFFFFFu;
     for (uint32_t c = 0; c < nc; ++c) {                        // (uniform)
-      long long x = ok ? (long long)vals[(size_t)nc * r + c] : 0ll;
-      for (uint32_t d = 1; d < (uint32_t)WAVE; d <<= 1) { const long long y = __shfl_up(x, d, WAVE); if (lane >= start + d) x += y; }
+      const long long x = ord_wave_incl(ok ? (long long)vals[(size_t)nc * r + c] : 0ll, lane, start);       // (a lane adds what lies d below only while that is inside its run)
       if (last && j < O.n) atomicAdd(&acc[(size_t)nc * j + c], (unsigned long long)x);
     }
     if (counts && last && j < O.n) atomicAdd(&cnt[j], lane - start + 1u);
@@ -514,19 +532,18 @@ __global__ __launch_bounds__(WAVE) void k_enc_mean_sum(uint8_t *arena, const Enc
 }
 
 // grid as above, tiles over KEPT entries: a thread per (kept entry, component).  No lane needs another: the host check runs it as it stands.
-__global__ __launch_bounds__(256) void k_enc_mean_store(uint8_t *arena, const EncOrder *clouds, const EncOrderTile *tiles, uint32_t nt, uint32_t passes,
+__global__ __launch_bounds__(256) void k_enc_mean_store(uint8_t *arena, const EncOrder *clouds, const EncOrderTile *tiles, uint32_t nt,
                                                         const EncMeanCloud *mclouds, const EncMean *means, uint32_t nm) {
   if (blockIdx.x >= nt) return;
   const EncOrderTile T = tiles[blockIdx.x];
   const EncOrder &O = clouds[T.cloud];
   const EncMeanCloud C = mclouds[T.cloud];
-  if (!O.merge || blockIdx.y >= C.count || C.first + blockIdx.y >= nm) return;
+  uint32_t e0, end;
+  if (!O.merge || blockIdx.y >= C.count || C.first + blockIdx.y >= nm || !ord_tile(O, T, O.m, e0, end)) return;
   const EncMean M = means[C.first + blockIdx.y];
   if (M.nc == 0u || M.nc > 4u) return;                         // (never by the layout)
-  const uint32_t m = O.m < O.n ? O.m : O.n, e0 = T.tile * ORD_TILE;
-  if (e0 >= m) return;
-  const uint32_t nc = M.nc, total = (m - e0 < ORD_TILE ? m - e0 : ORD_TILE) * nc;
-  const uint32_t *kept = (const uint32_t *)(arena + O.row[(passes + 1u) & 1u]);
+  const uint32_t nc = M.nc, total = (end - e0) * nc;
+  const uint32_t *kept = (const uint32_t *)(arena + ord_kept(O));
   const long long *acc = (const long long *)(arena + M.acc);
   const uint32_t *cnt = (const uint32_t *)(arena + C.cnt);
   int32_t *vals = (int32_t *)(arena + M.vals);
@@ -537,41 +554,34 @@ __global__ __launch_bounds__(256) void k_enc_mean_store(uint8_t *arena, const En
   }
 }
 
-// The means behind enc_merge_launch, on its lists: `mclouds` one record per cloud, `means` the chunk's nm masked streams, gy the most
-// a cloud has.  The accumulators and counts are zero when this is called (one memset on the stream in the product).
-template <class Launch>
-static inline void enc_mean_launch(Launch &&launch, uint8_t *arena, const EncOrder *clouds, uint32_t nc, const EncOrderTile *tiles, uint32_t nt, uint32_t passes,
-                                   const EncMeanCloud *mclouds, const EncMean *means, uint32_t nm, uint32_t gy) {
-  if (nc == 0 || nt == 0 || nm == 0 || gy == 0) return;
-  launch(k_enc_mean_sum, nt, gy, (uint32_t)WAVE, arena, clouds, tiles, nt, passes, mclouds, means, nm);
-  launch(k_enc_mean_store, nt, gy, 256u, arena, clouds, tiles, nt, passes, mclouds, means, nm);
-}
-
-// ---- part_cells (the header comment has the contract): a thread per part slot of the chunk, behind k_enc_merge_scan
+// ---- part_cells (the header comment has the contract): a thread per part slot of the chunk, behind k_enc_merge_scan and, for a
+// cloud with levels, behind k_enc_lod_scan and k_enc_lod_scatter.  The parts of level 0, then of level 1, ...: a cloud without
+// levels is one level of its m kept entries from 0 on (it has no table region: none is read for it).
 template <class Stream>
-__global__ __launch_bounds__(WAVE) void k_enc_part_cells(EncOrder *clouds, uint32_t nc, EncPart *parts, uint32_t np, Stream *streams, uint32_t ns, uint32_t passes) {
+__global__ __launch_bounds__(WAVE) void k_enc_part_cells(uint8_t *arena, const EncOrder *clouds, uint32_t nc, EncPart *parts, uint32_t np, Stream *streams, uint32_t ns) {
   const uint32_t i = blockIdx.x * WAVE + threadIdx.x;
   if (i >= np) return;
   EncPart &P = parts[i];
   if (P.cloud >= nc) return;
   const EncOrder &O = clouds[P.cloud];
-  if (O.part_cells == 0u || i < O.part0 || i - O.part0 >= O.part_slots) return;       // (never by the layout)
-  const uint64_t p = i - O.part0, m = O.m < O.n ? O.m : O.n, live = (m + O.part_cells - 1u) / O.part_cells;
-  uint32_t lo = 0, cnt = 0;
-  if (p < live) { lo = (uint32_t)(p * m / live); cnt = (uint32_t)((p + 1u) * m / live) - lo; }      // (64 bits: p m < 2^16 2^28)
-  P.lo = lo; P.n = cnt;
-  const uint64_t kept = O.row[(passes + 1u) & 1u] + 4ull * lo, s0 = (uint64_t)O.stream0 + p * O.streams;
-  for (uint32_t k = 0; k < O.streams; ++k) if (s0 + k < ns) { Stream &S = streams[s0 + k]; S.nv = cnt; S.e2v = kept; if (cnt == 0u) S.kind = 3u; }      // (empty: an empty list, which every step passes by)
+  const uint32_t levels = O.lod_bits ? ord_lod_levels(O) : 1u;
+  if (levels == 0u || O.part_cells == 0u || i < O.part0 || i - O.part0 >= O.part_slots) return;       // (never by the layout)
+  const EncLodTable *table = O.lod_bits ? (const EncLodTable *)(arena + O.lod_table) : nullptr;
+  const uint32_t m = O.m < O.n ? O.m : O.n;
+  uint64_t p = i - O.part0;
+  uint32_t lo = 0, cnt = 0, level = 0;
+  for (uint32_t l = 0; l < levels; ++l) {
+    const uint64_t ml = table ? table->count[l] : m, live = (ml + O.part_cells - 1u) / O.part_cells;
+    if (p < live) { lo = (table ? table->base[l] : 0u) + (uint32_t)(p * ml / live); cnt = (uint32_t)((p + 1u) * ml / live) - (uint32_t)(p * ml / live); level = l; break; }      // (64 bits: p m < 2^16 2^28)
+    p -= live;
+  }
+  if (lo > O.n || cnt > O.n - lo) { lo = 0; cnt = 0; level = 0; }      // (never by the scan: the comparison keeps a fault elsewhere inside the cloud's buffers)
+  P.lo = lo; P.n = cnt; P.pad = level;
+  const uint64_t rows = ord_part_rows(O) + 4ull * lo, s0 = (uint64_t)O.stream0 + (uint64_t)(i - O.part0) * O.streams;
+  for (uint32_t k = 0; k < O.streams; ++k) if (s0 + k < ns) { Stream &S = streams[s0 + k]; S.nv = cnt; S.e2v = rows; if (cnt == 0u) S.kind = 3u; }      // (empty: an empty list, which every step passes by)
 }
 
-// The part sizes behind enc_merge_launch and in front of enc_part_launch: `parts` the chunk's np EncPart records (slots).
-template <class Launch, class Stream>
-static inline void enc_part_cells_launch(Launch &&launch, EncOrder *clouds, uint32_t nc, EncPart *parts, uint32_t np, Stream *streams, uint32_t ns, uint32_t passes) {
-  if (nc == 0 || np == 0) return;
-  launch(k_enc_part_cells<Stream>, (np + (uint32_t)WAVE - 1u) / (uint32_t)WAVE, 1u, (uint32_t)WAVE, clouds, nc, parts, np, streams, ns, passes);
-}
-
-// ---- lod_base_bits (the header comment has the contract): behind enc_merge_launch, in place of enc_part_cells_launch
+// ---- lod_base_bits (the header comment has the contract): behind the merge, in front of k_enc_part_cells
 // The level of a kept point from its key and the key of the kept point in front of it: c leading bit-triples in common out of
 // `bits`, level max(0, c + 1 - D).  (Equal keys never come here, the kept keys are distinct: the comparison keeps the level below L.)
 __device__ __forceinline__ uint32_t ord_lod_level(uint64_t a, uint64_t b, uint32_t bits, uint32_t base_bits) {
@@ -587,16 +597,15 @@ __device__ __forceinline__ uint32_t ord_lod_level(uint64_t a, uint64_t b, uint32
 }
 
 // grid = the chunk's (cloud, tile) pairs, tiles over KEPT entries
-__global__ __launch_bounds__(WAVE) void k_enc_lod_levels(uint8_t *arena, const EncOrder *clouds, const EncOrderTile *tiles, uint32_t nt, uint32_t passes) {
+__global__ __launch_bounds__(WAVE) void k_enc_lod_levels(uint8_t *arena, const EncOrder *clouds, const EncOrderTile *tiles, uint32_t nt) {
   if (blockIdx.x >= nt) return;
   const EncOrderTile T = tiles[blockIdx.x];
   const EncOrder &O = clouds[T.cloud];
-  if (O.lod_bits == 0u || O.lod_bits > O.bits || O.bits - O.lod_bits >= ORD_LOD_LEVELS) return;
-  const uint32_t m = O.m < O.n ? O.m : O.n, e0 = T.tile * ORD_TILE;
-  if (e0 >= m) return;
-  const uint32_t lane = threadIdx.x, end = m - e0 < ORD_TILE ? m : e0 + ORD_TILE, levels = O.bits - O.lod_bits + 1u;
+  const uint32_t lane = threadIdx.x, levels = ord_lod_levels(O);
+  uint32_t e0, end;
+  if (levels == 0u || !ord_tile(O, T, O.m, e0, end)) return;
   const int32_t *vals = (const int32_t *)(arena + O.vals);
-  const uint32_t *kept = (const uint32_t *)(arena + O.row[(passes + 1u) & 1u]);
+  const uint32_t *kept = (const uint32_t *)(arena + ord_kept(O));
   uint32_t *pos = (uint32_t *)(arena + O.lod_rows) + O.n;       // (the level of every kept entry until k_enc_lod_scatter puts its place there)
   uint32_t *hist = (uint32_t *)(arena + O.hist);
 #if defined(__HIPCC__)
@@ -631,8 +640,9 @@ __global__ __launch_bounds__(WAVE) void k_enc_lod_levels(uint8_t *arena, const E
 __global__ __launch_bounds__(WAVE) void k_enc_lod_scan(uint8_t *arena, const EncOrder *clouds, uint32_t nc) {
   if (blockIdx.x >= nc) return;
   const EncOrder &O = clouds[blockIdx.x];
-  if (O.lod_bits == 0u || O.lod_bits > O.bits || O.bits - O.lod_bits >= ORD_LOD_LEVELS) return;
-  const uint32_t m = O.m < O.n ? O.m : O.n, live = (m + ORD_TILE - 1u) / ORD_TILE, levels = O.bits - O.lod_bits + 1u;
+  const uint32_t levels = ord_lod_levels(O);
+  if (levels == 0u) return;
+  const uint32_t m = O.m < O.n ? O.m : O.n, live = (m + ORD_TILE - 1u) / ORD_TILE;
   const uint32_t total = levels * live, lane = threadIdx.x;     // (live <= 2^18, levels <= 20)
   uint32_t *hist = (uint32_t *)(arena + O.hist);
   EncLodTable &table = *(EncLodTable *)(arena + O.lod_table);
@@ -641,9 +651,7 @@ __global__ __launch_bounds__(WAVE) void k_enc_lod_scan(uint8_t *arena, const Enc
   for (uint32_t i0 = 0; i0 < total; i0 += WAVE) {
     const uint32_t i = i0 + lane, l = i < total ? i / live : 0u;
     const size_t at = (size_t)l * O.tiles + (i - l * live);
-    const uint32_t x = i < total ? hist[at] : 0u;
-    uint32_t incl = x;
-    for (int d = 1; d < WAVE; d <<= 1) { const uint32_t y = (uint32_t)__shfl_up((int)incl, d, WAVE); if ((int)lane >= d) incl += y; }
+    const uint32_t x = i < total ? hist[at] : 0u, incl = ord_wave_incl(x, lane);
     if (i < total) hist[at] = base + incl - x;
     base += (uint32_t)__shfl((int)incl, WAVE - 1, WAVE);
   }
@@ -664,15 +672,14 @@ __global__ __launch_bounds__(WAVE) void k_enc_lod_scan(uint8_t *arena, const Enc
 #endif
 }
 
-__global__ __launch_bounds__(WAVE) void k_enc_lod_scatter(uint8_t *arena, const EncOrder *clouds, const EncOrderTile *tiles, uint32_t nt, uint32_t passes) {
+__global__ __launch_bounds__(WAVE) void k_enc_lod_scatter(uint8_t *arena, const EncOrder *clouds, const EncOrderTile *tiles, uint32_t nt) {
   if (blockIdx.x >= nt) return;
   const EncOrderTile T = tiles[blockIdx.x];
   const EncOrder &O = clouds[T.cloud];
-  if (O.lod_bits == 0u || O.lod_bits > O.bits || O.bits - O.lod_bits >= ORD_LOD_LEVELS) return;
-  const uint32_t m = O.m < O.n ? O.m : O.n, e0 = T.tile * ORD_TILE;
-  if (e0 >= m) return;
-  const uint32_t lane = threadIdx.x, end = m - e0 < ORD_TILE ? m : e0 + ORD_TILE, levels = O.bits - O.lod_bits + 1u;
-  const uint32_t *kept = (const uint32_t *)(arena + O.row[(passes + 1u) & 1u]);
+  const uint32_t lane = threadIdx.x, levels = ord_lod_levels(O);
+  uint32_t e0, end;
+  if (levels == 0u || !ord_tile(O, T, O.m, e0, end)) return;
+  const uint32_t *kept = (const uint32_t *)(arena + ord_kept(O));
   uint32_t *lod = (uint32_t *)(arena + O.lod_rows), *pos = lod + O.n;
   const uint32_t *hist = (const uint32_t *)(arena + O.hist);
 #if defined(__HIPCC__)
@@ -684,12 +691,7 @@ __global__ __launch_bounds__(WAVE) void k_enc_lod_scatter(uint8_t *arena, const 
     const uint32_t j = s0 + lane;
     const bool valid = j < end;
     const uint32_t r = valid ? kept[j] : 0u, seen = valid ? pos[j] : 0u, level = seen < levels ? seen : levels - 1u;
-    unsigned long long same = __ballot(valid);                 // the lanes of this lane's level
-    for (uint32_t b = 0; b < 5u; ++b) {
-      const bool bit = ((level >> b) & 1u) != 0;
-      const unsigned long long with = __ballot(valid && bit);
-      same &= bit ? with : ~with;
-    }
+    const unsigned long long same = ord_match<5>(level, valid);       // the lanes of this lane's level
     const uint32_t at = valid ? s_next[level] : 0u;
     __syncthreads();                                           // (every lane has read before a level's lowest lane advances its count)
     if (valid && (same & below) == 0ull) s_next[level] = at + (uint32_t)__popcll(same);
@@ -710,53 +712,16 @@ __global__ __launch_bounds__(256) void k_enc_lod_cells(uint8_t *arena, const Enc
   if (blockIdx.x >= nt) return;
   const EncOrderTile T = tiles[blockIdx.x];
   const EncOrder &O = clouds[T.cloud];
-  if (O.lod_bits == 0u || O.cells == 0) return;
+  uint32_t e0, end;
+  if (O.lod_bits == 0u || O.cells == 0 || !ord_tile(O, T, O.n, e0, end)) return;
   const uint32_t m = O.m < O.n ? O.m : O.n;
   uint32_t *cells = (uint32_t *)(arena + O.cells);
   const uint32_t *pos = (const uint32_t *)(arena + O.lod_rows) + O.n;
-  const uint32_t end = O.n - T.tile * ORD_TILE < ORD_TILE ? O.n : (T.tile + 1u) * ORD_TILE;
-  for (uint32_t r = T.tile * ORD_TILE + threadIdx.x; r < end; r += blockDim.x) { const uint32_t j = cells[r]; if (j < m) cells[r] = pos[j]; }
-}
-
-// a thread per part slot of the chunk: k_enc_part_cells with a level table
-template <class Stream>
-__global__ __launch_bounds__(WAVE) void k_enc_lod_parts(uint8_t *arena, const EncOrder *clouds, uint32_t nc, EncPart *parts, uint32_t np, Stream *streams, uint32_t ns) {
-  const uint32_t i = blockIdx.x * WAVE + threadIdx.x;
-  if (i >= np) return;
-  EncPart &P = parts[i];
-  if (P.cloud >= nc) return;
-  const EncOrder &O = clouds[P.cloud];
-  if (O.lod_bits == 0u || O.lod_bits > O.bits || O.bits - O.lod_bits >= ORD_LOD_LEVELS || O.part_cells == 0u || i < O.part0 || i - O.part0 >= O.part_slots) return;       // (never by the layout)
-  const EncLodTable &table = *(const EncLodTable *)(arena + O.lod_table);
-  const uint32_t levels = O.bits - O.lod_bits + 1u;
-  uint64_t p = i - O.part0;
-  uint32_t lo = 0, cnt = 0, level = 0;
-  for (uint32_t l = 0; l < levels; ++l) {
-    const uint64_t ml = table.count[l], live = (ml + O.part_cells - 1u) / O.part_cells;
-    if (p < live) { lo = table.base[l] + (uint32_t)(p * ml / live); cnt = (uint32_t)((p + 1u) * ml / live) - (uint32_t)(p * ml / live); level = l; break; }      // (64 bits: p m < 2^16 2^28)
-    p -= live;
-  }
-  if (lo > O.n || cnt > O.n - lo) { lo = 0; cnt = 0; level = 0; }      // (never by the scan: the comparison keeps a fault elsewhere inside the cloud's buffers)
-  P.lo = lo; P.n = cnt; P.pad = level;
-  const uint64_t rows = O.lod_rows + 4ull * lo, s0 = (uint64_t)O.stream0 + (uint64_t)(i - O.part0) * O.streams;
-  for (uint32_t k = 0; k < O.streams; ++k) if (s0 + k < ns) { Stream &S = streams[s0 + k]; S.nv = cnt; S.e2v = rows; if (cnt == 0u) S.kind = 3u; }      // (empty: an empty list, which every step passes by)
-}
-
-// The levels behind enc_merge_launch and in front of enc_part_launch, on the merge's lists and the chunk's np EncPart records (slots).
-template <class Launch, class Stream>
-static inline void enc_lod_launch(Launch &&launch, uint8_t *arena, const EncOrder *clouds, uint32_t nc, const EncOrderTile *tiles, uint32_t nt, uint32_t passes,
-                                  EncPart *parts, uint32_t np, Stream *streams, uint32_t ns) {
-  if (nc == 0 || nt == 0 || np == 0) return;
-  launch(k_enc_lod_levels, nt, 1u, (uint32_t)WAVE, arena, clouds, tiles, nt, passes);
-  launch(k_enc_lod_scan, nc, 1u, (uint32_t)WAVE, arena, clouds, nc);
-  launch(k_enc_lod_scatter, nt, 1u, (uint32_t)WAVE, arena, clouds, tiles, nt, passes);
-  launch(k_enc_lod_cells, nt, 1u, 256u, arena, clouds, tiles, nt);
-  launch(k_enc_lod_parts<Stream>, (np + (uint32_t)WAVE - 1u) / (uint32_t)WAVE, 1u, (uint32_t)WAVE, arena, clouds, nc, parts, np, streams, ns);
+  for (uint32_t r = e0 + threadIdx.x; r < end; r += blockDim.x) { const uint32_t j = cells[r]; if (j < m) cells[r] = pos[j]; }
 }
 
 // ---- part_points (the header comment has the contract): grid = the chunk's (part, tile) pairs, one wave each
-__global__ __launch_bounds__(WAVE) void k_enc_part_bounds(uint8_t *arena, const EncOrder *clouds, uint32_t nc, EncPart *parts, uint32_t np, const EncPartTile *tiles, uint32_t nt,
-                                                          uint32_t passes) {
+__global__ __launch_bounds__(WAVE) void k_enc_part_bounds(uint8_t *arena, const EncOrder *clouds, uint32_t nc, EncPart *parts, uint32_t np, const EncPartTile *tiles, uint32_t nt) {
   if (blockIdx.x >= nt) return;
   const EncPartTile T = tiles[blockIdx.x];
   if (T.part >= np) return;
@@ -767,7 +732,7 @@ __global__ __launch_bounds__(WAVE) void k_enc_part_bounds(uint8_t *arena, const 
   if (t0 >= P.n || P.lo > O.n || P.n > O.n - P.lo) return;       // (never by the layout: the comparisons keep a fault elsewhere inside the cloud's buffers)
   const int32_t *vals = (const int32_t *)(arena + O.vals);
   // (merge: the parts are runs of the kept rows; lod_bits: of the kept rows in (level, kept) order)
-  const uint32_t *row = (const uint32_t *)(arena + (O.lod_bits ? O.lod_rows : O.row[(passes + (O.merge ? 1u : 0u)) & 1u]));
+  const uint32_t *row = (const uint32_t *)(arena + ord_part_rows(O));
   const uint32_t lane = threadIdx.x, e0 = P.lo + t0, end = P.lo + (P.n - t0 < ORD_TILE ? P.n : t0 + ORD_TILE);
   int32_t mn[3] = {0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF}, mx[3] = {(int32_t)0x80000000, (int32_t)0x80000000, (int32_t)0x80000000};
 #if defined(__HIPCC__)
@@ -788,14 +753,6 @@ __global__ __launch_bounds__(WAVE) void k_enc_part_bounds(uint8_t *arena, const 
     for (uint32_t c = 0; c < 3u; ++c) { const int32_t x = vals[3ull * row[e] + c]; mn[c] = x < mn[c] ? x : mn[c]; mx[c] = x > mx[c] ? x : mx[c]; }
   for (uint32_t c = 0; c < 3u; ++c) { P.qmin[c] = mn[c] < P.qmin[c] ? mn[c] : P.qmin[c]; P.qmax[c] = mx[c] > P.qmax[c] ? mx[c] : P.qmax[c]; }
 #endif
-}
-
-// The part boxes behind enc_order_launch: `parts` the chunk's np EncPart records, `tiles` its nt (part, tile) pairs.
-template <class Launch>
-static inline void enc_part_launch(Launch &&launch, uint8_t *arena, const EncOrder *clouds, uint32_t nc, EncPart *parts, uint32_t np, const EncPartTile *tiles, uint32_t nt,
-                                   uint32_t passes) {
-  if (nc == 0 || np == 0 || nt == 0) return;
-  launch(k_enc_part_bounds, nt, 1u, (uint32_t)WAVE, arena, clouds, nc, parts, np, tiles, nt, passes);
 }
 
 }  // namespace dsa

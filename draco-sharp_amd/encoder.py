@@ -908,41 +908,38 @@ class DracoEncoder:
             print("[EncodeBatch] native call %.1f ms, result handles %.1f ms" % ((t1 - t0) * 1e3, (time.perf_counter() - t1) * 1e3), flush=True)
         return r
 
+    # The sequential entry points from the widest to the narrowest: (the option that asks for it, the builder of its options, the entry
+    # point, whether its handle has a slot per stream, so that n is read back from it).  A Config reaches the first whose option it
+    # sets -- the widest call only when its option is set, and the plain case keeps arriving through the call it always took.
+    _SEQUENTIAL_CALLS = (
+        ("mean_attributes", "_native_mean", "dsa_encode_mean_sequential_batch", True),
+        ("lod_base_bits", "_native_lod", "dsa_encode_lod_sequential_batch", True),
+        ("part_cells", "_native_cell_parts", "dsa_encode_cell_parts_sequential_batch", True),
+        ("part_points", "_native_split", "dsa_encode_split_sequential_batch", True),
+        ("merge_points", "_native_merge", "dsa_encode_merged_sequential_batch", False),
+        ("point_order", "_native_order", "dsa_encode_ordered_sequential_batch", False),
+        (None, "_native_sequential", "dsa_encode_grid_sequential_batch", False),
+    )
+
     def _encode_sequential(self, ctx, meshes, config, geometry, handle=False):
         n = len(meshes)
         arr, grids, keep = _native_meshes(meshes)
         h = C.c_void_p()
-        if getattr(config, "mean_attributes", 0) != 0 and config._mean_mask(meshes) != 0:       # (the widest call only when its option is set)
-            opt = config._native_mean(geometry, meshes)
-            st = native.lib().dsa_encode_mean_sequential_batch(ctx._h, n, arr, grids, C.byref(opt), C.byref(h))
-            if st == 0:
-                n = native.lib().dsa_encoded_size(h)
-        elif getattr(config, "lod_base_bits", 0) != 0:  # (the widest call only when its option is set)
-            opt = config._native_lod(geometry)
-            st = native.lib().dsa_encode_lod_sequential_batch(ctx._h, n, arr, grids, C.byref(opt), C.byref(h))
-            if st == 0:
-                n = native.lib().dsa_encoded_size(h)
-        elif getattr(config, "part_cells", 0) != 0:     # (the widest call only when its option is set: the handle then has a slot per stream)
-            opt = config._native_cell_parts(geometry)
-            st = native.lib().dsa_encode_cell_parts_sequential_batch(ctx._h, n, arr, grids, C.byref(opt), C.byref(h))
-            if st == 0:
-                n = native.lib().dsa_encoded_size(h)
-        elif getattr(config, "part_points", 0) != 0:    # (the widest call only when its option is set: the handle then has a slot per stream)
-            opt = config._native_split(geometry)
-            st = native.lib().dsa_encode_split_sequential_batch(ctx._h, n, arr, grids, C.byref(opt), C.byref(h))
-            if st == 0:
-                n = native.lib().dsa_encoded_size(h)
-        elif getattr(config, "merge_points", 0) != 0:   # (the widest call only when its option is set)
-            opt = config._native_merge(geometry)
-            st = native.lib().dsa_encode_merged_sequential_batch(ctx._h, n, arr, grids, C.byref(opt), C.byref(h))
-        elif getattr(config, "point_order", 0) != 0:    # (the plain case keeps arriving through the call it always took)
-            opt = config._native_order(geometry)
-            st = native.lib().dsa_encode_ordered_sequential_batch(ctx._h, n, arr, grids, C.byref(opt), C.byref(h))
-        else:
-            opt = config._native_sequential(geometry)
-            st = native.lib().dsa_encode_grid_sequential_batch(ctx._h, n, arr, grids, C.byref(opt), C.byref(h))
+        for option, build, entry, slots in self._SEQUENTIAL_CALLS:
+            if option is not None and getattr(config, option, 0) == 0:
+                continue
+            if option == "mean_attributes":             # (a mask that names no attribute the meshes have asks for nothing)
+                if config._mean_mask(meshes) == 0:
+                    continue
+                opt = config._native_mean(geometry, meshes)
+            else:
+                opt = getattr(config, build)(geometry)
+            break
+        st = getattr(native.lib(), entry)(ctx._h, n, arr, grids, C.byref(opt), C.byref(h))
         if st != 0:
             _raise(st, ctx.error())
+        if slots:
+            n = native.lib().dsa_encoded_size(h)
         return (ctx, h, n) if handle else EncodedStreams(ctx, h, n)
 
     def TryEncodeBatch(self, meshes, config=None, keep=False):

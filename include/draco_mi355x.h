@@ -864,7 +864,7 @@ dsa_status dsa_encode_cell_parts_sequential_batch(dsa_context *ctx, uint32_t n, 
  *   reserved words stay zero; dsa_encoded_lod_info(encoded, stream, out) says which level a slot belongs to.  On a handle made
  *   without lod_base_bits >= 1 it returns DSA_ERR_INVALID_ARGUMENT and the message names lod_base_bits.
  *   The host can bound the slots only by S_max = ceil(n / N) + L - 1 (sum ceil(m_l / N) <= ceil(m / N) + non-empty levels - 1): the
- *   layout reserves S_max slots and the device sizes them (k_enc_lod_parts, dsa_encode_order.h).  A cloud with S_max >
+ *   layout reserves S_max slots and the device sizes them (k_enc_part_cells, dsa_encode_order.h).  A cloud with S_max >
  *   DSA_ENCODE_MAX_PARTS fails alone with DSA_ERR_INVALID_ARGUMENT; the message names lod_base_bits, part_cells, n and the limit.  A
  *   refused cloud keeps one slot.
  *   lod_base_bits = 0: the bytes, the messages, the work, the rows and the handle shape of dsa_encode_cell_parts_sequential_batch.

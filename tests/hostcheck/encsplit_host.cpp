@@ -1,85 +1,35 @@
 // tests/hostcheck/encsplit_host.cpp -- TEST INFRASTRUCTURE ONLY.
 //
 // The encoder's part kernel (draco-sharp_amd/csrc/dsa_encode_order.h: k_enc_part_bounds) compiled for the host with
-// AddressSanitizer + UBSan and run thread by thread behind the product's sort (enc_order_launch, then enc_part_launch) in the arena
-// the product's layout hands out for a split chunk (enc_layout_sequential with EncRequest::point_order and part_points: stream
-// records, order records, part records, both tile lists and every region are the library's own) -- once forwards, once backwards
-// -- against the host coder (dsa_encode_host.h: synth::split_parts, synth::part_boxes) on the same points: the same ranges in the
-// part records and in nv / e2v of every part's stream records, the same boxes, the same rows in the slice of the sorted buffer
-// every stream of a part reads as its entry -> row map, and not one access outside a region (the arena's gaps are poisoned).
-// k_enc_gather itself lives in dsa_encode.h, which needs HIP: its accesses -- e2v[e], vals[nc e2v[e] + c], d[nc e + c] for e < nv of
-// every stream record -- are made here in its place, in the product's regions, and what lands in d is held to the order.
-// Every cloud carries normals, so that a part has two streams on two sets of shared integers.  The clouds of one position_bits and
-// part_points are one chunk.  Nothing here is linked into the product.
+// AddressSanitizer + UBSan and run thread by thread behind the product's sort, by the product's launch sequence (enc_order_stage),
+// in the arena the product's layout hands out for a split chunk (enc_layout_sequential with EncRequest::point_order and part_points:
+// stream records, order records, part records, both tile lists and every region are the library's own; encorder_common.h has the
+// harness) -- once forwards, once backwards -- against the host coder (dsa_encode_host.h: synth::split_parts, synth::part_boxes) on
+// the same points: the same ranges in the part records and in nv / e2v of every part's stream records, the same boxes, the same rows
+// in the slice of the sorted buffer every stream of a part reads as its entry -> row map, and not one access outside a region (the
+// arena's gaps are poisoned).  The accesses of k_enc_gather are made in its place, in the product's regions, and what lands in d is
+// held to the order.  Every cloud carries normals, so that a part has two streams on two sets of shared integers.  The clouds of one
+// position_bits and part_points are one chunk.  Nothing here is linked into the product.
 //
 //   encsplit_host <cases.bin>   file: u32 count, then per case u32 n, bits, has_grid, part_points; f32 pos[3 n]; with a grid f32 origin[3], range
-#include <sanitizer/asan_interface.h>
-
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <string>
-#include <vector>
-
-#include "../../draco-sharp_amd/csrc/dsa_common.h"
-#include "../../draco-sharp_amd/csrc/dsa_types.h"
-
-#include "hip_on_host.h"
-
-#include "../../draco-sharp_amd/csrc/dsa_encode_layout.h"
-
-struct In {
-  uint32_t n = 0, bits = 0, has_grid = 0, part_points = 0;
-  std::vector<float> pos;
-  float grid[4] = {0, 0, 0, 0};
-};
+#include "encorder_common.h"
 
 #define FAIL(...) do { fprintf(stderr, "bits %u, part_points %u, %s: ", bits, part_points, backwards ? "backwards" : "forwards"); fprintf(stderr, __VA_ARGS__); fprintf(stderr, "\n"); return 1; } while (0)
 
 // the cases `which` as one chunk of a request of point clouds
 static int run(const std::vector<const In *> &which, uint32_t bits, uint32_t part_points, bool backwards, uint64_t &points, uint64_t &parts_seen) {
-  const uint32_t n = (uint32_t)which.size();
-  std::vector<dsa_mesh_attr_input> meshes(n);
-  std::vector<EncMeshGrids> grids(n);
-  memset(meshes.data(), 0, sizeof(dsa_mesh_attr_input) * n);
-  bool any_grid = false;
-  for (uint32_t i = 0; i < n; ++i) {
-    const In &c = *which[i];
-    dsa_mesh_input &m = meshes[i].mesh.mesh;
-    m.num_vertices = c.n; m.positions = c.pos.data(); m.normals = c.pos.data();
-    if (c.has_grid) { synth::Grid &g = grids[i].slot[0]; memcpy(g.origin, c.grid, 12); g.range = c.grid[3]; g.mode = 1; any_grid = true; }
-  }
-  EncRequest rq;
-  rq.n = n; rq.meshes = meshes.data(); rq.sequential = true; rq.point_order = true; rq.part_points = part_points;
-  if (any_grid) rq.grids = grids.data();
-  memset(&rq.seq, 0, sizeof(rq.seq));
-  synth::Options d;
-  dsa_encode_options &o = rq.seq.base;
-  o.position_bits = (int32_t)bits; o.texcoord_bits = d.uv_bits; o.normal_bits = d.normal_bits; o.symbol_scheme = d.force_scheme; o.compression_level = d.compression_level;
-  rq.seq.geometry = 0; rq.seq.compress_connectivity = 0;
-  if (!rq.split()) FAIL("the request is not a split one");
-  EncChunk ck(rq, 0, n, n);
+  Run R;
+  Ask ask;
+  ask.bits = bits; ask.part_points = part_points; ask.normals = true;
+  if (!R.begin(which, ask)) FAIL("%s", R.why.c_str());
+  const EncLayout &L = R.L();
+  const EncChunk &ck = *R.ck;
+  const uint32_t n = R.n;
+  uint8_t *arena = R.arena;
+  if (!R.rq.split()) FAIL("the request is not a split one");
   if (!ck.E->split || ck.E->parts.size() != n || ck.parts.size() != n) FAIL("the chunk's handle keeps no parts");
-  std::vector<std::pair<uint64_t, uint64_t>> log;
-  ck.region_log = &log;
-  for (uint32_t i = 0; i < n; ++i) { enc_check_sequential_mesh(ck, i); if (!ck.good(i)) FAIL("case %u refused: %s", i, ck.E->messages[i].c_str()); }
-  enc_layout_sequential(ck);
-  const EncLayout &L = ck.L;
-  if (!L.split || L.merge || L.ord.size() != n || L.ord_of_mesh.size() != n || L.part_of_mesh.size() != n || L.ord_passes != (3 * bits + 7) / 8)
-    FAIL("%zu order records for %u clouds, %u passes", L.ord.size(), n, L.ord_passes);
-  // the arena: the uploads as enc_upload copies them, everything behind them zero, every gap between two regions poisoned
-  std::vector<uint8_t> store(L.total_bytes + 256, 0);
-  uint8_t *arena = store.data();
-  for (const EncUpload &u : L.uploads) {
-    if (u.off >= L.input_bytes || u.off + u.bytes > L.input_bytes || u.narrow) FAIL("an upload outside the inputs");
-    if (u.bytes) memcpy(arena + u.off, u.src, u.bytes);
-  }
-  std::map<uint64_t, uint64_t> region;
-  for (const auto &r : log) { if (r.first + r.second > L.total_bytes) FAIL("a region outside the arena"); region[r.first] = std::max(region[r.first], r.second); }
-  auto sized = [&](uint64_t off, uint64_t bytes) { auto it = region.find(off); return it != region.end() && it->second >= bytes; };
-  if (!sized(L.parts_at, sizeof(dsa::EncPart) * L.parts.size()) || !sized(L.part_tiles_at, sizeof(dsa::EncPartTile) * L.part_tiles.size())) FAIL("the part records are not among the uploads");
-  const uint32_t perm_buffer = L.ord_passes & 1;
+  if (!L.split || L.merge || L.ord_of_mesh.size() != n || L.part_of_mesh.size() != n) FAIL("%zu order records for %u clouds, %u passes", L.ord.size(), n, L.ord_passes);
+  if (!R.sized(L.parts_at, sizeof(dsa::EncPart) * L.parts.size()) || !R.sized(L.part_tiles_at, sizeof(dsa::EncPartTile) * L.part_tiles.size())) FAIL("the part records are not among the uploads");
   std::vector<std::vector<uint32_t>> want_perm(n);
   std::vector<std::vector<std::pair<uint32_t, uint32_t>>> want_ranges(n);
   std::vector<std::vector<int32_t>> want_min(n), want_max(n);
@@ -88,12 +38,11 @@ static int run(const std::vector<const In *> &which, uint32_t bits, uint32_t par
     const In &c = *which[i];
     const dsa::EncOrder &O = L.ord[i];
     const uint32_t s0 = L.first_stream[i];
-    const synth::Grid *grid = c.has_grid ? &grids[i].slot[0] : nullptr;
-    synth::part_boxes(c.pos.data(), c.n, (int)bits, grid, part_points, want_perm[i], want_ranges[i], want_min[i], want_max[i]);
+    synth::part_boxes(c.pos.data(), c.n, (int)bits, R.grid(i), part_points, want_perm[i], want_ranges[i], want_min[i], want_max[i]);
     const uint32_t np = (uint32_t)want_ranges[i].size();
     if (L.ord_of_mesh[i] != i || O.n != c.n || O.merge != 0 || O.rank != 0 || O.count != 0 || O.cells != 0) FAIL("case %u: order record", i);
     if (ck.num_parts(i) != np || L.part_of_mesh[i] != part_at || L.first_stream[i + 1] != s0 + 2 * np) FAIL("case %u: %u parts laid out, the host coder cuts %u", i, ck.num_parts(i), np);
-    if (!sized(O.key[0], 8ull * c.n) || !sized(O.key[1], 8ull * c.n) || !sized(O.row[0], 4ull * c.n) || !sized(O.row[1], 4ull * c.n) || !sized(O.hist, 4ull * O.tiles))
+    if (!R.sized(O.key[0], 8ull * c.n) || !R.sized(O.key[1], 8ull * c.n) || !R.sized(O.row[0], 4ull * c.n) || !R.sized(O.row[1], 4ull * c.n) || !R.sized(O.hist, 4ull * O.tiles))
       FAIL("case %u: order regions too small", i);
     for (uint32_t p = 0; p < np; ++p, ++part_at) {
       const dsa::EncPart &P = L.parts[part_at];
@@ -104,45 +53,30 @@ static int run(const std::vector<const In *> &which, uint32_t bits, uint32_t par
         if (tile_at >= L.part_tiles.size() || L.part_tiles[tile_at].part != part_at || L.part_tiles[tile_at].tile != t) FAIL("case %u part %u: tile %u is not in the list", i, p, t);
       for (uint32_t k = 0; k < 2; ++k) {
         const dsa::EncStream &S = L.streams[s0 + 2 * p + k], &first = L.streams[s0 + k];
-        if (S.linear != 0 || S.nv != cnt || S.rows != c.n || S.e2v != O.row[perm_buffer] + 4ull * lo || S.vals != first.vals || S.src != first.src || S.part != (p ? 1u : 0u))
+        if (S.linear != 0 || S.nv != cnt || S.rows != c.n || S.e2v != dsa::ord_sorted(O).row + 4ull * lo || S.e2v != dsa::ord_part_rows(O) + 4ull * lo || S.vals != first.vals || S.src != first.src || S.part != (p ? 1u : 0u))
           FAIL("case %u part %u: stream %u does not read its slice of the cloud's rows and values", i, p, k);
         if (p && (S.grid_mode != 0 || S.d == first.d || S.syms == first.syms || S.hist_raw == first.hist_raw || S.out_rans == first.out_rans)) FAIL("case %u part %u: stream %u shares a region of the first part's", i, p, k);
-        if (S.d == S.vals || !sized(S.d, 4ull * S.nc * cnt) || !sized(S.syms, 4ull * S.nc * cnt) || !sized(S.bl, cnt) || !sized(first.vals, 4ull * S.nc * c.n) || S.out_cap < 4u * cnt * S.nc + 16u ||
-            !sized(S.out_rans, S.out_cap) || !sized(S.out_bits, S.out_cap))
+        if (S.d == S.vals || !R.sized(S.d, 4ull * S.nc * cnt) || !R.sized(S.syms, 4ull * S.nc * cnt) || !R.sized(S.bl, cnt) || !R.sized(first.vals, 4ull * S.nc * c.n) || S.out_cap < 4u * cnt * S.nc + 16u ||
+            !R.sized(S.out_rans, S.out_cap) || !R.sized(S.out_bits, S.out_cap))
           FAIL("case %u part %u: regions of stream %u too small", i, p, k);
       }
     }
     if (O.vals != L.streams[s0].vals) FAIL("case %u: the sort does not read the positions' integers", i);
-    synth::PortableAttr a;
-    a.att_type = 0; a.nc = a.nc_out = 3; a.seq_type = 2; a.grid = grid;
-    synth::quantize(c.pos.data(), c.n, 3, (int)bits, a);
-    memcpy(arena + O.vals, a.vals.data(), 12ull * c.n);
+    R.write_positions(i);
     int32_t *nv = (int32_t *)(arena + L.streams[s0 + 1].vals);       // the normals' two integers per row: the row, told apart per component
     for (uint32_t r = 0; r < c.n; ++r) { nv[2 * r] = (int32_t)r; nv[2 * r + 1] = ~(int32_t)r; }
   }
   if (tile_at != L.part_tiles.size() || part_at != L.parts.size()) FAIL("%zu part tiles and %zu parts laid out, %zu and %zu expected", L.part_tiles.size(), L.parts.size(), tile_at, part_at);
-  const dsa::EncOrder *clouds = (const dsa::EncOrder *)(arena + L.ord_at);
-  const dsa::EncOrderTile *tiles = (const dsa::EncOrderTile *)(arena + L.ord_tiles_at);
-  dsa::EncPart *parts = (dsa::EncPart *)(arena + L.parts_at);
-  const dsa::EncPartTile *part_tiles = (const dsa::EncPartTile *)(arena + L.part_tiles_at);
-  ASAN_POISON_MEMORY_REGION(arena, store.size());
-  for (const auto &r : region) ASAN_UNPOISON_MEMORY_REGION(arena + r.first, r.second);
-  auto go = [backwards](auto kernel, uint32_t grid_x, uint32_t grid_y, uint32_t block, auto... args) { launch(kernel, grid_x, grid_y, block, backwards, args...); };
-  dsa::enc_order_launch(go, arena, clouds, n, tiles, (uint32_t)L.ord_tiles.size(), L.ord_passes, false, 0u);
-  dsa::enc_part_launch(go, arena, clouds, n, parts, (uint32_t)L.parts.size(), part_tiles, (uint32_t)L.part_tiles.size(), L.ord_passes);
-  // the gather's accesses, stream record by stream record
-  for (const dsa::EncStream &S : L.streams) {
-    const int32_t *vals = (const int32_t *)(arena + S.vals);
-    const uint32_t *e2v = (const uint32_t *)(arena + S.e2v);
-    int32_t *dst = (int32_t *)(arena + S.d);
-    for (uint32_t e = 0; e < S.nv; ++e)
-      for (uint32_t k = 0; k < S.nc; ++k) dst[(size_t)e * S.nc + k] = vals[(size_t)e2v[e] * S.nc + k];
-  }
+  R.poison();
+  if (!R.stage(backwards)) FAIL("%s", R.why.c_str());
+  R.gather();
+  const dsa::EncOrder *clouds = R.clouds();
+  const dsa::EncPart *parts = R.parts();
   part_at = 0;
   for (uint32_t i = 0; i < n; ++i) {
     const In &c = *which[i];
     const uint32_t s0 = L.first_stream[i];
-    const uint32_t *perm = (const uint32_t *)(arena + clouds[i].row[perm_buffer]);
+    const uint32_t *perm = (const uint32_t *)(arena + dsa::ord_sorted(clouds[i]).row);
     for (uint32_t e = 0; e < c.n; ++e) if (perm[e] != want_perm[i][e]) FAIL("case %u (%u points): entry %u carries row %u, the host coder says %u", i, c.n, e, perm[e], want_perm[i][e]);
     const int32_t *q = (const int32_t *)(arena + clouds[i].vals);
     for (uint32_t p = 0; p < want_ranges[i].size(); ++p, ++part_at) {
@@ -160,36 +94,24 @@ static int run(const std::vector<const In *> &which, uint32_t bits, uint32_t par
     }
     points += c.n;
   }
-  ASAN_UNPOISON_MEMORY_REGION(arena, store.size());
+  R.unpoison();
   return 0;
 }
 
 int main(int argc, char **argv) {
   if (argc < 2) { fprintf(stderr, "usage: encsplit_host <cases.bin>\n"); return 2; }
-  FILE *f = fopen(argv[1], "rb");
-  if (!f) { perror(argv[1]); return 2; }
-  uint32_t count = 0;
-  if (fread(&count, 4, 1, f) != 1) return 2;
-  std::vector<In> cases(count);
-  for (auto &c : cases) {
-    uint32_t head[4];
-    if (fread(head, 4, 4, f) != 4) return 2;
-    c.n = head[0]; c.bits = head[1]; c.has_grid = head[2]; c.part_points = head[3];
-    if (c.n == 0 || c.bits < 1 || c.bits > 20 || c.part_points == 0 || c.part_points > 0x7FFFFFFFu) return 2;
-    c.pos.resize((size_t)3 * c.n);
-    if (fread(c.pos.data(), 4, c.pos.size(), f) != c.pos.size()) return 2;
-    if (c.has_grid && fread(c.grid, 4, 4, f) != 4) return 2;
-  }
-  fclose(f);
+  std::vector<In> cases;
+  if (!read_cases(argv[1], 4, false, cases)) return 2;
+  for (const In &c : cases) if (c.more[0] == 0 || c.more[0] > 0x7FFFFFFFu) return 2;
   uint32_t chunks = 0;
   uint64_t points = 0, parts = 0;
   std::map<std::pair<uint32_t, uint32_t>, std::vector<const In *>> groups;      // (bits, part_points): one request
-  for (const In &c : cases) groups[{c.bits, c.part_points}].push_back(&c);
+  for (const In &c : cases) groups[{c.bits, c.more[0]}].push_back(&c);
   for (const auto &g : groups) {
     for (int backwards = 0; backwards < 2; ++backwards) if (run(g.second, g.first.first, g.first.second, backwards != 0, points, parts) != 0) return 1;
     ++chunks;
   }
-  printf("encsplit: %u cases in %u chunks cut as the host coder cuts them, forwards and backwards (%llu points, %llu parts)\n", count, chunks,
+  printf("encsplit: %u cases in %u chunks cut as the host coder cuts them, forwards and backwards (%llu points, %llu parts)\n", (uint32_t)cases.size(), chunks,
          (unsigned long long)points, (unsigned long long)parts);
   return 0;
 }

@@ -1,6 +1,6 @@
 """Encode direction, additive levels of detail of merged point clouds on the device (dsa_encode_lod_sequential_batch,
-lod_base_bits >= 1; Config(merge_points=MERGE_CELLS, part_cells=N, lod_base_bits=D); k_enc_lod_levels / _scan / _scatter / _cells /
-_parts of draco-sharp_amd/csrc/dsa_encode_order.h and the slots of dsa_encode_layout.h).  Every slot's stream must be, byte for
+lod_base_bits >= 1; Config(merge_points=MERGE_CELLS, part_cells=N, lod_base_bits=D); k_enc_lod_levels / _scan / _scatter / _cells and
+k_enc_part_cells of draco-sharp_amd/csrc/dsa_encode_order.h and the slots of dsa_encode_layout.h).  Every slot's stream must be, byte for
 byte, the CPU coder's (synth.encode_lod_parts); the handle's slots, slices of lod, row entries, part records and level records must
 be the twin's; all slots decode side by side to the merged single stream's points, and every prefix of levels is one point per cell
 of its grid.  The shapes sit on the kernels' edges: the 64 entries of a wave step and the 1024-entry tile, in level populations, in

@@ -1,6 +1,6 @@
 """The encoder's level-of-detail steps (draco-sharp_amd/csrc/dsa_encode_order.h: k_enc_lod_levels, k_enc_lod_scan,
-k_enc_lod_scatter, k_enc_lod_cells, k_enc_lod_parts, between the product's merge and its part boxes, under the product's launch
-sequences, in the arena of the product's layout for a chunk with lod_base_bits >= 1 -- ceil(n / N) + L - 1 part slots sized on the
+k_enc_lod_scatter, k_enc_lod_cells, k_enc_part_cells, between the product's merge and its part boxes, under the product's launch
+sequence, in the arena of the product's layout for a chunk with lod_base_bits >= 1 -- ceil(n / N) + L - 1 part slots sized on the
 device, a set of stream records per slot on one set of values, lod and pos in the sort's dead key buffer) compiled for the host
 under AddressSanitizer + UBSan (tests/hostcheck/enclod_host.cpp, a program of its own) and held against the host coder
 (synth::lod_parts) on every case of tests/lodcases.py, with the threads run forwards and backwards, the arena's gaps poisoned, and

@@ -2,8 +2,9 @@
 and merge and under the product's launch sequences, in the arena of the product's layout) compiled for the host under
 AddressSanitizer + UBSan (tests/hostcheck/encmeans_host.cpp) and held against the host coder (synth::merge_points,
 synth::merge_means) on every case of tests/mergecases.py, with one and with two masked streams per cloud, the threads run forwards
-and backwards, the arena's gaps poisoned and the sums and counts filled with a pattern until the product's memset.  A check of the
-product source on CPU, not a CPU encode path of the product."""
+and backwards, the arena's gaps poisoned and the sums and counts filled with a pattern until the product's memset; and, with
+part_cells and lod_base_bits, through the levels and the part slots the product runs behind the means (synth::lod_parts).  A check of
+the product source on CPU, not a CPU encode path of the product."""
 import os
 import re
 import struct
@@ -26,19 +27,19 @@ def exe(tmp_path_factory):
     return out
 
 
-def write(path, cases):
+def write(path, cases, part_cells=0, lod_base_bits=0):
     with open(path, "wb") as f:
         f.write(struct.pack("<I", len(cases)))
         for c in cases:
-            f.write(struct.pack("<IIII", len(c.pos), c.bits, int(c.grid is not None), 0))
+            f.write(struct.pack("<IIIII", len(c.pos), c.bits, int(c.grid is not None), part_cells, lod_base_bits))
             f.write(np.ascontiguousarray(c.pos, np.float32).tobytes())
             if c.grid is not None:
                 f.write(np.float32(list(c.grid[0]) + [c.grid[1]]).tobytes())
 
 
-def run(exe, tmp_path, cases):
+def run(exe, tmp_path, cases, **slots):
     path = tmp_path / "cases.bin"
-    write(path, cases)
+    write(path, cases, **slots)
     r = subprocess.run([exe, str(path)], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     points = sum(len(c.pos) for c in cases)
@@ -59,3 +60,13 @@ def test_a_large_cloud(exe, tmp_path):
     c = mergecases.large()
     assert 60000 < len(c.pos) < 80000
     run(exe, tmp_path, [c])
+
+
+def test_means_through_levels_and_slots(exe, tmp_path):
+    """three clouds of 1, 1 025 and 2 100 points with duplicates at 6 bits, part_cells = 7, lod_base_bits = 4: the steps the product
+    runs behind the means -- k_enc_lod_cells rewrites the cells[] the means read -- held to synth::merge_means followed by
+    synth::lod_parts; the largest cloud crosses a tile edge in the sorted and in the kept order, and slots stay empty"""
+    cases = [mergecases.half_duplicated(n, 90 + n, bits=6) for n in (1, mergecases.TILE + 1, 2100)]
+    n, m = len(cases[2].pos), len(mergecases.pin(cases[2].pos, 6, cases[2].grid)[0])
+    assert n > 2 * mergecases.TILE and mergecases.TILE < m < n and -(-n // 7) + 2 > -(-m // 7) + 2
+    run(exe, tmp_path, cases, part_cells=7, lod_base_bits=4)

@@ -1,5 +1,5 @@
 """The encoder's point-order kernels (draco-sharp_amd/csrc/dsa_encode_order.h: keys, the segmented radix sort, rank, the faces
-through rank, under the product's launch sequence enc_order_launch and in the arena of the product's layout) compiled for the host
+through rank, under the product's launch sequence enc_order_stage and in the arena of the product's layout) compiled for the host
 under AddressSanitizer + UBSan (tests/hostcheck/encorder_host.cpp) and held against the host coder's order (synth::point_order) on
 every case of tests/ordercases.py, with the threads run forwards and backwards and the arena's gaps poisoned.  A check of the
 product source on CPU, not a CPU encode path of the product."""

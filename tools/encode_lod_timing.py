@@ -8,7 +8,7 @@ points, streams and bytes.  One warm-up pass of every leg, then `rounds` alterna
 usage: python tools/encode_lod_timing.py [millions of points [rounds [multiplicity]]]
        python tools/encode_lod_timing.py --cpu [millions [multiplicity]]      the byte table alone, from the CPU coder: no device
        python tools/encode_lod_timing.py --laps [millions [bits [D [passes]]]]     lod encodes (11 bits, D = 7, one pass) with DSA_ENC_TIMING
-              set, and a cell-parts encode behind each: the laps of the chunk's device stage on stderr, "levels" the five kernels of this call
+              set, and a cell-parts encode behind each: the laps of the chunk's device stage on stderr, "levels" the kernels of this call
        python tools/encode_lod_timing.py --calls [millions [rounds]]          the merged call and the cell-parts call (256 parts) alone,
               seven passes each behind a warm-up, median and spread: run once per library build (DSA_LIB) to hold two builds against
               each other on one box -- neither call is new, so a build without the new entry point runs this leg too"""
