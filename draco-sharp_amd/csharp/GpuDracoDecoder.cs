@@ -220,6 +220,104 @@ public sealed unsafe class GpuDracoDecoder : IDisposable
         return result;
     }
 
+    /// <summary>The joined arrays of one group of DecodeJoinedArrays: one array per attribute with a row per point of all members;
+    /// member k's points are rows FirstRows[k] .. FirstRows[k] + MemberRows[k] (stream order).</summary>
+    public sealed class JoinedArrays
+    {
+        public int NumRows;
+        public int[] FirstRows = [];
+        public int[] MemberRows = [];
+        public VertexAttributeArray?[] Attributes = [];   // null: left out, as in VertexArrays
+    }
+
+    /// <summary>Decodes the part streams of point clouds (GpuDracoEncoder.PartPoints / PartCells / LodBaseBits cut a cloud into many
+    /// ordinary streams) and returns, per group (first stream, stream count), ONE array per attribute with the rows of all its
+    /// members in stream order: gathered on the GPU behind the decode (k_joined_arrays, dsa_batch_joined_arrays), ONE transfer to the
+    /// host.  The levels of a lod handle given in slot order are prefixes of every array.  A group that cannot be joined (a mesh
+    /// member, differing attribute tables, a stream that fails to decode, different quantisation grids with quantized) yields null
+    /// in its place and its exception in errors.</summary>
+    public JoinedArrays?[] DecodeJoinedArrays(IReadOnlyList<byte[]> streams, IReadOnlyList<(int First, int Count)> groups, bool quantized, out Exception?[] errors)
+    {
+        var handles = new System.Runtime.InteropServices.GCHandle[streams.Count];
+        var ptrs = new byte*[streams.Count];
+        var lens = new nuint[streams.Count];
+        var list = new DsaJoinGroup[Math.Max(1, groups.Count)];
+        for (int g = 0; g < groups.Count; ++g) list[g] = new DsaJoinGroup { FirstMesh = (uint)groups[g].First, NumMeshes = (uint)groups[g].Count };
+        IntPtr batch = IntPtr.Zero;
+        try
+        {
+            for (int i = 0; i < streams.Count; ++i)
+            {
+                handles[i] = System.Runtime.InteropServices.GCHandle.Alloc(streams[i], System.Runtime.InteropServices.GCHandleType.Pinned);
+                ptrs[i] = (byte*)handles[i].AddrOfPinnedObject();
+                lens[i] = (nuint)streams[i].Length;
+            }
+            fixed (byte** p = ptrs)
+            fixed (nuint* l = lens)
+            {
+                NativeMethods.Check(NativeMethods.dsa_batch_create(_ctx, (uint)streams.Count, p, l, out batch), _ctx, "dsa_batch_create");
+            }
+            NativeMethods.Check(NativeMethods.dsa_batch_decode(batch), _ctx, "dsa_batch_decode");
+            var request = new DsaJoinRequest { Arrays = new DsaVertexRequest { Format = quantized ? 1 : 0 }, Order = 0 };
+            fixed (DsaJoinGroup* gp = list)
+            {
+                NativeMethods.Check(NativeMethods.dsa_batch_joined_arrays(batch, in request, (uint)groups.Count, gp, IntPtr.Zero, null, null, 0), _ctx, "dsa_batch_joined_arrays");
+            }
+            NativeMethods.Check(NativeMethods.dsa_batch_wait(batch), _ctx, "dsa_batch_wait");
+            var results = new JoinedArrays?[groups.Count];
+            errors = new Exception?[groups.Count];
+            for (uint g = 0; g < groups.Count; ++g)
+            {
+                try { results[g] = MaterializeJoinedArrays(batch, g); }
+                catch (Exception e) when (e is InvalidDataException or NotImplementedException or ArgumentException) { errors[g] = e; }
+            }
+            return results;
+        }
+        finally
+        {
+            if (batch != IntPtr.Zero) NativeMethods.dsa_batch_free(batch);
+            foreach (var h in handles) if (h.IsAllocated) h.Free();
+        }
+    }
+
+    private JoinedArrays MaterializeJoinedArrays(IntPtr batch, uint group)
+    {
+        NativeMethods.Check(NativeMethods.dsa_batch_joined_arrays_layout(batch, group, out var layout), _ctx, "dsa_batch_joined_arrays_layout");
+        byte* block = (byte*)NativeMethods.dsa_batch_host_joined_arrays(batch);
+        if (block == null) throw new InvalidOperationException("the joined arrays are not on the host");
+        NativeMethods.Check(NativeMethods.dsa_batch_mesh_info(batch, layout.FirstMesh, out var info), _ctx, "dsa_batch_mesh_info");
+        var result = new JoinedArrays
+        {
+            NumRows = (int)layout.NumRows, FirstRows = new int[layout.NumMeshes], MemberRows = new int[layout.NumMeshes],
+            Attributes = new VertexAttributeArray?[info.NumAttributes]
+        };
+        for (uint k = 0; k < layout.NumMeshes; ++k)
+        {
+            NativeMethods.Check(NativeMethods.dsa_batch_joined_member(batch, layout.FirstMesh + k, out _, out var first, out var rows), _ctx, "dsa_batch_joined_member");
+            result.FirstRows[k] = (int)first; result.MemberRows[k] = (int)rows;
+        }
+        for (uint a = 0; a < info.NumAttributes; ++a)
+        {
+            var va = layout.Attribute(a);
+            if ((va.Flags & 1) != 0) continue;      // DSA_VA_ABSENT
+            NativeMethods.Check(NativeMethods.dsa_batch_attribute_info(batch, layout.FirstMesh, a, out var ai), _ctx, "dsa_batch_attribute_info");
+            var array = new VertexAttributeArray
+            {
+                AttributeType = (GeometryAttributeType)ai.AttributeType, UniqueId = ai.UniqueId, DataType = (DataType)va.DataType,
+                NumComponents = (int)va.NumComponents, Stride = (int)va.Stride, Data = new byte[(long)layout.NumRows * va.Stride]
+            };
+            fixed (byte* d = array.Data) Buffer.MemoryCopy(block + va.Offset, d, array.Data.LongLength, array.Data.LongLength);
+            if ((ai.DecoderType == 2 || ai.DecoderType == 3) && va.DataType == 4 && ai.DataType != 4)
+            {
+                var min = new float[ai.NumComponents];
+                for (int c = 0; c < min.Length && c < 4; ++c) min[c] = ai.MinValues[c];
+                array.Quantization = (min, ai.Range, ai.QuantizationBits);
+            }
+            result.Attributes[a] = array;
+        }
+        return result;
+    }
+
     private Draco Materialize(IntPtr batch, uint mesh) => Materialize(_ctx, batch, mesh);
 
     internal static Draco Materialize(IntPtr _ctx, IntPtr batch, uint mesh)

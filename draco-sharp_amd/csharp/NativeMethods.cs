@@ -95,6 +95,35 @@ internal struct DsaMeshVertexArrays // 408 bytes
     }
 }
 
+// dsa_join_group / dsa_join_request / dsa_joined_arrays (dsa_batch_joined_arrays): the part streams of a cloud as one array per attribute
+[StructLayout(LayoutKind.Sequential)]
+internal struct DsaJoinGroup        // 8 bytes
+{
+    public uint FirstMesh, NumMeshes;   // meshes FirstMesh .. FirstMesh + NumMeshes of the batch
+}
+
+[StructLayout(LayoutKind.Sequential)]
+internal unsafe struct DsaJoinRequest   // 64 bytes
+{
+    public DsaVertexRequest Arrays; // exactly as for dsa_batch_vertex_arrays
+    public int Order;               // 0 DSA_JOIN_STREAM_ORDER, 1 DSA_JOIN_INPUT_ORDER
+    public fixed uint Reserved[7];  // zero
+}
+
+[StructLayout(LayoutKind.Sequential)]
+internal struct DsaJoinedArrays     // 400 bytes
+{
+    public uint FirstMesh, NumMeshes, NumRows;
+    public int Order;
+    public DsaVertexAttribute A0, A1, A2, A3, A4, A5, A6, A7, A8, A9, A10, A11, A12, A13, A14, A15;   // attributes[DSA_MAX_ATTRIBUTES]
+
+    internal unsafe DsaVertexAttribute Attribute(uint a)
+    {
+        if (a >= 16) throw new ArgumentOutOfRangeException(nameof(a));
+        fixed (DsaVertexAttribute* p = &A0) return p[a];
+    }
+}
+
 [StructLayout(LayoutKind.Sequential)]
 internal struct DsaEncodeOptions
 {
@@ -396,6 +425,12 @@ internal static unsafe partial class NativeMethods
     [DllImport(Lib)] internal static extern DsaStatus dsa_batch_vertex_arrays_layout(IntPtr batch, uint mesh, out DsaMeshVertexArrays layout);
     [DllImport(Lib)] internal static extern IntPtr dsa_batch_host_vertex_arrays(IntPtr batch, uint block);
     [DllImport(Lib)] internal static extern IntPtr dsa_batch_device_vertex_arrays(IntPtr batch, uint block);
+    [DllImport(Lib)] internal static extern ulong dsa_batch_joined_arrays_bytes(IntPtr batch, in DsaJoinRequest request, uint numGroups, DsaJoinGroup* groups);
+    [DllImport(Lib)] internal static extern DsaStatus dsa_batch_joined_arrays(IntPtr batch, in DsaJoinRequest request, uint numGroups, DsaJoinGroup* groups, IntPtr encoded, uint* encodedMesh, void* dst, nuint dstBytes);
+    [DllImport(Lib)] internal static extern DsaStatus dsa_batch_joined_arrays_layout(IntPtr batch, uint group, out DsaJoinedArrays layout);
+    [DllImport(Lib)] internal static extern DsaStatus dsa_batch_joined_member(IntPtr batch, uint mesh, out uint group, out uint firstRow, out uint numRows);
+    [DllImport(Lib)] internal static extern IntPtr dsa_batch_host_joined_arrays(IntPtr batch);
+    [DllImport(Lib)] internal static extern IntPtr dsa_batch_device_joined_arrays(IntPtr batch);
     [DllImport(Lib)] internal static extern IntPtr dsa_host_alloc(nuint bytes);
     [DllImport(Lib)] internal static extern void dsa_host_free(IntPtr p);
     [DllImport(Lib)] internal static extern DsaStatus dsa_host_register(void* p, nuint bytes);

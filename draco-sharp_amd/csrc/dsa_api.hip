@@ -22,6 +22,7 @@
 #include "dsa_host_parse.h"
 #include "dsa_host_util.h"
 #include "dsa_vertex_arrays.h"
+#include "dsa_joined_arrays.h"
 #include "dsa_encode_rows.h"
 
 namespace {
@@ -229,6 +230,26 @@ struct dsa_batch {
   bool sr_to_host = true;
   bool sr_valid = false, sr_queued = false, sr_done = false;
   hipEvent_t ev_sr = nullptr;
+  // Joined arrays (dsa_batch_joined_arrays; dsa_joined_arrays.h, dsa_joined_api.h), shaped like the source rows: a device block of
+  // their own [member list | group records | uploaded target rows | arrays], pinned staging of what goes up, a host copy of the
+  // arrays, an event of their own.  What is known at the call is kept per group; what the decode decides is read from the
+  // descriptors when the layout is asked for.
+  std::vector<JaMember> ja_members;       // the member list of the most recent request (groups refused at the call have no entry)
+  std::vector<JaGroup> ja_groups;
+  std::vector<dsa_join_group> ja_list;    // the groups as the caller named them
+  std::vector<int32_t> ja_status;         // per group: DSA_OK, or why the call refused it
+  std::vector<std::string> ja_text;       // ... in words
+  std::vector<uint32_t> ja_first_row;     // per mesh: its first row in its group
+  std::vector<int32_t> ja_group_of;       // per mesh: its group, -1: none
+  dsa_join_request ja_req = {};
+  uint64_t ja_bytes = 0, ja_head_bytes = 0;
+  uint8_t *d_ja = nullptr;                // from the context's cache (spare_vertex)
+  uint64_t d_ja_cap = 0;
+  uint8_t *ja_pin = nullptr;              // pinned staging of the head (from spare_mirrors)
+  uint64_t ja_pin_bytes = 0;
+  HostCopy ja_mirror;
+  bool ja_valid = false, ja_queued = false, ja_done = false;
+  hipEvent_t ev_ja = nullptr;
   bool all_general = false;
   // meshes the fast kernels handed back (DSA_SITE_RETRY_GENERAL): decoded again through the general path in a batch
   // of their own by dsa_batch_wait; every per-mesh accessor follows retry_index (locate)
@@ -651,6 +672,8 @@ dsa_status dsa_batch_decode(dsa_batch *b) {
   b->va_valid = false;                                                                                 // a new decode invalidates them
   if (b->sr_queued && !b->sr_done) HIP_TRY(ctx, hipStreamWaitEvent(st, b->ev_sr, 0));               // its source rows read the maps
   b->sr_valid = false;
+  if (b->ja_queued && !b->ja_done) HIP_TRY(ctx, hipStreamWaitEvent(st, b->ev_ja, 0));               // its joined arrays read the values
+  b->ja_valid = false;
   HIP_TRY(ctx, hipStreamWaitEvent(st, b->ev_uploaded, 0));           // the streams and layouts are in the arena
   HIP_TRY(ctx, hipMemsetAsync(b->d_descs, 0, sizeof(MeshDesc) * n, st));
   HIP_TRY(ctx, hipMemsetAsync(&b->d_globals->pool_cursor, 0, sizeof(unsigned long long) * 2, st));   // the table pool starts empty
@@ -1082,6 +1105,7 @@ static dsa_status batch_wait(dsa_batch *b) {
     if (b->download_queued && !b->downloaded) { HIP_TRY(ctx, hipEventSynchronize(b->ev_down)); b->downloaded = true; }
     if (b->va_valid && b->va_queued && !b->va_done) { HIP_TRY(ctx, hipEventSynchronize(b->ev_va)); b->va_done = true; }
     if (b->sr_valid && b->sr_queued && !b->sr_done) { HIP_TRY(ctx, hipEventSynchronize(b->ev_sr)); b->sr_done = true; }
+    if (b->ja_valid && b->ja_queued && !b->ja_done) { HIP_TRY(ctx, hipEventSynchronize(b->ev_ja)); b->ja_done = true; }
     HIP_TRY(ctx, late_kernel_times(b));
     if (b->retry) return dsa_batch_wait(b->retry);
     return DSA_OK;
@@ -1091,6 +1115,7 @@ static dsa_status batch_wait(dsa_batch *b) {
   if (b->download_queued) { HIP_TRY(ctx, hipEventSynchronize(b->ev_down)); b->downloaded = true; }
   if (b->va_valid && b->va_queued) { HIP_TRY(ctx, hipEventSynchronize(b->ev_va)); b->va_done = true; }
   if (b->sr_valid && b->sr_queued) { HIP_TRY(ctx, hipEventSynchronize(b->ev_sr)); b->sr_done = true; }
+  if (b->ja_valid && b->ja_queued) { HIP_TRY(ctx, hipEventSynchronize(b->ev_ja)); b->ja_done = true; }
   if (b->n) memcpy(b->descs.data(), b->descs_pin, sizeof(MeshDesc) * (size_t)b->n);
   if (ctx->profiling && b->have_events && b->n) {
     for (int i = 0; i < STG_TOTAL; ++i) HIP_TRY(ctx, hipEventElapsedTime(&b->stage_ms[i], b->ev[i], b->ev[i + 1]));
@@ -1154,7 +1179,11 @@ void dsa_batch_free(dsa_batch *b) {
   if (b->ev_down) { if (b->download_queued) (void)hipEventSynchronize(b->ev_down); (void)hipEventDestroy(b->ev_down); }
   if (b->ev_va) { if (b->va_queued) (void)hipEventSynchronize(b->ev_va); (void)hipEventDestroy(b->ev_va); }
   if (b->ev_sr) { if (b->sr_queued) (void)hipEventSynchronize(b->ev_sr); (void)hipEventDestroy(b->ev_sr); }
+  if (b->ev_ja) { if (b->ja_queued) (void)hipEventSynchronize(b->ev_ja); (void)hipEventDestroy(b->ev_ja); }
   dsa_context *ctx = b->ctx;
+  ctx->spare_mirrors.give(b->ja_pin, b->ja_pin_bytes);
+  release(ctx, b->ja_mirror);
+  ctx->spare_vertex.give(b->d_ja, b->d_ja_cap);
   ctx->spare_mirrors.give(b->sr_pin, b->sr_pin_bytes);
   release(ctx, b->sr_mirror);
   ctx->spare_vertex.give(b->d_sr, b->d_sr_cap);
@@ -1658,4 +1687,5 @@ dsa_status dsa_batch_stage_times(const dsa_batch *b, float ms[DSA_NUM_STAGES], c
 
 #include "dsa_encode.h"
 #include "dsa_source_rows.h"
+#include "dsa_joined_api.h"
 #include "dsa_pool.h"

@@ -533,6 +533,133 @@ class Batch:
         return [np.frombuffer((C.c_uint8 * (4 * lay.num_points)).from_address(base + lay.rows[a]), np.uint32, lay.num_points) if lay.num_points else np.zeros(0, np.uint32)
                 for a in range(lay.num_attributes)]
 
+    # ---- joined arrays (dsa_batch_joined_arrays): the part streams of a cloud as one array per attribute, gathered on the device
+    _JOIN_ORDERS = {"stream": native.DSA_JOIN_STREAM_ORDER, "input": native.DSA_JOIN_INPUT_ORDER}
+
+    def _join_request(self, groups, format, attribute_types, order, device_only):
+        if order not in self._JOIN_ORDERS:
+            raise ValueError("order must be 'stream' or 'input', not %r" % (order,))
+        req = native.JoinRequest(self._vertex_request(format, attribute_types, device_only), self._JOIN_ORDERS[order])
+        groups = [(int(f), int(c)) for f, c in groups]
+        arr = (native.JoinGroup * max(1, len(groups)))(*[native.JoinGroup(f, c) for f, c in groups])
+        return req, arr, len(groups)
+
+    def joined_arrays_bytes(self, groups, format="values", attribute_types=None):
+        """Bytes of the joined-array block this request would make (fixed by the stream headers)."""
+        req, arr, n = self._join_request(groups, format, attribute_types, "stream", False)
+        return int(self._L.dsa_batch_joined_arrays_bytes(self._h, C.byref(req), n, arr))
+
+    def joined_arrays(self, groups, format="values", attribute_types=None, order="stream", encoded=None, encoded_mesh=None, wait=True, device_only=False):
+        """Queues the gather of joined vertex arrays behind the batch's kernels and ONE device -> host transfer of them
+        (dsa_batch_joined_arrays): per group (first_mesh, num_meshes) of point-cloud meshes of the batch and per attribute ONE array
+        with a row per point of all members -- the parts of a cloud that part_points / part_cells / lod_base_bits cut, back in one
+        piece.  order "stream": the rows of member 0, then member 1 ... (joined_views(g)["members"] says where each starts; the levels
+        of a lod handle given in slot order are prefixes); order "input": row r is the point that carries row r of the arrays the
+        encoder was given -- needs `encoded`, the open EncodedStreams of a sequential config without merge_points, the groups being
+        all parts of one input each (encoder.join_plan), encoded_mesh[i] the stream mesh i was created from (None: stream i).
+        format, attribute_types, device_only: as for vertex_arrays.  Returns a list with joined_views(g) per group (with device_only
+        device_joined_views(g)), a group that has no arrays represented by the exception that says why; with wait=False None:
+        joined_views(g) after wait().  `encoded` must stay open until then."""
+        if not self._h:
+            raise DeviceException("the batch is closed")
+        req, arr, n = self._join_request(groups, format, attribute_types, order, device_only)
+        if encoded is not None and getattr(encoded, "_h", None) is None:
+            raise ValueError("joined_arrays takes the open EncodedStreams the batch's streams came from")
+        em = None
+        if encoded_mesh is not None:
+            em = np.ascontiguousarray(encoded_mesh, np.uint32)
+            if em.shape != (self.n,):
+                raise ValueError("encoded_mesh: one stream index per mesh of the batch")
+        self._join_of = (encoded, em)                    # (the library reads the handle until the wait is over)
+        st = self._L.dsa_batch_joined_arrays(self._h, C.byref(req), n, arr, None if encoded is None else encoded._h, None if em is None else em.ctypes.data, None, 0)
+        if st != 0:
+            _raise(st, self.ctx.error())
+        if not wait:
+            return None
+        self.wait()
+        out = []
+        for g in range(n):
+            try:
+                out.append(self.device_joined_views(g) if device_only else self.joined_views(g))
+            except Exception as e:          # noqa: BLE001  (the exception is the group's result)
+                out.append(e)
+        return out
+
+    def joined_member(self, i):
+        """(group, first_row, num_rows) of mesh i in the most recent joined_arrays()."""
+        g, f, r = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        st = self._L.dsa_batch_joined_member(self._h, i, C.byref(g), C.byref(f), C.byref(r))
+        if st != 0:
+            _raise(st, self.ctx.error())
+        return g.value, f.value, r.value
+
+    def _joined_layout(self, g):
+        lay = native.JoinedArrays()
+        st = self._L.dsa_batch_joined_arrays_layout(self._h, g, C.byref(lay))
+        if st != 0:
+            _raise(st, self.ctx.error())
+        infos = []
+        for a in range(self.mesh_info(lay.first_mesh).num_attributes):
+            ai = native.AttributeInfo()
+            st = self._L.dsa_batch_attribute_info(self._h, lay.first_mesh, a, C.byref(ai))
+            if st != 0:
+                _raise(st, self.ctx.error())
+            infos.append(ai)
+        members = [(i,) + self.joined_member(i)[1:] for i in range(lay.first_mesh, lay.first_mesh + lay.num_meshes)]
+        return lay, infos, members
+
+    def joined_views(self, g):
+        """Zero-copy numpy views of group g's joined arrays in the host copy: {"num_rows", "members": [(mesh, first_row, num_rows)],
+        "attributes": [{"info", "values": [num_rows, components] (None when absent, as in vertex_views), "quantization"}]}; info and
+        quantization are those of the first member.  Valid until the batch is closed, decoded again or asked for joined arrays
+        again."""
+        lay, infos, members = self._joined_layout(g)
+        base = self._L.dsa_batch_host_joined_arrays(self._h)
+        if not base:
+            raise RuntimeError("the batch has no joined arrays on the host (Batch.joined_arrays, then wait)")
+        out = {"num_rows": lay.num_rows, "members": members, "attributes": []}
+        for a, ai in enumerate(infos):
+            va = lay.attributes[a]
+            values = None
+            if not va.flags & native.DSA_VA_ABSENT:
+                dt = np.dtype(_DT_NUMPY[va.data_type])
+                cols = va.stride // dt.itemsize
+                if lay.num_rows == 0:
+                    values = np.zeros((0, va.num_components), dt)
+                else:
+                    values = np.frombuffer((C.c_uint8 * (lay.num_rows * va.stride)).from_address(base + va.offset), dt, lay.num_rows * cols).reshape(lay.num_rows, cols)[:, :va.num_components]
+            out["attributes"].append({"info": ai, "values": values, "quantization": self._vertex_quantization(ai, va)})
+        return out
+
+    def device_joined_views(self, g):
+        """joined_views(g) as torch tensors over the device block (also after joined_arrays(device_only=True)); unsigned arrays as
+        signed views of the same bits, as in device_vertex_views."""
+        import torch
+        lay, infos, members = self._joined_layout(g)
+        base = self._L.dsa_batch_device_joined_arrays(self._h)
+        if not base:
+            raise RuntimeError("the batch has no joined arrays (Batch.joined_arrays)")
+        dev = "cuda:%d" % self.ctx.device
+
+        class _Ptr:                                    # __cuda_array_interface__ v2 carrier
+            def __init__(self, ptr, shape, typestr):
+                self.__cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (int(ptr), False), "version": 2}
+
+        typestr = {1: "|i1", 2: "|u1", 3: "<i2", 4: "<i2", 5: "<i4", 6: "<i4", 9: "<f4"}
+        torch_dt = {"|i1": torch.int8, "|u1": torch.uint8, "<i2": torch.int16, "<i4": torch.int32, "<f4": torch.float32}
+        out = {"num_rows": lay.num_rows, "members": members, "attributes": []}
+        for a, ai in enumerate(infos):
+            va = lay.attributes[a]
+            ts = typestr.get(va.data_type)
+            values = None
+            if not va.flags & native.DSA_VA_ABSENT and ts:
+                if lay.num_rows == 0:
+                    values = torch.empty((0, va.num_components), dtype=torch_dt[ts], device=dev)
+                else:
+                    values = torch.as_tensor(_Ptr(base + va.offset, (lay.num_rows, va.stride // int(ts[2])), ts), device=dev)[:, :va.num_components]
+            out["attributes"].append({"info": ai, "values": values, "quantization": self._vertex_quantization(ai, va)})
+        return out
+
     @property
     def algorithmic_bytes(self):
         return int(self._L.dsa_batch_algorithmic_bytes(self._h))

@@ -754,6 +754,39 @@ class _EncodedHandle:
         self.close()
 
 
+def join_plan(encoded, inputs=None):
+    """What dsa.Batch and Batch.joined_arrays take to put the parts of the inputs of an encode back together: (streams, groups,
+    encoded_mesh) -- the streams of the inputs (None: all of the call) one after the other, per input a group (first_mesh,
+    num_meshes) of the batch made from `streams`, and per mesh of that batch the stream of `encoded` it came from.  `encoded`: an
+    open EncodedStreams, or the handle of TryEncodeBatch(keep=True); an input that was refused is left out."""
+    h = getattr(encoded, "_h", None)
+    if h is None:
+        raise ValueError("join_plan takes an open encoded batch")
+    L = native.lib()
+    first, count = C.c_uint32(), C.c_uint32()
+    if inputs is None:
+        inputs = []
+        while L.dsa_encoded_parts(h, len(inputs), C.byref(first), C.byref(count)) == 0:
+            inputs.append(len(inputs))
+    streams, groups, encoded_mesh = [], [], []
+    p, ln = C.c_void_p(), C.c_size_t()
+    for i in inputs:
+        if L.dsa_encoded_parts(h, int(i), C.byref(first), C.byref(count)) != 0:
+            raise ValueError("no input %r" % (i,))
+        taken = []
+        for s in range(first.value, first.value + count.value):
+            if L.dsa_encoded_stream(h, s, C.byref(p), C.byref(ln)) != 0:
+                taken = None                     # a refused input keeps one slot, which returns its status
+                break
+            taken.append(C.string_at(p, ln.value))
+        if not taken:
+            continue
+        groups.append((len(streams), len(taken)))
+        encoded_mesh += range(first.value, first.value + count.value)
+        streams += taken
+    return streams, groups, np.asarray(encoded_mesh, np.uint32)
+
+
 def _entry_rows(ctx, handle, i):
     """dsa_encoded_entry_rows of mesh i for every attribute dsa_encoded_attributes counts."""
     L = native.lib()

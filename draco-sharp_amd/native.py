@@ -17,6 +17,7 @@ DSA_VA_ABSENT = 1                           # dsa_vertex_attribute.flags
 DSA_VA_INDICES_U16 = 1                      # dsa_mesh_vertex_arrays.flags
 VA_NONE = 0xFFFFFFFFFFFFFFFF                # an array that is not in the block
 DSA_SOURCE_ROWS_DEVICE_ONLY = C.c_size_t(-1).value      # dsa_batch_source_rows: dst NULL with this dst_bytes: no host copy
+DSA_JOIN_STREAM_ORDER, DSA_JOIN_INPUT_ORDER = 0, 1      # dsa_join_request.order
 
 # every symbol include/draco_mi355x.h declares
 EXPORTS = [
@@ -28,6 +29,7 @@ EXPORTS = [
     "dsa_batch_device_point_map", "dsa_batch_output_bytes", "dsa_batch_download", "dsa_batch_compact_bytes", "dsa_batch_download_compact", "dsa_batch_host_output", "dsa_batch_output_layout",
     "dsa_batch_vertex_arrays_bytes", "dsa_batch_vertex_arrays", "dsa_batch_vertex_arrays_layout", "dsa_batch_host_vertex_arrays", "dsa_batch_device_vertex_arrays",
     "dsa_batch_source_rows_bytes", "dsa_batch_source_rows", "dsa_batch_source_rows_layout", "dsa_batch_host_source_rows", "dsa_batch_device_source_rows",
+    "dsa_batch_joined_arrays_bytes", "dsa_batch_joined_arrays", "dsa_batch_joined_arrays_layout", "dsa_batch_joined_member", "dsa_batch_host_joined_arrays", "dsa_batch_device_joined_arrays",
     "dsa_host_alloc", "dsa_host_free", "dsa_host_register", "dsa_host_unregister", "dsa_batch_copy_metadata", "dsa_batch_copy_debug", "dsa_context_set_profiling", "dsa_batch_stage_times",
     "dsa_batch_kernel_times", "dsa_context_trim", "dsa_context_schedule_note",
     "dsa_encode_default_options", "dsa_encode_batch", "dsa_encode_batch_corners",
@@ -265,6 +267,21 @@ class MeshSourceRows(C.Structure):
     _fields_ = [("block", C.c_uint32), ("num_points", C.c_uint32), ("num_attributes", C.c_uint32), ("reserved", C.c_uint32), ("rows", C.c_uint64 * 16)]
 
 
+class JoinGroup(C.Structure):
+    """dsa_join_group: meshes first_mesh .. first_mesh + num_meshes of the batch."""
+    _fields_ = [("first_mesh", C.c_uint32), ("num_meshes", C.c_uint32)]
+
+
+class JoinRequest(C.Structure):
+    """dsa_join_request: arrays (as for dsa_batch_vertex_arrays), order (DSA_JOIN_STREAM_ORDER / DSA_JOIN_INPUT_ORDER)."""
+    _fields_ = [("arrays", VertexRequest), ("order", C.c_int32), ("reserved", C.c_uint32 * 7)]
+
+
+class JoinedArrays(C.Structure):
+    """dsa_joined_arrays: where the arrays of one group lie in the block of dsa_batch_joined_arrays."""
+    _fields_ = [("first_mesh", C.c_uint32), ("num_meshes", C.c_uint32), ("num_rows", C.c_uint32), ("order", C.c_int32), ("attributes", VertexAttribute * 16)]
+
+
 class AttributeInfo(C.Structure):
     _fields_ = [("attribute_type", C.c_int32), ("data_type", C.c_int32), ("num_components", C.c_int32),
                 ("normalized", C.c_int32), ("unique_id", C.c_uint32), ("num_entries", C.c_uint32),
@@ -343,6 +360,15 @@ def lib():
             for f in ("dsa_batch_host_source_rows", "dsa_batch_device_source_rows"):
                 getattr(L, f).restype = vp
                 getattr(L, f).argtypes = [vp, u32]
+        if hasattr(L, "dsa_batch_joined_arrays"):
+            L.dsa_batch_joined_arrays_bytes.restype = C.c_uint64
+            L.dsa_batch_joined_arrays_bytes.argtypes = [vp, C.POINTER(JoinRequest), u32, C.POINTER(JoinGroup)]
+            L.dsa_batch_joined_arrays.argtypes = [vp, C.POINTER(JoinRequest), u32, C.POINTER(JoinGroup), vp, vp, vp, C.c_size_t]
+            L.dsa_batch_joined_arrays_layout.argtypes = [vp, u32, C.POINTER(JoinedArrays)]
+            L.dsa_batch_joined_member.argtypes = [vp, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
+            for f in ("dsa_batch_host_joined_arrays", "dsa_batch_device_joined_arrays"):
+                getattr(L, f).restype = vp
+                getattr(L, f).argtypes = [vp]
         L.dsa_host_alloc.restype = vp
         L.dsa_host_alloc.argtypes = [C.c_size_t]
         L.dsa_host_free.restype = None

@@ -779,7 +779,7 @@ dsa_status dsa_encoded_row_entries(const dsa_encoded *encoded, uint32_t mesh, ui
  * faces cut); with merge_points = 1; a non-zero reserved word.  Refusals of the nested option structs keep their own words.
  * Not built: parts with merge_points = 1 (the number of kept points, and so of parts, is known only on the device; the merged call
  * already lowers nv there and the same step could size parts -- a follow-up), parts of sequential meshes, parts of the caller's
- * order (point_order = 0), a joined vertex-array layout of the parts on the decode side.
+ * order (point_order = 0).  (The parts as one array per attribute on the decode side: dsa_batch_joined_arrays.)
  * Added after ABI 4 without changing it: callers detect the feature by the symbol dsa_encode_split_sequential_batch. */
 #define DSA_ENCODE_MAX_PARTS 65536u        /* parts of one cloud */
 typedef struct dsa_encode_split_options {
@@ -827,7 +827,8 @@ dsa_status dsa_encoded_part_info(const dsa_encoded *encoded, uint32_t stream, ds
  * Fails the call with DSA_ERR_INVALID_ARGUMENT before any mesh is looked at, dsa_last_error naming the field: part_cells < 0;
  * part_cells >= 1 with merge_points != 1, with point_order != 1, with geometry != 0, with part_points != 0; a non-zero reserved
  * word.  Refusals of the nested option structs keep their own words.
- * Not built: parts of sequential meshes, parts of the caller's order, a joined vertex-array layout of the parts on the decode side.
+ * Not built: parts of sequential meshes, parts of the caller's order.  (The parts as one array per attribute on the decode side:
+ * dsa_batch_joined_arrays, in stream order.)
  * Added after ABI 4 without changing it: callers detect the feature by the symbol dsa_encode_cell_parts_sequential_batch. */
 typedef struct dsa_encode_cell_parts_options {
   dsa_encode_split_options split;          /* as for dsa_encode_split_sequential_batch, same legal values */
@@ -872,7 +873,8 @@ dsa_status dsa_encode_cell_parts_sequential_batch(dsa_context *ctx, uint32_t n, 
  * lod_base_bits > position_bits; lod_base_bits >= 1 with part_cells = 0, or without merge_points = 1 / point_order = 1 / geometry 0;
  * a non-zero reserved word.  Refusals of the nested option structs keep their own words.
  * Not built: a representative nearest the cell centre instead of first in Morton order; levels of sequential meshes; levels
- * without the merge; a joined decode-side layout of the levels.
+ * without the merge.  The joined decode-side layout of the levels, every level a prefix of one array per attribute, is
+ * dsa_batch_joined_arrays in stream order (below).
  * Added after ABI 4 without changing it: callers detect the feature by the symbol dsa_encode_lod_sequential_batch. */
 typedef struct dsa_encode_lod_options {
   dsa_encode_cell_parts_options cell_parts; /* as for dsa_encode_cell_parts_sequential_batch, same legal values */
@@ -963,6 +965,70 @@ dsa_status dsa_batch_source_rows(dsa_batch *batch, const dsa_encoded *encoded, c
 dsa_status dsa_batch_source_rows_layout(const dsa_batch *batch, uint32_t mesh, dsa_mesh_source_rows *out);
 const void *dsa_batch_host_source_rows(const dsa_batch *batch, uint32_t block);
 const void *dsa_batch_device_source_rows(const dsa_batch *batch, uint32_t block);
+/* Joined vertex arrays: the part streams of a cloud (part_points, merge_points + part_cells, lod_base_bits, mean_attributes cut one
+ * cloud into many ordinary streams) as ONE array per attribute and cloud.  A group names meshes first_mesh .. first_mesh + num_meshes
+ * of a decoded batch; a HIP kernel behind the decode (k_joined_arrays, dsa_joined_arrays.h) gathers the rows of all its members
+ * into the group's arrays, and one transfer downloads the block -- no concatenation per attribute and no inverse permutation on the
+ * host.  Shaped like dsa_batch_vertex_arrays and dsa_batch_source_rows.
+ *   Block: a function of the stream headers only.  Per group, in group order, each attribute of the members' common attribute table
+ *     gets one 64-byte aligned array of num_rows rows, num_rows = the sum of the members' header point counts.  Stride, data type,
+ *     components and the DSA_VA_ABSENT rules (the type mask; more than 16 bits in the quantised format) are those of
+ *     dsa_batch_vertex_arrays, and a row holds bit for bit what that call with the same `arrays` request puts in the member's own
+ *     array.  Meshes of the batch that are in no group get nothing.
+ *   order = DSA_JOIN_STREAM_ORDER: the rows of member 0, then member 1, ...; dsa_batch_joined_member says where a mesh's rows start.
+ *     Levels: given the members of a lod handle in slot order, level l is a prefix of every array -- rows [0, first_row of the first
+ *     member of level l + 1), the whole array for the last level: a caller slices by dsa_batch_joined_member and dsa_encoded_lod_info.
+ *   order = DSA_JOIN_INPUT_ORDER: row r is the point that carries row r of the arrays the encoder was given.  Needs `encoded`
+ *     (encoded_mesh as for dsa_batch_source_rows; NULL: stream i), a handle of a sequential call whose streams carry every input row
+ *     exactly once (point_order 0 or 1, part_points; not merge_points = 1).  The members of a group must be ALL parts of one input, in
+ *     part order (a handle without parts: one member per group).  The member's slice of the permutation is uploaded and the kernel
+ *     writes point p of member k to row perm[lo_k + p], a bijection onto 0 .. n - 1; a target at or beyond num_rows is skipped.
+ *     `encoded` must stay alive until dsa_batch_wait has returned.
+ *   When: wherever dsa_batch_vertex_arrays may be called, before dsa_batch_wait included; queued on the download stream behind the
+ *     batch's kernels with an event of its own that dsa_batch_wait waits for.  A download, vertex arrays and source rows may be
+ *     outstanding beside it; a second join request while one is in flight is refused; a new dsa_batch_decode invalidates the block.
+ *     dst == NULL: a pinned mirror of the library's, filled in one transfer (dsa_batch_host_joined_arrays); a dst of the caller's
+ *     (dsa_batch_joined_arrays_bytes; pinned for the link's full rate) receives the arrays alone, one transfer per array: bytes of
+ *     dst outside the reported arrays are left as they were; DSA_VA_DEVICE_ONLY transfers nothing
+ *     (dsa_batch_device_joined_arrays).  Batches a pool owns are const and take no request.
+ *   Fails the call with DSA_ERR_INVALID_ARGUMENT, dsa_last_error naming the field: a fault of `arrays`; order outside its values; a
+ *     non-zero reserved word; num_groups > 0 with groups == NULL; a group of 0 meshes or one reaching beyond the batch; a mesh in two
+ *     groups; DSA_JOIN_INPUT_ORDER without `encoded`, with a handle without rows, or with an Edgebreaker handle; a dst that is too
+ *     small.
+ *   A group fails alone -- its arrays stay reserved, what they hold is unspecified, dsa_batch_joined_arrays_layout returns the status
+ *     and a message that names the group and the member.  Known at the call, DSA_ERR_INVALID_ARGUMENT: a member has faces; members
+ *     differ in attribute count, or per attribute in type, data type, components or decoder type; the row sum is above 2^32 - 1; for
+ *     input order the members are not the parts of one input in order, the handle is merged, or a member's compressed length or
+ *     attribute count is not the named stream's.  Known behind the decode: a member failed to decode (the group gets its status); a
+ *     member is on decode_path 2 (DSA_ERR_INVALID_ARGUMENT: the join does not read the retry batch; no point-cloud stream this
+ *     library writes goes there); with DSA_VA_QUANTIZED a quantised attribute's (quantization_bits, min_values, range) differs
+ *     between members, compared as bit patterns -- one grid is what makes joined integers meaningful (DSA_VA_VALUES needs no such
+ *     check).
+ * Not in this call: joined index arrays of meshes; input order for merged handles (many rows share an entry: the caller gathers
+ * joined[row_entries]); members decoded a second time; a join across batches or pool jobs; glTF.
+ * Added after ABI 4 without changing it: callers detect the feature by the symbol dsa_batch_joined_arrays. */
+#define DSA_JOIN_STREAM_ORDER 0   /* rows of member 0, then member 1, ...: point p of member k is row first_row[k] + p */
+#define DSA_JOIN_INPUT_ORDER  1   /* row r is the point that carries row r of the arrays the encoder was given */
+typedef struct dsa_join_group { uint32_t first_mesh, num_meshes; } dsa_join_group;      /* meshes first_mesh .. + num_meshes of the batch */
+typedef struct dsa_join_request {
+  dsa_vertex_request arrays;      /* format, flags (DSA_VA_DEVICE_ONLY), attribute_types: exactly as for dsa_batch_vertex_arrays */
+  int32_t order;                  /* DSA_JOIN_* */
+  uint32_t reserved[7];           /* must be zero */
+} dsa_join_request;               /* 64 bytes */
+typedef struct dsa_joined_arrays {
+  uint32_t first_mesh, num_meshes, num_rows; int32_t order;
+  dsa_vertex_attribute attributes[DSA_MAX_ATTRIBUTES];
+} dsa_joined_arrays;              /* 400 bytes */
+/* Bytes of the block for this request (0: no batch, or a request the call would refuse). */
+uint64_t dsa_batch_joined_arrays_bytes(const dsa_batch *batch, const dsa_join_request *request, uint32_t num_groups, const dsa_join_group *groups);
+dsa_status dsa_batch_joined_arrays(dsa_batch *batch, const dsa_join_request *request, uint32_t num_groups, const dsa_join_group *groups,
+                                   const dsa_encoded *encoded, const uint32_t *encoded_mesh, void *dst, size_t dst_bytes);
+/* Where group `group`'s arrays lie in the block (after dsa_batch_wait; for the most recent request), or why it has none. */
+dsa_status dsa_batch_joined_arrays_layout(const dsa_batch *batch, uint32_t group, dsa_joined_arrays *out);
+/* The group of the most recent request mesh `mesh` is a member of, and its rows there in stream order. */
+dsa_status dsa_batch_joined_member(const dsa_batch *batch, uint32_t mesh, uint32_t *group, uint32_t *first_row, uint32_t *num_rows);
+const void *dsa_batch_host_joined_arrays(const dsa_batch *batch);       /* NULL until dsa_batch_wait has seen the transfer finish (always with DSA_VA_DEVICE_ONLY) */
+const void *dsa_batch_device_joined_arrays(const dsa_batch *batch);     /* valid until dsa_batch_free, the next dsa_batch_decode or the next request */
 uint32_t dsa_encoded_size(const dsa_encoded *encoded);
 /* Bytes of stream `mesh` (owned by `encoded`, valid until dsa_encoded_free) or that mesh's failure status. */
 dsa_status dsa_encoded_stream(const dsa_encoded *encoded, uint32_t mesh, const uint8_t **bytes, size_t *length);
