@@ -115,6 +115,13 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
     // rows.  Positions and normals carry no mean: a cloud whose mask names them, or an attribute it does not have, fails alone.
     // PartCells and LodBaseBits compose with it; EntryRows, RowEntries, PartInfo and LodInfo are unchanged.  Needs MergePoints 1.
     public uint MeanAttributes { get; set; }
+    // VoteAttributes (dsa_encode_vote_sequential_batch): the most frequent value of the cell WITH MergePoints, for labels -- a
+    // classification, an instance id, a return number -- whose mean is a class nobody assigned.  Bit a set: attribute a of the stream
+    // (counted as for MeanAttributes; 1 or 2 components) carries the tuple of coded integers that the most input rows of the cell
+    // have, among tuples of equally many rows the lexicographically smallest (signed components, component 0 first), whatever the
+    // order of the rows.  Positions, normals and attributes of 3 or 4 components are not voted on: a cloud whose mask names them, or
+    // an attribute it does not have, fails alone.  An attribute takes the vote or the mean, not both.  Needs MergePoints 1.
+    public uint VoteAttributes { get; set; }
     public struct PartBox
     {
         public uint Input, Part, Parts, FirstEntry, NumPoints, PositionBits;
@@ -232,6 +239,8 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
                 }
             }
             if (MeanAttributes != 0 && MergePoints != 1) throw new ArgumentException("MeanAttributes needs MergePoints 1: the mean is the mean over the points of a cell");
+            if (VoteAttributes != 0 && MergePoints != 1) throw new ArgumentException("VoteAttributes needs MergePoints 1: the vote is a vote of the points of a cell");
+            if ((VoteAttributes & MeanAttributes) != 0) throw new ArgumentException("VoteAttributes and MeanAttributes share a bit: an attribute carries the most frequent value of its cell or the mean, not both");
             if (LodBaseBits != 0 && PartCells == 0) throw new ArgumentException("LodBaseBits needs PartCells >= 1: every level is cut into parts of at most PartCells points");
             if (PartPoints != 0 || PartCells != 0)
             {
@@ -243,7 +252,18 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
                 po.PartPoints = PartPoints;
                 var ain = new DsaMeshAttrInput[items.Count];
                 for (int i = 0; i < items.Count; ++i) { ain[i].Mesh.Mesh = inputs[i]; Extras(items[i], null, (uint)items[i].PointsCount, ref ain[i], pins); }
-                if (MeanAttributes != 0)        // (the widest call only when its option is set)
+                if (VoteAttributes != 0)        // (the widest call only when its option is set)
+                {
+                    NativeMethods.dsa_encode_default_vote_options(out var vo);
+                    vo.Mean.Lod.CellParts.Split = po;
+                    vo.Mean.Lod.CellParts.PartCells = PartCells;
+                    vo.Mean.Lod.LodBaseBits = LodBaseBits;
+                    vo.Mean.MeanAttributes = MeanAttributes;
+                    vo.VoteAttributes = VoteAttributes;
+                    fixed (DsaMeshAttrInput* p = ain)
+                        NativeMethods.Check(NativeMethods.dsa_encode_vote_sequential_batch(_ctx, (uint)items.Count, p, null, in vo, out encoded), _ctx, "dsa_encode_vote_sequential_batch");
+                }
+                else if (MeanAttributes != 0)   // (the widest call only when its option is set)
                 {
                     NativeMethods.dsa_encode_default_mean_options(out var eo);
                     eo.Lod.CellParts.Split = po;
@@ -320,7 +340,16 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
                 mo.MergePoints = MergePoints;
                 var ain = new DsaMeshAttrInput[items.Count];
                 for (int i = 0; i < items.Count; ++i) { ain[i].Mesh.Mesh = inputs[i]; Extras(items[i], null, (uint)items[i].PointsCount, ref ain[i], pins); }
-                if (MeanAttributes != 0)        // (the widest call only when its option is set)
+                if (VoteAttributes != 0)        // (the widest call only when its option is set)
+                {
+                    NativeMethods.dsa_encode_default_vote_options(out var vo);
+                    vo.Mean.Lod.CellParts.Split.Merge = mo;
+                    vo.Mean.MeanAttributes = MeanAttributes;
+                    vo.VoteAttributes = VoteAttributes;
+                    fixed (DsaMeshAttrInput* p = ain)
+                        NativeMethods.Check(NativeMethods.dsa_encode_vote_sequential_batch(_ctx, (uint)items.Count, p, null, in vo, out encoded), _ctx, "dsa_encode_vote_sequential_batch");
+                }
+                else if (MeanAttributes != 0)   // (the widest call only when its option is set)
                 {
                     NativeMethods.dsa_encode_default_mean_options(out var eo);
                     eo.Lod.CellParts.Split.Merge = mo;

@@ -313,6 +313,15 @@ internal unsafe struct DsaEncodeMeanOptions
     public fixed int Reserved[7];   // zero
 }
 
+// dsa_encode_vote_options (dsa_encode_vote_sequential_batch)
+[StructLayout(LayoutKind.Sequential)]
+internal unsafe struct DsaEncodeVoteOptions
+{
+    public DsaEncodeMeanOptions Mean;
+    public uint VoteAttributes;     // 0: the request of the mean call; bit a: attribute a of the stream (1 or 2 components) carries the most frequent value of its cell's rows (needs MergePoints 1)
+    public fixed int Reserved[7];   // zero
+}
+
 // dsa_lod_info (dsa_encoded_lod_info)
 [StructLayout(LayoutKind.Sequential)]
 internal unsafe struct DsaLodInfo
@@ -486,6 +495,8 @@ internal static unsafe partial class NativeMethods
     [DllImport(Lib)] internal static extern DsaStatus dsa_encoded_lod_info(IntPtr encoded, uint stream, out DsaLodInfo info);
     [DllImport(Lib)] internal static extern void dsa_encode_default_mean_options(out DsaEncodeMeanOptions options);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_mean_sequential_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, in DsaEncodeMeanOptions options, out IntPtr encoded);
+    [DllImport(Lib)] internal static extern void dsa_encode_default_vote_options(out DsaEncodeVoteOptions options);
+    [DllImport(Lib)] internal static extern DsaStatus dsa_encode_vote_sequential_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, in DsaEncodeVoteOptions options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encoded_parts(IntPtr encoded, uint input, out uint firstStream, out uint count);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encoded_part_info(IntPtr encoded, uint stream, out DsaPartInfo info);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_rows_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, DsaMeshAttributeCorners* corners, in DsaEncodeRowsOptions options, out IntPtr encoded);

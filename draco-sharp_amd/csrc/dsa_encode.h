@@ -35,6 +35,8 @@
 //                                                level in parts: levels, scan, scatter, row entries and the slots, in place of k_enc_part_cells
 //                              k_enc_mean_*      dsa_encode_mean_sequential_batch, mean_attributes != 0: the mean of the cell into the masked
 //                                                attributes' integers at every kept row, behind the merge
+//                              k_enc_vote_*      dsa_encode_vote_sequential_batch, vote_attributes != 0: the most frequent tuple of the cell
+//                                                into the voted attributes' integers at every kept row, beside the means
 //         (dsa_encode_layout.h) the request of an entry point, the state of a chunk, the per-mesh checks and plans, the arena layout
 // Every entry point fills an EncRequest and calls encode_request; a chunk of it goes through the stages of encode_chunk (or of
 // encode_sequential_chunk, dsa_encode_sequential.h) on a lane.
@@ -1252,6 +1254,8 @@ static dsa_status enc_stage_attributes(dsa_context *ctx, EncLane &lane, EncChunk
   ENC_TRY(hipMemcpyAsync(L.streams.data(), d_streams, sizeof(dsa::EncStream) * ns, hipMemcpyDeviceToHost, st));
   if (device_conn) ENC_TRY(hipMemcpyAsync(L.conns.data(), d_conns, sizeof(dsa::EncConn) * n, hipMemcpyDeviceToHost, st));
   if (nz) ENC_TRY(hipMemcpyAsync(L.seams.data(), d_seams, sizeof(dsa::EncSeam) * nz, hipMemcpyDeviceToHost, st));
+  // vote_attributes: the records of the voted streams, for EncVote::full (enc_vote_refusals)
+  if (!L.votes.empty()) ENC_TRY(hipMemcpyAsync(L.votes.data(), arena + L.votes_at, sizeof(dsa::EncVote) * L.votes.size(), hipMemcpyDeviceToHost, st));
   ENC_TRY(hipStreamSynchronize(st));
   if (order_timing) order_lap("gather to entropy coding");
   return DSA_OK;
@@ -1340,6 +1344,19 @@ static void enc_quantiser_refusals(EncChunk &ck) {
     }
   }
 }
+// vote_attributes: a voted stream whose table k_enc_vote_count found full (EncVote::full; it cannot be at two slots a point): its
+// cloud fails alone, nothing is coded from it
+static void enc_vote_refusals(EncChunk &ck) {
+  for (size_t k = 0; k < ck.L.votes.size(); ++k) {
+    if (!ck.L.votes[k].full) continue;
+    const uint32_t s = ck.L.vote_stream[k], i = (uint32_t)ck.stream_mesh[s];
+    if (!ck.good(i)) continue;
+    char buf[160];
+    snprintf(buf, sizeof(buf), "internal error: the vote table of attribute %u (vote_attributes 0x%x, %u slots) was found full", s - ck.L.first_stream[i], ck.rq.vote_attributes, ck.L.votes[k].cap);
+    ck.refuse(i, DSA_ERR_DEVICE, buf);
+    for (uint32_t t = ck.L.first_stream[i]; t < ck.L.first_stream[i + 1]; ++t) ck.L.streams[t].overflow = 1;
+  }
+}
 // host phase 2 and device phase 2, shared with encode_sequential_chunk: scheme choice and rANS tables from the device statistics
 // (by the host, or what k_enc_plan said), then the entropy coding and its downloads; `lap`, when given, between the two
 static dsa_status enc_stage_code(dsa_context *ctx, EncLane &lane, EncChunk &ck, EncLap *lap) {
@@ -1347,6 +1364,7 @@ static dsa_status enc_stage_code(dsa_context *ctx, EncLane &lane, EncChunk &ck, 
   ck.splans.resize(ns); ck.stream_mesh.assign(ns, 0);
   for (uint32_t i = 0; i < ck.n; ++i) for (uint32_t s = ck.L.first_stream[i]; s < ck.L.first_stream[i + 1]; ++s) ck.stream_mesh[s] = (int)i;
   enc_quantiser_refusals(ck);
+  enc_vote_refusals(ck);
   if (ck.host_plan) ENC_STAGE(enc_host_plans(ctx, lane, ck));
   else enc_device_plan_errors(ck);
   if (lap) (*lap)("histograms + symbol plans");
@@ -1550,6 +1568,15 @@ static dsa_status enc_check_options(dsa_context *ctx, const dsa_encode_mean_opti
   if (o.mean_attributes >> DSA_MAX_ATTRIBUTES) ENC_REFUSE("mean_attributes 0x%x: a bit at or above %d (DSA_MAX_ATTRIBUTES) names no attribute of a stream", (unsigned)o.mean_attributes, (int)DSA_MAX_ATTRIBUTES);
   ENC_RESERVED(o, 7, "dsa_encode_mean_options");
   return enc_check_options(ctx, o.lod, null_argument);
+}
+// ... or with the most frequent value of the cell in the voted attributes of the kept points (dsa_encode_order.h)
+static dsa_status enc_check_options(dsa_context *ctx, const dsa_encode_vote_options &o, bool null_argument) {
+  const dsa_encode_merge_options &m = o.mean.lod.cell_parts.split.merge;
+  if (o.vote_attributes != 0 && m.merge_points != 1) ENC_REFUSE("vote_attributes 0x%x needs merge_points 1 (it was %d): the vote is a vote of the points of a cell", (unsigned)o.vote_attributes, (int)m.merge_points);
+  if (o.vote_attributes >> DSA_MAX_ATTRIBUTES) ENC_REFUSE("vote_attributes 0x%x: a bit at or above %d (DSA_MAX_ATTRIBUTES) names no attribute of a stream", (unsigned)o.vote_attributes, (int)DSA_MAX_ATTRIBUTES);
+  if (o.vote_attributes & o.mean.mean_attributes) ENC_REFUSE("vote_attributes 0x%x and mean_attributes 0x%x share a bit: an attribute carries the most frequent value of its cell or the mean, not both", (unsigned)o.vote_attributes, (unsigned)o.mean.mean_attributes);
+  ENC_RESERVED(o, 7, "dsa_encode_vote_options");
+  return enc_check_options(ctx, o.mean, null_argument);
 }
 #undef ENC_RESERVED
 #undef ENC_REFUSE
@@ -1819,8 +1846,9 @@ static dsa_status encode_edgebreaker(dsa_context *ctx, uint32_t n, const dsa_mes
   rq.track_rows = w.track_rows == 1;
   return encode_checked(ctx, rq, grids, o.grid.repair.topology == 1, out);
 }
-static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_mean_options &a, dsa_encoded **out) {
-  if (enc_check_options(ctx, a, !ctx || !out || (n && !meshes)) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_vote_options &v, dsa_encoded **out) {
+  if (enc_check_options(ctx, v, !ctx || !out || (n && !meshes)) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+  const dsa_encode_mean_options &a = v.mean;
   const dsa_encode_lod_options &l = a.lod;
   const dsa_encode_cell_parts_options &c = l.cell_parts;
   const dsa_encode_split_options &s = c.split;
@@ -1829,10 +1857,16 @@ static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh
   EncRequest rq;
   rq.n = n; rq.meshes = meshes; rq.sequential = true;
   rq.seq = o.sequential; rq.point_order = o.point_order == 1; rq.merge_points = m.merge_points == 1; rq.part_points = (uint32_t)s.part_points; rq.part_cells = (uint32_t)c.part_cells; rq.lod_base_bits = (uint32_t)l.lod_base_bits;
-  rq.mean_attributes = a.mean_attributes;
+  rq.mean_attributes = a.mean_attributes; rq.vote_attributes = v.vote_attributes;
   const dsa_status st = encode_checked(ctx, rq, grids, false, out);
   if (st == DSA_OK && rq.lod()) (*out)->lod_bits = rq.lod_base_bits;
   return st;
+}
+static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_mean_options &a, dsa_encoded **out) {
+  dsa_encode_vote_options v;
+  dsa_encode_default_vote_options(&v);
+  v.mean = a;
+  return encode_sequential(ctx, n, meshes, grids, v, out);
 }
 static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_lod_options &l, dsa_encoded **out) {
   dsa_encode_mean_options a;
@@ -1933,6 +1967,11 @@ void dsa_encode_default_mean_options(dsa_encode_mean_options *o) {
   if (!o) return;
   memset(o, 0, sizeof(*o));
   dsa_encode_default_lod_options(&o->lod);
+}
+void dsa_encode_default_vote_options(dsa_encode_vote_options *o) {
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  dsa_encode_default_mean_options(&o->mean);
 }
 void dsa_encode_default_repair_options(dsa_encode_repair_options *o) {
   if (!o) return;
@@ -2068,6 +2107,11 @@ dsa_status dsa_encode_lod_sequential_batch(dsa_context *ctx, uint32_t n, const d
 // mean_attributes = 0 is the very request of the call above.
 dsa_status dsa_encode_mean_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_mean_options *options, dsa_encoded **out) {
   DSA_GUARD(ctx, [&] { dsa_encode_mean_options o; dsa_encode_default_mean_options(&o); if (options) o = *options; return encode_sequential(ctx, n, meshes, grids, o, out); }());
+}
+// ... or, with vote_attributes != 0, the most frequent value of the cell in the voted attributes of every kept point (k_enc_vote_*,
+// dsa_encode_order.h); vote_attributes = 0 is the very request of the call above, which arrives here.
+dsa_status dsa_encode_vote_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_vote_options *options, dsa_encoded **out) {
+  DSA_GUARD(ctx, [&] { dsa_encode_vote_options o; dsa_encode_default_vote_options(&o); if (options) o = *options; return encode_sequential(ctx, n, meshes, grids, o, out); }());
 }
 
 struct dsa_welded {

@@ -2147,6 +2147,34 @@ static void merge_means(const int32_t *q, uint32_t n, int nc, const std::vector<
     for (int c = 0; c < nc; ++c) means[(size_t)j * nc + c] = cell_mean(sum[(size_t)j * nc + c], cnt[j]);
   }
 }
+// The most frequent value of every cell in an attribute of the kept points (dsa_encode_vote_sequential_batch, a bit of
+// vote_attributes; the device's kernels are k_enc_vote_* of dsa_encode_order.h, with which this shares nothing): q, row_entries and m as
+// merge_means takes them, nc 1 or 2; votes[m * nc], entry j the tuple (q[r][0], .., q[r][nc - 1]) that the most rows r of cell j
+// have, among tuples with equally many rows the lexicographically smallest (signed components, component 0 first).  By a sort of
+// every cell's tuples: equal tuples are adjacent, the first longest run of the ascending order wins.
+static void merge_votes(const int32_t *q, uint32_t n, int nc, const std::vector<uint32_t> &row_entries, uint32_t m, std::vector<int32_t> &votes) {
+  check(q != nullptr && n > 0 && nc >= 1 && nc <= 2 && row_entries.size() == n, "merge_votes: n rows of 1 - 2 integers and their row entries");
+  std::vector<std::vector<std::pair<int32_t, int32_t>>> of(m);
+  for (uint32_t r = 0; r < n; ++r) {
+    check(row_entries[r] < m, "merge_votes: a row entry at or above m");
+    of[row_entries[r]].push_back({q[(size_t)r * nc], nc == 2 ? q[(size_t)r * nc + 1] : 0});
+  }
+  votes.resize((size_t)m * nc);
+  for (uint32_t j = 0; j < m; ++j) {
+    std::vector<std::pair<int32_t, int32_t>> &t = of[j];
+    check(!t.empty(), "merge_votes: a cell without rows");
+    std::sort(t.begin(), t.end());
+    size_t best = 0, best_len = 0;
+    for (size_t a = 0; a < t.size();) {
+      size_t b = a;
+      while (b < t.size() && t[b] == t[a]) ++b;
+      if (b - a > best_len) { best = a; best_len = b - a; }
+      a = b;
+    }
+    votes[(size_t)j * nc] = t[best].first;
+    if (nc == 2) votes[(size_t)j * nc + 1] = t[best].second;
+  }
+}
 // The sorted order of a cloud in parts of at most part_points points (dsa_encode_split_sequential_batch, part_points >= 1): P =
 // ceil(n / part_points) parts, part p sorted entries [floor(p n / P), floor((p + 1) n / P)), in 64 bits -- 1 .. part_points points
 // each, sizes that differ by at most one.  part_points 0: one part.

@@ -251,6 +251,8 @@ struct EncRequest {
   uint32_t lod_levels() const { return lod() ? (uint32_t)seq.base.position_bits - lod_base_bits + 1u : 1u; }      // L (D <= position_bits: enc_check_options)
   uint32_t mean_attributes = 0;            // dsa_encode_mean_sequential_batch (with merge_points): bit a: attribute a of the stream carries the mean of its cell (k_enc_mean_*)
   bool means() const { return merged() && seq.geometry == 0 && mean_attributes != 0; }
+  uint32_t vote_attributes = 0;            // dsa_encode_vote_sequential_batch (with merge_points): bit a: attribute a of the stream carries the most frequent value of its cell (k_enc_vote_*)
+  bool votes() const { return merged() && seq.geometry == 0 && vote_attributes != 0; }
   int rows_kind() const { return weld_sink ? dsa_encoded::ROWS_NONE : (sequential ? (point_order ? dsa_encoded::ROWS_ORDERED : dsa_encoded::ROWS_LINEAR) : (track_rows ? dsa_encoded::ROWS_TRACKED : dsa_encoded::ROWS_NONE)); }
   dsa_encode_level_options level{};        // Edgebreaker streams
   dsa_encode_sequential_options seq{};     // sequential streams
@@ -330,6 +332,14 @@ struct EncLayout {
   std::vector<uint32_t> mean_stream;
   uint64_t mean_clouds_at = 0, means_at = 0, mean_zero_at = 0, mean_zero_bytes = 0;
   uint32_t mean_most = 0;                   // the most masked streams a cloud of the chunk has: the y of the mean kernels' grid
+  // EncRequest::votes: likewise a record per cloud (parallel to `ord`) and per voted stream among the uploads; vote_stream[k] the stream
+  // of record k; tables, counts and values are one range of the arena behind the means', zeroed on the stream in front of
+  // k_enc_vote_count.  The records come back behind the stage: EncVote::full (enc_vote_refusals)
+  std::vector<dsa::EncVoteCloud> vote_clouds;
+  std::vector<dsa::EncVote> votes;
+  std::vector<uint32_t> vote_stream;
+  uint64_t vote_clouds_at = 0, votes_at = 0, vote_zero_at = 0, vote_zero_bytes = 0;
+  uint32_t vote_most = 0;                   // the most voted streams a cloud of the chunk has: the y of the vote kernels' grid
 };
 
 // ---- the point-order stage of a chunk whose layout has order records (dsa_encode_order.h has the kernels and their contracts): the
@@ -346,7 +356,7 @@ template <class Launch, class Zero, class After>
 static inline bool enc_order_stage(Launch &&launch, Zero &&zero, After &&after, const EncLayout &L, bool meshes, uint32_t gx_faces,
                                    uint8_t *arena, dsa::EncStream *streams, uint32_t ns) {
   const uint32_t nc = (uint32_t)L.ord.size(), nt = (uint32_t)L.ord_tiles.size(), np = (uint32_t)L.parts.size(), npt = (uint32_t)L.part_tiles.size();
-  const uint32_t nm = (uint32_t)L.means.size(), wave = (uint32_t)WAVE;
+  const uint32_t nm = (uint32_t)L.means.size(), nv = (uint32_t)L.votes.size(), wave = (uint32_t)WAVE;
   if (nc == 0 || nt == 0) return true;
   dsa::EncOrder *clouds = (dsa::EncOrder *)(arena + L.ord_at);
   const dsa::EncOrderTile *tiles = (const dsa::EncOrderTile *)(arena + L.ord_tiles_at);
@@ -354,6 +364,8 @@ static inline bool enc_order_stage(Launch &&launch, Zero &&zero, After &&after, 
   const dsa::EncPartTile *part_tiles = (const dsa::EncPartTile *)(arena + L.part_tiles_at);
   const dsa::EncMeanCloud *mclouds = (const dsa::EncMeanCloud *)(arena + L.mean_clouds_at);
   const dsa::EncMean *means = (const dsa::EncMean *)(arena + L.means_at);
+  const dsa::EncVoteCloud *vclouds = (const dsa::EncVoteCloud *)(arena + L.vote_clouds_at);
+  dsa::EncVote *votes = (dsa::EncVote *)(arena + L.votes_at);
   // the permutation of every cloud, behind the quantisers and in front of the gather
   launch(dsa::k_enc_order_keys, nt, 1u, 256u, arena, clouds, tiles, nt);
   for (uint32_t p = 0; p < L.ord_passes; ++p) {
@@ -377,6 +389,16 @@ static inline bool enc_order_stage(Launch &&launch, Zero &&zero, After &&after, 
       launch(dsa::k_enc_mean_store, nt, L.mean_most, 256u, arena, clouds, tiles, nt, mclouds, means, nm);
     }
     if (!after("cell means")) return false;
+  }
+  if (!L.votes.empty()) {      // vote_attributes: the most frequent tuple of the cell into vals at every kept row, beside the means (other streams), in front of the same readers
+    zero(L.vote_zero_at, L.vote_zero_bytes);
+    if (L.vote_most) {
+      launch(dsa::k_enc_vote_count, nt, L.vote_most, wave, arena, clouds, tiles, nt, vclouds, votes, nv);
+      launch(dsa::k_enc_vote_best, nt, L.vote_most, 256u, arena, clouds, tiles, nt, vclouds, (const dsa::EncVote *)votes, nv, 0u);
+      launch(dsa::k_enc_vote_best, nt, L.vote_most, 256u, arena, clouds, tiles, nt, vclouds, (const dsa::EncVote *)votes, nv, 1u);
+      launch(dsa::k_enc_vote_store, nt, L.vote_most, 256u, arena, clouds, tiles, nt, vclouds, (const dsa::EncVote *)votes, nv);
+    }
+    if (!after("cell votes")) return false;
   }
   if (L.lod && np) {           // lod_base_bits: the kept order by (level, kept); the slot sizer below cuts every level into its parts
     launch(dsa::k_enc_lod_levels, nt, 1u, wave, arena, clouds, tiles, nt);
@@ -723,6 +745,19 @@ static void enc_check_sequential_mesh(EncChunk &ck, uint32_t i) {
       return ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, buf);
     }
   }
+  if (ck.rq.votes()) {       // vote_attributes: every set bit names an attribute of this cloud's stream whose tuples can be voted on
+    const std::vector<synth::PortableAttr> &atts = ck.plans[i].atts;
+    char buf[240];
+    for (uint32_t a = 0; a < 32u; ++a) {
+      if (!((ck.rq.vote_attributes >> a) & 1u)) continue;
+      if (a >= atts.size()) snprintf(buf, sizeof(buf), "vote_attributes 0x%x: bit %u names attribute %u of the stream, which has %zu attributes", ck.rq.vote_attributes, a, a, atts.size());
+      else if (a == 0) snprintf(buf, sizeof(buf), "vote_attributes 0x%x: bit 0 names attribute 0, the positions: they are equal inside a cell and are never voted on", ck.rq.vote_attributes);
+      else if (atts[a].seq_type == 3) snprintf(buf, sizeof(buf), "vote_attributes 0x%x: bit %u names attribute %u, the normals: a vote over octahedral integers is not built", ck.rq.vote_attributes, a, a);
+      else if (atts[a].nc > 2) snprintf(buf, sizeof(buf), "vote_attributes 0x%x: bit %u names attribute %u of %d components: only tuples of 1 or 2 components, which pack into 64 bits, are built", ck.rq.vote_attributes, a, a, (int)atts[a].nc);
+      else continue;
+      return ck.refuse(i, DSA_ERR_INVALID_ARGUMENT, buf);
+    }
+  }
   if (!ck.rq.split()) return;
   // (lod_base_bits: a level more can cost a slot more -- sum ceil(m_l / N) <= ceil(m / N) + non-empty levels - 1)
   const uint64_t parts = synth::split_count(m.num_vertices, ck.rq.part_size()) + (ck.rq.lod_levels() - 1u);
@@ -1012,6 +1047,9 @@ static void enc_layout(EncChunk &ck) {
 // EncRequest::means (merge with mean_attributes): an EncMeanCloud per cloud and an EncMean per masked stream among the uploads; behind
 // every other region a u32[n] count region per cloud and an i64[n nc] sum region per masked stream, one range that is zeroed on the
 // stream in front of k_enc_mean_sum.  No region is reused and nothing else grows.
+// EncRequest::votes (merge with vote_attributes): likewise an EncVoteCloud per cloud and an EncVote per voted stream among the uploads;
+// behind the means' range per voted stream a table of 2 n slots of 8 bytes (a crowded chunk of small clouds pays for its points, not
+// for tiles), u32[n] counts and u64[n] values, one range that is zeroed on the stream in front of k_enc_vote_count.
 static void enc_layout_sequential(EncChunk &ck) {
   EncLayout &L = ck.L;
   const bool is_mesh = ck.rq.seq.geometry == 1, compressed = is_mesh && ck.rq.seq.compress_connectivity == 1, ordered = ck.rq.point_order;
@@ -1054,6 +1092,21 @@ static void enc_layout_sequential(EncChunk &ck) {
         L.mean_most = std::max(L.mean_most, MC.count);
         L.mean_clouds.push_back(MC);
       }
+      if (ck.rq.votes()) {                                     // the voted streams of the cloud (the first part's, as above)
+        dsa::EncVoteCloud VC;
+        memset(&VC, 0, sizeof(VC));
+        VC.first = (uint32_t)L.votes.size();
+        for (uint32_t k = 1; k < atts.size() && k < 32u; ++k) {
+          if (!((ck.rq.vote_attributes >> k) & 1u)) continue;
+          dsa::EncVote X;
+          memset(&X, 0, sizeof(X));
+          X.nc = L.streams[s0 + k].nc; X.cap = 2u * V;         // (V <= 2^28: enc_check_sequential_mesh)
+          L.votes.push_back(X); L.vote_stream.push_back(s0 + k);
+          ++VC.count;
+        }
+        L.vote_most = std::max(L.vote_most, VC.count);
+        L.vote_clouds.push_back(VC);
+      }
       for (uint32_t t = 0; t < O.tiles; ++t) L.ord_tiles.push_back({(uint32_t)L.ord.size(), t});
       if (split) {                                             // the parts of the cloud: their sizes need nothing of the device
         L.part_of_mesh[i] = (uint32_t)L.parts.size();
@@ -1089,6 +1142,10 @@ static void enc_layout_sequential(EncChunk &ck) {
   if (!L.means.empty()) {
     L.mean_clouds_at = A.put(L.uploads, L.mean_clouds.data(), sizeof(dsa::EncMeanCloud) * L.mean_clouds.size(), false);
     L.means_at = A.put(L.uploads, L.means.data(), sizeof(dsa::EncMean) * L.means.size(), false);
+  }
+  if (!L.votes.empty()) {
+    L.vote_clouds_at = A.put(L.uploads, L.vote_clouds.data(), sizeof(dsa::EncVoteCloud) * L.vote_clouds.size(), false);
+    L.votes_at = A.put(L.uploads, L.votes.data(), sizeof(dsa::EncVote) * L.votes.size(), false);
   }
   if (!L.parts.empty()) {
     L.parts_at = A.put(L.uploads, L.parts.data(), sizeof(dsa::EncPart) * L.parts.size(), false);
@@ -1142,6 +1199,16 @@ static void enc_layout_sequential(EncChunk &ck) {
       for (uint32_t k = MC.first; k < MC.first + MC.count; ++k) { dsa::EncMean &M = L.means[k]; M.vals = L.streams[L.mean_stream[k]].vals; M.acc = A.take(8ull * V * M.nc); }
     }
     L.mean_zero_bytes = A.cur - L.mean_zero_at;
+  }
+  if (!L.votes.empty()) {                                      // the table, the counts and the values of every voted stream: one range behind the means', zeroed as one
+    L.vote_zero_at = A.cur;
+    for (size_t k = 0; k < L.votes.size(); ++k) {
+      dsa::EncVote &X = L.votes[k];
+      const uint64_t V = X.cap / 2u;
+      X.vals = L.streams[L.vote_stream[k]].vals;
+      X.table = A.take(8ull * X.cap); X.best_cnt = A.take(4ull * V); X.best_val = A.take(8ull * V);
+    }
+    L.vote_zero_bytes = A.cur - L.vote_zero_at;
   }
   L.total_bytes = A.cur;
 }

@@ -152,6 +152,37 @@
 // kernel above.  The host coder's twin is synth::merge_means; tests/hostcheck/encmeans_host.cpp runs the serial forms in the
 // product's layout against it, tests/test_gpu_encode_means.py the ballots, shuffles and atomics.
 // gfx950, hipcc -O3 (VGPR / SGPR / LDS bytes per block): k_enc_mean_sum 24 / 45 / 0, store 23 / 29 / 0; no scratch, no spills, 8 waves per SIMD.
+//
+// dsa_encode_vote_sequential_batch with vote_attributes != 0 (point clouds, merge_points = 1): entry j of a voted attribute of nc <= 2
+// components carries the tuple (q[r][0], .., q[r][nc - 1]) that the most rows r of cell j have, among tuples of equally many rows the
+// lexicographically smallest one (components as signed 32-bit integers, component 0 first) -- a function of the set of rows.  As the
+// mean, the winner is written into the stream's `vals` at row kept[j], behind the merge and beside the mean kernels (the two masks
+// share no attribute), in front of k_enc_lod_*, k_enc_part_cells, k_enc_part_bounds and k_enc_gather, on the merge's (cloud, tile)
+// list with the cloud's voted streams in blockIdx.y; launched only when the chunk has a voted stream.  No sort:
+//   k_enc_vote_count      a wave per (tile, voted stream), 64 sorted entries a step: the rows of every distinct (cell, tuple) counted
+//                         in an open-addressing table of the stream, cap >= 2 n slots of (representative row + 1, count), 0 = empty.
+//                         A slot is claimed by one 32-bit atomicCAS of the row; a later row compares its own (cells[r], tuple) with
+//                         the representative's, read from cells and vals, which nothing writes during this step, and on a match
+//                         adds to the slot's count, else goes on to the next slot (linear probing from a hash of cell and tuple; at
+//                         most cap probes, no lane waits for another).  Which row represents a tuple and which slot it lands in
+//                         depend on arrival; the count of every (cell, tuple) does not.  Inside the wave first: the lanes of a
+//                         (run, step) whose tuple equals that of the run's first lane of the step (the head ballot of
+//                         k_enc_mean_sum, one shuffle, one ballot) make ONE insert with their popcount, the other lanes insert
+//                         singly -- a cell of a million equal labels costs one atomic a step, not one a row.  A table found full
+//                         (it cannot be at load <= 1/2) sets EncVote::full, and the host fails the cloud alone.
+//   k_enc_vote_best       a thread per slot, two launches: phase 0 atomicMax(best_cnt[j], count); phase 1, for the slots whose
+//                         count equals best_cnt[j], atomicMax(best_val[j], ~pack), pack = component 0 with the sign bit flipped in
+//                         the high word and component 1 likewise in the low word (nc = 1: component 0 alone, in the low word): the
+//                         maximum of ~pack is the minimum of pack, and it starts from the zero the one memset leaves.  Maximum
+//                         commutes: no atomic decides a value.
+//   k_enc_vote_store      a thread per kept entry, tiles over KEPT entries: vals[nc kept[j] + c] from ~best_val[j]; a cell of one
+//                         row keeps its value (its tuple wins).
+// The tables (u32[2 cap] per voted stream), best_cnt (u32[n]) and best_val (u64[n]) are regions of their own at the end of the arena,
+// behind the means', one range that one memset on the stream zeroes in front of the count; no region is reused.  The records are
+// EncVote / EncVoteCloud, among the uploads: EncOrder, EncMean and every kernel above are as they were.  The host coder's twin is
+// synth::merge_votes (a sort of every cell's tuples); tests/hostcheck/encvotes_host.cpp runs the serial forms in the product's layout
+// against it, tests/test_gpu_encode_votes.py the ballots, shuffles and atomics.
+// gfx950, hipcc -O3 (VGPR / SGPR / LDS bytes per block): k_enc_vote_count 28 / 52 / 0, best 16 / 50 / 0, store 9 / 30 / 0; no scratch, no spills, 8 waves per SIMD.
 #pragma once
 #include <stdint.h>
 
@@ -196,6 +227,15 @@ struct EncLodTable { uint32_t count[ORD_LOD_LEVELS], base[ORD_LOD_LEVELS]; };   
 // mean_attributes: records of the mean kernels' own, so that EncOrder and the kernels that index it stay as they are
 struct EncMean { uint64_t vals, acc; uint32_t nc, pad; };       // one per masked stream, a cloud's side by side: the stream's vals i32[n nc], its sums i64[n nc], its components
 struct EncMeanCloud { uint64_t cnt; uint32_t first, count; };   // one per EncOrder record: the rows of every cell u32[n]; its `count` EncMean records from `first` on (0: none)
+// vote_attributes: records of the vote kernels' own, beside the means'
+struct EncVote {                   // one per voted stream, a cloud's side by side
+  uint64_t vals;                   // the stream's vals i32[n nc]
+  uint64_t table;                  // u32[2 cap]: slot s = (representative row + 1, rows counted); zeroed in front of k_enc_vote_count
+  uint64_t best_cnt, best_val;     // u32[n] the most rows a tuple of cell j has; u64[n] the largest ~pack among the tuples with so many
+  uint32_t nc, cap;                // components (1 or 2); slots, >= 2 n
+  uint32_t full, pad;              // OUTPUT: not 0: a row found no slot (never at cap >= 2 n)
+};
+struct EncVoteCloud { uint32_t first, count; };                 // one per EncOrder record: its `count` EncVote records from `first` on (0: none)
 
 static inline uint32_t enc_order_passes(uint32_t bits) { return (3u * bits + 7u) / 8u; }
 
@@ -551,6 +591,153 @@ __global__ __launch_bounds__(256) void k_enc_mean_store(uint8_t *arena, const En
     const uint32_t j = e0 + i / nc, c = i % nc, r = kept[j], rows = cnt[j];
     if (r >= O.n || rows == 0u) continue;                      // (never by the merge: the comparisons keep a fault elsewhere inside the stream's values)
     if (rows > 1u) vals[(size_t)nc * r + c] = ord_mean((int64_t)acc[(size_t)nc * j + c], rows);       // (a cell of one point keeps its value)
+  }
+}
+
+// ---- vote_attributes (the header comment has the contract): behind the merge, beside the means, in front of everything that reads `vals`
+// The tuple of a row as one integer whose unsigned order is the lexicographic order of its signed components.
+__device__ __forceinline__ uint64_t ord_vote_pack(const int32_t *v, uint32_t nc) {
+  const uint64_t a = (uint32_t)v[0] ^ 0x80000000u;
+  return nc == 2u ? a << 32 | (uint64_t)((uint32_t)v[1] ^ 0x80000000u) : a;
+}
+__device__ __forceinline__ uint32_t ord_vote_hash(uint32_t j, uint64_t pack) {
+  uint64_t x = pack ^ ((uint64_t)j + 1u) * 0x9E3779B97F4A7C15ull;
+  x ^= x >> 32; x *= 0xD6E8FEB86659FD93ull; x ^= x >> 29;
+  return (uint32_t)x ^ (uint32_t)(x >> 32);
+}
+// a value other threads of the launch may have raised meanwhile (it only ever goes from 0 to its value, or up)
+__device__ __forceinline__ uint32_t ord_peek(const uint32_t *p) {
+#if defined(__HIPCC__)
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+  return *p;
+#endif
+}
+__device__ __forceinline__ void ord_raise(unsigned long long *p, unsigned long long x) {
+#if defined(__HIPCC__)
+  if (x > __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(p, x);
+#else
+  if (x > *p) *p = x;
+#endif
+}
+// `rows` rows of cell j with the tuple `pack`, row r one of them, into the table of `cap` slots: the slot of (j, pack), claimed if
+// nobody has.  At most cap probes, no wait.  False: no slot.
+__device__ __forceinline__ bool ord_vote_insert(uint32_t *table, uint32_t cap, const uint32_t *cells, const int32_t *vals, uint32_t n, uint32_t nc,
+                                                uint32_t r, uint32_t j, uint64_t pack, uint32_t rows) {
+  uint32_t s = ord_vote_hash(j, pack) % cap;
+  for (uint32_t probe = 0; probe < cap; ++probe) {
+    uint32_t rep = ord_peek(&table[2ull * s]);
+    if (rep == 0u) rep = atomicCAS(&table[2ull * s], 0u, r + 1u);
+    bool mine = rep == 0u;                                     // (claimed just now)
+    if (!mine) { const uint32_t q = rep - 1u; mine = q < n && cells[q] == j && ord_vote_pack(vals + (size_t)nc * q, nc) == pack; }
+    if (mine) { atomicAdd(&table[2ull * s + 1u], rows); return true; }
+    s = s + 1u < cap ? s + 1u : 0u;
+  }
+  return false;
+}
+
+// grid = (the chunk's (cloud, tile) pairs, the most voted streams a cloud has): one wave per (tile, voted stream)
+__global__ __launch_bounds__(WAVE) void k_enc_vote_count(uint8_t *arena, const EncOrder *clouds, const EncOrderTile *tiles, uint32_t nt,
+                                                         const EncVoteCloud *vclouds, EncVote *votes, uint32_t nv) {
+  if (blockIdx.x >= nt) return;
+  const EncOrderTile T = tiles[blockIdx.x];
+  const EncOrder &O = clouds[T.cloud];
+  const EncVoteCloud C = vclouds[T.cloud];
+  uint32_t e0, end;
+  if (!O.merge || blockIdx.y >= C.count || C.first + blockIdx.y >= nv || !ord_tile(O, T, O.n, e0, end)) return;
+  EncVote &V = votes[C.first + blockIdx.y];
+  const uint32_t lane = threadIdx.x, nc = V.nc, cap = V.cap;
+  if (nc == 0u || nc > 2u || cap == 0u) return;                // (never by the layout)
+  const uint32_t *row = (const uint32_t *)(arena + ord_sorted(O).row);
+  const uint32_t *cells = (const uint32_t *)(arena + O.cells);
+  const int32_t *vals = (const int32_t *)(arena + V.vals);
+  uint32_t *table = (uint32_t *)(arena + V.table);
+  bool lost = false;
+#if defined(__HIPCC__)
+  const uint64_t *key = (const uint64_t *)(arena + ord_sorted(O).key);
+  const unsigned long long below = (1ull << lane) - 1ull, upto = (2ull << lane) - 1ull;
+  for (uint32_t s0 = e0; s0 < end; s0 += WAVE) {               // (uniform: every lane takes every step)
+    const uint32_t e = s0 + lane;
+    const bool valid = e < end;
+    const bool head = valid && ord_head(key, e);
+    const unsigned long long heads = __ballot(head);
+    // the lanes of this lane's run inside the step: from the head at or below it (lane 0 for a run that came in from the step in
+    // front) to below the next head above it
+    const unsigned long long mine = heads & upto, higher = heads & ~upto;
+    const uint32_t start = mine ? 63u - (uint32_t)__clzll((long long)mine) : 0u;
+    const unsigned long long run = (higher ? (higher & (0ull - higher)) - 1ull : ~0ull) & ~((1ull << start) - 1ull);
+    const uint32_t r = valid ? row[e] : 0u;
+    const uint32_t j = valid && r < O.n ? cells[r] : 0xFFFFFFFFu;
+    const bool in = j < O.n;
+    const unsigned long long pack = in ? ord_vote_pack(vals + (size_t)nc * r, nc) : 0ull;
+    const unsigned long long first = __shfl(pack, (int)start, WAVE);
+    // the lanes of the run that hold the tuple of its first lane: the lowest of them inserts for all, the others of the run singly
+    const bool same = in && pack == first;
+    const unsigned long long agree = __ballot(same) & run;
+    const bool leads = same && (agree & below) == 0ull;
+    if (in && (!same || leads) && !ord_vote_insert(table, cap, cells, vals, O.n, nc, r, j, pack, leads ? (uint32_t)__popcll(agree) : 1u)) lost = true;
+  }
+#else       // (as k_enc_order_hist: lane 0 takes the tile's entries in their order)
+  if (lane != 0) return;
+  for (uint32_t e = e0; e < end; ++e) {
+    const uint32_t r = row[e], j = cells[r];
+    if (!ord_vote_insert(table, cap, cells, vals, O.n, nc, r, j, ord_vote_pack(vals + (size_t)nc * r, nc), 1u)) lost = true;
+  }
+#endif
+  if (lost) V.full = 1u;
+}
+
+// grid as above, tile t over slots 2 t ORD_TILE .. (cap = 2 n: two slots an entry; the cloud's last tile takes what is left): a
+// thread per slot.  phase 0: the most rows a tuple of every cell has; phase 1, a launch behind it: the smallest tuple among those.
+__global__ __launch_bounds__(256) void k_enc_vote_best(uint8_t *arena, const EncOrder *clouds, const EncOrderTile *tiles, uint32_t nt,
+                                                       const EncVoteCloud *vclouds, const EncVote *votes, uint32_t nv, uint32_t phase) {
+  if (blockIdx.x >= nt) return;
+  const EncOrderTile T = tiles[blockIdx.x];
+  const EncOrder &O = clouds[T.cloud];
+  const EncVoteCloud C = vclouds[T.cloud];
+  uint32_t e0, end;
+  if (!O.merge || blockIdx.y >= C.count || C.first + blockIdx.y >= nv || !ord_tile(O, T, O.n, e0, end)) return;
+  const EncVote V = votes[C.first + blockIdx.y];
+  const uint32_t nc = V.nc;
+  if (nc == 0u || nc > 2u) return;                             // (never by the layout)
+  const uint64_t s_end = T.tile + 1u == O.tiles || 2ull * end > V.cap ? V.cap : 2ull * end;
+  const uint32_t *cells = (const uint32_t *)(arena + O.cells);
+  const int32_t *vals = (const int32_t *)(arena + V.vals);
+  const uint32_t *table = (const uint32_t *)(arena + V.table);
+  uint32_t *best_cnt = (uint32_t *)(arena + V.best_cnt);
+  unsigned long long *best_val = (unsigned long long *)(arena + V.best_val);
+  for (uint64_t s = 2ull * e0 + threadIdx.x; s < s_end; s += blockDim.x) {
+    const uint32_t rep = table[2ull * s], rows = table[2ull * s + 1u];
+    if (rep == 0u || rep - 1u >= O.n) continue;                // (an empty slot)
+    const uint32_t q = rep - 1u, j = cells[q];
+    if (j >= O.n) continue;                                    // (never by the merge: the comparison keeps a fault elsewhere inside the cloud's regions)
+    if (phase == 0u) { if (rows > ord_peek(&best_cnt[j])) atomicMax(&best_cnt[j], rows); }
+    else if (rows == best_cnt[j]) ord_raise(&best_val[j], ~(unsigned long long)ord_vote_pack(vals + (size_t)nc * q, nc));
+  }
+}
+
+// grid as above, tiles over KEPT entries: a thread per kept entry.  No lane needs another.
+__global__ __launch_bounds__(256) void k_enc_vote_store(uint8_t *arena, const EncOrder *clouds, const EncOrderTile *tiles, uint32_t nt,
+                                                        const EncVoteCloud *vclouds, const EncVote *votes, uint32_t nv) {
+  if (blockIdx.x >= nt) return;
+  const EncOrderTile T = tiles[blockIdx.x];
+  const EncOrder &O = clouds[T.cloud];
+  const EncVoteCloud C = vclouds[T.cloud];
+  uint32_t e0, end;
+  if (!O.merge || blockIdx.y >= C.count || C.first + blockIdx.y >= nv || !ord_tile(O, T, O.m, e0, end)) return;
+  const EncVote V = votes[C.first + blockIdx.y];
+  const uint32_t nc = V.nc;
+  if (nc == 0u || nc > 2u) return;                             // (never by the layout)
+  const uint32_t *kept = (const uint32_t *)(arena + ord_kept(O));
+  const uint32_t *best_cnt = (const uint32_t *)(arena + V.best_cnt);
+  const unsigned long long *best_val = (const unsigned long long *)(arena + V.best_val);
+  int32_t *vals = (int32_t *)(arena + V.vals);
+  for (uint32_t j = e0 + threadIdx.x; j < end; j += blockDim.x) {
+    const uint32_t r = kept[j];
+    if (r >= O.n || best_cnt[j] == 0u) continue;               // (never by the merge and the count: a full table leaves the row as it is)
+    const unsigned long long pack = ~best_val[j];
+    if (nc == 2u) { vals[2ull * r] = (int32_t)((uint32_t)(pack >> 32) ^ 0x80000000u); vals[2ull * r + 1u] = (int32_t)((uint32_t)pack ^ 0x80000000u); }
+    else vals[r] = (int32_t)((uint32_t)pack ^ 0x80000000u);
   }
 }
 

@@ -104,7 +104,14 @@ class Config:
     but positions and normals; the clouds of a call must then have the same attributes): those attributes carry, per component,
     floor((2 S + cnt) / (2 cnt)) over the cnt input rows of the cell, S the sum of the integers the plain call codes for them -- the
     exact mean, ties upwards, whatever the order of the rows.  Positions and normals carry no mean.  part_cells and lod_base_bits
-    compose with it; entry_rows, row_entries, part_info and lod_info are unchanged, cell_counts(i) counts the rows of every cell."""
+    compose with it; entry_rows, row_entries, part_info and lod_info are unchanged, cell_counts(i) counts the rows of every cell.
+
+    vote_attributes (dsa_encode_vote_sequential_batch): the most frequent value of the cell WITH merge_points=MERGE_CELLS, for labels
+    -- a classification, an instance id, a return number -- whose mean is a class nobody assigned.  A mask or a list of attribute
+    indices of the stream, counted as for mean_attributes: those attributes (of 1 or 2 components) carry the tuple of coded integers
+    that the most input rows of the cell have, among tuples of equally many rows the lexicographically smallest (signed components,
+    component 0 first), whatever the order of the rows.  Positions and normals are not voted on, an attribute takes the vote or the
+    mean, not both, and the clouds of a call must have the same attributes.  Everything else is as with mean_attributes."""
 
     EDGEBREAKER_METHODS = (0, 2, -1)
     POSITION_PREDICTIONS = (0, 1)
@@ -120,7 +127,7 @@ class Config:
                  symbol_scheme=-1, position_prediction=1, texcoord_prediction=1, edgebreaker_method=0, normal_prediction=0,
                  encoding_method=1, compress_connectivity=False, multi_parallelogram=0, traversal_method=0, repair_topology=False, weld_points=False,
                  repair_seams=False, weld_attributes=False, track_rows=False, point_order=0, merge_points=0, part_points=0, part_cells=0,
-                 lod_base_bits=0, mean_attributes=0):
+                 lod_base_bits=0, mean_attributes=0, vote_attributes=0):
         for name, value, legal in (("encoding_method", encoding_method, self.ENCODING_METHODS),
                                    ("edgebreaker_method", edgebreaker_method, self.EDGEBREAKER_METHODS),
                                    ("position_prediction", position_prediction, self.POSITION_PREDICTIONS),
@@ -203,6 +210,28 @@ class Config:
             raise ValueError("mean_attributes takes the mean over the points of a cell: it needs merge_points=MERGE_CELLS "
                              "(a sequential config with point_order=POINT_ORDER_MORTON)")
 
+        if isinstance(vote_attributes, (list, tuple, set, frozenset)):
+            if any(int(a) != a or a < 0 for a in vote_attributes):
+                raise ValueError("vote_attributes %r: attribute indices of the stream, 0 and above" % (vote_attributes,))
+            mask = 0
+            for a in vote_attributes:
+                mask |= 1 << int(a)
+        elif isinstance(vote_attributes, str):
+            raise ValueError("vote_attributes %r: a mask or a list of attribute indices of the stream" % (vote_attributes,))
+        else:
+            mask = int(vote_attributes)
+        if mask < 0 or mask >> native.MAX_ATTRIBUTES:
+            raise ValueError("vote_attributes %r: a bit at or above %d names no attribute of a stream" % (vote_attributes, native.MAX_ATTRIBUTES))
+        if mask & 1:
+            raise ValueError("vote_attributes %r: attribute 0 holds the positions, which are equal inside a cell and are never voted on" % (vote_attributes,))
+        self.vote_attributes = mask
+        if self.vote_attributes != 0 and self.merge_points != native.MERGE_CELLS:
+            raise ValueError("vote_attributes takes the most frequent value over the points of a cell: it needs merge_points=MERGE_CELLS "
+                             "(a sequential config with point_order=POINT_ORDER_MORTON)")
+        if self.vote_attributes != 0 and (self.mean_attributes == "all" or self.mean_attributes & self.vote_attributes):
+            raise ValueError("vote_attributes %r and mean_attributes %r name the same attribute: it carries the most frequent value of its cell or the mean, not both"
+                             % (vote_attributes, mean_attributes))
+
     def _mean_mask(self, meshes):
         """mean_attributes as the mask of a call over `meshes`: "all" is every attribute but positions and normals, and needs clouds
         with the same attributes."""
@@ -221,6 +250,18 @@ class Config:
         native.lib().dsa_encode_default_mean_options(C.byref(o))
         o.lod = self._native_lod(geometry)
         o.mean_attributes = self._mean_mask(meshes)
+        return o
+
+    def _native_vote(self, geometry, meshes):
+        """the options of dsa_encode_vote_sequential_batch for a call over `meshes`, which must have the same attributes: the mask
+        counts the attributes of the stream"""
+        tables = {(m.normals is not None, m.texcoords is not None, m.generic is not None, len(m.attributes)) for m in meshes}
+        if len(tables) > 1:
+            raise ValueError("vote_attributes is one mask for the call: its clouds must have the same attributes (give a mask per call otherwise)")
+        o = native.EncodeVoteOptions()
+        native.lib().dsa_encode_default_vote_options(C.byref(o))
+        o.mean = self._native_mean(geometry, meshes)
+        o.vote_attributes = self.vote_attributes
         return o
 
     @property
@@ -945,6 +986,7 @@ class DracoEncoder:
     # point, whether its handle has a slot per stream, so that n is read back from it).  A Config reaches the first whose option it
     # sets -- the widest call only when its option is set, and the plain case keeps arriving through the call it always took.
     _SEQUENTIAL_CALLS = (
+        ("vote_attributes", "_native_vote", "dsa_encode_vote_sequential_batch", True),
         ("mean_attributes", "_native_mean", "dsa_encode_mean_sequential_batch", True),
         ("lod_base_bits", "_native_lod", "dsa_encode_lod_sequential_batch", True),
         ("part_cells", "_native_cell_parts", "dsa_encode_cell_parts_sequential_batch", True),
@@ -965,6 +1007,8 @@ class DracoEncoder:
                 if config._mean_mask(meshes) == 0:
                     continue
                 opt = config._native_mean(geometry, meshes)
+            elif option == "vote_attributes":
+                opt = config._native_vote(geometry, meshes)
             else:
                 opt = getattr(config, build)(geometry)
             break

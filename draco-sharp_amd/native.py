@@ -48,6 +48,7 @@ EXPORTS = [
     "dsa_encode_default_cell_parts_options", "dsa_encode_cell_parts_sequential_batch",
     "dsa_encode_default_lod_options", "dsa_encode_lod_sequential_batch", "dsa_encoded_lod_info",
     "dsa_encode_default_mean_options", "dsa_encode_mean_sequential_batch",
+    "dsa_encode_default_vote_options", "dsa_encode_vote_sequential_batch",
     "dsa_encoded_size", "dsa_encoded_stream", "dsa_encoded_free",
     "dsa_pool_create", "dsa_pool_destroy", "dsa_pool_size", "dsa_pool_last_error", "dsa_pool_decode", "dsa_pool_job_locate",
     "dsa_pool_job_chunks", "dsa_pool_job_free", "dsa_pool_plan",
@@ -137,6 +138,13 @@ class EncodeMeanOptions(C.Structure):
     attribute a of the stream carries, per component, the exact mean of the integers of the rows of the cell, ties upwards; positions
     and normals carry none)."""
     _fields_ = [("lod", EncodeLodOptions), ("mean_attributes", C.c_uint32), ("reserved", C.c_int32 * 7)]
+
+
+class EncodeVoteOptions(C.Structure):
+    """dsa_encode_vote_options: the options of dsa_encode_mean_sequential_batch, and vote_attributes (with merge_points = 1: bit a set:
+    attribute a of the stream, of 1 or 2 components, carries the tuple of coded integers that the most rows of the cell have, among
+    tuples of equally many rows the lexicographically smallest; positions and normals are not voted on, the two masks share no bit)."""
+    _fields_ = [("mean", EncodeMeanOptions), ("vote_attributes", C.c_uint32), ("reserved", C.c_int32 * 7)]
 
 
 class LodInfo(C.Structure):
@@ -459,6 +467,10 @@ def lib():
             L.dsa_encode_default_mean_options.argtypes = [C.POINTER(EncodeMeanOptions)]
             L.dsa_encode_default_mean_options.restype = None
             L.dsa_encode_mean_sequential_batch.argtypes = [vp, u32, C.POINTER(MeshAttrInput), C.POINTER(MeshGrids), C.POINTER(EncodeMeanOptions), C.POINTER(vp)]
+        if hasattr(L, "dsa_encode_vote_sequential_batch"):
+            L.dsa_encode_default_vote_options.argtypes = [C.POINTER(EncodeVoteOptions)]
+            L.dsa_encode_default_vote_options.restype = None
+            L.dsa_encode_vote_sequential_batch.argtypes = [vp, u32, C.POINTER(MeshAttrInput), C.POINTER(MeshGrids), C.POINTER(EncodeVoteOptions), C.POINTER(vp)]
         L.dsa_encoded_size.restype = u32
         L.dsa_encoded_size.argtypes = [vp]
         L.dsa_encoded_stream.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(C.c_size_t)]

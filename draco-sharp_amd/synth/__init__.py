@@ -240,6 +240,7 @@ def lib():
                                                  C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(Options), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
         L.synth_quantized.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.POINTER(Grid), C.c_void_p]
         L.synth_merge_means.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.synth_merge_votes.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]
         L.synth_point_order.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(Grid), C.c_void_p]
         L.synth_merge_points.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(Grid), C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]
         L.synth_split_parts.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
@@ -630,6 +631,21 @@ def merge_means(q, row_entries, m):
     return out
 
 
+def merge_votes(q, row_entries, m):
+    """The most frequent value of every cell: q (N, nc) int32 with nc 1 or 2, row_entries (N,) below m as merge_points has them;
+    (m, nc) int32, entry j the tuple q[r] that the most rows r of cell j have, among tuples with equally many rows the
+    lexicographically smallest (signed components, component 0 first).  What dsa_encode_vote_sequential_batch codes for a voted
+    attribute."""
+    L = lib()
+    q = np.ascontiguousarray(q, np.int32)
+    q = q.reshape(len(q), -1)
+    cells = np.ascontiguousarray(row_entries, np.uint32)
+    out = np.zeros((int(m), q.shape[1]), np.int32)
+    if L.synth_merge_votes(q.ctypes.data, len(q), q.shape[1], cells.ctypes.data, int(m), out.ctypes.data):
+        raise RuntimeError(_err())
+    return out
+
+
 def _extra_rows(e, rows, grid=None):
     """Extra e with its rows (and its portable integers) taken at `rows` (an index array or a slice); grid: in place of e.grid."""
     return Extra(e.values[rows], attribute_type=e.attribute_type, normalized=bool(e.normalized), unique_id=e.unique_id,
@@ -637,31 +653,41 @@ def _extra_rows(e, rows, grid=None):
                  portable=None if e.portable is None else e.portable[rows])
 
 
-def merged_arguments(pos, normals=None, uvs=None, generic=None, extra=None, opt=None, pos_grid=None, uv_grid=None, mean_attributes=0):
+def merged_arguments(pos, normals=None, uvs=None, generic=None, extra=None, opt=None, pos_grid=None, uv_grid=None, mean_attributes=0, vote_attributes=0):
     """The arguments of the plain call that writes a merged stream: (kept, row_entries, kwargs for encode_grid(form=0, geometry=0))
     -- every per-point array at [kept], every quantised attribute on an explicit grid equal to the bounds of ALL its rows (the
     grid given, where one was).  mean_attributes: bit a: attribute a of the stream (0 positions, then normals, uvs, generic and the
     extras, those given) carries merge_means of its cell in place of row kept[j] -- an integer attribute as the mean array, a
-    quantised one as portable integers (uv_portable / Extra.portable) on the unchanged grid."""
+    quantised one as portable integers (uv_portable / Extra.portable) on the unchanged grid.  vote_attributes: likewise, bit a:
+    attribute a (of 1 or 2 components) carries merge_votes of its cell; the two masks share no bit."""
     opt = opt or options()
     kept, cells = merge_points(pos, opt.pos_bits, pos_grid)
     m = len(kept)
     index = 1 + (normals is not None)                       # the stream's attribute index of the next attribute
     if mean_attributes & 1 or (normals is not None and mean_attributes & 2):
         raise ValueError("mean_attributes: positions and normals carry no mean")
+    if vote_attributes & 1 or (normals is not None and vote_attributes & 2):
+        raise ValueError("vote_attributes: positions and normals are not voted on")
+    if mean_attributes & vote_attributes:
+        raise ValueError("vote_attributes and mean_attributes share a bit")
+    replaced = mean_attributes | vote_attributes
+
+    def of_cells(q):        # what entry j carries in place of row kept[j], for the attribute `index` stands at
+        return (merge_votes if (vote_attributes >> index) & 1 else merge_means)(q, cells, m)
+
     take = lambda a, nc: None if a is None else np.ascontiguousarray(np.asarray(a).reshape(-1, nc)[kept])      # noqa: E731
     pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
     ug = uv_grid if uv_grid is not None or uvs is None else bounds_grid(np.asarray(uvs, np.float32).reshape(-1, 2))
     uv_portable = None
     if uvs is not None:
-        if (mean_attributes >> index) & 1:
-            uv_portable = merge_means(quantized(np.asarray(uvs, np.float32).reshape(-1, 2), opt.uv_bits, ug), cells, m)
+        if (replaced >> index) & 1:
+            uv_portable = of_cells(quantized(np.asarray(uvs, np.float32).reshape(-1, 2), opt.uv_bits, ug))
         index += 1
     gen = None if generic is None else np.asarray(generic)[kept]
     if generic is not None:
-        if (mean_attributes >> index) & 1:
+        if (replaced >> index) & 1:
             g = np.asarray(generic)
-            gen = merge_means(g.reshape(len(g), -1).astype(np.int32), cells, m).astype(g.dtype).reshape((m,) + g.shape[1:])
+            gen = of_cells(g.reshape(len(g), -1).astype(np.int32)).astype(g.dtype).reshape((m,) + g.shape[1:])
         index += 1
     ex = []
     for e in (extra or []):
@@ -671,16 +697,18 @@ def merged_arguments(pos, normals=None, uvs=None, generic=None, extra=None, opt=
         if g is None and is_float:
             g = bounds_grid(e.values)
         x = _extra_rows(e, kept, g)
-        if (mean_attributes >> index) & 1:
+        if (replaced >> index) & 1:
             if is_float:
                 bits = e.quantization_bits or (opt.uv_bits if e.attribute_type == 3 else 8)
-                x.portable = merge_means(quantized(e.values, bits, g), cells, m)
+                x.portable = of_cells(quantized(e.values, bits, g))
             else:
-                x.values = np.ascontiguousarray(merge_means(e.values.astype(np.int64).astype(np.int32), cells, m).astype(e.values.dtype))
+                x.values = np.ascontiguousarray(of_cells(e.values.astype(np.int64).astype(np.int32)).astype(e.values.dtype))
         ex.append(x)
         index += 1
     if mean_attributes >> index:
         raise ValueError("mean_attributes: a bit names an attribute the stream does not have")
+    if vote_attributes >> index:
+        raise ValueError("vote_attributes: a bit names an attribute the stream does not have")
     kw = dict(pos=pos[kept], normals=take(normals, 3), uvs=take(uvs, 2), generic=gen,
               extra=ex, opt=opt, pos_grid=pos_grid if pos_grid is not None else bounds_grid(pos), uv_grid=ug)
     if uv_portable is not None:
@@ -688,11 +716,11 @@ def merged_arguments(pos, normals=None, uvs=None, generic=None, extra=None, opt=
     return kept, cells, kw
 
 
-def encode_merged(pos, normals=None, uvs=None, generic=None, extra=None, opt=None, pos_grid=None, uv_grid=None, mean_attributes=0):
+def encode_merged(pos, normals=None, uvs=None, generic=None, extra=None, opt=None, pos_grid=None, uv_grid=None, mean_attributes=0, vote_attributes=0):
     """encode_grid(form=0, geometry=0) of one point per occupied cell: (stream, kept, row_entries), merged_arguments coded.  What
     dsa_encode_merged_sequential_batch with merge_points = 1 must write, and the rows its handle must report; with mean_attributes
-    what dsa_encode_mean_sequential_batch must."""
-    kept, cells, kw = merged_arguments(pos, normals, uvs, generic, extra, opt, pos_grid, uv_grid, mean_attributes)
+    what dsa_encode_mean_sequential_batch must, with vote_attributes what dsa_encode_vote_sequential_batch must."""
+    kept, cells, kw = merged_arguments(pos, normals, uvs, generic, extra, opt, pos_grid, uv_grid, mean_attributes, vote_attributes)
     p = kw.pop("pos")
     return encode_grid(p, None, form=0, geometry=0, **kw), kept, cells
 
@@ -787,7 +815,7 @@ def cell_parts(pos, bits, part_cells, grid=None):
 CellParts = collections.namedtuple("CellParts", "streams kept row_entries ranges qmin qmax")
 
 
-def encode_cell_parts(pos, normals=None, uvs=None, generic=None, extra=None, opt=None, pos_grid=None, uv_grid=None, part_cells=0, mean_attributes=0):
+def encode_cell_parts(pos, normals=None, uvs=None, generic=None, extra=None, opt=None, pos_grid=None, uv_grid=None, part_cells=0, mean_attributes=0, vote_attributes=0):
     """One point per occupied cell, and the kept order in parts of at most part_cells points, each coded as a point cloud of its own
     on the cloud's grid: CellParts(streams, kept, row_entries, ranges, qmin, qmax) with merged_arguments' rows and grids -- every
     per-point array at [kept[lo:hi]], every quantised attribute on an explicit grid equal to the bounds of ALL input rows (the grid
@@ -795,7 +823,7 @@ def encode_cell_parts(pos, normals=None, uvs=None, generic=None, extra=None, opt
     report."""
     opt = opt or options()
     kept, cells, ranges, qmin, qmax = cell_parts(pos, opt.pos_bits, part_cells, pos_grid)
-    _, _, kw = merged_arguments(pos, normals, uvs, generic, extra, opt, pos_grid, uv_grid, mean_attributes)
+    _, _, kw = merged_arguments(pos, normals, uvs, generic, extra, opt, pos_grid, uv_grid, mean_attributes, vote_attributes)
     p = kw.pop("pos")
     streams = []
     for lo, hi in ranges:
@@ -832,7 +860,7 @@ LodParts = collections.namedtuple("LodParts", "streams kept row_entries ranges q
 
 
 def encode_lod_parts(pos, normals=None, uvs=None, generic=None, extra=None, opt=None, pos_grid=None, uv_grid=None, part_cells=0, lod_base_bits=0,
-                     mean_attributes=0):
+                     mean_attributes=0, vote_attributes=0):
     """Additive levels of detail of the kept points, every level in parts of at most part_cells points, each part coded as a point
     cloud of its own on the cloud's grid: what encode_cell_parts returns with `kept` the rows in LOD order (ranges and row_entries
     count in it), plus `level` per stream and `levels` = L = position bits - lod_base_bits + 1.  Every per-point array at
@@ -841,10 +869,10 @@ def encode_lod_parts(pos, normals=None, uvs=None, generic=None, extra=None, opt=
     lod_base_bits 0: encode_cell_parts, every stream of level 0 of 1."""
     opt = opt or options()
     if lod_base_bits == 0:
-        cp = encode_cell_parts(pos, normals, uvs, generic, extra, opt, pos_grid, uv_grid, part_cells, mean_attributes)
+        cp = encode_cell_parts(pos, normals, uvs, generic, extra, opt, pos_grid, uv_grid, part_cells, mean_attributes, vote_attributes)
         return LodParts(*cp, level=np.zeros(len(cp.streams), np.uint32), levels=1)
     lod, cells, ranges, level, qmin, qmax = lod_parts(pos, opt.pos_bits, part_cells, lod_base_bits, pos_grid)
-    kept, _, kw = merged_arguments(pos, normals, uvs, generic, extra, opt, pos_grid, uv_grid, mean_attributes)
+    kept, _, kw = merged_arguments(pos, normals, uvs, generic, extra, opt, pos_grid, uv_grid, mean_attributes, vote_attributes)
     at = np.zeros(int(kept.max()) + 1, np.int64)
     at[kept] = np.arange(len(kept))
     idx = at[lod]                                # where in kept (the order of merged_arguments' arrays) every lod entry lies

@@ -502,6 +502,15 @@ int synth_merge_means(const int32_t *q, uint32_t n, int nc, const uint32_t *row_
     return 0;
   } catch (const std::exception &e) { snprintf(g_err, sizeof(g_err), "%s", e.what()); return 1; }
 }
+// The most frequent tuple of every cell (dsa_encode_host.h merge_votes): q[n * nc], nc 1 or 2, row_entries[n] below m; votes[m * nc].
+int synth_merge_votes(const int32_t *q, uint32_t n, int nc, const uint32_t *row_entries, uint32_t m, int32_t *votes) {
+  try {
+    std::vector<int32_t> out;
+    synth::merge_votes(q, n, nc, std::vector<uint32_t>(row_entries, row_entries + n), m, out);
+    memcpy(votes, out.data(), 4 * out.size());
+    return 0;
+  } catch (const std::exception &e) { snprintf(g_err, sizeof(g_err), "%s", e.what()); return 1; }
+}
 // synth_encode_grid with row ids per corner for attributes of the list (form 1) or the listed attributes welded alone (form 2, weld_attributes != 0)
 int synth_encode_corner_attributes_grid(int form, const float *pos, uint32_t nv, const uint32_t *faces, uint32_t nf, const float *normals, uint32_t nn,
                                         const uint32_t *normal_corners, const float *uvs, uint32_t nu, const uint32_t *uv_corners, const void *generic,

@@ -925,7 +925,8 @@ dsa_status dsa_encoded_lod_info(const dsa_encoded *encoded, uint32_t stream, dsa
  * dsa_encode_order.h) take 0.6 ms of a 64 ms call for a 4 Mi-point scan with a colour and a float attribute in 256 parts, against 264 ms
  * for download, host means and a second encode.
  * Not built: mean normals (octahedral integers do not average across the fold, a vector sum needs a fixed-point rule of its own);
- * weighted means; means per coarser lod cell (a level's point carries the mean of its finest cell); a vote for label attributes.
+ * weighted means; means per coarser lod cell (a level's point carries the mean of its finest cell).  Built since, for categories
+ * whose mean is a class nobody assigned: a vote for label attributes, dsa_encode_vote_sequential_batch below.
  * Added after ABI 4 without changing it: callers detect the feature by the symbol dsa_encode_mean_sequential_batch. */
 typedef struct dsa_encode_mean_options {
   dsa_encode_lod_options lod;              /* as for dsa_encode_lod_sequential_batch, same legal values */
@@ -935,6 +936,44 @@ typedef struct dsa_encode_mean_options {
 void dsa_encode_default_mean_options(dsa_encode_mean_options *options);
 dsa_status dsa_encode_mean_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids,
                                             const dsa_encode_mean_options *options, dsa_encoded **out);
+/* dsa_encode_mean_sequential_batch with the most frequent value of every cell in chosen attributes of its kept point: what a
+ * voxel-grid downsample does to a classification, an instance id, a return number or a feature id -- categories, whose mean is a
+ * class nobody assigned, and of which the kept point otherwise carries whichever row came first in the caller's order.
+ *   vote_attributes: bit a set: attribute a of the STREAM (counted as mean_attributes counts them) carries the cell's most frequent
+ *   value.  Taken only with merge_points = 1; part_cells, lod_base_bits and mean_attributes (on other attributes) compose with it
+ *   as they are.
+ *   key, perm, kept, row_entries, R(j) and q_a[r][c] are exactly what the mean call defines.  For a voted attribute a with nc
+ *   components the value of row r is the tuple (q_a[r][0], .., q_a[r][nc - 1]) as a whole.  Entry j carries the tuple that the most
+ *   rows of R(j) have; among tuples with equally many rows the lexicographically smallest one, components compared as signed 32-bit
+ *   integers, component 0 first.  The winner is a function of the SET of rows of the cell, not of their order (ties are the common
+ *   case in cells of two to four rows), bit-identical on host and device; a cell of one row keeps its value.  The voted tuple is
+ *   the tuple of some row of the cell, so bounds, grids, histogram sizes, wrap ranges and every refusal are those of the call
+ *   without the mask.  Integer attributes of every element type, the built-in texture coordinates and quantised float attributes
+ *   of 1 or 2 components are voted on their coded integers.
+ *   Every stream is byte for byte what the same call with vote_attributes = 0 writes for an input that holds the winners at row
+ *   kept[j].  The handle is unchanged: its shape, dsa_encoded_entry_rows, dsa_encoded_row_entries, the cell counts, part_info,
+ *   lod_info, dsa_batch_source_rows and the join plan.
+ *   vote_attributes = 0: the bytes, the messages, the work and the handle of dsa_encode_mean_sequential_batch.
+ * Fails the call with DSA_ERR_INVALID_ARGUMENT before any mesh is looked at, dsa_last_error naming the field: vote_attributes != 0
+ * without merge_points = 1; a bit at or above DSA_MAX_ATTRIBUTES; a bit set in both vote_attributes and mean_attributes; a
+ * non-zero reserved word.  Refusals of the nested option structs keep their own words.  A cloud fails alone with
+ * DSA_ERR_INVALID_ARGUMENT (it keeps one slot; the message names vote_attributes and the attribute) when a set bit names the
+ * positions, the normals (a vote over octahedral integers is not built), an attribute its stream does not have, or an attribute
+ * of 3 or 4 components (only tuples that pack into 64 bits are built).
+ * On the device four launches behind the merge, beside the mean kernels (k_enc_vote_count, k_enc_vote_best twice, k_enc_vote_store;
+ * dsa_encode_order.h): an open-addressing table of two slots a point per voted attribute counts the rows of every (cell, tuple),
+ * no sort; DESIGN.md 7.3 has what it costs.
+ * Not built: tuples of 3 or 4 components; a vote over normals; weighted votes; votes per coarser lod cell; the winning count or
+ * share per cell in the handle; votes without the merge.
+ * Added after ABI 4 without changing it: callers detect the feature by the symbol dsa_encode_vote_sequential_batch. */
+typedef struct dsa_encode_vote_options {
+  dsa_encode_mean_options mean;            /* as for dsa_encode_mean_sequential_batch, same legal values */
+  uint32_t vote_attributes;                /* 0 (default): the very request of the mean call; bit a: attribute a of the stream carries the cell's most frequent value */
+  int32_t reserved[7];                     /* must be zero */
+} dsa_encode_vote_options;
+void dsa_encode_default_vote_options(dsa_encode_vote_options *options);
+dsa_status dsa_encode_vote_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids,
+                                            const dsa_encode_vote_options *options, dsa_encoded **out);
 /* The rows of a decoded batch per POINT: for every mesh of `batch` and every attribute a of its stream,
  *     rows[a][p] = entry_rows[a][map[a][p]]          (map: the decoder's point -> entry map, dsa_batch_device_point_map)
  * -- which row of the arrays given to the encoder point p carries, gathered on the device (k_source_rows) so that neither the maps
