@@ -1255,7 +1255,7 @@ static dsa_status enc_stage_attributes(dsa_context *ctx, EncLane &lane, EncChunk
   if (device_conn) ENC_TRY(hipMemcpyAsync(L.conns.data(), d_conns, sizeof(dsa::EncConn) * n, hipMemcpyDeviceToHost, st));
   if (nz) ENC_TRY(hipMemcpyAsync(L.seams.data(), d_seams, sizeof(dsa::EncSeam) * nz, hipMemcpyDeviceToHost, st));
   // vote_attributes: the records of the voted streams, for EncVote::full (enc_vote_refusals)
-  if (!L.votes.empty()) ENC_TRY(hipMemcpyAsync(L.votes.data(), arena + L.votes_at, sizeof(dsa::EncVote) * L.votes.size(), hipMemcpyDeviceToHost, st));
+  if (!L.votes.empty()) ENC_TRY(hipMemcpyAsync(L.votes.data(), arena + L.vote_pass.records_at, sizeof(dsa::EncVote) * L.votes.size(), hipMemcpyDeviceToHost, st));
   ENC_TRY(hipStreamSynchronize(st));
   if (order_timing) order_lap("gather to entropy coding");
   return DSA_OK;
@@ -1349,7 +1349,7 @@ static void enc_quantiser_refusals(EncChunk &ck) {
 static void enc_vote_refusals(EncChunk &ck) {
   for (size_t k = 0; k < ck.L.votes.size(); ++k) {
     if (!ck.L.votes[k].full) continue;
-    const uint32_t s = ck.L.vote_stream[k], i = (uint32_t)ck.stream_mesh[s];
+    const uint32_t s = ck.L.vote_pass.stream[k], i = (uint32_t)ck.stream_mesh[s];
     if (!ck.good(i)) continue;
     char buf[160];
     snprintf(buf, sizeof(buf), "internal error: the vote table of attribute %u (vote_attributes 0x%x, %u slots) was found full", s - ck.L.first_stream[i], ck.rq.vote_attributes, ck.L.votes[k].cap);
@@ -1561,19 +1561,21 @@ static dsa_status enc_check_options(dsa_context *ctx, const dsa_encode_lod_optio
   if (o.lod_base_bits > bits) ENC_REFUSE("lod_base_bits %d is above position_bits %d: level 0 cannot be finer than the quantisation grid", (int)o.lod_base_bits, bits);
   return DSA_OK;
 }
+// a mask over the attributes of a merged cloud's stream (`name`: mean_attributes, vote_attributes; `is`: what it asks of the points of a cell)
+static dsa_status enc_check_cell_mask(dsa_context *ctx, const char *name, uint32_t mask, const dsa_encode_merge_options &m, const char *is) {
+  if (mask != 0 && m.merge_points != 1) ENC_REFUSE("%s 0x%x needs merge_points 1 (it was %d): %s of a cell", name, (unsigned)mask, (int)m.merge_points, is);
+  if (mask >> DSA_MAX_ATTRIBUTES) ENC_REFUSE("%s 0x%x: a bit at or above %d (DSA_MAX_ATTRIBUTES) names no attribute of a stream", name, (unsigned)mask, (int)DSA_MAX_ATTRIBUTES);
+  return DSA_OK;
+}
 // ... with the mean of the cell in the masked attributes of the kept points (dsa_encode_order.h)
 static dsa_status enc_check_options(dsa_context *ctx, const dsa_encode_mean_options &o, bool null_argument) {
-  const dsa_encode_merge_options &m = o.lod.cell_parts.split.merge;
-  if (o.mean_attributes != 0 && m.merge_points != 1) ENC_REFUSE("mean_attributes 0x%x needs merge_points 1 (it was %d): the mean is the mean over the points of a cell", (unsigned)o.mean_attributes, (int)m.merge_points);
-  if (o.mean_attributes >> DSA_MAX_ATTRIBUTES) ENC_REFUSE("mean_attributes 0x%x: a bit at or above %d (DSA_MAX_ATTRIBUTES) names no attribute of a stream", (unsigned)o.mean_attributes, (int)DSA_MAX_ATTRIBUTES);
+  if (enc_check_cell_mask(ctx, "mean_attributes", o.mean_attributes, o.lod.cell_parts.split.merge, "the mean is the mean over the points") != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
   ENC_RESERVED(o, 7, "dsa_encode_mean_options");
   return enc_check_options(ctx, o.lod, null_argument);
 }
 // ... or with the most frequent value of the cell in the voted attributes of the kept points (dsa_encode_order.h)
 static dsa_status enc_check_options(dsa_context *ctx, const dsa_encode_vote_options &o, bool null_argument) {
-  const dsa_encode_merge_options &m = o.mean.lod.cell_parts.split.merge;
-  if (o.vote_attributes != 0 && m.merge_points != 1) ENC_REFUSE("vote_attributes 0x%x needs merge_points 1 (it was %d): the vote is a vote of the points of a cell", (unsigned)o.vote_attributes, (int)m.merge_points);
-  if (o.vote_attributes >> DSA_MAX_ATTRIBUTES) ENC_REFUSE("vote_attributes 0x%x: a bit at or above %d (DSA_MAX_ATTRIBUTES) names no attribute of a stream", (unsigned)o.vote_attributes, (int)DSA_MAX_ATTRIBUTES);
+  if (enc_check_cell_mask(ctx, "vote_attributes", o.vote_attributes, o.mean.lod.cell_parts.split.merge, "the vote is a vote of the points") != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
   if (o.vote_attributes & o.mean.mean_attributes) ENC_REFUSE("vote_attributes 0x%x and mean_attributes 0x%x share a bit: an attribute carries the most frequent value of its cell or the mean, not both", (unsigned)o.vote_attributes, (unsigned)o.mean.mean_attributes);
   ENC_RESERVED(o, 7, "dsa_encode_vote_options");
   return enc_check_options(ctx, o.mean, null_argument);

@@ -294,6 +294,32 @@ struct EncArena {
   uint64_t take(uint64_t bytes) { const uint64_t at = cur; cur = (cur + bytes + 255) & ~255ull; if (log) log->push_back({at, bytes}); return at; }
   uint64_t put(std::vector<EncUpload> &ups, const void *src, uint64_t bytes, bool narrow) { const uint64_t at = take(bytes); ups.push_back({at, src, (size_t)bytes, narrow}); return at; }
 };
+// A cell pass of the point-order stage (dsa_encode_order.h: the means, the votes) beside its typed records, one per chosen stream.
+struct EncCellPass {
+  std::vector<dsa::EncCellStreams> clouds;  // one per cloud, parallel to EncLayout::ord
+  std::vector<uint32_t> stream;             // stream[k]: the stream of the pass's record k
+  uint64_t clouds_at = 0, records_at = 0;   // both among the uploads
+  uint32_t most = 0;                        // the most chosen streams a cloud of the chunk has: the y of the kernels' grid
+  // the streams of a cloud of `na` attributes from stream s0 on that `mask` names (never the positions): record(stream) appends
+  // the typed record of each; then the cloud's own record
+  template <class Append>
+  void list(uint32_t mask, uint32_t s0, size_t na, Append &&record) {
+    dsa::EncCellStreams C{(uint32_t)stream.size(), 0u};
+    for (uint32_t k = 1; k < na && k < 32u; ++k) {
+      if (!((mask >> k) & 1u)) continue;
+      record(s0 + k); stream.push_back(s0 + k);
+      ++C.count;
+    }
+    most = std::max(most, C.count);
+    clouds.push_back(C);
+  }
+  template <class Record>
+  void upload(const std::vector<Record> &records, EncArena &A, std::vector<EncUpload> &uploads) {
+    if (records.empty()) return;
+    clouds_at = A.put(uploads, clouds.data(), sizeof(dsa::EncCellStreams) * clouds.size(), false);
+    records_at = A.put(uploads, records.data(), sizeof(Record) * records.size(), false);
+  }
+};
 struct EncLayout {
   std::vector<dsa::EncStream> streams;
   std::vector<dsa::EncConn> conns;          // device connectivity: one per mesh (a mesh that failed the host's checks: F = 0, no arrays)
@@ -325,21 +351,14 @@ struct EncLayout {
   std::vector<dsa::EncPartTile> part_tiles;
   std::vector<uint32_t> part_of_mesh;
   uint64_t parts_at = 0, part_tiles_at = 0;
-  // EncRequest::means: a record per cloud (parallel to `ord`) and per masked stream, both among the uploads; mean_stream[k] the
-  // stream of record k; the sums and counts are one range of the arena, zeroed on the stream in front of k_enc_mean_sum
-  std::vector<dsa::EncMeanCloud> mean_clouds;
+  // EncRequest::means, EncRequest::votes: a cell pass each (EncCellPass above) with its typed records, one per masked / voted stream,
+  // and what it accumulates in, one range of the arena that is zeroed on the stream in front of its kernels: the means' holds the
+  // sums and counts, the votes' behind it tables, counts and values.  The vote records come back behind the stage: EncVote::full
+  // (enc_vote_refusals)
+  EncCellPass mean_pass, vote_pass;
+  uint64_t mean_zero_at = 0, mean_zero_bytes = 0, vote_zero_at = 0, vote_zero_bytes = 0;
   std::vector<dsa::EncMean> means;
-  std::vector<uint32_t> mean_stream;
-  uint64_t mean_clouds_at = 0, means_at = 0, mean_zero_at = 0, mean_zero_bytes = 0;
-  uint32_t mean_most = 0;                   // the most masked streams a cloud of the chunk has: the y of the mean kernels' grid
-  // EncRequest::votes: likewise a record per cloud (parallel to `ord`) and per voted stream among the uploads; vote_stream[k] the stream
-  // of record k; tables, counts and values are one range of the arena behind the means', zeroed on the stream in front of
-  // k_enc_vote_count.  The records come back behind the stage: EncVote::full (enc_vote_refusals)
-  std::vector<dsa::EncVoteCloud> vote_clouds;
   std::vector<dsa::EncVote> votes;
-  std::vector<uint32_t> vote_stream;
-  uint64_t vote_clouds_at = 0, votes_at = 0, vote_zero_at = 0, vote_zero_bytes = 0;
-  uint32_t vote_most = 0;                   // the most voted streams a cloud of the chunk has: the y of the vote kernels' grid
 };
 
 // ---- the point-order stage of a chunk whose layout has order records (dsa_encode_order.h has the kernels and their contracts): the
@@ -362,10 +381,15 @@ static inline bool enc_order_stage(Launch &&launch, Zero &&zero, After &&after, 
   const dsa::EncOrderTile *tiles = (const dsa::EncOrderTile *)(arena + L.ord_tiles_at);
   dsa::EncPart *parts = (dsa::EncPart *)(arena + L.parts_at);
   const dsa::EncPartTile *part_tiles = (const dsa::EncPartTile *)(arena + L.part_tiles_at);
-  const dsa::EncMeanCloud *mclouds = (const dsa::EncMeanCloud *)(arena + L.mean_clouds_at);
-  const dsa::EncMean *means = (const dsa::EncMean *)(arena + L.means_at);
-  const dsa::EncVoteCloud *vclouds = (const dsa::EncVoteCloud *)(arena + L.vote_clouds_at);
-  dsa::EncVote *votes = (dsa::EncVote *)(arena + L.votes_at);
+  const dsa::EncMean *means = (const dsa::EncMean *)(arena + L.mean_pass.records_at);
+  dsa::EncVote *votes = (dsa::EncVote *)(arena + L.vote_pass.records_at);
+  // a cell pass: its range zeroed, kernels(the clouds' records, grid y), its lap
+  auto cell_pass = [&](const EncCellPass &P, uint64_t zero_at, uint64_t zero_bytes, const char *lap, auto &&kernels) -> bool {
+    if (P.stream.empty()) return true;
+    zero(zero_at, zero_bytes);
+    if (P.most) kernels((const dsa::EncCellStreams *)(arena + P.clouds_at), P.most);
+    return after(lap);
+  };
   // the permutation of every cloud, behind the quantisers and in front of the gather
   launch(dsa::k_enc_order_keys, nt, 1u, 256u, arena, clouds, tiles, nt);
   for (uint32_t p = 0; p < L.ord_passes; ++p) {
@@ -382,24 +406,18 @@ static inline bool enc_order_stage(Launch &&launch, Zero &&zero, After &&after, 
     launch(dsa::k_enc_merge_compact, nt, 1u, wave, arena, clouds, tiles, nt);
     if (!after("point merge")) return false;
   }
-  if (!L.means.empty()) {      // mean_attributes: the mean of the cell into vals at every kept row, in front of everything that reads vals or turns row_entries into lod order
-    zero(L.mean_zero_at, L.mean_zero_bytes);
-    if (L.mean_most) {
-      launch(dsa::k_enc_mean_sum, nt, L.mean_most, wave, arena, clouds, tiles, nt, mclouds, means, nm);
-      launch(dsa::k_enc_mean_store, nt, L.mean_most, 256u, arena, clouds, tiles, nt, mclouds, means, nm);
-    }
-    if (!after("cell means")) return false;
-  }
-  if (!L.votes.empty()) {      // vote_attributes: the most frequent tuple of the cell into vals at every kept row, beside the means (other streams), in front of the same readers
-    zero(L.vote_zero_at, L.vote_zero_bytes);
-    if (L.vote_most) {
-      launch(dsa::k_enc_vote_count, nt, L.vote_most, wave, arena, clouds, tiles, nt, vclouds, votes, nv);
-      launch(dsa::k_enc_vote_best, nt, L.vote_most, 256u, arena, clouds, tiles, nt, vclouds, (const dsa::EncVote *)votes, nv, 0u);
-      launch(dsa::k_enc_vote_best, nt, L.vote_most, 256u, arena, clouds, tiles, nt, vclouds, (const dsa::EncVote *)votes, nv, 1u);
-      launch(dsa::k_enc_vote_store, nt, L.vote_most, 256u, arena, clouds, tiles, nt, vclouds, (const dsa::EncVote *)votes, nv);
-    }
-    if (!after("cell votes")) return false;
-  }
+  // mean_attributes: the mean of the cell into vals at every kept row, in front of everything that reads vals or turns row_entries into lod order
+  if (!cell_pass(L.mean_pass, L.mean_zero_at, L.mean_zero_bytes, "cell means", [&](const dsa::EncCellStreams *mclouds, uint32_t most) {
+        launch(dsa::k_enc_mean_sum, nt, most, wave, arena, clouds, tiles, nt, mclouds, means, nm);
+        launch(dsa::k_enc_mean_store, nt, most, 256u, arena, clouds, tiles, nt, mclouds, means, nm);
+      })) return false;
+  // vote_attributes: the most frequent tuple of the cell into vals at every kept row, beside the means (other streams), in front of the same readers
+  if (!cell_pass(L.vote_pass, L.vote_zero_at, L.vote_zero_bytes, "cell votes", [&](const dsa::EncCellStreams *vclouds, uint32_t most) {
+        launch(dsa::k_enc_vote_count, nt, most, wave, arena, clouds, tiles, nt, vclouds, votes, nv);
+        launch(dsa::k_enc_vote_best, nt, most, 256u, arena, clouds, tiles, nt, vclouds, (const dsa::EncVote *)votes, nv, 0u);
+        launch(dsa::k_enc_vote_best, nt, most, 256u, arena, clouds, tiles, nt, vclouds, (const dsa::EncVote *)votes, nv, 1u);
+        launch(dsa::k_enc_vote_store, nt, most, 256u, arena, clouds, tiles, nt, vclouds, (const dsa::EncVote *)votes, nv);
+      })) return false;
   if (L.lod && np) {           // lod_base_bits: the kept order by (level, kept); the slot sizer below cuts every level into its parts
     launch(dsa::k_enc_lod_levels, nt, 1u, wave, arena, clouds, tiles, nt);
     launch(dsa::k_enc_lod_scan, nc, 1u, wave, arena, clouds, nc);
@@ -1044,10 +1062,10 @@ static void enc_layout(EncChunk &ck) {
 // is the kept buffer, as with the merge, and k_enc_part_cells writes every slot's lo, n, nv and e2v.
 // EncRequest::lod (cell_parts with levels): ceil(n / part_cells) + L - 1 slots, the streams' map is the lod buffer, which with pos takes
 // the sort's dead key buffer; a level table per cloud among the kernels' regions; k_enc_part_cells writes the slots from it.
-// EncRequest::means (merge with mean_attributes): an EncMeanCloud per cloud and an EncMean per masked stream among the uploads; behind
+// EncRequest::means (merge with mean_attributes): an EncCellStreams per cloud and an EncMean per masked stream among the uploads; behind
 // every other region a u32[n] count region per cloud and an i64[n nc] sum region per masked stream, one range that is zeroed on the
 // stream in front of k_enc_mean_sum.  No region is reused and nothing else grows.
-// EncRequest::votes (merge with vote_attributes): likewise an EncVoteCloud per cloud and an EncVote per voted stream among the uploads;
+// EncRequest::votes (merge with vote_attributes): likewise an EncCellStreams per cloud and an EncVote per voted stream among the uploads;
 // behind the means' range per voted stream a table of 2 n slots of 8 bytes (a crowded chunk of small clouds pays for its points, not
 // for tiles), u32[n] counts and u64[n] values, one range that is zeroed on the stream in front of k_enc_vote_count.
 static void enc_layout_sequential(EncChunk &ck) {
@@ -1077,36 +1095,19 @@ static void enc_layout_sequential(EncChunk &ck) {
       O.n = V; O.tiles = (V + ORD_TILE - 1u) / ORD_TILE; O.bits = (uint32_t)ck.opt.pos_bits; O.last = dsa::enc_order_passes(O.bits) & 1u;
       if (merge) { O.merge = 1; O.stream0 = s0; O.streams = (uint32_t)atts.size(); }
       if (merge || split) L.ord_of_mesh[i] = (uint32_t)L.ord.size();
-      if (ck.rq.means()) {                                     // the masked streams of the cloud (the first part's: the parts share its vals)
-        dsa::EncMeanCloud MC;
-        memset(&MC, 0, sizeof(MC));
-        MC.first = (uint32_t)L.means.size();
-        for (uint32_t k = 1; k < atts.size() && k < 32u; ++k) {
-          if (!((ck.rq.mean_attributes >> k) & 1u)) continue;
-          dsa::EncMean M;
-          memset(&M, 0, sizeof(M));
-          M.nc = L.streams[s0 + k].nc;
-          L.means.push_back(M); L.mean_stream.push_back(s0 + k);
-          ++MC.count;
-        }
-        L.mean_most = std::max(L.mean_most, MC.count);
-        L.mean_clouds.push_back(MC);
-      }
-      if (ck.rq.votes()) {                                     // the voted streams of the cloud (the first part's, as above)
-        dsa::EncVoteCloud VC;
-        memset(&VC, 0, sizeof(VC));
-        VC.first = (uint32_t)L.votes.size();
-        for (uint32_t k = 1; k < atts.size() && k < 32u; ++k) {
-          if (!((ck.rq.vote_attributes >> k) & 1u)) continue;
-          dsa::EncVote X;
-          memset(&X, 0, sizeof(X));
-          X.nc = L.streams[s0 + k].nc; X.cap = 2u * V;         // (V <= 2^28: enc_check_sequential_mesh)
-          L.votes.push_back(X); L.vote_stream.push_back(s0 + k);
-          ++VC.count;
-        }
-        L.vote_most = std::max(L.vote_most, VC.count);
-        L.vote_clouds.push_back(VC);
-      }
+      // the masked and the voted streams of the cloud (the first part's: the parts share its vals)
+      if (ck.rq.means()) L.mean_pass.list(ck.rq.mean_attributes, s0, atts.size(), [&](uint32_t s) {
+        dsa::EncMean M;
+        memset(&M, 0, sizeof(M));
+        M.nc = L.streams[s].nc;
+        L.means.push_back(M);
+      });
+      if (ck.rq.votes()) L.vote_pass.list(ck.rq.vote_attributes, s0, atts.size(), [&](uint32_t s) {
+        dsa::EncVote X;
+        memset(&X, 0, sizeof(X));
+        X.nc = L.streams[s].nc; X.cap = 2u * V;                // (V <= 2^28: enc_check_sequential_mesh)
+        L.votes.push_back(X);
+      });
       for (uint32_t t = 0; t < O.tiles; ++t) L.ord_tiles.push_back({(uint32_t)L.ord.size(), t});
       if (split) {                                             // the parts of the cloud: their sizes need nothing of the device
         L.part_of_mesh[i] = (uint32_t)L.parts.size();
@@ -1139,14 +1140,8 @@ static void enc_layout_sequential(EncChunk &ck) {
     L.ord_at = A.put(L.uploads, L.ord.data(), sizeof(dsa::EncOrder) * L.ord.size(), false);
     L.ord_tiles_at = A.put(L.uploads, L.ord_tiles.data(), sizeof(dsa::EncOrderTile) * L.ord_tiles.size(), false);
   }
-  if (!L.means.empty()) {
-    L.mean_clouds_at = A.put(L.uploads, L.mean_clouds.data(), sizeof(dsa::EncMeanCloud) * L.mean_clouds.size(), false);
-    L.means_at = A.put(L.uploads, L.means.data(), sizeof(dsa::EncMean) * L.means.size(), false);
-  }
-  if (!L.votes.empty()) {
-    L.vote_clouds_at = A.put(L.uploads, L.vote_clouds.data(), sizeof(dsa::EncVoteCloud) * L.vote_clouds.size(), false);
-    L.votes_at = A.put(L.uploads, L.votes.data(), sizeof(dsa::EncVote) * L.votes.size(), false);
-  }
+  L.mean_pass.upload(L.means, A, L.uploads);
+  L.vote_pass.upload(L.votes, A, L.uploads);
   if (!L.parts.empty()) {
     L.parts_at = A.put(L.uploads, L.parts.data(), sizeof(dsa::EncPart) * L.parts.size(), false);
     L.part_tiles_at = A.put(L.uploads, L.part_tiles.data(), sizeof(dsa::EncPartTile) * L.part_tiles.size(), false);
@@ -1189,26 +1184,23 @@ static void enc_layout_sequential(EncChunk &ck) {
     L.max_rows = std::max(L.max_rows, V);
     if (compressed) enc_list_stream_regions(L.streams[s0 + na], A, true, false);
   }
-  if (!L.means.empty()) {                                      // the counts of every cloud and the sums of every masked stream: one range, zeroed as one
-    L.mean_zero_at = A.cur;
-    for (size_t o = 0; o < L.mean_clouds.size(); ++o) {
-      dsa::EncMeanCloud &MC = L.mean_clouds[o];
-      if (MC.count == 0) continue;
-      const uint64_t V = L.ord[o].n;
-      MC.cnt = A.take(4ull * V);
-      for (uint32_t k = MC.first; k < MC.first + MC.count; ++k) { dsa::EncMean &M = L.means[k]; M.vals = L.streams[L.mean_stream[k]].vals; M.acc = A.take(8ull * V * M.nc); }
+  // what a cell pass accumulates in: one range behind everything else, zeroed as one
+  auto range = [&](const EncCellPass &P, uint64_t &at, uint64_t &bytes, auto &&regions) { if (P.stream.empty()) return; at = A.cur; regions(); bytes = A.cur - at; };
+  range(L.mean_pass, L.mean_zero_at, L.mean_zero_bytes, [&] {      // the counts of every cloud and the sums of every masked stream
+    for (size_t o = 0; o < L.mean_pass.clouds.size(); ++o) {
+      const dsa::EncCellStreams &C = L.mean_pass.clouds[o];
+      if (C.count == 0) continue;
+      const uint64_t V = L.ord[o].n, cnt = A.take(4ull * V);
+      for (uint32_t k = C.first; k < C.first + C.count; ++k) { dsa::EncMean &M = L.means[k]; M.vals = L.streams[L.mean_pass.stream[k]].vals; M.cnt = cnt; M.acc = A.take(8ull * V * M.nc); }
     }
-    L.mean_zero_bytes = A.cur - L.mean_zero_at;
-  }
-  if (!L.votes.empty()) {                                      // the table, the counts and the values of every voted stream: one range behind the means', zeroed as one
-    L.vote_zero_at = A.cur;
+  });
+  range(L.vote_pass, L.vote_zero_at, L.vote_zero_bytes, [&] {      // behind the means': the table, the counts and the values of every voted stream
     for (size_t k = 0; k < L.votes.size(); ++k) {
       dsa::EncVote &X = L.votes[k];
       const uint64_t V = X.cap / 2u;
-      X.vals = L.streams[L.vote_stream[k]].vals;
+      X.vals = L.streams[L.vote_pass.stream[k]].vals;
       X.table = A.take(8ull * X.cap); X.best_cnt = A.take(4ull * V); X.best_val = A.take(8ull * V);
     }
-    L.vote_zero_bytes = A.cur - L.vote_zero_at;
-  }
+  });
   L.total_bytes = A.cur;
 }

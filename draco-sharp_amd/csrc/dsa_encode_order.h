@@ -148,9 +148,10 @@
 //                         cnt; a cell of one row keeps its value.  A pass of its own: kept[j]'s value is an addend of the first.
 // acc (i64[n nc] per masked stream) and cnt (u32[n] per cloud) are regions of their own at the end of the arena, one range that one
 // memset on the stream zeroes in front of the sum; no region is reused (the histograms are too small, the key buffers are the
-// lod's), nothing else grows.  The records are EncMean / EncMeanCloud, among the uploads: EncOrder is as it was, and so is every
-// kernel above.  The host coder's twin is synth::merge_means; tests/hostcheck/encmeans_host.cpp runs the serial forms in the
-// product's layout against it, tests/test_gpu_encode_means.py the ballots, shuffles and atomics.
+// lod's), nothing else grows.  The records are EncMean (every masked stream of a cloud carries the cloud's one cnt) and the cloud's
+// EncCellStreams, among the uploads: EncOrder is as it was, and so is every kernel above.  The host coder's twin is
+// synth::merge_means; tests/hostcheck/encmeans_host.cpp runs the serial forms in the product's layout against it,
+// tests/test_gpu_encode_means.py the ballots, shuffles and atomics.
 // gfx950, hipcc -O3 (VGPR / SGPR / LDS bytes per block): k_enc_mean_sum 24 / 45 / 0, store 23 / 29 / 0; no scratch, no spills, 8 waves per SIMD.
 //
 // dsa_encode_vote_sequential_batch with vote_attributes != 0 (point clouds, merge_points = 1): entry j of a voted attribute of nc <= 2
@@ -179,7 +180,8 @@
 //                         row keeps its value (its tuple wins).
 // The tables (u32[2 cap] per voted stream), best_cnt (u32[n]) and best_val (u64[n]) are regions of their own at the end of the arena,
 // behind the means', one range that one memset on the stream zeroes in front of the count; no region is reused.  The records are
-// EncVote / EncVoteCloud, among the uploads: EncOrder, EncMean and every kernel above are as they were.  The host coder's twin is
+// EncVote and an EncCellStreams of the votes' own per cloud, among the uploads; the five kernels of the two passes begin alike
+// (ord_cell_block).  The host coder's twin is
 // synth::merge_votes (a sort of every cell's tuples); tests/hostcheck/encvotes_host.cpp runs the serial forms in the product's layout
 // against it, tests/test_gpu_encode_votes.py the ballots, shuffles and atomics.
 // gfx950, hipcc -O3 (VGPR / SGPR / LDS bytes per block): k_enc_vote_count 28 / 52 / 0, best 16 / 50 / 0, store 9 / 30 / 0; no scratch, no spills, 8 waves per SIMD.
@@ -224,10 +226,13 @@ struct EncPart {                   // one per part of a split cloud, the parts o
 struct EncPartTile { uint32_t part, tile; };
 #define ORD_LOD_LEVELS 20u         // position_bits is at most 20 (enc_check_bits): L = bits - D + 1 <= 20
 struct EncLodTable { uint32_t count[ORD_LOD_LEVELS], base[ORD_LOD_LEVELS]; };      // m_l and base_l of a cloud (k_enc_lod_scan), zero from L on
-// mean_attributes: records of the mean kernels' own, so that EncOrder and the kernels that index it stay as they are
-struct EncMean { uint64_t vals, acc; uint32_t nc, pad; };       // one per masked stream, a cloud's side by side: the stream's vals i32[n nc], its sums i64[n nc], its components
-struct EncMeanCloud { uint64_t cnt; uint32_t first, count; };   // one per EncOrder record: the rows of every cell u32[n]; its `count` EncMean records from `first` on (0: none)
-// vote_attributes: records of the vote kernels' own, beside the means'
+// mean_attributes, vote_attributes: records of the cell passes' own, so that EncOrder and the kernels that index it stay as they are
+struct EncCellStreams { uint32_t first, count; };               // one per EncOrder record and pass: the cloud's `count` EncMean / EncVote records from `first` on (0: none)
+struct EncMean {                   // one per masked stream, a cloud's side by side
+  uint64_t vals, acc;              // the stream's vals i32[n nc], its sums i64[n nc]
+  uint64_t cnt;                    // u32[n]: the rows of every cell, one region per cloud, the same in all of its records
+  uint32_t nc, pad;                // components
+};
 struct EncVote {                   // one per voted stream, a cloud's side by side
   uint64_t vals;                   // the stream's vals i32[n nc]
   uint64_t table;                  // u32[2 cap]: slot s = (representative row + 1, rows counted); zeroed in front of k_enc_vote_count
@@ -235,7 +240,6 @@ struct EncVote {                   // one per voted stream, a cloud's side by si
   uint32_t nc, cap;                // components (1 or 2); slots, >= 2 n
   uint32_t full, pad;              // OUTPUT: not 0: a row found no slot (never at cap >= 2 n)
 };
-struct EncVoteCloud { uint32_t first, count; };                 // one per EncOrder record: its `count` EncVote records from `first` on (0: none)
 
 static inline uint32_t enc_order_passes(uint32_t bits) { return (3u * bits + 7u) / 8u; }
 
@@ -510,7 +514,21 @@ __global__ __launch_bounds__(WAVE) void k_enc_merge_compact(uint8_t *arena, cons
 #endif
 }
 
-// ---- mean_attributes (the header comment has the contract): behind the merge, in front of everything that reads `vals`
+// ---- the cell passes (mean_attributes, vote_attributes): behind the merge, in front of everything that reads `vals`, grid = (the
+// chunk's (cloud, tile) pairs, the most chosen streams a cloud has).  What every kernel of a pass begins with: this block's cloud and
+// tile, its entries e0 .. end -- over all entries of the cloud, or with `kept` over its KEPT ones -- and `rec`, the record of its
+// stream among the pass's nr.  False: nothing to do (no such tile or stream; never by the layout: no merge, a record beyond nr).
+struct EncCellBlock { const EncOrder *O; EncOrderTile T; uint32_t e0, end, rec; };
+__device__ __forceinline__ bool ord_cell_block(EncCellBlock &B, const EncOrder *clouds, const EncOrderTile *tiles, uint32_t nt, const EncCellStreams *streams, uint32_t nr, bool kept) {
+  if (blockIdx.x >= nt) return false;
+  B.T = tiles[blockIdx.x];
+  B.O = &clouds[B.T.cloud];
+  const EncCellStreams C = streams[B.T.cloud];
+  B.rec = C.first + blockIdx.y;
+  return B.O->merge && blockIdx.y < C.count && B.rec < nr && ord_tile(*B.O, B.T, kept ? B.O->m : B.O->n, B.e0, B.end);
+}
+
+// ---- mean_attributes (the header comment has the contract)
 // floor((2 S + cnt) / (2 cnt)) in 64 bits: the exact mean of cnt >= 1 integers whose sum is S, ties toward +infinity
 // (|S| <= 2^28 rows of 2^31: 2 S + cnt fits)
 __device__ __forceinline__ int32_t ord_mean(int64_t sum, uint32_t cnt) {
@@ -522,20 +540,18 @@ __device__ __forceinline__ int32_t ord_mean(int64_t sum, uint32_t cnt) {
 
 // grid = (the chunk's (cloud, tile) pairs, the most masked streams a cloud has): one wave per (tile, masked stream)
 __global__ __launch_bounds__(WAVE) void k_enc_mean_sum(uint8_t *arena, const EncOrder *clouds, const EncOrderTile *tiles, uint32_t nt,
-                                                       const EncMeanCloud *mclouds, const EncMean *means, uint32_t nm) {
-  if (blockIdx.x >= nt) return;
-  const EncOrderTile T = tiles[blockIdx.x];
-  const EncOrder &O = clouds[T.cloud];
-  const EncMeanCloud C = mclouds[T.cloud];
-  uint32_t e0, end;
-  if (!O.merge || blockIdx.y >= C.count || C.first + blockIdx.y >= nm || !ord_tile(O, T, O.n, e0, end)) return;
-  const EncMean M = means[C.first + blockIdx.y];
+                                                       const EncCellStreams *mclouds, const EncMean *means, uint32_t nm) {
+  EncCellBlock B;
+  if (!ord_cell_block(B, clouds, tiles, nt, mclouds, nm, false)) return;
+  const EncOrder &O = *B.O;
+  const uint32_t e0 = B.e0, end = B.end;
+  const EncMean M = means[B.rec];
   if (M.nc == 0u || M.nc > 4u) return;                         // (never by the layout)
   const uint32_t *row = (const uint32_t *)(arena + ord_sorted(O).row);
   const uint32_t *cells = (const uint32_t *)(arena + O.cells);
   const int32_t *vals = (const int32_t *)(arena + M.vals);
   unsigned long long *acc = (unsigned long long *)(arena + M.acc);       // (two's complement: the sums are signed)
-  uint32_t *cnt = (uint32_t *)(arena + C.cnt);
+  uint32_t *cnt = (uint32_t *)(arena + M.cnt);
   const bool counts = blockIdx.y == 0u;                        // the cloud's first masked stream counts the rows of every cell
   const uint32_t lane = threadIdx.x, nc = M.nc;
 #if defined(__HIPCC__)
@@ -573,19 +589,17 @@ __global__ __launch_bounds__(WAVE) void k_enc_mean_sum(uint8_t *arena, const Enc
 
 // grid as above, tiles over KEPT entries: a thread per (kept entry, component).  No lane needs another: the host check runs it as it stands.
 __global__ __launch_bounds__(256) void k_enc_mean_store(uint8_t *arena, const EncOrder *clouds, const EncOrderTile *tiles, uint32_t nt,
-                                                        const EncMeanCloud *mclouds, const EncMean *means, uint32_t nm) {
-  if (blockIdx.x >= nt) return;
-  const EncOrderTile T = tiles[blockIdx.x];
-  const EncOrder &O = clouds[T.cloud];
-  const EncMeanCloud C = mclouds[T.cloud];
-  uint32_t e0, end;
-  if (!O.merge || blockIdx.y >= C.count || C.first + blockIdx.y >= nm || !ord_tile(O, T, O.m, e0, end)) return;
-  const EncMean M = means[C.first + blockIdx.y];
+                                                        const EncCellStreams *mclouds, const EncMean *means, uint32_t nm) {
+  EncCellBlock B;
+  if (!ord_cell_block(B, clouds, tiles, nt, mclouds, nm, true)) return;
+  const EncOrder &O = *B.O;
+  const uint32_t e0 = B.e0, end = B.end;
+  const EncMean M = means[B.rec];
   if (M.nc == 0u || M.nc > 4u) return;                         // (never by the layout)
   const uint32_t nc = M.nc, total = (end - e0) * nc;
   const uint32_t *kept = (const uint32_t *)(arena + ord_kept(O));
   const long long *acc = (const long long *)(arena + M.acc);
-  const uint32_t *cnt = (const uint32_t *)(arena + C.cnt);
+  const uint32_t *cnt = (const uint32_t *)(arena + M.cnt);
   int32_t *vals = (int32_t *)(arena + M.vals);
   for (uint32_t i = threadIdx.x; i < total; i += blockDim.x) {
     const uint32_t j = e0 + i / nc, c = i % nc, r = kept[j], rows = cnt[j];
@@ -638,14 +652,12 @@ __device__ __forceinline__ bool ord_vote_insert(uint32_t *table, uint32_t cap, c
 
 // grid = (the chunk's (cloud, tile) pairs, the most voted streams a cloud has): one wave per (tile, voted stream)
 __global__ __launch_bounds__(WAVE) void k_enc_vote_count(uint8_t *arena, const EncOrder *clouds, const EncOrderTile *tiles, uint32_t nt,
-                                                         const EncVoteCloud *vclouds, EncVote *votes, uint32_t nv) {
-  if (blockIdx.x >= nt) return;
-  const EncOrderTile T = tiles[blockIdx.x];
-  const EncOrder &O = clouds[T.cloud];
-  const EncVoteCloud C = vclouds[T.cloud];
-  uint32_t e0, end;
-  if (!O.merge || blockIdx.y >= C.count || C.first + blockIdx.y >= nv || !ord_tile(O, T, O.n, e0, end)) return;
-  EncVote &V = votes[C.first + blockIdx.y];
+                                                         const EncCellStreams *vclouds, EncVote *votes, uint32_t nv) {
+  EncCellBlock B;
+  if (!ord_cell_block(B, clouds, tiles, nt, vclouds, nv, false)) return;
+  const EncOrder &O = *B.O;
+  const uint32_t e0 = B.e0, end = B.end;
+  EncVote &V = votes[B.rec];
   const uint32_t lane = threadIdx.x, nc = V.nc, cap = V.cap;
   if (nc == 0u || nc > 2u || cap == 0u) return;                // (never by the layout)
   const uint32_t *row = (const uint32_t *)(arena + ord_sorted(O).row);
@@ -690,17 +702,15 @@ __global__ __launch_bounds__(WAVE) void k_enc_vote_count(uint8_t *arena, const E
 // grid as above, tile t over slots 2 t ORD_TILE .. (cap = 2 n: two slots an entry; the cloud's last tile takes what is left): a
 // thread per slot.  phase 0: the most rows a tuple of every cell has; phase 1, a launch behind it: the smallest tuple among those.
 __global__ __launch_bounds__(256) void k_enc_vote_best(uint8_t *arena, const EncOrder *clouds, const EncOrderTile *tiles, uint32_t nt,
-                                                       const EncVoteCloud *vclouds, const EncVote *votes, uint32_t nv, uint32_t phase) {
-  if (blockIdx.x >= nt) return;
-  const EncOrderTile T = tiles[blockIdx.x];
-  const EncOrder &O = clouds[T.cloud];
-  const EncVoteCloud C = vclouds[T.cloud];
-  uint32_t e0, end;
-  if (!O.merge || blockIdx.y >= C.count || C.first + blockIdx.y >= nv || !ord_tile(O, T, O.n, e0, end)) return;
-  const EncVote V = votes[C.first + blockIdx.y];
+                                                       const EncCellStreams *vclouds, const EncVote *votes, uint32_t nv, uint32_t phase) {
+  EncCellBlock B;
+  if (!ord_cell_block(B, clouds, tiles, nt, vclouds, nv, false)) return;
+  const EncOrder &O = *B.O;
+  const uint32_t e0 = B.e0, end = B.end;
+  const EncVote V = votes[B.rec];
   const uint32_t nc = V.nc;
   if (nc == 0u || nc > 2u) return;                             // (never by the layout)
-  const uint64_t s_end = T.tile + 1u == O.tiles || 2ull * end > V.cap ? V.cap : 2ull * end;
+  const uint64_t s_end = B.T.tile + 1u == O.tiles || 2ull * end > V.cap ? V.cap : 2ull * end;
   const uint32_t *cells = (const uint32_t *)(arena + O.cells);
   const int32_t *vals = (const int32_t *)(arena + V.vals);
   const uint32_t *table = (const uint32_t *)(arena + V.table);
@@ -718,14 +728,12 @@ __global__ __launch_bounds__(256) void k_enc_vote_best(uint8_t *arena, const Enc
 
 // grid as above, tiles over KEPT entries: a thread per kept entry.  No lane needs another.
 __global__ __launch_bounds__(256) void k_enc_vote_store(uint8_t *arena, const EncOrder *clouds, const EncOrderTile *tiles, uint32_t nt,
-                                                        const EncVoteCloud *vclouds, const EncVote *votes, uint32_t nv) {
-  if (blockIdx.x >= nt) return;
-  const EncOrderTile T = tiles[blockIdx.x];
-  const EncOrder &O = clouds[T.cloud];
-  const EncVoteCloud C = vclouds[T.cloud];
-  uint32_t e0, end;
-  if (!O.merge || blockIdx.y >= C.count || C.first + blockIdx.y >= nv || !ord_tile(O, T, O.m, e0, end)) return;
-  const EncVote V = votes[C.first + blockIdx.y];
+                                                        const EncCellStreams *vclouds, const EncVote *votes, uint32_t nv) {
+  EncCellBlock B;
+  if (!ord_cell_block(B, clouds, tiles, nt, vclouds, nv, true)) return;
+  const EncOrder &O = *B.O;
+  const uint32_t e0 = B.e0, end = B.end;
+  const EncVote V = votes[B.rec];
   const uint32_t nc = V.nc;
   if (nc == 0u || nc > 2u) return;                             // (never by the layout)
   const uint32_t *kept = (const uint32_t *)(arena + ord_kept(O));

@@ -16,6 +16,14 @@ from . import native
 from .decoder import DeviceException, _raise, default_context
 
 
+def _shared(meshes, table, what):
+    """table(m) of the clouds of a call, which a mask over the attributes of the stream (`what`) needs to be one; None without clouds"""
+    tables = {table(m) for m in meshes}
+    if len(tables) > 1:
+        raise ValueError("%s is one mask for the call: its clouds must have the same attributes (give a mask per call otherwise)" % what)
+    return tables.pop() if tables else None
+
+
 class Config:
     """Subset of src/Draco/IO/Config.cs that the device path honours.
 
@@ -237,13 +245,11 @@ class Config:
         with the same attributes."""
         if self.mean_attributes != "all":
             return self.mean_attributes
-        masks = set()
-        for m in meshes:
+
+        def every(m):
             count = 1 + (m.normals is not None) + (m.texcoords is not None) + (m.generic is not None) + len(m.attributes)
-            masks.add(((1 << count) - 1) & ~1 & ~(2 if m.normals is not None else 0))
-        if len(masks) > 1:
-            raise ValueError("mean_attributes=\"all\" is one mask for the call: its clouds must have the same attributes (give a mask per call otherwise)")
-        return masks.pop() if masks else 0
+            return ((1 << count) - 1) & ~1 & ~(2 if m.normals is not None else 0)
+        return _shared(meshes, every, "mean_attributes=\"all\"") or 0
 
     def _native_mean(self, geometry, meshes):
         o = native.EncodeMeanOptions()
@@ -255,9 +261,7 @@ class Config:
     def _native_vote(self, geometry, meshes):
         """the options of dsa_encode_vote_sequential_batch for a call over `meshes`, which must have the same attributes: the mask
         counts the attributes of the stream"""
-        tables = {(m.normals is not None, m.texcoords is not None, m.generic is not None, len(m.attributes)) for m in meshes}
-        if len(tables) > 1:
-            raise ValueError("vote_attributes is one mask for the call: its clouds must have the same attributes (give a mask per call otherwise)")
+        _shared(meshes, lambda m: (m.normals is not None, m.texcoords is not None, m.generic is not None, len(m.attributes)), "vote_attributes")
         o = native.EncodeVoteOptions()
         native.lib().dsa_encode_default_vote_options(C.byref(o))
         o.mean = self._native_mean(geometry, meshes)

@@ -5,7 +5,7 @@
 // with mean_attributes != 0 (enc_order_stage: the sort, the merge, the zeroing of the sums and counts, the means, and whatever the
 // product runs behind them for the request -- with part_cells and lod_base_bits the levels, which turn row_entries into lod order,
 // the part sizes and the part boxes) in the arena the product's layout hands out for such a chunk (enc_layout_sequential with
-// EncRequest::point_order, merge_points and mean_attributes: stream records, order records, the EncMean / EncMeanCloud records, the
+// EncRequest::point_order, merge_points and mean_attributes: stream records, order records, the EncMean / EncCellStreams records, the
 // tile list and every region are the library's own; encorder_common.h has the harness) -- once forwards, once backwards -- against
 // the host coder (dsa_encode_host.h: synth::merge_points, synth::merge_means, and behind them synth::lod_parts) on the same points
 // and integers: at every kept row of a masked stream the mean of its cell, every other integer of every stream as it was, and not
@@ -43,8 +43,8 @@ static int run(const std::vector<const In *> &which, uint32_t bits, uint32_t par
   if (!R.ck->E->merged || R.ck->E->cells.size() != n) FAIL("the chunk's handle keeps no row entries");
   const uint32_t per_cloud = (mask >> 1 & 1u) + (mask >> 2 & 1u);
   if (!L.merge || L.lod != (part_cells != 0)) FAIL("%zu order records for %u clouds, %u passes", L.ord.size(), n, L.ord_passes);
-  if (L.mean_clouds.size() != n || L.means.size() != (size_t)per_cloud * n || L.mean_stream.size() != L.means.size() || L.mean_most != per_cloud) FAIL("%zu mean records for %u clouds", L.means.size(), n);
-  if (!R.sized(L.mean_clouds_at, sizeof(dsa::EncMeanCloud) * n) || !R.sized(L.means_at, sizeof(dsa::EncMean) * L.means.size())) FAIL("the mean records are not among the uploads");
+  if (L.mean_pass.clouds.size() != n || L.means.size() != (size_t)per_cloud * n || L.mean_pass.stream.size() != L.means.size() || L.mean_pass.most != per_cloud) FAIL("%zu mean records for %u clouds", L.means.size(), n);
+  if (!R.sized(L.mean_pass.clouds_at, sizeof(dsa::EncCellStreams) * n) || !R.sized(L.mean_pass.records_at, sizeof(dsa::EncMean) * L.means.size())) FAIL("the mean records are not among the uploads");
   if (L.mean_zero_at < L.input_bytes || L.mean_zero_at + L.mean_zero_bytes != L.total_bytes) FAIL("the sums and counts are not the end of the arena");
   std::vector<std::vector<uint32_t>> want_kept(n), want_cells(n), want_lod(n), want_lod_cells(n), want_levels(n);
   std::vector<Run::Ranges> want_ranges(n);
@@ -56,16 +56,17 @@ static int run(const std::vector<const In *> &which, uint32_t bits, uint32_t par
   for (uint32_t i = 0, rec = 0; i < n; ++i) {
     const In &c = *which[i];
     const dsa::EncOrder &O = L.ord[i];
-    const dsa::EncMeanCloud &MC = L.mean_clouds[i];
+    const dsa::EncCellStreams &MC = L.mean_pass.clouds[i];
     const uint32_t s0 = L.first_stream[i], room = part_cells ? std::min(part_cells, c.n) : c.n;      // the entries a set of stream records holds
     if (O.n != c.n || O.merge != 1 || O.stream0 != s0 || O.streams != 3 || (!part_cells && L.first_stream[i + 1] != s0 + 3) || O.cells == 0) FAIL("case %u: order record", i);
-    if (MC.first != rec || MC.count != per_cloud || !R.sized(MC.cnt, 4ull * c.n) || MC.cnt < L.mean_zero_at) FAIL("case %u: mean record of the cloud", i);
+    const uint64_t cnt = L.means[rec].cnt;                    // (per_cloud >= 1: the cloud's one count region, in every record of the cloud)
+    if (MC.first != rec || MC.count != per_cloud || !R.sized(cnt, 4ull * c.n) || cnt < L.mean_zero_at) FAIL("case %u: mean record of the cloud", i);
     for (uint32_t k = 1; k < 3; ++k) {
       const dsa::EncStream &S = L.streams[s0 + k];
       if (S.nc != k + 1 || S.e2v != dsa::ord_kept(O) || S.d == S.vals || !R.sized(S.vals, 4ull * S.nc * c.n) || !R.sized(S.d, 4ull * S.nc * room)) FAIL("case %u: stream %u", i, k);
       if (!((mask >> k) & 1u)) continue;
       const dsa::EncMean &M = L.means[rec];
-      if (L.mean_stream[rec] != s0 + k || M.vals != S.vals || M.nc != S.nc || !R.sized(M.acc, 8ull * S.nc * c.n) || M.acc < L.mean_zero_at) FAIL("case %u: mean record of stream %u", i, k);
+      if (L.mean_pass.stream[rec] != s0 + k || M.vals != S.vals || M.nc != S.nc || M.cnt != cnt || !R.sized(M.acc, 8ull * S.nc * c.n) || M.acc < L.mean_zero_at) FAIL("case %u: mean record of stream %u", i, k);
       ++rec;
     }
     R.write_positions(i);
@@ -97,7 +98,7 @@ static int run(const std::vector<const In *> &which, uint32_t bits, uint32_t par
     for (uint32_t r = 0; r < c.n; ++r) if (row_entries[r] != entries[r]) FAIL("case %u (%u points): row %u lies in entry %u, the host coder says %u", i, c.n, r, row_entries[r], entries[r]);
     std::vector<uint32_t> rows(m, 0);
     for (uint32_t r = 0; r < c.n; ++r) ++rows[want_cells[i][r]];
-    if (per_cloud) { const uint32_t *cnt = (const uint32_t *)(arena + L.mean_clouds[i].cnt); for (uint32_t j = 0; j < m; ++j) if (cnt[j] != rows[j]) FAIL("case %u: cell %u counted %u rows, it has %u", i, j, cnt[j], rows[j]); }
+    if (per_cloud) { const uint32_t *cnt = (const uint32_t *)(arena + L.means[L.mean_pass.clouds[i].first].cnt); for (uint32_t j = 0; j < m; ++j) if (cnt[j] != rows[j]) FAIL("case %u: cell %u counted %u rows, it has %u", i, j, cnt[j], rows[j]); }
     std::vector<int32_t> want[3];                             // the integers behind the means: the mean at every kept row of a masked stream
     for (uint32_t k = 0; k < 3; ++k) {
       const dsa::EncStream &S = R.records[s0 + k];

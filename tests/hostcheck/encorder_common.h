@@ -1,11 +1,11 @@
 // tests/hostcheck/encorder_common.h -- TEST INFRASTRUCTURE ONLY.
 //
-// What the host checks of the encoder's point-order stage share (encorder, encmerge, encsplit, enccellparts, enclod, encmeans): the
+// What the host checks of the encoder's point-order stage share (encorder, encmerge, encsplit, enccellparts, enclod, encmeans, encvotes): the
 // kernels of draco-sharp_amd/csrc/dsa_encode_order.h compiled for the host with AddressSanitizer + UBSan and run thread by thread by
 // the product's own launch sequence (enc_order_stage, dsa_encode_layout.h: what enc_stage_attributes runs for the request, nothing
 // restated here) in the arena the product's layout hands out (enc_layout_sequential: records, tile lists and every region are the
-// library's own), forwards or backwards, with every gap between two regions poisoned.  The sums and counts of the means are filled
-// with a pattern and poisoned until the stage zeroes its one range, as the product's memset does.  Each program keeps the
+// library's own), forwards or backwards, with every gap between two regions poisoned.  What the means and the votes accumulate in is
+// filled with a pattern and poisoned until the stage zeroes each pass's one range, as the product's memset does.  Each program keeps the
 // assertions that are its own.  Nothing here is linked into the product.
 #pragma once
 #include <sanitizer/asan_interface.h>
@@ -63,8 +63,9 @@ static bool read_cases(const char *path, uint32_t words, bool faces, std::vector
 struct Ask {
   uint32_t bits = 0;
   bool merge = false;
-  uint32_t part_points = 0, part_cells = 0, lod_base_bits = 0, mean_mask = 0;
+  uint32_t part_points = 0, part_cells = 0, lod_base_bits = 0, mean_mask = 0, vote_mask = 0;
   bool normals = false, listed = false;     // every cloud carries normals; or texture coordinates and a generic attribute of three bytes
+  bool label = false;                       // ... and behind them a listed uint8 attribute of one component
   bool is_mesh = false, compressed = false; // meshes with raw / with compressed indices
 };
 
@@ -75,6 +76,7 @@ struct Run {
   Ask ask;
   std::vector<dsa_mesh_attr_input> meshes;
   std::vector<EncMeshGrids> grids;
+  std::vector<dsa_attribute_input> labels;
   EncRequest rq;
   std::unique_ptr<EncChunk> ck;
   std::vector<std::pair<uint64_t, uint64_t>> log;
@@ -95,7 +97,7 @@ struct Run {
   // them and everything behind them zero, the region map
   bool begin(const std::vector<const In *> &cases, const Ask &a) {
     which = cases; n = (uint32_t)cases.size(); ask = a;
-    meshes.resize(n); grids.resize(n);
+    meshes.resize(n); grids.resize(n); labels.assign(a.label ? n : 0, dsa_attribute_input());
     memset(meshes.data(), 0, sizeof(dsa_mesh_attr_input) * n);
     bool any_grid = false;
     for (uint32_t i = 0; i < n; ++i) {
@@ -105,11 +107,17 @@ struct Run {
       if (a.normals) m.normals = c.pos.data();
       // (texcoords: 2 n floats, generic: 3 n bytes -- both inside the 3 n floats of the positions; their values are not read here)
       if (a.listed) { m.texcoords = c.pos.data(); m.generic = (const uint8_t *)c.pos.data(); m.generic_components = 3; }
+      if (a.label) {                                           // (its bytes are the positions' too)
+        dsa_attribute_input &x = labels[i];
+        memset(&x, 0, sizeof(x));
+        x.attribute_type = 4; x.data_type = 2; x.num_components = 1; x.unique_id = DSA_UNIQUE_ID_DEFAULT; x.values = c.pos.data();
+        meshes[i].attributes = &x; meshes[i].num_attributes = 1;
+      }
       if (a.is_mesh) { m.num_faces = (uint32_t)(c.faces.size() / 3); m.faces = c.faces.data(); }
       if (c.has_grid) { synth::Grid &g = grids[i].slot[0]; memcpy(g.origin, c.grid, 12); g.range = c.grid[3]; g.mode = 1; any_grid = true; }
     }
     rq.n = n; rq.meshes = meshes.data(); rq.sequential = true; rq.point_order = true; rq.merge_points = a.merge;
-    rq.part_points = a.part_points; rq.part_cells = a.part_cells; rq.lod_base_bits = a.lod_base_bits; rq.mean_attributes = a.mean_mask;
+    rq.part_points = a.part_points; rq.part_cells = a.part_cells; rq.lod_base_bits = a.lod_base_bits; rq.mean_attributes = a.mean_mask; rq.vote_attributes = a.vote_mask;
     if (any_grid) rq.grids = grids.data();
     memset(&rq.seq, 0, sizeof(rq.seq));
     synth::Options d;
@@ -142,14 +150,15 @@ struct Run {
     memcpy(arena + ck->L.ord[i].vals, a.vals.data(), 12ull * c.n);
   }
   // every gap between two regions poisoned, and the regions `untouched` (of slots that stay empty: no kernel touches them); the
-  // means' range holds what an arena used before leaves there, poisoned until the stage zeroes it
+  // means' and the votes' ranges hold what an arena used before leaves there, poisoned until the stage zeroes them
   void poison(const std::vector<std::pair<uint64_t, uint64_t>> &untouched = {}) {
     const EncLayout &L = ck->L;
-    if (L.mean_zero_bytes) memset(arena + L.mean_zero_at, 0xAB, L.mean_zero_bytes);
+    const std::pair<uint64_t, uint64_t> ranges[2] = {{L.mean_zero_at, L.mean_zero_bytes}, {L.vote_zero_at, L.vote_zero_bytes}};
+    for (const auto &r : ranges) if (r.second) memset(arena + r.first, 0xAB, r.second);
     ASAN_POISON_MEMORY_REGION(arena, store.size());
     for (const auto &r : region) ASAN_UNPOISON_MEMORY_REGION(arena + r.first, r.second);
     for (const auto &r : untouched) ASAN_POISON_MEMORY_REGION(arena + r.first, r.second);
-    if (L.mean_zero_bytes) ASAN_POISON_MEMORY_REGION(arena + L.mean_zero_at, L.mean_zero_bytes);
+    for (const auto &r : ranges) if (r.second) ASAN_POISON_MEMORY_REGION(arena + r.first, r.second);
   }
   void unpoison() { ASAN_UNPOISON_MEMORY_REGION(arena, store.size()); }
   // the product's stage for the request, every thread of every grid one after the other

@@ -5,7 +5,7 @@
 // sequence for a chunk with vote_attributes != 0 (enc_order_stage: the sort, the merge, the means where the request has them, the
 // zeroing of the tables, counts and values, the votes, and whatever the product runs behind them for the request -- with part_cells
 // and lod_base_bits the levels, which turn row_entries into lod order, the part sizes and the part boxes) in the arena the product's
-// layout hands out for such a chunk (enc_layout_sequential: stream records, order records, the EncVote / EncVoteCloud records, the
+// layout hands out for such a chunk (enc_layout_sequential: stream records, order records, the EncVote / EncCellStreams records, the
 // tile list and every region are the library's own; encorder_common.h has the harness) -- once forwards, once backwards, so that the
 // tiles arrive at the tables in another order and the slots are placed differently -- against the host coder (dsa_encode_host.h:
 // synth::merge_points, synth::merge_votes, synth::merge_means), with which the kernels share nothing: at every kept row of the voted
@@ -44,50 +44,19 @@ static Pairs pairs_of(const std::vector<uint32_t> &cells, const std::vector<int3
   for (size_t r = 0; r < cells.size(); ++r) out.insert(std::make_tuple(cells[r], q[nc * r], nc == 2 ? q[nc * r + 1] : 0));
   return out;
 }
-// Run::begin, then a uint8 label of one component listed for every cloud (its bytes are the cloud's positions': the values are
-// not read here) and the chunk checked and laid out once more, as begin does it
-static bool begin_with_labels(Run &R, std::vector<dsa_attribute_input> &labels, const std::vector<const In *> &which, const Ask &ask) {
-  if (!R.begin(which, ask)) return false;
-  labels.assign(R.n, dsa_attribute_input());
-  for (uint32_t i = 0; i < R.n; ++i) {
-    dsa_attribute_input &a = labels[i];
-    memset(&a, 0, sizeof(a));
-    a.attribute_type = 4; a.data_type = 2; a.num_components = 1; a.unique_id = DSA_UNIQUE_ID_DEFAULT; a.values = which[i]->pos.data();
-    R.meshes[i].attributes = &a; R.meshes[i].num_attributes = 1;
-  }
-  R.rq.vote_attributes = VOTE_MASK;
-  R.log.clear(); R.region.clear();
-  R.ck.reset(new EncChunk(R.rq, 0, R.n, R.n));
-  R.ck->region_log = &R.log;
-  for (uint32_t i = 0; i < R.n; ++i) { enc_check_sequential_mesh(*R.ck, i); if (!R.ck->good(i)) return R.fail("case " + std::to_string(i) + " refused: " + R.ck->E->messages[i]); }
-  enc_layout_sequential(*R.ck);
-  const EncLayout &L = R.ck->L;
-  R.store.assign(L.total_bytes + 256, 0);
-  R.arena = R.store.data();
-  for (const EncUpload &u : L.uploads) {
-    if (u.off >= L.input_bytes || u.off + u.bytes > L.input_bytes || u.narrow) return R.fail("an upload outside the inputs");
-    if (u.bytes) memcpy(R.arena + u.off, u.src, u.bytes);
-  }
-  for (const auto &r : R.log) { if (r.first + r.second > L.total_bytes) return R.fail("a region outside the arena"); R.region[r.first] = std::max(R.region[r.first], r.second); }
-  R.laid = R.records = L.streams;
-  return true;
-}
-
 // the cases `which` as one chunk of a request of point clouds; starve: the first cloud with more than STARVED_SLOTS (cell, tuple)
 // pairs gets a table of STARVED_SLOTS slots
 static int run(const std::vector<const In *> &which, uint32_t bits, uint32_t part_cells, uint32_t lod_bits, uint32_t mean_mask, bool backwards, bool starve, uint64_t &points, uint64_t &cells, uint64_t &ties) {
   Run R;
-  std::vector<dsa_attribute_input> labels;
   Ask ask;
-  ask.bits = bits; ask.merge = true; ask.mean_mask = mean_mask; ask.listed = true; ask.part_cells = part_cells; ask.lod_base_bits = lod_bits;
-  R.rq.vote_attributes = 1u << VOTED[0];                      // (begin sets the fields of the request it knows and leaves this one; the label's bit joins it with the label)
-  if (!begin_with_labels(R, labels, which, ask)) FAIL("%s", R.why.c_str());
+  ask.bits = bits; ask.merge = true; ask.mean_mask = mean_mask; ask.vote_mask = VOTE_MASK; ask.listed = ask.label = true; ask.part_cells = part_cells; ask.lod_base_bits = lod_bits;
+  if (!R.begin(which, ask)) FAIL("%s", R.why.c_str());
   const EncLayout &L = R.L();
   const uint32_t n = R.n;
   uint8_t *arena = R.arena;
   if (!R.rq.merged() || !R.rq.votes() || R.rq.means() != (mean_mask != 0) || R.rq.lod() != (part_cells != 0)) FAIL("the request is not one with votes");
-  if (L.vote_clouds.size() != n || L.votes.size() != 2ull * n || L.vote_stream.size() != 2ull * n || L.vote_most != 2u) FAIL("%zu vote records for %u clouds", L.votes.size(), n);
-  if (!R.sized(L.vote_clouds_at, sizeof(dsa::EncVoteCloud) * n) || !R.sized(L.votes_at, sizeof(dsa::EncVote) * 2ull * n)) FAIL("the vote records are not among the uploads");
+  if (L.vote_pass.clouds.size() != n || L.votes.size() != 2ull * n || L.vote_pass.stream.size() != 2ull * n || L.vote_pass.most != 2u) FAIL("%zu vote records for %u clouds", L.votes.size(), n);
+  if (!R.sized(L.vote_pass.clouds_at, sizeof(dsa::EncCellStreams) * n) || !R.sized(L.vote_pass.records_at, sizeof(dsa::EncVote) * 2ull * n)) FAIL("the vote records are not among the uploads");
   if (L.vote_zero_at < L.input_bytes || L.vote_zero_at + L.vote_zero_bytes != L.total_bytes || L.vote_zero_at < L.mean_zero_at + L.mean_zero_bytes) FAIL("tables, counts and values are not the end of the arena, behind the means'");
   std::vector<std::vector<uint32_t>> want_kept(n), want_cells(n);
   std::vector<std::vector<int32_t>> given[STREAMS];           // per stream and cloud: the integers as they come in
@@ -96,14 +65,14 @@ static int run(const std::vector<const In *> &which, uint32_t bits, uint32_t par
   for (uint32_t i = 0; i < n; ++i) {
     const In &c = *which[i];
     const dsa::EncOrder &O = L.ord[i];
-    const dsa::EncVoteCloud &VC = L.vote_clouds[i];
+    const dsa::EncCellStreams &VC = L.vote_pass.clouds[i];
     const uint32_t s0 = L.first_stream[i];
     if (O.n != c.n || O.merge != 1 || O.stream0 != s0 || O.streams != STREAMS || O.cells == 0) FAIL("case %u: order record", i);
     if (VC.first != 2u * i || VC.count != 2u) FAIL("case %u: vote record of the cloud", i);
     for (uint32_t v = 0; v < 2u; ++v) {
       const dsa::EncVote &V = L.votes[2u * i + v];
       const dsa::EncStream &S = L.streams[s0 + VOTED[v]];
-      if (L.vote_stream[2u * i + v] != s0 + VOTED[v] || S.nc != NC[VOTED[v]] || V.nc != S.nc || V.vals != S.vals || V.cap < 2u * c.n || V.full != 0u || !R.sized(S.vals, 4ull * S.nc * c.n)) FAIL("case %u: vote record of stream %u", i, VOTED[v]);
+      if (L.vote_pass.stream[2u * i + v] != s0 + VOTED[v] || S.nc != NC[VOTED[v]] || V.nc != S.nc || V.vals != S.vals || V.cap < 2u * c.n || V.full != 0u || !R.sized(S.vals, 4ull * S.nc * c.n)) FAIL("case %u: vote record of stream %u", i, VOTED[v]);
       if (!R.sized(V.table, 8ull * V.cap) || !R.sized(V.best_cnt, 4ull * c.n) || !R.sized(V.best_val, 8ull * c.n) || V.table < L.vote_zero_at || V.best_cnt < L.vote_zero_at || V.best_val < L.vote_zero_at) FAIL("case %u: the regions of the vote of stream %u", i, VOTED[v]);
       if (V.cap > 2u * c.n + 64u) FAIL("case %u: %u slots for %u points: a small cloud pays for a tile", i, V.cap, c.n);
     }
@@ -117,17 +86,14 @@ static int run(const std::vector<const In *> &which, uint32_t bits, uint32_t par
       memcpy(arena + L.streams[s0 + k].vals, given[k][i].data(), 4ull * nc * c.n);
     }
     synth::merge_points(c.pos.data(), c.n, (int)bits, R.grid(i), want_kept[i], want_cells[i]);
-    if (starve && starved == DSA_INVALID && pairs_of(want_cells[i], given[1][i], 2u).size() > STARVED_SLOTS) { starved = i; ((dsa::EncVote *)(arena + L.votes_at))[2u * i].cap = STARVED_SLOTS; }
+    if (starve && starved == DSA_INVALID && pairs_of(want_cells[i], given[1][i], 2u).size() > STARVED_SLOTS) { starved = i; ((dsa::EncVote *)(arena + L.vote_pass.records_at))[2u * i].cap = STARVED_SLOTS; }
   }
   if (starve && starved == DSA_INVALID) FAIL("no cloud to starve");
   R.poison();
-  ASAN_UNPOISON_MEMORY_REGION(arena + L.vote_zero_at, L.vote_zero_bytes);      // what an arena used before leaves there, poisoned until the stage zeroes it
-  memset(arena + L.vote_zero_at, 0xAB, L.vote_zero_bytes);
-  ASAN_POISON_MEMORY_REGION(arena + L.vote_zero_at, L.vote_zero_bytes);
   if (!R.stage(backwards)) FAIL("%s", R.why.c_str());
   R.gather();
   const dsa::EncOrder *clouds = R.clouds();
-  const dsa::EncVote *votes = (const dsa::EncVote *)(arena + L.votes_at);
+  const dsa::EncVote *votes = (const dsa::EncVote *)(arena + L.vote_pass.records_at);
   for (uint32_t i = 0; i < n; ++i) {
     const In &c = *which[i];
     const uint32_t s0 = L.first_stream[i], m = (uint32_t)want_kept[i].size();

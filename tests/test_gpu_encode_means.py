@@ -200,6 +200,41 @@ def test_refusals(ctx):
         dsa.DracoEncoder(ctx).EncodeBatch([plain, with_normals], config("all", position_bits=11))
 
 
+def mixed_clouds(seed):
+    """three clouds of 1, 65 and 1 025 points at 6 bits (one entry, a wave step and one, a tile and one), the first with one listed
+    attribute, the others with three: a label of one byte, a colour, a float at 10 bits"""
+    out = []
+    for k, n in enumerate((1, 65, T + 1)):
+        c = mc.half_duplicated(n, seed + n, bits=6)
+        rng = np.random.default_rng(seed + 7 * n)
+        atts = [dsa.Attribute(rng.integers(0, 4, (n, 1)).astype(np.uint8))]
+        if k:
+            atts += [dsa.Attribute(rng.integers(0, 256, (n, 3)).astype(np.uint8)), dsa.Attribute(rng.random((n, 1)).astype(np.float32), quantization_bits=10)]
+        out.append(cpt.cloud(c, attributes=atts))
+    return out
+
+
+def test_clouds_with_different_attribute_lists_in_one_call(ctx):
+    """an integer mask over all three listed attributes and the clouds of mixed_clouds in one call.  The mask names two attributes the
+    first cloud does not have: the library refuses that cloud alone (test_refusals has the words) and so does the twin, so every cloud
+    that is laid out lists as many masked streams as the mask has bits -- a block beyond a cloud's own streams (the kernels' return
+    on blockIdx.y) is a guard that no accepted call reaches.  Held here: the refused cloud in front takes no record, the two clouds
+    behind it read their own, and their streams, kept rows and row entries are the twin's"""
+    clouds, mask = mixed_clouds(990), 0b1110
+    cfg = config(mask, position_bits=6)
+    got = dsa.DracoEncoder(ctx).TryEncodeBatch(clouds, cfg, keep=True)
+    assert len(got) == 3
+    with pytest.raises(ValueError, match="does not have"):
+        synth.encode_merged(mean_attributes=mask, **cpt.cpu_args(clouds[0], cfg))
+    assert isinstance(got[0], Exception) and all(w in str(got[0]) for w in ("mean_attributes 0xe", "attribute 2", "has 2 attributes")), got[0]
+    for i in (1, 2):
+        stream, kept, cells = synth.encode_merged(mean_attributes=mask, **cpt.cpu_args(clouds[i], cfg))
+        assert got[i] == stream, (i, got[i] if isinstance(got[i], Exception) else len(got[i]), len(stream))
+        assert len(kept) < len(clouds[i].positions) and all(np.array_equal(r, kept) for r in got.encoded.entry_rows(i))
+        assert np.array_equal(got.encoded.row_entries(i), cells)
+    got.encoded.close()
+
+
 def test_an_explicit_grid_on_a_masked_float_attribute(ctx):
     """the means are means of the integers on the caller's grid, and the header carries that grid"""
     rng = np.random.default_rng(970)

@@ -17,6 +17,7 @@ import mergecases as mc
 import ordercases as oc
 import test_gpu_encode_cell_parts as cpt
 import test_gpu_encode_lod as lodt
+import test_gpu_encode_means as mnt
 import votecases as vc
 import draco_sharp_amd as dsa
 import draco_sharp_amd.synth as synth
@@ -203,6 +204,30 @@ def test_refusals(ctx):
         dsa.Config(vote_attributes=[1], mean_attributes=[1, 2], merge_points=dsa.MERGE_CELLS, **base)
     with pytest.raises(ValueError, match="same attributes"):
         dsa.DracoEncoder(ctx).EncodeBatch([plain, with_normals], config(2, position_bits=11))
+
+
+def test_clouds_with_different_attribute_lists_in_one_call(ctx):
+    """the three clouds of test_gpu_encode_means.mixed_clouds (1, 65 and 1 025 points; one listed attribute, then three) through the
+    entry point itself -- the package refuses such a call -- with a mask that names the one-component attribute only the larger
+    clouds have.  As with the means, the library refuses the first cloud alone and so does the twin: no cloud that is laid out has
+    fewer voted streams than the mask has bits, and the kernels' return on blockIdx.y guards what no accepted call reaches.  Held
+    here: the refused cloud in front takes no record, the two behind it read their own and are the twin's, kept rows and row
+    entries included"""
+    clouds, mask = mnt.mixed_clouds(991), 0b1000
+    cfg = config(mask, position_bits=6)
+    with pytest.raises(ValueError, match="same attributes"):
+        cfg._native_vote(0, clouds)
+    st, h = call(ctx, clouds, cfg._native_vote(0, clouds[1:]))
+    assert st == 0
+    ranges, got = cpt.handle_of(ctx, h, clouds, 1)
+    assert ranges == [(0, 1), (1, 1), (2, 1)] and len(got) == 3
+    with pytest.raises(ValueError, match="does not have"):
+        synth.encode_merged(vote_attributes=mask, **cpt.cpu_args(clouds[0], cfg))
+    assert got[0][0] == native.DSA_ERR_INVALID_ARGUMENT and all(w in got[0][1] for w in ("vote_attributes 0x8", "attribute 3", "has 2 attributes")), got[0]
+    for i in (1, 2):
+        stream, kept, cells = synth.encode_merged(vote_attributes=mask, **cpt.cpu_args(clouds[i], cfg))
+        assert got[i][:2] == (0, stream), (i, got[i][0])
+        assert len(kept) < len(clouds[i].positions) and got[i][2] == np.asarray(kept, np.uint32).tobytes() and got[i][3] == np.asarray(cells, np.uint32).tobytes()
 
 
 def test_the_refused_cases(ctx):
