@@ -122,6 +122,11 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
     // order of the rows.  Positions, normals and attributes of 3 or 4 components are not voted on: a cloud whose mask names them, or
     // an attribute it does not have, fails alone.  An attribute takes the vote or the mean, not both.  Needs MergePoints 1.
     public uint VoteAttributes { get; set; }
+    // MeanNormals (dsa_encode_normal_mean_sequential_batch): true: WITH MergePoints the normals of every cloud that has them carry, per
+    // kept point, the code of the normalised sum of the unit normals of the cell's rows, by the rule in 64-bit integers on the
+    // octahedral codes that the header states, whatever the order of the rows; a cell of one row keeps its code.  A cloud without
+    // normals is coded as before.  PartCells, LodBaseBits, MeanAttributes and VoteAttributes compose with it.  Needs MergePoints 1.
+    public bool MeanNormals { get; set; }
     public struct PartBox
     {
         public uint Input, Part, Parts, FirstEntry, NumPoints, PositionBits;
@@ -240,6 +245,7 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
             }
             if (MeanAttributes != 0 && MergePoints != 1) throw new ArgumentException("MeanAttributes needs MergePoints 1: the mean is the mean over the points of a cell");
             if (VoteAttributes != 0 && MergePoints != 1) throw new ArgumentException("VoteAttributes needs MergePoints 1: the vote is a vote of the points of a cell");
+            if (MeanNormals && MergePoints != 1) throw new ArgumentException("MeanNormals needs MergePoints 1: the mean normal is the mean over the points of a cell");
             if ((VoteAttributes & MeanAttributes) != 0) throw new ArgumentException("VoteAttributes and MeanAttributes share a bit: an attribute carries the most frequent value of its cell or the mean, not both");
             if (LodBaseBits != 0 && PartCells == 0) throw new ArgumentException("LodBaseBits needs PartCells >= 1: every level is cut into parts of at most PartCells points");
             if (PartPoints != 0 || PartCells != 0)
@@ -252,7 +258,19 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
                 po.PartPoints = PartPoints;
                 var ain = new DsaMeshAttrInput[items.Count];
                 for (int i = 0; i < items.Count; ++i) { ain[i].Mesh.Mesh = inputs[i]; Extras(items[i], null, (uint)items[i].PointsCount, ref ain[i], pins); }
-                if (VoteAttributes != 0)        // (the widest call only when its option is set)
+                if (MeanNormals)                // (the widest call only when its option is set)
+                {
+                    NativeMethods.dsa_encode_default_normal_mean_options(out var no);
+                    no.Vote.Mean.Lod.CellParts.Split = po;
+                    no.Vote.Mean.Lod.CellParts.PartCells = PartCells;
+                    no.Vote.Mean.Lod.LodBaseBits = LodBaseBits;
+                    no.Vote.Mean.MeanAttributes = MeanAttributes;
+                    no.Vote.VoteAttributes = VoteAttributes;
+                    no.MeanNormals = 1;
+                    fixed (DsaMeshAttrInput* p = ain)
+                        NativeMethods.Check(NativeMethods.dsa_encode_normal_mean_sequential_batch(_ctx, (uint)items.Count, p, null, in no, out encoded), _ctx, "dsa_encode_normal_mean_sequential_batch");
+                }
+                else if (VoteAttributes != 0)   // (the widest call only when its option is set)
                 {
                     NativeMethods.dsa_encode_default_vote_options(out var vo);
                     vo.Mean.Lod.CellParts.Split = po;
@@ -340,7 +358,17 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
                 mo.MergePoints = MergePoints;
                 var ain = new DsaMeshAttrInput[items.Count];
                 for (int i = 0; i < items.Count; ++i) { ain[i].Mesh.Mesh = inputs[i]; Extras(items[i], null, (uint)items[i].PointsCount, ref ain[i], pins); }
-                if (VoteAttributes != 0)        // (the widest call only when its option is set)
+                if (MeanNormals)                // (the widest call only when its option is set)
+                {
+                    NativeMethods.dsa_encode_default_normal_mean_options(out var no);
+                    no.Vote.Mean.Lod.CellParts.Split.Merge = mo;
+                    no.Vote.Mean.MeanAttributes = MeanAttributes;
+                    no.Vote.VoteAttributes = VoteAttributes;
+                    no.MeanNormals = 1;
+                    fixed (DsaMeshAttrInput* p = ain)
+                        NativeMethods.Check(NativeMethods.dsa_encode_normal_mean_sequential_batch(_ctx, (uint)items.Count, p, null, in no, out encoded), _ctx, "dsa_encode_normal_mean_sequential_batch");
+                }
+                else if (VoteAttributes != 0)   // (the widest call only when its option is set)
                 {
                     NativeMethods.dsa_encode_default_vote_options(out var vo);
                     vo.Mean.Lod.CellParts.Split.Merge = mo;

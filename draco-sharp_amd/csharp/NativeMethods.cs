@@ -322,6 +322,15 @@ internal unsafe struct DsaEncodeVoteOptions
     public fixed int Reserved[7];   // zero
 }
 
+// dsa_encode_normal_mean_options (dsa_encode_normal_mean_sequential_batch)
+[StructLayout(LayoutKind.Sequential)]
+internal unsafe struct DsaEncodeNormalMeanOptions
+{
+    public DsaEncodeVoteOptions Vote;
+    public uint MeanNormals;        // 0: the request of the vote call; 1: the normals of every kept point are the mean normal of its cell (needs MergePoints 1)
+    public fixed int Reserved[7];   // zero
+}
+
 // dsa_lod_info (dsa_encoded_lod_info)
 [StructLayout(LayoutKind.Sequential)]
 internal unsafe struct DsaLodInfo
@@ -497,6 +506,8 @@ internal static unsafe partial class NativeMethods
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_mean_sequential_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, in DsaEncodeMeanOptions options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern void dsa_encode_default_vote_options(out DsaEncodeVoteOptions options);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_vote_sequential_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, in DsaEncodeVoteOptions options, out IntPtr encoded);
+    [DllImport(Lib)] internal static extern void dsa_encode_default_normal_mean_options(out DsaEncodeNormalMeanOptions options);
+    [DllImport(Lib)] internal static extern DsaStatus dsa_encode_normal_mean_sequential_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, in DsaEncodeNormalMeanOptions options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encoded_parts(IntPtr encoded, uint input, out uint firstStream, out uint count);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encoded_part_info(IntPtr encoded, uint stream, out DsaPartInfo info);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_rows_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, DsaMeshAttributeCorners* corners, in DsaEncodeRowsOptions options, out IntPtr encoded);

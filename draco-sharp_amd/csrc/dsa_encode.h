@@ -37,6 +37,8 @@
 //                                                attributes' integers at every kept row, behind the merge
 //                              k_enc_vote_*      dsa_encode_vote_sequential_batch, vote_attributes != 0: the most frequent tuple of the cell
 //                                                into the voted attributes' integers at every kept row, beside the means
+//                              k_enc_normal_*    dsa_encode_normal_mean_sequential_batch, mean_normals = 1: the mean normal of the cell into
+//                                                the normals' octahedral codes at every kept row, beside the two above
 //         (dsa_encode_layout.h) the request of an entry point, the state of a chunk, the per-mesh checks and plans, the arena layout
 // Every entry point fills an EncRequest and calls encode_request; a chunk of it goes through the stages of encode_chunk (or of
 // encode_sequential_chunk, dsa_encode_sequential.h) on a lane.
@@ -124,20 +126,7 @@ __device__ void enc_oct_from_float(const float *in, int32_t bits, int32_t &s, in
   else { s0 = 1; s1 = 0; s2 = 0; }
   int32_t i0 = (int32_t)floor(__dadd_rn(__dmul_rn(s0, (double)center), 0.5));
   int32_t i1 = (int32_t)floor(__dadd_rn(__dmul_rn(s1, (double)center), 0.5));
-  int32_t i2 = center - abs(i0) - abs(i1);
-  if (i2 < 0) { if (i1 > 0) i1 += i2; else i1 -= i2; i2 = 0; }
-  if (s2 < 0) i2 = -i2;
-  if (i0 >= 0) { s = i1 + center; t = i2 + center; }
-  else {
-    s = i1 < 0 ? abs(i2) : max_value - abs(i2);
-    t = i2 < 0 ? abs(i1) : max_value - abs(i1);
-  }
-  // canonicalize
-  if ((s == 0 && t == 0) || (s == 0 && t == max_value) || (s == max_value && t == 0)) { s = max_value; t = max_value; }
-  else if (s == 0 && t > center) t = center - (t - center);
-  else if (s == max_value && t < center) t = center + (center - t);
-  else if (t == max_value && s < center) s = center + (center - s);
-  else if (t == 0 && s > center) s = center - (s - center);
+  enc_oct_from_scaled(center, max_value, i0, i1, s2 < 0, s, t);      // (the tail and the canonicalisation: dsa_encode_schemes.h, with the mean normals)
 }
 
 template <bool GRID>      // (as for k_enc_bounds)
@@ -1580,6 +1569,14 @@ static dsa_status enc_check_options(dsa_context *ctx, const dsa_encode_vote_opti
   ENC_RESERVED(o, 7, "dsa_encode_vote_options");
   return enc_check_options(ctx, o.mean, null_argument);
 }
+// ... or with the mean normal of the cell in the normals of the kept points (dsa_encode_order.h)
+static dsa_status enc_check_options(dsa_context *ctx, const dsa_encode_normal_mean_options &o, bool null_argument) {
+  const dsa_encode_merge_options &m = o.vote.mean.lod.cell_parts.split.merge;
+  if (o.mean_normals > 1) ENC_REFUSE("mean_normals %u: 0 (the request of dsa_encode_vote_sequential_batch) or 1 (the normals of every kept point are the mean normal of its cell)", (unsigned)o.mean_normals);
+  if (o.mean_normals != 0 && m.merge_points != 1) ENC_REFUSE("mean_normals %u needs merge_points 1 (it was %d): the mean normal is the mean over the points of a cell", (unsigned)o.mean_normals, (int)m.merge_points);
+  ENC_RESERVED(o, 7, "dsa_encode_normal_mean_options");
+  return enc_check_options(ctx, o.vote, null_argument);
+}
 #undef ENC_RESERVED
 #undef ENC_REFUSE
 
@@ -1848,8 +1845,9 @@ static dsa_status encode_edgebreaker(dsa_context *ctx, uint32_t n, const dsa_mes
   rq.track_rows = w.track_rows == 1;
   return encode_checked(ctx, rq, grids, o.grid.repair.topology == 1, out);
 }
-static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_vote_options &v, dsa_encoded **out) {
-  if (enc_check_options(ctx, v, !ctx || !out || (n && !meshes)) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_normal_mean_options &nm, dsa_encoded **out) {
+  if (enc_check_options(ctx, nm, !ctx || !out || (n && !meshes)) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+  const dsa_encode_vote_options &v = nm.vote;
   const dsa_encode_mean_options &a = v.mean;
   const dsa_encode_lod_options &l = a.lod;
   const dsa_encode_cell_parts_options &c = l.cell_parts;
@@ -1859,10 +1857,16 @@ static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh
   EncRequest rq;
   rq.n = n; rq.meshes = meshes; rq.sequential = true;
   rq.seq = o.sequential; rq.point_order = o.point_order == 1; rq.merge_points = m.merge_points == 1; rq.part_points = (uint32_t)s.part_points; rq.part_cells = (uint32_t)c.part_cells; rq.lod_base_bits = (uint32_t)l.lod_base_bits;
-  rq.mean_attributes = a.mean_attributes; rq.vote_attributes = v.vote_attributes;
+  rq.mean_attributes = a.mean_attributes; rq.vote_attributes = v.vote_attributes; rq.mean_normals = nm.mean_normals == 1;
   const dsa_status st = encode_checked(ctx, rq, grids, false, out);
   if (st == DSA_OK && rq.lod()) (*out)->lod_bits = rq.lod_base_bits;
   return st;
+}
+static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_vote_options &v, dsa_encoded **out) {
+  dsa_encode_normal_mean_options nm;
+  dsa_encode_default_normal_mean_options(&nm);
+  nm.vote = v;
+  return encode_sequential(ctx, n, meshes, grids, nm, out);
 }
 static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_mean_options &a, dsa_encoded **out) {
   dsa_encode_vote_options v;
@@ -1974,6 +1978,11 @@ void dsa_encode_default_vote_options(dsa_encode_vote_options *o) {
   if (!o) return;
   memset(o, 0, sizeof(*o));
   dsa_encode_default_mean_options(&o->mean);
+}
+void dsa_encode_default_normal_mean_options(dsa_encode_normal_mean_options *o) {
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  dsa_encode_default_vote_options(&o->vote);
 }
 void dsa_encode_default_repair_options(dsa_encode_repair_options *o) {
   if (!o) return;
@@ -2114,6 +2123,11 @@ dsa_status dsa_encode_mean_sequential_batch(dsa_context *ctx, uint32_t n, const 
 // dsa_encode_order.h); vote_attributes = 0 is the very request of the call above, which arrives here.
 dsa_status dsa_encode_vote_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_vote_options *options, dsa_encoded **out) {
   DSA_GUARD(ctx, [&] { dsa_encode_vote_options o; dsa_encode_default_vote_options(&o); if (options) o = *options; return encode_sequential(ctx, n, meshes, grids, o, out); }());
+}
+// ... or, with mean_normals = 1, the mean normal of the cell in the normals of every kept point (k_enc_normal_*, dsa_encode_order.h);
+// mean_normals = 0 is the very request of the call above, which arrives here.
+dsa_status dsa_encode_normal_mean_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_normal_mean_options *options, dsa_encoded **out) {
+  DSA_GUARD(ctx, [&] { dsa_encode_normal_mean_options o; dsa_encode_default_normal_mean_options(&o); if (options) o = *options; return encode_sequential(ctx, n, meshes, grids, o, out); }());
 }
 
 struct dsa_welded {

@@ -912,12 +912,14 @@ struct Octa {
     double sv[3];
     if (abs_sum > 1e-6) { double sc = 1.0 / abs_sum; sv[0] = v[0] * sc; sv[1] = v[1] * sc; sv[2] = v[2] * sc; }
     else { sv[0] = 1; sv[1] = 0; sv[2] = 0; }
-    int iv[3];
-    iv[0] = (int)std::floor(sv[0] * center + 0.5);
-    iv[1] = (int)std::floor(sv[1] * center + 0.5);
-    iv[2] = center - std::abs(iv[0]) - std::abs(iv[1]);
+    from_scaled((int)std::floor(sv[0] * center + 0.5), (int)std::floor(sv[1] * center + 0.5), sv[2] < 0, s, t);
+  }
+  // the quantiser's tail, shared with merge_mean_normals: the code of the vector scaled to L1 norm `center` whose first two
+  // components rounded to i0 and i1 and whose third is negative or not
+  void from_scaled(int i0, int i1, bool z_negative, int &s, int &t) const {
+    int iv[3] = {i0, i1, center - std::abs(i0) - std::abs(i1)};
     if (iv[2] < 0) { if (iv[1] > 0) iv[1] += iv[2]; else iv[1] -= iv[2]; iv[2] = 0; }
-    if (sv[2] < 0) iv[2] *= -1;
+    if (z_negative) iv[2] *= -1;
     from_int_vector(iv, s, t);
   }
   bool in_diamond(int s, int t) const { return (uint32_t)std::abs(s) + (uint32_t)std::abs(t) <= (uint32_t)center; }
@@ -1175,6 +1177,7 @@ struct MeshIn {
   const ExtraAttr *extras = nullptr; uint32_t num_extras = 0;      // written behind the attributes above, in list order
   const Grid *pos_grid = nullptr, *uv_grid = nullptr;              // the caller's quantisation grids (null: the attribute's own bounds)
   const int32_t *uv_portable = nullptr;                            // sequential streams: the integers `uvs` is coded as, in place of the quantiser's output (ExtraAttr::portable)
+  const int32_t *normal_portable = nullptr;                        // ... and the octahedral codes (s, t) `normals` is coded as, nv rows of 2
 };
 
 // Why the extras of a mesh cannot be written ("" when they can): the attribute's index in the list and the field.
@@ -2050,6 +2053,7 @@ static void encode_sequential(const MeshIn &in, const Options &opt, bool mesh, b
       Octa o(opt.normal_bits);
       a.vals.resize((size_t)in.nv * 2);
       for (uint32_t v = 0; v < in.nv; ++v) { int s, t; o.from_float_vector(in.normals + (size_t)v * 3, s, t); a.vals[(size_t)v * 2] = s; a.vals[(size_t)v * 2 + 1] = t; }
+      if (in.normal_portable) a.vals.assign(in.normal_portable, in.normal_portable + (size_t)in.nv * 2);
     } else if (a.att_type == 3) { quantize(in.uvs, in.nv, 2, opt.uv_bits, a); if (in.uv_portable) a.vals.assign(in.uv_portable, in.uv_portable + (size_t)in.nv * 2); }
     else { a.vals.resize((size_t)in.nv * a.nc); for (size_t k = 0; k < (size_t)in.nv * a.nc; ++k) a.vals[k] = generic_value(in.generic, k, a.data_type); }
   }
@@ -2173,6 +2177,54 @@ static void merge_votes(const int32_t *q, uint32_t n, int nc, const std::vector<
     }
     votes[(size_t)j * nc] = t[best].first;
     if (nc == 2) votes[(size_t)j * nc + 1] = t[best].second;
+  }
+}
+// The mean normal of every cell of the kept points (dsa_encode_normal_mean_sequential_batch, mean_normals = 1; the device's kernels are
+// k_enc_normal_* of dsa_encode_order.h, with which this shares nothing but the quantiser's tail, Octa::from_scaled): q[n * 2] the
+// octahedral codes (s, t) the plain call codes for the rows at `bits` normal bits, row_entries and m as merge_points has them;
+// codes[m * 2].  With c = center and rdiv(a, b) = floor((2 a + b) / (2 b)), floor division:
+//   a row's code gives a = s - c, b = t - c and the integer vector v of L1 norm c it stands for: (c - |a| - |b|, a, b) inside the
+//   diamond |a| + |b| <= c, else (c - |a| - |b|, sg(a) (c - |b|), sg(b) (c - |a|)), sg(0) = +1;
+//   its unit vector in Q30 is u_k = rdiv(v_k 2^42, isqrt((v . v) 2^24)), isqrt the exact floor square root;
+//   U = the sum of u over the cnt rows of the cell, M_k = rdiv(U_k, cnt), A = |M_0| + |M_1| + |M_2|;
+//   A = 0 (the normals cancel): the code of (1, 0, 0), as the quantiser codes a zero vector; else the quantiser's tail on
+//   i0 = rdiv(M_0 c, A), i1 = rdiv(M_1 c, A) and the sign of M_2.
+// All in 64 bits: a function of the set of rows.  A cell of one row keeps its code.
+static inline int64_t floor_div(int64_t a, int64_t b) { int64_t q = a / b; if ((a % b != 0) && ((a < 0) != (b < 0))) --q; return q; }
+static inline int64_t round_div(int64_t num, int64_t den) { return floor_div(2 * num + den, 2 * den); }
+static inline int64_t floor_sqrt(uint64_t x) {       // bit by bit, no floating point
+  uint64_t r = 0;
+  for (int b = 31; b >= 0; --b) { const uint64_t t = r | (1ull << b); if (t * t <= x) r = t; }
+  return (int64_t)r;
+}
+static void merge_mean_normals(const int32_t *q, uint32_t n, int bits, const std::vector<uint32_t> &row_entries, uint32_t m, std::vector<int32_t> &codes) {
+  check(q != nullptr && n > 0 && bits >= 2 && bits <= 20 && row_entries.size() == n, "merge_mean_normals: n rows of octahedral codes at 2 - 20 bits and their row entries");
+  const Octa o(bits);
+  const int64_t c = o.center;
+  std::vector<int64_t> sum((size_t)m * 3, 0);
+  std::vector<uint32_t> cnt(m, 0), first(m, 0);
+  for (uint32_t r = 0; r < n; ++r) {
+    const uint32_t j = row_entries[r];
+    check(j < m, "merge_mean_normals: a row entry at or above m");
+    const int64_t s = q[(size_t)r * 2], t = q[(size_t)r * 2 + 1];
+    check(s >= 0 && s <= o.max_value && t >= 0 && t <= o.max_value, "merge_mean_normals: a code outside 0 .. max_value");
+    const int64_t a = s - c, b = t - c, aa = std::llabs(a), ab = std::llabs(b);
+    int64_t v[3] = {c - aa - ab, a, b};
+    if (aa + ab > c) { v[1] = (a < 0 ? -1 : 1) * (c - ab); v[2] = (b < 0 ? -1 : 1) * (c - aa); }
+    const int64_t len = floor_sqrt((uint64_t)(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]) << 24);
+    for (int k = 0; k < 3; ++k) sum[(size_t)j * 3 + k] += round_div(v[k] * ((int64_t)1 << 42), len);
+    if (cnt[j]++ == 0) first[j] = r;
+  }
+  codes.resize((size_t)m * 2);
+  for (uint32_t j = 0; j < m; ++j) {
+    check(cnt[j] >= 1, "merge_mean_normals: a cell without rows");
+    if (cnt[j] == 1) { codes[(size_t)j * 2] = q[(size_t)first[j] * 2]; codes[(size_t)j * 2 + 1] = q[(size_t)first[j] * 2 + 1]; continue; }
+    int64_t M[3], A = 0;
+    for (int k = 0; k < 3; ++k) { M[k] = round_div(sum[(size_t)j * 3 + k], cnt[j]); A += std::llabs(M[k]); }
+    int s, t;
+    if (A == 0) o.from_scaled(o.center, 0, false, s, t);
+    else o.from_scaled((int)round_div(M[0] * c, A), (int)round_div(M[1] * c, A), M[2] < 0, s, t);
+    codes[(size_t)j * 2] = s; codes[(size_t)j * 2 + 1] = t;
   }
 }
 // The sorted order of a cloud in parts of at most part_points points (dsa_encode_split_sequential_batch, part_points >= 1): P =

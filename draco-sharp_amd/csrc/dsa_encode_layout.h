@@ -253,6 +253,8 @@ struct EncRequest {
   bool means() const { return merged() && seq.geometry == 0 && mean_attributes != 0; }
   uint32_t vote_attributes = 0;            // dsa_encode_vote_sequential_batch (with merge_points): bit a: attribute a of the stream carries the most frequent value of its cell (k_enc_vote_*)
   bool votes() const { return merged() && seq.geometry == 0 && vote_attributes != 0; }
+  bool mean_normals = false;               // dsa_encode_normal_mean_sequential_batch (with merge_points): the normals of a cloud that has them carry the mean normal of the cell (k_enc_normal_*)
+  bool normal_means() const { return merged() && seq.geometry == 0 && mean_normals; }
   int rows_kind() const { return weld_sink ? dsa_encoded::ROWS_NONE : (sequential ? (point_order ? dsa_encoded::ROWS_ORDERED : dsa_encoded::ROWS_LINEAR) : (track_rows ? dsa_encoded::ROWS_TRACKED : dsa_encoded::ROWS_NONE)); }
   dsa_encode_level_options level{};        // Edgebreaker streams
   dsa_encode_sequential_options seq{};     // sequential streams
@@ -294,7 +296,7 @@ struct EncArena {
   uint64_t take(uint64_t bytes) { const uint64_t at = cur; cur = (cur + bytes + 255) & ~255ull; if (log) log->push_back({at, bytes}); return at; }
   uint64_t put(std::vector<EncUpload> &ups, const void *src, uint64_t bytes, bool narrow) { const uint64_t at = take(bytes); ups.push_back({at, src, (size_t)bytes, narrow}); return at; }
 };
-// A cell pass of the point-order stage (dsa_encode_order.h: the means, the votes) beside its typed records, one per chosen stream.
+// A cell pass of the point-order stage (dsa_encode_order.h: the means, the votes, the mean normals) beside its typed records, one per chosen stream.
 struct EncCellPass {
   std::vector<dsa::EncCellStreams> clouds;  // one per cloud, parallel to EncLayout::ord
   std::vector<uint32_t> stream;             // stream[k]: the stream of the pass's record k
@@ -354,11 +356,13 @@ struct EncLayout {
   // EncRequest::means, EncRequest::votes: a cell pass each (EncCellPass above) with its typed records, one per masked / voted stream,
   // and what it accumulates in, one range of the arena that is zeroed on the stream in front of its kernels: the means' holds the
   // sums and counts, the votes' behind it tables, counts and values.  The vote records come back behind the stage: EncVote::full
-  // (enc_vote_refusals)
-  EncCellPass mean_pass, vote_pass;
-  uint64_t mean_zero_at = 0, mean_zero_bytes = 0, vote_zero_at = 0, vote_zero_bytes = 0;
+  // (enc_vote_refusals).  EncRequest::normal_means: a third pass, a record per cloud that has normals, its range -- vector sums and
+  // counts -- behind the votes'; a chunk without normals has no record, no range and no launch of it
+  EncCellPass mean_pass, vote_pass, normal_pass;
+  uint64_t mean_zero_at = 0, mean_zero_bytes = 0, vote_zero_at = 0, vote_zero_bytes = 0, normal_zero_at = 0, normal_zero_bytes = 0;
   std::vector<dsa::EncMean> means;
   std::vector<dsa::EncVote> votes;
+  std::vector<dsa::EncNormal> normals;
 };
 
 // ---- the point-order stage of a chunk whose layout has order records (dsa_encode_order.h has the kernels and their contracts): the
@@ -375,7 +379,7 @@ template <class Launch, class Zero, class After>
 static inline bool enc_order_stage(Launch &&launch, Zero &&zero, After &&after, const EncLayout &L, bool meshes, uint32_t gx_faces,
                                    uint8_t *arena, dsa::EncStream *streams, uint32_t ns) {
   const uint32_t nc = (uint32_t)L.ord.size(), nt = (uint32_t)L.ord_tiles.size(), np = (uint32_t)L.parts.size(), npt = (uint32_t)L.part_tiles.size();
-  const uint32_t nm = (uint32_t)L.means.size(), nv = (uint32_t)L.votes.size(), wave = (uint32_t)WAVE;
+  const uint32_t nm = (uint32_t)L.means.size(), nv = (uint32_t)L.votes.size(), nn = (uint32_t)L.normals.size(), wave = (uint32_t)WAVE;
   if (nc == 0 || nt == 0) return true;
   dsa::EncOrder *clouds = (dsa::EncOrder *)(arena + L.ord_at);
   const dsa::EncOrderTile *tiles = (const dsa::EncOrderTile *)(arena + L.ord_tiles_at);
@@ -383,6 +387,7 @@ static inline bool enc_order_stage(Launch &&launch, Zero &&zero, After &&after, 
   const dsa::EncPartTile *part_tiles = (const dsa::EncPartTile *)(arena + L.part_tiles_at);
   const dsa::EncMean *means = (const dsa::EncMean *)(arena + L.mean_pass.records_at);
   dsa::EncVote *votes = (dsa::EncVote *)(arena + L.vote_pass.records_at);
+  const dsa::EncNormal *normals = (const dsa::EncNormal *)(arena + L.normal_pass.records_at);
   // a cell pass: its range zeroed, kernels(the clouds' records, grid y), its lap
   auto cell_pass = [&](const EncCellPass &P, uint64_t zero_at, uint64_t zero_bytes, const char *lap, auto &&kernels) -> bool {
     if (P.stream.empty()) return true;
@@ -417,6 +422,11 @@ static inline bool enc_order_stage(Launch &&launch, Zero &&zero, After &&after, 
         launch(dsa::k_enc_vote_best, nt, most, 256u, arena, clouds, tiles, nt, vclouds, (const dsa::EncVote *)votes, nv, 0u);
         launch(dsa::k_enc_vote_best, nt, most, 256u, arena, clouds, tiles, nt, vclouds, (const dsa::EncVote *)votes, nv, 1u);
         launch(dsa::k_enc_vote_store, nt, most, 256u, arena, clouds, tiles, nt, vclouds, (const dsa::EncVote *)votes, nv);
+      })) return false;
+  // mean_normals: the mean normal of the cell into the normals' codes at every kept row, beside the two above (another stream), in front of the same readers
+  if (!cell_pass(L.normal_pass, L.normal_zero_at, L.normal_zero_bytes, "cell normals", [&](const dsa::EncCellStreams *nclouds, uint32_t most) {
+        launch(dsa::k_enc_normal_sum, nt, most, wave, arena, clouds, tiles, nt, nclouds, normals, nn);
+        launch(dsa::k_enc_normal_store, nt, most, 256u, arena, clouds, tiles, nt, nclouds, normals, nn);
       })) return false;
   if (L.lod && np) {           // lod_base_bits: the kept order by (level, kept); the slot sizer below cuts every level into its parts
     launch(dsa::k_enc_lod_levels, nt, 1u, wave, arena, clouds, tiles, nt);
@@ -1068,6 +1078,9 @@ static void enc_layout(EncChunk &ck) {
 // EncRequest::votes (merge with vote_attributes): likewise an EncCellStreams per cloud and an EncVote per voted stream among the uploads;
 // behind the means' range per voted stream a table of 2 n slots of 8 bytes (a crowded chunk of small clouds pays for its points, not
 // for tiles), u32[n] counts and u64[n] values, one range that is zeroed on the stream in front of k_enc_vote_count.
+// EncRequest::normal_means (merge with mean_normals): an EncCellStreams per cloud and an EncNormal per cloud that has normals among the
+// uploads; behind the votes' range per such cloud a u32[n] count region and an i64[3 n] sum region, one range that is zeroed on the
+// stream in front of k_enc_normal_sum.  A chunk without normals has none of it.
 static void enc_layout_sequential(EncChunk &ck) {
   EncLayout &L = ck.L;
   const bool is_mesh = ck.rq.seq.geometry == 1, compressed = is_mesh && ck.rq.seq.compress_connectivity == 1, ordered = ck.rq.point_order;
@@ -1108,6 +1121,13 @@ static void enc_layout_sequential(EncChunk &ck) {
         X.nc = L.streams[s].nc; X.cap = 2u * V;                // (V <= 2^28: enc_check_sequential_mesh)
         L.votes.push_back(X);
       });
+      // the normals of the cloud, attribute 1 where it has them (plan_sequential_attributes)
+      if (ck.rq.normal_means()) L.normal_pass.list(atts.size() > 1 && atts[1].att_type == 1 && !atts[1].extra_values ? 2u : 0u, s0, atts.size(), [&](uint32_t s) {
+        dsa::EncNormal X;
+        memset(&X, 0, sizeof(X));
+        X.bits = L.streams[s].bits;
+        L.normals.push_back(X);
+      });
       for (uint32_t t = 0; t < O.tiles; ++t) L.ord_tiles.push_back({(uint32_t)L.ord.size(), t});
       if (split) {                                             // the parts of the cloud: their sizes need nothing of the device
         L.part_of_mesh[i] = (uint32_t)L.parts.size();
@@ -1142,6 +1162,7 @@ static void enc_layout_sequential(EncChunk &ck) {
   }
   L.mean_pass.upload(L.means, A, L.uploads);
   L.vote_pass.upload(L.votes, A, L.uploads);
+  L.normal_pass.upload(L.normals, A, L.uploads);
   if (!L.parts.empty()) {
     L.parts_at = A.put(L.uploads, L.parts.data(), sizeof(dsa::EncPart) * L.parts.size(), false);
     L.part_tiles_at = A.put(L.uploads, L.part_tiles.data(), sizeof(dsa::EncPartTile) * L.part_tiles.size(), false);
@@ -1200,6 +1221,15 @@ static void enc_layout_sequential(EncChunk &ck) {
       const uint64_t V = X.cap / 2u;
       X.vals = L.streams[L.vote_pass.stream[k]].vals;
       X.table = A.take(8ull * X.cap); X.best_cnt = A.take(4ull * V); X.best_val = A.take(8ull * V);
+    }
+  });
+  range(L.normal_pass, L.normal_zero_at, L.normal_zero_bytes, [&] {  // behind the votes': the counts and the vector sums of every cloud with normals
+    for (size_t o = 0; o < L.normal_pass.clouds.size(); ++o) {
+      const dsa::EncCellStreams &C = L.normal_pass.clouds[o];
+      if (C.count == 0) continue;
+      const uint64_t V = L.ord[o].n;
+      dsa::EncNormal &X = L.normals[C.first];
+      X.vals = L.streams[L.normal_pass.stream[C.first]].vals; X.cnt = A.take(4ull * V); X.acc = A.take(24ull * V);
     }
   });
   L.total_bytes = A.cur;

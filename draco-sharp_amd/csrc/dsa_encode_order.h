@@ -29,7 +29,7 @@
 // k_enc_gather behind it puts every attribute in the order.  Nothing between the quantisers and k_enc_gather goes through the host.
 // Every cloud fits the same three steps a pass; a one-workgroup LDS sort for clouds of one tile was not built (DESIGN.md 7.3 has
 // what the crowded batch of small clouds costs).
-// The order of all steps of this file -- the sort, then the merge, the means, the levels, the part sizes and the part boxes where the
+// The order of all steps of this file -- the sort, then the merge, the means, the votes, the mean normals, the levels, the part sizes and the part boxes where the
 // request has them -- is written down once, in enc_order_stage (dsa_encode_layout.h), which the product and every host check run.
 // Which buffer of a pair a step reads follows from EncOrder::last alone (ord_sorted, ord_kept, ord_part_rows below).
 //
@@ -185,6 +185,41 @@
 // synth::merge_votes (a sort of every cell's tuples); tests/hostcheck/encvotes_host.cpp runs the serial forms in the product's layout
 // against it, tests/test_gpu_encode_votes.py the ballots, shuffles and atomics.
 // gfx950, hipcc -O3 (VGPR / SGPR / LDS bytes per block): k_enc_vote_count 28 / 52 / 0, best 16 / 50 / 0, store 9 / 30 / 0; no scratch, no spills, 8 waves per SIMD.
+//
+// dsa_encode_normal_mean_sequential_batch with mean_normals = 1 (point clouds, merge_points = 1): entry j of the normals of a cloud that
+// has them carries the code of the normalised sum of the unit normals of the cnt rows of cell j, by a rule in 64-bit integers on the
+// octahedral codes (s, t) the plain call codes at normal_bits = b -- the mean of the integers s and t themselves points elsewhere
+// wherever a cell lies across the fold (x < 0) or the diamond edge.  With max_value = 2^b - 2, c = max_value / 2 and rdiv(num, den) =
+// floor((2 num + den) / (2 den)), floor division:
+//   1. a = s - c, b' = t - c; v = (c - |a| - |b'|, a, b') where |a| + |b'| <= c, else (c - |a| - |b'|, sg(a) (c - |b'|), sg(b') (c - |a|)),
+//      sg(0) = +1: the inverse of the quantiser's tail, |v|_1 = c
+//   2. u_k = rdiv(v_k << 42, len), len = isqrt((v . v) << 24) the exact floor square root (the argument is below 2^62, 2 |v_k| 2^42 +
+//      len below 2^63): the unit vector in Q30
+//   3. U = the sum of u over the rows of the cell (at most 2^28 rows: below 2^59)
+//   4. M_k = rdiv(U_k, cnt)
+//   5. A = |M_0| + |M_1| + |M_2|; A = 0 (the normals cancel): i0 = c, i1 = 0, z positive, what the quantiser makes of a zero vector;
+//      else i0 = rdiv(M_0 c, A), i1 = rdiv(M_1 c, A), z negative iff M_2 < 0; then the quantiser's own tail from i2 = c - |i0| - |i1|
+//      through the canonicalisation (enc_oct_from_scaled, dsa_encode_schemes.h: one copy, which enc_oct_from_float calls too)
+//   6. a cell of one row keeps its code
+// -- a function of the SET of rows.  As the means, written into the stream's `vals` at row kept[j], behind the merge, beside the means
+// and the votes (the normals are in neither mask), in front of k_enc_lod_*, k_enc_part_cells, k_enc_part_bounds and k_enc_gather, on
+// the merge's (cloud, tile) list; launched only when a cloud of the chunk has normals:
+//   k_enc_normal_sum      a wave per tile, 64 sorted entries a step: the head ballot, the run's first lane and the last lane of
+//                         every (run, step) as k_enc_mean_sum finds them; steps 1 and 2 per lane -- the square root from a double
+//                         seed put right in integers (ord_isqrt), the three quotients as unsigned 64-bit divisions of magnitudes
+//                         (ord_normal_unit): both exact, no result depends on a float rounding -- then three segmented inclusive
+//                         sums in int64 (ord_wave_incl) and one 64-bit atomicAdd per (run, step) and component into acc[3 j + k],
+//                         one 32-bit atomicAdd of the run's rows into cnt[j].  Integer adds commute.
+//   k_enc_normal_store    a thread per kept entry, tiles over KEPT entries: steps 4 - 6 into vals[2 kept[j] ..]
+// acc (i64[3 n]) and cnt (u32[n], the pass's own: the means count theirs, every count region is added to once) per cloud with normals
+// are regions of their own at the end of the arena, behind the votes', one range that one memset on the stream zeroes in front of the
+// sum; no region is reused.  The records are EncNormal and an EncCellStreams of the pass's own per cloud, among the uploads; both
+// kernels begin with ord_cell_block.  EncOrder and every kernel above are as they were.  The host coder's twin is
+// synth::merge_mean_normals (serial, a bitwise square root, floor division of signed numbers); tests/hostcheck/encnormalmeans_host.cpp
+// runs the serial forms in the product's layout against it, tests/test_gpu_encode_normal_means.py the ballots, shuffles and atomics.
+// Not built: a vote over normals, weighted means, means per coarser lod cell, mean normals of meshes.
+// gfx950, hipcc -O3 (VGPR / SGPR / LDS bytes per block): k_enc_normal_sum 40 / 52 / 0 (the three 64-bit divisions are inline code, no
+// call), store 31 / 41 / 0; no scratch, no spills, 8 waves per SIMD.
 #pragma once
 #include <stdint.h>
 
@@ -239,6 +274,11 @@ struct EncVote {                   // one per voted stream, a cloud's side by si
   uint64_t best_cnt, best_val;     // u32[n] the most rows a tuple of cell j has; u64[n] the largest ~pack among the tuples with so many
   uint32_t nc, cap;                // components (1 or 2); slots, >= 2 n
   uint32_t full, pad;              // OUTPUT: not 0: a row found no slot (never at cap >= 2 n)
+};
+struct EncNormal {                 // mean_normals: one per cloud that has normals
+  uint64_t vals, acc;              // the normal stream's codes i32[2 n]; the sums of its rows' unit vectors in Q30, i64[3 n]
+  uint64_t cnt;                    // u32[n]: the rows of every cell, counted by this pass for itself (the means' count theirs)
+  uint32_t bits, pad;              // normal_bits
 };
 
 static inline uint32_t enc_order_passes(uint32_t bits) { return (3u * bits + 7u) / 8u; }
@@ -746,6 +786,124 @@ __global__ __launch_bounds__(256) void k_enc_vote_store(uint8_t *arena, const En
     const unsigned long long pack = ~best_val[j];
     if (nc == 2u) { vals[2ull * r] = (int32_t)((uint32_t)(pack >> 32) ^ 0x80000000u); vals[2ull * r + 1u] = (int32_t)((uint32_t)pack ^ 0x80000000u); }
     else vals[r] = (int32_t)((uint32_t)pack ^ 0x80000000u);
+  }
+}
+
+// ---- mean_normals (the header comment has the contract): behind the merge, beside the means and the votes, in front of everything that reads `vals`
+// rdiv(num, den) = floor((2 num + den) / (2 den)), den > 0: num / den rounded to the nearest integer, ties toward +infinity (ord_mean in 64 bits)
+__device__ __forceinline__ int64_t ord_rdiv(int64_t num, int64_t den) {
+  const int64_t a = 2 * num + den, b = 2 * den;
+  int64_t q = a / b;
+  if (a % b < 0) --q;                                          // (C++ division truncates toward zero)
+  return q;
+}
+// the exact floor square root of x < 2^62: a double seed (off by at most one either way, whatever its rounding), put right in integers
+__device__ __forceinline__ uint64_t ord_isqrt(uint64_t x) {
+  uint64_t r = (uint64_t)sqrt((double)x);
+  if (r > 0x80000000ull) r = 0x80000000ull;                    // (r * r and (r + 1)^2 below stay inside 64 bits)
+  while (r * r > x) --r;
+  while ((r + 1ull) * (r + 1ull) <= x) ++r;
+  return r;
+}
+// The unit vector of the octahedral code (s, t) in Q30, steps 1 and 2 of the rule: the integer vector v of L1 norm `center` the code
+// stands for, u_k = rdiv(v_k << 42, len), len = isqrt((v . v) << 24).  The quotient is taken of magnitudes, one unsigned division a
+// component: for v_k < 0, floor((-a + len) / (2 len)) = -floor((a + len - 1) / (2 len)) with a = 2 |v_k| 2^42 > len.
+__device__ __forceinline__ void ord_normal_unit(int32_t s, int32_t t, int32_t center, long long u[3]) {
+  const int32_t a = s - center, b = t - center, aa = a < 0 ? -a : a, ab = b < 0 ? -b : b;
+  int32_t v[3];
+  if (aa + ab <= center) { v[0] = center - aa - ab; v[1] = a; v[2] = b; }
+  else { v[0] = center - aa - ab; v[1] = a < 0 ? ab - center : center - ab; v[2] = b < 0 ? aa - center : center - aa; }
+  uint64_t n2 = 0;
+  for (int k = 0; k < 3; ++k) n2 += (uint64_t)((int64_t)v[k] * v[k]);
+  const uint64_t len = n2 < (1ull << 38) ? ord_isqrt(n2 << 24) : 0ull;      // (|v|_1 = center < 2^19 by the quantiser: the comparison keeps a code from elsewhere inside 62 bits)
+  for (int k = 0; k < 3; ++k) {
+    const uint64_t mag = (uint64_t)(v[k] < 0 ? -(int64_t)v[k] : (int64_t)v[k]) << 43;       // 2 |v_k| 2^42 < 2^62
+    const uint64_t q = len ? (mag + len - (v[k] < 0 ? 1ull : 0ull)) / (2ull * len) : 0ull;
+    u[k] = v[k] < 0 ? -(long long)q : (long long)q;
+  }
+}
+// The code of the mean vector M, step 5: the quantiser's tail (enc_oct_from_scaled, dsa_encode_schemes.h) on rdiv(M_k center, |M|_1).
+__device__ __forceinline__ void ord_normal_code(const int64_t M[3], int32_t center, int32_t max_value, int32_t &s, int32_t &t) {
+  const int64_t A = (M[0] < 0 ? -M[0] : M[0]) + (M[1] < 0 ? -M[1] : M[1]) + (M[2] < 0 ? -M[2] : M[2]);
+  int32_t i0 = center, i1 = 0;                                 // (the normals cancel: what the quantiser makes of a zero vector)
+  if (A != 0) { i0 = (int32_t)ord_rdiv(M[0] * center, A); i1 = (int32_t)ord_rdiv(M[1] * center, A); }       // (|M_k| <= 2^30 + 1, center < 2^19)
+  enc_oct_from_scaled(center, max_value, i0, i1, A != 0 && M[2] < 0, s, t);
+}
+
+// grid = (the chunk's (cloud, tile) pairs, 1): one wave per tile of a cloud with normals
+__global__ __launch_bounds__(WAVE) void k_enc_normal_sum(uint8_t *arena, const EncOrder *clouds, const EncOrderTile *tiles, uint32_t nt,
+                                                         const EncCellStreams *nclouds, const EncNormal *normals, uint32_t nn) {
+  EncCellBlock B;
+  if (!ord_cell_block(B, clouds, tiles, nt, nclouds, nn, false)) return;
+  const EncOrder &O = *B.O;
+  const uint32_t e0 = B.e0, end = B.end;
+  const EncNormal N = normals[B.rec];
+  if (N.bits < 2u || N.bits > 20u) return;                     // (never by the layout)
+  const int32_t center = (int32_t)(((1u << N.bits) - 2u) / 2u);
+  const uint32_t *row = (const uint32_t *)(arena + ord_sorted(O).row);
+  const uint32_t *cells = (const uint32_t *)(arena + O.cells);
+  const int32_t *vals = (const int32_t *)(arena + N.vals);
+  unsigned long long *acc = (unsigned long long *)(arena + N.acc);       // (two's complement: the sums are signed)
+  uint32_t *cnt = (uint32_t *)(arena + N.cnt);
+  const uint32_t lane = threadIdx.x;
+#if defined(__HIPCC__)
+  const uint64_t *key = (const uint64_t *)(arena + ord_sorted(O).key);
+  const unsigned long long upto = (2ull << lane) - 1ull;       // the lanes at or below this one
+  for (uint32_t s0 = e0; s0 < end; s0 += WAVE) {               // (uniform: every lane takes every step)
+    const uint32_t e = s0 + lane;
+    const bool valid = e < end;
+    const bool head = valid && ord_head(key, e);
+    const unsigned long long heads = __ballot(head), live = __ballot(valid);
+    // the run of this lane inside the step and its last lane, as k_enc_mean_sum finds them
+    const unsigned long long mine = heads & upto;
+    const uint32_t start = mine ? 63u - (uint32_t)__clzll((long long)mine) : 0u;
+    const unsigned long long above = (live >> lane) >> 1, head_above = (heads >> lane) >> 1;
+    const bool last = valid && ((above & 1ull) == 0ull || (head_above & 1ull) != 0ull);
+    const uint32_t r = valid ? row[e] : 0u;
+    const bool ok = valid && r < O.n;
+    const uint32_t j = ok ? cells[r] : 0xFFFFFFFFu;
+    long long u[3] = {0ll, 0ll, 0ll};
+    if (ok) ord_normal_unit(vals[2ull * r], vals[2ull * r + 1u], center, u);
+    for (uint32_t c = 0; c < 3u; ++c) {                        // (uniform)
+      const long long x = ord_wave_incl(u[c], lane, start);
+      if (last && j < O.n) atomicAdd(&acc[3ull * j + c], (unsigned long long)x);
+    }
+    if (last && j < O.n) atomicAdd(&cnt[j], lane - start + 1u);
+  }
+#else       // (as k_enc_order_hist: lane 0 takes the tile's entries in their order)
+  if (lane != 0) return;
+  for (uint32_t e = e0; e < end; ++e) {
+    const uint32_t r = row[e], j = cells[r];
+    long long u[3];
+    ord_normal_unit(vals[2ull * r], vals[2ull * r + 1u], center, u);
+    for (uint32_t c = 0; c < 3u; ++c) acc[3ull * j + c] += (unsigned long long)u[c];
+    cnt[j] += 1u;
+  }
+#endif
+}
+
+// grid as above, tiles over KEPT entries: a thread per kept entry.  No lane needs another: the host check runs it as it stands.
+__global__ __launch_bounds__(256) void k_enc_normal_store(uint8_t *arena, const EncOrder *clouds, const EncOrderTile *tiles, uint32_t nt,
+                                                          const EncCellStreams *nclouds, const EncNormal *normals, uint32_t nn) {
+  EncCellBlock B;
+  if (!ord_cell_block(B, clouds, tiles, nt, nclouds, nn, true)) return;
+  const EncOrder &O = *B.O;
+  const uint32_t e0 = B.e0, end = B.end;
+  const EncNormal N = normals[B.rec];
+  if (N.bits < 2u || N.bits > 20u) return;                     // (never by the layout)
+  const int32_t max_value = (int32_t)((1u << N.bits) - 2u), center = max_value / 2;
+  const uint32_t *kept = (const uint32_t *)(arena + ord_kept(O));
+  const long long *acc = (const long long *)(arena + N.acc);
+  const uint32_t *cnt = (const uint32_t *)(arena + N.cnt);
+  int32_t *vals = (int32_t *)(arena + N.vals);
+  for (uint32_t j = e0 + threadIdx.x; j < end; j += blockDim.x) {
+    const uint32_t r = kept[j], rows = cnt[j];
+    if (r >= O.n || rows <= 1u) continue;                      // (a cell of one row keeps its code; r < n and rows >= 1 by the merge and the sum)
+    int64_t M[3];
+    for (int k = 0; k < 3; ++k) M[k] = ord_rdiv((int64_t)acc[3ull * j + k], (int64_t)rows);
+    int32_t s, t;
+    ord_normal_code(M, center, max_value, s, t);
+    vals[2ull * r] = s; vals[2ull * r + 1u] = t;
   }
 }
 

@@ -108,6 +108,16 @@ __device__ __forceinline__ void enc_oct_from_int(int32_t center, int32_t max_val
   else if (t == max_value && s < center) s = center + (center - s);
   else if (t == 0 && s > center) s = center - (s - center);
 }
+// The tail of the octahedral quantiser (Octa::from_float_vector of the host coder from iv[2] on), shared by enc_oct_from_float and
+// the mean normals (k_enc_normal_store): the code of the vector scaled to L1 norm `center` whose first two components rounded to
+// i0 and i1 and whose third is negative or not.
+__device__ __forceinline__ void enc_oct_from_scaled(int32_t center, int32_t max_value, int32_t i0, int32_t i1, bool z_negative, int32_t &s, int32_t &t) {
+  int32_t i2 = center - abs(i0) - abs(i1);
+  if (i2 < 0) { if (i1 > 0) i1 += i2; else i1 -= i2; i2 = 0; }
+  if (z_negative) i2 = -i2;
+  const int32_t v[3] = {i0, i1, i2};
+  enc_oct_from_int(center, max_value, v, s, t);
+}
 
 // GeometricNormal correction of entry p (geometric_normal_prediction + the flip choice of write_attribute_values): the area-weighted
 // ring of the entry's corner on the attribute's table, positions of the position table, 64-bit sums; the prediction or its

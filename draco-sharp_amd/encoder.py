@@ -119,7 +119,13 @@ class Config:
     indices of the stream, counted as for mean_attributes: those attributes (of 1 or 2 components) carry the tuple of coded integers
     that the most input rows of the cell have, among tuples of equally many rows the lexicographically smallest (signed components,
     component 0 first), whatever the order of the rows.  Positions and normals are not voted on, an attribute takes the vote or the
-    mean, not both, and the clouds of a call must have the same attributes.  Everything else is as with mean_attributes."""
+    mean, not both, and the clouds of a call must have the same attributes.  Everything else is as with mean_attributes.
+
+    mean_normals (dsa_encode_normal_mean_sequential_batch): True: WITH merge_points=MERGE_CELLS the normals of every cloud that has
+    them carry, per kept point, the code of the normalised sum of the unit normals of the cell's rows -- by a rule in 64-bit integers
+    on the octahedral codes (include/draco_mi355x.h), whatever the order of the rows; a cell of one row keeps its code.  A cloud
+    without normals is coded as before; a bit of mean_attributes or vote_attributes on the normals stays refused.  part_cells,
+    lod_base_bits and the two masks compose with it; the handle is unchanged."""
 
     EDGEBREAKER_METHODS = (0, 2, -1)
     POSITION_PREDICTIONS = (0, 1)
@@ -135,7 +141,7 @@ class Config:
                  symbol_scheme=-1, position_prediction=1, texcoord_prediction=1, edgebreaker_method=0, normal_prediction=0,
                  encoding_method=1, compress_connectivity=False, multi_parallelogram=0, traversal_method=0, repair_topology=False, weld_points=False,
                  repair_seams=False, weld_attributes=False, track_rows=False, point_order=0, merge_points=0, part_points=0, part_cells=0,
-                 lod_base_bits=0, mean_attributes=0, vote_attributes=0):
+                 lod_base_bits=0, mean_attributes=0, vote_attributes=0, mean_normals=False):
         for name, value, legal in (("encoding_method", encoding_method, self.ENCODING_METHODS),
                                    ("edgebreaker_method", edgebreaker_method, self.EDGEBREAKER_METHODS),
                                    ("position_prediction", position_prediction, self.POSITION_PREDICTIONS),
@@ -240,6 +246,13 @@ class Config:
             raise ValueError("vote_attributes %r and mean_attributes %r name the same attribute: it carries the most frequent value of its cell or the mean, not both"
                              % (vote_attributes, mean_attributes))
 
+        if mean_normals not in (False, True, 0, 1):
+            raise ValueError("mean_normals %r: False or True" % (mean_normals,))
+        self.mean_normals = bool(mean_normals)
+        if self.mean_normals and self.merge_points != native.MERGE_CELLS:
+            raise ValueError("mean_normals takes the mean normal over the points of a cell: it needs merge_points=MERGE_CELLS "
+                             "(a sequential config with point_order=POINT_ORDER_MORTON)")
+
     def _mean_mask(self, meshes):
         """mean_attributes as the mask of a call over `meshes`: "all" is every attribute but positions and normals, and needs clouds
         with the same attributes."""
@@ -266,6 +279,18 @@ class Config:
         native.lib().dsa_encode_default_vote_options(C.byref(o))
         o.mean = self._native_mean(geometry, meshes)
         o.vote_attributes = self.vote_attributes
+        return o
+
+    def _native_normal_mean(self, geometry, meshes):
+        """the options of dsa_encode_normal_mean_sequential_batch for a call over `meshes` (which must have the same attributes only
+        where a mask says so)"""
+        o = native.EncodeNormalMeanOptions()
+        native.lib().dsa_encode_default_normal_mean_options(C.byref(o))
+        if self.vote_attributes != 0:
+            o.vote = self._native_vote(geometry, meshes)
+        else:
+            o.vote.mean = self._native_mean(geometry, meshes)
+        o.mean_normals = 1 if self.mean_normals else 0
         return o
 
     @property
@@ -990,6 +1015,7 @@ class DracoEncoder:
     # point, whether its handle has a slot per stream, so that n is read back from it).  A Config reaches the first whose option it
     # sets -- the widest call only when its option is set, and the plain case keeps arriving through the call it always took.
     _SEQUENTIAL_CALLS = (
+        ("mean_normals", "_native_normal_mean", "dsa_encode_normal_mean_sequential_batch", True),
         ("vote_attributes", "_native_vote", "dsa_encode_vote_sequential_batch", True),
         ("mean_attributes", "_native_mean", "dsa_encode_mean_sequential_batch", True),
         ("lod_base_bits", "_native_lod", "dsa_encode_lod_sequential_batch", True),
@@ -1011,8 +1037,8 @@ class DracoEncoder:
                 if config._mean_mask(meshes) == 0:
                     continue
                 opt = config._native_mean(geometry, meshes)
-            elif option == "vote_attributes":
-                opt = config._native_vote(geometry, meshes)
+            elif option in ("vote_attributes", "mean_normals"):
+                opt = getattr(config, build)(geometry, meshes)
             else:
                 opt = getattr(config, build)(geometry)
             break

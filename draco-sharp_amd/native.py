@@ -49,6 +49,7 @@ EXPORTS = [
     "dsa_encode_default_lod_options", "dsa_encode_lod_sequential_batch", "dsa_encoded_lod_info",
     "dsa_encode_default_mean_options", "dsa_encode_mean_sequential_batch",
     "dsa_encode_default_vote_options", "dsa_encode_vote_sequential_batch",
+    "dsa_encode_default_normal_mean_options", "dsa_encode_normal_mean_sequential_batch",
     "dsa_encoded_size", "dsa_encoded_stream", "dsa_encoded_free",
     "dsa_pool_create", "dsa_pool_destroy", "dsa_pool_size", "dsa_pool_last_error", "dsa_pool_decode", "dsa_pool_job_locate",
     "dsa_pool_job_chunks", "dsa_pool_job_free", "dsa_pool_plan",
@@ -145,6 +146,12 @@ class EncodeVoteOptions(C.Structure):
     attribute a of the stream, of 1 or 2 components, carries the tuple of coded integers that the most rows of the cell have, among
     tuples of equally many rows the lexicographically smallest; positions and normals are not voted on, the two masks share no bit)."""
     _fields_ = [("mean", EncodeMeanOptions), ("vote_attributes", C.c_uint32), ("reserved", C.c_int32 * 7)]
+
+
+class EncodeNormalMeanOptions(C.Structure):
+    """dsa_encode_normal_mean_options: the options of dsa_encode_vote_sequential_batch, and mean_normals (with merge_points = 1: 1: the
+    normals of every cloud that has them carry, per kept point, the mean normal of its cell by the integer rule of the header)."""
+    _fields_ = [("vote", EncodeVoteOptions), ("mean_normals", C.c_uint32), ("reserved", C.c_int32 * 7)]
 
 
 class LodInfo(C.Structure):
@@ -471,6 +478,10 @@ def lib():
             L.dsa_encode_default_vote_options.argtypes = [C.POINTER(EncodeVoteOptions)]
             L.dsa_encode_default_vote_options.restype = None
             L.dsa_encode_vote_sequential_batch.argtypes = [vp, u32, C.POINTER(MeshAttrInput), C.POINTER(MeshGrids), C.POINTER(EncodeVoteOptions), C.POINTER(vp)]
+        if hasattr(L, "dsa_encode_normal_mean_sequential_batch"):
+            L.dsa_encode_default_normal_mean_options.argtypes = [C.POINTER(EncodeNormalMeanOptions)]
+            L.dsa_encode_default_normal_mean_options.restype = None
+            L.dsa_encode_normal_mean_sequential_batch.argtypes = [vp, u32, C.POINTER(MeshAttrInput), C.POINTER(MeshGrids), C.POINTER(EncodeNormalMeanOptions), C.POINTER(vp)]
         L.dsa_encoded_size.restype = u32
         L.dsa_encoded_size.argtypes = [vp]
         L.dsa_encoded_stream.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(C.c_size_t)]

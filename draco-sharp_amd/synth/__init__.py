@@ -237,10 +237,12 @@ def lib():
                                         C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(ExtraInput), C.c_uint32,
                                         C.POINTER(GridsInput), C.POINTER(Options), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
         L.synth_encode_grid_portable.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ExtraInput), C.c_uint32, C.POINTER(GridsInput),
-                                                 C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(Options), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+                                                 C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(Options), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
         L.synth_quantized.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.POINTER(Grid), C.c_void_p]
         L.synth_merge_means.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]
         L.synth_merge_votes.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.synth_merge_mean_normals.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.synth_quantized_normals.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]
         L.synth_point_order.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(Grid), C.c_void_p]
         L.synth_merge_points.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(Grid), C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]
         L.synth_split_parts.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
@@ -485,13 +487,14 @@ def encode_mesh_points(pos, faces, normals=None, uvs=None, generic=None, extra=N
 
 
 def encode_grid(pos, faces=None, normals=None, uvs=None, generic=None, extra=None, opt=None, form=1, normal_corners=None, uv_corners=None,
-                geometry=1, compressed=False, pos_grid=None, uv_grid=None, weld_attributes=False, uv_portable=None):
+                geometry=1, compressed=False, pos_grid=None, uv_grid=None, weld_attributes=False, uv_portable=None, normal_portable=None):
     """Any stream of this module with quantisation grids given by the caller: pos_grid / uv_grid / Extra.grid are Grids (grid(),
     shared_grid()) or None for the attribute's own bounds.  form 1: the arguments of encode_mesh_corners (Edgebreaker); form 0:
     of encode_sequential (geometry 1) / encode_point_cloud_attributes (geometry 0, faces None); form 2: of encode_mesh_points
     (one row per point).  Without a grid the bytes are those calls'.  What dsa_encode_grid_batch /
     dsa_encode_grid_sequential_batch must write.  uv_portable (N, 2) int32 / Extra.portable (form 0, point clouds): the integers
-    coded for that quantised attribute in place of the quantiser's output, the header's bounds or grid as the floats give them."""
+    coded for that quantised attribute in place of the quantiser's output, the header's bounds or grid as the floats give them;
+    normal_portable (N, 2) int32 likewise: the octahedral codes (s, t) coded for the normals."""
     L = lib()
     pos, fc, nrm, uv, gen, extra, arr, opt = _points_args(pos, np.zeros((0, 3), np.uint32) if faces is None else faces, normals if normal_corners is None else None,
                                                           uvs if uv_corners is None else None, generic, extra, opt)
@@ -514,7 +517,9 @@ def encode_grid(pos, faces=None, normals=None, uvs=None, generic=None, extra=Non
     ptr = lambda a: None if a is None else a.ctypes.data          # noqa: E731
     out, n = C.c_void_p(), C.c_size_t()
     ec = _extra_corners(extra, len(fc))
-    if uv_portable is not None or any(e.portable is not None for e in extra):
+    if normal_portable is not None and nrm is None:
+        raise ValueError("normal_portable goes with normals")
+    if uv_portable is not None or normal_portable is not None or any(e.portable is not None for e in extra):
         if form != 0 or geometry != 0 or len(fc) or ec is not None:
             raise ValueError("portable integers go with a point cloud (form 0, geometry 0)")
         up = None if uv_portable is None else np.ascontiguousarray(uv_portable, np.int32).reshape(len(pos), 2)
@@ -522,7 +527,8 @@ def encode_grid(pos, faces=None, normals=None, uvs=None, generic=None, extra=Non
             if e.portable is not None and e.portable.shape != (len(pos), e.num_components):
                 raise ValueError("extra attribute %d: portable holds one row of num_components integers per point" % k)
         ep = (C.c_void_p * max(1, len(extra)))(*[None if e.portable is None else e.portable.ctypes.data for e in extra])
-        rc = L.synth_encode_grid_portable(ptr(pos), len(pos), ptr(nrm), ptr(uv), ptr(gen), arr, len(extra), C.byref(gi), ptr(up), ep, C.byref(opt),
+        npt = None if normal_portable is None else np.ascontiguousarray(normal_portable, np.int32).reshape(len(pos), 2)
+        rc = L.synth_encode_grid_portable(ptr(pos), len(pos), ptr(nrm), ptr(uv), ptr(gen), arr, len(extra), C.byref(gi), ptr(npt), ptr(up), ep, C.byref(opt),
                                           C.byref(out), C.byref(n))
     elif ec is None and not weld_attributes:
         rc = L.synth_encode_grid(form, ptr(pos), len(pos), ptr(fc) if len(fc) else None, len(fc), ptr(nrm), 0 if nrm is None else len(nrm), ptr(nci),
@@ -646,6 +652,29 @@ def merge_votes(q, row_entries, m):
     return out
 
 
+def quantized_normals(normals, bits):
+    """The octahedral codes (s, t) the coder quantises the normals (N, 3) to at `bits` normal bits: (N, 2) int32."""
+    L = lib()
+    nrm = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    out = np.zeros((len(nrm), 2), np.int32)
+    if L.synth_quantized_normals(nrm.ctypes.data, len(nrm), int(bits), out.ctypes.data):
+        raise RuntimeError(_err())
+    return out
+
+
+def merge_mean_normals(q, bits, row_entries, m):
+    """The mean normal of every cell: q (N, 2) int32 octahedral codes at `bits` normal bits, row_entries (N,) below m as merge_points
+    has them; (m, 2) int32, entry j the code of the normalised sum of the unit normals of the rows of cell j by the integer rule of
+    dsa_encode_normal_mean_sequential_batch (a cell of one row keeps its code).  What that call codes for the normals."""
+    L = lib()
+    q = np.ascontiguousarray(q, np.int32).reshape(-1, 2)
+    cells = np.ascontiguousarray(row_entries, np.uint32)
+    out = np.zeros((int(m), 2), np.int32)
+    if L.synth_merge_mean_normals(q.ctypes.data, len(q), int(bits), cells.ctypes.data, int(m), out.ctypes.data):
+        raise RuntimeError(_err())
+    return out
+
+
 def _extra_rows(e, rows, grid=None):
     """Extra e with its rows (and its portable integers) taken at `rows` (an index array or a slice); grid: in place of e.grid."""
     return Extra(e.values[rows], attribute_type=e.attribute_type, normalized=bool(e.normalized), unique_id=e.unique_id,
@@ -653,13 +682,15 @@ def _extra_rows(e, rows, grid=None):
                  portable=None if e.portable is None else e.portable[rows])
 
 
-def merged_arguments(pos, normals=None, uvs=None, generic=None, extra=None, opt=None, pos_grid=None, uv_grid=None, mean_attributes=0, vote_attributes=0):
+def merged_arguments(pos, normals=None, uvs=None, generic=None, extra=None, opt=None, pos_grid=None, uv_grid=None, mean_attributes=0, vote_attributes=0,
+                     mean_normals=False):
     """The arguments of the plain call that writes a merged stream: (kept, row_entries, kwargs for encode_grid(form=0, geometry=0))
     -- every per-point array at [kept], every quantised attribute on an explicit grid equal to the bounds of ALL its rows (the
     grid given, where one was).  mean_attributes: bit a: attribute a of the stream (0 positions, then normals, uvs, generic and the
     extras, those given) carries merge_means of its cell in place of row kept[j] -- an integer attribute as the mean array, a
     quantised one as portable integers (uv_portable / Extra.portable) on the unchanged grid.  vote_attributes: likewise, bit a:
-    attribute a (of 1 or 2 components) carries merge_votes of its cell; the two masks share no bit."""
+    attribute a (of 1 or 2 components) carries merge_votes of its cell; the two masks share no bit.  mean_normals: the normals, where
+    given, carry merge_mean_normals of their cell as portable codes (normal_portable)."""
     opt = opt or options()
     kept, cells = merge_points(pos, opt.pos_bits, pos_grid)
     m = len(kept)
@@ -713,14 +744,18 @@ def merged_arguments(pos, normals=None, uvs=None, generic=None, extra=None, opt=
               extra=ex, opt=opt, pos_grid=pos_grid if pos_grid is not None else bounds_grid(pos), uv_grid=ug)
     if uv_portable is not None:
         kw["uv_portable"] = uv_portable
+    if mean_normals and normals is not None:
+        kw["normal_portable"] = merge_mean_normals(quantized_normals(np.asarray(normals, np.float32).reshape(-1, 3), opt.normal_bits), opt.normal_bits, cells, m)
     return kept, cells, kw
 
 
-def encode_merged(pos, normals=None, uvs=None, generic=None, extra=None, opt=None, pos_grid=None, uv_grid=None, mean_attributes=0, vote_attributes=0):
+def encode_merged(pos, normals=None, uvs=None, generic=None, extra=None, opt=None, pos_grid=None, uv_grid=None, mean_attributes=0, vote_attributes=0,
+                  mean_normals=False):
     """encode_grid(form=0, geometry=0) of one point per occupied cell: (stream, kept, row_entries), merged_arguments coded.  What
     dsa_encode_merged_sequential_batch with merge_points = 1 must write, and the rows its handle must report; with mean_attributes
-    what dsa_encode_mean_sequential_batch must, with vote_attributes what dsa_encode_vote_sequential_batch must."""
-    kept, cells, kw = merged_arguments(pos, normals, uvs, generic, extra, opt, pos_grid, uv_grid, mean_attributes, vote_attributes)
+    what dsa_encode_mean_sequential_batch must, with vote_attributes what dsa_encode_vote_sequential_batch must, with mean_normals
+    what dsa_encode_normal_mean_sequential_batch must."""
+    kept, cells, kw = merged_arguments(pos, normals, uvs, generic, extra, opt, pos_grid, uv_grid, mean_attributes, vote_attributes, mean_normals)
     p = kw.pop("pos")
     return encode_grid(p, None, form=0, geometry=0, **kw), kept, cells
 
@@ -815,7 +850,8 @@ def cell_parts(pos, bits, part_cells, grid=None):
 CellParts = collections.namedtuple("CellParts", "streams kept row_entries ranges qmin qmax")
 
 
-def encode_cell_parts(pos, normals=None, uvs=None, generic=None, extra=None, opt=None, pos_grid=None, uv_grid=None, part_cells=0, mean_attributes=0, vote_attributes=0):
+def encode_cell_parts(pos, normals=None, uvs=None, generic=None, extra=None, opt=None, pos_grid=None, uv_grid=None, part_cells=0, mean_attributes=0, vote_attributes=0,
+                      mean_normals=False):
     """One point per occupied cell, and the kept order in parts of at most part_cells points, each coded as a point cloud of its own
     on the cloud's grid: CellParts(streams, kept, row_entries, ranges, qmin, qmax) with merged_arguments' rows and grids -- every
     per-point array at [kept[lo:hi]], every quantised attribute on an explicit grid equal to the bounds of ALL input rows (the grid
@@ -823,14 +859,15 @@ def encode_cell_parts(pos, normals=None, uvs=None, generic=None, extra=None, opt
     report."""
     opt = opt or options()
     kept, cells, ranges, qmin, qmax = cell_parts(pos, opt.pos_bits, part_cells, pos_grid)
-    _, _, kw = merged_arguments(pos, normals, uvs, generic, extra, opt, pos_grid, uv_grid, mean_attributes, vote_attributes)
+    _, _, kw = merged_arguments(pos, normals, uvs, generic, extra, opt, pos_grid, uv_grid, mean_attributes, vote_attributes, mean_normals)
     p = kw.pop("pos")
     streams = []
     for lo, hi in ranges:
         take = lambda a: None if a is None else np.ascontiguousarray(a[lo:hi])          # noqa: E731
         ex = [_extra_rows(e, slice(lo, hi)) for e in kw["extra"]]
         streams.append(encode_grid(take(p), None, normals=take(kw["normals"]), uvs=take(kw["uvs"]), generic=take(kw["generic"]), extra=ex, opt=opt,
-                                   form=0, geometry=0, pos_grid=kw["pos_grid"], uv_grid=kw["uv_grid"], uv_portable=take(kw.get("uv_portable"))))
+                                   form=0, geometry=0, pos_grid=kw["pos_grid"], uv_grid=kw["uv_grid"], uv_portable=take(kw.get("uv_portable")),
+                                   normal_portable=take(kw.get("normal_portable"))))
     return CellParts(streams, kept, cells, ranges, qmin, qmax)
 
 
@@ -860,7 +897,7 @@ LodParts = collections.namedtuple("LodParts", "streams kept row_entries ranges q
 
 
 def encode_lod_parts(pos, normals=None, uvs=None, generic=None, extra=None, opt=None, pos_grid=None, uv_grid=None, part_cells=0, lod_base_bits=0,
-                     mean_attributes=0, vote_attributes=0):
+                     mean_attributes=0, vote_attributes=0, mean_normals=False):
     """Additive levels of detail of the kept points, every level in parts of at most part_cells points, each part coded as a point
     cloud of its own on the cloud's grid: what encode_cell_parts returns with `kept` the rows in LOD order (ranges and row_entries
     count in it), plus `level` per stream and `levels` = L = position bits - lod_base_bits + 1.  Every per-point array at
@@ -869,10 +906,10 @@ def encode_lod_parts(pos, normals=None, uvs=None, generic=None, extra=None, opt=
     lod_base_bits 0: encode_cell_parts, every stream of level 0 of 1."""
     opt = opt or options()
     if lod_base_bits == 0:
-        cp = encode_cell_parts(pos, normals, uvs, generic, extra, opt, pos_grid, uv_grid, part_cells, mean_attributes, vote_attributes)
+        cp = encode_cell_parts(pos, normals, uvs, generic, extra, opt, pos_grid, uv_grid, part_cells, mean_attributes, vote_attributes, mean_normals)
         return LodParts(*cp, level=np.zeros(len(cp.streams), np.uint32), levels=1)
     lod, cells, ranges, level, qmin, qmax = lod_parts(pos, opt.pos_bits, part_cells, lod_base_bits, pos_grid)
-    kept, _, kw = merged_arguments(pos, normals, uvs, generic, extra, opt, pos_grid, uv_grid, mean_attributes, vote_attributes)
+    kept, _, kw = merged_arguments(pos, normals, uvs, generic, extra, opt, pos_grid, uv_grid, mean_attributes, vote_attributes, mean_normals)
     at = np.zeros(int(kept.max()) + 1, np.int64)
     at[kept] = np.arange(len(kept))
     idx = at[lod]                                # where in kept (the order of merged_arguments' arrays) every lod entry lies
@@ -882,7 +919,8 @@ def encode_lod_parts(pos, normals=None, uvs=None, generic=None, extra=None, opt=
         take = lambda a: None if a is None else np.ascontiguousarray(a[idx[lo:hi]])          # noqa: E731
         ex = [_extra_rows(e, idx[lo:hi]) for e in kw["extra"]]
         streams.append(encode_grid(take(p), None, normals=take(kw["normals"]), uvs=take(kw["uvs"]), generic=take(kw["generic"]), extra=ex, opt=opt,
-                                   form=0, geometry=0, pos_grid=kw["pos_grid"], uv_grid=kw["uv_grid"], uv_portable=take(kw.get("uv_portable"))))
+                                   form=0, geometry=0, pos_grid=kw["pos_grid"], uv_grid=kw["uv_grid"], uv_portable=take(kw.get("uv_portable")),
+                                   normal_portable=take(kw.get("normal_portable"))))
     return LodParts(streams, lod, cells, ranges, qmin, qmax, level, opt.pos_bits - lod_base_bits + 1)
 
 

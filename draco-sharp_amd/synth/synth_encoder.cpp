@@ -404,7 +404,8 @@ static int encode_grid(int form, const float *pos, uint32_t nv, const uint32_t *
                        int geometry, int compressed, const synth_extra *extras, const synth_extra_corners *extra_corners, uint32_t num_extras,
                        const synth_grids *grids, const synth_options *opt, int weld_attributes, uint8_t **out, size_t *out_len,
                        std::vector<std::vector<uint32_t>> *rows = nullptr,       // rows: the entry rows of the stream in place of its bytes (synth_entry_rows)
-                       const int32_t *uv_portable = nullptr, const int32_t *const *extra_portable = nullptr) {      // form 0: integers in place of the quantiser's output (synth_encode_grid_portable)
+                       const int32_t *uv_portable = nullptr, const int32_t *const *extra_portable = nullptr,        // form 0: integers in place of the quantiser's output (synth_encode_grid_portable)
+                       const int32_t *normal_portable = nullptr) {                                                  // ... and octahedral codes in place of the normals'
   try {
     synth::check(form >= 0 && form <= 2, "form: 0 (sequential), 1 (Edgebreaker) or 2 (one row per point)");
     std::vector<synth::ExtraAttr> ex, ex2;
@@ -415,8 +416,9 @@ static int encode_grid(int form, const float *pos, uint32_t nv, const uint32_t *
         ex[k].corners = extra_corners[k].corners; ex[k].rows = extra_corners[k].num_rows;
       }
     { const std::string why = synth::extras_error(in); synth::check(why.empty(), why.c_str()); }
-    synth::check(form == 0 || (!uv_portable && !extra_portable), "portable integers go with a sequential stream (form 0)");
+    synth::check(form == 0 || (!uv_portable && !extra_portable && !normal_portable), "portable integers go with a sequential stream (form 0)");
     in.uv_portable = uvs ? uv_portable : nullptr;
+    in.normal_portable = normals ? normal_portable : nullptr;
     for (uint32_t k = 0; k < num_extras && extra_portable; ++k) ex[k].portable = extra_portable[k];
     if (grids) {
       in.pos_grid = &grids->position;
@@ -474,13 +476,33 @@ int synth_encode_grid(int form, const float *pos, uint32_t nv, const uint32_t *f
                       const synth_options *opt, uint8_t **out, size_t *out_len) {
   return encode_grid(form, pos, nv, faces, nf, normals, nn, normal_corners, uvs, nu, uv_corners, generic, geometry, compressed, extras, nullptr, num_extras, grids, opt, 0, out, out_len);
 }
-// synth_encode_grid, form 0, with integers given in place of the quantiser's output: uv_portable (nv rows of 2, or NULL) for the
-// texture coordinates, extra_portable (NULL, or num_extras pointers, each NULL or nv rows of the attribute's components) for float32
-// attributes of the list.  Bounds, grids and the stream's header are what the floats give; only the coded integers are replaced.
+// synth_encode_grid, form 0, with integers given in place of the quantiser's output: normal_portable (nv rows of the octahedral code
+// (s, t), or NULL) for the normals, uv_portable (nv rows of 2, or NULL) for the texture coordinates, extra_portable (NULL, or
+// num_extras pointers, each NULL or nv rows of the attribute's components) for float32 attributes of the list.  Bounds, grids and
+// the stream's header are what the floats give; only the coded integers are replaced.
 int synth_encode_grid_portable(const float *pos, uint32_t nv, const float *normals, const float *uvs, const void *generic, const synth_extra *extras, uint32_t num_extras,
-                               const synth_grids *grids, const int32_t *uv_portable, const int32_t *const *extra_portable, const synth_options *opt, uint8_t **out, size_t *out_len) {
+                               const synth_grids *grids, const int32_t *normal_portable, const int32_t *uv_portable, const int32_t *const *extra_portable, const synth_options *opt,
+                               uint8_t **out, size_t *out_len) {
   return encode_grid(0, pos, nv, nullptr, 0, normals, normals ? nv : 0, nullptr, uvs, uvs ? nv : 0, nullptr, generic, 0, 0, extras, nullptr, num_extras, grids, opt, 0, out, out_len, nullptr,
-                     uv_portable, extra_portable);
+                     uv_portable, extra_portable, normal_portable);
+}
+// The octahedral codes (s, t) the coder quantises `n` normals to at `bits` bits (dsa_encode_host.h Octa::from_float_vector).
+int synth_quantized_normals(const float *normals, uint32_t n, int bits, int32_t *out) {
+  try {
+    synth::check(normals != nullptr && n > 0 && bits >= 2 && bits <= 20, "quantized_normals: n rows of 3 floats at 2 - 20 bits");
+    const synth::Octa o(bits);
+    for (uint32_t r = 0; r < n; ++r) { int s, t; o.from_float_vector(normals + (size_t)r * 3, s, t); out[(size_t)r * 2] = s; out[(size_t)r * 2 + 1] = t; }
+    return 0;
+  } catch (const std::exception &e) { snprintf(g_err, sizeof(g_err), "%s", e.what()); return 1; }
+}
+// The mean normal of every cell (dsa_encode_host.h merge_mean_normals): q[n * 2] codes at `bits` bits, row_entries[n] below m; codes[m * 2].
+int synth_merge_mean_normals(const int32_t *q, uint32_t n, int bits, const uint32_t *row_entries, uint32_t m, int32_t *codes) {
+  try {
+    std::vector<int32_t> out;
+    synth::merge_mean_normals(q, n, bits, std::vector<uint32_t>(row_entries, row_entries + n), m, out);
+    memcpy(codes, out.data(), 4 * out.size());
+    return 0;
+  } catch (const std::exception &e) { snprintf(g_err, sizeof(g_err), "%s", e.what()); return 1; }
 }
 // The integers the coder quantises `n` rows of `nc` floats to at `bits` bits (dsa_encode_host.h quantize): on their own bounds, or on `grid`.
 int synth_quantized(const float *values, uint32_t n, int nc, int bits, const synth::Grid *grid, int32_t *out) {

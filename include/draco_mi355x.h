@@ -924,9 +924,10 @@ dsa_status dsa_encoded_lod_info(const dsa_encoded *encoded, uint32_t stream, dsa
  * On the device two kernels behind the merge (k_enc_mean_sum 24 VGPR / 45 SGPR, k_enc_mean_store 23 / 29; no LDS, no scratch;
  * dsa_encode_order.h) take 0.6 ms of a 64 ms call for a 4 Mi-point scan with a colour and a float attribute in 256 parts, against 264 ms
  * for download, host means and a second encode.
- * Not built: mean normals (octahedral integers do not average across the fold, a vector sum needs a fixed-point rule of its own);
- * weighted means; means per coarser lod cell (a level's point carries the mean of its finest cell).  Built since, for categories
- * whose mean is a class nobody assigned: a vote for label attributes, dsa_encode_vote_sequential_batch below.
+ * Not built: weighted means; means per coarser lod cell (a level's point carries the mean of its finest cell).  Built since, for
+ * categories whose mean is a class nobody assigned: a vote for label attributes, dsa_encode_vote_sequential_batch below; and
+ * mean normals (octahedral integers do not average across the fold: a vector sum by a fixed-point rule of its own, not a bit of
+ * this mask, which stays refused), dsa_encode_normal_mean_sequential_batch below.
  * Added after ABI 4 without changing it: callers detect the feature by the symbol dsa_encode_mean_sequential_batch. */
 typedef struct dsa_encode_mean_options {
   dsa_encode_lod_options lod;              /* as for dsa_encode_lod_sequential_batch, same legal values */
@@ -974,6 +975,43 @@ typedef struct dsa_encode_vote_options {
 void dsa_encode_default_vote_options(dsa_encode_vote_options *options);
 dsa_status dsa_encode_vote_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids,
                                             const dsa_encode_vote_options *options, dsa_encoded **out);
+/* dsa_encode_vote_sequential_batch with the mean normal of every cell in the normals of its kept point: what a voxel-grid downsample
+ * does to normals.  With merge_points = 1 alone a kept point carries the normal of whichever row came first in the caller's order.
+ *   mean_normals = 1: in every cloud that has normals, entry j of the normal attribute carries the code of the normalised sum of the
+ *   unit normals of the rows of cell j.  Taken only with merge_points = 1; part_cells, lod_base_bits, mean_attributes and
+ *   vote_attributes (on the other attributes) compose with it as they are.  A cloud without normals is coded as before.
+ *   The rule works on the octahedral codes (s, t) the plain call codes for the rows at normal_bits = b, in 64-bit integers.  With
+ *   max_value = 2^b - 2, c = max_value / 2 and rdiv(num, den) = floor((2 num + den) / (2 den)), floor division, den > 0:
+ *     1. a = s - c, b' = t - c; v = (c - |a| - |b'|, a, b') where |a| + |b'| <= c, else
+ *        v = (c - |a| - |b'|, sg(a) (c - |b'|), sg(b') (c - |a|)), sg(0) = +1: the integer vector of L1 norm c the code stands for;
+ *     2. len = isqrt((v . v) << 24), the exact floor square root, and u_k = rdiv(v_k << 42, len): the unit vector in Q30;
+ *     3. U = the sum of u over the cnt rows of the cell;
+ *     4. M_k = rdiv(U_k, cnt);
+ *     5. A = |M_0| + |M_1| + |M_2|.  A = 0 (the normals cancel): i0 = c, i1 = 0, z positive -- the code the quantiser gives a zero
+ *        vector, that of (1, 0, 0).  Else i0 = rdiv(M_0 c, A), i1 = rdiv(M_1 c, A), z negative iff M_2 < 0.  From there the
+ *        quantiser's own tail: i2 = c - |i0| - |i1|, its correction where that is negative, the fold and the canonicalisation;
+ *     6. a cell of one row keeps its code.
+ *   Pure integer arithmetic: a function of the SET of rows of the cell, bit-identical on host and device.  The angle to the
+ *   float64 mean direction stays within the quantiser's own largest angle at those bits.  Bounds, grids, histogram sizes and every
+ *   refusal are those of the call without it.
+ *   Every stream is byte for byte what the same call with mean_normals = 0 writes for an input whose normals are coded, at row
+ *   kept[j], as the mean codes.  The handle is unchanged, the cell counts included.
+ *   mean_normals = 0: the bytes, the messages, the work and the handle of dsa_encode_vote_sequential_batch.
+ * Fails the call with DSA_ERR_INVALID_ARGUMENT before any mesh is looked at, dsa_last_error naming the field: mean_normals above 1;
+ * mean_normals = 1 without merge_points = 1; a non-zero reserved word.  Refusals of the nested option structs keep their own
+ * words, and a mean_attributes or vote_attributes bit on the normals stays refused per cloud.
+ * On the device two kernels behind the merge, beside the means and the votes (k_enc_normal_sum, k_enc_normal_store;
+ * dsa_encode_order.h); DESIGN.md 7.3 has what they cost.
+ * Not built: a vote over normals; weighted means; means per coarser lod cell; mean normals of meshes.
+ * Added after ABI 4 without changing it: callers detect the feature by the symbol dsa_encode_normal_mean_sequential_batch. */
+typedef struct dsa_encode_normal_mean_options {
+  dsa_encode_vote_options vote;            /* as for dsa_encode_vote_sequential_batch, same legal values */
+  uint32_t mean_normals;                   /* 0 (default): the very request of the vote call; 1: the normals of every kept point are the mean normal of its cell */
+  int32_t reserved[7];                     /* must be zero */
+} dsa_encode_normal_mean_options;
+void dsa_encode_default_normal_mean_options(dsa_encode_normal_mean_options *options);
+dsa_status dsa_encode_normal_mean_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids,
+                                                   const dsa_encode_normal_mean_options *options, dsa_encoded **out);
 /* The rows of a decoded batch per POINT: for every mesh of `batch` and every attribute a of its stream,
  *     rows[a][p] = entry_rows[a][map[a][p]]          (map: the decoder's point -> entry map, dsa_batch_device_point_map)
  * -- which row of the arrays given to the encoder point p carries, gathered on the device (k_source_rows) so that neither the maps
