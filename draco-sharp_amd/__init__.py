@@ -8,3 +8,4 @@ from .decoder import (Batch, Context, DataBuffer, DeviceException, Draco, DracoD
                       InvalidDataException, Mesh, MetadataElement, PointAttribute, PointCloud, Pool, PoolJob, parse_metadata, pool_plan)
 from .encoder import Attribute, Config, DracoEncoder, Grid, MeshData, PointCloudData, WeldedMaps  # noqa: E402,F401
 from .native import ENCODE_MAX_PARTS, ENCODE_ORDER_TILE, MERGE_CELLS, MERGE_NONE, POINT_ORDER_CALLER, POINT_ORDER_MORTON  # noqa: E402,F401
+from .native import VOXEL_POINT_CENTROID, VOXEL_POINT_FIRST, VOXEL_POINT_NEAREST  # noqa: E402,F401

@@ -127,6 +127,13 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
     // octahedral codes that the header states, whatever the order of the rows; a cell of one row keeps its code.  A cloud without
     // normals is coded as before.  PartCells, LodBaseBits, MeanAttributes and VoteAttributes compose with it.  Needs MergePoints 1.
     public bool MeanNormals { get; set; }
+    // VoxelBits, VoxelPoint (dsa_encode_voxel_sequential_batch): VoxelBits = C >= 1: WITH MergePoints one point per occupied cell of the
+    // grid with C bits per axis is kept, whatever PositionBits >= C the positions are stored at.  VoxelPoint: 0 the voxel's first row
+    // in (key, row) order; 1 that row, its position coded as the exact integer mean of the voxel's quantised positions (ties
+    // upwards); 2 the input row nearest the voxel's centre (ties to the smaller row).  MeanAttributes, VoteAttributes and MeanNormals
+    // reduce over the voxel, PartCells cuts the kept voxels, LodBaseBits = D needs D <= C and gives C - D + 1 levels.
+    public int VoxelBits { get; set; }
+    public int VoxelPoint { get; set; }
     public struct PartBox
     {
         public uint Input, Part, Parts, FirstEntry, NumPoints, PositionBits;
@@ -246,6 +253,8 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
             if (MeanAttributes != 0 && MergePoints != 1) throw new ArgumentException("MeanAttributes needs MergePoints 1: the mean is the mean over the points of a cell");
             if (VoteAttributes != 0 && MergePoints != 1) throw new ArgumentException("VoteAttributes needs MergePoints 1: the vote is a vote of the points of a cell");
             if (MeanNormals && MergePoints != 1) throw new ArgumentException("MeanNormals needs MergePoints 1: the mean normal is the mean over the points of a cell");
+            if (VoxelBits != 0 && MergePoints != 1) throw new ArgumentException("VoxelBits needs MergePoints 1: a voxel keeps one of the points of a cell");
+            if (VoxelPoint != 0 && VoxelBits == 0) throw new ArgumentException("VoxelPoint needs VoxelBits >= 1: the centroid and the nearest point are those of a voxel");
             if ((VoteAttributes & MeanAttributes) != 0) throw new ArgumentException("VoteAttributes and MeanAttributes share a bit: an attribute carries the most frequent value of its cell or the mean, not both");
             if (LodBaseBits != 0 && PartCells == 0) throw new ArgumentException("LodBaseBits needs PartCells >= 1: every level is cut into parts of at most PartCells points");
             if (PartPoints != 0 || PartCells != 0)
@@ -258,7 +267,21 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
                 po.PartPoints = PartPoints;
                 var ain = new DsaMeshAttrInput[items.Count];
                 for (int i = 0; i < items.Count; ++i) { ain[i].Mesh.Mesh = inputs[i]; Extras(items[i], null, (uint)items[i].PointsCount, ref ain[i], pins); }
-                if (MeanNormals)                // (the widest call only when its option is set)
+                if (VoxelBits != 0)             // (the widest call only when its option is set)
+                {
+                    NativeMethods.dsa_encode_default_voxel_options(out var xo);
+                    xo.NormalMean.Vote.Mean.Lod.CellParts.Split = po;
+                    xo.NormalMean.Vote.Mean.Lod.CellParts.PartCells = PartCells;
+                    xo.NormalMean.Vote.Mean.Lod.LodBaseBits = LodBaseBits;
+                    xo.NormalMean.Vote.Mean.MeanAttributes = MeanAttributes;
+                    xo.NormalMean.Vote.VoteAttributes = VoteAttributes;
+                    xo.NormalMean.MeanNormals = MeanNormals ? 1u : 0u;
+                    xo.VoxelBits = VoxelBits;
+                    xo.VoxelPoint = VoxelPoint;
+                    fixed (DsaMeshAttrInput* p = ain)
+                        NativeMethods.Check(NativeMethods.dsa_encode_voxel_sequential_batch(_ctx, (uint)items.Count, p, null, in xo, out encoded), _ctx, "dsa_encode_voxel_sequential_batch");
+                }
+                else if (MeanNormals)           // (the widest call only when its option is set)
                 {
                     NativeMethods.dsa_encode_default_normal_mean_options(out var no);
                     no.Vote.Mean.Lod.CellParts.Split = po;
@@ -358,7 +381,19 @@ public sealed unsafe class GpuDracoEncoder : IDisposable
                 mo.MergePoints = MergePoints;
                 var ain = new DsaMeshAttrInput[items.Count];
                 for (int i = 0; i < items.Count; ++i) { ain[i].Mesh.Mesh = inputs[i]; Extras(items[i], null, (uint)items[i].PointsCount, ref ain[i], pins); }
-                if (MeanNormals)                // (the widest call only when its option is set)
+                if (VoxelBits != 0)             // (the widest call only when its option is set)
+                {
+                    NativeMethods.dsa_encode_default_voxel_options(out var xo);
+                    xo.NormalMean.Vote.Mean.Lod.CellParts.Split.Merge = mo;
+                    xo.NormalMean.Vote.Mean.MeanAttributes = MeanAttributes;
+                    xo.NormalMean.Vote.VoteAttributes = VoteAttributes;
+                    xo.NormalMean.MeanNormals = MeanNormals ? 1u : 0u;
+                    xo.VoxelBits = VoxelBits;
+                    xo.VoxelPoint = VoxelPoint;
+                    fixed (DsaMeshAttrInput* p = ain)
+                        NativeMethods.Check(NativeMethods.dsa_encode_voxel_sequential_batch(_ctx, (uint)items.Count, p, null, in xo, out encoded), _ctx, "dsa_encode_voxel_sequential_batch");
+                }
+                else if (MeanNormals)           // (the widest call only when its option is set)
                 {
                     NativeMethods.dsa_encode_default_normal_mean_options(out var no);
                     no.Vote.Mean.Lod.CellParts.Split.Merge = mo;

@@ -331,6 +331,16 @@ internal unsafe struct DsaEncodeNormalMeanOptions
     public fixed int Reserved[7];   // zero
 }
 
+// dsa_encode_voxel_options (dsa_encode_voxel_sequential_batch)
+[StructLayout(LayoutKind.Sequential)]
+internal unsafe struct DsaEncodeVoxelOptions
+{
+    public DsaEncodeNormalMeanOptions NormalMean;
+    public int VoxelBits;           // 0: the request of the normal-mean call; C >= 1: one point per cell of the grid with C bits per axis (needs MergePoints 1)
+    public int VoxelPoint;          // 0 the voxel's first row, 1 that row at the voxel's mean position, 2 the row nearest the voxel's centre
+    public fixed int Reserved[6];   // zero
+}
+
 // dsa_lod_info (dsa_encoded_lod_info)
 [StructLayout(LayoutKind.Sequential)]
 internal unsafe struct DsaLodInfo
@@ -508,6 +518,8 @@ internal static unsafe partial class NativeMethods
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_vote_sequential_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, in DsaEncodeVoteOptions options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern void dsa_encode_default_normal_mean_options(out DsaEncodeNormalMeanOptions options);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_normal_mean_sequential_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, in DsaEncodeNormalMeanOptions options, out IntPtr encoded);
+    [DllImport(Lib)] internal static extern void dsa_encode_default_voxel_options(out DsaEncodeVoxelOptions options);
+    [DllImport(Lib)] internal static extern DsaStatus dsa_encode_voxel_sequential_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, in DsaEncodeVoxelOptions options, out IntPtr encoded);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encoded_parts(IntPtr encoded, uint input, out uint firstStream, out uint count);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encoded_part_info(IntPtr encoded, uint stream, out DsaPartInfo info);
     [DllImport(Lib)] internal static extern DsaStatus dsa_encode_rows_batch(IntPtr ctx, uint n, DsaMeshAttrInput* meshes, DsaMeshGrids* grids, DsaMeshAttributeCorners* corners, in DsaEncodeRowsOptions options, out IntPtr encoded);

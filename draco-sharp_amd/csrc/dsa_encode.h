@@ -39,6 +39,8 @@
 //                                                into the voted attributes' integers at every kept row, beside the means
 //                              k_enc_normal_*    dsa_encode_normal_mean_sequential_batch, mean_normals = 1: the mean normal of the cell into
 //                                                the normals' octahedral codes at every kept row, beside the two above
+//                              k_enc_voxel_*     dsa_encode_voxel_sequential_batch, voxel_bits >= 1: the cell is the key without its low
+//                                                3 (position_bits - voxel_bits) bits; the nearest point of every voxel into kept
 //         (dsa_encode_layout.h) the request of an entry point, the state of a chunk, the per-mesh checks and plans, the arena layout
 // Every entry point fills an EncRequest and calls encode_request; a chunk of it goes through the stages of encode_chunk (or of
 // encode_sequential_chunk, dsa_encode_sequential.h) on a lane.
@@ -1577,6 +1579,21 @@ static dsa_status enc_check_options(dsa_context *ctx, const dsa_encode_normal_me
   ENC_RESERVED(o, 7, "dsa_encode_normal_mean_options");
   return enc_check_options(ctx, o.vote, null_argument);
 }
+// ... or with voxels coarser than the position grid and a choice of the point each keeps (dsa_encode_order.h)
+static dsa_status enc_check_options(dsa_context *ctx, const dsa_encode_voxel_options &o, bool null_argument) {
+  const dsa_encode_lod_options &l = o.normal_mean.vote.mean.lod;
+  const dsa_encode_merge_options &m = l.cell_parts.split.merge;
+  const int bits = (int)m.order.sequential.base.position_bits;
+  if (o.voxel_bits < 0) ENC_REFUSE("voxel_bits %d: 0 (the request of dsa_encode_normal_mean_sequential_batch) or the bits per axis of the voxel grid, 1 .. position_bits", (int)o.voxel_bits);
+  if (o.voxel_bits >= 1 && m.merge_points != 1) ENC_REFUSE("voxel_bits %d needs merge_points 1 (it was %d): a voxel keeps one of the points of a cell", (int)o.voxel_bits, (int)m.merge_points);
+  if (o.voxel_point < 0 || o.voxel_point > 2) ENC_REFUSE("voxel_point %d: 0 (DSA_VOXEL_POINT_FIRST), 1 (DSA_VOXEL_POINT_CENTROID) or 2 (DSA_VOXEL_POINT_NEAREST)", (int)o.voxel_point);
+  if (o.voxel_point != 0 && o.voxel_bits == 0) ENC_REFUSE("voxel_point %d needs voxel_bits >= 1 (it was 0): the centroid and the nearest point are those of a voxel", (int)o.voxel_point);
+  ENC_RESERVED(o, 6, "dsa_encode_voxel_options");
+  if (enc_check_options(ctx, o.normal_mean, null_argument) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+  if (o.voxel_bits > bits) ENC_REFUSE("voxel_bits %d is above position_bits %d: a voxel cannot be finer than the quantisation grid", (int)o.voxel_bits, bits);
+  if (o.voxel_bits >= 1 && l.lod_base_bits > o.voxel_bits) ENC_REFUSE("lod_base_bits %d is above voxel_bits %d: level 0 cannot be finer than the voxel grid", (int)l.lod_base_bits, (int)o.voxel_bits);
+  return DSA_OK;
+}
 #undef ENC_RESERVED
 #undef ENC_REFUSE
 
@@ -1845,8 +1862,9 @@ static dsa_status encode_edgebreaker(dsa_context *ctx, uint32_t n, const dsa_mes
   rq.track_rows = w.track_rows == 1;
   return encode_checked(ctx, rq, grids, o.grid.repair.topology == 1, out);
 }
-static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_normal_mean_options &nm, dsa_encoded **out) {
-  if (enc_check_options(ctx, nm, !ctx || !out || (n && !meshes)) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_voxel_options &vx, dsa_encoded **out) {
+  if (enc_check_options(ctx, vx, !ctx || !out || (n && !meshes)) != DSA_OK) return DSA_ERR_INVALID_ARGUMENT;
+  const dsa_encode_normal_mean_options &nm = vx.normal_mean;
   const dsa_encode_vote_options &v = nm.vote;
   const dsa_encode_mean_options &a = v.mean;
   const dsa_encode_lod_options &l = a.lod;
@@ -1858,9 +1876,16 @@ static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh
   rq.n = n; rq.meshes = meshes; rq.sequential = true;
   rq.seq = o.sequential; rq.point_order = o.point_order == 1; rq.merge_points = m.merge_points == 1; rq.part_points = (uint32_t)s.part_points; rq.part_cells = (uint32_t)c.part_cells; rq.lod_base_bits = (uint32_t)l.lod_base_bits;
   rq.mean_attributes = a.mean_attributes; rq.vote_attributes = v.vote_attributes; rq.mean_normals = nm.mean_normals == 1;
+  rq.voxel_bits = (uint32_t)vx.voxel_bits; rq.voxel_point = (uint32_t)vx.voxel_point;
   const dsa_status st = encode_checked(ctx, rq, grids, false, out);
   if (st == DSA_OK && rq.lod()) (*out)->lod_bits = rq.lod_base_bits;
   return st;
+}
+static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_normal_mean_options &nm, dsa_encoded **out) {
+  dsa_encode_voxel_options vx;
+  dsa_encode_default_voxel_options(&vx);
+  vx.normal_mean = nm;
+  return encode_sequential(ctx, n, meshes, grids, vx, out);
 }
 static dsa_status encode_sequential(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_vote_options &v, dsa_encoded **out) {
   dsa_encode_normal_mean_options nm;
@@ -1983,6 +2008,11 @@ void dsa_encode_default_normal_mean_options(dsa_encode_normal_mean_options *o) {
   if (!o) return;
   memset(o, 0, sizeof(*o));
   dsa_encode_default_vote_options(&o->vote);
+}
+void dsa_encode_default_voxel_options(dsa_encode_voxel_options *o) {
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  dsa_encode_default_normal_mean_options(&o->normal_mean);
 }
 void dsa_encode_default_repair_options(dsa_encode_repair_options *o) {
   if (!o) return;
@@ -2128,6 +2158,12 @@ dsa_status dsa_encode_vote_sequential_batch(dsa_context *ctx, uint32_t n, const 
 // mean_normals = 0 is the very request of the call above, which arrives here.
 dsa_status dsa_encode_normal_mean_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_normal_mean_options *options, dsa_encoded **out) {
   DSA_GUARD(ctx, [&] { dsa_encode_normal_mean_options o; dsa_encode_default_normal_mean_options(&o); if (options) o = *options; return encode_sequential(ctx, n, meshes, grids, o, out); }());
+}
+// ... or, with voxel_bits >= 1, one point per cell of a grid coarser than the position grid: its first point, its centroid or the point
+// nearest its centre (a shift in the head predicate, the means pass, k_enc_voxel_*; dsa_encode_order.h); voxel_bits = 0 is the very
+// request of the call above, which arrives here.
+dsa_status dsa_encode_voxel_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids, const dsa_encode_voxel_options *options, dsa_encoded **out) {
+  DSA_GUARD(ctx, [&] { dsa_encode_voxel_options o; dsa_encode_default_voxel_options(&o); if (options) o = *options; return encode_sequential(ctx, n, meshes, grids, o, out); }());
 }
 
 struct dsa_welded {

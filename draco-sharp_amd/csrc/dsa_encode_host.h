@@ -1178,6 +1178,7 @@ struct MeshIn {
   const Grid *pos_grid = nullptr, *uv_grid = nullptr;              // the caller's quantisation grids (null: the attribute's own bounds)
   const int32_t *uv_portable = nullptr;                            // sequential streams: the integers `uvs` is coded as, in place of the quantiser's output (ExtraAttr::portable)
   const int32_t *normal_portable = nullptr;                        // ... and the octahedral codes (s, t) `normals` is coded as, nv rows of 2
+  const int32_t *pos_portable = nullptr;                           // ... and the integers `pos` is coded as, nv rows of 3 (voxel centroids)
 };
 
 // Why the extras of a mesh cannot be written ("" when they can): the attribute's index in the list and the field.
@@ -2048,7 +2049,7 @@ static void encode_sequential(const MeshIn &in, const Options &opt, bool mesh, b
   plan_sequential_attributes(in, opt, atts);
   for (auto &a : atts) {
     if (a.extra_values) fill_extra_values(a, in.nv, a);
-    else if (a.att_type == 0) quantize(in.pos, in.nv, 3, opt.pos_bits, a);
+    else if (a.att_type == 0) { quantize(in.pos, in.nv, 3, opt.pos_bits, a); if (in.pos_portable) a.vals.assign(in.pos_portable, in.pos_portable + (size_t)in.nv * 3); }
     else if (a.att_type == 1) {
       Octa o(opt.normal_bits);
       a.vals.resize((size_t)in.nv * 2);
@@ -2105,11 +2106,23 @@ static void point_order(const float *pos, uint32_t n, int bits, const Grid *grid
 }
 // One point per occupied cell of the position grid (dsa_encode_merged_sequential_batch, merge_points = 1; the device's kernels are
 // k_enc_merge_* of dsa_encode_order.h): with key and perm as above, entry e of the sorted order is a head iff e == 0 or
-// key[perm[e]] != key[perm[e - 1]]; kept lists perm[e] over the heads in sorted order (the sort is stable: the smallest row of
+// key[perm[e]] != key[perm[e - 1]]; kept lists perm[e] over the heads in sorted order (the sort is stable: with voxel_bits = 0 the smallest row of
 // every cell), row_entries[r] is the index in kept of the cell of row r.
-static void merge_points(const float *pos, uint32_t n, int bits, const Grid *grid, std::vector<uint32_t> &kept, std::vector<uint32_t> &row_entries) {
+static void merge_means(const int32_t *q, uint32_t n, int nc, const std::vector<uint32_t> &row_entries, uint32_t m, std::vector<int32_t> &means);
+// dsa_encode_voxel_sequential_batch, voxel_bits = C >= 1: the cell is key >> 3 s, s = bits - C (0: the position cell), and
+// voxel_point says which row of a voxel is kept and what its position is coded as -- 0: the voxel's first row in (key, row) order;
+// 1 (centroid): that row, its position integers the mean of the voxel's by the rule of merge_means; 2 (nearest): the row with the
+// smallest (dist, row), dist = the sum over c of (2 (q[r][c] & (2^s - 1)) - (2^s - 1))^2.  coded (where given): the integers the
+// position stream codes for every row, the quantiser's output with the centroids at the kept rows -- what the levels and the part
+// boxes read.  A serial pass over the voxels' rows; the device's kernels (the head predicate, k_enc_mean_*, k_enc_voxel_*) share
+// nothing with it.
+static void merge_points(const float *pos, uint32_t n, int bits, const Grid *grid, std::vector<uint32_t> &kept, std::vector<uint32_t> &row_entries,
+                         int voxel_bits = 0, int voxel_point = 0, std::vector<int32_t> *coded = nullptr) {
   check(bits >= 1 && bits <= 20, "quantisation bits out of range (positions/texcoords 1..20, normals 2..20)");
   check(pos != nullptr && n > 0, "positions are missing");
+  check(voxel_bits >= 0 && voxel_bits <= bits, "voxel_bits out of range (0, or 1 .. position bits)");
+  check(voxel_point >= 0 && voxel_point <= 2 && (voxel_point == 0 || voxel_bits >= 1), "voxel_point: 0 (first), 1 (centroid) or 2 (nearest), the latter two with voxel_bits >= 1");
+  const int s = voxel_bits ? bits - voxel_bits : 0;
   PortableAttr a;
   a.att_type = 0; a.nc = a.nc_out = 3; a.seq_type = 2; a.grid = grid;
   quantize(pos, n, 3, bits, a);
@@ -2120,9 +2133,26 @@ static void merge_points(const float *pos, uint32_t n, int bits, const Grid *gri
   std::stable_sort(perm.begin(), perm.end(), [&](uint32_t x, uint32_t y) { return key[x] < key[y]; });
   kept.clear(); row_entries.assign(n, 0);
   for (uint32_t e = 0; e < n; ++e) {
-    if (e == 0 || key[perm[e]] != key[perm[e - 1]]) kept.push_back(perm[e]);
+    if (e == 0 || (key[perm[e]] >> (3 * s)) != (key[perm[e - 1]] >> (3 * s))) kept.push_back(perm[e]);
     row_entries[perm[e]] = (uint32_t)kept.size() - 1u;
   }
+  const uint32_t m = (uint32_t)kept.size();
+  if (voxel_point == 2) {                                      // the row of every voxel with the smallest (dist, row): rows ascending, a strictly smaller dist wins
+    const int64_t span = ((int64_t)1 << s) - 1;
+    std::vector<uint64_t> best(m, ~0ull);
+    for (uint32_t r = 0; r < n; ++r) {
+      uint64_t dist = 0;
+      for (int c = 0; c < 3; ++c) { const int64_t d = 2 * (int64_t)((uint32_t)a.vals[(size_t)3 * r + c] & (uint32_t)span) - span; dist += (uint64_t)(d * d); }
+      const uint32_t j = row_entries[r];
+      if (dist < best[j]) { best[j] = dist; kept[j] = r; }
+    }
+  }
+  if (voxel_point == 1) {                                      // the mean of the voxel's position integers at the kept row
+    std::vector<int32_t> mean;
+    merge_means(a.vals.data(), n, 3, row_entries, m, mean);
+    for (uint32_t j = 0; j < m; ++j) for (int c = 0; c < 3; ++c) a.vals[(size_t)3 * kept[j] + c] = mean[(size_t)3 * j + c];
+  }
+  if (coded) coded->swap(a.vals);
 }
 // The mean of every cell in an attribute of the kept points (dsa_encode_mean_sequential_batch, a bit of mean_attributes; the device's
 // kernels are k_enc_mean_* of dsa_encode_order.h): q[n * nc] the integers the plain call codes for the rows -- the quantiser's output
@@ -2259,12 +2289,10 @@ static void part_boxes(const float *pos, uint32_t n, int bits, const Grid *grid,
 // device sizes them in k_enc_part_cells of dsa_encode_order.h): merge_points, then split_parts over the m kept entries in place of
 // the n rows, and per part and component the minimum and maximum of the position integers of rows kept[lo:hi], qmin / qmax[3 p + c].
 static void cell_parts(const float *pos, uint32_t n, int bits, const Grid *grid, uint32_t part_cells, std::vector<uint32_t> &kept, std::vector<uint32_t> &row_entries,
-                       std::vector<std::pair<uint32_t, uint32_t>> &ranges, std::vector<int32_t> &qmin, std::vector<int32_t> &qmax) {
-  merge_points(pos, n, bits, grid, kept, row_entries);
+                       std::vector<std::pair<uint32_t, uint32_t>> &ranges, std::vector<int32_t> &qmin, std::vector<int32_t> &qmax, int voxel_bits = 0, int voxel_point = 0) {
+  PortableAttr a;              // (vals: the integers the position stream codes, the voxels' centroids among them)
+  merge_points(pos, n, bits, grid, kept, row_entries, voxel_bits, voxel_point, &a.vals);
   split_parts((uint32_t)kept.size(), part_cells, ranges);
-  PortableAttr a;
-  a.att_type = 0; a.nc = a.nc_out = 3; a.seq_type = 2; a.grid = grid;
-  quantize(pos, n, 3, bits, a);
   qmin.assign(3 * ranges.size(), INT32_MAX); qmax.assign(3 * ranges.size(), INT32_MIN);
   for (size_t p = 0; p < ranges.size(); ++p)
     for (uint32_t e = ranges[p].first; e < ranges[p].second; ++e)
@@ -2280,15 +2308,15 @@ static void cell_parts(const float *pos, uint32_t n, int bits, const Grid *grid,
 // to its m_l points (an empty level has no part), ranges / levels / qmin / qmax say where every part lies in lod, which level it
 // belongs to and the box of its position integers.
 static void lod_parts(const float *pos, uint32_t n, int bits, const Grid *grid, uint32_t part_cells, int base_bits, std::vector<uint32_t> &lod, std::vector<uint32_t> &row_entries,
-                      std::vector<std::pair<uint32_t, uint32_t>> &ranges, std::vector<uint32_t> &levels, std::vector<int32_t> &qmin, std::vector<int32_t> &qmax) {
-  check(base_bits >= 1 && base_bits <= bits, "lod_base_bits out of range (1 .. position bits)");
+                      std::vector<std::pair<uint32_t, uint32_t>> &ranges, std::vector<uint32_t> &levels, std::vector<int32_t> &qmin, std::vector<int32_t> &qmax,
+                      int voxel_bits = 0, int voxel_point = 0) {
+  const int cell_bits = voxel_bits ? voxel_bits : bits;        // C: the kept points differ within their top C triples, L = C - D + 1
+  check(base_bits >= 1 && base_bits <= cell_bits, "lod_base_bits out of range (1 .. position bits, 1 .. voxel_bits with voxels)");
   check(part_cells >= 1, "lod_base_bits needs part_cells >= 1");
   std::vector<uint32_t> kept;
-  merge_points(pos, n, bits, grid, kept, row_entries);
-  PortableAttr a;
-  a.att_type = 0; a.nc = a.nc_out = 3; a.seq_type = 2; a.grid = grid;
-  quantize(pos, n, 3, bits, a);
-  const uint32_t m = (uint32_t)kept.size(), L = (uint32_t)(bits - base_bits + 1);
+  PortableAttr a;              // (vals: the integers the position stream codes, the voxels' centroids among them)
+  merge_points(pos, n, bits, grid, kept, row_entries, voxel_bits, voxel_point, &a.vals);
+  const uint32_t m = (uint32_t)kept.size(), L = (uint32_t)(cell_bits - base_bits + 1);
   std::vector<uint32_t> level(m, 0), count(L, 0), place(m, 0);
   for (uint32_t j = 1; j < m; ++j) {
     const uint64_t x = point_order_key(a.vals.data() + (size_t)3 * kept[j], bits), y = point_order_key(a.vals.data() + (size_t)3 * kept[j - 1], bits);

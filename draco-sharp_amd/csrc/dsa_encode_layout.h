@@ -248,9 +248,13 @@ struct EncRequest {
   uint32_t part_size() const { return cell_parts() ? part_cells : part_points; }      // N of either
   uint32_t lod_base_bits = 0;              // dsa_encode_lod_sequential_batch, lod_base_bits D >= 1 (with part_cells): the kept order by (level, kept), every level in parts
   bool lod() const { return cell_parts() && lod_base_bits >= 1; }
-  uint32_t lod_levels() const { return lod() ? (uint32_t)seq.base.position_bits - lod_base_bits + 1u : 1u; }      // L (D <= position_bits: enc_check_options)
+  uint32_t voxel_bits = 0, voxel_point = 0; // dsa_encode_voxel_sequential_batch (with merge_points): C >= 1: one point per cell of the grid with C bits per axis; DSA_VOXEL_POINT_*
+  uint32_t voxel_shift() const { return merged() && seq.geometry == 0 && voxel_bits >= 1 && voxel_bits < (uint32_t)seq.base.position_bits ? (uint32_t)seq.base.position_bits - voxel_bits : 0u; }      // s = B - C
+  bool centroids() const { return voxel_shift() != 0 && voxel_point == DSA_VOXEL_POINT_CENTROID; }      // (C = B: every rule keeps what the merge keeps, nothing more runs)
+  bool nearest() const { return voxel_shift() != 0 && voxel_point == DSA_VOXEL_POINT_NEAREST; }
+  uint32_t lod_levels() const { return lod() ? (uint32_t)seq.base.position_bits - voxel_shift() - lod_base_bits + 1u : 1u; }      // L = C - D + 1 (D <= C <= position_bits: enc_check_options)
   uint32_t mean_attributes = 0;            // dsa_encode_mean_sequential_batch (with merge_points): bit a: attribute a of the stream carries the mean of its cell (k_enc_mean_*)
-  bool means() const { return merged() && seq.geometry == 0 && mean_attributes != 0; }
+  bool means() const { return merged() && seq.geometry == 0 && (mean_attributes != 0 || centroids()); }      // (centroids: the positions are a stream of the means pass)
   uint32_t vote_attributes = 0;            // dsa_encode_vote_sequential_batch (with merge_points): bit a: attribute a of the stream carries the most frequent value of its cell (k_enc_vote_*)
   bool votes() const { return merged() && seq.geometry == 0 && vote_attributes != 0; }
   bool mean_normals = false;               // dsa_encode_normal_mean_sequential_batch (with merge_points): the normals of a cloud that has them carry the mean normal of the cell (k_enc_normal_*)
@@ -302,12 +306,12 @@ struct EncCellPass {
   std::vector<uint32_t> stream;             // stream[k]: the stream of the pass's record k
   uint64_t clouds_at = 0, records_at = 0;   // both among the uploads
   uint32_t most = 0;                        // the most chosen streams a cloud of the chunk has: the y of the kernels' grid
-  // the streams of a cloud of `na` attributes from stream s0 on that `mask` names (never the positions): record(stream) appends
-  // the typed record of each; then the cloud's own record
+  // the streams of a cloud of `na` attributes from stream s0 on that `mask` names (the positions only for the voxel rules, which
+  // pass lowest = 0): record(stream) appends the typed record of each; then the cloud's own record
   template <class Append>
-  void list(uint32_t mask, uint32_t s0, size_t na, Append &&record) {
+  void list(uint32_t mask, uint32_t s0, size_t na, Append &&record, uint32_t lowest = 1u) {
     dsa::EncCellStreams C{(uint32_t)stream.size(), 0u};
-    for (uint32_t k = 1; k < na && k < 32u; ++k) {
+    for (uint32_t k = lowest; k < na && k < 32u; ++k) {
       if (!((mask >> k) & 1u)) continue;
       record(s0 + k); stream.push_back(s0 + k);
       ++C.count;
@@ -358,8 +362,12 @@ struct EncLayout {
   // sums and counts, the votes' behind it tables, counts and values.  The vote records come back behind the stage: EncVote::full
   // (enc_vote_refusals).  EncRequest::normal_means: a third pass, a record per cloud that has normals, its range -- vector sums and
   // counts -- behind the votes'; a chunk without normals has no record, no range and no launch of it
-  EncCellPass mean_pass, vote_pass, normal_pass;
-  uint64_t mean_zero_at = 0, mean_zero_bytes = 0, vote_zero_at = 0, vote_zero_bytes = 0, normal_zero_at = 0, normal_zero_bytes = 0;
+  // EncRequest::nearest: a fourth pass, in front of the three (they write at the rows it picks), a record per cloud, its range -- the
+  // best distance and row of every voxel -- behind the normals'.  EncRequest::centroids: the positions are the first record of the
+  // means pass of every cloud, which then runs with mean_attributes = 0 too
+  EncCellPass mean_pass, vote_pass, normal_pass, near_pass;
+  uint64_t mean_zero_at = 0, mean_zero_bytes = 0, vote_zero_at = 0, vote_zero_bytes = 0, normal_zero_at = 0, normal_zero_bytes = 0, near_zero_at = 0, near_zero_bytes = 0;
+  std::vector<dsa::EncVoxel> voxels;
   std::vector<dsa::EncMean> means;
   std::vector<dsa::EncVote> votes;
   std::vector<dsa::EncNormal> normals;
@@ -388,6 +396,8 @@ static inline bool enc_order_stage(Launch &&launch, Zero &&zero, After &&after, 
   const dsa::EncMean *means = (const dsa::EncMean *)(arena + L.mean_pass.records_at);
   dsa::EncVote *votes = (dsa::EncVote *)(arena + L.vote_pass.records_at);
   const dsa::EncNormal *normals = (const dsa::EncNormal *)(arena + L.normal_pass.records_at);
+  const dsa::EncVoxel *voxels = (const dsa::EncVoxel *)(arena + L.near_pass.records_at);
+  const uint32_t nx = (uint32_t)L.voxels.size();
   // a cell pass: its range zeroed, kernels(the clouds' records, grid y), its lap
   auto cell_pass = [&](const EncCellPass &P, uint64_t zero_at, uint64_t zero_bytes, const char *lap, auto &&kernels) -> bool {
     if (P.stream.empty()) return true;
@@ -411,7 +421,15 @@ static inline bool enc_order_stage(Launch &&launch, Zero &&zero, After &&after, 
     launch(dsa::k_enc_merge_compact, nt, 1u, wave, arena, clouds, tiles, nt);
     if (!after("point merge")) return false;
   }
+  // voxel_point = nearest: kept[j] becomes the row of voxel j nearest its centre, in front of the three passes below, which write at kept[j]
+  if (!cell_pass(L.near_pass, L.near_zero_at, L.near_zero_bytes, "voxel nearest", [&](const dsa::EncCellStreams *xclouds, uint32_t most) {
+        launch(dsa::k_enc_voxel_near, nt, most, wave, arena, clouds, tiles, nt, xclouds, voxels, nx, 0u);
+        launch(dsa::k_enc_voxel_near, nt, most, wave, arena, clouds, tiles, nt, xclouds, voxels, nx, 1u);
+        launch(dsa::k_enc_voxel_pick, nt, most, 256u, arena, clouds, tiles, nt, xclouds, voxels, nx);
+      })) return false;
   // mean_attributes: the mean of the cell into vals at every kept row, in front of everything that reads vals or turns row_entries into lod order
+  // (voxel_point = centroid: the positions among them -- behind everything that reads the positions of other rows, the nearest pass, and
+  // in front of the levels and the boxes, which read keys and boxes from vals at the kept rows)
   if (!cell_pass(L.mean_pass, L.mean_zero_at, L.mean_zero_bytes, "cell means", [&](const dsa::EncCellStreams *mclouds, uint32_t most) {
         launch(dsa::k_enc_mean_sum, nt, most, wave, arena, clouds, tiles, nt, mclouds, means, nm);
         launch(dsa::k_enc_mean_store, nt, most, 256u, arena, clouds, tiles, nt, mclouds, means, nm);
@@ -1106,15 +1124,21 @@ static void enc_layout_sequential(EncChunk &ck) {
       dsa::EncOrder O;
       memset(&O, 0, sizeof(O));
       O.n = V; O.tiles = (V + ORD_TILE - 1u) / ORD_TILE; O.bits = (uint32_t)ck.opt.pos_bits; O.last = dsa::enc_order_passes(O.bits) & 1u;
-      if (merge) { O.merge = 1; O.stream0 = s0; O.streams = (uint32_t)atts.size(); }
+      if (merge) { O.merge = 1; O.stream0 = s0; O.streams = (uint32_t)atts.size(); O.voxel_shift = ck.rq.voxel_shift(); O.voxel_point = O.voxel_shift ? ck.rq.voxel_point : 0u; }
       if (merge || split) L.ord_of_mesh[i] = (uint32_t)L.ord.size();
       // the masked and the voted streams of the cloud (the first part's: the parts share its vals)
-      if (ck.rq.means()) L.mean_pass.list(ck.rq.mean_attributes, s0, atts.size(), [&](uint32_t s) {
+      // (centroids: the positions too, the cloud's first record -- the one that counts the rows of every voxel)
+      if (ck.rq.means()) L.mean_pass.list(ck.rq.mean_attributes | (ck.rq.centroids() ? 1u : 0u), s0, atts.size(), [&](uint32_t s) {
         dsa::EncMean M;
         memset(&M, 0, sizeof(M));
         M.nc = L.streams[s].nc;
         L.means.push_back(M);
-      });
+      }, ck.rq.centroids() ? 0u : 1u);
+      if (ck.rq.nearest()) L.near_pass.list(1u, s0, atts.size(), [&](uint32_t) {
+        dsa::EncVoxel X;
+        memset(&X, 0, sizeof(X));
+        L.voxels.push_back(X);
+      }, 0u);
       if (ck.rq.votes()) L.vote_pass.list(ck.rq.vote_attributes, s0, atts.size(), [&](uint32_t s) {
         dsa::EncVote X;
         memset(&X, 0, sizeof(X));
@@ -1163,6 +1187,7 @@ static void enc_layout_sequential(EncChunk &ck) {
   L.mean_pass.upload(L.means, A, L.uploads);
   L.vote_pass.upload(L.votes, A, L.uploads);
   L.normal_pass.upload(L.normals, A, L.uploads);
+  L.near_pass.upload(L.voxels, A, L.uploads);
   if (!L.parts.empty()) {
     L.parts_at = A.put(L.uploads, L.parts.data(), sizeof(dsa::EncPart) * L.parts.size(), false);
     L.part_tiles_at = A.put(L.uploads, L.part_tiles.data(), sizeof(dsa::EncPartTile) * L.part_tiles.size(), false);
@@ -1230,6 +1255,15 @@ static void enc_layout_sequential(EncChunk &ck) {
       const uint64_t V = L.ord[o].n;
       dsa::EncNormal &X = L.normals[C.first];
       X.vals = L.streams[L.normal_pass.stream[C.first]].vals; X.cnt = A.take(4ull * V); X.acc = A.take(24ull * V);
+    }
+  });
+  range(L.near_pass, L.near_zero_at, L.near_zero_bytes, [&] {      // behind the normals': the best distance and row of every voxel of every cloud
+    for (size_t o = 0; o < L.near_pass.clouds.size(); ++o) {
+      const dsa::EncCellStreams &C = L.near_pass.clouds[o];
+      if (C.count == 0) continue;
+      const uint64_t V = L.ord[o].n;
+      dsa::EncVoxel &X = L.voxels[C.first];
+      X.best_dist = A.take(8ull * V); X.best_row = A.take(4ull * V);
     }
   });
   L.total_bytes = A.cur;

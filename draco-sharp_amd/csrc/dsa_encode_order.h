@@ -30,7 +30,7 @@
 // Every cloud fits the same three steps a pass; a one-workgroup LDS sort for clouds of one tile was not built (DESIGN.md 7.3 has
 // what the crowded batch of small clouds costs).
 // The order of all steps of this file -- the sort, then the merge, the means, the votes, the mean normals, the levels, the part sizes and the part boxes where the
-// request has them -- is written down once, in enc_order_stage (dsa_encode_layout.h), which the product and every host check run.
+// request has them (merge, nearest pick, means with the centroids, votes, normals, levels, slot sizes, boxes) -- is written down once, in enc_order_stage (dsa_encode_layout.h), which the product and every host check run.
 // Which buffer of a pair a step reads follows from EncOrder::last alone (ord_sorted, ord_kept, ord_part_rows below).
 //
 // Wave64 throughout: the tile steps are blocks of one wave (__launch_bounds__(64)), so their barriers order LDS within a wave and
@@ -44,7 +44,7 @@
 // dsa_encode_merged_sequential_batch with merge_points = 1 (point clouds): one point per occupied cell of the position grid.  The
 // cell of a point is its key, and behind the sort the points of a cell are adjacent: entry e of the sorted order is a head iff
 // e == 0 or key[perm[e]] != key[perm[e - 1]]; kept lists perm[e] over the heads in sorted order, m of them (the sort is stable:
-// kept[j] is the smallest row of its cell), and row_entries[r] is the j whose cell row r lies in.  Three steps behind the last
+// kept[j] is the smallest row of its cell, with voxel_bits = 0), and row_entries[r] is the j whose cell row r lies in.  Three steps behind the last
 // scatter pass and in front of k_enc_gather, on the same (cloud, tile) list:
 //   k_enc_merge_heads     a wave per tile: head flags from the sorted keys (entry e0 of a tile reads key[e0 - 1] of the tile in
 //                         front: the sorted buffers are only read from here on), a ballot and a popcount per 64 entries, the
@@ -220,6 +220,45 @@
 // Not built: a vote over normals, weighted means, means per coarser lod cell, mean normals of meshes.
 // gfx950, hipcc -O3 (VGPR / SGPR / LDS bytes per block): k_enc_normal_sum 40 / 52 / 0 (the three 64-bit divisions are inline code, no
 // call), store 31 / 41 / 0; no scratch, no spills, 8 waves per SIMD.
+//
+// dsa_encode_voxel_sequential_batch with voxel_bits = C >= 1 (point clouds, merge_points = 1): one point per occupied cell of the grid
+// with C bits per axis, whatever B = position_bits >= C the positions are stored at.  With s = B - C (EncOrder::voxel_shift) the
+// voxel of a row is key >> 3 s -- the sort has put the rows of any coarser cell side by side -- and that is all the merge, the means,
+// the votes and the mean normals need to know: ord_head, the one head predicate of k_enc_merge_heads, k_enc_merge_compact,
+// k_enc_mean_sum, k_enc_vote_count and k_enc_normal_sum, compares key >> 3 s, and with s = 0 every one of them does what it did.
+// kept[j] is then the voxel's smallest (key, row), no longer its smallest row; cells[] and the vote table's hash and compare go by
+// the entry, so they follow.  The levels (ord_lod_levels, and through it k_enc_lod_*, k_enc_part_cells and the layout's slot count)
+// are L = C - D + 1: two kept points differ within their top C triples.  voxel_point (EncOrder::voxel_point) says which point a voxel
+// keeps:
+//   first      kept[j] as the merge leaves it.
+//   centroid   the positions are one more stream of the means pass -- the cloud's FIRST EncMean record {vals = O.vals, nc = 3}, so the
+//              one that counts the rows of every voxel, once -- and the pass runs for such a chunk with mean_attributes = 0 too.
+//              k_enc_mean_store writes floor((2 S + cnt) / (2 cnt)) into O.vals at kept[j], behind everything that reads the
+//              positions of other rows (k_enc_voxel_near: never in the same request) and in front of k_enc_lod_levels and
+//              k_enc_part_bounds, which read keys and boxes from vals at the kept rows.  A component's mean lies between its minimum
+//              and maximum over the voxel: the centroid lies in its voxel, the kept keys stay distinct and ascending.  No new kernel.
+//   nearest    a pass of its own behind the merge and in front of the three cell passes, which write at kept[j], on the merge's
+//              (cloud, tile) list; dist(r) = the sum over c of (2 (q[r][c] & (2^s - 1)) - (2^s - 1))^2 < 2^42, and the pair (dist,
+//              row) does not fit 64 bits, so two phases as k_enc_vote_best has them:
+//   k_enc_voxel_near      a wave per tile, 64 sorted entries a step: the head ballot, the run's first lane and the last lane of every
+//                         (run, step) as k_enc_mean_sum finds them; phase 0: ~dist per lane, a segmented inclusive MAXIMUM across the
+//                         wave (ord_wave_incl_max: ord_wave_incl's shape, max in place of +), the last lane of (run, step) raises
+//                         best_dist[j] by a 64-bit atomicMax -- the maximum of ~dist is the minimum of dist, and it starts from the
+//                         zero the one memset leaves; phase 1, a launch behind it: the lanes whose ~dist equals best_dist[j] stand
+//                         with ~row, the others with 0, the same segmented maximum, a 32-bit atomicMax into best_row[j].  A voxel of a
+//                         million rows costs one atomic a step, not one a row.  Maximum commutes: no atomic decides a value by arrival.
+//   k_enc_voxel_pick      a thread per kept entry, tiles over KEPT entries: kept[j] = ~best_row[j]
+// best_dist (u64[n]) and best_row (u32[n]) per cloud are regions of their own at the end of the arena, behind the normals', one range
+// that one memset on the stream zeroes in front of phase 0; no region is reused.  The records are EncVoxel and an EncCellStreams of the
+// pass's own per cloud, among the uploads; both kernels begin with ord_cell_block.  C = B is the merge as it stands under every rule:
+// the layout leaves s = 0 and runs nothing more.  The host coder's twin is synth::merge_points with voxel_bits and voxel_point (a
+// serial pass over the voxels' rows); tests/hostcheck/encvoxel_host.cpp runs the serial forms in the product's layout against it,
+// tests/test_gpu_encode_voxel.py the ballots, shuffles and atomics.
+// Not built: weighted centroids, the row nearest the centroid, a voxel edge that is not a power of two of the grid step, voxels of
+// meshes, reductions per coarser lod cell.
+// gfx950, hipcc -O3 (VGPR / SGPR / LDS bytes per block): k_enc_voxel_near 26 / 34 / 0, pick 6 / 25 / 0; with the shift k_enc_merge_heads
+// 12 / 27 / 0, compact 14 / 27 / 0, k_enc_mean_sum 25 / 45 / 0, k_enc_vote_count 28 / 52 / 0, k_enc_normal_sum 40 / 52 / 0,
+// k_enc_lod_levels 24 / 35 / 0, scan 22 / 37 / 0, k_enc_part_cells 44 / 23 / 0; no scratch, no spills, 8 waves per SIMD.
 #pragma once
 #include <stdint.h>
 
@@ -250,6 +289,8 @@ struct EncOrder {                  // one per cloud of the chunk; in the arena, 
   uint64_t lod_rows;               // u32[n] OUTPUT lod[m], the kept rows in (level, kept) order -- the e2v of the cloud's streams -- and behind it u32[n] pos[m],
                                    //   the place of every kept entry in lod: the key buffer the last sort pass did not write, key[last ^ 1]
   uint64_t lod_table;              // EncLodTable OUTPUT: points and first lod entry of every level
+  uint32_t voxel_shift, voxel_point;       // voxel_bits C >= 1: s = bits - C, the cell of the merge is key >> 3 s (0: the position cell, the merge as it was);
+                                   //   DSA_VOXEL_POINT_* (0 first, 1 centroid: a record of the means pass, 2 nearest: k_enc_voxel_*)
 };
 struct EncOrderTile { uint32_t cloud, tile; };
 struct EncPart {                   // one per part of a split cloud, the parts of a cloud side by side; in the arena, among the uploads
@@ -280,6 +321,10 @@ struct EncNormal {                 // mean_normals: one per cloud that has norma
   uint64_t cnt;                    // u32[n]: the rows of every cell, counted by this pass for itself (the means' count theirs)
   uint32_t bits, pad;              // normal_bits
 };
+struct EncVoxel {                  // voxel_point = nearest: one per cloud
+  uint64_t best_dist;              // u64[n]: the largest ~dist a row of voxel j has (zeroed in front of k_enc_voxel_near)
+  uint64_t best_row;               // u32[n]: the largest ~row among the rows of that distance
+};
 
 static inline uint32_t enc_order_passes(uint32_t bits) { return (3u * bits + 7u) / 8u; }
 
@@ -301,11 +346,17 @@ __device__ __forceinline__ bool ord_tile(const EncOrder &O, const EncOrderTile &
   end = limit - e0 < ORD_TILE ? limit : e0 + ORD_TILE;
   return true;
 }
-// entry e of a cloud's sorted keys begins a cell
-__device__ __forceinline__ bool ord_head(const uint64_t *key, uint32_t e) { return e == 0u || key[e] != key[e - 1u]; }
-// the levels of a cloud, L = bits - D + 1; 0: none (no lod_base_bits, or -- never by the layout -- one the table cannot hold)
+// entry e of a cloud's sorted keys begins a cell: the cell of an entry is its key without the low 3 s bits, s = O.voxel_shift (0: the key)
+__device__ __forceinline__ bool ord_head(const EncOrder &O, const uint64_t *key, uint32_t e) {
+  const uint32_t shift = O.voxel_shift < 20u ? 3u * O.voxel_shift : 0u;      // (s < bits <= 20 by the layout: the comparison keeps the shift below 64)
+  return e == 0u || (key[e] >> shift) != (key[e - 1u] >> shift);
+}
+// the bits per axis of the grid the merge keeps one point per cell of: C = bits - s
+__device__ __forceinline__ uint32_t ord_cell_bits(const EncOrder &O) { return O.voxel_shift < O.bits ? O.bits - O.voxel_shift : O.bits; }
+// the levels of a cloud, L = C - D + 1; 0: none (no lod_base_bits, or -- never by the layout -- one the table cannot hold)
 __device__ __forceinline__ uint32_t ord_lod_levels(const EncOrder &O) {
-  return O.lod_bits == 0u || O.lod_bits > O.bits || O.bits - O.lod_bits >= ORD_LOD_LEVELS ? 0u : O.bits - O.lod_bits + 1u;
+  const uint32_t C = ord_cell_bits(O);
+  return O.lod_bits == 0u || O.lod_bits > C || C - O.lod_bits >= ORD_LOD_LEVELS ? 0u : C - O.lod_bits + 1u;
 }
 #if defined(__HIPCC__)
 // the inclusive sum of x over the lanes of the wave from lane `start` up to this one (start 0: over all lanes below and this one)
@@ -481,13 +532,13 @@ __global__ __launch_bounds__(WAVE) void k_enc_merge_heads(uint8_t *arena, const 
 #if defined(__HIPCC__)
   for (uint32_t s0 = e0; s0 < end; s0 += WAVE) {               // (uniform: every lane takes every step)
     const uint32_t e = s0 + lane;
-    const bool head = e < end && ord_head(key, e);
+    const bool head = e < end && ord_head(O, key, e);
     heads += (uint32_t)__popcll(__ballot(head));
   }
   if (lane == 0) counts[T.tile] = heads;
 #else       // (as k_enc_order_hist: lane 0 counts)
   if (lane != 0) return;
-  for (uint32_t e = e0; e < end; ++e) heads += ord_head(key, e) ? 1u : 0u;
+  for (uint32_t e = e0; e < end; ++e) heads += ord_head(O, key, e) ? 1u : 0u;
   counts[T.tile] = heads;
 #endif
 }
@@ -536,7 +587,7 @@ __global__ __launch_bounds__(WAVE) void k_enc_merge_compact(uint8_t *arena, cons
   for (uint32_t s0 = e0; s0 < end; s0 += WAVE) {               // (uniform: every lane takes every step)
     const uint32_t e = s0 + lane;
     const bool valid = e < end;
-    const bool head = valid && ord_head(key, e);
+    const bool head = valid && ord_head(O, key, e);
     const unsigned long long heads = __ballot(head);
     const uint32_t at = next + (uint32_t)__popcll(heads & below);       // heads in front of this entry
     const uint32_t r = valid ? row[e] : 0u;
@@ -548,7 +599,7 @@ __global__ __launch_bounds__(WAVE) void k_enc_merge_compact(uint8_t *arena, cons
 #else       // (as k_enc_order_hist: lane 0 places the tile's entries in their order)
   if (lane != 0) return;
   for (uint32_t e = e0; e < end; ++e) {
-    if (ord_head(key, e)) kept[next++] = row[e];
+    if (ord_head(O, key, e)) kept[next++] = row[e];
     cells[row[e]] = next - 1u;
   }
 #endif
@@ -600,7 +651,7 @@ __global__ __launch_bounds__(WAVE) void k_enc_mean_sum(uint8_t *arena, const Enc
   for (uint32_t s0 = e0; s0 < end; s0 += WAVE) {               // (uniform: every lane takes every step)
     const uint32_t e = s0 + lane;
     const bool valid = e < end;
-    const bool head = valid && ord_head(key, e);
+    const bool head = valid && ord_head(O, key, e);
     const unsigned long long heads = __ballot(head), live = __ballot(valid);
     // the lane this lane's run begins at inside the step: the head at or below it, lane 0 for a run that came in from the step in front
     const unsigned long long mine = heads & upto;
@@ -711,7 +762,7 @@ __global__ __launch_bounds__(WAVE) void k_enc_vote_count(uint8_t *arena, const E
   for (uint32_t s0 = e0; s0 < end; s0 += WAVE) {               // (uniform: every lane takes every step)
     const uint32_t e = s0 + lane;
     const bool valid = e < end;
-    const bool head = valid && ord_head(key, e);
+    const bool head = valid && ord_head(O, key, e);
     const unsigned long long heads = __ballot(head);
     // the lanes of this lane's run inside the step: from the head at or below it (lane 0 for a run that came in from the step in
     // front) to below the next head above it
@@ -852,7 +903,7 @@ __global__ __launch_bounds__(WAVE) void k_enc_normal_sum(uint8_t *arena, const E
   for (uint32_t s0 = e0; s0 < end; s0 += WAVE) {               // (uniform: every lane takes every step)
     const uint32_t e = s0 + lane;
     const bool valid = e < end;
-    const bool head = valid && ord_head(key, e);
+    const bool head = valid && ord_head(O, key, e);
     const unsigned long long heads = __ballot(head), live = __ballot(valid);
     // the run of this lane inside the step and its last lane, as k_enc_mean_sum finds them
     const unsigned long long mine = heads & upto;
@@ -907,6 +958,92 @@ __global__ __launch_bounds__(256) void k_enc_normal_store(uint8_t *arena, const 
   }
 }
 
+// ---- voxel_point = DSA_VOXEL_POINT_NEAREST (the header comment has the contract): behind the merge, in front of the three passes above,
+// which write at kept[j].  The distance of a row from the centre of its voxel in doubled coordinates, from the low s bits of its
+// position integers: d_c = 2 (q_c & (2^s - 1)) - (2^s - 1), dist = d_0^2 + d_1^2 + d_2^2 < 3 2^40 (s <= 19).
+__device__ __forceinline__ uint64_t ord_voxel_dist(const int32_t *q, uint32_t s) {
+  const int64_t span = (int64_t)((1u << s) - 1u);
+  uint64_t dist = 0;
+  for (int c = 0; c < 3; ++c) { const int64_t d = 2 * (int64_t)((uint32_t)q[c] & (uint32_t)span) - span; dist += (uint64_t)(d * d); }
+  return dist;
+}
+#if defined(__HIPCC__)
+// the inclusive maximum of x over the lanes of the wave from lane `start` up to this one: ord_wave_incl with max in place of +
+__device__ __forceinline__ unsigned long long ord_wave_incl_max(unsigned long long x, uint32_t lane, uint32_t start) {
+  for (uint32_t d = 1; d < (uint32_t)WAVE; d <<= 1) { const unsigned long long y = __shfl_up(x, d, WAVE); if (lane >= start + d && y > x) x = y; }
+  return x;
+}
+#endif
+
+// grid = (the chunk's (cloud, tile) pairs, 1): one wave per tile of a cloud with nearest points, two launches.  phase 0: the largest
+// ~dist of every voxel; phase 1, a launch behind it: the largest ~row among the rows of that distance.
+__global__ __launch_bounds__(WAVE) void k_enc_voxel_near(uint8_t *arena, const EncOrder *clouds, const EncOrderTile *tiles, uint32_t nt,
+                                                         const EncCellStreams *xclouds, const EncVoxel *voxels, uint32_t nx, uint32_t phase) {
+  EncCellBlock B;
+  if (!ord_cell_block(B, clouds, tiles, nt, xclouds, nx, false)) return;
+  const EncOrder &O = *B.O;
+  const uint32_t e0 = B.e0, end = B.end;
+  const EncVoxel X = voxels[B.rec];
+  if (O.voxel_shift == 0u || O.voxel_shift >= 20u) return;     // (never by the layout)
+  const uint32_t *row = (const uint32_t *)(arena + ord_sorted(O).row);
+  const uint32_t *cells = (const uint32_t *)(arena + O.cells);
+  const int32_t *vals = (const int32_t *)(arena + O.vals);
+  unsigned long long *best_dist = (unsigned long long *)(arena + X.best_dist);
+  uint32_t *best_row = (uint32_t *)(arena + X.best_row);
+  const uint32_t lane = threadIdx.x;
+#if defined(__HIPCC__)
+  const uint64_t *key = (const uint64_t *)(arena + ord_sorted(O).key);
+  const unsigned long long upto = (2ull << lane) - 1ull;       // the lanes at or below this one
+  for (uint32_t s0 = e0; s0 < end; s0 += WAVE) {               // (uniform: every lane takes every step)
+    const uint32_t e = s0 + lane;
+    const bool valid = e < end;
+    const bool head = valid && ord_head(O, key, e);
+    const unsigned long long heads = __ballot(head), live = __ballot(valid);
+    // the run of this lane inside the step and its last lane, as k_enc_mean_sum finds them
+    const unsigned long long mine = heads & upto;
+    const uint32_t start = mine ? 63u - (uint32_t)__clzll((long long)mine) : 0u;
+    const unsigned long long above = (live >> lane) >> 1, head_above = (heads >> lane) >> 1;
+    const bool last = valid && ((above & 1ull) == 0ull || (head_above & 1ull) != 0ull);
+    const uint32_t r = valid ? row[e] : 0u;
+    const bool ok = valid && r < O.n;
+    const uint32_t j = ok ? cells[r] : 0xFFFFFFFFu;
+    const unsigned long long near = ok ? ~(unsigned long long)ord_voxel_dist(vals + 3ull * r, O.voxel_shift) : 0ull;       // (not 0: dist < 2^42)
+    if (phase == 0u) {
+      const unsigned long long x = ord_wave_incl_max(near, lane, start);
+      if (last && j < O.n && x > __hip_atomic_load(&best_dist[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&best_dist[j], x);
+    } else {
+      // (~row is not 0: r < n <= 2^28; a row farther than the voxel's nearest stands back with 0)
+      const unsigned long long mark = ok && j < O.n && near == best_dist[j] ? (unsigned long long)(~r) : 0ull;
+      const uint32_t x = (uint32_t)ord_wave_incl_max(mark, lane, start);
+      if (last && j < O.n && x > ord_peek(&best_row[j])) atomicMax(&best_row[j], x);
+    }
+  }
+#else       // (as k_enc_order_hist: lane 0 takes the tile's entries in their order)
+  if (lane != 0) return;
+  for (uint32_t e = e0; e < end; ++e) {
+    const uint32_t r = row[e], j = cells[r];
+    const unsigned long long near = ~(unsigned long long)ord_voxel_dist(vals + 3ull * r, O.voxel_shift);
+    if (phase == 0u) { if (near > best_dist[j]) best_dist[j] = near; }
+    else if (near == best_dist[j] && ~r > best_row[j]) best_row[j] = ~r;
+  }
+#endif
+}
+
+// grid as above, tiles over KEPT entries: a thread per kept entry.  No lane needs another: the host check runs it as it stands.
+__global__ __launch_bounds__(256) void k_enc_voxel_pick(uint8_t *arena, const EncOrder *clouds, const EncOrderTile *tiles, uint32_t nt,
+                                                        const EncCellStreams *xclouds, const EncVoxel *voxels, uint32_t nx) {
+  EncCellBlock B;
+  if (!ord_cell_block(B, clouds, tiles, nt, xclouds, nx, true)) return;
+  const EncOrder &O = *B.O;
+  const EncVoxel X = voxels[B.rec];
+  uint32_t *kept = (uint32_t *)(arena + ord_kept(O));
+  const uint32_t *best_row = (const uint32_t *)(arena + X.best_row);
+  for (uint32_t j = B.e0 + threadIdx.x; j < B.end; j += blockDim.x) {
+    const uint32_t r = ~best_row[j];
+    if (r < O.n) kept[j] = r;                                  // (always by the two phases: an untouched entry keeps the voxel's first row)
+  }
+}
+
 // ---- part_cells (the header comment has the contract): a thread per part slot of the chunk, behind k_enc_merge_scan and, for a
 // cloud with levels, behind k_enc_lod_scan and k_enc_lod_scatter.  The parts of level 0, then of level 1, ...: a cloud without
 // levels is one level of its m kept entries from 0 on (it has no table region: none is read for it).
@@ -937,14 +1074,14 @@ __global__ __launch_bounds__(WAVE) void k_enc_part_cells(uint8_t *arena, const E
 // ---- lod_base_bits (the header comment has the contract): behind the merge, in front of k_enc_part_cells
 // The level of a kept point from its key and the key of the kept point in front of it: c leading bit-triples in common out of
 // `bits`, level max(0, c + 1 - D).  (Equal keys never come here, the kept keys are distinct: the comparison keeps the level below L.)
-__device__ __forceinline__ uint32_t ord_lod_level(uint64_t a, uint64_t b, uint32_t bits, uint32_t base_bits) {
+__device__ __forceinline__ uint32_t ord_lod_level(uint64_t a, uint64_t b, uint32_t bits, uint32_t base_bits, uint32_t top) {
   const uint64_t x = a ^ b;
 #if defined(__HIPCC__)
   const uint32_t len = x ? 64u - (uint32_t)__clzll((long long)x) : 0u;
 #else
   const uint32_t len = x ? 64u - (uint32_t)__builtin_clzll(x) : 0u;
 #endif
-  const uint32_t triples = (len + 2u) / 3u, c = triples < bits ? bits - triples : 0u, top = bits - base_bits;
+  const uint32_t triples = (len + 2u) / 3u, c = triples < bits ? bits - triples : 0u;
   const uint32_t level = c + 1u > base_bits ? c + 1u - base_bits : 0u;
   return level < top ? level : top;
 }
@@ -969,7 +1106,7 @@ __global__ __launch_bounds__(WAVE) void k_enc_lod_levels(uint8_t *arena, const E
     uint32_t level = 0;
     if (valid && j != 0u) {
       const uint32_t r = kept[j], q = kept[j - 1u];
-      if (r < O.n && q < O.n) level = ord_lod_level(ord_key(vals + 3ull * r, O.bits), ord_key(vals + 3ull * q, O.bits), O.bits, O.lod_bits);
+      if (r < O.n && q < O.n) level = ord_lod_level(ord_key(vals + 3ull * r, O.bits), ord_key(vals + 3ull * q, O.bits), O.bits, O.lod_bits, levels - 1u);
     }
     if (valid) pos[j] = level;
     for (uint32_t l = 0; l < levels; ++l) {
@@ -982,7 +1119,7 @@ __global__ __launch_bounds__(WAVE) void k_enc_lod_levels(uint8_t *arena, const E
   if (lane != 0) return;
   for (uint32_t l = 0; l < levels; ++l) hist[(size_t)l * O.tiles + T.tile] = 0;
   for (uint32_t j = e0; j < end; ++j) {
-    const uint32_t level = j == 0u ? 0u : ord_lod_level(ord_key(vals + 3ull * kept[j], O.bits), ord_key(vals + 3ull * kept[j - 1u], O.bits), O.bits, O.lod_bits);
+    const uint32_t level = j == 0u ? 0u : ord_lod_level(ord_key(vals + 3ull * kept[j], O.bits), ord_key(vals + 3ull * kept[j - 1u], O.bits), O.bits, O.lod_bits, levels - 1u);
     pos[j] = level;
     hist[(size_t)level * O.tiles + T.tile] += 1u;
   }

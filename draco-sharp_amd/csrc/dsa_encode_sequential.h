@@ -21,6 +21,7 @@
 //                                of every level, in place of k_enc_part_cells; the host reads the level of every slot from its record
 //          k_enc_vote_*          dsa_encode_vote_sequential_batch, vote_attributes != 0: the most frequent tuple of the cell into the voted attributes' integers
 //          k_enc_normal_*        dsa_encode_normal_mean_sequential_batch, mean_normals = 1: the mean normal of the cell into the normals' octahedral codes
+//          k_enc_voxel_*         dsa_encode_voxel_sequential_batch, voxel_point = nearest: kept[j] the row of voxel j nearest its centre, in front of the cell passes
 //          k_enc_mean_*          dsa_encode_mean_sequential_batch, mean_attributes != 0: the mean of the cell into the masked attributes' integers
 //                                at every kept row, behind the merge; nothing of it comes back to the host
 //          k_enc_seq_indices     compressed indices: symbols and their statistics (dsa_encode_seqidx.h)

@@ -125,7 +125,15 @@ class Config:
     them carry, per kept point, the code of the normalised sum of the unit normals of the cell's rows -- by a rule in 64-bit integers
     on the octahedral codes (include/draco_mi355x.h), whatever the order of the rows; a cell of one row keeps its code.  A cloud
     without normals is coded as before; a bit of mean_attributes or vote_attributes on the normals stays refused.  part_cells,
-    lod_base_bits and the two masks compose with it; the handle is unchanged."""
+    lod_base_bits and the two masks compose with it; the handle is unchanged.
+
+    voxel_bits, voxel_point (dsa_encode_voxel_sequential_batch): voxel_bits = C >= 1: WITH merge_points=MERGE_CELLS one point per
+    occupied cell of the grid with C bits per axis is kept, whatever position_bits >= C the positions are stored at -- the voxel of a
+    point is the top 3 C bits of its Morton key.  voxel_point says which: VOXEL_POINT_FIRST the voxel's first row in (key, row)
+    order, VOXEL_POINT_CENTROID that row with its position coded as the exact integer mean of the voxel's quantised positions (ties
+    upwards), VOXEL_POINT_NEAREST the input row nearest the voxel's centre (ties to the smaller row), as it is.  mean_attributes,
+    vote_attributes and mean_normals reduce over the voxel; part_cells cuts the kept voxels; lod_base_bits = D needs D <= C and gives
+    C - D + 1 levels.  voxel_bits=0 (default) is the request without it; voxel_bits=position_bits keeps what merge_points keeps."""
 
     EDGEBREAKER_METHODS = (0, 2, -1)
     POSITION_PREDICTIONS = (0, 1)
@@ -136,12 +144,13 @@ class Config:
     TRAVERSAL_METHODS = (0, 1, 2)
     POINT_ORDERS = (native.POINT_ORDER_CALLER, native.POINT_ORDER_MORTON)
     MERGE_POINTS = (native.MERGE_NONE, native.MERGE_CELLS)
+    VOXEL_POINTS = (native.VOXEL_POINT_FIRST, native.VOXEL_POINT_CENTROID, native.VOXEL_POINT_NEAREST)
 
     def __init__(self, position_bits=11, texcoord_bits=10, normal_bits=8, speed=5, single_connectivity=False,
                  symbol_scheme=-1, position_prediction=1, texcoord_prediction=1, edgebreaker_method=0, normal_prediction=0,
                  encoding_method=1, compress_connectivity=False, multi_parallelogram=0, traversal_method=0, repair_topology=False, weld_points=False,
                  repair_seams=False, weld_attributes=False, track_rows=False, point_order=0, merge_points=0, part_points=0, part_cells=0,
-                 lod_base_bits=0, mean_attributes=0, vote_attributes=0, mean_normals=False):
+                 lod_base_bits=0, mean_attributes=0, vote_attributes=0, mean_normals=False, voxel_bits=0, voxel_point=0):
         for name, value, legal in (("encoding_method", encoding_method, self.ENCODING_METHODS),
                                    ("edgebreaker_method", edgebreaker_method, self.EDGEBREAKER_METHODS),
                                    ("position_prediction", position_prediction, self.POSITION_PREDICTIONS),
@@ -253,6 +262,20 @@ class Config:
             raise ValueError("mean_normals takes the mean normal over the points of a cell: it needs merge_points=MERGE_CELLS "
                              "(a sequential config with point_order=POINT_ORDER_MORTON)")
 
+        if isinstance(voxel_bits, bool) or not isinstance(voxel_bits, int) or not 0 <= voxel_bits <= self.position_bits:
+            raise ValueError("voxel_bits %r: 0 (no voxels) or the bits per axis of the voxel grid, 1 .. position_bits (%d)" % (voxel_bits, self.position_bits))
+        self.voxel_bits = voxel_bits
+        if voxel_point not in self.VOXEL_POINTS:
+            raise ValueError("voxel_point %r: one of VOXEL_POINT_FIRST, VOXEL_POINT_CENTROID, VOXEL_POINT_NEAREST %r" % (voxel_point, self.VOXEL_POINTS))
+        self.voxel_point = int(voxel_point)
+        if self.voxel_bits != 0 and self.merge_points != native.MERGE_CELLS:
+            raise ValueError("voxel_bits keeps one of the points of a voxel: it needs merge_points=MERGE_CELLS "
+                             "(a sequential config with point_order=POINT_ORDER_MORTON)")
+        if self.voxel_point != 0 and self.voxel_bits == 0:
+            raise ValueError("voxel_point %r needs voxel_bits >= 1: the centroid and the nearest point are those of a voxel" % (voxel_point,))
+        if self.voxel_bits != 0 and self.lod_base_bits > self.voxel_bits:
+            raise ValueError("lod_base_bits %d is above voxel_bits %d: level 0 cannot be finer than the voxel grid" % (self.lod_base_bits, self.voxel_bits))
+
     def _mean_mask(self, meshes):
         """mean_attributes as the mask of a call over `meshes`: "all" is every attribute but positions and normals, and needs clouds
         with the same attributes."""
@@ -291,6 +314,15 @@ class Config:
         else:
             o.vote.mean = self._native_mean(geometry, meshes)
         o.mean_normals = 1 if self.mean_normals else 0
+        return o
+
+    def _native_voxel(self, geometry, meshes):
+        """the options of dsa_encode_voxel_sequential_batch for a call over `meshes`"""
+        o = native.EncodeVoxelOptions()
+        native.lib().dsa_encode_default_voxel_options(C.byref(o))
+        o.normal_mean = self._native_normal_mean(geometry, meshes)
+        o.voxel_bits = self.voxel_bits
+        o.voxel_point = self.voxel_point
         return o
 
     @property
@@ -1015,6 +1047,7 @@ class DracoEncoder:
     # point, whether its handle has a slot per stream, so that n is read back from it).  A Config reaches the first whose option it
     # sets -- the widest call only when its option is set, and the plain case keeps arriving through the call it always took.
     _SEQUENTIAL_CALLS = (
+        ("voxel_bits", "_native_voxel", "dsa_encode_voxel_sequential_batch", True),
         ("mean_normals", "_native_normal_mean", "dsa_encode_normal_mean_sequential_batch", True),
         ("vote_attributes", "_native_vote", "dsa_encode_vote_sequential_batch", True),
         ("mean_attributes", "_native_mean", "dsa_encode_mean_sequential_batch", True),
@@ -1037,7 +1070,7 @@ class DracoEncoder:
                 if config._mean_mask(meshes) == 0:
                     continue
                 opt = config._native_mean(geometry, meshes)
-            elif option in ("vote_attributes", "mean_normals"):
+            elif option in ("vote_attributes", "mean_normals", "voxel_bits"):
                 opt = getattr(config, build)(geometry, meshes)
             else:
                 opt = getattr(config, build)(geometry)

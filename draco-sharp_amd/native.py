@@ -50,6 +50,7 @@ EXPORTS = [
     "dsa_encode_default_mean_options", "dsa_encode_mean_sequential_batch",
     "dsa_encode_default_vote_options", "dsa_encode_vote_sequential_batch",
     "dsa_encode_default_normal_mean_options", "dsa_encode_normal_mean_sequential_batch",
+    "dsa_encode_default_voxel_options", "dsa_encode_voxel_sequential_batch",
     "dsa_encoded_size", "dsa_encoded_stream", "dsa_encoded_free",
     "dsa_pool_create", "dsa_pool_destroy", "dsa_pool_size", "dsa_pool_last_error", "dsa_pool_decode", "dsa_pool_job_locate",
     "dsa_pool_job_chunks", "dsa_pool_job_free", "dsa_pool_plan",
@@ -152,6 +153,17 @@ class EncodeNormalMeanOptions(C.Structure):
     """dsa_encode_normal_mean_options: the options of dsa_encode_vote_sequential_batch, and mean_normals (with merge_points = 1: 1: the
     normals of every cloud that has them carry, per kept point, the mean normal of its cell by the integer rule of the header)."""
     _fields_ = [("vote", EncodeVoteOptions), ("mean_normals", C.c_uint32), ("reserved", C.c_int32 * 7)]
+
+
+# dsa_encode_voxel_options.voxel_point (DSA_VOXEL_POINT_*)
+VOXEL_POINT_FIRST, VOXEL_POINT_CENTROID, VOXEL_POINT_NEAREST = 0, 1, 2
+
+
+class EncodeVoxelOptions(C.Structure):
+    """dsa_encode_voxel_options: the options of dsa_encode_normal_mean_sequential_batch, voxel_bits (with merge_points = 1: C >= 1: one
+    point per occupied cell of the grid with C bits per axis, whatever position_bits the positions are stored at) and voxel_point
+    (VOXEL_POINT_*: the voxel's first row, that row at the voxel's mean position, or the row nearest the voxel's centre)."""
+    _fields_ = [("normal_mean", EncodeNormalMeanOptions), ("voxel_bits", C.c_int32), ("voxel_point", C.c_int32), ("reserved", C.c_int32 * 6)]
 
 
 class LodInfo(C.Structure):
@@ -482,6 +494,10 @@ def lib():
             L.dsa_encode_default_normal_mean_options.argtypes = [C.POINTER(EncodeNormalMeanOptions)]
             L.dsa_encode_default_normal_mean_options.restype = None
             L.dsa_encode_normal_mean_sequential_batch.argtypes = [vp, u32, C.POINTER(MeshAttrInput), C.POINTER(MeshGrids), C.POINTER(EncodeNormalMeanOptions), C.POINTER(vp)]
+        if hasattr(L, "dsa_encode_voxel_sequential_batch"):
+            L.dsa_encode_default_voxel_options.argtypes = [C.POINTER(EncodeVoxelOptions)]
+            L.dsa_encode_default_voxel_options.restype = None
+            L.dsa_encode_voxel_sequential_batch.argtypes = [vp, u32, C.POINTER(MeshAttrInput), C.POINTER(MeshGrids), C.POINTER(EncodeVoxelOptions), C.POINTER(vp)]
         L.dsa_encoded_size.restype = u32
         L.dsa_encoded_size.argtypes = [vp]
         L.dsa_encoded_stream.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(C.c_size_t)]

@@ -237,7 +237,7 @@ def lib():
                                         C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(ExtraInput), C.c_uint32,
                                         C.POINTER(GridsInput), C.POINTER(Options), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
         L.synth_encode_grid_portable.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ExtraInput), C.c_uint32, C.POINTER(GridsInput),
-                                                 C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(Options), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+                                                 C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(Options), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p]
         L.synth_quantized.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.POINTER(Grid), C.c_void_p]
         L.synth_merge_means.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]
         L.synth_merge_votes.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]
@@ -245,12 +245,13 @@ def lib():
         L.synth_quantized_normals.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]
         L.synth_point_order.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(Grid), C.c_void_p]
         L.synth_merge_points.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(Grid), C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]
+        L.synth_merge_voxels.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(Grid), C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p]
         L.synth_split_parts.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         L.synth_part_boxes.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(Grid), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.synth_cell_parts.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(Grid), C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p,
-                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_int, C.c_int]
         L.synth_lod_parts.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(Grid), C.c_uint32, C.c_int, C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p,
-                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_int, C.c_int]
         L.synth_shared_grid.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_uint32, C.c_int, C.POINTER(Grid)]
         L.synth_free.argtypes = [C.c_void_p]
         L.synth_make_mesh.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_uint32),
@@ -487,14 +488,15 @@ def encode_mesh_points(pos, faces, normals=None, uvs=None, generic=None, extra=N
 
 
 def encode_grid(pos, faces=None, normals=None, uvs=None, generic=None, extra=None, opt=None, form=1, normal_corners=None, uv_corners=None,
-                geometry=1, compressed=False, pos_grid=None, uv_grid=None, weld_attributes=False, uv_portable=None, normal_portable=None):
+                geometry=1, compressed=False, pos_grid=None, uv_grid=None, weld_attributes=False, uv_portable=None, normal_portable=None, pos_portable=None):
     """Any stream of this module with quantisation grids given by the caller: pos_grid / uv_grid / Extra.grid are Grids (grid(),
     shared_grid()) or None for the attribute's own bounds.  form 1: the arguments of encode_mesh_corners (Edgebreaker); form 0:
     of encode_sequential (geometry 1) / encode_point_cloud_attributes (geometry 0, faces None); form 2: of encode_mesh_points
     (one row per point).  Without a grid the bytes are those calls'.  What dsa_encode_grid_batch /
     dsa_encode_grid_sequential_batch must write.  uv_portable (N, 2) int32 / Extra.portable (form 0, point clouds): the integers
     coded for that quantised attribute in place of the quantiser's output, the header's bounds or grid as the floats give them;
-    normal_portable (N, 2) int32 likewise: the octahedral codes (s, t) coded for the normals."""
+    normal_portable (N, 2) int32 likewise: the octahedral codes (s, t) coded for the normals; pos_portable (N, 3) int32 likewise: the
+    integers coded for the positions (the voxel centroids of dsa_encode_voxel_sequential_batch)."""
     L = lib()
     pos, fc, nrm, uv, gen, extra, arr, opt = _points_args(pos, np.zeros((0, 3), np.uint32) if faces is None else faces, normals if normal_corners is None else None,
                                                           uvs if uv_corners is None else None, generic, extra, opt)
@@ -519,7 +521,7 @@ def encode_grid(pos, faces=None, normals=None, uvs=None, generic=None, extra=Non
     ec = _extra_corners(extra, len(fc))
     if normal_portable is not None and nrm is None:
         raise ValueError("normal_portable goes with normals")
-    if uv_portable is not None or normal_portable is not None or any(e.portable is not None for e in extra):
+    if uv_portable is not None or normal_portable is not None or pos_portable is not None or any(e.portable is not None for e in extra):
         if form != 0 or geometry != 0 or len(fc) or ec is not None:
             raise ValueError("portable integers go with a point cloud (form 0, geometry 0)")
         up = None if uv_portable is None else np.ascontiguousarray(uv_portable, np.int32).reshape(len(pos), 2)
@@ -528,8 +530,9 @@ def encode_grid(pos, faces=None, normals=None, uvs=None, generic=None, extra=Non
                 raise ValueError("extra attribute %d: portable holds one row of num_components integers per point" % k)
         ep = (C.c_void_p * max(1, len(extra)))(*[None if e.portable is None else e.portable.ctypes.data for e in extra])
         npt = None if normal_portable is None else np.ascontiguousarray(normal_portable, np.int32).reshape(len(pos), 2)
+        ppt = None if pos_portable is None else np.ascontiguousarray(pos_portable, np.int32).reshape(len(pos), 3)
         rc = L.synth_encode_grid_portable(ptr(pos), len(pos), ptr(nrm), ptr(uv), ptr(gen), arr, len(extra), C.byref(gi), ptr(npt), ptr(up), ep, C.byref(opt),
-                                          C.byref(out), C.byref(n))
+                                          C.byref(out), C.byref(n), ptr(ppt))
     elif ec is None and not weld_attributes:
         rc = L.synth_encode_grid(form, ptr(pos), len(pos), ptr(fc) if len(fc) else None, len(fc), ptr(nrm), 0 if nrm is None else len(nrm), ptr(nci),
                                  ptr(uv), 0 if uv is None else len(uv), ptr(uci), ptr(gen), geometry, 1 if compressed else 0, arr, len(extra),
@@ -584,11 +587,34 @@ def encode_ordered(pos, faces=None, normals=None, uvs=None, generic=None, extra=
     return data, perm
 
 
+VOXEL_POINT_FIRST, VOXEL_POINT_CENTROID, VOXEL_POINT_NEAREST = 0, 1, 2
+
+
+def merge_voxels(pos, bits, grid=None, voxel_bits=0, voxel_point=0):
+    """merge_points over the cells of the grid with voxel_bits = C bits per axis (0: the position cells): (kept, row_entries, coded).
+    The voxel of a row is its key without the low 3 (bits - C) bits; entry e of the sorted order is a head iff e == 0 or its voxel
+    differs from that of entry e - 1.  voxel_point 0: kept[j] the voxel's first row in (key, row) order; 1 (centroid): that row,
+    its position integers floor((2 S + cnt) / (2 cnt)) per component over the voxel's rows; 2 (nearest): the row with the smallest
+    (dist, row), dist the squared distance from the voxel's centre in doubled coordinates.  coded (N, 3) int32: the integers the
+    position stream codes for every row -- the quantiser's output, the centroids at the kept rows.  What
+    dsa_encode_voxel_sequential_batch keeps."""
+    L = lib()
+    pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+    kept = np.zeros(len(pos), np.uint32)
+    cells = np.zeros(len(pos), np.uint32)
+    coded = np.zeros((len(pos), 3), np.int32)
+    m = C.c_uint32()
+    if L.synth_merge_voxels(pos.ctypes.data, len(pos), int(bits), None if grid is None else C.byref(grid), int(voxel_bits), int(voxel_point), kept.ctypes.data,
+                            C.byref(m), cells.ctypes.data, coded.ctypes.data):
+        raise RuntimeError(_err())
+    return kept[:m.value].copy(), cells, coded
+
+
 def merge_points(pos, bits, grid=None):
     """One point per occupied cell of the position grid: (kept, row_entries) for the points `pos` (N, 3) at `bits` position bits,
     quantised as point_order quantises them.  With perm = point_order(pos, bits, grid) and key the interleaved bits, entry e is a
     head iff e == 0 or key[perm[e]] != key[perm[e - 1]]; kept (uint32, m) lists perm[e] over the heads in sorted order -- the
-    smallest row of every cell -- and row_entries (uint32, N) holds for every row the index in kept of its cell.  What
+    smallest row of every cell, with voxel_bits = 0 -- and row_entries (uint32, N) holds for every row the index in kept of its cell.  What
     dsa_encode_merged_sequential_batch with merge_points = 1 keeps."""
     L = lib()
     pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
@@ -683,16 +709,17 @@ def _extra_rows(e, rows, grid=None):
 
 
 def merged_arguments(pos, normals=None, uvs=None, generic=None, extra=None, opt=None, pos_grid=None, uv_grid=None, mean_attributes=0, vote_attributes=0,
-                     mean_normals=False):
+                     mean_normals=False, voxel_bits=0, voxel_point=0):
     """The arguments of the plain call that writes a merged stream: (kept, row_entries, kwargs for encode_grid(form=0, geometry=0))
     -- every per-point array at [kept], every quantised attribute on an explicit grid equal to the bounds of ALL its rows (the
     grid given, where one was).  mean_attributes: bit a: attribute a of the stream (0 positions, then normals, uvs, generic and the
     extras, those given) carries merge_means of its cell in place of row kept[j] -- an integer attribute as the mean array, a
     quantised one as portable integers (uv_portable / Extra.portable) on the unchanged grid.  vote_attributes: likewise, bit a:
     attribute a (of 1 or 2 components) carries merge_votes of its cell; the two masks share no bit.  mean_normals: the normals, where
-    given, carry merge_mean_normals of their cell as portable codes (normal_portable)."""
+    given, carry merge_mean_normals of their cell as portable codes (normal_portable).  voxel_bits / voxel_point: the cells are
+    merge_voxels' and kept its rows; the centroids go as portable integers (pos_portable) on the unchanged grid."""
     opt = opt or options()
-    kept, cells = merge_points(pos, opt.pos_bits, pos_grid)
+    kept, cells, coded = merge_voxels(pos, opt.pos_bits, pos_grid, voxel_bits, voxel_point)
     m = len(kept)
     index = 1 + (normals is not None)                       # the stream's attribute index of the next attribute
     if mean_attributes & 1 or (normals is not None and mean_attributes & 2):
@@ -746,16 +773,19 @@ def merged_arguments(pos, normals=None, uvs=None, generic=None, extra=None, opt=
         kw["uv_portable"] = uv_portable
     if mean_normals and normals is not None:
         kw["normal_portable"] = merge_mean_normals(quantized_normals(np.asarray(normals, np.float32).reshape(-1, 3), opt.normal_bits), opt.normal_bits, cells, m)
+    if voxel_point == VOXEL_POINT_CENTROID:
+        kw["pos_portable"] = np.ascontiguousarray(coded[kept])
     return kept, cells, kw
 
 
 def encode_merged(pos, normals=None, uvs=None, generic=None, extra=None, opt=None, pos_grid=None, uv_grid=None, mean_attributes=0, vote_attributes=0,
-                  mean_normals=False):
+                  mean_normals=False, voxel_bits=0, voxel_point=0):
     """encode_grid(form=0, geometry=0) of one point per occupied cell: (stream, kept, row_entries), merged_arguments coded.  What
     dsa_encode_merged_sequential_batch with merge_points = 1 must write, and the rows its handle must report; with mean_attributes
     what dsa_encode_mean_sequential_batch must, with vote_attributes what dsa_encode_vote_sequential_batch must, with mean_normals
-    what dsa_encode_normal_mean_sequential_batch must."""
-    kept, cells, kw = merged_arguments(pos, normals, uvs, generic, extra, opt, pos_grid, uv_grid, mean_attributes, vote_attributes, mean_normals)
+    what dsa_encode_normal_mean_sequential_batch must, with voxel_bits / voxel_point what dsa_encode_voxel_sequential_batch must."""
+    kept, cells, kw = merged_arguments(pos, normals, uvs, generic, extra, opt, pos_grid, uv_grid, mean_attributes, vote_attributes, mean_normals,
+                                       voxel_bits, voxel_point)
     p = kw.pop("pos")
     return encode_grid(p, None, form=0, geometry=0, **kw), kept, cells
 
@@ -828,7 +858,7 @@ def encode_split(pos, normals=None, uvs=None, generic=None, extra=None, opt=None
     return out
 
 
-def cell_parts(pos, bits, part_cells, grid=None):
+def cell_parts(pos, bits, part_cells, grid=None, voxel_bits=0, voxel_point=0):
     """(kept, row_entries, ranges, qmin, qmax) of the points `pos` (N, 3): kept / row_entries = merge_points(pos, bits, grid), ranges =
     split_parts(len(kept), part_cells) -- parts of the KEPT order -- and qmin / qmax (P, 3) int32 the minimum and maximum per
     component of the integers the position stream codes for rows kept[lo:hi]."""
@@ -837,12 +867,13 @@ def cell_parts(pos, bits, part_cells, grid=None):
     kept, cells = np.zeros(len(pos), np.uint32), np.zeros(len(pos), np.uint32)
     m, parts = C.c_uint32(), C.c_uint64()
     grid = None if grid is None else C.byref(grid)
-    if L.synth_cell_parts(pos.ctypes.data, len(pos), int(bits), grid, int(part_cells), kept.ctypes.data, C.byref(m), cells.ctypes.data, None, None, None, 0, C.byref(parts)):
+    if L.synth_cell_parts(pos.ctypes.data, len(pos), int(bits), grid, int(part_cells), kept.ctypes.data, C.byref(m), cells.ctypes.data, None, None, None, 0, C.byref(parts),
+                          int(voxel_bits), int(voxel_point)):
         raise RuntimeError(_err())
     ranges = np.zeros((parts.value, 2), np.uint32)
     qmin, qmax = np.zeros((parts.value, 3), np.int32), np.zeros((parts.value, 3), np.int32)
     if L.synth_cell_parts(pos.ctypes.data, len(pos), int(bits), grid, int(part_cells), kept.ctypes.data, C.byref(m), cells.ctypes.data, ranges.ctypes.data,
-                          qmin.ctypes.data, qmax.ctypes.data, len(ranges), C.byref(parts)):
+                          qmin.ctypes.data, qmax.ctypes.data, len(ranges), C.byref(parts), int(voxel_bits), int(voxel_point)):
         raise RuntimeError(_err())
     return kept[:m.value].copy(), cells, ranges, qmin, qmax
 
@@ -851,15 +882,15 @@ CellParts = collections.namedtuple("CellParts", "streams kept row_entries ranges
 
 
 def encode_cell_parts(pos, normals=None, uvs=None, generic=None, extra=None, opt=None, pos_grid=None, uv_grid=None, part_cells=0, mean_attributes=0, vote_attributes=0,
-                      mean_normals=False):
+                      mean_normals=False, voxel_bits=0, voxel_point=0):
     """One point per occupied cell, and the kept order in parts of at most part_cells points, each coded as a point cloud of its own
     on the cloud's grid: CellParts(streams, kept, row_entries, ranges, qmin, qmax) with merged_arguments' rows and grids -- every
     per-point array at [kept[lo:hi]], every quantised attribute on an explicit grid equal to the bounds of ALL input rows (the grid
     given, where one was).  What dsa_encode_cell_parts_sequential_batch with part_cells >= 1 must write, and what its handle must
     report."""
     opt = opt or options()
-    kept, cells, ranges, qmin, qmax = cell_parts(pos, opt.pos_bits, part_cells, pos_grid)
-    _, _, kw = merged_arguments(pos, normals, uvs, generic, extra, opt, pos_grid, uv_grid, mean_attributes, vote_attributes, mean_normals)
+    kept, cells, ranges, qmin, qmax = cell_parts(pos, opt.pos_bits, part_cells, pos_grid, voxel_bits, voxel_point)
+    _, _, kw = merged_arguments(pos, normals, uvs, generic, extra, opt, pos_grid, uv_grid, mean_attributes, vote_attributes, mean_normals, voxel_bits, voxel_point)
     p = kw.pop("pos")
     streams = []
     for lo, hi in ranges:
@@ -867,11 +898,11 @@ def encode_cell_parts(pos, normals=None, uvs=None, generic=None, extra=None, opt
         ex = [_extra_rows(e, slice(lo, hi)) for e in kw["extra"]]
         streams.append(encode_grid(take(p), None, normals=take(kw["normals"]), uvs=take(kw["uvs"]), generic=take(kw["generic"]), extra=ex, opt=opt,
                                    form=0, geometry=0, pos_grid=kw["pos_grid"], uv_grid=kw["uv_grid"], uv_portable=take(kw.get("uv_portable")),
-                                   normal_portable=take(kw.get("normal_portable"))))
+                                   normal_portable=take(kw.get("normal_portable")), pos_portable=take(kw.get("pos_portable"))))
     return CellParts(streams, kept, cells, ranges, qmin, qmax)
 
 
-def lod_parts(pos, bits, part_cells, lod_base_bits, grid=None):
+def lod_parts(pos, bits, part_cells, lod_base_bits, grid=None, voxel_bits=0, voxel_point=0):
     """(lod, row_entries, ranges, levels, qmin, qmax) of the points `pos` (N, 3): lod the kept rows of merge_points in ascending
     (level, position in kept) -- level(0) = 0, level(j) = max(0, c + 1 - lod_base_bits) with c the leading bit-triples the keys of
     kept[j] and kept[j - 1] share -- row_entries the lod entry of the cell of every row, ranges (P, 2) the parts of every level in
@@ -883,12 +914,12 @@ def lod_parts(pos, bits, part_cells, lod_base_bits, grid=None):
     m, parts = C.c_uint32(), C.c_uint64()
     grid = None if grid is None else C.byref(grid)
     if L.synth_lod_parts(pos.ctypes.data, len(pos), int(bits), grid, int(part_cells), int(lod_base_bits), lod.ctypes.data, C.byref(m), cells.ctypes.data,
-                         None, None, None, None, 0, C.byref(parts)):
+                         None, None, None, None, 0, C.byref(parts), int(voxel_bits), int(voxel_point)):
         raise RuntimeError(_err())
     ranges, levels = np.zeros((parts.value, 2), np.uint32), np.zeros(parts.value, np.uint32)
     qmin, qmax = np.zeros((parts.value, 3), np.int32), np.zeros((parts.value, 3), np.int32)
     if L.synth_lod_parts(pos.ctypes.data, len(pos), int(bits), grid, int(part_cells), int(lod_base_bits), lod.ctypes.data, C.byref(m), cells.ctypes.data,
-                         ranges.ctypes.data, levels.ctypes.data, qmin.ctypes.data, qmax.ctypes.data, len(ranges), C.byref(parts)):
+                         ranges.ctypes.data, levels.ctypes.data, qmin.ctypes.data, qmax.ctypes.data, len(ranges), C.byref(parts), int(voxel_bits), int(voxel_point)):
         raise RuntimeError(_err())
     return lod[:m.value].copy(), cells, ranges, levels, qmin, qmax
 
@@ -897,19 +928,19 @@ LodParts = collections.namedtuple("LodParts", "streams kept row_entries ranges q
 
 
 def encode_lod_parts(pos, normals=None, uvs=None, generic=None, extra=None, opt=None, pos_grid=None, uv_grid=None, part_cells=0, lod_base_bits=0,
-                     mean_attributes=0, vote_attributes=0, mean_normals=False):
+                     mean_attributes=0, vote_attributes=0, mean_normals=False, voxel_bits=0, voxel_point=0):
     """Additive levels of detail of the kept points, every level in parts of at most part_cells points, each part coded as a point
     cloud of its own on the cloud's grid: what encode_cell_parts returns with `kept` the rows in LOD order (ranges and row_entries
-    count in it), plus `level` per stream and `levels` = L = position bits - lod_base_bits + 1.  Every per-point array at
+    count in it), plus `level` per stream and `levels` = L = position bits (voxel_bits, where given) - lod_base_bits + 1.  Every per-point array at
     [lod[lo:hi]], every quantised attribute on an explicit grid equal to the bounds of ALL input rows (the grid given, where one
     was).  What dsa_encode_lod_sequential_batch with lod_base_bits >= 1 must write, and what its handle must report.
     lod_base_bits 0: encode_cell_parts, every stream of level 0 of 1."""
     opt = opt or options()
     if lod_base_bits == 0:
-        cp = encode_cell_parts(pos, normals, uvs, generic, extra, opt, pos_grid, uv_grid, part_cells, mean_attributes, vote_attributes, mean_normals)
+        cp = encode_cell_parts(pos, normals, uvs, generic, extra, opt, pos_grid, uv_grid, part_cells, mean_attributes, vote_attributes, mean_normals, voxel_bits, voxel_point)
         return LodParts(*cp, level=np.zeros(len(cp.streams), np.uint32), levels=1)
-    lod, cells, ranges, level, qmin, qmax = lod_parts(pos, opt.pos_bits, part_cells, lod_base_bits, pos_grid)
-    kept, _, kw = merged_arguments(pos, normals, uvs, generic, extra, opt, pos_grid, uv_grid, mean_attributes, vote_attributes, mean_normals)
+    lod, cells, ranges, level, qmin, qmax = lod_parts(pos, opt.pos_bits, part_cells, lod_base_bits, pos_grid, voxel_bits, voxel_point)
+    kept, _, kw = merged_arguments(pos, normals, uvs, generic, extra, opt, pos_grid, uv_grid, mean_attributes, vote_attributes, mean_normals, voxel_bits, voxel_point)
     at = np.zeros(int(kept.max()) + 1, np.int64)
     at[kept] = np.arange(len(kept))
     idx = at[lod]                                # where in kept (the order of merged_arguments' arrays) every lod entry lies
@@ -920,8 +951,8 @@ def encode_lod_parts(pos, normals=None, uvs=None, generic=None, extra=None, opt=
         ex = [_extra_rows(e, idx[lo:hi]) for e in kw["extra"]]
         streams.append(encode_grid(take(p), None, normals=take(kw["normals"]), uvs=take(kw["uvs"]), generic=take(kw["generic"]), extra=ex, opt=opt,
                                    form=0, geometry=0, pos_grid=kw["pos_grid"], uv_grid=kw["uv_grid"], uv_portable=take(kw.get("uv_portable")),
-                                   normal_portable=take(kw.get("normal_portable"))))
-    return LodParts(streams, lod, cells, ranges, qmin, qmax, level, opt.pos_bits - lod_base_bits + 1)
+                                   normal_portable=take(kw.get("normal_portable")), pos_portable=take(kw.get("pos_portable"))))
+    return LodParts(streams, lod, cells, ranges, qmin, qmax, level, (voxel_bits or opt.pos_bits) - lod_base_bits + 1)
 
 
 def entry_rows(pos, faces=None, normals=None, uvs=None, generic=None, extra=None, opt=None, form=1, normal_corners=None, uv_corners=None,

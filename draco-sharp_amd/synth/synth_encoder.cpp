@@ -405,7 +405,8 @@ static int encode_grid(int form, const float *pos, uint32_t nv, const uint32_t *
                        const synth_grids *grids, const synth_options *opt, int weld_attributes, uint8_t **out, size_t *out_len,
                        std::vector<std::vector<uint32_t>> *rows = nullptr,       // rows: the entry rows of the stream in place of its bytes (synth_entry_rows)
                        const int32_t *uv_portable = nullptr, const int32_t *const *extra_portable = nullptr,        // form 0: integers in place of the quantiser's output (synth_encode_grid_portable)
-                       const int32_t *normal_portable = nullptr) {                                                  // ... and octahedral codes in place of the normals'
+                       const int32_t *normal_portable = nullptr,                                                    // ... and octahedral codes in place of the normals'
+                       const int32_t *pos_portable = nullptr) {                                                     // ... and integers in place of the positions' (voxel centroids)
   try {
     synth::check(form >= 0 && form <= 2, "form: 0 (sequential), 1 (Edgebreaker) or 2 (one row per point)");
     std::vector<synth::ExtraAttr> ex, ex2;
@@ -416,7 +417,8 @@ static int encode_grid(int form, const float *pos, uint32_t nv, const uint32_t *
         ex[k].corners = extra_corners[k].corners; ex[k].rows = extra_corners[k].num_rows;
       }
     { const std::string why = synth::extras_error(in); synth::check(why.empty(), why.c_str()); }
-    synth::check(form == 0 || (!uv_portable && !extra_portable && !normal_portable), "portable integers go with a sequential stream (form 0)");
+    synth::check(form == 0 || (!uv_portable && !extra_portable && !normal_portable && !pos_portable), "portable integers go with a sequential stream (form 0)");
+    in.pos_portable = pos_portable;
     in.uv_portable = uvs ? uv_portable : nullptr;
     in.normal_portable = normals ? normal_portable : nullptr;
     for (uint32_t k = 0; k < num_extras && extra_portable; ++k) ex[k].portable = extra_portable[k];
@@ -479,12 +481,13 @@ int synth_encode_grid(int form, const float *pos, uint32_t nv, const uint32_t *f
 // synth_encode_grid, form 0, with integers given in place of the quantiser's output: normal_portable (nv rows of the octahedral code
 // (s, t), or NULL) for the normals, uv_portable (nv rows of 2, or NULL) for the texture coordinates, extra_portable (NULL, or
 // num_extras pointers, each NULL or nv rows of the attribute's components) for float32 attributes of the list.  Bounds, grids and
-// the stream's header are what the floats give; only the coded integers are replaced.
+// the stream's header are what the floats give; only the coded integers are replaced.  pos_portable (nv rows of 3, or NULL): likewise for
+// the positions (the centroids of dsa_encode_voxel_sequential_batch).
 int synth_encode_grid_portable(const float *pos, uint32_t nv, const float *normals, const float *uvs, const void *generic, const synth_extra *extras, uint32_t num_extras,
                                const synth_grids *grids, const int32_t *normal_portable, const int32_t *uv_portable, const int32_t *const *extra_portable, const synth_options *opt,
-                               uint8_t **out, size_t *out_len) {
+                               uint8_t **out, size_t *out_len, const int32_t *pos_portable) {
   return encode_grid(0, pos, nv, nullptr, 0, normals, normals ? nv : 0, nullptr, uvs, uvs ? nv : 0, nullptr, generic, 0, 0, extras, nullptr, num_extras, grids, opt, 0, out, out_len, nullptr,
-                     uv_portable, extra_portable, normal_portable);
+                     uv_portable, extra_portable, normal_portable, pos_portable);
 }
 // The octahedral codes (s, t) the coder quantises `n` normals to at `bits` bits (dsa_encode_host.h Octa::from_float_vector).
 int synth_quantized_normals(const float *normals, uint32_t n, int bits, int32_t *out) {
@@ -587,6 +590,20 @@ int synth_merge_points(const float *pos, uint32_t n, int bits, const synth::Grid
     return 0;
   } catch (const std::exception &e) { snprintf(g_err, sizeof(g_err), "%s", e.what()); return 1; }
 }
+// One point per occupied voxel (merge_points with voxel_bits / voxel_point): kept[*m] (room for n), row_entries[n], and where `coded`
+// is given the integers the position stream codes for every row, coded[3 n] (the centroids at the kept rows).
+int synth_merge_voxels(const float *pos, uint32_t n, int bits, const synth::Grid *grid, int voxel_bits, int voxel_point, uint32_t *kept, uint32_t *m, uint32_t *row_entries, int32_t *coded) {
+  try {
+    std::vector<uint32_t> k, c;
+    std::vector<int32_t> q;
+    synth::merge_points(pos, n, bits, grid, k, c, voxel_bits, voxel_point, &q);
+    memcpy(kept, k.data(), 4 * k.size());
+    memcpy(row_entries, c.data(), 4 * c.size());
+    if (coded) memcpy(coded, q.data(), 4 * q.size());
+    *m = (uint32_t)k.size();
+    return 0;
+  } catch (const std::exception &e) { snprintf(g_err, sizeof(g_err), "%s", e.what()); return 1; }
+}
 // The sorted order of n points in parts of at most part_points (dsa_encode_host.h split_parts): *parts of them, and where `ranges`
 // is given (room for 2 * capacity) lo and hi of every part.
 int synth_split_parts(uint32_t n, uint32_t part_points, uint32_t *ranges, uint64_t capacity, uint64_t *parts) {
@@ -615,14 +632,15 @@ int synth_part_boxes(const float *pos, uint32_t n, int bits, const synth::Grid *
   } catch (const std::exception &e) { snprintf(g_err, sizeof(g_err), "%s", e.what()); return 1; }
 }
 // The kept order of merge_points in parts of at most part_cells (cell_parts): kept[n] of which *m are set, row_entries[n], and where
-// `ranges` is given (room for 2 * capacity) lo and hi of the *parts parts with their boxes, qmin / qmax[3 * capacity].
+// `ranges` is given (room for 2 * capacity) lo and hi of the *parts parts with their boxes, qmin / qmax[3 * capacity].  voxel_bits /
+// voxel_point: as merge_points takes them (0, 0: the position cells).
 int synth_cell_parts(const float *pos, uint32_t n, int bits, const synth::Grid *grid, uint32_t part_cells, uint32_t *kept, uint32_t *m, uint32_t *row_entries,
-                     uint32_t *ranges, int32_t *qmin, int32_t *qmax, uint64_t capacity, uint64_t *parts) {
+                     uint32_t *ranges, int32_t *qmin, int32_t *qmax, uint64_t capacity, uint64_t *parts, int voxel_bits, int voxel_point) {
   try {
     std::vector<uint32_t> k, c;
     std::vector<std::pair<uint32_t, uint32_t>> r;
     std::vector<int32_t> mn, mx;
-    synth::cell_parts(pos, n, bits, grid, part_cells, k, c, r, mn, mx);
+    synth::cell_parts(pos, n, bits, grid, part_cells, k, c, r, mn, mx, voxel_bits, voxel_point);
     *m = (uint32_t)k.size(); *parts = r.size();
     memcpy(kept, k.data(), 4 * k.size());
     memcpy(row_entries, c.data(), 4 * c.size());
@@ -636,14 +654,14 @@ int synth_cell_parts(const float *pos, uint32_t n, int bits, const synth::Grid *
 }
 // The kept points by (level, kept) and every level in parts of at most part_cells (lod_parts): lod[n] of which *m are set,
 // row_entries[n], and where `ranges` is given (room for 2 * capacity) lo and hi of the *parts parts in lod order with their level
-// (levels[capacity]) and their boxes, qmin / qmax[3 * capacity].
+// (levels[capacity]) and their boxes, qmin / qmax[3 * capacity].  voxel_bits / voxel_point: as merge_points takes them (0, 0: the position cells).
 int synth_lod_parts(const float *pos, uint32_t n, int bits, const synth::Grid *grid, uint32_t part_cells, int base_bits, uint32_t *lod, uint32_t *m, uint32_t *row_entries,
-                    uint32_t *ranges, uint32_t *levels, int32_t *qmin, int32_t *qmax, uint64_t capacity, uint64_t *parts) {
+                    uint32_t *ranges, uint32_t *levels, int32_t *qmin, int32_t *qmax, uint64_t capacity, uint64_t *parts, int voxel_bits, int voxel_point) {
   try {
     std::vector<uint32_t> k, c, lv;
     std::vector<std::pair<uint32_t, uint32_t>> r;
     std::vector<int32_t> mn, mx;
-    synth::lod_parts(pos, n, bits, grid, part_cells, base_bits, k, c, r, lv, mn, mx);
+    synth::lod_parts(pos, n, bits, grid, part_cells, base_bits, k, c, r, lv, mn, mx, voxel_bits, voxel_point);
     *m = (uint32_t)k.size(); *parts = r.size();
     memcpy(lod, k.data(), 4 * k.size());
     memcpy(row_entries, c.data(), 4 * c.size());

@@ -711,7 +711,7 @@ dsa_status dsa_encode_ordered_sequential_batch(dsa_context *ctx, uint32_t n, con
  *   merge_points = 1 (taken only with point_order = 1 and geometry 0): with key(r) and perm (the rows in ascending (key, row)) as
  *   documented for point_order = 1, entry e of the sorted order is a head iff e == 0 or key[perm[e]] != key[perm[e - 1]]; kept is
  *   the list of perm[e] over the heads in sorted order, m = its length.  The sort is stable, so kept[j] is the smallest input row
- *   of its cell, and the result is a function of the input alone.  The cell IS the key, built from the low position_bits bits of
+ *   of its cell (with voxel_bits = 0: dsa_encode_voxel_sequential_batch below), and the result is a function of the input alone.  The cell IS the key (with voxel_bits = 0), built from the low position_bits bits of
  *   the quantised integers: two rows merge exactly when the plain ordered call would give them equal keys, and no other notion of
  *   equality is introduced.  A value on a grid that the call refuses today is still refused, with its own text.
  *   The stream codes m points; entry j of EVERY attribute carries row kept[j] of the caller's array for that attribute.  Bounds
@@ -896,7 +896,7 @@ typedef struct dsa_lod_info {
 dsa_status dsa_encoded_lod_info(const dsa_encoded *encoded, uint32_t stream, dsa_lod_info *out);
 /* dsa_encode_lod_sequential_batch with the mean of every cell in chosen attributes of its kept point: what a voxel-grid downsample
  * does to colour, intensity or a UV, on the device.  With merge_points = 1 alone entry j of every attribute carries row kept[j], the
- * smallest input row of the cell: for anything but the position that is the value of whichever point came first in the caller's
+ * smallest input row of the cell (with voxel_bits = 0): for anything but the position that is the value of whichever point came first in the caller's
  * rows.  Here the masked attributes carry the mean over all rows of the cell instead.
  *   mean_attributes: bit a set: attribute a of the STREAM (0 the positions, then normals, texture coordinates, the generic
  *   attribute and the listed attributes, those the cloud has) carries the cell's mean.  Taken only with merge_points = 1 (and so
@@ -1012,6 +1012,58 @@ typedef struct dsa_encode_normal_mean_options {
 void dsa_encode_default_normal_mean_options(dsa_encode_normal_mean_options *options);
 dsa_status dsa_encode_normal_mean_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids,
                                                    const dsa_encode_normal_mean_options *options, dsa_encoded **out);
+/* dsa_encode_normal_mean_sequential_batch with voxels coarser than the position grid: with voxel_bits = C >= 1 the merge keeps one
+ * point per occupied cell of the grid with C bits per axis, whatever position_bits = B >= C the positions are stored at, and
+ * voxel_point says which point.  What PCL VoxelGrid / Open3D voxel_down_sample (centroid) and PCL UniformSampling (nearest) do, with
+ * a voxel edge of 2^(B - C) steps of the position grid.
+ *   Voxel.  s = B - C; key(r), perm and q[r][c] exactly what point_order = 1 defines; voxel(r) = key(r) >> 3 s, the top 3 C bits of
+ *   the key.  Entry e of the sorted order is a head iff e == 0 or voxel(perm[e]) != voxel(perm[e - 1]); m is the number of heads,
+ *   first[j] = perm[e] of head j, row_entries[r] the j whose voxel row r lies in, R(j) the rows with row_entries[r] == j, cnt =
+ *   |R(j)|.  With s = 0 this is the merge as it stands.  first[j] is the voxel's smallest (key, row): with s > 0 it is NOT in
+ *   general the smallest input row of the voxel (a later row may lie in a finer cell that sorts first).
+ *   DSA_VOXEL_POINT_FIRST.  kept[j] = first[j]; every attribute carries that row, positions included.
+ *   DSA_VOXEL_POINT_CENTROID.  kept[j] = first[j]; component c of the position at entry j is coded as
+ *       P[j][c] = floor((2 S + cnt) / (2 cnt)),   S = the sum of q[r][c] over R(j),
+ *   the rule of mean_attributes: 64-bit arithmetic, ties upwards, a voxel of one row keeps its value.  Each component's mean lies
+ *   between its minimum and maximum over the voxel, so P[j] lies in voxel j: the kept keys stay distinct and ascending, and the
+ *   bounds, the grid and every refusal stay those of the call without the option.  P[j] may be a fine cell that no input row
+ *   occupies.
+ *   DSA_VOXEL_POINT_NEAREST.  In doubled coordinates d_c(r) = 2 (q[r][c] & (2^s - 1)) - (2^s - 1), dist(r) = d_0^2 + d_1^2 + d_2^2
+ *   (below 2^42, unsigned 64 bits); kept[j] is the row of R(j) with the smallest (dist, row).  Every attribute carries row kept[j],
+ *   positions included, and no value is changed.  A function of the SET of rows.
+ *   Composition.  mean_attributes, vote_attributes and mean_normals reduce over R(j) of the VOXEL and write at kept[j]; part_cells
+ *   cuts the m entries; part boxes are those of the integers the stream codes (CENTROID: of the centroids); row_entries,
+ *   cell_counts, entry_rows, part_info, source_rows and the join plan keep their meaning with "cell" read as "voxel".
+ *   Levels.  With lod_base_bits = D the levels are those of the lod rule on the kept keys, 1 <= D <= C and L = C - D + 1: two kept
+ *   points differ within their top C triples, so levels 0 .. l are one point per occupied cell of the grid with D + l bits.
+ *   dsa_lod_info.levels and cell_bits report L and D + level; the slot bound is ceil(n / N) + L - 1.
+ *   Equal streams.  Every stream is byte for byte what dsa_encode_grid_sequential_batch (geometry 0) writes for the m rows kept with
+ *   these settings: every quantised attribute on the grid equal to the bounds of all n rows, or on the grid given or shared; for
+ *   CENTROID the position integers P in place of the quantiser's output; the masked, voted and normal attributes as their calls
+ *   define them over the voxels.
+ *   voxel_bits = 0 with voxel_point = 0: the bytes, the messages, the work, the rows and the handle of
+ *   dsa_encode_normal_mean_sequential_batch.  voxel_bits = B with any voxel_point: the same streams and rows as well.
+ * Fails the call with DSA_ERR_INVALID_ARGUMENT before any mesh is looked at, dsa_last_error naming the field: voxel_bits below 0 or
+ * above position_bits; voxel_bits >= 1 without merge_points = 1; voxel_point outside {0, 1, 2}; voxel_point != 0 with voxel_bits =
+ * 0; lod_base_bits above voxel_bits when voxel_bits >= 1; a non-zero reserved word.  Refusals of the nested option structs keep
+ * their own words, and a mean_attributes or vote_attributes bit on the positions stays refused per cloud.
+ * On the device: a shift in the head predicate of the merge and of the cell passes; CENTROID makes the positions a stream of the
+ * means pass; NEAREST is a pass of its own in front of them (k_enc_voxel_near, k_enc_voxel_pick; dsa_encode_order.h).
+ * Not built: weighted centroids; the row nearest the centroid; a voxel edge that is not a power of two of the grid step; voxels of
+ * meshes; reductions per coarser lod cell.
+ * Added after ABI 4 without changing it: callers detect the feature by the symbol dsa_encode_voxel_sequential_batch. */
+#define DSA_VOXEL_POINT_FIRST    0         /* the voxel's first row in (key, row) order, its position as it is */
+#define DSA_VOXEL_POINT_CENTROID 1         /* that row, its position replaced by the voxel's mean position */
+#define DSA_VOXEL_POINT_NEAREST  2         /* the input row nearest the voxel's centre, as it is */
+typedef struct dsa_encode_voxel_options {
+  dsa_encode_normal_mean_options normal_mean; /* as for dsa_encode_normal_mean_sequential_batch, same legal values */
+  int32_t voxel_bits;                      /* 0 (default): the very request of the normal-mean call; C >= 1: one point per cell of the grid with C bits per axis */
+  int32_t voxel_point;                     /* DSA_VOXEL_POINT_* */
+  int32_t reserved[6];                     /* must be zero */
+} dsa_encode_voxel_options;
+void dsa_encode_default_voxel_options(dsa_encode_voxel_options *options);
+dsa_status dsa_encode_voxel_sequential_batch(dsa_context *ctx, uint32_t n, const dsa_mesh_attr_input *meshes, const dsa_mesh_grids *grids,
+                                             const dsa_encode_voxel_options *options, dsa_encoded **out);
 /* The rows of a decoded batch per POINT: for every mesh of `batch` and every attribute a of its stream,
  *     rows[a][p] = entry_rows[a][map[a][p]]          (map: the decoder's point -> entry map, dsa_batch_device_point_map)
  * -- which row of the arrays given to the encoder point p carries, gathered on the device (k_source_rows) so that neither the maps
