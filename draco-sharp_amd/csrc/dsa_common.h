@@ -15,7 +15,10 @@
 #define __host__
 #define __forceinline__ inline
 #include <string.h>
+#include <math.h>
 static inline float __uint_as_float(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
+static inline double __dsqrt_rn(double x) { return sqrt(x); }                            // both correctly rounded, as on the device
+static inline double __fma_rn(double a, double b, double c) { return fma(a, b, c); }
 #endif
 
 namespace dsa {
@@ -470,6 +473,30 @@ __device__ __forceinline__ int64_t div_trunc_pos(int64_t x, int64_t y) {
   if (r >= y) { ++q; r -= y; }
   if (r >= y) { ++q; r -= y; }
   return x < 0 ? -(int64_t)q : (int64_t)q;
+}
+// floor(sqrt(n)) for TexCoordsPortable (k_texcoords_prepare, dsa_seams.h): the double root, stepped to the floor
+__device__ __forceinline__ uint64_t isqrt_floor(uint64_t n) {   // = Core/MathUtilities.cs:5-25 IntSqrt (its Newton iteration ends on floor(sqrt(n)))
+  if (n == 0) return 0;
+  uint64_t r = (uint64_t)__dsqrt_rn((double)n);
+  if (r > 0xFFFFFFFFull) r = 0xFFFFFFFFull;
+  while (r * r > n) --r;
+  while (r < 0xFFFFFFFFull && (r + 1) * (r + 1) <= n) ++r;
+  return r;
+}
+// su / d truncated toward zero (the C# operator) for the chain: the quotient from a double multiplication with 1 / d, put right by
+// the remainder -- exact while d fits 32 bits and the quotient 31 (anything else takes the operator's long road)
+__device__ __attribute__((noinline)) int64_t tc_div_slow(int64_t x, int64_t y) { return x / y; }      // (one copy: the chain is unrolled twelve entries deep)
+__device__ __forceinline__ int32_t tc_div(int64_t su, int64_t d, double inv, bool d_small) {
+  const double sd = __fma_rn((double)(int32_t)(su >> 32), 4294967296.0, (double)(uint32_t)su);      // exact below 2^53
+  const double qe = sd * inv;
+  if (!d_small || !(qe > -2147483000.0 && qe < 2147483000.0) || !(sd > -4.0e15 && sd < 4.0e15)) return (int32_t)tc_div_slow(su, d);
+  // toward zero; off by one at most: sd is exact, `inv` and the product carry one rounding each (2^-53 relative), the quotient is
+  // below 2^31 -- the estimate is within 2^-20 of the true quotient, so its truncation is the true one or its neighbour
+  int32_t q = (int32_t)qe;
+  const int64_t r = su - (int64_t)q * d;
+  if (su >= 0) q += r < 0 ? -1 : (r >= d ? 1 : 0);
+  else q += r > 0 ? 1 : (r <= -d ? -1 : 0);
+  return q;
 }
 // GeometricNormal, from the summed face normals n around the vertex to the value (MeshPredictionSchemeGeometricNormalPredictorArea.cs:43-63,
 // MeshPredictionSchemeGeometricNormalDecoder.cs:56-69, OctahedronToolBox.cs:28-77,121-137 with the bitstream's 64-bit arithmetic,

@@ -506,14 +506,6 @@ __global__ __launch_bounds__(256) void k_seam_maps(uint8_t *arena, const MeshLay
 //                            instruction stream is shared): per entry two multiply-adds, two divisions by an estimate put
 //                            right by remainders, the wrap transform
 // =========================================================================
-__device__ __forceinline__ uint64_t isqrt_floor(uint64_t n) {   // = Core/MathUtilities.cs:5-25 IntSqrt (its Newton iteration ends on floor(sqrt(n)))
-  if (n == 0) return 0;
-  uint64_t r = (uint64_t)__dsqrt_rn((double)n);
-  if (r > 0xFFFFFFFFull) r = 0xFFFFFFFFull;
-  while (r * r > n) --r;
-  while (r < 0xFFFFFFFFull && (r + 1) * (r + 1) <= n) ++r;
-  return r;
-}
 __device__ __forceinline__ int64_t div_trunc(int64_t x, int64_t y) { return y > 0 ? div_trunc_pos(x, y) : x / y; }
 
 // The orientation bits as the decoder will use them (:66-85: a bit says "same as the one before", starting from true).
@@ -618,21 +610,7 @@ __global__ __launch_bounds__(256) void k_texcoords_prepare(uint8_t *arena, const
 // (an entry of group g or g + 1 itself: the usual case for one of the two, the strip's previous entry) comes from a register window
 // of the last 2 TC_G results instead.
 #define TC_G 4
-// su / d truncated toward zero (the C# operator) for the chain: the quotient from a double multiplication with 1 / d, put right by
-// the remainder -- exact while d fits 32 bits and the quotient 31 (anything else takes the operator's long road)
-__device__ __noinline__ int64_t tc_div_slow(int64_t x, int64_t y) { return x / y; }      // (one copy: the chain is unrolled twelve entries deep)
-__device__ __forceinline__ int32_t tc_div(int64_t su, int64_t d, double inv, bool d_small) {
-  const double sd = __fma_rn((double)(int32_t)(su >> 32), 4294967296.0, (double)(uint32_t)su);      // exact below 2^53
-  const double qe = sd * inv;
-  if (!d_small || !(qe > -2147483000.0 && qe < 2147483000.0) || !(sd > -4.0e15 && sd < 4.0e15)) return (int32_t)tc_div_slow(su, d);
-  // toward zero; off by one at most: sd is exact, `inv` and the product carry one rounding each (2^-53 relative), the quotient is
-  // below 2^31 -- the estimate is within 2^-20 of the true quotient, so its truncation is the true one or its neighbour
-  int32_t q = (int32_t)qe;
-  const int64_t r = su - (int64_t)q * d;
-  if (su >= 0) q += r < 0 ? -1 : (r >= d ? 1 : 0);
-  else q += r > 0 ? 1 : (r <= -d ? -1 : 0);
-  return q;
-}
+// (tc_div, the chain's division, stands beside div_trunc_pos in dsa_common.h, where the host checks reach it)
 // The loop body has no memory load inside a branch: every request is issued in straight-line code, so that the waits the compiler
 // places count exactly the younger requests (vmcnt is one in-order counter) instead of draining everything that is in flight.
 #define TC_DEPTH 3        // groups of records in flight

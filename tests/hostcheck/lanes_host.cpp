@@ -127,7 +127,83 @@ static int divcheck(uint64_t seed, long count) {
   return 0;
 }
 
+// lanes_host isqrtcheck <seed> <count>: isqrt_floor (the root of TexCoordsPortable: a double root stepped to the floor, clamped at
+// 2^32 - 1) against the definition r * r <= n < (r + 1) * (r + 1) in 128 bits: 0, 1, 2^64 - 1, the neighbours k * k - 1, k * k,
+// k * k + 1 of the squares around 2^16, 2^26 (where a double stops telling them apart) and 2^32 - 1, and <count> random arguments of
+// every magnitude, half of them neighbours of random squares
+static int isqrtcheck(uint64_t seed, long count) {
+  typedef unsigned __int128 u128;
+  rng_state = seed * 2654435761ull + 88172645463325252ull;
+  auto r64 = []() { return ((uint64_t)rnd() << 42) ^ ((uint64_t)rnd() << 21) ^ rnd(); };
+  long n_checked = 0;
+  auto check = [&](uint64_t n) {
+    const uint64_t r = dsa::isqrt_floor(n);
+    ++n_checked;
+    if (r > 0xFFFFFFFFull || (u128)r * r > (u128)n || (u128)(r + 1) * (r + 1) <= (u128)n) { fprintf(stderr, "isqrtcheck: %llu: %llu\n", (unsigned long long)n, (unsigned long long)r); return false; }
+    return true;
+  };
+  auto around = [&](uint64_t k) { return (k == 0 || check(k * k - 1)) && check(k * k) && (k * k == ~(uint64_t)0 || check(k * k + 1)); };
+  if (!check(0) || !check(1) || !check(~(uint64_t)0)) return 1;
+  const uint64_t centres[3] = {(uint64_t)1 << 16, (uint64_t)1 << 26, 0xFFFFFFFFull};
+  for (uint64_t c : centres)
+    for (uint64_t k = c - 300; k <= c + 300 && k <= 0xFFFFFFFFull; ++k)
+      if (!around(k)) return 1;
+  for (long it = 0; it < count; ++it) {
+    const int bits = 1 + (int)(rnd() % 64);
+    const uint64_t x = r64() >> (64 - bits);
+    if (it & 1) { if (!around(x >> (bits > 32 ? bits - 32 : 0))) return 1; }
+    else if (!check(x)) return 1;
+  }
+  printf("isqrtcheck: %ld roots equal\n", n_checked);
+  return 0;
+}
+
+// lanes_host tcdivcheck <seed> <count>: tc_div (the division of k_texcoords: a double product with 1 / d put right by the remainder
+// while d fits 32 bits, the dividend stays below 4e15 and the quotient fits 31 bits, the operator otherwise) against the low 32 bits
+// of the 128-bit quotient truncated toward zero, called as the kernel calls it (inv from the low word of d, d_small from d): divisors
+// 1, 2, 3, around 2^16, 2^31, at 2^32 - 1, 2^32, 2^32 + 1 and up to 3 * 2^40, dividends at +-4e15, at +-(2^31 d), next to multiples
+// of d and of every magnitude, both signs
+static int tcdivcheck(uint64_t seed, long count) {
+  typedef __int128 i128;
+  rng_state = seed * 2654435761ull + 88172645463325252ull;
+  auto r64 = []() { return ((uint64_t)rnd() << 42) ^ ((uint64_t)rnd() << 21) ^ rnd(); };
+  long n_checked = 0, n_fast = 0;
+  auto check = [&](int64_t su, int64_t d) {
+    const bool d_small = d > 0 && d < (int64_t)0x100000000ll;
+    const double inv = 1.0 / (double)(uint32_t)d;
+    const int32_t got = dsa::tc_div(su, d, inv, d_small), want = (int32_t)(uint32_t)(uint64_t)((i128)su / (i128)d);
+    ++n_checked;
+    const double qe = (double)su * inv;
+    if (d_small && qe > -2147483000.0 && qe < 2147483000.0 && su > -4000000000000000ll && su < 4000000000000000ll) ++n_fast;
+    if (got != want) { fprintf(stderr, "tcdivcheck: %lld / %lld: %d vs %d\n", (long long)su, (long long)d, got, want); return false; }
+    return true;
+  };
+  const int64_t fixed[] = {1, 2, 3, 7, 65535, 65536, 65537, 0x7FFFFFFFll, 0x80000000ll, 0x80000001ll, 0xFFFFFFFEll, 0xFFFFFFFFll, 0x100000000ll, 0x100000001ll,
+                           0x1FFFFFFFFll, 0x200000000ll, 3ll << 40, (3ll << 40) - 1};
+  const int64_t edge = 4000000000000000ll;
+  for (int64_t d : fixed)
+    for (int sign = -1; sign <= 1; sign += 2)
+      for (int64_t off = -3; off <= 3; ++off) {
+        if (!check(sign * (edge + off), d) || !check(sign * (edge / d * d + off), d)) return 1;
+        if (d <= (3ll << 40) / 2 && (!check(sign * (d * 0x80000000ll + off), d) || !check(sign * (d * 2147483000ll + off), d) || !check(sign * (d * 0x7FFFFFFFll + off * d + off), d))) return 1;
+        if (!check(sign * off, d) || !check(sign * (d + off), d) || !check(sign * (d * 1000003ll + off), d)) return 1;
+      }
+  for (long it = 0; it < count; ++it) {
+    const int bd = 1 + (int)(rnd() % 42), bs = 1 + (int)(rnd() % 62);
+    int64_t d = it % 7 == 0 ? fixed[rnd() % (sizeof(fixed) / sizeof(fixed[0]))] : (int64_t)(r64() >> (64 - bd));
+    if (d <= 0) d = 1 + (int64_t)(rnd() % 5);
+    int64_t su = (int64_t)(r64() >> (64 - bs));
+    if (it % 3 == 0) { const int64_t k = (int64_t)(rnd() % 0x7FFFFFFFu); if (k < ((int64_t)1 << 62) / d) su = k * d + ((int64_t)(rnd() % 3) - 1); }
+    if (rnd() & 1) su = -su;
+    if (!check(su, d)) return 1;
+  }
+  printf("tcdivcheck: %ld divisions equal, %ld by the estimate\n", n_checked, n_fast);
+  return 0;
+}
+
 int main(int argc, char **argv) {
+  if (argc >= 4 && strcmp(argv[1], "isqrtcheck") == 0) return isqrtcheck(strtoull(argv[2], nullptr, 10), atol(argv[3]));
+  if (argc >= 4 && strcmp(argv[1], "tcdivcheck") == 0) return tcdivcheck(strtoull(argv[2], nullptr, 10), atol(argv[3]));
   if (argc >= 4 && strcmp(argv[1], "divcheck") == 0) return divcheck(strtoull(argv[2], nullptr, 10), atol(argv[3]));
   if (argc >= 3 && strcmp(argv[1], "octexhaust") == 0) return octexhaust(atoi(argv[2]));
   if (argc >= 4 && strcmp(argv[1], "octcheck") == 0) return octcheck(strtoull(argv[2], nullptr, 10), atoi(argv[3]));

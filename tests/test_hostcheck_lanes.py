@@ -158,3 +158,23 @@ def test_division_through_a_double_estimate_is_exact(exe):
     magnitude, a fifth of them next to exact multiples."""
     r = subprocess.run([exe, "divcheck", "5", "2000000"], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr[-2000:]
+
+
+def test_integer_square_root_is_the_floor_root(exe):
+    """isqrt_floor (dsa_common.h): the root of TexCoordsPortable on the device, a double-precision root stepped to the floor -- against
+    the definition in 128-bit arithmetic on 0, 1, 2^64 - 1, the neighbours of the squares around 2^16, 2^26 and 2^32 - 1 (the clamp) and
+    a million random arguments, half of them neighbours of squares.  The designs of tests/predictcases.py hand it wrapped products, which
+    are next to a square only by accident; the step DOWN from a double root that rounded up is reached here alone."""
+    r = subprocess.run([exe, "isqrtcheck", "7", "1000000"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr[-2000:]
+    assert "roots equal" in r.stdout
+
+
+def test_texture_coordinate_division_is_exact(exe):
+    """tc_div (dsa_common.h): k_texcoords' division by a double estimate, with its three ways out to the operator (divisor beyond 32 bits,
+    dividend beyond 4e15, quotient beyond 31 bits) -- against the 128-bit quotient at every one of those borders, both signs, and on two
+    million random pairs; at least a third of them must have taken the estimate."""
+    r = subprocess.run([exe, "tcdivcheck", "9", "2000000"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr[-2000:]
+    checked, fast = [int(w) for w in r.stdout.replace(",", "").split() if w.isdigit()]
+    assert checked > 2000000 and fast * 3 >= checked, r.stdout
